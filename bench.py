@@ -10,7 +10,7 @@ several concurrent SST builders of a compaction / flush (config.rs:1081, 1383-13
 job goes to rank j mod N (slatedb_amd/job.py); ranks share nothing, the only RCCL calls are the
 timing barrier and the max / sum of scalars.  `--job-ssts 64` runs configs[4] as a fixed job (strong
 scaling); `--batch 1` is the single-SST configs[1] shape.  The single-SST latency (sdb_encode_sst,
-one SST per launch sequence) is reported beside the headline as `single_sst`.
+one SST per launch sequence) is reported beside the headline as `single_sst` (with `--full`).
 
 `--streams S` (default 2) allows S such builders per GPU concurrently, each on its own HIP stream with its
 own workspace and outputs (step i on stream i mod S), after sdb_set_concurrent_builders(S): each builder's
@@ -20,7 +20,17 @@ builders fell into lock-step (profiles/r4_two_builders_trace.txt); at 128 of 256
 by ~7 % on some boxes and lost 5 % on others, so both are timed before the timed region and the
 faster one is used (`builders_per_gpu`).  The same sequences back to back on one stream are reported as `one_stream`.
 
+A plain run does only what the headline needs: set up the resident inputs, pick the builders per GPU, warm up,
+time `--steps` steps and print the result line.  `--full` adds the side measurements and checks, before the
+warmup: the bit-exact check against the oracle, the per-kernel HIP-event pass (`roofline.k_emit`,
+`roofline.stage_ms_per_step`), `single_sst`, the copy-bandwidth probes (`roofline.measured_copy_GBps`) and, after
+the timed region, the CPU baseline (`cpu_baseline`); without it those fields are null or empty.
+`--dump-outputs DIR` writes the outputs of the last timed step (every SST of that step: summary, block index
+arrays, bloom bitmap, a seeded sample and per-chunk checksums of the data section) as DIR/<name>.npy; the
+inputs are seeded, so two builds run with the same arguments can be compared file by file.
+
   python bench.py [--gpus N --steps K --warmup W --batch B]   (N > 1: spawns N ranks itself)
+  python bench.py --full                                      (every side measurement and check)
   python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
   python bench.py --gpus 2 --dry-run                          (rank plumbing on the CPU, gloo)
 """
@@ -67,7 +77,46 @@ def parse():
     p.add_argument("--block-size", type=int, default=4096, help="SstBlockSize (diagnostics; the metric is 4096)")
     p.add_argument("--dry-run", action="store_true",
                    help="rank plumbing only, no GPU: gloo, the SST assignment, barrier and max/sum aggregation")
+    p.add_argument("--full", action="store_true",
+                   help="also run the side measurements and checks: the bit-exact oracle check, the per-kernel "
+                        "HIP-event pass, the single-SST latency, the copy-bandwidth probes and the CPU baseline "
+                        "(--no-verify, --stage-steps, --single-steps, --no-cpu, --cpu-* select among them)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step produced as DIR/<name>.npy")
     return p.parse_args()
+
+
+DUMP_DATA_SAMPLES = 1 << 19  # data bytes sampled per SST by --dump-outputs
+DUMP_CHUNK = 4096            # bytes per checksum of the data section in --dump-outputs
+
+
+def dump_outputs(path, outs):
+    """--dump-outputs: the outputs of one sdb_encode_ssts set (the DeviceSstOutput of every SST of the last timed
+    step) as float32 / float64 .npy files, one row or one run per SST.  The small arrays are written whole; the
+    data section (64 MiB per SST) as a fixed seeded sample of byte positions plus two checksums per 4 KiB
+    chunk (plain and position-weighted byte sums, exact in float64), so a changed byte anywhere shows."""
+    os.makedirs(path, exist_ok=True)
+    frac = np.random.default_rng(0x5EED00D0).random(DUMP_DATA_SAMPLES)
+    cols = {k: [] for k in ("summary", "block_off", "block_first_entry", "index_key_len", "block_stats", "bloom",
+                            "data_sample", "data_chunk_sums")}
+    for o in outs:
+        sm = o.summary_host()
+        nb = sm.num_blocks
+        cols["summary"].append(np.array([float(getattr(sm, f)) for f, _ in _abi.SstSummary._fields_], np.float64))
+        cols["block_off"].append(o.block_off[:nb + 1].cpu().numpy().astype(np.float64))
+        cols["block_first_entry"].append(o.block_first[:nb + 1].cpu().numpy().astype(np.float64))
+        cols["index_key_len"].append(o.index_key_len[:nb].cpu().numpy().astype(np.float32))
+        cols["block_stats"].append(o.block_stats[:3 * nb].cpu().numpy().view(np.uint16).astype(np.float32))
+        cols["bloom"].append(o.bloom[:sm.bloom_len].cpu().numpy().astype(np.float32))
+        data = o.data[:sm.data_len]
+        pos = torch.from_numpy((frac * sm.data_len).astype(np.int64)).to(data.device)
+        cols["data_sample"].append(data[pos].cpu().numpy().astype(np.float32))
+        pad = (-sm.data_len) % DUMP_CHUNK
+        d = torch.nn.functional.pad(data, (0, pad)).view(-1, DUMP_CHUNK).to(torch.float64)
+        w = torch.arange(1, DUMP_CHUNK + 1, dtype=torch.float64, device=data.device)
+        cols["data_chunk_sums"].append(torch.stack((d.sum(1), (d * w).sum(1)), 1).reshape(-1).cpu().numpy())
+    for k, v in cols.items():
+        np.save(os.path.join(path, k + ".npy"), np.stack(v) if k in ("summary", "data_sample") else np.concatenate(v))
 
 
 def launch_ranks(args):
@@ -280,13 +329,14 @@ def main():
         q = i % nslot if not one_stream else i % 2
         st = stream if one_stream else streams[i % len(streams)]
         runtime.encode_ssts_device(sets[i % nsets], outs[q], prm, wss[q], st)
+        return q
 
     # verify against the oracle (bit-exact) before the warmup, so the timed region follows the warmup
     # steps directly (the host-side oracle check leaves the GPU idle for about a second)
     verified = None
     step(0)
     torch.cuda.synchronize()
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         from oracle import oracle as O
         oprm = O.params(block_size=args.block_size, sst_version=2, bloom_bits_per_key=args.bpk)
         verified = True
@@ -300,27 +350,31 @@ def main():
                       and np.array_equal(got["index_key_len"], ref.index_key_len))
                 assert ok, "GPU output of SST %d differs from the oracle" % q
     sm = outs[0][0].summary_host()
+    assert sm.status == 0, "encode failed: %s" % _abi.STATUS_NAMES.get(sm.status)
     alg_sst = hosts[0].algorithmic_input_bytes() + sm.data_len + sm.bloom_len
 
     # the side measurements run BEFORE the warmup and the timed region, so the timed steps start on a GPU
     # that has been busy for a while (not straight after the idle of the host-side oracle check)
     # per-kernel pass: HIP events recorded around each kernel on the encode stream (sdb_diag_*)
     lib.sdb_set_concurrent_builders(1)  # the side measurements: one builder on the whole chip
-    lib.sdb_diag_enable_stage_timing(1)
-    for i in range(args.stage_steps):
-        step(i, one_stream=True)
-    torch.cuda.synchronize()
-    lib.sdb_diag_enable_stage_timing(0)
-    ms = (C.c_double * 16)()
-    launches = C.c_uint64(0)
-    ns = lib.sdb_diag_stage_times(ms, 16, C.byref(launches))
-    nl = max(args.stage_steps, 1)
-    stage_ms = {_abi.STAGES[i]: ms[i] / nl for i in range(ns) if ms[i] > 0}
+    stage_ms = {}
+    if args.full:
+        lib.sdb_diag_enable_stage_timing(1)
+        for i in range(args.stage_steps):
+            step(i, one_stream=True)
+        torch.cuda.synchronize()
+        lib.sdb_diag_enable_stage_timing(0)
+        ms = (C.c_double * 16)()
+        launches = C.c_uint64(0)
+        ns = lib.sdb_diag_stage_times(ms, 16, C.byref(launches))
+        nl = max(args.stage_steps, 1)
+        stage_ms = {_abi.STAGES[i]: ms[i] / nl for i in range(ns) if ms[i] > 0}
     emit_ms = stage_ms.get("emit", 0.0)
     emit_bytes = batch * (hosts[0].algorithmic_input_bytes() + sm.data_len)  # read keys+values(+seq/flags), write data
     emit_gbs = emit_bytes / (emit_ms * 1e-3) / 1e9 if emit_ms else 0.0
 
-    # the same launch sequences back to back on one stream (no concurrent builders)
+    # the same launch sequences back to back on one stream (no concurrent builders); with the two-builder pass
+    # below this is what picks the builders of the timed region, so a plain run keeps both
     one_stream = None
     if len(streams) > 1:
         k1 = max(1, min(args.steps, 400))
@@ -337,7 +391,7 @@ def main():
 
     # single-SST latency (configs[1] shape: sdb_encode_sst, one SST per launch sequence)
     single = None
-    if args.single_steps and rank == 0:
+    if args.full and args.single_steps and rank == 0:
         one = runtime.DeviceSstOutput(hosts[0].n, logical, logical, prm, device=dev)
         for i in range(10):
             runtime.encode_sst_device(dbs[i % len(dbs)], one, stream)
@@ -353,7 +407,7 @@ def main():
         single = {"device_ms_per_sst": round(sms, 5), "GiB_per_s": round(logical / (sms * 1e-3) / 2**30, 2),
                   "achieved_GBps": round(sg, 1), "frac": round(sg / PEAK_HBM_GBS, 4)}
 
-    copy_gbs = measured_copy_gbs(dev)
+    copy_gbs = measured_copy_gbs(dev) if args.full else None
 
     # builders per GPU for the timed region: S concurrent builders overlap one builder's segmentation with the
     # other's block assembly, but whether that beats one builder on the whole chip depends on how the
@@ -387,10 +441,7 @@ def main():
     run_streams = streams[:builders]
 
     def run_step(i):
-        if builders == 1:
-            step(i, one_stream=True)
-        else:
-            step(i)
+        return step(i, one_stream=True) if builders == 1 else step(i)
 
     lib.sdb_set_concurrent_builders(builders)  # the timed region: the chosen builders in flight
     for i in range(args.warmup):
@@ -406,8 +457,9 @@ def main():
     ev0.record(stream)
     for st in run_streams[1:]:
         st.wait_event(ev0)
+    last_slot = None
     for i in range(args.steps):
-        run_step(i)
+        last_slot = run_step(i)
     for st in run_streams[1:]:
         j = torch.cuda.Event()
         j.record(st)
@@ -419,6 +471,9 @@ def main():
     elapsed = time.perf_counter() - t0
     dev_ms = ev0.elapsed_time(ev1)
     total_bytes, max_elapsed = job.aggregate(tdist if dist else None, args.steps * batch * logical, elapsed, dev)
+    if args.dump_outputs and last_slot is not None:
+        dump_outputs(args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, "rank%d" % rank),
+                     outs[last_slot])
 
     value = job.job_rate_gibs(total_bytes, max_elapsed)
     ms_per_step = max_elapsed / args.steps * 1e3
@@ -473,8 +528,11 @@ def main():
         "concurrent_builders": multi,
         "single_sst": single,
         "verified_vs_oracle": verified,
+        "full": args.full,
     }
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if not args.full:
+        line["roofline"]["k_emit"] = None  # the per-kernel pass is a --full measurement
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         line["cpu_baseline"] = cpu_baseline(args.cpu_seconds, args.cpu_threads or cpu_share())
     if rank == 0:
         print(json.dumps(line), flush=True)

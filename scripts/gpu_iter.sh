@@ -7,7 +7,7 @@ O=gpurun_out/iter
 rm -rf $O; mkdir -p $O
 timeout -k 10 600 python -u -m pytest -x -q --timeout 300 --timeout-method thread -m gpu ${TESTS:-tests} > $O/tests.log 2>&1
 rc=$?; tail -3 $O/tests.log; grep -E "^(FAILED|ERROR)" $O/tests.log | head; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python3 -u bench.py --steps 600 --warmup 10 --no-cpu > $O/bench.json 2> $O/bench.err
+timeout -k 10 300 python3 -u bench.py --full --steps 600 --warmup 10 --no-cpu > $O/bench.json 2> $O/bench.err
 rc=$?; [ $rc -eq 0 ] || { tail -5 $O/bench.err; exit $rc; }
 python3 -c "
 import json; d=json.load(open('$O/bench.json')); r=d['roofline']; b=d['config']['ssts_per_gpu_per_step']

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Refresh every measured number committed under profiles/ in one GPU call (round tag $TAG, default r3):
-#   1. bench.py default run (oracle verify + CPU baseline)               -> rp/bench.json
+#   1. bench.py --full (oracle verify, side measurements, CPU baseline)  -> rp/bench.json
 #   2. rocprofv3 --kernel-trace --stats over the bench, one stream        -> rp/enc/
 #   3. PMC passes FETCH_SIZE, WRITE_SIZE over the bench                    -> rp/pmc_*/
 #   4. scripts/bench_configs.py (every config, CPU baselines)             -> rp/configs.jsonl
@@ -23,7 +23,7 @@ step() {  # name timeout command...
   local rc=$?; echo "$n rc=$rc"; [ $rc -eq 0 ] || exit $rc
 }
 if [ "$PART" != 2 ]; then
-step bench 400 python3 bench.py
+step bench 400 python3 bench.py --full
 grep '^{' $O/bench.log > $O/bench.json; cut -c1-300 $O/bench.json
 step enc 300 rocprofv3 --kernel-trace --stats -d $O/enc -o run --output-format csv -- python3 bench.py --streams 1 --steps 100 --warmup 10 --no-cpu --no-verify --single-steps 0 --stage-steps 0
 for c in FETCH_SIZE WRITE_SIZE; do
