@@ -19,6 +19,24 @@ def build():
     subprocess.check_call(["make", "-s", "-C", HERE])
 
 
+class StreamStats(C.Structure):
+    """orc_stream_stats (sdb_oracle.h): every field a u32 or an array of them."""
+    _fields_ = [("nblocks", C.c_uint32), ("kinds", C.c_uint32 * 3), ("kind_seq", C.c_uint32 * 64),
+                ("z_max_ll_len", C.c_uint32), ("z_max_d_len", C.c_uint32), ("z_max_cl_len", C.c_uint32),
+                ("matches", C.c_uint32), ("max_match", C.c_uint32), ("max_dist", C.c_uint32),
+                ("z_ll_hist", C.c_uint32 * 286), ("z_cl_hist", C.c_uint32 * 19),
+                ("zs_fcs_bytes", C.c_uint32), ("zs_fcs", C.c_uint32), ("zs_lit_type", C.c_uint32 * 4),
+                ("zs_lit_streams", C.c_uint32 * 2), ("zs_lit_sizefmt", C.c_uint32 * 4),
+                ("zs_huf_direct", C.c_uint32), ("zs_huf_fse", C.c_uint32), ("zs_huf_maxbits", C.c_uint32),
+                ("zs_lit_hist", C.c_uint32 * 256),
+                ("zs_mode", (C.c_uint32 * 4) * 3),
+                ("zs_nseq", C.c_uint32), ("zs_rep", C.c_uint32), ("zs_rep_ll0", C.c_uint32),
+                ("zs_rep_after_raw", C.c_uint32),
+                ("lz_elems", C.c_uint32), ("lz_max_lit_ext", C.c_uint32), ("lz_max_match_ext", C.c_uint32),
+                ("lz_last_match_pos", C.c_uint32), ("sn_tag", C.c_uint32 * 4), ("sn_lit_tag_bytes", C.c_uint32 * 6),
+                ("sn_split64", C.c_uint32), ("sn_split60", C.c_uint32)]
+
+
 def _load():
     if not os.path.exists(LIB):
         build()
@@ -56,6 +74,7 @@ def _load():
         "orc_xxh64": (C.c_uint64, [V, C.c_size_t, C.c_uint64]),
         "orc_decompress": (C.c_int, [C.c_uint32, V, C.c_size_t, V, C.c_size_t, P(C.c_size_t)]),
         "orc_decompress_blocks": (C.c_int, [C.c_uint32, V, V, C.c_uint64, V, C.c_uint64, V, V, P(C.c_uint64)]),
+        "orc_stream_stats_of": (C.c_int, [C.c_uint32, V, C.c_size_t, P(StreamStats)]),
         "orc_merge_runs": (C.c_int, [P(_abi.Run), C.c_uint32, P(_abi.Retention), P(_abi.MergedOut)]),
         "orc_sst_cuts": (C.c_int, [P(_abi.KvBatch), P(_abi.SstParams), C.c_uint64, V, C.c_uint64, P(C.c_uint64)]),
     }
@@ -437,6 +456,23 @@ def decompress(codec, data):
     ol = C.c_size_t(0)
     st = lib().orc_decompress(codec, b.ctypes.data if b.size else None, b.size, out.ctypes.data, cap, C.byref(ol))
     return st, out[:ol.value].tobytes() if st == 0 else b""
+
+
+def stream_stats(codec, data):
+    """What the payload is made of, counted by the decompressors while they decode it (orc_stream_stats):
+    a dict of ints and lists.  "status" is orc_decompress's; "blocks" is the kinds of the deflate / zstd
+    blocks in order (the first 64): deflate 0 stored, 1 fixed, 2 dynamic; zstd 0 raw, 1 RLE, 2 compressed."""
+    b = np.frombuffer(bytes(data), np.uint8)
+    st = StreamStats()
+    status = lib().orc_stream_stats_of(codec, b.ctypes.data if b.size else None, b.size, C.byref(st))
+
+    def py(v):
+        return v if isinstance(v, int) else [py(x) for x in v]
+
+    d = {name: py(getattr(st, name)) for name, _ in StreamStats._fields_}
+    d["status"] = status
+    d["blocks"] = d.pop("kind_seq")[:min(st.nblocks, 64)]
+    return d
 
 
 class DecompressResult:

@@ -1669,6 +1669,8 @@ static int snappy_header(const uint8_t *in, size_t n, uint64_t *len, size_t *hdr
 int64_t orc_entropy_len(uint32_t codec, const uint8_t *in, size_t n);
 sdb_status orc_entropy_decompress(uint32_t codec, const uint8_t *in, size_t n, uint8_t *out, size_t cap,
                                   size_t *out_len);
+sdb_status orc_entropy_decompress_st(uint32_t codec, const uint8_t *in, size_t n, uint8_t *out, size_t cap,
+                                     size_t *out_len, orc_stream_stats *st);
 enum { ORC_CODEC_ZLIB = 2, ORC_CODEC_ZSTD = 4 };
 
 int64_t orc_decompressed_len(uint32_t codec, const uint8_t *in, size_t n) {
@@ -1690,19 +1692,25 @@ int64_t orc_decompressed_len(uint32_t codec, const uint8_t *in, size_t n) {
  * offset and the match.  lz4_flex decompresses into a buffer of the declared size and truncates to
  * what was written; writing past it, an offset of 0 or past the output start, or input that ends
  * inside a sequence is an error. */
-static sdb_status lz4_block(const uint8_t *in, size_t n, uint8_t *out, size_t cap, size_t *olen) {
+static sdb_status lz4_block(const uint8_t *in, size_t n, uint8_t *out, size_t cap, size_t *olen, orc_stream_stats *st) {
     size_t ip = 0, op = 0;
     for (;;) {
         if (ip >= n) return SDB_DECOMPRESSION_ERROR;
         const uint8_t tok = in[ip++];
         size_t lit = tok >> 4;
+        uint32_t ext = 0;
         if (lit == 15) {
             uint8_t b;
             do {
                 if (ip >= n) return SDB_DECOMPRESSION_ERROR;
                 b = in[ip++];
                 lit += b;
+                ext++;
             } while (b == 255);
+        }
+        if (st) {
+            st->lz_elems++;
+            if (ext > st->lz_max_lit_ext) st->lz_max_lit_ext = ext;
         }
         if (lit > n - ip || lit > cap - op) return SDB_DECOMPRESSION_ERROR;
         memcpy(out + op, in + ip, lit);
@@ -1713,15 +1721,24 @@ static sdb_status lz4_block(const uint8_t *in, size_t n, uint8_t *out, size_t ca
         const size_t off = (size_t)in[ip] | (size_t)in[ip + 1] << 8;
         ip += 2;
         size_t ml = (size_t)(tok & 15) + 4;
+        ext = 0;
         if ((tok & 15) == 15) {
             uint8_t b;
             do {
                 if (ip >= n) return SDB_DECOMPRESSION_ERROR;
                 b = in[ip++];
                 ml += b;
+                ext++;
             } while (b == 255);
         }
         if (off == 0 || off > op || ml > cap - op) return SDB_DECOMPRESSION_ERROR;
+        if (st) {
+            st->matches++;
+            if (ext > st->lz_max_match_ext) st->lz_max_match_ext = ext;
+            if (ml > st->max_match) st->max_match = (uint32_t)ml;
+            if (off > st->max_dist) st->max_dist = (uint32_t)off;
+            st->lz_last_match_pos = (uint32_t)op;
+        }
         for (size_t i = 0; i < ml; i++) out[op + i] = out[op - off + i];  /* overlapping copies repeat */
         op += ml;
     }
@@ -1733,12 +1750,19 @@ static sdb_status lz4_block(const uint8_t *in, size_t n, uint8_t *out, size_t ca
  * or 60..63 -> 1..4 little-endian length bytes), 1 copy of 4..11 bytes with an 11-bit offset, 2 copy of
  * 1..64 bytes with a 16-bit offset, 3 the same with a 32-bit offset.  snap checks every element
  * against the declared length and requires the output to end exactly there. */
-static sdb_status snappy_raw(const uint8_t *in, size_t n, uint8_t *out, size_t len) {
+static sdb_status snappy_raw(const uint8_t *in, size_t n, uint8_t *out, size_t len, orc_stream_stats *st) {
     size_t ip = 0, op = 0;
+    size_t prev_len = 0, prev_off = 0;  /* the element before, when it was a copy */
     while (ip < n) {
         const uint8_t tag = in[ip++];
+        if (st) {
+            st->lz_elems++;
+            st->sn_tag[tag & 3]++;
+        }
         if ((tag & 3) == 0) {
             size_t l = tag >> 2;
+            if (st) st->sn_lit_tag_bytes[l >= 60 ? l - 58 : 1]++;
+            prev_len = 0;
             if (l >= 60) {
                 const size_t nb = l - 59;
                 if (n - ip < nb) return SDB_DECOMPRESSION_ERROR;
@@ -1770,24 +1794,53 @@ static sdb_status snappy_raw(const uint8_t *in, size_t n, uint8_t *out, size_t l
             ip += 4;
         }
         if (off == 0 || off > op || l > len - op) return SDB_DECOMPRESSION_ERROR;
+        if (st) {
+            st->matches++;
+            if (l > st->max_match) st->max_match = (uint32_t)l;
+            if (off > st->max_dist) st->max_dist = (uint32_t)off;
+            st->lz_last_match_pos = (uint32_t)op;
+            if (prev_len == 64 && prev_off == off) st->sn_split64++;
+            if (prev_len == 60 && prev_off == off) st->sn_split60++;
+        }
+        prev_len = l;
+        prev_off = off;
         for (size_t i = 0; i < l; i++) out[op + i] = out[op - off + i];
         op += l;
     }
     return op == len ? SDB_OK : SDB_DECOMPRESSION_ERROR;
 }
 
-sdb_status orc_decompress(uint32_t codec, const uint8_t *in, size_t n, uint8_t *out, size_t cap, size_t *out_len) {
-    if (codec == ORC_CODEC_ZLIB || codec == ORC_CODEC_ZSTD) return orc_entropy_decompress(codec, in, n, out, cap, out_len);
+static sdb_status decompress_st(uint32_t codec, const uint8_t *in, size_t n, uint8_t *out, size_t cap, size_t *out_len,
+                                orc_stream_stats *st) {
+    if (codec == ORC_CODEC_ZLIB || codec == ORC_CODEC_ZSTD)
+        return orc_entropy_decompress_st(codec, in, n, out, cap, out_len, st);
     const int64_t len = orc_decompressed_len(codec, in, n);
     if (codec != ORC_CODEC_LZ4 && codec != ORC_CODEC_SNAPPY) return SDB_UNSUPPORTED;
     if (len < 0) return SDB_DECOMPRESSION_ERROR;
     if ((uint64_t)len > cap) return SDB_INVALID_ARGUMENT;
-    if (codec == ORC_CODEC_LZ4) return lz4_block(in + 4, n - 4, out, (size_t)len, out_len);
+    if (codec == ORC_CODEC_LZ4) return lz4_block(in + 4, n - 4, out, (size_t)len, out_len, st);
     uint64_t l = 0;
     size_t h = 0;
     snappy_header(in, n, &l, &h);
     *out_len = (size_t)len;
-    return snappy_raw(in + h, n - h, out, (size_t)len);
+    return snappy_raw(in + h, n - h, out, (size_t)len, st);
+}
+
+sdb_status orc_decompress(uint32_t codec, const uint8_t *in, size_t n, uint8_t *out, size_t cap, size_t *out_len) {
+    return decompress_st(codec, in, n, out, cap, out_len, NULL);
+}
+
+/* the stats of one payload: decoded into a scratch buffer of its declared (or counted) length */
+sdb_status orc_stream_stats_of(uint32_t codec, const uint8_t *in, size_t n, orc_stream_stats *st) {
+    memset(st, 0, sizeof(*st));
+    const int64_t len = orc_decompressed_len(codec, in, n);
+    if (len < 0 || (uint64_t)len > (64ull << 20)) return SDB_DECOMPRESSION_ERROR;
+    uint8_t *buf = (uint8_t *)malloc((size_t)len + 1);
+    if (!buf) return SDB_INVALID_ARGUMENT;
+    size_t ol = 0;
+    const sdb_status r = decompress_st(codec, in, n, buf, (size_t)len, &ol, st);
+    free(buf);
+    return r;
 }
 
 /* The output plan of sdb_decompress_plan: block k's slot holds its declared length + 4 (CRC) bytes; 0

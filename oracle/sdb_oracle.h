@@ -66,6 +66,47 @@ int orc_bloom_might_match(const uint8_t *bitmap, uint64_t bitmap_bytes, uint32_t
  * elements).  orc_decompressed_len: the declared length (-1: bad header / other codec). */
 int64_t orc_decompressed_len(uint32_t codec, const uint8_t *in, size_t n);
 sdb_status orc_decompress(uint32_t codec, const uint8_t *in, size_t n, uint8_t *out, size_t cap, size_t *out_len);
+
+/* What a compressed stream is made of, counted by the decoders above while they decode (the stats sink is
+ * optional everywhere: NULL changes nothing).  The tests read it to prove which encoder branches wrote a
+ * stream.  All fields are u32; oracle.py mirrors the layout. */
+#define ORC_STATS_KINDS 64
+typedef struct {
+    /* deflate blocks (0 stored, 1 fixed, 2 dynamic) / zstd blocks (0 raw, 1 RLE, 2 compressed) */
+    uint32_t nblocks;                      /* every block */
+    uint32_t kinds[3];                     /* per kind */
+    uint32_t kind_seq[ORC_STATS_KINDS];    /* the first ORC_STATS_KINDS blocks' kinds, in order */
+    /* zlib: over the dynamic blocks, the longest code per alphabet; over every block, the matches */
+    uint32_t z_max_ll_len, z_max_d_len, z_max_cl_len;
+    uint32_t matches, max_match, max_dist;
+    uint32_t z_ll_hist[286];               /* literal / length symbols (256 included) decoded in the dynamic
+                                              block with the longest literal / length code (the first such) */
+    uint32_t z_cl_hist[19];                /* code-length-code symbols decoded in the dynamic block with the
+                                              longest code-length code (the first such) */
+    /* zstd */
+    uint32_t zs_fcs_bytes;                 /* Frame_Content_Size field of the last frame: 0, 1, 2, 4 or 8 */
+    uint32_t zs_fcs;                       /* its value (low 32 bits) */
+    uint32_t zs_lit_type[4];               /* literals sections: raw, RLE, Huffman, treeless */
+    uint32_t zs_lit_streams[2];            /* Huffman / treeless sections with 1 and with 4 streams */
+    uint32_t zs_lit_sizefmt[4];            /* Huffman / treeless sections per Size_Format */
+    uint32_t zs_huf_direct, zs_huf_fse;    /* tree descriptions: direct weights, FSE-compressed weights */
+    uint32_t zs_huf_maxbits;               /* the longest Huffman code of any tree */
+    uint32_t zs_lit_hist[256];             /* the literals coded with the tree that has it (the first such) */
+    uint32_t zs_mode[3][4];                /* [LL, OF, ML][predefined, RLE, FSE, repeat] */
+    uint32_t zs_nseq, zs_rep, zs_rep_ll0;  /* sequences; with a repeat-offset code; of those, with ll == 0 */
+    uint32_t zs_rep_after_raw;             /* repeat-offset sequences in a block that follows a raw block */
+    /* lz4 / snappy */
+    uint32_t lz_elems;                     /* lz4 sequences / snappy elements */
+    uint32_t lz_max_lit_ext, lz_max_match_ext;  /* lz4: the longest length extension, in bytes */
+    uint32_t lz_last_match_pos;            /* output position of the last match's first byte */
+    uint32_t sn_tag[4];                    /* snappy elements per tag (literal, copy-1, copy-2, copy-4) */
+    uint32_t sn_lit_tag_bytes[6];          /* literals per tag size in bytes (1: the length in the tag) */
+    uint32_t sn_split64, sn_split60;       /* copies of 64 / 60 bytes followed by a copy at the same offset */
+} orc_stream_stats;
+/* orc_decompress into a scratch buffer with the stats sink set: *st is zeroed, then filled.  Returns
+ * orc_decompress's status (the counts cover what was decoded before an error). */
+sdb_status orc_stream_stats_of(uint32_t codec, const uint8_t *in, size_t n, orc_stream_stats *st);
+
 /* decode_block's first half over a block run (format/sst.rs:980-999): validate_checksum over the stored
  * bytes, decompress, then the block re-framed with the CRC32 of its uncompressed bytes, so that
  * [out_start[k], out_end[k]) is a plain block for orc_decode_blocks / sdb_decode_blocks_at.  out_start

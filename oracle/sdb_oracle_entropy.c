@@ -123,13 +123,19 @@ enum { Z_OK = 0, Z_TRUNC = 1, Z_ERR = -1 };
 
 /* inflate into o; the output so far is o->p[0, o->len) (count mode: history not kept, distances are
  * still checked against the bytes produced).  Z_TRUNC: the input ended before the final block did. */
-static int inflate_raw(lsb_bits *s, sink *o) {
+static int inflate_raw(lsb_bits *s, sink *o, orc_stream_stats *st) {
     static const uint8_t kOrder[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
     canon lit, dist;
     uint32_t last = 0;
     do {
         uint32_t type;
         if (lsb_get(s, 1, &last) || lsb_get(s, 2, &type)) return Z_TRUNC;
+        int hist = 0;  /* this block's symbols go to st->z_ll_hist */
+        if (st && type < 3) {
+            if (st->nblocks < ORC_STATS_KINDS) st->kind_seq[st->nblocks] = type;
+            st->nblocks++;
+            st->kinds[type]++;
+        }
         if (type == 0) {  /* stored: to the byte boundary, LEN, NLEN, bytes */
             s->buf >>= s->cnt & 7;
             s->cnt -= s->cnt & 7;
@@ -170,11 +176,23 @@ static int inflate_raw(lsb_bits *s, sink *o) {
             }
             canon clc;
             if (canon_build(&clc, cl, 19)) return Z_ERR;
+            int clhist = 0;  /* this block's code-length-code symbols go to st->z_cl_hist */
+            if (st) {
+                uint32_t mcl = 0;
+                for (int k = 0; k < 19; k++)
+                    if (cl[k] > mcl) mcl = cl[k];
+                if (mcl > st->z_max_cl_len) {
+                    st->z_max_cl_len = mcl;
+                    memset(st->z_cl_hist, 0, sizeof(st->z_cl_hist));
+                    clhist = 1;
+                }
+            }
             int i = 0;
             while (i < nlen + ndist) {
                 const int sym = canon_decode(s, &clc);
                 if (sym == -1) return Z_TRUNC;
                 if (sym < 0) return Z_ERR;
+                if (clhist) st->z_cl_hist[sym]++;
                 if (sym < 16) { lens[i++] = (uint8_t)sym; continue; }
                 uint32_t rep, v;
                 uint8_t val = 0;
@@ -194,6 +212,18 @@ static int inflate_raw(lsb_bits *s, sink *o) {
                 while (rep--) lens[i++] = val;
             }
             if (lens[256] == 0) return Z_ERR;  /* no end-of-block code */
+            if (st) {
+                uint32_t mll = 0;
+                for (int k = 0; k < nlen; k++)
+                    if (lens[k] > mll) mll = lens[k];
+                for (int k = 0; k < ndist; k++)
+                    if (lens[nlen + k] > st->z_max_d_len) st->z_max_d_len = lens[nlen + k];
+                if (mll > st->z_max_ll_len) {
+                    st->z_max_ll_len = mll;
+                    memset(st->z_ll_hist, 0, sizeof(st->z_ll_hist));
+                    hist = 1;
+                }
+            }
             memmove(lens + 288, lens + nlen, (size_t)ndist);
         }
         if (canon_build(&lit, lens, nlen) || canon_build(&dist, lens + 288, ndist)) return Z_ERR;
@@ -201,6 +231,7 @@ static int inflate_raw(lsb_bits *s, sink *o) {
             int sym = canon_decode(s, &lit);
             if (sym == -1) return Z_TRUNC;
             if (sym < 0) return Z_ERR;
+            if (hist && sym < 286) st->z_ll_hist[sym]++;
             if (sym < 256) {
                 if (put_byte(o, (uint8_t)sym)) return Z_ERR;
                 continue;
@@ -217,6 +248,11 @@ static int inflate_raw(lsb_bits *s, sink *o) {
             if (lsb_get(s, kDistExtra[ds], &v)) return Z_TRUNC;
             const uint32_t d = kDistBase[ds] + v;
             if (d > o->len) return Z_ERR;
+            if (st) {
+                st->matches++;
+                if (len > st->max_match) st->max_match = len;
+                if (d > st->max_dist) st->max_dist = d;
+            }
             for (uint32_t i = 0; i < len; i++) {
                 const uint8_t b = o->p ? o->p[o->len - d] : 0;
                 if (put_byte(o, b)) return Z_ERR;
@@ -237,12 +273,12 @@ static uint32_t adler32(const uint8_t *p, size_t n) {
 
 /* flate2 ZlibDecoder::read_to_end -> 0 or -1 (error); o holds the output.  Adler-32 is checked only
  * when the bytes are kept (o->p != NULL). */
-static int zlib_decode(const uint8_t *in, size_t n, sink *o) {
+static int zlib_decode(const uint8_t *in, size_t n, sink *o, orc_stream_stats *st) {
     if (n < 2) return 0;  /* EOF before the header: no output, no error */
     const uint32_t cmf = in[0], flg = in[1];
     if ((cmf & 0x0F) != 8 || (cmf >> 4) > 7 || ((cmf << 8) | flg) % 31 != 0 || (flg & 0x20)) return -1;
     lsb_bits s = {in, n, 2, 0, 0};
-    const int r = inflate_raw(&s, o);
+    const int r = inflate_raw(&s, o, st);
     if (r == Z_ERR) return -1;
     if (r == Z_TRUNC) return 0;
     /* Adler-32, big-endian, at the next byte boundary */
@@ -474,7 +510,7 @@ static int huf_from_weights(huf_table *h, const uint8_t *w, int nw) {
 }
 
 /* Huffman tree description -> table; returns bytes used or -1 */
-static int huf_read(huf_table *h, const uint8_t *in, size_t n) {
+static int huf_read(huf_table *h, const uint8_t *in, size_t n, orc_stream_stats *st) {
     if (n < 1) return -1;
     const int hb = in[0];
     uint8_t w[256];
@@ -485,6 +521,10 @@ static int huf_read(huf_table *h, const uint8_t *in, size_t n) {
         if ((size_t)nb + 1 > n) return -1;
         for (int i = 0; i < nw; i++) w[i] = (i & 1) ? (in[1 + i / 2] & 15) : (in[1 + i / 2] >> 4);
         if (huf_from_weights(h, w, nw)) return -1;
+        if (st) {
+            st->zs_huf_direct++;
+            if ((uint32_t)h->maxbits > st->zs_huf_maxbits) st->zs_huf_maxbits = (uint32_t)h->maxbits;
+        }
         return 1 + nb;
     }
     /* FSE-compressed weights: hb bytes = table description + backward stream, two interleaved states */
@@ -519,6 +559,10 @@ static int huf_read(huf_table *h, const uint8_t *in, size_t n) {
         }
     }
     if (huf_from_weights(h, w, nw)) return -1;
+    if (st) {
+        st->zs_huf_fse++;
+        if ((uint32_t)h->maxbits > st->zs_huf_maxbits) st->zs_huf_maxbits = (uint32_t)h->maxbits;
+    }
     return 1 + hb;
 }
 
@@ -591,7 +635,8 @@ static int seq_table(fse_table *ft, int *have, int mode, const uint8_t *in, size
 }
 
 /* a compressed block -> appended to the frame's output o (frame bytes o->p[fstart, o->len)) */
-static int zstd_block(zstd_ctx *z, const uint8_t *in, size_t n, sink *o, size_t fstart, uint64_t window) {
+static int zstd_block(zstd_ctx *z, const uint8_t *in, size_t n, sink *o, size_t fstart, uint64_t window,
+                      orc_stream_stats *st, int after_raw) {
     if (n < 1) return -1;
     /* literals section */
     const int ltype = in[0] & 3, sf = (in[0] >> 2) & 3;
@@ -617,8 +662,16 @@ static int zstd_block(zstd_ctx *z, const uint8_t *in, size_t n, sink *o, size_t 
         }
     }
     if (regen > 128 * 1024) return -1;
+    if (st) {
+        st->zs_lit_type[ltype]++;
+        if (ltype >= 2) {
+            st->zs_lit_streams[streams == 4]++;
+            st->zs_lit_sizefmt[sf]++;
+        }
+    }
     uint8_t *lit = (uint8_t *)malloc(regen + 1);
     size_t ip = hdr;
+    uint32_t deepest = 0;  /* stats: the longest code before this block's tree */
     int rc = -1;
     if (ltype == 0) {
         if (ip + regen > n) goto out;
@@ -633,7 +686,8 @@ static int zstd_block(zstd_ctx *z, const uint8_t *in, size_t n, sink *o, size_t 
         const uint8_t *c = in + ip;
         size_t cn = csize;
         if (ltype == 2) {
-            const int used = huf_read(&z->huf, c, cn);
+            deepest = st ? st->zs_huf_maxbits : 0;
+            const int used = huf_read(&z->huf, c, cn, st);
             if (used < 0) goto out;
             z->have_huf = 1;
             c += used;
@@ -655,6 +709,10 @@ static int zstd_block(zstd_ctx *z, const uint8_t *in, size_t n, sink *o, size_t 
                 goto out;
         }
         ip += csize;
+        if (st && ltype == 2 && st->zs_huf_maxbits > deepest) {
+            memset(st->zs_lit_hist, 0, sizeof(st->zs_lit_hist));
+            for (size_t i = 0; i < regen; i++) st->zs_lit_hist[lit[i]]++;
+        }
     }
     /* sequences section */
     {
@@ -676,6 +734,11 @@ static int zstd_block(zstd_ctx *z, const uint8_t *in, size_t n, sink *o, size_t 
             if (ip >= n) goto out;
             const int modes = in[ip++];
             if (modes & 3) goto out;
+            if (st) {
+                st->zs_mode[0][modes >> 6]++;
+                st->zs_mode[1][(modes >> 4) & 3]++;
+                st->zs_mode[2][(modes >> 2) & 3]++;
+            }
             int u;
             u = seq_table(&z->ll, &z->have_ll, modes >> 6, in + ip, n - ip, kLLDefault, 36, 6, 35, 9);
             if (u < 0) goto out;
@@ -702,6 +765,16 @@ static int zstd_block(zstd_ctx *z, const uint8_t *in, size_t n, sink *o, size_t 
                 }
                 if (b.pos < 0) goto out;
                 uint32_t off;
+                if (st) {
+                    st->zs_nseq++;
+                    if (ofv <= 3) {
+                        st->zs_rep++;
+                        if (ll == 0) st->zs_rep_ll0++;
+                        if (after_raw) st->zs_rep_after_raw++;
+                    }
+                    st->matches++;
+                    if (ml > st->max_match) st->max_match = ml;
+                }
                 if (ofv > 3) {
                     off = ofv - 3;
                     z->rep[2] = z->rep[1];
@@ -743,7 +816,7 @@ out:
 }
 
 /* zstd::stream::decode_all -> 0 or -1 */
-static int zstd_decode(const uint8_t *in, size_t n, sink *o) {
+static int zstd_decode(const uint8_t *in, size_t n, sink *o, orc_stream_stats *st) {
     size_t ip = 0;
     while (ip < n) {
         if (n - ip < 4) return -1;
@@ -784,6 +857,11 @@ static int zstd_decode(const uint8_t *in, size_t n, sink *o) {
         if (fcs_len == 2) fcs += 256;
         ip += fcs_len;
         if (single) window = fcs;
+        if (st) {
+            st->zs_fcs_bytes = (uint32_t)fcs_len;
+            st->zs_fcs = (uint32_t)fcs;
+        }
+        int prev_kind = -1;  /* the block before, within the frame */
         if (window > (1ull << 27) + 1) return -1;  /* ZSTD_MAXWINDOWSIZE_DEFAULT */
         zstd_ctx z;
         memset(&z, 0, sizeof(z));
@@ -799,6 +877,13 @@ static int zstd_decode(const uint8_t *in, size_t n, sink *o) {
             const int last = bh & 1, type = (bh >> 1) & 3;
             const size_t bs = bh >> 3;
             if (type == 3) return -1;
+            if (st) {
+                if (st->nblocks < ORC_STATS_KINDS) st->kind_seq[st->nblocks] = (uint32_t)type;
+                st->nblocks++;
+                st->kinds[type]++;
+            }
+            const int after_raw = prev_kind == 0;
+            prev_kind = type;
             if (type == 1) {  /* RLE: one byte, bs times */
                 if (bs > bmax || ip >= n) return -1;
                 for (size_t i = 0; i < bs; i++)
@@ -809,7 +894,7 @@ static int zstd_decode(const uint8_t *in, size_t n, sink *o) {
                 if (type == 0) {
                     for (size_t i = 0; i < bs; i++)
                         if (put_byte(o, in[ip + i])) return -1;
-                } else if (zstd_block(&z, in + ip, bs, o, fstart, window)) {
+                } else if (zstd_block(&z, in + ip, bs, o, fstart, window, st, after_raw)) {
                     return -1;
                 }
                 ip += bs;
@@ -889,17 +974,22 @@ int64_t orc_entropy_len(uint32_t codec, const uint8_t *in, size_t n) {
     /* count mode, as the device plan: the bytes are not kept, so Adler-32 / XXH64 are verified only by
      * the decode proper (a stream whose checksum fails gets a slot here and fails in step 2) */
     sink o = {NULL, (size_t)1 << 40, 0, 0};
-    const int r = codec == 2 ? zlib_decode(in, n, &o) : zstd_decode(in, n, &o);
+    const int r = codec == 2 ? zlib_decode(in, n, &o, NULL) : zstd_decode(in, n, &o, NULL);
     return r || o.overflow ? -1 : (int64_t)o.len;
 }
 
-sdb_status orc_entropy_decompress(uint32_t codec, const uint8_t *in, size_t n, uint8_t *out, size_t cap,
-                                  size_t *out_len) {
+sdb_status orc_entropy_decompress_st(uint32_t codec, const uint8_t *in, size_t n, uint8_t *out, size_t cap,
+                                     size_t *out_len, orc_stream_stats *st) {
     sink o = {out, cap, 0, 0};
-    const int r = codec == 2 ? zlib_decode(in, n, &o) : zstd_decode(in, n, &o);
+    const int r = codec == 2 ? zlib_decode(in, n, &o, st) : zstd_decode(in, n, &o, st);
     *out_len = o.len;
     /* zstd: a slot sized from the frames' content sizes overflows only when a frame decodes to more than
      * it declares, which libzstd reports as corruption (the reference: BlockDecompressionError) */
     if (o.overflow) return codec == 2 ? SDB_INVALID_ARGUMENT : SDB_DECOMPRESSION_ERROR;
     return r ? SDB_DECOMPRESSION_ERROR : SDB_OK;
+}
+
+sdb_status orc_entropy_decompress(uint32_t codec, const uint8_t *in, size_t n, uint8_t *out, size_t cap,
+                                  size_t *out_len) {
+    return orc_entropy_decompress_st(codec, in, n, out, cap, out_len, NULL);
 }

@@ -112,7 +112,8 @@ struct CzCfg {
 
 // block k's slot in the workspace (rel = block_off[k] - block_off[0]): compressed bytes + CRC stay under
 // n + n/8 + 48 for every codec here (literal-only worst cases: lz4 n + n/255 + 10, snappy n + 14, stored
-// deflate n + 5 per window + 6, raw zstd n + 3 per window + 12)
+// deflate n + 5 per window + 6, raw zstd n + 3 per window + 12; lz4 and snappy fall back to the literal-only
+// stream where their elements would be longer)
 __host__ __device__ inline uint64_t cz_slot(uint64_t rel, uint64_t k) { return (rel + rel / 8 + 64 * k + 15) & ~15ull; }
 
 struct CzArgs {
@@ -305,8 +306,15 @@ SDB_DEV uint32_t cz_crc_raw(lu8 *out, uint32_t m, lu8 *sc, bool first) {
 
 // ------------------------------------------------------------------------------------------------
 // One lane, any size: a literal-only stream of the codec straight into the global slot (lz4 blocks
-// over 4 KiB whose windows find no match to end a sequence).  Returns the bytes written (no CRC).
+// over 4 KiB whose windows find no match to end a sequence; snappy blocks whose elements came out longer
+// than this).  Returns the bytes written (no CRC).
 // ------------------------------------------------------------------------------------------------
+SDB_DEV uint32_t snappy_varint_bytes(uint32_t n) { return n < 128 ? 1 : (n < 16384 ? 2 : (n < (1u << 21) ? 3 : (n < (1u << 28) ? 4 : 5))); }
+SDB_DEV uint32_t snappy_literal_tag_bytes(uint32_t lit) {  // the tag and the length bytes of one literal element
+    if (!lit) return 0;
+    const uint32_t v = lit - 1;
+    return v < 60 ? 1 : v < 256 ? 2 : v < 65536 ? 3 : v < (1u << 24) ? 4 : 5;
+}
 SDB_DEV uint32_t cz_literal_only(uint32_t codec, const uint8_t *in, uint32_t n, uint8_t *o) {
     uint32_t p = 0;
     auto lit_copy = [&](const uint8_t *src, uint32_t len) {
@@ -321,6 +329,17 @@ SDB_DEV uint32_t cz_literal_only(uint32_t codec, const uint8_t *in, uint32_t n, 
             uint32_t x = n - 15;
             for (; x >= 255; x -= 255) o[p++] = 255;
             o[p++] = (uint8_t)x;
+        }
+        lit_copy(in, n);
+    } else if (codec == SDB_CODEC_SNAPPY) {
+        for (uint32_t x = n;; x >>= 7) {
+            o[p++] = (uint8_t)(x >= 0x80 ? (x & 0x7F) | 0x80 : x);
+            if (x < 0x80) break;
+        }
+        if (n) {
+            const uint32_t v = n - 1, nb = snappy_literal_tag_bytes(n) - 1;
+            o[p++] = (uint8_t)(nb ? (59 + nb) << 2 : v << 2);
+            for (uint32_t i = 0; i < nb; i++) o[p++] = (uint8_t)(v >> (8 * i));
         }
         lit_copy(in, n);
     }
@@ -1785,8 +1804,14 @@ __global__ __launch_bounds__(64 * CzCfg<CODEC>::kWaves) void k_cz(CzArgs a) {
 #else
                 if (!same && wn >= 16) {
 #endif
+                    const uint32_t r0 = rep[0], r1 = rep[1], r2 = rep[2];
                     content = cz_zstd_window(in, wn, seq, nseq, out, hb + 3, rep, hz, aux);
                     btype = content ? 2 : 0;
+                    if (!content) {  // a discarded attempt: a raw block leaves the decoder's repeat offsets alone
+                        rep[0] = r0;
+                        rep[1] = r1;
+                        rep[2] = r2;
+                    }
                 } else if (same) {
                     btype = 1;
                 }
@@ -1837,7 +1862,7 @@ __global__ __launch_bounds__(64 * CzCfg<CODEC>::kWaves) void k_cz(CzArgs a) {
             } else {
                 // LZ4 / Snappy: byte elements.  Header: lz4 u32 LE length; snappy varint length.
                 uint32_t hdr = 0;
-                if (first) hdr = CODEC == SDB_CODEC_LZ4 ? 4 : (n < 128 ? 1 : (n < 16384 ? 2 : (n < (1u << 21) ? 3 : 4)));
+                if (first) hdr = CODEC == SDB_CODEC_LZ4 ? 4 : snappy_varint_bytes(n);
                 if (first && l == 0) {
                     if (CODEC == SDB_CODEC_LZ4) {
                         out[0] = (uint8_t)n; out[1] = (uint8_t)(n >> 8); out[2] = (uint8_t)(n >> 16); out[3] = (uint8_t)(n >> 24);
@@ -1959,6 +1984,12 @@ __global__ __launch_bounds__(64 * CzCfg<CODEC>::kWaves) void k_cz(CzArgs a) {
                     for (uint32_t x = l; x < lit; x += 64) out[p + x] = in[carry_pos + x];
                     m = p + lit;
                 }
+                // snappy: short copies after short literals (and a 3-byte literal tag per window) can add up to
+                // more than one literal element of the whole block; the slot bound counts on the shorter one
+                if (CODEC == SDB_CODEC_SNAPPY && last && opos + m > snappy_varint_bytes(n) + snappy_literal_tag_bytes(n) + n) {
+                    fallback = true;
+                    break;
+                }
             }
             wsync();
             CZ_MARK(3, kt);
@@ -2000,7 +2031,7 @@ __global__ __launch_bounds__(64 * CzCfg<CODEC>::kWaves) void k_cz(CzArgs a) {
             }
             w0 = next_w0;
         }
-        if (fallback && l == 0) {  // lz4 only: one literal-only sequence, by one lane
+        if (fallback && l == 0) {  // lz4 / snappy: one literal-only sequence, by one lane
             const uint32_t m = cz_literal_only(CODEC, src, n, slot);
             uint32_t c = 0xFFFFFFFFu;
             for (uint32_t i = 0; i < m; i++) c = (c >> 8) ^ c_crc.t[0][(c ^ slot[i]) & 0xFF];

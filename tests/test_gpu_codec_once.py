@@ -167,10 +167,13 @@ def _device_compressed(codec, data, block_off):
 
 @pytest.mark.parametrize("slot", [8, 2048, 4160])
 def test_once_zlib_wide_pass(slot):
-    """The wide pass (every lane a decoder against the fixed code's shared tables): blocks the device write
-    side compressed (fixed-Huffman / stored deflate), alone and interleaved with Python-zlib blocks (dynamic
-    Huffman, listed for the per-decoder-table pass), at slots every block, some blocks and no block
-    overflows: once == the oracle, and the bytes == the uncompressed blocks."""
+    """The wide pass (every lane a decoder against the fixed code's shared tables) and its hand-over: blocks
+    the device write side compressed (a dynamic-Huffman, fixed-Huffman or stored deflate block per window,
+    whichever is shortest: on these SST blocks mostly dynamic, which the wide pass lists for the
+    per-decoder-table pass), alone and interleaved with Python-zlib blocks (dynamic Huffman, listed too), at
+    slots every block, some blocks and no block overflows: once == the oracle, and the bytes == the
+    uncompressed blocks.  Which streams stay in the wide pass and which leave it, and where, is pinned by
+    test_once_zlib_wide_pass_block_kinds."""
     b = datasets.d1(n=20000, sst_index=3)
     enc = O.encode_sst(b, O.params(block_size=4096, bloom_bits_per_key=0))
     nb = len(enc.block_off) - 1
@@ -195,3 +198,50 @@ def test_once_zlib_wide_pass(slot):
     c3 = np.frombuffer(b"".join(parts2), np.uint8).copy()
     o3 = np.cumsum([0] + [len(x) for x in parts2]).astype(np.uint64)
     _check(O.CODEC_ZLIB, c3, o3, slot)
+
+
+@pytest.mark.parametrize("slot", [8, 2048, 66000])
+def test_once_zlib_wide_pass_block_kinds(slot):
+    """The wide pass by what the streams are made of (O.stream_stats): Python-zlib streams of fixed-code blocks
+    only (Z_FIXED) and of stored blocks only (level 0) stay in it; default-level streams (but the one zlib itself codes as a fixed block) and the device write
+    side's streams that start with a dynamic block are listed for the per-decoder-table pass at once; device
+    streams whose first windows are stored or fixed-code and a later one dynamic are handed over from inside
+    the wide pass ("a dynamic block further into the stream").  All of them interleaved: once == the oracle,
+    and the bytes == the inputs."""
+    import zlib
+    from . import codec_payloads as P
+    from .test_codec_entropy import payloads
+    mixes = [p for _, p in P.window_mixes()] + [p for n, p in P.degenerate() if n.startswith(("len-", "rand-"))]
+    data, off = P.blocks_of([("", p) for p in mixes])
+    dev, doff = _device_compressed(O.CODEC_ZLIB, np.concatenate([data, np.zeros(64, np.uint8)]), off)
+    device = [dev[int(doff[k]):int(doff[k + 1]) - 4].tobytes() for k in range(len(mixes))]
+    plain = payloads()
+
+    def z(p, level, strategy):
+        c = zlib.compressobj(level, zlib.DEFLATED, 15, 8, strategy)
+        return c.compress(p) + c.flush()
+
+    groups = {"fixed": [(z(p, 6, zlib.Z_FIXED), p) for p in plain],
+              "stored": [(z(p, 0, zlib.Z_DEFAULT_STRATEGY), p) for p in plain],
+              "default": [(z(p, 6, zlib.Z_DEFAULT_STRATEGY), p) for p in plain if len(p) > 64],
+              "device": list(zip(device, mixes))}
+    kinds = {g: [O.stream_stats(O.CODEC_ZLIB, s)["blocks"] for s, _ in v] for g, v in groups.items()}
+    assert all(set(b) == {1} for b in kinds["fixed"]) and all(set(b) == {0} for b in kinds["stored"])
+    # default level: dynamic from the first block on, but for the inputs where zlib itself finds the fixed
+    # code shorter (the 256-value ramp: one fixed block, which stays in the wide pass)
+    assert all(b[0] == 2 or b == [1] for b in kinds["default"])
+    assert sum(b[0] == 2 for b in kinds["default"]) >= 8 and [1] in kinds["default"]
+    stay = [b for b in kinds["device"] if 2 not in b]
+    first = [b for b in kinds["device"] if b[0] == 2]
+    later = [b for b in kinds["device"] if b[0] != 2 and 2 in b]
+    assert stay and first and later, (len(stay), len(first), len(later))
+    assert any(0 in b for b in stay) and any(1 in b for b in stay) and any(b[0] == 0 for b in later)
+    # interleaved: fixed, stored, default, device, fixed, ...
+    order = [groups[g][i] for i in range(max(len(v) for v in groups.values())) for g in groups if i < len(groups[g])]
+    parts = [frame(s) for s, _ in order]
+    comp = np.frombuffer(b"".join(parts), np.uint8).copy()
+    coff = np.cumsum([0] + [len(x) for x in parts]).astype(np.uint64)
+    out, start, end, err, _ = _check(O.CODEC_ZLIB, comp, coff, slot)
+    assert err == NONE
+    for k, (_, p) in enumerate(order):
+        assert out[int(start[k]):int(end[k]) - 4].tobytes() == p, k
