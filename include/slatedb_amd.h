@@ -22,6 +22,9 @@
  *                                 DataBlockIterator ascending (block_iterator.rs:54-101,
  *                                 block_iterator_v2.rs:235-267) — the contract of the public
  *                                 SstFile::read_block (sst_reader.rs:287-309).
+ *   - sdb_sst_scan             -> SstIterator over a BytesRange, drained (sst_iter.rs:64-121, 548-673):
+ *                                 the blocks of partitions_covering_range (partitioned_keyspace.rs:
+ *                                 87-110), clipped to the range, many ranges per call.
  *   - sdb_sst_builder_*        -> host-side mirror of EncodedSsTableBuilder's add()/build()/
  *                                 next_block() call order (sst_builder.rs:224-276), batching
  *                                 entries into a columnar pinned buffer and encoding on the GPU.
@@ -426,6 +429,80 @@ uint64_t sdb_sst_lookup_workspace_bytes(uint64_t num_blocks, uint64_t nkeys);
 sdb_status sdb_sst_lookup(const sdb_sst_view *sst, const uint8_t *key_bytes, const uint64_t *key_off,
                           uint64_t nkeys, int32_t descending, const sdb_lookup_out *out,
                           void *workspace, uint64_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Range scans on one encoded SST (device): an SstIterator over a BytesRange, drained.  The range is
+ * the SstView's (sst_iter.rs:64-121): Db::scan builds it with new_owned(range, ..), Db::get with
+ * for_key, the range key..=key.  Many ranges are scanned by one call:
+ *   1. blocks: range_block = partitions_covering_range(index, start, end) over BlockMeta.first_key
+ *      (partitioned_keyspace.rs:87-110, called at sst_iter.rs:548-552), the Excluded(k) end with k
+ *      equal to a block's index key included (that block is not part of the range); block 0's index
+ *      key is empty.  start above end gives end < start, as the reference's Range would hold it;
+ *   2. entries: every entry of those blocks for which SstView::contains(key) holds (sst_iter.rs:
+ *      97-121, 655-673): one contiguous physical run with every version of every key in the range.
+ *      A range that is empty as a set (start above end, or equal keys with an excluded side) yields
+ *      nothing and reads no block.  Overlapping ranges each get their own copy;
+ *   3. order: ranges in input order.  descending == 0: physical order.  descending != 0: what
+ *      SstIterator::next yields in IterationOrder::Descending (sst_iter.rs:567-651): keys descend and
+ *      the versions of one key stay newest first, because fill_descending_buffer re-reverses each key
+ *      group, across block boundaries too.  This is NOT the order of SDB_DECODE_DESCENDING, which is
+ *      the block iterator's plain reverse (oldest version of a key first);
+ *   4. errors: every block of range_block is bounds- and CRC-checked (format/sst.rs:1029-1038) and its
+ *      rows parsed (flags, varints, as sdb_decode_blocks reports them) before a row is used;
+ *      range_status[r] is the status of the lowest-index failing block of range r, and a failing
+ *      range contributes zero entries.  That is all or nothing per range, like SDB_DECODE_FAIL_FAST;
+ *      the reference would yield the entries ahead of the bad block and then fail.  Other ranges are
+ *      unaffected; summary.status is the status of the lowest-numbered failing range.  A V2 block
+ *      whose restart table cannot be followed is SDB_CORRUPT_BLOCK in descending mode, as in
+ *      SDB_DECODE_DESCENDING (block_iterator_v2.rs:76);
+ *   5. capacity: the summary always holds the totals the call needs.  When num_entries > cap_entries
+ *      or key_bytes > key_arena_cap, summary.status is SDB_LIMIT_EXCEEDED and no column byte is
+ *      written; range_entry_start, range_block and range_status are still valid, so the caller can
+ *      size the columns and call again.
+ * Host-detectable errors are returned directly (NULL pointers, a short workspace: SDB_INVALID_ARGUMENT).
+ * A bound kind above 2 is SDB_INVALID_ARGUMENT too: from the call when no device is present (the
+ * arrays are then host memory), otherwise as that range's range_status (the kinds live in device
+ * memory, and the call does not synchronise).  n == 0 or num_blocks == 0 is SDB_OK with every range
+ * empty, the summary zeroed and range_entry_start all 0.  Compressed data sections are decompressed
+ * first (sdb_decompress_blocks_once).
+ * ------------------------------------------------------------------------------------------- */
+enum { SDB_BOUND_UNBOUNDED = 0, SDB_BOUND_INCLUDED = 1, SDB_BOUND_EXCLUDED = 2 };  /* std::ops::Bound */
+typedef struct sdb_scan_ranges {    /* device pointers; range r = (start bound, end bound) */
+    uint64_t n;
+    const uint8_t *start_bytes;     /* start key of range r = */
+    const uint64_t *start_off;      /*   start_bytes[start_off[r] .. start_off[r + 1]); ignored when UNBOUNDED */
+    const uint8_t *start_kind;      /* n: SDB_BOUND_* */
+    const uint8_t *end_bytes;
+    const uint64_t *end_off;        /* n + 1 */
+    const uint8_t *end_kind;        /* n */
+} sdb_scan_ranges;
+typedef struct sdb_scan_summary {
+    uint64_t num_entries;           /* totals the call needs (also when they exceed the capacities) */
+    uint64_t key_bytes;
+    uint64_t num_failed_ranges;
+    uint64_t blocks_read;           /* distinct blocks checked and parsed */
+    int32_t status;
+    uint32_t pad;
+} sdb_scan_summary;
+typedef struct sdb_scan_out {       /* device arrays */
+    uint64_t *range_entry_start;    /* n + 1: range r's entries are [res[r], res[r + 1]) */
+    uint32_t *range_block;          /* 2 n: start, end of range r's block range */
+    int32_t *range_status;          /* n */
+    uint8_t *key_arena;             /* full keys restored, as sdb_decoded_out */
+    uint64_t key_arena_cap;
+    uint64_t *key_off;              /* cap_entries + 1 */
+    uint64_t *val_off;              /* the value: sst->data[val_off .. val_off + val_len) (tombstone: 0, 0) */
+    uint32_t *val_len;
+    uint64_t *seq;
+    uint8_t *flags;                 /* RowFlags as the iterator returns them */
+    int64_t *create_ts;             /* valid iff flags & HAS_CREATE_TS */
+    int64_t *expire_ts;             /* valid iff flags & HAS_EXPIRE_TS */
+    uint64_t cap_entries;
+    sdb_scan_summary *summary;      /* device-writable */
+} sdb_scan_out;
+uint64_t sdb_sst_scan_workspace_bytes(uint64_t num_blocks, uint64_t nranges);
+sdb_status sdb_sst_scan(const sdb_sst_view *sst, const sdb_scan_ranges *ranges, int32_t descending,
+                        const sdb_scan_out *out, void *workspace, uint64_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Compaction (device): the output side of CompactionExecutor::run_subcompaction_merge

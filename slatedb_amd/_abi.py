@@ -142,6 +142,33 @@ class LookupOut(C.Structure):
     ]
 
 
+BOUND_UNBOUNDED, BOUND_INCLUDED, BOUND_EXCLUDED = 0, 1, 2  # std::ops::Bound of a scan range
+
+
+class ScanRanges(C.Structure):
+    _fields_ = [
+        ("n", C.c_uint64), ("start_bytes", C.c_void_p), ("start_off", C.c_void_p), ("start_kind", C.c_void_p),
+        ("end_bytes", C.c_void_p), ("end_off", C.c_void_p), ("end_kind", C.c_void_p),
+    ]
+
+
+class ScanSummary(C.Structure):
+    _fields_ = [
+        ("num_entries", C.c_uint64), ("key_bytes", C.c_uint64), ("num_failed_ranges", C.c_uint64),
+        ("blocks_read", C.c_uint64), ("status", C.c_int32), ("pad", C.c_uint32),
+    ]
+
+
+class ScanOut(C.Structure):
+    _fields_ = [
+        ("range_entry_start", C.c_void_p), ("range_block", C.c_void_p), ("range_status", C.c_void_p),
+        ("key_arena", C.c_void_p), ("key_arena_cap", C.c_uint64), ("key_off", C.c_void_p),
+        ("val_off", C.c_void_p), ("val_len", C.c_void_p), ("seq", C.c_void_p), ("flags", C.c_void_p),
+        ("create_ts", C.c_void_p), ("expire_ts", C.c_void_p), ("cap_entries", C.c_uint64),
+        ("summary", C.c_void_p),
+    ]
+
+
 class Run(C.Structure):
     _fields_ = [
         ("n", C.c_uint64), ("key_arena", C.c_void_p), ("key_off", C.c_void_p),
@@ -248,6 +275,9 @@ SIGNATURES = {
     "sdb_sst_lookup_workspace_bytes": (C.c_uint64, [C.c_uint64, C.c_uint64]),
     "sdb_sst_lookup": (C.c_int, [C.POINTER(SstView), C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32,
                                  C.POINTER(LookupOut), C.c_void_p, C.c_uint64, C.c_void_p]),
+    "sdb_sst_scan_workspace_bytes": (C.c_uint64, [C.c_uint64, C.c_uint64]),
+    "sdb_sst_scan": (C.c_int, [C.POINTER(SstView), C.POINTER(ScanRanges), C.c_int32, C.POINTER(ScanOut),
+                               C.c_void_p, C.c_uint64, C.c_void_p]),
     "sdb_merge_runs_workspace_bytes": (C.c_uint64, [C.POINTER(Run), C.c_uint32]),
     "sdb_merge_runs": (C.c_int, [C.POINTER(Run), C.c_uint32, C.POINTER(Retention), C.POINTER(MergedOut),
                                  C.c_void_p, C.c_uint64, C.c_void_p]),

@@ -32,6 +32,9 @@ struct LookupArgs {
 };
 uint64_t lookup_workspace_bytes(uint64_t num_blocks, uint64_t nkeys);
 hipError_t launch_lookup(LookupArgs a, hipStream_t st);
+uint64_t scan_workspace_bytes(uint64_t num_blocks, uint64_t nranges);
+hipError_t launch_scan(const sdb_sst_view &v, const sdb_scan_ranges &r, uint32_t desc, const sdb_scan_out &out, uint8_t *w,
+                       hipStream_t st);
 }  // namespace sdb
 
 using namespace sdb;
@@ -597,6 +600,38 @@ sdb_status sdb_sst_lookup(const sdb_sst_view *sst, const uint8_t *key_bytes, con
     w += (sst->num_blocks + 256) & ~255ull;
     a.bstat = (int32_t *)w;
     if (launch_lookup(a, S(stream)) != hipSuccess) return SDB_DEVICE_ERROR;
+    return SDB_OK;
+}
+
+uint64_t sdb_sst_scan_workspace_bytes(uint64_t num_blocks, uint64_t nranges) {
+    return scan_workspace_bytes(num_blocks, nranges) + 256;
+}
+
+sdb_status sdb_sst_scan(const sdb_sst_view *sst, const sdb_scan_ranges *ranges, int32_t descending,
+                        const sdb_scan_out *out, void *workspace, uint64_t workspace_bytes, void *stream) {
+    if (!sst || !ranges || !out) return SDB_INVALID_ARGUMENT;
+    if (sst->sst_version != 1 && sst->sst_version != 2) return SDB_INVALID_VERSION;
+    if (sst->num_blocks >= 0xFFFFFFFFull) return SDB_LIMIT_EXCEEDED;
+    const uint64_t n = ranges->n;
+    if (sst->num_blocks && (!sst->data || !sst->block_off || !sst->index_keys || !sst->index_key_off))
+        return SDB_INVALID_ARGUMENT;
+    if (!out->summary || !out->range_entry_start) return SDB_INVALID_ARGUMENT;
+    if (n && (!ranges->start_bytes || !ranges->start_off || !ranges->start_kind || !ranges->end_bytes ||
+              !ranges->end_off || !ranges->end_kind || !out->range_block || !out->range_status))
+        return SDB_INVALID_ARGUMENT;
+    if (!out->key_off || (out->key_arena_cap && !out->key_arena)) return SDB_INVALID_ARGUMENT;
+    if (out->cap_entries && (!out->val_off || !out->val_len || !out->seq || !out->flags || !out->create_ts ||
+                             !out->expire_ts))
+        return SDB_INVALID_ARGUMENT;
+    if (!workspace || workspace_bytes < sdb_sst_scan_workspace_bytes(sst->num_blocks, n)) return SDB_INVALID_ARGUMENT;
+    if (!device_ok()) {  // no device: the arrays are host memory, so the kinds can be checked here
+        for (uint64_t r = 0; r < n; r++)
+            if (ranges->start_kind[r] > SDB_BOUND_EXCLUDED || ranges->end_kind[r] > SDB_BOUND_EXCLUDED)
+                return SDB_INVALID_ARGUMENT;
+        return SDB_DEVICE_ERROR;
+    }
+    uint8_t *w = (uint8_t *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    if (launch_scan(*sst, *ranges, descending ? 1u : 0u, *out, w, S(stream)) != hipSuccess) return SDB_DEVICE_ERROR;
     return SDB_OK;
 }
 

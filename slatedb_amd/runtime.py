@@ -700,6 +700,81 @@ def sst_lookup_device(view_tensors, key_bytes, key_off, nkeys, descending=False,
     return res
 
 
+SCAN_COLUMNS = (("val_off", "int64"), ("val_len", "int32"), ("seq", "int64"), ("flags", "uint8"),
+                ("create_ts", "int64"), ("expire_ts", "int64"))
+
+
+def scan_ranges_columnar(ranges):
+    """[(start, start_kind, end, end_kind), ...] (keys: bytes or None, kinds: _abi.BOUND_*) -> the host
+    arrays of sdb_scan_ranges: dict of start_bytes, start_off, start_kind, end_bytes, end_off, end_kind."""
+    n = len(ranges)
+    out = {}
+    for side, ki, kk in (("start", 0, 1), ("end", 2, 3)):
+        keys = [bytes(r[ki] or b"") for r in ranges]
+        off = np.zeros(n + 1, np.uint64)
+        if n:
+            off[1:] = np.cumsum([len(k) for k in keys])
+        out[side + "_bytes"] = np.frombuffer(b"".join(keys) or b"\0", np.uint8).copy()
+        out[side + "_off"] = off
+        out[side + "_kind"] = np.array([int(r[kk]) for r in ranges] or [0], np.uint8)
+    return out
+
+
+def sst_scan_device(view_tensors, ranges, descending=False, stream=None, cap_entries=None, key_cap=None):
+    """sdb_sst_scan over device tensors.  view_tensors: as sst_lookup_device.  ranges: a list of (start,
+    start_kind, end, end_kind), or a dict of device tensors named as scan_ranges_columnar's arrays plus
+    "n".  Returns a dict of device tensors: range_entry_start (n + 1), range_block (2 n), range_status,
+    key_arena, key_off, the SCAN_COLUMNS and summary (the sdb_scan_summary words: num_entries, key_bytes,
+    num_failed_ranges, blocks_read, status).  With cap_entries / key_cap None the call runs once with
+    empty columns, reads the summary (a host synchronisation), allocates exactly and runs again."""
+    import torch
+    vt = view_tensors
+    dev = vt["data"].device
+    if isinstance(ranges, dict):
+        rt, n = ranges, int(ranges["n"])
+    else:
+        n = len(ranges)
+        rt = {}
+        for k, a in scan_ranges_columnar(ranges).items():
+            rt[k] = torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(dev)
+    v = _abi.SstView(vt["data"].data_ptr(), vt["block_off"].data_ptr(), vt["num_blocks"],
+                     vt["index_keys"].data_ptr(), vt["index_key_off"].data_ptr(), None, 0, 0,
+                     int(vt.get("sst_version", 2)), 0)
+    rg = _abi.ScanRanges(n, rt["start_bytes"].data_ptr(), rt["start_off"].data_ptr(), rt["start_kind"].data_ptr(),
+                         rt["end_bytes"].data_ptr(), rt["end_off"].data_ptr(), rt["end_kind"].data_ptr())
+    res = {"range_entry_start": torch.zeros(n + 1, dtype=torch.int64, device=dev),
+           "range_block": torch.zeros(max(2 * n, 1), dtype=torch.int32, device=dev),
+           "range_status": torch.zeros(max(n, 1), dtype=torch.int32, device=dev),
+           "summary": torch.zeros(5, dtype=torch.int64, device=dev)}
+    wsb = lib().sdb_sst_scan_workspace_bytes(vt["num_blocks"], n)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+
+    def run(ce, kc):
+        res["key_arena"] = torch.zeros(max(kc, 1), dtype=torch.uint8, device=dev)
+        res["key_off"] = torch.zeros(ce + 1, dtype=torch.int64, device=dev)
+        for f, dt in SCAN_COLUMNS:
+            res[f] = torch.zeros(max(ce, 1), dtype=getattr(torch, dt), device=dev)
+        out = _abi.ScanOut(res["range_entry_start"].data_ptr(), res["range_block"].data_ptr(),
+                           res["range_status"].data_ptr(), res["key_arena"].data_ptr(), kc,
+                           res["key_off"].data_ptr(), *[res[f].data_ptr() for f, _ in SCAN_COLUMNS], ce,
+                           res["summary"].data_ptr())
+        st = lib().sdb_sst_scan(C.byref(v), C.byref(rg), int(bool(descending)), C.byref(out), ws.data_ptr(), wsb,
+                                _sp(stream))
+        if st:
+            raise SdbError(st, "sdb_sst_scan")
+
+    if cap_entries is None or key_cap is None:
+        run(0 if cap_entries is None else cap_entries, 0 if key_cap is None else key_cap)
+        _sync(stream, dev)
+        sm = res["summary"].cpu().numpy()
+        if int(sm[4]) & 0xFFFFFFFF == _abi.SDB_LIMIT_EXCEEDED:
+            run(max(int(sm[0]), cap_entries or 0), max(int(sm[1]), key_cap or 0))
+    else:
+        run(cap_entries, key_cap)
+    res["_ws"], res["_ranges"] = ws, rt
+    return res
+
+
 # ------------------------------------------------------------------------------------------------
 # Compaction (sdb_merge_runs / sdb_sst_cuts / sdb_compactor_*)
 # ------------------------------------------------------------------------------------------------
