@@ -25,6 +25,9 @@
  *   - sdb_sst_scan             -> SstIterator over a BytesRange, drained (sst_iter.rs:64-121, 548-673):
  *                                 the blocks of partitions_covering_range (partitioned_keyspace.rs:
  *                                 87-110), clipped to the range, many ranges per call.
+ *   - sdb_lsm_get              -> the on-disk part of Reader::get_key_value_with_options (reader.rs:203-260):
+ *                                 GetIterator::from_lsm_tree (db_iter.rs:79-124) over L0 and the sorted
+ *                                 runs, snapshot-aware (max_seq), many keys per call.
  *   - sdb_sst_builder_*        -> host-side mirror of EncodedSsTableBuilder's add()/build()/
  *                                 next_block() call order (sst_builder.rs:224-276), batching
  *                                 entries into a columnar pinned buffer and encoding on the GPU.
@@ -503,6 +506,105 @@ typedef struct sdb_scan_out {       /* device arrays */
 uint64_t sdb_sst_scan_workspace_bytes(uint64_t num_blocks, uint64_t nranges);
 sdb_status sdb_sst_scan(const sdb_sst_view *sst, const sdb_scan_ranges *ranges, int32_t descending,
                         const sdb_scan_out *out, void *workspace, uint64_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Batched Db::get over a tree of encoded SSTs (device): the on-disk part of
+ * Reader::get_key_value_with_options (reader.rs:203-260).  For a point range the reference builds a
+ * GetIterator (db_iter.rs:48-138, 219-225); over the tree that is GetIterator::from_lsm_tree
+ * (db_iter.rs:79-90): a flat, lazy chain of per-SST iterators, not a merge.  Memtables and the write
+ * batch stay on the host and are consulted first.  Many keys are resolved by one call:
+ *   1. chain: for query q the chain is the concatenation, over the runs in order (newest first), of that
+ *      run's covering SSTs: the contiguous SSTs i of the run with first_key[i] <= key <= last_key[i], in
+ *      run order.  Every L0 SST is a run of one and comes first, newest first (build_l0_point_iters,
+ *      segment_iterator.rs:312-330); then each sorted run contributes tables_covering_point_key(key)
+ *      (build_sr_point_iters, segment_iterator.rs:332-353; db_state.rs:540-596, 662-665): the last SST
+ *      whose start key is <= key if its range holds the key, and the SSTs immediately before it while
+ *      their range still reaches the key (one key's versions straddling the cut between two output
+ *      SSTs).  For a well-formed sorted run the two agree (point_table_idx_covering_key); for a run of
+ *      one it equals searching that SST.  Projected views (visible_range) are out of scope: a view is a
+ *      whole SST;
+ *   2. per SST of the chain: the bloom filter (bloom != NULL) may rule the SST out (sst_iter.rs:201-227);
+ *      an empty bitmap rules every key out, as in sdb_sst_lookup.  Otherwise the block range is
+ *      partitions_covering_range([key, key]) over the SST's index keys.  EVERY block of that range is
+ *      bounds- and CRC-checked (format/sst.rs:1029-1038) and its rows parsed before a row is used; the
+ *      lowest failing block's status fails the query, as in sdb_sst_scan rule 4.  Then the first entry
+ *      in physical order with key == query and seq <= max_seq[q] is taken: versions above the bound are
+ *      dropped before the walk sees them (FilterIterator::new_with_max_seq, filter_iterator.rs:22-48,
+ *      db_iter.rs:354-372), across block boundaries and into the next covering SST of the run, so a
+ *      tombstone above the bound does not stop the search.  No such entry: the walk goes on;
+ *   3. decision (db_iter.rs:102-124): the first entry the first non-empty leaf yields decides the get.
+ *      A value: SDB_GET_FOUND.  A tombstone: SDB_GET_DELETED with value 0, 0; older SSTs are not looked
+ *      at.  A merge operand: SDB_GET_MERGE_OPERAND with status SDB_MERGE_OPERATOR_MISSING
+ *      (MergeOperatorRequiredIterator, merge_operator.rs:213-223); the operand's columns are reported, so
+ *      a caller with an operator knows where the chain begins (resolving operands is out of scope).  An
+ *      exhausted chain: SDB_GET_NOT_FOUND with sst = 0xFFFFFFFF and zeroed columns.  Expiry is NOT
+ *      filtered on this path: expire_ts is returned to the caller, as in KeyValue;
+ *   4. laziness of errors: a query reports a block error only from an SST that lies in its chain at or
+ *      before the SST that decides it; an SST the bloom filter ruled out for that query does not count.
+ *      A corrupt block in an older SST does not fail a query that a newer SST answered.  The call may
+ *      check more blocks than the reference would read (it marks the whole chain before it knows which
+ *      SST decides); those results never surface.  A failing query has state SDB_GET_NOT_FOUND,
+ *      sst = 0xFFFFFFFF and zeroed columns; ssts_read / ssts_filtered count up to and including the SST
+ *      that failed it;
+ *   5. mixed formats: sst_version is per view, V1 and V2 SSTs may share a tree.  A view whose version is
+ *      neither 1 nor 2 gives SDB_INVALID_VERSION to the queries that reach it (in their chain, not
+ *      filtered, not decided before it);
+ *   6. arguments: NULL structs, NULL arrays that a non-empty input needs and a short workspace return
+ *      SDB_INVALID_ARGUMENT from the call (total_blocks or num_ssts >= 0xFFFFFFFF, or nkeys * num_runs over 2^40:
+ *      SDB_LIMIT_EXCEEDED);
+ *      then SDB_DEVICE_ERROR when no device is present.  What lives in device memory is checked on the
+ *      device: block_base that disagrees with the views' num_blocks or with total_blocks, run_start that
+ *      is not monotone from 0 to num_ssts, or key offsets that descend fail EVERY query with
+ *      SDB_INVALID_ARGUMENT through status, and nothing is read through the malformed arrays.  A view
+ *      with blocks and a NULL array fails the queries that reach it the same way.  nkeys == 0,
+ *      num_ssts == 0 or total_blocks == 0 is SDB_OK with every query SDB_GET_NOT_FOUND and the summary
+ *      zeroed (no SST was searched, so no counter moves);
+ *   7. conventions: as every device entry point: no allocation, no synchronisation, launches only on
+ *      `stream`, safe to capture into a HIP graph as a linear sequence; the workspace is reusable by
+ *      the next call without a host-side reset.  Compressed data sections are decompressed first
+ *      (sdb_decompress_blocks_once).
+ * The counters num_found, num_deleted, num_not_found, num_merge and num_failed partition the queries
+ * (num_not_found: exhausted chains with status SDB_OK; num_merge: merge operands, which are not failures).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct sdb_lsm_view {        /* device pointers unless noted */
+    const sdb_sst_view *ssts;        /* DEVICE array of num_ssts views, in search order */
+    uint32_t num_ssts, num_runs;     /* host values */
+    const uint32_t *run_start;       /* num_runs + 1: run r = ssts[run_start[r] .. run_start[r + 1]); runs newest
+                                        first; an L0 SST is a run of one */
+    const uint8_t *first_key_bytes;  /* SsTableInfo.first_entry of SST i = */
+    const uint64_t *first_key_off;   /*   first_key_bytes[first_key_off[i] .. first_key_off[i + 1]) */
+    const uint8_t *last_key_bytes;   /* SsTableInfo.last_entry, same layout */
+    const uint64_t *last_key_off;
+    const uint64_t *block_base;      /* num_ssts + 1: prefix sums of ssts[i].num_blocks */
+    uint64_t total_blocks;           /* host value = block_base[num_ssts]; sizes the workspace and the grids */
+} sdb_lsm_view;
+enum { SDB_GET_NOT_FOUND = 0, SDB_GET_FOUND = 1, SDB_GET_DELETED = 2, SDB_GET_MERGE_OPERAND = 3 };
+typedef struct sdb_get_summary {
+    uint64_t num_found, num_deleted, num_not_found, num_merge, num_failed;
+    uint64_t blocks_checked;         /* distinct blocks the call CRC-checked */
+    int32_t status;                  /* status of the lowest-numbered failing query */
+    uint32_t pad;
+} sdb_get_summary;
+typedef struct sdb_get_out {         /* device arrays, one element per query */
+    uint8_t *state;                  /* SDB_GET_* */
+    int32_t *status;                 /* SDB_OK, a block error, SDB_MERGE_OPERATOR_MISSING, ... */
+    uint32_t *sst;                   /* index into ssts of the SST that decided the get (0xFFFFFFFF: none) */
+    uint32_t *block;                 /* block of the deciding entry inside that SST */
+    uint64_t *val_off;               /* ssts[sst].data[val_off .. val_off + val_len) (tombstone / none: 0, 0) */
+    uint32_t *val_len;
+    uint64_t *seq;
+    uint8_t *flags;                  /* RowFlags as the iterator returns them */
+    int64_t *create_ts;              /* valid iff flags & HAS_CREATE_TS */
+    int64_t *expire_ts;              /* valid iff flags & HAS_EXPIRE_TS */
+    uint32_t *ssts_read;             /* SSTs of the chain whose blocks this query consulted, up to and including
+                                        the deciding one */
+    uint32_t *ssts_filtered;         /* SSTs of the chain before the deciding one that the bloom filter ruled out */
+    sdb_get_summary *summary;        /* device-writable */
+} sdb_get_out;
+uint64_t sdb_lsm_get_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys);
+sdb_status sdb_lsm_get(const sdb_lsm_view *lsm, const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
+                       const uint64_t *max_seq /* device, nkeys; NULL = no bound */, const sdb_get_out *out,
+                       void *workspace, uint64_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Compaction (device): the output side of CompactionExecutor::run_subcompaction_merge

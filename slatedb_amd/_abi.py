@@ -169,6 +169,36 @@ class ScanOut(C.Structure):
     ]
 
 
+GET_NOT_FOUND, GET_FOUND, GET_DELETED, GET_MERGE_OPERAND = 0, 1, 2, 3  # SDB_GET_*
+NO_SST = 0xFFFFFFFF  # sdb_get_out.sst of a query that no SST decided
+
+
+class LsmView(C.Structure):
+    _fields_ = [
+        ("ssts", C.c_void_p), ("num_ssts", C.c_uint32), ("num_runs", C.c_uint32), ("run_start", C.c_void_p),
+        ("first_key_bytes", C.c_void_p), ("first_key_off", C.c_void_p),
+        ("last_key_bytes", C.c_void_p), ("last_key_off", C.c_void_p),
+        ("block_base", C.c_void_p), ("total_blocks", C.c_uint64),
+    ]
+
+
+class GetSummary(C.Structure):
+    _fields_ = [
+        ("num_found", C.c_uint64), ("num_deleted", C.c_uint64), ("num_not_found", C.c_uint64),
+        ("num_merge", C.c_uint64), ("num_failed", C.c_uint64), ("blocks_checked", C.c_uint64),
+        ("status", C.c_int32), ("pad", C.c_uint32),
+    ]
+
+
+class GetOut(C.Structure):
+    _fields_ = [
+        ("state", C.c_void_p), ("status", C.c_void_p), ("sst", C.c_void_p), ("block", C.c_void_p),
+        ("val_off", C.c_void_p), ("val_len", C.c_void_p), ("seq", C.c_void_p), ("flags", C.c_void_p),
+        ("create_ts", C.c_void_p), ("expire_ts", C.c_void_p), ("ssts_read", C.c_void_p),
+        ("ssts_filtered", C.c_void_p), ("summary", C.c_void_p),
+    ]
+
+
 class Run(C.Structure):
     _fields_ = [
         ("n", C.c_uint64), ("key_arena", C.c_void_p), ("key_off", C.c_void_p),
@@ -278,7 +308,10 @@ SIGNATURES = {
     "sdb_sst_scan_workspace_bytes": (C.c_uint64, [C.c_uint64, C.c_uint64]),
     "sdb_sst_scan": (C.c_int, [C.POINTER(SstView), C.POINTER(ScanRanges), C.c_int32, C.POINTER(ScanOut),
                                C.c_void_p, C.c_uint64, C.c_void_p]),
-    "sdb_merge_runs_workspace_bytes": (C.c_uint64, [C.POINTER(Run), C.c_uint32]),
+    "sdb_lsm_get_workspace_bytes": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64]),
+    "sdb_lsm_get": (C.c_int, [C.POINTER(LsmView), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                              C.POINTER(GetOut), C.c_void_p, C.c_uint64, C.c_void_p]),
+    "sdb_merge_runs_workspace_bytes":(C.c_uint64, [C.POINTER(Run), C.c_uint32]),
     "sdb_merge_runs": (C.c_int, [C.POINTER(Run), C.c_uint32, C.POINTER(Retention), C.POINTER(MergedOut),
                                  C.c_void_p, C.c_uint64, C.c_void_p]),
     "sdb_sst_cuts_workspace_bytes": (C.c_uint64, [C.c_uint64, C.POINTER(SstParams)]),

@@ -35,6 +35,9 @@ hipError_t launch_lookup(LookupArgs a, hipStream_t st);
 uint64_t scan_workspace_bytes(uint64_t num_blocks, uint64_t nranges);
 hipError_t launch_scan(const sdb_sst_view &v, const sdb_scan_ranges &r, uint32_t desc, const sdb_scan_out &out, uint8_t *w,
                        hipStream_t st);
+uint64_t get_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys);
+hipError_t launch_get(const sdb_lsm_view &t, const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
+                      const uint64_t *max_seq, const sdb_get_out &out, uint8_t *w, hipStream_t st);
 }  // namespace sdb
 
 using namespace sdb;
@@ -632,6 +635,33 @@ sdb_status sdb_sst_scan(const sdb_sst_view *sst, const sdb_scan_ranges *ranges, 
     }
     uint8_t *w = (uint8_t *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
     if (launch_scan(*sst, *ranges, descending ? 1u : 0u, *out, w, S(stream)) != hipSuccess) return SDB_DEVICE_ERROR;
+    return SDB_OK;
+}
+
+uint64_t sdb_lsm_get_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys) {
+    return get_workspace_bytes(total_blocks, num_ssts, num_runs, nkeys) + 256;
+}
+
+sdb_status sdb_lsm_get(const sdb_lsm_view *lsm, const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
+                       const uint64_t *max_seq, const sdb_get_out *out, void *workspace, uint64_t workspace_bytes,
+                       void *stream) {
+    if (!lsm || !out) return SDB_INVALID_ARGUMENT;
+    if (lsm->total_blocks >= 0xFFFFFFFFull || lsm->num_ssts == 0xFFFFFFFFu) return SDB_LIMIT_EXCEEDED;
+    if (lsm->num_runs && nkeys > (1ull << 40) / lsm->num_runs) return SDB_LIMIT_EXCEEDED;  // a byte per (query, run)
+    if (lsm->num_ssts && (!lsm->ssts || !lsm->run_start || !lsm->first_key_off || !lsm->last_key_off ||
+                          !lsm->block_base || !lsm->first_key_bytes || !lsm->last_key_bytes))
+        return SDB_INVALID_ARGUMENT;
+    if (!out->summary) return SDB_INVALID_ARGUMENT;
+    if (nkeys && (!key_bytes || !key_off || !out->state || !out->status || !out->sst || !out->block || !out->val_off ||
+                  !out->val_len || !out->seq || !out->flags || !out->create_ts || !out->expire_ts || !out->ssts_read ||
+                  !out->ssts_filtered))
+        return SDB_INVALID_ARGUMENT;
+    if (!workspace ||
+        workspace_bytes < sdb_lsm_get_workspace_bytes(lsm->total_blocks, lsm->num_ssts, lsm->num_runs, nkeys))
+        return SDB_INVALID_ARGUMENT;
+    if (!device_ok()) return SDB_DEVICE_ERROR;
+    uint8_t *w = (uint8_t *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    if (launch_get(*lsm, key_bytes, key_off, nkeys, max_seq, *out, w, S(stream)) != hipSuccess) return SDB_DEVICE_ERROR;
     return SDB_OK;
 }
 

@@ -1,0 +1,530 @@
+// sdb_get.hip — batched Db::get over a device-resident tree of encoded SSTs for gfx950.
+//
+// Replaces the on-disk part of Reader::get_key_value_with_options (reader.rs:203-260): the flat, lazy chain
+// of GetIterator::from_lsm_tree (db_iter.rs:79-90, 102-124), many keys per call:
+//   chain       every L0 SST newest first, then per sorted run the SSTs covering the key
+//               (build_l0_point_iters / build_sr_point_iters, segment_iterator.rs:312-353;
+//               tables_covering_point_key, db_state.rs:540-596, 662-665)
+//   per SST     bloom filter (sst_iter.rs:201-227), partitions_covering_range([key, key]), every block of
+//               it CRC-checked (format/sst.rs:1029-1038), versions above max_seq dropped before the walk
+//               sees them (FilterIterator::new_with_max_seq, filter_iterator.rs:22-48, db_iter.rs:354-372)
+//   decision    the first entry the first non-empty leaf yields: value / tombstone / merge operand
+//               (MergeOperatorRequiredIterator, merge_operator.rs:213-223)
+//
+// The unit of work is a (query, run) pair: a run contributes at most a few adjacent SSTs to a chain, and what
+// a run yields for a key (nothing / an entry / an error) does not depend on the runs before it.  Only the
+// last step, picking the first run in order that yields something, is per query.  Per pair the workspace
+// keeps one state byte and a 20-byte record, so it is O(blocks + SSTs + keys x runs) however the chains look.
+//   k_get_validate  one workgroup: run_start / block_base / the views are consistent (else every query
+//                   fails with SDB_INVALID_ARGUMENT and nothing is dereferenced through them); per-SST
+//                   status (version, NULL arrays); resets the summary accumulators
+//   k_get_locate    thread per (query, run): the run's covering SSTs, per SST the filter, the block range
+//                   and the marks at block_base[sst] + block — for the whole chain (eager: which SST
+//                   decides is not known before the blocks are checked).  A thread per pair, not per
+//                   query: the work is dependent loads (binary searches, filter probes), and 64 Ki queries
+//                   alone leave a CU four waves to hide them behind
+//   k_get_check     wave per marked block: bounds + CRC, the body k_lk_check uses (sdb_lookup.h)
+//   k_get_rows      thread per checked block: every row parsed, as sdb_sst_scan's k_sc_block reports them
+//   k_get_walk      thread per (query, run) that has an unfiltered covering SST: block statuses, the seek,
+//                   the versions above max_seq skipped -> the pair's record (entry position or error)
+//   k_get_resolve   thread per query: the first run in order whose record holds an entry or an error decides;
+//                   records behind it are never looked at, so their block errors never surface; one row
+//                   re-parsed for the columns; wave reduction + one atomic per counter and workgroup
+//   k_get_final     the summary
+#include <mutex>
+
+#include "sdb_lookup.h"
+
+namespace sdb {
+
+// no covering SST / its one covering SST filtered / search the run / search its one covering SST, whose block
+// range the record already holds
+enum { kRunNone = 0, kRunFiltered = 1, kRunOpen = 2, kRunOpen1 = 3 };
+// k_get_locate -> k_get_walk (kRunOpen1): sst, block = range start, at = range end.
+// k_get_walk -> k_get_resolve: st != 0: the run fails the query; hit: the entry at `at` (V2: byte offset, V1:
+// index) of block `block` of `sst`; nread / nfilt: the run's SSTs consulted / filtered up to there (a run's
+// covering SSTs are those whose range holds one key: a handful; the counts saturate at 65535).
+struct RunRec {
+    uint32_t sst, block, at;
+    uint16_t nread, nfilt;
+    uint8_t st, hit, pad[2];
+};
+struct GetArgs {
+    sdb_lsm_view t;
+    const uint8_t *key_bytes;
+    const uint64_t *key_off;
+    uint64_t nkeys;
+    const uint64_t *max_seq;
+    sdb_get_out out;
+    uint8_t *mark;             // per tree block: 1 = some chain reads it (cleared by k_get_check)
+    int32_t *bstat;            // per tree block: -1 = not read, else its sdb_status
+    int32_t *sstat;            // per SST: 0, SDB_INVALID_VERSION or SDB_INVALID_ARGUMENT
+    uint8_t *rstate;           // per pair, at run * nkeys + query: kRun*
+    RunRec *rec;               // per pair: see RunRec
+    unsigned long long *acc;   // kAcc* accumulators
+    uint32_t *bad;             // 1 = the tree is malformed
+};
+enum { kAccFound = 0, kAccDeleted, kAccNotFound, kAccMerge, kAccFailed, kAccBlocks, kAccFirstBad, kAccWords };
+
+__global__ __launch_bounds__(256) void k_get_validate(GetArgs a) {
+    const uint32_t ns = a.t.num_ssts, nr = a.t.num_runs;
+    int bad = 0;
+    for (uint32_t i = threadIdx.x; i < ns; i += blockDim.x) {
+        const sdb_sst_view v = a.t.ssts[i];
+        const uint64_t b0 = a.t.block_base[i], b1 = a.t.block_base[i + 1];
+        if (b1 < b0 || b1 - b0 != v.num_blocks || v.num_blocks >= 0xFFFFFFFFull || b1 > a.t.total_blocks) bad = 1;
+        if (i == 0 && b0 != 0) bad = 1;
+        if (i == ns - 1 && b1 != a.t.total_blocks) bad = 1;
+        if (a.t.first_key_off[i + 1] < a.t.first_key_off[i] || a.t.last_key_off[i + 1] < a.t.last_key_off[i]) bad = 1;
+        int st = 0;
+        if (v.sst_version != 1 && v.sst_version != 2) st = SDB_INVALID_VERSION;
+        else if (v.num_blocks && (!v.data || !v.block_off || !v.index_keys || !v.index_key_off)) st = SDB_INVALID_ARGUMENT;
+        a.sstat[i] = st;
+    }
+    for (uint32_t r = threadIdx.x; r < nr; r += blockDim.x) {
+        const uint32_t r0 = a.t.run_start[r], r1 = a.t.run_start[r + 1];
+        if (r1 < r0 || r1 > ns) bad = 1;
+        if (r == 0 && r0 != 0) bad = 1;
+        if (r == nr - 1 && r1 != ns) bad = 1;
+    }
+    bad = __syncthreads_or(bad);
+    if (threadIdx.x == 0) {
+        *a.bad = bad ? 1u : 0u;
+        for (int i = 0; i < kAccWords; i++) a.acc[i] = i == kAccFirstBad ? ~0ull : 0ull;
+    }
+}
+
+struct Key {
+    const uint8_t *t;
+    uint32_t nt;
+};
+SDB_DEV Key key_of(const GetArgs &a, uint64_t q) { return Key{a.key_bytes + a.key_off[q], (uint32_t)(a.key_off[q + 1] - a.key_off[q])}; }
+// sign(SsTableInfo.first_entry / last_entry of SST i cmp key)
+SDB_DEV int cmp_first(const GetArgs &a, uint32_t i, const Key &k) {
+    const uint64_t o = a.t.first_key_off[i];
+    return cmp_bytes(a.t.first_key_bytes + o, (uint32_t)(a.t.first_key_off[i + 1] - o), k.t, k.nt, 0).c;
+}
+SDB_DEV int cmp_last(const GetArgs &a, uint32_t i, const Key &k) {
+    const uint64_t o = a.t.last_key_off[i];
+    return cmp_bytes(a.t.last_key_bytes + o, (uint32_t)(a.t.last_key_off[i + 1] - o), k.t, k.nt, 0).c;
+}
+
+// The covering SSTs [first, last] of run r for key k, in run order: the last SST whose first key is <= k if
+// its range holds k, and the SSTs right before it while their range still reaches k
+// (point_table_idx_covering_key, db_state.rs:578-596).  false: none.  The chain of k is these, over the runs
+// in order.
+SDB_DEV bool get_run(const GetArgs &a, uint32_t r, const Key &k, uint32_t &first, uint32_t &last) {
+    const uint32_t rs = a.t.run_start[r], re = a.t.run_start[r + 1];
+    uint32_t lo = rs, hi = re;  // partition_point(first_key <= k)
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (cmp_first(a, mid, k) <= 0) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo == rs) return false;
+    last = lo - 1;
+    if (cmp_last(a, last, k) < 0) return false;
+    first = last;
+    while (first > rs && cmp_last(a, first - 1, k) >= 0) first--;
+    return true;
+}
+
+// What one SST of the chain means to a key: ruled out by the filter, unusable (st), or the block range
+// partitions_covering_range([k, k]) over its index keys.
+struct Step {
+    bool filtered;
+    int st;
+    uint32_t start, end;
+};
+SDB_DEV Step get_step(const GetArgs &a, const LookupArgs &l, uint32_t i, const Key &k, uint64_t h) {
+    Step s{false, 0, 0, 0};
+    if (l.v.bloom && !bloom_might_contain(l.v.bloom, l.v.bloom_len, l.v.num_probes, h)) {
+        s.filtered = true;
+        return s;
+    }
+    if ((s.st = a.sstat[i])) return s;
+    const uint64_t lt = partition_point(l, k.t, k.nt, false), le = partition_point(l, k.t, k.nt, true);
+    s.start = (uint32_t)(lt > 0 ? lt - 1 : 0);
+    s.end = (uint32_t)(le > 0 ? le : s.start);
+    return s;
+}
+
+__global__ __launch_bounds__(256) void k_get_locate(GetArgs a) {
+    if (*a.bad) return;
+    const uint32_t R = a.t.num_runs;
+    const uint64_t total = a.nkeys * R;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t q = t % a.nkeys;  // pair t = run * nkeys + query: a wave holds neighbouring queries of one run
+        const uint32_t r = (uint32_t)(t / a.nkeys);
+        const Key k = key_of(a, q);
+        uint32_t first, last;
+        uint8_t rs = kRunNone;
+        if (get_run(a, r, k, first, last)) {
+            const uint64_t h = siphash13(k.t, k.nt);  // filter_hash (filter.rs:196-204): one hash for every SST's filter
+            rs = last > first ? kRunOpen : kRunFiltered;  // several covering SSTs: the resolve counts them itself
+            for (uint32_t i = first; i <= last; i++) {
+                LookupArgs l{};
+                l.v = a.t.ssts[i];
+                const Step s = get_step(a, l, i, k, h);
+                if (s.filtered) continue;
+                rs = kRunOpen;
+                if (s.st) continue;
+                const uint64_t base = a.t.block_base[i];
+                for (uint32_t b = s.start; b < s.end; b++) a.mark[base + b] = 1;
+                if (last == first) {
+                    rs = kRunOpen1;
+                    a.rec[t] = RunRec{i, s.start, s.end, 0, 0, 0, 0, {0, 0}};
+                }
+            }
+        }
+        a.rstate[t] = rs;
+    }
+}
+
+// The SST of tree block k: the last i with block_base[i] <= k.
+SDB_DEV uint32_t sst_of_block(const GetArgs &a, uint64_t k) {
+    uint32_t lo = 0, hi = a.t.num_ssts;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (a.t.block_base[mid] <= k) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(kLkThreads) void k_get_check(GetArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    if (*a.bad) return;
+    crc_tables_to_lds((lu32 *)smem);
+    __syncthreads();
+    const uint32_t wave = threadIdx.x >> 6, l = (uint32_t)lane_id();
+    lu8 *img = lk_wave_image(smem, wave, l);
+    const uint64_t nw = (uint64_t)gridDim.x * (blockDim.x >> 6);
+    for (uint64_t k = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wave; k < a.t.total_blocks; k += nw) {
+        if (!a.mark[k]) continue;
+        const uint32_t i = sst_of_block(a, k);
+        const uint64_t b = k - a.t.block_base[i];
+        const uint8_t *data = a.t.ssts[i].data;
+        const uint64_t *off = a.t.ssts[i].block_off;
+        const int st = lk_check_block(data, off[b], off[b + 1], img, l);
+        if (l == 0) {
+            a.bstat[k] = st;
+            a.mark[k] = 0;  // ready for the next call
+        }
+    }
+}
+
+// Every row of a checked block parsed (flags, varints, lengths), as sdb_sst_scan reports them.
+__global__ __launch_bounds__(64) void k_get_rows(GetArgs a) {
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int st = -1;
+    if (k < a.t.total_blocks && !*a.bad) st = a.bstat[k];
+    if (st == 0) {
+        const uint32_t i = sst_of_block(a, k);
+        LookupArgs l{};
+        l.v = a.t.ssts[i];
+        Blk b;
+        st = blk_open(l, k - a.t.block_base[i], b);
+        if (!st && l.v.sst_version == 2) {
+            uint32_t kp, kn, pos = 0, curlen = 0;
+            if (b.count > 0) st = v2_restart_key(b, 0, kp, kn);
+            while (!st && pos < b.data_end) {
+                Row r;
+                if ((st = v2_row(b, pos, r))) break;
+                if (r.sh > curlen) st = SDB_CORRUPT_BLOCK;
+                curlen = r.sh + r.un;
+                pos = r.next;
+            }
+        } else if (!st) {
+            for (uint32_t j = 0; j < b.count && !st; j++) {
+                Row r;
+                st = v1_row(b, j, r);
+            }
+        }
+        a.bstat[k] = st;
+    }
+    const unsigned long long read = __ballot(st != -1);
+    if (threadIdx.x == 0 && read) atomicAdd(&a.acc[kAccBlocks], (unsigned long long)__popcll(read));
+}
+
+struct Hit {
+    bool ok;
+    uint32_t block, at;
+};
+
+// The first entry of blocks [start, end) of one SST, in physical order, with key == k and seq <= bound.
+SDB_DEV int get_walk(const LookupArgs &l, const Step &s, const Key &k, uint64_t bound, Hit &H) {
+    H.ok = false;
+    const bool v2 = l.v.sst_version == 2;
+    for (uint32_t blk = s.start; blk < s.end; blk++) {
+        Blk b;
+        if (int st = blk_open(l, blk, b)) return st;
+        if (b.count == 0) continue;
+        Pos P;
+        if (blk == s.start) {  // the seek; later blocks are entered at their first entry
+            if (int st = v2 ? v2_seek_asc(b, k.t, k.nt, P) : v1_seek(b, k.t, k.nt, false, P)) return st;
+            if (!P.ok) continue;
+        } else {
+            P.ok = true;
+            P.at = v2 ? boff(b, 0) : 0;
+            if (v2) {
+                uint32_t kp, kn;
+                if (int st = v2_restart_key(b, 0, kp, kn)) return st;
+                if (P.at >= b.data_end) continue;
+                P.key = cmp_bytes(b.d + kp, kn, k.t, k.nt, 0);
+            } else if (int st = v1_cmp(b, 0, k.t, k.nt, P.key)) {
+                return st;
+            }
+        }
+        for (;;) {  // entries from P on while they hold the key
+            if (P.key.c > 0) return 0;  // past the key: this SST has no visible version
+            Row r;
+            if (int st = v2 ? v2_row(b, P.at, r) : v1_row(b, P.at, r)) return st;
+            if (P.key.c == 0 && r.seq <= bound) {
+                H.ok = true;
+                H.block = blk;
+                H.at = P.at;
+                return 0;
+            }
+            if (v2) {
+                if (r.next >= b.data_end) break;
+                uint32_t p = r.next, sh, un, vl;
+                if (!rdv(b.d, b.data_end, p, sh) || !rdv(b.d, b.data_end, p, un) || !rdv(b.d, b.data_end, p, vl) ||
+                    sh > P.key.len || (uint64_t)p + un > b.data_end)
+                    return SDB_CORRUPT_BLOCK;
+                P.key = cmp_next(P.key, sh, b.d + p, un, k.t, k.nt);
+                P.at = r.next;
+            } else {
+                if (++P.at >= b.count) break;
+                if (int st = v1_cmp(b, P.at, k.t, k.nt, P.key)) return st;
+            }
+        }
+    }
+    return 0;
+}
+
+__global__ __launch_bounds__(64) void k_get_walk(GetArgs a) {
+    if (*a.bad) return;
+    const uint32_t R = a.t.num_runs;
+    const uint64_t total = a.nkeys * R;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x) {
+        const uint8_t rs = a.rstate[t];
+        if (rs != kRunOpen && rs != kRunOpen1) continue;
+        const uint64_t q = t % a.nkeys;
+        const Key k = key_of(a, q);
+        const uint64_t bound = a.max_seq ? a.max_seq[q] : ~0ull;
+        int st = 0;
+        uint32_t sst = 0xFFFFFFFFu, nread = 0, nfilt = 0;
+        Hit H;
+        H.ok = false;
+        auto search = [&](uint32_t i, const LookupArgs &l, const Step &s) {  // false: the run is decided
+            if (s.end <= s.start) return true;
+            nread++;
+            const uint64_t base = a.t.block_base[i];
+            for (uint32_t b = s.start; b < s.end && !st; b++) st = a.bstat[base + b];  // the lowest failing block
+            if (st < 0) st = SDB_INVALID_ARGUMENT;  // unreachable: locate marked this range
+            if (!st) st = get_walk(l, s, k, bound, H);
+            if (H.ok) sst = i;
+            return !st && !H.ok;
+        };
+        if (rs == kRunOpen1) {
+            const RunRec in = a.rec[t];
+            LookupArgs l{};
+            l.v = a.t.ssts[in.sst];
+            search(in.sst, l, Step{false, 0, in.block, in.at});
+        } else {
+            const uint64_t h = siphash13(k.t, k.nt);
+            uint32_t first = 0, last = 0;
+            bool go = get_run(a, (uint32_t)(t / a.nkeys), k, first, last);
+            for (uint32_t i = first; go && i <= last; i++) {
+                LookupArgs l{};
+                l.v = a.t.ssts[i];
+                const Step s = get_step(a, l, i, k, h);
+                if (s.filtered) nfilt++;
+                else if ((st = s.st)) go = false;
+                else go = search(i, l, s);
+            }
+        }
+        RunRec out{sst, H.ok ? H.block : 0, H.ok ? H.at : 0, (uint16_t)(nread > 0xFFFF ? 0xFFFF : nread),
+                   (uint16_t)(nfilt > 0xFFFF ? 0xFFFF : nfilt), (uint8_t)st, (uint8_t)(H.ok && !st), {0, 0}};
+        a.rec[t] = out;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_get_resolve(GetArgs a) {
+    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = q < a.nkeys;
+    int st = 0;
+    uint32_t state = SDB_GET_NOT_FOUND;
+    if (live) {
+        uint32_t sst = 0xFFFFFFFFu, nread = 0, nfilt = 0;
+        Hit H;
+        H.ok = false;
+        Row r{};
+        uint64_t vbase = 0;
+        if (*a.bad) {
+            st = SDB_INVALID_ARGUMENT;
+        } else {
+            const uint32_t R = a.t.num_runs;
+            for (uint32_t j = 0; j < R && !st && !H.ok; j++) {  // the first run in order that yields something
+                const uint8_t rs = a.rstate[j * a.nkeys + q];
+                if (rs == kRunFiltered) nfilt++;
+                if (rs != kRunOpen && rs != kRunOpen1) continue;
+                const RunRec x = a.rec[j * a.nkeys + q];
+                nread += x.nread;
+                nfilt += x.nfilt;
+                st = x.st;
+                if (!st && x.hit) {
+                    H.ok = true;
+                    H.block = x.block;
+                    H.at = x.at;
+                    sst = x.sst;
+                }
+            }
+            if (H.ok) {  // the row again, for its columns
+                LookupArgs l{};
+                l.v = a.t.ssts[sst];
+                Blk b;
+                if (!(st = blk_open(l, H.block, b))) st = l.v.sst_version == 2 ? v2_row(b, H.at, r) : v1_row(b, H.at, r);
+                vbase = b.base;
+            }
+        }
+        if (st) H.ok = false;
+        if (H.ok) {
+            if (r.flags & SDB_FLAG_TOMBSTONE) {
+                state = SDB_GET_DELETED;
+                r.vl = 0;
+            } else if (r.flags & SDB_FLAG_MERGE_OPERAND) {
+                state = SDB_GET_MERGE_OPERAND;
+                st = SDB_MERGE_OPERATOR_MISSING;
+            } else {
+                state = SDB_GET_FOUND;
+            }
+        } else {
+            sst = 0xFFFFFFFFu;
+        }
+        a.out.state[q] = (uint8_t)state;
+        a.out.status[q] = st;
+        a.out.sst[q] = sst;
+        a.out.block[q] = H.ok ? H.block : 0;
+        a.out.val_off[q] = H.ok && r.vl ? vbase + r.vpos : 0;
+        a.out.val_len[q] = H.ok ? r.vl : 0;
+        a.out.seq[q] = H.ok ? r.seq : 0;
+        a.out.flags[q] = H.ok ? r.flags : 0;
+        a.out.create_ts[q] = H.ok && (r.flags & SDB_FLAG_HAS_CREATE_TS) ? r.cts : 0;
+        a.out.expire_ts[q] = H.ok && (r.flags & SDB_FLAG_HAS_EXPIRE_TS) ? r.ets : 0;
+        a.out.ssts_read[q] = nread;
+        a.out.ssts_filtered[q] = nfilt;
+    }
+    const bool failed = live && st != 0 && state == SDB_GET_NOT_FOUND;
+    const unsigned long long nf = __ballot(live && state == SDB_GET_FOUND), nd = __ballot(live && state == SDB_GET_DELETED),
+                             nm = __ballot(live && state == SDB_GET_MERGE_OPERAND), nx = __ballot(failed),
+                             nn = __ballot(live && state == SDB_GET_NOT_FOUND && !failed);
+    if (threadIdx.x == 0) {
+        if (nf) atomicAdd(&a.acc[kAccFound], (unsigned long long)__popcll(nf));
+        if (nd) atomicAdd(&a.acc[kAccDeleted], (unsigned long long)__popcll(nd));
+        if (nm) atomicAdd(&a.acc[kAccMerge], (unsigned long long)__popcll(nm));
+        if (nn) atomicAdd(&a.acc[kAccNotFound], (unsigned long long)__popcll(nn));
+        if (nx) atomicAdd(&a.acc[kAccFailed], (unsigned long long)__popcll(nx));
+    }
+    if (failed) atomicMin(&a.acc[kAccFirstBad], (unsigned long long)(q << 8 | (uint64_t)st));
+}
+
+__global__ void k_get_final(GetArgs a) {
+    if (threadIdx.x != 0) return;
+    sdb_get_summary s{};
+    s.num_found = a.acc[kAccFound];
+    s.num_deleted = a.acc[kAccDeleted];
+    s.num_not_found = a.acc[kAccNotFound];
+    s.num_merge = a.acc[kAccMerge];
+    s.num_failed = a.acc[kAccFailed];
+    s.blocks_checked = a.acc[kAccBlocks];
+    s.status = a.acc[kAccFirstBad] == ~0ull ? 0 : (int32_t)(a.acc[kAccFirstBad] & 0xFF);
+    *a.out.summary = s;
+}
+
+struct GetWorkspace {
+    uint64_t mark, bstat, sstat, rstate, rec, misc, total;
+};
+static GetWorkspace get_workspace_layout(uint64_t tb, uint64_t ns, uint64_t nr, uint64_t n) {
+    GetWorkspace w{};
+    uint64_t off = 0;
+    auto take = [&](uint64_t bytes) {
+        const uint64_t r = off;
+        off += (bytes + 255) & ~255ull;
+        return r;
+    };
+    w.mark = take(tb + 1);
+    w.bstat = take(4 * (tb + 1));
+    w.sstat = take(4 * (ns + 1));
+    w.rstate = take(n * nr + 1);
+    w.rec = take(sizeof(RunRec) * (n * nr + 1));
+    w.misc = take(8 * kAccWords + 8);
+    w.total = off;
+    return w;
+}
+
+uint64_t get_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys) {
+    return get_workspace_layout(total_blocks, num_ssts, num_runs, nkeys).total;
+}
+
+hipError_t launch_get(const sdb_lsm_view &t, const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
+                      const uint64_t *max_seq, const sdb_get_out &out, uint8_t *w, hipStream_t st) {
+    const uint64_t tb = t.total_blocks, n = nkeys;
+    hipError_t e;
+    if ((e = hipMemsetAsync(out.summary, 0, sizeof(sdb_get_summary), st)) != hipSuccess) return e;
+    if (n == 0) return hipSuccess;
+    if (t.num_ssts == 0 || t.num_runs == 0 || tb == 0) {  // nothing to search: every query NOT_FOUND
+        if ((e = hipMemsetAsync(out.state, 0, n, st)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(out.status, 0, 4 * n, st)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(out.sst, 0xFF, 4 * n, st)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(out.block, 0, 4 * n, st)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(out.val_off, 0, 8 * n, st)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(out.val_len, 0, 4 * n, st)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(out.seq, 0, 8 * n, st)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(out.flags, 0, n, st)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(out.create_ts, 0, 8 * n, st)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(out.expire_ts, 0, 8 * n, st)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(out.ssts_read, 0, 4 * n, st)) != hipSuccess) return e;
+        return hipMemsetAsync(out.ssts_filtered, 0, 4 * n, st);
+    }
+    const GetWorkspace L = get_workspace_layout(tb, t.num_ssts, t.num_runs, n);
+    GetArgs a{};
+    a.t = t;
+    a.key_bytes = key_bytes;
+    a.key_off = key_off;
+    a.nkeys = n;
+    a.max_seq = max_seq;
+    a.out = out;
+    a.mark = w + L.mark;
+    a.bstat = (int32_t *)(w + L.bstat);
+    a.sstat = (int32_t *)(w + L.sstat);
+    a.rstate = w + L.rstate;
+    a.rec = (RunRec *)(w + L.rec);
+    a.acc = (unsigned long long *)(w + L.misc);
+    a.bad = (uint32_t *)(w + L.misc + 8 * kAccWords);
+    if ((e = hipMemsetAsync(a.mark, 0, tb, st)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(a.bstat, 0xFF, 4 * tb, st)) != hipSuccess) return e;
+    static std::once_flag once;
+    std::call_once(once, [] {
+        (void)hipFuncSetAttribute((const void *)k_get_check, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLkLds);
+        (void)hipGetLastError();
+    });
+    hipLaunchKernelGGL(k_get_validate, dim3(1), dim3(256), 0, st, a);
+    uint64_t lg = (n * t.num_runs + 255) / 256;  // the kernel strides past this cap
+    if (lg > (1u << 20)) lg = 1u << 20;
+    hipLaunchKernelGGL(k_get_locate, dim3((uint32_t)lg), dim3(256), 0, st, a);
+    uint64_t wgs = (tb + 3) / 4;
+    if (wgs > 4096) wgs = 4096;
+    hipLaunchKernelGGL(k_get_check, dim3((uint32_t)wgs), dim3(kLkThreads), kLkLds, st, a);
+    // the per-block parse and the per-query walk are latency-bound threads: one wave per workgroup spreads them over the CUs
+    hipLaunchKernelGGL(k_get_rows, dim3((uint32_t)((tb + 63) / 64)), dim3(64), 0, st, a);
+    uint64_t wg = (n * t.num_runs + 63) / 64;
+    if (wg > (1u << 22)) wg = 1u << 22;
+    hipLaunchKernelGGL(k_get_walk, dim3((uint32_t)wg), dim3(64), 0, st, a);
+    hipLaunchKernelGGL(k_get_resolve, dim3((uint32_t)((n + 63) / 64)), dim3(64), 0, st, a);
+    hipLaunchKernelGGL(k_get_final, dim3(1), dim3(64), 0, st, a);
+    return hipGetLastError();
+}
+
+}  // namespace sdb

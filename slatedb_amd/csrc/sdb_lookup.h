@@ -349,6 +349,61 @@ SDB_DEV uint64_t partition_point(const LookupArgs &a, const uint8_t *t, uint32_t
     return pp;
 }
 
+// might_contain (filter.rs:124-136) for the filter hash h; an empty bitmap answers false.
+SDB_DEV bool bloom_might_contain(const uint8_t *bloom, uint64_t bloom_len, uint32_t num_probes, uint64_t h) {
+    const uint32_t m = (uint32_t)(bloom_len * 8);
+    if (!m) return false;
+    uint32_t hh = (uint32_t)h % m, d = (uint32_t)(h >> 32) % m;
+    for (uint32_t i = 0; i < num_probes; i++) {
+        d = (uint32_t)(((uint64_t)d + i) % m);
+        if (!((bloom[hh >> 3] >> (hh & 7)) & 1)) return false;
+        hh = (uint32_t)(((uint64_t)hh + d) % m);
+    }
+    return true;
+}
+
+// Block::decode bounds + CRC of the block data[s, e) by one wave (lane l), over the wave's LDS image
+// (kLkImg bytes, 64 zeroed bytes before it): the body of k_lk_check and of the multi-SST k_get_check.
+constexpr uint32_t kLkThreads = 256;
+constexpr uint32_t kLkImg = 4096 + 32;
+constexpr uint32_t kLkLds = kCrcTablesLds + (kLkThreads / 64) * (kLkImg + 64);
+SDB_DEV lu8 *lk_wave_image(uint8_t *smem, uint32_t wave, uint32_t l) {
+    lu8 *img = (lu8 *)smem + kCrcTablesLds + wave * (kLkImg + 64) + 64;
+    if (l < 16) ((lu32 *)(img - 64))[l] = 0;  // zero lead-in of the right-aligned CRC segments
+    return img;
+}
+SDB_DEV int lk_check_block(const uint8_t *data, uint64_t s, uint64_t e, lu8 *img, uint32_t l) {
+    if (e < s || e - s < 6) return SDB_CORRUPT_BLOCK;
+    const uint32_t blen = (uint32_t)(e - s - 4);
+    uint32_t crc;
+    if (blen + 16 <= 4096 && blen >= 4) {
+        const uint32_t p0 = (uint32_t)(s & 15), Lc = p0 + blen;
+        const uint64_t a0 = s & ~15ull;
+        const uint32_t ng = (uint32_t)((((s + blen + 15) & ~15ull) - a0) >> 4);
+        for (uint32_t g = l; g < ng; g += 64) {
+            const uint4 v = ((const uint4 *)(data + a0))[g];
+            u32x4 w;
+            w.x = v.x;
+            w.y = v.y;
+            w.z = v.z;
+            w.w = v.w;
+            ((lu128 *)img)[g] = w;
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (l < p0) img[l] = 0;
+        if (l < 4) img[p0 + l] ^= 0xFF;  // crc32fast's init
+        __builtin_amdgcn_wave_barrier();
+        crc = wave_crc_image_ra(img, Lc);
+        __builtin_amdgcn_wave_barrier();
+    } else {  // large blocks: one lane, byte-wise
+        uint32_t x = 0xFFFFFFFFu;
+        if (l == 0)
+            for (uint32_t i = 0; i < blen; i++) x = c_crc.t[0][(x ^ data[s + i]) & 0xFF] ^ (x >> 8);
+        crc = (uint32_t)__builtin_amdgcn_readfirstlane((int)(x ^ 0xFFFFFFFFu));
+    }
+    return crc != (uint32_t)be_at(data + s + blen, 4) ? SDB_CHECKSUM_MISMATCH : 0;
+}
+
 // One wave per marked block: Block::decode bounds + CRC -> bstat; clears the marks (sdb_lookup.hip).
 hipError_t launch_lk_check(LookupArgs a, hipStream_t st);
 

@@ -27,23 +27,8 @@ __global__ __launch_bounds__(256) void k_lk_locate(LookupArgs a) {
     const uint32_t nt = (uint32_t)(a.key_off[q + 1] - a.key_off[q]);
     uint32_t start = 0, end = 0;
     bool filtered = false;
-    if (a.v.bloom) {  // might_contain (filter.rs:124-136): an empty bitmap answers false
-        const uint32_t m = (uint32_t)(a.v.bloom_len * 8);
-        filtered = true;
-        if (m) {
-            const uint64_t h = siphash13(t, nt);  // filter_hash (filter.rs:196-204)
-            uint32_t hh = (uint32_t)h % m, d = (uint32_t)(h >> 32) % m;
-            filtered = false;
-            for (uint32_t i = 0; i < a.v.num_probes; i++) {
-                d = (uint32_t)(((uint64_t)d + i) % m);
-                if (!((a.v.bloom[hh >> 3] >> (hh & 7)) & 1)) {
-                    filtered = true;
-                    break;
-                }
-                hh = (uint32_t)(((uint64_t)hh + d) % m);
-            }
-        }
-    }
+    // might_contain(filter_hash(key)) (filter.rs:124-136, 196-204)
+    if (a.v.bloom) filtered = !bloom_might_contain(a.v.bloom, a.v.bloom_len, a.v.num_probes, siphash13(t, nt));
     if (!filtered) {  // partitions_covering_range(Included(k), Included(k))
         const uint64_t lt = partition_point(a, t, nt, false), le = partition_point(a, t, nt, true);
         start = (uint32_t)(lt > 0 ? lt - 1 : 0);
@@ -59,52 +44,16 @@ __global__ __launch_bounds__(256) void k_lk_locate(LookupArgs a) {
 }
 
 // One wave per marked block: Block::decode bounds + CRC (the shared wave CRC over an LDS image).
-constexpr uint32_t kLkThreads = 256;
-constexpr uint32_t kLkImg = 4096 + 32;
 __global__ __launch_bounds__(kLkThreads) void k_lk_check(LookupArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     crc_tables_to_lds((lu32 *)smem);
     __syncthreads();
     const uint32_t wave = threadIdx.x >> 6, l = (uint32_t)lane_id();
-    lu8 *img = (lu8 *)smem + kCrcTablesLds + wave * (kLkImg + 64) + 64;
-    if (l < 16) ((lu32 *)(img - 64))[l] = 0;  // zero lead-in of the right-aligned CRC segments
+    lu8 *img = lk_wave_image(smem, wave, l);
     const uint64_t nw = (uint64_t)gridDim.x * (blockDim.x >> 6);
     for (uint64_t k = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wave; k < a.v.num_blocks; k += nw) {
         if (!a.mark[k]) continue;
-        const uint64_t s = a.v.block_off[k], e = a.v.block_off[k + 1];
-        int st = 0;
-        if (e < s || e - s < 6) {
-            st = SDB_CORRUPT_BLOCK;
-        } else {
-            const uint32_t blen = (uint32_t)(e - s - 4);
-            uint32_t crc;
-            if (blen + 16 <= 4096 && blen >= 4) {
-                const uint32_t p0 = (uint32_t)(s & 15), Lc = p0 + blen;
-                const uint64_t a0 = s & ~15ull;
-                const uint32_t ng = (uint32_t)((((s + blen + 15) & ~15ull) - a0) >> 4);
-                for (uint32_t g = l; g < ng; g += 64) {
-                    const uint4 v = ((const uint4 *)(a.v.data + a0))[g];
-                    u32x4 w;
-                    w.x = v.x;
-                    w.y = v.y;
-                    w.z = v.z;
-                    w.w = v.w;
-                    ((lu128 *)img)[g] = w;
-                }
-                __builtin_amdgcn_wave_barrier();
-                if (l < p0) img[l] = 0;
-                if (l < 4) img[p0 + l] ^= 0xFF;  // crc32fast's init
-                __builtin_amdgcn_wave_barrier();
-                crc = wave_crc_image_ra(img, Lc);
-                __builtin_amdgcn_wave_barrier();
-            } else {  // large blocks: one lane, byte-wise
-                uint32_t x = 0xFFFFFFFFu;
-                if (l == 0)
-                    for (uint32_t i = 0; i < blen; i++) x = c_crc.t[0][(x ^ a.v.data[s + i]) & 0xFF] ^ (x >> 8);
-                crc = (uint32_t)__builtin_amdgcn_readfirstlane((int)(x ^ 0xFFFFFFFFu));
-            }
-            if (crc != (uint32_t)be_at(a.v.data + s + blen, 4)) st = SDB_CHECKSUM_MISMATCH;
-        }
+        const int st = lk_check_block(a.v.data, a.v.block_off[k], a.v.block_off[k + 1], img, l);
         if (l == 0) {
             a.bstat[k] = st;
             a.mark[k] = 0;  // ready for the next call
@@ -221,13 +170,12 @@ hipError_t launch_lk_check(LookupArgs a, hipStream_t st) {
     static std::once_flag once;
     std::call_once(once, [] {
         (void)hipFuncSetAttribute((const void *)k_lk_check, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)(kCrcTablesLds + (kLkThreads / 64) * (kLkImg + 64)));
+                                  (int)kLkLds);
         (void)hipGetLastError();
     });
     uint64_t wgs = (a.v.num_blocks + 3) / 4;
     if (wgs > 4096) wgs = 4096;
-    hipLaunchKernelGGL(k_lk_check, dim3((uint32_t)wgs), dim3(kLkThreads), kCrcTablesLds + (kLkThreads / 64) * (kLkImg + 64),
-                       st, a);
+    hipLaunchKernelGGL(k_lk_check, dim3((uint32_t)wgs), dim3(kLkThreads), kLkLds, st, a);
     return hipGetLastError();
 }
 

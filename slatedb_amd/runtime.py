@@ -775,6 +775,88 @@ def sst_scan_device(view_tensors, ranges, descending=False, stream=None, cap_ent
     return res
 
 
+GET_FIELDS = (("state", "uint8"), ("status", "int32"), ("sst", "int32"), ("block", "int32"), ("val_off", "int64"),
+              ("val_len", "int32"), ("seq", "int64"), ("flags", "uint8"), ("create_ts", "int64"),
+              ("expire_ts", "int64"), ("ssts_read", "int32"), ("ssts_filtered", "int32"))
+GET_SUMMARY = ("num_found", "num_deleted", "num_not_found", "num_merge", "num_failed", "blocks_checked", "status")
+
+
+def keys_columnar(keys):
+    """[bytes, ...] -> (key_bytes uint8, key_off uint64) host arrays."""
+    off = np.zeros(len(keys) + 1, np.uint64)
+    if keys:
+        off[1:] = np.cumsum([len(k) for k in keys])
+    return np.frombuffer(b"".join(keys) or b"\0", np.uint8).copy(), off
+
+
+def lsm_tree_device(views, runs, device=None):
+    """The device-resident sdb_lsm_view of a tree.  views: per-SST tensor dicts in search order, as
+    sst_lookup_device takes them plus first_key / last_key (bytes: SsTableInfo.first_entry / last_entry;
+    absent or None for an SST without entries).  runs: the number of SSTs of each run, newest run first
+    (an L0 SST is a run of one).  Returns a dict: "lsm" (the _abi.LsmView), num_ssts, num_runs,
+    total_blocks and, under "_"-prefixed keys, the device arrays it points into."""
+    import torch
+    ns = len(views)
+    assert sum(runs) == ns and all(r >= 0 for r in runs), "runs must partition the views"
+    dev = device if device is not None else (views[0]["data"].device if ns else "cuda")
+    arr = (_abi.SstView * max(ns, 1))()
+    for i, vt in enumerate(views):
+        bloom = vt.get("bloom")
+        arr[i] = _abi.SstView(vt["data"].data_ptr(), vt["block_off"].data_ptr(), vt["num_blocks"],
+                              vt["index_keys"].data_ptr(), vt["index_key_off"].data_ptr(),
+                              bloom.data_ptr() if bloom is not None else None,
+                              int(vt.get("bloom_len", 0)) if bloom is not None else 0, int(vt.get("num_probes", 0)),
+                              int(vt.get("sst_version", 2)), 0)
+    dv = lambda a: torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(dev)  # noqa: E731
+    fkb, fko = keys_columnar([bytes(vt.get("first_key") or b"") for vt in views])
+    lkb, lko = keys_columnar([bytes(vt.get("last_key") or b"") for vt in views])
+    t = {"_views": views,
+         "_ssts": dv(np.frombuffer(bytes(arr), np.uint8).copy()),
+         "_run_start": dv(np.concatenate([[0], np.cumsum(runs)]).astype(np.int32)),
+         "_first_key_bytes": dv(fkb), "_first_key_off": dv(fko), "_last_key_bytes": dv(lkb), "_last_key_off": dv(lko),
+         "_block_base": dv(np.concatenate([[0], np.cumsum([int(vt["num_blocks"]) for vt in views])]).astype(np.uint64))}
+    total = sum(int(vt["num_blocks"]) for vt in views)
+    t["lsm"] = _abi.LsmView(t["_ssts"].data_ptr(), ns, len(runs), t["_run_start"].data_ptr(),
+                            t["_first_key_bytes"].data_ptr(), t["_first_key_off"].data_ptr(),
+                            t["_last_key_bytes"].data_ptr(), t["_last_key_off"].data_ptr(),
+                            t["_block_base"].data_ptr(), total)
+    t.update(num_ssts=ns, num_runs=len(runs), total_blocks=total, device=dev)
+    return t
+
+
+def lsm_get_device(views, runs, keys, max_seq=None, stream=None, workspace=None):
+    """sdb_lsm_get: a batch of Db::get over a device-resident tree.  views, runs: as lsm_tree_device, or
+    views = a tree lsm_tree_device built (runs is then ignored).  keys: a list of bytes, or device tensors
+    (key_bytes, key_off, nkeys).  max_seq: None (no bound), a list / array of nkeys bounds, or a device
+    int64 tensor.  workspace: a device uint8 tensor to use (and reuse) instead of a fresh one.  With device
+    tensors and a prebuilt tree the call copies nothing from the host, so it can be captured into a graph.  Returns a dict of device tensors (GET_FIELDS, and summary: the
+    sdb_get_summary words in GET_SUMMARY order); what the call allocated stays alive under "_" keys."""
+    import torch
+    tree = views if isinstance(views, dict) else lsm_tree_device(views, runs)
+    dev = tree["device"]
+    if isinstance(keys, (tuple, list)) and len(keys) == 3 and hasattr(keys[0], "data_ptr"):
+        kb, ko, n = keys
+    else:
+        n = len(keys)
+        hb, ho = keys_columnar([bytes(k) for k in keys])
+        kb, ko = torch.from_numpy(hb).to(dev), torch.from_numpy(ho.view(np.int64)).to(dev)
+    if max_seq is not None and not hasattr(max_seq, "data_ptr"):
+        max_seq = torch.from_numpy(np.asarray(max_seq, np.uint64).view(np.int64).copy()).to(dev)
+    res = {f: torch.zeros(max(n, 1), dtype=getattr(torch, dt), device=dev) for f, dt in GET_FIELDS}
+    res["summary"] = torch.zeros(len(GET_SUMMARY), dtype=torch.int64, device=dev)
+    out = _abi.GetOut(*[res[f].data_ptr() for f, _ in GET_FIELDS], res["summary"].data_ptr())
+    wsb = lib().sdb_lsm_get_workspace_bytes(tree["total_blocks"], tree["num_ssts"], tree["num_runs"], n)
+    ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=dev)
+    assert ws.numel() >= wsb, "workspace too small"
+    st = lib().sdb_lsm_get(C.byref(tree["lsm"]), kb.data_ptr(), ko.data_ptr(), n,
+                           max_seq.data_ptr() if max_seq is not None else None, C.byref(out), ws.data_ptr(), wsb,
+                           _sp(stream))
+    if st:
+        raise SdbError(st, "sdb_lsm_get")
+    res.update(_ws=ws, _tree=tree, _keys=(kb, ko), _max_seq=max_seq)
+    return res
+
+
 # ------------------------------------------------------------------------------------------------
 # Compaction (sdb_merge_runs / sdb_sst_cuts / sdb_compactor_*)
 # ------------------------------------------------------------------------------------------------
