@@ -19,19 +19,9 @@
 #include "sdb_compact.h"
 
 namespace sdb {
-struct LookupArgs {
-    sdb_sst_view v;
-    const uint8_t *key_bytes;
-    const uint64_t *key_off;
-    uint64_t nkeys;
-    uint32_t desc;
-    sdb_lookup_out out;
-    uint32_t *qrange;
-    uint8_t *mark;
-    int32_t *bstat;
-};
 uint64_t lookup_workspace_bytes(uint64_t num_blocks, uint64_t nkeys);
-hipError_t launch_lookup(LookupArgs a, hipStream_t st);
+hipError_t launch_lookup(const sdb_sst_view &v, const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
+                         uint32_t desc, const sdb_lookup_out &out, uint8_t *w, hipStream_t st);
 uint64_t scan_workspace_bytes(uint64_t num_blocks, uint64_t nranges);
 hipError_t launch_scan(const sdb_sst_view &v, const sdb_scan_ranges &r, uint32_t desc, const sdb_scan_out &out, uint8_t *w,
                        hipStream_t st);
@@ -590,19 +580,8 @@ sdb_status sdb_sst_lookup(const sdb_sst_view *sst, const uint8_t *key_bytes, con
     if (!device_ok()) return SDB_DEVICE_ERROR;
     if (!workspace || workspace_bytes < sdb_sst_lookup_workspace_bytes(sst->num_blocks, nkeys)) return SDB_INVALID_ARGUMENT;
     uint8_t *w = (uint8_t *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    LookupArgs a{};
-    a.v = *sst;
-    a.key_bytes = key_bytes;
-    a.key_off = key_off;
-    a.nkeys = nkeys;
-    a.desc = descending ? 1 : 0;
-    a.out = *out;
-    a.qrange = (uint32_t *)w;
-    w += (8 * (nkeys + 1) + 255) & ~255ull;
-    a.mark = w;
-    w += (sst->num_blocks + 256) & ~255ull;
-    a.bstat = (int32_t *)w;
-    if (launch_lookup(a, S(stream)) != hipSuccess) return SDB_DEVICE_ERROR;
+    if (launch_lookup(*sst, key_bytes, key_off, nkeys, descending ? 1u : 0u, *out, w, S(stream)) != hipSuccess)
+        return SDB_DEVICE_ERROR;
     return SDB_OK;
 }
 

@@ -188,6 +188,21 @@ SDB_DEV uint32_t crc_shift_bytes(uint32_t c, uint32_t n) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// Workspace carving (host): 256-byte-aligned arrays taken in order from base.  One function that takes a
+// launch's arrays both sizes its workspace (base == nullptr: nothing is bound, `off` ends as the size) and
+// binds it, so the two cannot disagree.
+// ------------------------------------------------------------------------------------------------
+struct Carver {
+    uint8_t *base;
+    uint64_t off;
+    template <typename T>
+    void take(T *&p, uint64_t count) {
+        p = base ? (T *)(base + off) : nullptr;
+        off += (sizeof(T) * count + 255) & ~255ull;
+    }
+};
+
+// ------------------------------------------------------------------------------------------------
 // Byte helpers
 // ------------------------------------------------------------------------------------------------
 SDB_DEV uint32_t varint_len(uint32_t v) {  // utils.rs:638-645

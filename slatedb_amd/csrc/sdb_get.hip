@@ -23,17 +23,16 @@
 //                   decides is not known before the blocks are checked).  A thread per pair, not per
 //                   query: the work is dependent loads (binary searches, filter probes), and 64 Ki queries
 //                   alone leave a CU four waves to hide them behind
-//   k_get_check     wave per marked block: bounds + CRC, the body k_lk_check uses (sdb_lookup.h)
-//   k_get_rows      thread per checked block: every row parsed, as sdb_sst_scan's k_sc_block reports them
+//   k_check         wave per marked block: bounds + CRC, the pass the lookups and scans run (sdb_lookup.hip)
+//   k_get_rows      thread per checked block: every row parsed, by the walker sdb_sst_scan's k_sc_block uses
+//                   (for_each_row of sdb_read.h)
 //   k_get_walk      thread per (query, run) that has an unfiltered covering SST: block statuses, the seek,
 //                   the versions above max_seq skipped -> the pair's record (entry position or error)
 //   k_get_resolve   thread per query: the first run in order whose record holds an entry or an error decides;
 //                   records behind it are never looked at, so their block errors never surface; one row
 //                   re-parsed for the columns; wave reduction + one atomic per counter and workgroup
 //   k_get_final     the summary
-#include <mutex>
-
-#include "sdb_lookup.h"
+#include "sdb_read.h"
 
 namespace sdb {
 
@@ -56,7 +55,7 @@ struct GetArgs {
     uint64_t nkeys;
     const uint64_t *max_seq;
     sdb_get_out out;
-    uint8_t *mark;             // per tree block: 1 = some chain reads it (cleared by k_get_check)
+    uint8_t *mark;             // per tree block: 1 = some chain reads it (cleared by k_check)
     int32_t *bstat;            // per tree block: -1 = not read, else its sdb_status
     int32_t *sstat;            // per SST: 0, SDB_INVALID_VERSION or SDB_INVALID_ARGUMENT
     uint8_t *rstate;           // per pair, at run * nkeys + query: kRun*
@@ -136,16 +135,13 @@ struct Step {
     int st;
     uint32_t start, end;
 };
-SDB_DEV Step get_step(const GetArgs &a, const LookupArgs &l, uint32_t i, const Key &k, uint64_t h) {
+SDB_DEV Step get_step(const GetArgs &a, const sdb_sst_view &v, uint32_t i, const Key &k, uint64_t h) {
     Step s{false, 0, 0, 0};
-    if (l.v.bloom && !bloom_might_contain(l.v.bloom, l.v.bloom_len, l.v.num_probes, h)) {
+    if (v.bloom && !bloom_might_contain(v.bloom, v.bloom_len, v.num_probes, h)) {
         s.filtered = true;
         return s;
     }
-    if ((s.st = a.sstat[i])) return s;
-    const uint64_t lt = partition_point(l, k.t, k.nt, false), le = partition_point(l, k.t, k.nt, true);
-    s.start = (uint32_t)(lt > 0 ? lt - 1 : 0);
-    s.end = (uint32_t)(le > 0 ? le : s.start);
+    if (!(s.st = a.sstat[i])) point_block_range(v, k.t, k.nt, s.start, s.end);
     return s;
 }
 
@@ -163,9 +159,8 @@ __global__ __launch_bounds__(256) void k_get_locate(GetArgs a) {
             const uint64_t h = siphash13(k.t, k.nt);  // filter_hash (filter.rs:196-204): one hash for every SST's filter
             rs = last > first ? kRunOpen : kRunFiltered;  // several covering SSTs: the resolve counts them itself
             for (uint32_t i = first; i <= last; i++) {
-                LookupArgs l{};
-                l.v = a.t.ssts[i];
-                const Step s = get_step(a, l, i, k, h);
+                const sdb_sst_view v = a.t.ssts[i];
+                const Step s = get_step(a, v, i, k, h);
                 if (s.filtered) continue;
                 rs = kRunOpen;
                 if (s.st) continue;
@@ -181,66 +176,17 @@ __global__ __launch_bounds__(256) void k_get_locate(GetArgs a) {
     }
 }
 
-// The SST of tree block k: the last i with block_base[i] <= k.
-SDB_DEV uint32_t sst_of_block(const GetArgs &a, uint64_t k) {
-    uint32_t lo = 0, hi = a.t.num_ssts;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (a.t.block_base[mid] <= k) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
-__global__ __launch_bounds__(kLkThreads) void k_get_check(GetArgs a) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    if (*a.bad) return;
-    crc_tables_to_lds((lu32 *)smem);
-    __syncthreads();
-    const uint32_t wave = threadIdx.x >> 6, l = (uint32_t)lane_id();
-    lu8 *img = lk_wave_image(smem, wave, l);
-    const uint64_t nw = (uint64_t)gridDim.x * (blockDim.x >> 6);
-    for (uint64_t k = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wave; k < a.t.total_blocks; k += nw) {
-        if (!a.mark[k]) continue;
-        const uint32_t i = sst_of_block(a, k);
-        const uint64_t b = k - a.t.block_base[i];
-        const uint8_t *data = a.t.ssts[i].data;
-        const uint64_t *off = a.t.ssts[i].block_off;
-        const int st = lk_check_block(data, off[b], off[b + 1], img, l);
-        if (l == 0) {
-            a.bstat[k] = st;
-            a.mark[k] = 0;  // ready for the next call
-        }
-    }
-}
-
 // Every row of a checked block parsed (flags, varints, lengths), as sdb_sst_scan reports them.
 __global__ __launch_bounds__(64) void k_get_rows(GetArgs a) {
     const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int st = -1;
     if (k < a.t.total_blocks && !*a.bad) st = a.bstat[k];
     if (st == 0) {
-        const uint32_t i = sst_of_block(a, k);
-        LookupArgs l{};
-        l.v = a.t.ssts[i];
+        const uint32_t i = sst_of_block(a.t, k);
+        const sdb_sst_view v = a.t.ssts[i];
         Blk b;
-        st = blk_open(l, k - a.t.block_base[i], b);
-        if (!st && l.v.sst_version == 2) {
-            uint32_t kp, kn, pos = 0, curlen = 0;
-            if (b.count > 0) st = v2_restart_key(b, 0, kp, kn);
-            while (!st && pos < b.data_end) {
-                Row r;
-                if ((st = v2_row(b, pos, r))) break;
-                if (r.sh > curlen) st = SDB_CORRUPT_BLOCK;
-                curlen = r.sh + r.un;
-                pos = r.next;
-            }
-        } else if (!st) {
-            for (uint32_t j = 0; j < b.count && !st; j++) {
-                Row r;
-                st = v1_row(b, j, r);
-            }
-        }
+        st = blk_open(v, k - a.t.block_base[i], b);
+        if (!st) st = for_each_row(v.sst_version, b, [](uint32_t, uint32_t, const Row &) {});
         a.bstat[k] = st;
     }
     const unsigned long long read = __ballot(st != -1);
@@ -253,30 +199,20 @@ struct Hit {
 };
 
 // The first entry of blocks [start, end) of one SST, in physical order, with key == k and seq <= bound.
-SDB_DEV int get_walk(const LookupArgs &l, const Step &s, const Key &k, uint64_t bound, Hit &H) {
+SDB_DEV int get_walk(const sdb_sst_view &v, const Step &s, const Key &k, uint64_t bound, Hit &H) {
     H.ok = false;
-    const bool v2 = l.v.sst_version == 2;
+    const bool v2 = v.sst_version == 2;
     for (uint32_t blk = s.start; blk < s.end; blk++) {
         Blk b;
-        if (int st = blk_open(l, blk, b)) return st;
+        if (int st = blk_open(v, blk, b)) return st;
         if (b.count == 0) continue;
         Pos P;
-        if (blk == s.start) {  // the seek; later blocks are entered at their first entry
-            if (int st = v2 ? v2_seek_asc(b, k.t, k.nt, P) : v1_seek(b, k.t, k.nt, false, P)) return st;
-            if (!P.ok) continue;
-        } else {
-            P.ok = true;
-            P.at = v2 ? boff(b, 0) : 0;
-            if (v2) {
-                uint32_t kp, kn;
-                if (int st = v2_restart_key(b, 0, kp, kn)) return st;
-                if (P.at >= b.data_end) continue;
-                P.key = cmp_bytes(b.d + kp, kn, k.t, k.nt, 0);
-            } else if (int st = v1_cmp(b, 0, k.t, k.nt, P.key)) {
-                return st;
-            }
+        if (blk != s.start) {  // the first block is seeked; later blocks are entered at their first entry
+            if (int st = first_entry(v2, b, k.t, k.nt, P)) return st;
+        } else if (int st = v2 ? v2_seek_asc(b, k.t, k.nt, P) : v1_seek(b, k.t, k.nt, false, P)) {
+            return st;
         }
-        for (;;) {  // entries from P on while they hold the key
+        while (P.ok) {  // entries from P on while they hold the key
             if (P.key.c > 0) return 0;  // past the key: this SST has no visible version
             Row r;
             if (int st = v2 ? v2_row(b, P.at, r) : v1_row(b, P.at, r)) return st;
@@ -286,18 +222,7 @@ SDB_DEV int get_walk(const LookupArgs &l, const Step &s, const Key &k, uint64_t 
                 H.at = P.at;
                 return 0;
             }
-            if (v2) {
-                if (r.next >= b.data_end) break;
-                uint32_t p = r.next, sh, un, vl;
-                if (!rdv(b.d, b.data_end, p, sh) || !rdv(b.d, b.data_end, p, un) || !rdv(b.d, b.data_end, p, vl) ||
-                    sh > P.key.len || (uint64_t)p + un > b.data_end)
-                    return SDB_CORRUPT_BLOCK;
-                P.key = cmp_next(P.key, sh, b.d + p, un, k.t, k.nt);
-                P.at = r.next;
-            } else {
-                if (++P.at >= b.count) break;
-                if (int st = v1_cmp(b, P.at, k.t, k.nt, P.key)) return st;
-            }
+            if (int st = next_entry(v2, b, r, k.t, k.nt, P)) return st;
         }
     }
     return 0;
@@ -317,32 +242,30 @@ __global__ __launch_bounds__(64) void k_get_walk(GetArgs a) {
         uint32_t sst = 0xFFFFFFFFu, nread = 0, nfilt = 0;
         Hit H;
         H.ok = false;
-        auto search = [&](uint32_t i, const LookupArgs &l, const Step &s) {  // false: the run is decided
+        auto search = [&](uint32_t i, const sdb_sst_view &v, const Step &s) {  // false: the run is decided
             if (s.end <= s.start) return true;
             nread++;
             const uint64_t base = a.t.block_base[i];
             for (uint32_t b = s.start; b < s.end && !st; b++) st = a.bstat[base + b];  // the lowest failing block
             if (st < 0) st = SDB_INVALID_ARGUMENT;  // unreachable: locate marked this range
-            if (!st) st = get_walk(l, s, k, bound, H);
+            if (!st) st = get_walk(v, s, k, bound, H);
             if (H.ok) sst = i;
             return !st && !H.ok;
         };
         if (rs == kRunOpen1) {
             const RunRec in = a.rec[t];
-            LookupArgs l{};
-            l.v = a.t.ssts[in.sst];
-            search(in.sst, l, Step{false, 0, in.block, in.at});
+            const sdb_sst_view v = a.t.ssts[in.sst];
+            search(in.sst, v, Step{false, 0, in.block, in.at});
         } else {
             const uint64_t h = siphash13(k.t, k.nt);
             uint32_t first = 0, last = 0;
             bool go = get_run(a, (uint32_t)(t / a.nkeys), k, first, last);
             for (uint32_t i = first; go && i <= last; i++) {
-                LookupArgs l{};
-                l.v = a.t.ssts[i];
-                const Step s = get_step(a, l, i, k, h);
+                const sdb_sst_view v = a.t.ssts[i];
+                const Step s = get_step(a, v, i, k, h);
                 if (s.filtered) nfilt++;
                 else if ((st = s.st)) go = false;
-                else go = search(i, l, s);
+                else go = search(i, v, s);
             }
         }
         RunRec out{sst, H.ok ? H.block : 0, H.ok ? H.at : 0, (uint16_t)(nread > 0xFFFF ? 0xFFFF : nread),
@@ -382,10 +305,9 @@ __global__ __launch_bounds__(64) void k_get_resolve(GetArgs a) {
                 }
             }
             if (H.ok) {  // the row again, for its columns
-                LookupArgs l{};
-                l.v = a.t.ssts[sst];
+                const sdb_sst_view v = a.t.ssts[sst];
                 Blk b;
-                if (!(st = blk_open(l, H.block, b))) st = l.v.sst_version == 2 ? v2_row(b, H.at, r) : v1_row(b, H.at, r);
+                if (!(st = blk_open(v, H.block, b))) st = v.sst_version == 2 ? v2_row(b, H.at, r) : v1_row(b, H.at, r);
                 vbase = b.base;
             }
         }
@@ -393,26 +315,21 @@ __global__ __launch_bounds__(64) void k_get_resolve(GetArgs a) {
         if (H.ok) {
             if (r.flags & SDB_FLAG_TOMBSTONE) {
                 state = SDB_GET_DELETED;
-                r.vl = 0;
             } else if (r.flags & SDB_FLAG_MERGE_OPERAND) {
                 state = SDB_GET_MERGE_OPERAND;
                 st = SDB_MERGE_OPERATOR_MISSING;
             } else {
                 state = SDB_GET_FOUND;
             }
-        } else {
+        } else {  // no entry: zero columns
             sst = 0xFFFFFFFFu;
+            r = Row{};
         }
         a.out.state[q] = (uint8_t)state;
         a.out.status[q] = st;
         a.out.sst[q] = sst;
         a.out.block[q] = H.ok ? H.block : 0;
-        a.out.val_off[q] = H.ok && r.vl ? vbase + r.vpos : 0;
-        a.out.val_len[q] = H.ok ? r.vl : 0;
-        a.out.seq[q] = H.ok ? r.seq : 0;
-        a.out.flags[q] = H.ok ? r.flags : 0;
-        a.out.create_ts[q] = H.ok && (r.flags & SDB_FLAG_HAS_CREATE_TS) ? r.cts : 0;
-        a.out.expire_ts[q] = H.ok && (r.flags & SDB_FLAG_HAS_EXPIRE_TS) ? r.ets : 0;
+        put_row(a.out, q, vbase, r);
         a.out.ssts_read[q] = nread;
         a.out.ssts_filtered[q] = nfilt;
     }
@@ -443,29 +360,27 @@ __global__ void k_get_final(GetArgs a) {
     *a.out.summary = s;
 }
 
-struct GetWorkspace {
-    uint64_t mark, bstat, sstat, rstate, rec, misc, total;
-};
-static GetWorkspace get_workspace_layout(uint64_t tb, uint64_t ns, uint64_t nr, uint64_t n) {
-    GetWorkspace w{};
-    uint64_t off = 0;
-    auto take = [&](uint64_t bytes) {
-        const uint64_t r = off;
-        off += (bytes + 255) & ~255ull;
-        return r;
-    };
-    w.mark = take(tb + 1);
-    w.bstat = take(4 * (tb + 1));
-    w.sstat = take(4 * (ns + 1));
-    w.rstate = take(n * nr + 1);
-    w.rec = take(sizeof(RunRec) * (n * nr + 1));
-    w.misc = take(8 * kAccWords + 8);
-    w.total = off;
-    return w;
+// The workspace arrays of a get of a.nkeys keys over the tree a.t, bound into a from w; -> their size.
+static uint64_t get_bind(GetArgs &a, uint8_t *w) {
+    const uint64_t tb = a.t.total_blocks, pairs = a.nkeys * a.t.num_runs;
+    Carver c{w, 0};
+    c.take(a.mark, tb + 1);
+    c.take(a.bstat, tb + 1);
+    c.take(a.sstat, (uint64_t)a.t.num_ssts + 1);
+    c.take(a.rstate, pairs + 1);
+    c.take(a.rec, pairs + 1);
+    c.take(a.acc, kAccWords + 1);  // the accumulators, then bad
+    if (w) a.bad = (uint32_t *)(a.acc + kAccWords);
+    return c.off;
 }
 
 uint64_t get_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys) {
-    return get_workspace_layout(total_blocks, num_ssts, num_runs, nkeys).total;
+    GetArgs a{};
+    a.t.total_blocks = total_blocks;
+    a.t.num_ssts = num_ssts;
+    a.t.num_runs = num_runs;
+    a.nkeys = nkeys;
+    return get_bind(a, nullptr);
 }
 
 hipError_t launch_get(const sdb_lsm_view &t, const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
@@ -488,7 +403,6 @@ hipError_t launch_get(const sdb_lsm_view &t, const uint8_t *key_bytes, const uin
         if ((e = hipMemsetAsync(out.ssts_read, 0, 4 * n, st)) != hipSuccess) return e;
         return hipMemsetAsync(out.ssts_filtered, 0, 4 * n, st);
     }
-    const GetWorkspace L = get_workspace_layout(tb, t.num_ssts, t.num_runs, n);
     GetArgs a{};
     a.t = t;
     a.key_bytes = key_bytes;
@@ -496,27 +410,14 @@ hipError_t launch_get(const sdb_lsm_view &t, const uint8_t *key_bytes, const uin
     a.nkeys = n;
     a.max_seq = max_seq;
     a.out = out;
-    a.mark = w + L.mark;
-    a.bstat = (int32_t *)(w + L.bstat);
-    a.sstat = (int32_t *)(w + L.sstat);
-    a.rstate = w + L.rstate;
-    a.rec = (RunRec *)(w + L.rec);
-    a.acc = (unsigned long long *)(w + L.misc);
-    a.bad = (uint32_t *)(w + L.misc + 8 * kAccWords);
+    get_bind(a, w);
     if ((e = hipMemsetAsync(a.mark, 0, tb, st)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(a.bstat, 0xFF, 4 * tb, st)) != hipSuccess) return e;
-    static std::once_flag once;
-    std::call_once(once, [] {
-        (void)hipFuncSetAttribute((const void *)k_get_check, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLkLds);
-        (void)hipGetLastError();
-    });
     hipLaunchKernelGGL(k_get_validate, dim3(1), dim3(256), 0, st, a);
     uint64_t lg = (n * t.num_runs + 255) / 256;  // the kernel strides past this cap
     if (lg > (1u << 20)) lg = 1u << 20;
     hipLaunchKernelGGL(k_get_locate, dim3((uint32_t)lg), dim3(256), 0, st, a);
-    uint64_t wgs = (tb + 3) / 4;
-    if (wgs > 4096) wgs = 4096;
-    hipLaunchKernelGGL(k_get_check, dim3((uint32_t)wgs), dim3(kLkThreads), kLkLds, st, a);
+    if ((e = launch_check(CheckArgs{{}, t, a.bad, tb, a.mark, a.bstat}, st)) != hipSuccess) return e;
     // the per-block parse and the per-query walk are latency-bound threads: one wave per workgroup spreads them over the CUs
     hipLaunchKernelGGL(k_get_rows, dim3((uint32_t)((tb + 63) / 64)), dim3(64), 0, st, a);
     uint64_t wg = (n * t.num_runs + 63) / 64;

@@ -1,24 +1,14 @@
-// sdb_lookup.h — device helpers shared by the point lookups (sdb_lookup.hip) and the range scans
-// (sdb_scan.hip): the incremental key comparators, Block::decode of a checked block, the row parsers
-// and the index partition_point.
+// sdb_read.h — the one reader of an encoded block, shared by the point lookups (sdb_lookup.hip), the range
+// scans (sdb_scan.hip) and the tree gets (sdb_get.hip): the incremental key comparators, Block::decode of a
+// checked block, the entry-header and row parsers, the seeks, the row walker and the row -> column writer, the
+// index partition_point, and the bounds + CRC pass over marked blocks.  Everything takes what it reads (an
+// sdb_sst_view, a Blk), never a kernel's argument struct.
 #pragma once
 #include "sdb_bloom.h"
 #include "sdb_crc.h"
 #include "sdb_device.h"
 
 namespace sdb {
-
-struct LookupArgs {
-    sdb_sst_view v;
-    const uint8_t *key_bytes;
-    const uint64_t *key_off;
-    uint64_t nkeys;
-    uint32_t desc;
-    sdb_lookup_out out;
-    uint32_t *qrange;     // per query: start, end (block range; end == start: empty)
-    uint8_t *mark;        // per block: 1 = a seek reads it
-    int32_t *bstat;       // per block: sdb_status of Block::decode + CRC
-};
 
 SDB_DEV uint64_t be_at(const uint8_t *p, int n) {
     uint64_t v = 0;
@@ -61,11 +51,11 @@ struct Blk {  // Block::decode of a checked block
     const uint8_t *offs;
     uint64_t base;
 };
-SDB_DEV int blk_open(const LookupArgs &a, uint64_t k, Blk &b) {
-    const uint64_t s = a.v.block_off[k], e = a.v.block_off[k + 1];
+SDB_DEV int blk_open(const sdb_sst_view &v, uint64_t k, Blk &b) {
+    const uint64_t s = v.block_off[k], e = v.block_off[k + 1];
     if (e < s || e - s < 6) return SDB_CORRUPT_BLOCK;
     const uint32_t blen = (uint32_t)(e - s - 4);
-    b.d = a.v.data + s;
+    b.d = v.data + s;
     b.base = s;
     b.count = (uint32_t)be_at(b.d + blen - 2, 2);
     if (2 + 2 * (uint64_t)b.count > blen) return SDB_CORRUPT_BLOCK;
@@ -96,40 +86,61 @@ struct Row {
     int64_t cts, ets;
     uint8_t flags;
 };
-SDB_DEV int v2_row(const Blk &b, uint32_t pos, Row &r) {  // SstRowCodecV2::decode (row_codec_v2.rs:172-220)
-    if (!rdv(b.d, b.data_end, pos, r.sh) || !rdv(b.d, b.data_end, pos, r.un) || !rdv(b.d, b.data_end, pos, r.vl))
-        return SDB_CORRUPT_BLOCK;
-    if ((uint64_t)pos + r.un + r.vl + 9 > b.data_end) return SDB_CORRUPT_BLOCK;
-    r.suf = pos;
-    pos += r.un;
-    r.vpos = pos;
-    pos += r.vl;
-    r.seq = be_at(b.d + pos, 8);
-    pos += 8;
-    r.flags = b.d[pos++];
+// The V2 entry header at byte p: the varints shared, unshared and value length (row_codec_v2.rs:172-186), with
+// shared <= max_sh (what the caller knows of the previous key) and the key suffix d[suf, suf + un) inside the
+// data.  !ok: corrupt.
+struct V2Hdr {
+    bool ok;
+    uint32_t sh, un, vl, suf;
+};
+SDB_DEV V2Hdr v2_hdr(const Blk &b, uint32_t p, uint32_t max_sh) {
+    V2Hdr h{};
+    if (!rdv(b.d, b.data_end, p, h.sh) || !rdv(b.d, b.data_end, p, h.un) || !rdv(b.d, b.data_end, p, h.vl) ||
+        h.sh > max_sh || (uint64_t)p + h.un > b.data_end)
+        return h;
+    h.ok = true;
+    h.suf = p;
+    return h;
+}
+// The row tail at byte p, its first nine bytes inside the data: seq, flags, then expire_ts and create_ts where
+// flagged.  p moves past it.
+SDB_DEV int row_tail(const Blk &b, uint32_t &p, Row &r) {
+    r.seq = be_at(b.d + p, 8);
+    r.flags = b.d[p + 8];
+    p += 9;
     if (!flags_valid(r.flags)) return SDB_INVALID_ROW_FLAGS;
     const uint32_t need = ((r.flags & SDB_FLAG_HAS_EXPIRE_TS) ? 8 : 0) + ((r.flags & SDB_FLAG_HAS_CREATE_TS) ? 8 : 0);
-    if ((uint64_t)pos + need > b.data_end) return SDB_CORRUPT_BLOCK;
+    if ((uint64_t)p + need > b.data_end) return SDB_CORRUPT_BLOCK;
     r.ets = r.cts = 0;
     if (r.flags & SDB_FLAG_HAS_EXPIRE_TS) {
-        r.ets = (int64_t)be_at(b.d + pos, 8);
-        pos += 8;
+        r.ets = (int64_t)be_at(b.d + p, 8);
+        p += 8;
     }
     if (r.flags & SDB_FLAG_HAS_CREATE_TS) {
-        r.cts = (int64_t)be_at(b.d + pos, 8);
-        pos += 8;
+        r.cts = (int64_t)be_at(b.d + p, 8);
+        p += 8;
     }
+    return 0;
+}
+SDB_DEV int v2_row(const Blk &b, uint32_t pos, Row &r) {  // SstRowCodecV2::decode (row_codec_v2.rs:172-220)
+    const V2Hdr h = v2_hdr(b, pos, ~0u);
+    if (!h.ok || (uint64_t)h.suf + h.un + h.vl + 9 > b.data_end) return SDB_CORRUPT_BLOCK;
+    r.sh = h.sh;
+    r.un = h.un;
+    r.vl = h.vl;
+    r.suf = h.suf;
+    r.vpos = r.suf + r.un;
+    pos = r.vpos + r.vl;
+    if (int st = row_tail(b, pos, r)) return st;
     r.next = pos;
     return 0;
 }
 // decode_first_key_at_restart (block_iterator_v2.rs:73-80): key = d[*kp, *kp + *kn), shared == 0
 SDB_DEV int v2_restart_key(const Blk &b, uint32_t ri, uint32_t &kp, uint32_t &kn) {
-    uint32_t p = boff(b, ri), sh, un, vl;
-    if (p > b.data_end || !rdv(b.d, b.data_end, p, sh) || !rdv(b.d, b.data_end, p, un) || !rdv(b.d, b.data_end, p, vl) ||
-        sh != 0 || (uint64_t)p + un > b.data_end)
-        return SDB_CORRUPT_BLOCK;
-    kp = p;
-    kn = un;
+    const V2Hdr h = v2_hdr(b, boff(b, ri), 0);  // an offset past the data has no first varint
+    if (!h.ok) return SDB_CORRUPT_BLOCK;
+    kp = h.suf;
+    kn = h.un;
     return 0;
 }
 SDB_DEV uint32_t region_end(const Blk &b, uint32_t ri) { return ri + 1 < b.count ? boff(b, ri + 1) : b.data_end; }
@@ -175,11 +186,9 @@ SDB_DEV int v2_seek_asc(const Blk &b, const uint8_t *t, uint32_t nt, Pos &P) {
         const uint32_t rend = region_end(b, ri);
         Cmp prev = rk;
         while (off < rend && off < b.data_end) {
-            uint32_t p = off, sh, un, vl;  // decode_key_at_offset (:115-126)
-            if (!rdv(b.d, b.data_end, p, sh) || !rdv(b.d, b.data_end, p, un) || !rdv(b.d, b.data_end, p, vl) ||
-                sh > prev.len || (uint64_t)p + un > b.data_end)
-                return SDB_CORRUPT_BLOCK;
-            const Cmp cur = cmp_next(prev, sh, b.d + p, un, t, nt);
+            const V2Hdr h = v2_hdr(b, off, prev.len);  // decode_key_at_offset (:115-126)
+            if (!h.ok) return SDB_CORRUPT_BLOCK;
+            const Cmp cur = cmp_next(prev, h.sh, b.d + h.suf, h.un, t, nt);
             if (cur.c >= 0) {
                 P.ok = true;
                 P.at = off;
@@ -273,25 +282,11 @@ SDB_DEV int v1_row(const Blk &b, uint32_t i, Row &r) {
     if (r.sh > fk || (uint64_t)p + r.un + 9 > b.data_end) return SDB_CORRUPT_BLOCK;
     r.suf = p;
     p += r.un;
-    r.seq = be_at(b.d + p, 8);
-    p += 8;
-    uint8_t f = b.d[p++];
-    if (!flags_valid(f)) return SDB_INVALID_ROW_FLAGS;
-    const uint32_t need = ((f & SDB_FLAG_HAS_EXPIRE_TS) ? 8 : 0) + ((f & SDB_FLAG_HAS_CREATE_TS) ? 8 : 0);
-    if ((uint64_t)p + need > b.data_end) return SDB_CORRUPT_BLOCK;
-    r.ets = r.cts = 0;
-    if (f & SDB_FLAG_HAS_EXPIRE_TS) {
-        r.ets = (int64_t)be_at(b.d + p, 8);
-        p += 8;
-    }
-    if (f & SDB_FLAG_HAS_CREATE_TS) {
-        r.cts = (int64_t)be_at(b.d + p, 8);
-        p += 8;
-    }
+    if (int st = row_tail(b, p, r)) return st;
     r.vl = 0;
     r.vpos = 0;
-    if (f & SDB_FLAG_TOMBSTONE) {
-        f = (uint8_t)(f & ~SDB_FLAG_HAS_EXPIRE_TS);
+    if (r.flags & SDB_FLAG_TOMBSTONE) {
+        r.flags = (uint8_t)(r.flags & ~SDB_FLAG_HAS_EXPIRE_TS);
     } else {
         if ((uint64_t)p + 4 > b.data_end) return SDB_CORRUPT_BLOCK;
         r.vl = (uint32_t)be_at(b.d + p, 4);
@@ -300,7 +295,6 @@ SDB_DEV int v1_row(const Blk &b, uint32_t i, Row &r) {
         r.vpos = p;
         p += r.vl;
     }
-    r.flags = f;
     r.next = p;
     return 0;
 }
@@ -329,14 +323,14 @@ SDB_DEV int v1_seek(const Blk &b, const uint8_t *t, uint32_t nt, bool desc, Pos 
 }
 
 // partition_point (partitioned_keyspace.rs:16-39); le: first_key <= key, else first_key < key
-SDB_DEV uint64_t partition_point(const LookupArgs &a, const uint8_t *t, uint32_t nt, bool le) {
-    const uint64_t n = a.v.num_blocks;
+SDB_DEV uint64_t partition_point(const sdb_sst_view &v, const uint8_t *t, uint32_t nt, bool le) {
+    const uint64_t n = v.num_blocks;
     if (n == 0) return 0;
     uint64_t lo = 0, hi = n - 1, pp = 0;
     while (lo <= hi) {
         const uint64_t mid = lo + (hi - lo) / 2;
-        const uint64_t f0 = a.v.index_key_off[mid], f1 = a.v.index_key_off[mid + 1];
-        const int c = cmp_bytes(a.v.index_keys + f0, (uint32_t)(f1 - f0), t, nt, 0).c;
+        const uint64_t f0 = v.index_key_off[mid], f1 = v.index_key_off[mid + 1];
+        const int c = cmp_bytes(v.index_keys + f0, (uint32_t)(f1 - f0), t, nt, 0).c;
         if (le ? c <= 0 : c < 0) {
             lo = mid + 1;
             pp = mid + 1;
@@ -347,6 +341,84 @@ SDB_DEV uint64_t partition_point(const LookupArgs &a, const uint8_t *t, uint32_t
         }
     }
     return pp;
+}
+// partitions_covering_range(Included(key), Included(key)) (partitioned_keyspace.rs:87-110): the blocks
+// [start, end) that can hold the key; end == start: none.
+SDB_DEV void point_block_range(const sdb_sst_view &v, const uint8_t *t, uint32_t nt, uint32_t &start, uint32_t &end) {
+    const uint64_t lt = partition_point(v, t, nt, false), le = partition_point(v, t, nt, true);
+    start = (uint32_t)(lt > 0 ? lt - 1 : 0);
+    end = (uint32_t)(le > 0 ? le : start);
+}
+
+// A fresh block iterator on entry 0 of a block with count > 0 (BlockIteratorV2::new, block_iterator_v2.rs:33-57:
+// byte 0 under restart 0's key; BlockIterator::new, V1: index 0).  !P.ok: the block holds no entry.
+SDB_DEV int first_entry(bool v2, const Blk &b, const uint8_t *t, uint32_t nt, Pos &P) {
+    P.at = 0;
+    P.ok = !v2 || b.data_end > 0;
+    if (!v2) return v1_cmp(b, 0, t, nt, P.key);
+    uint32_t kp, kn;
+    if (int st = v2_restart_key(b, 0, kp, kn)) return st;
+    P.key = cmp_bytes(b.d + kp, kn, t, nt, 0);
+    return 0;
+}
+// The entry after the one at P, whose row is r, with its key's order carried over from P's.  !P.ok: r was the
+// block's last.
+SDB_DEV int next_entry(bool v2, const Blk &b, const Row &r, const uint8_t *t, uint32_t nt, Pos &P) {
+    if (!v2) {
+        P.ok = ++P.at < b.count;
+        return P.ok ? v1_cmp(b, P.at, t, nt, P.key) : 0;
+    }
+    P.ok = r.next < b.data_end;
+    if (!P.ok) return 0;
+    const V2Hdr h = v2_hdr(b, r.next, P.key.len);
+    if (!h.ok) return SDB_CORRUPT_BLOCK;
+    P.at = r.next;  // before the key, as the V1 branch: with the key first the optimiser keeps P in scratch memory
+    P.key = cmp_next(P.key, h.sh, b.d + h.suf, h.un, t, nt);
+    return 0;
+}
+
+// Every row of a checked block parsed, in physical order: visit(row index, byte position, row).  The status is
+// what a full parse reports: the restart-0 key of a V2 block with restarts, shared <= the previous key's length,
+// and every v2_row / v1_row status; the rows before a failing one have been visited.
+template <typename F>
+SDB_DEV int for_each_row(uint32_t version, const Blk &b, F &&visit) {
+    int st = 0;
+    if (version == 2) {
+        uint32_t kp, kn, curlen = 0, pos = 0;
+        if (b.count > 0) st = v2_restart_key(b, 0, kp, kn);  // decode_first_key_at_restart(0)
+        for (uint32_t i = 0; !st && pos < b.data_end; i++) {
+            Row r;
+            if ((st = v2_row(b, pos, r))) break;
+            if (r.sh > curlen) {
+                st = SDB_CORRUPT_BLOCK;
+                break;
+            }
+            visit(i, pos, r);
+            curlen = r.sh + r.un;
+            pos = r.next;
+        }
+    } else {
+        for (uint32_t i = 0; i < b.count; i++) {
+            Row r;
+            if ((st = v1_row(b, i, r))) break;
+            visit(i, boff(b, i), r);
+        }
+    }
+    return st;
+}
+
+// A row's value reference, seq, flags and timestamps into slot i of an out struct (sdb_lookup_out, sdb_scan_out,
+// sdb_get_out).  A value offset is relative to the SST data (base = the block's); an empty value has offset 0; a
+// tombstone has no value (a V2 row still carries a length); a timestamp shows only under its flag.
+template <typename Out>
+SDB_DEV void put_row(const Out &o, uint64_t i, uint64_t base, const Row &r) {
+    const uint32_t vl = (r.flags & SDB_FLAG_TOMBSTONE) ? 0 : r.vl;
+    o.val_off[i] = vl ? base + r.vpos : 0;
+    o.val_len[i] = vl;
+    o.seq[i] = r.seq;
+    o.flags[i] = r.flags;
+    o.create_ts[i] = (r.flags & SDB_FLAG_HAS_CREATE_TS) ? r.cts : 0;
+    o.expire_ts[i] = (r.flags & SDB_FLAG_HAS_EXPIRE_TS) ? r.ets : 0;
 }
 
 // might_contain (filter.rs:124-136) for the filter hash h; an empty bitmap answers false.
@@ -363,7 +435,7 @@ SDB_DEV bool bloom_might_contain(const uint8_t *bloom, uint64_t bloom_len, uint3
 }
 
 // Block::decode bounds + CRC of the block data[s, e) by one wave (lane l), over the wave's LDS image
-// (kLkImg bytes, 64 zeroed bytes before it): the body of k_lk_check and of the multi-SST k_get_check.
+// (kLkImg bytes, 64 zeroed bytes before it): the body of k_check.
 constexpr uint32_t kLkThreads = 256;
 constexpr uint32_t kLkImg = 4096 + 32;
 constexpr uint32_t kLkLds = kCrcTablesLds + (kLkThreads / 64) * (kLkImg + 64);
@@ -404,7 +476,28 @@ SDB_DEV int lk_check_block(const uint8_t *data, uint64_t s, uint64_t e, lu8 *img
     return crc != (uint32_t)be_at(data + s + blen, 4) ? SDB_CHECKSUM_MISMATCH : 0;
 }
 
-// One wave per marked block: Block::decode bounds + CRC -> bstat; clears the marks (sdb_lookup.hip).
-hipError_t launch_lk_check(LookupArgs a, hipStream_t st);
+// The SST of tree block k: the last i with block_base[i] <= k.
+SDB_DEV uint32_t sst_of_block(const sdb_lsm_view &t, uint64_t k) {
+    uint32_t lo = 0, hi = t.num_ssts;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (t.block_base[mid] <= k) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// The block-check pass k_check (sdb_lookup.hip), one wave per marked block: Block::decode bounds + CRC -> bstat;
+// clears the marks.  The blocks are those of one SST (bad == nullptr: v), or of a tree's SSTs end to end (t, block
+// k at t.block_base[sst] + block; nothing is read through t when *bad).
+struct CheckArgs {
+    sdb_sst_view v;
+    sdb_lsm_view t;
+    const uint32_t *bad;
+    uint64_t num_blocks;
+    uint8_t *mark;
+    int32_t *bstat;
+};
+hipError_t launch_check(const CheckArgs &a, hipStream_t st);
 
 }  // namespace sdb

@@ -11,11 +11,12 @@
 // What depends only on the block is computed once per block and shared by every range that touches it;
 // what depends on the range is two clipped blocks (its first and its last).  No per-(range, block) state is
 // stored, so the workspace is O(blocks + ranges) however much the ranges overlap:
-//   k_sc_locate  thread per range: block range (partition_point of sdb_lookup.h), empty-set test
+//   k_sc_locate  thread per range: block range (partition_point of sdb_read.h), empty-set test
 //   k_sc_mark    workgroup per range: marks the blocks it reads
-//   k_lk_check   wave per marked block: bounds + CRC (sdb_lookup.hip, shared)
-//   k_sc_block   thread per read block: every row parsed (status), entries, restored-key bytes, the runs
-//                of equal keys at its head and tail, and whether its last key equals the next block's first
+//   k_check      wave per marked block: bounds + CRC (sdb_lookup.hip, shared)
+//   k_sc_block   thread per read block: every row parsed (for_each_row of sdb_read.h: the status), entries,
+//                restored-key bytes, the runs of equal keys at its head and tail, and whether its last key
+//                equals the next block's first
 //   scans        entries / key bytes / failed / read over blocks
 //   k_sc_edge    thread per range: status (first failing block), the clips [lo, hi) of its first and last
 //                block by the incremental comparators (keys are not materialised), totals
@@ -26,7 +27,7 @@
 //                Descending: entry p of the range's N, in the key group [gs, ge), lands at
 //                N - ge + (p - gs); a group's extent past the item's block comes from the per-block
 //                head / tail runs and joins, never from a pass over the output.
-#include "sdb_lookup.h"
+#include "sdb_read.h"
 #include "sdb_decode.h"
 
 namespace sdb {
@@ -37,7 +38,7 @@ struct ScanArgs {
     sdb_scan_out out;
     uint32_t desc, pad;
     // per block
-    uint8_t *mark;                    // 1 = some range reads it (cleared by k_lk_check)
+    uint8_t *mark;                    // 1 = some range reads it (cleared by k_check)
     int32_t *bstat;                   // -1 = not read, else the block's sdb_status
     uint64_t *cnt, *kb, *bad, *rd;    // entries, restored-key bytes, failed, read
     uint64_t *pc, *pk, *pb, *pr;      // their exclusive scans (num_blocks + 1)
@@ -55,20 +56,10 @@ struct ScanArgs {
     uint32_t *go;                     // 1 = the outputs fit: emit runs
 };
 
-__host__ __device__ inline LookupArgs as_lookup(const ScanArgs &a) {
-    LookupArgs l{};
-    l.v = a.v;
-    l.mark = a.mark;
-    l.bstat = a.bstat;
-    return l;
-}
-
 // Block::decode of block k.  A V2 block without restarts yields nothing descending (the existing
 // descending decode's rule, block_iterator_v2.rs:318-430).
 SDB_DEV int sc_open(const ScanArgs &a, uint64_t k, Blk &b) {
-    LookupArgs l{};
-    l.v = a.v;
-    if (int st = blk_open(l, k, b)) return st;
+    if (int st = blk_open(a.v, k, b)) return st;
     if (a.v.sst_version == 2 && a.desc && b.count == 0) b.data_end = 0;
     return 0;
 }
@@ -91,7 +82,6 @@ __global__ __launch_bounds__(256) void k_sc_locate(ScanArgs a) {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= a.r.n) return;
     const Bound s = start_of(a, r), e = end_of(a, r);
-    const LookupArgs l = as_lookup(a);
     const uint64_t nb = a.v.num_blocks;
     uint64_t start = 0, end = nb;
     if (s.kind > SDB_BOUND_EXCLUDED || e.kind > SDB_BOUND_EXCLUDED) {  // reported by k_sc_edge
@@ -100,11 +90,11 @@ __global__ __launch_bounds__(256) void k_sc_locate(ScanArgs a) {
         return;
     }
     if (s.kind) {  // first_partition_including_or_after_key (partitioned_keyspace.rs:43-68)
-        const uint64_t lt = partition_point(l, s.t, s.n, false);
+        const uint64_t lt = partition_point(a.v, s.t, s.n, false);
         start = lt > 0 ? lt - 1 : 0;
     }
     if (e.kind) {  // last_partition_including_key (:72-83), then :98-106
-        const uint64_t le = partition_point(l, e.t, e.n, true);
+        const uint64_t le = partition_point(a.v, e.t, e.n, true);
         if (le == 0) {
             end = start;
         } else if (e.kind == SDB_BOUND_INCLUDED) {
@@ -201,12 +191,10 @@ SDB_DEV bool sc_first_key(const ScanArgs &a, uint64_t k, const uint8_t *&t, uint
     Blk b;
     if (sc_open(a, k, b)) return false;
     if (a.v.sst_version == 2) {
-        uint32_t p = 0, sh, un, vl;
-        if (b.data_end == 0 || !rdv(b.d, b.data_end, p, sh) || !rdv(b.d, b.data_end, p, un) || !rdv(b.d, b.data_end, p, vl) ||
-            sh != 0 || (uint64_t)p + un > b.data_end)
-            return false;
-        t = b.d + p;
-        nt = un;
+        const V2Hdr h = v2_hdr(b, 0, 0);  // an empty block has no first varint
+        if (!h.ok) return false;
+        t = b.d + h.suf;
+        nt = h.un;
         return true;
     }
     if (b.count == 0 || b.data_end < 4) return false;
@@ -231,20 +219,19 @@ __global__ __launch_bounds__(256) void k_sc_block(ScanArgs a) {
         uint32_t nt = 0;
         // the runs of equal keys and the join with the next block place key groups: descending only
         const bool have_t = a.desc && k + 1 < a.v.num_blocks && sc_first_key(a, k + 1, t, nt);
+        auto count = [&](uint32_t i, const Row &r, bool same) {  // same: row i repeats the key of row i - 1
+            tail = same ? tail + 1 : 1;
+            if (same && head == i) head++;
+            if (i == 0) head = 1;
+            cnt = i + 1;
+            kb += r.sh + r.un;
+        };
+        Cmp c{0, 0, 0};
         if (a.v.sst_version == 2) {
-            uint32_t kp, kn, ri = 0;
+            uint32_t ri = 0;
             bool regular = b.count == 0 || boff(b, 0) == 0;
-            if (b.count > 0) st = v2_restart_key(b, 0, kp, kn);  // decode_first_key_at_restart(0)
-            uint32_t pos = 0, curlen = 0;
-            Cmp c{0, 0, 0};
             KeyTrack T{};
-            while (!st && pos < b.data_end) {
-                Row r;
-                if ((st = v2_row(b, pos, r))) break;
-                if (r.sh > curlen) {
-                    st = SDB_CORRUPT_BLOCK;
-                    break;
-                }
+            st = for_each_row(2, b, [&](uint32_t i, uint32_t pos, const Row &r) {
                 if (ri < b.count && boff(b, ri) == pos) {  // regions start at restarts with shared == 0, in order
                     if (r.sh != 0) regular = false;
                     ri++;
@@ -253,34 +240,18 @@ __global__ __launch_bounds__(256) void k_sc_block(ScanArgs a) {
                 }
                 const bool same = a.desc && kt_same(b, T, r, pos);
                 if (a.desc) kt_take(T, r, pos);
-                tail = same ? tail + 1 : 1;
-                if (same && head == cnt) head++;
-                if (cnt == 0) head = 1;
-                if (have_t) c = cnt == 0 ? cmp_bytes(b.d + r.suf, r.un, t, nt, 0) : cmp_next(c, r.sh, b.d + r.suf, r.un, t, nt);
-                curlen = r.sh + r.un;
-                cnt++;
-                kb += curlen;
-                pos = r.next;
-            }
+                count(i, r, same);
+                if (have_t) c = i == 0 ? cmp_bytes(b.d + r.suf, r.un, t, nt, 0) : cmp_next(c, r.sh, b.d + r.suf, r.un, t, nt);
+            });
             if (!st && a.desc && (ri != b.count || !regular)) st = SDB_CORRUPT_BLOCK;  // the descending decode's rule
             join = have_t && cnt > 0 && c.c == 0;
         } else {
             Row p{};
-            for (uint32_t i = 0; i < b.count; i++) {
-                Row r;
-                if ((st = v1_row(b, i, r))) break;
-                const bool same = a.desc && i > 0 && sc_same(a, b, r, p, 0);
-                tail = same ? tail + 1 : 1;
-                if (same && head == i) head++;
-                if (i == 0) head = 1;
-                kb += r.sh + r.un;
+            st = for_each_row(1, b, [&](uint32_t i, uint32_t, const Row &r) {
+                count(i, r, a.desc && i > 0 && sc_same(a, b, r, p, 0));
                 p = r;
-            }
-            cnt = b.count;
-            if (!st && have_t && cnt > 0) {
-                Cmp c;
-                join = v1_cmp(b, b.count - 1, t, nt, c) == 0 && c.c == 0;
-            }
+            });
+            if (!st && have_t && cnt > 0) join = v1_cmp(b, b.count - 1, t, nt, c) == 0 && c.c == 0;
         }
     }
     if (st > 0) cnt = kb = head = tail = 0;
@@ -524,15 +495,8 @@ __global__ __launch_bounds__(256) void k_sc_emit(ScanArgs a) {
                     sc_copy(dst + lead.sh, b.d + lead.suf, lead.un);
                     leadkey = dst;
                 }
-                const uint64_t o = E0 + di;
-                if (v2 && (q.flags & SDB_FLAG_TOMBSTONE)) q.vl = 0;
-                a.out.key_off[o] = K0 + dk;
-                a.out.val_off[o] = q.vl ? b.base + q.vpos : 0;
-                a.out.val_len[o] = q.vl;
-                a.out.seq[o] = q.seq;
-                a.out.flags[o] = q.flags;
-                a.out.create_ts[o] = (q.flags & SDB_FLAG_HAS_CREATE_TS) ? q.cts : 0;
-                a.out.expire_ts[o] = (q.flags & SDB_FLAG_HAS_EXPIRE_TS) ? q.ets : 0;
+                a.out.key_off[E0 + di] = K0 + dk;
+                put_row(a.out, E0 + di, b.base, q);
             }
             prevkey = leadkey;
             kcur += (uint64_t)g * L;
@@ -542,97 +506,61 @@ __global__ __launch_bounds__(256) void k_sc_emit(ScanArgs a) {
     }
 }
 
-struct ScanWorkspace {
-    uint64_t mark, bstat, cnt, kb, bad, rd, pc, pk, pb, pr, head, tail, join;
-    uint64_t rempty, lo_f, efb, elb, nf, kbf, nl, kbl, rn, rkb, ritems, rfail, rks, ris, rfs, tx, ty, misc, total;
-};
-static ScanWorkspace scan_workspace_layout(uint64_t nb, uint64_t n) {
-    ScanWorkspace w{};
-    uint64_t off = 0;
-    auto take = [&](uint64_t bytes) {
-        const uint64_t r = off;
-        off += (bytes + 255) & ~255ull;
-        return r;
-    };
-    w.mark = take(nb + 1);
-    w.bstat = take(4 * (nb + 1));
-    w.cnt = take(8 * (nb + 1));
-    w.kb = take(8 * (nb + 1));
-    w.bad = take(8 * (nb + 1));
-    w.rd = take(8 * (nb + 1));
-    w.pc = take(8 * (nb + 2));
-    w.pk = take(8 * (nb + 2));
-    w.pb = take(8 * (nb + 2));
-    w.pr = take(8 * (nb + 2));
-    w.head = take(4 * (nb + 1));
-    w.tail = take(4 * (nb + 1));
-    w.join = take(nb + 1);
-    w.rempty = take(n + 1);
-    w.lo_f = take(4 * (n + 1));
-    w.efb = take(4 * (n + 1));
-    w.elb = take(4 * (n + 1));
-    w.nf = take(8 * (n + 1));
-    w.kbf = take(8 * (n + 1));
-    w.nl = take(8 * (n + 1));
-    w.kbl = take(8 * (n + 1));
-    w.rn = take(8 * (n + 1));
-    w.rkb = take(8 * (n + 1));
-    w.ritems = take(8 * (n + 1));
-    w.rfail = take(8 * (n + 1));
-    w.rks = take(8 * (n + 2));
-    w.ris = take(8 * (n + 2));
-    w.rfs = take(8 * (n + 2));
-    const uint64_t m = nb > n ? nb : n, nt = (m + 1023) / 1024 + 2;
-    w.tx = take(8 * nt);
-    w.ty = take(8 * nt);
-    w.misc = take(64);
-    w.total = off;
-    return w;
+// The workspace arrays of a scan of a.r.n ranges over a.v.num_blocks blocks, bound into a from w; -> their size.
+static uint64_t scan_bind(ScanArgs &a, uint8_t *w) {
+    const uint64_t nb = a.v.num_blocks, n = a.r.n, nt = ((nb > n ? nb : n) + 1023) / 1024 + 2;  // nt: scan tiles
+    Carver c{w, 0};
+    c.take(a.mark, nb + 1);
+    c.take(a.bstat, nb + 1);
+    c.take(a.cnt, nb + 1);
+    c.take(a.kb, nb + 1);
+    c.take(a.bad, nb + 1);
+    c.take(a.rd, nb + 1);
+    c.take(a.pc, nb + 2);
+    c.take(a.pk, nb + 2);
+    c.take(a.pb, nb + 2);
+    c.take(a.pr, nb + 2);
+    c.take(a.head, nb + 1);
+    c.take(a.tail, nb + 1);
+    c.take(a.join, nb + 1);
+    c.take(a.rempty, n + 1);
+    c.take(a.lo_f, n + 1);
+    c.take(a.efb, n + 1);
+    c.take(a.elb, n + 1);
+    c.take(a.nf, n + 1);
+    c.take(a.kbf, n + 1);
+    c.take(a.nl, n + 1);
+    c.take(a.kbl, n + 1);
+    c.take(a.rn, n + 1);
+    c.take(a.rkb, n + 1);
+    c.take(a.ritems, n + 1);
+    c.take(a.rfail, n + 1);
+    c.take(a.rks, n + 2);
+    c.take(a.ris, n + 2);
+    c.take(a.rfs, n + 2);
+    c.take(a.tx, nt);
+    c.take(a.ty, nt);
+    c.take(a.firstbad, 8);  // 64 bytes: the word, then go
+    if (w) a.go = (uint32_t *)(a.firstbad + 1);
+    return c.off;
 }
 
-uint64_t scan_workspace_bytes(uint64_t num_blocks, uint64_t nranges) { return scan_workspace_layout(num_blocks, nranges).total; }
+uint64_t scan_workspace_bytes(uint64_t num_blocks, uint64_t nranges) {
+    ScanArgs a{};
+    a.v.num_blocks = num_blocks;
+    a.r.n = nranges;
+    return scan_bind(a, nullptr);
+}
 
 hipError_t launch_scan(const sdb_sst_view &v, const sdb_scan_ranges &r, uint32_t desc, const sdb_scan_out &out, uint8_t *w,
                        hipStream_t st) {
     const uint64_t nb = v.num_blocks, n = r.n;
-    const ScanWorkspace L = scan_workspace_layout(nb, n);
     ScanArgs a{};
     a.v = v;
     a.r = r;
     a.out = out;
     a.desc = desc;
-    a.mark = w + L.mark;
-    a.bstat = (int32_t *)(w + L.bstat);
-    a.cnt = (uint64_t *)(w + L.cnt);
-    a.kb = (uint64_t *)(w + L.kb);
-    a.bad = (uint64_t *)(w + L.bad);
-    a.rd = (uint64_t *)(w + L.rd);
-    a.pc = (uint64_t *)(w + L.pc);
-    a.pk = (uint64_t *)(w + L.pk);
-    a.pb = (uint64_t *)(w + L.pb);
-    a.pr = (uint64_t *)(w + L.pr);
-    a.head = (uint32_t *)(w + L.head);
-    a.tail = (uint32_t *)(w + L.tail);
-    a.join = w + L.join;
-    a.rempty = w + L.rempty;
-    a.lo_f = (uint32_t *)(w + L.lo_f);
-    a.efb = (uint32_t *)(w + L.efb);
-    a.elb = (uint32_t *)(w + L.elb);
-    a.nf = (uint64_t *)(w + L.nf);
-    a.kbf = (uint64_t *)(w + L.kbf);
-    a.nl = (uint64_t *)(w + L.nl);
-    a.kbl = (uint64_t *)(w + L.kbl);
-    a.rn = (uint64_t *)(w + L.rn);
-    a.rkb = (uint64_t *)(w + L.rkb);
-    a.ritems = (uint64_t *)(w + L.ritems);
-    a.rfail = (uint64_t *)(w + L.rfail);
-    a.rks = (uint64_t *)(w + L.rks);
-    a.ris = (uint64_t *)(w + L.ris);
-    a.rfs = (uint64_t *)(w + L.rfs);
-    a.tx = (uint64_t *)(w + L.tx);
-    a.ty = (uint64_t *)(w + L.ty);
-    a.firstbad = (unsigned long long *)(w + L.misc);
-    a.go = (uint32_t *)(w + L.misc + 8);
+    scan_bind(a, w);
     hipError_t e;
     if (n == 0 || nb == 0) {  // every range is empty
         if ((e = hipMemsetAsync(out.summary, 0, sizeof(sdb_scan_summary), st)) != hipSuccess) return e;
@@ -649,7 +577,7 @@ hipError_t launch_scan(const sdb_sst_view &v, const sdb_scan_ranges &r, uint32_t
     hipLaunchKernelGGL(k_sc_init, dim3(1), dim3(64), 0, st, a);
     hipLaunchKernelGGL(k_sc_locate, dim3(rb), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_sc_mark, dim3((uint32_t)(n < 4096 ? n : 4096)), dim3(256), 0, st, a);
-    if ((e = launch_lk_check(as_lookup(a), st)) != hipSuccess) return e;
+    if ((e = launch_check(CheckArgs{v, {}, nullptr, nb, a.mark, a.bstat}, st)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_sc_block, dim3(bw), dim3(64), 0, st, a);
     if ((e = launch_excl_scan2(a.cnt, a.kb, nb, a.tx, a.ty, a.pc, a.pk, st)) != hipSuccess) return e;
     if ((e = launch_excl_scan2(a.bad, a.rd, nb, a.tx, a.ty, a.pb, a.pr, st)) != hipSuccess) return e;

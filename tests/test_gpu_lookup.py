@@ -82,6 +82,44 @@ def test_lookup_d1_bloom_corrupt(rt, desc):
     assert (ref.status == _abi.SDB_CHECKSUM_MISMATCH).sum() == 3
 
 
+@pytest.mark.parametrize("version", [1, 2])
+@pytest.mark.parametrize("desc", [False, True])
+def test_lookup_workspace_canaries(rt, version, desc):
+    """The C ABI with a workspace of exactly sdb_sst_lookup_workspace_bytes at an odd offset inside a
+    0xA5-filled buffer: every field as the oracle's, and not one byte outside the workspace changes."""
+    import ctypes as C
+    import torch
+    from slatedb_amd.batch import Batch
+    es = [(b"key%04d" % (2 * i), _abi.KIND_TOMBSTONE if i == 21 else _abi.KIND_VALUE, b"v" * 40, 1000 - i,
+           7 + i if i % 3 == 0 else None, 90 + i if i % 4 == 1 else None) for i in range(60)]
+    b = Batch.from_entries(es)
+    e = O.encode_sst(b, O.params(block_size=1024, sst_version=version))
+    nb = len(e.block_off) - 1
+    assert nb in (3, 4)
+    ik, iko = O.sst_index_keys(b, e)
+    keys = [b"key%04d" % i for i in (0, 1, 14, 31, 32, 42, 43, 58, 59, 60, 77, 90, 117, 118)] + [b"a", b"key0119", b"key9999"]
+    koff = np.zeros(len(keys) + 1, np.uint64)
+    koff[1:] = np.cumsum([len(k) for k in keys])
+    dv = {"data": _dev(e.data), "block_off": _dev(e.block_off), "index_keys": _dev(ik), "index_key_off": _dev(iko),
+          "key_bytes": _dev(np.frombuffer(b"".join(keys), np.uint8).copy()), "key_off": _dev(koff)}
+    n = len(keys)
+    res = {f: torch.zeros(n, dtype=getattr(torch, dt), device="cuda") for f, dt in rt.LOOKUP_FIELDS}
+    v = _abi.SstView(dv["data"].data_ptr(), dv["block_off"].data_ptr(), nb, dv["index_keys"].data_ptr(),
+                     dv["index_key_off"].data_ptr(), None, 0, 0, version, 0)
+    out = _abi.LookupOut(*[res[f].data_ptr() for f, _ in rt.LOOKUP_FIELDS])
+    wsb, lead = rt.lib().sdb_sst_lookup_workspace_bytes(nb, n), 257
+    big = torch.full((lead + wsb + 512,), 0xA5, dtype=torch.uint8, device="cuda")
+    assert rt.lib().sdb_sst_lookup(C.byref(v), dv["key_bytes"].data_ptr(), dv["key_off"].data_ptr(), n, int(desc), C.byref(out),
+                                   big.data_ptr() + lead, wsb, None) == 0
+    torch.cuda.synchronize()
+    ref = O.sst_lookup(e.data, e.block_off, ik, iko, keys, descending=desc, sst_version=version)
+    for f, _ in O.LOOKUP_FIELDS:
+        assert np.array_equal(res[f].cpu().numpy().astype(np.int64), getattr(ref, f).astype(np.int64)), f
+    assert (ref.state == _abi.LOOKUP_FOUND).sum() >= 6 and (ref.state == _abi.LOOKUP_POSITIONED).sum() >= 6
+    assert (ref.state == _abi.LOOKUP_EXHAUSTED).sum() >= 1
+    assert bool((big[:lead] == 0xA5).all()) and bool((big[lead + wsb:] == 0xA5).all())
+
+
 def test_lookup_d3_mixed(rt):
     b = datasets.d3(n=3000)
     for version in (1, 2):
