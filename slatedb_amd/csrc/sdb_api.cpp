@@ -61,11 +61,6 @@ sdb_status check_params(const sdb_sst_params *p) {
     return SDB_OK;
 }
 
-template <typename T>
-T *carve(void *base, uint64_t off) {
-    return reinterpret_cast<T *>(reinterpret_cast<uint8_t *>(base) + off);
-}
-
 }  // namespace
 
 extern "C" {
@@ -122,13 +117,15 @@ sdb_status sdb_encode_bounds(uint64_t n, uint64_t total_key_bytes, uint64_t tota
 }  // extern "C"
 
 namespace {
-// One SST's workspace region (256-byte multiple) inside a set's workspace.
+// One SST's workspace region (256-byte multiple) inside a set's workspace: the encode's arrays, then the filter
+// build's (the prefix filter's scratch, or the larger of the fused bloom's slots and the standalone build's).
+// The 256 bytes after those are spare: they keep the public sizes what they have always been.
 bool prefix_filter(const sdb_sst_params *p) { return p->prefix_kind != SDB_PREFIX_NONE || p->no_whole_key; }
 uint64_t sst_ws_bytes(uint64_t n, const sdb_sst_params *p) {
-    if (prefix_filter(p))  // the prefix filter's scratch instead of the fused bloom's slots
-        return (encode_workspace_offsets(n, false).bloom_rep + prefix_workspace_bytes(n) + 511) & ~255ull;
+    const uint64_t fixed = encode_ws_layout(n, nullptr);
+    if (prefix_filter(p)) return fixed + prefix_workspace_bytes(n) + 256;
     const uint64_t fb = p->bloom_bits_per_key ? filter_bytes_for(n, p->bloom_bits_per_key) : 0;
-    return (encode_workspace_layout(n, fb, num_probes_for(p->bloom_bits_per_key)).total + 255) & ~255ull;
+    return fixed + (fb ? encode_bloom_workspace_bytes(n, num_probes_for(p->bloom_bits_per_key), fb) + 256 : 0);
 }
 
 sdb_status check_sst(const sdb_kv_batch *b, const sdb_sst_params *p, const sdb_sst_out *out) {
@@ -177,10 +174,9 @@ SstSlot plan_slot(const sdb_kv_batch *b, const sdb_sst_params *p, const sdb_sst_
     s.ws = ws;
     s.num_probes = want_filter ? num_probes_for(p->bloom_bits_per_key) : 0;
     s.filter_built = want_filter ? 1 : 0;
-    s.has_filter_ws = (p->bloom_bits_per_key && filter_bytes_for(n, p->bloom_bits_per_key)) ? 1 : 0;
     s.nchunks = (uint32_t)((n + kChunk - 1) / kChunk);
     s.nfacts = (uint32_t)((n + kFactsEntries - 1) / kFactsEntries);
-    fill_ws_layout(s);
+    encode_ws_layout(n, s.wso);
     {   // chunks per group: about sqrt(nchunks), so k_enum walks <= ~2 sqrt(nchunks) tables
         uint32_t g = 16;
         while ((uint64_t)g * g < s.nchunks) g++;
@@ -244,7 +240,7 @@ sdb_status sdb_encode_ssts(uint32_t count, const sdb_kv_batch *batches, const sd
     if (!device_ok()) return SDB_DEVICE_ERROR;
     if (!workspace || workspace_bytes < sdb_encode_ssts_workspace_bytes(count, batches, p)) return SDB_INVALID_ARGUMENT;
     hipStream_t s = S(stream);
-    uint8_t *ws = (uint8_t *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    uint8_t *ws = ws_align(workspace);
     SstSet P = set_header(p);
     size_t bin_lds = 0, fill_lds = 0;
     auto flush = [&]() -> bool {
@@ -268,10 +264,10 @@ sdb_status sdb_encode_ssts(uint32_t count, const sdb_kv_batch *batches, const sd
             if (slot.prefix_bloom)
                 e = launch_bloom_prefix(slot.key_bytes, slot.key_off, batches[i].prefix_len, slot.n, p->bloom_bits_per_key,
                                         p->prefix_kind, p->prefix_arg, p->no_whole_key ? 0 : 1, slot.bloom_out,
-                                        outs[i].bloom_cap, (uint64_t *)a.bloom_len_dev, (void *)a.bq.count, s);
+                                        outs[i].bloom_cap, (uint64_t *)a.bloom_len_dev, (uint8_t *)a.bq.count, s);
             else
                 e = launch_bloom_build(slot.key_bytes, slot.key_off, slot.n, slot.num_probes, slot.bloom_out, slot.bloom_len,
-                                       (void *)a.bq.count, s);
+                                       (uint8_t *)a.bq.count, s);
             if (e != hipSuccess) return SDB_DEVICE_ERROR;
             stage_mark(s, kStBloom, false);
         }
@@ -318,7 +314,7 @@ sdb_status sdb_bloom_build(const uint8_t *key_bytes, const uint64_t *key_off, ui
     // the word that holds the last byte
     if (((uintptr_t)bitmap & 3) || (!workspace && fb && bitmap_bytes < ((fb + 3) & ~3ull))) return SDB_INVALID_ARGUMENT;
     if (workspace && workspace_bytes < sdb_bloom_workspace_bytes(n, bits_per_key)) return SDB_INVALID_ARGUMENT;
-    if (launch_bloom_build(key_bytes, key_off, n, num_probes_for(bits_per_key), bitmap, fb, workspace, S(stream)) != hipSuccess)
+    if (launch_bloom_build(key_bytes, key_off, n, num_probes_for(bits_per_key), bitmap, fb, ws_align(workspace), S(stream)) != hipSuccess)
         return SDB_DEVICE_ERROR;
     return SDB_OK;
 }
@@ -336,7 +332,7 @@ sdb_status sdb_bloom_build_prefix(const uint8_t *key_bytes, const uint64_t *key_
         !workspace || workspace_bytes < sdb_bloom_prefix_workspace_bytes(n))
         return SDB_INVALID_ARGUMENT;
     if (launch_bloom_prefix(key_bytes, key_off, prefix_len, n, bits_per_key, prefix_kind, prefix_arg, whole_key ? 1 : 0,
-                            bitmap, bitmap_cap, bloom_len, workspace, S(stream)) != hipSuccess)
+                            bitmap, bitmap_cap, bloom_len, ws_align(workspace), S(stream)) != hipSuccess)
         return SDB_DEVICE_ERROR;
     return SDB_OK;
 }
@@ -365,7 +361,11 @@ sdb_status sdb_bloom_might_contain(const uint8_t *bitmap, uint64_t bitmap_bytes,
     return SDB_OK;
 }
 
-uint64_t sdb_decode_workspace_bytes(uint64_t nblocks) { return decode_workspace_layout(nblocks).total; }
+uint64_t sdb_decode_workspace_bytes(uint64_t nblocks) {
+    DecodeArgs a{};
+    a.nblocks = nblocks;
+    return decode_bind(a, nullptr);
+}
 
 static sdb_status decode_common(const uint8_t *blocks, const uint64_t *block_off, const uint64_t *block_end,
                                 uint64_t nblocks, uint16_t sst_version, const sdb_decoded_out *out, void *workspace,
@@ -374,8 +374,7 @@ static sdb_status decode_common(const uint8_t *blocks, const uint64_t *block_off
     if (sst_version != 1 && sst_version != 2) return SDB_INVALID_VERSION;  // block_iterator.rs:60-77
     if (nblocks && (!blocks || !block_off)) return SDB_INVALID_ARGUMENT;
     if (!device_ok()) return SDB_DEVICE_ERROR;
-    DecodeWorkspace wl = decode_workspace_layout(nblocks);
-    if (!workspace || workspace_bytes < wl.total) return SDB_INVALID_ARGUMENT;
+    if (!workspace || workspace_bytes < sdb_decode_workspace_bytes(nblocks)) return SDB_INVALID_ARGUMENT;
     DecodeArgs a{};
     a.blocks = blocks;
     a.block_off = block_off;
@@ -385,18 +384,7 @@ static sdb_status decode_common(const uint8_t *blocks, const uint64_t *block_off
     a.descending = (flags & SDB_DECODE_DESCENDING) ? 1u : 0u;
     a.fail_fast = (flags & SDB_DECODE_FAIL_FAST) ? 1u : 0u;
     a.out = *out;
-    a.cnt = carve<uint64_t>(workspace, wl.cnt);
-    a.kbytes = carve<uint64_t>(workspace, wl.kbytes);
-    a.flag = carve<uint8_t>(workspace, wl.flag);
-    a.rcnt = carve<uint64_t>(workspace, wl.rcnt);
-    a.rowpos = carve<uint16_t>(workspace, wl.rowpos);
-    a.ent_start = carve<uint64_t>(workspace, wl.ent_start);
-    a.key_start = carve<uint64_t>(workspace, wl.key_start);
-    a.tile_x = carve<uint64_t>(workspace, wl.tile_x);
-    a.tile_y = carve<uint64_t>(workspace, wl.tile_y);
-    a.err = carve<unsigned long long>(workspace, wl.err);
-    a.nbad = carve<unsigned long long>(workspace, wl.nbad);
-    a.done = carve<uint32_t>(workspace, wl.done);
+    decode_bind(a, ws_align(workspace));
     a.bad_block = out->bad_block;
     a.bad_cap = out->bad_cap;
     if (launch_decode(a, S(stream)) != hipSuccess) return SDB_DEVICE_ERROR;
@@ -425,7 +413,7 @@ sdb_status sdb_decode_blocks_at(const uint8_t *arena, const uint64_t *block_star
     return decode_common(arena, block_start, block_end, nblocks, sst_version, out, workspace, workspace_bytes, stream);
 }
 
-uint64_t sdb_decompress_workspace_bytes(uint64_t nblocks) { return decompress_workspace_bytes(nblocks); }
+uint64_t sdb_decompress_workspace_bytes(uint64_t nblocks) { return decompress_workspace_bytes(nblocks) + 256; }
 
 static bool lz_codec(uint32_t codec) {  // every compressing codec of CompressionCodec (format/sst.rs:884-917)
     return codec == SDB_CODEC_LZ4 || codec == SDB_CODEC_SNAPPY || codec == SDB_CODEC_ZLIB || codec == SDB_CODEC_ZSTD;
@@ -435,9 +423,9 @@ sdb_status sdb_decompress_plan(uint32_t codec, const uint8_t *blocks, const uint
                                uint64_t *out_start, void *workspace, uint64_t workspace_bytes, void *stream) {
     if (!lz_codec(codec)) return SDB_INVALID_ARGUMENT;
     if (!out_start || (nblocks && (!blocks || !block_off))) return SDB_INVALID_ARGUMENT;
-    if (!workspace || workspace_bytes < decompress_workspace_bytes(nblocks)) return SDB_INVALID_ARGUMENT;
+    if (!workspace || workspace_bytes < sdb_decompress_workspace_bytes(nblocks)) return SDB_INVALID_ARGUMENT;
     if (!device_ok()) return SDB_DEVICE_ERROR;
-    return launch_decompress_plan(codec, blocks, block_off, nblocks, out_start, workspace, S(stream)) == hipSuccess
+    return launch_decompress_plan(codec, blocks, block_off, nblocks, out_start, ws_align(workspace), S(stream)) == hipSuccess
                ? SDB_OK : SDB_DEVICE_ERROR;
 }
 
@@ -451,7 +439,7 @@ sdb_status sdb_decompress_blocks(uint32_t codec, const uint8_t *blocks, const ui
                                  (unsigned long long *)err, S(stream)) == hipSuccess ? SDB_OK : SDB_DEVICE_ERROR;
 }
 
-uint64_t sdb_decompress_once_workspace_bytes(uint64_t nblocks) { return decompress_once_workspace_bytes(nblocks); }
+uint64_t sdb_decompress_once_workspace_bytes(uint64_t nblocks) { return decompress_once_workspace_bytes(nblocks) + 256; }
 
 sdb_status sdb_decompress_blocks_once(uint32_t codec, const uint8_t *blocks, const uint64_t *block_off, uint64_t nblocks,
                                       uint64_t slot_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_start,
@@ -459,13 +447,13 @@ sdb_status sdb_decompress_blocks_once(uint32_t codec, const uint8_t *blocks, con
                                       void *stream) {
     if (!lz_codec(codec)) return SDB_INVALID_ARGUMENT;
     if (!err || !out_start || (nblocks && (!blocks || !block_off || !out_end || (out_cap && !out)))) return SDB_INVALID_ARGUMENT;
-    if (!workspace || workspace_bytes < decompress_once_workspace_bytes(nblocks)) return SDB_INVALID_ARGUMENT;
+    if (!workspace || workspace_bytes < sdb_decompress_once_workspace_bytes(nblocks)) return SDB_INVALID_ARGUMENT;
     if (codec == SDB_CODEC_ZLIB && (slot_bytes < 8 || slot_bytes > (1ull << 32) ||
                                     (nblocks && out_cap / nblocks < slot_bytes)))
         return SDB_INVALID_ARGUMENT;
     if (!device_ok()) return SDB_DEVICE_ERROR;
     return launch_decompress_once(codec, blocks, block_off, nblocks, slot_bytes, out, out_cap, out_start, out_end,
-                                  (unsigned long long *)err, workspace, S(stream)) == hipSuccess ? SDB_OK
+                                  (unsigned long long *)err, ws_align(workspace), S(stream)) == hipSuccess ? SDB_OK
                                                                                                  : SDB_DEVICE_ERROR;
 }
 
@@ -481,14 +469,14 @@ sdb_status sdb_compress_blocks(uint32_t codec, const uint8_t *blocks, const uint
     if (!workspace || workspace_bytes < sdb_compress_workspace_bytes(nblocks, in_bytes)) return SDB_INVALID_ARGUMENT;
     if (!device_ok()) return SDB_DEVICE_ERROR;
     return launch_compress(codec, blocks, block_off, nblocks, in_bytes, out, out_cap, out_off,
-                           (unsigned long long *)err, workspace, S(stream)) == hipSuccess ? SDB_OK : SDB_DEVICE_ERROR;
+                           (unsigned long long *)err, ws_align(workspace), S(stream)) == hipSuccess ? SDB_OK : SDB_DEVICE_ERROR;
 }
 
 uint64_t sdb_merge_runs_workspace_bytes(const sdb_run *runs, uint32_t nruns) {
     if (nruns && !runs) return 0;
-    uint64_t total = 0;
-    for (uint32_t r = 0; r < nruns; r++) total += runs[r].n;
-    return merge_workspace_layout(total).total + 256;
+    MergeArgs a{};
+    for (uint32_t r = 0; r < nruns; r++) a.total += runs[r].n;
+    return merge_bind(a, nullptr) + 256;
 }
 
 sdb_status sdb_merge_runs(const sdb_run *runs, uint32_t nruns, const sdb_retention *ret, const sdb_merged_out *out,
@@ -535,7 +523,7 @@ sdb_status sst_cuts_padded(const sdb_kv_batch *batch, const sdb_sst_params *para
     if (cut_cap < n + 1 || (n && (!batch->key_bytes || !batch->key_off || !batch->val_off))) return SDB_INVALID_ARGUMENT;
     if (!device_ok()) return SDB_DEVICE_ERROR;
     if (!workspace || workspace_bytes < sdb_sst_cuts_workspace_bytes(n, params)) return SDB_INVALID_ARGUMENT;
-    uint8_t *ws = (uint8_t *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    uint8_t *ws = ws_align(workspace);
     if (!n) {
         if (hipMemsetAsync(cut_start, 0, 8, s) != hipSuccess || hipMemsetAsync(num_ssts, 0, 8, s) != hipSuccess)
             return SDB_DEVICE_ERROR;
@@ -579,7 +567,7 @@ sdb_status sdb_sst_lookup(const sdb_sst_view *sst, const uint8_t *key_bytes, con
         return SDB_INVALID_ARGUMENT;
     if (!device_ok()) return SDB_DEVICE_ERROR;
     if (!workspace || workspace_bytes < sdb_sst_lookup_workspace_bytes(sst->num_blocks, nkeys)) return SDB_INVALID_ARGUMENT;
-    uint8_t *w = (uint8_t *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    uint8_t *w = ws_align(workspace);
     if (launch_lookup(*sst, key_bytes, key_off, nkeys, descending ? 1u : 0u, *out, w, S(stream)) != hipSuccess)
         return SDB_DEVICE_ERROR;
     return SDB_OK;
@@ -612,7 +600,7 @@ sdb_status sdb_sst_scan(const sdb_sst_view *sst, const sdb_scan_ranges *ranges, 
                 return SDB_INVALID_ARGUMENT;
         return SDB_DEVICE_ERROR;
     }
-    uint8_t *w = (uint8_t *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    uint8_t *w = ws_align(workspace);
     if (launch_scan(*sst, *ranges, descending ? 1u : 0u, *out, w, S(stream)) != hipSuccess) return SDB_DEVICE_ERROR;
     return SDB_OK;
 }
@@ -639,7 +627,7 @@ sdb_status sdb_lsm_get(const sdb_lsm_view *lsm, const uint8_t *key_bytes, const 
         workspace_bytes < sdb_lsm_get_workspace_bytes(lsm->total_blocks, lsm->num_ssts, lsm->num_runs, nkeys))
         return SDB_INVALID_ARGUMENT;
     if (!device_ok()) return SDB_DEVICE_ERROR;
-    uint8_t *w = (uint8_t *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    uint8_t *w = ws_align(workspace);
     if (launch_get(*lsm, key_bytes, key_off, nkeys, max_seq, *out, w, S(stream)) != hipSuccess) return SDB_DEVICE_ERROR;
     return SDB_OK;
 }
@@ -1249,17 +1237,12 @@ sdb_status sdb_decoder_decode_host(sdb_decoder *d, const uint8_t *blocks, const 
     uint64_t cap_e = total / 12 + 16;
     uint64_t key_cap = total * 4 + 4096;
     for (int attempt = 0; attempt < 2; attempt++) {
-        uint64_t off = 0;
-        auto take = [&](uint64_t bytes) {
-            uint64_t rr = off;
-            off += (bytes + 255) & ~255ull;
-            return rr;
-        };
-        uint64_t o_bes = take(8 * (nblocks + 1)), o_ka = take(key_cap), o_ko = take(8 * (cap_e + 1));
-        uint64_t o_vo = take(8 * cap_e), o_vl = take(4 * cap_e), o_seq = take(8 * cap_e), o_fl = take(cap_e);
-        uint64_t o_ct = take(8 * cap_e), o_et = take(8 * cap_e), o_bad = take(4 * (nblocks + 1));
-        uint64_t o_sm = take(sizeof(sdb_decode_summary));
-        uint64_t out_total = off;
+        Carver c{nullptr, 0};  // the outputs' offsets in the device buffer and in its host mirror
+        uint64_t o_bes = c.bytes(8 * (nblocks + 1)), o_ka = c.bytes(key_cap), o_ko = c.bytes(8 * (cap_e + 1));
+        uint64_t o_vo = c.bytes(8 * cap_e), o_vl = c.bytes(4 * cap_e), o_seq = c.bytes(8 * cap_e), o_fl = c.bytes(cap_e);
+        uint64_t o_ct = c.bytes(8 * cap_e), o_et = c.bytes(8 * cap_e), o_bad = c.bytes(4 * (nblocks + 1));
+        uint64_t o_sm = c.bytes(sizeof(sdb_decode_summary));
+        uint64_t out_total = c.off;
         uint64_t in_total = ((total + 16 + 255) & ~255ull) + 8 * (nblocks + 1);
         uint64_t wsb = sdb_decode_workspace_bytes(nblocks);
         if (d->h_in.ensure(in_total) || d->d_in.ensure(in_total) || d->h_out.ensure(out_total) ||
@@ -1335,6 +1318,5 @@ extern "C" uint64_t sdb_diag_bloom_slots(uint64_t n, const sdb_sst_params *p, ui
     *tiles = pl.tiles;
     *nslices = pl.nslices;
     *cap = bloom_slot_cap(pl);
-    const uint64_t off = sdb::encode_workspace_layout(n, fb, k).bloom_rep;
-    return (off + 255) & ~255ull;
+    return sdb::encode_ws_layout(n, nullptr);
 }

@@ -502,7 +502,5 @@ uint32_t bloom_slot_cap(const BloomPlan &pl);
 bool bloom_plan_fits(const BloomPlan &pl);
 size_t bloom_bin_lds(const BloomPlan &pl);
 size_t bloom_fill_lds(const BloomPlan &pl);
-uint64_t bloom_slots_bytes(const BloomPlan &pl);
-BloomSlots bloom_slots(void *ws, const BloomPlan &pl);
 
 }  // namespace sdb

@@ -128,13 +128,11 @@ static bool dense_fits(const DensePlan &d) {
     return d.k >= 1 && d.k <= 15 && d.m >= 2 && d.S <= kDenseMaxSlices && (uint64_t)d.T * d.k < 65536 &&
            dense_sort_lds(d) <= kBinLds && dense_or_lds(d) <= kOrLds;
 }
-static uint64_t dense_ws_bytes(const DensePlan &d) {
-    return 256 + (((uint64_t)d.tiles * d.rec_stride * 2 + 255) & ~255ull) + (uint64_t)d.tiles * d.tab_stride * 2;
-}
-static void dense_carve(DensePlan &d, void *ws) {
-    uint8_t *w = (uint8_t *)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-    d.rec = (uint16_t *)w;
-    d.tab = (uint16_t *)(w + (((uint64_t)d.tiles * d.rec_stride * 2 + 255) & ~255ull));
+static uint64_t dense_bind(DensePlan &d, uint8_t *w) {
+    Carver c{w, 0};
+    c.take(d.rec, d.tiles * d.rec_stride);
+    c.take(d.tab, (uint64_t)d.tiles * d.tab_stride);
+    return c.off;
 }
 
 // (h0, d0) of keys k0 + tid + j * kDenseThreads (j < KPT, only those < nk are meaningful).  Every load
@@ -403,7 +401,7 @@ static size_t dense_or_lds(const DensePlan &d) {  // the slices' bits, then one 
 }
 
 static hipError_t launch_bloom_dense(const uint8_t *key_bytes, const uint64_t *key_off, uint64_t n, DensePlan d,
-                                     uint8_t *bitmap, uint64_t bitmap_bytes, void *ws, hipStream_t st) {
+                                     uint8_t *bitmap, uint64_t bitmap_bytes, uint8_t *w, hipStream_t st) {
     static std::once_flag attrs;
     static hipError_t attr_err = hipSuccess;
     std::call_once(attrs, [] {
@@ -417,7 +415,7 @@ static hipError_t launch_bloom_dense(const uint8_t *key_bytes, const uint64_t *k
                                            (int)kOrLds);
     });
     if (attr_err != hipSuccess) return attr_err;
-    dense_carve(d, ws);
+    dense_bind(d, w);
     if (d.k == 6)  // 10 bits per key
         hipLaunchKernelGGL(k_bloom_sort6, dim3(d.tiles), dim3(kDenseThreads), dense_sort_lds(d), st, key_bytes,
                            key_off, n, d);
@@ -482,25 +480,17 @@ bool bloom_plan_fits(const BloomPlan &pl) {
            bloom_fill_lds(pl) <= 96 * 1024;
 }
 
-uint64_t bloom_slots_bytes(const BloomPlan &pl) {
-    const uint64_t counts = ((uint64_t)pl.tiles * pl.nslices * 4 + 255) & ~255ull;
-    return 256 + counts + (uint64_t)pl.nslices * pl.tiles * bloom_slot_cap(pl) * 4;
+static uint64_t bloom_slots_bytes(const BloomPlan &pl) {
+    BloomSlots q{nullptr, nullptr, bloom_slot_cap(pl)};
+    return bloom_slots_bind(q, pl, nullptr);
 }
 
+// either plan's arrays: launch_bloom_build chooses between them as here
 uint64_t bloom_workspace_bytes(uint64_t n, uint32_t k, uint64_t bitmap_bytes) {
-    const DensePlan d = dense_plan(n, k, bitmap_bytes);
+    DensePlan d = dense_plan(n, k, bitmap_bytes);
     const uint64_t a = bloom_slots_bytes(bloom_plan(n, k, bitmap_bytes));
-    const uint64_t b = dense_fits(d) ? dense_ws_bytes(d) : 0;
+    const uint64_t b = dense_fits(d) ? dense_bind(d, nullptr) : 0;
     return a > b ? a : b;
-}
-
-BloomSlots bloom_slots(void *ws, const BloomPlan &pl) {
-    uint8_t *w = (uint8_t *)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-    BloomSlots q;
-    q.count = (uint32_t *)w;
-    q.slot = (uint32_t *)(w + (((uint64_t)pl.tiles * pl.nslices * 4 + 255) & ~255ull));
-    q.cap = bloom_slot_cap(pl);
-    return q;
 }
 
 size_t bloom_bin_lds(const BloomPlan &pl) {
@@ -511,16 +501,16 @@ size_t bloom_bin_lds(const BloomPlan &pl) {
 size_t bloom_fill_lds(const BloomPlan &pl) { return 4 * ((size_t)(1u << (pl.sb - 5)) + pl.tiles); }
 
 hipError_t launch_bloom_build(const uint8_t *key_bytes, const uint64_t *key_off, uint64_t n,
-                              uint32_t num_probes, uint8_t *bitmap, uint64_t bitmap_bytes, void *ws,
+                              uint32_t num_probes, uint8_t *bitmap, uint64_t bitmap_bytes, uint8_t *w,
                               hipStream_t st) {
     if (bitmap_bytes == 0) return hipSuccess;
     if (n == 0 || num_probes == 0) return hipMemsetAsync(bitmap, 0, bitmap_bytes, st);
-    if (ws) {
+    if (w) {
         const DensePlan d = dense_plan(n, num_probes, bitmap_bytes);
-        if (dense_fits(d) && !((uintptr_t)bitmap & 3)) return launch_bloom_dense(key_bytes, key_off, n, d, bitmap, bitmap_bytes, ws, st);
+        if (dense_fits(d) && !((uintptr_t)bitmap & 3)) return launch_bloom_dense(key_bytes, key_off, n, d, bitmap, bitmap_bytes, w, st);
     }
     BloomPlan pl = bloom_plan(n, num_probes, bitmap_bytes);
-    if (!ws || !bloom_plan_fits(pl)) {
+    if (!w || !bloom_plan_fits(pl)) {
         // no workspace (or a plan the binning cannot hold): device-scope atomics into the bitmap
         hipError_t e = hipMemsetAsync(bitmap, 0, bitmap_bytes, st);
         if (e != hipSuccess) return e;
@@ -536,7 +526,8 @@ hipError_t launch_bloom_build(const uint8_t *key_bytes, const uint64_t *key_off,
         (void)hipFuncSetAttribute((const void *)k_bloom_fill, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
         (void)hipGetLastError();  // an unsupported attribute value must not poison the launch status
     });
-    const BloomSlots q = bloom_slots(ws, pl);
+    BloomSlots q{nullptr, nullptr, bloom_slot_cap(pl)};
+    bloom_slots_bind(q, pl, w);
     hipLaunchKernelGGL(k_bloom_bin, dim3(pl.tiles), dim3(kBinThreads), bloom_bin_lds(pl), st, key_bytes, key_off, n, pl, q);
     hipLaunchKernelGGL(k_bloom_fill, dim3(pl.nslices), dim3(kFillThreads), bloom_fill_lds(pl), st, key_bytes, key_off, n, pl,
                        q, bitmap, bitmap_bytes);
@@ -735,27 +726,27 @@ __global__ __launch_bounds__(256) void k_pf_set(const uint8_t *key_bytes, const 
     }
 }
 
-uint64_t prefix_workspace_bytes(uint64_t n) {
+static uint64_t prefix_bind(PrefixWs &p, uint64_t n, uint8_t *w) {
     const uint64_t nc = (n + kPfChunk - 1) / kPfChunk + 1;
-    return 3 * ((8 * nc + 255) & ~255ull) + ((n + 256) & ~255ull) + 256;
+    Carver c{w, 0};
+    c.take(p.plan, 8);
+    c.take(p.chunk_last, nc);
+    c.take(p.prev_last, nc);
+    c.take(p.chunk_cnt, nc);
+    c.take(p.is_new, n + 1);
+    return c.off;
 }
-static PrefixWs prefix_ws(void *ws, uint64_t n) {
-    const uint64_t nc = (n + kPfChunk - 1) / kPfChunk + 1, a = (8 * nc + 255) & ~255ull;
-    uint8_t *b = (uint8_t *)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-    PrefixWs w;
-    w.plan = (uint64_t *)b;
-    w.chunk_last = (int64_t *)(b + 256);
-    w.prev_last = (int64_t *)(b + 256 + a);
-    w.chunk_cnt = (uint64_t *)(b + 256 + 2 * a);
-    w.is_new = b + 256 + 3 * a;
-    return w;
+uint64_t prefix_workspace_bytes(uint64_t n) {
+    PrefixWs p;
+    return prefix_bind(p, n, nullptr);
 }
 
 hipError_t launch_bloom_prefix(const uint8_t *key_bytes, const uint64_t *key_off, const int32_t *lens, uint64_t n,
                                uint32_t bpk, uint32_t kind, uint32_t arg, uint32_t whole, uint8_t *bitmap, uint64_t cap,
-                               uint64_t *bloom_len, void *ws, hipStream_t st) {
+                               uint64_t *bloom_len, uint8_t *ws, hipStream_t st) {
     PrefixSpec ps{kind, arg, whole, 0, lens};
-    PrefixWs w = prefix_ws(ws, n);
+    PrefixWs w;
+    prefix_bind(w, n, ws);
     const uint64_t nc = (n + kPfChunk - 1) / kPfChunk;
     hipError_t e = hipMemsetAsync(w.plan, 0, 64, st);
     if (e != hipSuccess) return e;

@@ -449,9 +449,25 @@ __global__ void k_dz_init(unsigned long long *err) {
     if (threadIdx.x == 0) *err = ~0ull;
 }
 
-uint64_t decompress_workspace_bytes(uint64_t nblocks) {
+// The plan's workspace: the blocks' slot sizes and launch_excl_scan2's scratch and tile sums.
+struct DzPlanWs {
+    uint64_t *slot, *scratch, *tx, *ty;
+};
+static void dz_plan_take(Carver &c, DzPlanWs &p, uint64_t nblocks) {
     const uint64_t nt = (nblocks + 1023) / 1024 + 1;
-    return 256 + 8 * (nblocks + 2) * 2 + 16 * (nt + 2) + 256;
+    c.take(p.slot, nblocks + 2);
+    c.take(p.scratch, nblocks + 2);
+    c.take(p.tx, nt + 1);
+    c.take(p.ty, nt + 1);
+}
+static uint64_t dz_plan_bind(DzPlanWs &p, uint64_t nblocks, uint8_t *w) {
+    Carver c{w, 0};
+    dz_plan_take(c, p, nblocks);
+    return c.off;
+}
+uint64_t decompress_workspace_bytes(uint64_t nblocks) {
+    DzPlanWs p;
+    return dz_plan_bind(p, nblocks, nullptr);
 }
 
 static std::once_flag g_dz_once;
@@ -465,24 +481,22 @@ hipError_t launch_ent_run(uint32_t codec, const uint8_t *blocks, const uint64_t 
 static bool ent_codec(uint32_t codec) { return codec == SDB_CODEC_ZLIB || codec == SDB_CODEC_ZSTD; }
 
 hipError_t launch_decompress_plan(uint32_t codec, const uint8_t *blocks, const uint64_t *block_off, uint64_t nblocks,
-                                  uint64_t *out_start, void *ws, hipStream_t st) {
-    uint8_t *w = (uint8_t *)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-    const uint64_t nt = (nblocks + 1023) / 1024 + 1;
+                                  uint64_t *out_start, uint8_t *w, hipStream_t st) {
+    DzPlanWs p;
+    dz_plan_bind(p, nblocks, w);
     DzArgs a{};
     a.codec = codec;
     a.blocks = blocks;
     a.block_off = block_off;
     a.nblocks = nblocks;
-    a.slot = (uint64_t *)w;
-    uint64_t *scratch = a.slot + (nblocks + 2);
-    uint64_t *tx = scratch + (nblocks + 2), *ty = tx + (nt + 1);
+    a.slot = p.slot;
     if (ent_codec(codec)) {
         const hipError_t e = launch_ent_slots(codec, blocks, block_off, nblocks, a.slot, st);
         if (e != hipSuccess) return e;
     } else {
         hipLaunchKernelGGL(k_dz_plan, dim3((uint32_t)((nblocks + 256) / 256)), dim3(256), 0, st, a);
     }
-    return launch_excl_scan2(a.slot, a.slot, nblocks, tx, ty, out_start, scratch, st);
+    return launch_excl_scan2(a.slot, a.slot, nblocks, p.tx, p.ty, out_start, p.scratch, st);
 }
 
 hipError_t launch_decompress_run(uint32_t codec, const uint8_t *blocks, const uint64_t *block_off, uint64_t nblocks,
@@ -530,8 +544,28 @@ hipError_t launch_zl_once_run(int mode, const uint8_t *blocks, const uint64_t *b
                               unsigned long long *ovf_count, uint32_t *dyn_list, unsigned long long *dyn_count,
                               uint64_t *wres, hipStream_t st);
 
+// Decode-once's workspace begins with the plan's arrays: the codecs other than zlib hand it to the plan.
+struct DzOnceWs {
+    DzPlanWs plan;
+    uint64_t *pos;                     // the overflowed blocks' positions after the slots
+    unsigned long long *nlist, *ndyn;  // lengths of the two lists
+    uint32_t *list, *dyn;              // overflowed blocks; blocks with a dynamic-Huffman deflate block
+    uint64_t *wres;                    // the wide pass's results, 2 words per block
+};
+static uint64_t dz_once_bind(DzOnceWs &o, uint64_t nblocks, uint8_t *w) {
+    Carver c{w, 0};
+    dz_plan_take(c, o.plan, nblocks);
+    c.take(o.pos, nblocks + 2);
+    c.take(o.nlist, 1);
+    c.take(o.ndyn, 1);
+    c.take(o.list, nblocks + 2);
+    c.take(o.dyn, nblocks + 2);
+    c.take(o.wres, 2 * (nblocks + 2));
+    return c.off;
+}
 uint64_t decompress_once_workspace_bytes(uint64_t nblocks) {
-    return decompress_workspace_bytes(nblocks) + 8 * (nblocks + 2) + 8 * (nblocks + 2) + 16 * (nblocks + 2) + 1024;
+    DzOnceWs o;
+    return dz_once_bind(o, nblocks, nullptr);
 }
 
 #ifndef SDB_ZL_WIDE
@@ -564,23 +598,17 @@ __global__ void k_zo_fix(uint64_t *pos, uint64_t *out_start, uint64_t nblocks, u
 
 hipError_t launch_decompress_once(uint32_t codec, const uint8_t *blocks, const uint64_t *block_off, uint64_t nblocks,
                                   uint64_t slot_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_start,
-                                  uint64_t *out_end, unsigned long long *err, void *ws, hipStream_t st) {
+                                  uint64_t *out_end, unsigned long long *err, uint8_t *w, hipStream_t st) {
     if (codec != SDB_CODEC_ZLIB || !zl_once_supported()) {
-        const hipError_t e = launch_decompress_plan(codec, blocks, block_off, nblocks, out_start, ws, st);
+        const hipError_t e = launch_decompress_plan(codec, blocks, block_off, nblocks, out_start, w, st);
         if (e != hipSuccess) return e;
         return launch_decompress_run(codec, blocks, block_off, nblocks, out, out_cap, out_start, out_end, err, st);
     }
-    uint8_t *w = (uint8_t *)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-    const uint64_t nt = (nblocks + 1023) / 1024 + 1;
-    uint64_t *slot = (uint64_t *)w;
-    uint64_t *scratch = slot + (nblocks + 2);
-    uint64_t *tx = scratch + (nblocks + 2), *ty = tx + (nt + 1);
-    uint64_t *pos = ty + (nt + 1);
-    unsigned long long *nlist = (unsigned long long *)(pos + (nblocks + 2));
-    unsigned long long *ndyn = nlist + 1;
-    uint32_t *list = (uint32_t *)(ndyn + 1);
-    uint32_t *dyn = list + (nblocks + 2);
-    uint64_t *wres = (uint64_t *)(((uintptr_t)(dyn + (nblocks + 2)) + 15) & ~(uintptr_t)15);
+    DzOnceWs o;
+    dz_once_bind(o, nblocks, w);
+    uint64_t *const slot = o.plan.slot, *const pos = o.pos, *const wres = o.wres;
+    unsigned long long *const nlist = o.nlist, *const ndyn = o.ndyn;
+    uint32_t *const list = o.list, *const dyn = o.dyn;
     const uint32_t g = (uint32_t)((nblocks + 256) / 256);
     hipLaunchKernelGGL(k_zo_init, dim3(g), dim3(256), 0, st, out_start, nblocks, slot_bytes, err, nlist, ndyn);
     hipError_t e;
@@ -600,7 +628,7 @@ hipError_t launch_decompress_once(uint32_t codec, const uint8_t *blocks, const u
     }
     // 2. the listed blocks' exact sizes, packed after the slots, and their inflate
     if (e == hipSuccess) e = launch_zl_once_slots(blocks, block_off, nblocks, list, nlist, slot, st);
-    if (e == hipSuccess) e = launch_excl_scan2(slot, slot, nblocks, tx, ty, pos, scratch, st);
+    if (e == hipSuccess) e = launch_excl_scan2(slot, slot, nblocks, o.plan.tx, o.plan.ty, pos, o.plan.scratch, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_zo_fix, dim3(g), dim3(256), 0, st, pos, out_start, nblocks, nblocks * slot_bytes, list, nlist);
     return launch_zl_once_run(0, blocks, block_off, nblocks, out, out_cap, pos, out_end, err, list, nlist, false, nullptr,

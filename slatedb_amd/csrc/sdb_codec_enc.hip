@@ -2087,10 +2087,26 @@ extern "C" int sdb_diag_cz_phase(uint64_t *out, int reset) {  // -DSDB_CZ_PT bui
 
 static std::once_flag g_cz_once;
 
+struct CzScan {  // launch_excl_scan2's scratch and tile sums
+    uint64_t *scratch, *tx, *ty;
+};
+// Sizes (w == NULL) or binds the workspace of a compress of a.nblocks blocks, a.in_bytes in all.
+static uint64_t cz_bind(CzArgs &a, CzScan &s, uint8_t *w) {
+    const uint64_t nt = (a.nblocks + 1023) / 1024 + 1;
+    Carver c{w, 0};
+    c.take(a.slots, cz_slot(a.in_bytes, a.nblocks));
+    c.take(a.len, a.nblocks + 2);
+    c.take(s.scratch, a.nblocks + 2);
+    c.take(s.tx, nt + 1);
+    c.take(s.ty, nt + 1);
+    return c.off;
+}
 uint64_t compress_workspace_bytes(uint64_t nblocks, uint64_t in_bytes) {
-    const uint64_t slots = cz_slot(in_bytes, nblocks) + 256;
-    const uint64_t nt = (nblocks + 1023) / 1024 + 1;
-    return slots + 8 * (nblocks + 2) * 2 + 16 * (nt + 1) + 512;
+    CzArgs a{};
+    CzScan s;
+    a.nblocks = nblocks;
+    a.in_bytes = in_bytes;
+    return cz_bind(a, s, nullptr);
 }
 
 template <uint32_t C>
@@ -2103,7 +2119,7 @@ static void cz_launch(const CzArgs &a, hipStream_t st) {
 
 hipError_t launch_compress(uint32_t codec, const uint8_t *blocks, const uint64_t *block_off, uint64_t nblocks,
                            uint64_t in_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_off,
-                           unsigned long long *err, void *ws, hipStream_t st) {
+                           unsigned long long *err, uint8_t *w, hipStream_t st) {
     std::call_once(g_cz_once, [] {
         (void)hipFuncSetAttribute((const void *)k_cz<SDB_CODEC_LZ4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CzCfg<SDB_CODEC_LZ4>::kLds);
         (void)hipFuncSetAttribute((const void *)k_cz<SDB_CODEC_SNAPPY>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CzCfg<SDB_CODEC_SNAPPY>::kLds);
@@ -2111,19 +2127,14 @@ hipError_t launch_compress(uint32_t codec, const uint8_t *blocks, const uint64_t
         (void)hipFuncSetAttribute((const void *)k_cz<SDB_CODEC_ZSTD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CzCfg<SDB_CODEC_ZSTD>::kLds);
         (void)hipGetLastError();
     });
-    uint8_t *w = (uint8_t *)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
     CzArgs a{};
+    CzScan sc;
     a.codec = codec;
     a.blocks = blocks;
     a.block_off = block_off;
     a.nblocks = nblocks;
     a.in_bytes = in_bytes;
-    a.slots = w;
-    uint8_t *tail = w + ((cz_slot(in_bytes, nblocks) + 255) & ~255ull);
-    a.len = (uint64_t *)tail;
-    uint64_t *scratch = a.len + (nblocks + 2);
-    const uint64_t nt = (nblocks + 1023) / 1024 + 1;
-    uint64_t *tx = scratch + (nblocks + 2), *ty = tx + (nt + 1);
+    cz_bind(a, sc, w);
     a.out = out;
     a.out_cap = out_cap;
     a.out_off = out_off;
@@ -2136,7 +2147,7 @@ hipError_t launch_compress(uint32_t codec, const uint8_t *blocks, const uint64_t
         case SDB_CODEC_ZLIB: cz_launch<SDB_CODEC_ZLIB>(a, st); break;
         default: cz_launch<SDB_CODEC_ZSTD>(a, st); break;
     }
-    hipError_t e = launch_excl_scan2(a.len, a.len, nblocks, tx, ty, out_off, scratch, st);
+    hipError_t e = launch_excl_scan2(a.len, a.len, nblocks, sc.tx, sc.ty, out_off, sc.scratch, st);
     if (e != hipSuccess) return e;
     const uint32_t pgrid = (uint32_t)((nblocks + 3) / 4 < 4096 ? (nblocks + 3) / 4 : 4096);
     hipLaunchKernelGGL(k_cz_pack, dim3(pgrid), dim3(256), 0, st, a);

@@ -53,30 +53,21 @@ struct MergeArgs {
 };
 static_assert(sizeof(MergeArgs) < 4000, "MergeArgs is passed as kernel arguments");
 
-struct MergeWorkspace {
-    uint64_t pfx, perm, start, dec, tile_sum, bound, err, err_merge, metric, lcp0, total;
-};
-inline MergeWorkspace merge_workspace_layout(uint64_t total) {
-    MergeWorkspace w{};
-    uint64_t off = 0;
-    auto take = [&](uint64_t bytes) {
-        uint64_t r = off;
-        off += (bytes + 255) & ~255ull;
-        return r;
-    };
-    const uint64_t ntiles = (total + kMergeTile - 1) / kMergeTile;
-    w.pfx = take(8 * (total + 1));
-    w.perm = take(8 * (total + 1));
-    w.start = take(total + 1);
-    w.dec = take(total + 1);
-    w.tile_sum = take(24 * (ntiles + 1));
-    w.bound = take(16 * (uint64_t)kMaxRuns * ((total + 255) / 256 + 1));  // k_mg_bounds: 2 x runs per 256 entries
-    w.err = take(8);
-    w.err_merge = take(8);
-    w.metric = take(16);
-    w.lcp0 = take(8);
-    w.total = off;
-    return w;
+// Sizes (w == NULL) or binds the workspace of a merge of a.total entries.
+inline uint64_t merge_bind(MergeArgs &a, uint8_t *w) {
+    const uint64_t ntiles = (a.total + kMergeTile - 1) / kMergeTile;
+    Carver c{w, 0};
+    c.take(a.pfx, a.total + 1);
+    c.take(a.perm, a.total + 1);
+    c.take(a.start, a.total + 1);
+    c.take(a.dec, a.total + 1);
+    c.take(a.tile_sum, 3 * (ntiles + 1));
+    c.take(a.bound, 2 * (uint64_t)kMaxRuns * ((a.total + 255) / 256 + 1));  // k_mg_bounds: 2 x runs per 256 entries
+    c.take(a.err, 1);
+    c.take(a.err_merge, 1);
+    c.take(a.metric, 2);
+    c.take(a.lcp0, 2);
+    return c.off;
 }
 
 sdb_status build_merge_args(const sdb_run *runs, uint32_t nruns, const sdb_retention *ret, const sdb_merged_out *out,

@@ -1045,23 +1045,12 @@ sdb_status build_merge_args(const sdb_run *runs, uint32_t nruns, const sdb_reten
     }
     if (total >= (1ull << 40)) return SDB_LIMIT_EXCEEDED;
     if (total && (!out->kind || !out->seq || !out->create_ts || !out->expire_ts || !out->ts_mask)) return SDB_INVALID_ARGUMENT;
-    const MergeWorkspace w = merge_workspace_layout(total);
-    if (!workspace || workspace_bytes < w.total + 256) return SDB_INVALID_ARGUMENT;
-    uint8_t *ws = (uint8_t *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
     a.total = total;
+    if (!workspace || workspace_bytes < merge_bind(a, nullptr) + 256) return SDB_INVALID_ARGUMENT;
+    merge_bind(a, ws_align(workspace));
     a.ntiles = (uint32_t)((total + kMergeTile - 1) / kMergeTile);
     a.ret = *ret;
     a.out = *out;
-    a.pfx = (uint64_t *)(ws + w.pfx);
-    a.perm = (uint64_t *)(ws + w.perm);
-    a.start = ws + w.start;
-    a.dec = ws + w.dec;
-    a.tile_sum = (uint64_t *)(ws + w.tile_sum);
-    a.bound = (uint64_t *)(ws + w.bound);
-    a.err = (unsigned long long *)(ws + w.err);
-    a.err_merge = (unsigned long long *)(ws + w.err_merge);
-    a.metric = (unsigned long long *)(ws + w.metric);
-    a.lcp0 = (uint32_t *)(ws + w.lcp0);
     return SDB_OK;
 }
 

@@ -521,8 +521,7 @@ sdb_status sdb_compactor_run_ssts(sdb_compactor *c, const sdb_compaction_input *
                                          c->dec_ws.p, c->dec_ws.cap,
                                          stream);
     if (st) return st;
-    const unsigned long long *dec_err =
-        reinterpret_cast<const unsigned long long *>(static_cast<uint8_t *>(c->dec_ws.p) + decode_workspace_layout(B).err);
+    const unsigned long long *dec_err = decode_err_word(c->dec_ws.p, B);
     if (launch_cx_gate(in, dout.summary, dec_err, dout.block_entry_start, gate, s) != hipSuccess)
         return SDB_DEVICE_ERROR;
     std::vector<sdb_run> runs(nruns);

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/slatedb_amd.h"
+#include "sdb_workspace.h"
 
 namespace sdb {
 
@@ -32,32 +33,32 @@ struct DecodeArgs {
     uint64_t dn, dkb;                  // descending: entries and key bytes of the whole output (k_dec_emit)
 };
 
-struct DecodeWorkspace {
-    uint64_t cnt, kbytes, flag, rcnt, rowpos, ent_start, key_start, tile_x, tile_y, err, nbad, done, total;
-};
-inline DecodeWorkspace decode_workspace_layout(uint64_t nblocks) {
-    DecodeWorkspace w{};
-    uint64_t off = 0;
-    auto take = [&](uint64_t bytes) {
-        uint64_t r = off;
-        off += (bytes + 255) & ~255ull;
-        return r;
-    };
-    uint64_t nt = (nblocks + 1023) / 1024 + 1;
-    w.cnt = take(8 * (nblocks + 1));
-    w.kbytes = take(8 * (nblocks + 1));
-    w.flag = take(nblocks + 1);
-    w.rcnt = take(8 * (nblocks + 1));
-    w.rowpos = take(256 * (nblocks + 1));
-    w.ent_start = take(8 * (nblocks + 1));
-    w.key_start = take(8 * (nblocks + 1));
-    w.tile_x = take(8 * (nt + 1));
-    w.tile_y = take(8 * (nt + 1));
-    w.err = take(8);
-    w.nbad = take(8);
-    w.done = take(8);
-    w.total = off;
-    return w;
+// Sizes (w == NULL) or binds the workspace of a decode of a.nblocks blocks.  sdb_decode_workspace_bytes has no
+// 256 bytes of its own for the round-up of the caller's pointer: rowpos comes last, and its spare block's 256
+// bytes (the kernels index it by block < nblocks) pay for it.
+inline uint64_t decode_bind(DecodeArgs &a, uint8_t *w) {
+    const uint64_t nb = a.nblocks, nt = (nb + 1023) / 1024 + 1;
+    Carver c{w, 0};
+    c.take(a.cnt, nb + 1);
+    c.take(a.kbytes, nb + 1);
+    c.take(a.flag, nb + 1);
+    c.take(a.rcnt, nb + 1);
+    c.take(a.ent_start, nb + 1);
+    c.take(a.key_start, nb + 1);
+    c.take(a.tile_x, nt + 1);
+    c.take(a.tile_y, nt + 1);
+    c.take(a.err, 1);
+    c.take(a.nbad, 1);
+    c.take(a.done, 2);
+    c.take(a.rowpos, 128 * (nb + 1));
+    return c.off;
+}
+// The error word of a decode in the caller's `workspace` (min block << 8 | status, ~0: none).
+inline const unsigned long long *decode_err_word(void *workspace, uint64_t nblocks) {
+    DecodeArgs a{};
+    a.nblocks = nblocks;
+    decode_bind(a, ws_align(workspace));
+    return a.err;
 }
 
 hipError_t launch_decode(DecodeArgs a, hipStream_t st);
@@ -67,18 +68,18 @@ hipError_t launch_excl_scan2(const uint64_t *x, const uint64_t *y, uint64_t n, u
 // f3: per-block decompression (sdb_codec.hip)
 uint64_t decompress_workspace_bytes(uint64_t nblocks);
 hipError_t launch_decompress_plan(uint32_t codec, const uint8_t *blocks, const uint64_t *block_off, uint64_t nblocks,
-                                  uint64_t *out_start, void *ws, hipStream_t st);
+                                  uint64_t *out_start, uint8_t *w, hipStream_t st);
 hipError_t launch_decompress_run(uint32_t codec, const uint8_t *blocks, const uint64_t *block_off, uint64_t nblocks,
                                  uint8_t *out, uint64_t out_cap, const uint64_t *out_start, uint64_t *out_end,
                                  unsigned long long *err, hipStream_t st);
 uint64_t decompress_once_workspace_bytes(uint64_t nblocks);
 hipError_t launch_decompress_once(uint32_t codec, const uint8_t *blocks, const uint64_t *block_off, uint64_t nblocks,
                                   uint64_t slot_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_start,
-                                  uint64_t *out_end, unsigned long long *err, void *ws, hipStream_t st);
+                                  uint64_t *out_end, unsigned long long *err, uint8_t *w, hipStream_t st);
 // f3: per-block compression, the write side (sdb_codec_enc.hip)
 uint64_t compress_workspace_bytes(uint64_t nblocks, uint64_t in_bytes);
 hipError_t launch_compress(uint32_t codec, const uint8_t *blocks, const uint64_t *block_off, uint64_t nblocks,
                            uint64_t in_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_off,
-                           unsigned long long *err, void *ws, hipStream_t st);
+                           unsigned long long *err, uint8_t *w, hipStream_t st);
 
 }  // namespace sdb

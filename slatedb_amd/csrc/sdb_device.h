@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "../../include/slatedb_amd.h"
+#include "sdb_workspace.h"
 
 #define SDB_DEV __device__ __forceinline__
 
@@ -186,21 +187,6 @@ SDB_DEV uint32_t gf_mul(uint32_t a, uint32_t b) {
 SDB_DEV uint32_t crc_shift_bytes(uint32_t c, uint32_t n) {
     return gf_mul(gf_mul(c_seg.seg[n >> 6], c_x8.t[n & 63]), c);
 }
-
-// ------------------------------------------------------------------------------------------------
-// Workspace carving (host): 256-byte-aligned arrays taken in order from base.  One function that takes a
-// launch's arrays both sizes its workspace (base == nullptr: nothing is bound, `off` ends as the size) and
-// binds it, so the two cannot disagree.
-// ------------------------------------------------------------------------------------------------
-struct Carver {
-    uint8_t *base;
-    uint64_t off;
-    template <typename T>
-    void take(T *&p, uint64_t count) {
-        p = base ? (T *)(base + off) : nullptr;
-        off += (sizeof(T) * count + 255) & ~255ull;
-    }
-};
 
 // ------------------------------------------------------------------------------------------------
 // Byte helpers

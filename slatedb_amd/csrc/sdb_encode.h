@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/slatedb_amd.h"
+#include "sdb_workspace.h"
 
 namespace sdb {
 
@@ -95,7 +96,6 @@ struct EncodeArgs {
     // workspace
     uint32_t *lcp;
     uint32_t *szr, *sznr;   // per entry (k_facts): restart-row size, non-restart size (V1: both the row size)
-    uint64_t *hd;           // per entry (k_facts, fused bloom): h0 | d0 << 32, first probe and step
     uint32_t nfacts;        // k_facts workgroups (partials: stat_part / err_part are per facts workgroup)
     uint32_t *row_scratch;  // per entry: row offsets of slow-path blocks
     uint32_t *next;
@@ -143,73 +143,76 @@ struct EncodeArgs {
     const uint64_t *bloom_len_dev;  // prefix-extractor filter: the device-counted length (~0: error)
 };
 
-// Workspace layout for n entries (all offsets 256-byte aligned).  Everything up to `bloom_rep` depends
-// only on n (and whether a filter is built), so the kernels recompute the layout on the device from
-// the SST's workspace base; the bloom slots come last and are sized on the host.
-struct EncodeWorkspace {
-    uint64_t lcp, szr, sznr, hd, row_scratch, next, bbytes, tab_exit, tab_cnt, tab_bytes;
-    uint64_t anchor_e, anchor_blk, anchor_byte, err, wmax, slow_count, slow_list, big_count, big_list, desc, stat_part,
-        huge_part, wmax_part,
-        bloom_rep;
-    uint64_t err_part, done, gtab_exit, gtab_cnt, gtab_bytes, mode, blen;
-    uint64_t total;
+// The workspace arrays of one SST's encode: X(EncodeArgs member, element type, elements).  n entries, nc
+// chunks (k_seg / k_enum), nf k_facts workgroups, nt = nc * kSegLook + 1 table rows (seg_look candidate entry
+// points per chunk; one composed table per group, <= one per chunk).  This list is the only one: the field
+// indices, the slot's offsets (SstSlot::wso), the size and make_args' bindings all come from it.  The bloom
+// slots or the prefix filter's scratch (host-sized) follow the arrays, at wso[kWsTail].
+#define SDB_ENCODE_WS(X)                                                                                      \
+    X(lcp, uint32_t, n + 1)                                                                                   \
+    X(szr, uint32_t, n + 1)                                                                                   \
+    X(sznr, uint32_t, n + 1)                                                                                  \
+    X(row_scratch, uint32_t, n + 1)                                                                           \
+    X(next, uint32_t, n + 1)                                                                                  \
+    X(bbytes, uint32_t, n + 1)                                                                                \
+    X(tab_exit, uint32_t, nt)                                                                                 \
+    X(tab_cnt, uint32_t, nt)                                                                                  \
+    X(tab_bytes, uint64_t, nt)                                                                                \
+    X(anchor_e, uint32_t, nc + 2)                                                                             \
+    X(anchor_blk, uint32_t, nc + 2)                                                                           \
+    X(anchor_byte, uint64_t, nc + 2)                                                                          \
+    X(err, unsigned long long, 1)                                                                             \
+    X(wmax, uint32_t, 1)                                                                                      \
+    X(slow_count, uint32_t, 1)                                                                                \
+    X(slow_list, uint32_t, n + 1)                                                                             \
+    X(big_count, uint32_t, 1)                                                                                 \
+    X(big_list, uint32_t, n + 1)                                                                              \
+    X(desc, BlockDesc, n + 1)                                                                                 \
+    X(stat_part, uint64_t, 5 * (nf + 1))                                                                      \
+    X(huge_part, uint32_t, nf + 1)                                                                            \
+    X(wmax_part, uint32_t, nc + 1)                                                                            \
+    X(err_part, unsigned long long, nf + 1)                                                                   \
+    X(done, uint32_t, 2)                                                                                      \
+    X(gtab_exit, uint32_t, nt)                                                                                \
+    X(gtab_cnt, uint32_t, nt)                                                                                 \
+    X(gtab_bytes, uint64_t, nt)                                                                               \
+    X(mode, uint32_t, 1)                                                                                      \
+    X(bloom_len_dev, const uint64_t, 1)
+enum WsField {
+#define X(name, T, count) kWs_##name,
+    SDB_ENCODE_WS(X)
+#undef X
+    kWsTail,
+    kWsFields
 };
-uint64_t bloom_workspace_bytes(uint64_t n, uint32_t k, uint64_t bitmap_bytes);
+// The arrays' offsets for n entries in 256-byte units (wso: kWsFields values, or NULL); returns their bytes,
+// which is where the tail starts.
+inline uint64_t encode_ws_layout(uint64_t n, uint32_t *wso) {
+    const uint64_t nc = (n + kChunk - 1) / kChunk, nf = (n + kFactsEntries - 1) / kFactsEntries;
+    const uint64_t nt = nc * kSegLook + 1;
+    Carver c{nullptr, 0};
+    uint64_t at[kWsFields];
+#define X(name, T, count) at[kWs_##name] = c.bytes(sizeof(T) * (count));
+    SDB_ENCODE_WS(X)
+#undef X
+    at[kWsTail] = c.off;
+    for (int f = 0; wso && f < kWsFields; f++) wso[f] = (uint32_t)(at[f] >> 8);
+    return c.off;
+}
+// The bloom slots (BloomSlots, sdb_bloom.hip) at w: the counts, then the slots of q.cap probes.  Returns their
+// bytes (w == NULL: nothing is bound).
+__host__ __device__ inline uint64_t bloom_slots_bind(BloomSlots &q, const BloomPlan &pl, uint8_t *w) {
+    Carver c{w, 0};
+    c.take(q.count, (uint64_t)pl.tiles * pl.nslices);
+    c.take(q.slot, (uint64_t)pl.nslices * pl.tiles * q.cap);
+    return c.off;
+}
+// The tail of an encode workspace that builds a whole-key filter / a prefix-extractor filter.
 uint64_t encode_bloom_workspace_bytes(uint64_t n, uint32_t k, uint64_t bitmap_bytes);
-__host__ __device__ inline EncodeWorkspace encode_workspace_offsets(uint64_t n, bool has_filter) {
-    EncodeWorkspace w{};
-    uint64_t off = 0;
-    auto take = [&](uint64_t bytes) {
-        uint64_t r = off;
-        off += (bytes + 255) & ~255ull;
-        return r;
-    };
-    uint64_t nc = (n + kChunk - 1) / kChunk;
-    w.lcp = take(4 * (n + 1));
-    w.szr = take(4 * (n + 1));
-    w.sznr = take(4 * (n + 1));
-    w.hd = take(0);  // (the fused bloom bins inside k_facts: no per-entry hash array)
-    (void)has_filter;
-    w.row_scratch = take(4 * (n + 1));
-    w.next = take(4 * (n + 1));
-    w.bbytes = take(4 * (n + 1));
-    w.tab_exit = take(4 * (nc * kSegLook + 1));   // per chunk: seg_look candidate entry points
-    w.tab_cnt = take(4 * (nc * kSegLook + 1));
-    w.tab_bytes = take(8 * (nc * kSegLook + 1));
-    w.anchor_e = take(4 * (nc + 2));
-    w.anchor_blk = take(4 * (nc + 2));
-    w.anchor_byte = take(8 * (nc + 2));
-    w.err = take(8);
-    w.wmax = take(4);
-    w.slow_count = take(4);
-    w.slow_list = take(4 * (n + 1));
-    w.big_count = take(4);
-    w.big_list = take(4 * (n + 1));
-    w.desc = take(sizeof(BlockDesc) * (n + 1));
-    const uint64_t nf = (n + kFactsEntries - 1) / kFactsEntries;
-    w.stat_part = take(8 * 5 * (nf + 1));
-    w.huge_part = take(4 * (nf + 1));
-    w.wmax_part = take(4 * (nc + 1));
-    w.err_part = take(8 * (nf + 1));
-    w.done = take(8);
-    w.gtab_exit = take(4 * (nc * kSegLook + 1));  // one table per group (<= one per chunk)
-    w.gtab_cnt = take(4 * (nc * kSegLook + 1));
-    w.gtab_bytes = take(8 * (nc * kSegLook + 1));
-    w.mode = take(4);
-    w.blen = take(8);   // prefix-extractor filters: the filter length the device counted
-    w.bloom_rep = off;  // bloom slots or the prefix filter's scratch (host-sized) last
-    w.total = off;
-    return w;
-}
-inline EncodeWorkspace encode_workspace_layout(uint64_t n, uint64_t filter_bytes, uint32_t num_probes) {
-    EncodeWorkspace w = encode_workspace_offsets(n, filter_bytes != 0);
-    w.total = w.bloom_rep + ((filter_bytes ? encode_bloom_workspace_bytes(n, num_probes, filter_bytes) : 0) + 255) / 256 * 256;
-    return w;
-}
 uint64_t prefix_workspace_bytes(uint64_t n);
 hipError_t launch_bloom_prefix(const uint8_t *key_bytes, const uint64_t *key_off, const int32_t *lens, uint64_t n,
                                uint32_t bpk, uint32_t kind, uint32_t arg, uint32_t whole, uint8_t *bitmap, uint64_t cap,
-                               uint64_t *bloom_len, void *ws, hipStream_t st);
+                               uint64_t *bloom_len, uint8_t *ws, hipStream_t st);
 hipError_t launch_bloom_match(const uint8_t *bitmap, uint64_t bytes, uint32_t k, uint32_t whole, uint32_t kind,
                               uint32_t arg, const uint8_t *key_bytes, const uint64_t *key_off, const uint8_t *is_prefix,
                               const int32_t *qlens, uint64_t n, uint8_t *result, hipStream_t st);
@@ -222,12 +225,6 @@ hipError_t launch_bloom_match(const uint8_t *bitmap, uint64_t bytes, uint32_t k,
 // segmentation kernels of all of them at once.  Passed by value (kernel arguments).
 // ------------------------------------------------------------------------------------------------
 constexpr uint32_t kMaxSsts = 8;
-enum WsField {
-    kWsLcp = 0, kWsSzr, kWsSznr, kWsHd, kWsRowScratch, kWsNext, kWsBbytes, kWsTabExit, kWsTabCnt, kWsTabBytes,
-    kWsAnchorE, kWsAnchorBlk, kWsAnchorByte, kWsErr, kWsWmax, kWsSlowCount, kWsSlowList, kWsBigCount, kWsBigList,
-    kWsDesc, kWsStatPart, kWsHugePart, kWsWmaxPart, kWsBloomRep, kWsErrPart, kWsDone, kWsGtabExit, kWsGtabCnt,
-    kWsGtabBytes, kWsMode, kWsBlen, kWsFields
-};
 struct SstSlot {
     const uint8_t *key_bytes;
     const uint64_t *key_off;
@@ -249,12 +246,12 @@ struct SstSlot {
     uint8_t *bloom_out;
     uint64_t bloom_len;
     uint8_t *ws;              // this SST's workspace (256-byte aligned)
-    uint32_t num_probes, filter_built, bloom_fused, has_filter_ws;  // has_filter_ws: hd in the layout
+    uint32_t num_probes, filter_built, bloom_fused;
+    uint32_t prefix_bloom;    // the filter is a prefix-extractor one: its length is device-counted
     uint32_t nchunks, nfacts, group, slot_cap;
-    uint32_t prefix_bloom, pad2;  // the filter is a prefix-extractor one: its length is device-counted
     BloomPlan bpl;            // fused bloom plan (bloom_fused)
-    // encode_workspace_offsets(n, has_filter_ws) in 256-byte units, filled on the host (fill_ws_layout):
-    // the kernels load them instead of re-deriving the layout's 64-bit offset chain on the scalar unit
+    // encode_ws_layout(n) in 256-byte units, filled on the host: the kernels load the offsets instead of
+    // deriving the layout's 64-bit offset chain on the scalar unit
     uint32_t wso[kWsFields];
 };
 struct SstSet {
@@ -284,48 +281,18 @@ __host__ __device__ inline EncodeArgs make_args(const SstSet &P, uint32_t i) {
     a.wal = P.wal;
     a.nchunks = s.nchunks;
     a.seg_look = P.seg_look;
-    uint8_t *b = s.ws;
-    auto W = [&](int f) { return b + ((uint64_t)s.wso[f] << 8); };
-    a.lcp = (uint32_t *)W(kWsLcp);
-    a.szr = (uint32_t *)W(kWsSzr);
-    a.sznr = (uint32_t *)W(kWsSznr);
-    a.hd = (uint64_t *)W(kWsHd);
     a.nfacts = s.nfacts;
-    a.row_scratch = (uint32_t *)W(kWsRowScratch);
-    a.next = (uint32_t *)W(kWsNext);
-    a.bbytes = (uint32_t *)W(kWsBbytes);
-    a.tab_exit = (uint32_t *)W(kWsTabExit);
-    a.tab_cnt = (uint32_t *)W(kWsTabCnt);
-    a.tab_bytes = (uint64_t *)W(kWsTabBytes);
-    a.anchor_e = (uint32_t *)W(kWsAnchorE);
-    a.anchor_blk = (uint32_t *)W(kWsAnchorBlk);
-    a.anchor_byte = (uint64_t *)W(kWsAnchorByte);
-    a.err = (unsigned long long *)W(kWsErr);
-    a.wmax = (uint32_t *)W(kWsWmax);
-    a.slow_count = (uint32_t *)W(kWsSlowCount);
-    a.slow_list = (uint32_t *)W(kWsSlowList);
-    a.big_count = (uint32_t *)W(kWsBigCount);
-    a.big_list = (uint32_t *)W(kWsBigList);
-    a.desc = (BlockDesc *)W(kWsDesc);
-    a.stat_part = (uint64_t *)W(kWsStatPart);
-    a.huge_part = (uint32_t *)W(kWsHugePart);
-    a.wmax_part = (uint32_t *)W(kWsWmaxPart);
-    a.err_part = (unsigned long long *)W(kWsErrPart);
-    a.gtab_exit = (uint32_t *)W(kWsGtabExit);
-    a.gtab_cnt = (uint32_t *)W(kWsGtabCnt);
-    a.gtab_bytes = (uint64_t *)W(kWsGtabBytes);
-    a.mode = (uint32_t *)W(kWsMode);
+    // every array of SDB_ENCODE_WS at its offset: the list's element type must be the member's
+#define X(name, T, count) a.name = (T *)(s.ws + ((uint64_t)s.wso[kWs_##name] << 8));
+    SDB_ENCODE_WS(X)
+#undef X
+    if (!s.prefix_bloom) a.bloom_len_dev = nullptr;
     a.group = s.group;
     a.bloom_fused = s.bloom_fused;
     a.bpl = s.bpl;
-    {  // bloom slots (BloomSlots, sdb_bloom.hip): counts then slots, 256-byte aligned
-        uint8_t *q = W(kWsBloomRep);
-        a.bq.count = (uint32_t *)q;
-        a.bq.slot = (uint32_t *)(q + (((uint64_t)s.bpl.tiles * s.bpl.nslices * 4 + 255) & ~255ull));
-        a.bq.cap = s.slot_cap;
-    }
+    a.bq.cap = s.slot_cap;
+    bloom_slots_bind(a.bq, s.bpl, s.ws + ((uint64_t)s.wso[kWsTail] << 8));
     a.bloom_out = s.bloom_out;
-    a.done = (uint32_t *)W(kWsDone);
     a.nprep_wg = s.nchunks;
     a.seg_lds = kSegLds;
     a.out_data = s.out_data;
@@ -339,18 +306,7 @@ __host__ __device__ inline EncodeArgs make_args(const SstSet &P, uint32_t i) {
     a.bloom_len = s.bloom_len;
     a.num_probes = s.num_probes;
     a.filter_built = s.filter_built;
-    a.bloom_len_dev = s.prefix_bloom ? (uint64_t *)W(kWsBlen) : nullptr;
     return a;
-}
-
-// The slot's workspace layout (wso) from its n and has_filter_ws (host, after both are set).
-inline void fill_ws_layout(SstSlot &s) {
-    const EncodeWorkspace w = encode_workspace_offsets(s.n, s.has_filter_ws != 0);
-    const uint64_t off[kWsFields] = {w.lcp, w.szr, w.sznr, w.hd, w.row_scratch, w.next, w.bbytes, w.tab_exit, w.tab_cnt,
-                                     w.tab_bytes, w.anchor_e, w.anchor_blk, w.anchor_byte, w.err, w.wmax, w.slow_count,
-                                     w.slow_list, w.big_count, w.big_list, w.desc, w.stat_part, w.huge_part, w.wmax_part,
-                                     w.bloom_rep, w.err_part, w.done, w.gtab_exit, w.gtab_cnt, w.gtab_bytes, w.mode, w.blen};
-    for (int f = 0; f < kWsFields; f++) s.wso[f] = (uint32_t)(off[f] >> 8);
 }
 
 // Enqueue the encode of every SST of the set on `st` (one launch sequence).
@@ -364,13 +320,12 @@ void stage_mark(hipStream_t st, int stage, bool begin);
 bool stage_timing_on();
 
 // bloom (sdb_bloom.hip)
-
 // tile_keys: keys per binning tile (0: the standalone build's choice; the fused encode bins per chunk)
 BloomPlan bloom_plan(uint64_t n, uint32_t k, uint64_t bitmap_bytes, uint32_t tile_keys = 0);
 uint64_t bloom_workspace_bytes(uint64_t n, uint32_t k, uint64_t bitmap_bytes);
-// ws: bloom_workspace_bytes(...) of scratch, or NULL (device-scope atomics; slow)
+// w: bloom_workspace_bytes(...) of scratch (256-byte aligned), or NULL (device-scope atomics; slow)
 hipError_t launch_bloom_build(const uint8_t *key_bytes, const uint64_t *key_off, uint64_t n,
-                              uint32_t num_probes, uint8_t *bitmap, uint64_t bitmap_bytes, void *ws,
+                              uint32_t num_probes, uint8_t *bitmap, uint64_t bitmap_bytes, uint8_t *w,
                               hipStream_t st);
 hipError_t launch_bloom_query(const uint8_t *bitmap, uint64_t bitmap_bytes, uint32_t num_probes,
                               const uint8_t *key_bytes, const uint64_t *key_off, uint64_t n,
