@@ -28,6 +28,9 @@
  *   - sdb_lsm_get              -> the on-disk part of Reader::get_key_value_with_options (reader.rs:203-260):
  *                                 GetIterator::from_lsm_tree (db_iter.rs:79-124) over L0 and the sorted
  *                                 runs, snapshot-aware (max_seq), many keys per call.
+ *   - sdb_lsm_scan             -> the on-disk part of Reader::scan_with_options (reader.rs:275-320):
+ *                                 DbIterator::new (db_iter.rs:189-257) over L0 and the sorted runs, drained:
+ *                                 the newest visible version per key, many ranges per call.
  *   - sdb_sst_builder_*        -> host-side mirror of EncodedSsTableBuilder's add()/build()/
  *                                 next_block() call order (sst_builder.rs:224-276), batching
  *                                 entries into a columnar pinned buffer and encoding on the GPU.
@@ -605,6 +608,97 @@ uint64_t sdb_lsm_get_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, u
 sdb_status sdb_lsm_get(const sdb_lsm_view *lsm, const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
                        const uint64_t *max_seq /* device, nkeys; NULL = no bound */, const sdb_get_out *out,
                        void *workspace, uint64_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Batched Db::scan over a tree of encoded SSTs (device): the on-disk part of Reader::scan_with_options
+ * (reader.rs:275-320) -> DbIterator::new (db_iter.rs:189-257), drained.  Memtables and the write batch stay
+ * on the host; the caller merges them on top.  The tree is the sdb_lsm_view of sdb_lsm_get, the ranges are
+ * the sdb_scan_ranges of sdb_sst_scan.  Many ranges are scanned by one call:
+ *   1. SSTs of a range: SST i takes part in range r iff it has blocks and {k : first_key[i] <= k <=
+ *      last_key[i]} meets the range as a set: the range is not empty as a set, last_key[i] does not precede
+ *      its start bound and first_key[i] does not exceed its end bound.  This is per SST; runs only fix the
+ *      search order, which is the order of `ssts`, newest first.  The reference opens every L0 SST and, per
+ *      sorted run, tables_covering_range (segment_iterator.rs:355-414, db_state.rs:600-660); any SST it opens
+ *      beyond this rule holds no key of the range, so the entries agree.  No bloom filter is consulted: a
+ *      range has none without a prefix extractor.  A range that is empty as a set reads nothing.
+ *      range_ssts[r] is the number of SSTs that take part;
+ *   2. blocks: per participating SST, partitions_covering_range(index keys, start, end) exactly as
+ *      sdb_sst_scan rule 1 (partitioned_keyspace.rs:87-110).  EVERY such block is bounds- and CRC-checked
+ *      (format/sst.rs:1029-1038) and its rows are parsed before a row is used.  summary.blocks_checked is the
+ *      size of the union of those blocks over all ranges, exactly: nothing here is lazy;
+ *   3. rows: among all entries of the participating SSTs whose key the range contains, versions with
+ *      seq > max_seq[r] are dropped first (FilterIterator::new_with_max_seq, applied before the
+ *      deduplicating merge, db_iter.rs:205-217).  Per key the newest remaining version wins (MergeIterator
+ *      with dedup: key ascending, seq descending, merge_iterator.rs:55-69, 180-209).  Equal (key, seq) in two
+ *      SSTs, which the store never writes: the SST earlier in search order wins; within one SST the first in
+ *      physical order (an SST holds its rows key ascending, seq descending, as the store writes them).  A
+ *      winning tombstone yields nothing for the key (DbIterator::next_entry, db_iter.rs:280-303), a winning
+ *      value yields one row.  Expiry is NOT filtered, as in sdb_lsm_get;
+ *   4. merge operands: a key whose winner is a merge operand fails its range with
+ *      SDB_MERGE_OPERATOR_MISSING (MergeOperatorRequiredIterator, merge_operator.rs:213-223).  An operand
+ *      hidden behind a newer visible value or tombstone, or above the bound, does not.  Resolving operands is
+ *      out of scope;
+ *   5. order and errors: ranges in input order; inside a range keys ascend, or descend when descending != 0
+ *      (one row per key, so both orders hold the same rows).  A failing range contributes zero entries: all
+ *      or nothing, as sdb_sst_scan rule 4; the reference would yield the rows ahead of the failure first.
+ *      range_status[r] is the status of the lowest failing block: lowest SST in search order, then lowest
+ *      block.  A view with a version other than 1 or 2 gives SDB_INVALID_VERSION to the ranges it takes part
+ *      in, a view with blocks and a NULL array SDB_INVALID_ARGUMENT, at that SST's place in the order.  A
+ *      bound kind above 2 fails that range with SDB_INVALID_ARGUMENT (it takes part in nothing).  Block,
+ *      version and argument errors take precedence over rule 4.  Other ranges are unaffected;
+ *      summary.status is the status of the lowest-numbered failing range;
+ *   6. capacity: the call stages candidates in the workspace: every entry of rule 3's set before any
+ *      filtering, i.e. what sdb_sst_scan over each participating SST would yield for the range; ranges failed
+ *      by a block, version or argument error contribute none.  The summary always reports num_candidates /
+ *      candidate_key_bytes.  If they exceed cand_entries / cand_key_bytes: summary.status is
+ *      SDB_LIMIT_EXCEEDED, num_entries = key_bytes = 0, range_entry_start is all 0, no column byte is written,
+ *      and range_status (without rule 4) and range_ssts are valid.  If the candidates fit but
+ *      num_entries > cap_entries or key_bytes > key_arena_cap: summary.status is SDB_LIMIT_EXCEEDED with the
+ *      true totals, range_entry_start and range_status are valid and no column byte is written.
+ *      num_entries <= num_candidates, so a caller who sizes the columns like the staging needs at most two
+ *      calls;
+ *   7. arguments and conventions, as sdb_lsm_get rules 6-7: NULL structs or arrays that a non-empty input
+ *      needs, or a short workspace: SDB_INVALID_ARGUMENT from the call (total_blocks or num_ssts >=
+ *      0xFFFFFFFF, n * num_ssts or cand_entries over 2^40, or cand_key_bytes over 2^44: SDB_LIMIT_EXCEEDED);
+ *      then SDB_DEVICE_ERROR when no device is
+ *      present.  A malformed tree (run_start, block_base, key offsets or range offsets that descend) fails
+ *      EVERY range with SDB_INVALID_ARGUMENT on the device with blocks_checked 0, and nothing is read through
+ *      the malformed arrays.  n == 0, num_ssts == 0 or total_blocks == 0 is SDB_OK with every range empty and
+ *      the summary zeroed.  No allocation, no synchronisation, launches only on `stream`, safe to capture into
+ *      a HIP graph as a linear sequence; the workspace is reusable by the next call without a host-side
+ *      reset.  Compressed data sections are decompressed first (sdb_decompress_blocks_once).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct sdb_lsm_scan_summary {
+    uint64_t num_entries, key_bytes;               /* what the call yields over all ranges */
+    uint64_t num_candidates, candidate_key_bytes;  /* what it stages before the merge (rule 6) */
+    uint64_t num_failed_ranges;
+    uint64_t blocks_checked;                       /* distinct tree blocks CRC-checked: exact (rule 2) */
+    int32_t status;                                /* status of the lowest-numbered failing range, or LIMIT_EXCEEDED */
+    uint32_t pad;
+} sdb_lsm_scan_summary;
+typedef struct sdb_lsm_scan_out {    /* device arrays */
+    uint64_t *range_entry_start;     /* n + 1: range r's entries are [res[r], res[r + 1]) */
+    int32_t *range_status;           /* n */
+    uint32_t *range_ssts;            /* n: SSTs that took part in range r (rule 1) */
+    uint8_t *key_arena;              /* full keys restored */
+    uint64_t key_arena_cap;
+    uint64_t *key_off;               /* cap_entries + 1 */
+    uint32_t *sst;                   /* index into lsm->ssts of the SST that holds the row */
+    uint64_t *val_off;               /* the value: ssts[sst].data[val_off .. val_off + val_len) */
+    uint32_t *val_len;
+    uint64_t *seq;
+    uint8_t *flags;                  /* RowFlags as the iterator returns them */
+    int64_t *create_ts;              /* valid iff flags & HAS_CREATE_TS */
+    int64_t *expire_ts;              /* valid iff flags & HAS_EXPIRE_TS */
+    uint64_t cap_entries;
+    sdb_lsm_scan_summary *summary;   /* device-writable */
+} sdb_lsm_scan_out;
+uint64_t sdb_lsm_scan_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nranges,
+                                      uint64_t cand_entries, uint64_t cand_key_bytes);
+sdb_status sdb_lsm_scan(const sdb_lsm_view *lsm, const sdb_scan_ranges *ranges,
+                        const uint64_t *max_seq /* device, n; NULL = no bound */, int32_t descending,
+                        uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out *out,
+                        void *workspace, uint64_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Compaction (device): the output side of CompactionExecutor::run_subcompaction_merge

@@ -199,6 +199,24 @@ class GetOut(C.Structure):
     ]
 
 
+class LsmScanSummary(C.Structure):
+    _fields_ = [
+        ("num_entries", C.c_uint64), ("key_bytes", C.c_uint64), ("num_candidates", C.c_uint64),
+        ("candidate_key_bytes", C.c_uint64), ("num_failed_ranges", C.c_uint64), ("blocks_checked", C.c_uint64),
+        ("status", C.c_int32), ("pad", C.c_uint32),
+    ]
+
+
+class LsmScanOut(C.Structure):
+    _fields_ = [
+        ("range_entry_start", C.c_void_p), ("range_status", C.c_void_p), ("range_ssts", C.c_void_p),
+        ("key_arena", C.c_void_p), ("key_arena_cap", C.c_uint64), ("key_off", C.c_void_p), ("sst", C.c_void_p),
+        ("val_off", C.c_void_p), ("val_len", C.c_void_p), ("seq", C.c_void_p), ("flags", C.c_void_p),
+        ("create_ts", C.c_void_p), ("expire_ts", C.c_void_p), ("cap_entries", C.c_uint64),
+        ("summary", C.c_void_p),
+    ]
+
+
 class Run(C.Structure):
     _fields_ = [
         ("n", C.c_uint64), ("key_arena", C.c_void_p), ("key_off", C.c_void_p),
@@ -311,6 +329,10 @@ SIGNATURES = {
     "sdb_lsm_get_workspace_bytes": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64]),
     "sdb_lsm_get": (C.c_int, [C.POINTER(LsmView), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                               C.POINTER(GetOut), C.c_void_p, C.c_uint64, C.c_void_p]),
+    "sdb_lsm_scan_workspace_bytes": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
+                                                  C.c_uint64]),
+    "sdb_lsm_scan": (C.c_int, [C.POINTER(LsmView), C.POINTER(ScanRanges), C.c_void_p, C.c_int32, C.c_uint64,
+                               C.c_uint64, C.POINTER(LsmScanOut), C.c_void_p, C.c_uint64, C.c_void_p]),
     "sdb_merge_runs_workspace_bytes":(C.c_uint64, [C.POINTER(Run), C.c_uint32]),
     "sdb_merge_runs": (C.c_int, [C.POINTER(Run), C.c_uint32, C.POINTER(Retention), C.POINTER(MergedOut),
                                  C.c_void_p, C.c_uint64, C.c_void_p]),

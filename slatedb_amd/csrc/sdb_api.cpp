@@ -25,6 +25,11 @@ hipError_t launch_lookup(const sdb_sst_view &v, const uint8_t *key_bytes, const 
 uint64_t scan_workspace_bytes(uint64_t num_blocks, uint64_t nranges);
 hipError_t launch_scan(const sdb_sst_view &v, const sdb_scan_ranges &r, uint32_t desc, const sdb_scan_out &out, uint8_t *w,
                        hipStream_t st);
+uint64_t lsm_scan_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint64_t nranges, uint64_t cand_entries,
+                                  uint64_t cand_key_bytes);
+hipError_t launch_lsm_scan(const sdb_lsm_view &t, const sdb_scan_ranges &r, const uint64_t *max_seq, uint32_t desc,
+                           uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out &out, uint8_t *w,
+                           hipStream_t st);
 uint64_t get_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys);
 hipError_t launch_get(const sdb_lsm_view &t, const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
                       const uint64_t *max_seq, const sdb_get_out &out, uint8_t *w, hipStream_t st);
@@ -629,6 +634,42 @@ sdb_status sdb_lsm_get(const sdb_lsm_view *lsm, const uint8_t *key_bytes, const 
     if (!device_ok()) return SDB_DEVICE_ERROR;
     uint8_t *w = ws_align(workspace);
     if (launch_get(*lsm, key_bytes, key_off, nkeys, max_seq, *out, w, S(stream)) != hipSuccess) return SDB_DEVICE_ERROR;
+    return SDB_OK;
+}
+
+uint64_t sdb_lsm_scan_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nranges,
+                                      uint64_t cand_entries, uint64_t cand_key_bytes) {
+    (void)num_runs;  // runs only fix the search order: the workspace is per (range, SST)
+    return lsm_scan_workspace_bytes(total_blocks, num_ssts, nranges, cand_entries, cand_key_bytes) + 256;
+}
+
+sdb_status sdb_lsm_scan(const sdb_lsm_view *lsm, const sdb_scan_ranges *ranges, const uint64_t *max_seq,
+                        int32_t descending, uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out *out,
+                        void *workspace, uint64_t workspace_bytes, void *stream) {
+    if (!lsm || !ranges || !out) return SDB_INVALID_ARGUMENT;
+    if (lsm->total_blocks >= 0xFFFFFFFFull || lsm->num_ssts == 0xFFFFFFFFu) return SDB_LIMIT_EXCEEDED;
+    const uint64_t n = ranges->n;
+    if (lsm->num_ssts && n > (1ull << 40) / lsm->num_ssts) return SDB_LIMIT_EXCEEDED;  // per (range, SST) state
+    if (cand_entries > (1ull << 40) || cand_key_bytes > (1ull << 44)) return SDB_LIMIT_EXCEEDED;
+    if (lsm->num_ssts && (!lsm->ssts || !lsm->run_start || !lsm->first_key_off || !lsm->last_key_off ||
+                          !lsm->block_base || !lsm->first_key_bytes || !lsm->last_key_bytes))
+        return SDB_INVALID_ARGUMENT;
+    if (!out->summary || !out->range_entry_start || !out->key_off) return SDB_INVALID_ARGUMENT;
+    if (n && (!ranges->start_bytes || !ranges->start_off || !ranges->start_kind || !ranges->end_bytes ||
+              !ranges->end_off || !ranges->end_kind || !out->range_status || !out->range_ssts))
+        return SDB_INVALID_ARGUMENT;
+    if (out->key_arena_cap && !out->key_arena) return SDB_INVALID_ARGUMENT;
+    if (out->cap_entries && (!out->sst || !out->val_off || !out->val_len || !out->seq || !out->flags ||
+                             !out->create_ts || !out->expire_ts))
+        return SDB_INVALID_ARGUMENT;
+    if (!workspace || workspace_bytes < sdb_lsm_scan_workspace_bytes(lsm->total_blocks, lsm->num_ssts, lsm->num_runs, n,
+                                                                     cand_entries, cand_key_bytes))
+        return SDB_INVALID_ARGUMENT;
+    if (!device_ok()) return SDB_DEVICE_ERROR;
+    uint8_t *w = ws_align(workspace);
+    if (launch_lsm_scan(*lsm, *ranges, max_seq, descending ? 1u : 0u, cand_entries, cand_key_bytes, *out, w, S(stream)) !=
+        hipSuccess)
+        return SDB_DEVICE_ERROR;
     return SDB_OK;
 }
 

@@ -66,27 +66,7 @@ struct GetArgs {
 enum { kAccFound = 0, kAccDeleted, kAccNotFound, kAccMerge, kAccFailed, kAccBlocks, kAccFirstBad, kAccWords };
 
 __global__ __launch_bounds__(256) void k_get_validate(GetArgs a) {
-    const uint32_t ns = a.t.num_ssts, nr = a.t.num_runs;
-    int bad = 0;
-    for (uint32_t i = threadIdx.x; i < ns; i += blockDim.x) {
-        const sdb_sst_view v = a.t.ssts[i];
-        const uint64_t b0 = a.t.block_base[i], b1 = a.t.block_base[i + 1];
-        if (b1 < b0 || b1 - b0 != v.num_blocks || v.num_blocks >= 0xFFFFFFFFull || b1 > a.t.total_blocks) bad = 1;
-        if (i == 0 && b0 != 0) bad = 1;
-        if (i == ns - 1 && b1 != a.t.total_blocks) bad = 1;
-        if (a.t.first_key_off[i + 1] < a.t.first_key_off[i] || a.t.last_key_off[i + 1] < a.t.last_key_off[i]) bad = 1;
-        int st = 0;
-        if (v.sst_version != 1 && v.sst_version != 2) st = SDB_INVALID_VERSION;
-        else if (v.num_blocks && (!v.data || !v.block_off || !v.index_keys || !v.index_key_off)) st = SDB_INVALID_ARGUMENT;
-        a.sstat[i] = st;
-    }
-    for (uint32_t r = threadIdx.x; r < nr; r += blockDim.x) {
-        const uint32_t r0 = a.t.run_start[r], r1 = a.t.run_start[r + 1];
-        if (r1 < r0 || r1 > ns) bad = 1;
-        if (r == 0 && r0 != 0) bad = 1;
-        if (r == nr - 1 && r1 != ns) bad = 1;
-    }
-    bad = __syncthreads_or(bad);
+    const int bad = lsm_validate(a.t, a.sstat);
     if (threadIdx.x == 0) {
         *a.bad = bad ? 1u : 0u;
         for (int i = 0; i < kAccWords; i++) a.acc[i] = i == kAccFirstBad ? ~0ull : 0ull;

@@ -1,0 +1,633 @@
+// sdb_lsm_scan.hip — batched Db::scan over a device-resident tree of encoded SSTs for gfx950.
+//
+// Replaces the on-disk part of Reader::scan_with_options (reader.rs:275-320) -> DbIterator::new
+// (db_iter.rs:189-257), drained, many ranges per call:
+//   SSTs        every SST whose [first_key, last_key] meets the range (the reference opens every L0 SST and, per
+//               sorted run, tables_covering_range: segment_iterator.rs:355-414, db_state.rs:600-660)
+//   per SST     partitions_covering_range(index, start, end), every block of it CRC-checked and parsed
+//               (partitioned_keyspace.rs:87-110, format/sst.rs:1029-1038); the entries the range contains
+//   filter      versions above max_seq dropped before the merge (FilterIterator::new_with_max_seq,
+//               db_iter.rs:205-217)
+//   merge       key ascending, seq descending, the newest version per key (MergeIterator with dedup,
+//               merge_iterator.rs:55-69, 180-209); a tombstone yields nothing (db_iter.rs:280-303), a merge
+//               operand fails the range (MergeOperatorRequiredIterator, merge_operator.rs:213-223)
+//
+// The unit of work is a (range, SST) pair, p = range * num_ssts + sst, so a range's pairs and its staged
+// candidates are contiguous.  What depends only on a block is computed once per tree block; a pair's candidates
+// are the rows between two ranks in its SST, found by clipping one block at each end.
+//   k_ls_validate  one workgroup: lsm_validate of sdb_read.h (shared with sdb_lsm_get); resets the control words
+//   k_ls_ranges    thread per range: range offsets that descend make the call malformed
+//   k_ls_locate    thread per pair: participation, the block range, the marks at block_base[sst] + block
+//   k_check        wave per marked tree block: bounds + CRC (sdb_lookup.hip, shared)
+//   k_ls_block     thread per tree block: every row parsed (for_each_row) -> status, entries, restored-key bytes
+//   scans          entries / key bytes / failed / read over the tree blocks
+//   k_ls_edge      thread per pair: the lowest failing block, else the ranks [g0, g1) of its candidates
+//   k_ls_rstat     thread per range: status (lowest SST, then lowest block), range_ssts; a failing range stages
+//                  nothing
+//   scans          candidates / key bytes / work items over the pairs; k_ls_gate: do the candidates fit (and the winner flags zeroed)
+//   k_ls_stage     thread per (pair, block) item: keys restored into the staging arena, seq, flags and the row's
+//                  position, contiguous per pair in physical order (an SST holds key ascending, seq descending)
+//   k_ls_rank      thread per candidate: merged rank in its range = own index + one binary search per other
+//                  participating SST (the k_mg_rank pattern); the candidate's index goes to that rank, and with it
+//                  the winner flag: visible, and in no SST the last candidate before it is a visible version of
+//                  its key; an operand winner flags its range
+//   scan           winners / their key bytes over the merged positions
+//   k_ls_count     thread per range: rule 4, the totals -> scans -> range_entry_start
+//   k_ls_final     summary, capacity check
+//   k_ls_emit      thread per winner: key and columns (the row parsed once more) at its place
+#include "sdb_read.h"
+#include "sdb_decode.h"
+
+namespace sdb {
+
+struct LsArgs {
+    sdb_lsm_view t;
+    sdb_scan_ranges r;
+    const uint64_t *max_seq;
+    sdb_lsm_scan_out out;
+    uint32_t desc, pad;
+    uint64_t cand_entries, cand_key_bytes, pairs;
+    // per tree block
+    uint8_t *mark;                  // 1 = some range reads it (cleared by k_check)
+    int32_t *bstat;                 // -1 = not read, else the block's sdb_status
+    uint64_t *cnt, *kb, *bbad, *rd; // entries, restored-key bytes, failed, read
+    uint64_t *pc, *pk, *pb, *pr;    // their exclusive scans (total_blocks + 1)
+    int32_t *sstat;                 // per SST: 0, SDB_INVALID_VERSION or SDB_INVALID_ARGUMENT
+    // per pair
+    uint8_t *part;                  // the SST takes part in the range
+    uint32_t *bs, *be;              // its block range in the SST
+    int32_t *pst;                   // the pair's status: the SST's, else its lowest failing block's
+    uint32_t *fb;                   // the block of the first candidate
+    uint64_t *g0, *g1, *k0;         // tree-wide row ranks [g0, g1) of the candidates; key-byte rank of g0
+    uint64_t *pn, *pkb, *pit;       // candidates, their key bytes, work items (blocks with candidates)
+    uint64_t *cs, *cks, *pis;       // exclusive scans (pairs + 1)
+    // per range
+    uint32_t *rop;                  // 1 = an operand won a key of the range
+    uint64_t *rn, *rkb, *rks;       // entries, key bytes; the key-byte scan (n + 1)
+    // per candidate
+    uint8_t *ckeys;                 // restored keys (cand_key_bytes)
+    uint64_t *ckoff, *cseq;
+    uint32_t *cklen, *cblk, *cat;   // key length; block in the SST; V2: byte offset, V1: index of the row
+    uint8_t *cflags;
+    uint64_t *morder;               // candidate at merged position m
+    uint64_t *wn, *wkb, *wpos, *wkpos;  // winner flag / key bytes per merged position and their scans
+    uint64_t *tx, *ty;              // scan tiles
+    unsigned long long *ctl;        // kCtl* words
+};
+enum { kCtlFirstBad = 0, kCtlFailed, kCtlBad, kCtlGo1, kCtlGo2, kCtlWords = 8 };
+
+struct Bound {
+    const uint8_t *t;
+    uint32_t n, kind;
+};
+SDB_DEV Bound ls_start(const LsArgs &a, uint64_t r) {
+    return Bound{a.r.start_bytes + a.r.start_off[r], (uint32_t)(a.r.start_off[r + 1] - a.r.start_off[r]), a.r.start_kind[r]};
+}
+SDB_DEV Bound ls_end(const LsArgs &a, uint64_t r) {
+    return Bound{a.r.end_bytes + a.r.end_off[r], (uint32_t)(a.r.end_off[r + 1] - a.r.end_off[r]), a.r.end_kind[r]};
+}
+// BytesRange::contains from sign(key cmp bound)
+SDB_DEV bool ls_precedes(const Bound &s, int c) { return s.kind == SDB_BOUND_INCLUDED ? c < 0 : (s.kind == SDB_BOUND_EXCLUDED && c <= 0); }
+SDB_DEV bool ls_exceeds(const Bound &e, int c) { return e.kind == SDB_BOUND_INCLUDED ? c > 0 : (e.kind == SDB_BOUND_EXCLUDED && c >= 0); }
+SDB_DEV bool ls_bad_kind(const Bound &s, const Bound &e) { return s.kind > SDB_BOUND_EXCLUDED || e.kind > SDB_BOUND_EXCLUDED; }
+
+__global__ __launch_bounds__(256) void k_ls_validate(LsArgs a) {
+    const int bad = lsm_validate(a.t, a.sstat);
+    if (threadIdx.x == 0) {
+        for (int i = 0; i < kCtlWords; i++) a.ctl[i] = i == kCtlFirstBad ? ~0ull : 0ull;
+        a.ctl[kCtlBad] = bad ? 1ull : 0ull;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_ls_ranges(LsArgs a) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= a.r.n) return;
+    if (a.r.start_off[r + 1] < a.r.start_off[r] || a.r.end_off[r + 1] < a.r.end_off[r]) atomicOr(&a.ctl[kCtlBad], 1ull);
+}
+
+// Thread t of the per-pair kernels: neighbouring ranges of one SST share a wave.
+SDB_DEV void ls_pair(const LsArgs &a, uint64_t t, uint64_t &r, uint32_t &i, uint64_t &p) {
+    r = t % a.r.n;
+    i = (uint32_t)(t / a.r.n);
+    p = r * a.t.num_ssts + i;
+}
+
+__global__ __launch_bounds__(256) void k_ls_locate(LsArgs a) {
+    if (a.ctl[kCtlBad]) return;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < a.pairs; t += (uint64_t)gridDim.x * blockDim.x) {
+        uint64_t r, p;
+        uint32_t i;
+        ls_pair(a, t, r, i, p);
+        const Bound s = ls_start(a, r), e = ls_end(a, r);
+        const sdb_sst_view v = a.t.ssts[i];
+        bool part = !ls_bad_kind(s, e) && v.num_blocks > 0;
+        if (part && s.kind && e.kind) {  // empty as a set
+            const int c = cmp_bytes(s.t, s.n, e.t, e.n, 0).c;
+            part = !(c > 0 || (c == 0 && (s.kind == SDB_BOUND_EXCLUDED || e.kind == SDB_BOUND_EXCLUDED)));
+        }
+        if (part && s.kind) {  // the SST's last key precedes the range
+            const uint64_t o = a.t.last_key_off[i];
+            part = !ls_precedes(s, cmp_bytes(a.t.last_key_bytes + o, (uint32_t)(a.t.last_key_off[i + 1] - o), s.t, s.n, 0).c);
+        }
+        if (part && e.kind) {  // its first key exceeds it
+            const uint64_t o = a.t.first_key_off[i];
+            part = !ls_exceeds(e, cmp_bytes(a.t.first_key_bytes + o, (uint32_t)(a.t.first_key_off[i + 1] - o), e.t, e.n, 0).c);
+        }
+        uint64_t start = 0, end = 0;
+        if (part && !a.sstat[i]) {  // partitions_covering_range, as k_sc_locate
+            end = v.num_blocks;
+            if (s.kind) {
+                const uint64_t lt = partition_point(v, s.t, s.n, false);
+                start = lt > 0 ? lt - 1 : 0;
+            }
+            if (e.kind) {
+                const uint64_t le = partition_point(v, e.t, e.n, true);
+                if (le == 0) {
+                    end = start;
+                } else if (e.kind == SDB_BOUND_INCLUDED) {
+                    end = le;
+                } else {
+                    const uint64_t q = le - 1, f0 = v.index_key_off[q], f1 = v.index_key_off[q + 1];
+                    end = cmp_bytes(v.index_keys + f0, (uint32_t)(f1 - f0), e.t, e.n, 0).c == 0 ? q : q + 1;
+                }
+            }
+            if (end < start) end = start;
+            const uint64_t base = a.t.block_base[i];
+            for (uint64_t b = start; b < end; b++) a.mark[base + b] = 1;
+        }
+        a.part[p] = part;
+        a.bs[p] = (uint32_t)start;
+        a.be[p] = (uint32_t)end;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_ls_block(LsArgs a) {
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= a.t.total_blocks) return;
+    int st = a.ctl[kCtlBad] ? -1 : a.bstat[k];
+    uint64_t cnt = 0, kb = 0;
+    if (st == 0) {
+        const uint32_t i = sst_of_block(a.t, k);
+        const sdb_sst_view v = a.t.ssts[i];
+        Blk b;
+        st = blk_open(v, k - a.t.block_base[i], b);
+        if (!st)
+            st = for_each_row(v.sst_version, b, [&](uint32_t x, uint32_t, const Row &r) {
+                cnt = x + 1;
+                kb += r.sh + r.un;
+            });
+    }
+    if (st != 0) cnt = kb = 0;
+    a.bstat[k] = st;
+    a.cnt[k] = cnt;
+    a.kb[k] = kb;
+    a.bbad[k] = st > 0;
+    a.rd[k] = st != -1;
+}
+
+// In checked block k of v: the first row that does not precede bd (a start bound), or that exceeds it (an end
+// bound), by the incremental comparators; kbb = the key bytes of the rows before it.  None: the block's count.
+SDB_DEV void ls_find(const sdb_sst_view &v, uint64_t k, const Bound &bd, bool is_end, uint32_t &row, uint64_t &kbb) {
+    row = 0;
+    kbb = 0;
+    Blk b;
+    if (blk_open(v, k, b)) return;
+    const bool v2 = v.sst_version == 2;
+    bool found = false;
+    uint32_t n = 0;
+    uint64_t kb = 0;
+    Cmp c{0, 0, 0};
+    for_each_row(v.sst_version, b, [&](uint32_t x, uint32_t, const Row &r) {
+        if (found) return;
+        if (v2) c = x == 0 ? cmp_bytes(b.d + r.suf, r.un, bd.t, bd.n, 0) : cmp_next(c, r.sh, b.d + r.suf, r.un, bd.t, bd.n);
+        else if (v1_cmp(b, x, bd.t, bd.n, c)) found = true;
+        if (found || (is_end ? ls_exceeds(bd, c.c) : !ls_precedes(bd, c.c))) {
+            found = true;
+            return;
+        }
+        n = x + 1;
+        kb += r.sh + r.un;
+    });
+    row = n;
+    kbb = kb;
+}
+
+__global__ __launch_bounds__(64) void k_ls_edge(LsArgs a) {
+    const bool bad = a.ctl[kCtlBad] != 0;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < a.pairs; t += (uint64_t)gridDim.x * blockDim.x) {
+        uint64_t r, p;
+        uint32_t i;
+        ls_pair(a, t, r, i, p);
+        int st = 0;
+        uint32_t fb = 0;
+        uint64_t g0 = 0, g1 = 0, k0 = 0, k1 = 0, items = 0;
+        const bool part = !bad && a.part[p];
+        if (part && !(st = a.sstat[i]) && a.be[p] > a.bs[p]) {
+            const uint64_t base = a.t.block_base[i], bs = a.bs[p], be = a.be[p];
+            if (a.pb[base + be] != a.pb[base + bs]) {  // the lowest failing block of [bs, be)
+                uint64_t x = bs, y = be - 1;
+                while (x < y) {
+                    const uint64_t m = x + (y - x) / 2;
+                    if (a.pb[base + m + 1] > a.pb[base + bs]) y = m;
+                    else x = m + 1;
+                }
+                st = a.bstat[base + x];
+            } else {
+                // The rows of [bs, be) that the range contains lie between two ranks.  Interior blocks hold only keys
+                // of the range, except where a bound's key fills whole blocks (a long run of versions under an
+                // excluded bound): the walks move inwards past blocks that keep nothing.
+                const sdb_sst_view v = a.t.ssts[i];
+                const Bound s = ls_start(a, r), e = ls_end(a, r);
+                uint32_t row;
+                uint64_t kbb;
+                g0 = a.pc[base + be];
+                k0 = a.pk[base + be];
+                fb = (uint32_t)be;
+                if (!s.kind) {
+                    g0 = a.pc[base + bs];
+                    k0 = a.pk[base + bs];
+                    fb = (uint32_t)bs;
+                }
+                for (uint64_t k = bs; s.kind && k < be; k++) {
+                    ls_find(v, k, s, false, row, kbb);
+                    if (row < a.cnt[base + k]) {
+                        g0 = a.pc[base + k] + row;
+                        k0 = a.pk[base + k] + kbb;
+                        fb = (uint32_t)k;
+                        break;
+                    }
+                }
+                g1 = a.pc[e.kind ? base + bs : base + be];
+                k1 = a.pk[e.kind ? base + bs : base + be];
+                for (uint64_t k = be; e.kind && k-- > bs;) {
+                    ls_find(v, k, e, true, row, kbb);
+                    if (row > 0) {
+                        g1 = a.pc[base + k] + row;
+                        k1 = a.pk[base + k] + kbb;
+                        break;
+                    }
+                }
+                if (g1 <= g0 || k1 < k0) {
+                    g1 = g0;
+                    k1 = k0;
+                } else {  // the blocks fb .. the block of row g1 - 1
+                    uint64_t x = fb, y = be - 1;
+                    while (x < y) {
+                        const uint64_t m = x + (y - x) / 2;
+                        if (a.pc[base + m + 1] >= g1) y = m;
+                        else x = m + 1;
+                    }
+                    items = x - fb + 1;
+                }
+            }
+        }
+        a.part[p] = part;
+        a.pst[p] = st;
+        a.fb[p] = fb;
+        a.g0[p] = g0;
+        a.g1[p] = g1;
+        a.k0[p] = k0;
+        a.pn[p] = st ? 0 : g1 - g0;
+        a.pkb[p] = st ? 0 : k1 - k0;
+        a.pit[p] = st ? 0 : items;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_ls_rstat(LsArgs a) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= a.r.n) return;
+    const uint32_t S = a.t.num_ssts;
+    int st = 0;
+    uint32_t ns = 0;
+    if (a.ctl[kCtlBad]) {
+        st = SDB_INVALID_ARGUMENT;
+    } else if (ls_bad_kind(ls_start(a, r), ls_end(a, r))) {
+        st = SDB_INVALID_ARGUMENT;
+    } else {
+        for (uint32_t i = 0; i < S; i++) {
+            if (!a.part[r * S + i]) continue;
+            ns++;
+            if (!st) st = a.pst[r * S + i];
+        }
+    }
+    if (st)
+        for (uint32_t i = 0; i < S; i++) a.pn[r * S + i] = a.pkb[r * S + i] = a.pit[r * S + i] = 0;
+    a.out.range_status[r] = st;
+    a.out.range_ssts[r] = ns;
+    a.rop[r] = 0;
+}
+
+// Do the candidates fit; and the winner flags of every merged position zeroed (k_ls_rank sets the winners').
+__global__ __launch_bounds__(256) void k_ls_gate(LsArgs a) {
+    const uint64_t t0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t0 == 0) a.ctl[kCtlGo1] = a.cs[a.pairs] <= a.cand_entries && a.cks[a.pairs] <= a.cand_key_bytes;
+    for (uint64_t m = t0; m < a.cand_entries; m += (uint64_t)gridDim.x * blockDim.x) a.wn[m] = a.wkb[m] = 0;
+}
+
+SDB_DEV void ls_copy(uint8_t *dst, const uint8_t *src, uint32_t n) {
+    for (uint32_t j = 0; j < n; j++) dst[j] = src[j];
+}
+// The last x in [0, n) with s[x * stride] <= v (s ascends, s[0] <= v).
+SDB_DEV uint64_t ls_last_le(const uint64_t *s, uint64_t n, uint64_t stride, uint64_t v) {
+    uint64_t x = 0, y = n;
+    while (y - x > 1) {
+        const uint64_t m = x + (y - x) / 2;
+        if (s[m * stride] <= v) x = m;
+        else y = m;
+    }
+    return x;
+}
+
+__global__ __launch_bounds__(64) void k_ls_stage(LsArgs a) {
+    if (!a.ctl[kCtlGo1]) return;
+    const uint32_t S = a.t.num_ssts;
+    const uint64_t total = a.pis[a.pairs];
+    for (uint64_t it = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; it < total; it += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t p = ls_last_le(a.pis, a.pairs, 1, it);
+        const uint32_t i = (uint32_t)(p % S);
+        const sdb_sst_view v = a.t.ssts[i];
+        const uint64_t kl = a.fb[p] + (it - a.pis[p]), K = a.t.block_base[i] + kl;  // the block: in the SST, in the tree
+        if (kl >= v.num_blocks) continue;
+        const uint64_t g0 = a.g0[p], g1 = a.g1[p], c0 = a.pc[K], n = a.cnt[K];
+        const uint64_t lo = g0 > c0 ? g0 - c0 : 0, hi = g1 - c0 < n ? g1 - c0 : n;
+        if (g1 <= c0 || hi <= lo) continue;
+        const uint64_t cbase = a.cs[p], cend = a.cs[p + 1], kbase = a.cks[p], kend = a.cks[p + 1];
+        Blk b;
+        if (blk_open(v, kl, b)) continue;
+        const bool v2 = v.sst_version == 2;
+        uint64_t kb = 0;              // key bytes of the rows before the current one
+        const uint8_t *prev = nullptr;  // the previous staged key (V2 chains from it)
+        for_each_row(v.sst_version, b, [&](uint32_t x, uint32_t pos, const Row &r) {
+            const uint32_t L = r.sh + r.un;
+            const uint64_t kbx = kb;
+            kb += L;
+            if (x < lo || x >= hi) return;
+            const uint64_t c = cbase + (c0 + x - g0), ko = kbase + (a.pk[K] + kbx - a.k0[p]);
+            if (c >= cend || ko > kend || L > kend - ko) return;  // never out of the pair's slots
+            uint8_t *dst = a.ckeys + ko;
+            if (!v2) {
+                ls_copy(dst, b.d + 4, r.sh);
+            } else if (prev) {
+                ls_copy(dst, prev, r.sh);
+            } else if (r.sh) {  // chain from the block's first row: row y sets key[y.sh, y.sh + y.un)
+                uint32_t rp = 0;
+                for (uint32_t y = 0; y < x; y++) {
+                    Row q;
+                    if (v2_row(b, rp, q)) break;
+                    for (uint32_t j = q.sh; j < q.sh + q.un && j < r.sh; j++) dst[j] = b.d[q.suf + j - q.sh];
+                    rp = q.next;
+                }
+            }
+            ls_copy(dst + r.sh, b.d + r.suf, r.un);
+            prev = dst;
+            a.ckoff[c] = ko;
+            a.cklen[c] = L;
+            a.cblk[c] = (uint32_t)kl;
+            a.cat[c] = v2 ? pos : x;
+            a.cseq[c] = r.seq;
+            a.cflags[c] = r.flags;
+        });
+    }
+}
+
+SDB_DEV int ls_key_cmp(const LsArgs &a, uint64_t x, const uint8_t *t, uint32_t nt) {
+    return cmp_bytes(a.ckeys + a.ckoff[x], a.cklen[x], t, nt, 0).c;
+}
+
+// Candidate q is a visible version of the key t.
+SDB_DEV bool ls_hides(const LsArgs &a, uint64_t q, uint64_t bound, const uint8_t *t, uint32_t nt) {
+    return a.cseq[q] <= bound && a.cklen[q] == nt && ls_key_cmp(a, q, t, nt) == 0;
+}
+
+__global__ __launch_bounds__(64) void k_ls_rank(LsArgs a) {
+    if (!a.ctl[kCtlGo1]) return;
+    const uint32_t S = a.t.num_ssts;
+    const uint64_t total = a.cs[a.pairs];
+    for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < total; c += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t p = ls_last_le(a.cs, a.pairs, 1, c), r = p / S;
+        const uint32_t i = (uint32_t)(p % S);
+        const uint8_t *t = a.ckeys + a.ckoff[c];
+        const uint32_t nt = a.cklen[c];
+        const uint64_t seq = a.cseq[c], bound = a.max_seq ? a.max_seq[r] : ~0ull;
+        uint64_t rank = c - a.cs[p];
+        // c loses if it is not visible, or a visible version of its key comes before it.  In every SST the versions
+        // of a key stand newest first, so those above the bound come first: if any visible one comes before c, the last
+        // candidate of that SST before c is one.
+        bool lose = seq > bound || (rank > 0 && ls_hides(a, c - 1, bound, t, nt));
+        for (uint32_t j = 0; j < S; j++) {  // the candidates of SST j that come before c
+            if (j == i) continue;
+            uint64_t lo = a.cs[r * S + j], hi = a.cs[r * S + j + 1];
+            const uint64_t first = lo;
+            while (lo < hi) {
+                const uint64_t m = lo + (hi - lo) / 2;
+                const int k = ls_key_cmp(a, m, t, nt);
+                const uint64_t sm = a.cseq[m];
+                if (k < 0 || (k == 0 && (sm > seq || (sm == seq && j < i)))) lo = m + 1;
+                else hi = m;
+            }
+            rank += lo - first;
+            if (!lose && lo > first) lose = ls_hides(a, lo - 1, bound, t, nt);
+        }
+        const uint64_t rs = a.cs[r * S], re = a.cs[(r + 1) * S];
+        if (rank >= re - rs) continue;  // rows that are not sorted: never out of the range's slots
+        const uint8_t f = a.cflags[c];
+        a.morder[rs + rank] = c;
+        if (!lose && (f & SDB_FLAG_MERGE_OPERAND)) a.rop[r] = 1;
+        if (!lose && !(f & (SDB_FLAG_MERGE_OPERAND | SDB_FLAG_TOMBSTONE))) {  // k_ls_gate zeroed the flags
+            a.wn[rs + rank] = 1;
+            a.wkb[rs + rank] = nt;
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void k_ls_count(LsArgs a) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= a.r.n) return;
+    const uint32_t S = a.t.num_ssts;
+    int st = a.out.range_status[r];
+    uint64_t n = 0, kb = 0;
+    if (a.ctl[kCtlGo1]) {
+        if (!st && a.rop[r]) st = SDB_MERGE_OPERATOR_MISSING;
+        if (!st) {
+            const uint64_t rs = a.cs[r * S], re = a.cs[(r + 1) * S];
+            n = a.wpos[re] - a.wpos[rs];
+            kb = a.wkpos[re] - a.wkpos[rs];
+        }
+        a.out.range_status[r] = st;
+    }
+    a.rn[r] = n;
+    a.rkb[r] = kb;
+    if (st) {
+        atomicAdd(&a.ctl[kCtlFailed], 1ull);
+        atomicMin(&a.ctl[kCtlFirstBad], (unsigned long long)(r << 8 | (uint64_t)st));
+    }
+}
+
+__global__ void k_ls_final(LsArgs a) {
+    if (threadIdx.x != 0) return;
+    const uint64_t n = a.r.n;
+    sdb_lsm_scan_summary s{};
+    s.num_entries = a.out.range_entry_start[n];
+    s.key_bytes = a.rks[n];
+    s.num_candidates = a.cs[a.pairs];
+    s.candidate_key_bytes = a.cks[a.pairs];
+    s.num_failed_ranges = a.ctl[kCtlFailed];
+    s.blocks_checked = a.pr[a.t.total_blocks];
+    s.status = a.ctl[kCtlFirstBad] == ~0ull ? 0 : (int32_t)(a.ctl[kCtlFirstBad] & 0xFF);
+    const bool fits = a.ctl[kCtlGo1] && s.num_entries <= a.out.cap_entries && s.key_bytes <= a.out.key_arena_cap;
+    if (!fits) s.status = SDB_LIMIT_EXCEEDED;
+    else a.out.key_off[s.num_entries] = s.key_bytes;
+    *a.out.summary = s;
+    a.ctl[kCtlGo2] = fits;
+}
+
+__global__ __launch_bounds__(64) void k_ls_emit(LsArgs a) {
+    if (!a.ctl[kCtlGo2]) return;
+    const uint32_t S = a.t.num_ssts;
+    const uint64_t total = a.cs[a.pairs];
+    for (uint64_t m = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; m < total; m += (uint64_t)gridDim.x * blockDim.x) {
+        if (!a.wn[m]) continue;
+        const uint64_t r = ls_last_le(a.cs, a.r.n, S, m);
+        if (a.out.range_status[r]) continue;
+        const uint64_t rs = a.cs[r * S], c = a.morder[m];
+        const uint64_t E0 = a.out.range_entry_start[r], N = a.rn[r], K0 = a.rks[r], KB = a.rkb[r];
+        const uint64_t x = a.wpos[m] - a.wpos[rs], kx = a.wkpos[m] - a.wkpos[rs];
+        const uint32_t L = a.cklen[c];
+        if (x >= N || kx > KB || L > KB - kx) continue;
+        const uint64_t di = a.desc ? N - 1 - x : x, dk = a.desc ? KB - kx - L : kx;
+        const uint32_t i = (uint32_t)(ls_last_le(a.cs, a.pairs, 1, c) % S);
+        const sdb_sst_view v = a.t.ssts[i];
+        Blk b;
+        Row row;
+        if (blk_open(v, a.cblk[c], b)) continue;
+        if (v.sst_version == 2 ? v2_row(b, a.cat[c], row) : v1_row(b, a.cat[c], row)) continue;
+        ls_copy(a.out.key_arena + K0 + dk, a.ckeys + a.ckoff[c], L);
+        a.out.key_off[E0 + di] = K0 + dk;
+        a.out.sst[E0 + di] = i;
+        put_row(a.out, E0 + di, b.base, row);
+    }
+}
+
+// The workspace arrays of a scan of a.r.n ranges over the tree a.t with room for a.cand_entries candidates of
+// a.cand_key_bytes key bytes, bound into a from w; -> their size.
+static uint64_t lsm_scan_bind(LsArgs &a, uint8_t *w) {
+    const uint64_t tb = a.t.total_blocks, n = a.r.n, P = n * a.t.num_ssts, ce = a.cand_entries;
+    uint64_t big = tb > n ? tb : n;
+    if (P > big) big = P;
+    if (ce > big) big = ce;
+    const uint64_t nt = (big + 1023) / 1024 + 2;  // scan tiles
+    a.pairs = P;
+    Carver c{w, 0};
+    c.take(a.mark, tb + 1);
+    c.take(a.bstat, tb + 1);
+    c.take(a.cnt, tb + 1);
+    c.take(a.kb, tb + 1);
+    c.take(a.bbad, tb + 1);
+    c.take(a.rd, tb + 1);
+    c.take(a.pc, tb + 2);
+    c.take(a.pk, tb + 2);
+    c.take(a.pb, tb + 2);
+    c.take(a.pr, tb + 2);
+    c.take(a.sstat, (uint64_t)a.t.num_ssts + 1);
+    c.take(a.part, P + 1);
+    c.take(a.bs, P + 1);
+    c.take(a.be, P + 1);
+    c.take(a.pst, P + 1);
+    c.take(a.fb, P + 1);
+    c.take(a.g0, P + 1);
+    c.take(a.g1, P + 1);
+    c.take(a.k0, P + 1);
+    c.take(a.pn, P + 1);
+    c.take(a.pkb, P + 1);
+    c.take(a.pit, P + 1);
+    c.take(a.cs, P + 2);
+    c.take(a.cks, P + 2);
+    c.take(a.pis, P + 2);
+    c.take(a.rop, n + 1);
+    c.take(a.rn, n + 1);
+    c.take(a.rkb, n + 1);
+    c.take(a.rks, n + 2);
+    c.take(a.ckeys, a.cand_key_bytes + 1);
+    c.take(a.ckoff, ce + 1);
+    c.take(a.cseq, ce + 1);
+    c.take(a.cklen, ce + 1);
+    c.take(a.cblk, ce + 1);
+    c.take(a.cat, ce + 1);
+    c.take(a.cflags, ce + 1);
+    c.take(a.morder, ce + 1);
+    c.take(a.wn, ce + 1);
+    c.take(a.wkb, ce + 1);
+    c.take(a.wpos, ce + 2);
+    c.take(a.wkpos, ce + 2);
+    c.take(a.tx, nt);
+    c.take(a.ty, nt);
+    c.take(a.ctl, kCtlWords);
+    return c.off;
+}
+
+uint64_t lsm_scan_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint64_t nranges, uint64_t cand_entries,
+                                  uint64_t cand_key_bytes) {
+    LsArgs a{};
+    a.t.total_blocks = total_blocks;
+    a.t.num_ssts = num_ssts;
+    a.r.n = nranges;
+    a.cand_entries = cand_entries;
+    a.cand_key_bytes = cand_key_bytes;
+    return lsm_scan_bind(a, nullptr);
+}
+
+static uint32_t ls_grid(uint64_t items, uint32_t threads) {  // the kernels stride past this cap
+    uint64_t g = (items + threads - 1) / threads;
+    if (g < 1) g = 1;
+    return (uint32_t)(g > 32768 ? 32768 : g);
+}
+
+hipError_t launch_lsm_scan(const sdb_lsm_view &t, const sdb_scan_ranges &r, const uint64_t *max_seq, uint32_t desc,
+                           uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out &out, uint8_t *w,
+                           hipStream_t st) {
+    const uint64_t tb = t.total_blocks, n = r.n;
+    hipError_t e;
+    if (n == 0 || t.num_ssts == 0 || tb == 0) {  // every range is empty
+        if ((e = hipMemsetAsync(out.summary, 0, sizeof(sdb_lsm_scan_summary), st)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(out.range_entry_start, 0, 8 * (n + 1), st)) != hipSuccess) return e;
+        if (n && (e = hipMemsetAsync(out.range_status, 0, 4 * n, st)) != hipSuccess) return e;
+        if (n && (e = hipMemsetAsync(out.range_ssts, 0, 4 * n, st)) != hipSuccess) return e;
+        return hipMemsetAsync(out.key_off, 0, 8, st);
+    }
+    LsArgs a{};
+    a.t = t;
+    a.r = r;
+    a.max_seq = max_seq;
+    a.out = out;
+    a.desc = desc;
+    a.cand_entries = cand_entries;
+    a.cand_key_bytes = cand_key_bytes;
+    lsm_scan_bind(a, w);
+    const uint64_t P = a.pairs, ce = cand_entries;
+    if ((e = hipMemsetAsync(a.mark, 0, tb, st)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(a.bstat, 0xFF, 4 * tb, st)) != hipSuccess) return e;
+    const uint32_t rw = (uint32_t)((n + 63) / 64);
+    hipLaunchKernelGGL(k_ls_validate, dim3(1), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_ls_ranges, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_ls_locate, dim3(ls_grid(P, 256)), dim3(256), 0, st, a);
+    if ((e = launch_check(CheckArgs{{}, t, (const uint32_t *)(a.ctl + kCtlBad), tb, a.mark, a.bstat}, st)) != hipSuccess) return e;
+    // the per-block, per-pair and per-item walks are latency-bound threads: one wave per workgroup spreads them over the CUs
+    hipLaunchKernelGGL(k_ls_block, dim3((uint32_t)((tb + 63) / 64)), dim3(64), 0, st, a);
+    if ((e = launch_excl_scan2(a.cnt, a.kb, tb, a.tx, a.ty, a.pc, a.pk, st)) != hipSuccess) return e;
+    if ((e = launch_excl_scan2(a.bbad, a.rd, tb, a.tx, a.ty, a.pb, a.pr, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_ls_edge, dim3(ls_grid(P, 64)), dim3(64), 0, st, a);
+    hipLaunchKernelGGL(k_ls_rstat, dim3(rw), dim3(64), 0, st, a);
+    if ((e = launch_excl_scan2(a.pit, a.pit, P, a.tx, a.ty, a.pis, a.cs, st)) != hipSuccess) return e;
+    if ((e = launch_excl_scan2(a.pn, a.pkb, P, a.tx, a.ty, a.cs, a.cks, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_ls_gate, dim3(ls_grid(ce, 256)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_ls_stage, dim3(ls_grid(ce + P, 64)), dim3(64), 0, st, a);
+    hipLaunchKernelGGL(k_ls_rank, dim3(ls_grid(ce, 64)), dim3(64), 0, st, a);
+    if ((e = launch_excl_scan2(a.wn, a.wkb, ce, a.tx, a.ty, a.wpos, a.wkpos, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_ls_count, dim3(rw), dim3(64), 0, st, a);
+    if ((e = launch_excl_scan2(a.rn, a.rkb, n, a.tx, a.ty, out.range_entry_start, a.rks, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_ls_final, dim3(1), dim3(64), 0, st, a);
+    hipLaunchKernelGGL(k_ls_emit, dim3(ls_grid(ce, 64)), dim3(64), 0, st, a);
+    return hipGetLastError();
+}
+
+}  // namespace sdb

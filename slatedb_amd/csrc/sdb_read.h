@@ -1,7 +1,8 @@
 // sdb_read.h — the one reader of an encoded block, shared by the point lookups (sdb_lookup.hip), the range
-// scans (sdb_scan.hip) and the tree gets (sdb_get.hip): the incremental key comparators, Block::decode of a
-// checked block, the entry-header and row parsers, the seeks, the row walker and the row -> column writer, the
-// index partition_point, and the bounds + CRC pass over marked blocks.  Everything takes what it reads (an
+// scans (sdb_scan.hip), the tree gets (sdb_get.hip) and the tree scans (sdb_lsm_scan.hip): the incremental key
+// comparators, Block::decode of a checked block, the entry-header and row parsers, the seeks, the row walker and
+// the row -> column writer, the index partition_point, the bounds + CRC pass over marked blocks and the
+// consistency check of a tree's index arrays.  Everything takes what it reads (an
 // sdb_sst_view, a Blk), never a kernel's argument struct.
 #pragma once
 #include "sdb_bloom.h"
@@ -485,6 +486,34 @@ SDB_DEV uint32_t sst_of_block(const sdb_lsm_view &t, uint64_t k) {
         else hi = mid;
     }
     return lo;
+}
+
+// The consistency of a tree's index arrays, by one workgroup (every thread calls it): block_base against the views'
+// num_blocks and total_blocks, run_start monotone from 0 to num_ssts, first / last key offsets that do not
+// descend; sstat[i] = 0, SDB_INVALID_VERSION or SDB_INVALID_ARGUMENT (blocks and a NULL array) of SST i.
+// -> nonzero in every thread: the tree is malformed and nothing may be read through its arrays.
+SDB_DEV int lsm_validate(const sdb_lsm_view &t, int32_t *sstat) {
+    const uint32_t ns = t.num_ssts, nr = t.num_runs;
+    int bad = 0;
+    for (uint32_t i = threadIdx.x; i < ns; i += blockDim.x) {
+        const sdb_sst_view v = t.ssts[i];
+        const uint64_t b0 = t.block_base[i], b1 = t.block_base[i + 1];
+        if (b1 < b0 || b1 - b0 != v.num_blocks || v.num_blocks >= 0xFFFFFFFFull || b1 > t.total_blocks) bad = 1;
+        if (i == 0 && b0 != 0) bad = 1;
+        if (i == ns - 1 && b1 != t.total_blocks) bad = 1;
+        if (t.first_key_off[i + 1] < t.first_key_off[i] || t.last_key_off[i + 1] < t.last_key_off[i]) bad = 1;
+        int st = 0;
+        if (v.sst_version != 1 && v.sst_version != 2) st = SDB_INVALID_VERSION;
+        else if (v.num_blocks && (!v.data || !v.block_off || !v.index_keys || !v.index_key_off)) st = SDB_INVALID_ARGUMENT;
+        sstat[i] = st;
+    }
+    for (uint32_t r = threadIdx.x; r < nr; r += blockDim.x) {
+        const uint32_t r0 = t.run_start[r], r1 = t.run_start[r + 1];
+        if (r1 < r0 || r1 > ns) bad = 1;
+        if (r == 0 && r0 != 0) bad = 1;
+        if (r == nr - 1 && r1 != ns) bad = 1;
+    }
+    return __syncthreads_or(bad);
 }
 
 // The block-check pass k_check (sdb_lookup.hip), one wave per marked block: Block::decode bounds + CRC -> bstat;

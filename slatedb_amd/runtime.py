@@ -857,6 +857,74 @@ def lsm_get_device(views, runs, keys, max_seq=None, stream=None, workspace=None)
     return res
 
 
+LSM_SCAN_COLUMNS = (("sst", "int32"),) + SCAN_COLUMNS
+LSM_SCAN_SUMMARY = ("num_entries", "key_bytes", "num_candidates", "candidate_key_bytes", "num_failed_ranges",
+                    "blocks_checked", "status")
+
+
+def lsm_scan_device(tree, ranges, max_seq=None, descending=False, stream=None, workspace=None, cand=None, cap=None):
+    """sdb_lsm_scan: a batch of Db::scan over a device-resident tree.  tree: what lsm_tree_device built.
+    ranges: a list of (start, start_kind, end, end_kind), or a dict of device tensors named as
+    scan_ranges_columnar's arrays plus "n".  max_seq: None (no bound), a list / array of n bounds, or a device
+    int64 tensor.  cand: (cand_entries, cand_key_bytes), the staging capacity; cap: (cap_entries, key_arena_cap),
+    the column capacity.  With either None the call first runs without staging room, reads the candidate totals
+    (a host synchronisation), sizes both like the staging (num_entries <= num_candidates) and runs again; with
+    both given, device tensors for ranges and max_seq and a workspace it copies nothing from the host, so it can
+    be captured into a graph.  Returns a dict of device tensors: range_entry_start (n + 1), range_status,
+    range_ssts, key_arena, key_off, the LSM_SCAN_COLUMNS and summary (the sdb_lsm_scan_summary words in
+    LSM_SCAN_SUMMARY order); what the call allocated stays alive under "_" keys."""
+    import torch
+    dev = tree["device"]
+    if isinstance(ranges, dict):
+        rt, n = ranges, int(ranges["n"])
+    else:
+        n = len(ranges)
+        rt = {}
+        for k, a in scan_ranges_columnar(ranges).items():
+            rt[k] = torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(dev)
+    if max_seq is not None and not hasattr(max_seq, "data_ptr"):
+        max_seq = torch.from_numpy(np.asarray(list(max_seq) or [0], np.uint64).view(np.int64).copy()).to(dev)
+    rg = _abi.ScanRanges(n, rt["start_bytes"].data_ptr(), rt["start_off"].data_ptr(), rt["start_kind"].data_ptr(),
+                         rt["end_bytes"].data_ptr(), rt["end_off"].data_ptr(), rt["end_kind"].data_ptr())
+    res = {"range_entry_start": torch.zeros(n + 1, dtype=torch.int64, device=dev),
+           "range_status": torch.zeros(max(n, 1), dtype=torch.int32, device=dev),
+           "range_ssts": torch.zeros(max(n, 1), dtype=torch.int32, device=dev),
+           "summary": torch.zeros(len(LSM_SCAN_SUMMARY), dtype=torch.int64, device=dev)}
+
+    def run(ce, ckb, cap_e, cap_k):
+        wsb = lib().sdb_lsm_scan_workspace_bytes(tree["total_blocks"], tree["num_ssts"], tree["num_runs"], n, ce, ckb)
+        ws = workspace if workspace is not None and workspace.numel() >= wsb else None
+        if ws is None:
+            assert workspace is None or cand is None, "workspace too small"
+            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        res["key_arena"] = torch.zeros(max(cap_k, 1), dtype=torch.uint8, device=dev)
+        res["key_off"] = torch.zeros(cap_e + 1, dtype=torch.int64, device=dev)
+        for f, dt in LSM_SCAN_COLUMNS:
+            res[f] = torch.zeros(max(cap_e, 1), dtype=getattr(torch, dt), device=dev)
+        out = _abi.LsmScanOut(res["range_entry_start"].data_ptr(), res["range_status"].data_ptr(),
+                              res["range_ssts"].data_ptr(), res["key_arena"].data_ptr(), cap_k,
+                              res["key_off"].data_ptr(), *[res[f].data_ptr() for f, _ in LSM_SCAN_COLUMNS], cap_e,
+                              res["summary"].data_ptr())
+        st = lib().sdb_lsm_scan(C.byref(tree["lsm"]), C.byref(rg), max_seq.data_ptr() if max_seq is not None else None,
+                                int(bool(descending)), ce, ckb, C.byref(out), ws.data_ptr(), wsb, _sp(stream))
+        if st:
+            raise SdbError(st, "sdb_lsm_scan")
+        res["_ws"] = ws
+
+    if cand is None or cap is None:
+        ce, ckb = cand if cand is not None else (0, 0)
+        run(ce, ckb, *(cap if cap is not None else (0, 0)))
+        _sync(stream, dev)
+        sm = res["summary"].cpu().numpy()
+        if int(sm[6]) & 0xFFFFFFFF == _abi.SDB_LIMIT_EXCEEDED:
+            ce, ckb = max(ce, int(sm[2])), max(ckb, int(sm[3]))
+            run(ce, ckb, *(cap if cap is not None else (ce, ckb)))
+    else:
+        run(cand[0], cand[1], cap[0], cap[1])
+    res.update(_tree=tree, _ranges=rt, _max_seq=max_seq)
+    return res
+
+
 # ------------------------------------------------------------------------------------------------
 # Compaction (sdb_merge_runs / sdb_sst_cuts / sdb_compactor_*)
 # ------------------------------------------------------------------------------------------------

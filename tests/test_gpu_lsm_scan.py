@@ -1,0 +1,419 @@
+"""GPU parity of the batched Db::scan (sdb_lsm_scan, slatedb_amd/csrc/sdb_lsm_scan.hip) against the model of
+tests/lsm_scan_cases.py, every column of every row and the summary: a mixed tree (L0 + sorted runs, V1 and V2, an
+SST without blocks, a key straddling two SSTs of a run), both orders, snapshot bounds, the reference's own table,
+merge operands, block errors, a malformed tree, degenerate inputs, capacities, a workspace canary, workspace reuse
+and HIP graph capture."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from slatedb_amd import _abi
+
+from . import get_cases as G
+from . import lsm_scan_cases as L
+from . import test_gpu_get as TG
+from .scan_cases import EXC, INC, U
+
+pytestmark = pytest.mark.gpu
+
+U64_MAX = G.U64_MAX
+COLS = ("sst", "val_off", "val_len", "seq", "flags")
+
+
+@pytest.fixture(scope="module")
+def rt():
+    from slatedb_amd import runtime
+    runtime.require_device()
+    return runtime
+
+
+def host(res):
+    import torch
+    from slatedb_amd import runtime
+    torch.cuda.synchronize()
+    h = {k: v.cpu().numpy() for k, v in res.items() if not k.startswith("_")}
+    for i, f in enumerate(runtime.LSM_SCAN_SUMMARY):
+        h["sum_" + f] = int(h["summary"][i]) & (0xFFFFFFFF if f == "status" else U64_MAX)
+    return h
+
+
+def model(tree, rngs, bounds, desc):
+    return [L.scan(tree, r, None if bounds is None else bounds[q], desc) for q, r in enumerate(rngs)]
+
+
+def check_ranges(exp, h):
+    """range_status, range_ssts and the summary's error and block words against the model."""
+    n = len(exp)
+    assert (h["range_status"][:n].astype(np.int64) == np.array([e.status for e in exp], np.int64)).all() if n else True
+    assert (h["range_ssts"][:n].astype(np.int64) == np.array([len(e.ssts) for e in exp], np.int64)).all() if n else True
+    assert h["sum_blocks_checked"] == len(set().union(*[e.blocks for e in exp])) if n else h["sum_blocks_checked"] == 0
+
+
+def check(tree, rngs, bounds, desc, h, exp=None):
+    """Every column of every row, and the summary, against the model.  Returns the model's results."""
+    exp = exp or model(tree, rngs, bounds, desc)
+    n = len(rngs)
+    check_ranges(exp, h)
+    rows = [r for e in exp for r in e.rows]
+    starts = np.concatenate([[0], np.cumsum([len(e.rows) for e in exp])]).astype(np.int64)
+    assert (h["range_entry_start"][:n + 1].astype(np.int64) == starts).all()
+    failed = [q for q, e in enumerate(exp) if e.status]
+    assert h["sum_num_entries"] == len(rows) and h["sum_key_bytes"] == sum(len(r[0]) for r in rows)
+    assert h["sum_num_candidates"] == sum(e.candidates for e in exp)
+    assert h["sum_candidate_key_bytes"] == sum(e.cand_key_bytes for e in exp)
+    assert h["sum_num_failed_ranges"] == len(failed)
+    assert h["sum_status"] == (exp[failed[0]].status if failed else 0)
+    cols = [L.columns(tree, r) for r in rows]
+    ko = h["key_off"][:len(rows) + 1].astype(np.int64)
+    assert (ko == np.concatenate([[0], np.cumsum([len(r[0]) for r in rows])])).all()
+    assert h["key_arena"][:int(ko[-1])].tobytes() == b"".join(r[0] for r in rows)
+    for f in COLS:
+        want = np.array([c[f] for c in cols], np.uint64)
+        have = h[f][:len(rows)].astype(np.int64).astype(np.uint64)
+        if f in ("sst", "val_len"):
+            have &= np.uint64(0xFFFFFFFF)
+        bad = np.nonzero(want != have)[0]
+        assert not bad.size, (f, int(bad[0]), rows[int(bad[0])], int(want[bad[0]]), int(have[bad[0]]))
+    for f in ("create_ts", "expire_ts"):
+        want = np.array([c[f] if c[f] is not None else 0 for c in cols], np.int64)
+        assert (h[f][:len(rows)] == want).all(), f
+    return exp
+
+
+_plain, _main = {}, {}
+
+
+def plain(rt):
+    """The plain tree (no merge operands), its device form and its ranges, built once."""
+    if not _plain:
+        tree, straddler = L.plain_tree()
+        _plain.update(tree=tree, straddler=straddler, dev=TG.device_tree(rt, tree), ranges=L.ranges(tree, straddler))
+    return _plain
+
+
+def mainm(rt):
+    if not _main:
+        tree, straddler = G.main_tree()
+        _main.update(tree=tree, straddler=straddler, dev=TG.device_tree(rt, tree))
+    return _main
+
+
+@pytest.mark.parametrize("desc", [False, True])
+def test_scan_plain_tree(rt, desc):
+    m = plain(rt)
+    tree, rngs = m["tree"], m["ranges"]
+    assert 350 <= len(rngs) <= 450
+    h = host(rt.lsm_scan_device(m["dev"], rngs, descending=desc))
+    exp = check(tree, rngs, None, desc, h)
+    assert rngs[0] == (None, U, None, U) and len(exp[0].rows) >= 150 and len(exp[0].ssts) == 10
+    assert sum(1 for e in exp if not e.ssts) >= 8 and sum(1 for e in exp if len(e.rows) > 30) >= 20
+    dup = [q for q in range(1, len(rngs)) if rngs[q] == rngs[q - 1] and exp[q].rows]
+    assert dup  # overlapping ranges get their own copies
+    for q in dup:
+        a, b = int(h["range_entry_start"][q - 1]), int(h["range_entry_start"][q])
+        assert (h["seq"][a:b] == h["seq"][b:b + (b - a)]).all() and b - a == len(exp[q].rows)
+
+
+def test_scan_max_seq(rt):
+    m = plain(rt)
+    tree, straddler = m["tree"], m["straddler"]
+    rngs, bounds = L.bounds_for(tree, m["ranges"][:150], straddler)
+    h = host(rt.lsm_scan_device(m["dev"], rngs, max_seq=bounds))
+    exp = check(tree, rngs, bounds, False, h)
+    assert any(b == 0 for b in bounds) and any(b == U64_MAX for b in bounds)
+    assert sum(1 for r, b in zip(rngs, bounds) if r[0] == straddler and r[1] == INC and r[2] == straddler) >= 4
+    # a tombstone at the bound hides the key; just under it the older value shows
+    pairs = 0
+    for q in range(len(rngs) - 1):
+        if rngs[q] == rngs[q + 1] and bounds[q] == bounds[q + 1] + 1 and not exp[q].rows and exp[q + 1].rows:
+            pairs += 1
+    assert pairs >= 3
+    hd = host(rt.lsm_scan_device(m["dev"], rngs, max_seq=bounds, descending=True))
+    check(tree, rngs, bounds, True, hd)
+
+
+@pytest.mark.parametrize("version", [2, 1])
+def test_scan_golden_cases(rt, version):
+    """The reference's ScanTestCase table through the device: the recorded expectation."""
+    cases = L.golden_cases()
+    assert len(cases) == L.KEPT_CASES
+    for c in cases:
+        tree = L.golden_tree(c, version)
+        rngs = [L.golden_range(c)]
+        bounds = None if c["max_seq"] is None else [c["max_seq"]]
+        h = host(rt.lsm_scan_device(TG.device_tree(rt, tree), rngs, max_seq=bounds))
+        check(tree, rngs, bounds, False, h)
+        have = []
+        ko = h["key_off"].astype(np.int64)
+        for x in range(int(h["sum_num_entries"])):
+            data = tree.leaves[int(h["sst"][x])].sst.data
+            vo, vl = int(h["val_off"][x]), int(h["val_len"][x])
+            have.append([h["key_arena"][ko[x]:ko[x + 1]].tobytes().decode(), data[vo:vo + vl].tobytes().decode()])
+        assert have == c["expected"], c["description"]
+
+
+def test_scan_merge_operands(rt):
+    m = mainm(rt)
+    tree = m["tree"]
+    rngs = L.narrow_ranges(tree) + [(None, U, None, U)]
+    h = host(rt.lsm_scan_device(m["dev"], rngs))
+    exp = check(tree, rngs, None, False, h)
+    st = [e.status for e in exp]
+    assert st.count(_abi.SDB_MERGE_OPERATOR_MISSING) >= 30 and st.count(0) >= 30 and st[-1] == _abi.SDB_MERGE_OPERATOR_MISSING
+    # an operand above the bound, and an operand hidden by a newer value, do not fail the range
+    small = G.Tree([[G.leaf_of([(b"a", 0, b"x", 95, None, None), (b"k", 1, b"op", 90, None, 77)], 2, 4096)],
+                    [G.leaf_of([(b"k", 0, b"base", 50, None, None), (b"z", 0, b"y", 40, None, None)], 1, 4096)],
+                    [G.leaf_of([(b"h", 0, b"new", 30, None, None)], 2, 4096)],
+                    [G.leaf_of([(b"h", 1, b"old-op", 20, None, None)], 1, 4096)]])
+    rngs = [(b"a", INC, b"z", INC)] * 4 + [(b"h", INC, b"h", INC)] * 2
+    bounds = [U64_MAX, 90, 89, 49, U64_MAX, 25]
+    h = host(rt.lsm_scan_device(TG.device_tree(rt, small), rngs, max_seq=bounds))
+    exp = check(small, rngs, bounds, False, h)
+    M = _abi.SDB_MERGE_OPERATOR_MISSING
+    assert [e.status for e in exp] == [M, M, 0, 0, 0, M]
+    assert [r[0] for r in exp[2].rows] == [b"h", b"k", b"z"] and exp[2].rows[1][1] == 1  # the operand is above the bound
+    assert [r[0] for r in exp[4].rows] == [b"h"] and exp[4].rows[0][1] == 2  # the operand is hidden by the newer value
+
+
+@pytest.mark.parametrize("how", ["crc", "block_off"])
+def test_scan_block_errors(rt, how):
+    m = plain(rt)
+    tree, rngs = m["tree"], m["ranges"]
+    i = 6  # the middle SST of the newer sorted run
+    leaf = tree.leaves[i]
+    bad = leaf.sst.nb // 2
+    views = [TG.view_of(l) for l in tree.leaves]
+    if how == "crc":
+        status, block_status = _abi.SDB_CHECKSUM_MISMATCH, {bad: _abi.SDB_CHECKSUM_MISMATCH}
+        data = leaf.sst.data.copy()
+        data[int(leaf.sst.block_off[bad]) + 5] ^= 0x40
+        views[i] = TG.view_of(leaf, data=data)
+    else:  # the block's end cut to 3 bytes: Block::decode cannot hold it, and the next block starts astray
+        status, block_status = _abi.SDB_CORRUPT_BLOCK, {bad: _abi.SDB_CORRUPT_BLOCK, bad + 1: _abi.SDB_CHECKSUM_MISMATCH}
+        off = leaf.sst.block_off.copy()
+        off[bad + 1] = off[bad] + 3
+        views[i] = TG.view_of(leaf, block_off=off)
+    broken = TG.broken(tree, i, block_status)
+    h = host(rt.lsm_scan_device(TG.device_tree(rt, broken, views), rngs))
+    exp = check(broken, rngs, None, False, h)
+    clean = model(tree, rngs, None, False)
+    base = int(tree.block_base[i])
+    hit = [q for q, e in enumerate(clean) if base + bad in e.blocks]
+    rest = [q for q, e in enumerate(clean) if not ({base + b for b in block_status} & e.blocks)]
+    assert len(hit) >= 5 and len(rest) >= 50
+    for q in hit:  # exactly the ranges whose covering blocks hold it fail, with that status
+        assert exp[q].status == status and not exp[q].rows
+    for q in rest:
+        assert exp[q] == clean[q]
+
+
+def test_scan_invalid_version_view(rt):
+    m = plain(rt)
+    tree, rngs = m["tree"], m["ranges"][:200]
+    runs, j = [], 0
+    for r in tree.runs:
+        runs.append([G.Leaf(l.sst, False, None, 3 if j + x == 3 else l.version) for x, l in enumerate(r)])
+        j += len(r)
+    bad = G.Tree(runs)
+    h = host(rt.lsm_scan_device(TG.device_tree(rt, bad), rngs))
+    exp = check(bad, rngs, None, False, h)
+    hit = [e for e in exp if e.status == _abi.SDB_INVALID_VERSION]
+    assert 5 < len(hit) < len(rngs) - 5 and all(3 in e.ssts for e in hit)
+
+
+@pytest.mark.parametrize("what", ["block_base", "block_base_total", "run_start", "range_off"])
+def test_scan_malformed_tree(rt, what):
+    m = plain(rt)
+    rngs = m["ranges"][:100]
+    dev, t, ranges = m["dev"], m["dev"], rngs
+    if what == "block_base":  # disagrees with a view's num_blocks (the sums still end at total_blocks)
+        bb = dev["_block_base"].clone()
+        bb[3] -= 1
+        t = TG.with_arrays(rt, dev, block_base=bb)
+    elif what == "block_base_total":
+        bb = dev["_block_base"].clone()
+        bb[-1] -= 1
+        t = TG.with_arrays(rt, dev, block_base=bb)
+    elif what == "run_start":  # not monotone
+        rs = dev["_run_start"].clone()
+        rs[2], rs[3] = 3, 2
+        t = TG.with_arrays(rt, dev, run_start=rs)
+    else:  # range offsets that descend
+        ranges = {k: TG._dev(a) for k, a in rt.scan_ranges_columnar(rngs).items()}
+        ranges["n"] = len(rngs)
+        ranges["end_off"][40] = ranges["end_off"][41] + 1
+    h = host(rt.lsm_scan_device(t, ranges))
+    n = len(rngs)
+    assert (h["range_status"][:n] == _abi.SDB_INVALID_ARGUMENT).all() and not h["range_entry_start"].any()
+    assert not h["range_ssts"][:n].any()
+    assert h["sum_num_failed_ranges"] == n and h["sum_status"] == _abi.SDB_INVALID_ARGUMENT
+    assert h["sum_blocks_checked"] == 0 and h["sum_num_entries"] == 0 and h["sum_num_candidates"] == 0
+    check(m["tree"], rngs, None, False, host(rt.lsm_scan_device(dev, rngs)))  # the well-formed tree still answers
+
+
+def test_scan_bad_bound_kind(rt):
+    m = plain(rt)
+    tree = m["tree"]
+    rngs = list(m["ranges"][:20])
+    rngs[7] = (rngs[7][0] or b"k", 3, rngs[7][2] or b"l", INC)
+    rngs[9] = (b"k00010", INC, b"k00100", 200)
+    h = host(rt.lsm_scan_device(m["dev"], rngs))
+    exp = check(tree, rngs, None, False, h)
+    assert [q for q, e in enumerate(exp) if e.status] == [7, 9] and exp[7].status == _abi.SDB_INVALID_ARGUMENT
+
+
+def test_scan_degenerate(rt):
+    m = plain(rt)
+    h = host(rt.lsm_scan_device(m["dev"], []))
+    assert not h["summary"].any() and not h["range_entry_start"].any()
+    rngs = [(None, U, None, U), (b"a", INC, b"z", EXC), (b"k00002", INC, b"k00002", INC)]
+    of_empty = G.Tree([[G.Leaf(G.EmptySst())], [G.Leaf(G.EmptySst()), G.Leaf(G.EmptySst())]])
+    for dev in (rt.lsm_tree_device([], []), TG.device_tree(rt, of_empty)):
+        assert dev["total_blocks"] == 0
+        h = host(rt.lsm_scan_device(dev, rngs, max_seq=[5, 6, 7]))
+        assert not h["summary"].any() and not h["range_entry_start"].any()
+        assert not h["range_status"][:3].any() and not h["range_ssts"][:3].any()
+
+
+def raw_call(rt, dev, rngs, cand, cap, ws=None, fill=0xA5):
+    """One sdb_lsm_scan call over outputs pre-filled with `fill` -> (status, dict of device tensors)."""
+    import torch
+    n = len(rngs)
+    rg = {k: TG._dev(a) for k, a in rt.scan_ranges_columnar(rngs).items()}
+    ranges = _abi.ScanRanges(n, rg["start_bytes"].data_ptr(), rg["start_off"].data_ptr(), rg["start_kind"].data_ptr(),
+                             rg["end_bytes"].data_ptr(), rg["end_off"].data_ptr(), rg["end_kind"].data_ptr())
+    full = lambda count, dt: torch.full((max(count, 1),), fill, dtype=torch.uint8, device="cuda").repeat(  # noqa: E731
+        np.dtype(dt).itemsize).view(getattr(torch, dt))
+    res = {"range_entry_start": full(n + 1, "int64"), "range_status": full(n, "int32"), "range_ssts": full(n, "int32"),
+           "key_arena": full(cap[1] + 64, "uint8"), "key_off": full(cap[0] + 1, "int64"), "summary": full(7, "int64")}
+    for f, dt in rt.LSM_SCAN_COLUMNS:
+        res[f] = full(cap[0] + 8, dt)
+    out = _abi.LsmScanOut(res["range_entry_start"].data_ptr(), res["range_status"].data_ptr(), res["range_ssts"].data_ptr(),
+                          res["key_arena"].data_ptr(), cap[1], res["key_off"].data_ptr(),
+                          *[res[f].data_ptr() for f, _ in rt.LSM_SCAN_COLUMNS], cap[0], res["summary"].data_ptr())
+    wsb = rt.lib().sdb_lsm_scan_workspace_bytes(dev["total_blocks"], dev["num_ssts"], dev["num_runs"], n, cand[0], cand[1])
+    if ws is None:
+        ws = torch.empty(wsb, dtype=torch.uint8, device="cuda")
+    assert ws.numel() == wsb
+    st = rt.lib().sdb_lsm_scan(C.byref(dev["lsm"]), C.byref(ranges), None, 0, cand[0], cand[1], C.byref(out),
+                               ws.data_ptr(), wsb, None)
+    res["_keep"] = (rg, ws)
+    return st, res
+
+
+def untouched(h, fields):
+    return all((h[f].view(np.uint8) == 0xA5).all() for f in fields)
+
+
+def test_scan_capacity(rt):
+    m = plain(rt)
+    tree, rngs = m["tree"], m["ranges"][:120]
+    exp = model(tree, rngs, None, False)
+    nc, ckb = sum(e.candidates for e in exp), sum(e.cand_key_bytes for e in exp)
+    ne, kb = sum(len(e.rows) for e in exp), sum(len(r[0]) for e in exp for r in e.rows)
+    assert 0 < ne < nc
+    columns = ["key_arena", "key_off"] + [f for f, _ in rt.LSM_SCAN_COLUMNS]
+    # no staging room: the candidate totals, nothing else
+    st, res = raw_call(rt, m["dev"], rngs, (0, 0), (ne, kb))
+    h = host(res)
+    assert st == 0 and h["sum_status"] == _abi.SDB_LIMIT_EXCEEDED
+    assert (h["sum_num_candidates"], h["sum_candidate_key_bytes"]) == (nc, ckb)
+    assert h["sum_num_entries"] == 0 and h["sum_key_bytes"] == 0 and untouched(h, columns)
+    check_ranges(exp, h)
+    # exact staging, no column room: the true totals and a valid range_entry_start, not one column byte
+    st, res = raw_call(rt, m["dev"], rngs, (nc, ckb), (0, 0))
+    h = host(res)
+    assert st == 0 and h["sum_status"] == _abi.SDB_LIMIT_EXCEEDED
+    assert (h["sum_num_entries"], h["sum_key_bytes"]) == (ne, kb) and untouched(h, columns)
+    starts = np.concatenate([[0], np.cumsum([len(e.rows) for e in exp])])
+    assert (h["range_entry_start"][:len(rngs) + 1] == starts).all()
+    check_ranges(exp, h)
+    for short in ((ne - 1, kb), (ne, kb - 1)):  # one entry / one key byte short
+        st, res = raw_call(rt, m["dev"], rngs, (nc, ckb), short)
+        h = host(res)
+        assert h["sum_status"] == _abi.SDB_LIMIT_EXCEEDED and h["sum_num_entries"] == ne and untouched(h, columns)
+    for short in ((nc - 1, ckb), (nc, ckb - 1)):
+        st, res = raw_call(rt, m["dev"], rngs, short, (ne, kb))
+        h = host(res)
+        assert h["sum_status"] == _abi.SDB_LIMIT_EXCEEDED and h["sum_num_entries"] == 0 and untouched(h, columns)
+    # exact capacities: every row, and nothing past them
+    st, res = raw_call(rt, m["dev"], rngs, (nc, ckb), (ne, kb))
+    h = host(res)
+    assert st == 0
+    check(tree, rngs, None, False, h, exp)
+    assert (h["key_arena"][kb:] == 0xA5).all()
+    for f, _ in rt.LSM_SCAN_COLUMNS:
+        assert (h[f][ne:].view(np.uint8) == 0xA5).all(), f
+
+
+def test_scan_workspace_canary(rt):
+    import torch
+    m = plain(rt)
+    tree, rngs = m["tree"], m["ranges"][:150]
+    exp = model(tree, rngs, None, False)
+    cand = (sum(e.candidates for e in exp), sum(e.cand_key_bytes for e in exp))
+    cap = (sum(len(e.rows) for e in exp), sum(len(r[0]) for e in exp for r in e.rows))
+    dev = m["dev"]
+    wsb = rt.lib().sdb_lsm_scan_workspace_bytes(dev["total_blocks"], dev["num_ssts"], dev["num_runs"], len(rngs), *cand)
+    lead, tail = 257, 512
+    big = torch.full((lead + wsb + tail,), 0xA5, dtype=torch.uint8, device="cuda")
+    st, res = raw_call(rt, dev, rngs, cand, cap, ws=big[lead:lead + wsb])
+    assert st == 0
+    check(tree, rngs, None, False, host(res), exp)
+    assert bool((big[:lead] == 0xA5).all()), "bytes before the workspace changed"
+    assert bool((big[lead + wsb:] == 0xA5).all()), "bytes after the workspace changed"
+
+
+def test_scan_graph_capture_and_workspace_reuse(rt):
+    import torch
+    m = plain(rt)
+    tree, dev, straddler = m["tree"], m["dev"], m["straddler"]
+    rngs, bounds = L.bounds_for(tree, m["ranges"][:120], straddler)
+    n = len(rngs)
+    rngs2, bounds2 = rngs[::-1], [b if b in (0, U64_MAX) else b - 1 for b in bounds[::-1]]
+    exp_free = model(tree, rngs, None, False)
+    cand = (sum(e.candidates for e in exp_free), sum(e.cand_key_bytes for e in exp_free))
+
+    def tensors(rs, bs):
+        d = {k: TG._dev(a) for k, a in rt.scan_ranges_columnar(rs).items()}
+        d["n"] = len(rs)
+        return d, TG._dev(np.array(bs, np.uint64))
+
+    rg, ms = tensors(rngs, bounds)
+    rg2, ms2 = tensors(rngs2, bounds2)
+    assert rg["start_bytes"].numel() == rg2["start_bytes"].numel()
+    ws = torch.empty(rt.lib().sdb_lsm_scan_workspace_bytes(dev["total_blocks"], dev["num_ssts"], dev["num_runs"], n, *cand),
+                     dtype=torch.uint8, device="cuda")
+    kw = dict(workspace=ws, cand=cand, cap=cand)
+    # three calls back to back on one workspace, no reset and no synchronisation between them
+    r1 = rt.lsm_scan_device(dev, rg, max_seq=ms, **kw)
+    r2 = rt.lsm_scan_device(dev, rg2, max_seq=ms2, descending=True, **kw)
+    r3 = rt.lsm_scan_device(dev, rg, **kw)
+    assert r1["_ws"] is ws and r3["_ws"] is ws
+    check(tree, rngs, bounds, False, host(r1))
+    check(tree, rngs2, bounds2, True, host(r2))
+    check(tree, rngs, None, False, host(r3), exp_free)
+    # one captured call, replayed after the range and max_seq tensors are overwritten in place
+    names = [k for k in rg if k != "n"]
+    first = {k: rg[k].clone() for k in names}, ms.clone()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):  # the first launch (function attributes) outside the capture
+        warm = rt.lsm_scan_device(dev, rg, max_seq=ms, stream=s, **kw)
+    s.synchronize()
+    g = torch.cuda.CUDAGraph()
+    holder = {}
+    with torch.cuda.graph(g, stream=s):
+        holder["res"] = rt.lsm_scan_device(dev, rg, max_seq=ms, stream=s, **kw)
+    for rs, bs, (src, srcm) in ((rngs, bounds, first), (rngs2, bounds2, (rg2, ms2)), (rngs, bounds, first)):
+        for k in names:
+            rg[k].copy_(src[k])
+        ms.copy_(srcm)
+        for k, t in holder["res"].items():
+            if not k.startswith("_"):
+                t.zero_()
+        torch.cuda.synchronize()
+        g.replay()
+        check(tree, rs, bs, False, host(holder["res"]))
+    del warm
