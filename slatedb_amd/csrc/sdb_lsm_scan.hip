@@ -14,19 +14,23 @@
 //
 // The unit of work is a (range, SST) pair, p = range * num_ssts + sst, so a range's pairs and its staged
 // candidates are contiguous.  What depends only on a block is computed once per tree block; a pair's candidates
-// are the rows between two ranks in its SST, found by clipping one block at each end.
+// are the rows between two ranks in its SST, found by clipping one block at each end.  The bounds, the block
+// range, the clip of a block and the restored key are those of sdb_range.h, shared with sdb_scan.hip.
 //   k_ls_validate  one workgroup: lsm_validate of sdb_read.h (shared with sdb_lsm_get); resets the control words
 //   k_ls_ranges    thread per range: range offsets that descend make the call malformed
-//   k_ls_locate    thread per pair: participation, the block range, the marks at block_base[sst] + block
+//   k_ls_locate    thread per pair: participation, the block range (covering_blocks), the marks at
+//                  block_base[sst] + block
 //   k_check        wave per marked tree block: bounds + CRC (sdb_lookup.hip, shared)
 //   k_ls_block     thread per tree block: every row parsed (for_each_row) -> status, entries, restored-key bytes
 //   scans          entries / key bytes / failed / read over the tree blocks
-//   k_ls_edge      thread per pair: the lowest failing block, else the ranks [g0, g1) of its candidates
+//   k_ls_edge      thread per pair: the lowest failing block (lowest_failure), else the ranks [g0, g1) of its
+//                  candidates (clip_block)
 //   k_ls_rstat     thread per range: status (lowest SST, then lowest block), range_ssts; a failing range stages
 //                  nothing
 //   scans          candidates / key bytes / work items over the pairs; k_ls_gate: do the candidates fit (and the winner flags zeroed)
-//   k_ls_stage     thread per (pair, block) item: keys restored into the staging arena, seq, flags and the row's
-//                  position, contiguous per pair in physical order (an SST holds key ascending, seq descending)
+//   k_ls_stage     thread per (pair, block) item: keys restored (restore_key) into the staging arena, seq, flags and
+//                  the row's position, contiguous per pair in physical order (an SST holds key ascending, seq
+//                  descending)
 //   k_ls_rank      thread per candidate: merged rank in its range = own index + one binary search per other
 //                  participating SST (the k_mg_rank pattern); the candidate's index goes to that rank, and with it
 //                  the winner flag: visible, and in no SST the last candidate before it is a visible version of
@@ -35,7 +39,7 @@
 //   k_ls_count     thread per range: rule 4, the totals -> scans -> range_entry_start
 //   k_ls_final     summary, capacity check
 //   k_ls_emit      thread per winner: key and columns (the row parsed once more) at its place
-#include "sdb_read.h"
+#include "sdb_range.h"
 #include "sdb_decode.h"
 
 namespace sdb {
@@ -76,21 +80,6 @@ struct LsArgs {
 };
 enum { kCtlFirstBad = 0, kCtlFailed, kCtlBad, kCtlGo1, kCtlGo2, kCtlWords = 8 };
 
-struct Bound {
-    const uint8_t *t;
-    uint32_t n, kind;
-};
-SDB_DEV Bound ls_start(const LsArgs &a, uint64_t r) {
-    return Bound{a.r.start_bytes + a.r.start_off[r], (uint32_t)(a.r.start_off[r + 1] - a.r.start_off[r]), a.r.start_kind[r]};
-}
-SDB_DEV Bound ls_end(const LsArgs &a, uint64_t r) {
-    return Bound{a.r.end_bytes + a.r.end_off[r], (uint32_t)(a.r.end_off[r + 1] - a.r.end_off[r]), a.r.end_kind[r]};
-}
-// BytesRange::contains from sign(key cmp bound)
-SDB_DEV bool ls_precedes(const Bound &s, int c) { return s.kind == SDB_BOUND_INCLUDED ? c < 0 : (s.kind == SDB_BOUND_EXCLUDED && c <= 0); }
-SDB_DEV bool ls_exceeds(const Bound &e, int c) { return e.kind == SDB_BOUND_INCLUDED ? c > 0 : (e.kind == SDB_BOUND_EXCLUDED && c >= 0); }
-SDB_DEV bool ls_bad_kind(const Bound &s, const Bound &e) { return s.kind > SDB_BOUND_EXCLUDED || e.kind > SDB_BOUND_EXCLUDED; }
-
 __global__ __launch_bounds__(256) void k_ls_validate(LsArgs a) {
     const int bad = lsm_validate(a.t, a.sstat);
     if (threadIdx.x == 0) {
@@ -118,46 +107,27 @@ __global__ __launch_bounds__(256) void k_ls_locate(LsArgs a) {
         uint64_t r, p;
         uint32_t i;
         ls_pair(a, t, r, i, p);
-        const Bound s = ls_start(a, r), e = ls_end(a, r);
+        const Bound s = range_start(a.r, r), e = range_end(a.r, r);
         const sdb_sst_view v = a.t.ssts[i];
-        bool part = !ls_bad_kind(s, e) && v.num_blocks > 0;
-        if (part && s.kind && e.kind) {  // empty as a set
-            const int c = cmp_bytes(s.t, s.n, e.t, e.n, 0).c;
-            part = !(c > 0 || (c == 0 && (s.kind == SDB_BOUND_EXCLUDED || e.kind == SDB_BOUND_EXCLUDED)));
-        }
+        bool part = !bad_kind(s, e) && v.num_blocks > 0 && !empty_as_set(s, e);
         if (part && s.kind) {  // the SST's last key precedes the range
             const uint64_t o = a.t.last_key_off[i];
-            part = !ls_precedes(s, cmp_bytes(a.t.last_key_bytes + o, (uint32_t)(a.t.last_key_off[i + 1] - o), s.t, s.n, 0).c);
+            part = !precedes(s, cmp_bytes(a.t.last_key_bytes + o, (uint32_t)(a.t.last_key_off[i + 1] - o), s.t, s.n, 0).c);
         }
         if (part && e.kind) {  // its first key exceeds it
             const uint64_t o = a.t.first_key_off[i];
-            part = !ls_exceeds(e, cmp_bytes(a.t.first_key_bytes + o, (uint32_t)(a.t.first_key_off[i + 1] - o), e.t, e.n, 0).c);
+            part = !exceeds(e, cmp_bytes(a.t.first_key_bytes + o, (uint32_t)(a.t.first_key_off[i + 1] - o), e.t, e.n, 0).c);
         }
-        uint64_t start = 0, end = 0;
-        if (part && !a.sstat[i]) {  // partitions_covering_range, as k_sc_locate
-            end = v.num_blocks;
-            if (s.kind) {
-                const uint64_t lt = partition_point(v, s.t, s.n, false);
-                start = lt > 0 ? lt - 1 : 0;
-            }
-            if (e.kind) {
-                const uint64_t le = partition_point(v, e.t, e.n, true);
-                if (le == 0) {
-                    end = start;
-                } else if (e.kind == SDB_BOUND_INCLUDED) {
-                    end = le;
-                } else {
-                    const uint64_t q = le - 1, f0 = v.index_key_off[q], f1 = v.index_key_off[q + 1];
-                    end = cmp_bytes(v.index_keys + f0, (uint32_t)(f1 - f0), e.t, e.n, 0).c == 0 ? q : q + 1;
-                }
-            }
-            if (end < start) end = start;
+        BlockRange g{0, 0};
+        if (part && !a.sstat[i]) {
+            g = covering_blocks(v, s, e);
+            if (g.end < g.start) g.end = g.start;
             const uint64_t base = a.t.block_base[i];
-            for (uint64_t b = start; b < end; b++) a.mark[base + b] = 1;
+            for (uint64_t b = g.start; b < g.end; b++) a.mark[base + b] = 1;
         }
         a.part[p] = part;
-        a.bs[p] = (uint32_t)start;
-        a.be[p] = (uint32_t)end;
+        a.bs[p] = (uint32_t)g.start;
+        a.be[p] = (uint32_t)g.end;
     }
 }
 
@@ -185,31 +155,11 @@ __global__ __launch_bounds__(64) void k_ls_block(LsArgs a) {
     a.rd[k] = st != -1;
 }
 
-// In checked block k of v: the first row that does not precede bd (a start bound), or that exceeds it (an end
-// bound), by the incremental comparators; kbb = the key bytes of the rows before it.  None: the block's count.
-SDB_DEV void ls_find(const sdb_sst_view &v, uint64_t k, const Bound &bd, bool is_end, uint32_t &row, uint64_t &kbb) {
-    row = 0;
-    kbb = 0;
+// clip_block of checked block k of v.
+SDB_DEV Clip ls_clip(const sdb_sst_view &v, uint64_t k, const Bound &s, const Bound &e) {
     Blk b;
-    if (blk_open(v, k, b)) return;
-    const bool v2 = v.sst_version == 2;
-    bool found = false;
-    uint32_t n = 0;
-    uint64_t kb = 0;
-    Cmp c{0, 0, 0};
-    for_each_row(v.sst_version, b, [&](uint32_t x, uint32_t, const Row &r) {
-        if (found) return;
-        if (v2) c = x == 0 ? cmp_bytes(b.d + r.suf, r.un, bd.t, bd.n, 0) : cmp_next(c, r.sh, b.d + r.suf, r.un, bd.t, bd.n);
-        else if (v1_cmp(b, x, bd.t, bd.n, c)) found = true;
-        if (found || (is_end ? ls_exceeds(bd, c.c) : !ls_precedes(bd, c.c))) {
-            found = true;
-            return;
-        }
-        n = x + 1;
-        kb += r.sh + r.un;
-    });
-    row = n;
-    kbb = kb;
+    if (blk_open(v, k, b)) return Clip{0, 0, 0, 0};
+    return clip_block(v.sst_version, b, s, e);
 }
 
 __global__ __launch_bounds__(64) void k_ls_edge(LsArgs a) {
@@ -224,22 +174,12 @@ __global__ __launch_bounds__(64) void k_ls_edge(LsArgs a) {
         const bool part = !bad && a.part[p];
         if (part && !(st = a.sstat[i]) && a.be[p] > a.bs[p]) {
             const uint64_t base = a.t.block_base[i], bs = a.bs[p], be = a.be[p];
-            if (a.pb[base + be] != a.pb[base + bs]) {  // the lowest failing block of [bs, be)
-                uint64_t x = bs, y = be - 1;
-                while (x < y) {
-                    const uint64_t m = x + (y - x) / 2;
-                    if (a.pb[base + m + 1] > a.pb[base + bs]) y = m;
-                    else x = m + 1;
-                }
-                st = a.bstat[base + x];
-            } else {
+            if (!(st = lowest_failure(a.pb, a.bstat, base, bs, be))) {
                 // The rows of [bs, be) that the range contains lie between two ranks.  Interior blocks hold only keys
                 // of the range, except where a bound's key fills whole blocks (a long run of versions under an
                 // excluded bound): the walks move inwards past blocks that keep nothing.
                 const sdb_sst_view v = a.t.ssts[i];
-                const Bound s = ls_start(a, r), e = ls_end(a, r);
-                uint32_t row;
-                uint64_t kbb;
+                const Bound s = range_start(a.r, r), e = range_end(a.r, r), open{nullptr, 0, 0};
                 g0 = a.pc[base + be];
                 k0 = a.pk[base + be];
                 fb = (uint32_t)be;
@@ -249,10 +189,10 @@ __global__ __launch_bounds__(64) void k_ls_edge(LsArgs a) {
                     fb = (uint32_t)bs;
                 }
                 for (uint64_t k = bs; s.kind && k < be; k++) {
-                    ls_find(v, k, s, false, row, kbb);
-                    if (row < a.cnt[base + k]) {
-                        g0 = a.pc[base + k] + row;
-                        k0 = a.pk[base + k] + kbb;
+                    const Clip c = ls_clip(v, k, s, open);
+                    if (c.lo < a.cnt[base + k]) {
+                        g0 = a.pc[base + k] + c.lo;
+                        k0 = a.pk[base + k] + c.kb_before;
                         fb = (uint32_t)k;
                         break;
                     }
@@ -260,10 +200,10 @@ __global__ __launch_bounds__(64) void k_ls_edge(LsArgs a) {
                 g1 = a.pc[e.kind ? base + bs : base + be];
                 k1 = a.pk[e.kind ? base + bs : base + be];
                 for (uint64_t k = be; e.kind && k-- > bs;) {
-                    ls_find(v, k, e, true, row, kbb);
-                    if (row > 0) {
-                        g1 = a.pc[base + k] + row;
-                        k1 = a.pk[base + k] + kbb;
+                    const Clip c = ls_clip(v, k, open, e);
+                    if (c.hi > 0) {
+                        g1 = a.pc[base + k] + c.hi;
+                        k1 = a.pk[base + k] + c.kb;
                         break;
                     }
                 }
@@ -301,7 +241,7 @@ __global__ __launch_bounds__(64) void k_ls_rstat(LsArgs a) {
     uint32_t ns = 0;
     if (a.ctl[kCtlBad]) {
         st = SDB_INVALID_ARGUMENT;
-    } else if (ls_bad_kind(ls_start(a, r), ls_end(a, r))) {
+    } else if (bad_kind(range_start(a.r, r), range_end(a.r, r))) {
         st = SDB_INVALID_ARGUMENT;
     } else {
         for (uint32_t i = 0; i < S; i++) {
@@ -324,26 +264,12 @@ __global__ __launch_bounds__(256) void k_ls_gate(LsArgs a) {
     for (uint64_t m = t0; m < a.cand_entries; m += (uint64_t)gridDim.x * blockDim.x) a.wn[m] = a.wkb[m] = 0;
 }
 
-SDB_DEV void ls_copy(uint8_t *dst, const uint8_t *src, uint32_t n) {
-    for (uint32_t j = 0; j < n; j++) dst[j] = src[j];
-}
-// The last x in [0, n) with s[x * stride] <= v (s ascends, s[0] <= v).
-SDB_DEV uint64_t ls_last_le(const uint64_t *s, uint64_t n, uint64_t stride, uint64_t v) {
-    uint64_t x = 0, y = n;
-    while (y - x > 1) {
-        const uint64_t m = x + (y - x) / 2;
-        if (s[m * stride] <= v) x = m;
-        else y = m;
-    }
-    return x;
-}
-
 __global__ __launch_bounds__(64) void k_ls_stage(LsArgs a) {
     if (!a.ctl[kCtlGo1]) return;
     const uint32_t S = a.t.num_ssts;
     const uint64_t total = a.pis[a.pairs];
     for (uint64_t it = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; it < total; it += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t p = ls_last_le(a.pis, a.pairs, 1, it);
+        const uint64_t p = last_le(a.pis, a.pairs, 1, it);
         const uint32_t i = (uint32_t)(p % S);
         const sdb_sst_view v = a.t.ssts[i];
         const uint64_t kl = a.fb[p] + (it - a.pis[p]), K = a.t.block_base[i] + kl;  // the block: in the SST, in the tree
@@ -365,20 +291,7 @@ __global__ __launch_bounds__(64) void k_ls_stage(LsArgs a) {
             const uint64_t c = cbase + (c0 + x - g0), ko = kbase + (a.pk[K] + kbx - a.k0[p]);
             if (c >= cend || ko > kend || L > kend - ko) return;  // never out of the pair's slots
             uint8_t *dst = a.ckeys + ko;
-            if (!v2) {
-                ls_copy(dst, b.d + 4, r.sh);
-            } else if (prev) {
-                ls_copy(dst, prev, r.sh);
-            } else if (r.sh) {  // chain from the block's first row: row y sets key[y.sh, y.sh + y.un)
-                uint32_t rp = 0;
-                for (uint32_t y = 0; y < x; y++) {
-                    Row q;
-                    if (v2_row(b, rp, q)) break;
-                    for (uint32_t j = q.sh; j < q.sh + q.un && j < r.sh; j++) dst[j] = b.d[q.suf + j - q.sh];
-                    rp = q.next;
-                }
-            }
-            ls_copy(dst + r.sh, b.d + r.suf, r.un);
+            restore_key(v2, b, x, r, prev, dst);
             prev = dst;
             a.ckoff[c] = ko;
             a.cklen[c] = L;
@@ -404,7 +317,7 @@ __global__ __launch_bounds__(64) void k_ls_rank(LsArgs a) {
     const uint32_t S = a.t.num_ssts;
     const uint64_t total = a.cs[a.pairs];
     for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < total; c += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t p = ls_last_le(a.cs, a.pairs, 1, c), r = p / S;
+        const uint64_t p = last_le(a.cs, a.pairs, 1, c), r = p / S;
         const uint32_t i = (uint32_t)(p % S);
         const uint8_t *t = a.ckeys + a.ckoff[c];
         const uint32_t nt = a.cklen[c];
@@ -487,7 +400,7 @@ __global__ __launch_bounds__(64) void k_ls_emit(LsArgs a) {
     const uint64_t total = a.cs[a.pairs];
     for (uint64_t m = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; m < total; m += (uint64_t)gridDim.x * blockDim.x) {
         if (!a.wn[m]) continue;
-        const uint64_t r = ls_last_le(a.cs, a.r.n, S, m);
+        const uint64_t r = last_le(a.cs, a.r.n, S, m);
         if (a.out.range_status[r]) continue;
         const uint64_t rs = a.cs[r * S], c = a.morder[m];
         const uint64_t E0 = a.out.range_entry_start[r], N = a.rn[r], K0 = a.rks[r], KB = a.rkb[r];
@@ -495,13 +408,13 @@ __global__ __launch_bounds__(64) void k_ls_emit(LsArgs a) {
         const uint32_t L = a.cklen[c];
         if (x >= N || kx > KB || L > KB - kx) continue;
         const uint64_t di = a.desc ? N - 1 - x : x, dk = a.desc ? KB - kx - L : kx;
-        const uint32_t i = (uint32_t)(ls_last_le(a.cs, a.pairs, 1, c) % S);
+        const uint32_t i = (uint32_t)(last_le(a.cs, a.pairs, 1, c) % S);
         const sdb_sst_view v = a.t.ssts[i];
         Blk b;
         Row row;
         if (blk_open(v, a.cblk[c], b)) continue;
         if (v.sst_version == 2 ? v2_row(b, a.cat[c], row) : v1_row(b, a.cat[c], row)) continue;
-        ls_copy(a.out.key_arena + K0 + dk, a.ckeys + a.ckoff[c], L);
+        copy_bytes(a.out.key_arena + K0 + dk, a.ckeys + a.ckoff[c], L);
         a.out.key_off[E0 + di] = K0 + dk;
         a.out.sst[E0 + di] = i;
         put_row(a.out, E0 + di, b.base, row);
@@ -576,12 +489,6 @@ uint64_t lsm_scan_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint
     return lsm_scan_bind(a, nullptr);
 }
 
-static uint32_t ls_grid(uint64_t items, uint32_t threads) {  // the kernels stride past this cap
-    uint64_t g = (items + threads - 1) / threads;
-    if (g < 1) g = 1;
-    return (uint32_t)(g > 32768 ? 32768 : g);
-}
-
 hipError_t launch_lsm_scan(const sdb_lsm_view &t, const sdb_scan_ranges &r, const uint64_t *max_seq, uint32_t desc,
                            uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out &out, uint8_t *w,
                            hipStream_t st) {
@@ -609,24 +516,24 @@ hipError_t launch_lsm_scan(const sdb_lsm_view &t, const sdb_scan_ranges &r, cons
     const uint32_t rw = (uint32_t)((n + 63) / 64);
     hipLaunchKernelGGL(k_ls_validate, dim3(1), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_ls_ranges, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_ls_locate, dim3(ls_grid(P, 256)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_ls_locate, dim3(scan_grid(P, 256)), dim3(256), 0, st, a);
     if ((e = launch_check(CheckArgs{{}, t, (const uint32_t *)(a.ctl + kCtlBad), tb, a.mark, a.bstat}, st)) != hipSuccess) return e;
     // the per-block, per-pair and per-item walks are latency-bound threads: one wave per workgroup spreads them over the CUs
     hipLaunchKernelGGL(k_ls_block, dim3((uint32_t)((tb + 63) / 64)), dim3(64), 0, st, a);
     if ((e = launch_excl_scan2(a.cnt, a.kb, tb, a.tx, a.ty, a.pc, a.pk, st)) != hipSuccess) return e;
     if ((e = launch_excl_scan2(a.bbad, a.rd, tb, a.tx, a.ty, a.pb, a.pr, st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_ls_edge, dim3(ls_grid(P, 64)), dim3(64), 0, st, a);
+    hipLaunchKernelGGL(k_ls_edge, dim3(scan_grid(P, 64)), dim3(64), 0, st, a);
     hipLaunchKernelGGL(k_ls_rstat, dim3(rw), dim3(64), 0, st, a);
     if ((e = launch_excl_scan2(a.pit, a.pit, P, a.tx, a.ty, a.pis, a.cs, st)) != hipSuccess) return e;
     if ((e = launch_excl_scan2(a.pn, a.pkb, P, a.tx, a.ty, a.cs, a.cks, st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_ls_gate, dim3(ls_grid(ce, 256)), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_ls_stage, dim3(ls_grid(ce + P, 64)), dim3(64), 0, st, a);
-    hipLaunchKernelGGL(k_ls_rank, dim3(ls_grid(ce, 64)), dim3(64), 0, st, a);
+    hipLaunchKernelGGL(k_ls_gate, dim3(scan_grid(ce, 256)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_ls_stage, dim3(scan_grid(ce + P, 64)), dim3(64), 0, st, a);
+    hipLaunchKernelGGL(k_ls_rank, dim3(scan_grid(ce, 64)), dim3(64), 0, st, a);
     if ((e = launch_excl_scan2(a.wn, a.wkb, ce, a.tx, a.ty, a.wpos, a.wkpos, st)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_ls_count, dim3(rw), dim3(64), 0, st, a);
     if ((e = launch_excl_scan2(a.rn, a.rkb, n, a.tx, a.ty, out.range_entry_start, a.rks, st)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_ls_final, dim3(1), dim3(64), 0, st, a);
-    hipLaunchKernelGGL(k_ls_emit, dim3(ls_grid(ce, 64)), dim3(64), 0, st, a);
+    hipLaunchKernelGGL(k_ls_emit, dim3(scan_grid(ce, 64)), dim3(64), 0, st, a);
     return hipGetLastError();
 }
 

@@ -3,7 +3,8 @@
 // comparators, Block::decode of a checked block, the entry-header and row parsers, the seeks, the row walker and
 // the row -> column writer, the index partition_point, the bounds + CRC pass over marked blocks and the
 // consistency check of a tree's index arrays.  Everything takes what it reads (an
-// sdb_sst_view, a Blk), never a kernel's argument struct.
+// sdb_sst_view, a Blk), never a kernel's argument struct.  What reads a key range (the bounds, the covering block
+// range, the lowest failing block, the clip of a block, the restored key) is in sdb_range.h, on top of this header, for the two scans.
 #pragma once
 #include "sdb_bloom.h"
 #include "sdb_crc.h"

@@ -10,24 +10,25 @@
 //
 // What depends only on the block is computed once per block and shared by every range that touches it;
 // what depends on the range is two clipped blocks (its first and its last).  No per-(range, block) state is
-// stored, so the workspace is O(blocks + ranges) however much the ranges overlap:
-//   k_sc_locate  thread per range: block range (partition_point of sdb_read.h), empty-set test
+// stored, so the workspace is O(blocks + ranges) however much the ranges overlap.  The bounds, the block range,
+// the clip of a block and the restored key are those of sdb_range.h, shared with sdb_lsm_scan.hip:
+//   k_sc_locate  thread per range: block range (covering_blocks), empty-set test
 //   k_sc_mark    workgroup per range: marks the blocks it reads
 //   k_check      wave per marked block: bounds + CRC (sdb_lookup.hip, shared)
 //   k_sc_block   thread per read block: every row parsed (for_each_row of sdb_read.h: the status), entries,
 //                restored-key bytes, the runs of equal keys at its head and tail, and whether its last key
 //                equals the next block's first
 //   scans        entries / key bytes / failed / read over blocks
-//   k_sc_edge    thread per range: status (first failing block), the clips [lo, hi) of its first and last
-//                block by the incremental comparators (keys are not materialised), totals
+//   k_sc_edge    thread per range: status (lowest_failure), the clips [lo, hi) of its first and last block
+//                (clip_block: the incremental comparators, keys are not materialised), totals
 //   scans        entries / key bytes / items / failed over ranges -> range_entry_start
 //   k_sc_final   summary, capacity check
-//   k_sc_emit    thread per work item (range, block), found by binary search in the item scan: restores
-//                keys by chaining (V2) or from the block's first key (V1) and writes rows [lo, hi).
+//   k_sc_emit    thread per work item (range, block), found by binary search in the item scan (last_le):
+//                restores keys (restore_key) and writes rows [lo, hi).
 //                Descending: entry p of the range's N, in the key group [gs, ge), lands at
 //                N - ge + (p - gs); a group's extent past the item's block comes from the per-block
 //                head / tail runs and joins, never from a pass over the output.
-#include "sdb_read.h"
+#include "sdb_range.h"
 #include "sdb_decode.h"
 
 namespace sdb {
@@ -64,54 +65,19 @@ SDB_DEV int sc_open(const ScanArgs &a, uint64_t k, Blk &b) {
     return 0;
 }
 
-struct Bound {
-    const uint8_t *t;
-    uint32_t n, kind;
-};
-SDB_DEV Bound start_of(const ScanArgs &a, uint64_t r) {
-    return Bound{a.r.start_bytes + a.r.start_off[r], (uint32_t)(a.r.start_off[r + 1] - a.r.start_off[r]), a.r.start_kind[r]};
-}
-SDB_DEV Bound end_of(const ScanArgs &a, uint64_t r) {
-    return Bound{a.r.end_bytes + a.r.end_off[r], (uint32_t)(a.r.end_off[r + 1] - a.r.end_off[r]), a.r.end_kind[r]};
-}
-// key_precedes / key_exceeds (sst_iter.rs:104-120) from sign(key cmp bound)
-SDB_DEV bool precedes(const Bound &s, int c) { return s.kind == SDB_BOUND_INCLUDED ? c < 0 : (s.kind == SDB_BOUND_EXCLUDED && c <= 0); }
-SDB_DEV bool exceeds(const Bound &e, int c) { return e.kind == SDB_BOUND_INCLUDED ? c > 0 : (e.kind == SDB_BOUND_EXCLUDED && c >= 0); }
-
 __global__ __launch_bounds__(256) void k_sc_locate(ScanArgs a) {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= a.r.n) return;
-    const Bound s = start_of(a, r), e = end_of(a, r);
-    const uint64_t nb = a.v.num_blocks;
-    uint64_t start = 0, end = nb;
-    if (s.kind > SDB_BOUND_EXCLUDED || e.kind > SDB_BOUND_EXCLUDED) {  // reported by k_sc_edge
+    const Bound s = range_start(a.r, r), e = range_end(a.r, r);
+    if (bad_kind(s, e)) {  // reported by k_sc_edge
         a.out.range_block[2 * r] = a.out.range_block[2 * r + 1] = 0;
         a.rempty[r] = 2;
         return;
     }
-    if (s.kind) {  // first_partition_including_or_after_key (partitioned_keyspace.rs:43-68)
-        const uint64_t lt = partition_point(a.v, s.t, s.n, false);
-        start = lt > 0 ? lt - 1 : 0;
-    }
-    if (e.kind) {  // last_partition_including_key (:72-83), then :98-106
-        const uint64_t le = partition_point(a.v, e.t, e.n, true);
-        if (le == 0) {
-            end = start;
-        } else if (e.kind == SDB_BOUND_INCLUDED) {
-            end = le;
-        } else {
-            const uint64_t p = le - 1, f0 = a.v.index_key_off[p], f1 = a.v.index_key_off[p + 1];
-            end = cmp_bytes(a.v.index_keys + f0, (uint32_t)(f1 - f0), e.t, e.n, 0).c == 0 ? p : p + 1;
-        }
-    }
-    bool empty = false;
-    if (s.kind && e.kind) {
-        const int c = cmp_bytes(s.t, s.n, e.t, e.n, 0).c;
-        empty = c > 0 || (c == 0 && (s.kind == SDB_BOUND_EXCLUDED || e.kind == SDB_BOUND_EXCLUDED));
-    }
-    a.out.range_block[2 * r] = (uint32_t)start;
-    a.out.range_block[2 * r + 1] = (uint32_t)end;
-    a.rempty[r] = empty ? 1 : 0;
+    const BlockRange g = covering_blocks(a.v, s, e);
+    a.out.range_block[2 * r] = (uint32_t)g.start;
+    a.out.range_block[2 * r + 1] = (uint32_t)g.end;
+    a.rempty[r] = empty_as_set(s, e) ? 1 : 0;
 }
 
 __global__ __launch_bounds__(256) void k_sc_mark(ScanArgs a) {
@@ -125,9 +91,6 @@ __global__ __launch_bounds__(256) void k_sc_mark(ScanArgs a) {
 // Row i of an open block: V2 at byte `pos` (the walk's cursor), V1 by its offset.
 SDB_DEV int sc_row(const ScanArgs &a, const Blk &b, uint32_t i, uint32_t pos, Row &r) {
     return a.v.sst_version == 2 ? v2_row(b, pos, r) : v1_row(b, i, r);
-}
-SDB_DEV bool sc_more(const ScanArgs &a, const Blk &b, uint32_t i, uint32_t pos) {
-    return a.v.sst_version == 2 ? pos < b.data_end : i < b.count;
 }
 // V1: row x has the key of row p; a key is first_key[..sh] ++ suffix (row 0 holds the first key as its suffix).
 SDB_DEV bool sc_same(const ScanArgs &a, const Blk &b, const Row &x, const Row &p, uint32_t L) {
@@ -265,44 +228,12 @@ __global__ __launch_bounds__(256) void k_sc_block(ScanArgs a) {
     a.join[k] = join && st == 0;
 }
 
-// Rows [lo, hi) of block k that a range keeps: lo = the first row that does not precede s, hi = the first
-// row from lo on that exceeds e; kb = their restored-key bytes.  s.kind / e.kind 0: that side is open.
-SDB_DEV void sc_clip(const ScanArgs &a, uint64_t k, const Bound &s, const Bound &e, uint32_t &lo, uint32_t &hi, uint64_t &kb) {
-    lo = hi = 0;
-    kb = 0;
-    if (!s.kind && !e.kind) {  // nothing to clip: the block pass walked the same rows
-        hi = (uint32_t)a.cnt[k];
-        kb = a.kb[k];
-        return;
-    }
+// clip_block of block k.  With both sides open there is nothing to clip: the block pass walked the same rows.
+SDB_DEV Clip sc_clip(const ScanArgs &a, uint64_t k, const Bound &s, const Bound &e) {
+    if (!s.kind && !e.kind) return Clip{0, (uint32_t)a.cnt[k], 0, a.kb[k]};
     Blk b;
-    if (sc_open(a, k, b)) return;
-    uint32_t i = 0, pos = 0;
-    bool in = false;
-    Cmp cs{0, 0, 0}, ce{0, 0, 0};
-    while (sc_more(a, b, i, pos)) {
-        Row r;
-        if (sc_row(a, b, i, pos, r)) break;
-        if (a.v.sst_version == 2) {
-            if (s.kind) cs = i == 0 ? cmp_bytes(b.d + r.suf, r.un, s.t, s.n, 0) : cmp_next(cs, r.sh, b.d + r.suf, r.un, s.t, s.n);
-            if (e.kind) ce = i == 0 ? cmp_bytes(b.d + r.suf, r.un, e.t, e.n, 0) : cmp_next(ce, r.sh, b.d + r.suf, r.un, e.t, e.n);
-        } else {
-            if (s.kind && v1_cmp(b, i, s.t, s.n, cs)) break;
-            if (e.kind && v1_cmp(b, i, e.t, e.n, ce)) break;
-        }
-        if (!in && !precedes(s, cs.c)) {
-            in = true;
-            lo = i;
-        }
-        if (in) {
-            if (exceeds(e, ce.c)) break;
-            kb += r.sh + r.un;
-        }
-        i++;
-        pos = r.next;
-    }
-    hi = i;
-    if (!in) lo = hi;
+    if (sc_open(a, k, b)) return Clip{0, 0, 0, 0};
+    return clip_block(a.v.sst_version, b, s, e);
 }
 
 __global__ __launch_bounds__(256) void k_sc_edge(ScanArgs a) {
@@ -313,40 +244,31 @@ __global__ __launch_bounds__(256) void k_sc_edge(ScanArgs a) {
     int st = a.rempty[r] == 2 ? SDB_INVALID_ARGUMENT : 0;
     uint64_t n = 0, kb = 0, nf = 0, kbf = 0, nl = 0, kbl = 0;
     uint32_t lo = 0;
-    if (items && a.pb[end] != a.pb[start]) {  // the lowest failing block of [start, end)
-        uint64_t x = start, y = end - 1;
-        while (x < y) {
-            const uint64_t m = x + (y - x) / 2;
-            if (a.pb[m + 1] > a.pb[start]) y = m;
-            else x = m + 1;
-        }
-        st = a.bstat[x];
-    } else if (items) {
+    if (items && !(st = lowest_failure(a.pb, a.bstat, 0, start, end))) {
         // Interior blocks hold only keys of the range, except where a bound's key fills whole blocks (a
         // long run of versions under an excluded bound): the first and last block move inwards past
         // blocks that keep nothing, so [fb, lb] starts and ends with a kept row.
-        const Bound s = start_of(a, r), e = end_of(a, r), open{nullptr, 0, 0};
-        uint32_t hi = 0, l2, h2;
+        const Bound s = range_start(a.r, r), e = range_end(a.r, r), open{nullptr, 0, 0};
+        Clip f, l{0, 0, 0, 0};
         fb = start;
         lb = end - 1;
         for (;; fb++) {
-            sc_clip(a, fb, s, fb == lb ? e : open, lo, hi, kbf);
-            if (hi > lo || fb == lb) break;
+            f = sc_clip(a, fb, s, fb == lb ? e : open);
+            if (f.hi > f.lo || fb == lb) break;
         }
         for (; lb > fb; lb--) {
-            sc_clip(a, lb, open, e, l2, h2, kbl);
-            if (h2 > 0) break;
+            l = sc_clip(a, lb, open, e);
+            if (l.hi > 0) break;
         }
-        if (lb == fb && fb != end - 1) sc_clip(a, fb, s, e, lo, hi, kbf);  // the last block came down to the first
-        nf = hi - lo;
-        n = nf;
-        kb = kbf;
+        if (lb == fb && fb != end - 1) f = sc_clip(a, fb, s, e);  // the last block came down to the first
+        lo = f.lo;
+        n = nf = f.hi - f.lo;
+        kb = kbf = f.kb;
         if (lb > fb) {
-            nl = h2;
+            nl = l.hi;
+            kbl = l.kb;
             n += nl + (a.pc[lb] - a.pc[fb + 1]);
             kb += kbl + (a.pk[lb] - a.pk[fb + 1]);
-        } else {
-            kbl = 0;
         }
         items = n ? lb - fb + 1 : 0;
     }
@@ -388,24 +310,11 @@ __global__ void k_sc_final(ScanArgs a) {
     *a.go = fits ? 1u : 0u;
 }
 
-SDB_DEV void sc_copy(uint8_t *dst, const uint8_t *src, uint32_t n) {  // dst after src when they overlap: never
-    typedef uint64_t u64u __attribute__((aligned(1)));
-    uint32_t j = 0;
-    for (; j + 8 <= n; j += 8) *(u64u *)(dst + j) = *(const u64u *)(src + j);
-    for (; j < n; j++) dst[j] = src[j];
-}
-
 __global__ __launch_bounds__(256) void k_sc_emit(ScanArgs a) {
     if (!*a.go) return;
     const uint64_t nr = a.r.n, total = a.ris[nr];
     for (uint64_t it = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; it < total; it += (uint64_t)gridDim.x * blockDim.x) {
-        uint64_t x = 0, y = nr;  // the last range r with ris[r] <= it
-        while (y - x > 1) {
-            const uint64_t m = x + (y - x) / 2;
-            if (a.ris[m] <= it) x = m;
-            else y = m;
-        }
-        const uint64_t r = x, start = a.efb[r], end = (uint64_t)a.elb[r] + 1;  // the blocks that keep rows
+        const uint64_t r = last_le(a.ris, nr, 1, it), start = a.efb[r], end = (uint64_t)a.elb[r] + 1;  // the blocks that keep rows
         const uint64_t k = start + (it - a.ris[r]);
         const uint64_t E0 = a.out.range_entry_start[r], N = a.out.range_entry_start[r + 1] - E0;
         const uint64_t K0 = a.rks[r], KB = a.rks[r + 1] - K0;
@@ -477,22 +386,9 @@ __global__ __launch_bounds__(256) void k_sc_emit(ScanArgs a) {
                 if (di >= N || dk > KB || L > KB - dk) continue;  // rows that are not sorted: never out of the range's slots
                 uint8_t *dst = a.out.key_arena + K0 + dk;
                 if (leadkey) {
-                    sc_copy(dst, leadkey, L);
+                    copy_bytes(dst, leadkey, L);
                 } else {
-                    if (!v2) {
-                        sc_copy(dst, b.d + 4, lead.sh);
-                    } else if (prevkey) {
-                        sc_copy(dst, prevkey, lead.sh);
-                    } else if (lead.sh) {  // chain from the block's first row: row x sets key[x.sh, x.sh + x.un)
-                        uint32_t rp = 0;
-                        for (uint32_t x = 0; x < i; x++) {
-                            Row q2;
-                            if (v2_row(b, rp, q2)) break;
-                            for (uint32_t j = q2.sh; j < q2.sh + q2.un && j < lead.sh; j++) dst[j] = b.d[q2.suf + j - q2.sh];
-                            rp = q2.next;
-                        }
-                    }
-                    sc_copy(dst + lead.sh, b.d + lead.suf, lead.un);
+                    restore_key(v2, b, i, lead, prevkey, dst);
                     leadkey = dst;
                 }
                 a.out.key_off[E0 + di] = K0 + dk;
@@ -585,9 +481,8 @@ hipError_t launch_scan(const sdb_sst_view &v, const sdb_scan_ranges &r, uint32_t
     if ((e = launch_excl_scan2(a.rn, a.rkb, n, a.tx, a.ty, out.range_entry_start, a.rks, st)) != hipSuccess) return e;
     if ((e = launch_excl_scan2(a.ritems, a.rfail, n, a.tx, a.ty, a.ris, a.rfs, st)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_sc_final, dim3(1), dim3(64), 0, st, a);
-    uint64_t items = n * nb, eg = (items + 63) / 64;  // upper bound of the work items; the kernel strides
-    if (n > (1ull << 40) / nb || eg > 32768) eg = 32768;
-    hipLaunchKernelGGL(k_sc_emit, dim3((uint32_t)eg), dim3(64), 0, st, a);
+    const uint32_t eg = n > (1ull << 40) / nb ? 32768 : scan_grid(n * nb, 64);  // n * nb: upper bound of the work items
+    hipLaunchKernelGGL(k_sc_emit, dim3(eg), dim3(64), 0, st, a);
     return hipGetLastError();
 }
 

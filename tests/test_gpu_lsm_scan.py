@@ -2,7 +2,7 @@
 tests/lsm_scan_cases.py, every column of every row and the summary: a mixed tree (L0 + sorted runs, V1 and V2, an
 SST without blocks, a key straddling two SSTs of a run), both orders, snapshot bounds, the reference's own table,
 merge operands, block errors, a malformed tree, degenerate inputs, capacities, a workspace canary, workspace reuse
-and HIP graph capture."""
+and HIP graph capture; and, on a one-SST tree of unique keys, row for row against sdb_sst_scan."""
 import ctypes as C
 
 import numpy as np
@@ -417,3 +417,71 @@ def test_scan_graph_capture_and_workspace_reuse(rt):
         g.replay()
         check(tree, rs, bs, False, host(holder["res"]))
     del warm
+
+
+def _unique_leaf(version):
+    """About 200 unique keys, values only (some empty, some with timestamps), block size 256: with no bound on seq
+    every row wins, so a one-SST tree scans as its SST does."""
+    rng = np.random.default_rng(5)
+    es = [(b"k%05d" % k + (b"x" * int(rng.integers(1, 30)) if k % 25 == 0 else b""), 0,
+           bytes(rng.integers(0, 256, int(rng.integers(0, 30)), dtype=np.uint8)), 10**6 - k,
+           int(rng.integers(0, 2**40)) if rng.random() < 0.2 else None,
+           int(rng.integers(0, 2**40)) if rng.random() < 0.2 else None) for k in range(0, 400, 2)]
+    return G.leaf_of(es, version, 256)
+
+
+def _shared_ranges(sst):
+    """range_list's hand-made ranges (its random ones left out) and, per pair of bound kinds, the cases where the
+    two scans' bound handling could part: both bounds on a block's first key, an empty set, start after end."""
+    from .scan_cases import range_list
+    keys = sst.keys
+    mid, late = keys[len(keys) // 3], keys[2 * len(keys) // 3]
+    out = range_list(sst, seed=7)[:56]
+    assert out[0] == (None, U, None, U)  # the fully unbounded range
+    for sk in (INC, EXC):
+        for ek in (INC, EXC):
+            for k in {sst.index_keys[b] for b in (1, sst.nb // 2, sst.nb - 1)} | {keys[sst.bes[sst.nb // 2]]}:
+                out.append((k, sk, k, ek))
+            out.append((mid, sk, mid, ek))  # empty as a set unless both sides are included
+            out.append((late, sk, mid, ek))  # the start sorts after the end
+            out.append((sst.index_keys[2], sk, sst.index_keys[sst.nb - 2], ek))
+    return out
+
+
+@pytest.mark.parametrize("version", [2, 1])
+def test_lsm_scan_matches_sst_scan(rt, version):
+    """Where their contracts coincide (one SST, unique keys, values only, no bound on seq) sdb_lsm_scan and
+    sdb_sst_scan answer alike, row for row: they read ranges through the same code (sdb_range.h)."""
+    import torch
+    leaf = _unique_leaf(version)
+    sst, tree = leaf.sst, G.Tree([[leaf]])
+    assert sst.nb >= 8 and len(set(sst.keys)) == len(sst.keys) >= 190
+    rngs = _shared_ranges(sst)
+    view = TG.view_of(leaf)
+    dev = TG.device_tree(rt, tree)
+    asc = None
+    for desc in (False, True):
+        # the two models agree, so a difference below lies in the kernels
+        want = [[sst.rows[i] for i in sst.expect_idx(r, desc)[1].tolist()] for r in rngs]
+        mod = model(tree, rngs, None, desc)
+        assert [[sst.rows[x] for _, _, x in e.rows] for e in mod] == want and not any(e.status for e in mod)
+        one = rt.sst_scan_device(view, rngs, descending=desc)
+        many = rt.lsm_scan_device(dev, rngs, descending=desc)
+        torch.cuda.synchronize()
+        s = {k: v.cpu().numpy() for k, v in one.items() if not k.startswith("_")}
+        h = host(many)
+        n, N, KB = len(rngs), int(s["summary"][0]), int(s["summary"][1])
+        assert N == sum(len(w) for w in want) > 1000 and (N, KB) == (h["sum_num_entries"], h["sum_key_bytes"])
+        assert np.array_equal(s["range_entry_start"][:n + 1], h["range_entry_start"][:n + 1])
+        assert np.array_equal(s["range_status"][:n], h["range_status"][:n]) and not s["range_status"][:n].any()
+        assert np.array_equal(s["key_off"][:N + 1], h["key_off"][:N + 1])
+        assert s["key_arena"][:KB].tobytes() == h["key_arena"][:KB].tobytes() == b"".join(r[0] for w in want for r in w)
+        for f in ("seq", "flags", "val_off", "val_len", "create_ts", "expire_ts"):
+            assert np.array_equal(s[f][:N], h[f][:N]), f
+        assert not h["sst"][:N].any()
+        if desc:  # unique keys: descending is the exact reverse, range by range
+            res = s["range_entry_start"].tolist()
+            assert res == asc["range_entry_start"].tolist()
+            for q in range(n):
+                assert np.array_equal(s["seq"][res[q]:res[q + 1]], asc["seq"][res[q]:res[q + 1]][::-1])
+        asc = s
