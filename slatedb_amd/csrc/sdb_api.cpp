@@ -1,16 +1,15 @@
-// sdb_api.cpp — the C ABI (include/slatedb_amd.h): argument checks, workspace carving, launches,
-// and the host-buffer runtime (device arena + pinned staging + stream per handle).
+// sdb_api.cpp — the C ABI over device pointers (include/slatedb_amd.h): argument checks, workspace
+// carving, launches; then the stage-timing diagnostics.  The handles that stage host buffers around these
+// calls are in sdb_host.cpp and sdb_compactor.cpp.
 //
 // Host side of the drop-in for slatedb's EncodedSsTableBuilder / SsTableFormat::read_blocks
 // (slatedb/src/sst_builder.rs:224-417, format/sst.rs:938-1038).  No CPU fallback: without a HIP
 // device every compute entry point returns SDB_DEVICE_ERROR.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <string.h>
 
 #include <algorithm>
 #include <mutex>
-#include <thread>
 #include <vector>
 
 #include "../../include/slatedb_amd.h"
@@ -552,6 +551,31 @@ sdb_status sst_cuts_padded(const sdb_kv_batch *batch, const sdb_sst_params *para
 }
 }  // namespace sdb
 
+namespace {
+// What the read entry points check of their shared arguments (each after its own NULL checks).  A check that
+// returns another status than its neighbours stays where it was in each entry point, so every combination of
+// arguments gets the status it always got.
+sdb_status check_view(const sdb_sst_view *sst) {
+    if (sst->sst_version != 1 && sst->sst_version != 2) return SDB_INVALID_VERSION;
+    if (sst->num_blocks >= 0xFFFFFFFFull) return SDB_LIMIT_EXCEEDED;
+    if (sst->num_blocks && (!sst->data || !sst->block_off || !sst->index_keys || !sst->index_key_off))
+        return SDB_INVALID_ARGUMENT;
+    return SDB_OK;
+}
+sdb_status check_tree(const sdb_lsm_view *lsm) {
+    if (lsm->total_blocks >= 0xFFFFFFFFull || lsm->num_ssts == 0xFFFFFFFFu) return SDB_LIMIT_EXCEEDED;
+    if (lsm->num_ssts && (!lsm->ssts || !lsm->run_start || !lsm->first_key_off || !lsm->last_key_off ||
+                          !lsm->block_base || !lsm->first_key_bytes || !lsm->last_key_bytes))
+        return SDB_INVALID_ARGUMENT;
+    return SDB_OK;
+}
+sdb_status check_ranges(const sdb_scan_ranges *r) {
+    if (r->n && (!r->start_bytes || !r->start_off || !r->start_kind || !r->end_bytes || !r->end_off || !r->end_kind))
+        return SDB_INVALID_ARGUMENT;
+    return SDB_OK;
+}
+}  // namespace
+
 extern "C" {
 
 uint64_t sdb_sst_lookup_workspace_bytes(uint64_t num_blocks, uint64_t nkeys) {
@@ -562,10 +586,8 @@ sdb_status sdb_sst_lookup(const sdb_sst_view *sst, const uint8_t *key_bytes, con
                           uint64_t nkeys, int32_t descending, const sdb_lookup_out *out, void *workspace,
                           uint64_t workspace_bytes, void *stream) {
     if (!sst || !out) return SDB_INVALID_ARGUMENT;
-    if (sst->sst_version != 1 && sst->sst_version != 2) return SDB_INVALID_VERSION;
-    if (sst->num_blocks >= 0xFFFFFFFFull) return SDB_LIMIT_EXCEEDED;
-    if (sst->num_blocks && (!sst->data || !sst->block_off || !sst->index_keys || !sst->index_key_off))
-        return SDB_INVALID_ARGUMENT;
+    sdb_status st = check_view(sst);
+    if (st) return st;
     if (nkeys && (!key_bytes || !key_off || !out->state || !out->status || !out->block || !out->entry ||
                   !out->key_len || !out->val_off || !out->val_len || !out->seq || !out->flags || !out->create_ts ||
                   !out->expire_ts))
@@ -585,15 +607,11 @@ uint64_t sdb_sst_scan_workspace_bytes(uint64_t num_blocks, uint64_t nranges) {
 sdb_status sdb_sst_scan(const sdb_sst_view *sst, const sdb_scan_ranges *ranges, int32_t descending,
                         const sdb_scan_out *out, void *workspace, uint64_t workspace_bytes, void *stream) {
     if (!sst || !ranges || !out) return SDB_INVALID_ARGUMENT;
-    if (sst->sst_version != 1 && sst->sst_version != 2) return SDB_INVALID_VERSION;
-    if (sst->num_blocks >= 0xFFFFFFFFull) return SDB_LIMIT_EXCEEDED;
+    sdb_status st = check_view(sst);
+    if (st) return st;
     const uint64_t n = ranges->n;
-    if (sst->num_blocks && (!sst->data || !sst->block_off || !sst->index_keys || !sst->index_key_off))
-        return SDB_INVALID_ARGUMENT;
-    if (!out->summary || !out->range_entry_start) return SDB_INVALID_ARGUMENT;
-    if (n && (!ranges->start_bytes || !ranges->start_off || !ranges->start_kind || !ranges->end_bytes ||
-              !ranges->end_off || !ranges->end_kind || !out->range_block || !out->range_status))
-        return SDB_INVALID_ARGUMENT;
+    if (!out->summary || !out->range_entry_start || check_ranges(ranges)) return SDB_INVALID_ARGUMENT;
+    if (n && (!out->range_block || !out->range_status)) return SDB_INVALID_ARGUMENT;
     if (!out->key_off || (out->key_arena_cap && !out->key_arena)) return SDB_INVALID_ARGUMENT;
     if (out->cap_entries && (!out->val_off || !out->val_len || !out->seq || !out->flags || !out->create_ts ||
                              !out->expire_ts))
@@ -618,11 +636,10 @@ sdb_status sdb_lsm_get(const sdb_lsm_view *lsm, const uint8_t *key_bytes, const 
                        const uint64_t *max_seq, const sdb_get_out *out, void *workspace, uint64_t workspace_bytes,
                        void *stream) {
     if (!lsm || !out) return SDB_INVALID_ARGUMENT;
-    if (lsm->total_blocks >= 0xFFFFFFFFull || lsm->num_ssts == 0xFFFFFFFFu) return SDB_LIMIT_EXCEEDED;
+    // (the limits all give one status, so this one may come before the tree's)
     if (lsm->num_runs && nkeys > (1ull << 40) / lsm->num_runs) return SDB_LIMIT_EXCEEDED;  // a byte per (query, run)
-    if (lsm->num_ssts && (!lsm->ssts || !lsm->run_start || !lsm->first_key_off || !lsm->last_key_off ||
-                          !lsm->block_base || !lsm->first_key_bytes || !lsm->last_key_bytes))
-        return SDB_INVALID_ARGUMENT;
+    sdb_status st = check_tree(lsm);
+    if (st) return st;
     if (!out->summary) return SDB_INVALID_ARGUMENT;
     if (nkeys && (!key_bytes || !key_off || !out->state || !out->status || !out->sst || !out->block || !out->val_off ||
                   !out->val_len || !out->seq || !out->flags || !out->create_ts || !out->expire_ts || !out->ssts_read ||
@@ -647,17 +664,14 @@ sdb_status sdb_lsm_scan(const sdb_lsm_view *lsm, const sdb_scan_ranges *ranges, 
                         int32_t descending, uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out *out,
                         void *workspace, uint64_t workspace_bytes, void *stream) {
     if (!lsm || !ranges || !out) return SDB_INVALID_ARGUMENT;
-    if (lsm->total_blocks >= 0xFFFFFFFFull || lsm->num_ssts == 0xFFFFFFFFu) return SDB_LIMIT_EXCEEDED;
     const uint64_t n = ranges->n;
+    // (the limits all give one status, so these may come before the tree's)
     if (lsm->num_ssts && n > (1ull << 40) / lsm->num_ssts) return SDB_LIMIT_EXCEEDED;  // per (range, SST) state
     if (cand_entries > (1ull << 40) || cand_key_bytes > (1ull << 44)) return SDB_LIMIT_EXCEEDED;
-    if (lsm->num_ssts && (!lsm->ssts || !lsm->run_start || !lsm->first_key_off || !lsm->last_key_off ||
-                          !lsm->block_base || !lsm->first_key_bytes || !lsm->last_key_bytes))
-        return SDB_INVALID_ARGUMENT;
-    if (!out->summary || !out->range_entry_start || !out->key_off) return SDB_INVALID_ARGUMENT;
-    if (n && (!ranges->start_bytes || !ranges->start_off || !ranges->start_kind || !ranges->end_bytes ||
-              !ranges->end_off || !ranges->end_kind || !out->range_status || !out->range_ssts))
-        return SDB_INVALID_ARGUMENT;
+    sdb_status st = check_tree(lsm);
+    if (st) return st;
+    if (!out->summary || !out->range_entry_start || !out->key_off || check_ranges(ranges)) return SDB_INVALID_ARGUMENT;
+    if (n && (!out->range_status || !out->range_ssts)) return SDB_INVALID_ARGUMENT;
     if (out->key_arena_cap && !out->key_arena) return SDB_INVALID_ARGUMENT;
     if (out->cap_entries && (!out->sst || !out->val_off || !out->val_len || !out->seq || !out->flags ||
                              !out->create_ts || !out->expire_ts))
@@ -678,7 +692,6 @@ sdb_status sdb_lsm_scan(const sdb_lsm_view *lsm, const sdb_scan_ranges *ranges, 
 // =================================================================================================
 // Stage timing (diagnostics)
 // =================================================================================================
-#include <mutex>
 namespace sdb {
 namespace {
 std::mutex g_diag_mu;
@@ -730,623 +743,6 @@ int sdb_diag_stage_times(double *ms, int max_stages, uint64_t *launches) {
     g_launches = 0;
     return kNumStages;
 }
-}  // extern "C"
-
-// =================================================================================================
-// Host-buffer runtime
-// =================================================================================================
-namespace {
-
-struct DevBuf {
-    void *p = nullptr;
-    uint64_t cap = 0;
-    hipError_t ensure(uint64_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) hipFree(p);
-        p = nullptr;
-        cap = 0;
-        uint64_t want = std::max<uint64_t>(bytes + bytes / 4, 4096);
-        hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) {
-        o.p = nullptr;
-        o.cap = 0;
-    }
-    DevBuf &operator=(DevBuf &&o) noexcept {
-        if (this != &o) {
-            if (p) hipFree(p);
-            p = o.p;
-            cap = o.cap;
-            o.p = nullptr;
-            o.cap = 0;
-        }
-        return *this;
-    }
-    ~DevBuf() {
-        if (p) hipFree(p);
-    }
-};
-struct PinBuf {
-    void *p = nullptr;
-    uint64_t cap = 0;
-    hipError_t ensure(uint64_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        uint64_t want = std::max<uint64_t>(bytes + bytes / 4, 4096);
-        hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    PinBuf() = default;
-    PinBuf(const PinBuf &) = delete;
-    PinBuf &operator=(const PinBuf &) = delete;
-    PinBuf(PinBuf &&o) noexcept : p(o.p), cap(o.cap) {
-        o.p = nullptr;
-        o.cap = 0;
-    }
-    PinBuf &operator=(PinBuf &&o) noexcept {
-        if (this != &o) {
-            if (p) hipHostFree(p);
-            p = o.p;
-            cap = o.cap;
-            o.p = nullptr;
-            o.cap = 0;
-        }
-        return *this;
-    }
-    ~PinBuf() {
-        if (p) hipHostFree(p);
-    }
-};
-
-}  // namespace
-
-// One in-flight SST of the pipelined host path (sdb_encoder_encode_host_many).
-struct EncSlot {
-    PinBuf h_in;
-    DevBuf d_in, d_out, d_ws;
-    hipEvent_t h2d_done = nullptr, comp_done = nullptr, d2h_done = nullptr;
-    bool used = false;
-};
-
-struct sdb_encoder {
-    int device = 0;
-    sdb_sst_params params{};
-    hipStream_t stream = nullptr;  // kernels (and the whole single-SST path)
-    hipEvent_t ev[4] = {};
-    // device: input, output, workspace
-    DevBuf d_in, d_out, d_ws;
-    PinBuf h_in, h_out;
-    // pipelined path: H2D and D2H on their own streams (the two copy directions overlap each other
-    // and the kernels), two slots of staging / device buffers, one pinned output area per SST
-    hipStream_t s_h2d = nullptr, s_d2h = nullptr;
-    EncSlot slot[2];
-    std::vector<PinBuf> outs;
-    PinBuf sums;
-};
-
-namespace {
-
-struct InLayout {  // packed input arrays inside one allocation (256-byte aligned pieces)
-    uint64_t key_bytes, key_off, val_bytes, val_off, kind, seq, cts, ets, mask, plen, total;
-};
-// Only the columns the batch has take space (and H2D bytes).
-InLayout in_layout(const sdb_kv_batch *hb, uint64_t kb, uint64_t vb) {
-    const uint64_t n = hb->n;
-    InLayout l{};
-    uint64_t off = 0;
-    auto take = [&](uint64_t bytes) {
-        uint64_t r = off;
-        off += (bytes + 255) & ~255ull;
-        return r;
-    };
-    l.key_bytes = take(kb + 16);
-    l.key_off = take(8 * (n + 1));
-    l.val_bytes = take(vb + 16);
-    l.val_off = take(8 * (n + 1));
-    l.kind = take(hb->kind ? n + 1 : 0);
-    l.seq = take(hb->seq ? 8 * (n + 1) : 0);
-    l.cts = take(hb->create_ts ? 8 * (n + 1) : 0);
-    l.ets = take(hb->expire_ts ? 8 * (n + 1) : 0);
-    l.mask = take(hb->ts_mask ? n + 1 : 0);
-    l.plen = take(hb->prefix_len ? 4 * (n + 1) : 0);
-    l.total = off;
-    return l;
-}
-
-// The caller's (pageable) batch into pinned staging, offsets rebased to 0.  Large copies are split
-// over a few host threads: one thread's memcpy bandwidth is below the PCIe rate.
-void marshal(const sdb_kv_batch *hb, const InLayout &il, uint8_t *hi, uint64_t k0, uint64_t kb, uint64_t v0, uint64_t vb) {
-    const uint64_t n = hb->n;
-    if (!n) return;
-    std::vector<std::pair<uint8_t *, const uint8_t *>> dst_src;
-    std::vector<uint64_t> len;
-    auto add = [&](uint8_t *d, const void *s, uint64_t l) {
-        if (s && l) {
-            dst_src.push_back({d, (const uint8_t *)s});
-            len.push_back(l);
-        }
-    };
-    add(hi + il.key_bytes, hb->key_bytes + k0, kb);
-    add(hi + il.val_bytes, hb->val_bytes ? hb->val_bytes + v0 : nullptr, vb);
-    add(hi + il.kind, hb->kind, n);
-    add(hi + il.seq, hb->seq, 8 * n);
-    add(hi + il.cts, hb->create_ts, 8 * n);
-    add(hi + il.ets, hb->expire_ts, 8 * n);
-    add(hi + il.mask, hb->ts_mask, n);
-    add(hi + il.plen, hb->prefix_len, 4 * n);
-    uint64_t total = 0;
-    for (uint64_t l : len) total += l;
-    const unsigned nt = total >= (16u << 20) ? 8 : 1;
-    auto work = [&](unsigned t) {
-        // byte range [t * total / nt, (t + 1) * total / nt) of the concatenated copies
-        const uint64_t lo = total * t / nt, hi_ = total * (t + 1) / nt;
-        uint64_t base = 0;
-        for (size_t q = 0; q < len.size(); q++) {
-            const uint64_t a = std::max(lo, base), b = std::min(hi_, base + len[q]);
-            if (a < b) memcpy(dst_src[q].first + (a - base), dst_src[q].second + (a - base), b - a);
-            base += len[q];
-        }
-        // and entries [t * (n + 1) / nt, ...) of the rebased offsets
-        uint64_t *ko = (uint64_t *)(hi + il.key_off), *vo = (uint64_t *)(hi + il.val_off);
-        const uint64_t e0 = (n + 1) * t / nt, e1 = (n + 1) * (t + 1) / nt;
-        for (uint64_t i = e0; i < e1; i++) {
-            ko[i] = hb->key_off[i] - k0;
-            vo[i] = hb->val_off[i] - v0;
-        }
-    };
-    if (nt == 1) {
-        work(0);
-        return;
-    }
-    std::vector<std::thread> th;
-    for (unsigned t = 1; t < nt; t++) th.emplace_back(work, t);
-    work(0);
-    for (auto &x : th) x.join();
-}
-
-sdb_kv_batch dev_batch(const sdb_kv_batch *hb, const InLayout &il, uint8_t *di) {
-    sdb_kv_batch db{};
-    db.n = hb->n;
-    db.key_bytes = di + il.key_bytes;
-    db.key_off = (const uint64_t *)(di + il.key_off);
-    db.val_bytes = di + il.val_bytes;
-    db.val_off = (const uint64_t *)(di + il.val_off);
-    db.kind = hb->kind ? di + il.kind : nullptr;
-    db.seq = hb->seq ? (const uint64_t *)(di + il.seq) : nullptr;
-    db.create_ts = hb->create_ts ? (const int64_t *)(di + il.cts) : nullptr;
-    db.expire_ts = hb->expire_ts ? (const int64_t *)(di + il.ets) : nullptr;
-    db.ts_mask = hb->ts_mask ? di + il.mask : nullptr;
-    db.prefix_len = hb->prefix_len ? (const int32_t *)(di + il.plen) : nullptr;
-    return db;
-}
-struct OutLayout {
-    uint64_t data, block_off, block_first, index_key_len, block_stats, bloom, summary, total;
-};
-OutLayout out_layout(uint64_t data_cap, uint64_t block_cap, uint64_t bloom_cap) {
-    OutLayout l{};
-    uint64_t off = 0;
-    auto take = [&](uint64_t bytes) {
-        uint64_t r = off;
-        off += (bytes + 255) & ~255ull;
-        return r;
-    };
-    l.data = take(data_cap);
-    l.block_off = take(8 * (block_cap + 1));
-    l.block_first = take(4 * (block_cap + 1));
-    l.index_key_len = take(4 * (block_cap + 1));
-    l.block_stats = take(6 * (block_cap + 1));
-    l.bloom = take(bloom_cap);
-    l.summary = take(sizeof(sdb_sst_summary));
-    l.total = off;
-    return l;
-}
-
-}  // namespace
-
-extern "C" {
-
-sdb_encoder *sdb_encoder_create(int device, const sdb_sst_params *params) {
-    if (check_params(params) || !device_ok()) return nullptr;
-    if (hipSetDevice(device) != hipSuccess) return nullptr;
-    sdb_encoder *e = new sdb_encoder();
-    e->device = device;
-    e->params = *params;
-    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) {
-        delete e;
-        return nullptr;
-    }
-    for (auto &x : e->ev) hipEventCreate(&x);
-    if (hipStreamCreateWithFlags(&e->s_h2d, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&e->s_d2h, hipStreamNonBlocking) != hipSuccess) {
-        sdb_encoder_destroy(e);
-        return nullptr;
-    }
-    for (EncSlot &sl : e->slot) {
-        hipEventCreateWithFlags(&sl.h2d_done, hipEventDisableTiming);
-        hipEventCreateWithFlags(&sl.comp_done, hipEventDisableTiming);
-        hipEventCreateWithFlags(&sl.d2h_done, hipEventDisableTiming);
-    }
-    return e;
-}
-
-void sdb_encoder_destroy(sdb_encoder *e) {
-    if (!e) return;
-    hipSetDevice(e->device);
-    for (hipStream_t st : {e->stream, e->s_h2d, e->s_d2h})
-        if (st) hipStreamSynchronize(st);
-    for (auto &x : e->ev) hipEventDestroy(x);
-    for (EncSlot &sl : e->slot)
-        for (hipEvent_t x : {sl.h2d_done, sl.comp_done, sl.d2h_done})
-            if (x) hipEventDestroy(x);
-    for (hipStream_t st : {e->stream, e->s_h2d, e->s_d2h})
-        if (st) hipStreamDestroy(st);
-    delete e;
-}
-
-sdb_status sdb_encoder_encode_host(sdb_encoder *e, const sdb_kv_batch *hb, sdb_sst_host_result *r) {
-    if (!e || !hb || !r) return SDB_INVALID_ARGUMENT;
-    hipSetDevice(e->device);
-    const uint64_t n = hb->n;
-    const uint64_t k0 = n ? hb->key_off[0] : 0, kb = n ? hb->key_off[n] - k0 : 0;
-    const uint64_t v0 = n ? hb->val_off[0] : 0, vb = n ? hb->val_off[n] - v0 : 0;
-    uint64_t data_cap, block_cap, bloom_cap;
-    sdb_encode_bounds(n, kb, vb, &e->params, &data_cap, &block_cap, &bloom_cap);
-    if (data_cap >= (1ull << 32)) return SDB_LIMIT_EXCEEDED;  // u32 per-block/chunk byte counters
-    InLayout il = in_layout(hb, kb, vb);
-    OutLayout ol = out_layout(data_cap, block_cap, bloom_cap);
-    uint64_t wsb = sdb_encode_workspace_bytes(n, &e->params);
-    if (e->h_in.ensure(il.total) || e->d_in.ensure(il.total) || e->h_out.ensure(ol.total) ||
-        e->d_out.ensure(ol.total) || e->d_ws.ensure(wsb))
-        return SDB_DEVICE_ERROR;
-    uint8_t *hi = (uint8_t *)e->h_in.p;
-    marshal(hb, il, hi, k0, kb, v0, vb);
-    uint8_t *di = (uint8_t *)e->d_in.p, *dout = (uint8_t *)e->d_out.p;
-    hipEventRecord(e->ev[0], e->stream);
-    hipMemcpyAsync(di, hi, il.total, hipMemcpyHostToDevice, e->stream);
-    hipEventRecord(e->ev[1], e->stream);
-    const sdb_kv_batch db = dev_batch(hb, il, di);
-    sdb_sst_out o{};
-    o.data = dout + ol.data;
-    o.data_cap = data_cap;
-    o.block_off = (uint64_t *)(dout + ol.block_off);
-    o.block_first_entry = (uint32_t *)(dout + ol.block_first);
-    o.index_key_len = (uint32_t *)(dout + ol.index_key_len);
-    o.block_stats = (uint16_t *)(dout + ol.block_stats);
-    o.block_cap = block_cap;
-    o.bloom = dout + ol.bloom;
-    o.bloom_cap = bloom_cap;
-    o.summary = (sdb_sst_summary *)(dout + ol.summary);
-    sdb_status st = sdb_encode_sst(&db, &e->params, &o, e->d_ws.p, e->d_ws.cap, e->stream);
-    if (st) return st;
-    hipEventRecord(e->ev[2], e->stream);
-    // D2H: summary first (sizes), then only the used parts
-    uint8_t *ho = (uint8_t *)e->h_out.p;
-    hipMemcpyAsync(ho + ol.summary, dout + ol.summary, sizeof(sdb_sst_summary), hipMemcpyDeviceToHost, e->stream);
-    if (hipStreamSynchronize(e->stream) != hipSuccess) return SDB_DEVICE_ERROR;
-    sdb_sst_summary sm;
-    memcpy(&sm, ho + ol.summary, sizeof sm);
-    if (sm.status == SDB_OK) {
-        uint64_t nb = sm.num_blocks;
-        hipMemcpyAsync(ho + ol.data, dout + ol.data, sm.data_len, hipMemcpyDeviceToHost, e->stream);
-        hipMemcpyAsync(ho + ol.block_off, dout + ol.block_off, 8 * (nb + 1), hipMemcpyDeviceToHost, e->stream);
-        hipMemcpyAsync(ho + ol.block_first, dout + ol.block_first, 4 * (nb + 1), hipMemcpyDeviceToHost, e->stream);
-        hipMemcpyAsync(ho + ol.index_key_len, dout + ol.index_key_len, 4 * nb, hipMemcpyDeviceToHost, e->stream);
-        hipMemcpyAsync(ho + ol.block_stats, dout + ol.block_stats, 6 * nb, hipMemcpyDeviceToHost, e->stream);
-        if (sm.bloom_len)
-            hipMemcpyAsync(ho + ol.bloom, dout + ol.bloom, sm.bloom_len, hipMemcpyDeviceToHost, e->stream);
-    }
-    hipEventRecord(e->ev[3], e->stream);
-    if (hipStreamSynchronize(e->stream) != hipSuccess) return SDB_DEVICE_ERROR;
-    float t01 = 0, t12 = 0, t23 = 0;
-    hipEventElapsedTime(&t01, e->ev[0], e->ev[1]);
-    hipEventElapsedTime(&t12, e->ev[1], e->ev[2]);
-    hipEventElapsedTime(&t23, e->ev[2], e->ev[3]);
-    r->summary = sm;
-    r->data = ho + ol.data;
-    r->block_off = (const uint64_t *)(ho + ol.block_off);
-    r->block_first_entry = (const uint32_t *)(ho + ol.block_first);
-    r->index_key_len = (const uint32_t *)(ho + ol.index_key_len);
-    r->block_stats = (const uint16_t *)(ho + ol.block_stats);
-    r->bloom = ho + ol.bloom;
-    r->h2d_ms = t01;
-    r->kernel_ms = t12;
-    r->d2h_ms = t23;
-    return (sdb_status)sm.status;
-}
-
-// Several host batches, transfers overlapped: while SST i's kernels run, SST i+1 is marshalled
-// into the other slot's pinned staging and copied H2D, and SST i-1's outputs come back D2H (three
-// streams; the copy engines serve both directions at once).  The host waits only for each SST's
-// summary (to size its D2H) and for the last D2H.
-sdb_status sdb_encoder_encode_host_many(sdb_encoder *e, uint32_t count, const sdb_kv_batch *hbs,
-                                        sdb_sst_host_result *results) {
-    if (!e || (count && (!hbs || !results))) return SDB_INVALID_ARGUMENT;
-    if (hipSetDevice(e->device) != hipSuccess) return SDB_DEVICE_ERROR;
-    if (e->outs.size() < count) e->outs.resize(count);
-    if (e->sums.ensure(sizeof(sdb_sst_summary) * (count + 1))) return SDB_DEVICE_ERROR;
-    sdb_sst_summary *sums = (sdb_sst_summary *)e->sums.p;
-    struct Job {
-        InLayout il;
-        OutLayout ol;
-        uint64_t data_cap, block_cap, bloom_cap;
-    };
-    std::vector<Job> jobs(count);
-    sdb_status first = SDB_OK;
-    auto fail = [&](sdb_status st) {
-        for (hipStream_t x : {e->s_h2d, e->stream, e->s_d2h}) hipStreamSynchronize(x);
-        return st;
-    };
-    for (uint32_t i = 0; i <= count; i++) {
-        if (i < count) {
-            const sdb_kv_batch *hb = &hbs[i];
-            EncSlot &sl = e->slot[i & 1];
-            Job &jb = jobs[i];
-            const uint64_t n = hb->n;
-            const uint64_t k0 = n ? hb->key_off[0] : 0, kb = n ? hb->key_off[n] - k0 : 0;
-            const uint64_t v0 = n ? hb->val_off[0] : 0, vb = n ? hb->val_off[n] - v0 : 0;
-            if (sdb_encode_bounds(n, kb, vb, &e->params, &jb.data_cap, &jb.block_cap, &jb.bloom_cap)) return fail(SDB_INVALID_ARGUMENT);
-            if (jb.data_cap >= (1ull << 32)) return fail(SDB_LIMIT_EXCEEDED);
-            jb.il = in_layout(hb, kb, vb);
-            jb.ol = out_layout(jb.data_cap, jb.block_cap, jb.bloom_cap);
-            const uint64_t wsb = sdb_encode_workspace_bytes(n, &e->params);
-            // the slot's previous SST (i - 2) must be out of its staging (H2D) before the marshal
-            // overwrites it; buffers only grow after every use of the slot has drained
-            if (sl.used) hipEventSynchronize(sl.h2d_done);
-            const bool grow = sl.h_in.cap < jb.il.total || sl.d_in.cap < jb.il.total || sl.d_out.cap < jb.ol.total ||
-                              sl.d_ws.cap < wsb;
-            if (grow && sl.used) {
-                hipEventSynchronize(sl.comp_done);
-                hipEventSynchronize(sl.d2h_done);
-            }
-            if (sl.h_in.ensure(jb.il.total) || sl.d_in.ensure(jb.il.total) || sl.d_out.ensure(jb.ol.total) ||
-                sl.d_ws.ensure(wsb))
-                return fail(SDB_DEVICE_ERROR);
-            marshal(hb, jb.il, (uint8_t *)sl.h_in.p, k0, kb, v0, vb);
-            // H2D once the slot's previous kernels no longer read d_in
-            if (sl.used) hipStreamWaitEvent(e->s_h2d, sl.comp_done, 0);
-            hipMemcpyAsync(sl.d_in.p, sl.h_in.p, jb.il.total, hipMemcpyHostToDevice, e->s_h2d);
-            hipEventRecord(sl.h2d_done, e->s_h2d);
-            // kernels once the input is there and the slot's previous outputs are back on the host
-            hipStreamWaitEvent(e->stream, sl.h2d_done, 0);
-            if (sl.used) hipStreamWaitEvent(e->stream, sl.d2h_done, 0);
-            const sdb_kv_batch db = dev_batch(hb, jb.il, (uint8_t *)sl.d_in.p);
-            uint8_t *dout = (uint8_t *)sl.d_out.p;
-            sdb_sst_out o{};
-            o.data = dout + jb.ol.data;
-            o.data_cap = jb.data_cap;
-            o.block_off = (uint64_t *)(dout + jb.ol.block_off);
-            o.block_first_entry = (uint32_t *)(dout + jb.ol.block_first);
-            o.index_key_len = (uint32_t *)(dout + jb.ol.index_key_len);
-            o.block_stats = (uint16_t *)(dout + jb.ol.block_stats);
-            o.block_cap = jb.block_cap;
-            o.bloom = dout + jb.ol.bloom;
-            o.bloom_cap = jb.bloom_cap;
-            o.summary = (sdb_sst_summary *)(dout + jb.ol.summary);
-            const sdb_status st = sdb_encode_sst(&db, &e->params, &o, sl.d_ws.p, sl.d_ws.cap, e->stream);
-            if (st) return fail(st);
-            hipMemcpyAsync(&sums[i], o.summary, sizeof(sdb_sst_summary), hipMemcpyDeviceToHost, e->stream);
-            hipEventRecord(sl.comp_done, e->stream);
-            sl.used = true;
-        }
-        if (i >= 1) {  // SST j's outputs: sized by its summary, copied on the D2H stream
-            const uint32_t j = i - 1;
-            EncSlot &sl = e->slot[j & 1];
-            const Job &jb = jobs[j];
-            if (hipEventSynchronize(sl.comp_done) != hipSuccess) return fail(SDB_DEVICE_ERROR);
-            const sdb_sst_summary sm = sums[j];
-            PinBuf &ho = e->outs[j];
-            if (ho.ensure(jb.ol.total)) return fail(SDB_DEVICE_ERROR);
-            uint8_t *h = (uint8_t *)ho.p, *d = (uint8_t *)sl.d_out.p;
-            hipStreamWaitEvent(e->s_d2h, sl.comp_done, 0);
-            if (sm.status == SDB_OK) {
-                const uint64_t nb = sm.num_blocks;
-                hipMemcpyAsync(h + jb.ol.data, d + jb.ol.data, sm.data_len, hipMemcpyDeviceToHost, e->s_d2h);
-                hipMemcpyAsync(h + jb.ol.block_off, d + jb.ol.block_off, 8 * (nb + 1), hipMemcpyDeviceToHost, e->s_d2h);
-                hipMemcpyAsync(h + jb.ol.block_first, d + jb.ol.block_first, 4 * (nb + 1), hipMemcpyDeviceToHost, e->s_d2h);
-                hipMemcpyAsync(h + jb.ol.index_key_len, d + jb.ol.index_key_len, 4 * nb, hipMemcpyDeviceToHost, e->s_d2h);
-                hipMemcpyAsync(h + jb.ol.block_stats, d + jb.ol.block_stats, 6 * nb, hipMemcpyDeviceToHost, e->s_d2h);
-                if (sm.bloom_len)
-                    hipMemcpyAsync(h + jb.ol.bloom, d + jb.ol.bloom, sm.bloom_len, hipMemcpyDeviceToHost, e->s_d2h);
-            }
-            hipEventRecord(sl.d2h_done, e->s_d2h);
-            sdb_sst_host_result &r = results[j];
-            r.summary = sm;
-            r.data = h + jb.ol.data;
-            r.block_off = (const uint64_t *)(h + jb.ol.block_off);
-            r.block_first_entry = (const uint32_t *)(h + jb.ol.block_first);
-            r.index_key_len = (const uint32_t *)(h + jb.ol.index_key_len);
-            r.block_stats = (const uint16_t *)(h + jb.ol.block_stats);
-            r.bloom = h + jb.ol.bloom;
-            r.h2d_ms = r.kernel_ms = r.d2h_ms = 0;
-            if (!first && sm.status) first = (sdb_status)sm.status;
-        }
-    }
-    if (hipStreamSynchronize(e->s_d2h) != hipSuccess) return SDB_DEVICE_ERROR;
-    return first;
-}
-
-}  // extern "C"
-
-// -------------------------------------------------------------------------------------------------
-// EncodedSsTableBuilder mirror
-// -------------------------------------------------------------------------------------------------
-struct sdb_sst_builder {
-    sdb_encoder *enc = nullptr;
-    std::vector<uint8_t> keys, vals, kind, mask;
-    std::vector<uint64_t> koff{0}, voff{0}, seq;
-    std::vector<int64_t> cts, ets;
-};
-
-extern "C" {
-
-sdb_sst_builder *sdb_sst_builder_new(int device, const sdb_sst_params *params) {
-    sdb_encoder *e = sdb_encoder_create(device, params);
-    if (!e) return nullptr;
-    sdb_sst_builder *b = new sdb_sst_builder();
-    b->enc = e;
-    return b;
-}
-
-void sdb_sst_builder_free(sdb_sst_builder *b) {
-    if (!b) return;
-    sdb_encoder_destroy(b->enc);
-    delete b;
-}
-
-sdb_status sdb_sst_builder_add(sdb_sst_builder *b, const uint8_t *key, uint64_t key_len, uint8_t kind,
-                               const uint8_t *val, uint64_t val_len, uint64_t seq, int32_t has_create_ts,
-                               int64_t create_ts, int32_t has_expire_ts, int64_t expire_ts) {
-    if (!b || kind > SDB_KIND_TOMBSTONE) return SDB_INVALID_ARGUMENT;
-    b->keys.insert(b->keys.end(), key, key + key_len);
-    if (kind != SDB_KIND_TOMBSTONE && val_len) b->vals.insert(b->vals.end(), val, val + val_len);
-    b->koff.push_back(b->keys.size());
-    b->voff.push_back(b->vals.size());
-    b->kind.push_back(kind);
-    b->seq.push_back(seq);
-    b->cts.push_back(create_ts);
-    b->ets.push_back(expire_ts);
-    b->mask.push_back((uint8_t)((has_create_ts ? SDB_TS_CREATE : 0) | (has_expire_ts ? SDB_TS_EXPIRE : 0)));
-    return SDB_OK;
-}
-
-sdb_status sdb_sst_builder_build(sdb_sst_builder *b, sdb_sst_host_result *r) {
-    if (!b) return SDB_INVALID_ARGUMENT;
-    sdb_kv_batch hb{};
-    hb.n = b->kind.size();
-    static const uint8_t zero16[16] = {0};
-    hb.key_bytes = b->keys.empty() ? zero16 : b->keys.data();
-    hb.key_off = b->koff.data();
-    hb.val_bytes = b->vals.empty() ? zero16 : b->vals.data();
-    hb.val_off = b->voff.data();
-    hb.kind = b->kind.data();
-    hb.seq = b->seq.data();
-    hb.create_ts = b->cts.data();
-    hb.expire_ts = b->ets.data();
-    hb.ts_mask = b->mask.data();
-    return sdb_encoder_encode_host(b->enc, &hb, r);
-}
-
-}  // extern "C"
-
-// -------------------------------------------------------------------------------------------------
-// Host decode
-// -------------------------------------------------------------------------------------------------
-struct sdb_decoder {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    DevBuf d_in, d_out, d_ws;
-    PinBuf h_in, h_out;
-};
-
-extern "C" {
-
-sdb_decoder *sdb_decoder_create(int device) {
-    if (!device_ok() || hipSetDevice(device) != hipSuccess) return nullptr;
-    sdb_decoder *d = new sdb_decoder();
-    d->device = device;
-    if (hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) != hipSuccess) {
-        delete d;
-        return nullptr;
-    }
-    return d;
-}
-
-void sdb_decoder_destroy(sdb_decoder *d) {
-    if (!d) return;
-    hipSetDevice(d->device);
-    hipStreamSynchronize(d->stream);
-    hipStreamDestroy(d->stream);
-    delete d;
-}
-
-sdb_status sdb_decoder_decode_host(sdb_decoder *d, const uint8_t *blocks, const uint64_t *block_off,
-                                   uint64_t nblocks, uint16_t sst_version, sdb_decode_host_result *r) {
-    if (!d || !r || (nblocks && (!blocks || !block_off))) return SDB_INVALID_ARGUMENT;
-    hipSetDevice(d->device);
-    const uint64_t b0 = nblocks ? block_off[0] : 0;
-    const uint64_t total = nblocks ? block_off[nblocks] - b0 : 0;
-    // capacities: every row >= 12 bytes; restored keys can exceed encoded bytes (shared prefixes),
-    // bounded by rows x (64 KiB V0 keys) — use a generous first guess and retry once if too small.
-    uint64_t cap_e = total / 12 + 16;
-    uint64_t key_cap = total * 4 + 4096;
-    for (int attempt = 0; attempt < 2; attempt++) {
-        Carver c{nullptr, 0};  // the outputs' offsets in the device buffer and in its host mirror
-        uint64_t o_bes = c.bytes(8 * (nblocks + 1)), o_ka = c.bytes(key_cap), o_ko = c.bytes(8 * (cap_e + 1));
-        uint64_t o_vo = c.bytes(8 * cap_e), o_vl = c.bytes(4 * cap_e), o_seq = c.bytes(8 * cap_e), o_fl = c.bytes(cap_e);
-        uint64_t o_ct = c.bytes(8 * cap_e), o_et = c.bytes(8 * cap_e), o_bad = c.bytes(4 * (nblocks + 1));
-        uint64_t o_sm = c.bytes(sizeof(sdb_decode_summary));
-        uint64_t out_total = c.off;
-        uint64_t in_total = ((total + 16 + 255) & ~255ull) + 8 * (nblocks + 1);
-        uint64_t wsb = sdb_decode_workspace_bytes(nblocks);
-        if (d->h_in.ensure(in_total) || d->d_in.ensure(in_total) || d->h_out.ensure(out_total) ||
-            d->d_out.ensure(out_total) || d->d_ws.ensure(wsb))
-            return SDB_DEVICE_ERROR;
-        uint8_t *hi = (uint8_t *)d->h_in.p;
-        uint64_t o_boff = (total + 16 + 255) & ~255ull;
-        memcpy(hi, blocks + b0, total);
-        uint64_t *bo = (uint64_t *)(hi + o_boff);
-        for (uint64_t k = 0; k <= nblocks; k++) bo[k] = block_off[k] - b0;
-        uint8_t *di = (uint8_t *)d->d_in.p, *dout = (uint8_t *)d->d_out.p;
-        hipMemcpyAsync(di, hi, in_total, hipMemcpyHostToDevice, d->stream);
-        sdb_decoded_out o{};
-        o.block_entry_start = (uint64_t *)(dout + o_bes);
-        o.key_arena = dout + o_ka;
-        o.key_arena_cap = key_cap;
-        o.key_off = (uint64_t *)(dout + o_ko);
-        o.val_off = (uint64_t *)(dout + o_vo);
-        o.val_len = (uint32_t *)(dout + o_vl);
-        o.seq = (uint64_t *)(dout + o_seq);
-        o.flags = dout + o_fl;
-        o.create_ts = (int64_t *)(dout + o_ct);
-        o.expire_ts = (int64_t *)(dout + o_et);
-        o.cap_entries = cap_e;
-        o.bad_block = (uint32_t *)(dout + o_bad);
-        o.bad_cap = nblocks + 1;
-        o.summary = (sdb_decode_summary *)(dout + o_sm);
-        sdb_status st = sdb_decode_blocks(di, (const uint64_t *)(di + o_boff), nblocks, sst_version, &o, d->d_ws.p,
-                                          d->d_ws.cap, d->stream);
-        if (st) return st;
-        uint8_t *ho = (uint8_t *)d->h_out.p;
-        hipMemcpyAsync(ho, dout, out_total, hipMemcpyDeviceToHost, d->stream);
-        if (hipStreamSynchronize(d->stream) != hipSuccess) return SDB_DEVICE_ERROR;
-        sdb_decode_summary sm;
-        memcpy(&sm, ho + o_sm, sizeof sm);
-        if (sm.status == SDB_INVALID_ARGUMENT && attempt == 0 &&
-            (sm.num_entries > cap_e || sm.key_bytes > key_cap)) {
-            cap_e = sm.num_entries + 16;
-            key_cap = sm.key_bytes + 4096;
-            continue;
-        }
-        // value references are positions in the caller's `blocks` (block_off[0] was rebased to 0)
-        uint64_t *vo_h = (uint64_t *)(ho + o_vo);
-        const uint32_t *vl_h = (const uint32_t *)(ho + o_vl);
-        if (b0)
-            for (uint64_t i = 0; i < sm.num_entries && i < cap_e; i++)
-                if (vl_h[i]) vo_h[i] += b0;
-        r->summary = sm;
-        r->block_entry_start = (const uint64_t *)(ho + o_bes);
-        r->key_arena = ho + o_ka;
-        r->key_off = (const uint64_t *)(ho + o_ko);
-        r->val_off = (const uint64_t *)(ho + o_vo);
-        r->val_len = (const uint32_t *)(ho + o_vl);
-        r->seq = (const uint64_t *)(ho + o_seq);
-        r->flags = ho + o_fl;
-        r->create_ts = (const int64_t *)(ho + o_ct);
-        r->expire_ts = (const int64_t *)(ho + o_et);
-        r->bad_block = (const uint32_t *)(ho + o_bad);
-        return (sdb_status)sm.status;
-    }
-    return SDB_INVALID_ARGUMENT;
-}
-
 }  // extern "C"
 
 // Diagnostics: the fused bloom's slot plan inside sdb_encode_sst's workspace: byte offset of the run

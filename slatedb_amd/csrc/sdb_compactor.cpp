@@ -8,7 +8,7 @@
 //                            merged stream padded to the input count -> sdb_encode_ssts; two host
 //                            synchronisations (merged count + cuts together, summaries).
 // The outputs stay in the handle's device memory; every SST of the job is encoded by one launch sequence
-// per 8 SSTs.
+// per 8 SSTs.  The handle's buffers (DevBuf, PinBuf) and every layout inside them come from sdb_host.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -19,65 +19,9 @@
 #include "../../include/slatedb_amd.h"
 #include "sdb_compact.h"
 #include "sdb_decode.h"
+#include "sdb_host.h"
 
 using namespace sdb;
-
-namespace {
-
-struct DevBuf {
-    void *p = nullptr;
-    uint64_t cap = 0;
-    bool ensure(uint64_t bytes) {
-        if (bytes <= cap && p) return true;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const uint64_t c = bytes + bytes / 4 + 256;
-        if (hipMalloc(&p, c) != hipSuccess) {
-            p = nullptr;
-            return false;
-        }
-        cap = c;
-        return true;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    template <typename T>
-    T *at(uint64_t off) const {
-        return reinterpret_cast<T *>(reinterpret_cast<uint8_t *>(p) + off);
-    }
-};
-
-uint64_t al256(uint64_t x) { return (x + 255) & ~255ull; }
-
-}  // namespace
-
-struct PinBuf {  // pinned host staging (async device -> host copies)
-    void *p = nullptr;
-    uint64_t cap = 0;
-    PinBuf() = default;
-    PinBuf(const PinBuf &) = delete;
-    PinBuf &operator=(const PinBuf &) = delete;
-    bool ensure(uint64_t bytes) {
-        if (bytes <= cap && p) return true;
-        release();
-        const uint64_t c = bytes + bytes / 4 + 256;
-        if (hipHostMalloc(&p, c, hipHostMallocDefault) != hipSuccess) {
-            p = nullptr;
-            return false;
-        }
-        cap = c;
-        return true;
-    }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
 
 struct GroupBufs {  // a group of runs merged ahead of the job (runs beyond SDB_MAX_RUNS)
     DevBuf cols, keys, vals, asrun;
@@ -95,45 +39,56 @@ struct sdb_compactor {
     sdb_kv_batch merged{};
     sdb_merge_summary msum{};
     std::vector<sdb_compacted_sst> ssts;
+    // the buffers free themselves after this; only the pinned tables need an order: the last job's upload
+    // may still read them
     ~sdb_compactor() {
         (void)hipSetDevice(device);
-        for (DevBuf *b : {&merge_ws, &cols, &keys, &vals, &cut_ws, &cuts, &sst_meta, &sst_data, &sst_bloom, &enc_ws,
-                          &dec, &dec_ws, &cx_tab})
-            b->release();
-        for (GroupBufs &g : groups)
-            for (DevBuf *b : {&g.cols, &g.keys, &g.vals, &g.asrun}) b->release();
         if (tab_ev) (void)hipEventSynchronize(tab_ev);
-        pin.release();
-        pin_tab.release();
         if (tab_ev) (void)hipEventDestroy(tab_ev);
     }
 };
 
 namespace {
 
+// Sizes (base == NULL) or binds the merged-stream columns of `total` entries.
+uint64_t merged_bind(sdb_merged_out &o, uint64_t total, uint8_t *base) {
+    Carver c{base, 0};
+    c.take(o.key_off, total + 1);
+    c.take(o.val_off, total + 1);
+    c.take(o.kind, total + 1);
+    c.take(o.seq, total + 1);
+    c.take(o.create_ts, total + 1);
+    c.take(o.expire_ts, total + 1);
+    c.take(o.ts_mask, total + 1);
+    c.take(o.summary, 1);
+    return c.off;
+}
 // merged-stream columns for `total` entries in `cols`: the sdb_merged_out (byte arenas unset)
 sdb_status merged_columns_in(DevBuf &cols, uint64_t total, sdb_merged_out *out) {
-    const uint64_t o_koff = 0, o_voff = al256(8 * (total + 1)), o_kind = o_voff + al256(8 * (total + 1));
-    const uint64_t o_seq = o_kind + al256(total + 1), o_cts = o_seq + al256(8 * (total + 1));
-    const uint64_t o_ets = o_cts + al256(8 * (total + 1)), o_mask = o_ets + al256(8 * (total + 1));
-    const uint64_t o_sum = o_mask + al256(total + 1), cols_bytes = o_sum + al256(sizeof(sdb_merge_summary));
-    if (!cols.ensure(cols_bytes)) return SDB_DEVICE_ERROR;
     *out = sdb_merged_out{};
     out->key_cap = ~0ull;
-    out->key_off = cols.at<uint64_t>(o_koff);
     out->val_cap = ~0ull;
-    out->val_off = cols.at<uint64_t>(o_voff);
-    out->kind = cols.at<uint8_t>(o_kind);
-    out->seq = cols.at<uint64_t>(o_seq);
-    out->create_ts = cols.at<int64_t>(o_cts);
-    out->expire_ts = cols.at<int64_t>(o_ets);
-    out->ts_mask = cols.at<uint8_t>(o_mask);
     out->cap_entries = total;
-    out->summary = cols.at<sdb_merge_summary>(o_sum);
+    if (!cols.ensure(merged_bind(*out, total, nullptr))) return SDB_DEVICE_ERROR;
+    merged_bind(*out, total, cols.at<uint8_t>(0));
     return SDB_OK;
 }
-sdb_status merged_columns(sdb_compactor *c, uint64_t total, sdb_merged_out *out) {
-    return merged_columns_in(c->cols, total, out);
+
+// The cut list of a stream of n entries: the cut count, n + 2 cuts, n + 2 (key, value) byte offset pairs.
+struct CutLayout {
+    uint64_t num, cut, off;
+};
+CutLayout cut_layout(Carver &c, uint64_t n) { return {c.bytes(8), c.bytes(8 * (n + 2)), c.bytes(16 * (n + 2))}; }
+// The device cut list of a stream of n entries (in c->cuts) and the cut walk's workspace (c->cut_ws).
+bool cut_buffers(sdb_compactor *c, uint64_t n, const sdb_sst_params *params, uint64_t **num, uint64_t **cut,
+                 uint64_t **off) {
+    Carver k{nullptr, 0};
+    const CutLayout l = cut_layout(k, n);
+    if (!c->cut_ws.ensure(sdb_sst_cuts_workspace_bytes(n, params)) || !c->cuts.ensure(k.off)) return false;
+    *num = c->cuts.at<uint64_t>(l.num);
+    *cut = c->cuts.at<uint64_t>(l.cut);
+    *off = c->cuts.at<uint64_t>(l.off);
+    return true;
 }
 
 // A job with more runs than one merge takes (SDB_MAX_RUNS): groups of SDB_MAX_RUNS consecutive runs are
@@ -179,15 +134,16 @@ sdb_status group_runs(sdb_compactor *c, const sdb_run *runs, uint32_t nruns, con
             if (sm.status == SDB_INVALID_ARGUMENT && sm.first_error_entry != ~0ull) fail->first_error_entry += base;
             return (sdb_status)sm.status;
         }
-        if (!B.keys.ensure(sm.key_bytes + 16) || !B.vals.ensure(sm.val_bytes + 16) ||
-            !B.asrun.ensure(al256(4 * (total + 1)) + al256(total + 1)))
+        Carver rc{nullptr, 0};  // what a run has and a merged stream lacks: value lengths, then row flags
+        const uint64_t o_vlen = rc.bytes(4 * (total + 1)), o_flags = rc.bytes(total + 1);
+        if (!B.keys.ensure(sm.key_bytes + 16) || !B.vals.ensure(sm.val_bytes + 16) || !B.asrun.ensure(rc.off))
             return SDB_DEVICE_ERROR;
         a.out.key_bytes = B.keys.at<uint8_t>(0);
         a.out.key_cap = sm.key_bytes;
         a.out.val_bytes = B.vals.at<uint8_t>(0);
         a.out.val_cap = sm.val_bytes;
-        uint32_t *vlen = B.asrun.at<uint32_t>(0);
-        uint8_t *flags = B.asrun.at<uint8_t>(al256(4 * (total + 1)));
+        uint32_t *vlen = B.asrun.at<uint32_t>(o_vlen);
+        uint8_t *flags = B.asrun.at<uint8_t>(o_flags);
         if (launch_merge_emit(a, s) != hipSuccess || launch_merged_as_run(a.out, total, vlen, flags, s) != hipSuccess)
             return SDB_DEVICE_ERROR;
         sdb_run R{};
@@ -232,8 +188,6 @@ sdb_status encode_outputs(sdb_compactor *c, const uint64_t *cut, const uint64_t 
     sdb_status st = SDB_OK;
     std::vector<sdb_kv_batch> batches(ns);
     std::vector<sdb_sst_out> outs(ns);
-    std::vector<uint64_t> data_at(ns), bloom_at(ns), meta_at(ns);
-    uint64_t data_total = 0, bloom_total = 0, meta_total = al256(ns * sizeof(sdb_sst_summary));
     for (uint64_t i = 0; i < ns; i++) {
         const uint64_t b = cut[i], e = cut[i + 1], ni = e - b;
         sdb_kv_batch &x = batches[i];
@@ -246,37 +200,29 @@ sdb_status encode_outputs(sdb_compactor *c, const uint64_t *cut, const uint64_t 
         x.create_ts = m.create_ts + b;
         x.expire_ts = m.expire_ts + b;
         x.ts_mask = m.ts_mask + b;
-        uint64_t dcap = 0, bcap = 0, fcap = 0;
-        st = sdb_encode_bounds(ni, off[2 * (i + 1)] - off[2 * i], off[2 * (i + 1) + 1] - off[2 * i + 1], params, &dcap,
-                               &bcap, &fcap);
+        st = sdb_encode_bounds(ni, off[2 * (i + 1)] - off[2 * i], off[2 * (i + 1) + 1] - off[2 * i + 1], params,
+                               &outs[i].data_cap, &outs[i].block_cap, &outs[i].bloom_cap);
         if (st) return st;
-        outs[i].data_cap = dcap;
-        outs[i].block_cap = bcap;
-        outs[i].bloom_cap = fcap;
-        data_at[i] = data_total;
-        data_total += al256(dcap);
-        bloom_at[i] = bloom_total;
-        bloom_total += al256(fcap);
-        meta_at[i] = meta_total;
-        meta_total += al256(8 * (bcap + 1)) + al256(4 * (bcap + 1)) + al256(4 * bcap) + al256(6 * bcap);
     }
+    // data sections, filters and per-block arrays each in a buffer of their own; the summaries packed at the
+    // front of sst_meta, so one copy reads them back.  Sized with NULL bases, then bound.
+    uint64_t data_total = 0, bloom_total = 0, meta_total = 0;
+    auto bind = [&](uint8_t *data, uint8_t *bloom, uint8_t *meta) {
+        Carver cd{data, 0}, cb{bloom, 0}, cm{meta, 0};
+        sdb_sst_summary *sums = nullptr;
+        cm.take(sums, ns);
+        for (uint64_t i = 0; i < ns; i++) {
+            cd.take(outs[i].data, outs[i].data_cap);
+            cb.take(outs[i].bloom, outs[i].bloom_cap);
+            bind_sst_out(cm, outs[i], false);
+            outs[i].summary = sums ? sums + i : nullptr;
+        }
+        data_total = cd.off, bloom_total = cb.off, meta_total = cm.off;
+    };
+    bind(nullptr, nullptr, nullptr);
     if (!c->sst_data.ensure(data_total) || !c->sst_bloom.ensure(bloom_total) || !c->sst_meta.ensure(meta_total))
         return SDB_DEVICE_ERROR;
-    for (uint64_t i = 0; i < ns; i++) {
-        sdb_sst_out &o = outs[i];
-        const uint64_t bcap = o.block_cap;
-        uint64_t q = meta_at[i];
-        o.data = c->sst_data.at<uint8_t>(data_at[i]);
-        o.bloom = c->sst_bloom.at<uint8_t>(bloom_at[i]);
-        o.block_off = c->sst_meta.at<uint64_t>(q);
-        q += al256(8 * (bcap + 1));
-        o.block_first_entry = c->sst_meta.at<uint32_t>(q);
-        q += al256(4 * (bcap + 1));
-        o.index_key_len = c->sst_meta.at<uint32_t>(q);
-        q += al256(4 * bcap);
-        o.block_stats = c->sst_meta.at<uint16_t>(q);
-        o.summary = c->sst_meta.at<sdb_sst_summary>(i * sizeof(sdb_sst_summary));
-    }
+    bind(c->sst_data.at<uint8_t>(0), c->sst_bloom.at<uint8_t>(0), c->sst_meta.at<uint8_t>(0));
     const uint64_t ews = sdb_encode_ssts_workspace_bytes((uint32_t)ns, batches.data(), params);
     if (!c->enc_ws.ensure(ews)) return SDB_DEVICE_ERROR;
     st = sdb_encode_ssts((uint32_t)ns, batches.data(), params, outs.data(), c->enc_ws.p, c->enc_ws.cap, stream);
@@ -341,7 +287,7 @@ sdb_status sdb_compactor_run(sdb_compactor *c, const sdb_run *runs, uint32_t nru
 
     // 1. merge + retention, sized with unbounded byte capacities, then emitted
     sdb_merged_out out{};
-    sdb_status st = merged_columns(c, total, &out);
+    sdb_status st = merged_columns_in(c->cols, total, &out);
     if (st) return st;
     const uint64_t mws = sdb_merge_runs_workspace_bytes(runs, nruns);
     if (!c->merge_ws.ensure(mws)) return SDB_DEVICE_ERROR;
@@ -365,11 +311,8 @@ sdb_status sdb_compactor_run(sdb_compactor *c, const sdb_run *runs, uint32_t nru
     if (!n) return hipStreamSynchronize(s) == hipSuccess ? SDB_OK : SDB_DEVICE_ERROR;
 
     // 2. cuts (and the byte offsets of every cut, to size the SSTs)
-    const uint64_t cws = sdb_sst_cuts_workspace_bytes(n, params);
-    const uint64_t o_num = 0, o_cut = 256, o_off = o_cut + al256(8 * (n + 2));
-    if (!c->cut_ws.ensure(cws) || !c->cuts.ensure(o_off + al256(16 * (n + 2)))) return SDB_DEVICE_ERROR;
-    uint64_t *d_num = c->cuts.at<uint64_t>(o_num), *d_cut = c->cuts.at<uint64_t>(o_cut);
-    uint64_t *d_off = c->cuts.at<uint64_t>(o_off);
+    uint64_t *d_num, *d_cut, *d_off;
+    if (!cut_buffers(c, n, params, &d_num, &d_cut, &d_off)) return SDB_DEVICE_ERROR;
     st = sdb_sst_cuts(&m, params, max_sst_size, d_cut, n + 1, d_num, c->cut_ws.p, c->cut_ws.cap, stream);
     if (st) return st;
     // the cut count, the cuts and their byte offsets in one synchronisation: every SST but the last holds
@@ -426,9 +369,10 @@ sdb_status sdb_compactor_run_ssts(sdb_compactor *c, const sdb_compaction_input *
     CxInputs in{};
     in.n = ninputs;
     in.nruns = nruns;
-    const uint64_t t_data = 0, t_boff = al256(8ull * ninputs), t_first = t_boff + al256(8ull * ninputs);
-    const uint64_t t_rblk = t_first + al256(8ull * (ninputs + 1)), t_rent = t_rblk + al256(8ull * (nruns + 1));
-    const uint64_t t_total = t_rent + al256(8ull * (nruns + 1));
+    Carver tc{nullptr, 0};  // the tables' offsets in pin_tab and in cx_tab
+    const uint64_t t_data = tc.bytes(8ull * ninputs), t_boff = tc.bytes(8ull * ninputs);
+    const uint64_t t_first = tc.bytes(8ull * (ninputs + 1)), t_rblk = tc.bytes(8ull * (nruns + 1));
+    const uint64_t t_rent = tc.bytes(8ull * (nruns + 1)), t_total = tc.off;
     // the previous job's upload and kernels may still read pin_tab / cx_tab (a job that failed early
     // returns without a synchronisation, and the caller may alternate streams)
     if (c->tab_ev_live && hipEventSynchronize(c->tab_ev) != hipSuccess) return SDB_DEVICE_ERROR;
@@ -438,11 +382,10 @@ sdb_status sdb_compactor_run_ssts(sdb_compactor *c, const sdb_compaction_input *
         return SDB_DEVICE_ERROR;
     }
     if (!c->pin_tab.ensure(t_total) || !c->cx_tab.ensure(t_total)) return SDB_DEVICE_ERROR;
-    uint8_t *th = static_cast<uint8_t *>(c->pin_tab.p);
-    const uint8_t **h_data = reinterpret_cast<const uint8_t **>(th + t_data);
-    const uint64_t **h_boff = reinterpret_cast<const uint64_t **>(th + t_boff);
-    uint64_t *h_first = reinterpret_cast<uint64_t *>(th + t_first), *h_rblk = reinterpret_cast<uint64_t *>(th + t_rblk);
-    uint64_t *h_rent = reinterpret_cast<uint64_t *>(th + t_rent);
+    const uint8_t **h_data = c->pin_tab.at<const uint8_t *>(t_data);
+    const uint64_t **h_boff = c->pin_tab.at<const uint64_t *>(t_boff);
+    uint64_t *h_first = c->pin_tab.at<uint64_t>(t_first), *h_rblk = c->pin_tab.at<uint64_t>(t_rblk);
+    uint64_t *h_rent = c->pin_tab.at<uint64_t>(t_rent);
     uint64_t E = 0, K = 0, V = 0, B = 0;
     uintptr_t base = ~(uintptr_t)0;
     for (uint32_t i = 0; i < ninputs; i++) {
@@ -475,7 +418,7 @@ sdb_status sdb_compactor_run_ssts(sdb_compactor *c, const sdb_compaction_input *
     }
     in.key_bytes = K;
     if (E >= (1ull << 31)) return SDB_LIMIT_EXCEEDED;
-    if (hipMemcpyAsync(c->cx_tab.p, th, t_total, hipMemcpyHostToDevice, s) != hipSuccess) return SDB_DEVICE_ERROR;
+    if (hipMemcpyAsync(c->cx_tab.p, c->pin_tab.p, t_total, hipMemcpyHostToDevice, s) != hipSuccess) return SDB_DEVICE_ERROR;
     struct TabRelease {  // on every return from here: everything enqueued so far precedes the event
         sdb_compactor *c;
         hipStream_t s;
@@ -488,32 +431,32 @@ sdb_status sdb_compactor_run_ssts(sdb_compactor *c, const sdb_compaction_input *
     in.run_entry = c->cx_tab.at<const uint64_t>(t_rent);
 
     // 1. decode every input block into one columnar output (run r = entries [run_entry[r], run_entry[r+1]))
-    const uint64_t o_bs = 0, o_be = o_bs + al256(8 * (B + 1)), o_bes = o_be + al256(8 * (B + 1));
-    const uint64_t o_ka = o_bes + al256(8 * (B + 2)), o_ko = o_ka + al256(K + 64);
-    const uint64_t o_vo = o_ko + al256(8 * (E + 1)), o_vl = o_vo + al256(8 * (E + 1));
-    const uint64_t o_sq = o_vl + al256(4 * (E + 1)), o_fl = o_sq + al256(8 * (E + 1));
-    const uint64_t o_ct = o_fl + al256(E + 1), o_et = o_ct + al256(8 * (E + 1)), o_bad = o_et + al256(8 * (E + 1));
-    const uint64_t o_ds = o_bad + al256(4 * 16), o_gate = o_ds + al256(sizeof(sdb_decode_summary));
-    const uint64_t dec_bytes = o_gate + 256;
-    const uint64_t dws = sdb_decode_workspace_bytes(B);
-    if (!c->dec.ensure(dec_bytes) || !c->dec_ws.ensure(dws)) return SDB_DEVICE_ERROR;
-    uint64_t *bstart = c->dec.at<uint64_t>(o_bs), *bend = c->dec.at<uint64_t>(o_be);
+    uint64_t *bstart = nullptr, *bend = nullptr;
+    unsigned long long *gate = nullptr;
     sdb_decoded_out dout{};
-    dout.block_entry_start = c->dec.at<uint64_t>(o_bes);
-    dout.key_arena = c->dec.at<uint8_t>(o_ka);
     dout.key_arena_cap = K;
-    dout.key_off = c->dec.at<uint64_t>(o_ko);
-    dout.val_off = c->dec.at<uint64_t>(o_vo);
-    dout.val_len = c->dec.at<uint32_t>(o_vl);
-    dout.seq = c->dec.at<uint64_t>(o_sq);
-    dout.flags = c->dec.at<uint8_t>(o_fl);
-    dout.create_ts = c->dec.at<int64_t>(o_ct);
-    dout.expire_ts = c->dec.at<int64_t>(o_et);
     dout.cap_entries = E;
-    dout.bad_block = c->dec.at<uint32_t>(o_bad);
     dout.bad_cap = 16;
-    dout.summary = c->dec.at<sdb_decode_summary>(o_ds);
-    unsigned long long *gate = c->dec.at<unsigned long long>(o_gate);
+    auto bind_dec = [&](uint8_t *base) {  // sizes (NULL) or binds c->dec
+        Carver k{base, 0};
+        k.take(bstart, B + 1);
+        k.take(bend, B + 1);
+        k.take(dout.block_entry_start, B + 2);
+        k.take(dout.key_arena, K + 64);
+        k.take(dout.key_off, E + 1);
+        k.take(dout.val_off, E + 1);
+        k.take(dout.val_len, E + 1);
+        k.take(dout.seq, E + 1);
+        k.take(dout.flags, E + 1);
+        k.take(dout.create_ts, E + 1);
+        k.take(dout.expire_ts, E + 1);
+        k.take(dout.bad_block, dout.bad_cap);
+        k.take(dout.summary, 1);
+        k.take(gate, 1);
+        return k.off;
+    };
+    if (!c->dec.ensure(bind_dec(nullptr)) || !c->dec_ws.ensure(sdb_decode_workspace_bytes(B))) return SDB_DEVICE_ERROR;
+    bind_dec(c->dec.at<uint8_t>(0));
     const uint8_t *arena = reinterpret_cast<const uint8_t *>(base);
     if (launch_cx_blocks(in, bstart, bend, s) != hipSuccess) return SDB_DEVICE_ERROR;
     // fail-fast (a failing block fails the job anyway, as load_iterators' reads would): checksums in the emit pass
@@ -543,7 +486,7 @@ sdb_status sdb_compactor_run_ssts(sdb_compactor *c, const sdb_compaction_input *
     // 2. merge + retention + emit into buffers of the declared sizes (retention only drops entries and
     //    values), gated on the decode; the stream padded to E entries for the cut walk
     sdb_merged_out out{};
-    st = merged_columns(c, E, &out);
+    st = merged_columns_in(c->cols, E, &out);
     if (st) return st;
     if (!c->keys.ensure(K + 16) || !c->vals.ensure(V + 16)) return SDB_DEVICE_ERROR;
     out.key_bytes = c->keys.at<uint8_t>(0);
@@ -569,11 +512,8 @@ sdb_status sdb_compactor_run_ssts(sdb_compactor *c, const sdb_compaction_input *
 
     // cuts over the padded stream, ending at the merged count; merged summary, cut count, cuts and their
     // byte offsets read back in one synchronisation
-    const uint64_t cws = sdb_sst_cuts_workspace_bytes(E, params);
-    const uint64_t o_num = 0, o_cut = 256, o_off = o_cut + al256(8 * (E + 2));
-    if (!c->cut_ws.ensure(cws) || !c->cuts.ensure(o_off + al256(16 * (E + 2)))) return SDB_DEVICE_ERROR;
-    uint64_t *d_num = c->cuts.at<uint64_t>(o_num), *d_cut = c->cuts.at<uint64_t>(o_cut);
-    uint64_t *d_off = c->cuts.at<uint64_t>(o_off);
+    uint64_t *d_num, *d_cut, *d_off;
+    if (!cut_buffers(c, E, params, &d_num, &d_cut, &d_off)) return SDB_DEVICE_ERROR;
     if (E) {
         st = sst_cuts_padded(&padded, params, max_sst_size, d_cut, E + 1, d_num, c->cut_ws.p, c->cut_ws.cap, s,
                              &out.summary->num_out);
@@ -581,17 +521,17 @@ sdb_status sdb_compactor_run_ssts(sdb_compactor *c, const sdb_compaction_input *
         if (launch_cut_offsets(d_cut, d_num, out.key_off, out.val_off, d_off, s) != hipSuccess) return SDB_DEVICE_ERROR;
     }
     const uint64_t g = max_sst_size ? std::min<uint64_t>(E, 2 + (K + V + 64 * E) / max_sst_size) : E;
-    const uint64_t h_sum = 0, h_num = al256(sizeof(sdb_merge_summary)), h_cut = h_num + 256;
-    const uint64_t h_off = h_cut + al256(8 * (g + 2)), h_total = h_off + al256(16 * (g + 2));
-    if (!c->pin.ensure(h_total)) return SDB_DEVICE_ERROR;
-    uint8_t *hp = static_cast<uint8_t *>(c->pin.p);
-    sdb_merge_summary *hsum = reinterpret_cast<sdb_merge_summary *>(hp + h_sum);
-    uint64_t *hnum = reinterpret_cast<uint64_t *>(hp + h_num);
+    Carver hc{nullptr, 0};  // the readback in c->pin: the merged summary, then the first g cuts
+    const uint64_t h_sum = hc.bytes(sizeof(sdb_merge_summary));
+    const CutLayout hl = cut_layout(hc, g);
+    if (!c->pin.ensure(hc.off)) return SDB_DEVICE_ERROR;
+    sdb_merge_summary *hsum = c->pin.at<sdb_merge_summary>(h_sum);
+    uint64_t *hnum = c->pin.at<uint64_t>(hl.num), *hcut = c->pin.at<uint64_t>(hl.cut), *hoff = c->pin.at<uint64_t>(hl.off);
     *hnum = 0;
     if (hipMemcpyAsync(hsum, out.summary, sizeof(sdb_merge_summary), hipMemcpyDeviceToHost, s) != hipSuccess ||
         (E && (hipMemcpyAsync(hnum, d_num, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
-               hipMemcpyAsync(hp + h_cut, d_cut, 8 * (g + 1), hipMemcpyDeviceToHost, s) != hipSuccess ||
-               hipMemcpyAsync(hp + h_off, d_off, 16 * (g + 1), hipMemcpyDeviceToHost, s) != hipSuccess)) ||
+               hipMemcpyAsync(hcut, d_cut, 8 * (g + 1), hipMemcpyDeviceToHost, s) != hipSuccess ||
+               hipMemcpyAsync(hoff, d_off, 16 * (g + 1), hipMemcpyDeviceToHost, s) != hipSuccess)) ||
         hipStreamSynchronize(s) != hipSuccess)
         return SDB_DEVICE_ERROR;
     c->msum = *hsum;
@@ -607,8 +547,8 @@ sdb_status sdb_compactor_run_ssts(sdb_compactor *c, const sdb_compaction_input *
             hipMemcpy(off.data(), d_off, 16 * (ns + 1), hipMemcpyDeviceToHost) != hipSuccess)
             return SDB_DEVICE_ERROR;
     } else {
-        memcpy(cut.data(), hp + h_cut, 8 * (ns + 1));
-        memcpy(off.data(), hp + h_off, 16 * (ns + 1));
+        memcpy(cut.data(), hcut, 8 * (ns + 1));
+        memcpy(off.data(), hoff, 16 * (ns + 1));
     }
 
     // 3. encode every output SST

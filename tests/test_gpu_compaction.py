@@ -179,10 +179,10 @@ def sst_view(d):
                                  index_key_len=d["index_key_len"], block_stats=d["block_stats"], bloom=d["bloom"])
 
 
-def compact_both(rt, runs, ret, prm_kw, max_sst, druns=None):
+def compact_both(rt, runs, ret, prm_kw, max_sst, druns=None, comp=None):
     import torch
     druns = druns or [rt.DeviceRun.from_host(r) for r in runs]
-    comp = rt.Compactor()
+    comp = comp or rt.Compactor()
     st, ns = comp.run(druns, ret, rt.params(**prm_kw), max_sst)
     torch.cuda.synchronize()
     merged, msum, cuts, ssts = O.compact(runs, ret, O.params(**prm_kw), max_sst)
@@ -205,6 +205,22 @@ def test_compactor_big(rt, version):
     comp, ssts = compact_both(rt, runs, O.retention(min_seq=100000, compaction_start_ts=1000, filter_tombstone=True),
                               dict(sst_version=version, block_size=4096, bloom_bits_per_key=10), 2 << 20)
     assert len(ssts) >= 3
+    comp.close()
+
+
+def test_compactor_handle_across_job_sizes(rt):
+    """One handle, jobs of changing size: its buffers grow for the larger job, are reused as they are for the
+    smaller one after it (whose outputs then live in the larger buffers), and serve a run_ssts job after that;
+    every job bit-exact with the oracle."""
+    small, big = big_runs(41, 300, 3), big_runs(42, 6000, 4)
+    ret = O.retention(min_seq=200, compaction_start_ts=1000, filter_tombstone=True)
+    prm_kw = dict(block_size=4096, bloom_bits_per_key=10)
+    comp = rt.Compactor()
+    for runs, max_sst in ((small, 8000), (big, 100000), (small, 8000)):
+        _, ssts = compact_both(rt, runs, ret, prm_kw, max_sst, comp=comp)
+        assert len(ssts) >= 2
+    st, ns, _ = compact_ssts_both(rt, big, ret, prm_kw, 100000, comp=comp)
+    assert st == 0 and ns >= 2
     comp.close()
 
 
@@ -301,12 +317,14 @@ def encoded_inputs(rt, runs, prm_kw, split=1):
     return inputs, run_start, ref_runs
 
 
-def compact_ssts_both(rt, runs, ret, prm_kw, max_sst, split=1, version=2, out_kw=None):
-    """sdb_compactor_run_ssts on the runs' encoded SSTs vs O.compact on the runs."""
+def compact_ssts_both(rt, runs, ret, prm_kw, max_sst, split=1, version=2, out_kw=None, comp=None):
+    """sdb_compactor_run_ssts on the runs' encoded SSTs vs O.compact on the runs (on `comp`, left open, or on a
+    handle of its own)."""
     import torch
     inputs, run_start, runs = encoded_inputs(rt, runs, dict(prm_kw, sst_version=version), split)
     out_kw = out_kw or prm_kw
-    comp = rt.Compactor()
+    own = comp is None
+    comp = comp or rt.Compactor()
     st, ns = comp.run_ssts(inputs, ret, rt.params(**out_kw), max_sst, input_version=version,
                            run_start=run_start if split > 1 else None)
     torch.cuda.synchronize()
@@ -320,7 +338,8 @@ def compact_ssts_both(rt, runs, ret, prm_kw, max_sst, split=1, version=2, out_kw
             d = comp.sst(i)
             assert (d["entry_start"], d["entry_end"]) == (cuts[i], cuts[i + 1])
             assert_same(ref, sst_view(d), "sst %d" % i)
-    comp.close()
+    if own:
+        comp.close()
     return st, ns, inputs
 
 

@@ -310,3 +310,25 @@ def test_encode_host_many_grows_output_slots(rt):
         for i, (b, g) in enumerate(zip(hosts, got)):
             assert_same(O.encode_sst(b, O.params(**prm)), g, "grow %d/%d" % (i, len(sizes)))
     enc.close()
+
+
+def test_encode_host_many_edge_shapes(rt):
+    """One encoder: no batches; an empty batch between two others (its summary, no blocks); a batch that fails
+    (an empty key at entry 5) between two that do not, whose results stay the oracle's byte for byte."""
+    from .test_gpu_parity import ent
+    prm = dict(block_size=4096, sst_version=2, bloom_bits_per_key=10)
+    enc = rt.Encoder(rt.params(**prm))
+    assert enc.encode_many([]) == [] and enc.last_status == 0
+    empty = Batch.from_entries([])
+    bad = Batch.from_entries([ent(b"" if i == 5 else b"k%04d" % i, b"v", i) for i in range(20)])
+    for mid in (empty, bad):
+        hosts = [datasets.d1(sst_index=0, n=3000), mid, datasets.d1(sst_index=2, n=700)]
+        refs = [O.encode_sst(b, O.params(**prm)) for b in hosts]
+        got = enc.encode_many(hosts)
+        assert enc.last_status == refs[1].status
+        for i, (ref, g) in enumerate(zip(refs, got)):
+            assert_same(ref, g, "edge[%d]" % i)
+        assert got[1].num_blocks == 0 and len(got[1].data) == 0
+    assert refs[1].status == _abi.SDB_EMPTY_KEY and refs[1].summary.first_error_entry == 5
+    assert got[1].summary["first_error_entry"] == 5
+    enc.close()

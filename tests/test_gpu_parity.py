@@ -284,6 +284,19 @@ def test_decode_large_blocks_and_flags(rt):
     assert_decode_same(O.decode_blocks(arr, off, 2), dec.decode(arr, off, 2), "flags")
 
 
+def test_decode_capacity_retry_then_shrink(rt):
+    """600 keys of 600 bytes sharing a 590-byte prefix: 34,353 encoded bytes in 9 blocks restore to 360,000 key
+    bytes, past the decoder's first key capacity (4 x 34,353 + 4096 = 141,508), so its second attempt runs in
+    regrown buffers; then a small batch on the same handle, in the buffers the large one left."""
+    es = [ent(b"p" * 590 + b"%010d" % i, b"v", i) for i in range(600)]
+    enc = O.encode_sst(Batch.from_entries(es), O.params())
+    assert len(enc.data) == 34353 and len(enc.block_off) - 1 == 9
+    dec = rt.Decoder()
+    assert_decode_same(O.decode_blocks(enc.data, enc.block_off, 2), dec.decode(enc.data, enc.block_off, 2), "retry")
+    enc = O.encode_sst(datasets.d1(n=40), O.params())
+    assert_decode_same(O.decode_blocks(enc.data, enc.block_off, 2), dec.decode(enc.data, enc.block_off, 2), "shrink")
+
+
 def test_device_round_trip_full_d1(rt):
     """Encode on the GPU, decode on the GPU: size-independent round-trip property at full size."""
     b = datasets.d1()
