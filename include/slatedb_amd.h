@@ -93,7 +93,9 @@ typedef struct sdb_kv_batch {
     uint64_t n;
     const uint8_t *key_bytes;
     const uint64_t *key_off;    /* n+1 */
-    const uint8_t *val_bytes;   /* tombstones: value bytes are ignored (treated as empty) */
+    const uint8_t *val_bytes;   /* tombstones: value bytes are ignored (treated as empty); a batch should
+                                   not carry any: blocks near a tombstone whose val_off range is not
+                                   empty are assembled by the general, slower path */
     const uint64_t *val_off;    /* n+1 */
     const uint8_t *kind;        /* n; NULL = all SDB_KIND_VALUE */
     const uint64_t *seq;        /* n; NULL = all 0 */

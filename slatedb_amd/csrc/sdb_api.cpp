@@ -757,3 +757,17 @@ extern "C" uint64_t sdb_diag_bloom_slots(uint64_t n, const sdb_sst_params *p, ui
     *cap = bloom_slot_cap(pl);
     return sdb::encode_ws_layout(n, nullptr);
 }
+
+// Diagnostics: where sdb_encode_sst's workspace keeps the encode's routing state: byte offsets of the u32
+// slow_count (workgroup-path blocks), big_count (piece-path blocks), wmax (longest candidate block) and
+// mode (1: table composition, 0: the serial walk).  k_anchor zeroes the counters, k_blocks fills them and
+// nothing resets them afterwards, so they are readable once the encode's stream is synchronised.
+extern "C" void sdb_diag_encode_state(uint64_t n, uint64_t *slow_count, uint64_t *big_count, uint64_t *wmax,
+                                      uint64_t *mode) {
+    uint32_t wso[sdb::kWsFields];
+    sdb::encode_ws_layout(n, wso);
+    *slow_count = (uint64_t)wso[sdb::kWs_slow_count] << 8;
+    *big_count = (uint64_t)wso[sdb::kWs_big_count] << 8;
+    *wmax = (uint64_t)wso[sdb::kWs_wmax] << 8;
+    *mode = (uint64_t)wso[sdb::kWs_mode] << 8;
+}

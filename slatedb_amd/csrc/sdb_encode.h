@@ -71,8 +71,11 @@ struct BlockDesc {  // one per block, written by k_enum, streamed by k_emit (56 
     uint32_t s, e;        // entries [s, e)
     uint64_t off;         // byte offset of the block in the data section
     uint64_t vs, ve, ks, ke;  // value / key byte ranges of the block
-    uint32_t bb, pad;     // encoded bytes incl. CRC
+    uint32_t bb, route;   // encoded bytes incl. CRC; the assembler that takes the block (block_route)
 };
+enum : uint32_t { kRouteImage = 0, kRouteWorkgroup = 1, kRoutePieces = 2 };
+// huge_part, per chunk: a row too large for a piece; a tombstone whose ignored val_off range is not empty
+enum : uint32_t { kChunkHuge = 1, kChunkCarry = 2 };
 
 struct EncodeArgs {
     // batch (device)
@@ -114,7 +117,7 @@ struct EncodeArgs {
     uint32_t *big_list;
     BlockDesc *desc;
     uint64_t *stat_part;    // per k_facts workgroup: raw key, raw val, puts, deletes, merges
-    uint32_t *huge_part;    // per k_facts workgroup (= chunk): 1 if a row is too large for k_emit's piece path
+    uint32_t *huge_part;    // per k_facts workgroup (= chunk): kChunkHuge | kChunkCarry
     uint32_t *wmax_part;    // per chunk: longest candidate block (entries)
     unsigned long long *err_part;  // per k_facts workgroup: min (entry << 8 | code) of the checks (~0: none)
     uint32_t *gtab_exit;    // per group of kGroup chunks, seg_look candidates: composed transfer table

@@ -276,6 +276,10 @@ __global__ __launch_bounds__(kFactsThreads, 8) void k_facts(SstSet P) {
     uint64_t rk = 0, rv = 0, c = 0;
     uint64_t err = ~0ull;
     bool huge = false;  // a row k_emit's piece path cannot stage (the block goes to the workgroup path)
+    // a tombstone whose val_off range is not empty: those bytes are ignored (slatedb_amd.h), but a block's
+    // LDS value stage is the contiguous range [val_off[s], val_off[e]) and a value is only safe in it at or
+    // below its image position (copy_spans), so no LDS path takes a block of such a chunk
+    bool carry = false;
     uint32_t hh[kFactsPerT], dd[kFactsPerT];
 #pragma unroll
     for (uint32_t r = 0; r < kFactsPerT; r++) {
@@ -312,6 +316,7 @@ __global__ __launch_bounds__(kFactsThreads, 8) void k_facts(SstSet P) {
                 err = ev < err ? ev : err;
             }
             huge |= x.s_r > kPieceRowMax || x.klen > kPieceKeyMax || x.vlen > kPieceValMax;
+            carry |= x.kind == SDB_KIND_TOMBSTONE && f.vo1 != f.vo0;
             rk += x.klen;
             rv += x.vlen;
             c += (uint64_t)(x.kind == SDB_KIND_VALUE) | ((uint64_t)(x.kind == SDB_KIND_TOMBSTONE) << 20) |
@@ -332,8 +337,8 @@ __global__ __launch_bounds__(kFactsThreads, 8) void k_facts(SstSet P) {
         s_part[w][4] = (c >> 40) & 0xFFFFF;
         s_err[w] = err;
     }
-    const bool wh = __ballot(huge) != 0;
-    if (lane == 0) s_huge[w] = wh ? 1u : 0u;
+    const bool wh = __ballot(huge) != 0, wc = __ballot(carry) != 0;
+    if (lane == 0) s_huge[w] = (wh ? kChunkHuge : 0u) | (wc ? kChunkCarry : 0u);
     __syncthreads();
     if (tid < 5) {
         uint64_t t = 0;
@@ -958,14 +963,22 @@ SDB_DEV void wave_store(uint8_t *gdst, const uint8_t *img, uint64_t len) {
     }
 }
 
-// Blocks k_emit assembles in its per-wave LDS image; the rest take the workgroup slow path.
-SDB_DEV bool emit_fast(const BlockDesc &d) {
+// The assembler of a block (BlockDesc::route), decided once, by the kernel that writes the descriptor:
+// k_emit's per-wave LDS image when the block's rows, bytes and staged value / key granules fit it; else
+// k_emit_big's pieces; the workgroup path when a chunk the block touches holds a row too large for a
+// piece, or (image-sized blocks too) a tombstone carrying ignored bytes, which no LDS stage can skip.
+SDB_DEV uint32_t block_route(const EncodeArgs &a, const BlockDesc &d) {
     const uint32_t ne = d.e - d.s;
     const uint64_t va = d.vs & ~15ull, ka = d.ks & ~15ull;
     const uint32_t nv16 = d.ve > d.vs ? (uint32_t)((d.ve - va + 15) >> 4) : 0;
     const uint32_t nk16 = (uint32_t)((d.ke - ka + 15) >> 4);
-    return ne <= 64 && d.bb + 64 <= kImgCap && nv16 <= kStageCap / 16 && nk16 <= kKeyStageCap / 16;
+    const bool fits = ne <= 64 && d.bb + 64 <= kImgCap && nv16 <= kStageCap / 16 && nk16 <= kKeyStageCap / 16;
+    uint32_t h = 0;
+    for (uint32_t q = d.s / kChunk; q <= (d.e - 1) / kChunk; q++) h |= a.huge_part[q];
+    if (fits && !(h & kChunkCarry)) return kRouteImage;
+    return h ? kRouteWorkgroup : kRoutePieces;
 }
+SDB_DEV bool emit_fast(const BlockDesc &d) { return d.route == kRouteImage; }
 
 // ------------------------------------------------------------------------------------------------
 // K5a: enumerate the blocks of each chunk (binary lifting over next()) -> BlockMeta offsets and the
@@ -1206,19 +1219,9 @@ __global__ __launch_bounds__(kEnumThreads) void k_enum(SstSet P) {
         d.ks = a.key_off[s];
         d.ke = a.key_off[e];
         d.bb = bl_b[t];
-        d.pad = 0;
-        if (!emit_fast(d)) {
-            // too big for one wave image: k_emit's piece path, unless a row is too large for a piece
-            // (then the workgroup path, marked pad = 1)
-            uint32_t h = 0;
-            for (uint64_t q = s / kChunk; q <= (e - 1) / kChunk; q++) h |= a.huge_part[q];
-            if (h) {
-                d.pad = 1;
-                a.slow_list[atomicAdd(a.slow_count, 1u)] = blk;
-            } else {
-                big_local[atomicAdd(&s_nbig, 1u)] = blk;  // LDS: one global reservation per chunk below
-            }
-        }
+        d.route = block_route(a, d);
+        if (d.route == kRouteWorkgroup) a.slow_list[atomicAdd(a.slow_count, 1u)] = blk;
+        if (d.route == kRoutePieces) big_local[atomicAdd(&s_nbig, 1u)] = blk;  // LDS: one global reservation per chunk below
         a.desc[blk] = d;
     }
     __syncthreads();
@@ -1692,19 +1695,9 @@ __global__ __launch_bounds__(kBlkThreads) void k_blocks(SstSet P) {
             d.ks = a.key_off[s];
             d.ke = a.key_off[e];
             d.bb = bb;
-            d.pad = 0;
-            if (!emit_fast(d)) {
-                // too big for one wave image: k_emit's piece path, unless a row is too large for a piece
-                // (then the workgroup path, marked pad = 1)
-                uint32_t h = 0;
-                for (uint64_t q = s / kChunk; q <= (e - 1) / kChunk; q++) h |= a.huge_part[q];
-                if (h) {
-                    d.pad = 1;
-                    a.slow_list[atomicAdd(a.slow_count, 1u)] = blk;
-                } else {
-                    s_big[atomicAdd(&s_nbig, 1u)] = blk;  // one global reservation per batch below
-                }
-            }
+            d.route = block_route(a, d);
+            if (d.route == kRouteWorkgroup) a.slow_list[atomicAdd(a.slow_count, 1u)] = blk;
+            if (d.route == kRoutePieces) s_big[atomicAdd(&s_nbig, 1u)] = blk;  // one global reservation per batch below
             a.desc[blk] = d;
         }
         __syncthreads();
@@ -1959,7 +1952,7 @@ SDB_DEV BlockDesc desc_from_lanes(uint32_t dv) {  // lanes 0..13 hold the 14 dwo
     d.ks = w[8] | ((uint64_t)w[9] << 32);
     d.ke = w[10] | ((uint64_t)w[11] << 32);
     d.bb = w[12];
-    d.pad = w[13];
+    d.route = w[13];
     return d;
 }
 static_assert(sizeof(BlockDesc) == 56, "BlockDesc is 14 dwords");
