@@ -771,3 +771,22 @@ extern "C" void sdb_diag_encode_state(uint64_t n, uint64_t *slow_count, uint64_t
     *wmax = (uint64_t)wso[sdb::kWs_wmax] << 8;
     *mode = (uint64_t)wso[sdb::kWs_mode] << 8;
 }
+
+// Diagnostics: where sdb_merge_runs' workspace keeps the merge's state for `total` input entries: byte offsets,
+// from the workspace pointer rounded up to 256 bytes, of lcp0 (u32 L0), pfx (u64 per global entry), perm (u64 per
+// merged position), dec (u8 per merged position), tile_sum (3 u64 per tile) and bound (k_mg_bounds: 2 x nruns
+// u64 per 256 entries), as merge_bind carves them.  Nothing resets them after the merge, so they are readable
+// once the merge's stream is synchronised.
+extern "C" void sdb_diag_merge_state(uint64_t total, uint64_t *lcp0, uint64_t *pfx, uint64_t *perm, uint64_t *dec,
+                                     uint64_t *tile_sum, uint64_t *bound) {
+    sdb::MergeArgs a{};
+    a.total = total;
+    uint8_t *const base = (uint8_t *)(uintptr_t)256;  // merge_bind binds nothing at a null base
+    sdb::merge_bind(a, base);
+    *lcp0 = (uint64_t)((uint8_t *)a.lcp0 - base);
+    *pfx = (uint64_t)((uint8_t *)a.pfx - base);
+    *perm = (uint64_t)((uint8_t *)a.perm - base);
+    *dec = (uint64_t)((uint8_t *)a.dec - base);
+    *tile_sum = (uint64_t)((uint8_t *)a.tile_sum - base);
+    *bound = (uint64_t)((uint8_t *)a.bound - base);
+}

@@ -96,6 +96,28 @@ def test_bounds_and_argument_checks(lib):
     assert lib.sdb_decode_workspace_bytes(100) > 100 * 40
 
 
+def test_workspace_diagnostics_are_exported_and_inside_the_workspace(lib):
+    """sdb_diag_encode_state / sdb_diag_merge_state (host only, not in the header): exported, and the offsets they
+    report are distinct, 256-byte aligned and inside the workspace the sizing functions ask for."""
+    out = subprocess.check_output(["nm", "-D", "--defined-only", os.path.join(ROOT, "slatedb_amd", "libslatedb_amd.so")]).decode()
+    exported = set(re.findall(r" T (sdb_\w+)", out))
+    assert {"sdb_diag_encode_state", "sdb_diag_merge_state"} <= exported
+    cd = C.CDLL(os.path.join(ROOT, "slatedb_amd", "libslatedb_amd.so"))
+    cd.sdb_diag_merge_state.restype = None
+    cd.sdb_diag_merge_state.argtypes = [C.c_uint64] + [C.c_void_p] * 6
+    for total in (0, 1, 255, 256, 257, 1024, 1025, 540000):
+        off = [C.c_uint64() for _ in range(6)]
+        cd.sdb_diag_merge_state(total, *[C.byref(o) for o in off])
+        lcp0, pfx, perm, dec, tile_sum, bound = (o.value for o in off)
+        run = (_abi.Run * 1)(_abi.Run(total))
+        size = lib.sdb_merge_runs_workspace_bytes(run, 1)
+        assert pfx == 0 and pfx < perm < dec < tile_sum < bound < lcp0 < size - 256, (total, size)
+        assert all(o % 256 == 0 for o in (perm, dec, tile_sum, bound, lcp0))
+        assert perm - pfx >= 8 * total and dec - perm >= 8 * total and tile_sum - dec >= total
+        assert bound - tile_sum >= 24 * ((total + 1023) // 1024)
+        assert lcp0 - bound >= 8 * 2 * _abi.MAX_RUNS * ((total + 255) // 256)
+
+
 def test_no_device_fails_loudly(lib):
     """Without a GPU every compute entry point reports DEVICE_ERROR (no CPU fallback)."""
     if lib.sdb_device_count() > 0:
