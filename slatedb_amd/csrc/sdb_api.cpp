@@ -181,7 +181,7 @@ SstSlot plan_slot(const sdb_kv_batch *b, const sdb_sst_params *p, const sdb_sst_
     s.nchunks = (uint32_t)((n + kChunk - 1) / kChunk);
     s.nfacts = (uint32_t)((n + kFactsEntries - 1) / kFactsEntries);
     encode_ws_layout(n, s.wso);
-    {   // chunks per group: about sqrt(nchunks), so k_enum walks <= ~2 sqrt(nchunks) tables
+    {   // chunks per group: about sqrt(nchunks), so the chain walk (k_anchor, k_cut) takes ~2-3 sqrt(nchunks) table steps
         uint32_t g = 16;
         while ((uint64_t)g * g < s.nchunks) g++;
         s.group = g;

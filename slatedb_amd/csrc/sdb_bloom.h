@@ -108,7 +108,7 @@ SDB_DEV void for_each_probe(uint64_t hash, uint32_t k, uint32_t m, F f) {
 //         probes, an LDS counting sort by slice.  The run of slice s goes to the tile's own slot
 //         (s, tile) and its length to count[tile][s]: fixed places, so there is no global atomic
 //         and nothing to initialise between calls.
-//   fill  one workgroup per slice of 2^sb bits (k_bloom_fill, or k_enum's bloom role): every
+//   fill  one workgroup per slice of 2^sb bits (k_bloom_fill, or k_seg's bloom role): every
 //         tile's slot of the slice, ORed into an LDS copy of the slice, written with plain stores.
 // A slot holds the expected run + 6 sigma + 16 probes; a longer run (adversarial key sets only) is
 // recorded as kSlotOverflow and the fill rebuilds that slice from every key.  Deterministic (an OR).
@@ -396,7 +396,7 @@ SDB_DEV void bloom_bin_tile(uint32_t tile, const uint8_t *__restrict__ key_bytes
     bloom_bin_core<kBinKeysPerThread>(tile, hh, dd, nk, pl, q, lds);
 }
 
-// One bitmap slice (k_bloom_fill, or the bloom role of k_enum).  lds: bloom_fill_lds(pl) bytes of
+// One bitmap slice (k_bloom_fill, or the bloom role of k_seg).  lds: bloom_fill_lds(pl) bytes of
 // dynamic LDS (the slice's bits, then the run length of every tile).
 SDB_DEV void bloom_fill_slice(uint32_t s, const uint8_t *__restrict__ key_bytes, const uint64_t *__restrict__ key_off,
                               uint64_t n, const BloomPlan &pl, const BloomSlots &q, uint8_t *bitmap, uint64_t bytes,

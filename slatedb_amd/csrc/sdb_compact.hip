@@ -786,7 +786,7 @@ __global__ __launch_bounds__(kCutThreads) void k_cut(SstSet P, uint64_t max_sst,
     // stream, the one that reaches it is the tail block (never counted), and a chunk / group skip past it
     // adds no cut in either stream
     const uint64_t n = n_real ? *n_real : a.n;
-    const bool fast = *a.mode >= 1;  // 1 and 2: the chunk / group tables describe the chain
+    const bool fast = *a.mode >= 1;  // the chunk / group tables describe the chain
     const uint32_t W = *a.wmax, G = a.group, L = a.seg_look;
     const uint32_t K = a.nchunks, ngroups = (K + G - 1) / G;
     const bool glds = fast && (uint64_t)ngroups * W <= kCutTab, clds = fast && (uint64_t)G * W <= kCutTab;
@@ -878,7 +878,7 @@ __global__ __launch_bounds__(kCutThreads) void k_cut(SstSet P, uint64_t max_sst,
             for (uint32_t x = tid; x < nk * W; x += kCutThreads) {
                 const uint32_t q = x / W, o = x - q * W;
                 const uint64_t kk = k0 + q, ccs = kk * kChunk, cce = ccs + kChunk < n ? ccs + kChunk : n;
-                // candidates past a short last chunk were never written: no table entry
+                // not tab_clamp (sdb_encode.hip): the raw exit; 0xFFFFFFFF (far, or no entry) = step block by block
                 s_cx[x] = ccs + o < cce ? a.tab_exit[kk * L + o] : 0xFFFFFFFFu;
                 s_cb[x] = ccs + o < cce ? a.tab_bytes[kk * L + o] : 0;
             }

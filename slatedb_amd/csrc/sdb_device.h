@@ -13,8 +13,6 @@
 
 namespace sdb {
 
-constexpr int kWave = 64;
-
 // ------------------------------------------------------------------------------------------------
 // CRC-32/ISO-HDLC (crc32fast 1.5, reflected poly 0xEDB88320), tables built at compile time.
 // ------------------------------------------------------------------------------------------------
@@ -94,28 +92,6 @@ constexpr CrcSegShift make_seg_shift() {
 }
 static_assert(gf_mul_c(kXInv, 1u << 30) == (1u << 31), "x * x^-1 == 1");
 
-// seg_mul[k][b][v] = x^(8*64*k) * (v << 8b) mod P: multiplies a CRC by the weight of k trailing
-// 64-byte segments with 4 byte-table lookups.  Built by linearity from the 8 single-bit values.
-struct CrcSegMul {
-    uint32_t t[kSegShifts][4][256];
-};
-constexpr CrcSegMul make_seg_mul() {
-    CrcSegMul r{};
-    for (int k = 0; k < kSegShifts; k++) {
-        uint32_t K = x8n_c(64ull * k);
-        for (int b = 0; b < 4; b++) {
-            uint32_t basis[8] = {};
-            for (int i = 0; i < 8; i++) basis[i] = gf_mul_c(K, 1u << (8 * b + i));
-            r.t[k][b][0] = 0;
-            for (int v = 1; v < 256; v++) {
-                int lo = __builtin_ctz(v);
-                r.t[k][b][v] = r.t[k][b][v & (v - 1)] ^ basis[lo];
-            }
-        }
-    }
-    return r;
-}
-
 // mul256[b][v] = x^(8*32) * (v << 8b) mod P: shifts a CRC past 32 zero bytes (4 byte-table lookups).
 struct CrcMul256 {
     uint32_t t[4][256];
@@ -167,11 +143,6 @@ constexpr CrcX8 make_x8() {
     return r;
 }
 static __constant__ CrcX8 c_x8 = make_x8();
-static __device__ const CrcSegMul g_seg_mul = make_seg_mul();
-SDB_DEV uint32_t seg_shift_mul(uint32_t k, uint32_t c) {
-    const uint32_t(*t)[256] = g_seg_mul.t[k];
-    return t[0][c & 0xFF] ^ t[1][(c >> 8) & 0xFF] ^ t[2][(c >> 16) & 0xFF] ^ t[3][c >> 24];
-}
 
 // Runtime GF(2) multiply (branch-free, 32 steps).
 SDB_DEV uint32_t gf_mul(uint32_t a, uint32_t b) {
@@ -383,23 +354,9 @@ SDB_DEV uint32_t wave_crc32_lds(const uint8_t *msg, uint32_t len, const uint32_t
     return wave_crc_raw_lds(msg, len, tab, true) ^ 0xFFFFFFFFu;
 }
 
-// Raw CRC of one 64-byte segment held in registers (16 little-endian dwords, message order).
-SDB_DEV uint32_t crc_seg64(const uint32_t (&w)[16], const uint32_t (*tab)[256]) {
-    uint32_t c = 0;
-#pragma unroll
-    for (int q = 0; q < 8; q++) c = crc_slice8(c, w[2 * q], w[2 * q + 1], tab);
-    return c;
-}
-
-// LDS / global address-space helpers for LDS-DMA (global_load_lds_dword).
+// The LDS byte address of a pointer into LDS.
 typedef __attribute__((address_space(3))) uint8_t lds_u8;
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) void glb_void;
 SDB_DEV uint32_t lds_addr(const void *p) { return (uint32_t)(uintptr_t)(const lds_u8 *)p; }
-// dword at global `src` (any byte alignment) -> LDS byte address lds_base + 4 * lane
-SDB_DEV void glds_dword(const uint8_t *src, uint32_t lds_base) {
-    __builtin_amdgcn_global_load_lds((glb_void *)src, (lds_void *)(uintptr_t)lds_base, 4, 0, 0);
-}
 
 // Block-wide exclusive scan of u64 (blockDim.x <= 1024).  s_w: >= 17 u64 of LDS.
 SDB_DEV uint64_t block_excl_scan_u64(uint64_t v, uint64_t *s_w, uint64_t *total) {

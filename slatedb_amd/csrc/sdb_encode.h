@@ -34,8 +34,6 @@ constexpr uint32_t kFactsThreads = 1024;      // k_facts: a chunk (= a fused blo
 constexpr uint32_t kFactsPerT = 2;            //   entries per thread
 constexpr uint32_t kFactsEntries = kFactsThreads * kFactsPerT;
 constexpr uint32_t kSegLds = (2 * kSegSpan + 4) * 4 + kChunk * 6;  // 36 KiB: four workgroups per CU
-constexpr uint32_t kSegLdsMax = 64 * 1024;          // k_seg's LDS with the fused bloom binning
-constexpr uint32_t kHashPerT = kChunk / kSegThreads;  // chunk entries (hashes) per k_seg thread
 #ifndef SDB_EMIT_WAVES
 #define SDB_EMIT_WAVES 16
 #endif
@@ -45,11 +43,8 @@ constexpr uint32_t kEmitThreads = 64 * SDB_EMIT_WAVES;
 constexpr uint32_t kEmitWgPerCu = 1;
 constexpr uint32_t kEmitWaveLds = kStageGuard + kImgCap + 16 + kKeyStageCap + 64 * 16;  // guard, image, key stage, spans
 constexpr uint32_t kEmitLds = kCrcLds + 16 + (kEmitThreads / 64) * kEmitWaveLds;  // tables, ticket, waves
-constexpr uint32_t kEnumLds = kChunk * 16 + 11 * kChunk * 2;  // block list + 11 lifting levels (nb <= kChunk = 2^11)
-constexpr uint32_t kEnumTabLds = 11 * kChunk * 2;  // k_enum's table walk (aliases the lifting levels)
 constexpr uint32_t kGroupThreads = 1024;
-constexpr uint32_t kEnumThreads = 512;         // two workgroups per CU (76 KiB LDS, 85 VGPRs)
-constexpr uint32_t kGroupLds = kResolveLds;         // group tables, or the single-workgroup resolve
+constexpr uint32_t kGroupLds = kResolveLds;         // group tables (restated in tests/encode_cases.py, group_paths)
 
 // bloom build plan (sdb_bloom.hip): 2^sb-bit slices, T-key binning tiles
 struct BloomPlan {
@@ -67,7 +62,7 @@ struct BloomSlots {
     uint32_t cap;
 };
 
-struct BlockDesc {  // one per block, written by k_enum, streamed by k_emit (56 bytes)
+struct BlockDesc {  // one per block, written by k_blocks, streamed by k_emit (56 bytes)
     uint32_t s, e;        // entries [s, e)
     uint64_t off;         // byte offset of the block in the data section
     uint64_t vs, ve, ks, ke;  // value / key byte ranges of the block
@@ -123,9 +118,9 @@ struct EncodeArgs {
     uint32_t *gtab_exit;    // per group of kGroup chunks, seg_look candidates: composed transfer table
     uint32_t *gtab_cnt;
     uint64_t *gtab_bytes;
-    uint32_t *mode;         // k_group -> k_enum: 1 = compose the tables, 0 = anchors were walked
+    uint32_t *mode;         // chain head: 1 = k_seg's tables describe the chain, 0 = anchors by the serial walk
     uint32_t group;         // chunks per group (host: ~sqrt(nchunks))
-    // bloom fused into the encode: k_seg hashes and bins each chunk (tile = chunk), k_enum fills
+    // bloom fused into the encode: k_facts hashes and bins each chunk (tile = chunk), k_seg fills
     uint32_t bloom_fused;
     BloomPlan bpl;
     BloomSlots bq;
@@ -147,7 +142,7 @@ struct EncodeArgs {
 };
 
 // The workspace arrays of one SST's encode: X(EncodeArgs member, element type, elements).  n entries, nc
-// chunks (k_seg / k_enum), nf k_facts workgroups, nt = nc * kSegLook + 1 table rows (seg_look candidate entry
+// chunks (k_seg / k_blocks), nf k_facts workgroups, nt = nc * kSegLook + 1 table rows (seg_look candidate entry
 // points per chunk; one composed table per group, <= one per chunk).  This list is the only one: the field
 // indices, the slot's offsets (SstSlot::wso), the size and make_args' bindings all come from it.  The bloom
 // slots or the prefix filter's scratch (host-sized) follow the arrays, at wso[kWsTail].
@@ -315,7 +310,7 @@ __host__ __device__ inline EncodeArgs make_args(const SstSet &P, uint32_t i) {
 // Enqueue the encode of every SST of the set on `st` (one launch sequence).
 hipError_t launch_encode_set(const SstSet &P, size_t bin_lds, size_t fill_lds, hipStream_t st);
 hipError_t launch_encode_empty(EncodeArgs a, hipStream_t st);
-hipError_t launch_encode_prep(const SstSet &P, hipStream_t st);  // k_facts, k_seg, k_group only
+hipError_t launch_encode_prep(const SstSet &P, hipStream_t st);  // k_facts, k_seg, k_group: the cuts' chain
 
 // stage timing (diagnostics)
 enum Stage { kStBloom = 0, kStFacts, kStSeg, kStAnchor, kStBlocks, kStEmit, kStEmitBig, kStBloomFill, kNumStages };

@@ -49,12 +49,6 @@ __device__ uint64_t g_phase[1024][8];
         if (threadIdx.x == 0 && blockIdx.x < 1024) g_phase[blockIdx.x][i] = __builtin_amdgcn_s_memtime(); \
     } while (0)
 __device__ uint64_t g_wave_phase[8192][8];
-__device__ uint64_t g_phase_enum[1024][8];
-#define PHASE_MARK_E(i)                                                                  \
-    do {                                                                                 \
-        __syncthreads();                                                                 \
-        if (threadIdx.x == 0 && blockIdx.x < 1024) g_phase_enum[blockIdx.x][i] = __builtin_amdgcn_s_memtime(); \
-    } while (0)
 __device__ uint64_t g_wave_rt[8192][4];  // k_emit per wave: s_memrealtime start/end, s_memtime start/end
 #define WAVE_T(var)                                     \
     uint64_t var = __builtin_amdgcn_s_memtime();        \
@@ -70,9 +64,6 @@ __device__ uint64_t g_wave_rt[8192][4];  // k_emit per wave: s_memrealtime start
     } while (0)
 #define PHASE_MARK_AT(slot, i) \
     do {                       \
-    } while (0)
-#define PHASE_MARK_E(i) \
-    do {                \
     } while (0)
 #define WAVE_T(var) \
     do {            \
@@ -671,25 +662,19 @@ __global__ __launch_bounds__(kSegThreads, SDB_SEG_WAVES) void k_seg(SstSet P) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// K2 group: compose the chunk transfer tables of each group of a.group consecutive chunks (one
-// workgroup per group): for every candidate entry offset o < W into the group's first chunk, the
-// exit offset into the chunk after the group and the blocks / bytes on the way.  k_enum then walks
-// the group tables and its own group's chunk tables from entry 0 (<= ~2 sqrt(nchunks) steps).
-// Workgroup 0 also reduces the per-chunk SstStats / error partials and initialises the device
-// state the later kernels use.  When the tables cannot describe the chain (blocks longer than
-// the staged lookahead) or do not fit k_enum's LDS, workgroup 0 walks next() serially instead and
-// writes every chunk's anchors (mode 0).
+// The block chain's head, serial walk and chunk-table read: the one copy k_group and k_anchor share.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kGroupThreads) void k_group(SstSet P) {
-    const EncodeArgs a = make_args(P, blockIdx.y);
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+constexpr uint32_t kChainThreads = kGroupThreads;  // both kernels' workgroup (the head's per-wave partials)
+
+// Chain head (every thread of the workgroup calls it): W, the longest candidate block in entries,
+// reduced from k_seg's per-chunk maxima.  The workgroup that owns the SST's state (`own`) also
+// reduces the SstStats / error partials of k_facts, and its thread 0 initialises the device state
+// of the later kernels and the summary (the kernel runs alone on the stream).
+SDB_DEV uint32_t chain_head(const EncodeArgs &a, bool own) {
     __shared__ uint32_t s_W;
     __shared__ unsigned long long s_err;
-    __shared__ uint64_t s_stat[5][kGroupThreads / 64];
-    const uint32_t K = a.nchunks, g = blockIdx.x, G = a.group, ngroups = (K + G - 1) / G;
-    if (g >= ngroups) return;
-    const uint32_t tid = threadIdx.x, nt = blockDim.x;
-    if (blockIdx.y == 0) PHASE_MARK_AT(1023, 5);
+    __shared__ uint64_t s_stat[5][kChainThreads / 64];
+    const uint32_t K = a.nchunks, tid = threadIdx.x, nt = blockDim.x;
     if (tid == 0) {
         s_W = 0;
         s_err = ~0ull;
@@ -703,7 +688,7 @@ __global__ __launch_bounds__(kGroupThreads) void k_group(SstSet P) {
             const uint32_t w = a.wmax_part[q];
             m = w > m ? w : m;
         }
-        if (g == 0) {
+        if (own) {
             for (uint32_t q = tid; q < a.nfacts; q += nt) {
                 const unsigned long long ep = a.err_part[q];
                 em = ep < em ? ep : em;
@@ -713,7 +698,7 @@ __global__ __launch_bounds__(kGroupThreads) void k_group(SstSet P) {
         }
         m = wave_max(m);
         if (lane_id() == 0) atomicMax(&s_W, m);
-        if (g == 0) {
+        if (own) {
             if (em != ~0ull) atomicMin(&s_err, em);
 #pragma unroll
             for (int f = 0; f < 5; f++) {
@@ -724,31 +709,27 @@ __global__ __launch_bounds__(kGroupThreads) void k_group(SstSet P) {
     }
     __syncthreads();
     const uint32_t W = s_W;
-    // mode 1: the tables describe the chain and k_enum stages its walk in LDS; mode 2: the same walk
-    // straight from HBM (tables too large for k_enum's LDS: blocks of 16 KiB and more); mode 0: blocks
-    // longer than the staged lookahead, anchors by a serial walk of next()
-    const bool fast = W >= 1 && W <= a.seg_look;
-    const bool enum_lds = (uint64_t)W * (ngroups + G) * 16 + 64 <= kEnumTabLds;
-    if (g == 0 && tid == 0) {
-        // device state for k_enum / k_emit (this kernel runs alone on the stream)
+    if (own && tid == 0) {
         *a.wmax = W;
         *a.err = s_err;
         *a.slow_count = 0;
         *a.big_count = 0;
         a.done[0] = 0;
         a.done[1] = 0;
-        *a.mode = fast ? (enum_lds ? 1u : 2u) : 0u;
+        // 1: k_seg's tables describe the chain; 0: blocks longer than the staged lookahead, the
+        // anchors come from a serial walk of next()
+        *a.mode = W >= 1 && W <= a.seg_look ? 1u : 0u;
         sdb_sst_summary *sm = a.summary;
-        uint64_t t[5];
-        for (int f = 0; f < 5; f++) {
-            t[f] = 0;
-            for (uint32_t q = 0; q < nt / 64; q++) t[f] += s_stat[f][q];
-        }
-        sm->raw_key_size = t[0];
-        sm->raw_val_size = t[1];
-        sm->num_puts = t[2];
-        sm->num_deletes = t[3];
-        sm->num_merges = t[4];
+        auto total = [&](int f) {
+            uint64_t t = 0;
+            for (uint32_t q = 0; q < nt / 64; q++) t += s_stat[f][q];
+            return t;
+        };
+        sm->raw_key_size = total(0);
+        sm->raw_val_size = total(1);
+        sm->num_puts = total(2);
+        sm->num_deletes = total(3);
+        sm->num_merges = total(4);
         sm->num_entries = a.n;
         sm->bloom_len = 0;
         sm->num_probes = 0;
@@ -756,49 +737,102 @@ __global__ __launch_bounds__(kGroupThreads) void k_group(SstSet P) {
         sm->status = 0;
         sm->max_block_entries = 0;
         sm->first_error_entry = ~0ull;
-        if (!fast) {
-            // serial walk of the block chain (one next() step per block), anchors for every chunk
-            uint64_t e = 0, blk = 0, by = 0;
-            for (uint32_t k = 0; k < K; k++) {
-                const uint64_t cs = (uint64_t)k * kChunk, ce = cs + kChunk < a.n ? cs + kChunk : a.n;
-                a.anchor_e[k] = (uint32_t)e;
-                a.anchor_blk[k] = (uint32_t)blk;
-                a.anchor_byte[k] = by;
-                while (e < ce) {
-                    by += a.bbytes[e];
-                    blk++;
-                    e = a.next[e];
-                }
-            }
-            a.anchor_e[K] = (uint32_t)a.n;
-            a.anchor_blk[K] = (uint32_t)blk;
-            a.anchor_byte[K] = by;
-            sm->num_blocks = blk;
-            sm->data_len = by;
-            if (blk > a.block_cap || by > a.data_cap) report_error(a.err, 0, SDB_INVALID_ARGUMENT);
+    }
+    return W;
+}
+
+// Mode 0, one thread: the serial walk of the block chain (one next() step per block) writes the
+// anchors of chunks [0, K); the chain's blocks and bytes come back in blk / by.
+SDB_DEV void chain_walk_serial(const EncodeArgs &a, uint64_t &blk, uint64_t &by) {
+    uint64_t e = 0;
+    blk = by = 0;
+    for (uint32_t k = 0; k < a.nchunks; k++) {
+        const uint64_t cs = (uint64_t)k * kChunk, ce = cs + kChunk < a.n ? cs + kChunk : a.n;
+        a.anchor_e[k] = (uint32_t)e;
+        a.anchor_blk[k] = (uint32_t)blk;
+        a.anchor_byte[k] = by;
+        while (e < ce) {
+            by += a.bbytes[e];
+            blk++;
+            e = a.next[e];
         }
     }
+}
+
+// One thread: the chain's end (anchor entry K), its totals in the summary and the capacity check.
+SDB_DEV void chain_totals(const EncodeArgs &a, uint64_t blk, uint64_t by) {
+    const uint32_t K = a.nchunks;
+    a.anchor_e[K] = (uint32_t)a.n;
+    a.anchor_blk[K] = (uint32_t)blk;
+    a.anchor_byte[K] = by;
+    a.summary->num_blocks = blk;
+    a.summary->data_len = by;
+    if (blk > a.block_cap || by > a.data_cap) report_error(a.err, 0, SDB_INVALID_ARGUMENT);
+}
+
+// Chunk k's transfer table at candidate o, as the chain composes it: the exit offset into the next
+// chunk, the blocks and the bytes on the way.
+struct TabEntry {
+    uint32_t x, c;
+    uint64_t b;
+};
+// Candidates past the chunk's own bound are never entry points: they read as zeros.
+SDB_DEV bool tab_in(const EncodeArgs &a, uint32_t k, uint32_t o) {
+    const uint64_t cs = (uint64_t)k * kChunk, ce = cs + kChunk < a.n ? cs + kChunk : a.n;
+    return cs + o < ce;
+}
+// The entry from loaded values (te, tc, tb = tab_exit / tab_cnt / tab_bytes at k * seg_look + o): the
+// exit is clamped into [0, W), so that the stale slot of a candidate no chain reaches stays in range.
+SDB_DEV TabEntry tab_clamp(const EncodeArgs &a, uint32_t k, uint32_t o, uint32_t W, uint32_t te, uint32_t tc,
+                           uint64_t tb) {
+    const uint64_t cs = (uint64_t)k * kChunk, ce = cs + kChunk < a.n ? cs + kChunk : a.n;
+    const bool in = cs + o < ce;
+    const uint64_t tx = te;
+    return {in ? (tx >= ce && tx - ce < W ? (uint32_t)(tx - ce) : W - 1) : 0u, in ? tc : 0u, in ? tb : 0ull};
+}
+// The same with its own loads (none for a candidate past the bound); bulk stagers load first, then clamp.
+SDB_DEV TabEntry tab_load(const EncodeArgs &a, uint32_t k, uint32_t o, uint32_t W) {
+    if (!tab_in(a, k, o)) return {0u, 0u, 0ull};
+    const uint64_t t = (uint64_t)k * a.seg_look + o;
+    return tab_clamp(a, k, o, W, a.tab_exit[t], a.tab_cnt[t], a.tab_bytes[t]);
+}
+
+// ------------------------------------------------------------------------------------------------
+// K2 group (the compactor's SST cuts only, launch_encode_prep; the encode runs k_anchor instead):
+// compose the chunk transfer tables of each group of a.group consecutive chunks (one workgroup per
+// group): for every candidate entry offset o < W into the group's first chunk, the exit offset into
+// the chunk after the group and the blocks / bytes on the way.  k_cut (sdb_compact.hip) walks these
+// group tables and k_seg's chunk tables from HBM.  Workgroup 0 owns the chain head.  When the tables
+// cannot describe the chain (blocks longer than the staged lookahead), workgroup 0 walks next()
+// serially instead and writes every chunk's anchors (mode 0).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kGroupThreads) void k_group(SstSet P) {
+    const EncodeArgs a = make_args(P, blockIdx.y);
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const uint32_t K = a.nchunks, g = blockIdx.x, G = a.group, ngroups = (K + G - 1) / G;
+    if (g >= ngroups) return;
+    const uint32_t tid = threadIdx.x, nt = blockDim.x;
+    if (blockIdx.y == 0) PHASE_MARK_AT(1023, 5);
+    const uint32_t W = chain_head(a, g == 0);  // every group's workgroup reduces W itself
+    const bool fast = W >= 1 && W <= a.seg_look;
+    if (!fast && g == 0 && tid == 0) {
+        uint64_t blk, by;
+        chain_walk_serial(a, blk, by);
+        chain_totals(a, blk, by);
+    }
     if (!fast) return;
-    // this group's chunk tables -> LDS (exit offsets clamped into [0, W): candidates past a chunk's
-    // own bound are never entry points, their stale slots only need to stay in range)
+    // this group's chunk tables -> LDS
     const uint32_t k0 = g * G, k1 = k0 + G < K ? k0 + G : K, nk = k1 - k0;
     if ((uint64_t)nk * W * 14 + 64 > kGroupLds) {
-        // too large for LDS: each candidate walks the chunk tables in HBM (the same clamping)
+        // too large for LDS: each candidate walks the chunk tables in HBM
         for (uint32_t o = tid; o < W; o += nt) {
             uint32_t e = o, c = 0;
             uint64_t b = 0;
             for (uint32_t j = 0; j < nk; j++) {
-                const uint32_t k = k0 + j;
-                const uint64_t cs = (uint64_t)k * kChunk, ce = cs + kChunk < a.n ? cs + kChunk : a.n;
-                uint32_t x = 0;
-                if (cs + e < ce) {
-                    const uint64_t t = (uint64_t)k * a.seg_look + e;
-                    const uint32_t te = a.tab_exit[t];
-                    x = te >= ce && te - ce < W ? (uint32_t)(te - ce) : W - 1;
-                    c += a.tab_cnt[t];
-                    b += a.tab_bytes[t];
-                }
-                e = x;
+                const TabEntry t = tab_load(a, k0 + j, e, W);
+                c += t.c;
+                b += t.b;
+                e = t.x;
             }
             const uint64_t t = (uint64_t)g * a.seg_look + o;
             a.gtab_exit[t] = e;
@@ -811,20 +845,11 @@ __global__ __launch_bounds__(kGroupThreads) void k_group(SstSet P) {
     uint32_t *cn_ = (uint32_t *)(smem + ((2 * nk * W + 15) & ~15u)); // nk x W
     uint64_t *by_ = (uint64_t *)((uint8_t *)cn_ + ((4 * nk * W + 15) & ~15u));
     for (uint32_t idx = tid; idx < nk * W; idx += nt) {
-        const uint32_t j = idx / W, o = idx - j * W, k = k0 + j;
-        const uint64_t cs = (uint64_t)k * kChunk, ce = cs + kChunk < a.n ? cs + kChunk : a.n;
-        uint32_t x = 0, c = 0;
-        uint64_t b = 0;
-        if (cs + o < ce) {
-            const uint64_t t = (uint64_t)k * a.seg_look + o;
-            const uint32_t te = a.tab_exit[t];
-            x = te >= ce && te - ce < W ? (uint32_t)(te - ce) : W - 1;
-            c = a.tab_cnt[t];
-            b = a.tab_bytes[t];
-        }
-        ex[idx] = (uint16_t)x;
-        cn_[idx] = c;
-        by_[idx] = b;
+        const uint32_t j = idx / W, o = idx - j * W;
+        const TabEntry t = tab_load(a, k0 + j, o, W);
+        ex[idx] = (uint16_t)t.x;
+        cn_[idx] = t.c;
+        by_[idx] = t.b;
     }
     __syncthreads();
     for (uint32_t o = tid; o < W; o += nt) {
@@ -898,69 +923,10 @@ SDB_DEV void write_row_small(uint8_t *dst, const RowInfo &r, uint64_t seq, int64
     }
 }
 
-// Byte-granular copy between LDS regions with dword realignment (dst, src arbitrary alignment).
-SDB_DEV void lds_copy(uint8_t *dst, const uint8_t *src, uint32_t n) {
-    uint32_t i = 0;
-    while (i < n && (((uintptr_t)(dst + i)) & 3)) {
-        dst[i] = src[i];
-        i++;
-    }
-    if (i + 4 <= n) {
-        uintptr_t sa = (uintptr_t)(src + i);
-        uint32_t sh = (uint32_t)(sa & 3);
-        const uint32_t *sw = (const uint32_t *)(sa - sh);
-        uint32_t *dw = (uint32_t *)(dst + i);
-        uint32_t nw = (n - i) >> 2;
-        if (sh == 0) {
-            for (uint32_t w = 0; w < nw; w++) dw[w] = sw[w];
-        } else {
-            uint32_t lo = sw[0];
-            for (uint32_t w = 0; w < nw; w++) {
-                uint32_t hi = sw[w + 1];
-                dw[w] = __builtin_amdgcn_alignbyte(hi, lo, sh);
-                lo = hi;
-            }
-        }
-        i += nw * 4;
-    }
-    while (i < n) {
-        dst[i] = src[i];
-        i++;
-    }
-}
-
 SDB_DEV void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// Stage global bytes [g0, g1) into LDS so that stage[x - (g0 & ~15)] = g[x].  One wave, 16-byte
-// loads (every loaded 16-byte granule holds at least one requested byte).
-SDB_DEV void wave_stage(uint8_t *stage, const uint8_t *g, uint64_t g0, uint64_t g1) {
-    if (g1 <= g0) return;
-    uint64_t a0 = g0 & ~15ull, a1 = (g1 + 15) & ~15ull;
-    uint32_t nchunk = (uint32_t)((a1 - a0) >> 4);
-    const uint4 *src = (const uint4 *)(g + a0);
-    uint4 *dst = (uint4 *)stage;
-    for (uint32_t c = lane_id(); c < nchunk; c += 64) dst[c] = src[c];
-}
-
-// Store LDS image bytes [0, len) to global [dst, dst+len); image byte 0 sits at img + (dst & 15).
-SDB_DEV void wave_store(uint8_t *gdst, const uint8_t *img, uint64_t len) {
-    uintptr_t d0 = (uintptr_t)gdst, d1 = d0 + len;
-    uintptr_t a0 = d0 & ~(uintptr_t)15, a1 = (d1 + 15) & ~(uintptr_t)15;
-    uint32_t nchunk = (uint32_t)((a1 - a0) >> 4);
-    for (uint32_t c = lane_id(); c < nchunk; c += 64) {
-        uintptr_t ga = a0 + 16 * (uintptr_t)c;
-        const uint8_t *li = img + 16 * c;
-        if (ga >= d0 && ga + 16 <= d1) {
-            *(uint4 *)ga = *(const uint4 *)li;
-        } else {
-            for (int q = 0; q < 16; q++)
-                if (ga + q >= d0 && ga + q < d1) ((uint8_t *)ga)[q] = li[q];
-        }
-    }
 }
 
 // The assembler of a block (BlockDesc::route), decided once, by the kernel that writes the descriptor:
@@ -981,358 +947,33 @@ SDB_DEV uint32_t block_route(const EncodeArgs &a, const BlockDesc &d) {
 SDB_DEV bool emit_fast(const BlockDesc &d) { return d.route == kRouteImage; }
 
 // ------------------------------------------------------------------------------------------------
-// K5a: enumerate the blocks of each chunk (binary lifting over next()) -> BlockMeta offsets and the
-//      per-block descriptors the emitter streams.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kEnumThreads) void k_enum(SstSet P) {
-    const EncodeArgs a = make_args(P, blockIdx.y);
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    __shared__ uint64_t s_anc[4];  // entry point, first block, first byte, blocks of this chunk
-    const uint32_t k = blockIdx.x, K = a.nchunks;
-    if (k >= K) return;
-    if (*a.err != ~0ull) return;
-    const uint64_t cs = (uint64_t)k * kChunk;
-    const uint64_t ce = cs + kChunk < a.n ? cs + kChunk : a.n;
-    const uint32_t cn = (uint32_t)(ce - cs);
-    const uint32_t tid = threadIdx.x, nt = blockDim.x;
-    PHASE_MARK_E(0);
-    uint32_t *bl_s = (uint32_t *)smem;
-    uint32_t *bl_b = bl_s + kChunk;
-    uint64_t *bl_o = (uint64_t *)(bl_b + kChunk);
-    uint16_t *lv = (uint16_t *)(bl_o + kChunk);
-    // next() and the block bytes of every chunk entry are independent of the entry point: their loads
-    // go out now and land while the tables are walked (bl_b holds the bytes by entry until the scan)
-    constexpr uint32_t kU = (kChunk + kEnumThreads - 1) / kEnumThreads;
-    uint32_t nx[kU], eb[kU];
-#pragma unroll
-    for (uint32_t u = 0; u < kU; u++) {
-        const uint32_t x = u * nt + tid;
-        nx[u] = x < cn ? a.next[cs + x] : 0;
-        eb[u] = x < cn ? a.bbytes[cs + x] : 0;
-    }
-    if (*a.mode == 2) {
-        // the same walk as below, one thread straight through the tables in HBM (they do not fit LDS)
-        if (tid == 0) {
-            const uint32_t W = *a.wmax, G = a.group, g = k / G, k0 = g * G;
-            uint32_t e = 0;
-            uint64_t blk = 0, by = 0;
-            for (uint32_t q = 0; q < g; q++) {
-                const uint64_t t = (uint64_t)q * a.seg_look + e;
-                blk += a.gtab_cnt[t];
-                by += a.gtab_bytes[t];
-                const uint32_t x = a.gtab_exit[t];
-                e = x < W ? x : W - 1;
-            }
-            for (uint32_t kk = k0; kk < k; kk++) {
-                const uint64_t ccs = (uint64_t)kk * kChunk, cce = ccs + kChunk < a.n ? ccs + kChunk : a.n;
-                uint32_t x = 0;
-                if (ccs + e < cce) {
-                    const uint64_t t = (uint64_t)kk * a.seg_look + e;
-                    const uint32_t te = a.tab_exit[t];
-                    x = te >= cce ? te - (uint32_t)cce : 0;
-                    blk += a.tab_cnt[t];
-                    by += a.tab_bytes[t];
-                }
-                e = x < W ? x : W - 1;
-            }
-            uint32_t cn = 0;
-            uint64_t cb = 0;
-            if (cs + e < ce) {
-                const uint64_t t = (uint64_t)k * a.seg_look + e;
-                cn = a.tab_cnt[t];
-                cb = a.tab_bytes[t];
-            }
-            s_anc[0] = cs + e;
-            s_anc[1] = blk;
-            s_anc[2] = by;
-            s_anc[3] = cn;
-            if (k + 1 == K) {
-                const uint64_t tb = blk + cn, ty = by + cb;
-                a.anchor_blk[K] = (uint32_t)tb;
-                a.anchor_byte[K] = ty;
-                a.anchor_e[K] = (uint32_t)a.n;
-                a.summary->num_blocks = tb;
-                a.summary->data_len = ty;
-                if (tb > a.block_cap || ty > a.data_cap) report_error(a.err, 0, SDB_INVALID_ARGUMENT);
-            }
-        }
-        __syncthreads();
-    } else if (*a.mode) {
-        // walk the group tables of the groups before this chunk's, then this group's chunk tables
-        // (k's own last: its block count), from entry 0.  Tables -> LDS first (one batch of loads).
-        const uint32_t W = *a.wmax, G = a.group, g = k / G, k0 = g * G, nc = k - k0 + 1;
-        const uint32_t ntab = g + nc;
-        const uint32_t tb4 = (4 * ntab * W + 15) & ~15u;
-        uint32_t *t_ex = (uint32_t *)lv;                 // ntab x W each
-        uint32_t *t_cn = (uint32_t *)((uint8_t *)lv + tb4);
-        uint64_t *t_by = (uint64_t *)((uint8_t *)lv + 2 * tb4);
-        constexpr uint32_t kU = 8;  // table entries per thread per batch: all loads issued first
-        for (uint32_t base = 0; base < ntab * W; base += kU * nt) {
-            uint32_t x[kU], c[kU];
-            uint64_t b[kU];
-#pragma unroll
-            for (uint32_t u = 0; u < kU; u++) {
-                const uint32_t idx = base + u * nt + tid;
-                x[u] = c[u] = 0;
-                b[u] = 0;
-                if (idx >= ntab * W) continue;
-                const uint32_t q = idx / W, o = idx - q * W;
-                if (q < g) {
-                    const uint64_t t = (uint64_t)q * a.seg_look + o;
-                    x[u] = a.gtab_exit[t];
-                    c[u] = a.gtab_cnt[t];
-                    b[u] = a.gtab_bytes[t];
-                } else {
-                    const uint32_t kk = k0 + (q - g);
-                    const uint64_t ccs = (uint64_t)kk * kChunk, cce = ccs + kChunk < a.n ? ccs + kChunk : a.n;
-                    if (ccs + o < cce) {
-                        const uint64_t t = (uint64_t)kk * a.seg_look + o;
-                        const uint32_t te = a.tab_exit[t];
-                        x[u] = te >= cce ? te - (uint32_t)cce : 0;
-                        c[u] = a.tab_cnt[t];
-                        b[u] = a.tab_bytes[t];
-                    }
-                }
-            }
-#pragma unroll
-            for (uint32_t u = 0; u < kU; u++) {
-                const uint32_t idx = base + u * nt + tid;
-                if (idx >= ntab * W) continue;
-                t_ex[idx] = x[u] < W ? x[u] : W - 1;
-                t_cn[idx] = c[u];
-                t_by[idx] = b[u];
-            }
-        }
-        __syncthreads();
-        PHASE_MARK_E(1);
-        if (tid == 0) {
-            uint32_t e = 0;
-            uint64_t blk = 0, by = 0;
-            for (uint32_t q = 0; q + 1 < ntab; q++) {
-                blk += t_cn[q * W + e];
-                by += t_by[q * W + e];
-                e = t_ex[q * W + e];
-            }
-            const uint32_t q = ntab - 1;  // chunk k itself
-            s_anc[0] = cs + e;
-            s_anc[1] = blk;
-            s_anc[2] = by;
-            s_anc[3] = cs + e < ce ? t_cn[q * W + e] : 0;
-            if (k + 1 == K) {  // totals (the chain's last blocks are this chunk's)
-                const uint64_t tb = blk + s_anc[3], ty = by + (cs + e < ce ? t_by[q * W + e] : 0);
-                a.anchor_blk[K] = (uint32_t)tb;
-                a.anchor_byte[K] = ty;
-                a.anchor_e[K] = (uint32_t)a.n;
-                a.summary->num_blocks = tb;
-                a.summary->data_len = ty;
-                if (tb > a.block_cap || ty > a.data_cap) report_error(a.err, 0, SDB_INVALID_ARGUMENT);
-            }
-        }
-        __syncthreads();
-    } else if (tid == 0) {
-        s_anc[0] = a.anchor_e[k];
-        s_anc[1] = a.anchor_blk[k];
-        s_anc[2] = a.anchor_byte[k];
-        s_anc[3] = a.anchor_blk[k + 1] - a.anchor_blk[k];
-    }
-    __syncthreads();
-    PHASE_MARK_E(2);
-    const uint64_t e0 = s_anc[0];
-    const uint32_t blk0 = (uint32_t)s_anc[1];
-    const uint32_t nb = (uint32_t)s_anc[3];
-    const uint64_t byte0 = s_anc[2];
-    if (blk0 + (uint64_t)nb > a.block_cap) {  // capacity: the last chunk reports it
-        if (tid == 0) report_error(a.err, 0, SDB_INVALID_ARGUMENT);
-        return;
-    }
-    if (k + 1 == K && tid == 0) {
-        a.out_block_off[blk0 + nb] = a.anchor_byte[K];
-        a.out_block_first[blk0 + nb] = (uint32_t)a.n;
-    }
-    if (!nb) return;
-    uint32_t levels = 1;
-    while ((1u << levels) < nb) levels++;
-#pragma unroll
-    for (uint32_t u = 0; u < kU; u++) {
-        const uint32_t x = u * nt + tid;
-        if (x < cn) {
-            lv[x] = (uint16_t)(nx[u] >= ce ? cn : (uint32_t)(nx[u] - cs));
-            bl_b[x] = eb[u];  // by entry for now
-        }
-    }
-    __syncthreads();
-    PHASE_MARK_E(3);
-    for (uint32_t j = 1; j < levels; j++) {
-        uint16_t *src = lv + (uint64_t)(j - 1) * kChunk, *dst = lv + (uint64_t)j * kChunk;
-        for (uint32_t x = tid; x < cn; x += nt) {
-            uint16_t y = src[x];
-            dst[x] = (y >= cn) ? (uint16_t)cn : src[y];
-        }
-        __syncthreads();
-    }
-    uint32_t bx[kU];
-#pragma unroll
-    for (uint32_t u = 0; u < kU; u++) {
-        const uint32_t t = u * nt + tid;
-        bx[u] = 0;
-        if (t < nb) {
-            uint32_t x = (uint32_t)(e0 - cs);
-            for (uint32_t j = 0; j < levels; j++)
-                if ((t >> j) & 1) x = lv[(uint64_t)j * kChunk + x];
-            bl_s[t] = (uint32_t)cs + x;
-            bx[u] = bl_b[x];
-        }
-    }
-    __syncthreads();  // every by-entry read of bl_b is done: it becomes by block
-#pragma unroll
-    for (uint32_t u = 0; u < kU; u++) {
-        const uint32_t t = u * nt + tid;
-        if (t < nb) bl_b[t] = bx[u];
-    }
-    __syncthreads();
-    PHASE_MARK_E(4);
-    if (tid < 64) {
-        uint64_t carry = byte0;
-        for (uint32_t g = 0; g < nb; g += 64) {
-            uint32_t t = g + tid;
-            uint64_t v = t < nb ? bl_b[t] : 0;
-            uint64_t inc = wave_incl_scan(v);
-            if (t < nb) bl_o[t] = carry + inc - v;
-            carry += wave_readlane(inc, 63);
-        }
-    }
-    __shared__ uint32_t s_nbig, s_bigbase;
-    uint32_t *big_local = (uint32_t *)lv;  // the lifting levels are done: this chunk's piece-path blocks
-    if (tid == 0) s_nbig = 0;
-    __syncthreads();
-    for (uint32_t t = tid; t < nb; t += nt) {
-        const uint64_t s = bl_s[t], e = t + 1 < nb ? bl_s[t + 1] : a.next[s];
-        uint32_t blk = blk0 + t;
-        a.out_block_off[blk] = bl_o[t];
-        a.out_block_first[blk] = (uint32_t)s;
-        BlockDesc d;
-        d.s = (uint32_t)s;
-        d.e = (uint32_t)e;
-        d.off = bl_o[t];
-        d.vs = a.val_off[s];
-        d.ve = a.val_off[e];
-        d.ks = a.key_off[s];
-        d.ke = a.key_off[e];
-        d.bb = bl_b[t];
-        d.route = block_route(a, d);
-        if (d.route == kRouteWorkgroup) a.slow_list[atomicAdd(a.slow_count, 1u)] = blk;
-        if (d.route == kRoutePieces) big_local[atomicAdd(&s_nbig, 1u)] = blk;  // LDS: one global reservation per chunk below
-        a.desc[blk] = d;
-    }
-    __syncthreads();
-    const uint32_t nbig = s_nbig;
-    if (nbig) {  // (a global atomic per big block serialised on the counter: 65 us per SST at 8 KiB blocks)
-        if (tid == 0) s_bigbase = atomicAdd(a.big_count, nbig);
-        __syncthreads();
-        for (uint32_t i = tid; i < nbig; i += nt) a.big_list[s_bigbase + i] = big_local[i];
-    }
-    PHASE_MARK_E(5);
-}
-
-// ------------------------------------------------------------------------------------------------
-// K2' anchor (the encode's k_group + the table walks k_enum did per chunk): one workgroup per SST.
-//   1. workgroup 0's part of k_group: the SstStats / error partials, the longest candidate block (W)
-//      and the device state of the later kernels;
+// K2' anchor (the encode's chain; k_group composes the same tables for the compactor's cuts): one
+// workgroup per SST.
+//   1. the chain head: the SstStats / error partials, the longest candidate block (W) and the device
+//      state of the later kernels;
 //   2. every chunk's anchor (entry point, first block, first byte) from k_seg's chunk transfer tables,
 //      staged in LDS (u16 exit, u16 blocks, u64 bytes): composed per group of a.group chunks (a lane per
 //      (group, candidate)), the groups walked from entry 0 (one lane), then each group's chunks from its
-//      entry (a lane per group) — about 3 sqrt(nchunks) dependent LDS steps for the SST, where every
-//      k_enum workgroup used to stage its own group tables and walk them.  Tables over the LDS are
-//      walked the same way straight from HBM.
+//      entry (a lane per group) -- about 3 sqrt(nchunks) dependent LDS steps for the SST.  Tables over the
+//      LDS are streamed through per-wave buffers, or walked the same way straight from HBM.
 //   Mode 0 (blocks longer than the lookahead): the serial walk of next(), as k_group.
 // ------------------------------------------------------------------------------------------------
 constexpr uint32_t kAnchorThreads = 1024;
-constexpr uint32_t kAnchorLds = 148 * 1024;
+constexpr uint32_t kAnchorLds = 148 * 1024;  // (restated with the table layouts in tests/encode_cases.py, anchor_path)
+static_assert(kAnchorThreads == kChainThreads, "chain_head's per-wave partials");
 
 __global__ __launch_bounds__(kAnchorThreads) void k_anchor(SstSet P) {
     const EncodeArgs a = make_args(P, blockIdx.y);
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    __shared__ uint32_t s_W;
-    __shared__ unsigned long long s_err;
-    __shared__ uint64_t s_stat[5][kAnchorThreads / 64];
     const uint32_t K = a.nchunks, G = a.group, ngroups = (K + G - 1) / G;
     const uint32_t tid = threadIdx.x, nt = blockDim.x;
     if (blockIdx.y == 0) PHASE_MARK_AT(1023, 5);
-    if (tid == 0) {
-        s_W = 0;
-        s_err = ~0ull;
-    }
-    __syncthreads();
-    {
-        uint32_t m = 0;
-        unsigned long long em = ~0ull;
-        uint64_t st[5] = {0, 0, 0, 0, 0};
-        for (uint32_t q = tid; q < K; q += nt) {
-            const uint32_t w = a.wmax_part[q];
-            m = w > m ? w : m;
-        }
-        for (uint32_t q = tid; q < a.nfacts; q += nt) {
-            const unsigned long long ep = a.err_part[q];
-            em = ep < em ? ep : em;
-#pragma unroll
-            for (int f = 0; f < 5; f++) st[f] += a.stat_part[5 * (uint64_t)q + f];
-        }
-        m = wave_max(m);
-        if (lane_id() == 0) atomicMax(&s_W, m);
-        if (em != ~0ull) atomicMin(&s_err, em);
-#pragma unroll
-        for (int f = 0; f < 5; f++) {
-            const uint64_t t = wave_sum(st[f]);
-            if (lane_id() == 0) s_stat[f][tid >> 6] = t;
-        }
-    }
-    __syncthreads();
+    const uint32_t W = chain_head(a, true);
     if (blockIdx.y == 0) PHASE_MARK_AT(1023, 0);
-    const uint32_t W = s_W;
     const bool fast = W >= 1 && W <= a.seg_look;
-    sdb_sst_summary *sm = a.summary;
-    if (tid == 0) {
-        *a.wmax = W;
-        *a.err = s_err;
-        *a.slow_count = 0;
-        *a.big_count = 0;
-        a.done[0] = 0;
-        a.done[1] = 0;
-        *a.mode = fast ? 1u : 0u;
-        uint64_t t[5];
-        for (int f = 0; f < 5; f++) {
-            t[f] = 0;
-            for (uint32_t q = 0; q < nt / 64; q++) t[f] += s_stat[f][q];
-        }
-        sm->raw_key_size = t[0];
-        sm->raw_val_size = t[1];
-        sm->num_puts = t[2];
-        sm->num_deletes = t[3];
-        sm->num_merges = t[4];
-        sm->num_entries = a.n;
-        sm->bloom_len = 0;
-        sm->num_probes = 0;
-        sm->filter_built = 0;
-        sm->status = 0;
-        sm->max_block_entries = 0;
-        sm->first_error_entry = ~0ull;
-    }
     uint64_t tb = 0, ty = 0;  // the chain's blocks and bytes (thread 0)
     if (!fast) {
-        if (tid == 0) {  // serial walk of the block chain (one next() step per block)
-            uint64_t e = 0;
-            for (uint32_t k = 0; k < K; k++) {
-                const uint64_t cs = (uint64_t)k * kChunk, ce = cs + kChunk < a.n ? cs + kChunk : a.n;
-                a.anchor_e[k] = (uint32_t)e;
-                a.anchor_blk[k] = (uint32_t)tb;
-                a.anchor_byte[k] = ty;
-                while (e < ce) {
-                    ty += a.bbytes[e];
-                    tb++;
-                    e = a.next[e];
-                }
-            }
-        }
+        if (tid == 0) chain_walk_serial(a, tb, ty);
     } else {
         const uint64_t ntab = (uint64_t)K * W, ng = (uint64_t)ngroups * W;
         const uint64_t o_cn = (2 * ntab + 15) & ~15ull, o_by = o_cn + ((2 * ntab + 15) & ~15ull);
@@ -1344,29 +985,10 @@ __global__ __launch_bounds__(kAnchorThreads) void k_anchor(SstSet P) {
         uint64_t *g_by = (uint64_t *)(smem + o_gby);
         uint32_t *g_ent = (uint32_t *)(smem + o_ent);  // per group: entry offset, blocks before (bytes: g_ent64)
         uint64_t *g_b64 = (uint64_t *)(smem + o_ent + 8ull * ngroups);
-        // chunk k's table at candidate o (exit clamped into [0, W): candidates past a chunk's own bound are
-        // never entry points, their stale slots only need to stay in range)
-        auto tab_hbm = [&](uint32_t k, uint32_t o, uint32_t &x, uint32_t &c, uint64_t &b) {
-            const uint64_t cs = (uint64_t)k * kChunk, ce = cs + kChunk < a.n ? cs + kChunk : a.n;
-            x = c = 0;
-            b = 0;
-            if (cs + o < ce) {
-                const uint64_t t = (uint64_t)k * a.seg_look + o;
-                const uint32_t te = a.tab_exit[t];
-                x = te >= ce && te - ce < W ? (uint32_t)(te - ce) : W - 1;
-                c = a.tab_cnt[t];
-                b = a.tab_bytes[t];
-            }
-        };
-        auto tab = [&](uint32_t k, uint32_t o, uint32_t &x, uint32_t &c, uint64_t &b) {
-            if (in_lds) {
-                const uint64_t i = (uint64_t)k * W + o;
-                x = t_ex[i];
-                c = t_cn[i];
-                b = t_by[i];
-            } else {
-                tab_hbm(k, o, x, c, b);
-            }
+        // chunk k's table at candidate o, from the staged copy (in_lds)
+        auto tab = [&](uint32_t k, uint32_t o) -> TabEntry {
+            const uint64_t i = (uint64_t)k * W + o;
+            return {t_ex[i], t_cn[i], t_by[i]};
         };
         if (in_lds) {
             // stage the tables: eight entries per thread in flight, every load unconditional (chunk clamped);
@@ -1397,12 +1019,10 @@ __global__ __launch_bounds__(kAnchorThreads) void k_anchor(SstSet P) {
                 for (uint32_t u = 0; u < kU; u++) {
                     const uint32_t i = base + u * nt + tid;
                     if (i >= ntab32) continue;
-                    const uint64_t cs = (uint64_t)ku[u] * kChunk, ce = cs + kChunk < a.n ? cs + kChunk : a.n;
-                    const bool in = cs + ou[u] < ce;  // as tab_hbm
-                    const uint64_t tx = te[u];
-                    t_ex[i] = (uint16_t)(in ? (tx >= ce && tx - ce < W ? (uint32_t)(tx - ce) : W - 1) : 0u);
-                    t_cn[i] = (uint16_t)(in ? tc[u] : 0u);  // a block count inside one chunk: <= kChunk
-                    t_by[i] = in ? tb[u] : 0ull;
+                    const TabEntry t = tab_clamp(a, ku[u], ou[u], W, te[u], tc[u], tb[u]);
+                    t_ex[i] = (uint16_t)t.x;
+                    t_cn[i] = (uint16_t)t.c;  // a block count inside one chunk: <= kChunk
+                    t_by[i] = t.b;
                 }
             }
             __syncthreads();
@@ -1472,11 +1092,10 @@ __global__ __launch_bounds__(kAnchorThreads) void k_anchor(SstSet P) {
                     for (uint32_t u = 0; u < kU; u++) {
                         const uint32_t i = i0 + 64 * u + ln;
                         if (i >= ne) continue;
-                        const uint64_t cs = (uint64_t)(k0 + ks[u]) * kChunk, ce = cs + kChunk < a.n ? cs + kChunk : a.n;
-                        const bool in = cs + os[u] < ce;  // as tab_hbm
-                        bx[i] = (uint16_t)(in ? (te[u] >= ce && te[u] - ce < W ? (uint32_t)(te[u] - ce) : W - 1) : 0u);
-                        bc[i] = (uint16_t)(in ? tc[u] : 0u);
-                        bb[i] = in ? tbv[u] : 0ull;
+                        const TabEntry t = tab_clamp(a, k0 + ks[u], os[u], W, te[u], tc[u], tbv[u]);
+                        bx[i] = (uint16_t)t.x;
+                        bc[i] = (uint16_t)t.c;
+                        bb[i] = t.b;
                     }
                 }
                 __builtin_amdgcn_wave_barrier();
@@ -1542,12 +1161,10 @@ __global__ __launch_bounds__(kAnchorThreads) void k_anchor(SstSet P) {
             uint32_t e = (uint32_t)i - q * W, c = 0;
             uint64_t b = 0;
             for (uint32_t k = q * G; k < k1; k++) {
-                uint32_t x, cc;
-                uint64_t bb;
-                tab(k, e, x, cc, bb);
-                c += cc;
-                b += bb;
-                e = x;
+                const TabEntry t = tab(k, e);
+                c += t.c;
+                b += t.b;
+                e = t.x;
             }
             g_ex[i] = e;
             g_cn[i] = c;
@@ -1572,12 +1189,10 @@ __global__ __launch_bounds__(kAnchorThreads) void k_anchor(SstSet P) {
                         a.anchor_e[k] = (uint32_t)((uint64_t)k * kChunk + e);
                         a.anchor_blk[k] = (uint32_t)tb;
                         a.anchor_byte[k] = ty;
-                        uint32_t x, c;
-                        uint64_t b;
-                        tab_hbm(k, e, x, c, b);
-                        tb += c;
-                        ty += b;
-                        e = x;
+                        const TabEntry t = tab_load(a, k, e, W);
+                        tb += t.c;
+                        ty += t.b;
+                        e = t.x;
                     }
                 }
             }
@@ -1592,28 +1207,26 @@ __global__ __launch_bounds__(kAnchorThreads) void k_anchor(SstSet P) {
                 a.anchor_e[k] = (uint32_t)((uint64_t)k * kChunk + e);
                 a.anchor_blk[k] = (uint32_t)blk;
                 a.anchor_byte[k] = by;
-                uint32_t x, c;
-                uint64_t b;
-                tab(k, e, x, c, b);
-                blk += c;
-                by += b;
-                e = x;
+                const TabEntry t = tab(k, e);
+                blk += t.c;
+                by += t.b;
+                e = t.x;
             }
         }
     }
     if (blockIdx.y == 0) PHASE_MARK_AT(1023, 3);
     if (tid == 0) {
-        a.anchor_e[K] = (uint32_t)a.n;
-        a.anchor_blk[K] = (uint32_t)tb;
-        a.anchor_byte[K] = ty;
-        sm->num_blocks = tb;
-        sm->data_len = ty;
-        if (tb > a.block_cap || ty > a.data_cap) report_error(a.err, 0, SDB_INVALID_ARGUMENT);
+        // the tail's arguments (capacities, summary, error word) are loaded here: the kernel is at its SGPR
+        // limit, and kept from its entry, where the compiler hoists every kernel-argument load, they spill.
+        // The opaque copy of the SST index pins the loads below it.
+        uint32_t y = blockIdx.y;
+        asm volatile("" : "+s"(y));
+        chain_totals(make_args(P, y), tb, ty);
     }
 }
 
 // ------------------------------------------------------------------------------------------------
-// K5a' blocks (the encode's k_enum, from k_anchor's anchors): per chunk a 256-thread workgroup with
+// K5a' blocks (each chunk's blocks, from k_anchor's anchors): per chunk a 256-thread workgroup with
 // 16 KiB of LDS (eight per CU): next() and the block bytes of the chunk's entries staged in LDS, the
 // chunk's block chain walked from its anchor by one lane, then the blocks in batches of 256: offsets by
 // a workgroup scan of their bytes, BlockMeta outputs, descriptors and the big / slow block lists.
@@ -1727,37 +1340,6 @@ __global__ __launch_bounds__(kBlkThreads) void k_blocks(SstSet P) {
 // ------------------------------------------------------------------------------------------------
 SDB_DEV void lds_put_bytes(lu8 *p, uint64_t w, uint32_t n) {  // w little-endian, n <= 8
     for (uint32_t i = 0; i < n; i++) p[i] = (uint8_t)(w >> (8 * i));
-}
-
-// lane: image bytes [fa, fa + L) <- global src
-SDB_DEV void copy_field(lu8 *img, uint32_t fa, uint32_t L, const uint8_t *src) {
-    if (!L) return;
-    const uint32_t A0 = (fa + 3) & ~3u, A1 = (fa + L) & ~3u;
-    if (A1 <= A0) {  // no whole dword inside: <= 6 bytes
-        lds_put_bytes(img + fa, load8(src, L), L);
-        return;
-    }
-    const uint32_t hb = A0 - fa;
-    if (hb) lds_put_bytes(img + fa, load8(src, hb), hb);
-    const uint8_t *s = src + hb;
-    lu32 *d = (lu32 *)(img + A0);
-    const uint32_t nd = (A1 - A0) >> 2;
-    uint32_t k = 0;
-    for (; k + 4 <= nd; k += 4) {
-        uint4 v;
-        __builtin_memcpy(&v, s + 4 * k, 16);
-        d[k] = v.x;
-        d[k + 1] = v.y;
-        d[k + 2] = v.z;
-        d[k + 3] = v.w;
-    }
-    for (; k < nd; k++) {
-        uint32_t v;
-        __builtin_memcpy(&v, s + 4 * k, 4);
-        d[k] = v;
-    }
-    const uint32_t tb = fa + L - A1;
-    if (tb) lds_put_bytes(img + A1, load8(src + (A1 - fa), tb), tb);
 }
 
 // Key-suffix + value copy into the block image.  A row's copy span is [F0, F1): from its key suffix
@@ -2299,7 +1881,7 @@ SDB_DEV void emit_big(const EncodeArgs &a, uint32_t blk, const BlockDesc &d, lu8
         const bool fits = row && inc <= 4096 && (vo1 - va) <= kStageCap && (ko1 - ka) <= kKeyStageCap;
         const uint64_t nofit = __ballot(!fits);
         const uint32_t c = nofit ? (uint32_t)__builtin_ctzll(nofit) : 64u;
-        if (c == 0) {  // k_enum routes blocks with rows this large to the workgroup path
+        if (c == 0) {  // k_blocks routes blocks with rows this large to the workgroup path
             if (l == 0) report_error(a.err, d.s + r, SDB_DEVICE_ERROR);
             return;
         }
@@ -2482,7 +2064,7 @@ SDB_DEV void finish_summary(const EncodeArgs &a) {
 // One wave per block, blocks strided over the grid's waves; each wave runs a two-stage software
 // pipeline: while block i is assembled, CRC'd and stored from LDS, block i + 1's granules and row
 // metadata are in flight into registers, and block i + 2's descriptor behind them.  Blocks that do
-// not fit the LDS image (k_enum's slow list) are done first, one workgroup each.  The last
+// not fit the LDS image (k_blocks' slow list) are done first, one workgroup each.  The last
 // workgroup to finish writes the summary.
 template <int V>
 __global__ __launch_bounds__(kEmitThreads, 1) void k_emit(SstSet P) {
@@ -2889,9 +2471,6 @@ extern "C" int sdb_diag_wave_rt(uint64_t *out, int nwaves) {
     return -1;
 #endif
 }
-extern "C" int sdb_diag_enum_phase(uint64_t *out, int nblocks) {
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_phase_enum), sizeof(uint64_t) * 8 * nblocks) == hipSuccess ? 0 : -1;
-}
 extern "C" int sdb_diag_phase_times(uint64_t *out, int nblocks) {
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_phase), sizeof(uint64_t) * 8 * nblocks) == hipSuccess ? 0 : -1;
 }
@@ -2939,7 +2518,6 @@ static void set_lds_attrs() {
         (void)hipFuncSetAttribute((const void *)k_emit<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kEmitLds);
         (void)hipFuncSetAttribute((const void *)k_emit_big<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kEmitLds);
         (void)hipFuncSetAttribute((const void *)k_emit_big<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kEmitLds);
-        (void)hipFuncSetAttribute((const void *)k_enum, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kEnumLds);
         (void)hipFuncSetAttribute((const void *)k_group, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGroupLds);
         (void)hipFuncSetAttribute((const void *)k_anchor, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAnchorLds);
         (void)hipFuncSetAttribute((const void *)k_seg, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
@@ -2990,9 +2568,10 @@ hipError_t launch_encode_set(const SstSet &P, size_t bin_lds, size_t fill_lds, h
     return hipGetLastError();
 }
 
-// The block chain alone (k_facts -> k_seg -> k_group): per-entry next() / block bytes, the chunk and
-// group transfer tables and the walk mode, for the compactor's SST cuts (sdb_compact.hip).  The slot
-// builds no filter.
+// The block chain alone, for the compactor's SST cuts (k_cut, sdb_compact.hip): k_facts -> k_seg -> k_group
+// leave per-entry next() / block bytes, the chunk tables, the group tables in HBM (k_group runs only here:
+// the encode resolves its chain with k_anchor / k_blocks), the walk mode and the summary's stats; the chunk
+// anchors only in mode 0.  The slot builds no filter.
 hipError_t launch_encode_prep(const SstSet &P, hipStream_t st) {
     set_lds_attrs();
     if (!P.count) return hipSuccess;

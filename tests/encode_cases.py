@@ -599,6 +599,61 @@ def c_cases():
     return out
 
 
+# ------------------------------------------------------------------------------------------------
+# P: which table path a chain takes (k_anchor: tables in LDS, streamed per wave, HBM; k_group for the
+# compactor's cuts: LDS or HBM compose), the kernels' predicates restated for the host (sdb_encode.hip: kAnchorLds,
+# kAnchorThreads / 64, kGroupLds and the layouts in k_anchor / k_group -- a change there is repeated here, or the
+# P shapes below silently stop reaching their paths)
+# ------------------------------------------------------------------------------------------------
+ANCHOR_LDS, GROUP_LDS, ANCHOR_WAVES = 148 * 1024, 96 * 1024, 16
+
+
+def _al16(x):
+    return (x + 15) & ~15
+
+
+def chain_geometry(n):
+    """(chunks, chunks per group, groups) as plan_slot sizes them."""
+    k, g = (n + CHUNK - 1) // CHUNK, 16
+    while g * g < k:
+        g += 1
+    return k, g, (k + g - 1) // g
+
+
+def anchor_path(n, w, block_size):
+    """k_anchor's path for n entries whose longest candidate block is w entries."""
+    k, g, ng = chain_geometry(n)
+    if not 1 <= w <= seg_look(block_size):
+        return "mode0"
+    if 2 * _al16(2 * k * w) + 8 * k * w + 16 * ng * w + 16 * ng <= ANCHOR_LDS:
+        return "lds"
+    for gs in range(g, 0, -1):  # group tables + a buffer of gs chunk tables per wave
+        ngs = (k + gs - 1) // gs
+        tables = _al16(2 * _al16(4 * ngs * w) + 8 * ngs * w + 16 * ngs)
+        if tables + ANCHOR_WAVES * _al16(12 * gs * w) <= ANCHOR_LDS:
+            return "streamed"
+    return "hbm"
+
+
+def group_paths(n, w, block_size):
+    """k_group's compose path of every group (the last group may be shorter, and fit)."""
+    k, g, ng = chain_geometry(n)
+    if not 1 <= w <= seg_look(block_size):
+        return {"mode0"}
+    return {"lds" if min(g, k - q * g) * w * 14 + 64 <= GROUP_LDS else "hbm" for q in range(ng)}
+
+
+# 101 chunks of 13-byte rows, ~120 / ~127 candidates per chunk: the chunk tables outgrow k_anchor's LDS while
+# the group tables and a buffer per wave still fit (the smallest chunk count with such a window is 77)
+P_STREAMED_N, P_STREAMED_BS = 100 * CHUNK + 700, (1600, 1700)
+# 34 chunks, ~615 candidates: the 16 chunk tables of groups 0 and 1 outgrow k_group's LDS, the last group's 2 fit.
+# The cut sizes: under one group's bytes (~442 KB: the walk takes no group table), group 0 taken and the cut
+# right behind it / further into group 1, groups 0 and 1 taken (group 1 entered at candidate 389) and the cut
+# inside group 2, and one SST.
+P_CUTS_N, P_CUTS_BS = 33 * CHUNK + 100, 8192
+P_CUTS_MAX_SST = (30000, 450000, 600000, 880000, 10 ** 12)
+
+
 def all_cases():
     return (r_cases() + t_cases() + f_lattice_cases() + f_tail_cases() + f_geometry_cases() + f_error_cases() +
             c_cases())

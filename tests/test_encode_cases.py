@@ -228,3 +228,38 @@ def test_longest_candidate_bounds_the_oracle():
             # uniform rows: a candidate is at most one restart row (3 bytes dearer than the others) or one
             # shorter shared prefix away from an actual block
             assert w - ref.summary.max_block_entries <= 1, (v, ri, bs, w, ref.summary.max_block_entries)
+
+
+def test_p_shapes_take_their_chain_paths():
+    """The shapes the GPU tests use for k_anchor's streamed tables and k_group's HBM compose take those
+    paths by the kernels' predicates, and the oracle accepts them."""
+    b = E.tiny_rows(E.P_STREAMED_N)
+    for bs in E.P_STREAMED_BS:
+        w = E.longest_candidate(b, 2, bs, 16)
+        assert E.anchor_path(b.n, w, bs) == "streamed", (bs, w)
+        assert O.encode_sst(b, O.params(block_size=bs)).status == 0
+    b = E.tiny_rows(E.P_CUTS_N)
+    w = E.longest_candidate(b, 2, E.P_CUTS_BS, 16)
+    k, g, ng = E.chain_geometry(b.n)
+    assert (k, g, ng) == (34, 16, 3) and E.group_paths(b.n, w, E.P_CUTS_BS) == {"hbm", "lds"}, w
+    assert [min(g, k - q * g) * w * 14 + 64 > E.GROUP_LDS for q in range(ng)] == [True, True, False]
+    # the chain enters groups 1 and 2 at candidates other than 0, after byte0 / byte1 bytes: the cut sizes sit
+    # around them, so the walk takes group 0's table, then also group 1's, and cuts inside the next group
+    ref = O.encode_sst(b, O.params(block_size=E.P_CUTS_BS))
+    at = [int(np.searchsorted(ref.block_first_entry, q * g * E.CHUNK)) for q in (1, 2)]
+    (o1, byte0), (o2, byte1) = [(int(ref.block_first_entry[i]) - q * g * E.CHUNK, int(ref.block_off[i]))
+                                for q, i in zip((1, 2), at)]
+    assert 0 < o1 < w and 0 < o2 < w
+    small, behind, inside, both, one = E.P_CUTS_MAX_SST
+    # (byte1 is what group 0's and group 1's tables add up to: past `inside`, within `both`)
+    assert small < byte0 <= behind < inside < byte1 <= both < ref.summary.data_len < one
+    cuts = {m: O.sst_cuts(b, O.params(block_size=E.P_CUTS_BS), m) for m in E.P_CUTS_MAX_SST}
+    assert all(st == 0 for st, _ in cuts.values())
+    assert len(cuts[small][1]) > 20 and cuts[one][1] == [0, b.n]
+    first = lambda m: cuts[m][1][1]
+    assert g * E.CHUNK + o1 <= first(behind) < first(inside) < 2 * g * E.CHUNK  # the first cut lies in group 1
+    assert 2 * g * E.CHUNK + o2 <= first(both) < b.n  # ... in group 2
+    # the neighbours of the streamed window, and the serial walk
+    assert E.anchor_path(E.P_STREAMED_N, 100, 4096) == "lds" and E.anchor_path(E.P_STREAMED_N, 200, 4096) == "hbm"
+    assert E.anchor_path(E.C_N, E.SEG_LOOK + 1, 16384) == "mode0"
+    assert E.group_paths(E.C_N, E.SEG_LOOK + 1, 16384) == {"mode0"}

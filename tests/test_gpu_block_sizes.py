@@ -1,7 +1,7 @@
 """Every SstBlockSize (config.rs:231-267) against the oracle, bit for bit.  Blocks over one k_emit wave
 image take the piece path (k_emit_big: pieces of <= 64 rows / 4 KiB, CRC chained across pieces, short
-trailers gathered in LDS, long ones read back), chains whose chunk tables exceed k_enum's LDS take the
-HBM table walk (mode 2), and blocks with rows too large for a piece the workgroup path."""
+trailers gathered in LDS, long ones read back), chains whose chunk tables exceed k_anchor's LDS are streamed per wave or
+walked in HBM, and blocks with rows too large for a piece the workgroup path."""
 import numpy as np
 import pytest
 
@@ -9,6 +9,7 @@ from oracle import oracle as O
 from slatedb_amd import datasets
 from slatedb_amd.batch import Batch
 
+from .encode_cases import P_STREAMED_BS, P_STREAMED_N, tiny_rows
 from .test_gpu_parity import assert_same, encode_both, rt  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -54,6 +55,14 @@ def test_blocks_with_rows_too_large_for_a_piece(rt):  # noqa: F811
     b = Batch.from_entries(ents)
     ref, got = encode_both(rt, b, block_size=16384, sst_version=2, bloom_bits_per_key=10)
     assert_same(ref, got, "huge rows")
+
+
+@pytest.mark.parametrize("block_size", P_STREAMED_BS)
+def test_chain_tables_streamed(rt, block_size):  # noqa: F811
+    # chunk tables over k_anchor's LDS, group tables and a per-wave buffer inside it (encode_cases.anchor_path;
+    # test_d1_large_blocks covers the tables in LDS at 8 / 16 KiB and their HBM walk at 32 / 64 KiB)
+    ref, got = encode_both(rt, tiny_rows(P_STREAMED_N), block_size=block_size, sst_version=2, bloom_bits_per_key=10)
+    assert_same(ref, got, "streamed tables bs=%d" % block_size)
 
 
 # ------------------------------------------------------------------------------------------------

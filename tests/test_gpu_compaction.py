@@ -16,6 +16,7 @@ from oracle import oracle as O
 from slatedb_amd import _abi
 from slatedb_amd.batch import Batch, Run
 
+from .encode_cases import P_CUTS_BS, P_CUTS_MAX_SST, P_CUTS_N, tiny_rows
 from .test_compaction_oracle import GOLDEN, entries_of, rand_runs, to_entry
 from .test_gpu_parity import assert_same
 
@@ -170,6 +171,15 @@ def test_sst_cuts_tables_in_hbm_device(rt, max_sst):
     ents = [(b"%08d" % i, 0, b"", 1, None, None) for i in range(n)]
     b = Batch.from_entries(ents)
     cuts_both(rt, b, O.params(block_size=4096), max_sst)
+
+
+@pytest.mark.parametrize("max_sst", P_CUTS_MAX_SST)
+def test_sst_cuts_group_tables_composed_in_hbm_device(rt, max_sst):
+    """~615 candidates per chunk: the 16 chunk tables of groups 0 and 1 outgrow k_group's LDS and are composed
+    from HBM, the last group's two in LDS (encode_cases.group_paths).  The cut sizes make the walk take group
+    0's table, and group 1's at a candidate other than 0, with the cut inside the group behind them: its
+    place depends on the composed bytes and exits (tests/test_encode_cases.py checks the shape)."""
+    cuts_both(rt, tiny_rows(P_CUTS_N), O.params(block_size=P_CUTS_BS), max_sst)
 
 
 def sst_view(d):
