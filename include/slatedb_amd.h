@@ -31,6 +31,9 @@
  *   - sdb_lsm_scan             -> the on-disk part of Reader::scan_with_options (reader.rs:275-320):
  *                                 DbIterator::new (db_iter.rs:189-257) over L0 and the sorted runs, drained:
  *                                 the newest visible version per key, many ranges per call.
+ *   - sdb_lsm_get_merge,       -> the same two reads under MergeOperatorIterator (merge_operator.rs:242-485,
+ *     sdb_lsm_scan_merge         db_iter.rs:234-243): every key's operand chain located on the device, the
+ *                                 user's operator run on the host over the links.
  *   - sdb_sst_builder_*        -> host-side mirror of EncodedSsTableBuilder's add()/build()/
  *                                 next_block() call order (sst_builder.rs:224-276), batching
  *                                 entries into a columnar pinned buffer and encoding on the GPU.
@@ -77,6 +80,7 @@ typedef enum sdb_status {
     SDB_CORRUPT_BLOCK = 9,          /* block bytes that the reference would panic on while parsing */
     SDB_MERGE_OPERATOR_MISSING = 10,/* SlateDBError::MergeOperatorMissing (merge_operator.rs:213-223) */
     SDB_DECOMPRESSION_ERROR = 11,   /* SlateDBError::BlockDecompressionError (format/sst.rs:884-917) */
+    SDB_INVALID_SEQUENCE_ORDER = 12,/* SlateDBError::InvalidSequenceOrder (merge_operator.rs:293-299) */
     SDB_DEVICE_ERROR = 100          /* no HIP device / launch failure */
 } sdb_status;
 
@@ -541,7 +545,7 @@ sdb_status sdb_sst_scan(const sdb_sst_view *sst, const sdb_scan_ranges *ranges, 
  *      A value: SDB_GET_FOUND.  A tombstone: SDB_GET_DELETED with value 0, 0; older SSTs are not looked
  *      at.  A merge operand: SDB_GET_MERGE_OPERAND with status SDB_MERGE_OPERATOR_MISSING
  *      (MergeOperatorRequiredIterator, merge_operator.rs:213-223); the operand's columns are reported, so
- *      a caller with an operator knows where the chain begins (resolving operands is out of scope).  An
+ *      a caller with an operator knows where the chain begins (sdb_lsm_get_merge walks the chain).  An
  *      exhausted chain: SDB_GET_NOT_FOUND with sst = 0xFFFFFFFF and zeroed columns.  Expiry is NOT
  *      filtered on this path: expire_ts is returned to the caller, as in KeyValue;
  *   4. laziness of errors: a query reports a block error only from an SST that lies in its chain at or
@@ -638,8 +642,8 @@ sdb_status sdb_lsm_get(const sdb_lsm_view *lsm, const uint8_t *key_bytes, const 
  *      value yields one row.  Expiry is NOT filtered, as in sdb_lsm_get;
  *   4. merge operands: a key whose winner is a merge operand fails its range with
  *      SDB_MERGE_OPERATOR_MISSING (MergeOperatorRequiredIterator, merge_operator.rs:213-223).  An operand
- *      hidden behind a newer visible value or tombstone, or above the bound, does not.  Resolving operands is
- *      out of scope;
+ *      hidden behind a newer visible value or tombstone, or above the bound, does not.  A store with an
+ *      operator calls sdb_lsm_scan_merge;
  *   5. order and errors: ranges in input order; inside a range keys ascend, or descend when descending != 0
  *      (one row per key, so both orders hold the same rows).  A failing range contributes zero entries: all
  *      or nothing, as sdb_sst_scan rule 4; the reference would yield the rows ahead of the failure first.
@@ -701,6 +705,94 @@ sdb_status sdb_lsm_scan(const sdb_lsm_view *lsm, const sdb_scan_ranges *ranges,
                         const uint64_t *max_seq /* device, n; NULL = no bound */, int32_t descending,
                         uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out *out,
                         void *workspace, uint64_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Merge-operand chains in tree reads (device): what a store WITH a merge operator reads.  DbIterator::new
+ * wraps its iterator in MergeOperatorIterator (merge_different_expire_ts = true, no snapshot barrier:
+ * db_iter.rs:234-247) instead of MergeOperatorRequiredIterator.  The operator is a user trait object and
+ * stays on the host; the device finds the versions of a key that form its operand chain
+ * (merge_with_older_entries, merge_operator.rs:369-448) and the MergeTracker metadata (:262-303), and the
+ * host calls merge_batch on bytes that are already located.
+ *
+ * Chains come out in CSR form over the call's items (queries of a get, output rows of a scan): links newest
+ * first, the order in which merge_with_older_entries meets them.  A chain is a run of merge operands followed
+ * by at most one base value; a tombstone ends a chain and is never a link.
+ *
+ * sdb_lsm_get_merge: sdb_lsm_get rules 1-2 and 5-7 hold (the chain of SSTs, filters, block ranges, block
+ * checks, versions, arguments, conventions); rules 3-4 become:
+ *   3'. versions: each SST of the chain yields EVERY entry with key == query and seq <= max_seq[q], in
+ *      physical order, across blocks, into the next covering SST of the run and into the next run.  The first
+ *      entry decides the state: a value: SDB_GET_FOUND, one link; a tombstone: SDB_GET_DELETED, no link,
+ *      the tombstone's columns as sdb_lsm_get reports them; nothing: SDB_GET_NOT_FOUND; a merge operand:
+ *      SDB_GET_MERGE_OPERAND with status SDB_OK and at least one link: the walk goes on while entries are
+ *      operands; a value ends the chain as its base and last link; a tombstone ends it with no base
+ *      (GetIterator returns None there, db_iter.rs:108-114, so its timestamps are NOT folded on this path);
+ *      an exhausted chain of SSTs ends it with no base.
+ *      Per-query columns, the entry MergeOperatorIterator returns (merge_operator.rs:437-447): sst, block,
+ *      val_off, val_len and seq are the newest link's; create_ts is the maximum and expire_ts the minimum
+ *      over the links that carry one; flags holds HAS_CREATE_TS / HAS_EXPIRE_TS for those aggregates and
+ *      SDB_FLAG_MERGE_OPERAND iff no base was found (ValueDeletable::Merge against Value, :439-443).
+ *      A link whose seq exceeds the newest link's fails the query with SDB_INVALID_SEQUENCE_ORDER
+ *      (MergeTracker::update, :293-299); only a tree the store did not write holds one.  It is found per
+ *      run: it takes precedence over a block error of the same run, and ssts_read / ssts_filtered then
+ *      count that whole run's walk;
+ *   4'. laziness of errors: a query reports a block error from any SST of its chain at or before the SST
+ *      where the chain ENDED: the one holding the base or the tombstone, else the last SST of the chain; a
+ *      filtered SST never counts.  A corrupt block behind the end never surfaces.  ssts_read /
+ *      ssts_filtered count up to and including the ending SST.  A failing query has SDB_GET_NOT_FOUND,
+ *      sst = 0xFFFFFFFF, zeroed columns and no links.
+ * The summary is sdb_get_summary; num_merge counts operand winners and the five counters partition the
+ * queries.  chain->summary->num_links and chain_start (nkeys + 1) are always written; when num_links >
+ * cap_links the chain summary's status is SDB_LIMIT_EXCEEDED and no link column is written, while the
+ * per-query columns stay valid: a caller needs at most two calls.  chain, chain_start and chain->summary must
+ * not be NULL, the link columns not when cap_links > 0.
+ *
+ * sdb_lsm_scan_merge: sdb_lsm_scan rules 1-3 and 5-7 hold; rule 4 becomes: in the merged order of a range's
+ * visible candidates (key ascending, seq descending, earlier SST first on ties) the winner of a key is its
+ * first visible version.  A value winner yields a row with one link, a tombstone winner no row, an operand
+ * winner a row whose links are the operands that follow for the same key up to and including the first
+ * value.  A tombstone stops the chain and is not a link; HERE its create_ts / expire_ts are folded into the
+ * row's aggregates and the row's flags show a base: MergeIterator hands it to merge_with_older_entries as
+ * the base (merge_iterator.rs:193-206, merge_operator.rs:421-425).  Row columns as in the get variant;
+ * chain_start is indexed by output row (num_entries + 1 valid elements, array sized cap_entries + 1).  With
+ * descending != 0 the rows descend; a row's links stay newest first.  A point range k..=k is scanned like any
+ * other: the reference routes it through GetIterator, which does not fold a tombstone base's timestamps;
+ * callers who need that call sdb_lsm_get_merge.  Capacity (rule 6, extended): candidates, then rows, then
+ * links.  While candidates or rows do not fit the chain summary reports SDB_LIMIT_EXCEEDED (num_links is the
+ * true total once the candidates fit) and neither chain_start nor a link column is written.  When the rows
+ * fit but num_links > cap_links: the chain summary reports SDB_LIMIT_EXCEEDED with the true total, chain_start
+ * is valid, no link column is written and the row columns are complete.  SDB_MERGE_OPERATOR_MISSING never
+ * comes out of this entry point.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct sdb_chain_summary {
+    uint64_t num_links;              /* links the call needs, also when above cap_links */
+    uint64_t max_chain_len;
+    int32_t status;                  /* SDB_OK | SDB_LIMIT_EXCEEDED */
+    uint32_t pad;
+} sdb_chain_summary;
+typedef struct sdb_chain_out {       /* device arrays; CSR over the call's queries (get) or rows (scan) */
+    uint64_t *chain_start;           /* count + 1: links of item i are [chain_start[i], chain_start[i + 1]) */
+    uint32_t *sst;                   /* per link: index into lsm->ssts */
+    uint32_t *block;
+    uint64_t *val_off;               /* ssts[sst].data[val_off .. val_off + val_len) */
+    uint32_t *val_len;
+    uint64_t *seq;
+    uint8_t *flags;                  /* RowFlags of the link's row */
+    int64_t *create_ts;              /* valid iff flags & HAS_CREATE_TS */
+    int64_t *expire_ts;              /* valid iff flags & HAS_EXPIRE_TS */
+    uint64_t cap_links;
+    sdb_chain_summary *summary;      /* device-writable */
+} sdb_chain_out;
+uint64_t sdb_lsm_get_merge_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys);
+sdb_status sdb_lsm_get_merge(const sdb_lsm_view *lsm, const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
+                             const uint64_t *max_seq /* device, nkeys; NULL = no bound */, const sdb_get_out *out,
+                             const sdb_chain_out *chain, void *workspace, uint64_t workspace_bytes, void *stream);
+uint64_t sdb_lsm_scan_merge_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs,
+                                            uint64_t nranges, uint64_t cand_entries, uint64_t cand_key_bytes);
+sdb_status sdb_lsm_scan_merge(const sdb_lsm_view *lsm, const sdb_scan_ranges *ranges,
+                              const uint64_t *max_seq /* device, n; NULL = no bound */, int32_t descending,
+                              uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out *out,
+                              const sdb_chain_out *chain, void *workspace, uint64_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Compaction (device): the output side of CompactionExecutor::run_subcompaction_merge

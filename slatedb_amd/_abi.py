@@ -17,13 +17,15 @@ SDB_INVALID_ARGUMENT = 8
 SDB_CORRUPT_BLOCK = 9
 SDB_MERGE_OPERATOR_MISSING = 10
 SDB_DECOMPRESSION_ERROR = 11
+SDB_INVALID_SEQUENCE_ORDER = 12
 SDB_DEVICE_ERROR = 100
 CODEC_NONE, CODEC_SNAPPY, CODEC_ZLIB, CODEC_LZ4, CODEC_ZSTD = 0, 1, 2, 3, 4  # CompressionFormat
 
 STATUS_NAMES = {
     0: "OK", 1: "EMPTY_KEY", 2: "EMPTY_BLOCK", 3: "CHECKSUM_MISMATCH", 4: "INVALID_ROW_FLAGS",
     5: "INVALID_VERSION", 6: "LIMIT_EXCEEDED", 7: "UNSUPPORTED", 8: "INVALID_ARGUMENT",
-    9: "CORRUPT_BLOCK", 10: "MERGE_OPERATOR_MISSING", 11: "DECOMPRESSION_ERROR", 100: "DEVICE_ERROR",
+    9: "CORRUPT_BLOCK", 10: "MERGE_OPERATOR_MISSING", 11: "DECOMPRESSION_ERROR",
+    12: "INVALID_SEQUENCE_ORDER", 100: "DEVICE_ERROR",
 }
 
 KIND_VALUE, KIND_MERGE, KIND_TOMBSTONE = 0, 1, 2
@@ -217,6 +219,18 @@ class LsmScanOut(C.Structure):
     ]
 
 
+class ChainSummary(C.Structure):
+    _fields_ = [("num_links", C.c_uint64), ("max_chain_len", C.c_uint64), ("status", C.c_int32), ("pad", C.c_uint32)]
+
+
+class ChainOut(C.Structure):
+    _fields_ = [
+        ("chain_start", C.c_void_p), ("sst", C.c_void_p), ("block", C.c_void_p), ("val_off", C.c_void_p),
+        ("val_len", C.c_void_p), ("seq", C.c_void_p), ("flags", C.c_void_p), ("create_ts", C.c_void_p),
+        ("expire_ts", C.c_void_p), ("cap_links", C.c_uint64), ("summary", C.c_void_p),
+    ]
+
+
 class Run(C.Structure):
     _fields_ = [
         ("n", C.c_uint64), ("key_arena", C.c_void_p), ("key_off", C.c_void_p),
@@ -333,6 +347,14 @@ SIGNATURES = {
                                                   C.c_uint64]),
     "sdb_lsm_scan": (C.c_int, [C.POINTER(LsmView), C.POINTER(ScanRanges), C.c_void_p, C.c_int32, C.c_uint64,
                                C.c_uint64, C.POINTER(LsmScanOut), C.c_void_p, C.c_uint64, C.c_void_p]),
+    "sdb_lsm_get_merge_workspace_bytes": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64]),
+    "sdb_lsm_get_merge": (C.c_int, [C.POINTER(LsmView), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                    C.POINTER(GetOut), C.POINTER(ChainOut), C.c_void_p, C.c_uint64, C.c_void_p]),
+    "sdb_lsm_scan_merge_workspace_bytes": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
+                                                        C.c_uint64]),
+    "sdb_lsm_scan_merge": (C.c_int, [C.POINTER(LsmView), C.POINTER(ScanRanges), C.c_void_p, C.c_int32, C.c_uint64,
+                                     C.c_uint64, C.POINTER(LsmScanOut), C.POINTER(ChainOut), C.c_void_p, C.c_uint64,
+                                     C.c_void_p]),
     "sdb_merge_runs_workspace_bytes":(C.c_uint64, [C.POINTER(Run), C.c_uint32]),
     "sdb_merge_runs": (C.c_int, [C.POINTER(Run), C.c_uint32, C.POINTER(Retention), C.POINTER(MergedOut),
                                  C.c_void_p, C.c_uint64, C.c_void_p]),

@@ -25,10 +25,14 @@ uint64_t scan_workspace_bytes(uint64_t num_blocks, uint64_t nranges);
 hipError_t launch_scan(const sdb_sst_view &v, const sdb_scan_ranges &r, uint32_t desc, const sdb_scan_out &out, uint8_t *w,
                        hipStream_t st);
 uint64_t lsm_scan_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint64_t nranges, uint64_t cand_entries,
-                                  uint64_t cand_key_bytes);
+                                  uint64_t cand_key_bytes, bool merge);
 hipError_t launch_lsm_scan(const sdb_lsm_view &t, const sdb_scan_ranges &r, const uint64_t *max_seq, uint32_t desc,
-                           uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out &out, uint8_t *w,
-                           hipStream_t st);
+                           uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out &out,
+                           const sdb_chain_out *chain, uint8_t *w, hipStream_t st);
+uint64_t get_merge_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys);
+hipError_t launch_get_merge(const sdb_lsm_view &t, const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
+                            const uint64_t *max_seq, const sdb_get_out &out, const sdb_chain_out &chain, uint8_t *w,
+                            hipStream_t st);
 uint64_t get_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys);
 hipError_t launch_get(const sdb_lsm_view &t, const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
                       const uint64_t *max_seq, const sdb_get_out &out, uint8_t *w, hipStream_t st);
@@ -91,6 +95,7 @@ const char *sdb_status_name(int s) {
         case SDB_CORRUPT_BLOCK: return "CORRUPT_BLOCK";
         case SDB_MERGE_OPERATOR_MISSING: return "MERGE_OPERATOR_MISSING";
         case SDB_DECOMPRESSION_ERROR: return "DECOMPRESSION_ERROR";
+        case SDB_INVALID_SEQUENCE_ORDER: return "INVALID_SEQUENCE_ORDER";
         case SDB_DEVICE_ERROR: return "DEVICE_ERROR";
         default: return "UNKNOWN";
     }
@@ -654,16 +659,57 @@ sdb_status sdb_lsm_get(const sdb_lsm_view *lsm, const uint8_t *key_bytes, const 
     return SDB_OK;
 }
 
+// NULL: nothing missing.  The CSR offsets and the summary always, the link columns where there is room for a link.
+static bool chain_ok(const sdb_chain_out *c) {
+    if (!c || !c->chain_start || !c->summary) return false;
+    return !c->cap_links || (c->sst && c->block && c->val_off && c->val_len && c->seq && c->flags && c->create_ts &&
+                             c->expire_ts);
+}
+
+uint64_t sdb_lsm_get_merge_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys) {
+    return get_merge_workspace_bytes(total_blocks, num_ssts, num_runs, nkeys) + 256;
+}
+
+sdb_status sdb_lsm_get_merge(const sdb_lsm_view *lsm, const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
+                             const uint64_t *max_seq, const sdb_get_out *out, const sdb_chain_out *chain, void *workspace,
+                             uint64_t workspace_bytes, void *stream) {
+    if (!lsm || !out || !chain) return SDB_INVALID_ARGUMENT;
+    if (lsm->num_runs && nkeys > (1ull << 40) / lsm->num_runs) return SDB_LIMIT_EXCEEDED;  // as sdb_lsm_get
+    sdb_status st = check_tree(lsm);
+    if (st) return st;
+    if (!out->summary || !chain_ok(chain)) return SDB_INVALID_ARGUMENT;
+    if (nkeys && (!key_bytes || !key_off || !out->state || !out->status || !out->sst || !out->block || !out->val_off ||
+                  !out->val_len || !out->seq || !out->flags || !out->create_ts || !out->expire_ts || !out->ssts_read ||
+                  !out->ssts_filtered))
+        return SDB_INVALID_ARGUMENT;
+    if (!workspace ||
+        workspace_bytes < sdb_lsm_get_merge_workspace_bytes(lsm->total_blocks, lsm->num_ssts, lsm->num_runs, nkeys))
+        return SDB_INVALID_ARGUMENT;
+    if (!device_ok()) return SDB_DEVICE_ERROR;
+    uint8_t *w = ws_align(workspace);
+    if (launch_get_merge(*lsm, key_bytes, key_off, nkeys, max_seq, *out, *chain, w, S(stream)) != hipSuccess)
+        return SDB_DEVICE_ERROR;
+    return SDB_OK;
+}
+
 uint64_t sdb_lsm_scan_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nranges,
                                       uint64_t cand_entries, uint64_t cand_key_bytes) {
     (void)num_runs;  // runs only fix the search order: the workspace is per (range, SST)
-    return lsm_scan_workspace_bytes(total_blocks, num_ssts, nranges, cand_entries, cand_key_bytes) + 256;
+    return lsm_scan_workspace_bytes(total_blocks, num_ssts, nranges, cand_entries, cand_key_bytes, false) + 256;
 }
 
-sdb_status sdb_lsm_scan(const sdb_lsm_view *lsm, const sdb_scan_ranges *ranges, const uint64_t *max_seq,
-                        int32_t descending, uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out *out,
-                        void *workspace, uint64_t workspace_bytes, void *stream) {
-    if (!lsm || !ranges || !out) return SDB_INVALID_ARGUMENT;
+uint64_t sdb_lsm_scan_merge_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs,
+                                            uint64_t nranges, uint64_t cand_entries, uint64_t cand_key_bytes) {
+    (void)num_runs;
+    return lsm_scan_workspace_bytes(total_blocks, num_ssts, nranges, cand_entries, cand_key_bytes, true) + 256;
+}
+
+// sdb_lsm_scan (chain == NULL, merge == false) and sdb_lsm_scan_merge: one set of argument checks, in one order.
+static sdb_status lsm_scan_call(const sdb_lsm_view *lsm, const sdb_scan_ranges *ranges, const uint64_t *max_seq,
+                                int32_t descending, uint64_t cand_entries, uint64_t cand_key_bytes,
+                                const sdb_lsm_scan_out *out, bool merge, const sdb_chain_out *chain, void *workspace,
+                                uint64_t workspace_bytes, void *stream) {
+    if (!lsm || !ranges || !out || (merge && !chain)) return SDB_INVALID_ARGUMENT;
     const uint64_t n = ranges->n;
     // (the limits all give one status, so these may come before the tree's)
     if (lsm->num_ssts && n > (1ull << 40) / lsm->num_ssts) return SDB_LIMIT_EXCEEDED;  // per (range, SST) state
@@ -676,15 +722,31 @@ sdb_status sdb_lsm_scan(const sdb_lsm_view *lsm, const sdb_scan_ranges *ranges, 
     if (out->cap_entries && (!out->sst || !out->val_off || !out->val_len || !out->seq || !out->flags ||
                              !out->create_ts || !out->expire_ts))
         return SDB_INVALID_ARGUMENT;
-    if (!workspace || workspace_bytes < sdb_lsm_scan_workspace_bytes(lsm->total_blocks, lsm->num_ssts, lsm->num_runs, n,
-                                                                     cand_entries, cand_key_bytes))
+    if (merge && !chain_ok(chain)) return SDB_INVALID_ARGUMENT;
+    if (!workspace ||
+        workspace_bytes < lsm_scan_workspace_bytes(lsm->total_blocks, lsm->num_ssts, n, cand_entries, cand_key_bytes, merge) + 256)
         return SDB_INVALID_ARGUMENT;
     if (!device_ok()) return SDB_DEVICE_ERROR;
     uint8_t *w = ws_align(workspace);
-    if (launch_lsm_scan(*lsm, *ranges, max_seq, descending ? 1u : 0u, cand_entries, cand_key_bytes, *out, w, S(stream)) !=
-        hipSuccess)
+    if (launch_lsm_scan(*lsm, *ranges, max_seq, descending ? 1u : 0u, cand_entries, cand_key_bytes, *out,
+                        merge ? chain : nullptr, w, S(stream)) != hipSuccess)
         return SDB_DEVICE_ERROR;
     return SDB_OK;
+}
+
+sdb_status sdb_lsm_scan(const sdb_lsm_view *lsm, const sdb_scan_ranges *ranges, const uint64_t *max_seq,
+                        int32_t descending, uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out *out,
+                        void *workspace, uint64_t workspace_bytes, void *stream) {
+    return lsm_scan_call(lsm, ranges, max_seq, descending, cand_entries, cand_key_bytes, out, false, nullptr, workspace,
+                         workspace_bytes, stream);
+}
+
+sdb_status sdb_lsm_scan_merge(const sdb_lsm_view *lsm, const sdb_scan_ranges *ranges, const uint64_t *max_seq,
+                              int32_t descending, uint64_t cand_entries, uint64_t cand_key_bytes,
+                              const sdb_lsm_scan_out *out, const sdb_chain_out *chain, void *workspace,
+                              uint64_t workspace_bytes, void *stream) {
+    return lsm_scan_call(lsm, ranges, max_seq, descending, cand_entries, cand_key_bytes, out, true, chain, workspace,
+                         workspace_bytes, stream);
 }
 
 }  // extern "C"

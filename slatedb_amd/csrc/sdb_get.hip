@@ -32,6 +32,7 @@
 //                   records behind it are never looked at, so their block errors never surface; one row
 //                   re-parsed for the columns; wave reduction + one atomic per counter and workgroup
 //   k_get_final     the summary
+#include "sdb_decode.h"
 #include "sdb_read.h"
 
 namespace sdb {
@@ -48,6 +49,21 @@ struct RunRec {
     uint16_t nread, nfilt;
     uint8_t st, hit, pad[2];
 };
+// sdb_lsm_get_merge, k_gm_walk -> k_gm_resolve -> k_gm_emit: what the run contributes to the key's operand chain,
+// its visible versions up to and including the first that is no operand.  hit: the first of them, of any kind, at
+// `at` of block `block` of `sst`; nlinks: the operands and the value among them; end: how the run ended the chain;
+// seq0 / maxseq: the first link's seq and the highest; has / cts / ets: MergeTracker over the links (the flag bits
+// of the timestamps seen, the maximum create_ts, the minimum expire_ts).  The resolve adds off, the links of the
+// runs before this one, and use, for the runs the query's chain takes.
+enum { kEndOpen = 0, kEndValue = 1, kEndTombstone = 2 };
+struct MergeRec {
+    uint64_t seq0, maxseq, off;
+    int64_t cts, ets;
+    uint32_t sst, block, at, nlinks;
+    uint16_t nread, nfilt;
+    uint8_t st, hit, end, has, use, pad[3];
+};
+enum { kMaccMaxChain = 0, kMaccGo, kMaccWords };
 struct GetArgs {
     sdb_lsm_view t;
     const uint8_t *key_bytes;
@@ -62,6 +78,12 @@ struct GetArgs {
     RunRec *rec;               // per pair: see RunRec
     unsigned long long *acc;   // kAcc* accumulators
     uint32_t *bad;             // 1 = the tree is malformed
+    // sdb_lsm_get_merge only
+    sdb_chain_out chain;
+    MergeRec *mrec;            // per pair: see MergeRec
+    uint64_t *qn, *qscan;      // per query: its links; the second output of their scan (the first is chain_start)
+    uint64_t *tx, *ty;         // scan tiles
+    unsigned long long *macc;  // kMacc* words
 };
 enum { kAccFound = 0, kAccDeleted, kAccNotFound, kAccMerge, kAccFailed, kAccBlocks, kAccFirstBad, kAccWords };
 
@@ -178,9 +200,10 @@ struct Hit {
     uint32_t block, at;
 };
 
-// The first entry of blocks [start, end) of one SST, in physical order, with key == k and seq <= bound.
-SDB_DEV int get_walk(const sdb_sst_view &v, const Step &s, const Key &k, uint64_t bound, Hit &H) {
-    H.ok = false;
+// Every entry of blocks [start, end) of one SST with key == k and seq <= bound, in physical order:
+// visit(block, its Blk, position, row) -> false: stop (done).
+template <typename F>
+SDB_DEV int get_versions(const sdb_sst_view &v, const Step &s, const Key &k, uint64_t bound, bool &done, F &&visit) {
     const bool v2 = v.sst_version == 2;
     for (uint32_t blk = s.start; blk < s.end; blk++) {
         Blk b;
@@ -193,13 +216,11 @@ SDB_DEV int get_walk(const sdb_sst_view &v, const Step &s, const Key &k, uint64_
             return st;
         }
         while (P.ok) {  // entries from P on while they hold the key
-            if (P.key.c > 0) return 0;  // past the key: this SST has no visible version
+            if (P.key.c > 0) return 0;  // past the key: this SST has no further version
             Row r;
             if (int st = v2 ? v2_row(b, P.at, r) : v1_row(b, P.at, r)) return st;
-            if (P.key.c == 0 && r.seq <= bound) {
-                H.ok = true;
-                H.block = blk;
-                H.at = P.at;
+            if (P.key.c == 0 && r.seq <= bound && !visit(blk, b, P.at, r)) {
+                done = true;
                 return 0;
             }
             if (int st = next_entry(v2, b, r, k.t, k.nt, P)) return st;
@@ -208,50 +229,82 @@ SDB_DEV int get_walk(const sdb_sst_view &v, const Step &s, const Key &k, uint64_
     return 0;
 }
 
+// The walk of pair t: the visible versions of query t % nkeys in the covering SSTs of run t / nkeys, in chain order,
+// every block of an SST's range checked before its rows are used: visit(sst, block, its Blk, position, row) ->
+// false: stop.  -> the status that ends the walk; nread / nfilt: the SSTs consulted / filtered up to there.
+template <typename F>
+SDB_DEV int walk_pair(const GetArgs &a, uint64_t t, uint8_t rs, uint32_t &nread, uint32_t &nfilt, F &&visit) {
+    const uint64_t q = t % a.nkeys;
+    const Key k = key_of(a, q);
+    const uint64_t bound = a.max_seq ? a.max_seq[q] : ~0ull;
+    int st = 0;
+    bool done = false;
+    auto search = [&](uint32_t i, const sdb_sst_view &v, const Step &s) {  // false: the walk is over
+        if (s.end <= s.start) return true;
+        nread++;
+        const uint64_t base = a.t.block_base[i];
+        for (uint32_t b = s.start; b < s.end && !st; b++) st = a.bstat[base + b];  // the lowest failing block
+        if (st < 0) st = SDB_INVALID_ARGUMENT;  // unreachable: locate marked this range
+        if (!st)
+            st = get_versions(v, s, k, bound, done,
+                              [&](uint32_t blk, const Blk &b, uint32_t at, const Row &r) { return visit(i, blk, b, at, r); });
+        return !st && !done;
+    };
+    if (rs == kRunOpen1) {
+        const RunRec in = a.rec[t];
+        const sdb_sst_view v = a.t.ssts[in.sst];
+        search(in.sst, v, Step{false, 0, in.block, in.at});
+    } else {
+        const uint64_t h = siphash13(k.t, k.nt);
+        uint32_t first = 0, last = 0;
+        bool go = get_run(a, (uint32_t)(t / a.nkeys), k, first, last);
+        for (uint32_t i = first; go && i <= last; i++) {
+            const sdb_sst_view v = a.t.ssts[i];
+            const Step s = get_step(a, v, i, k, h);
+            if (s.filtered) nfilt++;
+            else if ((st = s.st)) go = false;
+            else go = search(i, v, s);
+        }
+    }
+    return st;
+}
+
 __global__ __launch_bounds__(64) void k_get_walk(GetArgs a) {
     if (*a.bad) return;
-    const uint32_t R = a.t.num_runs;
-    const uint64_t total = a.nkeys * R;
+    const uint64_t total = a.nkeys * a.t.num_runs;
     for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x) {
         const uint8_t rs = a.rstate[t];
         if (rs != kRunOpen && rs != kRunOpen1) continue;
-        const uint64_t q = t % a.nkeys;
-        const Key k = key_of(a, q);
-        const uint64_t bound = a.max_seq ? a.max_seq[q] : ~0ull;
-        int st = 0;
         uint32_t sst = 0xFFFFFFFFu, nread = 0, nfilt = 0;
         Hit H;
         H.ok = false;
-        auto search = [&](uint32_t i, const sdb_sst_view &v, const Step &s) {  // false: the run is decided
-            if (s.end <= s.start) return true;
-            nread++;
-            const uint64_t base = a.t.block_base[i];
-            for (uint32_t b = s.start; b < s.end && !st; b++) st = a.bstat[base + b];  // the lowest failing block
-            if (st < 0) st = SDB_INVALID_ARGUMENT;  // unreachable: locate marked this range
-            if (!st) st = get_walk(v, s, k, bound, H);
-            if (H.ok) sst = i;
-            return !st && !H.ok;
-        };
-        if (rs == kRunOpen1) {
-            const RunRec in = a.rec[t];
-            const sdb_sst_view v = a.t.ssts[in.sst];
-            search(in.sst, v, Step{false, 0, in.block, in.at});
-        } else {
-            const uint64_t h = siphash13(k.t, k.nt);
-            uint32_t first = 0, last = 0;
-            bool go = get_run(a, (uint32_t)(t / a.nkeys), k, first, last);
-            for (uint32_t i = first; go && i <= last; i++) {
-                const sdb_sst_view v = a.t.ssts[i];
-                const Step s = get_step(a, v, i, k, h);
-                if (s.filtered) nfilt++;
-                else if ((st = s.st)) go = false;
-                else go = search(i, v, s);
-            }
-        }
+        const int st = walk_pair(a, t, rs, nread, nfilt, [&](uint32_t i, uint32_t blk, const Blk &, uint32_t at, const Row &) {
+            H.ok = true;  // the first visible version decides
+            H.block = blk;
+            H.at = at;
+            sst = i;
+            return false;
+        });
         RunRec out{sst, H.ok ? H.block : 0, H.ok ? H.at : 0, (uint16_t)(nread > 0xFFFF ? 0xFFFF : nread),
                    (uint16_t)(nfilt > 0xFFFF ? 0xFFFF : nfilt), (uint8_t)st, (uint8_t)(H.ok && !st), {0, 0}};
         a.rec[t] = out;
     }
+}
+
+// The summary's counters of a wave of one-lane workgroups' queries (every lane calls it): ballots and one atomic per
+// counter, the lowest failing query by atomicMin on query << 8 | status.
+SDB_DEV void get_count(const GetArgs &a, uint64_t q, bool live, uint32_t state, bool failed, int st) {
+    const unsigned long long nf = __ballot(live && state == SDB_GET_FOUND), nd = __ballot(live && state == SDB_GET_DELETED),
+                             nm = __ballot(live && state == SDB_GET_MERGE_OPERAND), nx = __ballot(failed),
+                             nn = __ballot(live && state == SDB_GET_NOT_FOUND && !failed);
+    if (threadIdx.x == 0) {
+        if (nf) atomicAdd(&a.acc[kAccFound], (unsigned long long)__popcll(nf));
+        if (nd) atomicAdd(&a.acc[kAccDeleted], (unsigned long long)__popcll(nd));
+        if (nm) atomicAdd(&a.acc[kAccMerge], (unsigned long long)__popcll(nm));
+        if (nn) atomicAdd(&a.acc[kAccNotFound], (unsigned long long)__popcll(nn));
+        if (nx) atomicAdd(&a.acc[kAccFailed], (unsigned long long)__popcll(nx));
+    }
+    if (failed) atomicMin(&a.acc[kAccFirstBad], (unsigned long long)(q << 8 | (uint64_t)st));
 }
 
 __global__ __launch_bounds__(64) void k_get_resolve(GetArgs a) {
@@ -314,21 +367,10 @@ __global__ __launch_bounds__(64) void k_get_resolve(GetArgs a) {
         a.out.ssts_filtered[q] = nfilt;
     }
     const bool failed = live && st != 0 && state == SDB_GET_NOT_FOUND;
-    const unsigned long long nf = __ballot(live && state == SDB_GET_FOUND), nd = __ballot(live && state == SDB_GET_DELETED),
-                             nm = __ballot(live && state == SDB_GET_MERGE_OPERAND), nx = __ballot(failed),
-                             nn = __ballot(live && state == SDB_GET_NOT_FOUND && !failed);
-    if (threadIdx.x == 0) {
-        if (nf) atomicAdd(&a.acc[kAccFound], (unsigned long long)__popcll(nf));
-        if (nd) atomicAdd(&a.acc[kAccDeleted], (unsigned long long)__popcll(nd));
-        if (nm) atomicAdd(&a.acc[kAccMerge], (unsigned long long)__popcll(nm));
-        if (nn) atomicAdd(&a.acc[kAccNotFound], (unsigned long long)__popcll(nn));
-        if (nx) atomicAdd(&a.acc[kAccFailed], (unsigned long long)__popcll(nx));
-    }
-    if (failed) atomicMin(&a.acc[kAccFirstBad], (unsigned long long)(q << 8 | (uint64_t)st));
+    get_count(a, q, live, state, failed, st);
 }
 
-__global__ void k_get_final(GetArgs a) {
-    if (threadIdx.x != 0) return;
+SDB_DEV void get_summary(const GetArgs &a) {
     sdb_get_summary s{};
     s.num_found = a.acc[kAccFound];
     s.num_deleted = a.acc[kAccDeleted];
@@ -338,6 +380,9 @@ __global__ void k_get_final(GetArgs a) {
     s.blocks_checked = a.acc[kAccBlocks];
     s.status = a.acc[kAccFirstBad] == ~0ull ? 0 : (int32_t)(a.acc[kAccFirstBad] & 0xFF);
     *a.out.summary = s;
+}
+__global__ void k_get_final(GetArgs a) {
+    if (threadIdx.x == 0) get_summary(a);
 }
 
 // The workspace arrays of a get of a.nkeys keys over the tree a.t, bound into a from w; -> their size.
@@ -405,6 +450,243 @@ hipError_t launch_get(const sdb_lsm_view &t, const uint8_t *key_bytes, const uin
     hipLaunchKernelGGL(k_get_walk, dim3((uint32_t)wg), dim3(64), 0, st, a);
     hipLaunchKernelGGL(k_get_resolve, dim3((uint32_t)((n + 63) / 64)), dim3(64), 0, st, a);
     hipLaunchKernelGGL(k_get_final, dim3(1), dim3(64), 0, st, a);
+    return hipGetLastError();
+}
+
+// =================================================================================================
+// sdb_lsm_get_merge: the same chain of SSTs, walked past the first entry while the entries are merge operands
+// (MergeOperatorIterator::merge_with_older_entries over GetIterator, merge_operator.rs:369-448, db_iter.rs:102-124).
+// Validate, locate, k_check and k_get_rows are those above, and the walk of a pair is walk_pair; then
+//   k_gm_walk     thread per (query, run) with an unfiltered covering SST: the count walk -> the pair's MergeRec
+//   k_gm_resolve  thread per query: the runs in order up to the first that ended the chain or failed; the sequence
+//                 order, the aggregates, the per-query columns, each run's link offset, the query's link count
+//   scan          the link counts -> chain_start
+//   k_gm_final    both summaries, do the links fit
+//   k_gm_emit     thread per pair the chain takes: the walk again, its links written at chain_start[q] + off
+// =================================================================================================
+
+__global__ __launch_bounds__(64) void k_gm_walk(GetArgs a) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) a.macc[kMaccMaxChain] = a.macc[kMaccGo] = 0;
+    if (*a.bad) return;
+    const uint64_t total = a.nkeys * a.t.num_runs;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x) {
+        const uint8_t rs = a.rstate[t];
+        if (rs != kRunOpen && rs != kRunOpen1) continue;
+        MergeRec m{};
+        uint32_t nread = 0, nfilt = 0;
+        const int st = walk_pair(a, t, rs, nread, nfilt, [&](uint32_t i, uint32_t blk, const Blk &, uint32_t at, const Row &r) {
+            if (!m.hit) {
+                m.hit = 1;
+                m.sst = i;
+                m.block = blk;
+                m.at = at;
+            }
+            if (r.flags & SDB_FLAG_TOMBSTONE) {  // ends the chain and is no link (GetIterator returns None, db_iter.rs:108-114)
+                m.end = kEndTombstone;
+                return false;
+            }
+            if (!m.nlinks) m.seq0 = r.seq;
+            if (m.nlinks != 0xFFFFFFFFu) m.nlinks++;
+            if (r.seq > m.maxseq) m.maxseq = r.seq;
+            if (r.flags & SDB_FLAG_HAS_CREATE_TS) {  // MergeTracker::update (merge_operator.rs:289-292)
+                m.cts = (m.has & SDB_FLAG_HAS_CREATE_TS) && m.cts > r.cts ? m.cts : r.cts;
+                m.has |= SDB_FLAG_HAS_CREATE_TS;
+            }
+            if (r.flags & SDB_FLAG_HAS_EXPIRE_TS) {
+                m.ets = (m.has & SDB_FLAG_HAS_EXPIRE_TS) && m.ets < r.ets ? m.ets : r.ets;
+                m.has |= SDB_FLAG_HAS_EXPIRE_TS;
+            }
+            if (!(r.flags & SDB_FLAG_MERGE_OPERAND)) {  // the base value: the last link
+                m.end = kEndValue;
+                return false;
+            }
+            return true;
+        });
+        m.st = (uint8_t)st;
+        m.nread = (uint16_t)(nread > 0xFFFF ? 0xFFFF : nread);
+        m.nfilt = (uint16_t)(nfilt > 0xFFFF ? 0xFFFF : nfilt);
+        a.mrec[t] = m;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_gm_resolve(GetArgs a) {
+    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = q < a.nkeys;
+    int st = 0;
+    uint32_t state = SDB_GET_NOT_FOUND;
+    if (live) {
+        uint32_t sst = 0xFFFFFFFFu, nread = 0, nfilt = 0;
+        Hit H;
+        H.ok = false;
+        Row r{};
+        uint64_t vbase = 0, links = 0, newest = 0;
+        int64_t cts = 0, ets = 0;
+        uint8_t has = 0, end = kEndOpen;
+        if (*a.bad) {
+            st = SDB_INVALID_ARGUMENT;
+        } else {
+            const uint32_t R = a.t.num_runs;
+            for (uint32_t j = 0; j < R && !st && !end; j++) {  // the runs in order until one ends the chain or fails
+                const uint8_t rs = a.rstate[j * a.nkeys + q];
+                if (rs == kRunFiltered) nfilt++;
+                if (rs != kRunOpen && rs != kRunOpen1) continue;
+                MergeRec &x = a.mrec[j * a.nkeys + q];
+                nread += x.nread;
+                nfilt += x.nfilt;
+                if (x.hit && !H.ok) {
+                    H.ok = true;
+                    H.block = x.block;
+                    H.at = x.at;
+                    sst = x.sst;
+                }
+                if (x.nlinks) {
+                    if (!links) newest = x.seq0;
+                    if (x.maxseq > newest) {  // MergeTracker::update (merge_operator.rs:293-299)
+                        st = SDB_INVALID_SEQUENCE_ORDER;
+                        break;
+                    }
+                    if (x.has & SDB_FLAG_HAS_CREATE_TS) cts = (has & SDB_FLAG_HAS_CREATE_TS) && cts > x.cts ? cts : x.cts;
+                    if (x.has & SDB_FLAG_HAS_EXPIRE_TS) ets = (has & SDB_FLAG_HAS_EXPIRE_TS) && ets < x.ets ? ets : x.ets;
+                    has |= x.has;
+                    x.off = links;
+                    x.use = 1;
+                    links += x.nlinks;
+                }
+                st = x.st;
+                end = x.end;
+            }
+            if (H.ok && !st) {  // the first entry again, for its columns
+                const sdb_sst_view v = a.t.ssts[sst];
+                Blk b;
+                if (!(st = blk_open(v, H.block, b))) st = v.sst_version == 2 ? v2_row(b, H.at, r) : v1_row(b, H.at, r);
+                vbase = b.base;
+            }
+        }
+        if (st) {
+            H.ok = false;
+            links = 0;
+        }
+        if (H.ok) {
+            if (r.flags & SDB_FLAG_TOMBSTONE) {
+                state = SDB_GET_DELETED;
+            } else {  // the entry MergeOperatorIterator returns (merge_operator.rs:437-447)
+                const bool operand = (r.flags & SDB_FLAG_MERGE_OPERAND) != 0;
+                state = operand ? SDB_GET_MERGE_OPERAND : SDB_GET_FOUND;
+                r.flags = (uint8_t)(has | (operand && end != kEndValue ? SDB_FLAG_MERGE_OPERAND : 0));
+                r.cts = cts;
+                r.ets = ets;
+            }
+        } else {  // no entry: zero columns
+            sst = 0xFFFFFFFFu;
+            r = Row{};
+        }
+        a.out.state[q] = (uint8_t)state;
+        a.out.status[q] = st;
+        a.out.sst[q] = sst;
+        a.out.block[q] = H.ok ? H.block : 0;
+        put_row(a.out, q, vbase, r);
+        a.out.ssts_read[q] = nread;
+        a.out.ssts_filtered[q] = nfilt;
+        a.qn[q] = links;
+        if (links) atomicMax(&a.macc[kMaccMaxChain], (unsigned long long)links);
+    }
+    const bool failed = live && st != 0;
+    get_count(a, q, live, state, failed, st);
+}
+
+__global__ void k_gm_final(GetArgs a) {
+    if (threadIdx.x != 0) return;
+    get_summary(a);
+    sdb_chain_summary s{};
+    s.num_links = a.chain.chain_start[a.nkeys];
+    s.max_chain_len = a.macc[kMaccMaxChain];
+    const bool fits = s.num_links <= a.chain.cap_links;
+    s.status = fits ? SDB_OK : SDB_LIMIT_EXCEEDED;
+    *a.chain.summary = s;
+    a.macc[kMaccGo] = fits;
+}
+
+__global__ __launch_bounds__(64) void k_gm_emit(GetArgs a) {
+    if (*a.bad || !a.macc[kMaccGo]) return;
+    const uint64_t total = a.nkeys * a.t.num_runs;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x) {
+        const uint8_t rs = a.rstate[t];
+        if (rs != kRunOpen && rs != kRunOpen1) continue;
+        const uint64_t q = t % a.nkeys;
+        const uint32_t n = a.mrec[t].nlinks;
+        if (!a.mrec[t].use || !n || a.out.status[q]) continue;
+        const uint64_t at0 = a.chain.chain_start[q] + a.mrec[t].off;
+        uint32_t x = 0, nread = 0, nfilt = 0;
+        walk_pair(a, t, rs, nread, nfilt, [&](uint32_t i, uint32_t blk, const Blk &b, uint32_t, const Row &r) {
+            if (r.flags & SDB_FLAG_TOMBSTONE) return false;
+            const uint64_t d = at0 + x;
+            if (x >= n || d >= a.chain.cap_links) return false;  // never out of the pair's slots
+            a.chain.sst[d] = i;
+            a.chain.block[d] = blk;
+            put_row(a.chain, d, b.base, r);
+            x++;
+            return (r.flags & SDB_FLAG_MERGE_OPERAND) != 0 && x < n;
+        });
+    }
+}
+
+// The workspace arrays of a merging get: those of the get, then its own.
+static uint64_t get_merge_bind(GetArgs &a, uint8_t *w) {
+    const uint64_t pairs = a.nkeys * a.t.num_runs, n = a.nkeys;
+    Carver c{w, get_bind(a, w)};
+    c.take(a.mrec, pairs + 1);
+    c.take(a.qn, n + 1);
+    c.take(a.qscan, n + 2);
+    c.take(a.tx, (n + 1023) / 1024 + 2);
+    c.take(a.ty, (n + 1023) / 1024 + 2);
+    c.take(a.macc, kMaccWords);
+    return c.off;
+}
+
+uint64_t get_merge_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys) {
+    GetArgs a{};
+    a.t.total_blocks = total_blocks;
+    a.t.num_ssts = num_ssts;
+    a.t.num_runs = num_runs;
+    a.nkeys = nkeys;
+    return get_merge_bind(a, nullptr);
+}
+
+hipError_t launch_get_merge(const sdb_lsm_view &t, const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
+                            const uint64_t *max_seq, const sdb_get_out &out, const sdb_chain_out &chain, uint8_t *w,
+                            hipStream_t st) {
+    const uint64_t tb = t.total_blocks, n = nkeys;
+    hipError_t e;
+    if (n == 0 || t.num_ssts == 0 || t.num_runs == 0 || tb == 0) {  // no links; the columns as launch_get leaves them
+        if ((e = hipMemsetAsync(chain.summary, 0, sizeof(sdb_chain_summary), st)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(chain.chain_start, 0, 8 * (n + 1), st)) != hipSuccess) return e;
+        return launch_get(t, key_bytes, key_off, nkeys, max_seq, out, w, st);
+    }
+    if ((e = hipMemsetAsync(out.summary, 0, sizeof(sdb_get_summary), st)) != hipSuccess) return e;
+    GetArgs a{};
+    a.t = t;
+    a.key_bytes = key_bytes;
+    a.key_off = key_off;
+    a.nkeys = n;
+    a.max_seq = max_seq;
+    a.out = out;
+    a.chain = chain;
+    get_merge_bind(a, w);
+    if ((e = hipMemsetAsync(a.mark, 0, tb, st)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(a.bstat, 0xFF, 4 * tb, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_get_validate, dim3(1), dim3(256), 0, st, a);
+    uint64_t lg = (n * t.num_runs + 255) / 256;  // the kernels stride past these caps
+    if (lg > (1u << 20)) lg = 1u << 20;
+    hipLaunchKernelGGL(k_get_locate, dim3((uint32_t)lg), dim3(256), 0, st, a);
+    if ((e = launch_check(CheckArgs{{}, t, a.bad, tb, a.mark, a.bstat}, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_get_rows, dim3((uint32_t)((tb + 63) / 64)), dim3(64), 0, st, a);
+    uint64_t wg = (n * t.num_runs + 63) / 64;
+    if (wg > (1u << 22)) wg = 1u << 22;
+    hipLaunchKernelGGL(k_gm_walk, dim3((uint32_t)wg), dim3(64), 0, st, a);
+    hipLaunchKernelGGL(k_gm_resolve, dim3((uint32_t)((n + 63) / 64)), dim3(64), 0, st, a);
+    if ((e = launch_excl_scan2(a.qn, a.qn, n, a.tx, a.ty, chain.chain_start, a.qscan, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_gm_final, dim3(1), dim3(64), 0, st, a);
+    hipLaunchKernelGGL(k_gm_emit, dim3((uint32_t)wg), dim3(64), 0, st, a);
     return hipGetLastError();
 }
 

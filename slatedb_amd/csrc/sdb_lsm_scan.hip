@@ -39,6 +39,16 @@
 //   k_ls_count     thread per range: rule 4, the totals -> scans -> range_entry_start
 //   k_ls_final     summary, capacity check
 //   k_ls_emit      thread per winner: key and columns (the row parsed once more) at its place
+// sdb_lsm_scan_merge (merge != 0; MergeOperatorIterator over the same merge, merge_operator.rs:369-448) runs the same
+// sequence with an operand winner a row instead of a failure, and between k_ls_rank and the winner scan
+//   k_ls_links     thread per merged position: a winner's links, the contiguous stretch down to its key's first
+//                  non-operand, each position of it given its winner; a scan of the link counts
+// k_ls_final adds the chain summary (candidates, then rows, then links); then
+//   k_ls_fold      thread per merged position of a chain: the row parsed, folded into its winner's aggregates
+//                  (atomics), written as a link
+// and k_ls_emit takes a winner's chain_start, aggregates and flags from there.
+#include <climits>
+
 #include "sdb_range.h"
 #include "sdb_decode.h"
 
@@ -77,8 +87,16 @@ struct LsArgs {
     uint64_t *wn, *wkb, *wpos, *wkpos;  // winner flag / key bytes per merged position and their scans
     uint64_t *tx, *ty;              // scan tiles
     unsigned long long *ctl;        // kCtl* words
+    // sdb_lsm_scan_merge only
+    uint32_t merge, pad2;           // 1 = operands win and carry their chains
+    sdb_chain_out chain;
+    uint64_t *wl, *wlpos, *wldum;   // links per merged position (a winner's chain); their scan; its second output
+    uint64_t *lwin;                 // per merged position: the winner whose chain it belongs to (~0: none)
+    long long *wcts, *wets;         // per winner: MergeTracker's maximum create_ts / minimum expire_ts
+    uint32_t *whas;                 // per winner: the timestamp flag bits seen | kBase
 };
-enum { kCtlFirstBad = 0, kCtlFailed, kCtlBad, kCtlGo1, kCtlGo2, kCtlWords = 8 };
+enum { kBase = 0x100 };  // a value or a tombstone ended the chain
+enum { kCtlFirstBad = 0, kCtlFailed, kCtlBad, kCtlGo1, kCtlGo2, kCtlGo3, kCtlMaxChain, kCtlWords = 8 };
 
 __global__ __launch_bounds__(256) void k_ls_validate(LsArgs a) {
     const int bad = lsm_validate(a.t, a.sstat);
@@ -261,7 +279,15 @@ __global__ __launch_bounds__(64) void k_ls_rstat(LsArgs a) {
 __global__ __launch_bounds__(256) void k_ls_gate(LsArgs a) {
     const uint64_t t0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t0 == 0) a.ctl[kCtlGo1] = a.cs[a.pairs] <= a.cand_entries && a.cks[a.pairs] <= a.cand_key_bytes;
-    for (uint64_t m = t0; m < a.cand_entries; m += (uint64_t)gridDim.x * blockDim.x) a.wn[m] = a.wkb[m] = 0;
+    for (uint64_t m = t0; m < a.cand_entries; m += (uint64_t)gridDim.x * blockDim.x) {
+        a.wn[m] = a.wkb[m] = 0;
+        if (a.merge) {  // k_ls_links / k_ls_fold fill these
+            a.lwin[m] = ~0ull;
+            a.wcts[m] = LLONG_MIN;
+            a.wets[m] = LLONG_MAX;
+            a.whas[m] = 0;
+        }
+    }
 }
 
 __global__ __launch_bounds__(64) void k_ls_stage(LsArgs a) {
@@ -345,12 +371,59 @@ __global__ __launch_bounds__(64) void k_ls_rank(LsArgs a) {
         if (rank >= re - rs) continue;  // rows that are not sorted: never out of the range's slots
         const uint8_t f = a.cflags[c];
         a.morder[rs + rank] = c;
-        if (!lose && (f & SDB_FLAG_MERGE_OPERAND)) a.rop[r] = 1;
-        if (!lose && !(f & (SDB_FLAG_MERGE_OPERAND | SDB_FLAG_TOMBSTONE))) {  // k_ls_gate zeroed the flags
+        if (!lose && (f & SDB_FLAG_MERGE_OPERAND) && !a.merge) a.rop[r] = 1;
+        if (!lose && !(f & SDB_FLAG_TOMBSTONE) && (a.merge || !(f & SDB_FLAG_MERGE_OPERAND))) {  // k_ls_gate zeroed the flags
             a.wn[rs + rank] = 1;
             a.wkb[rs + rank] = nt;
         }
     }
+}
+
+// Candidate morder[mm] of range [rs, re) continues the chain of the winner at merged position m, whose key is t:
+// -> its index, or ~0 (a position the rank left unwritten, or another key).
+SDB_DEV uint64_t ls_chain_cand(const LsArgs &a, uint64_t rs, uint64_t re, uint64_t m, uint64_t mm, const uint8_t *t, uint32_t nt) {
+    const uint64_t c = a.morder[mm];
+    if (c < rs || c >= re) return ~0ull;
+    if (mm > m && !(a.cklen[c] == nt && ls_key_cmp(a, c, t, nt) == 0)) return ~0ull;
+    return c;
+}
+
+// sdb_lsm_scan_merge: the links of every winner: the contiguous stretch of the merged order from the winner to its
+// key's first non-operand, the tombstone excluded (merge_with_older_entries, merge_operator.rs:388-411).  The
+// versions behind a winner are visible: they are older than it.
+__global__ __launch_bounds__(64) void k_ls_links(LsArgs a) {
+    const uint32_t S = a.t.num_ssts;
+    const bool go = a.ctl[kCtlGo1] != 0;
+    const uint64_t total = go ? a.cs[a.pairs] : 0;
+    for (uint64_t m = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; m < a.cand_entries; m += (uint64_t)gridDim.x * blockDim.x) {
+        uint64_t n = 0;
+        if (m < total && a.wn[m]) {
+            const uint64_t r = last_le(a.cs, a.r.n, S, m), rs = a.cs[r * S], re = a.cs[(r + 1) * S], c0 = a.morder[m];
+            if (c0 >= rs && c0 < re) {
+                const uint8_t *t = a.ckeys + a.ckoff[c0];
+                const uint32_t nt = a.cklen[c0];
+                for (uint64_t mm = m; mm < re; mm++) {
+                    const uint64_t c = ls_chain_cand(a, rs, re, m, mm, t, nt);
+                    if (c == ~0ull) break;
+                    a.lwin[mm] = m;  // the links, and the tombstone behind them: k_ls_fold folds its timestamps
+                    if (a.cflags[c] & SDB_FLAG_TOMBSTONE) break;
+                    n++;
+                    if (!(a.cflags[c] & SDB_FLAG_MERGE_OPERAND)) break;
+                }
+            }
+            if (n) atomicMax(&a.ctl[kCtlMaxChain], (unsigned long long)n);
+        }
+        a.wl[m] = n;
+    }
+}
+
+// Where the links of the winner at merged position m of range r start: a range's rows descend with `desc`, a row's
+// links do not.
+SDB_DEV uint64_t ls_chain_start(const LsArgs &a, uint64_t r, uint64_t m) {
+    const uint32_t S = a.t.num_ssts;
+    const uint64_t rs = a.cs[r * S], re = a.cs[(r + 1) * S];
+    const uint64_t before = a.wlpos[m] - a.wlpos[rs], all = a.wlpos[re] - a.wlpos[rs];
+    return a.wlpos[rs] + (a.desc ? all - before - a.wl[m] : before);
 }
 
 __global__ __launch_bounds__(64) void k_ls_count(LsArgs a) {
@@ -392,6 +465,48 @@ __global__ void k_ls_final(LsArgs a) {
     else a.out.key_off[s.num_entries] = s.key_bytes;
     *a.out.summary = s;
     a.ctl[kCtlGo2] = fits;
+    if (a.merge) {  // candidates, then rows, then links
+        sdb_chain_summary cs{};
+        cs.num_links = a.ctl[kCtlGo1] ? a.wlpos[a.cand_entries] : 0;
+        cs.max_chain_len = a.ctl[kCtlMaxChain];
+        const bool lfits = fits && cs.num_links <= a.chain.cap_links;
+        cs.status = lfits ? SDB_OK : SDB_LIMIT_EXCEEDED;
+        if (fits) a.chain.chain_start[s.num_entries] = cs.num_links;
+        *a.chain.summary = cs;
+        a.ctl[kCtlGo3] = lfits;
+    }
+}
+
+// sdb_lsm_scan_merge, thread per merged position that k_ls_links gave to a winner w: the row parsed, its timestamps
+// folded into w's aggregates (MergeTracker, merge_operator.rs:289-292; a tombstone base too, :421-425), and, unless it
+// is that tombstone, written as link (position - w) of w's chain where the links fit.
+__global__ __launch_bounds__(64) void k_ls_fold(LsArgs a) {
+    if (!a.ctl[kCtlGo2]) return;
+    const uint32_t S = a.t.num_ssts;
+    const bool put = a.ctl[kCtlGo3] != 0;
+    const uint64_t total = a.cs[a.pairs];
+    for (uint64_t m = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; m < total; m += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t w = a.lwin[m];
+        if (w == ~0ull) continue;
+        const uint64_t c = a.morder[m];
+        const uint32_t i = (uint32_t)(last_le(a.cs, a.pairs, 1, c) % S);
+        const sdb_sst_view v = a.t.ssts[i];
+        Blk b;
+        Row lr;
+        if (blk_open(v, a.cblk[c], b)) continue;
+        if (v.sst_version == 2 ? v2_row(b, a.cat[c], lr) : v1_row(b, a.cat[c], lr)) continue;
+        if (lr.flags & SDB_FLAG_HAS_CREATE_TS) atomicMax(&a.wcts[w], (long long)lr.cts);
+        if (lr.flags & SDB_FLAG_HAS_EXPIRE_TS) atomicMin(&a.wets[w], (long long)lr.ets);
+        const uint32_t has = (lr.flags & (SDB_FLAG_HAS_CREATE_TS | SDB_FLAG_HAS_EXPIRE_TS)) |
+                             ((lr.flags & SDB_FLAG_MERGE_OPERAND) ? 0u : (uint32_t)kBase);
+        if (has) atomicOr(&a.whas[w], has);
+        if ((lr.flags & SDB_FLAG_TOMBSTONE) || !put) continue;
+        const uint64_t x = m - w, d = ls_chain_start(a, last_le(a.cs, a.r.n, S, w), w) + x;
+        if (x >= a.wl[w] || d >= a.chain.cap_links) continue;  // never out of the winner's slots
+        a.chain.sst[d] = i;
+        a.chain.block[d] = a.cblk[c];
+        put_row(a.chain, d, b.base, lr);
+    }
 }
 
 __global__ __launch_bounds__(64) void k_ls_emit(LsArgs a) {
@@ -417,6 +532,13 @@ __global__ __launch_bounds__(64) void k_ls_emit(LsArgs a) {
         copy_bytes(a.out.key_arena + K0 + dk, a.ckeys + a.ckoff[c], L);
         a.out.key_off[E0 + di] = K0 + dk;
         a.out.sst[E0 + di] = i;
+        if (a.merge) {  // the entry MergeOperatorIterator returns (merge_operator.rs:437-447): k_ls_fold's aggregates
+            a.chain.chain_start[E0 + di] = ls_chain_start(a, r, m);
+            const uint32_t has = a.whas[m];
+            row.flags = (uint8_t)((has & 0xFF) | ((has & kBase) ? 0 : SDB_FLAG_MERGE_OPERAND));
+            row.cts = a.wcts[m];
+            row.ets = a.wets[m];
+        }
         put_row(a.out, E0 + di, b.base, row);
     }
 }
@@ -478,23 +600,40 @@ static uint64_t lsm_scan_bind(LsArgs &a, uint8_t *w) {
     return c.off;
 }
 
+// The workspace arrays of a merging scan: those of the scan, then its own.
+static uint64_t lsm_scan_merge_bind(LsArgs &a, uint8_t *w) {
+    Carver c{w, lsm_scan_bind(a, w)};
+    c.take(a.wl, a.cand_entries + 1);
+    c.take(a.wlpos, a.cand_entries + 2);
+    c.take(a.wldum, a.cand_entries + 2);
+    c.take(a.lwin, a.cand_entries + 1);
+    c.take(a.wcts, a.cand_entries + 1);
+    c.take(a.wets, a.cand_entries + 1);
+    c.take(a.whas, a.cand_entries + 1);
+    return c.off;
+}
+
 uint64_t lsm_scan_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint64_t nranges, uint64_t cand_entries,
-                                  uint64_t cand_key_bytes) {
+                                  uint64_t cand_key_bytes, bool merge) {
     LsArgs a{};
     a.t.total_blocks = total_blocks;
     a.t.num_ssts = num_ssts;
     a.r.n = nranges;
     a.cand_entries = cand_entries;
     a.cand_key_bytes = cand_key_bytes;
-    return lsm_scan_bind(a, nullptr);
+    return merge ? lsm_scan_merge_bind(a, nullptr) : lsm_scan_bind(a, nullptr);
 }
 
 hipError_t launch_lsm_scan(const sdb_lsm_view &t, const sdb_scan_ranges &r, const uint64_t *max_seq, uint32_t desc,
-                           uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out &out, uint8_t *w,
-                           hipStream_t st) {
+                           uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out &out,
+                           const sdb_chain_out *chain /* sdb_lsm_scan_merge, else nullptr */, uint8_t *w, hipStream_t st) {
     const uint64_t tb = t.total_blocks, n = r.n;
     hipError_t e;
     if (n == 0 || t.num_ssts == 0 || tb == 0) {  // every range is empty
+        if (chain) {
+            if ((e = hipMemsetAsync(chain->summary, 0, sizeof(sdb_chain_summary), st)) != hipSuccess) return e;
+            if ((e = hipMemsetAsync(chain->chain_start, 0, 8, st)) != hipSuccess) return e;
+        }
         if ((e = hipMemsetAsync(out.summary, 0, sizeof(sdb_lsm_scan_summary), st)) != hipSuccess) return e;
         if ((e = hipMemsetAsync(out.range_entry_start, 0, 8 * (n + 1), st)) != hipSuccess) return e;
         if (n && (e = hipMemsetAsync(out.range_status, 0, 4 * n, st)) != hipSuccess) return e;
@@ -509,7 +648,13 @@ hipError_t launch_lsm_scan(const sdb_lsm_view &t, const sdb_scan_ranges &r, cons
     a.desc = desc;
     a.cand_entries = cand_entries;
     a.cand_key_bytes = cand_key_bytes;
-    lsm_scan_bind(a, w);
+    if (chain) {
+        a.merge = 1;
+        a.chain = *chain;
+        lsm_scan_merge_bind(a, w);
+    } else {
+        lsm_scan_bind(a, w);
+    }
     const uint64_t P = a.pairs, ce = cand_entries;
     if ((e = hipMemsetAsync(a.mark, 0, tb, st)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(a.bstat, 0xFF, 4 * tb, st)) != hipSuccess) return e;
@@ -529,10 +674,15 @@ hipError_t launch_lsm_scan(const sdb_lsm_view &t, const sdb_scan_ranges &r, cons
     hipLaunchKernelGGL(k_ls_gate, dim3(scan_grid(ce, 256)), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_ls_stage, dim3(scan_grid(ce + P, 64)), dim3(64), 0, st, a);
     hipLaunchKernelGGL(k_ls_rank, dim3(scan_grid(ce, 64)), dim3(64), 0, st, a);
+    if (chain) {
+        hipLaunchKernelGGL(k_ls_links, dim3(scan_grid(ce, 64)), dim3(64), 0, st, a);
+        if ((e = launch_excl_scan2(a.wl, a.wl, ce, a.tx, a.ty, a.wlpos, a.wldum, st)) != hipSuccess) return e;
+    }
     if ((e = launch_excl_scan2(a.wn, a.wkb, ce, a.tx, a.ty, a.wpos, a.wkpos, st)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_ls_count, dim3(rw), dim3(64), 0, st, a);
     if ((e = launch_excl_scan2(a.rn, a.rkb, n, a.tx, a.ty, out.range_entry_start, a.rks, st)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_ls_final, dim3(1), dim3(64), 0, st, a);
+    if (chain) hipLaunchKernelGGL(k_ls_fold, dim3(scan_grid(ce, 64)), dim3(64), 0, st, a);
     hipLaunchKernelGGL(k_ls_emit, dim3(scan_grid(ce, 64)), dim3(64), 0, st, a);
     return hipGetLastError();
 }

@@ -824,13 +824,9 @@ def lsm_tree_device(views, runs, device=None):
     return t
 
 
-def lsm_get_device(views, runs, keys, max_seq=None, stream=None, workspace=None):
-    """sdb_lsm_get: a batch of Db::get over a device-resident tree.  views, runs: as lsm_tree_device, or
-    views = a tree lsm_tree_device built (runs is then ignored).  keys: a list of bytes, or device tensors
-    (key_bytes, key_off, nkeys).  max_seq: None (no bound), a list / array of nkeys bounds, or a device
-    int64 tensor.  workspace: a device uint8 tensor to use (and reuse) instead of a fresh one.  With device
-    tensors and a prebuilt tree the call copies nothing from the host, so it can be captured into a graph.  Returns a dict of device tensors (GET_FIELDS, and summary: the
-    sdb_get_summary words in GET_SUMMARY order); what the call allocated stays alive under "_" keys."""
+def _get_call(views, runs, keys, max_seq):
+    """What lsm_get_device and lsm_get_merge_device marshal alike: the tree, the keys and bounds as device tensors,
+    the result dict with the GET_FIELDS and the summary, and the sdb_get_out over them."""
     import torch
     tree = views if isinstance(views, dict) else lsm_tree_device(views, runs)
     dev = tree["device"]
@@ -845,6 +841,18 @@ def lsm_get_device(views, runs, keys, max_seq=None, stream=None, workspace=None)
     res = {f: torch.zeros(max(n, 1), dtype=getattr(torch, dt), device=dev) for f, dt in GET_FIELDS}
     res["summary"] = torch.zeros(len(GET_SUMMARY), dtype=torch.int64, device=dev)
     out = _abi.GetOut(*[res[f].data_ptr() for f, _ in GET_FIELDS], res["summary"].data_ptr())
+    return tree, dev, kb, ko, n, max_seq, res, out
+
+
+def lsm_get_device(views, runs, keys, max_seq=None, stream=None, workspace=None):
+    """sdb_lsm_get: a batch of Db::get over a device-resident tree.  views, runs: as lsm_tree_device, or
+    views = a tree lsm_tree_device built (runs is then ignored).  keys: a list of bytes, or device tensors
+    (key_bytes, key_off, nkeys).  max_seq: None (no bound), a list / array of nkeys bounds, or a device
+    int64 tensor.  workspace: a device uint8 tensor to use (and reuse) instead of a fresh one.  With device
+    tensors and a prebuilt tree the call copies nothing from the host, so it can be captured into a graph.  Returns a dict of device tensors (GET_FIELDS, and summary: the
+    sdb_get_summary words in GET_SUMMARY order); what the call allocated stays alive under "_" keys."""
+    import torch
+    tree, dev, kb, ko, n, max_seq, res, out = _get_call(views, runs, keys, max_seq)
     wsb = lib().sdb_lsm_get_workspace_bytes(tree["total_blocks"], tree["num_ssts"], tree["num_runs"], n)
     ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=dev)
     assert ws.numel() >= wsb, "workspace too small"
@@ -862,17 +870,23 @@ LSM_SCAN_SUMMARY = ("num_entries", "key_bytes", "num_candidates", "candidate_key
                     "blocks_checked", "status")
 
 
-def lsm_scan_device(tree, ranges, max_seq=None, descending=False, stream=None, workspace=None, cand=None, cap=None):
-    """sdb_lsm_scan: a batch of Db::scan over a device-resident tree.  tree: what lsm_tree_device built.
-    ranges: a list of (start, start_kind, end, end_kind), or a dict of device tensors named as
-    scan_ranges_columnar's arrays plus "n".  max_seq: None (no bound), a list / array of n bounds, or a device
-    int64 tensor.  cand: (cand_entries, cand_key_bytes), the staging capacity; cap: (cap_entries, key_arena_cap),
-    the column capacity.  With either None the call first runs without staging room, reads the candidate totals
-    (a host synchronisation), sizes both like the staging (num_entries <= num_candidates) and runs again; with
-    both given, device tensors for ranges and max_seq and a workspace it copies nothing from the host, so it can
-    be captured into a graph.  Returns a dict of device tensors: range_entry_start (n + 1), range_status,
-    range_ssts, key_arena, key_off, the LSM_SCAN_COLUMNS and summary (the sdb_lsm_scan_summary words in
-    LSM_SCAN_SUMMARY order); what the call allocated stays alive under "_" keys."""
+def _lsm_scan_out(res, cap_e, cap_k, dev):
+    """Fresh row columns for cap_e rows and cap_k key bytes in res, and the sdb_lsm_scan_out over res."""
+    import torch
+    res["key_arena"] = torch.zeros(max(cap_k, 1), dtype=torch.uint8, device=dev)
+    res["key_off"] = torch.zeros(cap_e + 1, dtype=torch.int64, device=dev)
+    for f, dt in LSM_SCAN_COLUMNS:
+        res[f] = torch.zeros(max(cap_e, 1), dtype=getattr(torch, dt), device=dev)
+    out = _abi.LsmScanOut(res["range_entry_start"].data_ptr(), res["range_status"].data_ptr(),
+                          res["range_ssts"].data_ptr(), res["key_arena"].data_ptr(), cap_k,
+                          res["key_off"].data_ptr(), *[res[f].data_ptr() for f, _ in LSM_SCAN_COLUMNS], cap_e,
+                          res["summary"].data_ptr())
+    return out
+
+
+def _lsm_scan_call(tree, ranges, max_seq):
+    """What lsm_scan_device and lsm_scan_merge_device marshal alike: the ranges and bounds as device tensors, the
+    sdb_scan_ranges over them and the result dict with the per-range arrays and the summary."""
     import torch
     dev = tree["device"]
     if isinstance(ranges, dict):
@@ -890,6 +904,22 @@ def lsm_scan_device(tree, ranges, max_seq=None, descending=False, stream=None, w
            "range_status": torch.zeros(max(n, 1), dtype=torch.int32, device=dev),
            "range_ssts": torch.zeros(max(n, 1), dtype=torch.int32, device=dev),
            "summary": torch.zeros(len(LSM_SCAN_SUMMARY), dtype=torch.int64, device=dev)}
+    return dev, rt, n, max_seq, rg, res
+
+
+def lsm_scan_device(tree, ranges, max_seq=None, descending=False, stream=None, workspace=None, cand=None, cap=None):
+    """sdb_lsm_scan: a batch of Db::scan over a device-resident tree.  tree: what lsm_tree_device built.
+    ranges: a list of (start, start_kind, end, end_kind), or a dict of device tensors named as
+    scan_ranges_columnar's arrays plus "n".  max_seq: None (no bound), a list / array of n bounds, or a device
+    int64 tensor.  cand: (cand_entries, cand_key_bytes), the staging capacity; cap: (cap_entries, key_arena_cap),
+    the column capacity.  With either None the call first runs without staging room, reads the candidate totals
+    (a host synchronisation), sizes both like the staging (num_entries <= num_candidates) and runs again; with
+    both given, device tensors for ranges and max_seq and a workspace it copies nothing from the host, so it can
+    be captured into a graph.  Returns a dict of device tensors: range_entry_start (n + 1), range_status,
+    range_ssts, key_arena, key_off, the LSM_SCAN_COLUMNS and summary (the sdb_lsm_scan_summary words in
+    LSM_SCAN_SUMMARY order); what the call allocated stays alive under "_" keys."""
+    import torch
+    dev, rt, n, max_seq, rg, res = _lsm_scan_call(tree, ranges, max_seq)
 
     def run(ce, ckb, cap_e, cap_k):
         wsb = lib().sdb_lsm_scan_workspace_bytes(tree["total_blocks"], tree["num_ssts"], tree["num_runs"], n, ce, ckb)
@@ -897,14 +927,7 @@ def lsm_scan_device(tree, ranges, max_seq=None, descending=False, stream=None, w
         if ws is None:
             assert workspace is None or cand is None, "workspace too small"
             ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        res["key_arena"] = torch.zeros(max(cap_k, 1), dtype=torch.uint8, device=dev)
-        res["key_off"] = torch.zeros(cap_e + 1, dtype=torch.int64, device=dev)
-        for f, dt in LSM_SCAN_COLUMNS:
-            res[f] = torch.zeros(max(cap_e, 1), dtype=getattr(torch, dt), device=dev)
-        out = _abi.LsmScanOut(res["range_entry_start"].data_ptr(), res["range_status"].data_ptr(),
-                              res["range_ssts"].data_ptr(), res["key_arena"].data_ptr(), cap_k,
-                              res["key_off"].data_ptr(), *[res[f].data_ptr() for f, _ in LSM_SCAN_COLUMNS], cap_e,
-                              res["summary"].data_ptr())
+        out = _lsm_scan_out(res, cap_e, cap_k, dev)
         st = lib().sdb_lsm_scan(C.byref(tree["lsm"]), C.byref(rg), max_seq.data_ptr() if max_seq is not None else None,
                                 int(bool(descending)), ce, ckb, C.byref(out), ws.data_ptr(), wsb, _sp(stream))
         if st:
@@ -921,6 +944,97 @@ def lsm_scan_device(tree, ranges, max_seq=None, descending=False, stream=None, w
             run(ce, ckb, *(cap if cap is not None else (ce, ckb)))
     else:
         run(cand[0], cand[1], cap[0], cap[1])
+    res.update(_tree=tree, _ranges=rt, _max_seq=max_seq)
+    return res
+
+
+CHAIN_COLUMNS = (("sst", "int32"), ("block", "int32"), ("val_off", "int64"), ("val_len", "int32"), ("seq", "int64"),
+                 ("flags", "uint8"), ("create_ts", "int64"), ("expire_ts", "int64"))
+CHAIN_SUMMARY = ("num_links", "max_chain_len", "status")
+
+
+def _chain_out(res, items, cap_links, dev, fill=0):
+    """The sdb_chain_out of a call over `items` queries or rows with room for cap_links links; its tensors go
+    into res as chain_start, chain_<column> and chain_summary."""
+    import torch
+    res["chain_start"] = torch.zeros(items + 1, dtype=torch.int64, device=dev)
+    for f, dt in CHAIN_COLUMNS:
+        dtype = getattr(torch, dt)  # every byte of the link columns starts as `fill`
+        res["chain_" + f] = torch.full((max(cap_links, 1) * dtype.itemsize,), fill, dtype=torch.uint8, device=dev).view(dtype)
+    res["chain_summary"] = torch.zeros(len(CHAIN_SUMMARY), dtype=torch.int64, device=dev)
+    return _abi.ChainOut(res["chain_start"].data_ptr(), *[res["chain_" + f].data_ptr() for f, _ in CHAIN_COLUMNS],
+                         cap_links, res["chain_summary"].data_ptr())
+
+
+def lsm_get_merge_device(views, runs, keys, max_seq=None, stream=None, workspace=None, cap_links=None, fill=0):
+    """sdb_lsm_get_merge: lsm_get_device for a store with a merge operator.  Besides the GET_FIELDS and the
+    summary the result holds the operand chains: chain_start (nkeys + 1), chain_<CHAIN_COLUMNS> per link and
+    chain_summary (CHAIN_SUMMARY order).  cap_links: room for the links; None sizes it from a first call (a host
+    synchronisation) and calls again when the links did not fit.  With cap_links given, device tensors and a
+    workspace the call copies nothing from the host, so it can be captured into a graph.  fill: what the link
+    columns hold before the call, byte by byte."""
+    import torch
+    tree, dev, kb, ko, n, max_seq, res, out = _get_call(views, runs, keys, max_seq)
+    wsb = lib().sdb_lsm_get_merge_workspace_bytes(tree["total_blocks"], tree["num_ssts"], tree["num_runs"], n)
+    ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=dev)
+    assert ws.numel() >= wsb, "workspace too small"
+
+    def run(cap):
+        chain = _chain_out(res, n, cap, dev, fill)
+        st = lib().sdb_lsm_get_merge(C.byref(tree["lsm"]), kb.data_ptr(), ko.data_ptr(), n,
+                                     max_seq.data_ptr() if max_seq is not None else None, C.byref(out),
+                                     C.byref(chain), ws.data_ptr(), wsb, _sp(stream))
+        if st:
+            raise SdbError(st, "sdb_lsm_get_merge")
+
+    if cap_links is None:
+        run(n)  # one link per query is the least a tree of values needs
+        _sync(stream, dev)
+        sm = res["chain_summary"].cpu().numpy()
+        if int(sm[2]) & 0xFFFFFFFF == _abi.SDB_LIMIT_EXCEEDED:
+            run(int(sm[0]))
+    else:
+        run(cap_links)
+    res.update(_ws=ws, _tree=tree, _keys=(kb, ko), _max_seq=max_seq)
+    return res
+
+
+def lsm_scan_merge_device(tree, ranges, max_seq=None, descending=False, stream=None, workspace=None, cand=None,
+                          cap=None, cap_links=None, fill=0):
+    """sdb_lsm_scan_merge: lsm_scan_device for a store with a merge operator; arguments as there.  Besides its
+    tensors the result holds the rows' operand chains: chain_start (cap_entries + 1, indexed by output row),
+    chain_<CHAIN_COLUMNS> per link and chain_summary (CHAIN_SUMMARY order).  cap_links: room for the links; None
+    sizes it like the staging (every link is a candidate).  With cand, cap or cap_links None the call retries
+    once on SDB_LIMIT_EXCEEDED, after a host synchronisation, as lsm_scan_device does."""
+    import torch
+    dev, rt, n, max_seq, rg, res = _lsm_scan_call(tree, ranges, max_seq)
+
+    def run(ce, ckb, cap_e, cap_k, cap_l):
+        wsb = lib().sdb_lsm_scan_merge_workspace_bytes(tree["total_blocks"], tree["num_ssts"], tree["num_runs"], n, ce,
+                                                       ckb)
+        ws = workspace if workspace is not None and workspace.numel() >= wsb else None
+        if ws is None:
+            assert workspace is None or cand is None, "workspace too small"
+            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        out = _lsm_scan_out(res, cap_e, cap_k, dev)
+        chain = _chain_out(res, cap_e, cap_l, dev, fill)
+        st = lib().sdb_lsm_scan_merge(C.byref(tree["lsm"]), C.byref(rg),
+                                      max_seq.data_ptr() if max_seq is not None else None, int(bool(descending)), ce,
+                                      ckb, C.byref(out), C.byref(chain), ws.data_ptr(), wsb, _sp(stream))
+        if st:
+            raise SdbError(st, "sdb_lsm_scan_merge")
+        res["_ws"] = ws
+
+    if cand is None or cap is None or cap_links is None:
+        ce, ckb = cand if cand is not None else (0, 0)
+        run(ce, ckb, *(cap if cap is not None else (0, 0)), cap_links or 0)
+        _sync(stream, dev)
+        sm, cm = res["summary"].cpu().numpy(), res["chain_summary"].cpu().numpy()
+        if _abi.SDB_LIMIT_EXCEEDED in (int(sm[6]) & 0xFFFFFFFF, int(cm[2]) & 0xFFFFFFFF):
+            ce, ckb = max(ce, int(sm[2])), max(ckb, int(sm[3]))
+            run(ce, ckb, *(cap if cap is not None else (ce, ckb)), cap_links if cap_links is not None else ce)
+    else:
+        run(cand[0], cand[1], cap[0], cap[1], cap_links)
     res.update(_tree=tree, _ranges=rt, _max_seq=max_seq)
     return res
 
