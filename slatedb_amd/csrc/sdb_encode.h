@@ -118,6 +118,12 @@ struct EncodeArgs {
     uint32_t *gtab_exit;    // per group of kGroup chunks, seg_look candidates: composed transfer table
     uint32_t *gtab_cnt;
     uint64_t *gtab_bytes;
+    // per chunk, per candidate entry offset into the chunk's group: the chain's state before the chunk (offset
+    // into it, blocks and bytes since the group's entry), written with the group table by k_anchor
+    uint32_t *pre_exit;
+    uint32_t *pre_cnt;
+    uint64_t *pre_bytes;
+    uint32_t *anchor_arrived;  // k_anchor's group workgroups that have finished (the last one walks the chain)
     uint32_t *mode;         // chain head: 1 = k_seg's tables describe the chain, 0 = anchors by the serial walk
     uint32_t group;         // chunks per group (host: ~sqrt(nchunks))
     // bloom fused into the encode: k_facts hashes and bins each chunk (tile = chunk), k_seg fills
@@ -143,9 +149,9 @@ struct EncodeArgs {
 
 // The workspace arrays of one SST's encode: X(EncodeArgs member, element type, elements).  n entries, nc
 // chunks (k_seg / k_blocks), nf k_facts workgroups, nt = nc * kSegLook + 1 table rows (seg_look candidate entry
-// points per chunk; one composed table per group, <= one per chunk).  This list is the only one: the field
-// indices, the slot's offsets (SstSlot::wso), the size and make_args' bindings all come from it.  The bloom
-// slots or the prefix filter's scratch (host-sized) follow the arrays, at wso[kWsTail].
+// points per chunk; one composed table per group, <= one per chunk; one prefix table per chunk).  This list is
+// the only one: the field indices, the slot's offsets (SstSlot::wso), the size and make_args' bindings all come
+// from it.  The bloom slots or the prefix filter's scratch (host-sized) follow the arrays, at wso[kWsTail].
 #define SDB_ENCODE_WS(X)                                                                                      \
     X(lcp, uint32_t, n + 1)                                                                                   \
     X(szr, uint32_t, n + 1)                                                                                   \
@@ -174,6 +180,10 @@ struct EncodeArgs {
     X(gtab_exit, uint32_t, nt)                                                                                \
     X(gtab_cnt, uint32_t, nt)                                                                                 \
     X(gtab_bytes, uint64_t, nt)                                                                               \
+    X(pre_exit, uint32_t, nt)                                                                                 \
+    X(pre_cnt, uint32_t, nt)                                                                                  \
+    X(pre_bytes, uint64_t, nt)                                                                                \
+    X(anchor_arrived, uint32_t, 1)                                                                            \
     X(mode, uint32_t, 1)                                                                                      \
     X(bloom_len_dev, const uint64_t, 1)
 enum WsField {

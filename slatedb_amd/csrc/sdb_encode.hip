@@ -178,6 +178,17 @@ SDB_DEV EntryFacts entry_facts(const EncodeArgs &a, uint64_t i) {
 // first probe and step.  Lanes hold consecutive entries: the next entry's offsets and the previous
 // key's first 16 bytes come from the neighbour lane by DPP (lane 63 / lane 0 load their own).
 // ------------------------------------------------------------------------------------------------
+// Lane l gets lane l + 1's (kDppWaveShl1) or lane l - 1's (kDppWaveShr1) v; the lane at the wave's end, which
+// has no such neighbour, keeps `own` (a DPP move leaves its destination alone there): one move per 32 bits,
+// no zeroed destination and no select for the end lane afterwards.
+template <int CTRL>
+SDB_DEV uint64_t dpp_or_own(uint64_t own, uint64_t v) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)own, (int)(uint32_t)v, CTRL, 0xF, 0xF, false);
+    const uint32_t hi =
+        (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)(own >> 32), (int)(uint32_t)(v >> 32), CTRL, 0xF, 0xF, false);
+    return (uint64_t)hi << 32 | lo;
+}
+
 __global__ __launch_bounds__(kFactsThreads, 8) void k_facts(SstSet P) {
     const EncodeArgs a = make_args(P, blockIdx.y);
     if (blockIdx.x >= a.nfacts) return;
@@ -186,6 +197,7 @@ __global__ __launch_bounds__(kFactsThreads, 8) void k_facts(SstSet P) {
     __shared__ unsigned long long s_err[kFactsThreads / 64];
     __shared__ uint32_t s_huge[kFactsThreads / 64];
     const uint32_t tid = threadIdx.x, lane = (uint32_t)lane_id();
+    if (blockIdx.x == 0 && tid == 0) *a.anchor_arrived = 0;  // k_anchor's arrival counter, zeroed on every call
     const uint64_t e0 = (uint64_t)blockIdx.x * kFactsEntries + tid;  // entries e0 + r * kFactsThreads
     const uint64_t n = a.n;
     // all loads of both rounds first (offsets, then the first 16 key bytes), so they overlap
@@ -218,11 +230,8 @@ __global__ __launch_bounds__(kFactsThreads, 8) void k_facts(SstSet P) {
 #pragma unroll
     for (uint32_t r = 0; r < kFactsPerT; r++) {
         FactsIn &f = in[r];
-        const uint64_t nk = wave_next_lane(f.ko0), nv = wave_next_lane(f.vo0);
-        if (lane != 63) {
-            f.ko1 = nk;
-            f.vo1 = nv;
-        }
+        f.ko1 = dpp_or_own<kDppWaveShl1>(f.ko1, f.ko0);  // (lane 63 loaded its own)
+        f.vo1 = dpp_or_own<kDppWaveShl1>(f.vo1, f.vo0);
         const uint64_t e = e0 + r * kFactsThreads;
         const bool live = e < n;
         const uint8_t *safe = (const uint8_t *)a.key_off;  // >= 16 bytes (n + 1 >= 2 offsets)
@@ -264,7 +273,8 @@ __global__ __launch_bounds__(kFactsThreads, 8) void k_facts(SstSet P) {
             if (pn > 8) f.pk1 = load8(a.key_bytes + f.pko + 8, pn - 8);
         }
     }
-    uint64_t rk = 0, rv = 0, c = 0;
+    uint64_t rk = 0, rv = 0;
+    uint32_t cv = 0, ct = 0, cm = 0;  // entries of each kind in the wave (wave-uniform: ballots)
     uint64_t err = ~0ull;
     bool huge = false;  // a row k_emit's piece path cannot stage (the block goes to the workgroup path)
     // a tombstone whose val_off range is not empty: those bytes are ignored (slatedb_amd.h), but a block's
@@ -276,17 +286,12 @@ __global__ __launch_bounds__(kFactsThreads, 8) void k_facts(SstSet P) {
     for (uint32_t r = 0; r < kFactsPerT; r++) {
         FactsIn &f = in[r];
         const uint64_t e = e0 + r * kFactsThreads;
-        {
-            const uint64_t pko = wave_prev_lane(f.ko0), pk0 = wave_prev_lane(f.ck0), pk1 = wave_prev_lane(f.ck1);
-            if (lane != 0) {
-                f.pko = pko;
-                f.pk0 = pk0;
-                f.pk1 = pk1;
-            } else if (e == 0) {
-                f.pko = f.ko0;
-            }
-        }
+        if (e == 0) f.pko = f.ko0;
+        f.pko = dpp_or_own<kDppWaveShr1>(f.pko, f.ko0);  // (lane 0 loaded its own)
+        f.pk0 = dpp_or_own<kDppWaveShr1>(f.pk0, f.ck0);
+        f.pk1 = dpp_or_own<kDppWaveShr1>(f.pk1, f.ck1);
         hh[r] = dd[r] = 0;
+        uint32_t kq = SDB_KIND_TOMBSTONE + 1;  // this entry's kind (none past the batch's end)
         if (e < n) {
             const EntryFacts x = facts_finish(a, e, f);
             a.lcp[e] = x.lcp;
@@ -310,25 +315,36 @@ __global__ __launch_bounds__(kFactsThreads, 8) void k_facts(SstSet P) {
             carry |= x.kind == SDB_KIND_TOMBSTONE && f.vo1 != f.vo0;
             rk += x.klen;
             rv += x.vlen;
-            c += (uint64_t)(x.kind == SDB_KIND_VALUE) | ((uint64_t)(x.kind == SDB_KIND_TOMBSTONE) << 20) |
-                 ((uint64_t)(x.kind == SDB_KIND_MERGE) << 40);
+            kq = x.kind;
         }
+        cv += (uint32_t)__popcll(__ballot(kq == SDB_KIND_VALUE));
+        ct += (uint32_t)__popcll(__ballot(kq == SDB_KIND_TOMBSTONE));
+        cm += (uint32_t)__popcll(__ballot(kq == SDB_KIND_MERGE));
     }
-    // SstStats (sst_builder.rs:225-226, 315-317) and the first error: per-workgroup partials
-    rk = wave_sum(rk);
-    rv = wave_sum(rv);
-    c = wave_sum(c);
-    err = wave_readlane(wave_incl_scan_op(err, [](uint64_t x, uint64_t y) { return x < y ? x : y; }), 63);
+    // SstStats (sst_builder.rs:225-226, 315-317) and the first error: per-workgroup partials.  A wave without
+    // a huge row (keys <= kPieceKeyMax, values <= kPieceValMax: its sums stay below 2^20) adds in 32 bits,
+    // and only a wave that saw an error looks for the first one.
+    static_assert(64ull * kFactsPerT * (kPieceKeyMax > kPieceValMax ? kPieceKeyMax : kPieceValMax) < (1ull << 32),
+                  "a wave's 32-bit sums");
+    const bool wh = __ballot(huge) != 0, wc = __ballot(carry) != 0;
+    if (wh) {
+        rk = wave_sum(rk);
+        rv = wave_sum(rv);
+    } else {
+        rk = wave_sum((uint32_t)rk);
+        rv = wave_sum((uint32_t)rv);
+    }
+    if (__ballot(err != ~0ull) != 0)
+        err = wave_readlane(wave_incl_scan_op(err, [](uint64_t x, uint64_t y) { return x < y ? x : y; }), 63);
     const uint32_t w = tid >> 6;
     if (lane == 0) {
         s_part[w][0] = rk;
         s_part[w][1] = rv;
-        s_part[w][2] = c & 0xFFFFF;
-        s_part[w][3] = (c >> 20) & 0xFFFFF;
-        s_part[w][4] = (c >> 40) & 0xFFFFF;
+        s_part[w][2] = cv;
+        s_part[w][3] = ct;
+        s_part[w][4] = cm;
         s_err[w] = err;
     }
-    const bool wh = __ballot(huge) != 0, wc = __ballot(carry) != 0;
     if (lane == 0) s_huge[w] = (wh ? kChunkHuge : 0u) | (wc ? kChunkCarry : 0u);
     __syncthreads();
     if (tid < 5) {
@@ -947,83 +963,133 @@ SDB_DEV uint32_t block_route(const EncodeArgs &a, const BlockDesc &d) {
 SDB_DEV bool emit_fast(const BlockDesc &d) { return d.route == kRouteImage; }
 
 // ------------------------------------------------------------------------------------------------
-// K2' anchor (the encode's chain; k_group composes the same tables for the compactor's cuts): one
-// workgroup per SST.
-//   1. the chain head: the SstStats / error partials, the longest candidate block (W) and the device
-//      state of the later kernels;
-//   2. every chunk's anchor (entry point, first block, first byte) from k_seg's chunk transfer tables,
-//      staged in LDS (u16 exit, u16 blocks, u64 bytes): composed per group of a.group chunks (a lane per
-//      (group, candidate)), the groups walked from entry 0 (one lane), then each group's chunks from its
-//      entry (a lane per group) -- about 3 sqrt(nchunks) dependent LDS steps for the SST.  Tables over the
-//      LDS are streamed through per-wave buffers, or walked the same way straight from HBM.
-//   Mode 0 (blocks longer than the lookahead): the serial walk of next(), as k_group.
+// K2' anchor (the encode's chain; k_group composes the same group tables for the compactor's cuts): one
+// workgroup per group of a.group chunks of each SST.
+//   a. every workgroup composes its group: the group's chunk transfer tables (k_seg) staged in LDS (u16
+//      exit, u16 blocks, u64 bytes), a lane per candidate entry offset walks them and leaves the state
+//      before each chunk (prefix tables) and after the last one (the group's table) in HBM; then the group
+//      arrives at the SST's counter.  No workgroup waits: all but the last one to arrive are done.
+//   b. the last workgroup to arrive takes the chain head (the SstStats / error partials, the longest
+//      candidate block W and the device state of the later kernels), stages the group tables in LDS (one
+//      load round), walks the groups from entry 0 (one lane, sqrt(nchunks) dependent LDS steps) and a lane
+//      per chunk adds the chunk's prefix row at its group's entry to the group's state (one gather): every
+//      chunk's anchor (entry point, first block, first byte).
+//   Chunk tables that would not fit one workgroup's LDS as a whole (long SSTs with long blocks) are not
+//   composed per group: the last workgroup streams them through per-wave buffers in groups of its own size,
+//   or walks them straight from HBM on one lane, as before.
+//   Mode 0 (blocks longer than the lookahead): the serial walk of next() by the last workgroup, as k_group.
 // ------------------------------------------------------------------------------------------------
 constexpr uint32_t kAnchorThreads = 1024;
 constexpr uint32_t kAnchorLds = 148 * 1024;  // (restated with the table layouts in tests/encode_cases.py, anchor_path)
 static_assert(kAnchorThreads == kChainThreads, "chain_head's per-wave partials");
 
+// A table word between workgroups of one kernel (k_anchor's group workgroups and the last of them): written
+// through and read at device scope, so neither side flushes or invalidates a cache (a __threadfence() does
+// both to the whole L2).
+template <typename T>
+SDB_DEV void tab_store(T *p, T v) {
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+template <typename T>
+SDB_DEV T tab_fetch(const T *p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 __global__ __launch_bounds__(kAnchorThreads) void k_anchor(SstSet P) {
     const EncodeArgs a = make_args(P, blockIdx.y);
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const uint32_t K = a.nchunks, G = a.group, ngroups = (K + G - 1) / G;
+    const uint32_t K = a.nchunks, G = a.group, ngroups = (K + G - 1) / G, L = a.seg_look;
     const uint32_t tid = threadIdx.x, nt = blockDim.x;
+    const uint32_t g = blockIdx.x;
+    if (g >= ngroups) return;
+    // 2a. the group's own bound on its candidates, so that no group needs the SST-wide head first: an entry
+    //     offset into chunk k lies below the longest candidate block of chunk k - 1 (into the group's first
+    //     chunk: of the chunk before the group; the exit of its last chunk: of that chunk)
+    const uint32_t k0 = g * G, nk = (k0 + G < K ? k0 + G : K) - k0;
+    __shared__ uint32_t s_wl;
+    if (tid == 0) s_wl = 0;
+    __syncthreads();
+    {
+        uint32_t m = 0;
+        for (uint32_t q = tid + (k0 == 0); q <= nk; q += nt) {
+            const uint32_t w = a.wmax_part[k0 + q - 1];
+            m = w > m ? w : m;
+        }
+        m = wave_max(m);
+        if (lane_id() == 0 && m) atomicMax(&s_wl, m);
+    }
+    __syncthreads();
+    {
+        // the group's chunk tables -> LDS (every load in flight at once), then a lane per candidate entry offset
+        // o walks them: before chunk k, the chain's state there (offset into the chunk, blocks and bytes since
+        // the group's entry) goes to row k of the prefix tables, the state after the last chunk to the group's
+        // table.  A group whose tables do not fit leaves them: the last workgroup then takes an older path.
+        const uint32_t W = s_wl;
+        const uint64_t ne = (uint64_t)nk * W, o_cn = (2 * ne + 15) & ~15ull, o_by = 2 * o_cn;
+        uint16_t *t_ex = (uint16_t *)smem, *t_cn = (uint16_t *)(smem + o_cn);
+        uint64_t *t_by = (uint64_t *)(smem + o_by);
+        const bool fits = W >= 1 && W <= L && o_by + 8 * ne <= kAnchorLds;
+        for (uint32_t i = tid; i < nk * W && fits; i += nt) {
+            const uint32_t j = i / W, o = i - j * W;
+            const TabEntry t = tab_load(a, k0 + j, o, W);
+            t_ex[i] = (uint16_t)t.x;
+            t_cn[i] = (uint16_t)t.c;  // a block count inside one chunk: <= kChunk
+            t_by[i] = t.b;
+        }
+        __syncthreads();
+        for (uint32_t o = tid; o < W && fits; o += nt) {
+            uint32_t e = o, c = 0;
+            uint64_t b = 0;
+            for (uint32_t j = 0; j < nk; j++) {
+                const uint64_t p = (uint64_t)(k0 + j) * L + o;
+                tab_store(&a.pre_exit[p], e);
+                tab_store(&a.pre_cnt[p], c);
+                tab_store(&a.pre_bytes[p], b);
+                const uint32_t i = j * W + e;
+                c += t_cn[i];
+                b += t_by[i];
+                e = t_ex[i];
+            }
+            const uint64_t t = (uint64_t)g * L + o;
+            tab_store(&a.gtab_exit[t], e);
+            tab_store(&a.gtab_cnt[t], c);
+            tab_store(&a.gtab_bytes[t], b);
+        }
+    }
+    // the group arrives (k_facts zeroed the counter); the last group to arrive goes on: no workgroup waits
+    __shared__ uint32_t s_last;
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this group's tables are written through, before its arrival
+    __syncthreads();
+    if (tid == 0) s_last = atomicAdd(a.anchor_arrived, 1u) == ngroups - 1;
+    __syncthreads();
+    if (!s_last) return;
     if (blockIdx.y == 0) PHASE_MARK_AT(1023, 5);
     const uint32_t W = chain_head(a, true);
     if (blockIdx.y == 0) PHASE_MARK_AT(1023, 0);
-    const bool fast = W >= 1 && W <= a.seg_look;
+    const bool fast = W >= 1 && W <= L;
+    const uint64_t ntab = (uint64_t)K * W, ng = (uint64_t)ngroups * W;
+    const uint64_t o_cn = (2 * ntab + 15) & ~15ull, o_by = o_cn + ((2 * ntab + 15) & ~15ull);
+    const uint64_t o_gex = o_by + 8 * ntab, o_gcn = o_gex + 4 * ng, o_gby = o_gcn + 4 * ng, o_ent = o_gby + 8 * ng;
+    // the chunk tables would fit the LDS as a whole, so each group's did and every group is composed
+    // (its bound is at most W); the group tables then take a part of it
+    const bool in_lds = fast && o_ent + 16ull * ngroups <= kAnchorLds;
     uint64_t tb = 0, ty = 0;  // the chain's blocks and bytes (thread 0)
     if (!fast) {
         if (tid == 0) chain_walk_serial(a, tb, ty);
     } else {
-        const uint64_t ntab = (uint64_t)K * W, ng = (uint64_t)ngroups * W;
-        const uint64_t o_cn = (2 * ntab + 15) & ~15ull, o_by = o_cn + ((2 * ntab + 15) & ~15ull);
-        const uint64_t o_gex = o_by + 8 * ntab, o_gcn = o_gex + 4 * ng, o_gby = o_gcn + 4 * ng, o_ent = o_gby + 8 * ng;
-        const bool in_lds = o_ent + 16ull * ngroups <= kAnchorLds;
-        uint16_t *t_ex = (uint16_t *)smem, *t_cn = (uint16_t *)(smem + o_cn);
-        uint64_t *t_by = (uint64_t *)(smem + o_by);
         uint32_t *g_ex = (uint32_t *)(smem + o_gex), *g_cn = (uint32_t *)(smem + o_gcn);
         uint64_t *g_by = (uint64_t *)(smem + o_gby);
         uint32_t *g_ent = (uint32_t *)(smem + o_ent);  // per group: entry offset, blocks before (bytes: g_ent64)
         uint64_t *g_b64 = (uint64_t *)(smem + o_ent + 8ull * ngroups);
-        // chunk k's table at candidate o, from the staged copy (in_lds)
-        auto tab = [&](uint32_t k, uint32_t o) -> TabEntry {
-            const uint64_t i = (uint64_t)k * W + o;
-            return {t_ex[i], t_cn[i], t_by[i]};
-        };
         if (in_lds) {
-            // stage the tables: eight entries per thread in flight, every load unconditional (chunk clamped);
-            // entry i's (chunk, candidate) advanced by nt incrementally -- a 64-bit i / W and i % W per entry
-            // was half of this kernel's time on one SST
-            constexpr uint32_t kU = 8;
-            const uint32_t ntab32 = (uint32_t)ntab, qn = nt / W, rn = nt % W;
-            uint32_t kk = tid / W, oo = tid % W;
-            for (uint32_t base = 0; base < ntab32; base += kU * nt) {
-                uint32_t te[kU], tc[kU], ku[kU], ou[kU];
-                uint64_t tb[kU];
-#pragma unroll
-                for (uint32_t u = 0; u < kU; u++) {
-                    ku[u] = kk;
-                    ou[u] = oo;
-                    oo += rn;
-                    kk += qn;
-                    if (oo >= W) {
-                        oo -= W;
-                        kk++;
-                    }
-                    const uint64_t t = (uint64_t)(ku[u] < K ? ku[u] : K - 1) * a.seg_look + ou[u];
-                    te[u] = a.tab_exit[t];
-                    tc[u] = a.tab_cnt[t];
-                    tb[u] = a.tab_bytes[t];
-                }
-#pragma unroll
-                for (uint32_t u = 0; u < kU; u++) {
-                    const uint32_t i = base + u * nt + tid;
-                    if (i >= ntab32) continue;
-                    const TabEntry t = tab_clamp(a, ku[u], ou[u], W, te[u], tc[u], tb[u]);
-                    t_ex[i] = (uint16_t)t.x;
-                    t_cn[i] = (uint16_t)t.c;  // a block count inside one chunk: <= kChunk
-                    t_by[i] = t.b;
-                }
+            // 2b. the group tables -> LDS (one load round)
+            for (uint32_t i = tid; i < (uint32_t)ng; i += nt) {
+                const uint32_t q = i / W, o = i - q * W;
+                const uint64_t t = (uint64_t)q * L + o;
+                const uint32_t x = tab_fetch(&a.gtab_exit[t]);
+                g_ex[i] = x < W ? x : W - 1;  // (a candidate past its group's bound: a stale slot no chain reaches)
+                g_cn[i] = tab_fetch(&a.gtab_cnt[t]);
+                g_by[i] = tab_fetch(&a.gtab_bytes[t]);
             }
             __syncthreads();
             if (blockIdx.y == 0) PHASE_MARK_AT(1023, 1);
@@ -1155,23 +1221,6 @@ __global__ __launch_bounds__(kAnchorThreads) void k_anchor(SstSet P) {
                 __builtin_amdgcn_wave_barrier();
             }
         }
-        // group tables: lane per (group, candidate)
-        for (uint64_t i = tid; i < ng && in_lds; i += nt) {
-            const uint32_t q = (uint32_t)i / W, k1 = (q + 1) * G < K ? (q + 1) * G : K;  // (ng < 2^32 in LDS)
-            uint32_t e = (uint32_t)i - q * W, c = 0;
-            uint64_t b = 0;
-            for (uint32_t k = q * G; k < k1; k++) {
-                const TabEntry t = tab(k, e);
-                c += t.c;
-                b += t.b;
-                e = t.x;
-            }
-            g_ex[i] = e;
-            g_cn[i] = c;
-            g_by[i] = b;
-        }
-        __syncthreads();
-        if (blockIdx.y == 0 && in_lds) PHASE_MARK_AT(1023, 2);
         if (tid == 0 && !streamed) {  // the groups from entry 0
             uint32_t e = 0;
             for (uint32_t q = 0; q < ngroups; q++) {
@@ -1199,19 +1248,14 @@ __global__ __launch_bounds__(kAnchorThreads) void k_anchor(SstSet P) {
         }
         __syncthreads();
         if (blockIdx.y == 0 && in_lds) PHASE_MARK_AT(1023, 4);
-        for (uint32_t q = tid; q < ngroups && in_lds; q += nt) {  // each group's chunks from its entry
-            uint32_t e = g_ent[2 * q];
-            uint64_t blk = g_ent[2 * q + 1], by = g_b64[q];
-            const uint32_t k1 = (q + 1) * G < K ? (q + 1) * G : K;
-            for (uint32_t k = q * G; k < k1; k++) {
-                a.anchor_e[k] = (uint32_t)((uint64_t)k * kChunk + e);
-                a.anchor_blk[k] = (uint32_t)blk;
-                a.anchor_byte[k] = by;
-                const TabEntry t = tab(k, e);
-                blk += t.c;
-                by += t.b;
-                e = t.x;
-            }
+        // 2c. every chunk's anchor: its group's entry state plus the chunk's prefix row at that entry (one gather)
+        for (uint32_t k = tid; k < K && in_lds; k += nt) {
+            const uint32_t q = k / G;
+            const uint64_t p = (uint64_t)k * L + g_ent[2 * q];
+            const uint32_t x = tab_fetch(&a.pre_exit[p]);
+            a.anchor_e[k] = (uint32_t)((uint64_t)k * kChunk + (x < W ? x : W - 1));
+            a.anchor_blk[k] = g_ent[2 * q + 1] + tab_fetch(&a.pre_cnt[p]);
+            a.anchor_byte[k] = g_b64[q] + tab_fetch(&a.pre_bytes[p]);
         }
     }
     if (blockIdx.y == 0) PHASE_MARK_AT(1023, 3);
@@ -2546,9 +2590,9 @@ hipError_t launch_encode_set(const SstSet &P, size_t bin_lds, size_t fill_lds, h
     const size_t seg_lds = kSegLds > fill_lds ? kSegLds : fill_lds;
     hipLaunchKernelGGL(k_seg, dim3(P.max_chunks + P.max_slices, P.count), dim3(kSegThreads), seg_lds, st, P);
     stage_mark(st, kStSeg, false);
-    // the chain: every chunk's anchor (one workgroup per SST), then each chunk's blocks
+    // the chain: every chunk's anchor (one workgroup per group of chunks), then each chunk's blocks
     stage_mark(st, kStAnchor, true);
-    hipLaunchKernelGGL(k_anchor, dim3(1, P.count), dim3(kAnchorThreads), kAnchorLds, st, P);
+    hipLaunchKernelGGL(k_anchor, dim3(P.max_groups, P.count), dim3(kAnchorThreads), kAnchorLds, st, P);
     stage_mark(st, kStAnchor, false);
     stage_mark(st, kStBlocks, true);
     hipLaunchKernelGGL(k_blocks, dim3(P.max_chunks, P.count), dim3(kBlkThreads), 0, st, P);
