@@ -626,7 +626,8 @@ sdb_status sdb_lsm_get(const sdb_lsm_view *lsm, const uint8_t *key_bytes, const 
  *      search order, which is the order of `ssts`, newest first.  The reference opens every L0 SST and, per
  *      sorted run, tables_covering_range (segment_iterator.rs:355-414, db_state.rs:600-660); any SST it opens
  *      beyond this rule holds no key of the range, so the entries agree.  No bloom filter is consulted: a
- *      range has none without a prefix extractor.  A range that is empty as a set reads nothing.
+ *      range has none without a prefix extractor (sdb_lsm_scan_filtered is the call that consults them).  A range
+ *      that is empty as a set reads nothing.
  *      range_ssts[r] is the number of SSTs that take part;
  *   2. blocks: per participating SST, partitions_covering_range(index keys, start, end) exactly as
  *      sdb_sst_scan rule 1 (partitioned_keyspace.rs:87-110).  EVERY such block is bounds- and CRC-checked
@@ -793,6 +794,92 @@ sdb_status sdb_lsm_scan_merge(const sdb_lsm_view *lsm, const sdb_scan_ranges *ra
                               const uint64_t *max_seq /* device, n; NULL = no bound */, int32_t descending,
                               uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out *out,
                               const sdb_chain_out *chain, void *workspace, uint64_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Filter policies in tree reads (device): Db::scan_prefix and gets over SSTs whose "_bf" filter was built with a
+ * prefix extractor.  The reference's public Db::scan_prefix (db.rs:1071-1143) puts the prefix into
+ * SstIteratorOptions.prefix (scan_with_options, reader.rs:284-293), and every per-SST iterator evaluates its
+ * FilterQuery before it opens the SST (sst_iter.rs:848-862, 785-810, 201-227): a ruled-out SST is never opened,
+ * its blocks are never fetched and its errors never surface.  sdb_lsm_scan_filtered is sdb_lsm_scan (chain ==
+ * NULL: a winning operand fails its range) or sdb_lsm_scan_merge (chain != NULL) with that step;
+ * sdb_lsm_get_filtered is sdb_lsm_get (chain == NULL) or sdb_lsm_get_merge with the filter step of rule 2 made
+ * aware of the SST's policy: a tree written with no_whole_key = 1 stores no full-key hashes, so probing
+ * might_contain(filter_hash(key)) there answers false for present keys.
+ *   F1. the query of a pair (range r, SST i): a point range (start and end both SDB_BOUND_INCLUDED with equal
+ *       keys: SstView::point_key, sst_iter.rs:82-87) asks Point(key), also when has_prefix[r] is set
+ *       (sst_iter.rs:852-856); otherwise, if has_prefix[r], Prefix(p); otherwise there is no query and no filter
+ *       is consulted.  prefixes == NULL: no range has a prefix.  In a get the query is always Point(key);
+ *   F2. the answer is Filter::might_match exactly as sdb_bloom_might_match defines it (filter.rs:150-175): a
+ *       Point under whole-key filtering (no_whole_key == 0) probes the full key; anything else probes
+ *       target[..n], n from the SST's extractor: SDB_PREFIX_FIXED: len >= prefix_arg ? prefix_arg : None;
+ *       SDB_PREFIX_DELIM: through the first delimiter byte, else None; SDB_PREFIX_LENGTHS: probe_len of the
+ *       range / key (a NULL array or -1: None); SDB_PREFIX_NONE: None.  None answers "might match".  An empty
+ *       bitmap (bloom != NULL, bloom_len == 0) answers "no" to every query that has something to probe and
+ *       "might match" to a None.  bloom == NULL: the SST has no filter and takes part.  policies == NULL: every
+ *       SST has {SDB_PREFIX_NONE, 0, 0}, the plain whole-key policy;
+ *   F3. in the scan a ruled-out SST takes no part in that range: no block of it is marked, checked or staged
+ *       for the range; it is not counted in range_ssts or num_candidates but in range_filtered[r]; its block
+ *       errors, an invalid sst_version and NULL arrays do not surface for that range (the filter is evaluated
+ *       first, as FilterIterator::init does and as the gets do).  blocks_checked stays the exact size of the
+ *       union of the covering blocks of the pairs that take part.  Everything else of sdb_lsm_scan rules 1-7
+ *       and of sdb_lsm_scan_merge's rule 4 holds unchanged: errors, the capacity protocol (range_filtered and
+ *       num_filtered are valid whenever range_ssts is), ordering;
+ *   F4. the caller's obligation, as in the reference (db.rs:233-236): when has_prefix[r] is set every key of
+ *       range r starts with the prefix.  The device does not verify this; a violation can only lose rows of
+ *       filtered SSTs and never reads out of bounds.  A probe_len above the length of the probed target counts
+ *       as None;
+ *   F5. in the get only rule 2's filter step changes, from might_contain(filter_hash(key)) to F2 with
+ *       Point(key); ssts_filtered, ssts_read and the laziness rules are unchanged.  policies == NULL and
+ *       probe_len == NULL give exactly sdb_lsm_get / sdb_lsm_get_merge;
+ *   F6. arguments and conventions as the tree reads above: no allocation, no synchronisation, one stream,
+ *       capturable into a HIP graph as a linear sequence, the workspace reusable without a host-side reset.  A
+ *       NULL fout, or a NULL array inside it (or inside a non-NULL prefixes, probe_len aside) for n > 0, is
+ *       SDB_INVALID_ARGUMENT from the call.  Prefix offsets that descend make the call malformed: every range
+ *       gets SDB_INVALID_ARGUMENT, like range offsets.  A prefix_kind above SDB_PREFIX_LENGTHS in policies fails
+ *       the queries and ranges that reach that SST with SDB_INVALID_ARGUMENT at that SST's place in the order;
+ *       it is checked before the filter, which then rules nothing out.  With no device: SDB_DEVICE_ERROR, after
+ *       the host checks.
+ * The probe bytes of a query, and so their SipHash, depend on (query, policy) and not on the SST: when all
+ * policies of the tree agree (the normal store) the hash is computed once per range or key, else per pair.
+ * ------------------------------------------------------------------------------------------- */
+/* What BloomFilter::decode is given for one SST's "_bf" filter (filter.rs:94-106), from the policy name in
+ * the SST's metadata ("_bf", "_bf:p=<extractor>[:wh=0]", filter_policy.rs:237-250). */
+typedef struct sdb_filter_policy {
+    uint32_t prefix_kind;    /* SDB_PREFIX_NONE | _FIXED | _DELIM | _LENGTHS */
+    uint32_t prefix_arg;
+    uint32_t no_whole_key;   /* as sdb_sst_params.no_whole_key */
+    uint32_t pad;
+} sdb_filter_policy;
+typedef struct sdb_scan_prefixes {      /* device pointers, one element per range */
+    const uint8_t *prefix_bytes;        /* the scan prefix of range r = */
+    const uint64_t *prefix_off;         /*   prefix_bytes[prefix_off[r] .. prefix_off[r + 1]); n + 1 */
+    const uint8_t *has_prefix;          /* n: 1 = Db::scan_prefix, 0 = plain Db::scan (no prefix query) */
+    const int32_t *probe_len;           /* n or NULL: prefix_len(Prefix(p)) of the caller's extractor (of Point(key)
+                                           for a point range), -1 = None; read only for SSTs whose prefix_kind is
+                                           SDB_PREFIX_LENGTHS */
+} sdb_scan_prefixes;
+typedef struct sdb_scan_filter_out {    /* device */
+    uint32_t *range_filtered;           /* n: SSTs of rule 1 that the filter ruled out for range r */
+    uint64_t *num_filtered;             /* one u64: their sum */
+} sdb_scan_filter_out;
+uint64_t sdb_lsm_scan_filtered_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs,
+                                               uint64_t nranges, uint64_t cand_entries, uint64_t cand_key_bytes,
+                                               int32_t merge /* 1: a chain is passed */);
+sdb_status sdb_lsm_scan_filtered(const sdb_lsm_view *lsm, const sdb_filter_policy *policies /* device, num_ssts; or NULL */,
+                                 const sdb_scan_ranges *ranges, const sdb_scan_prefixes *prefixes /* or NULL */,
+                                 const uint64_t *max_seq /* device, n; NULL = no bound */, int32_t descending,
+                                 uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out *out,
+                                 const sdb_chain_out *chain /* or NULL */, const sdb_scan_filter_out *fout,
+                                 void *workspace, uint64_t workspace_bytes, void *stream);
+uint64_t sdb_lsm_get_filtered_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs,
+                                              uint64_t nkeys, int32_t merge /* 1: a chain is passed */);
+sdb_status sdb_lsm_get_filtered(const sdb_lsm_view *lsm, const sdb_filter_policy *policies /* device, num_ssts; or NULL */,
+                                const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
+                                const int32_t *probe_len /* device, nkeys: prefix_len(Point(key)) for SDB_PREFIX_LENGTHS
+                                                            SSTs, -1 = None; or NULL */,
+                                const uint64_t *max_seq /* device, nkeys; NULL = no bound */, const sdb_get_out *out,
+                                const sdb_chain_out *chain /* or NULL */, void *workspace, uint64_t workspace_bytes,
+                                void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Compaction (device): the output side of CompactionExecutor::run_subcompaction_merge

@@ -231,6 +231,22 @@ class ChainOut(C.Structure):
     ]
 
 
+PREFIX_NONE, PREFIX_FIXED, PREFIX_DELIM, PREFIX_LENGTHS = 0, 1, 2, 3  # SDB_PREFIX_*
+
+
+class FilterPolicy(C.Structure):
+    _fields_ = [("prefix_kind", C.c_uint32), ("prefix_arg", C.c_uint32), ("no_whole_key", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class ScanPrefixes(C.Structure):
+    _fields_ = [("prefix_bytes", C.c_void_p), ("prefix_off", C.c_void_p), ("has_prefix", C.c_void_p),
+                ("probe_len", C.c_void_p)]
+
+
+class ScanFilterOut(C.Structure):
+    _fields_ = [("range_filtered", C.c_void_p), ("num_filtered", C.c_void_p)]
+
+
 class Run(C.Structure):
     _fields_ = [
         ("n", C.c_uint64), ("key_arena", C.c_void_p), ("key_off", C.c_void_p),
@@ -355,6 +371,15 @@ SIGNATURES = {
     "sdb_lsm_scan_merge": (C.c_int, [C.POINTER(LsmView), C.POINTER(ScanRanges), C.c_void_p, C.c_int32, C.c_uint64,
                                      C.c_uint64, C.POINTER(LsmScanOut), C.POINTER(ChainOut), C.c_void_p, C.c_uint64,
                                      C.c_void_p]),
+    "sdb_lsm_scan_filtered_workspace_bytes": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
+                                                           C.c_uint64, C.c_int32]),
+    "sdb_lsm_scan_filtered": (C.c_int, [C.POINTER(LsmView), C.c_void_p, C.POINTER(ScanRanges), C.POINTER(ScanPrefixes),
+                                        C.c_void_p, C.c_int32, C.c_uint64, C.c_uint64, C.POINTER(LsmScanOut),
+                                        C.POINTER(ChainOut), C.POINTER(ScanFilterOut), C.c_void_p, C.c_uint64, C.c_void_p]),
+    "sdb_lsm_get_filtered_workspace_bytes": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int32]),
+    "sdb_lsm_get_filtered": (C.c_int, [C.POINTER(LsmView), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                       C.c_void_p, C.POINTER(GetOut), C.POINTER(ChainOut), C.c_void_p, C.c_uint64,
+                                       C.c_void_p]),
     "sdb_merge_runs_workspace_bytes":(C.c_uint64, [C.POINTER(Run), C.c_uint32]),
     "sdb_merge_runs": (C.c_int, [C.POINTER(Run), C.c_uint32, C.POINTER(Retention), C.POINTER(MergedOut),
                                  C.c_void_p, C.c_uint64, C.c_void_p]),

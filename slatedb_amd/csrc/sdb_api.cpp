@@ -25,17 +25,19 @@ uint64_t scan_workspace_bytes(uint64_t num_blocks, uint64_t nranges);
 hipError_t launch_scan(const sdb_sst_view &v, const sdb_scan_ranges &r, uint32_t desc, const sdb_scan_out &out, uint8_t *w,
                        hipStream_t st);
 uint64_t lsm_scan_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint64_t nranges, uint64_t cand_entries,
-                                  uint64_t cand_key_bytes, bool merge);
+                                  uint64_t cand_key_bytes, bool merge, bool filter);
 hipError_t launch_lsm_scan(const sdb_lsm_view &t, const sdb_scan_ranges &r, const uint64_t *max_seq, uint32_t desc,
                            uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out &out,
-                           const sdb_chain_out *chain, uint8_t *w, hipStream_t st);
+                           const sdb_chain_out *chain, const sdb_filter_policy *pol, const sdb_scan_prefixes *px,
+                           const sdb_scan_filter_out *fout, uint8_t *w, hipStream_t st);
 uint64_t get_merge_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys);
-hipError_t launch_get_merge(const sdb_lsm_view &t, const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
-                            const uint64_t *max_seq, const sdb_get_out &out, const sdb_chain_out &chain, uint8_t *w,
-                            hipStream_t st);
+hipError_t launch_get_merge(const sdb_lsm_view &t, const sdb_filter_policy *pol, const uint8_t *key_bytes,
+                            const uint64_t *key_off, uint64_t nkeys, const int32_t *probe_len, const uint64_t *max_seq,
+                            const sdb_get_out &out, const sdb_chain_out &chain, uint8_t *w, hipStream_t st);
 uint64_t get_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys);
-hipError_t launch_get(const sdb_lsm_view &t, const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
-                      const uint64_t *max_seq, const sdb_get_out &out, uint8_t *w, hipStream_t st);
+hipError_t launch_get(const sdb_lsm_view &t, const sdb_filter_policy *pol, const uint8_t *key_bytes, const uint64_t *key_off,
+                      uint64_t nkeys, const int32_t *probe_len, const uint64_t *max_seq, const sdb_get_out &out, uint8_t *w,
+                      hipStream_t st);
 }  // namespace sdb
 
 using namespace sdb;
@@ -637,33 +639,44 @@ uint64_t sdb_lsm_get_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, u
     return get_workspace_bytes(total_blocks, num_ssts, num_runs, nkeys) + 256;
 }
 
-sdb_status sdb_lsm_get(const sdb_lsm_view *lsm, const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
-                       const uint64_t *max_seq, const sdb_get_out *out, void *workspace, uint64_t workspace_bytes,
-                       void *stream) {
-    if (!lsm || !out) return SDB_INVALID_ARGUMENT;
-    // (the limits all give one status, so this one may come before the tree's)
-    if (lsm->num_runs && nkeys > (1ull << 40) / lsm->num_runs) return SDB_LIMIT_EXCEEDED;  // a byte per (query, run)
-    sdb_status st = check_tree(lsm);
-    if (st) return st;
-    if (!out->summary) return SDB_INVALID_ARGUMENT;
-    if (nkeys && (!key_bytes || !key_off || !out->state || !out->status || !out->sst || !out->block || !out->val_off ||
-                  !out->val_len || !out->seq || !out->flags || !out->create_ts || !out->expire_ts || !out->ssts_read ||
-                  !out->ssts_filtered))
-        return SDB_INVALID_ARGUMENT;
-    if (!workspace ||
-        workspace_bytes < sdb_lsm_get_workspace_bytes(lsm->total_blocks, lsm->num_ssts, lsm->num_runs, nkeys))
-        return SDB_INVALID_ARGUMENT;
-    if (!device_ok()) return SDB_DEVICE_ERROR;
-    uint8_t *w = ws_align(workspace);
-    if (launch_get(*lsm, key_bytes, key_off, nkeys, max_seq, *out, w, S(stream)) != hipSuccess) return SDB_DEVICE_ERROR;
-    return SDB_OK;
-}
-
 // NULL: nothing missing.  The CSR offsets and the summary always, the link columns where there is room for a link.
 static bool chain_ok(const sdb_chain_out *c) {
     if (!c || !c->chain_start || !c->summary) return false;
     return !c->cap_links || (c->sst && c->block && c->val_off && c->val_len && c->seq && c->flags && c->create_ts &&
                              c->expire_ts);
+}
+
+// sdb_lsm_get (merge == false), sdb_lsm_get_merge and sdb_lsm_get_filtered (either, with policies and probe_len): one
+// set of argument checks, in one order.
+static sdb_status lsm_get_call(const sdb_lsm_view *lsm, const sdb_filter_policy *policies, const uint8_t *key_bytes,
+                               const uint64_t *key_off, uint64_t nkeys, const int32_t *probe_len, const uint64_t *max_seq,
+                               const sdb_get_out *out, bool merge, const sdb_chain_out *chain, void *workspace,
+                               uint64_t workspace_bytes, void *stream) {
+    if (!lsm || !out || (merge && !chain)) return SDB_INVALID_ARGUMENT;
+    // (the limits all give one status, so this one may come before the tree's)
+    if (lsm->num_runs && nkeys > (1ull << 40) / lsm->num_runs) return SDB_LIMIT_EXCEEDED;  // a byte per (query, run)
+    sdb_status st = check_tree(lsm);
+    if (st) return st;
+    if (!out->summary || (merge && !chain_ok(chain))) return SDB_INVALID_ARGUMENT;
+    if (nkeys && (!key_bytes || !key_off || !out->state || !out->status || !out->sst || !out->block || !out->val_off ||
+                  !out->val_len || !out->seq || !out->flags || !out->create_ts || !out->expire_ts || !out->ssts_read ||
+                  !out->ssts_filtered))
+        return SDB_INVALID_ARGUMENT;
+    const uint64_t need = merge ? sdb_lsm_get_merge_workspace_bytes(lsm->total_blocks, lsm->num_ssts, lsm->num_runs, nkeys)
+                                : sdb_lsm_get_workspace_bytes(lsm->total_blocks, lsm->num_ssts, lsm->num_runs, nkeys);
+    if (!workspace || workspace_bytes < need) return SDB_INVALID_ARGUMENT;
+    if (!device_ok()) return SDB_DEVICE_ERROR;
+    uint8_t *w = ws_align(workspace);
+    const hipError_t e = merge ? launch_get_merge(*lsm, policies, key_bytes, key_off, nkeys, probe_len, max_seq, *out, *chain, w, S(stream))
+                               : launch_get(*lsm, policies, key_bytes, key_off, nkeys, probe_len, max_seq, *out, w, S(stream));
+    return e != hipSuccess ? SDB_DEVICE_ERROR : SDB_OK;
+}
+
+sdb_status sdb_lsm_get(const sdb_lsm_view *lsm, const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
+                       const uint64_t *max_seq, const sdb_get_out *out, void *workspace, uint64_t workspace_bytes,
+                       void *stream) {
+    return lsm_get_call(lsm, nullptr, key_bytes, key_off, nkeys, nullptr, max_seq, out, false, nullptr, workspace,
+                        workspace_bytes, stream);
 }
 
 uint64_t sdb_lsm_get_merge_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys) {
@@ -673,43 +686,51 @@ uint64_t sdb_lsm_get_merge_workspace_bytes(uint64_t total_blocks, uint32_t num_s
 sdb_status sdb_lsm_get_merge(const sdb_lsm_view *lsm, const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
                              const uint64_t *max_seq, const sdb_get_out *out, const sdb_chain_out *chain, void *workspace,
                              uint64_t workspace_bytes, void *stream) {
-    if (!lsm || !out || !chain) return SDB_INVALID_ARGUMENT;
-    if (lsm->num_runs && nkeys > (1ull << 40) / lsm->num_runs) return SDB_LIMIT_EXCEEDED;  // as sdb_lsm_get
-    sdb_status st = check_tree(lsm);
-    if (st) return st;
-    if (!out->summary || !chain_ok(chain)) return SDB_INVALID_ARGUMENT;
-    if (nkeys && (!key_bytes || !key_off || !out->state || !out->status || !out->sst || !out->block || !out->val_off ||
-                  !out->val_len || !out->seq || !out->flags || !out->create_ts || !out->expire_ts || !out->ssts_read ||
-                  !out->ssts_filtered))
-        return SDB_INVALID_ARGUMENT;
-    if (!workspace ||
-        workspace_bytes < sdb_lsm_get_merge_workspace_bytes(lsm->total_blocks, lsm->num_ssts, lsm->num_runs, nkeys))
-        return SDB_INVALID_ARGUMENT;
-    if (!device_ok()) return SDB_DEVICE_ERROR;
-    uint8_t *w = ws_align(workspace);
-    if (launch_get_merge(*lsm, key_bytes, key_off, nkeys, max_seq, *out, *chain, w, S(stream)) != hipSuccess)
-        return SDB_DEVICE_ERROR;
-    return SDB_OK;
+    return lsm_get_call(lsm, nullptr, key_bytes, key_off, nkeys, nullptr, max_seq, out, true, chain, workspace,
+                        workspace_bytes, stream);
+}
+
+uint64_t sdb_lsm_get_filtered_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys,
+                                              int32_t merge) {
+    return merge ? sdb_lsm_get_merge_workspace_bytes(total_blocks, num_ssts, num_runs, nkeys)
+                 : sdb_lsm_get_workspace_bytes(total_blocks, num_ssts, num_runs, nkeys);
+}
+
+sdb_status sdb_lsm_get_filtered(const sdb_lsm_view *lsm, const sdb_filter_policy *policies, const uint8_t *key_bytes,
+                                const uint64_t *key_off, uint64_t nkeys, const int32_t *probe_len, const uint64_t *max_seq,
+                                const sdb_get_out *out, const sdb_chain_out *chain, void *workspace, uint64_t workspace_bytes,
+                                void *stream) {
+    return lsm_get_call(lsm, policies, key_bytes, key_off, nkeys, probe_len, max_seq, out, chain != nullptr, chain,
+                        workspace, workspace_bytes, stream);
 }
 
 uint64_t sdb_lsm_scan_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nranges,
                                       uint64_t cand_entries, uint64_t cand_key_bytes) {
     (void)num_runs;  // runs only fix the search order: the workspace is per (range, SST)
-    return lsm_scan_workspace_bytes(total_blocks, num_ssts, nranges, cand_entries, cand_key_bytes, false) + 256;
+    return lsm_scan_workspace_bytes(total_blocks, num_ssts, nranges, cand_entries, cand_key_bytes, false, false) + 256;
 }
 
 uint64_t sdb_lsm_scan_merge_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs,
                                             uint64_t nranges, uint64_t cand_entries, uint64_t cand_key_bytes) {
     (void)num_runs;
-    return lsm_scan_workspace_bytes(total_blocks, num_ssts, nranges, cand_entries, cand_key_bytes, true) + 256;
+    return lsm_scan_workspace_bytes(total_blocks, num_ssts, nranges, cand_entries, cand_key_bytes, true, false) + 256;
 }
 
-// sdb_lsm_scan (chain == NULL, merge == false) and sdb_lsm_scan_merge: one set of argument checks, in one order.
+uint64_t sdb_lsm_scan_filtered_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs,
+                                               uint64_t nranges, uint64_t cand_entries, uint64_t cand_key_bytes,
+                                               int32_t merge) {
+    (void)num_runs;
+    return lsm_scan_workspace_bytes(total_blocks, num_ssts, nranges, cand_entries, cand_key_bytes, merge != 0, true) + 256;
+}
+
+// sdb_lsm_scan (chain == NULL, merge == false), sdb_lsm_scan_merge and sdb_lsm_scan_filtered (filter: either, with
+// policies, prefixes and fout): one set of argument checks, in one order.
 static sdb_status lsm_scan_call(const sdb_lsm_view *lsm, const sdb_scan_ranges *ranges, const uint64_t *max_seq,
                                 int32_t descending, uint64_t cand_entries, uint64_t cand_key_bytes,
-                                const sdb_lsm_scan_out *out, bool merge, const sdb_chain_out *chain, void *workspace,
-                                uint64_t workspace_bytes, void *stream) {
-    if (!lsm || !ranges || !out || (merge && !chain)) return SDB_INVALID_ARGUMENT;
+                                const sdb_lsm_scan_out *out, bool merge, const sdb_chain_out *chain, bool filter,
+                                const sdb_filter_policy *policies, const sdb_scan_prefixes *prefixes,
+                                const sdb_scan_filter_out *fout, void *workspace, uint64_t workspace_bytes, void *stream) {
+    if (!lsm || !ranges || !out || (merge && !chain) || (filter && !fout)) return SDB_INVALID_ARGUMENT;
     const uint64_t n = ranges->n;
     // (the limits all give one status, so these may come before the tree's)
     if (lsm->num_ssts && n > (1ull << 40) / lsm->num_ssts) return SDB_LIMIT_EXCEEDED;  // per (range, SST) state
@@ -723,13 +744,16 @@ static sdb_status lsm_scan_call(const sdb_lsm_view *lsm, const sdb_scan_ranges *
                              !out->create_ts || !out->expire_ts))
         return SDB_INVALID_ARGUMENT;
     if (merge && !chain_ok(chain)) return SDB_INVALID_ARGUMENT;
-    if (!workspace ||
-        workspace_bytes < lsm_scan_workspace_bytes(lsm->total_blocks, lsm->num_ssts, n, cand_entries, cand_key_bytes, merge) + 256)
+    if (filter && n && (!fout->range_filtered || !fout->num_filtered)) return SDB_INVALID_ARGUMENT;
+    if (filter && n && prefixes && (!prefixes->prefix_bytes || !prefixes->prefix_off || !prefixes->has_prefix))
+        return SDB_INVALID_ARGUMENT;
+    if (!workspace || workspace_bytes < lsm_scan_workspace_bytes(lsm->total_blocks, lsm->num_ssts, n, cand_entries,
+                                                                 cand_key_bytes, merge, filter) + 256)
         return SDB_INVALID_ARGUMENT;
     if (!device_ok()) return SDB_DEVICE_ERROR;
     uint8_t *w = ws_align(workspace);
     if (launch_lsm_scan(*lsm, *ranges, max_seq, descending ? 1u : 0u, cand_entries, cand_key_bytes, *out,
-                        merge ? chain : nullptr, w, S(stream)) != hipSuccess)
+                        merge ? chain : nullptr, policies, prefixes, filter ? fout : nullptr, w, S(stream)) != hipSuccess)
         return SDB_DEVICE_ERROR;
     return SDB_OK;
 }
@@ -737,16 +761,25 @@ static sdb_status lsm_scan_call(const sdb_lsm_view *lsm, const sdb_scan_ranges *
 sdb_status sdb_lsm_scan(const sdb_lsm_view *lsm, const sdb_scan_ranges *ranges, const uint64_t *max_seq,
                         int32_t descending, uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out *out,
                         void *workspace, uint64_t workspace_bytes, void *stream) {
-    return lsm_scan_call(lsm, ranges, max_seq, descending, cand_entries, cand_key_bytes, out, false, nullptr, workspace,
-                         workspace_bytes, stream);
+    return lsm_scan_call(lsm, ranges, max_seq, descending, cand_entries, cand_key_bytes, out, false, nullptr, false,
+                         nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
 }
 
 sdb_status sdb_lsm_scan_merge(const sdb_lsm_view *lsm, const sdb_scan_ranges *ranges, const uint64_t *max_seq,
                               int32_t descending, uint64_t cand_entries, uint64_t cand_key_bytes,
                               const sdb_lsm_scan_out *out, const sdb_chain_out *chain, void *workspace,
                               uint64_t workspace_bytes, void *stream) {
-    return lsm_scan_call(lsm, ranges, max_seq, descending, cand_entries, cand_key_bytes, out, true, chain, workspace,
-                         workspace_bytes, stream);
+    return lsm_scan_call(lsm, ranges, max_seq, descending, cand_entries, cand_key_bytes, out, true, chain, false, nullptr,
+                         nullptr, nullptr, workspace, workspace_bytes, stream);
+}
+
+sdb_status sdb_lsm_scan_filtered(const sdb_lsm_view *lsm, const sdb_filter_policy *policies, const sdb_scan_ranges *ranges,
+                                 const sdb_scan_prefixes *prefixes, const uint64_t *max_seq, int32_t descending,
+                                 uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out *out,
+                                 const sdb_chain_out *chain, const sdb_scan_filter_out *fout, void *workspace,
+                                 uint64_t workspace_bytes, void *stream) {
+    return lsm_scan_call(lsm, ranges, max_seq, descending, cand_entries, cand_key_bytes, out, chain != nullptr, chain, true,
+                         policies, prefixes, fout, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@
 #include <mutex>
 
 #include "sdb_bloom.h"
+#include "sdb_filter.h"
 
 namespace sdb {
 
@@ -571,10 +572,6 @@ namespace sdb {
 //   k_pf_plan   one workgroup: total hashes -> filter_size_bytes (u32 arithmetic), m, fastmod constant
 //   k_pf_set    per entry: the probes of its hashes, device-scope atomicOr into the zeroed bitmap
 // ------------------------------------------------------------------------------------------------
-struct PrefixSpec {
-    uint32_t kind, arg, whole, pad;
-    const int32_t *lens;  // SDB_PREFIX_LENGTHS
-};
 struct PrefixWs {
     int64_t *chunk_last;   // per chunk: last entry with a prefix (-1: none)
     int64_t *prev_last;    // per chunk: last entry with a prefix before the chunk
@@ -584,17 +581,7 @@ struct PrefixWs {
 };
 constexpr uint32_t kPfChunk = 1024;
 
-SDB_DEV int64_t pf_len(const PrefixSpec &ps, const uint8_t *k, uint32_t kl, uint64_t i) {  // -1 = None
-    if (ps.kind == SDB_PREFIX_FIXED) return kl >= ps.arg ? (int64_t)ps.arg : -1;
-    if (ps.kind == SDB_PREFIX_DELIM) {
-        for (uint32_t x = 0; x < kl; x++)
-            if (k[x] == (uint8_t)ps.arg) return (int64_t)x + 1;
-        return -1;
-    }
-    if (ps.kind == SDB_PREFIX_LENGTHS) return ps.lens ? (int64_t)ps.lens[i] : -1;
-    return -1;
-}
-
+// (PrefixSpec and pf_len, the extractor, are in sdb_filter.h: the reads extract with them too.)
 // Entry indices travel as i + 1 (0 = none) so the scans are unsigned maxima with identity 0 (the DPP
 // lanes without a source read 0).
 SDB_DEV uint64_t umax64(uint64_t x, uint64_t y) { return x > y ? x : y; }
@@ -768,34 +755,15 @@ hipError_t launch_bloom_prefix(const uint8_t *key_bytes, const uint64_t *key_off
     return hipGetLastError();
 }
 
-// Filter::might_match (filter.rs:149-175)
+// Filter::might_match (filter.rs:149-175): filter_probe_len and filter_might_match of sdb_filter.h per query
 __global__ __launch_bounds__(256) void k_bloom_match(const uint8_t *bitmap, uint64_t bytes, uint32_t k, uint32_t whole,
                                                      PrefixSpec ps, const uint8_t *key_bytes, const uint64_t *key_off,
                                                      const uint8_t *is_prefix, uint64_t n, uint8_t *result) {
-    const uint32_t m = (uint32_t)(bytes * 8);
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
         const uint64_t ko = key_off[i];
         const uint32_t kl = (uint32_t)(key_off[i + 1] - ko);
-        const bool pfx = is_prefix && is_prefix[i];
-        int64_t len = -1;
-        if (!pfx && whole) len = kl;
-        else if (ps.kind != SDB_PREFIX_NONE) len = pf_len(ps, key_bytes + ko, kl, i);
-        uint8_t r = 1;  // nothing to probe: no false negative
-        if (len >= 0) {
-            r = 0;
-            if (m) {  // might_contain: an empty bitmap answers false
-                r = 1;
-                const uint64_t h = siphash13(key_bytes + ko, (uint64_t)len);
-                for_each_probe(h, k, m, [&](uint32_t p) {
-                    if (!((bitmap[p >> 3] >> (p & 7)) & 1u)) {
-                        r = 0;
-                        return false;
-                    }
-                    return true;
-                });
-            }
-        }
-        result[i] = r;
+        const Probe pr = filter_probe(ps, is_prefix && is_prefix[i], key_bytes + ko, kl, i);
+        result[i] = filter_might_match(bitmap, bytes, k, pr.len, pr.h);  // nothing to probe: no false negative
     }
 }
 

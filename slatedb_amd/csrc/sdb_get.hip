@@ -32,6 +32,10 @@
 //                   records behind it are never looked at, so their block errors never surface; one row
 //                   re-parsed for the columns; wave reduction + one atomic per counter and workgroup
 //   k_get_final     the summary
+// sdb_lsm_get_filtered passes the SSTs' filter policies: the filter step of k_get_locate and of the walk asks
+// Filter::might_match for Point(key) under the SST's policy (sdb_filter.h) where sdb_lsm_get, the plain policy, probes the
+// full key.  What a key probes depends on the policy alone: k_get_validate finds whether the policies agree, and then
+// a pair's thread hashes once for all its SSTs, as before; else once per SST that has a filter.
 #include "sdb_decode.h"
 #include "sdb_read.h"
 
@@ -78,6 +82,10 @@ struct GetArgs {
     RunRec *rec;               // per pair: see RunRec
     unsigned long long *acc;   // kAcc* accumulators
     uint32_t *bad;             // 1 = the tree is malformed
+    // sdb_lsm_get_filtered only (else nullptr: every SST has the plain whole-key policy)
+    const sdb_filter_policy *pol;  // per SST
+    const int32_t *probe_len;  // per query: prefix_len(Point(key)) for SDB_PREFIX_LENGTHS SSTs
+    uint32_t *uni;             // 1 = the policies agree: a key's probe is the same for every SST
     // sdb_lsm_get_merge only
     sdb_chain_out chain;
     MergeRec *mrec;            // per pair: see MergeRec
@@ -89,8 +97,10 @@ enum { kAccFound = 0, kAccDeleted, kAccNotFound, kAccMerge, kAccFailed, kAccBloc
 
 __global__ __launch_bounds__(256) void k_get_validate(GetArgs a) {
     const int bad = lsm_validate(a.t, a.sstat);
+    const int uni = policies_validate(a.pol, a.t.num_ssts, a.sstat);
     if (threadIdx.x == 0) {
         *a.bad = bad ? 1u : 0u;
+        *a.uni = uni ? 1u : 0u;
         for (int i = 0; i < kAccWords; i++) a.acc[i] = i == kAccFirstBad ? ~0ull : 0ull;
     }
 }
@@ -137,16 +147,38 @@ struct Step {
     int st;
     uint32_t start, end;
 };
-SDB_DEV Step get_step(const GetArgs &a, const sdb_sst_view &v, uint32_t i, const Key &k, uint64_t h) {
+// What Point(k) of query q probes in the filter of SST i (filter_probe of sdb_filter.h); it depends on the SST only
+// through its policy.
+SDB_DEV Probe get_probe(const GetArgs &a, uint64_t q, const Key &k, uint32_t i) {
+    return filter_probe(policy_spec(a.pol, i, a.probe_len), false, k.t, k.nt, q);
+}
+// P: the call has filter policies (sdb_lsm_get_filtered); the kernels of the filter step exist once without them, where
+// the probe is the full key's hash as sdb_lsm_get always computed it, and once with them, so the plain calls keep
+// their registers and occupancy.  pr: the probe of the last SST with a filter, have: there was one; when the policies
+// agree (uni) it is every SST's, so a pair's thread hashes once.
+template <bool P>
+struct PairProbe {
+    bool uni, have;
+    Probe pr;
+    SDB_DEV PairProbe(const GetArgs &a, const Key &k)
+        : uni(P ? *a.uni != 0 : true), have(!P), pr(P ? Probe{-1, 0} : Probe{(int64_t)k.nt, siphash13(k.t, k.nt)}) {}
+};
+template <bool P>
+SDB_DEV Step get_step(const GetArgs &a, const sdb_sst_view &v, uint32_t i, uint64_t q, const Key &k, PairProbe<P> &pp) {
     Step s{false, 0, 0, 0};
-    if (v.bloom && !bloom_might_contain(v.bloom, v.bloom_len, v.num_probes, h)) {
-        s.filtered = true;
-        return s;
+    if (v.bloom) {
+        if (P && (!pp.have || !pp.uni)) pp.pr = get_probe(a, q, k, i);
+        pp.have = true;
+        if (!filter_might_match(v.bloom, v.bloom_len, v.num_probes, pp.pr.len, pp.pr.h)) {
+            s.filtered = true;
+            return s;
+        }
     }
     if (!(s.st = a.sstat[i])) point_block_range(v, k.t, k.nt, s.start, s.end);
     return s;
 }
 
+template <bool P>
 __global__ __launch_bounds__(256) void k_get_locate(GetArgs a) {
     if (*a.bad) return;
     const uint32_t R = a.t.num_runs;
@@ -158,11 +190,11 @@ __global__ __launch_bounds__(256) void k_get_locate(GetArgs a) {
         uint32_t first, last;
         uint8_t rs = kRunNone;
         if (get_run(a, r, k, first, last)) {
-            const uint64_t h = siphash13(k.t, k.nt);  // filter_hash (filter.rs:196-204): one hash for every SST's filter
+            PairProbe<P> pp(a, k);  // filter_hash (filter.rs:196-204): one hash for every SST's filter
             rs = last > first ? kRunOpen : kRunFiltered;  // several covering SSTs: the resolve counts them itself
             for (uint32_t i = first; i <= last; i++) {
                 const sdb_sst_view v = a.t.ssts[i];
-                const Step s = get_step(a, v, i, k, h);
+                const Step s = get_step<P>(a, v, i, q, k, pp);
                 if (s.filtered) continue;
                 rs = kRunOpen;
                 if (s.st) continue;
@@ -232,7 +264,7 @@ SDB_DEV int get_versions(const sdb_sst_view &v, const Step &s, const Key &k, uin
 // The walk of pair t: the visible versions of query t % nkeys in the covering SSTs of run t / nkeys, in chain order,
 // every block of an SST's range checked before its rows are used: visit(sst, block, its Blk, position, row) ->
 // false: stop.  -> the status that ends the walk; nread / nfilt: the SSTs consulted / filtered up to there.
-template <typename F>
+template <bool P, typename F>
 SDB_DEV int walk_pair(const GetArgs &a, uint64_t t, uint8_t rs, uint32_t &nread, uint32_t &nfilt, F &&visit) {
     const uint64_t q = t % a.nkeys;
     const Key k = key_of(a, q);
@@ -255,12 +287,12 @@ SDB_DEV int walk_pair(const GetArgs &a, uint64_t t, uint8_t rs, uint32_t &nread,
         const sdb_sst_view v = a.t.ssts[in.sst];
         search(in.sst, v, Step{false, 0, in.block, in.at});
     } else {
-        const uint64_t h = siphash13(k.t, k.nt);
         uint32_t first = 0, last = 0;
         bool go = get_run(a, (uint32_t)(t / a.nkeys), k, first, last);
+        PairProbe<P> pp(a, k);
         for (uint32_t i = first; go && i <= last; i++) {
             const sdb_sst_view v = a.t.ssts[i];
-            const Step s = get_step(a, v, i, k, h);
+            const Step s = get_step<P>(a, v, i, q, k, pp);
             if (s.filtered) nfilt++;
             else if ((st = s.st)) go = false;
             else go = search(i, v, s);
@@ -269,6 +301,7 @@ SDB_DEV int walk_pair(const GetArgs &a, uint64_t t, uint8_t rs, uint32_t &nread,
     return st;
 }
 
+template <bool P>
 __global__ __launch_bounds__(64) void k_get_walk(GetArgs a) {
     if (*a.bad) return;
     const uint64_t total = a.nkeys * a.t.num_runs;
@@ -278,7 +311,7 @@ __global__ __launch_bounds__(64) void k_get_walk(GetArgs a) {
         uint32_t sst = 0xFFFFFFFFu, nread = 0, nfilt = 0;
         Hit H;
         H.ok = false;
-        const int st = walk_pair(a, t, rs, nread, nfilt, [&](uint32_t i, uint32_t blk, const Blk &, uint32_t at, const Row &) {
+        const int st = walk_pair<P>(a, t, rs, nread, nfilt, [&](uint32_t i, uint32_t blk, const Blk &, uint32_t at, const Row &) {
             H.ok = true;  // the first visible version decides
             H.block = blk;
             H.at = at;
@@ -394,8 +427,9 @@ static uint64_t get_bind(GetArgs &a, uint8_t *w) {
     c.take(a.sstat, (uint64_t)a.t.num_ssts + 1);
     c.take(a.rstate, pairs + 1);
     c.take(a.rec, pairs + 1);
-    c.take(a.acc, kAccWords + 1);  // the accumulators, then bad
+    c.take(a.acc, kAccWords + 1);  // the accumulators, then bad and uni
     if (w) a.bad = (uint32_t *)(a.acc + kAccWords);
+    if (w) a.uni = a.bad + 1;
     return c.off;
 }
 
@@ -408,8 +442,9 @@ uint64_t get_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t 
     return get_bind(a, nullptr);
 }
 
-hipError_t launch_get(const sdb_lsm_view &t, const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
-                      const uint64_t *max_seq, const sdb_get_out &out, uint8_t *w, hipStream_t st) {
+hipError_t launch_get(const sdb_lsm_view &t, const sdb_filter_policy *pol, const uint8_t *key_bytes, const uint64_t *key_off,
+                      uint64_t nkeys, const int32_t *probe_len, const uint64_t *max_seq, const sdb_get_out &out, uint8_t *w,
+                      hipStream_t st) {
     const uint64_t tb = t.total_blocks, n = nkeys;
     hipError_t e;
     if ((e = hipMemsetAsync(out.summary, 0, sizeof(sdb_get_summary), st)) != hipSuccess) return e;
@@ -435,19 +470,23 @@ hipError_t launch_get(const sdb_lsm_view &t, const uint8_t *key_bytes, const uin
     a.nkeys = n;
     a.max_seq = max_seq;
     a.out = out;
+    a.pol = pol;
+    a.probe_len = probe_len;
     get_bind(a, w);
     if ((e = hipMemsetAsync(a.mark, 0, tb, st)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(a.bstat, 0xFF, 4 * tb, st)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_get_validate, dim3(1), dim3(256), 0, st, a);
     uint64_t lg = (n * t.num_runs + 255) / 256;  // the kernel strides past this cap
     if (lg > (1u << 20)) lg = 1u << 20;
-    hipLaunchKernelGGL(k_get_locate, dim3((uint32_t)lg), dim3(256), 0, st, a);
+    if (a.pol || a.probe_len) hipLaunchKernelGGL(k_get_locate<true>, dim3((uint32_t)lg), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_get_locate<false>, dim3((uint32_t)lg), dim3(256), 0, st, a);
     if ((e = launch_check(CheckArgs{{}, t, a.bad, tb, a.mark, a.bstat}, st)) != hipSuccess) return e;
     // the per-block parse and the per-query walk are latency-bound threads: one wave per workgroup spreads them over the CUs
     hipLaunchKernelGGL(k_get_rows, dim3((uint32_t)((tb + 63) / 64)), dim3(64), 0, st, a);
     uint64_t wg = (n * t.num_runs + 63) / 64;
     if (wg > (1u << 22)) wg = 1u << 22;
-    hipLaunchKernelGGL(k_get_walk, dim3((uint32_t)wg), dim3(64), 0, st, a);
+    if (a.pol || a.probe_len) hipLaunchKernelGGL(k_get_walk<true>, dim3((uint32_t)wg), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL(k_get_walk<false>, dim3((uint32_t)wg), dim3(64), 0, st, a);
     hipLaunchKernelGGL(k_get_resolve, dim3((uint32_t)((n + 63) / 64)), dim3(64), 0, st, a);
     hipLaunchKernelGGL(k_get_final, dim3(1), dim3(64), 0, st, a);
     return hipGetLastError();
@@ -465,6 +504,7 @@ hipError_t launch_get(const sdb_lsm_view &t, const uint8_t *key_bytes, const uin
 //   k_gm_emit     thread per pair the chain takes: the walk again, its links written at chain_start[q] + off
 // =================================================================================================
 
+template <bool P>
 __global__ __launch_bounds__(64) void k_gm_walk(GetArgs a) {
     if (blockIdx.x == 0 && threadIdx.x == 0) a.macc[kMaccMaxChain] = a.macc[kMaccGo] = 0;
     if (*a.bad) return;
@@ -474,7 +514,7 @@ __global__ __launch_bounds__(64) void k_gm_walk(GetArgs a) {
         if (rs != kRunOpen && rs != kRunOpen1) continue;
         MergeRec m{};
         uint32_t nread = 0, nfilt = 0;
-        const int st = walk_pair(a, t, rs, nread, nfilt, [&](uint32_t i, uint32_t blk, const Blk &, uint32_t at, const Row &r) {
+        const int st = walk_pair<P>(a, t, rs, nread, nfilt, [&](uint32_t i, uint32_t blk, const Blk &, uint32_t at, const Row &r) {
             if (!m.hit) {
                 m.hit = 1;
                 m.sst = i;
@@ -606,6 +646,7 @@ __global__ void k_gm_final(GetArgs a) {
     a.macc[kMaccGo] = fits;
 }
 
+template <bool P>
 __global__ __launch_bounds__(64) void k_gm_emit(GetArgs a) {
     if (*a.bad || !a.macc[kMaccGo]) return;
     const uint64_t total = a.nkeys * a.t.num_runs;
@@ -617,7 +658,7 @@ __global__ __launch_bounds__(64) void k_gm_emit(GetArgs a) {
         if (!a.mrec[t].use || !n || a.out.status[q]) continue;
         const uint64_t at0 = a.chain.chain_start[q] + a.mrec[t].off;
         uint32_t x = 0, nread = 0, nfilt = 0;
-        walk_pair(a, t, rs, nread, nfilt, [&](uint32_t i, uint32_t blk, const Blk &b, uint32_t, const Row &r) {
+        walk_pair<P>(a, t, rs, nread, nfilt, [&](uint32_t i, uint32_t blk, const Blk &b, uint32_t, const Row &r) {
             if (r.flags & SDB_FLAG_TOMBSTONE) return false;
             const uint64_t d = at0 + x;
             if (x >= n || d >= a.chain.cap_links) return false;  // never out of the pair's slots
@@ -652,15 +693,15 @@ uint64_t get_merge_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uin
     return get_merge_bind(a, nullptr);
 }
 
-hipError_t launch_get_merge(const sdb_lsm_view &t, const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
-                            const uint64_t *max_seq, const sdb_get_out &out, const sdb_chain_out &chain, uint8_t *w,
-                            hipStream_t st) {
+hipError_t launch_get_merge(const sdb_lsm_view &t, const sdb_filter_policy *pol, const uint8_t *key_bytes,
+                            const uint64_t *key_off, uint64_t nkeys, const int32_t *probe_len, const uint64_t *max_seq,
+                            const sdb_get_out &out, const sdb_chain_out &chain, uint8_t *w, hipStream_t st) {
     const uint64_t tb = t.total_blocks, n = nkeys;
     hipError_t e;
     if (n == 0 || t.num_ssts == 0 || t.num_runs == 0 || tb == 0) {  // no links; the columns as launch_get leaves them
         if ((e = hipMemsetAsync(chain.summary, 0, sizeof(sdb_chain_summary), st)) != hipSuccess) return e;
         if ((e = hipMemsetAsync(chain.chain_start, 0, 8 * (n + 1), st)) != hipSuccess) return e;
-        return launch_get(t, key_bytes, key_off, nkeys, max_seq, out, w, st);
+        return launch_get(t, pol, key_bytes, key_off, nkeys, probe_len, max_seq, out, w, st);
     }
     if ((e = hipMemsetAsync(out.summary, 0, sizeof(sdb_get_summary), st)) != hipSuccess) return e;
     GetArgs a{};
@@ -670,6 +711,8 @@ hipError_t launch_get_merge(const sdb_lsm_view &t, const uint8_t *key_bytes, con
     a.nkeys = n;
     a.max_seq = max_seq;
     a.out = out;
+    a.pol = pol;
+    a.probe_len = probe_len;
     a.chain = chain;
     get_merge_bind(a, w);
     if ((e = hipMemsetAsync(a.mark, 0, tb, st)) != hipSuccess) return e;
@@ -677,16 +720,19 @@ hipError_t launch_get_merge(const sdb_lsm_view &t, const uint8_t *key_bytes, con
     hipLaunchKernelGGL(k_get_validate, dim3(1), dim3(256), 0, st, a);
     uint64_t lg = (n * t.num_runs + 255) / 256;  // the kernels stride past these caps
     if (lg > (1u << 20)) lg = 1u << 20;
-    hipLaunchKernelGGL(k_get_locate, dim3((uint32_t)lg), dim3(256), 0, st, a);
+    if (a.pol || a.probe_len) hipLaunchKernelGGL(k_get_locate<true>, dim3((uint32_t)lg), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_get_locate<false>, dim3((uint32_t)lg), dim3(256), 0, st, a);
     if ((e = launch_check(CheckArgs{{}, t, a.bad, tb, a.mark, a.bstat}, st)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_get_rows, dim3((uint32_t)((tb + 63) / 64)), dim3(64), 0, st, a);
     uint64_t wg = (n * t.num_runs + 63) / 64;
     if (wg > (1u << 22)) wg = 1u << 22;
-    hipLaunchKernelGGL(k_gm_walk, dim3((uint32_t)wg), dim3(64), 0, st, a);
+    if (a.pol || a.probe_len) hipLaunchKernelGGL(k_gm_walk<true>, dim3((uint32_t)wg), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL(k_gm_walk<false>, dim3((uint32_t)wg), dim3(64), 0, st, a);
     hipLaunchKernelGGL(k_gm_resolve, dim3((uint32_t)((n + 63) / 64)), dim3(64), 0, st, a);
     if ((e = launch_excl_scan2(a.qn, a.qn, n, a.tx, a.ty, chain.chain_start, a.qscan, st)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_gm_final, dim3(1), dim3(64), 0, st, a);
-    hipLaunchKernelGGL(k_gm_emit, dim3((uint32_t)wg), dim3(64), 0, st, a);
+    if (a.pol || a.probe_len) hipLaunchKernelGGL(k_gm_emit<true>, dim3((uint32_t)wg), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL(k_gm_emit<false>, dim3((uint32_t)wg), dim3(64), 0, st, a);
     return hipGetLastError();
 }
 

@@ -47,6 +47,16 @@
 //   k_ls_fold      thread per merged position of a chain: the row parsed, folded into its winner's aggregates
 //                  (atomics), written as a link
 // and k_ls_emit takes a winner's chain_start, aggregates and flags from there.
+// sdb_lsm_scan_filtered (filter != 0; Db::scan_prefix: SstIteratorOptions.prefix, reader.rs:284-293, evaluated by every
+// per-SST iterator before it opens the SST, sst_iter.rs:848-862) runs either sequence with the filters consulted:
+//   k_ls_validate  also: do the SSTs' policies agree; a prefix_kind that does not exist makes its SST unusable
+//   k_ls_ranges    also: prefix offsets that descend; when the policies agree, what the range's query probes
+//                  (filter_probe of sdb_filter.h) and its SipHash, once for every SST
+//   k_ls_locate    ahead of the marking: Filter::might_match of the pair (the range's probe, else the pair's own) ->
+//                  the pair's `filt` byte; a ruled-out SST takes no part, so nothing of it is marked, checked or staged
+//                  and none of its errors shows; neighbouring ranges of one SST share a wave, so a wave's probes hit
+//                  one bitmap
+//   k_ls_rstat     also: range_filtered, and their sum for k_ls_final
 #include <climits>
 
 #include "sdb_range.h"
@@ -94,22 +104,64 @@ struct LsArgs {
     uint64_t *lwin;                 // per merged position: the winner whose chain it belongs to (~0: none)
     long long *wcts, *wets;         // per winner: MergeTracker's maximum create_ts / minimum expire_ts
     uint32_t *whas;                 // per winner: the timestamp flag bits seen | kBase
+    // sdb_lsm_scan_filtered only
+    uint32_t filter, pad3;          // 1 = the SSTs' filters are consulted
+    const sdb_filter_policy *pol;   // per SST, or nullptr: the plain whole-key policy
+    sdb_scan_prefixes px;           // all nullptr: no range has a prefix
+    sdb_scan_filter_out fout;
+    uint8_t *filt;                  // per pair: 1 = the SST's filter ruled it out for the range
+    int64_t *qlen;                  // per range, when the policies agree: what its query probes in every SST:
+    uint64_t *qh;                   //   the length (< 0: nothing) and the filter hash
 };
 enum { kBase = 0x100 };  // a value or a tombstone ended the chain
-enum { kCtlFirstBad = 0, kCtlFailed, kCtlBad, kCtlGo1, kCtlGo2, kCtlGo3, kCtlMaxChain, kCtlWords = 8 };
+enum { kCtlFirstBad = 0, kCtlFailed, kCtlBad, kCtlGo1, kCtlGo2, kCtlGo3, kCtlMaxChain, kCtlFiltered, kCtlUniform, kCtlWords = 16 };
 
 __global__ __launch_bounds__(256) void k_ls_validate(LsArgs a) {
     const int bad = lsm_validate(a.t, a.sstat);
+    const int uni = policies_validate(a.pol, a.t.num_ssts, a.sstat);
     if (threadIdx.x == 0) {
         for (int i = 0; i < kCtlWords; i++) a.ctl[i] = i == kCtlFirstBad ? ~0ull : 0ull;
         a.ctl[kCtlBad] = bad ? 1ull : 0ull;
+        a.ctl[kCtlUniform] = uni ? 1ull : 0ull;
     }
+}
+
+// What range r asks the filters (F1 of sdb_lsm_scan_filtered): a point range Point(key), else Prefix(p) where it has a
+// prefix; false: nothing.
+struct Query {
+    const uint8_t *t;
+    uint32_t n;
+    bool prefix;
+};
+SDB_DEV bool ls_query(const LsArgs &a, uint64_t r, const Bound &s, const Bound &e, Query &q) {
+    if (s.kind == SDB_BOUND_INCLUDED && e.kind == SDB_BOUND_INCLUDED && s.n == e.n && cmp_bytes(s.t, s.n, e.t, e.n, 0).c == 0) {
+        q = Query{s.t, s.n, false};  // SstView::point_key
+        return true;
+    }
+    if (!a.px.has_prefix || !a.px.has_prefix[r]) return false;
+    const uint64_t o = a.px.prefix_off[r];
+    q = Query{a.px.prefix_bytes + o, (uint32_t)(a.px.prefix_off[r + 1] - o), true};
+    return true;
+}
+// What that query probes in the filter of SST i; it depends on the SST only through its policy.
+SDB_DEV Probe ls_probe(const LsArgs &a, uint64_t r, const Query &q, uint32_t i) {
+    return filter_probe(policy_spec(a.pol, i, a.px.probe_len), q.prefix, q.t, q.n, r);
 }
 
 __global__ __launch_bounds__(256) void k_ls_ranges(LsArgs a) {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= a.r.n) return;
-    if (a.r.start_off[r + 1] < a.r.start_off[r] || a.r.end_off[r + 1] < a.r.end_off[r]) atomicOr(&a.ctl[kCtlBad], 1ull);
+    bool bad = a.r.start_off[r + 1] < a.r.start_off[r] || a.r.end_off[r + 1] < a.r.end_off[r];
+    if (a.filter && a.px.prefix_off && a.px.prefix_off[r + 1] < a.px.prefix_off[r]) bad = true;
+    if (bad) atomicOr(&a.ctl[kCtlBad], 1ull);
+    if (bad || !a.filter || !a.ctl[kCtlUniform]) return;
+    // the policies agree: what the range probes, and its SipHash, once for every SST
+    const Bound s = range_start(a.r, r), e = range_end(a.r, r);
+    Probe pr{-1, 0};
+    Query q;
+    if (!bad_kind(s, e) && ls_query(a, r, s, e, q)) pr = ls_probe(a, r, q, 0);
+    a.qlen[r] = pr.len;
+    a.qh[r] = pr.h;
 }
 
 // Thread t of the per-pair kernels: neighbouring ranges of one SST share a wave.
@@ -119,6 +171,9 @@ SDB_DEV void ls_pair(const LsArgs &a, uint64_t t, uint64_t &r, uint32_t &i, uint
     p = r * a.t.num_ssts + i;
 }
 
+// FILTER: the call consults the filters (sdb_lsm_scan_filtered); the kernel exists once without the step, so the plain
+// scans keep their registers and occupancy.
+template <bool FILTER>
 __global__ __launch_bounds__(256) void k_ls_locate(LsArgs a) {
     if (a.ctl[kCtlBad]) return;
     for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < a.pairs; t += (uint64_t)gridDim.x * blockDim.x) {
@@ -135,6 +190,18 @@ __global__ __launch_bounds__(256) void k_ls_locate(LsArgs a) {
         if (part && e.kind) {  // its first key exceeds it
             const uint64_t o = a.t.first_key_off[i];
             part = !exceeds(e, cmp_bytes(a.t.first_key_bytes + o, (uint32_t)(a.t.first_key_off[i + 1] - o), e.t, e.n, 0).c);
+        }
+        if (FILTER) {  // the filter first (FilterIterator::init): a ruled-out SST takes no part, whatever its state
+            uint8_t filt = 0;
+            if (part && v.bloom) {
+                Probe pr{-1, 0};
+                Query q;
+                if (a.ctl[kCtlUniform]) pr = Probe{a.qlen[r], a.qh[r]};
+                else if (ls_query(a, r, s, e, q)) pr = ls_probe(a, r, q, i);
+                filt = !filter_might_match(v.bloom, v.bloom_len, v.num_probes, pr.len, pr.h);
+                if (filt) part = false;
+            }
+            a.filt[p] = filt;
         }
         BlockRange g{0, 0};
         if (part && !a.sstat[i]) {
@@ -256,13 +323,14 @@ __global__ __launch_bounds__(64) void k_ls_rstat(LsArgs a) {
     if (r >= a.r.n) return;
     const uint32_t S = a.t.num_ssts;
     int st = 0;
-    uint32_t ns = 0;
+    uint32_t ns = 0, nf = 0;
     if (a.ctl[kCtlBad]) {
         st = SDB_INVALID_ARGUMENT;
     } else if (bad_kind(range_start(a.r, r), range_end(a.r, r))) {
         st = SDB_INVALID_ARGUMENT;
     } else {
         for (uint32_t i = 0; i < S; i++) {
+            if (a.filter && a.filt[r * S + i]) nf++;
             if (!a.part[r * S + i]) continue;
             ns++;
             if (!st) st = a.pst[r * S + i];
@@ -273,6 +341,10 @@ __global__ __launch_bounds__(64) void k_ls_rstat(LsArgs a) {
     a.out.range_status[r] = st;
     a.out.range_ssts[r] = ns;
     a.rop[r] = 0;
+    if (a.filter) {
+        a.fout.range_filtered[r] = nf;
+        if (nf) atomicAdd(&a.ctl[kCtlFiltered], (unsigned long long)nf);
+    }
 }
 
 // Do the candidates fit; and the winner flags of every merged position zeroed (k_ls_rank sets the winners').
@@ -464,6 +536,7 @@ __global__ void k_ls_final(LsArgs a) {
     if (!fits) s.status = SDB_LIMIT_EXCEEDED;
     else a.out.key_off[s.num_entries] = s.key_bytes;
     *a.out.summary = s;
+    if (a.filter) *a.fout.num_filtered = a.ctl[kCtlFiltered];
     a.ctl[kCtlGo2] = fits;
     if (a.merge) {  // candidates, then rows, then links
         sdb_chain_summary cs{};
@@ -613,20 +686,32 @@ static uint64_t lsm_scan_merge_bind(LsArgs &a, uint8_t *w) {
     return c.off;
 }
 
+// The workspace arrays of a filtered scan: those of the scan or the merging scan, then its own.
+static uint64_t lsm_scan_filter_bind(LsArgs &a, uint8_t *w, bool merge) {
+    Carver c{w, merge ? lsm_scan_merge_bind(a, w) : lsm_scan_bind(a, w)};
+    c.take(a.filt, a.pairs + 1);
+    c.take(a.qlen, a.r.n + 1);
+    c.take(a.qh, a.r.n + 1);
+    return c.off;
+}
+
 uint64_t lsm_scan_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint64_t nranges, uint64_t cand_entries,
-                                  uint64_t cand_key_bytes, bool merge) {
+                                  uint64_t cand_key_bytes, bool merge, bool filter) {
     LsArgs a{};
     a.t.total_blocks = total_blocks;
     a.t.num_ssts = num_ssts;
     a.r.n = nranges;
     a.cand_entries = cand_entries;
     a.cand_key_bytes = cand_key_bytes;
+    if (filter) return lsm_scan_filter_bind(a, nullptr, merge);
     return merge ? lsm_scan_merge_bind(a, nullptr) : lsm_scan_bind(a, nullptr);
 }
 
 hipError_t launch_lsm_scan(const sdb_lsm_view &t, const sdb_scan_ranges &r, const uint64_t *max_seq, uint32_t desc,
                            uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out &out,
-                           const sdb_chain_out *chain /* sdb_lsm_scan_merge, else nullptr */, uint8_t *w, hipStream_t st) {
+                           const sdb_chain_out *chain /* sdb_lsm_scan_merge, else nullptr */,
+                           const sdb_filter_policy *pol, const sdb_scan_prefixes *px,
+                           const sdb_scan_filter_out *fout /* sdb_lsm_scan_filtered, else nullptr */, uint8_t *w, hipStream_t st) {
     const uint64_t tb = t.total_blocks, n = r.n;
     hipError_t e;
     if (n == 0 || t.num_ssts == 0 || tb == 0) {  // every range is empty
@@ -638,6 +723,8 @@ hipError_t launch_lsm_scan(const sdb_lsm_view &t, const sdb_scan_ranges &r, cons
         if ((e = hipMemsetAsync(out.range_entry_start, 0, 8 * (n + 1), st)) != hipSuccess) return e;
         if (n && (e = hipMemsetAsync(out.range_status, 0, 4 * n, st)) != hipSuccess) return e;
         if (n && (e = hipMemsetAsync(out.range_ssts, 0, 4 * n, st)) != hipSuccess) return e;
+        if (fout && n && (e = hipMemsetAsync(fout->range_filtered, 0, 4 * n, st)) != hipSuccess) return e;
+        if (fout && fout->num_filtered && (e = hipMemsetAsync(fout->num_filtered, 0, 8, st)) != hipSuccess) return e;
         return hipMemsetAsync(out.key_off, 0, 8, st);
     }
     LsArgs a{};
@@ -651,6 +738,14 @@ hipError_t launch_lsm_scan(const sdb_lsm_view &t, const sdb_scan_ranges &r, cons
     if (chain) {
         a.merge = 1;
         a.chain = *chain;
+    }
+    if (fout) {
+        a.filter = 1;
+        a.pol = pol;
+        if (px) a.px = *px;
+        a.fout = *fout;
+        lsm_scan_filter_bind(a, w, chain != nullptr);
+    } else if (chain) {
         lsm_scan_merge_bind(a, w);
     } else {
         lsm_scan_bind(a, w);
@@ -661,7 +756,8 @@ hipError_t launch_lsm_scan(const sdb_lsm_view &t, const sdb_scan_ranges &r, cons
     const uint32_t rw = (uint32_t)((n + 63) / 64);
     hipLaunchKernelGGL(k_ls_validate, dim3(1), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_ls_ranges, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_ls_locate, dim3(scan_grid(P, 256)), dim3(256), 0, st, a);
+    if (a.filter) hipLaunchKernelGGL(k_ls_locate<true>, dim3(scan_grid(P, 256)), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_ls_locate<false>, dim3(scan_grid(P, 256)), dim3(256), 0, st, a);
     if ((e = launch_check(CheckArgs{{}, t, (const uint32_t *)(a.ctl + kCtlBad), tb, a.mark, a.bstat}, st)) != hipSuccess) return e;
     // the per-block, per-pair and per-item walks are latency-bound threads: one wave per workgroup spreads them over the CUs
     hipLaunchKernelGGL(k_ls_block, dim3((uint32_t)((tb + 63) / 64)), dim3(64), 0, st, a);

@@ -9,6 +9,7 @@
 #include "sdb_bloom.h"
 #include "sdb_crc.h"
 #include "sdb_device.h"
+#include "sdb_filter.h"
 
 namespace sdb {
 
@@ -421,19 +422,6 @@ SDB_DEV void put_row(const Out &o, uint64_t i, uint64_t base, const Row &r) {
     o.flags[i] = r.flags;
     o.create_ts[i] = (r.flags & SDB_FLAG_HAS_CREATE_TS) ? r.cts : 0;
     o.expire_ts[i] = (r.flags & SDB_FLAG_HAS_EXPIRE_TS) ? r.ets : 0;
-}
-
-// might_contain (filter.rs:124-136) for the filter hash h; an empty bitmap answers false.
-SDB_DEV bool bloom_might_contain(const uint8_t *bloom, uint64_t bloom_len, uint32_t num_probes, uint64_t h) {
-    const uint32_t m = (uint32_t)(bloom_len * 8);
-    if (!m) return false;
-    uint32_t hh = (uint32_t)h % m, d = (uint32_t)(h >> 32) % m;
-    for (uint32_t i = 0; i < num_probes; i++) {
-        d = (uint32_t)(((uint64_t)d + i) % m);
-        if (!((bloom[hh >> 3] >> (hh & 7)) & 1)) return false;
-        hh = (uint32_t)(((uint64_t)hh + d) % m);
-    }
-    return true;
 }
 
 // Block::decode bounds + CRC of the block data[s, e) by one wave (lane l), over the wave's LDS image

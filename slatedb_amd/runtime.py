@@ -792,9 +792,12 @@ def keys_columnar(keys):
 def lsm_tree_device(views, runs, device=None):
     """The device-resident sdb_lsm_view of a tree.  views: per-SST tensor dicts in search order, as
     sst_lookup_device takes them plus first_key / last_key (bytes: SsTableInfo.first_entry / last_entry;
-    absent or None for an SST without entries).  runs: the number of SSTs of each run, newest run first
-    (an L0 SST is a run of one).  Returns a dict: "lsm" (the _abi.LsmView), num_ssts, num_runs,
-    total_blocks and, under "_"-prefixed keys, the device arrays it points into."""
+    absent or None for an SST without entries) and optionally policy: (prefix_kind, prefix_arg, no_whole_key),
+    what the SST's filter was built with (absent: the plain whole-key policy), which the filtered reads
+    (lsm_scan_filtered_device, lsm_get_filtered_device) take as "_policies" (None when no view has one).  runs:
+    the number of SSTs of each run, newest run first (an L0 SST is a run of one).  Returns a dict: "lsm" (the
+    _abi.LsmView), num_ssts, num_runs, total_blocks and, under "_"-prefixed keys, the device arrays it points
+    into."""
     import torch
     ns = len(views)
     assert sum(runs) == ns and all(r >= 0 for r in runs), "runs must partition the views"
@@ -820,6 +823,12 @@ def lsm_tree_device(views, runs, device=None):
                             t["_first_key_bytes"].data_ptr(), t["_first_key_off"].data_ptr(),
                             t["_last_key_bytes"].data_ptr(), t["_last_key_off"].data_ptr(),
                             t["_block_base"].data_ptr(), total)
+    t["_policies"] = None
+    if any(vt.get("policy") is not None for vt in views):
+        pol = np.zeros((ns, 4), np.uint32)
+        for i, vt in enumerate(views):
+            pol[i, :3] = vt.get("policy") or (0, 0, 0)
+        t["_policies"] = dv(pol.view(np.int32).reshape(-1))
     t.update(num_ssts=ns, num_runs=len(runs), total_blocks=total, device=dev)
     return t
 
@@ -1036,6 +1045,112 @@ def lsm_scan_merge_device(tree, ranges, max_seq=None, descending=False, stream=N
     else:
         run(cand[0], cand[1], cap[0], cap[1], cap_links)
     res.update(_tree=tree, _ranges=rt, _max_seq=max_seq)
+    return res
+
+
+def scan_prefixes_columnar(prefixes, probe_len=None):
+    """[prefix bytes or None per range] (None: a plain Db::scan, no prefix query) and optionally the
+    SDB_PREFIX_LENGTHS answers per range -> the host arrays of sdb_scan_prefixes: dict of prefix_bytes,
+    prefix_off, has_prefix and probe_len (None when not given)."""
+    kb, ko = keys_columnar([bytes(p or b"") for p in prefixes])
+    return {"prefix_bytes": kb, "prefix_off": ko,
+            "has_prefix": np.array([p is not None for p in prefixes] or [0], np.uint8),
+            "probe_len": None if probe_len is None else np.array(list(probe_len) or [0], np.int32)}
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def lsm_scan_filtered_device(tree, ranges, prefixes=None, probe_len=None, max_seq=None, descending=False, stream=None,
+                             workspace=None, cand=None, cap=None, cap_links=None, fill=0, merge=False):
+    """sdb_lsm_scan_filtered: lsm_scan_device (merge=False) or lsm_scan_merge_device (merge=True) with the SSTs'
+    filters consulted under the tree's policies (lsm_tree_device's per-view policy).  prefixes: None (no range has
+    a prefix), a list with the scan prefix of every range (bytes: Db::scan_prefix, None: Db::scan), or a dict of
+    device tensors named as scan_prefixes_columnar's arrays; probe_len: with a list of prefixes, the per-range
+    lengths for SDB_PREFIX_LENGTHS SSTs.  The other arguments, the retry once on SDB_LIMIT_EXCEEDED and the result
+    are the unfiltered call's, plus range_filtered (n) and num_filtered (one element)."""
+    import torch
+    dev, rt, n, max_seq, rg, res = _lsm_scan_call(tree, ranges, max_seq)
+    pt = prefixes
+    if prefixes is not None and not isinstance(prefixes, dict):
+        assert len(prefixes) == n, "one prefix (or None) per range"
+        pt = {k: None if a is None else torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(dev)
+              for k, a in scan_prefixes_columnar(prefixes, probe_len).items()}
+    px = None if pt is None else _abi.ScanPrefixes(_ptr(pt["prefix_bytes"]), _ptr(pt["prefix_off"]), _ptr(pt["has_prefix"]),
+                                                   _ptr(pt.get("probe_len")))
+    res["range_filtered"] = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    res["num_filtered"] = torch.zeros(1, dtype=torch.int64, device=dev)
+    fout = _abi.ScanFilterOut(res["range_filtered"].data_ptr(), res["num_filtered"].data_ptr())
+    pol = tree.get("_policies")
+
+    def run(ce, ckb, cap_e, cap_k, cap_l):
+        wsb = lib().sdb_lsm_scan_filtered_workspace_bytes(tree["total_blocks"], tree["num_ssts"], tree["num_runs"], n, ce,
+                                                          ckb, int(bool(merge)))
+        ws = workspace if workspace is not None and workspace.numel() >= wsb else None
+        if ws is None:
+            assert workspace is None or cand is None, "workspace too small"
+            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        out = _lsm_scan_out(res, cap_e, cap_k, dev)
+        chain = _chain_out(res, cap_e, cap_l, dev, fill) if merge else None
+        st = lib().sdb_lsm_scan_filtered(C.byref(tree["lsm"]), _ptr(pol), C.byref(rg), C.byref(px) if px is not None else None,
+                                         _ptr(max_seq), int(bool(descending)), ce, ckb, C.byref(out),
+                                         C.byref(chain) if merge else None, C.byref(fout), ws.data_ptr(), wsb, _sp(stream))
+        if st:
+            raise SdbError(st, "sdb_lsm_scan_filtered")
+        res["_ws"] = ws
+
+    if cand is None or cap is None or (merge and cap_links is None):
+        ce, ckb = cand if cand is not None else (0, 0)
+        run(ce, ckb, *(cap if cap is not None else (0, 0)), cap_links or 0)
+        _sync(stream, dev)
+        status = [int(res["summary"].cpu().numpy()[6]) & 0xFFFFFFFF]
+        if merge:
+            status.append(int(res["chain_summary"].cpu().numpy()[2]) & 0xFFFFFFFF)
+        if _abi.SDB_LIMIT_EXCEEDED in status:
+            sm = res["summary"].cpu().numpy()
+            ce, ckb = max(ce, int(sm[2])), max(ckb, int(sm[3]))
+            run(ce, ckb, *(cap if cap is not None else (ce, ckb)), cap_links if cap_links is not None else ce)
+    else:
+        run(cand[0], cand[1], cap[0], cap[1], cap_links or 0)
+    res.update(_tree=tree, _ranges=rt, _max_seq=max_seq, _prefixes=pt)
+    return res
+
+
+def lsm_get_filtered_device(views, runs, keys, probe_len=None, max_seq=None, stream=None, workspace=None, cap_links=None,
+                            fill=0, merge=False):
+    """sdb_lsm_get_filtered: lsm_get_device (merge=False) or lsm_get_merge_device (merge=True) with every SST's
+    filter probed under its policy (lsm_tree_device's per-view policy), so trees written with a prefix extractor or
+    without whole-key hashes are served.  probe_len: None, a list / array of nkeys lengths for SDB_PREFIX_LENGTHS
+    SSTs (-1: None), or a device int32 tensor.  The other arguments, the retry on links that do not fit and the
+    result are the unfiltered call's."""
+    import torch
+    tree, dev, kb, ko, n, max_seq, res, out = _get_call(views, runs, keys, max_seq)
+    if probe_len is not None and not hasattr(probe_len, "data_ptr"):
+        probe_len = torch.from_numpy(np.asarray(list(probe_len) or [0], np.int32)).to(dev)
+    wsb = lib().sdb_lsm_get_filtered_workspace_bytes(tree["total_blocks"], tree["num_ssts"], tree["num_runs"], n,
+                                                     int(bool(merge)))
+    ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=dev)
+    assert ws.numel() >= wsb, "workspace too small"
+    pol = tree.get("_policies")
+
+    def run(cap):
+        chain = _chain_out(res, n, cap, dev, fill) if merge else None
+        st = lib().sdb_lsm_get_filtered(C.byref(tree["lsm"]), _ptr(pol), kb.data_ptr(), ko.data_ptr(), n, _ptr(probe_len),
+                                        _ptr(max_seq), C.byref(out), C.byref(chain) if merge else None, ws.data_ptr(),
+                                        wsb, _sp(stream))
+        if st:
+            raise SdbError(st, "sdb_lsm_get_filtered")
+
+    if merge and cap_links is None:
+        run(n)  # one link per query is the least a tree of values needs
+        _sync(stream, dev)
+        sm = res["chain_summary"].cpu().numpy()
+        if int(sm[2]) & 0xFFFFFFFF == _abi.SDB_LIMIT_EXCEEDED:
+            run(int(sm[0]))
+    else:
+        run(cap_links or 0)
+    res.update(_ws=ws, _tree=tree, _keys=(kb, ko), _max_seq=max_seq, _probe_len=probe_len)
     return res
 
 
