@@ -16,29 +16,7 @@
 #include "sdb_decode.h"
 #include "sdb_bloom.h"
 #include "sdb_compact.h"
-
-namespace sdb {
-uint64_t lookup_workspace_bytes(uint64_t num_blocks, uint64_t nkeys);
-hipError_t launch_lookup(const sdb_sst_view &v, const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
-                         uint32_t desc, const sdb_lookup_out &out, uint8_t *w, hipStream_t st);
-uint64_t scan_workspace_bytes(uint64_t num_blocks, uint64_t nranges);
-hipError_t launch_scan(const sdb_sst_view &v, const sdb_scan_ranges &r, uint32_t desc, const sdb_scan_out &out, uint8_t *w,
-                       hipStream_t st);
-uint64_t lsm_scan_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint64_t nranges, uint64_t cand_entries,
-                                  uint64_t cand_key_bytes, bool merge, bool filter);
-hipError_t launch_lsm_scan(const sdb_lsm_view &t, const sdb_scan_ranges &r, const uint64_t *max_seq, uint32_t desc,
-                           uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out &out,
-                           const sdb_chain_out *chain, const sdb_filter_policy *pol, const sdb_scan_prefixes *px,
-                           const sdb_scan_filter_out *fout, uint8_t *w, hipStream_t st);
-uint64_t get_merge_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys);
-hipError_t launch_get_merge(const sdb_lsm_view &t, const sdb_filter_policy *pol, const uint8_t *key_bytes,
-                            const uint64_t *key_off, uint64_t nkeys, const int32_t *probe_len, const uint64_t *max_seq,
-                            const sdb_get_out &out, const sdb_chain_out &chain, uint8_t *w, hipStream_t st);
-uint64_t get_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys);
-hipError_t launch_get(const sdb_lsm_view &t, const sdb_filter_policy *pol, const uint8_t *key_bytes, const uint64_t *key_off,
-                      uint64_t nkeys, const int32_t *probe_len, const uint64_t *max_seq, const sdb_get_out &out, uint8_t *w,
-                      hipStream_t st);
-}  // namespace sdb
+#include "sdb_reads.h"
 
 using namespace sdb;
 
@@ -636,7 +614,7 @@ sdb_status sdb_sst_scan(const sdb_sst_view *sst, const sdb_scan_ranges *ranges, 
 }
 
 uint64_t sdb_lsm_get_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys) {
-    return get_workspace_bytes(total_blocks, num_ssts, num_runs, nkeys) + 256;
+    return get_workspace_bytes(total_blocks, num_ssts, num_runs, nkeys, false) + 256;
 }
 
 // NULL: nothing missing.  The CSR offsets and the summary always, the link columns where there is room for a link.
@@ -662,14 +640,14 @@ static sdb_status lsm_get_call(const sdb_lsm_view *lsm, const sdb_filter_policy 
                   !out->val_len || !out->seq || !out->flags || !out->create_ts || !out->expire_ts || !out->ssts_read ||
                   !out->ssts_filtered))
         return SDB_INVALID_ARGUMENT;
-    const uint64_t need = merge ? sdb_lsm_get_merge_workspace_bytes(lsm->total_blocks, lsm->num_ssts, lsm->num_runs, nkeys)
-                                : sdb_lsm_get_workspace_bytes(lsm->total_blocks, lsm->num_ssts, lsm->num_runs, nkeys);
-    if (!workspace || workspace_bytes < need) return SDB_INVALID_ARGUMENT;
+    if (!workspace || workspace_bytes < get_workspace_bytes(lsm->total_blocks, lsm->num_ssts, lsm->num_runs, nkeys, merge) + 256)
+        return SDB_INVALID_ARGUMENT;
     if (!device_ok()) return SDB_DEVICE_ERROR;
     uint8_t *w = ws_align(workspace);
-    const hipError_t e = merge ? launch_get_merge(*lsm, policies, key_bytes, key_off, nkeys, probe_len, max_seq, *out, *chain, w, S(stream))
-                               : launch_get(*lsm, policies, key_bytes, key_off, nkeys, probe_len, max_seq, *out, w, S(stream));
-    return e != hipSuccess ? SDB_DEVICE_ERROR : SDB_OK;
+    if (launch_get(*lsm, policies, key_bytes, key_off, nkeys, probe_len, max_seq, *out, merge ? chain : nullptr, w,
+                   S(stream)) != hipSuccess)
+        return SDB_DEVICE_ERROR;
+    return SDB_OK;
 }
 
 sdb_status sdb_lsm_get(const sdb_lsm_view *lsm, const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
@@ -680,7 +658,7 @@ sdb_status sdb_lsm_get(const sdb_lsm_view *lsm, const uint8_t *key_bytes, const 
 }
 
 uint64_t sdb_lsm_get_merge_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys) {
-    return get_merge_workspace_bytes(total_blocks, num_ssts, num_runs, nkeys) + 256;
+    return get_workspace_bytes(total_blocks, num_ssts, num_runs, nkeys, true) + 256;
 }
 
 sdb_status sdb_lsm_get_merge(const sdb_lsm_view *lsm, const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
@@ -692,8 +670,7 @@ sdb_status sdb_lsm_get_merge(const sdb_lsm_view *lsm, const uint8_t *key_bytes, 
 
 uint64_t sdb_lsm_get_filtered_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys,
                                               int32_t merge) {
-    return merge ? sdb_lsm_get_merge_workspace_bytes(total_blocks, num_ssts, num_runs, nkeys)
-                 : sdb_lsm_get_workspace_bytes(total_blocks, num_ssts, num_runs, nkeys);
+    return get_workspace_bytes(total_blocks, num_ssts, num_runs, nkeys, merge != 0) + 256;
 }
 
 sdb_status sdb_lsm_get_filtered(const sdb_lsm_view *lsm, const sdb_filter_policy *policies, const uint8_t *key_bytes,

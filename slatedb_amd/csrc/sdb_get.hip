@@ -32,10 +32,23 @@
 //                   records behind it are never looked at, so their block errors never surface; one row
 //                   re-parsed for the columns; wave reduction + one atomic per counter and workgroup
 //   k_get_final     the summary
+// sdb_lsm_get_merge (launch_get with a chain) shares everything up to k_get_rows and replaces the tail: a pair's
+// walk goes on past the first entry while the entries are merge operands, into a 72-byte record of its own.
+//   k_gm_walk       thread per (query, run) with an unfiltered covering SST: the count walk -> the pair's MergeRec
+//   k_get_resolve   its <true> instantiation: the runs in order up to the first that ended the chain or failed; the
+//                   sequence order, the aggregates, the per-query columns, each run's link offset, the query's
+//                   link count
+//   scan            the link counts -> chain_start
+//   k_gm_final      both summaries, do the links fit
+//   k_gm_emit       thread per pair the chain takes: the walk again, its links written at chain_start[q] + off
+// One launcher (launch_get), one workspace layout (get_bind: the plain get's arrays are a prefix of the merging
+// get's) and one resolve body serve both; what differs between them is chosen at compile time.
 // sdb_lsm_get_filtered passes the SSTs' filter policies: the filter step of k_get_locate and of the walk asks
 // Filter::might_match for Point(key) under the SST's policy (sdb_filter.h) where sdb_lsm_get, the plain policy, probes the
 // full key.  What a key probes depends on the policy alone: k_get_validate finds whether the policies agree, and then
 // a pair's thread hashes once for all its SSTs, as before; else once per SST that has a filter.
+#include <algorithm>
+
 #include "sdb_decode.h"
 #include "sdb_read.h"
 
@@ -340,6 +353,19 @@ SDB_DEV void get_count(const GetArgs &a, uint64_t q, bool live, uint32_t state, 
     if (failed) atomicMin(&a.acc[kAccFirstBad], (unsigned long long)(q << 8 | (uint64_t)st));
 }
 
+// The records of the pairs as the walk left them: k_get_walk's (MERGE false) or k_gm_walk's.
+template <bool MERGE>
+SDB_DEV auto pair_recs(const GetArgs &a) {
+    if constexpr (MERGE) return a.mrec;
+    else return a.rec;
+}
+
+// MERGE false, sdb_lsm_get: the first run in order whose record holds an entry or an error decides; an operand there
+// is reported (SDB_MERGE_OPERATOR_MISSING) with its own columns and does not count as failed.  MERGE true,
+// sdb_lsm_get_merge: the runs in order until one ends the chain or fails; the columns are the first entry's with the
+// links' aggregates, and every run the chain takes learns where its links go (off, use).  A compile-time choice: the
+// plain resolve keeps the registers of a kernel that knows nothing of chains.
+template <bool MERGE>
 __global__ __launch_bounds__(64) void k_get_resolve(GetArgs a) {
     const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = q < a.nkeys;
@@ -350,38 +376,65 @@ __global__ __launch_bounds__(64) void k_get_resolve(GetArgs a) {
         Hit H;
         H.ok = false;
         Row r{};
-        uint64_t vbase = 0;
+        uint64_t vbase = 0, links = 0, newest = 0;
+        int64_t cts = 0, ets = 0;
+        uint8_t has = 0, end = kEndOpen;
         if (*a.bad) {
             st = SDB_INVALID_ARGUMENT;
         } else {
             const uint32_t R = a.t.num_runs;
-            for (uint32_t j = 0; j < R && !st && !H.ok; j++) {  // the first run in order that yields something
+            for (uint32_t j = 0; j < R && !st && (MERGE ? !end : !H.ok); j++) {
                 const uint8_t rs = a.rstate[j * a.nkeys + q];
                 if (rs == kRunFiltered) nfilt++;
                 if (rs != kRunOpen && rs != kRunOpen1) continue;
-                const RunRec x = a.rec[j * a.nkeys + q];
+                auto &x = pair_recs<MERGE>(a)[j * a.nkeys + q];
                 nread += x.nread;
                 nfilt += x.nfilt;
-                st = x.st;
-                if (!st && x.hit) {
+                if (x.hit && !H.ok) {  // (a record with an error holds no hit unless it is a chain's)
                     H.ok = true;
                     H.block = x.block;
                     H.at = x.at;
                     sst = x.sst;
                 }
+                if constexpr (MERGE) {
+                    if (x.nlinks) {
+                        if (!links) newest = x.seq0;
+                        if (x.maxseq > newest) {  // MergeTracker::update (merge_operator.rs:293-299)
+                            st = SDB_INVALID_SEQUENCE_ORDER;
+                            break;
+                        }
+                        if (x.has & SDB_FLAG_HAS_CREATE_TS) cts = (has & SDB_FLAG_HAS_CREATE_TS) && cts > x.cts ? cts : x.cts;
+                        if (x.has & SDB_FLAG_HAS_EXPIRE_TS) ets = (has & SDB_FLAG_HAS_EXPIRE_TS) && ets < x.ets ? ets : x.ets;
+                        has |= x.has;
+                        x.off = links;
+                        x.use = 1;
+                        links += x.nlinks;
+                    }
+                    end = x.end;
+                }
+                st = x.st;
             }
-            if (H.ok) {  // the row again, for its columns
+            if (H.ok && !st) {  // the first entry again, for its columns
                 const sdb_sst_view v = a.t.ssts[sst];
                 Blk b;
                 if (!(st = blk_open(v, H.block, b))) st = v.sst_version == 2 ? v2_row(b, H.at, r) : v1_row(b, H.at, r);
                 vbase = b.base;
             }
         }
-        if (st) H.ok = false;
+        if (st) {
+            H.ok = false;
+            links = 0;
+        }
         if (H.ok) {
+            const bool operand = (r.flags & SDB_FLAG_MERGE_OPERAND) != 0;
             if (r.flags & SDB_FLAG_TOMBSTONE) {
                 state = SDB_GET_DELETED;
-            } else if (r.flags & SDB_FLAG_MERGE_OPERAND) {
+            } else if (MERGE) {  // the entry MergeOperatorIterator returns (merge_operator.rs:437-447)
+                state = operand ? SDB_GET_MERGE_OPERAND : SDB_GET_FOUND;
+                r.flags = (uint8_t)(has | (operand && end != kEndValue ? SDB_FLAG_MERGE_OPERAND : 0));
+                r.cts = cts;
+                r.ets = ets;
+            } else if (operand) {
                 state = SDB_GET_MERGE_OPERAND;
                 st = SDB_MERGE_OPERATOR_MISSING;
             } else {
@@ -398,8 +451,12 @@ __global__ __launch_bounds__(64) void k_get_resolve(GetArgs a) {
         put_row(a.out, q, vbase, r);
         a.out.ssts_read[q] = nread;
         a.out.ssts_filtered[q] = nfilt;
+        if constexpr (MERGE) {
+            a.qn[q] = links;
+            if (links) atomicMax(&a.macc[kMaccMaxChain], (unsigned long long)links);
+        }
     }
-    const bool failed = live && st != 0 && state == SDB_GET_NOT_FOUND;
+    const bool failed = live && st != 0 && (MERGE || state == SDB_GET_NOT_FOUND);
     get_count(a, q, live, state, failed, st);
 }
 
@@ -418,90 +475,10 @@ __global__ void k_get_final(GetArgs a) {
     if (threadIdx.x == 0) get_summary(a);
 }
 
-// The workspace arrays of a get of a.nkeys keys over the tree a.t, bound into a from w; -> their size.
-static uint64_t get_bind(GetArgs &a, uint8_t *w) {
-    const uint64_t tb = a.t.total_blocks, pairs = a.nkeys * a.t.num_runs;
-    Carver c{w, 0};
-    c.take(a.mark, tb + 1);
-    c.take(a.bstat, tb + 1);
-    c.take(a.sstat, (uint64_t)a.t.num_ssts + 1);
-    c.take(a.rstate, pairs + 1);
-    c.take(a.rec, pairs + 1);
-    c.take(a.acc, kAccWords + 1);  // the accumulators, then bad and uni
-    if (w) a.bad = (uint32_t *)(a.acc + kAccWords);
-    if (w) a.uni = a.bad + 1;
-    return c.off;
-}
-
-uint64_t get_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys) {
-    GetArgs a{};
-    a.t.total_blocks = total_blocks;
-    a.t.num_ssts = num_ssts;
-    a.t.num_runs = num_runs;
-    a.nkeys = nkeys;
-    return get_bind(a, nullptr);
-}
-
-hipError_t launch_get(const sdb_lsm_view &t, const sdb_filter_policy *pol, const uint8_t *key_bytes, const uint64_t *key_off,
-                      uint64_t nkeys, const int32_t *probe_len, const uint64_t *max_seq, const sdb_get_out &out, uint8_t *w,
-                      hipStream_t st) {
-    const uint64_t tb = t.total_blocks, n = nkeys;
-    hipError_t e;
-    if ((e = hipMemsetAsync(out.summary, 0, sizeof(sdb_get_summary), st)) != hipSuccess) return e;
-    if (n == 0) return hipSuccess;
-    if (t.num_ssts == 0 || t.num_runs == 0 || tb == 0) {  // nothing to search: every query NOT_FOUND
-        if ((e = hipMemsetAsync(out.state, 0, n, st)) != hipSuccess) return e;
-        if ((e = hipMemsetAsync(out.status, 0, 4 * n, st)) != hipSuccess) return e;
-        if ((e = hipMemsetAsync(out.sst, 0xFF, 4 * n, st)) != hipSuccess) return e;
-        if ((e = hipMemsetAsync(out.block, 0, 4 * n, st)) != hipSuccess) return e;
-        if ((e = hipMemsetAsync(out.val_off, 0, 8 * n, st)) != hipSuccess) return e;
-        if ((e = hipMemsetAsync(out.val_len, 0, 4 * n, st)) != hipSuccess) return e;
-        if ((e = hipMemsetAsync(out.seq, 0, 8 * n, st)) != hipSuccess) return e;
-        if ((e = hipMemsetAsync(out.flags, 0, n, st)) != hipSuccess) return e;
-        if ((e = hipMemsetAsync(out.create_ts, 0, 8 * n, st)) != hipSuccess) return e;
-        if ((e = hipMemsetAsync(out.expire_ts, 0, 8 * n, st)) != hipSuccess) return e;
-        if ((e = hipMemsetAsync(out.ssts_read, 0, 4 * n, st)) != hipSuccess) return e;
-        return hipMemsetAsync(out.ssts_filtered, 0, 4 * n, st);
-    }
-    GetArgs a{};
-    a.t = t;
-    a.key_bytes = key_bytes;
-    a.key_off = key_off;
-    a.nkeys = n;
-    a.max_seq = max_seq;
-    a.out = out;
-    a.pol = pol;
-    a.probe_len = probe_len;
-    get_bind(a, w);
-    if ((e = hipMemsetAsync(a.mark, 0, tb, st)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(a.bstat, 0xFF, 4 * tb, st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_get_validate, dim3(1), dim3(256), 0, st, a);
-    uint64_t lg = (n * t.num_runs + 255) / 256;  // the kernel strides past this cap
-    if (lg > (1u << 20)) lg = 1u << 20;
-    if (a.pol || a.probe_len) hipLaunchKernelGGL(k_get_locate<true>, dim3((uint32_t)lg), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_get_locate<false>, dim3((uint32_t)lg), dim3(256), 0, st, a);
-    if ((e = launch_check(CheckArgs{{}, t, a.bad, tb, a.mark, a.bstat}, st)) != hipSuccess) return e;
-    // the per-block parse and the per-query walk are latency-bound threads: one wave per workgroup spreads them over the CUs
-    hipLaunchKernelGGL(k_get_rows, dim3((uint32_t)((tb + 63) / 64)), dim3(64), 0, st, a);
-    uint64_t wg = (n * t.num_runs + 63) / 64;
-    if (wg > (1u << 22)) wg = 1u << 22;
-    if (a.pol || a.probe_len) hipLaunchKernelGGL(k_get_walk<true>, dim3((uint32_t)wg), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL(k_get_walk<false>, dim3((uint32_t)wg), dim3(64), 0, st, a);
-    hipLaunchKernelGGL(k_get_resolve, dim3((uint32_t)((n + 63) / 64)), dim3(64), 0, st, a);
-    hipLaunchKernelGGL(k_get_final, dim3(1), dim3(64), 0, st, a);
-    return hipGetLastError();
-}
-
 // =================================================================================================
 // sdb_lsm_get_merge: the same chain of SSTs, walked past the first entry while the entries are merge operands
 // (MergeOperatorIterator::merge_with_older_entries over GetIterator, merge_operator.rs:369-448, db_iter.rs:102-124).
-// Validate, locate, k_check and k_get_rows are those above, and the walk of a pair is walk_pair; then
-//   k_gm_walk     thread per (query, run) with an unfiltered covering SST: the count walk -> the pair's MergeRec
-//   k_gm_resolve  thread per query: the runs in order up to the first that ended the chain or failed; the sequence
-//                 order, the aggregates, the per-query columns, each run's link offset, the query's link count
-//   scan          the link counts -> chain_start
-//   k_gm_final    both summaries, do the links fit
-//   k_gm_emit     thread per pair the chain takes: the walk again, its links written at chain_start[q] + off
+// Its own kernels: the count walk before the resolve (k_get_resolve<true> above), the final and the emit after it.
 // =================================================================================================
 
 template <bool P>
@@ -549,91 +526,6 @@ __global__ __launch_bounds__(64) void k_gm_walk(GetArgs a) {
     }
 }
 
-__global__ __launch_bounds__(64) void k_gm_resolve(GetArgs a) {
-    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = q < a.nkeys;
-    int st = 0;
-    uint32_t state = SDB_GET_NOT_FOUND;
-    if (live) {
-        uint32_t sst = 0xFFFFFFFFu, nread = 0, nfilt = 0;
-        Hit H;
-        H.ok = false;
-        Row r{};
-        uint64_t vbase = 0, links = 0, newest = 0;
-        int64_t cts = 0, ets = 0;
-        uint8_t has = 0, end = kEndOpen;
-        if (*a.bad) {
-            st = SDB_INVALID_ARGUMENT;
-        } else {
-            const uint32_t R = a.t.num_runs;
-            for (uint32_t j = 0; j < R && !st && !end; j++) {  // the runs in order until one ends the chain or fails
-                const uint8_t rs = a.rstate[j * a.nkeys + q];
-                if (rs == kRunFiltered) nfilt++;
-                if (rs != kRunOpen && rs != kRunOpen1) continue;
-                MergeRec &x = a.mrec[j * a.nkeys + q];
-                nread += x.nread;
-                nfilt += x.nfilt;
-                if (x.hit && !H.ok) {
-                    H.ok = true;
-                    H.block = x.block;
-                    H.at = x.at;
-                    sst = x.sst;
-                }
-                if (x.nlinks) {
-                    if (!links) newest = x.seq0;
-                    if (x.maxseq > newest) {  // MergeTracker::update (merge_operator.rs:293-299)
-                        st = SDB_INVALID_SEQUENCE_ORDER;
-                        break;
-                    }
-                    if (x.has & SDB_FLAG_HAS_CREATE_TS) cts = (has & SDB_FLAG_HAS_CREATE_TS) && cts > x.cts ? cts : x.cts;
-                    if (x.has & SDB_FLAG_HAS_EXPIRE_TS) ets = (has & SDB_FLAG_HAS_EXPIRE_TS) && ets < x.ets ? ets : x.ets;
-                    has |= x.has;
-                    x.off = links;
-                    x.use = 1;
-                    links += x.nlinks;
-                }
-                st = x.st;
-                end = x.end;
-            }
-            if (H.ok && !st) {  // the first entry again, for its columns
-                const sdb_sst_view v = a.t.ssts[sst];
-                Blk b;
-                if (!(st = blk_open(v, H.block, b))) st = v.sst_version == 2 ? v2_row(b, H.at, r) : v1_row(b, H.at, r);
-                vbase = b.base;
-            }
-        }
-        if (st) {
-            H.ok = false;
-            links = 0;
-        }
-        if (H.ok) {
-            if (r.flags & SDB_FLAG_TOMBSTONE) {
-                state = SDB_GET_DELETED;
-            } else {  // the entry MergeOperatorIterator returns (merge_operator.rs:437-447)
-                const bool operand = (r.flags & SDB_FLAG_MERGE_OPERAND) != 0;
-                state = operand ? SDB_GET_MERGE_OPERAND : SDB_GET_FOUND;
-                r.flags = (uint8_t)(has | (operand && end != kEndValue ? SDB_FLAG_MERGE_OPERAND : 0));
-                r.cts = cts;
-                r.ets = ets;
-            }
-        } else {  // no entry: zero columns
-            sst = 0xFFFFFFFFu;
-            r = Row{};
-        }
-        a.out.state[q] = (uint8_t)state;
-        a.out.status[q] = st;
-        a.out.sst[q] = sst;
-        a.out.block[q] = H.ok ? H.block : 0;
-        put_row(a.out, q, vbase, r);
-        a.out.ssts_read[q] = nread;
-        a.out.ssts_filtered[q] = nfilt;
-        a.qn[q] = links;
-        if (links) atomicMax(&a.macc[kMaccMaxChain], (unsigned long long)links);
-    }
-    const bool failed = live && st != 0;
-    get_count(a, q, live, state, failed, st);
-}
-
 __global__ void k_gm_final(GetArgs a) {
     if (threadIdx.x != 0) return;
     get_summary(a);
@@ -671,10 +563,20 @@ __global__ __launch_bounds__(64) void k_gm_emit(GetArgs a) {
     }
 }
 
-// The workspace arrays of a merging get: those of the get, then its own.
-static uint64_t get_merge_bind(GetArgs &a, uint8_t *w) {
-    const uint64_t pairs = a.nkeys * a.t.num_runs, n = a.nkeys;
-    Carver c{w, get_bind(a, w)};
+// The workspace arrays of a get of a.nkeys keys over the tree a.t, bound into a from w; -> their size.  merge: those
+// of the plain get, then the merging get's own.
+static uint64_t get_bind(GetArgs &a, uint8_t *w, bool merge) {
+    const uint64_t tb = a.t.total_blocks, n = a.nkeys, pairs = n * a.t.num_runs;
+    Carver c{w, 0};
+    c.take(a.mark, tb + 1);
+    c.take(a.bstat, tb + 1);
+    c.take(a.sstat, (uint64_t)a.t.num_ssts + 1);
+    c.take(a.rstate, pairs + 1);
+    c.take(a.rec, pairs + 1);
+    c.take(a.acc, kAccWords + 1);  // the accumulators, then bad and uni
+    if (w) a.bad = (uint32_t *)(a.acc + kAccWords);
+    if (w) a.uni = a.bad + 1;
+    if (!merge) return c.off;
     c.take(a.mrec, pairs + 1);
     c.take(a.qn, n + 1);
     c.take(a.qscan, n + 2);
@@ -684,26 +586,66 @@ static uint64_t get_merge_bind(GetArgs &a, uint8_t *w) {
     return c.off;
 }
 
-uint64_t get_merge_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys) {
+uint64_t get_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys, bool merge) {
     GetArgs a{};
     a.t.total_blocks = total_blocks;
     a.t.num_ssts = num_ssts;
     a.t.num_runs = num_runs;
     a.nkeys = nkeys;
-    return get_merge_bind(a, nullptr);
+    return get_bind(a, nullptr, merge);
 }
 
-hipError_t launch_get_merge(const sdb_lsm_view &t, const sdb_filter_policy *pol, const uint8_t *key_bytes,
-                            const uint64_t *key_off, uint64_t nkeys, const int32_t *probe_len, const uint64_t *max_seq,
-                            const sdb_get_out &out, const sdb_chain_out &chain, uint8_t *w, hipStream_t st) {
-    const uint64_t tb = t.total_blocks, n = nkeys;
+// The kernels of a bound get in stream order.  P: the call has filter policies, chosen once for the kernels that hold
+// the filter step; merge: a.chain is given.
+template <bool P>
+static hipError_t launch_get_kernels(const GetArgs &a, bool merge, hipStream_t st) {
+    const uint64_t tb = a.t.total_blocks, n = a.nkeys, pairs = n * a.t.num_runs;
+    // the kernels stride past these caps; the per-block parse and the per-pair walks are latency-bound threads: one
+    // wave per workgroup spreads them over the CUs
+    const dim3 lg((uint32_t)std::min<uint64_t>((pairs + 255) / 256, 1u << 20));
+    const dim3 wg((uint32_t)std::min<uint64_t>((pairs + 63) / 64, 1u << 22)), qg((uint32_t)((n + 63) / 64));
     hipError_t e;
-    if (n == 0 || t.num_ssts == 0 || t.num_runs == 0 || tb == 0) {  // no links; the columns as launch_get leaves them
-        if ((e = hipMemsetAsync(chain.summary, 0, sizeof(sdb_chain_summary), st)) != hipSuccess) return e;
-        if ((e = hipMemsetAsync(chain.chain_start, 0, 8 * (n + 1), st)) != hipSuccess) return e;
-        return launch_get(t, pol, key_bytes, key_off, nkeys, probe_len, max_seq, out, w, st);
+    hipLaunchKernelGGL(k_get_validate, dim3(1), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_get_locate<P>, lg, dim3(256), 0, st, a);
+    if ((e = launch_check(CheckArgs{{}, a.t, a.bad, tb, a.mark, a.bstat}, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_get_rows, dim3((uint32_t)((tb + 63) / 64)), dim3(64), 0, st, a);
+    if (!merge) {
+        hipLaunchKernelGGL(k_get_walk<P>, wg, dim3(64), 0, st, a);
+        hipLaunchKernelGGL(k_get_resolve<false>, qg, dim3(64), 0, st, a);
+        hipLaunchKernelGGL(k_get_final, dim3(1), dim3(64), 0, st, a);
+    } else {
+        hipLaunchKernelGGL(k_gm_walk<P>, wg, dim3(64), 0, st, a);
+        hipLaunchKernelGGL(k_get_resolve<true>, qg, dim3(64), 0, st, a);
+        if ((e = launch_excl_scan2(a.qn, a.qn, n, a.tx, a.ty, a.chain.chain_start, a.qscan, st)) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_gm_final, dim3(1), dim3(64), 0, st, a);
+        hipLaunchKernelGGL(k_gm_emit<P>, wg, dim3(64), 0, st, a);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_get(const sdb_lsm_view &t, const sdb_filter_policy *pol, const uint8_t *key_bytes, const uint64_t *key_off,
+                      uint64_t nkeys, const int32_t *probe_len, const uint64_t *max_seq, const sdb_get_out &out,
+                      const sdb_chain_out *chain /* sdb_lsm_get_merge, else nullptr */, uint8_t *w, hipStream_t st) {
+    const uint64_t tb = t.total_blocks, n = nkeys;
+    const bool none = n == 0 || t.num_ssts == 0 || t.num_runs == 0 || tb == 0;  // nothing to search
+    hipError_t e;
+    if (none && chain) {  // no links
+        if ((e = hipMemsetAsync(chain->summary, 0, sizeof(sdb_chain_summary), st)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(chain->chain_start, 0, 8 * (n + 1), st)) != hipSuccess) return e;
     }
     if ((e = hipMemsetAsync(out.summary, 0, sizeof(sdb_get_summary), st)) != hipSuccess) return e;
+    if (none) {  // every query NOT_FOUND: sst 0xFFFFFFFF, the other columns zero
+        const struct {
+            void *p;
+            int fill;
+            uint64_t width;
+        } cols[] = {{out.state, 0, 1},     {out.status, 0, 4},    {out.sst, 0xFF, 4},    {out.block, 0, 4},
+                    {out.val_off, 0, 8},   {out.val_len, 0, 4},   {out.seq, 0, 8},       {out.flags, 0, 1},
+                    {out.create_ts, 0, 8}, {out.expire_ts, 0, 8}, {out.ssts_read, 0, 4}, {out.ssts_filtered, 0, 4}};
+        for (const auto &c : cols)
+            if (n && (e = hipMemsetAsync(c.p, c.fill, c.width * n, st)) != hipSuccess) return e;
+        return hipSuccess;
+    }
     GetArgs a{};
     a.t = t;
     a.key_bytes = key_bytes;
@@ -713,27 +655,11 @@ hipError_t launch_get_merge(const sdb_lsm_view &t, const sdb_filter_policy *pol,
     a.out = out;
     a.pol = pol;
     a.probe_len = probe_len;
-    a.chain = chain;
-    get_merge_bind(a, w);
+    if (chain) a.chain = *chain;
+    get_bind(a, w, chain != nullptr);
     if ((e = hipMemsetAsync(a.mark, 0, tb, st)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(a.bstat, 0xFF, 4 * tb, st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_get_validate, dim3(1), dim3(256), 0, st, a);
-    uint64_t lg = (n * t.num_runs + 255) / 256;  // the kernels stride past these caps
-    if (lg > (1u << 20)) lg = 1u << 20;
-    if (a.pol || a.probe_len) hipLaunchKernelGGL(k_get_locate<true>, dim3((uint32_t)lg), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_get_locate<false>, dim3((uint32_t)lg), dim3(256), 0, st, a);
-    if ((e = launch_check(CheckArgs{{}, t, a.bad, tb, a.mark, a.bstat}, st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_get_rows, dim3((uint32_t)((tb + 63) / 64)), dim3(64), 0, st, a);
-    uint64_t wg = (n * t.num_runs + 63) / 64;
-    if (wg > (1u << 22)) wg = 1u << 22;
-    if (a.pol || a.probe_len) hipLaunchKernelGGL(k_gm_walk<true>, dim3((uint32_t)wg), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL(k_gm_walk<false>, dim3((uint32_t)wg), dim3(64), 0, st, a);
-    hipLaunchKernelGGL(k_gm_resolve, dim3((uint32_t)((n + 63) / 64)), dim3(64), 0, st, a);
-    if ((e = launch_excl_scan2(a.qn, a.qn, n, a.tx, a.ty, chain.chain_start, a.qscan, st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_gm_final, dim3(1), dim3(64), 0, st, a);
-    if (a.pol || a.probe_len) hipLaunchKernelGGL(k_gm_emit<true>, dim3((uint32_t)wg), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL(k_gm_emit<false>, dim3((uint32_t)wg), dim3(64), 0, st, a);
-    return hipGetLastError();
+    return pol || probe_len ? launch_get_kernels<true>(a, chain != nullptr, st) : launch_get_kernels<false>(a, chain != nullptr, st);
 }
 
 }  // namespace sdb

@@ -10,6 +10,7 @@
 #include "sdb_crc.h"
 #include "sdb_device.h"
 #include "sdb_filter.h"
+#include "sdb_reads.h"
 
 namespace sdb {
 

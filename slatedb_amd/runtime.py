@@ -789,6 +789,12 @@ def keys_columnar(keys):
     return np.frombuffer(b"".join(keys) or b"\0", np.uint8).copy(), off
 
 
+def _to_dev(array, dev):
+    """A host array as a tensor on dev; uint64 goes as int64, bit for bit (torch has no uint64 to speak of)."""
+    import torch
+    return torch.from_numpy(array.view(np.int64) if array.dtype == np.uint64 else array).to(dev)
+
+
 def lsm_tree_device(views, runs, device=None):
     """The device-resident sdb_lsm_view of a tree.  views: per-SST tensor dicts in search order, as
     sst_lookup_device takes them plus first_key / last_key (bytes: SsTableInfo.first_entry / last_entry;
@@ -810,7 +816,7 @@ def lsm_tree_device(views, runs, device=None):
                               bloom.data_ptr() if bloom is not None else None,
                               int(vt.get("bloom_len", 0)) if bloom is not None else 0, int(vt.get("num_probes", 0)),
                               int(vt.get("sst_version", 2)), 0)
-    dv = lambda a: torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(dev)  # noqa: E731
+    dv = lambda a: _to_dev(a, dev)  # noqa: E731
     fkb, fko = keys_columnar([bytes(vt.get("first_key") or b"") for vt in views])
     lkb, lko = keys_columnar([bytes(vt.get("last_key") or b"") for vt in views])
     t = {"_views": views,
@@ -833,9 +839,21 @@ def lsm_tree_device(views, runs, device=None):
     return t
 
 
-def _get_call(views, runs, keys, max_seq):
-    """What lsm_get_device and lsm_get_merge_device marshal alike: the tree, the keys and bounds as device tensors,
-    the result dict with the GET_FIELDS and the summary, and the sdb_get_out over them."""
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _limit_exceeded(summary, word):
+    return int(summary.cpu().numpy()[word]) & 0xFFFFFFFF == _abi.SDB_LIMIT_EXCEEDED
+
+
+def _lsm_get(entry, views, runs, keys, max_seq, stream, workspace, merge=False, cap_links=None, fill=0, filtered=False,
+             probe_len=None):
+    """The tree gets.  entry: the C entry point (sdb_lsm_get, sdb_lsm_get_merge or sdb_lsm_get_filtered; its sizer
+    is entry + "_workspace_bytes"); filtered: it takes the policies, probe_len and an optional chain; merge: the
+    call has a chain.  Marshals the tree, the keys, the bounds and probe_len as device tensors, the result dict with
+    the GET_FIELDS and the summary; a caller's workspace must hold the call; with merge and cap_links None the links
+    are sized at nkeys first and, when they did not fit, at the reported num_links in a second call."""
     import torch
     tree = views if isinstance(views, dict) else lsm_tree_device(views, runs)
     dev = tree["device"]
@@ -843,14 +861,37 @@ def _get_call(views, runs, keys, max_seq):
         kb, ko, n = keys
     else:
         n = len(keys)
-        hb, ho = keys_columnar([bytes(k) for k in keys])
-        kb, ko = torch.from_numpy(hb).to(dev), torch.from_numpy(ho.view(np.int64)).to(dev)
+        kb, ko = (_to_dev(a, dev) for a in keys_columnar([bytes(k) for k in keys]))
     if max_seq is not None and not hasattr(max_seq, "data_ptr"):
-        max_seq = torch.from_numpy(np.asarray(max_seq, np.uint64).view(np.int64).copy()).to(dev)
+        max_seq = _to_dev(np.asarray(max_seq, np.uint64).copy(), dev)
+    if probe_len is not None and not hasattr(probe_len, "data_ptr"):
+        probe_len = _to_dev(np.asarray(list(probe_len) or [0], np.int32), dev)
     res = {f: torch.zeros(max(n, 1), dtype=getattr(torch, dt), device=dev) for f, dt in GET_FIELDS}
     res["summary"] = torch.zeros(len(GET_SUMMARY), dtype=torch.int64, device=dev)
     out = _abi.GetOut(*[res[f].data_ptr() for f, _ in GET_FIELDS], res["summary"].data_ptr())
-    return tree, dev, kb, ko, n, max_seq, res, out
+    wsb = getattr(lib(), entry + "_workspace_bytes")(tree["total_blocks"], tree["num_ssts"], tree["num_runs"], n,
+                                                     *([int(bool(merge))] if filtered else []))
+    ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=dev)
+    assert ws.numel() >= wsb, "workspace too small"
+
+    def run(cap):
+        chain = _chain_out(res, n, cap, dev, fill) if merge else None
+        args = [C.byref(tree["lsm"])] + ([_ptr(tree.get("_policies"))] if filtered else [])
+        args += [kb.data_ptr(), ko.data_ptr(), n] + ([_ptr(probe_len)] if filtered else [])
+        args += [_ptr(max_seq), C.byref(out)] + ([C.byref(chain) if merge else None] if merge or filtered else [])
+        st = getattr(lib(), entry)(*args, ws.data_ptr(), wsb, _sp(stream))
+        if st:
+            raise SdbError(st, entry)
+
+    if merge and cap_links is None:
+        run(n)  # one link per query is the least a tree of values needs
+        _sync(stream, dev)
+        if _limit_exceeded(res["chain_summary"], 2):
+            run(int(res["chain_summary"][0].item()))
+    else:
+        run(cap_links or 0)
+    res.update(_ws=ws, _tree=tree, _keys=(kb, ko), _max_seq=max_seq, _probe_len=probe_len)
+    return res
 
 
 def lsm_get_device(views, runs, keys, max_seq=None, stream=None, workspace=None):
@@ -860,18 +901,7 @@ def lsm_get_device(views, runs, keys, max_seq=None, stream=None, workspace=None)
     int64 tensor.  workspace: a device uint8 tensor to use (and reuse) instead of a fresh one.  With device
     tensors and a prebuilt tree the call copies nothing from the host, so it can be captured into a graph.  Returns a dict of device tensors (GET_FIELDS, and summary: the
     sdb_get_summary words in GET_SUMMARY order); what the call allocated stays alive under "_" keys."""
-    import torch
-    tree, dev, kb, ko, n, max_seq, res, out = _get_call(views, runs, keys, max_seq)
-    wsb = lib().sdb_lsm_get_workspace_bytes(tree["total_blocks"], tree["num_ssts"], tree["num_runs"], n)
-    ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=dev)
-    assert ws.numel() >= wsb, "workspace too small"
-    st = lib().sdb_lsm_get(C.byref(tree["lsm"]), kb.data_ptr(), ko.data_ptr(), n,
-                           max_seq.data_ptr() if max_seq is not None else None, C.byref(out), ws.data_ptr(), wsb,
-                           _sp(stream))
-    if st:
-        raise SdbError(st, "sdb_lsm_get")
-    res.update(_ws=ws, _tree=tree, _keys=(kb, ko), _max_seq=max_seq)
-    return res
+    return _lsm_get("sdb_lsm_get", views, runs, keys, max_seq, stream, workspace)
 
 
 LSM_SCAN_COLUMNS = (("sst", "int32"),) + SCAN_COLUMNS
@@ -893,27 +923,71 @@ def _lsm_scan_out(res, cap_e, cap_k, dev):
     return out
 
 
-def _lsm_scan_call(tree, ranges, max_seq):
-    """What lsm_scan_device and lsm_scan_merge_device marshal alike: the ranges and bounds as device tensors, the
-    sdb_scan_ranges over them and the result dict with the per-range arrays and the summary."""
+def _lsm_scan(entry, tree, ranges, max_seq, descending, stream, workspace, cand, cap, merge=False, cap_links=None, fill=0,
+              filtered=False, prefixes=None, probe_len=None):
+    """The tree scans.  entry: the C entry point (sdb_lsm_scan, sdb_lsm_scan_merge or sdb_lsm_scan_filtered; its
+    sizer is entry + "_workspace_bytes"); filtered: it takes the policies, the prefixes, an optional chain and the
+    filter outputs; merge: the call has a chain.  Marshals the ranges, the bounds and the prefixes as device tensors
+    and the result dict; a caller's workspace that is too small is replaced by a fresh one, unless cand was given.
+    With a capacity None (cap_links counts only with merge) the call runs once, and on SDB_LIMIT_EXCEEDED again
+    with the staging at max(given, reported), cap like the staging and cap_links like cand_entries where those
+    were None."""
     import torch
     dev = tree["device"]
     if isinstance(ranges, dict):
         rt, n = ranges, int(ranges["n"])
     else:
         n = len(ranges)
-        rt = {}
-        for k, a in scan_ranges_columnar(ranges).items():
-            rt[k] = torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(dev)
+        rt = {k: _to_dev(a, dev) for k, a in scan_ranges_columnar(ranges).items()}
     if max_seq is not None and not hasattr(max_seq, "data_ptr"):
-        max_seq = torch.from_numpy(np.asarray(list(max_seq) or [0], np.uint64).view(np.int64).copy()).to(dev)
+        max_seq = _to_dev(np.asarray(list(max_seq) or [0], np.uint64), dev)
     rg = _abi.ScanRanges(n, rt["start_bytes"].data_ptr(), rt["start_off"].data_ptr(), rt["start_kind"].data_ptr(),
                          rt["end_bytes"].data_ptr(), rt["end_off"].data_ptr(), rt["end_kind"].data_ptr())
     res = {"range_entry_start": torch.zeros(n + 1, dtype=torch.int64, device=dev),
            "range_status": torch.zeros(max(n, 1), dtype=torch.int32, device=dev),
            "range_ssts": torch.zeros(max(n, 1), dtype=torch.int32, device=dev),
            "summary": torch.zeros(len(LSM_SCAN_SUMMARY), dtype=torch.int64, device=dev)}
-    return dev, rt, n, max_seq, rg, res
+    pt = prefixes
+    if filtered:
+        if prefixes is not None and not isinstance(prefixes, dict):
+            assert len(prefixes) == n, "one prefix (or None) per range"
+            pt = {k: None if a is None else _to_dev(a, dev) for k, a in scan_prefixes_columnar(prefixes, probe_len).items()}
+        px = None if pt is None else _abi.ScanPrefixes(_ptr(pt["prefix_bytes"]), _ptr(pt["prefix_off"]),
+                                                       _ptr(pt["has_prefix"]), _ptr(pt.get("probe_len")))
+        res["range_filtered"] = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        res["num_filtered"] = torch.zeros(1, dtype=torch.int64, device=dev)
+        fout = _abi.ScanFilterOut(res["range_filtered"].data_ptr(), res["num_filtered"].data_ptr())
+
+    def run(ce, ckb, cap_e, cap_k, cap_l):
+        wsb = getattr(lib(), entry + "_workspace_bytes")(tree["total_blocks"], tree["num_ssts"], tree["num_runs"], n, ce,
+                                                         ckb, *([int(bool(merge))] if filtered else []))
+        ws = workspace if workspace is not None and workspace.numel() >= wsb else None
+        if ws is None:
+            assert workspace is None or cand is None, "workspace too small"
+            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        out = _lsm_scan_out(res, cap_e, cap_k, dev)
+        chain = _chain_out(res, cap_e, cap_l, dev, fill) if merge else None
+        args = [C.byref(tree["lsm"])] + ([_ptr(tree.get("_policies"))] if filtered else []) + [C.byref(rg)]
+        args += ([C.byref(px) if px is not None else None] if filtered else [])
+        args += [_ptr(max_seq), int(bool(descending)), ce, ckb, C.byref(out)]
+        args += ([C.byref(chain) if merge else None] if merge or filtered else []) + ([C.byref(fout)] if filtered else [])
+        st = getattr(lib(), entry)(*args, ws.data_ptr(), wsb, _sp(stream))
+        if st:
+            raise SdbError(st, entry)
+        res["_ws"] = ws
+
+    if cand is None or cap is None or (merge and cap_links is None):
+        ce, ckb = cand if cand is not None else (0, 0)
+        run(ce, ckb, *(cap if cap is not None else (0, 0)), cap_links or 0)
+        _sync(stream, dev)
+        if _limit_exceeded(res["summary"], 6) or (merge and _limit_exceeded(res["chain_summary"], 2)):
+            sm = res["summary"].cpu().numpy()
+            ce, ckb = max(ce, int(sm[2])), max(ckb, int(sm[3]))
+            run(ce, ckb, *(cap if cap is not None else (ce, ckb)), cap_links if cap_links is not None else ce)
+    else:
+        run(cand[0], cand[1], cap[0], cap[1], cap_links or 0)
+    res.update(_tree=tree, _ranges=rt, _max_seq=max_seq, _prefixes=pt)
+    return res
 
 
 def lsm_scan_device(tree, ranges, max_seq=None, descending=False, stream=None, workspace=None, cand=None, cap=None):
@@ -927,34 +1001,7 @@ def lsm_scan_device(tree, ranges, max_seq=None, descending=False, stream=None, w
     be captured into a graph.  Returns a dict of device tensors: range_entry_start (n + 1), range_status,
     range_ssts, key_arena, key_off, the LSM_SCAN_COLUMNS and summary (the sdb_lsm_scan_summary words in
     LSM_SCAN_SUMMARY order); what the call allocated stays alive under "_" keys."""
-    import torch
-    dev, rt, n, max_seq, rg, res = _lsm_scan_call(tree, ranges, max_seq)
-
-    def run(ce, ckb, cap_e, cap_k):
-        wsb = lib().sdb_lsm_scan_workspace_bytes(tree["total_blocks"], tree["num_ssts"], tree["num_runs"], n, ce, ckb)
-        ws = workspace if workspace is not None and workspace.numel() >= wsb else None
-        if ws is None:
-            assert workspace is None or cand is None, "workspace too small"
-            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        out = _lsm_scan_out(res, cap_e, cap_k, dev)
-        st = lib().sdb_lsm_scan(C.byref(tree["lsm"]), C.byref(rg), max_seq.data_ptr() if max_seq is not None else None,
-                                int(bool(descending)), ce, ckb, C.byref(out), ws.data_ptr(), wsb, _sp(stream))
-        if st:
-            raise SdbError(st, "sdb_lsm_scan")
-        res["_ws"] = ws
-
-    if cand is None or cap is None:
-        ce, ckb = cand if cand is not None else (0, 0)
-        run(ce, ckb, *(cap if cap is not None else (0, 0)))
-        _sync(stream, dev)
-        sm = res["summary"].cpu().numpy()
-        if int(sm[6]) & 0xFFFFFFFF == _abi.SDB_LIMIT_EXCEEDED:
-            ce, ckb = max(ce, int(sm[2])), max(ckb, int(sm[3]))
-            run(ce, ckb, *(cap if cap is not None else (ce, ckb)))
-    else:
-        run(cand[0], cand[1], cap[0], cap[1])
-    res.update(_tree=tree, _ranges=rt, _max_seq=max_seq)
-    return res
+    return _lsm_scan("sdb_lsm_scan", tree, ranges, max_seq, descending, stream, workspace, cand, cap)
 
 
 CHAIN_COLUMNS = (("sst", "int32"), ("block", "int32"), ("val_off", "int64"), ("val_len", "int32"), ("seq", "int64"),
@@ -982,30 +1029,8 @@ def lsm_get_merge_device(views, runs, keys, max_seq=None, stream=None, workspace
     synchronisation) and calls again when the links did not fit.  With cap_links given, device tensors and a
     workspace the call copies nothing from the host, so it can be captured into a graph.  fill: what the link
     columns hold before the call, byte by byte."""
-    import torch
-    tree, dev, kb, ko, n, max_seq, res, out = _get_call(views, runs, keys, max_seq)
-    wsb = lib().sdb_lsm_get_merge_workspace_bytes(tree["total_blocks"], tree["num_ssts"], tree["num_runs"], n)
-    ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=dev)
-    assert ws.numel() >= wsb, "workspace too small"
-
-    def run(cap):
-        chain = _chain_out(res, n, cap, dev, fill)
-        st = lib().sdb_lsm_get_merge(C.byref(tree["lsm"]), kb.data_ptr(), ko.data_ptr(), n,
-                                     max_seq.data_ptr() if max_seq is not None else None, C.byref(out),
-                                     C.byref(chain), ws.data_ptr(), wsb, _sp(stream))
-        if st:
-            raise SdbError(st, "sdb_lsm_get_merge")
-
-    if cap_links is None:
-        run(n)  # one link per query is the least a tree of values needs
-        _sync(stream, dev)
-        sm = res["chain_summary"].cpu().numpy()
-        if int(sm[2]) & 0xFFFFFFFF == _abi.SDB_LIMIT_EXCEEDED:
-            run(int(sm[0]))
-    else:
-        run(cap_links)
-    res.update(_ws=ws, _tree=tree, _keys=(kb, ko), _max_seq=max_seq)
-    return res
+    return _lsm_get("sdb_lsm_get_merge", views, runs, keys, max_seq, stream, workspace, merge=True, cap_links=cap_links,
+                    fill=fill)
 
 
 def lsm_scan_merge_device(tree, ranges, max_seq=None, descending=False, stream=None, workspace=None, cand=None,
@@ -1015,37 +1040,8 @@ def lsm_scan_merge_device(tree, ranges, max_seq=None, descending=False, stream=N
     chain_<CHAIN_COLUMNS> per link and chain_summary (CHAIN_SUMMARY order).  cap_links: room for the links; None
     sizes it like the staging (every link is a candidate).  With cand, cap or cap_links None the call retries
     once on SDB_LIMIT_EXCEEDED, after a host synchronisation, as lsm_scan_device does."""
-    import torch
-    dev, rt, n, max_seq, rg, res = _lsm_scan_call(tree, ranges, max_seq)
-
-    def run(ce, ckb, cap_e, cap_k, cap_l):
-        wsb = lib().sdb_lsm_scan_merge_workspace_bytes(tree["total_blocks"], tree["num_ssts"], tree["num_runs"], n, ce,
-                                                       ckb)
-        ws = workspace if workspace is not None and workspace.numel() >= wsb else None
-        if ws is None:
-            assert workspace is None or cand is None, "workspace too small"
-            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        out = _lsm_scan_out(res, cap_e, cap_k, dev)
-        chain = _chain_out(res, cap_e, cap_l, dev, fill)
-        st = lib().sdb_lsm_scan_merge(C.byref(tree["lsm"]), C.byref(rg),
-                                      max_seq.data_ptr() if max_seq is not None else None, int(bool(descending)), ce,
-                                      ckb, C.byref(out), C.byref(chain), ws.data_ptr(), wsb, _sp(stream))
-        if st:
-            raise SdbError(st, "sdb_lsm_scan_merge")
-        res["_ws"] = ws
-
-    if cand is None or cap is None or cap_links is None:
-        ce, ckb = cand if cand is not None else (0, 0)
-        run(ce, ckb, *(cap if cap is not None else (0, 0)), cap_links or 0)
-        _sync(stream, dev)
-        sm, cm = res["summary"].cpu().numpy(), res["chain_summary"].cpu().numpy()
-        if _abi.SDB_LIMIT_EXCEEDED in (int(sm[6]) & 0xFFFFFFFF, int(cm[2]) & 0xFFFFFFFF):
-            ce, ckb = max(ce, int(sm[2])), max(ckb, int(sm[3]))
-            run(ce, ckb, *(cap if cap is not None else (ce, ckb)), cap_links if cap_links is not None else ce)
-    else:
-        run(cand[0], cand[1], cap[0], cap[1], cap_links)
-    res.update(_tree=tree, _ranges=rt, _max_seq=max_seq)
-    return res
+    return _lsm_scan("sdb_lsm_scan_merge", tree, ranges, max_seq, descending, stream, workspace, cand, cap, merge=True,
+                     cap_links=cap_links, fill=fill)
 
 
 def scan_prefixes_columnar(prefixes, probe_len=None):
@@ -1058,10 +1054,6 @@ def scan_prefixes_columnar(prefixes, probe_len=None):
             "probe_len": None if probe_len is None else np.array(list(probe_len) or [0], np.int32)}
 
 
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
-
-
 def lsm_scan_filtered_device(tree, ranges, prefixes=None, probe_len=None, max_seq=None, descending=False, stream=None,
                              workspace=None, cand=None, cap=None, cap_links=None, fill=0, merge=False):
     """sdb_lsm_scan_filtered: lsm_scan_device (merge=False) or lsm_scan_merge_device (merge=True) with the SSTs'
@@ -1070,51 +1062,9 @@ def lsm_scan_filtered_device(tree, ranges, prefixes=None, probe_len=None, max_se
     device tensors named as scan_prefixes_columnar's arrays; probe_len: with a list of prefixes, the per-range
     lengths for SDB_PREFIX_LENGTHS SSTs.  The other arguments, the retry once on SDB_LIMIT_EXCEEDED and the result
     are the unfiltered call's, plus range_filtered (n) and num_filtered (one element)."""
-    import torch
-    dev, rt, n, max_seq, rg, res = _lsm_scan_call(tree, ranges, max_seq)
-    pt = prefixes
-    if prefixes is not None and not isinstance(prefixes, dict):
-        assert len(prefixes) == n, "one prefix (or None) per range"
-        pt = {k: None if a is None else torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(dev)
-              for k, a in scan_prefixes_columnar(prefixes, probe_len).items()}
-    px = None if pt is None else _abi.ScanPrefixes(_ptr(pt["prefix_bytes"]), _ptr(pt["prefix_off"]), _ptr(pt["has_prefix"]),
-                                                   _ptr(pt.get("probe_len")))
-    res["range_filtered"] = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
-    res["num_filtered"] = torch.zeros(1, dtype=torch.int64, device=dev)
-    fout = _abi.ScanFilterOut(res["range_filtered"].data_ptr(), res["num_filtered"].data_ptr())
-    pol = tree.get("_policies")
-
-    def run(ce, ckb, cap_e, cap_k, cap_l):
-        wsb = lib().sdb_lsm_scan_filtered_workspace_bytes(tree["total_blocks"], tree["num_ssts"], tree["num_runs"], n, ce,
-                                                          ckb, int(bool(merge)))
-        ws = workspace if workspace is not None and workspace.numel() >= wsb else None
-        if ws is None:
-            assert workspace is None or cand is None, "workspace too small"
-            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        out = _lsm_scan_out(res, cap_e, cap_k, dev)
-        chain = _chain_out(res, cap_e, cap_l, dev, fill) if merge else None
-        st = lib().sdb_lsm_scan_filtered(C.byref(tree["lsm"]), _ptr(pol), C.byref(rg), C.byref(px) if px is not None else None,
-                                         _ptr(max_seq), int(bool(descending)), ce, ckb, C.byref(out),
-                                         C.byref(chain) if merge else None, C.byref(fout), ws.data_ptr(), wsb, _sp(stream))
-        if st:
-            raise SdbError(st, "sdb_lsm_scan_filtered")
-        res["_ws"] = ws
-
-    if cand is None or cap is None or (merge and cap_links is None):
-        ce, ckb = cand if cand is not None else (0, 0)
-        run(ce, ckb, *(cap if cap is not None else (0, 0)), cap_links or 0)
-        _sync(stream, dev)
-        status = [int(res["summary"].cpu().numpy()[6]) & 0xFFFFFFFF]
-        if merge:
-            status.append(int(res["chain_summary"].cpu().numpy()[2]) & 0xFFFFFFFF)
-        if _abi.SDB_LIMIT_EXCEEDED in status:
-            sm = res["summary"].cpu().numpy()
-            ce, ckb = max(ce, int(sm[2])), max(ckb, int(sm[3]))
-            run(ce, ckb, *(cap if cap is not None else (ce, ckb)), cap_links if cap_links is not None else ce)
-    else:
-        run(cand[0], cand[1], cap[0], cap[1], cap_links or 0)
-    res.update(_tree=tree, _ranges=rt, _max_seq=max_seq, _prefixes=pt)
-    return res
+    return _lsm_scan("sdb_lsm_scan_filtered", tree, ranges, max_seq, descending, stream, workspace, cand, cap,
+                     merge=bool(merge), cap_links=cap_links, fill=fill, filtered=True, prefixes=prefixes,
+                     probe_len=probe_len)
 
 
 def lsm_get_filtered_device(views, runs, keys, probe_len=None, max_seq=None, stream=None, workspace=None, cap_links=None,
@@ -1124,34 +1074,8 @@ def lsm_get_filtered_device(views, runs, keys, probe_len=None, max_seq=None, str
     without whole-key hashes are served.  probe_len: None, a list / array of nkeys lengths for SDB_PREFIX_LENGTHS
     SSTs (-1: None), or a device int32 tensor.  The other arguments, the retry on links that do not fit and the
     result are the unfiltered call's."""
-    import torch
-    tree, dev, kb, ko, n, max_seq, res, out = _get_call(views, runs, keys, max_seq)
-    if probe_len is not None and not hasattr(probe_len, "data_ptr"):
-        probe_len = torch.from_numpy(np.asarray(list(probe_len) or [0], np.int32)).to(dev)
-    wsb = lib().sdb_lsm_get_filtered_workspace_bytes(tree["total_blocks"], tree["num_ssts"], tree["num_runs"], n,
-                                                     int(bool(merge)))
-    ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=dev)
-    assert ws.numel() >= wsb, "workspace too small"
-    pol = tree.get("_policies")
-
-    def run(cap):
-        chain = _chain_out(res, n, cap, dev, fill) if merge else None
-        st = lib().sdb_lsm_get_filtered(C.byref(tree["lsm"]), _ptr(pol), kb.data_ptr(), ko.data_ptr(), n, _ptr(probe_len),
-                                        _ptr(max_seq), C.byref(out), C.byref(chain) if merge else None, ws.data_ptr(),
-                                        wsb, _sp(stream))
-        if st:
-            raise SdbError(st, "sdb_lsm_get_filtered")
-
-    if merge and cap_links is None:
-        run(n)  # one link per query is the least a tree of values needs
-        _sync(stream, dev)
-        sm = res["chain_summary"].cpu().numpy()
-        if int(sm[2]) & 0xFFFFFFFF == _abi.SDB_LIMIT_EXCEEDED:
-            run(int(sm[0]))
-    else:
-        run(cap_links or 0)
-    res.update(_ws=ws, _tree=tree, _keys=(kb, ko), _max_seq=max_seq, _probe_len=probe_len)
-    return res
+    return _lsm_get("sdb_lsm_get_filtered", views, runs, keys, max_seq, stream, workspace, merge=bool(merge),
+                    cap_links=cap_links, fill=fill, filtered=True, probe_len=probe_len)
 
 
 # ------------------------------------------------------------------------------------------------

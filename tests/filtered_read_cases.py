@@ -268,3 +268,21 @@ def merge_tree(seed=8):
     c = G._cut_inside_key(es, len(es) // 2)
     runs.append([build_leaf(es[:c], 2, 128, pol), build_leaf(es[c:], 1, 64, pol)])
     return Tree(runs)
+
+
+def mixed_merge_tree(seed=8):
+    """merge_tree's chains under main_tree's policies, which do not agree, so a merging get probes per SST: the L0
+    SSTs under FIXED(4) with whole keys, DELIM(':') without whole keys and LENGTHS with whole keys; the run's first
+    SST under the plain policy, its second without a filter; the run cut inside a key's versions."""
+    rng = np.random.default_rng(seed)
+    kinds = (1, 1, 1, 0, 2)
+    seq = 10**6
+    shape = [(2, 64, Policy(FIXED, 4, 0)), (1, 128, Policy(DELIM, ord(":"), 1)), (2, 256, Policy(LENGTHS, 0, 0))]
+    runs = []
+    for tenants, (version, bs, pol) in zip(L0_TENANTS, shape):
+        es, seq = _entries(rng, tenants, 30, seq, kinds)
+        runs.append([build_leaf(es, version, bs, pol, 10, LENGTHS_LEN)])
+    es, seq = _entries(rng, range(TENANTS), 25, seq, kinds)
+    c = G._cut_inside_key(es, len(es) // 2)
+    runs.append([build_leaf(es[:c], 2, 128, PLAIN), build_leaf(es[c:], 1, 64, Policy(FIXED, 4, 0), bloom=None)])
+    return Tree(runs)

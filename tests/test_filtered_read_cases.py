@@ -97,6 +97,19 @@ def test_model_get_finds_every_key():
     assert len(miss) * 2 > len(l.sst.keys)
 
 
+def test_mixed_merge_tree_conditions():
+    """What the merging get under policies that do not agree needs of its tree: conditions on the input alone."""
+    from . import merge_read_cases as M
+    t = F.mixed_merge_tree()
+    assert [len(r) for r in t.runs] == [1, 1, 1, 2] and len({tuple(l.policy) for l in t.leaves}) > 1
+    assert [(l.policy.kind, l.policy.no_whole_key) for l in t.leaves[:4]] == [(F.FIXED, 0), (F.DELIM, 1), (F.LENGTHS, 0), (F.NONE, 0)]
+    assert t.leaves[4].bloom is None and all(len(l.bloom) > 0 for l in t.leaves[:4])
+    chains = [{i for i, _, _ in M.get_merge(t, k).links} for k in L.all_keys(t)]
+    assert any({3, 4} <= c for c in chains)  # a chain spans the run's cut
+    assert any(min(c) < 3 <= max(c) for c in chains if c)  # a chain crosses from an L0 SST into the run
+    assert max(len(M.get_merge(t, k).links) for k in L.all_keys(t)) >= 3
+
+
 def test_an_empty_bitmap_rules_out_what_has_a_probe(tree):
     l = F.Leaf(tree.leaves[0].sst, F.Policy(F.FIXED, 4, 0), tree.leaves[0].bloom[:0], 6)
     assert F.ruled_out(l, (b"t00:0001", False)) and F.ruled_out(l, (b"t00:", True))

@@ -433,6 +433,61 @@ def test_get_merge_variant(rt):
     assert bool((h["ssts_read"] <= g["ssts_read"]).all())
 
 
+def test_get_merge_under_policies_that_differ(rt):
+    """The merging get with a probe per SST (the policies do not agree) and a run cut inside a key: links, offsets
+    and columns are those of sdb_lsm_get_merge over the same tree without filters."""
+    import torch
+    m = fixture(rt, "mixed_merge_tree")
+    keys = F.get_keys(m["tree"])
+    h = rt.lsm_get_filtered_device(m["dev"], None, keys, probe_len=[F.LENGTHS_LEN] * len(keys), merge=True)
+    g = rt.lsm_get_merge_device(m["plain"], None, keys)
+    torch.cuda.synchronize()
+    nl = int(g["chain_summary"][0])
+    assert nl > len(keys) // 2 and int(h["chain_summary"][0]) == nl and int(g["chain_summary"][1]) >= 3
+    assert int(h["chain_summary"][2]) == 0 and int(g["chain_summary"][2]) == 0
+    assert bool((h["chain_start"] == g["chain_start"]).all())
+    for f, _ in rt.CHAIN_COLUMNS:
+        assert bool((h["chain_" + f][:nl] == g["chain_" + f][:nl]).all()), f
+    for f, _ in rt.GET_FIELDS:
+        if f not in ("ssts_read", "ssts_filtered"):
+            assert bool((h[f] == g[f]).all()), f
+    assert int(h["ssts_filtered"].sum()) > 0 and int(g["ssts_filtered"].sum()) == 0
+    assert bool((h["ssts_read"] <= g["ssts_read"]).all())
+
+
+def test_get_filtered_with_a_chain_degenerate(rt):
+    """No keys, and keys over a tree without SSTs: the chain summary, chain_start[0..nkeys] and the get summary are
+    zeroed whatever they held, every query is NOT_FOUND with no SST, no link is written."""
+    import torch
+    m = fixture(rt, "mixed_merge_tree")
+    for dev, keys in ((m["dev"], []), (rt.lsm_tree_device([], []), [b"a", b"", b"t03:0001"])):
+        n = len(keys)
+        kb, ko = (TG._dev(a) for a in rt.keys_columnar(keys))
+        res = {f: torch.full((max(n, 1),), 0x5A, dtype=getattr(torch, dt), device="cuda") for f, dt in rt.GET_FIELDS}
+        res["summary"] = torch.full((len(rt.GET_SUMMARY),), 0x5A5A, dtype=torch.int64, device="cuda")
+        out = _abi.GetOut(*[res[f].data_ptr() for f, _ in rt.GET_FIELDS], res["summary"].data_ptr())
+        chain = rt._chain_out(res, n, 4, "cuda", 0x5A)
+        res["chain_start"].fill_(77)
+        res["chain_summary"].fill_(77)
+        wsb = rt.lib().sdb_lsm_get_filtered_workspace_bytes(dev["total_blocks"], dev["num_ssts"], dev["num_runs"], n, 1)
+        ws = torch.empty(wsb, dtype=torch.uint8, device="cuda")
+        pol = dev["_policies"]
+        st = rt.lib().sdb_lsm_get_filtered(C.byref(dev["lsm"]), pol.data_ptr() if pol is not None else None, kb.data_ptr(),
+                                           ko.data_ptr(), n, None, None, C.byref(out), C.byref(chain), ws.data_ptr(), wsb, None)
+        assert st == 0
+        torch.cuda.synchronize()
+        h = {k: v.cpu().numpy() for k, v in res.items()}
+        assert not h["chain_summary"].any() and not h["chain_start"][:n + 1].any() and not h["summary"].any()
+        assert (h["chain_seq"].view(np.uint8) == 0x5A).all()
+        if n:
+            assert (h["state"] == _abi.GET_NOT_FOUND).all() and not h["status"].any()
+            assert ((h["sst"].astype(np.int64) & 0xFFFFFFFF) == _abi.NO_SST).all()
+            for f in ("block", "val_off", "val_len", "seq", "flags", "create_ts", "expire_ts", "ssts_read", "ssts_filtered"):
+                assert not h[f].any(), f
+        else:
+            assert (h["state"] == 0x5A).all()
+
+
 def test_get_canaries_and_workspace_reuse(rt):
     import torch
     m = fixture(rt, "main_tree")
