@@ -530,8 +530,8 @@ sdb_status sdb_sst_scan(const sdb_sst_view *sst, const sdb_scan_ranges *ranges, 
  *      whose start key is <= key if its range holds the key, and the SSTs immediately before it while
  *      their range still reaches the key (one key's versions straddling the cut between two output
  *      SSTs).  For a well-formed sorted run the two agree (point_table_idx_covering_key); for a run of
- *      one it equals searching that SST.  Projected views (visible_range) are out of scope: a view is a
- *      whole SST;
+ *      one it equals searching that SST.  Here a view is a whole SST; projected views (visible_range) are
+ *      read by sdb_lsm_get_projected;
  *   2. per SST of the chain: the bloom filter (bloom != NULL) may rule the SST out (sst_iter.rs:201-227);
  *      an empty bitmap rules every key out, as in sdb_sst_lookup.  Otherwise the block range is
  *      partitions_covering_range([key, key]) over the SST's index keys.  EVERY block of that range is
@@ -627,7 +627,8 @@ sdb_status sdb_lsm_get(const sdb_lsm_view *lsm, const uint8_t *key_bytes, const 
  *      sorted run, tables_covering_range (segment_iterator.rs:355-414, db_state.rs:600-660); any SST it opens
  *      beyond this rule holds no key of the range, so the entries agree.  No bloom filter is consulted: a
  *      range has none without a prefix extractor (sdb_lsm_scan_filtered is the call that consults them).  A range
- *      that is empty as a set reads nothing.
+ *      that is empty as a set reads nothing.  Here a view is a whole SST; sdb_lsm_scan_projected reads projected
+ *      views (visible_range).
  *      range_ssts[r] is the number of SSTs that take part;
  *   2. blocks: per participating SST, partitions_covering_range(index keys, start, end) exactly as
  *      sdb_sst_scan rule 1 (partitioned_keyspace.rs:87-110).  EVERY such block is bounds- and CRC-checked
@@ -880,6 +881,76 @@ sdb_status sdb_lsm_get_filtered(const sdb_lsm_view *lsm, const sdb_filter_policy
                                 const uint64_t *max_seq /* device, nkeys; NULL = no bound */, const sdb_get_out *out,
                                 const sdb_chain_out *chain /* or NULL */, void *workspace, uint64_t workspace_bytes,
                                 void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Tree reads over projected SST views (device).  In the reference an SST of the manifest is an SsTableView: the
+ * physical handle plus an optional visible_range (db_state.rs:61-78).  Range-restricted clones and projected or
+ * segmented databases produce such views (manifest/mod.rs:1039-1158), and every read path honours them
+ * (effective_range and calculate_view_range, db_state.rs:116-141, 243-251; compacted_effective_start_key in the
+ * sorted-run searches, :540-665; SstIterator::new_owned / for_key, sst_iter.rs:324-365).  sdb_lsm_get_projected and
+ * sdb_lsm_scan_projected are sdb_lsm_get_filtered and sdb_lsm_scan_filtered (themselves the supersets of the plain
+ * and _merge calls) with a visible range per SST.  `proj` is an sdb_scan_ranges with n == lsm->num_ssts: element i
+ * is SsTableView.visible_range of ssts[i], (SDB_BOUND_UNBOUNDED, SDB_BOUND_UNBOUNDED) meaning None, the whole SST.
+ * sdb_lsm_view and sdb_sst_view are unchanged.
+ *   P1. effective range: E[i] = [first_key[i], last_key[i]] intersected with visible[i] as BytesRange::intersect
+ *       does (comparable_range.rs:224-236): the tighter start, where Unbounded < Included(a) < Excluded(a), and the
+ *       tighter end, where Excluded(a) < Included(a) < Unbounded.  It is empty exactly when non_empty (:265-274)
+ *       says so: the start key above the end key, or equal to it with a side excluded.  An SST whose E[i] is empty
+ *       takes part in nothing (try_with_visible_range, db_state.rs:169-176; the reference never builds such a view);
+ *   P2. get, rule 1 under projection: SST i is in key k's chain iff E[i] holds k.  In a sorted run the covering
+ *       SSTs are found as point_table_idx_covering_key finds them (db_state.rs:578-596): a partition point over the
+ *       effective start keys max(first_key[i], visible start) (compacted_effective_start_key, :198-204), the last
+ *       such SST if its E holds k, and the SSTs right before it while their E still holds k.  An L0 SST is a run of
+ *       one (SstIterator::for_key -> calculate_view_range([k, k]) -> None).  An SST that is not in the chain is not
+ *       probed, marked, checked or counted: it appears in neither ssts_read nor ssts_filtered and none of its errors
+ *       surfaces; a tombstone or a newer version that the view hides shadows nothing.  Everything else of
+ *       sdb_lsm_get rules 2-7, 3'/4' and F5 is unchanged;
+ *   P3. scan, rules 1-3 under projection: for the pair (range r, SST i) the view range is V = range r intersected
+ *       with visible[i] (calculate_view_range).  If V is empty the SST takes no part in r and is counted in neither
+ *       range_ssts nor range_filtered.  Otherwise rules 1-3 hold with V in place of the range: participation is
+ *       judged against [first_key, last_key], the blocks are partitions_covering_range(index, V.start, V.end), the
+ *       candidates are the entries whose key V contains.  blocks_checked stays the exact size of the union of those
+ *       blocks over the participating pairs; a corrupt block of an SST that no V covers never surfaces.  The
+ *       capacity protocol, the ordering, sdb_lsm_scan_merge's rule 4 and the laziness rules are unchanged;
+ *   P4. the filter query of a projected pair: the reference judges point_key on the view range (sst_iter.rs:82-87,
+ *       849-856).  If V is Included(k)..=Included(k) the pair asks Point(k), also when the range is wide and has a
+ *       prefix; otherwise Prefix(p) where has_prefix[r], else nothing, as F1.  For an SST whose projection is
+ *       (UNBOUNDED, UNBOUNDED) V is the range, so F1 holds as it stands.  probe_len[r] belongs to the range's own
+ *       query: a pair that is a point only through its projection has no caller-supplied length, so an
+ *       SDB_PREFIX_LENGTHS SST answers None there ("might match").  The once-per-range hash of the agreeing-policies
+ *       path serves the pairs whose query is the range's; a point-by-projection pair hashes for itself;
+ *   P5. a malformed projection is found on the device, like a malformed run_start: a start kind other than
+ *       SDB_BOUND_UNBOUNDED or SDB_BOUND_INCLUDED (new_projected's assert, db_state.rs:126-130), an end kind above
+ *       SDB_BOUND_EXCLUDED, or offsets that descend fail EVERY query or range with SDB_INVALID_ARGUMENT, with
+ *       blocks_checked 0, and nothing is read through the arrays.  On the host, proj->n != num_ssts, or a NULL array
+ *       inside a non-NULL proj when num_ssts > 0, is SDB_INVALID_ARGUMENT from the call; SDB_DEVICE_ERROR comes
+ *       after the host checks;
+ *   P6. proj == NULL gives exactly the _filtered call: every column, counter and summary word; so do projections
+ *       that are all (UNBOUNDED, UNBOUNDED);
+ *   P7. the caller's obligation, as the manifest's projection guarantees it: within a sorted run the effective
+ *       start keys ascend and neighbouring E share at most a boundary key.  The device does not verify this; a
+ *       violation can lose rows but never reads out of bounds.
+ * The workspace is that of the _filtered call: a pair's view range is recomputed where it is read.
+ * ------------------------------------------------------------------------------------------- */
+uint64_t sdb_lsm_get_projected_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs,
+                                               uint64_t nkeys, int32_t merge /* 1: a chain is passed */);
+sdb_status sdb_lsm_get_projected(const sdb_lsm_view *lsm, const sdb_scan_ranges *proj /* n == num_ssts; or NULL */,
+                                 const sdb_filter_policy *policies /* device, num_ssts; or NULL */,
+                                 const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
+                                 const int32_t *probe_len /* device, nkeys; or NULL */,
+                                 const uint64_t *max_seq /* device, nkeys; NULL = no bound */, const sdb_get_out *out,
+                                 const sdb_chain_out *chain /* or NULL */, void *workspace, uint64_t workspace_bytes,
+                                 void *stream);
+uint64_t sdb_lsm_scan_projected_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs,
+                                                uint64_t nranges, uint64_t cand_entries, uint64_t cand_key_bytes,
+                                                int32_t merge /* 1: a chain is passed */);
+sdb_status sdb_lsm_scan_projected(const sdb_lsm_view *lsm, const sdb_scan_ranges *proj /* n == num_ssts; or NULL */,
+                                  const sdb_filter_policy *policies /* device, num_ssts; or NULL */,
+                                  const sdb_scan_ranges *ranges, const sdb_scan_prefixes *prefixes /* or NULL */,
+                                  const uint64_t *max_seq /* device, n; NULL = no bound */, int32_t descending,
+                                  uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out *out,
+                                  const sdb_chain_out *chain /* or NULL */, const sdb_scan_filter_out *fout,
+                                  void *workspace, uint64_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Compaction (device): the output side of CompactionExecutor::run_subcompaction_merge

@@ -380,6 +380,16 @@ SIGNATURES = {
     "sdb_lsm_get_filtered": (C.c_int, [C.POINTER(LsmView), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                        C.c_void_p, C.POINTER(GetOut), C.POINTER(ChainOut), C.c_void_p, C.c_uint64,
                                        C.c_void_p]),
+    "sdb_lsm_scan_projected_workspace_bytes": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
+                                                            C.c_uint64, C.c_int32]),
+    "sdb_lsm_scan_projected": (C.c_int, [C.POINTER(LsmView), C.POINTER(ScanRanges), C.c_void_p, C.POINTER(ScanRanges),
+                                         C.POINTER(ScanPrefixes), C.c_void_p, C.c_int32, C.c_uint64, C.c_uint64,
+                                         C.POINTER(LsmScanOut), C.POINTER(ChainOut), C.POINTER(ScanFilterOut), C.c_void_p,
+                                         C.c_uint64, C.c_void_p]),
+    "sdb_lsm_get_projected_workspace_bytes": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int32]),
+    "sdb_lsm_get_projected": (C.c_int, [C.POINTER(LsmView), C.POINTER(ScanRanges), C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(GetOut), C.POINTER(ChainOut),
+                                        C.c_void_p, C.c_uint64, C.c_void_p]),
     "sdb_merge_runs_workspace_bytes":(C.c_uint64, [C.POINTER(Run), C.c_uint32]),
     "sdb_merge_runs": (C.c_int, [C.POINTER(Run), C.c_uint32, C.POINTER(Retention), C.POINTER(MergedOut),
                                  C.c_void_p, C.c_uint64, C.c_void_p]),

@@ -624,17 +624,25 @@ static bool chain_ok(const sdb_chain_out *c) {
                              c->expire_ts);
 }
 
-// sdb_lsm_get (merge == false), sdb_lsm_get_merge and sdb_lsm_get_filtered (either, with policies and probe_len): one
-// set of argument checks, in one order.
-static sdb_status lsm_get_call(const sdb_lsm_view *lsm, const sdb_filter_policy *policies, const uint8_t *key_bytes,
-                               const uint64_t *key_off, uint64_t nkeys, const int32_t *probe_len, const uint64_t *max_seq,
-                               const sdb_get_out *out, bool merge, const sdb_chain_out *chain, void *workspace,
-                               uint64_t workspace_bytes, void *stream) {
+// The projections of a projected tree read (P5): one per SST, every array there when there is an SST.
+static sdb_status check_projections(const sdb_lsm_view *lsm, const sdb_scan_ranges *proj) {
+    if (!proj) return SDB_OK;
+    if (proj->n != lsm->num_ssts) return SDB_INVALID_ARGUMENT;
+    return check_ranges(proj);
+}
+
+// sdb_lsm_get (merge == false), sdb_lsm_get_merge, sdb_lsm_get_filtered (either, with policies and probe_len) and
+// sdb_lsm_get_projected (that, with proj): one set of argument checks, in one order.
+static sdb_status lsm_get_call(const sdb_lsm_view *lsm, const sdb_scan_ranges *proj, const sdb_filter_policy *policies,
+                               const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys, const int32_t *probe_len,
+                               const uint64_t *max_seq, const sdb_get_out *out, bool merge, const sdb_chain_out *chain,
+                               void *workspace, uint64_t workspace_bytes, void *stream) {
     if (!lsm || !out || (merge && !chain)) return SDB_INVALID_ARGUMENT;
     // (the limits all give one status, so this one may come before the tree's)
     if (lsm->num_runs && nkeys > (1ull << 40) / lsm->num_runs) return SDB_LIMIT_EXCEEDED;  // a byte per (query, run)
     sdb_status st = check_tree(lsm);
     if (st) return st;
+    if (check_projections(lsm, proj)) return SDB_INVALID_ARGUMENT;
     if (!out->summary || (merge && !chain_ok(chain))) return SDB_INVALID_ARGUMENT;
     if (nkeys && (!key_bytes || !key_off || !out->state || !out->status || !out->sst || !out->block || !out->val_off ||
                   !out->val_len || !out->seq || !out->flags || !out->create_ts || !out->expire_ts || !out->ssts_read ||
@@ -644,7 +652,7 @@ static sdb_status lsm_get_call(const sdb_lsm_view *lsm, const sdb_filter_policy 
         return SDB_INVALID_ARGUMENT;
     if (!device_ok()) return SDB_DEVICE_ERROR;
     uint8_t *w = ws_align(workspace);
-    if (launch_get(*lsm, policies, key_bytes, key_off, nkeys, probe_len, max_seq, *out, merge ? chain : nullptr, w,
+    if (launch_get(*lsm, policies, key_bytes, key_off, nkeys, probe_len, max_seq, *out, merge ? chain : nullptr, proj, w,
                    S(stream)) != hipSuccess)
         return SDB_DEVICE_ERROR;
     return SDB_OK;
@@ -653,7 +661,7 @@ static sdb_status lsm_get_call(const sdb_lsm_view *lsm, const sdb_filter_policy 
 sdb_status sdb_lsm_get(const sdb_lsm_view *lsm, const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
                        const uint64_t *max_seq, const sdb_get_out *out, void *workspace, uint64_t workspace_bytes,
                        void *stream) {
-    return lsm_get_call(lsm, nullptr, key_bytes, key_off, nkeys, nullptr, max_seq, out, false, nullptr, workspace,
+    return lsm_get_call(lsm, nullptr, nullptr, key_bytes, key_off, nkeys, nullptr, max_seq, out, false, nullptr, workspace,
                         workspace_bytes, stream);
 }
 
@@ -664,7 +672,7 @@ uint64_t sdb_lsm_get_merge_workspace_bytes(uint64_t total_blocks, uint32_t num_s
 sdb_status sdb_lsm_get_merge(const sdb_lsm_view *lsm, const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
                              const uint64_t *max_seq, const sdb_get_out *out, const sdb_chain_out *chain, void *workspace,
                              uint64_t workspace_bytes, void *stream) {
-    return lsm_get_call(lsm, nullptr, key_bytes, key_off, nkeys, nullptr, max_seq, out, true, chain, workspace,
+    return lsm_get_call(lsm, nullptr, nullptr, key_bytes, key_off, nkeys, nullptr, max_seq, out, true, chain, workspace,
                         workspace_bytes, stream);
 }
 
@@ -677,7 +685,20 @@ sdb_status sdb_lsm_get_filtered(const sdb_lsm_view *lsm, const sdb_filter_policy
                                 const uint64_t *key_off, uint64_t nkeys, const int32_t *probe_len, const uint64_t *max_seq,
                                 const sdb_get_out *out, const sdb_chain_out *chain, void *workspace, uint64_t workspace_bytes,
                                 void *stream) {
-    return lsm_get_call(lsm, policies, key_bytes, key_off, nkeys, probe_len, max_seq, out, chain != nullptr, chain,
+    return lsm_get_call(lsm, nullptr, policies, key_bytes, key_off, nkeys, probe_len, max_seq, out, chain != nullptr, chain,
+                        workspace, workspace_bytes, stream);
+}
+
+uint64_t sdb_lsm_get_projected_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys,
+                                               int32_t merge) {
+    return get_workspace_bytes(total_blocks, num_ssts, num_runs, nkeys, merge != 0) + 256;  // a projection needs no state
+}
+
+sdb_status sdb_lsm_get_projected(const sdb_lsm_view *lsm, const sdb_scan_ranges *proj, const sdb_filter_policy *policies,
+                                 const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys, const int32_t *probe_len,
+                                 const uint64_t *max_seq, const sdb_get_out *out, const sdb_chain_out *chain, void *workspace,
+                                 uint64_t workspace_bytes, void *stream) {
+    return lsm_get_call(lsm, proj, policies, key_bytes, key_off, nkeys, probe_len, max_seq, out, chain != nullptr, chain,
                         workspace, workspace_bytes, stream);
 }
 
@@ -700,9 +721,10 @@ uint64_t sdb_lsm_scan_filtered_workspace_bytes(uint64_t total_blocks, uint32_t n
     return lsm_scan_workspace_bytes(total_blocks, num_ssts, nranges, cand_entries, cand_key_bytes, merge != 0, true) + 256;
 }
 
-// sdb_lsm_scan (chain == NULL, merge == false), sdb_lsm_scan_merge and sdb_lsm_scan_filtered (filter: either, with
-// policies, prefixes and fout): one set of argument checks, in one order.
-static sdb_status lsm_scan_call(const sdb_lsm_view *lsm, const sdb_scan_ranges *ranges, const uint64_t *max_seq,
+// sdb_lsm_scan (chain == NULL, merge == false), sdb_lsm_scan_merge, sdb_lsm_scan_filtered (filter: either, with
+// policies, prefixes and fout) and sdb_lsm_scan_projected (that, with proj): one set of argument checks, in one order.
+static sdb_status lsm_scan_call(const sdb_lsm_view *lsm, const sdb_scan_ranges *proj, const sdb_scan_ranges *ranges,
+                                const uint64_t *max_seq,
                                 int32_t descending, uint64_t cand_entries, uint64_t cand_key_bytes,
                                 const sdb_lsm_scan_out *out, bool merge, const sdb_chain_out *chain, bool filter,
                                 const sdb_filter_policy *policies, const sdb_scan_prefixes *prefixes,
@@ -714,6 +736,7 @@ static sdb_status lsm_scan_call(const sdb_lsm_view *lsm, const sdb_scan_ranges *
     if (cand_entries > (1ull << 40) || cand_key_bytes > (1ull << 44)) return SDB_LIMIT_EXCEEDED;
     sdb_status st = check_tree(lsm);
     if (st) return st;
+    if (check_projections(lsm, proj)) return SDB_INVALID_ARGUMENT;
     if (!out->summary || !out->range_entry_start || !out->key_off || check_ranges(ranges)) return SDB_INVALID_ARGUMENT;
     if (n && (!out->range_status || !out->range_ssts)) return SDB_INVALID_ARGUMENT;
     if (out->key_arena_cap && !out->key_arena) return SDB_INVALID_ARGUMENT;
@@ -730,7 +753,8 @@ static sdb_status lsm_scan_call(const sdb_lsm_view *lsm, const sdb_scan_ranges *
     if (!device_ok()) return SDB_DEVICE_ERROR;
     uint8_t *w = ws_align(workspace);
     if (launch_lsm_scan(*lsm, *ranges, max_seq, descending ? 1u : 0u, cand_entries, cand_key_bytes, *out,
-                        merge ? chain : nullptr, policies, prefixes, filter ? fout : nullptr, w, S(stream)) != hipSuccess)
+                        merge ? chain : nullptr, policies, prefixes, filter ? fout : nullptr, filter ? proj : nullptr, w,
+                        S(stream)) != hipSuccess)
         return SDB_DEVICE_ERROR;
     return SDB_OK;
 }
@@ -738,7 +762,7 @@ static sdb_status lsm_scan_call(const sdb_lsm_view *lsm, const sdb_scan_ranges *
 sdb_status sdb_lsm_scan(const sdb_lsm_view *lsm, const sdb_scan_ranges *ranges, const uint64_t *max_seq,
                         int32_t descending, uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out *out,
                         void *workspace, uint64_t workspace_bytes, void *stream) {
-    return lsm_scan_call(lsm, ranges, max_seq, descending, cand_entries, cand_key_bytes, out, false, nullptr, false,
+    return lsm_scan_call(lsm, nullptr, ranges, max_seq, descending, cand_entries, cand_key_bytes, out, false, nullptr, false,
                          nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
 }
 
@@ -746,8 +770,8 @@ sdb_status sdb_lsm_scan_merge(const sdb_lsm_view *lsm, const sdb_scan_ranges *ra
                               int32_t descending, uint64_t cand_entries, uint64_t cand_key_bytes,
                               const sdb_lsm_scan_out *out, const sdb_chain_out *chain, void *workspace,
                               uint64_t workspace_bytes, void *stream) {
-    return lsm_scan_call(lsm, ranges, max_seq, descending, cand_entries, cand_key_bytes, out, true, chain, false, nullptr,
-                         nullptr, nullptr, workspace, workspace_bytes, stream);
+    return lsm_scan_call(lsm, nullptr, ranges, max_seq, descending, cand_entries, cand_key_bytes, out, true, chain, false,
+                         nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
 }
 
 sdb_status sdb_lsm_scan_filtered(const sdb_lsm_view *lsm, const sdb_filter_policy *policies, const sdb_scan_ranges *ranges,
@@ -755,8 +779,24 @@ sdb_status sdb_lsm_scan_filtered(const sdb_lsm_view *lsm, const sdb_filter_polic
                                  uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out *out,
                                  const sdb_chain_out *chain, const sdb_scan_filter_out *fout, void *workspace,
                                  uint64_t workspace_bytes, void *stream) {
-    return lsm_scan_call(lsm, ranges, max_seq, descending, cand_entries, cand_key_bytes, out, chain != nullptr, chain, true,
-                         policies, prefixes, fout, workspace, workspace_bytes, stream);
+    return lsm_scan_call(lsm, nullptr, ranges, max_seq, descending, cand_entries, cand_key_bytes, out, chain != nullptr, chain,
+                         true, policies, prefixes, fout, workspace, workspace_bytes, stream);
+}
+
+uint64_t sdb_lsm_scan_projected_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs,
+                                                uint64_t nranges, uint64_t cand_entries, uint64_t cand_key_bytes,
+                                                int32_t merge) {
+    (void)num_runs;  // a pair's view range is recomputed where it is read: no state beyond the filtered scan's
+    return lsm_scan_workspace_bytes(total_blocks, num_ssts, nranges, cand_entries, cand_key_bytes, merge != 0, true) + 256;
+}
+
+sdb_status sdb_lsm_scan_projected(const sdb_lsm_view *lsm, const sdb_scan_ranges *proj, const sdb_filter_policy *policies,
+                                  const sdb_scan_ranges *ranges, const sdb_scan_prefixes *prefixes, const uint64_t *max_seq,
+                                  int32_t descending, uint64_t cand_entries, uint64_t cand_key_bytes,
+                                  const sdb_lsm_scan_out *out, const sdb_chain_out *chain, const sdb_scan_filter_out *fout,
+                                  void *workspace, uint64_t workspace_bytes, void *stream) {
+    return lsm_scan_call(lsm, proj, ranges, max_seq, descending, cand_entries, cand_key_bytes, out, chain != nullptr, chain,
+                         true, policies, prefixes, fout, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -47,10 +47,14 @@
 // Filter::might_match for Point(key) under the SST's policy (sdb_filter.h) where sdb_lsm_get, the plain policy, probes the
 // full key.  What a key probes depends on the policy alone: k_get_validate finds whether the policies agree, and then
 // a pair's thread hashes once for all its SSTs, as before; else once per SST that has a filter.
+// sdb_lsm_get_projected passes a visible range per SST (SsTableView.visible_range, db_state.rs:61-78): an SST is in a
+// key's chain iff its effective range, [first_key, last_key] intersected with the visible range, holds the key, and a
+// run is searched by its effective start keys (get_run<V>).  Inside an SST of the chain every version of the key is
+// visible, so only the chain changes; k_get_validate also checks the projections.
 #include <algorithm>
 
 #include "sdb_decode.h"
-#include "sdb_read.h"
+#include "sdb_range.h"
 
 namespace sdb {
 
@@ -105,12 +109,23 @@ struct GetArgs {
     uint64_t *qn, *qscan;      // per query: its links; the second output of their scan (the first is chain_start)
     uint64_t *tx, *ty;         // scan tiles
     unsigned long long *macc;  // kMacc* words
+    // sdb_lsm_get_projected only
+    sdb_scan_ranges proj;      // per SST: SsTableView.visible_range, (UNBOUNDED, UNBOUNDED) = None
 };
 enum { kAccFound = 0, kAccDeleted, kAccNotFound, kAccMerge, kAccFailed, kAccBlocks, kAccFirstBad, kAccWords };
 
+// V: the call has projections (sdb_lsm_get_projected).  As P below: the kernels that read them exist once without the
+// step, so the calls without projections launch what they always launched.
+template <bool V>
 __global__ __launch_bounds__(256) void k_get_validate(GetArgs a) {
-    const int bad = lsm_validate(a.t, a.sstat);
+    int bad = lsm_validate(a.t, a.sstat);
     const int uni = policies_validate(a.pol, a.t.num_ssts, a.sstat);
+    if (V) {  // P5: a malformed projection makes the call malformed
+        int pb = 0;
+        for (uint32_t i = threadIdx.x; i < a.t.num_ssts; i += blockDim.x)
+            if (bad_projection(a.proj, i)) pb = 1;
+        bad |= __syncthreads_or(pb);
+    }
     if (threadIdx.x == 0) {
         *a.bad = bad ? 1u : 0u;
         *a.uni = uni ? 1u : 0u;
@@ -133,23 +148,39 @@ SDB_DEV int cmp_last(const GetArgs &a, uint32_t i, const Key &k) {
     return cmp_bytes(a.t.last_key_bytes + o, (uint32_t)(a.t.last_key_off[i + 1] - o), k.t, k.nt, 0).c;
 }
 
+// Under projection (P1-P2 of sdb_lsm_get_projected): the effective start key of SST i, max(first_key, visible start)
+// (compacted_effective_start_key, db_state.rs:198-204), is <= k; and the effective range E[i] = [first_key, last_key]
+// intersected with the visible range (effective_range, :116-141) holds k.
+SDB_DEV bool eff_start_le(const GetArgs &a, uint32_t i, const Key &k) {
+    if (cmp_first(a, i, k) > 0) return false;
+    const Bound s = range_start(a.proj, i);
+    return !s.kind || cmp_bytes(k.t, k.nt, s.t, s.n, 0).c >= 0;
+}
+SDB_DEV bool eff_holds(const GetArgs &a, uint32_t i, const Key &k) {
+    if (cmp_first(a, i, k) > 0 || cmp_last(a, i, k) < 0) return false;
+    const Bound s = range_start(a.proj, i), e = range_end(a.proj, i);
+    if (s.kind && precedes(s, cmp_bytes(k.t, k.nt, s.t, s.n, 0).c)) return false;
+    return !(e.kind && exceeds(e, cmp_bytes(k.t, k.nt, e.t, e.n, 0).c));
+}
+
 // The covering SSTs [first, last] of run r for key k, in run order: the last SST whose first key is <= k if
 // its range holds k, and the SSTs right before it while their range still reaches k
 // (point_table_idx_covering_key, db_state.rs:578-596).  false: none.  The chain of k is these, over the runs
-// in order.
+// in order.  V: over the effective start keys and the effective ranges.
+template <bool V>
 SDB_DEV bool get_run(const GetArgs &a, uint32_t r, const Key &k, uint32_t &first, uint32_t &last) {
     const uint32_t rs = a.t.run_start[r], re = a.t.run_start[r + 1];
     uint32_t lo = rs, hi = re;  // partition_point(first_key <= k)
     while (lo < hi) {
         const uint32_t mid = lo + (hi - lo) / 2;
-        if (cmp_first(a, mid, k) <= 0) lo = mid + 1;
+        if (V ? eff_start_le(a, mid, k) : cmp_first(a, mid, k) <= 0) lo = mid + 1;
         else hi = mid;
     }
     if (lo == rs) return false;
     last = lo - 1;
-    if (cmp_last(a, last, k) < 0) return false;
+    if (V ? !eff_holds(a, last, k) : cmp_last(a, last, k) < 0) return false;
     first = last;
-    while (first > rs && cmp_last(a, first - 1, k) >= 0) first--;
+    while (first > rs && (V ? eff_holds(a, first - 1, k) : cmp_last(a, first - 1, k) >= 0)) first--;
     return true;
 }
 
@@ -191,7 +222,7 @@ SDB_DEV Step get_step(const GetArgs &a, const sdb_sst_view &v, uint32_t i, uint6
     return s;
 }
 
-template <bool P>
+template <bool P, bool V>
 __global__ __launch_bounds__(256) void k_get_locate(GetArgs a) {
     if (*a.bad) return;
     const uint32_t R = a.t.num_runs;
@@ -202,7 +233,7 @@ __global__ __launch_bounds__(256) void k_get_locate(GetArgs a) {
         const Key k = key_of(a, q);
         uint32_t first, last;
         uint8_t rs = kRunNone;
-        if (get_run(a, r, k, first, last)) {
+        if (get_run<V>(a, r, k, first, last)) {
             PairProbe<P> pp(a, k);  // filter_hash (filter.rs:196-204): one hash for every SST's filter
             rs = last > first ? kRunOpen : kRunFiltered;  // several covering SSTs: the resolve counts them itself
             for (uint32_t i = first; i <= last; i++) {
@@ -277,7 +308,7 @@ SDB_DEV int get_versions(const sdb_sst_view &v, const Step &s, const Key &k, uin
 // The walk of pair t: the visible versions of query t % nkeys in the covering SSTs of run t / nkeys, in chain order,
 // every block of an SST's range checked before its rows are used: visit(sst, block, its Blk, position, row) ->
 // false: stop.  -> the status that ends the walk; nread / nfilt: the SSTs consulted / filtered up to there.
-template <bool P, typename F>
+template <bool P, bool V, typename F>
 SDB_DEV int walk_pair(const GetArgs &a, uint64_t t, uint8_t rs, uint32_t &nread, uint32_t &nfilt, F &&visit) {
     const uint64_t q = t % a.nkeys;
     const Key k = key_of(a, q);
@@ -301,7 +332,7 @@ SDB_DEV int walk_pair(const GetArgs &a, uint64_t t, uint8_t rs, uint32_t &nread,
         search(in.sst, v, Step{false, 0, in.block, in.at});
     } else {
         uint32_t first = 0, last = 0;
-        bool go = get_run(a, (uint32_t)(t / a.nkeys), k, first, last);
+        bool go = get_run<V>(a, (uint32_t)(t / a.nkeys), k, first, last);
         PairProbe<P> pp(a, k);
         for (uint32_t i = first; go && i <= last; i++) {
             const sdb_sst_view v = a.t.ssts[i];
@@ -314,7 +345,7 @@ SDB_DEV int walk_pair(const GetArgs &a, uint64_t t, uint8_t rs, uint32_t &nread,
     return st;
 }
 
-template <bool P>
+template <bool P, bool V>
 __global__ __launch_bounds__(64) void k_get_walk(GetArgs a) {
     if (*a.bad) return;
     const uint64_t total = a.nkeys * a.t.num_runs;
@@ -324,7 +355,7 @@ __global__ __launch_bounds__(64) void k_get_walk(GetArgs a) {
         uint32_t sst = 0xFFFFFFFFu, nread = 0, nfilt = 0;
         Hit H;
         H.ok = false;
-        const int st = walk_pair<P>(a, t, rs, nread, nfilt, [&](uint32_t i, uint32_t blk, const Blk &, uint32_t at, const Row &) {
+        const int st = walk_pair<P, V>(a, t, rs, nread, nfilt, [&](uint32_t i, uint32_t blk, const Blk &, uint32_t at, const Row &) {
             H.ok = true;  // the first visible version decides
             H.block = blk;
             H.at = at;
@@ -481,7 +512,7 @@ __global__ void k_get_final(GetArgs a) {
 // Its own kernels: the count walk before the resolve (k_get_resolve<true> above), the final and the emit after it.
 // =================================================================================================
 
-template <bool P>
+template <bool P, bool V>
 __global__ __launch_bounds__(64) void k_gm_walk(GetArgs a) {
     if (blockIdx.x == 0 && threadIdx.x == 0) a.macc[kMaccMaxChain] = a.macc[kMaccGo] = 0;
     if (*a.bad) return;
@@ -491,7 +522,7 @@ __global__ __launch_bounds__(64) void k_gm_walk(GetArgs a) {
         if (rs != kRunOpen && rs != kRunOpen1) continue;
         MergeRec m{};
         uint32_t nread = 0, nfilt = 0;
-        const int st = walk_pair<P>(a, t, rs, nread, nfilt, [&](uint32_t i, uint32_t blk, const Blk &, uint32_t at, const Row &r) {
+        const int st = walk_pair<P, V>(a, t, rs, nread, nfilt, [&](uint32_t i, uint32_t blk, const Blk &, uint32_t at, const Row &r) {
             if (!m.hit) {
                 m.hit = 1;
                 m.sst = i;
@@ -538,7 +569,7 @@ __global__ void k_gm_final(GetArgs a) {
     a.macc[kMaccGo] = fits;
 }
 
-template <bool P>
+template <bool P, bool V>
 __global__ __launch_bounds__(64) void k_gm_emit(GetArgs a) {
     if (*a.bad || !a.macc[kMaccGo]) return;
     const uint64_t total = a.nkeys * a.t.num_runs;
@@ -550,7 +581,7 @@ __global__ __launch_bounds__(64) void k_gm_emit(GetArgs a) {
         if (!a.mrec[t].use || !n || a.out.status[q]) continue;
         const uint64_t at0 = a.chain.chain_start[q] + a.mrec[t].off;
         uint32_t x = 0, nread = 0, nfilt = 0;
-        walk_pair<P>(a, t, rs, nread, nfilt, [&](uint32_t i, uint32_t blk, const Blk &b, uint32_t, const Row &r) {
+        walk_pair<P, V>(a, t, rs, nread, nfilt, [&](uint32_t i, uint32_t blk, const Blk &b, uint32_t, const Row &r) {
             if (r.flags & SDB_FLAG_TOMBSTONE) return false;
             const uint64_t d = at0 + x;
             if (x >= n || d >= a.chain.cap_links) return false;  // never out of the pair's slots
@@ -595,9 +626,9 @@ uint64_t get_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t 
     return get_bind(a, nullptr, merge);
 }
 
-// The kernels of a bound get in stream order.  P: the call has filter policies, chosen once for the kernels that hold
-// the filter step; merge: a.chain is given.
-template <bool P>
+// The kernels of a bound get in stream order.  P: the call has filter policies, V: it has projections, each chosen
+// once for the kernels that hold the step; merge: a.chain is given.
+template <bool P, bool V>
 static hipError_t launch_get_kernels(const GetArgs &a, bool merge, hipStream_t st) {
     const uint64_t tb = a.t.total_blocks, n = a.nkeys, pairs = n * a.t.num_runs;
     // the kernels stride past these caps; the per-block parse and the per-pair walks are latency-bound threads: one
@@ -605,27 +636,28 @@ static hipError_t launch_get_kernels(const GetArgs &a, bool merge, hipStream_t s
     const dim3 lg((uint32_t)std::min<uint64_t>((pairs + 255) / 256, 1u << 20));
     const dim3 wg((uint32_t)std::min<uint64_t>((pairs + 63) / 64, 1u << 22)), qg((uint32_t)((n + 63) / 64));
     hipError_t e;
-    hipLaunchKernelGGL(k_get_validate, dim3(1), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_get_locate<P>, lg, dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_get_validate<V>, dim3(1), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((k_get_locate<P, V>), lg, dim3(256), 0, st, a);
     if ((e = launch_check(CheckArgs{{}, a.t, a.bad, tb, a.mark, a.bstat}, st)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_get_rows, dim3((uint32_t)((tb + 63) / 64)), dim3(64), 0, st, a);
     if (!merge) {
-        hipLaunchKernelGGL(k_get_walk<P>, wg, dim3(64), 0, st, a);
+        hipLaunchKernelGGL((k_get_walk<P, V>), wg, dim3(64), 0, st, a);
         hipLaunchKernelGGL(k_get_resolve<false>, qg, dim3(64), 0, st, a);
         hipLaunchKernelGGL(k_get_final, dim3(1), dim3(64), 0, st, a);
     } else {
-        hipLaunchKernelGGL(k_gm_walk<P>, wg, dim3(64), 0, st, a);
+        hipLaunchKernelGGL((k_gm_walk<P, V>), wg, dim3(64), 0, st, a);
         hipLaunchKernelGGL(k_get_resolve<true>, qg, dim3(64), 0, st, a);
         if ((e = launch_excl_scan2(a.qn, a.qn, n, a.tx, a.ty, a.chain.chain_start, a.qscan, st)) != hipSuccess) return e;
         hipLaunchKernelGGL(k_gm_final, dim3(1), dim3(64), 0, st, a);
-        hipLaunchKernelGGL(k_gm_emit<P>, wg, dim3(64), 0, st, a);
+        hipLaunchKernelGGL((k_gm_emit<P, V>), wg, dim3(64), 0, st, a);
     }
     return hipGetLastError();
 }
 
 hipError_t launch_get(const sdb_lsm_view &t, const sdb_filter_policy *pol, const uint8_t *key_bytes, const uint64_t *key_off,
                       uint64_t nkeys, const int32_t *probe_len, const uint64_t *max_seq, const sdb_get_out &out,
-                      const sdb_chain_out *chain /* sdb_lsm_get_merge, else nullptr */, uint8_t *w, hipStream_t st) {
+                      const sdb_chain_out *chain /* sdb_lsm_get_merge, else nullptr */,
+                      const sdb_scan_ranges *proj /* sdb_lsm_get_projected, else nullptr */, uint8_t *w, hipStream_t st) {
     const uint64_t tb = t.total_blocks, n = nkeys;
     const bool none = n == 0 || t.num_ssts == 0 || t.num_runs == 0 || tb == 0;  // nothing to search
     hipError_t e;
@@ -659,7 +691,12 @@ hipError_t launch_get(const sdb_lsm_view &t, const sdb_filter_policy *pol, const
     get_bind(a, w, chain != nullptr);
     if ((e = hipMemsetAsync(a.mark, 0, tb, st)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(a.bstat, 0xFF, 4 * tb, st)) != hipSuccess) return e;
-    return pol || probe_len ? launch_get_kernels<true>(a, chain != nullptr, st) : launch_get_kernels<false>(a, chain != nullptr, st);
+    const bool merge = chain != nullptr;
+    if (proj) {
+        a.proj = *proj;
+        return pol || probe_len ? launch_get_kernels<true, true>(a, merge, st) : launch_get_kernels<false, true>(a, merge, st);
+    }
+    return pol || probe_len ? launch_get_kernels<true, false>(a, merge, st) : launch_get_kernels<false, false>(a, merge, st);
 }
 
 }  // namespace sdb

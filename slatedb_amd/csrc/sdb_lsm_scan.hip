@@ -57,6 +57,15 @@
 //                  and none of its errors shows; neighbouring ranges of one SST share a wave, so a wave's probes hit
 //                  one bitmap
 //   k_ls_rstat     also: range_filtered, and their sum for k_ls_final
+// sdb_lsm_scan_projected (a filtered scan with proj: SsTableView.visible_range per SST, db_state.rs:61-78) runs that
+// sequence with a pair's range replaced by its view range V = range r intersected with visible[i]
+// (calculate_view_range, db_state.rs:243-251; ls_view):
+//   k_ls_validate  also: a projection with a start kind other than unbounded / included, an end kind above excluded or
+//                  offsets that descend makes the call malformed
+//   k_ls_locate    participation, the block range and the marks from V; a pair whose V is a point while its range is
+//                  not asks Point(k) and hashes for itself (point_key is judged on the view range, sst_iter.rs:82-87)
+//   k_ls_edge      the candidates are the rows V contains
+// Everything behind k_ls_edge sees fewer pairs and candidates and knows nothing of projections.
 #include <climits>
 
 #include "sdb_range.h"
@@ -112,13 +121,24 @@ struct LsArgs {
     uint8_t *filt;                  // per pair: 1 = the SST's filter ruled it out for the range
     int64_t *qlen;                  // per range, when the policies agree: what its query probes in every SST:
     uint64_t *qh;                   //   the length (< 0: nothing) and the filter hash
+    // sdb_lsm_scan_projected only
+    sdb_scan_ranges proj;           // per SST: SsTableView.visible_range, (UNBOUNDED, UNBOUNDED) = None
 };
 enum { kBase = 0x100 };  // a value or a tombstone ended the chain
 enum { kCtlFirstBad = 0, kCtlFailed, kCtlBad, kCtlGo1, kCtlGo2, kCtlGo3, kCtlMaxChain, kCtlFiltered, kCtlUniform, kCtlWords = 16 };
 
+// PROJ: the call has projections (sdb_lsm_scan_projected).  As FILTER below: the kernels that read them exist once
+// without the step, so the six calls without projections launch what they always launched.
+template <bool PROJ>
 __global__ __launch_bounds__(256) void k_ls_validate(LsArgs a) {
-    const int bad = lsm_validate(a.t, a.sstat);
+    int bad = lsm_validate(a.t, a.sstat);
     const int uni = policies_validate(a.pol, a.t.num_ssts, a.sstat);
+    if (PROJ) {  // P5: a malformed projection makes the call malformed
+        int pb = 0;
+        for (uint32_t i = threadIdx.x; i < a.t.num_ssts; i += blockDim.x)
+            if (bad_projection(a.proj, i)) pb = 1;
+        bad |= __syncthreads_or(pb);
+    }
     if (threadIdx.x == 0) {
         for (int i = 0; i < kCtlWords; i++) a.ctl[i] = i == kCtlFirstBad ? ~0ull : 0ull;
         a.ctl[kCtlBad] = bad ? 1ull : 0ull;
@@ -171,18 +191,32 @@ SDB_DEV void ls_pair(const LsArgs &a, uint64_t t, uint64_t &r, uint32_t &i, uint
     p = r * a.t.num_ssts + i;
 }
 
+// The view range of pair (r, SST i) (P3 of sdb_lsm_scan_projected; calculate_view_range, db_state.rs:243-251): range r
+// with the SST's projection intersected into s / e.  The pair takes part only while it is not empty as a set.
+SDB_DEV void ls_view(const LsArgs &a, uint32_t i, Bound &s, Bound &e) {
+    s = tighter_start(s, range_start(a.proj, i));
+    e = tighter_end(e, range_end(a.proj, i));
+}
+
 // FILTER: the call consults the filters (sdb_lsm_scan_filtered); the kernel exists once without the step, so the plain
 // scans keep their registers and occupancy.
-template <bool FILTER>
+template <bool FILTER, bool PROJ>
 __global__ __launch_bounds__(256) void k_ls_locate(LsArgs a) {
     if (a.ctl[kCtlBad]) return;
     for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < a.pairs; t += (uint64_t)gridDim.x * blockDim.x) {
         uint64_t r, p;
         uint32_t i;
         ls_pair(a, t, r, i, p);
-        const Bound s = range_start(a.r, r), e = range_end(a.r, r);
+        Bound s = range_start(a.r, r), e = range_end(a.r, r);
         const sdb_sst_view v = a.t.ssts[i];
-        bool part = !bad_kind(s, e) && v.num_blocks > 0 && !empty_as_set(s, e);
+        const bool okind = !bad_kind(s, e);
+        bool own = false;  // P4: the view range is a point and the range is not: the pair asks Point(k) on its own
+        if (PROJ && okind) {
+            const bool rpoint = is_point(s, e);
+            ls_view(a, i, s, e);
+            own = !rpoint && is_point(s, e);
+        }
+        bool part = okind && v.num_blocks > 0 && !empty_as_set(s, e);
         if (part && s.kind) {  // the SST's last key precedes the range
             const uint64_t o = a.t.last_key_off[i];
             part = !precedes(s, cmp_bytes(a.t.last_key_bytes + o, (uint32_t)(a.t.last_key_off[i + 1] - o), s.t, s.n, 0).c);
@@ -196,7 +230,8 @@ __global__ __launch_bounds__(256) void k_ls_locate(LsArgs a) {
             if (part && v.bloom) {
                 Probe pr{-1, 0};
                 Query q;
-                if (a.ctl[kCtlUniform]) pr = Probe{a.qlen[r], a.qh[r]};
+                if (PROJ && own) pr = filter_probe(policy_spec(a.pol, i, nullptr), false, s.t, s.n, r);  // (probe_len is the range's)
+                else if (a.ctl[kCtlUniform]) pr = Probe{a.qlen[r], a.qh[r]};
                 else if (ls_query(a, r, s, e, q)) pr = ls_probe(a, r, q, i);
                 filt = !filter_might_match(v.bloom, v.bloom_len, v.num_probes, pr.len, pr.h);
                 if (filt) part = false;
@@ -247,6 +282,7 @@ SDB_DEV Clip ls_clip(const sdb_sst_view &v, uint64_t k, const Bound &s, const Bo
     return clip_block(v.sst_version, b, s, e);
 }
 
+template <bool PROJ>
 __global__ __launch_bounds__(64) void k_ls_edge(LsArgs a) {
     const bool bad = a.ctl[kCtlBad] != 0;
     for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < a.pairs; t += (uint64_t)gridDim.x * blockDim.x) {
@@ -264,7 +300,9 @@ __global__ __launch_bounds__(64) void k_ls_edge(LsArgs a) {
                 // of the range, except where a bound's key fills whole blocks (a long run of versions under an
                 // excluded bound): the walks move inwards past blocks that keep nothing.
                 const sdb_sst_view v = a.t.ssts[i];
-                const Bound s = range_start(a.r, r), e = range_end(a.r, r), open{nullptr, 0, 0};
+                Bound s = range_start(a.r, r), e = range_end(a.r, r);
+                const Bound open{nullptr, 0, 0};
+                if (PROJ) ls_view(a, i, s, e);  // the candidates are the entries the view range contains
                 g0 = a.pc[base + be];
                 k0 = a.pk[base + be];
                 fb = (uint32_t)be;
@@ -711,7 +749,9 @@ hipError_t launch_lsm_scan(const sdb_lsm_view &t, const sdb_scan_ranges &r, cons
                            uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out &out,
                            const sdb_chain_out *chain /* sdb_lsm_scan_merge, else nullptr */,
                            const sdb_filter_policy *pol, const sdb_scan_prefixes *px,
-                           const sdb_scan_filter_out *fout /* sdb_lsm_scan_filtered, else nullptr */, uint8_t *w, hipStream_t st) {
+                           const sdb_scan_filter_out *fout /* sdb_lsm_scan_filtered, else nullptr */,
+                           const sdb_scan_ranges *proj /* sdb_lsm_scan_projected (with fout), else nullptr */, uint8_t *w,
+                           hipStream_t st) {
     const uint64_t tb = t.total_blocks, n = r.n;
     hipError_t e;
     if (n == 0 || t.num_ssts == 0 || tb == 0) {  // every range is empty
@@ -744,6 +784,7 @@ hipError_t launch_lsm_scan(const sdb_lsm_view &t, const sdb_scan_ranges &r, cons
         a.pol = pol;
         if (px) a.px = *px;
         a.fout = *fout;
+        if (proj) a.proj = *proj;
         lsm_scan_filter_bind(a, w, chain != nullptr);
     } else if (chain) {
         lsm_scan_merge_bind(a, w);
@@ -754,16 +795,20 @@ hipError_t launch_lsm_scan(const sdb_lsm_view &t, const sdb_scan_ranges &r, cons
     if ((e = hipMemsetAsync(a.mark, 0, tb, st)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(a.bstat, 0xFF, 4 * tb, st)) != hipSuccess) return e;
     const uint32_t rw = (uint32_t)((n + 63) / 64);
-    hipLaunchKernelGGL(k_ls_validate, dim3(1), dim3(256), 0, st, a);
+    const bool pj = a.filter && proj;
+    if (pj) hipLaunchKernelGGL(k_ls_validate<true>, dim3(1), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_ls_validate<false>, dim3(1), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_ls_ranges, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, a);
-    if (a.filter) hipLaunchKernelGGL(k_ls_locate<true>, dim3(scan_grid(P, 256)), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_ls_locate<false>, dim3(scan_grid(P, 256)), dim3(256), 0, st, a);
+    if (pj) hipLaunchKernelGGL((k_ls_locate<true, true>), dim3(scan_grid(P, 256)), dim3(256), 0, st, a);
+    else if (a.filter) hipLaunchKernelGGL((k_ls_locate<true, false>), dim3(scan_grid(P, 256)), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_ls_locate<false, false>), dim3(scan_grid(P, 256)), dim3(256), 0, st, a);
     if ((e = launch_check(CheckArgs{{}, t, (const uint32_t *)(a.ctl + kCtlBad), tb, a.mark, a.bstat}, st)) != hipSuccess) return e;
     // the per-block, per-pair and per-item walks are latency-bound threads: one wave per workgroup spreads them over the CUs
     hipLaunchKernelGGL(k_ls_block, dim3((uint32_t)((tb + 63) / 64)), dim3(64), 0, st, a);
     if ((e = launch_excl_scan2(a.cnt, a.kb, tb, a.tx, a.ty, a.pc, a.pk, st)) != hipSuccess) return e;
     if ((e = launch_excl_scan2(a.bbad, a.rd, tb, a.tx, a.ty, a.pb, a.pr, st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_ls_edge, dim3(scan_grid(P, 64)), dim3(64), 0, st, a);
+    if (pj) hipLaunchKernelGGL(k_ls_edge<true>, dim3(scan_grid(P, 64)), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL(k_ls_edge<false>, dim3(scan_grid(P, 64)), dim3(64), 0, st, a);
     hipLaunchKernelGGL(k_ls_rstat, dim3(rw), dim3(64), 0, st, a);
     if ((e = launch_excl_scan2(a.pit, a.pit, P, a.tx, a.ty, a.pis, a.cs, st)) != hipSuccess) return e;
     if ((e = launch_excl_scan2(a.pn, a.pkb, P, a.tx, a.ty, a.cs, a.cks, st)) != hipSuccess) return e;

@@ -28,6 +28,39 @@ SDB_DEV bool empty_as_set(const Bound &s, const Bound &e) {
     const int c = cmp_bytes(s.t, s.n, e.t, e.n, 0).c;
     return c > 0 || (c == 0 && (s.kind == SDB_BOUND_EXCLUDED || e.kind == SDB_BOUND_EXCLUDED));
 }
+// BytesRange::intersect (comparable_range.rs:224-236) a bound at a time: the tighter of two start bounds (Unbounded <
+// Included(a) < Excluded(a)) and the tighter of two end bounds (Excluded(a) < Included(a) < Unbounded).  The
+// intersection is empty exactly when empty_as_set of the two results says so (non_empty, :265-274).
+// (a bound is picked field by field: a pick between two structs goes through scratch memory)
+SDB_DEV Bound pick_bound(bool first, const Bound &x, const Bound &y) {
+    return Bound{first ? x.t : y.t, first ? x.n : y.n, first ? x.kind : y.kind};
+}
+SDB_DEV Bound tighter_start(const Bound &x, const Bound &y) {
+    bool first = x.kind != 0;
+    if (x.kind && y.kind) {
+        const int c = cmp_bytes(x.t, x.n, y.t, y.n, 0).c;
+        first = c > 0 || (c == 0 && x.kind == SDB_BOUND_EXCLUDED);
+    }
+    return pick_bound(first, x, y);
+}
+SDB_DEV Bound tighter_end(const Bound &x, const Bound &y) {
+    bool first = x.kind != 0;
+    if (x.kind && y.kind) {
+        const int c = cmp_bytes(x.t, x.n, y.t, y.n, 0).c;
+        first = c < 0 || (c == 0 && x.kind == SDB_BOUND_EXCLUDED);
+    }
+    return pick_bound(first, x, y);
+}
+// Included(k)..=Included(k): SstView::point_key (sst_iter.rs:82-87)
+SDB_DEV bool is_point(const Bound &s, const Bound &e) {
+    return s.kind == SDB_BOUND_INCLUDED && e.kind == SDB_BOUND_INCLUDED && s.n == e.n && cmp_bytes(s.t, s.n, e.t, e.n, 0).c == 0;
+}
+// Projection i (SsTableView.visible_range) of an sdb_scan_ranges is malformed: a start other than Unbounded or Included
+// (new_projected's assert, db_state.rs:126-130), an end that is no std::ops::Bound, or offsets that descend.
+SDB_DEV bool bad_projection(const sdb_scan_ranges &g, uint64_t i) {
+    return g.start_kind[i] > SDB_BOUND_INCLUDED || g.end_kind[i] > SDB_BOUND_EXCLUDED || g.start_off[i + 1] < g.start_off[i] ||
+           g.end_off[i + 1] < g.end_off[i];
+}
 
 // partitions_covering_range(index, start, end) (partitioned_keyspace.rs:87-110) over v's index keys: the blocks
 // [start, end), as the reference returns them: end may be below start.

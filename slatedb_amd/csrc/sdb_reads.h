@@ -18,18 +18,20 @@ uint64_t scan_workspace_bytes(uint64_t num_blocks, uint64_t nranges);
 hipError_t launch_scan(const sdb_sst_view &v, const sdb_scan_ranges &r, uint32_t desc, const sdb_scan_out &out, uint8_t *w,
                        hipStream_t st);
 
-// chain != NULL: the merging get (sdb_lsm_get_merge); pol / probe_len: sdb_lsm_get_filtered's, else NULL
+// chain != NULL: the merging get (sdb_lsm_get_merge); pol / probe_len: sdb_lsm_get_filtered's, else NULL; proj:
+// sdb_lsm_get_projected's, else NULL
 uint64_t get_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys, bool merge);
 hipError_t launch_get(const sdb_lsm_view &t, const sdb_filter_policy *pol, const uint8_t *key_bytes, const uint64_t *key_off,
                       uint64_t nkeys, const int32_t *probe_len, const uint64_t *max_seq, const sdb_get_out &out,
-                      const sdb_chain_out *chain, uint8_t *w, hipStream_t st);
+                      const sdb_chain_out *chain, const sdb_scan_ranges *proj, uint8_t *w, hipStream_t st);
 
-// chain != NULL: the merging scan; fout != NULL: the filtered one, with pol and px
+// chain != NULL: the merging scan; fout != NULL: the filtered one, with pol and px; proj != NULL (with fout): the
+// projected one
 uint64_t lsm_scan_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint64_t nranges, uint64_t cand_entries,
                                   uint64_t cand_key_bytes, bool merge, bool filter);
 hipError_t launch_lsm_scan(const sdb_lsm_view &t, const sdb_scan_ranges &r, const uint64_t *max_seq, uint32_t desc,
                            uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out &out,
                            const sdb_chain_out *chain, const sdb_filter_policy *pol, const sdb_scan_prefixes *px,
-                           const sdb_scan_filter_out *fout, uint8_t *w, hipStream_t st);
+                           const sdb_scan_filter_out *fout, const sdb_scan_ranges *proj, uint8_t *w, hipStream_t st);
 
 }  // namespace sdb

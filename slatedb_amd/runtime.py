@@ -847,10 +847,35 @@ def _limit_exceeded(summary, word):
     return int(summary.cpu().numpy()[word]) & 0xFFFFFFFF == _abi.SDB_LIMIT_EXCEEDED
 
 
+def projections_columnar(visible):
+    """[SsTableView.visible_range per SST: None (the whole SST) or (start, start_kind, end, end_kind)] -> the host
+    arrays of the sdb_scan_ranges that the projected reads take as `proj`, as scan_ranges_columnar names them;
+    None becomes (UNBOUNDED, UNBOUNDED)."""
+    return scan_ranges_columnar([v if v is not None else (None, _abi.BOUND_UNBOUNDED, None, _abi.BOUND_UNBOUNDED)
+                                 for v in visible])
+
+
+def _projections(projections, tree):
+    """The `proj` argument of a projected read: None, one visible range (or None) per SST of the tree, or a dict of
+    device tensors named as projections_columnar's arrays plus "n" -> (the tensors kept alive, the _abi.ScanRanges
+    or None)."""
+    if projections is None:
+        return None, None
+    if isinstance(projections, dict):
+        pt, n = projections, int(projections["n"])
+    else:
+        assert len(projections) == tree["num_ssts"], "one visible range (or None) per SST"
+        n = len(projections)
+        pt = {k: _to_dev(a, tree["device"]) for k, a in projections_columnar(projections).items()}
+    return pt, _abi.ScanRanges(n, _ptr(pt["start_bytes"]), _ptr(pt["start_off"]), _ptr(pt["start_kind"]),
+                               _ptr(pt["end_bytes"]), _ptr(pt["end_off"]), _ptr(pt["end_kind"]))
+
+
 def _lsm_get(entry, views, runs, keys, max_seq, stream, workspace, merge=False, cap_links=None, fill=0, filtered=False,
-             probe_len=None):
-    """The tree gets.  entry: the C entry point (sdb_lsm_get, sdb_lsm_get_merge or sdb_lsm_get_filtered; its sizer
-    is entry + "_workspace_bytes"); filtered: it takes the policies, probe_len and an optional chain; merge: the
+             probe_len=None, projected=False, projections=None):
+    """The tree gets.  entry: the C entry point (sdb_lsm_get, sdb_lsm_get_merge, sdb_lsm_get_filtered or
+    sdb_lsm_get_projected; its sizer is entry + "_workspace_bytes"); filtered: it takes the policies, probe_len and an
+    optional chain; projected: it is a filtered call that takes the projections too; merge: the
     call has a chain.  Marshals the tree, the keys, the bounds and probe_len as device tensors, the result dict with
     the GET_FIELDS and the summary; a caller's workspace must hold the call; with merge and cap_links None the links
     are sized at nkeys first and, when they did not fit, at the reported num_links in a second call."""
@@ -873,10 +898,12 @@ def _lsm_get(entry, views, runs, keys, max_seq, stream, workspace, merge=False, 
                                                      *([int(bool(merge))] if filtered else []))
     ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=dev)
     assert ws.numel() >= wsb, "workspace too small"
+    pjt, pj = _projections(projections, tree)
 
     def run(cap):
         chain = _chain_out(res, n, cap, dev, fill) if merge else None
-        args = [C.byref(tree["lsm"])] + ([_ptr(tree.get("_policies"))] if filtered else [])
+        args = [C.byref(tree["lsm"])] + ([C.byref(pj) if pj is not None else None] if projected else [])
+        args += ([_ptr(tree.get("_policies"))] if filtered else [])
         args += [kb.data_ptr(), ko.data_ptr(), n] + ([_ptr(probe_len)] if filtered else [])
         args += [_ptr(max_seq), C.byref(out)] + ([C.byref(chain) if merge else None] if merge or filtered else [])
         st = getattr(lib(), entry)(*args, ws.data_ptr(), wsb, _sp(stream))
@@ -890,7 +917,7 @@ def _lsm_get(entry, views, runs, keys, max_seq, stream, workspace, merge=False, 
             run(int(res["chain_summary"][0].item()))
     else:
         run(cap_links or 0)
-    res.update(_ws=ws, _tree=tree, _keys=(kb, ko), _max_seq=max_seq, _probe_len=probe_len)
+    res.update(_ws=ws, _tree=tree, _keys=(kb, ko), _max_seq=max_seq, _probe_len=probe_len, _projections=pjt)
     return res
 
 
@@ -924,11 +951,12 @@ def _lsm_scan_out(res, cap_e, cap_k, dev):
 
 
 def _lsm_scan(entry, tree, ranges, max_seq, descending, stream, workspace, cand, cap, merge=False, cap_links=None, fill=0,
-              filtered=False, prefixes=None, probe_len=None):
-    """The tree scans.  entry: the C entry point (sdb_lsm_scan, sdb_lsm_scan_merge or sdb_lsm_scan_filtered; its
-    sizer is entry + "_workspace_bytes"); filtered: it takes the policies, the prefixes, an optional chain and the
-    filter outputs; merge: the call has a chain.  Marshals the ranges, the bounds and the prefixes as device tensors
-    and the result dict; a caller's workspace that is too small is replaced by a fresh one, unless cand was given.
+              filtered=False, prefixes=None, probe_len=None, projected=False, projections=None):
+    """The tree scans.  entry: the C entry point (sdb_lsm_scan, sdb_lsm_scan_merge, sdb_lsm_scan_filtered or
+    sdb_lsm_scan_projected; its sizer is entry + "_workspace_bytes"); filtered: it takes the policies, the prefixes, an
+    optional chain and the filter outputs; projected: it is a filtered call that takes the projections too; merge: the
+    call has a chain.  Marshals the ranges, the bounds, the prefixes and the projections as device tensors and the
+    result dict; a caller's workspace that is too small is replaced by a fresh one, unless cand was given.
     With a capacity None (cap_links counts only with merge) the call runs once, and on SDB_LIMIT_EXCEEDED again
     with the staging at max(given, reported), cap like the staging and cap_links like cand_entries where those
     were None."""
@@ -957,6 +985,7 @@ def _lsm_scan(entry, tree, ranges, max_seq, descending, stream, workspace, cand,
         res["range_filtered"] = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
         res["num_filtered"] = torch.zeros(1, dtype=torch.int64, device=dev)
         fout = _abi.ScanFilterOut(res["range_filtered"].data_ptr(), res["num_filtered"].data_ptr())
+    pjt, pj = _projections(projections, tree)
 
     def run(ce, ckb, cap_e, cap_k, cap_l):
         wsb = getattr(lib(), entry + "_workspace_bytes")(tree["total_blocks"], tree["num_ssts"], tree["num_runs"], n, ce,
@@ -967,7 +996,8 @@ def _lsm_scan(entry, tree, ranges, max_seq, descending, stream, workspace, cand,
             ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
         out = _lsm_scan_out(res, cap_e, cap_k, dev)
         chain = _chain_out(res, cap_e, cap_l, dev, fill) if merge else None
-        args = [C.byref(tree["lsm"])] + ([_ptr(tree.get("_policies"))] if filtered else []) + [C.byref(rg)]
+        args = [C.byref(tree["lsm"])] + ([C.byref(pj) if pj is not None else None] if projected else [])
+        args += ([_ptr(tree.get("_policies"))] if filtered else []) + [C.byref(rg)]
         args += ([C.byref(px) if px is not None else None] if filtered else [])
         args += [_ptr(max_seq), int(bool(descending)), ce, ckb, C.byref(out)]
         args += ([C.byref(chain) if merge else None] if merge or filtered else []) + ([C.byref(fout)] if filtered else [])
@@ -986,7 +1016,7 @@ def _lsm_scan(entry, tree, ranges, max_seq, descending, stream, workspace, cand,
             run(ce, ckb, *(cap if cap is not None else (ce, ckb)), cap_links if cap_links is not None else ce)
     else:
         run(cand[0], cand[1], cap[0], cap[1], cap_links or 0)
-    res.update(_tree=tree, _ranges=rt, _max_seq=max_seq, _prefixes=pt)
+    res.update(_tree=tree, _ranges=rt, _max_seq=max_seq, _prefixes=pt, _projections=pjt)
     return res
 
 
@@ -1076,6 +1106,26 @@ def lsm_get_filtered_device(views, runs, keys, probe_len=None, max_seq=None, str
     result are the unfiltered call's."""
     return _lsm_get("sdb_lsm_get_filtered", views, runs, keys, max_seq, stream, workspace, merge=bool(merge),
                     cap_links=cap_links, fill=fill, filtered=True, probe_len=probe_len)
+
+
+def lsm_scan_projected_device(tree, projections, ranges, prefixes=None, probe_len=None, max_seq=None, descending=False,
+                              stream=None, workspace=None, cand=None, cap=None, cap_links=None, fill=0, merge=False):
+    """sdb_lsm_scan_projected: lsm_scan_filtered_device over projected SST views.  projections: None (no SST is
+    projected: exactly the filtered call), a list with SsTableView.visible_range of every SST of the tree (None: the
+    whole SST, else (start, start_kind, end, end_kind)), or a dict of device tensors named as projections_columnar's
+    arrays plus "n".  The other arguments and the result are the filtered call's."""
+    return _lsm_scan("sdb_lsm_scan_projected", tree, ranges, max_seq, descending, stream, workspace, cand, cap,
+                     merge=bool(merge), cap_links=cap_links, fill=fill, filtered=True, prefixes=prefixes,
+                     probe_len=probe_len, projected=True, projections=projections)
+
+
+def lsm_get_projected_device(views, runs, projections, keys, probe_len=None, max_seq=None, stream=None, workspace=None,
+                             cap_links=None, fill=0, merge=False):
+    """sdb_lsm_get_projected: lsm_get_filtered_device over projected SST views; projections as
+    lsm_scan_projected_device takes them.  The other arguments and the result are the filtered call's."""
+    return _lsm_get("sdb_lsm_get_projected", views, runs, keys, max_seq, stream, workspace, merge=bool(merge),
+                    cap_links=cap_links, fill=fill, filtered=True, probe_len=probe_len, projected=True,
+                    projections=projections)
 
 
 # ------------------------------------------------------------------------------------------------
