@@ -81,6 +81,7 @@ typedef enum sdb_status {
     SDB_MERGE_OPERATOR_MISSING = 10,/* SlateDBError::MergeOperatorMissing (merge_operator.rs:213-223) */
     SDB_DECOMPRESSION_ERROR = 11,   /* SlateDBError::BlockDecompressionError (format/sst.rs:884-917) */
     SDB_INVALID_SEQUENCE_ORDER = 12,/* SlateDBError::InvalidSequenceOrder (merge_operator.rs:293-299) */
+    SDB_MERGE_OPERATOR_ERROR = 13,  /* SlateDBError::MergeOperatorError: the user's operator failed */
     SDB_DEVICE_ERROR = 100          /* no HIP device / launch failure */
 } sdb_status;
 
@@ -1083,6 +1084,73 @@ sdb_status sdb_compactor_run_ssts(sdb_compactor *c, const sdb_compaction_input *
 sdb_status sdb_compactor_sst(const sdb_compactor *c, uint32_t i, sdb_compacted_sst *out);
 /* The merged stream of the last run (device batch view) and its summary (host copy). */
 sdb_status sdb_compactor_merged(const sdb_compactor *c, sdb_kv_batch *batch, sdb_merge_summary *summary);
+
+/* ---------------------------------------------------------------------------------------------
+ * Compaction with a merge operator: the same two jobs with MergeOperatorIterator(op, iter,
+ * merge_different_expire_ts = false, snapshot_barrier_seq = retention_min_seq) between the MergeIterator
+ * and the RetentionIterator, as compaction and memtable flush build it (compactor_executor.rs:390-400,
+ * flush.rs:212-222).  The device finds the operand chains in the merged order, the host runs `op` over
+ * bytes the device gathered, and retention, cuts and encode run over the collapsed stream.
+ *
+ * The walk (merge_operator.rs:324-485) runs over the versions of one key in MergeIterator order (seq
+ * descending, equal seqs in run order), before retention's equal-seq replacement, and partitions them
+ * into units:
+ *   - a version that is not a merge operand is a unit of its own (:474-476);
+ *   - a merge operand with seq > barrier is a unit of its own (:465-469); barrier = retention->min_seq
+ *     when has_min_seq, else there is none; the compare is strict;
+ *   - any other merge operand opens a chain with first_expire_ts = its Option<expire_ts>.  Over the
+ *     following versions of the key (:387-412): one whose Option<expire_ts> differs (None == None,
+ *     Some(a) == Some(a) only; :330-335, checked before the kind) ends the chain without a base and starts
+ *     the next unit; a matching value or tombstone ends the chain as its base and is consumed; a matching
+ *     operand is a link.  The walk then goes on with the key's remaining versions.
+ *   - a chain unit: seq = its first link's; create_ts = the maximum and expire_ts = the minimum over the
+ *     links and the base that carry one (MergeTracker, :262-303); kind Value when a base was found (a
+ *     tombstone base included: its value is None), else Merge (:437-441); value = the operands newest first
+ *     in batches of 100 (MERGE_BATCH_SIZE), each batch reversed and merged with no existing value, the
+ *     batch results reversed and merged once with the base (:341-447).  A chain of one link without a base
+ *     goes through the operator twice like any other.
+ * SDB_INVALID_SEQUENCE_ORDER (:293-299) cannot arise: the run-order check of the merge (SDB_INVALID_ARGUMENT)
+ * already guarantees descending seqs per key.
+ * Retention (retention_iterator.rs:91-204) then runs unchanged over the units: each unit's seq, kind,
+ * expire_ts and value length.  An expired Merge unit is skipped and counts once in expired_merges.
+ * retention->merge_operands is ignored: operands that reach retention are legitimate here.
+ *
+ * The operator.  Operands arrive oldest first; existing == NULL: no existing value.  *result must stay
+ * valid until the next call with the same ctx; the library copies it at once.  A non-zero return fails the
+ * job with SDB_MERGE_OPERATOR_ERROR, first_error_entry = the merged position of the chain's first link; no
+ * output SST is valid.  op == NULL: SDB_INVALID_ARGUMENT.
+ *
+ * Host synchronisations: those of sdb_compactor_run / sdb_compactor_run_ssts, plus, between the merge order
+ * and retention, one for the chain summary (groups, links, bytes: it sizes the tables) and, when the job has
+ * a chain, one for the chain tables: a pinned D2H of the group table, the link table and the staging arena
+ * (group keys and link values, gathered contiguously on the device), the operator calls, and an H2D of the
+ * merged values and their offsets.  A job without a chain does no copy and never calls the operator.
+ * sdb_compactor_run_ssts_merge sizes its value buffer as declared val_bytes - link_bytes + merged_bytes (a
+ * merged value may be longer than all of its inputs).  sdb_compactor_sst / sdb_compactor_merged read the
+ * results as for the other jobs.
+ * ------------------------------------------------------------------------------------------- */
+typedef int32_t (*sdb_merge_batch_fn)(void *ctx, const uint8_t *key, uint64_t key_len,
+                                      const uint8_t *existing /* NULL: none */, uint64_t existing_len,
+                                      const uint8_t *const *operands, const uint64_t *operand_len, uint32_t n,
+                                      const uint8_t **result, uint64_t *result_len);
+typedef struct sdb_merge_op_stats {
+    uint64_t groups;                /* chains */
+    uint64_t links;                 /* operands plus bases of every chain */
+    uint64_t link_bytes;            /* value bytes of the links (D2H) */
+    uint64_t merged_bytes;          /* value bytes of the chains' merged values (H2D) */
+    uint64_t operator_calls;
+} sdb_merge_op_stats;
+sdb_status sdb_compactor_run_merge(sdb_compactor *c, const sdb_run *runs, uint32_t nruns,
+                                   const sdb_retention *retention, sdb_merge_batch_fn op, void *ctx,
+                                   const sdb_sst_params *params, uint64_t max_sst_size, void *stream,
+                                   uint32_t *num_ssts);
+sdb_status sdb_compactor_run_ssts_merge(sdb_compactor *c, const sdb_compaction_input *inputs, uint32_t ninputs,
+                                        const uint32_t *run_start, uint32_t nruns, uint16_t input_sst_version,
+                                        const sdb_retention *retention, sdb_merge_batch_fn op, void *ctx,
+                                        const sdb_sst_params *params, uint64_t max_sst_size, void *stream,
+                                        uint32_t *num_ssts);
+/* The chains of the last sdb_compactor_run_merge / sdb_compactor_run_ssts_merge job (zeros after any other). */
+sdb_status sdb_compactor_merge_stats(const sdb_compactor *c, sdb_merge_op_stats *stats);
 
 /* ---------------------------------------------------------------------------------------------
  * SST footer (host): everything after the data section, so data ++ footer is the whole SST object

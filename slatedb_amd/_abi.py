@@ -18,6 +18,7 @@ SDB_CORRUPT_BLOCK = 9
 SDB_MERGE_OPERATOR_MISSING = 10
 SDB_DECOMPRESSION_ERROR = 11
 SDB_INVALID_SEQUENCE_ORDER = 12
+SDB_MERGE_OPERATOR_ERROR = 13
 SDB_DEVICE_ERROR = 100
 CODEC_NONE, CODEC_SNAPPY, CODEC_ZLIB, CODEC_LZ4, CODEC_ZSTD = 0, 1, 2, 3, 4  # CompressionFormat
 
@@ -25,7 +26,7 @@ STATUS_NAMES = {
     0: "OK", 1: "EMPTY_KEY", 2: "EMPTY_BLOCK", 3: "CHECKSUM_MISMATCH", 4: "INVALID_ROW_FLAGS",
     5: "INVALID_VERSION", 6: "LIMIT_EXCEEDED", 7: "UNSUPPORTED", 8: "INVALID_ARGUMENT",
     9: "CORRUPT_BLOCK", 10: "MERGE_OPERATOR_MISSING", 11: "DECOMPRESSION_ERROR",
-    12: "INVALID_SEQUENCE_ORDER", 100: "DEVICE_ERROR",
+    12: "INVALID_SEQUENCE_ORDER", 13: "MERGE_OPERATOR_ERROR", 100: "DEVICE_ERROR",
 }
 
 KIND_VALUE, KIND_MERGE, KIND_TOMBSTONE = 0, 1, 2
@@ -299,7 +300,16 @@ class CompactionInput(C.Structure):
         ("key_bytes", C.c_uint64), ("val_bytes", C.c_uint64),
     ]
 
+class MergeOpStats(C.Structure):
+    _fields_ = [
+        ("groups", C.c_uint64), ("links", C.c_uint64), ("link_bytes", C.c_uint64), ("merged_bytes", C.c_uint64),
+        ("operator_calls", C.c_uint64),
+    ]
 
+
+# sdb_merge_batch_fn: (ctx, key, key_len, existing, existing_len, operands, operand_len, n, result, result_len)
+MERGE_BATCH_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, u8p, C.c_uint64, u8p, C.c_uint64, C.POINTER(u8p), u64p,
+                             C.c_uint32, C.POINTER(u8p), u64p)
 
 DECODE_DESCENDING = 1
 DECODE_FAIL_FAST = 2  # SDB_DECODE_FAIL_FAST
@@ -403,6 +413,13 @@ SIGNATURES = {
     "sdb_compactor_run_ssts": (C.c_int, [C.c_void_p, C.POINTER(CompactionInput), C.c_uint32, u32p, C.c_uint32,
                                          C.c_uint16, C.POINTER(Retention), C.POINTER(SstParams), C.c_uint64,
                                          C.c_void_p, u32p]),
+    "sdb_compactor_run_merge": (C.c_int, [C.c_void_p, C.POINTER(Run), C.c_uint32, C.POINTER(Retention),
+                                          MERGE_BATCH_FN, C.c_void_p, C.POINTER(SstParams), C.c_uint64, C.c_void_p,
+                                          u32p]),
+    "sdb_compactor_run_ssts_merge": (C.c_int, [C.c_void_p, C.POINTER(CompactionInput), C.c_uint32, u32p, C.c_uint32,
+                                               C.c_uint16, C.POINTER(Retention), MERGE_BATCH_FN, C.c_void_p,
+                                               C.POINTER(SstParams), C.c_uint64, C.c_void_p, u32p]),
+    "sdb_compactor_merge_stats": (C.c_int, [C.c_void_p, C.POINTER(MergeOpStats)]),
     "sdb_compactor_sst": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(CompactedSst)]),
     "sdb_compactor_merged": (C.c_int, [C.c_void_p, C.POINTER(KvBatch), C.POINTER(MergeSummary)]),
     "sdb_sst_footer": (C.c_int, [C.POINTER(FooterIn), C.c_void_p, C.c_uint64, u64p]),

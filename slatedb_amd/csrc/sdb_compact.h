@@ -31,6 +31,65 @@ struct RunDesc {  // sdb_run + the run's first global entry index
     const int64_t *expire_ts;
 };
 
+// ---- operand chains of a compaction with a merge operator (k_mg_chain, k_mg_chain_scan, k_mg_chain_emit) ----
+// What a merged position is in the stream MergeOperatorIterator yields (merge_operator.rs:324-485; the rules
+// are restated in include/slatedb_amd.h, "Compaction with a merge operator").
+constexpr uint8_t kUnitAbsorbed = 0;  // a link (or the base) of a chain that starts at an earlier position
+constexpr uint8_t kUnitPass = 1;      // a unit of its own
+constexpr uint8_t kUnitChain = 2;     // the first link of a chain without a base: kind Merge
+constexpr uint8_t kUnitChainBase = 3; // the first link of a chain with a base: kind Value
+constexpr uint8_t kBaseNone = 0, kBaseValue = 1, kBaseTombstone = 2;
+struct ChainGroup {  // one chain; read by the host
+    uint64_t head;       // merged position of its first link: its links are positions [head, head + nlinks)
+    uint64_t link0;      // its first entry of the link table
+    uint64_t nlinks;     // operands plus the base
+    uint64_t seq;        // the first link's
+    int64_t create_ts, expire_ts;  // max / min over the links that carry one (ts_mask: SDB_TS_*)
+    uint64_t key_off;    // its key in the staging arena
+    uint32_t key_len;
+    uint8_t base, ts_mask;
+    uint16_t pad;
+};
+struct ChainLink {  // newest first within a group; the base (if any) is the group's last link
+    uint64_t off;    // its value in the staging arena
+    uint64_t pos;    // merged position
+    uint32_t len, pad;
+};
+struct ChainSummary {
+    uint64_t groups, links, link_bytes, key_bytes;
+};
+struct ChainArgs {  // all NULL in a job without a merge operator
+    uint8_t *unit;        // per merged position: kUnit*
+    uint64_t *uinfo;      // per chain head: its link count (k_mg_chain), then its group (k_mg_chain_emit)
+    uint64_t *ubytes;     // per chain head: the value bytes of its links
+    uint64_t *tile_sum;   // per tile of head positions: groups, links, link bytes, key bytes (exclusive after the scan)
+    ChainSummary *summary;
+    ChainGroup *group;    // the tables: sized from the summary
+    ChainLink *link;
+    uint8_t *arena;       // group keys [0, key_bytes), then link values
+    const uint64_t *moff; // uploaded: group g's merged value = mval[moff[g], moff[g + 1])
+    const uint8_t *mval;
+};
+// Sizes (w == NULL) or binds the per-position chain state of a merge of `total` entries.
+inline uint64_t chain_bind(ChainArgs &c, uint64_t total, uint8_t *w) {
+    const uint64_t ntiles = (total + kMergeTile - 1) / kMergeTile;
+    Carver k{w, 0};
+    k.take(c.unit, total + 1);
+    k.take(c.uinfo, total + 1);
+    k.take(c.ubytes, total + 1);
+    k.take(c.tile_sum, 4 * (ntiles + 1));
+    k.take(c.summary, 1);
+    return k.off;
+}
+// Sizes or binds the chain tables a summary asks for.
+inline uint64_t chain_tables_bind(ChainArgs &c, const ChainSummary &s, uint8_t *w) {
+    Carver k{w, 0};
+    k.take(c.group, s.groups);
+    k.take(c.link, s.links);
+    k.take(c.arena, s.key_bytes + s.link_bytes);
+    return k.off;
+}
+
 struct MergeArgs {
     uint32_t nruns, ntiles;
     uint32_t raw, pad;           // raw: no retention, no merge-operand check (every entry kept as it is)
@@ -49,6 +108,7 @@ struct MergeArgs {
     unsigned long long *err_merge;  // merge operands (MergeOperatorRequiredIterator): min merged position << 8 | code
     unsigned long long *metric;  // expired values, expired merges
     const unsigned long long *gate;  // NULL, or (entry << 8 | status) of a failed input (~0: none): no merge
+    ChainArgs ch;
     RunDesc r[kMaxRuns];
 };
 static_assert(sizeof(MergeArgs) < 4000, "MergeArgs is passed as kernel arguments");
@@ -78,6 +138,15 @@ hipError_t launch_merged_as_run(const sdb_merged_out &out, uint64_t n, uint32_t 
 // merge + retention (+ emit when `emit`), all on `st`
 hipError_t launch_merge(const MergeArgs &a, bool emit, hipStream_t st);
 hipError_t launch_merge_emit(const MergeArgs &a, hipStream_t st);
+// A merge with an operator, in three steps around the host's fold (a.ch bound by chain_bind):
+//   launch_merge_chains       merged order, the unit code of every position, the chain summary
+//   launch_chain_tables       group table, link table and staging arena (a.ch bound by chain_tables_bind)
+//   launch_merge_units        retention over the units (+ emit when `emit`); a.ch.moff / mval uploaded
+//   launch_merge_emit_units   the emit alone, after launch_merge_units(a, false)
+hipError_t launch_merge_chains(const MergeArgs &a, hipStream_t st);
+hipError_t launch_chain_tables(const MergeArgs &a, hipStream_t st);
+hipError_t launch_merge_units(const MergeArgs &a, bool emit, hipStream_t st);
+hipError_t launch_merge_emit_units(const MergeArgs &a, hipStream_t st);
 
 // SST cuts over the chain tables of a prep-only encode set of one slot (launch_encode_prep).  n_real
 // (device, or NULL = the slot's n): the stream's true length when the slot covers a padded stream; the

@@ -11,6 +11,10 @@
 //                 kMergeTile positions
 //   k_mg_scan     one workgroup: tile offsets, the summary
 //   k_mg_emit     per kMergeTile positions: the output batch (metadata + key / value bytes)
+//   k_mg_chain, k_mg_chain_scan, k_mg_chain_emit   with a merge operator, between k_mg_rank and k_mg_keys:
+//                 the operand chains of MergeOperatorIterator (merge_operator.rs:324-485) per merged
+//                 position, their tables and the bytes the host's operator reads; k_mg_keys / k_mg_emit
+//                 then run over the units (their <true> instantiations)
 //   k_cut         one lane: the compactor's max_sst_size walk (compactor_executor.rs:833-858) over
 //                 the chain tables of the encoder's k_seg / k_group (group, chunk, then block steps)
 //
@@ -310,15 +314,85 @@ SDB_DEV PosInfo pos_info(const MergeArgs &a, uint64_t q) {
     return x;
 }
 
-// Per merged position p: is it the first version of its key (its key differs from position p - 1's,
-// MergeIterator order)?  The merge operand check (MergeOperatorRequiredIterator, merge_operator.rs:
-// 213-223).  The thread of a key's first version then runs retention over the key's versions, newest
+// The entry at merged position p with what tells whether it is the first version of its key (its key
+// differs from position p - 1's, MergeIterator order) and whether position p + 1 holds the key too.  Lanes
+// hold consecutive positions: the neighbours' keys come by DPP (lanes 0 / 63 gather theirs alongside their
+// own), so every lane of the wave calls this (a lane past the end gathers position n - 1; n > 0).
+struct KeyEdge {
+    PosInfo me;
+    bool live, first, more;
+};
+SDB_DEV KeyEdge key_edge(const MergeArgs &a, uint64_t p, uint32_t lane, uint32_t L0) {
+    const uint64_t n = a.total;
+    KeyEdge e;
+    e.live = p < n;
+    // lane 0 also gathers position p - 1, lane 63 position p + 1 (the others re-read their own)
+    const uint64_t qo = lane == 0 ? (p > 0 ? p - 1 : p) : lane == 63 ? (p + 1 < n ? p + 1 : p) : p;
+    // both gathers unconditional (a lane past the end reads position n - 1): under a branch the
+    // compiler waited for the first gather's loads before issuing the second's
+    const uint64_t pc = e.live ? p : n - 1, qc = e.live ? qo : n - 1;
+    e.me = pos_info(a, pc);
+    const PosInfo ot = pos_info(a, qc);
+    const PosInfo &me = e.me;
+    uint64_t ppf = wave_prev_lane(me.pf), pkp = wave_prev_lane((uint64_t)me.kp);
+    uint32_t pkn = wave_prev_lane(me.kn);
+    uint64_t npf = wave_next_lane(me.pf), nkp = wave_next_lane((uint64_t)me.kp);
+    uint32_t nkn = wave_next_lane(me.kn);
+    if (lane == 0) {
+        ppf = ot.pf;
+        pkp = (uint64_t)ot.kp;
+        pkn = ot.kn;
+    } else if (lane == 63) {
+        npf = ot.pf;
+        nkp = (uint64_t)ot.kp;
+        nkn = ot.kn;
+    }
+    e.first = e.live && (p == 0 || cmp_key(ppf, (const uint8_t *)pkp, pkn, me.pf, me.kp, me.kn, L0) != 0);
+    e.more = e.live && p + 1 < n && cmp_key(npf, (const uint8_t *)nkp, nkn, me.pf, me.kp, me.kn, L0) == 0;
+    return e;
+}
+// One past the last position of the key whose first two versions sit at p and p + 1 (walked from HBM).
+SDB_DEV uint64_t key_end(const MergeArgs &a, uint64_t p, const PosInfo &me, uint32_t L0) {
+    uint64_t end = p + 2;
+    for (; end < a.total; end++) {
+        const uint64_t h = a.perm[end];
+        const RunDesc &Q = a.r[run_of(a, h)];
+        const KeyAt x = key_at(Q, h - Q.base);
+        if (cmp_key(a.pfx[h], x.p, x.n, me.pf, me.kp, me.kn, L0) != 0) break;
+    }
+    return end;
+}
+
+// With a merge operator (U) retention runs over the units k_mg_chain found: an absorbed position is
+// dropped, a chain head is its chain's one entry (kind Value when the chain has a base, value = the merged
+// bytes the host uploaded; its expire_ts is the head's own, as every link of a chain carries the same).
+template <bool U>
+SDB_DEV uint8_t unit_flags(const MergeArgs &a, uint64_t q, uint8_t flags) {
+    if constexpr (U) {
+        if (a.ch.unit[q] == kUnitChainBase) flags &= (uint8_t)~SDB_FLAG_MERGE_OPERAND;
+    }
+    return flags;
+}
+template <bool U>
+SDB_DEV uint32_t unit_vlen(const MergeArgs &a, uint64_t q, uint32_t vlen) {
+    if constexpr (U) {
+        if (a.ch.unit[q] >= kUnitChain) {
+            const uint64_t g = a.ch.uinfo[q];
+            vlen = (uint32_t)(a.ch.moff[g + 1] - a.ch.moff[g]);
+        }
+    }
+    return vlen;
+}
+
+// Per merged position p: is it the first version of its key?  The merge operand check
+// (MergeOperatorRequiredIterator, merge_operator.rs:213-223; not with a merge operator, U).  The thread of
+// a key's first version then runs retention over the key's versions (U: units), newest
 // first (retention_iterator.rs:91-204 over the RetentionBuffer's BTreeMap, :381-398), writes dec[] per
 // version and sums the kept entries / key bytes / value bytes into the tile of kMergeTile positions
 // each version lies in (k_mg_lcp0 zeroed the tile sums; one atomic per workgroup and field, a version
-// past the workgroup's tile adds on its own).  Lanes hold consecutive positions: the neighbours' keys
-// come by DPP (lanes 0 / 63 gather theirs alongside their own), and a key with one version (the common
-// case) is decided from the lane's own gathers.
+// past the workgroup's tile adds on its own).  A key with one version (the common case) is decided from
+// the lane's own gathers (key_edge).
+template <bool U>
 __global__ __launch_bounds__(kPfxThreads) void k_mg_keys(MergeArgs a) {
     __shared__ unsigned long long s_sum[3];
     const uint32_t tid = threadIdx.x, lane = tid & 63;
@@ -329,39 +403,22 @@ __global__ __launch_bounds__(kPfxThreads) void k_mg_keys(MergeArgs a) {
     uint64_t c = 0, kb = 0, vb = 0;  // this workgroup's tile
     if (*a.err == ~0ull && a.total) {  // (uniform: the DPP exchanges below run on every lane)
         const uint32_t L0 = *a.lcp0;
-        const uint64_t n = a.total;
-        const bool live = p < n;
-        // lane 0 also gathers position p - 1, lane 63 position p + 1 (the others re-read their own)
-        const uint64_t qo = lane == 0 ? (p > 0 ? p - 1 : p) : lane == 63 ? (p + 1 < n ? p + 1 : p) : p;
-        // both gathers unconditional (a lane past the end reads position n - 1): under a branch the
-        // compiler waited for the first gather's loads before issuing the second's
-        const uint64_t pc = live ? p : n - 1, qc = live ? qo : n - 1;
-        const PosInfo me = pos_info(a, pc), ot = pos_info(a, qc);
-        uint64_t ppf = wave_prev_lane(me.pf), pkp = wave_prev_lane((uint64_t)me.kp);
-        uint32_t pkn = wave_prev_lane(me.kn);
-        uint64_t npf = wave_next_lane(me.pf), nkp = wave_next_lane((uint64_t)me.kp);
-        uint32_t nkn = wave_next_lane(me.kn);
-        if (lane == 0) {
-            ppf = ot.pf;
-            pkp = (uint64_t)ot.kp;
-            pkn = ot.kn;
-        } else if (lane == 63) {
-            npf = ot.pf;
-            nkp = (uint64_t)ot.kp;
-            nkn = ot.kn;
-        }
+        const KeyEdge edge = key_edge(a, p, lane, L0);
+        const bool live = edge.live;
+        PosInfo me = edge.me;
         if (live && a.raw) {  // a group of a job's runs merged ahead of the job (no retention): keep it
             a.dec[p] = 1;
             c = 1;
             kb = me.kn;
             vb = (me.flags & SDB_FLAG_TOMBSTONE) ? 0 : me.vlen;
         } else if (live) {
-            if (!a.ret.merge_operands && (me.flags & SDB_FLAG_MERGE_OPERAND))
+            if (!U && !a.ret.merge_operands && (me.flags & SDB_FLAG_MERGE_OPERAND))
                 report_error(a.err_merge, p, SDB_MERGE_OPERATOR_MISSING);
-            const bool first = p == 0 || cmp_key(ppf, (const uint8_t *)pkp, pkn, me.pf, me.kp, me.kn, L0) != 0;
-            const bool more = p + 1 < n && cmp_key(npf, (const uint8_t *)nkp, nkn, me.pf, me.kp, me.kn, L0) == 0;
+            const bool first = edge.first, more = edge.more;
             const sdb_retention &rt = a.ret;
             if (first && !more) {  // one version: it is the newest, so only expiry and the tombstone filter apply
+                me.flags = unit_flags<U>(a, p, me.flags);
+                me.vlen = unit_vlen<U>(a, p, me.vlen);
                 uint8_t d = 1;
                 if ((me.flags & SDB_FLAG_HAS_EXPIRE_TS) && (me.ets_src ? *me.ets_src : 0) <= rt.compaction_start_ts) {
                     const bool is_merge = (me.flags & SDB_FLAG_MERGE_OPERAND) != 0;
@@ -376,23 +433,24 @@ __global__ __launch_bounds__(kPfxThreads) void k_mg_keys(MergeArgs a) {
                     vb = (d == 1 && !(me.flags & SDB_FLAG_TOMBSTONE)) ? me.vlen : 0;
                 }
             } else if (first) {  // several versions: walk them from HBM
-                auto same = [&](uint64_t q) {  // position q holds this key
-                    const uint64_t h = a.perm[q];
-                    const RunDesc &Q = a.r[run_of(a, h)];
-                    const KeyAt x = key_at(Q, h - Q.base);
-                    return cmp_key(a.pfx[h], x.p, x.n, me.pf, me.kp, me.kn, L0) == 0;
-                };
-                uint64_t end = p + 2;
-                while (end < n && same(end)) end++;
+                const uint64_t end = key_end(a, p, me, L0);
                 uint64_t nv = 0, nm = 0;
                 bool broken = false;
-                Ver cur = ver_at(a, p);
-                for (uint64_t q = p; q < end; q++) {
+                auto ver = [&](uint64_t q) {
+                    Ver v = ver_at(a, q);
+                    v.flags = unit_flags<U>(a, q, v.flags);
+                    return v;
+                };
+                Ver cur = ver(p);
+                for (uint64_t q = p, qn; q < end; q = qn) {
+                    qn = q + 1;  // the next version (U: unit; the positions a chain absorbed are dropped)
+                    if constexpr (U)
+                        for (; qn < end && a.ch.unit[qn] == kUnitAbsorbed; qn++) a.dec[qn] = 0;
                     Ver nxt{};
-                    if (q + 1 < end) nxt = ver_at(a, q + 1);
+                    if (qn < end) nxt = ver(qn);
                     uint8_t d = 0;
                     // a later version with the same seq replaces this one (BTreeMap::insert)
-                    if (!broken && !(q + 1 < end && nxt.seq == cur.seq)) {
+                    if (!broken && !(qn < end && nxt.seq == cur.seq)) {
                         const bool is_merge = (cur.flags & SDB_FLAG_MERGE_OPERAND) != 0;
                         bool skip = false;
                         d = 1;
@@ -432,7 +490,7 @@ __global__ __launch_bounds__(kPfxThreads) void k_mg_keys(MergeArgs a) {
                     const uint64_t h = a.perm[q];
                     const RunDesc &Q = a.r[run_of(a, h)];
                     const uint64_t qi = h - Q.base;
-                    const uint64_t v = (d == 1 && !(Q.flags[qi] & SDB_FLAG_TOMBSTONE)) ? Q.val_len[qi] : 0;
+                    const uint64_t v = (d == 1 && !(Q.flags[qi] & SDB_FLAG_TOMBSTONE)) ? unit_vlen<U>(a, q, Q.val_len[qi]) : 0;
                     const uint64_t T = q / kMergeTile;
                     if (T == T0) {
                         c++;
@@ -510,6 +568,141 @@ __global__ __launch_bounds__(kMergeThreads) void k_mg_scan(MergeArgs a) {
         a.out.key_off[carry[0]] = carry[1];
         a.out.val_off[carry[0]] = carry[2];
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Operand chains (a compaction with a merge operator): MergeOperatorIterator with
+// merge_different_expire_ts = false and snapshot_barrier_seq = retention_min_seq, between the merged
+// order and retention (merge_operator.rs:324-485, compactor_executor.rs:390-400).
+// ------------------------------------------------------------------------------------------------
+struct LinkAt {
+    uint64_t seq;
+    int64_t ets, cts;
+    uint32_t vlen;
+    uint8_t flags;
+};
+SDB_DEV LinkAt link_at(const MergeArgs &a, uint64_t p) {
+    const uint64_t g = a.perm[p];
+    const RunDesc &R = a.r[run_of(a, g)];
+    const uint64_t i = g - R.base;
+    LinkAt v;
+    v.seq = R.seq[i];
+    v.flags = R.flags[i];
+    v.vlen = (v.flags & SDB_FLAG_TOMBSTONE) ? 0 : R.val_len[i];
+    v.ets = (v.flags & SDB_FLAG_HAS_EXPIRE_TS) ? R.expire_ts[i] : 0;
+    v.cts = (v.flags & SDB_FLAG_HAS_CREATE_TS) ? R.create_ts[i] : 0;
+    return v;
+}
+// a merge operand at or under the barrier opens a chain (merge_operator.rs:463-472)
+SDB_DEV bool opens_chain(const sdb_retention &rt, uint8_t flags, uint64_t seq) {
+    return (flags & SDB_FLAG_MERGE_OPERAND) && !(rt.has_min_seq && seq > rt.min_seq);
+}
+
+// Per merged position: its unit code.  As in k_mg_keys the thread of a key's first version decides the
+// key: one version from the lane's own gathers (a lone operand at or under the barrier is a chain of one
+// link), several by a walk over them in the merged order, which is the order MergeOperatorIterator sees
+// (before retention's equal-seq replacement).  A chain head also gets its link count and its links' value
+// bytes, and adds itself to the sums of the tile its position lies in (the memset before the launch
+// zeroed them): groups, links, link value bytes, key bytes.
+__global__ __launch_bounds__(kPfxThreads) void k_mg_chain(MergeArgs a) {
+    __shared__ unsigned long long s_sum[4];
+    const uint32_t tid = threadIdx.x, lane = tid & 63;
+    if (tid < 4) s_sum[tid] = 0;
+    __syncthreads();
+    const uint64_t p0 = (uint64_t)blockIdx.x * kPfxThreads, p = p0 + tid, T0 = p0 / kMergeTile;
+    const ChainArgs &ch = a.ch;
+    unsigned long long *ts = (unsigned long long *)ch.tile_sum;
+    uint64_t sg = 0, sl = 0, sb = 0, sk = 0;  // this workgroup's tile
+    if (*a.err == ~0ull && a.total) {  // (uniform: key_edge's DPP exchanges run on every lane)
+        const uint32_t L0 = *a.lcp0;
+        const KeyEdge edge = key_edge(a, p, lane, L0);
+        const PosInfo &me = edge.me;
+        const sdb_retention &rt = a.ret;
+        if (edge.first && !edge.more) {
+            const bool head = opens_chain(rt, me.flags, me.seq);
+            ch.unit[p] = head ? kUnitChain : kUnitPass;
+            if (head) {
+                ch.uinfo[p] = 1;
+                ch.ubytes[p] = me.vlen;
+                sg = 1, sl = 1, sb = me.vlen, sk = me.kn;
+            }
+        } else if (edge.first) {
+            const uint64_t end = key_end(a, p, me, L0);
+            uint64_t q = p;
+            while (q < end) {
+                const LinkAt h = link_at(a, q);
+                if (!opens_chain(rt, h.flags, h.seq)) {
+                    ch.unit[q++] = kUnitPass;
+                    continue;
+                }
+                // first_expire_ts = h's Option<expire_ts>; a version that differs ends the chain and is
+                // not consumed (is_matching_entry, :330-335, before the kind check of :392)
+                const bool he = (h.flags & SDB_FLAG_HAS_EXPIRE_TS) != 0;
+                uint64_t nl = 1, lb = h.vlen, r = q + 1;
+                bool base = false;
+                while (r < end && !base) {
+                    const LinkAt w = link_at(a, r);
+                    const bool we = (w.flags & SDB_FLAG_HAS_EXPIRE_TS) != 0;
+                    if (we != he || (he && w.ets != h.ets)) break;
+                    base = !(w.flags & SDB_FLAG_MERGE_OPERAND);  // a value or a tombstone: consumed as the base
+                    ch.unit[r++] = kUnitAbsorbed;
+                    nl++;
+                    lb += w.vlen;
+                }
+                ch.unit[q] = base ? kUnitChainBase : kUnitChain;
+                ch.uinfo[q] = nl;
+                ch.ubytes[q] = lb;
+                if (q / kMergeTile == T0) {
+                    sg++, sl += nl, sb += lb, sk += me.kn;
+                } else {
+                    unsigned long long *t = ts + 4 * (q / kMergeTile);
+                    atomicAdd(&t[0], 1ull);
+                    atomicAdd(&t[1], (unsigned long long)nl);
+                    atomicAdd(&t[2], (unsigned long long)lb);
+                    atomicAdd(&t[3], (unsigned long long)me.kn);
+                }
+                q = r;
+            }
+        }
+    }
+    sg = wave_sum(sg);
+    sl = wave_sum(sl);
+    sb = wave_sum(sb);
+    sk = wave_sum(sk);
+    if (lane == 0 && sg) {
+        atomicAdd(&s_sum[0], (unsigned long long)sg);
+        atomicAdd(&s_sum[1], (unsigned long long)sl);
+        atomicAdd(&s_sum[2], (unsigned long long)sb);
+        atomicAdd(&s_sum[3], (unsigned long long)sk);
+    }
+    __syncthreads();
+    if (tid < 4 && s_sum[tid]) atomicAdd(&ts[4 * T0 + tid], s_sum[tid]);
+}
+
+// One workgroup: exclusive tile offsets of the chain sums, and the chain summary (zeros when the merge
+// failed: no chain is read then).
+__global__ __launch_bounds__(kMergeThreads) void k_mg_chain_scan(MergeArgs a) {
+    __shared__ uint64_t s_w[17];
+    const ChainArgs &ch = a.ch;
+    uint64_t carry[4] = {0, 0, 0, 0};
+    if (*a.err == ~0ull) {
+        for (uint32_t base = 0; base < a.ntiles; base += kMergeThreads) {
+            const uint32_t t = base + threadIdx.x;
+#pragma unroll
+            for (int f = 0; f < 4; f++) {
+                const uint64_t v = t < a.ntiles ? ch.tile_sum[4 * (uint64_t)t + f] : 0;
+                uint64_t tot;
+                const uint64_t ex = block_excl_scan_u64(v, s_w, &tot);
+                if (t < a.ntiles) ch.tile_sum[4 * (uint64_t)t + f] = carry[f] + ex;
+                carry[f] += tot;
+            }
+        }
+    }
+    if (threadIdx.x) return;
+    ch.summary->groups = carry[0];
+    ch.summary->links = carry[1];
+    ch.summary->link_bytes = carry[2];
+    ch.summary->key_bytes = carry[3];
 }
 
 // Unaligned vector / scalar accesses for byte ranges at any alignment (unaligned global access is
@@ -661,6 +854,7 @@ struct EntIn {
     uint32_t kb, vb, run, i;  // timestamps (rare) are read at the store from (run, i)
     uint8_t d, f;
 };
+template <bool U>
 SDB_DEV void ent_load(const MergeArgs &a, uint64_t p, EntIn &x) {
     x.d = 0;
     x.kb = x.vb = 0;
@@ -680,6 +874,13 @@ SDB_DEV void ent_load(const MergeArgs &a, uint64_t p, EntIn &x) {
     x.vs = R.val_base + R.val_off[i];
     x.seq = R.seq[i];
     x.vb = (x.d == 1 && !(x.f & SDB_FLAG_TOMBSTONE)) ? vl : 0;
+    if constexpr (U) {  // a chain head: the chain's kind, and its merged value in the uploaded arena
+        if (a.ch.unit[p] >= kUnitChain) {
+            x.f = unit_flags<U>(a, p, x.f);
+            x.vs = a.ch.mval + a.ch.moff[a.ch.uinfo[p]];
+            x.vb = x.d == 1 ? unit_vlen<U>(a, p, vl) : 0;
+        }
+    }
 }
 
 // Columns from each thread's kPerT consecutive positions; the key / value bytes then move half a tile at
@@ -687,6 +888,7 @@ SDB_DEV void ent_load(const MergeArgs &a, uint64_t p, EntIn &x) {
 // the output is written as one stream per wave (a thread's strided entries left lines half-written).
 constexpr uint32_t kCopyHalf = kMergeTile / 2;
 
+template <bool U>
 __global__ __launch_bounds__(kMergeThreads) void k_mg_emit(MergeArgs a) {
     if (a.out.summary->status != SDB_OK) return;
     __shared__ uint64_t s_w[17];
@@ -694,7 +896,7 @@ __global__ __launch_bounds__(kMergeThreads) void k_mg_emit(MergeArgs a) {
     const uint64_t p0 = (uint64_t)blockIdx.x * kMergeTile + (uint64_t)threadIdx.x * kPerT;
     EntIn x[kPerT];
 #pragma unroll
-    for (uint32_t u = 0; u < kPerT; u++) ent_load(a, p0 + u, x[u]);
+    for (uint32_t u = 0; u < kPerT; u++) ent_load<U>(a, p0 + u, x[u]);
     uint64_t c = 0, kb = 0, vb = 0, tot;
 #pragma unroll
     for (uint32_t u = 0; u < kPerT; u++) {
@@ -717,7 +919,19 @@ __global__ __launch_bounds__(kMergeThreads) void k_mg_emit(MergeArgs a) {
         uint8_t mask = 0;
         if (e.f & SDB_FLAG_HAS_CREATE_TS) mask |= SDB_TS_CREATE;
         if ((e.f & SDB_FLAG_HAS_EXPIRE_TS) && e.d == 1) mask |= SDB_TS_EXPIRE;  // converted: expire_ts None
-        {
+        bool chain = false;
+        if constexpr (U) chain = a.ch.unit[p0 + u] >= kUnitChain;
+        if (chain) {  // the timestamps MergeTracker aggregated over the chain (merge_operator.rs:262-303)
+            const ChainGroup &G = a.ch.group[a.ch.uinfo[p0 + u]];
+            mask = (uint8_t)(G.ts_mask & (e.d == 1 ? (SDB_TS_CREATE | SDB_TS_EXPIRE) : SDB_TS_CREATE));
+            o.key_off[j] = ko;
+            o.val_off[j] = vo;
+            o.kind[j] = tomb ? SDB_KIND_TOMBSTONE : (e.f & SDB_FLAG_MERGE_OPERAND) ? SDB_KIND_MERGE : SDB_KIND_VALUE;
+            o.seq[j] = e.seq;
+            o.ts_mask[j] = mask;
+            o.create_ts[j] = (mask & SDB_TS_CREATE) ? G.create_ts : 0;
+            o.expire_ts[j] = (mask & SDB_TS_EXPIRE) ? G.expire_ts : 0;
+        } else {
         o.key_off[j] = ko;
         o.val_off[j] = vo;
         o.kind[j] = tomb ? SDB_KIND_TOMBSTONE : (e.f & SDB_FLAG_MERGE_OPERAND) ? SDB_KIND_MERGE : SDB_KIND_VALUE;
@@ -759,6 +973,120 @@ __global__ __launch_bounds__(kMergeThreads) void k_mg_emit(MergeArgs a) {
             for (uint32_t xk = x0; xk < mk; xk += 128) copy_group_chunks<true>(cd, l, xk + 16 * (l & 7));
             for (uint32_t xv = x0; xv < mv; xv += 128) copy_group_chunks<false>(cd, l, xv + 16 * (l & 7));
         }
+        __syncthreads();
+    }
+}
+
+// What the host's fold reads, per kMergeTile positions: the group table and the link table (newest first)
+// of the chains whose heads lie in the tile, from each thread's kPerT consecutive positions (a head's
+// thread walks its links: consecutive merged positions), then the staging arena: the tile's group keys and
+// link values, gathered by the wave-cooperative chunk copies of k_mg_emit, 64 links (keys) per wave and
+// step.  A chain head's uinfo becomes its group.
+__global__ __launch_bounds__(kMergeThreads) void k_mg_chain_emit(MergeArgs a) {
+    __shared__ uint64_t s_w[17];
+    __shared__ CopyDesc s_cd[kMergeThreads];
+    const ChainArgs &ch = a.ch;
+    if (!ch.summary->groups) return;
+    const uint32_t tid = threadIdx.x, l = tid & 63, w = tid >> 6;
+    const uint64_t p0 = (uint64_t)blockIdx.x * kMergeTile + (uint64_t)tid * kPerT;
+    const uint64_t vbase = ch.summary->key_bytes;  // the arena: every group's key, then the link values
+    const uint8_t *kp[kPerT];
+    uint32_t kn[kPerT];
+    uint64_t nl[kPerT], ng = 0, sl = 0, sb = 0, sk = 0;
+#pragma unroll
+    for (uint32_t u = 0; u < kPerT; u++) {
+        const uint64_t p = p0 + u;
+        nl[u] = 0;
+        kn[u] = 0;
+        kp[u] = nullptr;
+        if (p >= a.total || ch.unit[p] < kUnitChain) continue;
+        const uint64_t g = a.perm[p];
+        const RunDesc &R = a.r[run_of(a, g)];
+        const KeyAt k = key_at(R, g - R.base);
+        kp[u] = k.p;
+        kn[u] = k.n;
+        nl[u] = ch.uinfo[p];
+        ng++;
+        sl += nl[u];
+        sb += ch.ubytes[p];
+        sk += k.n;
+    }
+    const uint64_t *ts = ch.tile_sum + 4 * (uint64_t)blockIdx.x;
+    uint64_t tg, tl, tot;
+    const uint64_t G0 = ts[0], L0 = ts[1];
+    uint64_t gi = G0 + block_excl_scan_u64(ng, s_w, &tg);
+    uint64_t li = L0 + block_excl_scan_u64(sl, s_w, &tl);
+    uint64_t vo = vbase + ts[2] + block_excl_scan_u64(sb, s_w, &tot);
+    uint64_t ko = ts[3] + block_excl_scan_u64(sk, s_w, &tot);
+#pragma unroll
+    for (uint32_t u = 0; u < kPerT; u++) {
+        if (!nl[u]) continue;
+        const uint64_t p = p0 + u;
+        ChainGroup G{};
+        G.head = p;
+        G.link0 = li;
+        G.nlinks = nl[u];
+        G.key_off = ko;
+        G.key_len = kn[u];
+        for (uint64_t j = 0; j < nl[u]; j++) {
+            const LinkAt v = link_at(a, p + j);
+            if (j == 0) G.seq = v.seq;
+            if (v.flags & SDB_FLAG_HAS_CREATE_TS) {
+                G.create_ts = (G.ts_mask & SDB_TS_CREATE) && G.create_ts > v.cts ? G.create_ts : v.cts;
+                G.ts_mask |= SDB_TS_CREATE;
+            }
+            if (v.flags & SDB_FLAG_HAS_EXPIRE_TS) {
+                G.expire_ts = (G.ts_mask & SDB_TS_EXPIRE) && G.expire_ts < v.ets ? G.expire_ts : v.ets;
+                G.ts_mask |= SDB_TS_EXPIRE;
+            }
+            if (!(v.flags & SDB_FLAG_MERGE_OPERAND))  // the base: the chain's last link
+                G.base = (v.flags & SDB_FLAG_TOMBSTONE) ? kBaseTombstone : kBaseValue;
+            ch.link[li + j] = ChainLink{vo, p + j, v.vlen, 0};
+            vo += v.vlen;
+        }
+        ch.group[gi] = G;
+        ch.uinfo[p] = gi;
+        gi++;
+        li += nl[u];
+        ko += kn[u];
+    }
+    __syncthreads();  // the tile's tables are written: its waves gather what they list
+    constexpr uint32_t kStep = kMergeThreads;  // 64 per wave
+    CopyDesc *cd = s_cd + w * 64;
+    for (uint64_t b = 0; b < tl; b += kStep) {  // (uniform)
+        const uint64_t j = b + tid;
+        CopyDesc d{nullptr, nullptr, nullptr, nullptr, 0, 0};
+        if (j < tl) {
+            const ChainLink k = ch.link[L0 + j];
+            if (k.len) {
+                const uint64_t g = a.perm[k.pos];
+                const RunDesc &R = a.r[run_of(a, g)];
+                d.vs = R.val_base + R.val_off[g - R.base];
+                d.vd = ch.arena + k.off;
+                d.vb = k.len;
+            }
+        }
+        cd[l] = d;
+        __syncthreads();
+        const uint32_t mv = wave_max(cd[l].vb);
+        for (uint32_t x = 0; x < mv; x += 128) copy_group_chunks<false>(cd, l, x + 16 * (l & 7));
+        __syncthreads();
+    }
+    for (uint64_t b = 0; b < tg; b += kStep) {
+        const uint64_t j = b + tid;
+        CopyDesc d{nullptr, nullptr, nullptr, nullptr, 0, 0};
+        if (j < tg) {
+            const ChainGroup &G = ch.group[G0 + j];
+            const uint64_t g = a.perm[G.head];
+            const RunDesc &R = a.r[run_of(a, g)];
+            d.ks = key_at(R, g - R.base).p;
+            d.kd = ch.arena + G.key_off;
+            d.kb = G.key_len;
+        }
+        cd[l] = d;
+        __syncthreads();
+        const uint32_t mk = wave_max(cd[l].kb);
+        for (uint32_t x = 0; x < mk; x += 128) copy_group_chunks<true>(cd, l, x + 16 * (l & 7));
         __syncthreads();
     }
 }
@@ -1054,10 +1382,11 @@ sdb_status build_merge_args(const sdb_run *runs, uint32_t nruns, const sdb_reten
     return SDB_OK;
 }
 
-hipError_t launch_merge(const MergeArgs &a, bool emit, hipStream_t st) {
+// The merged order: perm (and the run-order check).  Returns the k_mg_prefix-sized grid (0: no entries).
+static uint32_t launch_merge_order(const MergeArgs &a, hipStream_t st) {
     if (hipMemsetAsync(a.err, 0xFF, 8, st) != hipSuccess || hipMemsetAsync(a.err_merge, 0xFF, 8, st) != hipSuccess ||
         hipMemsetAsync(a.metric, 0, 16, st) != hipSuccess)
-        return hipErrorUnknown;
+        return ~0u;
     const uint32_t gb = (uint32_t)((a.total + kPfxThreads - 1) / kPfxThreads);
     if (gb) {
         hipLaunchKernelGGL(k_mg_lcp0, dim3(1), dim3(256), 0, st, a);
@@ -1065,17 +1394,50 @@ hipError_t launch_merge(const MergeArgs &a, bool emit, hipStream_t st) {
         const uint64_t nb = (uint64_t)gb * 2 * a.nruns;
         hipLaunchKernelGGL(k_mg_bounds, dim3((uint32_t)((nb + 255) / 256)), dim3(256), 0, st, a);
         hipLaunchKernelGGL(k_mg_rank, dim3(gb), dim3(kPfxThreads), 0, st, a);
-        hipLaunchKernelGGL(k_mg_keys, dim3(gb), dim3(kPfxThreads), 0, st, a);
     }
+    return gb;
+}
+
+hipError_t launch_merge(const MergeArgs &a, bool emit, hipStream_t st) {
+    const uint32_t gb = launch_merge_order(a, st);
+    if (gb == ~0u) return hipErrorUnknown;
+    if (gb) hipLaunchKernelGGL(k_mg_keys<false>, dim3(gb), dim3(kPfxThreads), 0, st, a);
     hipLaunchKernelGGL(k_mg_scan, dim3(1), dim3(kMergeThreads), 0, st, a);
-    if (emit && a.ntiles) hipLaunchKernelGGL(k_mg_emit, dim3(a.ntiles), dim3(kMergeThreads), 0, st, a);
+    if (emit && a.ntiles) hipLaunchKernelGGL(k_mg_emit<false>, dim3(a.ntiles), dim3(kMergeThreads), 0, st, a);
     return hipGetLastError();
 }
 
 // The emit alone, after launch_merge(a, false) sized the output with unbounded capacities (the
 // caller then points a.out at buffers of exactly the reported sizes).
 hipError_t launch_merge_emit(const MergeArgs &a, hipStream_t st) {
-    if (a.ntiles) hipLaunchKernelGGL(k_mg_emit, dim3(a.ntiles), dim3(kMergeThreads), 0, st, a);
+    if (a.ntiles) hipLaunchKernelGGL(k_mg_emit<false>, dim3(a.ntiles), dim3(kMergeThreads), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_merge_chains(const MergeArgs &a, hipStream_t st) {
+    const uint32_t gb = launch_merge_order(a, st);
+    if (gb == ~0u || hipMemsetAsync(a.ch.tile_sum, 0, 32 * ((uint64_t)a.ntiles + 1), st) != hipSuccess)
+        return hipErrorUnknown;
+    if (gb) hipLaunchKernelGGL(k_mg_chain, dim3(gb), dim3(kPfxThreads), 0, st, a);
+    hipLaunchKernelGGL(k_mg_chain_scan, dim3(1), dim3(kMergeThreads), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_chain_tables(const MergeArgs &a, hipStream_t st) {
+    if (a.ntiles) hipLaunchKernelGGL(k_mg_chain_emit, dim3(a.ntiles), dim3(kMergeThreads), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_merge_units(const MergeArgs &a, bool emit, hipStream_t st) {
+    const uint32_t gb = (uint32_t)((a.total + kPfxThreads - 1) / kPfxThreads);
+    if (gb) hipLaunchKernelGGL(k_mg_keys<true>, dim3(gb), dim3(kPfxThreads), 0, st, a);
+    hipLaunchKernelGGL(k_mg_scan, dim3(1), dim3(kMergeThreads), 0, st, a);
+    if (emit && a.ntiles) hipLaunchKernelGGL(k_mg_emit<true>, dim3(a.ntiles), dim3(kMergeThreads), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_merge_emit_units(const MergeArgs &a, hipStream_t st) {
+    if (a.ntiles) hipLaunchKernelGGL(k_mg_emit<true>, dim3(a.ntiles), dim3(kMergeThreads), 0, st, a);
     return hipGetLastError();
 }
 

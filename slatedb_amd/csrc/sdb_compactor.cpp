@@ -7,6 +7,11 @@
 //                            retention + emit into buffers sized by the inputs' SstStats -> SST cuts over the
 //                            merged stream padded to the input count -> sdb_encode_ssts; two host
 //                            synchronisations (merged count + cuts together, summaries).
+//   sdb_compactor_run_merge / sdb_compactor_run_ssts_merge: the same jobs with the user's merge operator
+//                            between the merged order and retention (chain_step): the device finds the operand
+//                            chains and gathers their bytes, the host folds each chain through the operator,
+//                            and retention, cuts and encode run over the collapsed stream; two more host
+//                            synchronisations (the chain summary; the chain tables, only when there is a chain).
 // The outputs stay in the handle's device memory; every SST of the job is encoded by one launch sequence
 // per 8 SSTs.  The handle's buffers (DevBuf, PinBuf) and every layout inside them come from sdb_host.h.
 #include <hip/hip_runtime.h>
@@ -27,11 +32,54 @@ struct GroupBufs {  // a group of runs merged ahead of the job (runs beyond SDB_
     DevBuf cols, keys, vals, asrun;
 };
 
+// A device buffer of the merge-operator step.  With canaries on (sdb_diag_compactor_canaries) every ensure()
+// allocates exactly the bytes asked for between two guard bands and fills all of it with 0xA5, so a test sees
+// a write outside the sized regions, or a kernel that relies on zeroed memory.
+struct GuardBuf {
+    static constexpr uint64_t kGuard = 512;
+    DevBuf buf;
+    uint64_t bytes = 0;
+    bool guarded = false;
+    bool ensure(uint64_t n, bool guard) {
+        if (!guard) {
+            guarded = false;
+            return buf.ensure(n);
+        }
+        buf.release();
+        guarded = false;
+        if (!buf.ensure(n + 2 * kGuard) || hipMemset(buf.p, 0xA5, buf.cap) != hipSuccess ||
+            hipDeviceSynchronize() != hipSuccess)
+            return false;
+        bytes = n;
+        guarded = true;
+        return true;
+    }
+    uint8_t *base() const { return buf.at<uint8_t>(guarded ? kGuard : 0); }
+    // guard bytes that changed (the slack behind the sized bytes counts as guard), or -1
+    int64_t damaged() const {
+        if (!guarded) return 0;
+        std::vector<uint8_t> h(buf.cap);
+        if (hipMemcpy(h.data(), buf.p, buf.cap, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+        int64_t bad = 0;
+        for (uint64_t i = 0; i < buf.cap; i++)
+            if ((i < kGuard || i >= kGuard + bytes) && h[i] != 0xA5) bad++;
+        return bad;
+    }
+};
+
 struct sdb_compactor {
     int device = 0;
     DevBuf merge_ws, cols, keys, vals, cut_ws, cuts, sst_meta, sst_data, sst_bloom, enc_ws, dec, dec_ws, cx_tab;
     std::vector<GroupBufs> groups;
     PinBuf pin, pin_tab;
+    // the merge-operator step: per-position chain state, the chain tables + staging arena (device and pinned
+    // mirror), the merged values (pinned, then device)
+    GuardBuf chain_ws, chain_tab, chain_up;
+    PinBuf pin_chain, pin_up;
+    hipEvent_t up_ev = nullptr;  // the upload of pin_up: the next job waits for it before it rewrites pin_up
+    bool up_ev_live = false;
+    bool canaries = false;
+    sdb_merge_op_stats mstats{};
     // recorded on the job's stream when a run_ssts job returns (every path): the next job waits for it
     // before it rewrites pin_tab / cx_tab, which that job's upload and kernels may still be reading
     hipEvent_t tab_ev = nullptr;
@@ -45,6 +93,8 @@ struct sdb_compactor {
         (void)hipSetDevice(device);
         if (tab_ev) (void)hipEventSynchronize(tab_ev);
         if (tab_ev) (void)hipEventDestroy(tab_ev);
+        if (up_ev) (void)hipEventSynchronize(up_ev);
+        if (up_ev) (void)hipEventDestroy(up_ev);
     }
 };
 
@@ -163,6 +213,136 @@ sdb_status group_runs(sdb_compactor *c, const sdb_run *runs, uint32_t nruns, con
     return SDB_OK;
 }
 
+// One chain through the operator as MergeOperatorIterator::merge_with_older_entries does it
+// (merge_operator.rs:341-447; slatedb_amd/merge.py fold): the operands, newest first, in batches of
+// MERGE_BATCH_SIZE, each batch reversed to oldest first and merged with no existing value; the batch results,
+// reversed to oldest first, merged once with the base.  Appends the merged value to `out`.
+constexpr uint32_t kMergeBatch = 100;  // merge_operator.rs:194
+bool fold_chain(sdb_merge_batch_fn op, void *ctx, const uint8_t *key, uint64_t key_len,
+                const std::vector<const uint8_t *> &vals, const std::vector<uint64_t> &lens, const uint8_t *base,
+                uint64_t base_len, std::vector<uint8_t> &out, uint64_t *calls) {
+    std::vector<std::vector<uint8_t>> results;
+    std::vector<const uint8_t *> bp;
+    std::vector<uint64_t> bl;
+    const uint64_t m = vals.size();
+    for (uint64_t i = 0; i < m; i += kMergeBatch) {
+        const uint64_t e = std::min<uint64_t>(m, i + kMergeBatch);
+        bp.clear();
+        bl.clear();
+        for (uint64_t j = e; j-- > i;) {
+            bp.push_back(vals[j]);
+            bl.push_back(lens[j]);
+        }
+        const uint8_t *r = nullptr;
+        uint64_t rl = 0;
+        ++*calls;
+        if (op(ctx, key, key_len, nullptr, 0, bp.data(), bl.data(), (uint32_t)bp.size(), &r, &rl) != 0 || (rl && !r))
+            return false;
+        results.emplace_back(r, r + rl);  // copied at once: *result lives until the next call
+    }
+    bp.clear();
+    bl.clear();
+    for (uint64_t j = results.size(); j-- > 0;) {
+        bp.push_back(results[j].data());
+        bl.push_back(results[j].size());
+    }
+    const uint8_t *r = nullptr;
+    uint64_t rl = 0;
+    ++*calls;
+    if (op(ctx, key, key_len, base, base ? base_len : 0, bp.data(), bl.data(), (uint32_t)bp.size(), &r, &rl) != 0 ||
+        (rl && !r))
+        return false;
+    out.insert(out.end(), r, r + rl);
+    return true;
+}
+
+// The merge-operator step of a job, between the merged order and retention: a's merged order and unit codes
+// (one synchronisation: the chain summary), then, when there is a chain, the chain tables and the staging
+// arena to pinned memory (one synchronisation), the fold of every chain through `op`, and the merged values
+// and their offsets back to the device (a.ch.moff / mval; asynchronous, from pin_up).  Leaves the job's chain
+// counts in c->mstats.  An operator failure: SDB_MERGE_OPERATOR_ERROR, with c->msum filled.
+sdb_status chain_step(sdb_compactor *c, MergeArgs &a, sdb_merge_batch_fn op, void *ctx, hipStream_t s) {
+    if (!c->chain_ws.ensure(chain_bind(a.ch, a.total, nullptr), c->canaries)) return SDB_DEVICE_ERROR;
+    chain_bind(a.ch, a.total, c->chain_ws.base());
+    ChainSummary cs{};
+    if (launch_merge_chains(a, s) != hipSuccess ||
+        hipMemcpyAsync(&cs, a.ch.summary, sizeof(cs), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return SDB_DEVICE_ERROR;
+    sdb_merge_op_stats &ms = c->mstats;
+    ms.groups = cs.groups;
+    ms.links = cs.links;
+    ms.link_bytes = cs.link_bytes;
+    if (!cs.groups) return SDB_OK;  // no chain: no copy, no operator call
+
+    const uint64_t tab_bytes = chain_tables_bind(a.ch, cs, nullptr);
+    if (!c->chain_tab.ensure(tab_bytes, c->canaries) || !c->pin_chain.ensure(tab_bytes)) return SDB_DEVICE_ERROR;
+    chain_tables_bind(a.ch, cs, c->chain_tab.base());
+    if (launch_chain_tables(a, s) != hipSuccess ||
+        hipMemcpyAsync(c->pin_chain.p, c->chain_tab.base(), tab_bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return SDB_DEVICE_ERROR;
+    ChainArgs h{};  // the tables' host mirror
+    chain_tables_bind(h, cs, c->pin_chain.at<uint8_t>(0));
+
+    std::vector<uint8_t> merged;
+    std::vector<uint64_t> moff(cs.groups + 1);
+    std::vector<const uint8_t *> vals;
+    std::vector<uint64_t> lens;
+    merged.reserve(cs.link_bytes);
+    for (uint64_t g = 0; g < cs.groups; g++) {
+        const ChainGroup &G = h.group[g];
+        const uint64_t nops = G.nlinks - (G.base != kBaseNone ? 1 : 0);
+        vals.clear();
+        lens.clear();
+        for (uint64_t j = 0; j < nops; j++) {
+            const ChainLink &L = h.link[G.link0 + j];
+            vals.push_back(h.arena + L.off);
+            lens.push_back(L.len);
+        }
+        const uint8_t *base = nullptr;
+        uint64_t base_len = 0;
+        if (G.base == kBaseValue) {  // (a tombstone base has no value: None)
+            const ChainLink &L = h.link[G.link0 + nops];
+            base = h.arena + L.off;
+            base_len = L.len;
+        }
+        moff[g] = merged.size();
+        if (!fold_chain(op, ctx, h.arena + G.key_off, G.key_len, vals, lens, base, base_len, merged, &ms.operator_calls)) {
+            c->msum = sdb_merge_summary{};
+            c->msum.num_in = a.total;
+            c->msum.status = SDB_MERGE_OPERATOR_ERROR;
+            c->msum.first_error_entry = G.head;
+            return SDB_MERGE_OPERATOR_ERROR;
+        }
+        if (merged.size() - moff[g] > 0xFFFFFFFFull) return SDB_LIMIT_EXCEEDED;  // value lengths are u32
+    }
+    moff[cs.groups] = merged.size();
+    ms.merged_bytes = merged.size();
+
+    // the upload: offsets, then bytes (+ 16: the emit's 16-byte chunk loads stay inside)
+    Carver uc{nullptr, 0};
+    const uint64_t u_off = uc.bytes(8 * (cs.groups + 1)), u_val = uc.bytes(merged.size() + 16);
+    if (c->up_ev_live && hipEventSynchronize(c->up_ev) != hipSuccess) return SDB_DEVICE_ERROR;
+    c->up_ev_live = false;
+    if (!c->up_ev && hipEventCreateWithFlags(&c->up_ev, hipEventDisableTiming) != hipSuccess) {
+        c->up_ev = nullptr;
+        return SDB_DEVICE_ERROR;
+    }
+    if (!c->chain_up.ensure(uc.off, c->canaries) || !c->pin_up.ensure(uc.off)) return SDB_DEVICE_ERROR;
+    memcpy(c->pin_up.at<uint8_t>(u_off), moff.data(), 8 * (cs.groups + 1));
+    if (!merged.empty()) memcpy(c->pin_up.at<uint8_t>(u_val), merged.data(), merged.size());
+    memset(c->pin_up.at<uint8_t>(u_val) + merged.size(), 0, 16);
+    uint8_t *up = c->chain_up.base();
+    if (hipMemcpyAsync(up + u_off, c->pin_up.at<uint8_t>(u_off), 8 * (cs.groups + 1), hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(up + u_val, c->pin_up.at<uint8_t>(u_val), merged.size() + 16, hipMemcpyHostToDevice, s) != hipSuccess)
+        return SDB_DEVICE_ERROR;
+    c->up_ev_live = hipEventRecord(c->up_ev, s) == hipSuccess;
+    a.ch.moff = reinterpret_cast<const uint64_t *>(up + u_off);
+    a.ch.mval = up + u_val;
+    return SDB_OK;
+}
+
 sdb_kv_batch batch_of(const sdb_merged_out &o, uint64_t n) {
     sdb_kv_batch m{};
     m.n = n;
@@ -264,13 +444,20 @@ sdb_compactor *sdb_compactor_create(int device) {
 
 void sdb_compactor_destroy(sdb_compactor *c) { delete c; }
 
-sdb_status sdb_compactor_run(sdb_compactor *c, const sdb_run *runs, uint32_t nruns, const sdb_retention *ret,
-                             const sdb_sst_params *params, uint64_t max_sst_size, void *stream, uint32_t *num_ssts) {
+}  // extern "C"
+
+namespace {
+
+// sdb_compactor_run (op == NULL) / sdb_compactor_run_merge
+sdb_status run_job(sdb_compactor *c, const sdb_run *runs, uint32_t nruns, const sdb_retention *ret,
+                   sdb_merge_batch_fn op, void *ctx, const sdb_sst_params *params, uint64_t max_sst_size,
+                   void *stream, uint32_t *num_ssts) {
     if (!c || !params || !num_ssts) return SDB_INVALID_ARGUMENT;
     *num_ssts = 0;
     c->ssts.clear();
     c->merged = sdb_kv_batch{};
     c->msum = sdb_merge_summary{};
+    c->mstats = sdb_merge_op_stats{};
     if (params->sst_type != SDB_SST_COMPACTED) return SDB_INVALID_ARGUMENT;  // compactions write compacted SSTs
     if ((nruns && !runs) || !ret) return SDB_INVALID_ARGUMENT;  // before group_runs reads runs[]
     if (hipSetDevice(c->device) != hipSuccess) return SDB_DEVICE_ERROR;
@@ -294,7 +481,13 @@ sdb_status sdb_compactor_run(sdb_compactor *c, const sdb_run *runs, uint32_t nru
     MergeArgs a;
     st = build_merge_args(runs, nruns, ret, &out, c->merge_ws.p, c->merge_ws.cap, &a);
     if (st) return st;
-    if (launch_merge(a, false, s) != hipSuccess) return SDB_DEVICE_ERROR;
+    if (op) {  // chains, the operator, then retention over the units
+        st = chain_step(c, a, op, ctx, s);
+        if (st) return st;
+        if (launch_merge_units(a, false, s) != hipSuccess) return SDB_DEVICE_ERROR;
+    } else if (launch_merge(a, false, s) != hipSuccess) {
+        return SDB_DEVICE_ERROR;
+    }
     if (hipMemcpyAsync(&c->msum, out.summary, sizeof(sdb_merge_summary), hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
         return SDB_DEVICE_ERROR;
@@ -304,7 +497,7 @@ sdb_status sdb_compactor_run(sdb_compactor *c, const sdb_run *runs, uint32_t nru
     a.out.key_cap = c->msum.key_bytes;
     a.out.val_bytes = c->vals.at<uint8_t>(0);
     a.out.val_cap = c->msum.val_bytes;
-    if (launch_merge_emit(a, s) != hipSuccess) return SDB_DEVICE_ERROR;
+    if ((op ? launch_merge_emit_units(a, s) : launch_merge_emit(a, s)) != hipSuccess) return SDB_DEVICE_ERROR;
     const uint64_t n = c->msum.num_out;
     sdb_kv_batch &m = c->merged;
     m = batch_of(a.out, n);
@@ -343,15 +536,17 @@ sdb_status sdb_compactor_run(sdb_compactor *c, const sdb_run *runs, uint32_t nru
     return first;
 }
 
-sdb_status sdb_compactor_run_ssts(sdb_compactor *c, const sdb_compaction_input *inputs, uint32_t ninputs,
-                                  const uint32_t *run_start, uint32_t nruns, uint16_t input_sst_version,
-                                  const sdb_retention *ret, const sdb_sst_params *params, uint64_t max_sst_size,
-                                  void *stream, uint32_t *num_ssts) {
+// sdb_compactor_run_ssts (op == NULL) / sdb_compactor_run_ssts_merge
+sdb_status run_ssts_job(sdb_compactor *c, const sdb_compaction_input *inputs, uint32_t ninputs,
+                        const uint32_t *run_start, uint32_t nruns, uint16_t input_sst_version,
+                        const sdb_retention *ret, sdb_merge_batch_fn op, void *ctx, const sdb_sst_params *params,
+                        uint64_t max_sst_size, void *stream, uint32_t *num_ssts) {
     if (!c || !params || !num_ssts || !ret || (ninputs && !inputs)) return SDB_INVALID_ARGUMENT;
     *num_ssts = 0;
     c->ssts.clear();
     c->merged = sdb_kv_batch{};
     c->msum = sdb_merge_summary{};
+    c->mstats = sdb_merge_op_stats{};
     if (params->sst_type != SDB_SST_COMPACTED) return SDB_INVALID_ARGUMENT;
     if (input_sst_version != 1 && input_sst_version != 2) return SDB_INVALID_VERSION;
     if (!run_start) nruns = ninputs;
@@ -488,10 +683,10 @@ sdb_status sdb_compactor_run_ssts(sdb_compactor *c, const sdb_compaction_input *
     sdb_merged_out out{};
     st = merged_columns_in(c->cols, E, &out);
     if (st) return st;
-    if (!c->keys.ensure(K + 16) || !c->vals.ensure(V + 16)) return SDB_DEVICE_ERROR;
+    if (!c->keys.ensure(K + 16) || (!op && !c->vals.ensure(V + 16))) return SDB_DEVICE_ERROR;
     out.key_bytes = c->keys.at<uint8_t>(0);
     out.key_cap = K;
-    out.val_bytes = c->vals.at<uint8_t>(0);
+    out.val_bytes = op ? nullptr : c->vals.at<uint8_t>(0);  // (with an operator: sized after the fold)
     out.val_cap = V;
     const sdb_run *mruns = runs.data();
     uint32_t mn = nruns;
@@ -507,7 +702,19 @@ sdb_status sdb_compactor_run_ssts(sdb_compactor *c, const sdb_compaction_input *
     st = build_merge_args(mruns, mn, ret, &out, c->merge_ws.p, c->merge_ws.cap, &a);
     if (st) return st;
     a.gate = gate;
-    if (launch_merge(a, true, s) != hipSuccess || launch_merge_pad(out, E, s) != hipSuccess) return SDB_DEVICE_ERROR;
+    if (op) {
+        st = chain_step(c, a, op, ctx, s);
+        if (st) return st;
+        // a merged value can be longer than all of its inputs: the links' bytes leave, the merged bytes come
+        V = (V > c->mstats.link_bytes ? V - c->mstats.link_bytes : 0) + c->mstats.merged_bytes;
+        if (!c->vals.ensure(V + 16)) return SDB_DEVICE_ERROR;
+        a.out.val_bytes = out.val_bytes = c->vals.at<uint8_t>(0);
+        a.out.val_cap = out.val_cap = V;
+        if (launch_merge_units(a, true, s) != hipSuccess) return SDB_DEVICE_ERROR;
+    } else if (launch_merge(a, true, s) != hipSuccess) {
+        return SDB_DEVICE_ERROR;
+    }
+    if (launch_merge_pad(out, E, s) != hipSuccess) return SDB_DEVICE_ERROR;
     const sdb_kv_batch padded = batch_of(out, E);
 
     // cuts over the padded stream, ending at the merged count; merged summary, cut count, cuts and their
@@ -555,6 +762,57 @@ sdb_status sdb_compactor_run_ssts(sdb_compactor *c, const sdb_compaction_input *
     const sdb_status first = encode_outputs(c, cut.data(), off.data(), ns, params, stream);
     if (first == SDB_OK || c->ssts.size() == ns) *num_ssts = (uint32_t)ns;
     return first;
+}
+
+}  // namespace
+
+extern "C" {
+
+sdb_status sdb_compactor_run(sdb_compactor *c, const sdb_run *runs, uint32_t nruns, const sdb_retention *ret,
+                             const sdb_sst_params *params, uint64_t max_sst_size, void *stream, uint32_t *num_ssts) {
+    return run_job(c, runs, nruns, ret, nullptr, nullptr, params, max_sst_size, stream, num_ssts);
+}
+
+sdb_status sdb_compactor_run_merge(sdb_compactor *c, const sdb_run *runs, uint32_t nruns, const sdb_retention *ret,
+                                   sdb_merge_batch_fn op, void *ctx, const sdb_sst_params *params,
+                                   uint64_t max_sst_size, void *stream, uint32_t *num_ssts) {
+    if (!op) return SDB_INVALID_ARGUMENT;
+    return run_job(c, runs, nruns, ret, op, ctx, params, max_sst_size, stream, num_ssts);
+}
+
+sdb_status sdb_compactor_run_ssts(sdb_compactor *c, const sdb_compaction_input *inputs, uint32_t ninputs,
+                                  const uint32_t *run_start, uint32_t nruns, uint16_t input_sst_version,
+                                  const sdb_retention *ret, const sdb_sst_params *params, uint64_t max_sst_size,
+                                  void *stream, uint32_t *num_ssts) {
+    return run_ssts_job(c, inputs, ninputs, run_start, nruns, input_sst_version, ret, nullptr, nullptr, params,
+                        max_sst_size, stream, num_ssts);
+}
+
+sdb_status sdb_compactor_run_ssts_merge(sdb_compactor *c, const sdb_compaction_input *inputs, uint32_t ninputs,
+                                        const uint32_t *run_start, uint32_t nruns, uint16_t input_sst_version,
+                                        const sdb_retention *ret, sdb_merge_batch_fn op, void *ctx,
+                                        const sdb_sst_params *params, uint64_t max_sst_size, void *stream,
+                                        uint32_t *num_ssts) {
+    if (!op) return SDB_INVALID_ARGUMENT;
+    return run_ssts_job(c, inputs, ninputs, run_start, nruns, input_sst_version, ret, op, ctx, params, max_sst_size,
+                        stream, num_ssts);
+}
+
+sdb_status sdb_compactor_merge_stats(const sdb_compactor *c, sdb_merge_op_stats *stats) {
+    if (!c || !stats) return SDB_INVALID_ARGUMENT;
+    *stats = c->mstats;
+    return SDB_OK;
+}
+
+// Diagnostics (not in the header): guard bands around the buffers of the merge-operator step (GuardBuf), and
+// the guard bytes the last job changed (synchronises the device; -1: the check could not run).
+void sdb_diag_compactor_canaries(sdb_compactor *c, int on) {
+    if (c) c->canaries = on != 0;
+}
+int64_t sdb_diag_compactor_canary_damage(sdb_compactor *c) {
+    if (!c || hipSetDevice(c->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return -1;
+    const int64_t x = c->chain_ws.damaged(), y = c->chain_tab.damaged(), z = c->chain_up.damaged();
+    return x < 0 || y < 0 || z < 0 ? -1 : x + y + z;
 }
 
 sdb_status sdb_compactor_sst(const sdb_compactor *c, uint32_t i, sdb_compacted_sst *out) {

@@ -1286,6 +1286,65 @@ class Compactor:
         self.status = st
         return st, ns.value
 
+    @staticmethod
+    def _operator_callback(operator):
+        """`operator` (merge_batch(key, existing, operands) -> bytes, slatedb_amd/merge.py) as an sdb_merge_batch_fn.
+        The result of a call stays alive, in `keep`, until the next one; an exception in the operator becomes a
+        non-zero return (the job fails with SDB_MERGE_OPERATOR_ERROR) and is kept in keep["error"]."""
+        keep = {"result": None, "error": None}
+
+        def call(ctx, key, key_len, existing, existing_len, operands, operand_len, n, result, result_len):
+            try:
+                k = C.string_at(key, key_len) if key_len else b""
+                ex = None if not existing else C.string_at(existing, existing_len)
+                ops = [C.string_at(operands[i], operand_len[i]) if operand_len[i] else b"" for i in range(n)]
+                r = bytes(operator.merge_batch(k, ex, ops))
+                buf = (C.c_uint8 * max(len(r), 1)).from_buffer_copy(r or b"\0")
+                keep["result"] = buf
+                result[0] = C.cast(buf, _abi.u8p)
+                result_len[0] = len(r)
+                return 0
+            except Exception as e:  # never unwind through the C frames
+                keep["error"] = e
+                return 1
+        return _abi.MERGE_BATCH_FN(call), keep
+
+    def run_merge(self, druns, ret, operator, prm, max_sst_size, stream=None):
+        """sdb_compactor_run_merge: run() with the store's merge operator (an object with
+        merge_batch(key, existing, operands), slatedb_amd/merge.py) between the merge and retention."""
+        cr = (_abi.Run * max(len(druns), 1))(*[r.to_ctypes() for r in druns])
+        ns = C.c_uint32(0)
+        cb, self.operator_state = self._operator_callback(operator)
+        st = lib().sdb_compactor_run_merge(self.h, cr, len(druns), C.byref(ret), cb, None, C.byref(prm), max_sst_size,
+                                           _sp(stream), C.byref(ns))
+        self.status = st
+        return st, ns.value
+
+    def run_ssts_merge(self, inputs, ret, operator, prm, max_sst_size, input_version=2, run_start=None, stream=None):
+        """sdb_compactor_run_ssts_merge: run_ssts() with the store's merge operator."""
+        ci = (_abi.CompactionInput * max(len(inputs), 1))(*[
+            _abi.CompactionInput(x.data.data_ptr(), x.block_off.data_ptr(), x.block_off.numel() - 1, x.num_entries,
+                                 x.key_bytes, x.val_bytes) for x in inputs])
+        rs = None
+        nruns = len(inputs)
+        if run_start is not None:
+            rs = (C.c_uint32 * len(run_start))(*run_start)
+            nruns = len(run_start) - 1
+        ns = C.c_uint32(0)
+        cb, self.operator_state = self._operator_callback(operator)
+        st = lib().sdb_compactor_run_ssts_merge(self.h, ci, len(inputs), rs, nruns, input_version, C.byref(ret), cb,
+                                                None, C.byref(prm), max_sst_size, _sp(stream), C.byref(ns))
+        self.status = st
+        return st, ns.value
+
+    def merge_stats(self):
+        """sdb_merge_op_stats of the last job (zeros after a job without an operator)."""
+        ms = _abi.MergeOpStats()
+        st = lib().sdb_compactor_merge_stats(self.h, C.byref(ms))
+        if st:
+            raise SdbError(st, "sdb_compactor_merge_stats")
+        return ms
+
     def merged(self):
         kb, sm = _abi.KvBatch(), _abi.MergeSummary()
         st = lib().sdb_compactor_merged(self.h, C.byref(kb), C.byref(sm))
