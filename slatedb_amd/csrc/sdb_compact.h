@@ -15,7 +15,7 @@ constexpr uint32_t kMaxRuns = SDB_MAX_RUNS;
 #ifndef SDB_MERGE_THREADS
 #define SDB_MERGE_THREADS 512
 #endif
-constexpr uint32_t kMergeTile = SDB_MERGE_TILE;  // merged positions per k_mg_tiles / k_mg_emit workgroup
+constexpr uint32_t kMergeTile = SDB_MERGE_TILE;  // merged positions per tile: one k_mg_emit workgroup, one row of the tile sums
 constexpr uint32_t kMergeThreads = SDB_MERGE_THREADS;
 
 struct RunDesc {  // sdb_run + the run's first global entry index
@@ -100,7 +100,6 @@ struct MergeArgs {
     uint64_t *pfx;               // per global entry: key bytes [L0, L0 + 8), big-endian, zero padded
     uint32_t *lcp0;              // L0: the prefix every key of the (sorted) runs shares
     uint64_t *perm;              // merged position -> global entry
-    uint8_t *start;              // merged position: first version of its key
     uint8_t *dec;                // merged position: 0 drop, 1 keep, 2 keep as a tombstone
     uint64_t *tile_sum;          // per tile: kept entries, key bytes, value bytes (exclusive offsets after k_mg_scan)
     uint64_t *bound;             // per 256 entries (k_mg_rank workgroup) and side: the first / last entry's count in each run
@@ -119,7 +118,6 @@ inline uint64_t merge_bind(MergeArgs &a, uint8_t *w) {
     Carver c{w, 0};
     c.take(a.pfx, a.total + 1);
     c.take(a.perm, a.total + 1);
-    c.take(a.start, a.total + 1);
     c.take(a.dec, a.total + 1);
     c.take(a.tile_sum, 3 * (ntiles + 1));
     c.take(a.bound, 2 * (uint64_t)kMaxRuns * ((a.total + 255) / 256 + 1));  // k_mg_bounds: 2 x runs per 256 entries
@@ -135,18 +133,22 @@ sdb_status build_merge_args(const sdb_run *runs, uint32_t nruns, const sdb_reten
 // A merged stream as an sdb_run (the per-entry value lengths and RowFlags the runs carry): val_len[i],
 // flags[i] for i < n (device, written on st).
 hipError_t launch_merged_as_run(const sdb_merged_out &out, uint64_t n, uint32_t *val_len, uint8_t *flags, hipStream_t st);
-// merge + retention (+ emit when `emit`), all on `st`
-hipError_t launch_merge(const MergeArgs &a, bool emit, hipStream_t st);
+// A merge in three steps, all on `st`.  Retention and the emit run over the units of a merge operator when
+// a.ch is bound (a.ch.unit != NULL; a.ch.moff / mval uploaded), else over the entries.
+//   launch_merge_order        perm (the merged order), the run-order check
+//   launch_merge_retention    dec, the tile offsets and the summary (+ the emit when `emit`)
+//   launch_merge_emit         the emit alone, after launch_merge_retention(a, false) sized the output with
+//                             unbounded capacities (the caller then points a.out at buffers of the reported sizes)
+//   launch_merge              order + retention
+hipError_t launch_merge_order(const MergeArgs &a, hipStream_t st);
+hipError_t launch_merge_retention(const MergeArgs &a, bool emit, hipStream_t st);
 hipError_t launch_merge_emit(const MergeArgs &a, hipStream_t st);
-// A merge with an operator, in three steps around the host's fold (a.ch bound by chain_bind):
-//   launch_merge_chains       merged order, the unit code of every position, the chain summary
+hipError_t launch_merge(const MergeArgs &a, bool emit, hipStream_t st);
+// The operator step between order and retention, around the host's fold (a.ch bound by chain_bind):
+//   launch_merge_chains       order, the unit code of every position, the chain summary
 //   launch_chain_tables       group table, link table and staging arena (a.ch bound by chain_tables_bind)
-//   launch_merge_units        retention over the units (+ emit when `emit`); a.ch.moff / mval uploaded
-//   launch_merge_emit_units   the emit alone, after launch_merge_units(a, false)
 hipError_t launch_merge_chains(const MergeArgs &a, hipStream_t st);
 hipError_t launch_chain_tables(const MergeArgs &a, hipStream_t st);
-hipError_t launch_merge_units(const MergeArgs &a, bool emit, hipStream_t st);
-hipError_t launch_merge_emit_units(const MergeArgs &a, hipStream_t st);
 
 // SST cuts over the chain tables of a prep-only encode set of one slot (launch_encode_prep).  n_real
 // (device, or NULL = the slot's n): the stream's true length when the slot covers a padded stream; the

@@ -1,7 +1,9 @@
 // sdb_compact.hip — the compaction output side on the device: merge of sorted runs, retention, and
 // the SST cuts of the output stream (include/slatedb_amd.h, "Compaction").
 //
+//   k_mg_lcp0     one lane: the prefix every key shares (the 8-byte prefixes start behind it)
 //   k_mg_prefix   per input entry: 8-byte big-endian key prefix; run order check
+//   k_mg_bounds   per k_mg_rank workgroup and run: the search window of the workgroup's entries
 //   k_mg_rank     per input entry: its merged position = own index + one binary search per other run
 //                 (MergeIterator order, merge_iterator.rs:55-69: key asc, seq desc, then run)
 //   k_mg_keys     per merged position: first version of its key?; merge operand check
@@ -9,14 +11,17 @@
 //                 version's thread: apply_retention_filter (retention_iterator.rs:91-204) -> keep / drop /
 //                 keep as a tombstone per version, and the kept entries / key / value bytes per
 //                 kMergeTile positions
-//   k_mg_scan     one workgroup: tile offsets, the summary
+//   k_mg_scan     one workgroup: tile offsets (tile_scan), the summary
 //   k_mg_emit     per kMergeTile positions: the output batch (metadata + key / value bytes)
 //   k_mg_chain, k_mg_chain_scan, k_mg_chain_emit   with a merge operator, between k_mg_rank and k_mg_keys:
 //                 the operand chains of MergeOperatorIterator (merge_operator.rs:324-485) per merged
 //                 position, their tables and the bytes the host's operator reads; k_mg_keys / k_mg_emit
-//                 then run over the units (their <true> instantiations)
+//                 then run over the units (their <true> instantiations, taken when a.ch is bound)
+//   k_mg_asrun, k_mg_pad   a merged stream as a run of a later merge; its padding for the cut walk
 //   k_cut         one lane: the compactor's max_sst_size walk (compactor_executor.rs:833-858) over
 //                 the chain tables of the encoder's k_seg / k_group (group, chunk, then block steps)
+//   k_cut_offsets, k_cx_blocks, k_cx_gate   the byte offsets of the cuts; sdb_compactor_run_ssts' block list
+//                 and its gate between decode and merge
 //
 // The work here is integer / byte movement bound by HBM and by the dependent loads of the binary
 // searches; nothing is GEMM-shaped.
@@ -272,19 +277,23 @@ __global__ __launch_bounds__(kPfxThreads) void k_mg_rank(MergeArgs a) {
     a.perm[pos] = g;
 }
 
-struct Ver {
+// The version at merged position p, for the walks over a key's versions (retention, the operand chains).
+struct LinkAt {
     uint64_t seq;
-    int64_t ets;
+    int64_t ets, cts;
+    uint32_t vlen;
     uint8_t flags;
 };
-SDB_DEV Ver ver_at(const MergeArgs &a, uint64_t p) {
+SDB_DEV LinkAt link_at(const MergeArgs &a, uint64_t p) {
     const uint64_t g = a.perm[p];
     const RunDesc &R = a.r[run_of(a, g)];
     const uint64_t i = g - R.base;
-    Ver v;
+    LinkAt v;
     v.seq = R.seq[i];
     v.flags = R.flags[i];
+    v.vlen = (v.flags & SDB_FLAG_TOMBSTONE) ? 0 : R.val_len[i];
     v.ets = (v.flags & SDB_FLAG_HAS_EXPIRE_TS) ? R.expire_ts[i] : 0;
+    v.cts = (v.flags & SDB_FLAG_HAS_CREATE_TS) ? R.create_ts[i] : 0;
     return v;
 }
 
@@ -437,16 +446,16 @@ __global__ __launch_bounds__(kPfxThreads) void k_mg_keys(MergeArgs a) {
                 uint64_t nv = 0, nm = 0;
                 bool broken = false;
                 auto ver = [&](uint64_t q) {
-                    Ver v = ver_at(a, q);
+                    LinkAt v = link_at(a, q);
                     v.flags = unit_flags<U>(a, q, v.flags);
                     return v;
                 };
-                Ver cur = ver(p);
+                LinkAt cur = ver(p);
                 for (uint64_t q = p, qn; q < end; q = qn) {
                     qn = q + 1;  // the next version (U: unit; the positions a chain absorbed are dropped)
                     if constexpr (U)
                         for (; qn < end && a.ch.unit[qn] == kUnitAbsorbed; qn++) a.dec[qn] = 0;
-                    Ver nxt{};
+                    LinkAt nxt{};
                     if (qn < end) nxt = ver(qn);
                     uint8_t d = 0;
                     // a later version with the same seq replaces this one (BTreeMap::insert)
@@ -477,7 +486,7 @@ __global__ __launch_bounds__(kPfxThreads) void k_mg_keys(MergeArgs a) {
                     for (uint64_t q = end; q-- > p;) {
                         const uint8_t d = a.dec[q];
                         if (!d) continue;
-                        if (d == 2 || (ver_at(a, q).flags & SDB_FLAG_TOMBSTONE)) a.dec[q] = 0;
+                        if (d == 2 || (link_at(a, q).flags & SDB_FLAG_TOMBSTONE)) a.dec[q] = 0;  // (the raw flags)
                         else break;
                     }
                 }
@@ -519,6 +528,23 @@ __global__ __launch_bounds__(kPfxThreads) void k_mg_keys(MergeArgs a) {
 
 constexpr uint32_t kPerT = kMergeTile / kMergeThreads;
 
+// One workgroup: the F sums of every tile (ts[F * tile + f]) become exclusive offsets, kMergeThreads tiles per
+// pass; total[f] (zero on entry) = field f over every tile.
+template <int F>
+SDB_DEV void tile_scan(uint64_t *ts, uint32_t ntiles, uint64_t *s_w, uint64_t (&total)[F]) {
+    for (uint32_t base = 0; base < ntiles; base += kMergeThreads) {
+        const uint32_t t = base + threadIdx.x;
+#pragma unroll
+        for (int f = 0; f < F; f++) {
+            const uint64_t v = t < ntiles ? ts[F * (uint64_t)t + f] : 0;
+            uint64_t tot;
+            const uint64_t ex = block_excl_scan_u64(v, s_w, &tot);
+            if (t < ntiles) ts[F * (uint64_t)t + f] = total[f] + ex;
+            total[f] += tot;
+        }
+    }
+}
+
 // One workgroup: exclusive tile offsets, the totals and the summary.
 __global__ __launch_bounds__(kMergeThreads) void k_mg_scan(MergeArgs a) {
     __shared__ uint64_t s_w[17];
@@ -527,19 +553,7 @@ __global__ __launch_bounds__(kMergeThreads) void k_mg_scan(MergeArgs a) {
     const unsigned long long e2 = *a.err_merge;
     if (e1 == ~0ull && a.gate && *a.gate != ~0ull) e1 = *a.gate;  // (no entries: k_mg_lcp0 did not run)
     uint64_t carry[3] = {0, 0, 0};
-    if (e1 == ~0ull && e2 == ~0ull) {
-        for (uint32_t base = 0; base < a.ntiles; base += kMergeThreads) {
-            const uint32_t t = base + threadIdx.x;
-#pragma unroll
-            for (int f = 0; f < 3; f++) {
-                const uint64_t v = t < a.ntiles ? a.tile_sum[3 * (uint64_t)t + f] : 0;
-                uint64_t tot;
-                const uint64_t ex = block_excl_scan_u64(v, s_w, &tot);
-                if (t < a.ntiles) a.tile_sum[3 * (uint64_t)t + f] = carry[f] + ex;
-                carry[f] += tot;
-            }
-        }
-    }
+    if (e1 == ~0ull && e2 == ~0ull) tile_scan<3>(a.tile_sum, a.ntiles, s_w, carry);
     if (threadIdx.x) return;
     // (a job that fails reports no retention counts: k_mg_keys ran its walks before the errors were known)
     const bool clean = e1 == ~0ull && e2 == ~0ull;
@@ -575,24 +589,6 @@ __global__ __launch_bounds__(kMergeThreads) void k_mg_scan(MergeArgs a) {
 // merge_different_expire_ts = false and snapshot_barrier_seq = retention_min_seq, between the merged
 // order and retention (merge_operator.rs:324-485, compactor_executor.rs:390-400).
 // ------------------------------------------------------------------------------------------------
-struct LinkAt {
-    uint64_t seq;
-    int64_t ets, cts;
-    uint32_t vlen;
-    uint8_t flags;
-};
-SDB_DEV LinkAt link_at(const MergeArgs &a, uint64_t p) {
-    const uint64_t g = a.perm[p];
-    const RunDesc &R = a.r[run_of(a, g)];
-    const uint64_t i = g - R.base;
-    LinkAt v;
-    v.seq = R.seq[i];
-    v.flags = R.flags[i];
-    v.vlen = (v.flags & SDB_FLAG_TOMBSTONE) ? 0 : R.val_len[i];
-    v.ets = (v.flags & SDB_FLAG_HAS_EXPIRE_TS) ? R.expire_ts[i] : 0;
-    v.cts = (v.flags & SDB_FLAG_HAS_CREATE_TS) ? R.create_ts[i] : 0;
-    return v;
-}
 // a merge operand at or under the barrier opens a chain (merge_operator.rs:463-472)
 SDB_DEV bool opens_chain(const sdb_retention &rt, uint8_t flags, uint64_t seq) {
     return (flags & SDB_FLAG_MERGE_OPERAND) && !(rt.has_min_seq && seq > rt.min_seq);
@@ -685,19 +681,7 @@ __global__ __launch_bounds__(kMergeThreads) void k_mg_chain_scan(MergeArgs a) {
     __shared__ uint64_t s_w[17];
     const ChainArgs &ch = a.ch;
     uint64_t carry[4] = {0, 0, 0, 0};
-    if (*a.err == ~0ull) {
-        for (uint32_t base = 0; base < a.ntiles; base += kMergeThreads) {
-            const uint32_t t = base + threadIdx.x;
-#pragma unroll
-            for (int f = 0; f < 4; f++) {
-                const uint64_t v = t < a.ntiles ? ch.tile_sum[4 * (uint64_t)t + f] : 0;
-                uint64_t tot;
-                const uint64_t ex = block_excl_scan_u64(v, s_w, &tot);
-                if (t < a.ntiles) ch.tile_sum[4 * (uint64_t)t + f] = carry[f] + ex;
-                carry[f] += tot;
-            }
-        }
-    }
+    if (*a.err == ~0ull) tile_scan<4>(ch.tile_sum, a.ntiles, s_w, carry);
     if (threadIdx.x) return;
     ch.summary->groups = carry[0];
     ch.summary->links = carry[1];
@@ -742,20 +726,6 @@ SDB_DEV void chunk_load(Chunk &c, const uint8_t *src, uint32_t n) {
     if (o) c.hi = t;
     else c.lo = t;
 }
-SDB_DEV void chunk_store(const Chunk &c, uint8_t *dst, uint32_t n) {
-    if (n >= 16) {
-        u32x4_u v;
-        v.x = (uint32_t)c.lo, v.y = (uint32_t)(c.lo >> 32), v.z = (uint32_t)c.hi, v.w = (uint32_t)(c.hi >> 32);
-        *(u32x4_u *)dst = v;
-        return;
-    }
-    const uint32_t o = n & 8, b4 = n & 4, b2 = n & 2;
-    if (o) *(u64_u *)dst = c.lo;
-    const uint64_t t = o ? c.hi : c.lo;
-    if (b4) *(u32_u *)(dst + o) = (uint32_t)t;
-    if (b2) *(u16_u *)(dst + o + b4) = (uint16_t)(t >> (8 * b4));
-    if (n & 1) dst[o + b4 + b2] = (uint8_t)(t >> (8 * (b4 + b2)));
-}
 // The unconditional form of a lane chunk (a load under a branch makes the compiler wait for every earlier
 // load at the join, so the chunks of eight entries went out one at a time): a range of >= 16 bytes reads
 // the 16 bytes at x, or for its tail the 16 ending at its end (shifted down at the store); a lane with no
@@ -773,7 +743,8 @@ typedef __attribute__((address_space(1))) u32_u g_u32_u;
 typedef __attribute__((address_space(1))) u16_u g_u16_u;
 typedef __attribute__((address_space(1))) uint8_t g_u8;
 SDB_DEV u32x4_u chunk_ld(const uint8_t *p) { return *(const g_u32x4_u *)(uintptr_t)p; }
-SDB_DEV void chunk_store_g(const Chunk &c, uint8_t *dst0, uint32_t n) {
+// (the destination of every copy is global memory)
+SDB_DEV void chunk_store(const Chunk &c, uint8_t *dst0, uint32_t n) {
     const uintptr_t dst = (uintptr_t)dst0;
     if (n >= 16) {
         u32x4_u v;
@@ -810,7 +781,7 @@ SDB_DEV void chunk_put(const u32x4_u &w, const uint8_t *src, uint8_t *dst, uint3
     Chunk c;
     c.lo = lo;
     c.hi = hi;
-    chunk_store_g(c, dst + x, n);
+    chunk_store(c, dst + x, n);
 }
 // lane chunk x of every listed entry's key and value bytes: all sixteen loads, then the stores
 SDB_DEV void copy_group_chunks_kv(const CopyDesc *cd, uint32_t l, uint32_t x) {
@@ -919,27 +890,20 @@ __global__ __launch_bounds__(kMergeThreads) void k_mg_emit(MergeArgs a) {
         uint8_t mask = 0;
         if (e.f & SDB_FLAG_HAS_CREATE_TS) mask |= SDB_TS_CREATE;
         if ((e.f & SDB_FLAG_HAS_EXPIRE_TS) && e.d == 1) mask |= SDB_TS_EXPIRE;  // converted: expire_ts None
-        bool chain = false;
-        if constexpr (U) chain = a.ch.unit[p0 + u] >= kUnitChain;
-        if (chain) {  // the timestamps MergeTracker aggregated over the chain (merge_operator.rs:262-303)
-            const ChainGroup &G = a.ch.group[a.ch.uinfo[p0 + u]];
-            mask = (uint8_t)(G.ts_mask & (e.d == 1 ? (SDB_TS_CREATE | SDB_TS_EXPIRE) : SDB_TS_CREATE));
-            o.key_off[j] = ko;
-            o.val_off[j] = vo;
-            o.kind[j] = tomb ? SDB_KIND_TOMBSTONE : (e.f & SDB_FLAG_MERGE_OPERAND) ? SDB_KIND_MERGE : SDB_KIND_VALUE;
-            o.seq[j] = e.seq;
-            o.ts_mask[j] = mask;
-            o.create_ts[j] = (mask & SDB_TS_CREATE) ? G.create_ts : 0;
-            o.expire_ts[j] = (mask & SDB_TS_EXPIRE) ? G.expire_ts : 0;
-        } else {
+        const ChainGroup *G = nullptr;  // a chain head: the timestamps MergeTracker aggregated over the chain
+        if constexpr (U) {              // (merge_operator.rs:262-303) instead of the entry's own
+            if (a.ch.unit[p0 + u] >= kUnitChain) {
+                G = &a.ch.group[a.ch.uinfo[p0 + u]];
+                mask = (uint8_t)(G->ts_mask & (e.d == 1 ? (SDB_TS_CREATE | SDB_TS_EXPIRE) : SDB_TS_CREATE));
+            }
+        }
         o.key_off[j] = ko;
         o.val_off[j] = vo;
         o.kind[j] = tomb ? SDB_KIND_TOMBSTONE : (e.f & SDB_FLAG_MERGE_OPERAND) ? SDB_KIND_MERGE : SDB_KIND_VALUE;
         o.seq[j] = e.seq;
         o.ts_mask[j] = mask;
-        o.create_ts[j] = (mask & SDB_TS_CREATE) ? a.r[e.run].create_ts[e.i] : 0;
-        o.expire_ts[j] = (mask & SDB_TS_EXPIRE) ? a.r[e.run].expire_ts[e.i] : 0;
-        }
+        o.create_ts[j] = !(mask & SDB_TS_CREATE) ? 0 : G ? G->create_ts : a.r[e.run].create_ts[e.i];
+        o.expire_ts[j] = !(mask & SDB_TS_EXPIRE) ? 0 : G ? G->expire_ts : a.r[e.run].expire_ts[e.i];
         cd.ks = e.ks;
         cd.kd = o.key_bytes + ko;
         cd.kb = e.kb;
@@ -1382,62 +1346,51 @@ sdb_status build_merge_args(const sdb_run *runs, uint32_t nruns, const sdb_reten
     return SDB_OK;
 }
 
-// The merged order: perm (and the run-order check).  Returns the k_mg_prefix-sized grid (0: no entries).
-static uint32_t launch_merge_order(const MergeArgs &a, hipStream_t st) {
+static uint32_t key_grid(const MergeArgs &a) { return (uint32_t)((a.total + kPfxThreads - 1) / kPfxThreads); }
+
+hipError_t launch_merge_order(const MergeArgs &a, hipStream_t st) {
     if (hipMemsetAsync(a.err, 0xFF, 8, st) != hipSuccess || hipMemsetAsync(a.err_merge, 0xFF, 8, st) != hipSuccess ||
         hipMemsetAsync(a.metric, 0, 16, st) != hipSuccess)
-        return ~0u;
-    const uint32_t gb = (uint32_t)((a.total + kPfxThreads - 1) / kPfxThreads);
-    if (gb) {
+        return hipErrorUnknown;
+    if (const uint32_t gb = key_grid(a)) {
         hipLaunchKernelGGL(k_mg_lcp0, dim3(1), dim3(256), 0, st, a);
         hipLaunchKernelGGL(k_mg_prefix, dim3(gb), dim3(kPfxThreads), 0, st, a);
         const uint64_t nb = (uint64_t)gb * 2 * a.nruns;
         hipLaunchKernelGGL(k_mg_bounds, dim3((uint32_t)((nb + 255) / 256)), dim3(256), 0, st, a);
         hipLaunchKernelGGL(k_mg_rank, dim3(gb), dim3(kPfxThreads), 0, st, a);
     }
-    return gb;
+    return hipGetLastError();
+}
+
+hipError_t launch_merge_retention(const MergeArgs &a, bool emit, hipStream_t st) {
+    const auto keys = a.ch.unit ? k_mg_keys<true> : k_mg_keys<false>;
+    if (const uint32_t gb = key_grid(a)) hipLaunchKernelGGL(keys, dim3(gb), dim3(kPfxThreads), 0, st, a);
+    hipLaunchKernelGGL(k_mg_scan, dim3(1), dim3(kMergeThreads), 0, st, a);
+    return emit ? launch_merge_emit(a, st) : hipGetLastError();
+}
+
+hipError_t launch_merge_emit(const MergeArgs &a, hipStream_t st) {
+    const auto emit = a.ch.unit ? k_mg_emit<true> : k_mg_emit<false>;
+    if (a.ntiles) hipLaunchKernelGGL(emit, dim3(a.ntiles), dim3(kMergeThreads), 0, st, a);
+    return hipGetLastError();
 }
 
 hipError_t launch_merge(const MergeArgs &a, bool emit, hipStream_t st) {
-    const uint32_t gb = launch_merge_order(a, st);
-    if (gb == ~0u) return hipErrorUnknown;
-    if (gb) hipLaunchKernelGGL(k_mg_keys<false>, dim3(gb), dim3(kPfxThreads), 0, st, a);
-    hipLaunchKernelGGL(k_mg_scan, dim3(1), dim3(kMergeThreads), 0, st, a);
-    if (emit && a.ntiles) hipLaunchKernelGGL(k_mg_emit<false>, dim3(a.ntiles), dim3(kMergeThreads), 0, st, a);
-    return hipGetLastError();
-}
-
-// The emit alone, after launch_merge(a, false) sized the output with unbounded capacities (the
-// caller then points a.out at buffers of exactly the reported sizes).
-hipError_t launch_merge_emit(const MergeArgs &a, hipStream_t st) {
-    if (a.ntiles) hipLaunchKernelGGL(k_mg_emit<false>, dim3(a.ntiles), dim3(kMergeThreads), 0, st, a);
-    return hipGetLastError();
+    const hipError_t e = launch_merge_order(a, st);
+    return e != hipSuccess ? e : launch_merge_retention(a, emit, st);
 }
 
 hipError_t launch_merge_chains(const MergeArgs &a, hipStream_t st) {
-    const uint32_t gb = launch_merge_order(a, st);
-    if (gb == ~0u || hipMemsetAsync(a.ch.tile_sum, 0, 32 * ((uint64_t)a.ntiles + 1), st) != hipSuccess)
+    if (launch_merge_order(a, st) != hipSuccess ||
+        hipMemsetAsync(a.ch.tile_sum, 0, 32 * ((uint64_t)a.ntiles + 1), st) != hipSuccess)
         return hipErrorUnknown;
-    if (gb) hipLaunchKernelGGL(k_mg_chain, dim3(gb), dim3(kPfxThreads), 0, st, a);
+    if (const uint32_t gb = key_grid(a)) hipLaunchKernelGGL(k_mg_chain, dim3(gb), dim3(kPfxThreads), 0, st, a);
     hipLaunchKernelGGL(k_mg_chain_scan, dim3(1), dim3(kMergeThreads), 0, st, a);
     return hipGetLastError();
 }
 
 hipError_t launch_chain_tables(const MergeArgs &a, hipStream_t st) {
     if (a.ntiles) hipLaunchKernelGGL(k_mg_chain_emit, dim3(a.ntiles), dim3(kMergeThreads), 0, st, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_merge_units(const MergeArgs &a, bool emit, hipStream_t st) {
-    const uint32_t gb = (uint32_t)((a.total + kPfxThreads - 1) / kPfxThreads);
-    if (gb) hipLaunchKernelGGL(k_mg_keys<true>, dim3(gb), dim3(kPfxThreads), 0, st, a);
-    hipLaunchKernelGGL(k_mg_scan, dim3(1), dim3(kMergeThreads), 0, st, a);
-    if (emit && a.ntiles) hipLaunchKernelGGL(k_mg_emit<true>, dim3(a.ntiles), dim3(kMergeThreads), 0, st, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_merge_emit_units(const MergeArgs &a, hipStream_t st) {
-    if (a.ntiles) hipLaunchKernelGGL(k_mg_emit<true>, dim3(a.ntiles), dim3(kMergeThreads), 0, st, a);
     return hipGetLastError();
 }
 

@@ -12,6 +12,8 @@
 //                            chains and gathers their bytes, the host folds each chain through the operator,
 //                            and retention, cuts and encode run over the collapsed stream; two more host
 //                            synchronisations (the chain summary; the chain tables, only when there is a chain).
+// Both job families share begin_job, order_step (the merged order; with an operator chain_step), the cut readback
+// (CutRead) and encode_outputs; a.ch, bound by chain_step, selects the unit forms of retention and emit.
 // The outputs stay in the handle's device memory; every SST of the job is encoded by one launch sequence
 // per 8 SSTs.  The handle's buffers (DevBuf, PinBuf) and every layout inside them come from sdb_host.h.
 #include <hip/hip_runtime.h>
@@ -67,6 +69,24 @@ struct GuardBuf {
     }
 };
 
+// Orders the reuse of a host buffer behind the stream work that still reads it: the job that queued the work
+// records the event, the next job waits for it before it rewrites the buffer.
+struct StreamEvent {
+    hipEvent_t ev = nullptr;
+    bool live = false;
+    bool wait() {  // (creates the event once)
+        if (live && hipEventSynchronize(ev) != hipSuccess) return false;
+        live = false;
+        if (!ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) ev = nullptr;
+        return ev != nullptr;
+    }
+    void record(hipStream_t s) { live = hipEventRecord(ev, s) == hipSuccess; }
+    ~StreamEvent() {
+        if (ev) (void)hipEventSynchronize(ev);
+        if (ev) (void)hipEventDestroy(ev);
+    }
+};
+
 struct sdb_compactor {
     int device = 0;
     DevBuf merge_ws, cols, keys, vals, cut_ws, cuts, sst_meta, sst_data, sst_bloom, enc_ws, dec, dec_ws, cx_tab;
@@ -76,26 +96,18 @@ struct sdb_compactor {
     // mirror), the merged values (pinned, then device)
     GuardBuf chain_ws, chain_tab, chain_up;
     PinBuf pin_chain, pin_up;
-    hipEvent_t up_ev = nullptr;  // the upload of pin_up: the next job waits for it before it rewrites pin_up
-    bool up_ev_live = false;
+    StreamEvent up_ev;  // the upload of pin_up: the next job waits for it before it rewrites pin_up
     bool canaries = false;
     sdb_merge_op_stats mstats{};
     // recorded on the job's stream when a run_ssts job returns (every path): the next job waits for it
     // before it rewrites pin_tab / cx_tab, which that job's upload and kernels may still be reading
-    hipEvent_t tab_ev = nullptr;
-    bool tab_ev_live = false;
+    StreamEvent tab_ev;
     sdb_kv_batch merged{};
     sdb_merge_summary msum{};
     std::vector<sdb_compacted_sst> ssts;
-    // the buffers free themselves after this; only the pinned tables need an order: the last job's upload
-    // may still read them
-    ~sdb_compactor() {
-        (void)hipSetDevice(device);
-        if (tab_ev) (void)hipEventSynchronize(tab_ev);
-        if (tab_ev) (void)hipEventDestroy(tab_ev);
-        if (up_ev) (void)hipEventSynchronize(up_ev);
-        if (up_ev) (void)hipEventDestroy(up_ev);
-    }
+    // the members free themselves after this, last declared first: the two events wait for the last job's
+    // uploads before the pinned tables they read (declared above them) go
+    ~sdb_compactor() { (void)hipSetDevice(device); }
 };
 
 namespace {
@@ -323,13 +335,7 @@ sdb_status chain_step(sdb_compactor *c, MergeArgs &a, sdb_merge_batch_fn op, voi
     // the upload: offsets, then bytes (+ 16: the emit's 16-byte chunk loads stay inside)
     Carver uc{nullptr, 0};
     const uint64_t u_off = uc.bytes(8 * (cs.groups + 1)), u_val = uc.bytes(merged.size() + 16);
-    if (c->up_ev_live && hipEventSynchronize(c->up_ev) != hipSuccess) return SDB_DEVICE_ERROR;
-    c->up_ev_live = false;
-    if (!c->up_ev && hipEventCreateWithFlags(&c->up_ev, hipEventDisableTiming) != hipSuccess) {
-        c->up_ev = nullptr;
-        return SDB_DEVICE_ERROR;
-    }
-    if (!c->chain_up.ensure(uc.off, c->canaries) || !c->pin_up.ensure(uc.off)) return SDB_DEVICE_ERROR;
+    if (!c->up_ev.wait() || !c->chain_up.ensure(uc.off, c->canaries) || !c->pin_up.ensure(uc.off)) return SDB_DEVICE_ERROR;
     memcpy(c->pin_up.at<uint8_t>(u_off), moff.data(), 8 * (cs.groups + 1));
     if (!merged.empty()) memcpy(c->pin_up.at<uint8_t>(u_val), merged.data(), merged.size());
     memset(c->pin_up.at<uint8_t>(u_val) + merged.size(), 0, 16);
@@ -337,7 +343,7 @@ sdb_status chain_step(sdb_compactor *c, MergeArgs &a, sdb_merge_batch_fn op, voi
     if (hipMemcpyAsync(up + u_off, c->pin_up.at<uint8_t>(u_off), 8 * (cs.groups + 1), hipMemcpyHostToDevice, s) != hipSuccess ||
         hipMemcpyAsync(up + u_val, c->pin_up.at<uint8_t>(u_val), merged.size() + 16, hipMemcpyHostToDevice, s) != hipSuccess)
         return SDB_DEVICE_ERROR;
-    c->up_ev_live = hipEventRecord(c->up_ev, s) == hipSuccess;
+    c->up_ev.record(s);
     a.ch.moff = reinterpret_cast<const uint64_t *>(up + u_off);
     a.ch.mval = up + u_val;
     return SDB_OK;
@@ -359,13 +365,83 @@ sdb_kv_batch batch_of(const sdb_merged_out &o, uint64_t n) {
     return m;
 }
 
-// step 3 of both jobs: encode every output SST (sets of up to 8 per launch sequence) over the cut
-// ranges of c->merged, then read the summaries back (one synchronisation)
-sdb_status encode_outputs(sdb_compactor *c, const uint64_t *cut, const uint64_t *off, uint64_t ns,
-                          const sdb_sst_params *params, void *stream) {
+// The prologue of every job: the handle's results of the last job reset, the arguments every job takes checked.
+sdb_status begin_job(sdb_compactor *c, const sdb_retention *ret, const sdb_sst_params *params, uint32_t *num_ssts) {
+    if (!c || !params || !num_ssts) return SDB_INVALID_ARGUMENT;
+    *num_ssts = 0;
+    c->ssts.clear();
+    c->merged = sdb_kv_batch{};
+    c->msum = sdb_merge_summary{};
+    c->mstats = sdb_merge_op_stats{};
+    if (params->sst_type != SDB_SST_COMPACTED || !ret) return SDB_INVALID_ARGUMENT;  // compactions write compacted SSTs
+    return SDB_OK;
+}
+
+// The merged order of a job; with an operator the chains, the fold and the upload behind it (chain_step), which
+// bind a.ch, so the retention and emit launches that follow run over the units.
+sdb_status order_step(sdb_compactor *c, MergeArgs &a, sdb_merge_batch_fn op, void *ctx, hipStream_t s) {
+    if (op) return chain_step(c, a, op, ctx, s);
+    return launch_merge_order(a, s) == hipSuccess ? SDB_OK : SDB_DEVICE_ERROR;
+}
+
+// The readback of a job's cuts through c->pin, around the job's synchronisation.  Every SST but the last holds
+// more than max_sst_size bytes of blocks, and a block costs at most its keys, values and 64 bytes per row, so g
+// bounds the count for a stream of n entries and `bytes` key and value bytes; a larger one takes a second copy.
+struct CutRead {
+    uint64_t g;
+    const uint64_t *d_cut, *d_off;
+    const sdb_merge_summary *sum;     // pinned: the merged summary (NULL: not asked for)
+    const uint64_t *num, *cut, *off;  // pinned: the count, g + 1 cuts, their offsets
+};
+// Enqueues the copies: the merged summary d_sum (unless NULL), then (n > 0) the count and the first g + 1 cuts
+// and offsets of the device cut list.
+bool cut_read_begin(sdb_compactor *c, CutRead &r, uint64_t n, uint64_t bytes, uint64_t max_sst_size,
+                    const sdb_merge_summary *d_sum, const uint64_t *d_num, const uint64_t *d_cut, const uint64_t *d_off,
+                    hipStream_t s) {
+    const uint64_t g = max_sst_size ? std::min<uint64_t>(n, 2 + (bytes + 64 * n) / max_sst_size) : n;
+    Carver hc{nullptr, 0};
+    const uint64_t h_sum = hc.bytes(sizeof(sdb_merge_summary));
+    const CutLayout hl = cut_layout(hc, g);
+    if (!c->pin.ensure(hc.off)) return false;
+    sdb_merge_summary *hsum = c->pin.at<sdb_merge_summary>(h_sum);
+    uint64_t *hnum = c->pin.at<uint64_t>(hl.num), *hcut = c->pin.at<uint64_t>(hl.cut), *hoff = c->pin.at<uint64_t>(hl.off);
+    *hnum = 0;
+    r = CutRead{g, d_cut, d_off, d_sum ? hsum : nullptr, hnum, hcut, hoff};
+    return (!d_sum || hipMemcpyAsync(hsum, d_sum, sizeof(sdb_merge_summary), hipMemcpyDeviceToHost, s) == hipSuccess) &&
+           (!n || (hipMemcpyAsync(hnum, d_num, 8, hipMemcpyDeviceToHost, s) == hipSuccess &&
+                   hipMemcpyAsync(hcut, d_cut, 8 * (g + 1), hipMemcpyDeviceToHost, s) == hipSuccess &&
+                   hipMemcpyAsync(hoff, d_off, 16 * (g + 1), hipMemcpyDeviceToHost, s) == hipSuccess));
+}
+// After the synchronisation: the SST count of a merged stream of n > 0 entries, its cuts and their offsets (taken
+// out of c->pin, which encode_outputs reuses).
+sdb_status cut_read_end(const CutRead &r, uint64_t n, uint64_t *num, std::vector<uint64_t> &cut, std::vector<uint64_t> &off) {
+    const uint64_t ns = *r.num;
+    if (ns == 0 || ns > n) return SDB_DEVICE_ERROR;
+    cut.resize(ns + 1);
+    off.resize(2 * (ns + 1));
+    if (ns > r.g) {
+        if (hipMemcpy(cut.data(), r.d_cut, 8 * (ns + 1), hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(off.data(), r.d_off, 16 * (ns + 1), hipMemcpyDeviceToHost) != hipSuccess)
+            return SDB_DEVICE_ERROR;
+    } else {
+        memcpy(cut.data(), r.cut, 8 * (ns + 1));
+        memcpy(off.data(), r.off, 16 * (ns + 1));
+    }
+    *num = ns;
+    return SDB_OK;
+}
+
+// step 3 of both jobs, after the synchronisation of the cut readback: encode every output SST (sets of up to 8
+// per launch sequence) over the cut ranges of c->merged (n > 0 entries), then read the summaries back (one
+// synchronisation)
+sdb_status encode_outputs(sdb_compactor *c, const CutRead &rd, uint64_t n, const sdb_sst_params *params, void *stream,
+                          uint32_t *num_ssts) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const sdb_kv_batch &m = c->merged;
-    sdb_status st = SDB_OK;
+    uint64_t ns = 0;
+    std::vector<uint64_t> cut, off;
+    sdb_status st = cut_read_end(rd, n, &ns, cut, off);
+    if (st) return st;
     std::vector<sdb_kv_batch> batches(ns);
     std::vector<sdb_sst_out> outs(ns);
     for (uint64_t i = 0; i < ns; i++) {
@@ -427,6 +503,7 @@ sdb_status encode_outputs(sdb_compactor *c, const uint64_t *cut, const uint64_t 
         v.summary = sums[i];
         if (!first && sums[i].status) first = (sdb_status)sums[i].status;
     }
+    *num_ssts = (uint32_t)ns;
     return first;
 }
 
@@ -452,14 +529,9 @@ namespace {
 sdb_status run_job(sdb_compactor *c, const sdb_run *runs, uint32_t nruns, const sdb_retention *ret,
                    sdb_merge_batch_fn op, void *ctx, const sdb_sst_params *params, uint64_t max_sst_size,
                    void *stream, uint32_t *num_ssts) {
-    if (!c || !params || !num_ssts) return SDB_INVALID_ARGUMENT;
-    *num_ssts = 0;
-    c->ssts.clear();
-    c->merged = sdb_kv_batch{};
-    c->msum = sdb_merge_summary{};
-    c->mstats = sdb_merge_op_stats{};
-    if (params->sst_type != SDB_SST_COMPACTED) return SDB_INVALID_ARGUMENT;  // compactions write compacted SSTs
-    if ((nruns && !runs) || !ret) return SDB_INVALID_ARGUMENT;  // before group_runs reads runs[]
+    sdb_status st = begin_job(c, ret, params, num_ssts);
+    if (st) return st;
+    if (nruns && !runs) return SDB_INVALID_ARGUMENT;  // before group_runs reads runs[]
     if (hipSetDevice(c->device) != hipSuccess) return SDB_DEVICE_ERROR;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     uint64_t total = 0;
@@ -474,21 +546,17 @@ sdb_status run_job(sdb_compactor *c, const sdb_run *runs, uint32_t nruns, const 
 
     // 1. merge + retention, sized with unbounded byte capacities, then emitted
     sdb_merged_out out{};
-    sdb_status st = merged_columns_in(c->cols, total, &out);
+    st = merged_columns_in(c->cols, total, &out);
     if (st) return st;
     const uint64_t mws = sdb_merge_runs_workspace_bytes(runs, nruns);
     if (!c->merge_ws.ensure(mws)) return SDB_DEVICE_ERROR;
     MergeArgs a;
     st = build_merge_args(runs, nruns, ret, &out, c->merge_ws.p, c->merge_ws.cap, &a);
     if (st) return st;
-    if (op) {  // chains, the operator, then retention over the units
-        st = chain_step(c, a, op, ctx, s);
-        if (st) return st;
-        if (launch_merge_units(a, false, s) != hipSuccess) return SDB_DEVICE_ERROR;
-    } else if (launch_merge(a, false, s) != hipSuccess) {
-        return SDB_DEVICE_ERROR;
-    }
-    if (hipMemcpyAsync(&c->msum, out.summary, sizeof(sdb_merge_summary), hipMemcpyDeviceToHost, s) != hipSuccess ||
+    st = order_step(c, a, op, ctx, s);
+    if (st) return st;
+    if (launch_merge_retention(a, false, s) != hipSuccess ||
+        hipMemcpyAsync(&c->msum, out.summary, sizeof(sdb_merge_summary), hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
         return SDB_DEVICE_ERROR;
     if (c->msum.status) return (sdb_status)c->msum.status;
@@ -497,7 +565,7 @@ sdb_status run_job(sdb_compactor *c, const sdb_run *runs, uint32_t nruns, const 
     a.out.key_cap = c->msum.key_bytes;
     a.out.val_bytes = c->vals.at<uint8_t>(0);
     a.out.val_cap = c->msum.val_bytes;
-    if ((op ? launch_merge_emit_units(a, s) : launch_merge_emit(a, s)) != hipSuccess) return SDB_DEVICE_ERROR;
+    if (launch_merge_emit(a, s) != hipSuccess) return SDB_DEVICE_ERROR;
     const uint64_t n = c->msum.num_out;
     sdb_kv_batch &m = c->merged;
     m = batch_of(a.out, n);
@@ -508,32 +576,15 @@ sdb_status run_job(sdb_compactor *c, const sdb_run *runs, uint32_t nruns, const 
     if (!cut_buffers(c, n, params, &d_num, &d_cut, &d_off)) return SDB_DEVICE_ERROR;
     st = sdb_sst_cuts(&m, params, max_sst_size, d_cut, n + 1, d_num, c->cut_ws.p, c->cut_ws.cap, stream);
     if (st) return st;
-    // the cut count, the cuts and their byte offsets in one synchronisation: every SST but the last holds
-    // more than max_sst_size bytes of blocks, and a block costs at most its keys, values and 64 bytes
-    // per row, so g bounds the count (a larger one takes a second copy)
-    const uint64_t g = max_sst_size ? std::min<uint64_t>(n, 2 + (c->msum.key_bytes + c->msum.val_bytes + 64 * n) / max_sst_size) : n;
-    uint64_t ns = 0;
-    std::vector<uint64_t> cut(g + 1), off(2 * (g + 1));
+    // the cut count, the cuts and their byte offsets in one synchronisation
+    CutRead rd;
     if (launch_cut_offsets(d_cut, d_num, m.key_off, m.val_off, d_off, s) != hipSuccess ||
-        hipMemcpyAsync(&ns, d_num, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(cut.data(), d_cut, 8 * (g + 1), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(off.data(), d_off, 16 * (g + 1), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        !cut_read_begin(c, rd, n, c->msum.key_bytes + c->msum.val_bytes, max_sst_size, nullptr, d_num, d_cut, d_off, s) ||
         hipStreamSynchronize(s) != hipSuccess)
         return SDB_DEVICE_ERROR;
-    if (ns == 0 || ns > n) return SDB_DEVICE_ERROR;
-    if (ns > g) {
-        cut.resize(ns + 1);
-        off.resize(2 * (ns + 1));
-        if (hipMemcpyAsync(cut.data(), d_cut, 8 * (ns + 1), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipMemcpyAsync(off.data(), d_off, 16 * (ns + 1), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess)
-            return SDB_DEVICE_ERROR;
-    }
 
     // 3. encode every output SST
-    const sdb_status first = encode_outputs(c, cut.data(), off.data(), ns, params, stream);
-    if (first == SDB_OK || c->ssts.size() == ns) *num_ssts = (uint32_t)ns;
-    return first;
+    return encode_outputs(c, rd, n, params, stream, num_ssts);
 }
 
 // sdb_compactor_run_ssts (op == NULL) / sdb_compactor_run_ssts_merge
@@ -541,13 +592,9 @@ sdb_status run_ssts_job(sdb_compactor *c, const sdb_compaction_input *inputs, ui
                         const uint32_t *run_start, uint32_t nruns, uint16_t input_sst_version,
                         const sdb_retention *ret, sdb_merge_batch_fn op, void *ctx, const sdb_sst_params *params,
                         uint64_t max_sst_size, void *stream, uint32_t *num_ssts) {
-    if (!c || !params || !num_ssts || !ret || (ninputs && !inputs)) return SDB_INVALID_ARGUMENT;
-    *num_ssts = 0;
-    c->ssts.clear();
-    c->merged = sdb_kv_batch{};
-    c->msum = sdb_merge_summary{};
-    c->mstats = sdb_merge_op_stats{};
-    if (params->sst_type != SDB_SST_COMPACTED) return SDB_INVALID_ARGUMENT;
+    sdb_status st = begin_job(c, ret, params, num_ssts);
+    if (st) return st;
+    if (ninputs && !inputs) return SDB_INVALID_ARGUMENT;
     if (input_sst_version != 1 && input_sst_version != 2) return SDB_INVALID_VERSION;
     if (!run_start) nruns = ninputs;
     if ((uint64_t)nruns > (uint64_t)kMaxRuns * kMaxRuns) return SDB_LIMIT_EXCEEDED;  // two merge levels
@@ -570,13 +617,7 @@ sdb_status run_ssts_job(sdb_compactor *c, const sdb_compaction_input *inputs, ui
     const uint64_t t_rent = tc.bytes(8ull * (nruns + 1)), t_total = tc.off;
     // the previous job's upload and kernels may still read pin_tab / cx_tab (a job that failed early
     // returns without a synchronisation, and the caller may alternate streams)
-    if (c->tab_ev_live && hipEventSynchronize(c->tab_ev) != hipSuccess) return SDB_DEVICE_ERROR;
-    c->tab_ev_live = false;
-    if (!c->tab_ev && hipEventCreateWithFlags(&c->tab_ev, hipEventDisableTiming) != hipSuccess) {
-        c->tab_ev = nullptr;
-        return SDB_DEVICE_ERROR;
-    }
-    if (!c->pin_tab.ensure(t_total) || !c->cx_tab.ensure(t_total)) return SDB_DEVICE_ERROR;
+    if (!c->tab_ev.wait() || !c->pin_tab.ensure(t_total) || !c->cx_tab.ensure(t_total)) return SDB_DEVICE_ERROR;
     const uint8_t **h_data = c->pin_tab.at<const uint8_t *>(t_data);
     const uint64_t **h_boff = c->pin_tab.at<const uint64_t *>(t_boff);
     uint64_t *h_first = c->pin_tab.at<uint64_t>(t_first), *h_rblk = c->pin_tab.at<uint64_t>(t_rblk);
@@ -617,7 +658,7 @@ sdb_status run_ssts_job(sdb_compactor *c, const sdb_compaction_input *inputs, ui
     struct TabRelease {  // on every return from here: everything enqueued so far precedes the event
         sdb_compactor *c;
         hipStream_t s;
-        ~TabRelease() { c->tab_ev_live = hipEventRecord(c->tab_ev, s) == hipSuccess; }
+        ~TabRelease() { c->tab_ev.record(s); }
     } tab_release{c, s};
     in.data = c->cx_tab.at<const uint8_t *const>(t_data);
     in.block_off = c->cx_tab.at<const uint64_t *const>(t_boff);
@@ -655,9 +696,8 @@ sdb_status run_ssts_job(sdb_compactor *c, const sdb_compaction_input *inputs, ui
     const uint8_t *arena = reinterpret_cast<const uint8_t *>(base);
     if (launch_cx_blocks(in, bstart, bend, s) != hipSuccess) return SDB_DEVICE_ERROR;
     // fail-fast (a failing block fails the job anyway, as load_iterators' reads would): checksums in the emit pass
-    sdb_status st = sdb_decode_blocks_ex(arena, bstart, bend, B, input_sst_version, SDB_DECODE_FAIL_FAST, &dout,
-                                         c->dec_ws.p, c->dec_ws.cap,
-                                         stream);
+    st = sdb_decode_blocks_ex(arena, bstart, bend, B, input_sst_version, SDB_DECODE_FAIL_FAST, &dout,
+                              c->dec_ws.p, c->dec_ws.cap, stream);
     if (st) return st;
     const unsigned long long *dec_err = decode_err_word(c->dec_ws.p, B);
     if (launch_cx_gate(in, dout.summary, dec_err, dout.block_entry_start, gate, s) != hipSuccess)
@@ -702,19 +742,17 @@ sdb_status run_ssts_job(sdb_compactor *c, const sdb_compaction_input *inputs, ui
     st = build_merge_args(mruns, mn, ret, &out, c->merge_ws.p, c->merge_ws.cap, &a);
     if (st) return st;
     a.gate = gate;
+    st = order_step(c, a, op, ctx, s);
+    if (st) return st;
     if (op) {
-        st = chain_step(c, a, op, ctx, s);
-        if (st) return st;
         // a merged value can be longer than all of its inputs: the links' bytes leave, the merged bytes come
         V = (V > c->mstats.link_bytes ? V - c->mstats.link_bytes : 0) + c->mstats.merged_bytes;
         if (!c->vals.ensure(V + 16)) return SDB_DEVICE_ERROR;
         a.out.val_bytes = out.val_bytes = c->vals.at<uint8_t>(0);
         a.out.val_cap = out.val_cap = V;
-        if (launch_merge_units(a, true, s) != hipSuccess) return SDB_DEVICE_ERROR;
-    } else if (launch_merge(a, true, s) != hipSuccess) {
-        return SDB_DEVICE_ERROR;
     }
-    if (launch_merge_pad(out, E, s) != hipSuccess) return SDB_DEVICE_ERROR;
+    if (launch_merge_retention(a, true, s) != hipSuccess || launch_merge_pad(out, E, s) != hipSuccess)
+        return SDB_DEVICE_ERROR;
     const sdb_kv_batch padded = batch_of(out, E);
 
     // cuts over the padded stream, ending at the merged count; merged summary, cut count, cuts and their
@@ -727,41 +765,18 @@ sdb_status run_ssts_job(sdb_compactor *c, const sdb_compaction_input *inputs, ui
         if (st) return st;
         if (launch_cut_offsets(d_cut, d_num, out.key_off, out.val_off, d_off, s) != hipSuccess) return SDB_DEVICE_ERROR;
     }
-    const uint64_t g = max_sst_size ? std::min<uint64_t>(E, 2 + (K + V + 64 * E) / max_sst_size) : E;
-    Carver hc{nullptr, 0};  // the readback in c->pin: the merged summary, then the first g cuts
-    const uint64_t h_sum = hc.bytes(sizeof(sdb_merge_summary));
-    const CutLayout hl = cut_layout(hc, g);
-    if (!c->pin.ensure(hc.off)) return SDB_DEVICE_ERROR;
-    sdb_merge_summary *hsum = c->pin.at<sdb_merge_summary>(h_sum);
-    uint64_t *hnum = c->pin.at<uint64_t>(hl.num), *hcut = c->pin.at<uint64_t>(hl.cut), *hoff = c->pin.at<uint64_t>(hl.off);
-    *hnum = 0;
-    if (hipMemcpyAsync(hsum, out.summary, sizeof(sdb_merge_summary), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        (E && (hipMemcpyAsync(hnum, d_num, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
-               hipMemcpyAsync(hcut, d_cut, 8 * (g + 1), hipMemcpyDeviceToHost, s) != hipSuccess ||
-               hipMemcpyAsync(hoff, d_off, 16 * (g + 1), hipMemcpyDeviceToHost, s) != hipSuccess)) ||
+    CutRead rd;
+    if (!cut_read_begin(c, rd, E, K + V, max_sst_size, out.summary, d_num, d_cut, d_off, s) ||
         hipStreamSynchronize(s) != hipSuccess)
         return SDB_DEVICE_ERROR;
-    c->msum = *hsum;
+    c->msum = *rd.sum;
     if (c->msum.status) return (sdb_status)c->msum.status;
     const uint64_t n = c->msum.num_out;
     c->merged = batch_of(out, n);
-    const uint64_t ns = *hnum;
     if (!n) return SDB_OK;
-    if (ns == 0 || ns > n) return SDB_DEVICE_ERROR;
-    std::vector<uint64_t> cut(ns + 1), off(2 * (ns + 1));
-    if (ns > g) {
-        if (hipMemcpy(cut.data(), d_cut, 8 * (ns + 1), hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(off.data(), d_off, 16 * (ns + 1), hipMemcpyDeviceToHost) != hipSuccess)
-            return SDB_DEVICE_ERROR;
-    } else {
-        memcpy(cut.data(), hcut, 8 * (ns + 1));
-        memcpy(off.data(), hoff, 16 * (ns + 1));
-    }
 
     // 3. encode every output SST
-    const sdb_status first = encode_outputs(c, cut.data(), off.data(), ns, params, stream);
-    if (first == SDB_OK || c->ssts.size() == ns) *num_ssts = (uint32_t)ns;
-    return first;
+    return encode_outputs(c, rd, n, params, stream, num_ssts);
 }
 
 }  // namespace

@@ -1254,24 +1254,32 @@ def sst_cuts_device(dbatch, prm, max_sst_size, stream=None):
 class Compactor:
     """sdb_compactor_*: one compaction job (merge + retention + cuts + encode) per run()."""
 
+    _PLAIN = object()  # `operator` of a job without one
+
     def __init__(self, device=0):
         require_device()
         self.h = lib().sdb_compactor_create(device)
         if not self.h:
             raise SdbError(_abi.SDB_DEVICE_ERROR, "sdb_compactor_create")
 
-    def run(self, druns, ret, prm, max_sst_size, stream=None):
-        cr = (_abi.Run * max(len(druns), 1))(*[r.to_ctypes() for r in druns])
+    def _job(self, symbol, head, ret, operator, prm, max_sst_size, stream):
+        """One job entry point: the inputs `head`, then ret, (with an operator) its callback and a NULL context,
+        params, max_sst_size, stream, num_ssts."""
+        op = ()
+        if operator is not self._PLAIN:
+            cb, self.operator_state = self._operator_callback(operator)
+            op = (cb, None)
         ns = C.c_uint32(0)
-        st = lib().sdb_compactor_run(self.h, cr, len(druns), C.byref(ret), C.byref(prm), max_sst_size, _sp(stream),
-                                     C.byref(ns))
+        st = getattr(lib(), symbol)(self.h, *head, C.byref(ret), *op, C.byref(prm), max_sst_size, _sp(stream), C.byref(ns))
         self.status = st
         return st, ns.value
 
-    def run_ssts(self, inputs, ret, prm, max_sst_size, input_version=2, run_start=None, stream=None):
-        """sdb_compactor_run_ssts: the job from encoded input SSTs (decode included).  inputs: objects with
-        .data / .block_off (device tensors: the data section, block_off u64[num_blocks + 1]) and the
-        SstStats counts .num_entries / .key_bytes / .val_bytes; run_start: inputs of each sorted run."""
+    def _run(self, druns, ret, operator, prm, max_sst_size, stream):
+        cr = (_abi.Run * max(len(druns), 1))(*[r.to_ctypes() for r in druns])
+        return self._job("sdb_compactor_run" + ("_merge" if operator is not self._PLAIN else ""), (cr, len(druns)), ret,
+                         operator, prm, max_sst_size, stream)
+
+    def _run_ssts(self, inputs, ret, operator, prm, max_sst_size, input_version, run_start, stream):
         ci = (_abi.CompactionInput * max(len(inputs), 1))(*[
             _abi.CompactionInput(x.data.data_ptr(), x.block_off.data_ptr(), x.block_off.numel() - 1, x.num_entries,
                                  x.key_bytes, x.val_bytes) for x in inputs])
@@ -1280,11 +1288,17 @@ class Compactor:
         if run_start is not None:
             rs = (C.c_uint32 * len(run_start))(*run_start)
             nruns = len(run_start) - 1
-        ns = C.c_uint32(0)
-        st = lib().sdb_compactor_run_ssts(self.h, ci, len(inputs), rs, nruns, input_version, C.byref(ret), C.byref(prm),
-                                          max_sst_size, _sp(stream), C.byref(ns))
-        self.status = st
-        return st, ns.value
+        return self._job("sdb_compactor_run_ssts" + ("_merge" if operator is not self._PLAIN else ""),
+                         (ci, len(inputs), rs, nruns, input_version), ret, operator, prm, max_sst_size, stream)
+
+    def run(self, druns, ret, prm, max_sst_size, stream=None):
+        return self._run(druns, ret, self._PLAIN, prm, max_sst_size, stream)
+
+    def run_ssts(self, inputs, ret, prm, max_sst_size, input_version=2, run_start=None, stream=None):
+        """sdb_compactor_run_ssts: the job from encoded input SSTs (decode included).  inputs: objects with
+        .data / .block_off (device tensors: the data section, block_off u64[num_blocks + 1]) and the
+        SstStats counts .num_entries / .key_bytes / .val_bytes; run_start: inputs of each sorted run."""
+        return self._run_ssts(inputs, ret, self._PLAIN, prm, max_sst_size, input_version, run_start, stream)
 
     @staticmethod
     def _operator_callback(operator):
@@ -1312,30 +1326,11 @@ class Compactor:
     def run_merge(self, druns, ret, operator, prm, max_sst_size, stream=None):
         """sdb_compactor_run_merge: run() with the store's merge operator (an object with
         merge_batch(key, existing, operands), slatedb_amd/merge.py) between the merge and retention."""
-        cr = (_abi.Run * max(len(druns), 1))(*[r.to_ctypes() for r in druns])
-        ns = C.c_uint32(0)
-        cb, self.operator_state = self._operator_callback(operator)
-        st = lib().sdb_compactor_run_merge(self.h, cr, len(druns), C.byref(ret), cb, None, C.byref(prm), max_sst_size,
-                                           _sp(stream), C.byref(ns))
-        self.status = st
-        return st, ns.value
+        return self._run(druns, ret, operator, prm, max_sst_size, stream)
 
     def run_ssts_merge(self, inputs, ret, operator, prm, max_sst_size, input_version=2, run_start=None, stream=None):
         """sdb_compactor_run_ssts_merge: run_ssts() with the store's merge operator."""
-        ci = (_abi.CompactionInput * max(len(inputs), 1))(*[
-            _abi.CompactionInput(x.data.data_ptr(), x.block_off.data_ptr(), x.block_off.numel() - 1, x.num_entries,
-                                 x.key_bytes, x.val_bytes) for x in inputs])
-        rs = None
-        nruns = len(inputs)
-        if run_start is not None:
-            rs = (C.c_uint32 * len(run_start))(*run_start)
-            nruns = len(run_start) - 1
-        ns = C.c_uint32(0)
-        cb, self.operator_state = self._operator_callback(operator)
-        st = lib().sdb_compactor_run_ssts_merge(self.h, ci, len(inputs), rs, nruns, input_version, C.byref(ret), cb,
-                                                None, C.byref(prm), max_sst_size, _sp(stream), C.byref(ns))
-        self.status = st
-        return st, ns.value
+        return self._run_ssts(inputs, ret, operator, prm, max_sst_size, input_version, run_start, stream)
 
     def merge_stats(self):
         """sdb_merge_op_stats of the last job (zeros after a job without an operator)."""

@@ -304,6 +304,41 @@ def test_operator_failure(rt):
     comp.close()
 
 
+def test_more_tiles_than_scan_threads(rt):
+    """512 * 1024 + 2 entries: one tile more than k_mg_scan / k_mg_chain_scan scan in a pass (512 tiles of 1024
+    positions), so the tile offsets of the last tile come from the second pass of the shared tile scan.  Every key
+    an operand over a value; the columns and the stats in closed form."""
+    import torch
+    n = 512 * 1024 + 2
+    m = n // 2
+    keys = np.arange(m, dtype=">u4")
+    flags = np.tile(np.array([_abi.FLAG_MERGE_OPERAND, 0], np.uint8), m)  # seq 2: the operand, seq 1: the value
+    vals = np.empty(n, np.uint8)
+    vals[0::2] = (np.arange(m) % 251).astype(np.uint8)  # operand of key i
+    vals[1::2] = (np.arange(m) % 241).astype(np.uint8)  # base value of key i
+    zeros = np.zeros(n, np.int64)
+    run = Run(np.repeat(keys, 2).view(np.uint8), 4 * np.arange(n + 1), vals, np.arange(n), np.ones(n, np.uint32),
+              np.tile(np.array([2, 1], np.uint64), m), flags, zeros, zeros)
+    comp = rt.Compactor()
+    st, ns = comp.run_merge([rt.DeviceRun.from_host(run)], O.retention(), merge.StringConcat, rt.params(**PRM), 1 << 30)
+    torch.cuda.synchronize()
+    assert st == 0 and ns == 1
+    got, sm = comp.merged()
+    assert (sm.status, sm.num_in, sm.num_out, sm.key_bytes, sm.val_bytes) == (0, n, m, 4 * m, 2 * m)
+    assert (sm.expired_values, sm.expired_merges) == (0, 0)
+    assert got.n == m
+    assert np.array_equal(got.key_bytes, keys.view(np.uint8)) and np.array_equal(got.key_off, 4 * np.arange(m + 1))
+    # StringConcat: the base value, then the operand
+    assert np.array_equal(got.val_bytes.reshape(m, 2), np.stack([vals[1::2], vals[0::2]], axis=1))
+    assert np.array_equal(got.val_off, 2 * np.arange(m + 1))
+    assert np.all(got.kind == V) and np.all(got.seq == 2) and not got.ts_mask.any()
+    assert not got.create_ts.any() and not got.expire_ts.any()
+    ms = comp.merge_stats()
+    assert (ms.groups, ms.links, ms.link_bytes, ms.merged_bytes) == (m, n, n, n)
+    assert ms.operator_calls == 2 * m  # per chain: its one operand batch, then the batch results with the base
+    comp.close()
+
+
 @pytest.mark.parametrize("total", [1, 255, 256, 257, 1025])
 def test_workspace_canaries(rt, total):
     """The buffers of the merge-operator step (per-position chain state, chain tables and staging arena, merged
