@@ -21,32 +21,16 @@
 //             than the LDS images are decoded by one lane straight between HBM buffers.
 #include <mutex>
 
-#include "sdb_crc.h"
-#include "sdb_decode.h"
-#include "sdb_device.h"
+#include "sdb_codec.h"
 
 namespace sdb {
 
 constexpr uint32_t kDzThreads = 1024;                   // 16 waves per workgroup, one workgroup per CU
 constexpr uint32_t kDzIn = 4096 + 256;                  // compressed bytes staged per wave (a 4 KiB block)
 constexpr uint32_t kDzOut = 4096 + 256;                 // decompressed image per wave
-constexpr uint64_t kMaxBlockOut = 64ull << 20;          // larger declared lengths: SDB_LIMIT_EXCEEDED
 constexpr uint32_t kDzWaveLds = kDzIn + 32 + kDzOut;
 constexpr uint32_t kDzLds = 8 * 1024 + (kDzThreads / 64) * kDzWaveLds;  // slicing tables, then the waves
 static_assert(kDzLds <= 160 * 1024, "decompress LDS");
-
-struct DzArgs {
-    uint32_t codec;
-    const uint8_t *blocks;
-    const uint64_t *block_off;  // nblocks + 1
-    uint64_t nblocks;
-    uint64_t *slot;             // workspace: per block slot bytes (nblocks + 1)
-    uint8_t *out;
-    uint64_t out_cap;
-    const uint64_t *out_start;  // nblocks + 1 (the plan)
-    uint64_t *out_end;          // nblocks
-    unsigned long long *err;    // min (block << 8 | status), ~0 = none
-};
 
 // Declared uncompressed length from the payload header (lz4_flex block::uncompressed_size,
 // snap raw::decompress_len); -1 when unreadable.
@@ -345,14 +329,6 @@ SDB_DEV int dz_payload(uint32_t codec, PI in, uint32_t n, PO out, uint32_t decl,
     return step > 1 ? dz_snappy_win(in + h, n - h, out, decl, first) : dz_snappy(in + h, n - h, out, decl, first, step);
 }
 
-// crc32fast::hash of msg[0, n) (generic pointer: LDS or HBM), every lane; tab: slicing tables in LDS.
-SDB_DEV uint32_t dz_crc(const uint8_t *msg, uint64_t n, const uint32_t (*tab)[256]) {
-    if (n >= 4) return wave_crc32_lds(msg, (uint32_t)n, tab);
-    uint32_t x = 0xFFFFFFFFu;
-    for (uint32_t q = 0; q < n; q++) x = tab[0][(x ^ msg[q]) & 0xFF] ^ (x >> 8);
-    return x ^ 0xFFFFFFFFu;
-}
-
 __global__ __launch_bounds__(kDzThreads) void k_dz_run(DzArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     crc_slice_tables_to_lds((lu32 *)smem);
@@ -369,7 +345,7 @@ __global__ __launch_bounds__(kDzThreads) void k_dz_run(DzArgs a) {
         uint32_t ol = 0;
         const uint8_t *in = nullptr;
         uint64_t bl = 0;
-        if (e < s || e - s < 4 || e - s > 0xFFFFFFFFull) {
+        if (frame_corrupt(s, e)) {
             st = SDB_CORRUPT_BLOCK;
         } else {
             bl = e - s - 4;
@@ -384,27 +360,16 @@ __global__ __launch_bounds__(kDzThreads) void k_dz_run(DzArgs a) {
             } else {
                 in = a.blocks + s;
             }
-            const uint32_t stored = (uint32_t)in[bl] << 24 | (uint32_t)in[bl + 1] << 16 | (uint32_t)in[bl + 2] << 8 |
-                                    (uint32_t)in[bl + 3];
-            if (dz_crc(in, bl, tab) != stored) {
-                st = SDB_CHECKSUM_MISMATCH;  // validate_checksum (format/sst.rs:1029-1038)
-            } else if (slot == 0) {
-                st = dz_declared(a.codec, in, bl) < 0 ? SDB_DECOMPRESSION_ERROR : SDB_LIMIT_EXCEEDED;
-            } else if (o + slot > a.out_cap) {
-                st = SDB_INVALID_ARGUMENT;
-            } else {
+            // an empty slot: the plan found the length over kMaxBlockOut, or the header unreadable
+            st = frame_status(in, bl, tab, o, slot, a.out_cap, SDB_LIMIT_EXCEEDED);
+            if (st == SDB_LIMIT_EXCEEDED && dz_declared(a.codec, in, bl) < 0) st = SDB_DECOMPRESSION_ERROR;
+            if (!st) {
                 const uint32_t decl = (uint32_t)(slot - 4);
                 if (staged && decl <= kDzOut) {
                     st = dz_payload(a.codec, (const uint8_t *)in, (uint32_t)bl, img, decl, &ol, l, 64u);
                     dz_sync(true);
                     if (!st) {
-                        const uint32_t c = dz_crc(img, ol, tab);
-                        if (l == 0) {
-                            img[ol] = (uint8_t)(c >> 24);
-                            img[ol + 1] = (uint8_t)(c >> 16);
-                            img[ol + 2] = (uint8_t)(c >> 8);
-                            img[ol + 3] = (uint8_t)c;
-                        }
+                        frame_trailer(img, ol, tab);
                         dz_sync(true);
                         // 16-byte stores (unaligned in HBM, aligned in LDS), the < 16-byte tail by bytes
                         uint8_t *g = a.out + o;
@@ -425,22 +390,11 @@ __global__ __launch_bounds__(kDzThreads) void k_dz_run(DzArgs a) {
                     ol = (uint32_t)__shfl((int)w, 0, 64);
                     __threadfence_block();
                     dz_sync(true);
-                    if (!st) {
-                        const uint32_t c = dz_crc(g, ol, tab);
-                        if (l == 0) {
-                            g[ol] = (uint8_t)(c >> 24);
-                            g[ol + 1] = (uint8_t)(c >> 16);
-                            g[ol + 2] = (uint8_t)(c >> 8);
-                            g[ol + 3] = (uint8_t)c;
-                        }
-                    }
+                    if (!st) frame_trailer(g, ol, tab);
                 }
             }
         }
-        if (l == 0) {
-            a.out_end[k] = st ? o : o + ol + 4;
-            if (st) atomicMin(a.err, (unsigned long long)((k << 8) | (uint64_t)st));
-        }
+        frame_publish(a, k, o, ol, st);
         dz_sync(true);
     }
 }
@@ -472,31 +426,43 @@ uint64_t decompress_workspace_bytes(uint64_t nblocks) {
 
 static std::once_flag g_dz_once;
 
-// entropy-coded codecs (sdb_codec_ent.hip)
-hipError_t launch_ent_slots(uint32_t codec, const uint8_t *blocks, const uint64_t *block_off, uint64_t nblocks,
-                            uint64_t *slot, hipStream_t st);
-hipError_t launch_ent_run(uint32_t codec, const uint8_t *blocks, const uint64_t *block_off, uint64_t nblocks, uint8_t *out,
-                          uint64_t out_cap, const uint64_t *out_start, uint64_t *out_end, unsigned long long *err,
-                          hipStream_t st);
 static bool ent_codec(uint32_t codec) { return codec == SDB_CODEC_ZLIB || codec == SDB_CODEC_ZSTD; }
+
+static EntArgs dz_input(uint32_t codec, const uint8_t *blocks, const uint64_t *block_off, uint64_t nblocks) {
+    EntArgs a{};
+    a.codec = codec;
+    a.blocks = blocks;
+    a.block_off = block_off;
+    a.nblocks = nblocks;
+    return a;
+}
+static void dz_output(EntArgs &a, uint8_t *out, uint64_t out_cap, const uint64_t *out_start, uint64_t *out_end,
+                      unsigned long long *err) {
+    a.out = out;
+    a.out_cap = out_cap;
+    a.out_start = out_start;
+    a.out_end = out_end;
+    a.err = err;
+}
+
+// Z1 on the filled arguments: a.slot <- the blocks' slot bytes, pos <- their exclusive scan (nblocks + 1).
+static hipError_t dz_plan(const EntArgs &a, const DzPlanWs &p, uint64_t *pos, hipStream_t st) {
+    if (ent_codec(a.codec)) {
+        const hipError_t e = launch_ent_slots(a, st);
+        if (e != hipSuccess) return e;
+    } else {
+        hipLaunchKernelGGL(k_dz_plan, dim3((uint32_t)((a.nblocks + 256) / 256)), dim3(256), 0, st, (const DzArgs &)a);
+    }
+    return launch_excl_scan2(a.slot, a.slot, a.nblocks, p.tx, p.ty, pos, p.scratch, st);
+}
 
 hipError_t launch_decompress_plan(uint32_t codec, const uint8_t *blocks, const uint64_t *block_off, uint64_t nblocks,
                                   uint64_t *out_start, uint8_t *w, hipStream_t st) {
     DzPlanWs p;
     dz_plan_bind(p, nblocks, w);
-    DzArgs a{};
-    a.codec = codec;
-    a.blocks = blocks;
-    a.block_off = block_off;
-    a.nblocks = nblocks;
+    EntArgs a = dz_input(codec, blocks, block_off, nblocks);
     a.slot = p.slot;
-    if (ent_codec(codec)) {
-        const hipError_t e = launch_ent_slots(codec, blocks, block_off, nblocks, a.slot, st);
-        if (e != hipSuccess) return e;
-    } else {
-        hipLaunchKernelGGL(k_dz_plan, dim3((uint32_t)((nblocks + 256) / 256)), dim3(256), 0, st, a);
-    }
-    return launch_excl_scan2(a.slot, a.slot, nblocks, p.tx, p.ty, out_start, p.scratch, st);
+    return dz_plan(a, p, out_start, st);
 }
 
 hipError_t launch_decompress_run(uint32_t codec, const uint8_t *blocks, const uint64_t *block_off, uint64_t nblocks,
@@ -506,27 +472,12 @@ hipError_t launch_decompress_run(uint32_t codec, const uint8_t *blocks, const ui
         (void)hipFuncSetAttribute((const void *)k_dz_run, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kDzLds);
         (void)hipGetLastError();
     });
-    DzArgs a{};
-    a.codec = codec;
-    a.blocks = blocks;
-    a.block_off = block_off;
-    a.nblocks = nblocks;
-    a.out = out;
-    a.out_cap = out_cap;
-    a.out_start = out_start;
-    a.out_end = out_end;
-    a.err = err;
+    EntArgs a = dz_input(codec, blocks, block_off, nblocks);
+    dz_output(a, out, out_cap, out_start, out_end, err);
     hipLaunchKernelGGL(k_dz_init, dim3(1), dim3(64), 0, st, err);
-    if (ent_codec(codec)) return launch_ent_run(codec, blocks, block_off, nblocks, out, out_cap, out_start, out_end, err, st);
-    if (nblocks) {
-        int dev = 0, cus = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        uint64_t wgs = (nblocks + 15) / 16;
-        const uint64_t most = (uint64_t)(cus > 0 ? cus : 256) * 2;
-        if (wgs > most) wgs = most;
-        hipLaunchKernelGGL(k_dz_run, dim3((uint32_t)wgs), dim3(kDzThreads), kDzLds, st, a);
-    }
+    if (ent_codec(codec)) return launch_ent_run(a, st);
+    if (nblocks)
+        hipLaunchKernelGGL(k_dz_run, dim3(wgs_capped((nblocks + 15) / 16, 2)), dim3(kDzThreads), kDzLds, st, (const DzArgs &)a);
     return hipGetLastError();
 }
 
@@ -535,14 +486,6 @@ hipError_t launch_decompress_run(uint32_t codec, const uint8_t *blocks, const ui
 // once into a fixed slot of slot_bytes (out_start[k] = k * slot_bytes), lists the blocks whose output overflowed
 // their slot, and only those are planned and inflated again, packed after the slots.  The other codecs' plans
 // read a length header, so for them it is the plan and the run back to back on the stream.
-bool zl_once_supported();
-hipError_t launch_zl_once_slots(const uint8_t *blocks, const uint64_t *block_off, uint64_t nblocks, const uint32_t *list,
-                                const unsigned long long *nlist, uint64_t *slot, hipStream_t st);
-hipError_t launch_zl_once_run(int mode, const uint8_t *blocks, const uint64_t *block_off, uint64_t nblocks, uint8_t *out,
-                              uint64_t out_cap, const uint64_t *out_start, uint64_t *out_end, unsigned long long *err,
-                              const uint32_t *list, const unsigned long long *nlist, bool out_by_block, uint32_t *ovf_list,
-                              unsigned long long *ovf_count, uint32_t *dyn_list, unsigned long long *dyn_count,
-                              uint64_t *wres, hipStream_t st);
 
 // Decode-once's workspace begins with the plan's arrays: the codecs other than zlib hand it to the plan.
 struct DzOnceWs {
@@ -567,10 +510,6 @@ uint64_t decompress_once_workspace_bytes(uint64_t nblocks) {
     DzOnceWs o;
     return dz_once_bind(o, nblocks, nullptr);
 }
-
-#ifndef SDB_ZL_WIDE
-#define SDB_ZL_WIDE 1
-#endif
 
 __global__ void k_zo_init(uint64_t *out_start, uint64_t nblocks, uint64_t slot_bytes, unsigned long long *err,
                           unsigned long long *nlist, unsigned long long *ndyn) {
@@ -599,40 +538,43 @@ __global__ void k_zo_fix(uint64_t *pos, uint64_t *out_start, uint64_t nblocks, u
 hipError_t launch_decompress_once(uint32_t codec, const uint8_t *blocks, const uint64_t *block_off, uint64_t nblocks,
                                   uint64_t slot_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_start,
                                   uint64_t *out_end, unsigned long long *err, uint8_t *w, hipStream_t st) {
-    if (codec != SDB_CODEC_ZLIB || !zl_once_supported()) {
+    if (codec != SDB_CODEC_ZLIB) {
         const hipError_t e = launch_decompress_plan(codec, blocks, block_off, nblocks, out_start, w, st);
         if (e != hipSuccess) return e;
         return launch_decompress_run(codec, blocks, block_off, nblocks, out, out_cap, out_start, out_end, err, st);
     }
     DzOnceWs o;
     dz_once_bind(o, nblocks, w);
-    uint64_t *const slot = o.plan.slot, *const pos = o.pos, *const wres = o.wres;
-    unsigned long long *const nlist = o.nlist, *const ndyn = o.ndyn;
-    uint32_t *const list = o.list, *const dyn = o.dyn;
     const uint32_t g = (uint32_t)((nblocks + 256) / 256);
-    hipLaunchKernelGGL(k_zo_init, dim3(g), dim3(256), 0, st, out_start, nblocks, slot_bytes, err, nlist, ndyn);
-    hipError_t e;
-    if (SDB_ZL_WIDE) {
-        // 1. every block once into its slot, all 64 lanes decoding against the fixed code's shared tables;
-        //    blocks with dynamic-Huffman deflate blocks listed, then decoded by the per-decoder-table run into
-        //    their slots (out_start[block]); overflowed blocks listed by both
-        e = launch_zl_once_run(1, blocks, block_off, nblocks, out, out_cap, out_start, out_end, err, nullptr, nullptr,
-                               false, list, nlist, dyn, ndyn, wres, st);
-        if (e == hipSuccess)
-            e = launch_zl_once_run(0, blocks, block_off, nblocks, out, out_cap, out_start, out_end, err, dyn, ndyn, true,
-                                   list, nlist, nullptr, nullptr, nullptr, st);
-    } else {
-        // 1. every block once into its slot; the overflowed ones listed
-        e = launch_zl_once_run(0, blocks, block_off, nblocks, out, out_cap, out_start, out_end, err, nullptr, nullptr,
-                               false, list, nlist, nullptr, nullptr, nullptr, st);
-    }
+    hipLaunchKernelGGL(k_zo_init, dim3(g), dim3(256), 0, st, out_start, nblocks, slot_bytes, err, o.nlist, o.ndyn);
+    // one set of arguments; the passes differ in which blocks they take (list, nlist), whether a listed block's
+    // output goes to its own slot (out_by_block), and whether an overflowed slot is listed or fails (ovf_list)
+    EntArgs a = dz_input(codec, blocks, block_off, nblocks);
+    dz_output(a, out, out_cap, out_start, out_end, err);
+    a.slot = o.plan.slot;
+    a.ovf_count = o.nlist;
+    a.dyn_list = o.dyn;
+    a.dyn_count = o.ndyn;
+    a.wres = o.wres;
+    // 1. every block once into its slot, all 64 lanes decoding against the fixed code's shared tables;
+    //    blocks with dynamic-Huffman deflate blocks listed, then decoded by the per-decoder-table run into
+    //    their slots (out_start[block]); overflowed blocks listed by both
+    a.ovf_list = o.list;
+    hipError_t e = launch_zl_wide(a, st);
+    a.list = o.dyn;
+    a.nlist = o.ndyn;
+    a.out_by_block = true;
+    if (e == hipSuccess) e = launch_ent_run(a, st);
     // 2. the listed blocks' exact sizes, packed after the slots, and their inflate
-    if (e == hipSuccess) e = launch_zl_once_slots(blocks, block_off, nblocks, list, nlist, slot, st);
-    if (e == hipSuccess) e = launch_excl_scan2(slot, slot, nblocks, o.plan.tx, o.plan.ty, pos, o.plan.scratch, st);
+    a.list = o.list;
+    a.nlist = o.nlist;
+    a.out_by_block = false;
+    a.ovf_list = nullptr;
+    if (e == hipSuccess) e = dz_plan(a, o.plan, o.pos, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_zo_fix, dim3(g), dim3(256), 0, st, pos, out_start, nblocks, nblocks * slot_bytes, list, nlist);
-    return launch_zl_once_run(0, blocks, block_off, nblocks, out, out_cap, pos, out_end, err, list, nlist, false, nullptr,
-                              nullptr, nullptr, nullptr, nullptr, st);
+    hipLaunchKernelGGL(k_zo_fix, dim3(g), dim3(256), 0, st, o.pos, out_start, nblocks, nblocks * slot_bytes, o.list, o.nlist);
+    a.out_start = o.pos;
+    return launch_ent_run(a, st);
 }
 
 }  // namespace sdb

@@ -8,13 +8,18 @@
 // these kernels are checked against).
 //
 // Neither format says how long the output is before it is decoded, so both steps decode:
-//   E1 plan  one wave per block, lane 0 decodes in count mode (no stores; distances and offsets are
-//            still checked against the bytes produced) -> slot = length + 4, or 0 on an error.
-//   E2 run   one wave per block: the wave CRC32 of the stored bytes (validate_checksum), lane 0 decodes
-//            into the block's slot in HBM (matches read back its own stores), the wave CRC32 of the
-//            output, the CRC trailer and out_end.
-// (Zlib runs both steps with five decoders per wave, lanes 0-4 each on its own block: k_zl_plan_multi,
-// k_zl_run_multi; zstd runs one decoder per wave on all lanes, EntOut::wide and the *_wide table builds.)
+//   E1 plan  a decoder in count mode (no stores; distances and offsets are still checked against the
+//            bytes produced) -> slot = length + 4, or 0 on an error.  zstd (k_ent_plan): one wave per
+//            block, lane 0 decodes, and only frames without a Frame_Content_Size.  zlib
+//            (k_zl_plan_multi): five decoders per wave, lanes 0-4 each on a block of its own.
+//   E2 run   the wave CRC32 of the stored bytes (validate_checksum), the decode into the block's slot in
+//            HBM (matches read back the decoder's own stores), the wave CRC32 of the output, the CRC
+//            trailer and out_end.  zstd (k_ent_run): one wave per block, every lane runs the decoder
+//            with the same state and the copies and table builds are spread over the lanes
+//            (EntOut::wide, the *_wide builds).  zlib (k_zl_run_multi): five blocks per wave, the CRCs
+//            and Adler-32 by the whole wave one block after the other, lanes 0-4 decoding in between.
+//   decode-once (zlib): k_zl_wide, 64 decoders per wave on the fixed code's shared tables, and
+//            k_zl_verify, the wave-wide checks of what it decoded; the rest goes to k_zl_run_multi.
 // Entropy decoding is serial within a stream, so the parallelism is across blocks (a read_blocks range
 // holds hundreds).  Per wave, the LDS holds the code tables: deflate's canonical codes (count + symbols
 // by code order), zstd's three FSE sequence tables and the literal Huffman table.  zstd literals are
@@ -24,44 +29,11 @@
 #include <atomic>
 #include <mutex>
 
-#include "sdb_crc.h"
-#include "sdb_decode.h"
-#include "sdb_device.h"
+#include "sdb_codec.h"
 
 namespace sdb {
 
-#ifndef SDB_ZS_WFSE
-#define SDB_ZS_WFSE 1
-#endif
-#ifndef SDB_ZS_WHUF
-#define SDB_ZS_WHUF 1
-#endif
 constexpr uint32_t kEntThreads = 768;  // 12 waves per workgroup
-constexpr uint64_t kEntMaxOut = 64ull << 20;
-
-struct EntArgs {
-    uint32_t codec;
-    const uint8_t *blocks;
-    const uint64_t *block_off;
-    uint64_t nblocks;
-    uint64_t *slot;             // plan: per block slot bytes
-    uint8_t *out;
-    uint64_t out_cap;
-    const uint64_t *out_start;  // nblocks + 1
-    uint64_t *out_end;
-    unsigned long long *err;
-    // zlib decode-once (launch_decompress_once): slot i decodes block list[i] (i < *nlist) instead of block
-    // i; the optimistic run lists the blocks whose output overflowed their slot instead of failing them,
-    // the wide run those with dynamic-Huffman blocks; out_by_block: a list pass writes to out_start[list[i]]
-    const uint32_t *list;
-    const unsigned long long *nlist;
-    uint32_t *ovf_list;
-    unsigned long long *ovf_count;
-    uint32_t *dyn_list;
-    unsigned long long *dyn_count;
-    bool out_by_block;
-    uint64_t *wres;  // the wide pass's per-block results for k_zl_verify: 2 words per block
-};
 
 // ------------------------------------------------------------------------------------------------
 // per-wave LDS tables
@@ -70,10 +42,9 @@ struct FseCell {
     uint8_t sym, nb;
     uint16_t base;
 };
-#ifndef SDB_ZL_FAST_DIST
-#define SDB_ZL_FAST_DIST 7
-#endif
-constexpr int kFastLit = 9, kFastDist = SDB_ZL_FAST_DIST;  // the fast tables' index bits
+// the fast tables' index bits: 9 holds every fixed literal / length code; 7 for distances keeps a table set
+// under 2 KB, which is what makes room for five decoders per wave (kZpD)
+constexpr int kFastLit = 9, kFastDist = 7;
 template <int N>  // N: the alphabet's size (lengths 288, distances 32, code lengths 19)
 struct CanonT {
     uint16_t count[16];
@@ -120,8 +91,7 @@ struct EntOut {
     uint64_t len, cap;
     bool bad;
     bool wide;
-    bool adler_defer;     // zlib: leave the Adler-32 check to the caller (adler_want, have_adler)
-    bool have_adler;
+    bool have_adler;      // zlib: the stream's Adler-32 trailer was read (adler_want); the caller checks it
     uint32_t adler_want;
     SDB_DEV void flush() {}  // (EntOutWC: its pending bytes)
     SDB_DEV uint32_t lane() const { return wide ? (uint32_t)lane_id() : 0u; }
@@ -483,15 +453,9 @@ SDB_DEV void zl_fixed_tables(ZTab &t, uint32_t tid, uint32_t nt) {
     }
 }
 
-#ifndef SDB_ZL_UNIFORM_REFILL
-#define SDB_ZL_UNIFORM_REFILL 1
-#endif
-#ifndef SDB_ZL_REFILL_AT
-#define SDB_ZL_REFILL_AT 9  // (bits under which a wave refills: a literal / length code needs at most 9 here)
-#endif
-// SHARED: t holds the fixed code's tables (zl_fixed_tables), read-only and shared by the decoders of a
-// workgroup; a dynamic-Huffman block returns kZDyn (its decoder has no tables of its own)
-template <bool SHARED = false, class Out>
+constexpr int kZRefillAt = 9;  // bits under which a wave refills: the fast table's literal / length codes need 9
+// one decoder's inflate, the code tables of each deflate block built in t: kZOk, kZTrunc or kZErr
+template <class Out>
 SDB_DEV int inflate_raw(LsbBits &s, Out &o, ZTab &t) {
     uint32_t last = 0;
     uint8_t *lens = t.lens;
@@ -532,13 +496,8 @@ SDB_DEV int inflate_raw(LsbBits &s, Out &o, ZTab &t) {
             continue;
         }
         if (type == 3) return kZErr;
-        if constexpr (SHARED) {
-            if (type == 2) return kZDyn;
-        }
         int nlen, ndist;
-        if (SHARED) {
-            // the fixed code's tables are already in t
-        } else if (type == 1) {
+        if (type == 1) {
             for (int i = 0; i < 288; i++) lens[i] = i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : 8;
             for (int i = 0; i < 32; i++) lens[288 + i] = 5;
             nlen = 288;
@@ -586,24 +545,18 @@ SDB_DEV int inflate_raw(LsbBits &s, Out &o, ZTab &t) {
             if (lens[256] == 0) return kZErr;
             for (int q = ndist - 1; q >= 0; q--) lens[288 + q] = lens[nlen + q];
         }
-        if (!SHARED) {
-            if (canon_build(t.lit, lens, nlen) || canon_build(t.dist, lens + 288, ndist)) return kZErr;
-            canon_fast<kFastLit>(t.lit, t.fast_lit);
-            canon_fast<kFastDist>(t.dist, t.fast_dist);
-        }
+        if (canon_build(t.lit, lens, nlen) || canon_build(t.dist, lens + 288, ndist)) return kZErr;
+        canon_fast<kFastLit>(t.lit, t.fast_lit);
+        canon_fast<kFastDist>(t.dist, t.fast_dist);
         // a symbol through the fast table (mask: its size - 1) when its code is short enough and the bits
         // are there
         auto fast_decode = [&](const uint16_t *fast, uint32_t mask, const auto &h) -> int {
-            if constexpr (SHARED || SDB_ZL_UNIFORM_REFILL) {
-                // a wave of decoders: when any lane runs low, every lane here refills and stores its pending
-                // output bytes, so the loads and stores a refill's wait covers were issued a refill ago
-                // (lane by lane, some lane's fresh load or store would be waited on at every symbol)
-                if (__ballot(s.cnt < SDB_ZL_REFILL_AT)) {
-                    s.refill();
-                    o.flush();
-                }
-            } else if (s.cnt < 9) {
+            // a wave of decoders: when any lane runs low, every lane here refills and stores its pending
+            // output bytes, so the loads and stores a refill's wait covers were issued a refill ago
+            // (lane by lane, some lane's fresh load or store would be waited on at every symbol)
+            if (__ballot(s.cnt < kZRefillAt)) {
                 s.refill();
+                o.flush();
             }
             const uint16_t e = fast[s.buf & mask];
             const int L = e >> 12;
@@ -640,54 +593,39 @@ SDB_DEV int inflate_raw(LsbBits &s, Out &o, ZTab &t) {
     return kZOk;
 }
 
-// 0 or -1; Adler-32 checked when the bytes are kept
-// 0, -1, or (SHARED) 1: a dynamic-Huffman block, left to a decoder with its own tables
-template <bool SHARED = false, class Out>
-SDB_DEV int zlib_decode(const uint8_t *in, uint64_t n, Out &o, ZTab &t) {
-    if (n < 2) return 0;
+// the zlib header (RFC 1950): deflate, a window of at most 32 KiB, the check bits, no preset dictionary
+SDB_DEV bool zlib_header_ok(const uint8_t *in) {
     const uint32_t cmf = in[0], flg = in[1];
-    if ((cmf & 0x0F) != 8 || (cmf >> 4) > 7 || ((cmf << 8) | flg) % 31 != 0 || (flg & 0x20)) return -1;
-    LsbBits s{in, n, 2, 0, 0, 0, 0};
-    s.start();
-    const int r = inflate_raw<SHARED>(s, o, t);
-    if (r == kZDyn) return 1;
-    if (r == kZErr) return -1;
-    if (r == kZTrunc) return 0;
+    return (cmf & 0x0F) == 8 && (cmf >> 4) <= 7 && ((cmf << 8) | flg) % 31 == 0 && !(flg & 0x20);
+}
+// the Adler-32 trailer after the last deflate block -> o.have_adler / o.adler_want, for the caller to check
+// (a whole wave, after the decode); a stream that ends inside it has none
+template <class Out>
+SDB_DEV void zlib_trailer(LsbBits &s, Out &o) {
     s.align();
     uint32_t a = 0;
     for (int i = 0; i < 4; i++) {
         uint32_t b;
-        if (!s.get(8, b)) return 0;
+        if (!s.get(8, b)) return;
         a = a << 8 | b;
     }
-    if (o.p && o.adler_defer) {  // the caller checks it (a whole wave, after the decode)
-        o.have_adler = true;
-        o.adler_want = a;
-    } else if (o.p && o.wide) {
-        // Adler-32 over n bytes as sums: A = 1 + sum b_i, B = n + sum (n - i) b_i (mod 65521), lane l
-        // taking bytes l, l + 64, ... (coalesced); (n - i) b_i < 2^34 and a lane adds at most 2^20 of
-        // them per 64 MiB, so the u64 sums never wrap
-        const uint64_t n = o.len;
-        uint64_t sa = 0, sb = 0;
-        for (uint64_t i = (uint64_t)lane_id(); i < n; i += 64) {
-            const uint64_t b = o.p[i];
-            sa += b;
-            sb += (n - i) * b;
-        }
-        sa = wave_sum(sa);
-        sb = wave_sum(sb);
-        const uint32_t x = (uint32_t)((1 + sa) % 65521u), y = (uint32_t)((n % 65521u + sb % 65521u) % 65521u);
-        if ((y << 16 | x) != a) return -1;
-    } else if (o.p) {
-        uint32_t x = 1, y = 0;
-        for (uint64_t i = 0; i < o.len; i++) {
-            x += o.p[i];
-            if (x >= 65521u) x -= 65521u;
-            y += x;
-            if (y >= 65521u) y -= 65521u;
-        }
-        if ((y << 16 | x) != a) return -1;
-    }
+    o.have_adler = true;
+    o.adler_want = a;
+}
+
+// 0 or -1 (a cut stream keeps what it decoded: 0); the Adler-32 trailer, when read, is left in o
+template <class Out>
+SDB_DEV int zlib_decode(const uint8_t *in, uint64_t n, Out &o, ZTab &t) {
+    if (n < 2) return 0;
+    if (!zlib_header_ok(in)) return -1;
+    LsbBits s{in, n, 2, 0, 0, 0, 0};
+    s.start();
+    const int r = inflate_raw(s, o, t);
+    // (two early returns, not one test around the trailer: written that way k_zl_plan_multi spilled 28 more
+    // SGPRs and the plan went from 8.8 to 11.0 ms)
+    if (r == kZErr) return -1;
+    if (r == kZTrunc) return 0;
+    zlib_trailer(s, o);
     return 0;
 }
 
@@ -696,11 +634,11 @@ SDB_DEV int zlib_decode(const uint8_t *in, uint64_t n, Out &o, ZTab &t) {
 // of a pending match — so lanes that meet a match do not hold the others through its whole copy (the
 // divergent literal and match paths of inflate_raw ran one after the other for all 64 lanes).  Refills
 // and the pending output stores happen at wave-uniform points (any lane under 32 bits: every step needs
-// at most 9 + 5 + 5 + 13).  Returns what zlib_decode<true> returns: 0, -1, or 1 for a dynamic block.
+// at most 9 + 5 + 5 + 13).  Returns zlib_decode's 0 or -1, or 1 for a dynamic-Huffman block: left to a
+// decoder with tables of its own.
 SDB_DEV int zlib_decode_wide(const uint8_t *in, uint64_t n, EntOutRing &o, const ZTab &t) {
     if (n < 2) return 0;
-    const uint32_t cmf = in[0], flg = in[1];
-    if ((cmf & 0x0F) != 8 || (cmf >> 4) > 7 || ((cmf << 8) | flg) % 31 != 0 || (flg & 0x20)) return -1;
+    if (!zlib_header_ok(in)) return -1;
     LsbBits s{in, n, 2, 0, 0, 0, 0};
     s.start();
     int r = kZOk;
@@ -838,15 +776,7 @@ SDB_DEV int zlib_decode_wide(const uint8_t *in, uint64_t n, EntOutRing &o, const
     if (r == kZDyn) return 1;
     if (r == kZErr) return -1;
     if (r == kZTrunc) return 0;
-    s.align();
-    uint32_t a = 0;
-    for (int i = 0; i < 4; i++) {
-        uint32_t b;
-        if (!s.get(8, b)) return 0;
-        a = a << 8 | b;
-    }
-    o.have_adler = true;  // (k_zl_verify checks it)
-    o.adler_want = a;
+    zlib_trailer(s, o);  // (k_zl_verify checks it)
     return 0;
 }
 
@@ -946,7 +876,7 @@ SDB_DEV int fse_build(FseCell *t, int16_t *norm, uint16_t *next, int nsym, int a
 // symbol's cells in cell order (a ballot per symbol).  Other tables: the serial build.
 __device__ __attribute__((noinline)) int fse_build_wide(FseCell *t, int16_t *norm, uint16_t *next, int nsym, int al) {
     const int size = 1 << al;
-    if (!SDB_ZS_WFSE || size > 64 || nsym > 64) return fse_build(t, norm, next, nsym, al);
+    if (size > 64 || nsym > 64) return fse_build(t, norm, next, nsym, al);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // norm, as every lane stored it
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -1162,7 +1092,7 @@ SDB_DEV int huf_read(EntLds &t, const uint8_t *in, uint64_t n, int *maxbits, boo
         const int nb = (nw + 1) / 2;
         if ((uint64_t)nb + 1 > n) return -1;
         for (int i = 0; i < nw; i++) w[i] = (i & 1) ? (in[1 + i / 2] & 15) : (in[1 + i / 2] >> 4);
-        if (wide && SDB_ZS_WHUF ? huf_from_weights_wide(t, nw, maxbits) : huf_from_weights(t, nw, maxbits)) return -1;
+        if (wide ? huf_from_weights_wide(t, nw, maxbits) : huf_from_weights(t, nw, maxbits)) return -1;
         return 1 + nb;
     }
     if ((uint64_t)hb + 1 > n || hb == 0) return -1;
@@ -1196,7 +1126,7 @@ SDB_DEV int huf_read(EntLds &t, const uint8_t *in, uint64_t n, int *maxbits, boo
             break;
         }
     }
-    if (wide && SDB_ZS_WHUF ? huf_from_weights_wide(t, nw, maxbits) : huf_from_weights(t, nw, maxbits)) return -1;
+    if (wide ? huf_from_weights_wide(t, nw, maxbits) : huf_from_weights(t, nw, maxbits)) return -1;
     return 1 + hb;
 }
 
@@ -1643,24 +1573,16 @@ SDB_DEV int zstd_frames_size(const uint8_t *in, uint64_t n, uint64_t *total) {
         }
         // an untrusted header: a content size that would carry the sum past the output bound (or wrap it) is
         // malformed (a size its blocks do not produce is rejected by the run, zstd_decode)
-        if (fcs > kEntMaxOut - sum) return -1;
+        if (fcs > kMaxBlockOut - sum) return -1;
         sum += fcs;
     }
     *total = sum;
     return 0;
 }
 
-// one codec per kernel instance (ZL: zlib, else zstd), so neither decoder's registers weigh on the other's
-template <bool ZL>
-SDB_DEV int ent_decode(const uint8_t *in, uint64_t n, EntOut &o, EntLds &t) {
-    if constexpr (ZL) return zlib_decode(in, n, o, t.z);
-    else return zstd_decode(in, n, o, t);
-}
-
 // ------------------------------------------------------------------------------------------------
-// kernels
+// kernels (zstd: k_ent_*; zlib: k_zl_*, so neither decoder's registers weigh on the other's)
 // ------------------------------------------------------------------------------------------------
-template <bool ZL>
 __global__ __launch_bounds__(kEntThreads) void k_ent_plan(EntArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t l = (uint32_t)lane_id(), wave = threadIdx.x >> 6;
@@ -1675,11 +1597,11 @@ __global__ __launch_bounds__(kEntThreads) void k_ent_plan(EntArgs a) {
             const uint64_t s = a.block_off[k], e = a.block_off[k + 1];
             uint64_t fsz = 0;
             if (e >= s && e - s >= 4) {
-                if (!ZL && !zstd_frames_size(a.blocks + s, e - s - 4, &fsz)) {
+                if (!zstd_frames_size(a.blocks + s, e - s - 4, &fsz)) {
                     slot = fsz + 4;
                 } else {
-                    EntOut o{nullptr, 0, kEntMaxOut, false, false};
-                    if (!ent_decode<ZL>(a.blocks + s, e - s - 4, o, t) && !o.bad) slot = o.len + 4;
+                    EntOut o{nullptr, 0, kMaxBlockOut, false, false};
+                    if (!zstd_decode(a.blocks + s, e - s - 4, o, t) && !o.bad) slot = o.len + 4;
                 }
             }
         }
@@ -1687,19 +1609,10 @@ __global__ __launch_bounds__(kEntThreads) void k_ent_plan(EntArgs a) {
     }
 }
 
-// crc32fast::hash of msg[0, n), every lane (tab: slicing tables in LDS)
-SDB_DEV uint32_t ent_crc(const uint8_t *msg, uint64_t n, const uint32_t (*tab)[256]) {
-    if (n >= 4) return wave_crc32_lds(msg, (uint32_t)n, tab);
-    uint32_t x = 0xFFFFFFFFu;
-    for (uint32_t q = 0; q < n; q++) x = tab[0][(x ^ msg[q]) & 0xFF] ^ (x >> 8);
-    return x ^ 0xFFFFFFFFu;
-}
-
-template <bool ZL>
 __global__ __launch_bounds__(kEntThreads) void k_ent_run(EntArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     crc_slice_tables_to_lds((lu32 *)smem);
-    const uint32_t l = (uint32_t)lane_id(), wave = threadIdx.x >> 6;
+    const uint32_t wave = threadIdx.x >> 6;
     EntLds &t = *(EntLds *)(smem + 8 * 1024 + wave * kEntWaveLds);
     seq_codes_to_lds(t);
     __syncthreads();
@@ -1710,107 +1623,35 @@ __global__ __launch_bounds__(kEntThreads) void k_ent_run(EntArgs a) {
         const uint64_t slot = a.out_start[k + 1] - o;
         int st = 0;
         uint64_t ol = 0;
-        if (e < s || e - s < 4 || e - s > 0xFFFFFFFFull) {
+        if (frame_corrupt(s, e)) {
             st = SDB_CORRUPT_BLOCK;
         } else {
             const uint64_t bl = e - s - 4;
             const uint8_t *in = a.blocks + s;
-            const uint32_t stored = (uint32_t)in[bl] << 24 | (uint32_t)in[bl + 1] << 16 | (uint32_t)in[bl + 2] << 8 |
-                                    (uint32_t)in[bl + 3];
-            if (ent_crc(in, bl, tab) != stored) {
-                st = SDB_CHECKSUM_MISMATCH;  // validate_checksum (format/sst.rs:1029-1038)
-            } else if (slot == 0) {
-                st = SDB_DECOMPRESSION_ERROR;
-            } else if (o + slot > a.out_cap) {
-                st = SDB_INVALID_ARGUMENT;
-            } else {
+            st = frame_status(in, bl, tab, o, slot, a.out_cap, SDB_DECOMPRESSION_ERROR);
+            if (!st) {
                 // every lane runs the decoder (same state; the copies spread over the lanes, EntOut::wide)
                 EntOut out{a.out + o, 0, slot - 4, false, true};
-                const int r = ent_decode<ZL>(in, bl, out, t) || out.bad ? SDB_DECOMPRESSION_ERROR : 0;
+                const int r = zstd_decode(in, bl, out, t) || out.bad ? SDB_DECOMPRESSION_ERROR : 0;
                 st = __shfl(r, 0, 64);
                 ol = (uint64_t)__shfl((long long)out.len, 0, 64);
                 __threadfence_block();
                 __builtin_amdgcn_wave_barrier();
-                if (!st) {
-                    const uint32_t c = ent_crc(a.out + o, ol, tab);
-                    if (l == 0) {
-                        uint8_t *g = a.out + o;
-                        g[ol] = (uint8_t)(c >> 24);
-                        g[ol + 1] = (uint8_t)(c >> 16);
-                        g[ol + 2] = (uint8_t)(c >> 8);
-                        g[ol + 3] = (uint8_t)c;
-                    }
-                }
+                if (!st) frame_trailer(a.out + o, ol, tab);
             }
         }
-        if (l == 0) {
-            a.out_end[k] = st ? o : o + ol + 4;
-            if (st) atomicMin(a.err, (unsigned long long)((k << 8) | (uint64_t)st));
-        }
+        frame_publish(a, k, o, ol, st);
         __builtin_amdgcn_wave_barrier();
     }
 }
 
-// Zlib has smaller code tables than zstd (ZTab, 4.3 KB), which leaves room in every wave's LDS for the
-// compressed block itself: the bit reader's refills then hit LDS instead of HBM, one dependent round
-// trip per 56 bits less.  Blocks over the stage are read from HBM as before.
-constexpr uint32_t kZThreads = 1024;  // 16 waves per workgroup
-constexpr uint32_t kZStage = 4352;
-struct ZWave {
-    ZTab t;
-    uint8_t in[kZStage];
-};
-constexpr uint32_t kZWaveLds = (sizeof(ZWave) + 15) & ~15u;
-constexpr uint32_t kZLds = 8 * 1024 + (kZThreads / 64) * kZWaveLds;
-static_assert(kZLds <= 160 * 1024, "zlib decoder LDS");
-
-// the block's bytes [g, g + n) staged in the wave's LDS (16-byte granules; the returned pointer is
-// byte 0), or g itself when they do not fit.  Called by the whole wave.
-SDB_DEV const uint8_t *zl_stage(const uint8_t *g, uint64_t n, uint8_t *buf) {
-    const uintptr_t a0 = (uintptr_t)g & ~(uintptr_t)15;
-    const uint32_t off = (uint32_t)((uintptr_t)g & 15);
-    if (off + n + 15 > kZStage) return g;
-    const uint32_t ng = (uint32_t)((off + n + 15) >> 4);
-    for (uint32_t q = (uint32_t)lane_id(); q < ng; q += 64) ((uint4 *)buf)[q] = ((const uint4 *)a0)[q];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    return buf + off;
-}
-
-__global__ __launch_bounds__(kZThreads) void k_zl_plan(EntArgs a) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const uint32_t l = (uint32_t)lane_id(), wave = threadIdx.x >> 6;
-    ZWave &zw = *(ZWave *)(smem + 8 * 1024 + wave * kZWaveLds);
-    const uint64_t nw = (uint64_t)gridDim.x * (blockDim.x >> 6);
-    for (uint64_t k = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wave; k <= a.nblocks; k += nw) {
-        uint64_t slot = 0;
-        if (k < a.nblocks) {
-            const uint64_t s = a.block_off[k], e = a.block_off[k + 1];
-            if (e >= s && e - s >= 4) {
-                const uint8_t *in = zl_stage(a.blocks + s, e - s - 4, zw.in);
-                if (l == 0) {
-                    EntOut o{nullptr, 0, kEntMaxOut, false, false};
-                    if (!zlib_decode(in, e - s - 4, o, zw.t) && !o.bad) slot = o.len + 4;
-                }
-            }
-        }
-        if (l == 0) a.slot[k] = slot;
-        __builtin_amdgcn_wave_barrier();
-    }
-}
-
-// The count-mode plan with several decoders per wave: lanes 0 .. D - 1 each decode their own block
-// with their own code tables, reading the compressed bytes from HBM (the plan's speed tracks the number
-// of decoders per CU, not where its input lives).
-#ifndef SDB_ZL_PLAN_D
-#define SDB_ZL_PLAN_D 5
-#endif
-constexpr uint32_t kZpD = SDB_ZL_PLAN_D, kZpTab = (sizeof(ZTab) + 15) & ~15u;
-#ifndef SDB_ZL_WAVES
-#define SDB_ZL_WAVES 14
-#endif
-constexpr uint32_t kZpThreads = 64 * SDB_ZL_WAVES;  // 70 decoders per workgroup (CU)
+// The zlib kernels run several decoders per wave: the deflate state machine's speed tracks the number of
+// decoders per CU, not where its input lives, and LDS (a code-table set per decoder) is what bounds them.
+// The count-mode plan: lanes 0 .. kZpD - 1 each decode their own block with their own code tables, reading
+// the compressed bytes from HBM.
+constexpr uint32_t kZpD = 5;  // decoders per wave: what 14 waves' table sets leave room for (four: run 15.6 against 13.4 ms)
+constexpr uint32_t kZpTab = (sizeof(ZTab) + 15) & ~15u;
+constexpr uint32_t kZpThreads = 64 * 14;  // 14 waves, 70 decoders per workgroup (CU): 10 / 12 / 16 waves measured slower
 constexpr uint32_t kZpLds = (kZpThreads / 64) * kZpD * kZpTab;
 static_assert(kZpLds <= 160 * 1024, "zlib plan LDS");
 __global__ __launch_bounds__(kZpThreads) void k_zl_plan_multi(EntArgs a) {
@@ -1826,7 +1667,7 @@ __global__ __launch_bounds__(kZpThreads) void k_zl_plan_multi(EntArgs a) {
             const uint64_t b = a.list ? (uint64_t)a.list[k] : k;
             const uint64_t s = a.block_off[b], e = a.block_off[b + 1];
             if (e >= s && e - s >= 4) {
-                EntOut o{nullptr, 0, kEntMaxOut, false, false};
+                EntOut o{nullptr, 0, kMaxBlockOut, false, false};
                 if (!zlib_decode(a.blocks + s, e - s - 4, o, t) && !o.bad) slot = o.len + 4;
             }
         }
@@ -1834,7 +1675,15 @@ __global__ __launch_bounds__(kZpThreads) void k_zl_plan_multi(EntArgs a) {
     }
 }
 
-// Adler-32 of p[0, n) by the whole wave (the sums of zlib_decode's wide path), in every lane
+// Adler-32 over n bytes as sums: A = 1 + sum b_i, B = n + sum (n - i) b_i (mod 65521).  (n - i) b_i < 2^34
+// and a lane adds at most 2^20 of them per 64 MiB, so the lanes' u64 sums sa, sb never wrap.
+SDB_DEV uint32_t wave_adler32_close(uint64_t sa, uint64_t sb, uint64_t n) {
+    sa = wave_sum(sa);
+    sb = wave_sum(sb);
+    const uint32_t x = (uint32_t)((1 + sa) % 65521u), y = (uint32_t)((n % 65521u + sb % 65521u) % 65521u);
+    return y << 16 | x;
+}
+// Adler-32 of p[0, n) by the whole wave, in every lane: lane l takes bytes l, l + 64, ... (coalesced)
 SDB_DEV uint32_t wave_adler32(const uint8_t *p, uint64_t n) {
     uint64_t sa = 0, sb = 0;
     for (uint64_t i = (uint64_t)lane_id(); i < n; i += 64) {
@@ -1842,10 +1691,7 @@ SDB_DEV uint32_t wave_adler32(const uint8_t *p, uint64_t n) {
         sa += b;
         sb += (n - i) * b;
     }
-    sa = wave_sum(sa);
-    sb = wave_sum(sb);
-    const uint32_t x = (uint32_t)((1 + sa) % 65521u), y = (uint32_t)((n % 65521u + sb % 65521u) % 65521u);
-    return y << 16 | x;
+    return wave_adler32_close(sa, sb, n);
 }
 // The same with lane l summing the 64-byte segments l, l + 64, ... from four 16-byte loads each, all in
 // flight before the sums (k_zl_verify: one latency per 4 KiB instead of one per 64 bytes; more VGPRs)
@@ -1886,24 +1732,15 @@ SDB_DEV uint32_t wave_adler32_seg(const uint8_t *p, uint64_t n) {
         sa += a32;
         sb += (uint64_t)(n - base - 63) * a32 + b32;
     }
-    sa = wave_sum(sa);
-    sb = wave_sum(sb);
-    const uint32_t x = (uint32_t)((1 + sa) % 65521u), y = (uint32_t)((n % 65521u + sb % 65521u) % 65521u);
-    return y << 16 | x;
+    return wave_adler32_close(sa, sb, n);
 }
 
 // The run the same way: each wave takes kZpD blocks, checks their stored CRCs one after the other with
-// the whole wave, lets lanes 0 .. kZpD - 1 decode one block each (copies and Adler-32 on that lane), then
-// computes and appends the output CRCs with the whole wave again.
-#ifndef SDB_ZL_WC
-#define SDB_ZL_WC 1
-#endif
-#ifndef SDB_ZL_RUN_MULTI
-#define SDB_ZL_RUN_MULTI 1
-#endif
+// the whole wave, lets lanes 0 .. kZpD - 1 decode one block each (its copies on that lane, literals gathered
+// into 8-byte stores: EntOutWC), then checks the Adler-32 trailers and computes and appends the output CRCs
+// with the whole wave again.
 constexpr uint32_t kZrLds = 8 * 1024 + kZpLds;
 static_assert(kZrLds <= 160 * 1024, "zlib run LDS");
-template <bool>
 __global__ __launch_bounds__(kZpThreads) void k_zl_run_multi(EntArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     crc_slice_tables_to_lds((lu32 *)smem);
@@ -1927,18 +1764,9 @@ __global__ __launch_bounds__(kZpThreads) void k_zl_run_multi(EntArgs a) {
             const uint64_t b = blk(k);
             const uint64_t s = a.block_off[b], e = a.block_off[b + 1], o = a.out_start[oix(k, b)];
             const uint64_t slot = a.out_start[oix(k, b) + 1] - o;
-            int sj = 0;
-            if (e < s || e - s < 4 || e - s > 0xFFFFFFFFull) {
-                sj = SDB_CORRUPT_BLOCK;
-            } else {
-                const uint64_t bl = e - s - 4;
-                const uint8_t *g = a.blocks + s;
-                const uint32_t stored = (uint32_t)g[bl] << 24 | (uint32_t)g[bl + 1] << 16 | (uint32_t)g[bl + 2] << 8 |
-                                        (uint32_t)g[bl + 3];
-                if (ent_crc(g, bl, tab) != stored) sj = SDB_CHECKSUM_MISMATCH;
-                else if (slot == 0) sj = SDB_DECOMPRESSION_ERROR;
-                else if (o + slot > a.out_cap) sj = SDB_INVALID_ARGUMENT;
-            }
+            const int sj = frame_corrupt(s, e) ? SDB_CORRUPT_BLOCK
+                                               : frame_status(a.blocks + s, e - s - 4, tab, o, slot, a.out_cap,
+                                                              SDB_DECOMPRESSION_ERROR);
             if (l == j) st = sj;
         }
         // 2. lane j decodes block k0 + j (its Adler-32 checked below by the whole wave); optimistic slots: an
@@ -1950,24 +1778,13 @@ __global__ __launch_bounds__(kZpThreads) void k_zl_run_multi(EntArgs a) {
             const uint64_t b = blk(kl);
             const uint64_t s = a.block_off[b], e = a.block_off[b + 1], o = a.out_start[oix(kl, b)];
             const uint64_t slot = a.out_start[oix(kl, b) + 1] - o;
-            bool bad = false;
-            int r;
-            if (SDB_ZL_WC) {
-                EntOutWC out{{a.out + o, 0, slot - 4, false, false, true, false, 0}, 0, 0};
-                r = zlib_decode(a.blocks + s, e - s - 4, out, t);
-                out.flush();
-                bad = out.bad;
-                ol = out.len;
-                have = out.have_adler ? 1u : 0u;
-                want = out.adler_want;
-            } else {
-                EntOut out{a.out + o, 0, slot - 4, false, false, true, false, 0};
-                r = zlib_decode(a.blocks + s, e - s - 4, out, t);
-                bad = out.bad;
-                ol = out.len;
-                have = out.have_adler ? 1u : 0u;
-                want = out.adler_want;
-            }
+            EntOutWC out{{a.out + o, 0, slot - 4, false, false, false, 0}, 0, 0};
+            const int r = zlib_decode(a.blocks + s, e - s - 4, out, t);
+            out.flush();
+            const bool bad = out.bad;
+            ol = out.len;
+            have = out.have_adler ? 1u : 0u;
+            want = out.adler_want;
             st = r || bad ? SDB_DECOMPRESSION_ERROR : 0;
             if (optimistic && bad) {
                 st = 0;
@@ -1993,20 +1810,8 @@ __global__ __launch_bounds__(kZpThreads) void k_zl_run_multi(EntArgs a) {
             }
             if (!sj && __shfl((int)have, (int)j, 64) && wave_adler32(a.out + o, olj) != (uint32_t)__shfl((int)want, (int)j, 64))
                 sj = SDB_DECOMPRESSION_ERROR;
-            if (!sj) {
-                const uint32_t c = ent_crc(a.out + o, olj, tab);
-                if (l == 0) {
-                    uint8_t *gw = a.out + o;
-                    gw[olj] = (uint8_t)(c >> 24);
-                    gw[olj + 1] = (uint8_t)(c >> 16);
-                    gw[olj + 2] = (uint8_t)(c >> 8);
-                    gw[olj + 3] = (uint8_t)c;
-                }
-            }
-            if (l == 0) {
-                a.out_end[b] = sj ? o : o + olj + 4;
-                if (sj) atomicMin(a.err, (unsigned long long)((b << 8) | (uint64_t)sj));
-            }
+            if (!sj) frame_trailer(a.out + o, olj, tab);
+            frame_publish(a, b, o, olj, sj);
         }
         __builtin_amdgcn_wave_barrier();
     }
@@ -2020,10 +1825,6 @@ __global__ __launch_bounds__(kZpThreads) void k_zl_run_multi(EntArgs a) {
 // 64 times over).  Blocks whose first deflate block is dynamic (or that meet one later), and streams too
 // short for the bit reader's trailer rule, are listed (a.dyn_list) for k_zl_run_multi; blocks past their
 // slot, as there, for the exact-size pass (a.ovf_list).
-#ifndef SDB_ZL_WIDE_D
-#define SDB_ZL_WIDE_D 64
-#endif
-constexpr uint32_t kZwD = SDB_ZL_WIDE_D;
 constexpr uint32_t kZwThreads = 256, kZwRing = 256 * 64;  // a wave's history rings (EntOutRing)
 constexpr uint32_t kZwLds = kZpTab + (kZwThreads / 64) * kZwRing;
 static_assert(kZpTab % 16 == 0, "ZTab copies as 16-byte words");
@@ -2037,10 +1838,9 @@ __global__ __launch_bounds__(kZwThreads) void k_zl_wide(EntArgs a) {
     zl_fixed_tables(t, threadIdx.x, blockDim.x);
     __syncthreads();
     const uint64_t n = a.nblocks;
-    // kZwD decoding lanes per wave (the rest idle): fewer lanes, more waves to overlap the refill latency
-    const uint64_t bstep = (uint64_t)gridDim.x * (blockDim.x >> 6) * kZwD;
-    for (uint64_t b0 = ((uint64_t)blockIdx.x * (blockDim.x >> 6) + wave) * kZwD; b0 < n; b0 += bstep) {
-        const uint64_t b = l < kZwD ? b0 + l : n;
+    const uint64_t bstep = (uint64_t)gridDim.x * (blockDim.x >> 6) * 64;
+    for (uint64_t b0 = ((uint64_t)blockIdx.x * (blockDim.x >> 6) + wave) * 64; b0 < n; b0 += bstep) {
+        const uint64_t b = b0 + l;
         bool dyn = false, ovf = false;
         if (b < n) {
             const uint64_t s = a.block_off[b], e = a.block_off[b + 1], o = a.out_start[b];
@@ -2051,13 +1851,9 @@ __global__ __launch_bounds__(kZwThreads) void k_zl_wide(EntArgs a) {
             } else if (o + slot > a.out_cap) {
                 code = kWrCap;
             } else {
-                EntOutRing out{{{a.out + o, 0, slot - 4, false, false, true, false, 0}, 0, 0},
+                EntOutRing out{{{a.out + o, 0, slot - 4, false, false, false, 0}, 0, 0},
                                (lu8 *)smem + kZpTab + wave * kZwRing + l};
-#ifdef SDB_ZL_WIDE_INFLATE  // (diagnostic: inflate_raw's nested loops on the shared tables)
-                const int r = zlib_decode<true>(a.blocks + s, e - s - 4, out, t);
-#else
                 const int r = zlib_decode_wide(a.blocks + s, e - s - 4, out, t);
-#endif
                 out.flush();
                 if (r == 1) dyn = true;                // a dynamic block further into the stream
                 else if (out.bad) ovf = true;          // past the slot: the exact-size pass
@@ -2097,7 +1893,7 @@ __global__ __launch_bounds__(kZvThreads) void k_zl_verify(EntArgs a) {
     crc_slice_tables_to_lds((lu32 *)smem);
     __syncthreads();
     const uint32_t(*tab)[256] = (const uint32_t(*)[256])smem;
-    const uint32_t l = (uint32_t)lane_id(), wave = threadIdx.x >> 6;
+    const uint32_t wave = threadIdx.x >> 6;
     for (uint64_t b = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wave; b < a.nblocks;
          b += (uint64_t)gridDim.x * (blockDim.x >> 6)) {
         const uint64_t w0 = a.wres[2 * b], code = w0 >> 48;
@@ -2105,84 +1901,18 @@ __global__ __launch_bounds__(kZvThreads) void k_zl_verify(EntArgs a) {
         const uint64_t s = a.block_off[b], e = a.block_off[b + 1], o = a.out_start[b], ol = w0 & 0xFFFFFFFFFFFFull;
         const uint64_t bl = e - s - 4;
         const uint8_t *g = a.blocks + s;
-        const uint32_t stored = (uint32_t)g[bl] << 24 | (uint32_t)g[bl + 1] << 16 | (uint32_t)g[bl + 2] << 8 | (uint32_t)g[bl + 3];
+        const uint32_t stored = frame_stored_crc(g, bl);
         int st = 0;
-        if (ent_crc(g, bl, tab) != stored) st = SDB_CHECKSUM_MISMATCH;
+        // frame_status's order, with the capacity check as k_zl_wide made it (no slot here is empty)
+        if (frame_crc(g, bl, tab) != stored) st = SDB_CHECKSUM_MISMATCH;
         else if (code == kWrCap) st = SDB_INVALID_ARGUMENT;
         else if (code == kWrErr) st = SDB_DECOMPRESSION_ERROR;
         else {
             const uint64_t w1 = a.wres[2 * b + 1];
             if ((w1 >> 32) && wave_adler32_seg(a.out + o, ol) != (uint32_t)w1) st = SDB_DECOMPRESSION_ERROR;
         }
-        if (!st) {
-            const uint32_t c = ent_crc(a.out + o, ol, tab);
-            if (l == 0) {
-                uint8_t *gw = a.out + o;
-                gw[ol] = (uint8_t)(c >> 24);
-                gw[ol + 1] = (uint8_t)(c >> 16);
-                gw[ol + 2] = (uint8_t)(c >> 8);
-                gw[ol + 3] = (uint8_t)c;
-            }
-        }
-        if (l == 0) {
-            a.out_end[b] = st ? o : o + ol + 4;
-            if (st) atomicMin(a.err, (unsigned long long)((b << 8) | (uint64_t)st));
-        }
-    }
-}
-
-__global__ __launch_bounds__(kZThreads) void k_zl_run(EntArgs a) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    crc_slice_tables_to_lds((lu32 *)smem);
-    __syncthreads();
-    const uint32_t(*tab)[256] = (const uint32_t(*)[256])smem;
-    const uint32_t l = (uint32_t)lane_id(), wave = threadIdx.x >> 6;
-    ZWave &zw = *(ZWave *)(smem + 8 * 1024 + wave * kZWaveLds);
-    const uint64_t nw = (uint64_t)gridDim.x * (blockDim.x >> 6);
-    for (uint64_t k = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wave; k < a.nblocks; k += nw) {
-        const uint64_t s = a.block_off[k], e = a.block_off[k + 1], o = a.out_start[k];
-        const uint64_t slot = a.out_start[k + 1] - o;
-        int st = 0;
-        uint64_t ol = 0;
-        if (e < s || e - s < 4 || e - s > 0xFFFFFFFFull) {
-            st = SDB_CORRUPT_BLOCK;
-        } else {
-            const uint64_t bl = e - s - 4;
-            const uint8_t *g = a.blocks + s;
-            const uint32_t stored = (uint32_t)g[bl] << 24 | (uint32_t)g[bl + 1] << 16 | (uint32_t)g[bl + 2] << 8 |
-                                    (uint32_t)g[bl + 3];
-            const uint8_t *in = zl_stage(g, bl, zw.in);
-            if (ent_crc(in, bl, tab) != stored) {
-                st = SDB_CHECKSUM_MISMATCH;  // validate_checksum (format/sst.rs:1029-1038)
-            } else if (slot == 0) {
-                st = SDB_DECOMPRESSION_ERROR;
-            } else if (o + slot > a.out_cap) {
-                st = SDB_INVALID_ARGUMENT;
-            } else {
-                // every lane runs the decoder (same state; the copies spread over the lanes, EntOut::wide)
-                EntOut out{a.out + o, 0, slot - 4, false, true};
-                const int r = zlib_decode(in, bl, out, zw.t) || out.bad ? SDB_DECOMPRESSION_ERROR : 0;
-                st = __shfl(r, 0, 64);
-                ol = (uint64_t)__shfl((long long)out.len, 0, 64);
-                __threadfence_block();
-                __builtin_amdgcn_wave_barrier();
-                if (!st) {
-                    const uint32_t c = ent_crc(a.out + o, ol, tab);
-                    if (l == 0) {
-                        uint8_t *gw = a.out + o;
-                        gw[ol] = (uint8_t)(c >> 24);
-                        gw[ol + 1] = (uint8_t)(c >> 16);
-                        gw[ol + 2] = (uint8_t)(c >> 8);
-                        gw[ol + 3] = (uint8_t)c;
-                    }
-                }
-            }
-        }
-        if (l == 0) {
-            a.out_end[k] = st ? o : o + ol + 4;
-            if (st) atomicMin(a.err, (unsigned long long)((k << 8) | (uint64_t)st));
-        }
-        __builtin_amdgcn_wave_barrier();
+        if (!st) frame_trailer(a.out + o, ol, tab);
+        frame_publish(a, b, o, ol, st);
     }
 }
 
@@ -2190,141 +1920,54 @@ static std::once_flag g_ent_once;
 static hipError_t g_ent_attr = hipSuccess;
 static void ent_attrs() {
     std::call_once(g_ent_once, [] {
-        // (zlib takes its own kernels below; the <true> instances of the generic ones are never launched)
-        for (const void *f : {(const void *)k_ent_plan<false>, (const void *)k_ent_run<false>})
+        auto lds = [](const void *f, uint32_t bytes) {
             if (g_ent_attr == hipSuccess)
-                g_ent_attr = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kEntLds);
-        if (g_ent_attr == hipSuccess)
-            g_ent_attr = hipFuncSetAttribute((const void *)k_zl_plan, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kZLds);
-        if (g_ent_attr == hipSuccess)
-            g_ent_attr = hipFuncSetAttribute((const void *)k_zl_run, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kZLds);
-        if (g_ent_attr == hipSuccess)
-            g_ent_attr = hipFuncSetAttribute((const void *)k_zl_plan_multi, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                              (int)kZpLds);
-        if (g_ent_attr == hipSuccess)
-            g_ent_attr = hipFuncSetAttribute((const void *)k_zl_run_multi<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                              (int)kZrLds);
-        if (g_ent_attr == hipSuccess)
-            g_ent_attr = hipFuncSetAttribute((const void *)k_zl_wide, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kZwLds);
+                g_ent_attr = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        };
+        lds((const void *)k_ent_plan, kEntLds);
+        lds((const void *)k_ent_run, kEntLds);
+        lds((const void *)k_zl_plan_multi, kZpLds);
+        lds((const void *)k_zl_run_multi, kZrLds);
+        lds((const void *)k_zl_wide, kZwLds);
     });
 }
+// workgroups of `threads` for nwaves waves, at most one per CU
 static uint32_t ent_grid(uint64_t nwaves, uint32_t threads = kEntThreads) {
-    int dev = 0, cus = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    uint64_t wgs = (nwaves + threads / 64 - 1) / (threads / 64);
-    const uint64_t most = (uint64_t)(cus > 0 ? cus : 256);
-    if (wgs > most) wgs = most;
-    return (uint32_t)(wgs ? wgs : 1);
+    const uint32_t wgs = wgs_capped((nwaves + threads / 64 - 1) / (threads / 64), 1);
+    return wgs ? wgs : 1;
 }
 
-// the plan's per-block slots (the caller scans them)
-hipError_t launch_ent_slots(uint32_t codec, const uint8_t *blocks, const uint64_t *block_off, uint64_t nblocks,
-                            uint64_t *slot, hipStream_t st) {
+hipError_t launch_ent_slots(const EntArgs &a, hipStream_t st) {
     ent_attrs();
     if (g_ent_attr != hipSuccess) return g_ent_attr;
-    EntArgs a{};
-    a.codec = codec;
-    a.blocks = blocks;
-    a.block_off = block_off;
-    a.nblocks = nblocks;
-    a.slot = slot;
-    if (codec == SDB_CODEC_ZLIB && kZpD > 1)
-        hipLaunchKernelGGL(k_zl_plan_multi, dim3(ent_grid((nblocks + kZpD) / kZpD, kZpThreads)), dim3(kZpThreads), kZpLds, st, a);
-    else if (codec == SDB_CODEC_ZLIB)
-        hipLaunchKernelGGL(k_zl_plan, dim3(ent_grid(nblocks + 1, kZThreads)), dim3(kZThreads), kZLds, st, a);
+    if (a.codec == SDB_CODEC_ZLIB)
+        hipLaunchKernelGGL(k_zl_plan_multi, dim3(ent_grid((a.nblocks + kZpD) / kZpD, kZpThreads)), dim3(kZpThreads), kZpLds, st, a);
     else
-        hipLaunchKernelGGL(k_ent_plan<false>, dim3(ent_grid(nblocks + 1)), dim3(kEntThreads), kEntLds, st, a);
+        hipLaunchKernelGGL(k_ent_plan, dim3(ent_grid(a.nblocks + 1)), dim3(kEntThreads), kEntLds, st, a);
     return hipGetLastError();
 }
 
-hipError_t launch_ent_run(uint32_t codec, const uint8_t *blocks, const uint64_t *block_off, uint64_t nblocks, uint8_t *out,
-                          uint64_t out_cap, const uint64_t *out_start, uint64_t *out_end, unsigned long long *err,
-                          hipStream_t st) {
+hipError_t launch_ent_run(const EntArgs &a, hipStream_t st) {
     ent_attrs();
     if (g_ent_attr != hipSuccess) return g_ent_attr;
-    EntArgs a{};
-    a.codec = codec;
-    a.blocks = blocks;
-    a.block_off = block_off;
-    a.nblocks = nblocks;
-    a.out = out;
-    a.out_cap = out_cap;
-    a.out_start = out_start;
-    a.out_end = out_end;
-    a.err = err;
-    if (nblocks && codec == SDB_CODEC_ZLIB && SDB_ZL_RUN_MULTI)
-        hipLaunchKernelGGL(k_zl_run_multi<false>, dim3(ent_grid((nblocks + kZpD - 1) / kZpD, kZpThreads)), dim3(kZpThreads), kZrLds,
+    if (a.nblocks && a.codec == SDB_CODEC_ZLIB)
+        hipLaunchKernelGGL(k_zl_run_multi, dim3(ent_grid((a.nblocks + kZpD - 1) / kZpD, kZpThreads)), dim3(kZpThreads), kZrLds,
                            st, a);
-    else if (nblocks && codec == SDB_CODEC_ZLIB)
-        hipLaunchKernelGGL(k_zl_run, dim3(ent_grid(nblocks, kZThreads)), dim3(kZThreads), kZLds, st, a);
-    else if (nblocks)
-        hipLaunchKernelGGL(k_ent_run<false>, dim3(ent_grid(nblocks)), dim3(kEntThreads), kEntLds, st, a);
+    else if (a.nblocks)
+        hipLaunchKernelGGL(k_ent_run, dim3(ent_grid(a.nblocks)), dim3(kEntThreads), kEntLds, st, a);
     return hipGetLastError();
 }
 
-// zlib decode-once (launch_decompress_once, sdb_codec.hip): the optimistic run over fixed slots, which lists
-// the blocks that overflowed theirs, and the exact plan + run over that list
-bool zl_once_supported() { return SDB_ZL_RUN_MULTI && kZpD > 1; }
-
-hipError_t launch_zl_once_slots(const uint8_t *blocks, const uint64_t *block_off, uint64_t nblocks, const uint32_t *list,
-                                const unsigned long long *nlist, uint64_t *slot, hipStream_t st) {
+hipError_t launch_zl_wide(const EntArgs &a, hipStream_t st) {
     ent_attrs();
     if (g_ent_attr != hipSuccess) return g_ent_attr;
-    EntArgs a{};
-    a.codec = SDB_CODEC_ZLIB;
-    a.blocks = blocks;
-    a.block_off = block_off;
-    a.nblocks = nblocks;
-    a.slot = slot;
-    a.list = list;
-    a.nlist = nlist;
-    hipLaunchKernelGGL(k_zl_plan_multi, dim3(ent_grid((nblocks + kZpD) / kZpD, kZpThreads)), dim3(kZpThreads), kZpLds, st, a);
-    return hipGetLastError();
-}
-
-// mode 0: the per-decoder-table run; 1: the wide run (fixed-code blocks, the others to dyn_list)
-hipError_t launch_zl_once_run(int mode, const uint8_t *blocks, const uint64_t *block_off, uint64_t nblocks, uint8_t *out,
-                              uint64_t out_cap, const uint64_t *out_start, uint64_t *out_end, unsigned long long *err,
-                              const uint32_t *list, const unsigned long long *nlist, bool out_by_block, uint32_t *ovf_list,
-                              unsigned long long *ovf_count, uint32_t *dyn_list, unsigned long long *dyn_count,
-                              uint64_t *wres, hipStream_t st) {
-    ent_attrs();
-    if (g_ent_attr != hipSuccess) return g_ent_attr;
-    EntArgs a{};
-    a.codec = SDB_CODEC_ZLIB;
-    a.blocks = blocks;
-    a.block_off = block_off;
-    a.nblocks = nblocks;
-    a.out = out;
-    a.out_cap = out_cap;
-    a.out_start = out_start;
-    a.out_end = out_end;
-    a.err = err;
-    a.list = list;
-    a.nlist = nlist;
-    a.out_by_block = out_by_block;
-    a.ovf_list = ovf_list;
-    a.ovf_count = ovf_count;
-    a.dyn_list = dyn_list;
-    a.dyn_count = dyn_count;
-    a.wres = wres;
-    if (nblocks && mode == 1) {
-        int dev = 0, cus = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        const uint64_t most = 8ull * (cus > 0 ? cus : 256);
-        uint64_t wgs = (nblocks + kZwD * (kZwThreads / 64) - 1) / (kZwD * (kZwThreads / 64));
-        wgs = wgs < most ? wgs : most;
-        hipLaunchKernelGGL(k_zl_wide, dim3((uint32_t)wgs), dim3(kZwThreads), kZwLds, st, a);
-        uint64_t vgs = (nblocks + kZvThreads / 64 - 1) / (kZvThreads / 64);
-        vgs = vgs < most ? vgs : most;
-        hipLaunchKernelGGL(k_zl_verify, dim3((uint32_t)vgs), dim3(kZvThreads), 8 * 1024, st, a);
+    if (a.nblocks) {  // a block per lane, then a wave per block; at most eight workgroups per CU
+        hipLaunchKernelGGL(k_zl_wide, dim3(wgs_capped((a.nblocks + kZwThreads - 1) / kZwThreads, 8)), dim3(kZwThreads), kZwLds, st, a);
+        const uint64_t vwaves = kZvThreads / 64;
+        hipLaunchKernelGGL(k_zl_verify, dim3(wgs_capped((a.nblocks + vwaves - 1) / vwaves, 8)), dim3(kZvThreads), 8 * 1024, st, a);
     }
-    else if (nblocks)
-        hipLaunchKernelGGL(k_zl_run_multi<false>, dim3(ent_grid((nblocks + kZpD - 1) / kZpD, kZpThreads)), dim3(kZpThreads),
-                           kZrLds, st, a);
     return hipGetLastError();
 }
 
 }  // namespace sdb
+
