@@ -1153,6 +1153,76 @@ sdb_status sdb_compactor_run_ssts_merge(sdb_compactor *c, const sdb_compaction_i
 sdb_status sdb_compactor_merge_stats(const sdb_compactor *c, sdb_merge_op_stats *stats);
 
 /* ---------------------------------------------------------------------------------------------
+ * Ranged compaction over SST views: sdb_compactor_run_ssts / _merge as the reference runs every job.
+ * run_subcompaction_merge (compactor_executor.rs:779-881) handles a whole job (an unbounded range) and an RFC-0028
+ * subcompaction on one path: load_iterators (:327-435) opens every input over job_args.range and its view, so an
+ * input SST is read only over calculate_view_range(range) = range intersected with visible_range
+ * (db_state.rs:243-251), and only the blocks partitions_covering_range returns for it are fetched.  `job_range`
+ * and `proj` are sdb_scan_ranges with device arrays, exactly as the tree reads take them.
+ *   R1. view range: V[i] = job_range intersected with visible[i] as BytesRange::intersect does
+ *       (comparable_range.rs:224-236): the tighter start and the tighter end (P1).  V[i] is empty exactly when the
+ *       start key lies above the end key, or equals it with a side excluded.  A projection of (UNBOUNDED, UNBOUNDED)
+ *       means None.  An input whose V is empty contributes nothing: none of its blocks is read and none of its
+ *       errors surfaces;
+ *   R2. blocks: input i reads partitions_covering_range(index keys of i, V.start, V.end), exactly as sdb_sst_scan
+ *       rule 1 (an excluded end that equals a block's index key leaves that block out).  Only these blocks are
+ *       bounds- and CRC-checked and parsed: a corrupt block outside them never fails the job; a failing block inside
+ *       them fails it with its status, lowest block first, first_error_entry = that block's index among ALL inputs'
+ *       blocks (the numbering of sdb_compactor_run_ssts).  One deviation: an input whose keys all lie outside a
+ *       non-empty V still has one covering block checked (the partition search needs no key of the SST's); the
+ *       reference's sorted-run search would not open that SST;
+ *   R3. rows: input i contributes the entries of those blocks whose key V[i] contains (SstView::contains): all
+ *       versions of a key, or none.  A run is the concatenation of its inputs' contributions in input order; the
+ *       rows dropped between two inputs leave no gap (the contributions are closed up into columns of their own
+ *       whenever a row was dropped).  Ordering within a run is the caller's obligation (as P7); the merge's
+ *       run-order check still reports a violation as SDB_INVALID_ARGUMENT;
+ *   R4. everything after the inputs is unchanged: merge order, the operator walk when op != NULL
+ *       (sdb_compactor_run_ssts_merge) or MergeOperatorRequiredIterator when op == NULL, retention, cuts and encode;
+ *       more than SDB_MAX_RUNS runs merge in groups first.  sdb_compactor_sst, sdb_compactor_merged and
+ *       sdb_compactor_merge_stats read the results as for the other jobs;
+ *   R5. identity: with job_range == NULL (or unbounded) and proj == NULL (or all unbounded) the job's outputs,
+ *       statuses and summary words are those of sdb_compactor_run_ssts / _merge on the same inputs;
+ *   R6. counts: an input whose V is unbounded on both sides must decode to exactly its declared num_entries, as in
+ *       sdb_compactor_run_ssts.  For a clipped input the declared counts are upper bounds: more decoded rows in its
+ *       covering blocks than num_entries is SDB_INVALID_ARGUMENT (first_error_entry = its first covering block).
+ *       The totals of key_bytes / val_bytes are exact when no input is clipped and upper bounds otherwise (the
+ *       declared counts of the inputs that have a covering block size the decode and the merge);
+ *   R7. malformed ranges.  Found on the device, failing the job with SDB_INVALID_ARGUMENT, blocks_checked 0 and
+ *       nothing read through the arrays: a job bound kind above SDB_BOUND_EXCLUDED; a projection start other than
+ *       UNBOUNDED / INCLUDED or an end kind above EXCLUDED; offsets that descend.  Found on the host,
+ *       SDB_INVALID_ARGUMENT from the call before SDB_DEVICE_ERROR: job_range->n != 1; proj->n != ninputs; a NULL
+ *       array inside a non-NULL struct; num_blocks > 0 with NULL data, block_off, index_keys or index_key_off;
+ *   R8. synchronisations: exactly two more than sdb_compactor_run_ssts[_merge] on the same inputs, in every job
+ *       (the unbounded one included).  The first reads the covering block range of every input (2 words per input
+ *       and the ranges' status): it sizes the decode, its workspace and the merge from the covered blocks and the
+ *       declared counts of the inputs that have any.  The second reads the gate and each run's first row (4 + nruns
+ *       + 1 words): sdb_run.n and the merge's grid are host values.  A job that fails at either returns there.
+ *       No allocation in steady state: the handle's buffers grow, and one handle serves ranged and whole jobs of
+ *       any sizes in any order.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct sdb_compaction_view {     /* one input SST as the ranged job reads it */
+    sdb_compaction_input sst;            /* data, block_off, num_blocks and the SstStats counts (rule R6) */
+    const uint8_t *index_keys;           /* device: BlockMeta.first_key of block k, as sdb_sst_view */
+    const uint64_t *index_key_off;       /* device: num_blocks + 1 */
+} sdb_compaction_view;
+typedef struct sdb_range_job_stats {
+    uint64_t inputs_read;                /* inputs with a non-empty block range */
+    uint64_t blocks_total;               /* sum of num_blocks */
+    uint64_t blocks_checked;             /* blocks CRC-checked and parsed: exactly the covering blocks (R2) */
+    uint64_t entries_decoded;            /* rows of those blocks */
+    uint64_t entries_in;                 /* rows inside their view range = merged summary num_in */
+} sdb_range_job_stats;
+sdb_status sdb_compactor_run_ssts_ranged(sdb_compactor *c, const sdb_compaction_view *inputs, uint32_t ninputs,
+                                         const uint32_t *run_start, uint32_t nruns, uint16_t input_sst_version,
+                                         const sdb_scan_ranges *job_range /* n == 1; or NULL = unbounded */,
+                                         const sdb_scan_ranges *proj /* n == ninputs: visible_range per input; or NULL */,
+                                         const sdb_retention *retention, sdb_merge_batch_fn op /* NULL: no operator */,
+                                         void *ctx, const sdb_sst_params *params, uint64_t max_sst_size, void *stream,
+                                         uint32_t *num_ssts);
+/* The input side of the last sdb_compactor_run_ssts_ranged job (zeros after any other). */
+sdb_status sdb_compactor_range_stats(const sdb_compactor *c, sdb_range_job_stats *stats);
+
+/* ---------------------------------------------------------------------------------------------
  * SST footer (host): everything after the data section, so data ++ footer is the whole SST object
  * EncodedSsTableBuilder::build / EncodedWalSsTableBuilder::build hand to write_sst.
  * Replaces EncodedSsTableFooterBuilder::build (format/sst.rs:383-487) plus the index the builders

@@ -300,6 +300,18 @@ class CompactionInput(C.Structure):
         ("key_bytes", C.c_uint64), ("val_bytes", C.c_uint64),
     ]
 
+
+class CompactionView(C.Structure):
+    _fields_ = [("sst", CompactionInput), ("index_keys", C.c_void_p), ("index_key_off", C.c_void_p)]
+
+
+class RangeJobStats(C.Structure):
+    _fields_ = [
+        ("inputs_read", C.c_uint64), ("blocks_total", C.c_uint64), ("blocks_checked", C.c_uint64),
+        ("entries_decoded", C.c_uint64), ("entries_in", C.c_uint64),
+    ]
+
+
 class MergeOpStats(C.Structure):
     _fields_ = [
         ("groups", C.c_uint64), ("links", C.c_uint64), ("link_bytes", C.c_uint64), ("merged_bytes", C.c_uint64),
@@ -420,6 +432,11 @@ SIGNATURES = {
                                                C.c_uint16, C.POINTER(Retention), MERGE_BATCH_FN, C.c_void_p,
                                                C.POINTER(SstParams), C.c_uint64, C.c_void_p, u32p]),
     "sdb_compactor_merge_stats": (C.c_int, [C.c_void_p, C.POINTER(MergeOpStats)]),
+    "sdb_compactor_run_ssts_ranged": (C.c_int, [C.c_void_p, C.POINTER(CompactionView), C.c_uint32, u32p, C.c_uint32,
+                                                C.c_uint16, C.POINTER(ScanRanges), C.POINTER(ScanRanges),
+                                                C.POINTER(Retention), MERGE_BATCH_FN, C.c_void_p,
+                                                C.POINTER(SstParams), C.c_uint64, C.c_void_p, u32p]),
+    "sdb_compactor_range_stats": (C.c_int, [C.c_void_p, C.POINTER(RangeJobStats)]),
     "sdb_compactor_sst": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(CompactedSst)]),
     "sdb_compactor_merged": (C.c_int, [C.c_void_p, C.POINTER(KvBatch), C.POINTER(MergeSummary)]),
     "sdb_sst_footer": (C.c_int, [C.POINTER(FooterIn), C.c_void_p, C.c_uint64, u64p]),

@@ -1,4 +1,5 @@
-// sdb_compact.h — kernel arguments of the compaction output side (sdb_compact.hip).
+// sdb_compact.h — kernel arguments of the compaction output side (sdb_compact.hip) and of the ranged job's input
+// side (sdb_compact_range.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -180,6 +181,43 @@ sdb_status sst_cuts_padded(const sdb_kv_batch *batch, const sdb_sst_params *para
 // merged positions [summary.num_out + 1, cap]: empty entries (offsets = the totals), so a prep over the
 // padded stream reads defined bytes
 hipError_t launch_merge_pad(const sdb_merged_out &out, uint64_t cap, hipStream_t st);
+
+// ---- sdb_compactor_run_ssts_ranged (sdb_compact_range.hip): the job range and the inputs' visible ranges ----
+struct RxInputs {  // kernel arguments: per-input tables in device memory
+    uint32_t n, nruns;
+    uint32_t has_job, has_proj;            // job / proj were passed (else: unbounded)
+    sdb_scan_ranges job, proj;             // job.n == 1, proj.n == n
+    // uploaded by the host
+    const uint8_t *const *index_keys;      // n
+    const uint64_t *const *index_key_off;  // n
+    const uint64_t *const *block_off;      // n: each input's BlockMeta offsets
+    const uint64_t *num_blocks;            // n
+    const uint64_t *gblock;                // n + 1: prefix of num_blocks (the job's block numbering)
+    const uint64_t *num_entries;           // n: declared
+    const uint32_t *run_start;             // nruns + 1: first input of each run
+    // written by k_rx_cover
+    uint64_t *cover;                       // 2 n + 1: covering blocks [start, end) of each input (end <= start:
+                                           // none), then the status of the ranges (SDB_OK | SDB_INVALID_ARGUMENT)
+    uint8_t *clipped;                      // n: V[i] has a bound
+    const uint64_t **cov_off;              // n: block_off[i] + cover start: the covered blocks' offsets
+    uint64_t *cov_first;                   // n + 1: prefix of the covered block counts (the decode's numbering)
+    // written by k_rx_clip / k_rx_gate
+    uint64_t *lo, *hi;                     // n: the rows V[i] contains, in the decoded columns
+    uint64_t *out_first, *out_key;         // n + 1: prefix of hi - lo and of their key bytes
+    uint64_t *result;                      // kRxResult words, then run_entry (nruns + 1: each run's first row)
+};
+// result words (read back with run_entry in the job's second synchronisation)
+enum { kRxGate = 0, kRxDecoded = 1, kRxIn = 2, kRxKeyBytes = 3, kRxResult = 4 };
+// V[i] = job ∩ visible[i], its covering blocks, and their compaction into the decode's block list (a.cov_*)
+hipError_t launch_rx_cover(const RxInputs &a, hipStream_t st);
+// after the decode of the covered blocks: the rows V[i] contains, the counts against the declared ones (R6), the
+// per-run row ranges and the job's result words; decl_*: the declared totals of every input (exact when no input
+// is clipped)
+hipError_t launch_rx_clip_gate(const RxInputs &a, const sdb_decoded_out &dec, const unsigned long long *dec_err,
+                               uint64_t decl_entries, uint64_t decl_key_bytes, hipStream_t st);
+// the contributed rows of every input, closed up: columns and keys of `dec` into `out` (`rows` = out_first[n])
+hipError_t launch_rx_compact(const RxInputs &a, const sdb_decoded_out &dec, const sdb_decoded_out &out, uint64_t rows,
+                             hipStream_t st);
 
 // out[2i], out[2i+1] = key_off[cut[i]], val_off[cut[i]] for i <= ns
 hipError_t launch_cut_offsets(const uint64_t *cut, const uint64_t *num, const uint64_t *key_off, const uint64_t *val_off,

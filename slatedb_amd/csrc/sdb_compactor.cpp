@@ -12,6 +12,11 @@
 //                            chains and gathers their bytes, the host folds each chain through the operator,
 //                            and retention, cuts and encode run over the collapsed stream; two more host
 //                            synchronisations (the chain summary; the chain tables, only when there is a chain).
+//   sdb_compactor_run_ssts_ranged: run_ssts[_merge] over one job range and a visible range per input: the covering
+//                            blocks of every input (k_rx_cover), their decode, the rows inside the view ranges
+//                            (k_rx_clip, k_rx_gate; closed up by k_rx_compact when a row was dropped), then the same
+//                            merge, cuts and encode (merge_encode); two more host synchronisations (the covering
+//                            block ranges, which size the decode; the per-run row ranges, which size the merge).
 // Both job families share begin_job, order_step (the merged order; with an operator chain_step), the cut readback
 // (CutRead) and encode_outputs; a.ch, bound by chain_step, selects the unit forms of retention and emit.
 // The outputs stay in the handle's device memory; every SST of the job is encoded by one launch sequence
@@ -99,6 +104,10 @@ struct sdb_compactor {
     StreamEvent up_ev;  // the upload of pin_up: the next job waits for it before it rewrites pin_up
     bool canaries = false;
     sdb_merge_op_stats mstats{};
+    // the ranged job: what its cover, clip and gate kernels write (rx_ws), and the contributed rows closed up
+    // into columns of their own when a range dropped any (rx_cols)
+    GuardBuf rx_ws, rx_cols;
+    sdb_range_job_stats rstats{};
     // recorded on the job's stream when a run_ssts job returns (every path): the next job waits for it
     // before it rewrites pin_tab / cx_tab, which that job's upload and kernels may still be reading
     StreamEvent tab_ev;
@@ -373,6 +382,7 @@ sdb_status begin_job(sdb_compactor *c, const sdb_retention *ret, const sdb_sst_p
     c->merged = sdb_kv_batch{};
     c->msum = sdb_merge_summary{};
     c->mstats = sdb_merge_op_stats{};
+    c->rstats = sdb_range_job_stats{};
     if (params->sst_type != SDB_SST_COMPACTED || !ret) return SDB_INVALID_ARGUMENT;  // compactions write compacted SSTs
     return SDB_OK;
 }
@@ -587,6 +597,126 @@ sdb_status run_job(sdb_compactor *c, const sdb_run *runs, uint32_t nruns, const 
     return encode_outputs(c, rd, n, params, stream, num_ssts);
 }
 
+// The decode of a job's input blocks: its block list, the decoded columns and the gate word, in c->dec.
+struct DecodeBufs {
+    uint64_t *bstart, *bend;
+    unsigned long long *gate;
+    sdb_decoded_out out;
+};
+// Sizes (base == NULL) or binds them for B blocks of at most E entries and K key bytes.
+uint64_t decode_bufs_bind(DecodeBufs &b, uint64_t B, uint64_t K, uint64_t E, uint8_t *base) {
+    sdb_decoded_out &dout = b.out;
+    dout = sdb_decoded_out{};
+    dout.key_arena_cap = K;
+    dout.cap_entries = E;
+    dout.bad_cap = 16;
+    Carver k{base, 0};
+    k.take(b.bstart, B + 1);
+    k.take(b.bend, B + 1);
+    k.take(dout.block_entry_start, B + 2);
+    k.take(dout.key_arena, K + 64);
+    k.take(dout.key_off, E + 1);
+    k.take(dout.val_off, E + 1);
+    k.take(dout.val_len, E + 1);
+    k.take(dout.seq, E + 1);
+    k.take(dout.flags, E + 1);
+    k.take(dout.create_ts, E + 1);
+    k.take(dout.expire_ts, E + 1);
+    k.take(dout.bad_block, dout.bad_cap);
+    k.take(dout.summary, 1);
+    k.take(b.gate, 1);
+    return k.off;
+}
+
+// The runs of a job over decoded columns: run r = entries [run_entry[r], run_entry[r + 1]), values in `arena`.
+std::vector<sdb_run> runs_over(const sdb_decoded_out &dout, const uint8_t *arena, const uint64_t *run_entry, uint32_t nruns) {
+    std::vector<sdb_run> runs(nruns);
+    for (uint32_t r = 0; r < nruns; r++) {
+        const uint64_t e0 = run_entry[r];
+        sdb_run &R = runs[r];
+        R.n = run_entry[r + 1] - e0;
+        R.key_arena = dout.key_arena;
+        R.key_off = dout.key_off + e0;
+        R.val_base = arena;
+        R.val_off = dout.val_off + e0;
+        R.val_len = dout.val_len + e0;
+        R.seq = dout.seq + e0;
+        R.flags = dout.flags + e0;
+        R.create_ts = dout.create_ts + e0;
+        R.expire_ts = dout.expire_ts + e0;
+    }
+    return runs;
+}
+
+// Steps 2 and 3 of the jobs over encoded inputs, behind the decode: `runs` of E entries, K key bytes and at most V
+// value bytes; gate: the decode's gate word on the device (NULL: the host has already read it).
+sdb_status merge_encode(sdb_compactor *c, const std::vector<sdb_run> &runs, uint64_t E, uint64_t K, uint64_t V,
+                        const unsigned long long *gate, const sdb_retention *ret, sdb_merge_batch_fn op, void *ctx,
+                        const sdb_sst_params *params, uint64_t max_sst_size, void *stream, uint32_t *num_ssts) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const uint32_t nruns = (uint32_t)runs.size();
+    sdb_status st;
+    // 2. merge + retention + emit into buffers of the declared sizes (retention only drops entries and
+    //    values), gated on the decode; the stream padded to E entries for the cut walk
+    sdb_merged_out out{};
+    st = merged_columns_in(c->cols, E, &out);
+    if (st) return st;
+    if (!c->keys.ensure(K + 16) || (!op && !c->vals.ensure(V + 16))) return SDB_DEVICE_ERROR;
+    out.key_bytes = c->keys.at<uint8_t>(0);
+    out.key_cap = K;
+    out.val_bytes = op ? nullptr : c->vals.at<uint8_t>(0);  // (with an operator: sized after the fold)
+    out.val_cap = V;
+    const sdb_run *mruns = runs.data();
+    uint32_t mn = nruns;
+    std::vector<sdb_run> grouped;
+    if (nruns > kMaxRuns) {  // more runs than one merge takes: groups merged ahead (group_runs)
+        const sdb_status gs = group_runs(c, mruns, nruns, gate, grouped, &c->msum, s);
+        if (gs) return gs;
+        mruns = grouped.data();
+        mn = (uint32_t)grouped.size();
+    }
+    if (!c->merge_ws.ensure(sdb_merge_runs_workspace_bytes(mruns, mn))) return SDB_DEVICE_ERROR;
+    MergeArgs a;
+    st = build_merge_args(mruns, mn, ret, &out, c->merge_ws.p, c->merge_ws.cap, &a);
+    if (st) return st;
+    a.gate = gate;
+    st = order_step(c, a, op, ctx, s);
+    if (st) return st;
+    if (op) {
+        // a merged value can be longer than all of its inputs: the links' bytes leave, the merged bytes come
+        V = (V > c->mstats.link_bytes ? V - c->mstats.link_bytes : 0) + c->mstats.merged_bytes;
+        if (!c->vals.ensure(V + 16)) return SDB_DEVICE_ERROR;
+        a.out.val_bytes = out.val_bytes = c->vals.at<uint8_t>(0);
+        a.out.val_cap = out.val_cap = V;
+    }
+    if (launch_merge_retention(a, true, s) != hipSuccess || launch_merge_pad(out, E, s) != hipSuccess)
+        return SDB_DEVICE_ERROR;
+    const sdb_kv_batch padded = batch_of(out, E);
+
+    // cuts over the padded stream, ending at the merged count; merged summary, cut count, cuts and their
+    // byte offsets read back in one synchronisation
+    uint64_t *d_num, *d_cut, *d_off;
+    if (!cut_buffers(c, E, params, &d_num, &d_cut, &d_off)) return SDB_DEVICE_ERROR;
+    if (E) {
+        st = sst_cuts_padded(&padded, params, max_sst_size, d_cut, E + 1, d_num, c->cut_ws.p, c->cut_ws.cap, s,
+                             &out.summary->num_out);
+        if (st) return st;
+        if (launch_cut_offsets(d_cut, d_num, out.key_off, out.val_off, d_off, s) != hipSuccess) return SDB_DEVICE_ERROR;
+    }
+    CutRead rd;
+    if (!cut_read_begin(c, rd, E, K + V, max_sst_size, out.summary, d_num, d_cut, d_off, s) ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return SDB_DEVICE_ERROR;
+    c->msum = *rd.sum;
+    if (c->msum.status) return (sdb_status)c->msum.status;
+    const uint64_t n = c->msum.num_out;
+    c->merged = batch_of(out, n);
+    if (!n) return SDB_OK;
+
+    // 3. encode every output SST
+    return encode_outputs(c, rd, n, params, stream, num_ssts);
+}
+
 // sdb_compactor_run_ssts (op == NULL) / sdb_compactor_run_ssts_merge
 sdb_status run_ssts_job(sdb_compactor *c, const sdb_compaction_input *inputs, uint32_t ninputs,
                         const uint32_t *run_start, uint32_t nruns, uint16_t input_sst_version,
@@ -667,32 +797,13 @@ sdb_status run_ssts_job(sdb_compactor *c, const sdb_compaction_input *inputs, ui
     in.run_entry = c->cx_tab.at<const uint64_t>(t_rent);
 
     // 1. decode every input block into one columnar output (run r = entries [run_entry[r], run_entry[r+1]))
-    uint64_t *bstart = nullptr, *bend = nullptr;
-    unsigned long long *gate = nullptr;
-    sdb_decoded_out dout{};
-    dout.key_arena_cap = K;
-    dout.cap_entries = E;
-    dout.bad_cap = 16;
-    auto bind_dec = [&](uint8_t *base) {  // sizes (NULL) or binds c->dec
-        Carver k{base, 0};
-        k.take(bstart, B + 1);
-        k.take(bend, B + 1);
-        k.take(dout.block_entry_start, B + 2);
-        k.take(dout.key_arena, K + 64);
-        k.take(dout.key_off, E + 1);
-        k.take(dout.val_off, E + 1);
-        k.take(dout.val_len, E + 1);
-        k.take(dout.seq, E + 1);
-        k.take(dout.flags, E + 1);
-        k.take(dout.create_ts, E + 1);
-        k.take(dout.expire_ts, E + 1);
-        k.take(dout.bad_block, dout.bad_cap);
-        k.take(dout.summary, 1);
-        k.take(gate, 1);
-        return k.off;
-    };
-    if (!c->dec.ensure(bind_dec(nullptr)) || !c->dec_ws.ensure(sdb_decode_workspace_bytes(B))) return SDB_DEVICE_ERROR;
-    bind_dec(c->dec.at<uint8_t>(0));
+    DecodeBufs db;
+    if (!c->dec.ensure(decode_bufs_bind(db, B, K, E, nullptr)) || !c->dec_ws.ensure(sdb_decode_workspace_bytes(B)))
+        return SDB_DEVICE_ERROR;
+    decode_bufs_bind(db, B, K, E, c->dec.at<uint8_t>(0));
+    uint64_t *const bstart = db.bstart, *const bend = db.bend;
+    unsigned long long *const gate = db.gate;
+    const sdb_decoded_out &dout = db.out;
     const uint8_t *arena = reinterpret_cast<const uint8_t *>(base);
     if (launch_cx_blocks(in, bstart, bend, s) != hipSuccess) return SDB_DEVICE_ERROR;
     // fail-fast (a failing block fails the job anyway, as load_iterators' reads would): checksums in the emit pass
@@ -702,81 +813,186 @@ sdb_status run_ssts_job(sdb_compactor *c, const sdb_compaction_input *inputs, ui
     const unsigned long long *dec_err = decode_err_word(c->dec_ws.p, B);
     if (launch_cx_gate(in, dout.summary, dec_err, dout.block_entry_start, gate, s) != hipSuccess)
         return SDB_DEVICE_ERROR;
-    std::vector<sdb_run> runs(nruns);
-    for (uint32_t r = 0; r < nruns; r++) {
-        const uint64_t e0 = run_entry[r];
-        sdb_run &R = runs[r];
-        R.n = run_entry[r + 1] - e0;
-        R.key_arena = dout.key_arena;
-        R.key_off = dout.key_off + e0;
-        R.val_base = arena;
-        R.val_off = dout.val_off + e0;
-        R.val_len = dout.val_len + e0;
-        R.seq = dout.seq + e0;
-        R.flags = dout.flags + e0;
-        R.create_ts = dout.create_ts + e0;
-        R.expire_ts = dout.expire_ts + e0;
-    }
+    std::vector<sdb_run> runs = runs_over(dout, arena, run_entry.data(), nruns);
+    return merge_encode(c, runs, E, K, V, gate, ret, op, ctx, params, max_sst_size, stream, num_ssts);
+}
 
-    // 2. merge + retention + emit into buffers of the declared sizes (retention only drops entries and
-    //    values), gated on the decode; the stream padded to E entries for the cut walk
-    sdb_merged_out out{};
-    st = merged_columns_in(c->cols, E, &out);
-    if (st) return st;
-    if (!c->keys.ensure(K + 16) || (!op && !c->vals.ensure(V + 16))) return SDB_DEVICE_ERROR;
-    out.key_bytes = c->keys.at<uint8_t>(0);
-    out.key_cap = K;
-    out.val_bytes = op ? nullptr : c->vals.at<uint8_t>(0);  // (with an operator: sized after the fold)
-    out.val_cap = V;
-    const sdb_run *mruns = runs.data();
-    uint32_t mn = nruns;
-    std::vector<sdb_run> grouped;
-    if (nruns > kMaxRuns) {  // more runs than one merge takes: groups merged ahead (group_runs)
-        const sdb_status gs = group_runs(c, mruns, nruns, gate, grouped, &c->msum, s);
-        if (gs) return gs;
-        mruns = grouped.data();
-        mn = (uint32_t)grouped.size();
-    }
-    if (!c->merge_ws.ensure(sdb_merge_runs_workspace_bytes(mruns, mn))) return SDB_DEVICE_ERROR;
-    MergeArgs a;
-    st = build_merge_args(mruns, mn, ret, &out, c->merge_ws.p, c->merge_ws.cap, &a);
-    if (st) return st;
-    a.gate = gate;
-    st = order_step(c, a, op, ctx, s);
-    if (st) return st;
-    if (op) {
-        // a merged value can be longer than all of its inputs: the links' bytes leave, the merged bytes come
-        V = (V > c->mstats.link_bytes ? V - c->mstats.link_bytes : 0) + c->mstats.merged_bytes;
-        if (!c->vals.ensure(V + 16)) return SDB_DEVICE_ERROR;
-        a.out.val_bytes = out.val_bytes = c->vals.at<uint8_t>(0);
-        a.out.val_cap = out.val_cap = V;
-    }
-    if (launch_merge_retention(a, true, s) != hipSuccess || launch_merge_pad(out, E, s) != hipSuccess)
-        return SDB_DEVICE_ERROR;
-    const sdb_kv_batch padded = batch_of(out, E);
+bool ranges_null(const sdb_scan_ranges *g) {  // a NULL array inside a non-NULL struct
+    return !g->start_bytes || !g->start_off || !g->start_kind || !g->end_bytes || !g->end_off || !g->end_kind;
+}
 
-    // cuts over the padded stream, ending at the merged count; merged summary, cut count, cuts and their
-    // byte offsets read back in one synchronisation
-    uint64_t *d_num, *d_cut, *d_off;
-    if (!cut_buffers(c, E, params, &d_num, &d_cut, &d_off)) return SDB_DEVICE_ERROR;
-    if (E) {
-        st = sst_cuts_padded(&padded, params, max_sst_size, d_cut, E + 1, d_num, c->cut_ws.p, c->cut_ws.cap, s,
-                             &out.summary->num_out);
-        if (st) return st;
-        if (launch_cut_offsets(d_cut, d_num, out.key_off, out.val_off, d_off, s) != hipSuccess) return SDB_DEVICE_ERROR;
+// Sizes (base == NULL) or binds the columns of `rows` contributed rows and K key bytes.
+uint64_t range_cols_bind(sdb_decoded_out &o, uint64_t rows, uint64_t K, uint8_t *base) {
+    o = sdb_decoded_out{};
+    o.key_arena_cap = K;
+    o.cap_entries = rows;
+    Carver k{base, 0};
+    k.take(o.key_arena, K + 64);
+    k.take(o.key_off, rows + 1);
+    k.take(o.val_off, rows + 1);
+    k.take(o.val_len, rows + 1);
+    k.take(o.seq, rows + 1);
+    k.take(o.flags, rows + 1);
+    k.take(o.create_ts, rows + 1);
+    k.take(o.expire_ts, rows + 1);
+    return k.off;
+}
+
+// sdb_compactor_run_ssts_ranged.  The host arguments were checked by the entry point (R7).
+sdb_status run_ranged_job(sdb_compactor *c, const sdb_compaction_view *inputs, uint32_t ninputs, const uint32_t *run_start,
+                          uint32_t nruns, uint16_t input_sst_version, const sdb_scan_ranges *job,
+                          const sdb_scan_ranges *proj, const sdb_retention *ret, sdb_merge_batch_fn op, void *ctx,
+                          const sdb_sst_params *params, uint64_t max_sst_size, void *stream, uint32_t *num_ssts) {
+    sdb_status st = begin_job(c, ret, params, num_ssts);
+    if (st) return st;
+    if (input_sst_version != 1 && input_sst_version != 2) return SDB_INVALID_VERSION;
+    if (!run_start) nruns = ninputs;
+    if ((uint64_t)nruns > (uint64_t)kMaxRuns * kMaxRuns) return SDB_LIMIT_EXCEEDED;  // two merge levels
+    if (run_start) {
+        if (run_start[0] != 0 || run_start[nruns] != ninputs) return SDB_INVALID_ARGUMENT;
+        for (uint32_t r = 0; r < nruns; r++)
+            if (run_start[r + 1] < run_start[r]) return SDB_INVALID_ARGUMENT;
     }
-    CutRead rd;
-    if (!cut_read_begin(c, rd, E, K + V, max_sst_size, out.summary, d_num, d_cut, d_off, s) ||
+    if (hipSetDevice(c->device) != hipSuccess) return SDB_DEVICE_ERROR;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const uint64_t n = ninputs;
+
+    // the per-input and per-run tables the host knows, to device memory (pin_tab / cx_tab, as run_ssts_job)
+    RxInputs a{};
+    a.n = ninputs;
+    a.nruns = nruns;
+    if (job) a.has_job = 1, a.job = *job;
+    if (proj) a.has_proj = 1, a.proj = *proj;
+    Carver tc{nullptr, 0};
+    const uint64_t t_data = tc.bytes(8 * n), t_ikeys = tc.bytes(8 * n), t_ikoff = tc.bytes(8 * n), t_boff = tc.bytes(8 * n);
+    const uint64_t t_nblk = tc.bytes(8 * n), t_gblk = tc.bytes(8 * (n + 1)), t_nent = tc.bytes(8 * n);
+    const uint64_t t_rstart = tc.bytes(4 * ((uint64_t)nruns + 1)), t_total = tc.off;
+    if (!c->tab_ev.wait() || !c->pin_tab.ensure(t_total) || !c->cx_tab.ensure(t_total)) return SDB_DEVICE_ERROR;
+    const uint8_t **h_data = c->pin_tab.at<const uint8_t *>(t_data), **h_ikeys = c->pin_tab.at<const uint8_t *>(t_ikeys);
+    const uint64_t **h_ikoff = c->pin_tab.at<const uint64_t *>(t_ikoff), **h_boff = c->pin_tab.at<const uint64_t *>(t_boff);
+    uint64_t *h_nblk = c->pin_tab.at<uint64_t>(t_nblk), *h_gblk = c->pin_tab.at<uint64_t>(t_gblk);
+    uint64_t *h_nent = c->pin_tab.at<uint64_t>(t_nent);
+    uint32_t *h_rstart = c->pin_tab.at<uint32_t>(t_rstart);
+    uint64_t B_all = 0, E_all = 0, K_all = 0;
+    uintptr_t base = ~(uintptr_t)0;
+    for (uint32_t i = 0; i < ninputs; i++) {
+        const sdb_compaction_input &x = inputs[i].sst;
+        if (x.num_blocks && (uintptr_t)x.data < base) base = (uintptr_t)x.data;
+        h_data[i] = x.data;
+        h_ikeys[i] = inputs[i].index_keys;
+        h_ikoff[i] = inputs[i].index_key_off;
+        h_boff[i] = x.block_off;
+        h_nblk[i] = x.num_blocks;
+        h_gblk[i] = B_all;
+        h_nent[i] = x.num_entries;
+        B_all += x.num_blocks;
+        E_all += x.num_entries;
+        K_all += x.key_bytes;
+    }
+    h_gblk[ninputs] = B_all;
+    if (base == ~(uintptr_t)0) base = 0;
+    for (uint32_t r = 0; r <= nruns; r++) h_rstart[r] = run_start ? run_start[r] : r;
+    if (hipMemcpyAsync(c->cx_tab.p, c->pin_tab.p, t_total, hipMemcpyHostToDevice, s) != hipSuccess) return SDB_DEVICE_ERROR;
+    struct TabRelease {  // on every return from here: everything enqueued so far precedes the event
+        sdb_compactor *c;
+        hipStream_t s;
+        ~TabRelease() { c->tab_ev.record(s); }
+    } tab_release{c, s};
+    a.index_keys = c->cx_tab.at<const uint8_t *const>(t_ikeys);
+    a.index_key_off = c->cx_tab.at<const uint64_t *const>(t_ikoff);
+    a.block_off = c->cx_tab.at<const uint64_t *const>(t_boff);
+    a.num_blocks = c->cx_tab.at<const uint64_t>(t_nblk);
+    a.gblock = c->cx_tab.at<const uint64_t>(t_gblk);
+    a.num_entries = c->cx_tab.at<const uint64_t>(t_nent);
+    a.run_start = c->cx_tab.at<const uint32_t>(t_rstart);
+    // what the kernels write
+    const uint64_t nres = kRxResult + (uint64_t)nruns + 1;
+    auto bind_rx = [&](uint8_t *w) {
+        Carver k{w, 0};
+        k.take(a.cover, 2 * n + 1);
+        k.take(a.cov_off, n);
+        k.take(a.cov_first, n + 1);
+        k.take(a.lo, n);
+        k.take(a.hi, n);
+        k.take(a.out_first, n + 1);
+        k.take(a.out_key, n + 1);
+        k.take(a.result, nres);
+        k.take(a.clipped, n);
+        return k.off;
+    };
+    if (!c->rx_ws.ensure(bind_rx(nullptr), c->canaries)) return SDB_DEVICE_ERROR;
+    bind_rx(c->rx_ws.base());
+
+    // 1. the view ranges and their covering blocks; synchronisation 1: the host sizes the decode from them
+    if (!c->pin.ensure(8 * std::max(2 * n + 1, nres))) return SDB_DEVICE_ERROR;
+    uint64_t *h_words = c->pin.at<uint64_t>(0);
+    if (launch_rx_cover(a, s) != hipSuccess ||
+        hipMemcpyAsync(h_words, a.cover, 8 * (2 * n + 1), hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
         return SDB_DEVICE_ERROR;
-    c->msum = *rd.sum;
-    if (c->msum.status) return (sdb_status)c->msum.status;
-    const uint64_t n = c->msum.num_out;
-    c->merged = batch_of(out, n);
-    if (!n) return SDB_OK;
+    sdb_range_job_stats &rs = c->rstats;
+    rs.blocks_total = B_all;
+    if (h_words[2 * n]) {  // R7: a malformed range
+        c->msum.status = (int32_t)h_words[2 * n];
+        c->msum.first_error_entry = ~0ull;
+        return (sdb_status)c->msum.status;
+    }
+    uint64_t B = 0, E = 0, K = 0, V = 0;  // the covered blocks, and the declared counts of the inputs that have any
+    for (uint32_t i = 0; i < ninputs; i++) {
+        const uint64_t nb = h_words[2 * i + 1] - h_words[2 * i];
+        if (!nb) continue;
+        const sdb_compaction_input &x = inputs[i].sst;
+        rs.inputs_read++;
+        B += nb;
+        E += x.num_entries;
+        K += x.key_bytes;
+        V += x.val_bytes;
+    }
+    rs.blocks_checked = B;
+    if (E >= (1ull << 31)) return SDB_LIMIT_EXCEEDED;
 
-    // 3. encode every output SST
-    return encode_outputs(c, rd, n, params, stream, num_ssts);
+    // 2. decode the covered blocks, clip their rows to the view ranges, gate; synchronisation 2: the row ranges
+    CxInputs in{};
+    in.n = ninputs;
+    in.nruns = nruns;
+    in.base = base;
+    in.nblocks = B;
+    in.data = c->cx_tab.at<const uint8_t *const>(t_data);
+    in.block_off = a.cov_off;
+    in.first_block = a.cov_first;
+    DecodeBufs db;
+    if (!c->dec.ensure(decode_bufs_bind(db, B, K, E, nullptr)) || !c->dec_ws.ensure(sdb_decode_workspace_bytes(B)))
+        return SDB_DEVICE_ERROR;
+    decode_bufs_bind(db, B, K, E, c->dec.at<uint8_t>(0));
+    const uint8_t *arena = reinterpret_cast<const uint8_t *>(base);
+    if (launch_cx_blocks(in, db.bstart, db.bend, s) != hipSuccess) return SDB_DEVICE_ERROR;
+    st = sdb_decode_blocks_ex(arena, db.bstart, db.bend, B, input_sst_version, SDB_DECODE_FAIL_FAST, &db.out, c->dec_ws.p,
+                              c->dec_ws.cap, stream);
+    if (st) return st;
+    if (launch_rx_clip_gate(a, db.out, decode_err_word(c->dec_ws.p, B), E_all, K_all, s) != hipSuccess ||
+        hipMemcpyAsync(h_words, a.result, 8 * nres, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return SDB_DEVICE_ERROR;
+    const uint64_t gate = h_words[kRxGate], rows = h_words[kRxIn], key_bytes = h_words[kRxKeyBytes];
+    rs.entries_decoded = h_words[kRxDecoded];
+    rs.entries_in = rows;
+    if (gate != ~0ull) {  // a failing covered block, or counts that disagree (R6): nothing is merged
+        c->msum.num_in = E;
+        c->msum.status = (int32_t)(gate & 0xFF);
+        c->msum.first_error_entry = gate >> 8;
+        return (sdb_status)c->msum.status;
+    }
+    const std::vector<uint64_t> run_entry(h_words + kRxResult, h_words + nres);  // (c->pin is reused below)
+    const sdb_decoded_out *src = &db.out;
+    sdb_decoded_out closed;
+    if (rows != rs.entries_decoded) {  // a range dropped rows: the runs must not have gaps
+        if (!c->rx_cols.ensure(range_cols_bind(closed, rows, key_bytes, nullptr), c->canaries)) return SDB_DEVICE_ERROR;
+        range_cols_bind(closed, rows, key_bytes, c->rx_cols.base());
+        if (launch_rx_compact(a, db.out, closed, rows, s) != hipSuccess) return SDB_DEVICE_ERROR;
+        src = &closed;
+    }
+    const std::vector<sdb_run> runs = runs_over(*src, arena, run_entry.data(), nruns);
+    return merge_encode(c, runs, rows, key_bytes, V, nullptr, ret, op, ctx, params, max_sst_size, stream, num_ssts);
 }
 
 }  // namespace
@@ -813,21 +1029,56 @@ sdb_status sdb_compactor_run_ssts_merge(sdb_compactor *c, const sdb_compaction_i
                         stream, num_ssts);
 }
 
+sdb_status sdb_compactor_run_ssts_ranged(sdb_compactor *c, const sdb_compaction_view *inputs, uint32_t ninputs,
+                                         const uint32_t *run_start, uint32_t nruns, uint16_t input_sst_version,
+                                         const sdb_scan_ranges *job_range, const sdb_scan_ranges *proj,
+                                         const sdb_retention *ret, sdb_merge_batch_fn op, void *ctx,
+                                         const sdb_sst_params *params, uint64_t max_sst_size, void *stream,
+                                         uint32_t *num_ssts) {
+    // R7 on the host, before anything needs a device
+    if (!ret || !params || !num_ssts || (ninputs && !inputs)) return SDB_INVALID_ARGUMENT;
+    if (job_range && (job_range->n != 1 || ranges_null(job_range))) return SDB_INVALID_ARGUMENT;
+    if (proj && (proj->n != ninputs || ranges_null(proj))) return SDB_INVALID_ARGUMENT;
+    for (uint32_t i = 0; i < ninputs; i++) {
+        const sdb_compaction_view &x = inputs[i];
+        if (x.sst.num_blocks && (!x.sst.data || !x.sst.block_off || !x.index_keys || !x.index_key_off))
+            return SDB_INVALID_ARGUMENT;
+    }
+    if (!c) {  // (no handle exists without a device)
+        int n = 0;
+        return hipGetDeviceCount(&n) != hipSuccess || n == 0 ? SDB_DEVICE_ERROR : SDB_INVALID_ARGUMENT;
+    }
+    return run_ranged_job(c, inputs, ninputs, run_start, nruns, input_sst_version, job_range, proj, ret, op, ctx, params,
+                          max_sst_size, stream, num_ssts);
+}
+
+sdb_status sdb_compactor_range_stats(const sdb_compactor *c, sdb_range_job_stats *stats) {
+    if (!c || !stats) return SDB_INVALID_ARGUMENT;
+    *stats = c->rstats;
+    return SDB_OK;
+}
+
 sdb_status sdb_compactor_merge_stats(const sdb_compactor *c, sdb_merge_op_stats *stats) {
     if (!c || !stats) return SDB_INVALID_ARGUMENT;
     *stats = c->mstats;
     return SDB_OK;
 }
 
-// Diagnostics (not in the header): guard bands around the buffers of the merge-operator step (GuardBuf), and
+// Diagnostics (not in the header): guard bands around the buffers of the merge-operator step and of the ranged
+// job's input side (GuardBuf), and
 // the guard bytes the last job changed (synchronises the device; -1: the check could not run).
 void sdb_diag_compactor_canaries(sdb_compactor *c, int on) {
     if (c) c->canaries = on != 0;
 }
 int64_t sdb_diag_compactor_canary_damage(sdb_compactor *c) {
     if (!c || hipSetDevice(c->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return -1;
-    const int64_t x = c->chain_ws.damaged(), y = c->chain_tab.damaged(), z = c->chain_up.damaged();
-    return x < 0 || y < 0 || z < 0 ? -1 : x + y + z;
+    int64_t sum = 0;
+    for (const GuardBuf *b : {&c->chain_ws, &c->chain_tab, &c->chain_up, &c->rx_ws, &c->rx_cols}) {
+        const int64_t x = b->damaged();
+        if (x < 0) return -1;
+        sum += x;
+    }
+    return sum;
 }
 
 sdb_status sdb_compactor_sst(const sdb_compactor *c, uint32_t i, sdb_compacted_sst *out) {

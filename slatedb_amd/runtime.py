@@ -1332,6 +1332,53 @@ class Compactor:
         """sdb_compactor_run_ssts_merge: run_ssts() with the store's merge operator."""
         return self._run_ssts(inputs, ret, operator, prm, max_sst_size, input_version, run_start, stream)
 
+    def run_ssts_ranged(self, inputs, ret, prm, max_sst_size, job_range=None, projections=None, operator=None,
+                        input_version=2, run_start=None, stream=None):
+        """sdb_compactor_run_ssts_ranged: run_ssts() (with `operator`: run_ssts_merge()) over one job range and a
+        visible range per input.  inputs: as run_ssts, plus .index_keys / .index_key_off (device tensors: each
+        block's index key).  job_range: (start, start_kind, end, end_kind) as scan_ranges_columnar takes it, or
+        None = unbounded; projections: one such tuple or None (the whole SST) per input, as projections_columnar
+        takes them, or None; either may also be the dict of arrays those functions return (host arrays, or device
+        tensors the caller keeps)."""
+        dev = inputs[0].data.device if inputs else "cuda"
+        cv = (_abi.CompactionView * max(len(inputs), 1))(*[
+            _abi.CompactionView(_abi.CompactionInput(x.data.data_ptr(), x.block_off.data_ptr(), x.block_off.numel() - 1,
+                                                     x.num_entries, x.key_bytes, x.val_bytes),
+                                x.index_keys.data_ptr(), x.index_key_off.data_ptr()) for x in inputs])
+        rs = None
+        nruns = len(inputs)
+        if run_start is not None:
+            rs = (C.c_uint32 * len(run_start))(*run_start)
+            nruns = len(run_start) - 1
+        keep = []
+
+        def ranges(arrays):  # the arrays of an sdb_scan_ranges (host, or already on the device) -> the struct
+            t = {k: a if hasattr(a, "data_ptr") else _to_dev(a, dev) for k, a in arrays.items() if k != "n"}
+            keep.append(t)
+            return C.byref(_abi.ScanRanges(len(t["start_off"]) - 1, _ptr(t["start_bytes"]), _ptr(t["start_off"]),
+                                           _ptr(t["start_kind"]), _ptr(t["end_bytes"]), _ptr(t["end_off"]),
+                                           _ptr(t["end_kind"])))
+        columnar = lambda x, f: x if isinstance(x, dict) else f(x)  # noqa: E731  (a dict: the host arrays themselves)
+        jr = None if job_range is None else ranges(columnar(job_range, lambda r: scan_ranges_columnar([r])))
+        pj = None if projections is None else ranges(columnar(projections, projections_columnar))
+        cb = _abi.MERGE_BATCH_FN()  # NULL: no operator
+        if operator is not None:
+            cb, self.operator_state = self._operator_callback(operator)
+        ns = C.c_uint32(0)
+        st = lib().sdb_compactor_run_ssts_ranged(self.h, cv, len(inputs), rs, nruns, input_version, jr, pj, C.byref(ret),
+                                                 cb, None, C.byref(prm), max_sst_size, _sp(stream), C.byref(ns))
+        _sync(stream, dev)  # the range tensors are released on return
+        self.status = st
+        return st, ns.value
+
+    def range_stats(self):
+        """sdb_range_job_stats of the last run_ssts_ranged job (zeros after any other)."""
+        rs = _abi.RangeJobStats()
+        st = lib().sdb_compactor_range_stats(self.h, C.byref(rs))
+        if st:
+            raise SdbError(st, "sdb_compactor_range_stats")
+        return rs
+
     def merge_stats(self):
         """sdb_merge_op_stats of the last job (zeros after a job without an operator)."""
         ms = _abi.MergeOpStats()

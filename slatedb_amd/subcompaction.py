@@ -11,7 +11,8 @@ ranges reach the next multiple of max(total / max_subcompactions, largest input 
 Here the planner is host code over the same metadata this repo's footer writes (block first keys =
 index keys, BlockMeta offsets, the data section's end), and a subcompaction is a compaction of every
 input run cut to its range (`slice_run`: a binary search on the run's sorted keys; runs are views, nothing
-is copied).  Range r goes to rank r mod N (the same dealing as job.assign for SSTs), each rank runs its
+is copied), or, from the encoded inputs, sdb_compactor_run_ssts_ranged with `range_bounds` of the range: the
+device then reads only the blocks that cover it.  Range r goes to rank r mod N (the same dealing as job.assign for SSTs), each rank runs its
 ranges through its own sdb_compactor, and there is no collective on the data path: the ranges are
 independent, and their outputs concatenate to the unsplit compaction's merged stream (the retention
 filter sees every version of a key inside one range, since a key never straddles a boundary).
@@ -94,11 +95,13 @@ def select_boundaries(anchors, max_subcompactions, min_range_bytes):
 class SstMeta:
     """What the planner reads of one input SST: its index (block first keys, BlockMeta offsets), the end of
     the data section (filter_offset) and its size estimate (index_offset + index_len, db_state.rs:50-52)."""
-    __slots__ = ("first_keys", "offsets", "data_len", "size")
+    __slots__ = ("first_keys", "offsets", "data_len", "size", "effective_range")
 
-    def __init__(self, first_keys, offsets, data_len, size=None):
+    def __init__(self, first_keys, offsets, data_len, size=None, effective_range=None):
         self.first_keys, self.offsets, self.data_len = list(first_keys), np.asarray(offsets), int(data_len)
         self.size = int(size) if size is not None else int(data_len)
+        # SsTableView::effective_range of a projected input (any object with contains(key)); None: the whole SST
+        self.effective_range = effective_range
 
     @classmethod
     def from_encoded(cls, batch, enc, footer_len=0):
@@ -119,8 +122,16 @@ def plan_subcompaction_ranges(ssts, max_subcompactions, max_anchors=MAX_ANCHORS_
     min_range_bytes = max((s.size for s in ssts), default=0)
     anchors = []
     for s in ssts:
-        anchors += sample_anchors(s.first_keys, s.offsets, s.data_len, max_anchors)
+        anchors += sample_anchors(s.first_keys, s.offsets, s.data_len, max_anchors, s.effective_range)  # :155-160
     return select_boundaries(anchors, max_subcompactions, min_range_bytes)
+
+
+def range_bounds(rng):
+    """The job range of a planner range, as Compactor.run_ssts_ranged takes it: (start, start_kind, end, end_kind)
+    = Included(start) / Excluded(end), an open side unbounded."""
+    from . import _abi
+    return (rng.start, _abi.BOUND_UNBOUNDED if rng.start is None else _abi.BOUND_INCLUDED,
+            rng.end, _abi.BOUND_UNBOUNDED if rng.end is None else _abi.BOUND_EXCLUDED)
 
 
 def assign_ranges(ranges, world):
