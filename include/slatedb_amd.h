@@ -1223,6 +1223,95 @@ sdb_status sdb_compactor_run_ssts_ranged(sdb_compactor *c, const sdb_compaction_
 sdb_status sdb_compactor_range_stats(const sdb_compactor *c, sdb_range_job_stats *stats);
 
 /* ---------------------------------------------------------------------------------------------
+ * WAL replay / device memtable: decoded rows in WAL (arrival) order -> the replayed memtables as sorted
+ * runs, ready for the flush (sdb_compactor_run with one run).  Replaces WalReplayIterator::next
+ * (wal_replay.rs:111-184) feeding KVTable::put (mem_table.rs:524-557), one skiplist insert per row.
+ * Input: `nbatches` WAL batches in order, a batch being the rows of one WalRows (wal/slatedb/iterator.rs:
+ * 376-423) in insertion order; the rows of all batches are concatenated in one sdb_run (what
+ * sdb_decode_blocks* produces from WAL SST blocks), batch b = rows [batch_start[b], batch_start[b + 1]).
+ * A batch may be empty.
+ *   W1  a row with seq <= min_seq (when has_min_seq) is skipped (wal_replay.rs:146) and touches nothing.
+ *   W2  the smallest seq of a non-empty batch must exceed the largest seq of every earlier batch
+ *       (iterator.rs:394-419), over all rows, before W1: else status SDB_INVALID_ARGUMENT with
+ *       first_error_entry = the first offending batch, and nothing is emitted.
+ *   W3  a table's rows are ordered key ascending (<[u8] as Ord>), then seq descending (mem_table.rs:38-44).
+ *   W4  of two kept rows with equal (key, seq) the later arrival replaces the earlier (compare_insert with
+ *       an always-true predicate, mem_table.rs:540-547); by W2 both lie in one batch.
+ *   W5  per batch, after W1 and W4: sdb_wal_batch_facts.
+ *   W6  the host walks the facts: batches are applied in order, and a non-empty table whose
+ *       estimate_encoded_size_compacted(entry_num, entries_size_in_bytes) >= max_memtable_bytes closes after
+ *       the batch (wal_replay.rs:157-165); a table that had a batch applied is returned even when empty.
+ *       The estimate is host configuration (format/sst.rs:1041-1160), so this step stays on the host:
+ *       slatedb_amd/replay.py split_tables.
+ *   W7  table metadata (entry_num, entries_size_in_bytes, first_seq, last_seq, last_tick) are sums / minima /
+ *       maxima of the facts of the table's batches.
+ * sdb_wal_replay_sort: W1, W2, the order of W3 as a permutation in the workspace, W4, W5 and the summary.
+ * sdb_wal_replay_emit: given the W6 split (table t = batches [table_batch_start[t], table_batch_start[t + 1]),
+ * ntables <= nbatches), the tables as one output stream: table t = rows [table_row_start[t],
+ * table_row_start[t + 1]), viewed as an sdb_kv_batch like a compactor's cut SST views the merged stream
+ * (key_off / val_off are offsets into the one arena; values are copied, so every table's are contiguous).
+ * Both calls are asynchronous on `stream`, allocate nothing, can be captured into a HIP graph, and reuse
+ * the workspace without a host reset.  Capacities: cap_entries >= n, key_cap >= the input's key bytes and
+ * val_cap >= its value bytes always suffice; a short one gives SDB_LIMIT_EXCEEDED in the summary (with the
+ * sizes needed) and nothing else is written.  batch_start must run monotonically from 0 to n and
+ * table_batch_start from 0 to nbatches: checked on the device, a violation gives SDB_INVALID_ARGUMENT in
+ * the summary (first_error_entry = the index of the offending element) and nothing is read through it.
+ * n == 0 or nbatches == 0: SDB_OK with zeroed facts and summary (with n == 0 and batches, batch_start is still
+ * checked: every element 0).  n < 2^31.
+ * A live memtable collected in arrival order is the same pair of calls with nbatches = 1, has_min_seq = 0.
+ * Out of scope: WAL object listing and fetch, touched_segments, the sequence tracker, and errors the WAL
+ * iterator holds back (terminal_result): the caller stops feeding batches at the error.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct sdb_wal_batch_facts {     /* W5; all zero for a batch no row of which passed W1 */
+    uint64_t rows;                       /* rows that survive W1 and W4 */
+    uint64_t bytes;                      /* sum of RowEntry::estimated_size (types.rs:48-60) over the survivors */
+    uint64_t replaced;                   /* rows W4 removed */
+    uint64_t min_seq, max_seq;           /* over every row that passed W1, replaced rows included (put updates
+                                            them before the insert, mem_table.rs:531-537); valid iff rows > 0 */
+    int64_t max_create_ts;               /* over the same rows that carry one; valid iff any_create_ts */
+    uint32_t any_create_ts;
+    uint32_t pad;
+} sdb_wal_batch_facts;
+typedef struct sdb_wal_replay_summary {
+    uint64_t rows_in;                    /* n */
+    uint64_t rows_skipped;               /* W1 */
+    uint64_t rows_replaced;              /* W4 */
+    uint64_t rows_out;                   /* survivors = rows of all tables */
+    uint64_t key_bytes, val_bytes;       /* of the survivors (a tombstone's value bytes are 0) */
+    int32_t status;                      /* SDB_OK | SDB_INVALID_ARGUMENT | SDB_LIMIT_EXCEEDED (emit) */
+    uint32_t pad;
+    uint64_t first_error_entry;          /* the batch (W2, batch_start) or table_batch_start element; else ~0 */
+} sdb_wal_replay_summary;
+typedef struct sdb_wal_tables_out {      /* the columns of sdb_merged_out + the tables' row ranges */
+    uint8_t *key_bytes;
+    uint64_t key_cap;
+    uint64_t *key_off;                   /* cap_entries + 1 */
+    uint8_t *val_bytes;
+    uint64_t val_cap;
+    uint64_t *val_off;                   /* cap_entries + 1 */
+    uint8_t *kind;                       /* from the RowFlags: tombstone, merge operand, else value */
+    uint64_t *seq;
+    int64_t *create_ts;
+    int64_t *expire_ts;
+    uint8_t *ts_mask;
+    uint64_t cap_entries;
+    uint64_t *table_row_start;           /* device, ntables + 1 */
+    sdb_wal_replay_summary *summary;     /* device-writable */
+} sdb_wal_tables_out;
+uint64_t sdb_wal_replay_workspace_bytes(uint64_t n, uint64_t nbatches);
+sdb_status sdb_wal_replay_sort(const sdb_run *rows, const uint64_t *batch_start /* device, nbatches + 1 */,
+                               uint64_t nbatches, uint64_t min_seq, int32_t has_min_seq,
+                               sdb_wal_batch_facts *facts /* device, nbatches */,
+                               sdb_wal_replay_summary *summary /* device */,
+                               void *workspace, uint64_t workspace_bytes, void *stream);
+sdb_status sdb_wal_replay_emit(const sdb_run *rows, const uint64_t *batch_start, uint64_t nbatches,
+                               const uint64_t *table_batch_start /* device, ntables + 1, batch indices */,
+                               uint64_t ntables, const sdb_wal_tables_out *out,
+                               void *workspace /* as _sort left it */, uint64_t workspace_bytes, void *stream);
+/* Rows one tile-sort workgroup orders in LDS (the tests sit on its boundaries). */
+uint32_t sdb_diag_replay_tile(void);
+
+/* ---------------------------------------------------------------------------------------------
  * SST footer (host): everything after the data section, so data ++ footer is the whole SST object
  * EncodedSsTableBuilder::build / EncodedWalSsTableBuilder::build hand to write_sst.
  * Replaces EncodedSsTableFooterBuilder::build (format/sst.rs:383-487) plus the index the builders

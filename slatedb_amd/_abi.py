@@ -319,6 +319,30 @@ class MergeOpStats(C.Structure):
     ]
 
 
+class WalBatchFacts(C.Structure):
+    _fields_ = [
+        ("rows", C.c_uint64), ("bytes", C.c_uint64), ("replaced", C.c_uint64), ("min_seq", C.c_uint64),
+        ("max_seq", C.c_uint64), ("max_create_ts", C.c_int64), ("any_create_ts", C.c_uint32), ("pad", C.c_uint32),
+    ]
+
+
+class WalReplaySummary(C.Structure):
+    _fields_ = [
+        ("rows_in", C.c_uint64), ("rows_skipped", C.c_uint64), ("rows_replaced", C.c_uint64), ("rows_out", C.c_uint64),
+        ("key_bytes", C.c_uint64), ("val_bytes", C.c_uint64), ("status", C.c_int32), ("pad", C.c_uint32),
+        ("first_error_entry", C.c_uint64),
+    ]
+
+
+class WalTablesOut(C.Structure):
+    _fields_ = [
+        ("key_bytes", C.c_void_p), ("key_cap", C.c_uint64), ("key_off", C.c_void_p),
+        ("val_bytes", C.c_void_p), ("val_cap", C.c_uint64), ("val_off", C.c_void_p),
+        ("kind", C.c_void_p), ("seq", C.c_void_p), ("create_ts", C.c_void_p), ("expire_ts", C.c_void_p),
+        ("ts_mask", C.c_void_p), ("cap_entries", C.c_uint64), ("table_row_start", C.c_void_p), ("summary", C.c_void_p),
+    ]
+
+
 # sdb_merge_batch_fn: (ctx, key, key_len, existing, existing_len, operands, operand_len, n, result, result_len)
 MERGE_BATCH_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, u8p, C.c_uint64, u8p, C.c_uint64, C.POINTER(u8p), u64p,
                              C.c_uint32, C.POINTER(u8p), u64p)
@@ -437,6 +461,12 @@ SIGNATURES = {
                                                 C.POINTER(Retention), MERGE_BATCH_FN, C.c_void_p,
                                                 C.POINTER(SstParams), C.c_uint64, C.c_void_p, u32p]),
     "sdb_compactor_range_stats": (C.c_int, [C.c_void_p, C.POINTER(RangeJobStats)]),
+    "sdb_wal_replay_workspace_bytes": (C.c_uint64, [C.c_uint64, C.c_uint64]),
+    "sdb_wal_replay_sort": (C.c_int, [C.POINTER(Run), C.c_void_p, C.c_uint64, C.c_uint64, C.c_int32, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "sdb_wal_replay_emit": (C.c_int, [C.POINTER(Run), C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                      C.POINTER(WalTablesOut), C.c_void_p, C.c_uint64, C.c_void_p]),
+    "sdb_diag_replay_tile": (C.c_uint32, []),
     "sdb_compactor_sst": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(CompactedSst)]),
     "sdb_compactor_merged": (C.c_int, [C.c_void_p, C.POINTER(KvBatch), C.POINTER(MergeSummary)]),
     "sdb_sst_footer": (C.c_int, [C.POINTER(FooterIn), C.c_void_p, C.c_uint64, u64p]),

@@ -17,6 +17,7 @@
 #include "sdb_bloom.h"
 #include "sdb_compact.h"
 #include "sdb_reads.h"
+#include "sdb_replay.h"
 
 using namespace sdb;
 
@@ -799,6 +800,73 @@ sdb_status sdb_lsm_scan_projected(const sdb_lsm_view *lsm, const sdb_scan_ranges
     return lsm_scan_call(lsm, proj, ranges, max_seq, descending, cand_entries, cand_key_bytes, out, chain != nullptr, chain,
                          true, policies, prefixes, fout, workspace, workspace_bytes, stream);
 }
+
+// ---- WAL replay / device memtable ----
+uint64_t sdb_wal_replay_workspace_bytes(uint64_t n, uint64_t nbatches) {
+    ReplayArgs a{};
+    a.n = n;
+    a.nbatches = nbatches;
+    return replay_bind(a, nullptr) + 256;
+}
+
+// The checks both calls share, and the arguments they share.
+static sdb_status replay_args(const sdb_run *rows, const uint64_t *batch_start, uint64_t nbatches, void *workspace,
+                              uint64_t workspace_bytes, ReplayArgs *a) {
+    if (!rows || !workspace) return SDB_INVALID_ARGUMENT;
+    const uint64_t n = rows->n;
+    if (nbatches && !batch_start) return SDB_INVALID_ARGUMENT;
+    if (n && (!rows->key_arena || !rows->key_off || !rows->val_base || !rows->val_off || !rows->val_len || !rows->seq ||
+              !rows->flags))
+        return SDB_INVALID_ARGUMENT;
+    if (n >= kReplaySkip) return SDB_LIMIT_EXCEEDED;  // the permutation is 31 bits and a flag
+    *a = ReplayArgs{};
+    a->n = n;
+    a->nbatches = nbatches;
+    a->r = *rows;
+    a->batch_start = batch_start;
+    if (workspace_bytes < replay_bind(*a, nullptr) + 256) return SDB_INVALID_ARGUMENT;
+    replay_bind(*a, ws_align(workspace));
+    a->ntiles = (uint32_t)((n + kReplayTile - 1) / kReplayTile);
+    a->nblocks = (uint32_t)((n + kReplayBlock - 1) / kReplayBlock);
+    for (uint64_t run = kReplayTile; run < n; run *= 2) a->npass++;
+    a->sorted = a->perm[a->npass & 1];
+    return SDB_OK;
+}
+
+sdb_status sdb_wal_replay_sort(const sdb_run *rows, const uint64_t *batch_start, uint64_t nbatches, uint64_t min_seq,
+                               int32_t has_min_seq, sdb_wal_batch_facts *facts, sdb_wal_replay_summary *summary,
+                               void *workspace, uint64_t workspace_bytes, void *stream) {
+    ReplayArgs a;
+    if (!summary || (nbatches && !facts)) return SDB_INVALID_ARGUMENT;
+    sdb_status st = replay_args(rows, batch_start, nbatches, workspace, workspace_bytes, &a);
+    if (st) return st;
+    a.min_seq = min_seq;
+    a.has_min_seq = has_min_seq ? 1u : 0u;
+    a.facts = facts;
+    a.summary = summary;
+    if (!device_ok()) return SDB_DEVICE_ERROR;
+    return launch_replay_sort(a, S(stream)) == hipSuccess ? SDB_OK : SDB_DEVICE_ERROR;
+}
+
+sdb_status sdb_wal_replay_emit(const sdb_run *rows, const uint64_t *batch_start, uint64_t nbatches,
+                               const uint64_t *table_batch_start, uint64_t ntables, const sdb_wal_tables_out *out,
+                               void *workspace, uint64_t workspace_bytes, void *stream) {
+    ReplayArgs a;
+    if (!out || !out->summary || !out->table_row_start || !table_batch_start || ntables > nbatches)
+        return SDB_INVALID_ARGUMENT;
+    sdb_status st = replay_args(rows, batch_start, nbatches, workspace, workspace_bytes, &a);
+    if (st) return st;
+    if (a.n && (!out->key_bytes || !out->key_off || !out->val_bytes || !out->val_off || !out->kind || !out->seq ||
+                !out->create_ts || !out->expire_ts || !out->ts_mask))
+        return SDB_INVALID_ARGUMENT;
+    a.table_batch_start = table_batch_start;
+    a.ntables = ntables;
+    a.out = *out;
+    if (!device_ok()) return SDB_DEVICE_ERROR;
+    return launch_replay_emit(a, S(stream)) == hipSuccess ? SDB_OK : SDB_DEVICE_ERROR;
+}
+
+uint32_t sdb_diag_replay_tile(void) { return kReplayTile; }
 
 }  // extern "C"
 

@@ -193,6 +193,28 @@ SDB_DEV uint32_t lcp_bytes(const uint8_t *a, uint32_t na, const uint8_t *b, uint
     return n;
 }
 
+// Comparison keys of the merge and of the WAL replay sort (sdb_compact.hip, sdb_replay.hip).
+SDB_DEV uint64_t key_prefix(const uint8_t *p, uint32_t n) {  // first 8 bytes, big-endian, zero padded
+    if (!n) return 0;
+    const uint32_t need = n < 8 ? n : 8;
+    uint64_t v = load8(p, need);
+    if (need < 8) v &= (~0ull) >> (8 * (8 - need));
+    return bswap64(v);
+}
+
+// <[u8] as Ord>::cmp given the prefixes of bytes [s, s + 8) of two keys whose bytes [0, s) are equal:
+// -1, 0, 1
+SDB_DEV int cmp_key(uint64_t pa, const uint8_t *a, uint32_t na, uint64_t pb, const uint8_t *b, uint32_t nb,
+                    uint32_t s = 0) {
+    if (pa != pb) return pa < pb ? -1 : 1;
+    const uint32_t t = s + 8;
+    if (na > t && nb > t) {
+        const uint32_t l = lcp_bytes(a + t, na - t, b + t, nb - t), m = (na < nb ? na : nb) - t;
+        if (l < m) return a[t + l] < b[t + l] ? -1 : 1;
+    }
+    return na < nb ? -1 : (na > nb ? 1 : 0);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Wave primitives (wave64)
 // ------------------------------------------------------------------------------------------------

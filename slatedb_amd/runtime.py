@@ -1430,3 +1430,141 @@ class Compactor:
             self.close()
         except Exception:
             pass
+
+
+# ------------------------------------------------------------------------------------------------
+# WAL replay / device memtable (sdb_wal_replay_sort, sdb_wal_replay_emit)
+# ------------------------------------------------------------------------------------------------
+class ReplayedTable:
+    """One replayed memtable: rows [lo, hi) of the replay's output stream (device tensors shared by every table
+    of the call) and its W7 metadata (replay.table_metadata)."""
+
+    def __init__(self, cols, lo, hi, meta):
+        self.cols, self.lo, self.hi, self.meta = cols, lo, hi, meta
+        self.n = hi - lo
+
+    def _p(self, name, width):
+        return self.cols[name].data_ptr() + self.lo * width
+
+    def to_ctypes(self):
+        """The table as an sdb_kv_batch: offsets index the shared arenas, as a compactor's cut SST views the
+        merged stream."""
+        c = self.cols
+        return _abi.KvBatch(self.n, c["key_bytes"].data_ptr(), self._p("key_off", 8), c["val_bytes"].data_ptr(),
+                            self._p("val_off", 8), self._p("kind", 1), self._p("seq", 8), self._p("create_ts", 8),
+                            self._p("expire_ts", 8), self._p("ts_mask", 1), None)
+
+    def as_run(self):
+        """The table as the one sorted run of its flush (sdb_compactor_run, flush.rs:186-236)."""
+        import torch
+        c, lo, hi = self.cols, self.lo, self.hi
+        koff, voff = c["key_off"][lo:hi + 1], c["val_off"][lo:hi + 1]
+        kind, mask = c["kind"][lo:hi], c["ts_mask"][lo:hi]
+        flags = (torch.where(kind == _abi.KIND_TOMBSTONE, _abi.FLAG_TOMBSTONE, 0) |
+                 torch.where(kind == _abi.KIND_MERGE, _abi.FLAG_MERGE_OPERAND, 0) |
+                 torch.where((mask & _abi.TS_CREATE) != 0, _abi.FLAG_HAS_CREATE_TS, 0) |
+                 torch.where((mask & _abi.TS_EXPIRE) != 0, _abi.FLAG_HAS_EXPIRE_TS, 0)).to(torch.uint8)
+        vlen = (voff[1:] - voff[:-1]).to(torch.int32)
+        pad = lambda t: torch.cat([t.contiguous().view(torch.uint8), torch.zeros(16, dtype=torch.uint8, device=t.device)])
+        kb = int((koff[-1] - koff[0]).item()) if self.n else 0
+        vb = int((voff[-1] - voff[0]).item()) if self.n else 0
+        return DeviceRun(self.n, c["key_bytes"], pad(koff), c["val_bytes"], pad(voff[:-1]), pad(vlen), pad(c["seq"][lo:hi]),
+                         pad(flags), pad(c["create_ts"][lo:hi]), pad(c["expire_ts"][lo:hi]), kb, vb)
+
+    def to_host(self):
+        lo, hi = self.lo, self.hi
+        v = lambda k, dt: self.cols[k][lo:hi].cpu().numpy().view(dt)
+        ko = self.cols["key_off"][lo:hi + 1].cpu().numpy().view(np.uint64)
+        vo = self.cols["val_off"][lo:hi + 1].cpu().numpy().view(np.uint64)
+        kb = self.cols["key_bytes"][int(ko[0]):int(ko[-1])].cpu().numpy()
+        vb = self.cols["val_bytes"][int(vo[0]):int(vo[-1])].cpu().numpy()
+        return Batch(kb, ko - ko[0], vb, vo - vo[0], v("kind", np.uint8), v("seq", np.uint64), v("create_ts", np.int64),
+                     v("expire_ts", np.int64), v("ts_mask", np.uint8))
+
+
+class WalReplay:
+    """The two device calls of a replay over one DeviceRun, with the host step between them left to the caller:
+    sort() -> (facts, summary); emit(cuts) -> (columns, table_row_start, summary)."""
+
+    def __init__(self, drun, batch_start, workspace=None, fill=None):
+        import torch
+        self.drun, self.dev = drun, drun.t[0].device
+        self.nb = len(batch_start) - 1
+        self.bs = torch.tensor([int(x) for x in batch_start], dtype=torch.int64, device=self.dev)
+        self.wsb = lib().sdb_wal_replay_workspace_bytes(drun.n, self.nb)
+        self.ws = workspace if workspace is not None else torch.empty(max(self.wsb, 256), dtype=torch.uint8, device=self.dev)
+        self.fill = fill
+        self.run = drun.to_ctypes()
+
+    def _new(self, count, dt):
+        import torch
+        nbytes = max(count, 1) * torch.empty(0, dtype=dt).element_size()
+        return torch.full((nbytes,), self.fill or 0, dtype=torch.uint8, device=self.dev).view(dt)  # fill: the tests' canary
+
+    def sort(self, min_seq=None, stream=None, ws_ptr=None, ws_bytes=None):
+        import torch
+        self.facts_t = self._new(self.nb * C.sizeof(_abi.WalBatchFacts), torch.uint8)
+        self.summary_t = self._new(C.sizeof(_abi.WalReplaySummary), torch.uint8)
+        st = lib().sdb_wal_replay_sort(C.byref(self.run), self.bs.data_ptr(), self.nb, 0 if min_seq is None else min_seq,
+                                       0 if min_seq is None else 1, self.facts_t.data_ptr(), self.summary_t.data_ptr(),
+                                       self.ws.data_ptr() if ws_ptr is None else ws_ptr,
+                                       self.ws.numel() if ws_bytes is None else ws_bytes, _sp(stream))
+        if st:
+            raise SdbError(st, "sdb_wal_replay_sort")
+        _sync(stream, self.dev)
+        raw = self.facts_t.cpu().numpy().tobytes()
+        sz = C.sizeof(_abi.WalBatchFacts)
+        facts = [_abi.WalBatchFacts.from_buffer_copy(raw[b * sz:(b + 1) * sz]) for b in range(self.nb)]
+        return facts, _abi.WalReplaySummary.from_buffer_copy(self.summary_t.cpu().numpy().tobytes())
+
+    def emit(self, cuts, cap_entries=None, key_cap=None, val_cap=None, stream=None, ws_ptr=None, ws_bytes=None, extra=0):
+        """extra: elements allocated behind every capacity (the tests' canaries)."""
+        import torch
+        r = self.drun
+        ce = r.n if cap_entries is None else cap_entries
+        kc = r.key_bytes if key_cap is None else key_cap
+        vc = r.val_bytes if val_cap is None else val_cap
+        nt = len(cuts) - 1
+        tbs = torch.tensor([int(x) for x in cuts], dtype=torch.int64, device=self.dev)
+        x = extra
+        o = {"key_bytes": self._new(kc + 16 + x, torch.uint8), "key_off": self._new(ce + 1 + x, torch.int64),
+             "val_bytes": self._new(vc + 16 + x, torch.uint8), "val_off": self._new(ce + 1 + x, torch.int64),
+             "kind": self._new(ce + x, torch.uint8), "seq": self._new(ce + x, torch.int64),
+             "create_ts": self._new(ce + x, torch.int64), "expire_ts": self._new(ce + x, torch.int64),
+             "ts_mask": self._new(ce + x, torch.uint8),
+             "table_row_start": self._new(nt + 1, torch.int64),
+             "summary": self._new(C.sizeof(_abi.WalReplaySummary), torch.uint8)}
+        out = _abi.WalTablesOut(o["key_bytes"].data_ptr(), kc, o["key_off"].data_ptr(), o["val_bytes"].data_ptr(), vc,
+                                o["val_off"].data_ptr(), o["kind"].data_ptr(), o["seq"].data_ptr(),
+                                o["create_ts"].data_ptr(), o["expire_ts"].data_ptr(), o["ts_mask"].data_ptr(), ce,
+                                o["table_row_start"].data_ptr(), o["summary"].data_ptr())
+        st = lib().sdb_wal_replay_emit(C.byref(self.run), self.bs.data_ptr(), self.nb, tbs.data_ptr(), nt, C.byref(out),
+                                       self.ws.data_ptr() if ws_ptr is None else ws_ptr,
+                                       self.ws.numel() if ws_bytes is None else ws_bytes, _sp(stream))
+        if st:
+            raise SdbError(st, "sdb_wal_replay_emit")
+        _sync(stream, self.dev)
+        sm = _abi.WalReplaySummary.from_buffer_copy(o["summary"].cpu().numpy().tobytes())
+        return o, sm
+
+
+def wal_replay_device(drun, batch_start, min_seq, prm, max_memtable_bytes, last_l0_seq=0, last_l0_clock_tick=-(1 << 63),
+                      wal_ids=None, stream=None):
+    """WalReplayIterator over decoded WAL rows (wal_replay.rs:111-184): drun holds the rows of every batch in
+    arrival order, batch b = rows [batch_start[b], batch_start[b + 1]); min_seq None = no filter.  Runs
+    sdb_wal_replay_sort, reads the per-batch facts, splits the tables on the host (replay.split_tables) and runs
+    sdb_wal_replay_emit.  Returns the ReplayedTables in order (all of them views of one device output)."""
+    from . import replay
+    w = WalReplay(drun, batch_start)
+    facts, sm = w.sort(min_seq, stream)
+    if sm.status:
+        raise SdbError(sm.status, "sdb_wal_replay_sort: batch %d" % sm.first_error_entry)
+    cuts = replay.split_tables(facts, prm, max_memtable_bytes)
+    if len(cuts) < 2:
+        return []
+    o, sm = w.emit(cuts, stream=stream)
+    if sm.status:
+        raise SdbError(sm.status, "sdb_wal_replay_emit")
+    trs = [int(x) for x in o["table_row_start"].cpu().numpy()]
+    meta = replay.table_metadata(facts, cuts, last_l0_seq, last_l0_clock_tick, wal_ids)
+    return [ReplayedTable(o, trs[t], trs[t + 1], meta[t]) for t in range(len(cuts) - 1)]
