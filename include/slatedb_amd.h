@@ -34,6 +34,9 @@
  *   - sdb_lsm_get_merge,       -> the same two reads under MergeOperatorIterator (merge_operator.rs:242-485,
  *     sdb_lsm_scan_merge         db_iter.rs:234-243): every key's operand chain located on the device, the
  *                                 user's operator run on the host over the links.
+ *   - sdb_lsm_get_mem          -> Reader::get_key_value_with_options from the active memtable down
+ *                                 (reader.rs:133-182): device memtables (sorted runs, as sdb_wal_replay_emit
+ *                                 leaves them) searched ahead of the tree, with or without operand chains.
  *   - sdb_sst_builder_*        -> host-side mirror of EncodedSsTableBuilder's add()/build()/
  *                                 next_block() call order (sst_builder.rs:224-276), batching
  *                                 entries into a columnar pinned buffer and encoding on the GPU.
@@ -522,7 +525,8 @@ sdb_status sdb_sst_scan(const sdb_sst_view *sst, const sdb_scan_ranges *ranges, 
  * Reader::get_key_value_with_options (reader.rs:203-260).  For a point range the reference builds a
  * GetIterator (db_iter.rs:48-138, 219-225); over the tree that is GetIterator::from_lsm_tree
  * (db_iter.rs:79-90): a flat, lazy chain of per-SST iterators, not a merge.  Memtables and the write
- * batch stay on the host and are consulted first.  Many keys are resolved by one call:
+ * batch stay on the host and are consulted first (memtables in device memory: sdb_lsm_get_mem).  Many keys are
+ * resolved by one call:
  *   1. chain: for query q the chain is the concatenation, over the runs in order (newest first), of that
  *      run's covering SSTs: the contiguous SSTs i of the run with first_key[i] <= key <= last_key[i], in
  *      run order.  Every L0 SST is a run of one and comes first, newest first (build_l0_point_iters,
@@ -1310,6 +1314,92 @@ sdb_status sdb_wal_replay_emit(const sdb_run *rows, const uint64_t *batch_start,
                                void *workspace /* as _sort left it */, uint64_t workspace_bytes, void *stream);
 /* Rows one tile-sort workgroup orders in LDS (the tests sit on its boundaries). */
 uint32_t sdb_diag_replay_tile(void);
+
+/* ---------------------------------------------------------------------------------------------
+ * Batched Db::get over device memtables and the tree (device): Reader::get_key_value_with_options
+ * (reader.rs:133-182, 203-260) from the active memtable down.  The reference's get is one flat, lazy chain
+ * (GetIterator::new, db_iter.rs:55-68, 102-124): the write batch, the active memtable, the immutable memtables
+ * front first, the tree; max_seq is applied per leaf (apply_filters, db_iter.rs:215).  sdb_lsm_get_mem is
+ * sdb_lsm_get_projected (itself the superset of the plain, _merge and _filtered gets) with memtables, sorted
+ * runs in the sdb_run layout such as sdb_wal_replay_emit leaves them, searched ahead of run 0.
+ *   M1. layers: a key's chain is tables 0 .. num_tables - 1 in order, then the tree chain of sdb_lsm_get rule 1
+ *       (P2 under projection).  Filters and projections concern SSTs only;
+ *   M2. one table: its rows are ordered key ascending, then seq descending (W3 of the replay,
+ *       mem_table.rs:38-44).  It yields the entries with key == query and seq <= max_seq[q], in table order
+ *       (KVTable::range(key..=key) under FilterIterator::new_with_max_seq).  The first of them is the lower
+ *       bound of (query, max_seq) in that order, if the row there has the query's key.  A version above the
+ *       bound is not seen, and an above-bound tombstone hides nothing.  Rows of other keys never match, also
+ *       when one key is a proper prefix of its neighbour.  NULL create_ts / expire_ts mean none anywhere, as
+ *       in sdb_run;
+ *   M3. decision without a chain: the first layer that yields an entry decides; state and status follow
+ *       sdb_lsm_get rule 3 (a merge operand: SDB_GET_MERGE_OPERAND / SDB_MERGE_OPERATOR_MISSING with its own
+ *       columns).  When a table decides, mout->table and mout->row name the entry, out->sst = 0xFFFFFFFF,
+ *       out->block = 0, val_off / val_len are the row's (tables[t].val_base[val_off .. + val_len); 0, 0 for a
+ *       tombstone and for an empty value, as everywhere), seq, flags and the timestamps are the row's, and
+ *       ssts_read = ssts_filtered = 0.  When the tree decides or nothing does, mout->table = 0xFFFFFFFF,
+ *       mout->row = 0 and every sdb_get_out column is what sdb_lsm_get_projected writes.  Expiry is not
+ *       filtered, as before;
+ *   M4. with a chain: rules 3'/4' of sdb_lsm_get_merge run across the layers.  The walk goes on inside a table
+ *       while rows are operands of the key, then into the next table, then into the tree.  A value ends the
+ *       chain as its base; a tombstone ends it with no base, is no link, and its timestamps are not folded
+ *       (db_iter.rs:108-114).  Links come newest first; a link lies either in a table (mchain->table / row;
+ *       chain->sst = 0xFFFFFFFF, chain->block = 0, the other link columns the row's) or in an SST (chain->sst /
+ *       block, mchain->table = 0xFFFFFFFF, mchain->row = 0).  The per-query columns are the newest link's with
+ *       the MergeTracker aggregates over all links of all layers.  A link whose seq exceeds the newest link's
+ *       fails the query with SDB_INVALID_SEQUENCE_ORDER, found per table as it is per run.  The cap_links
+ *       protocol is unchanged, and covers the mchain columns;
+ *   M5. laziness: a query that ends in the tables (without a chain: a table yields an entry; with a chain: a
+ *       value or tombstone in a table ends it) consults no SST: it marks no block and probes no filter, no SST
+ *       error surfaces for it, and ssts_read / ssts_filtered stay 0.  blocks_checked counts only blocks marked
+ *       for the other queries; a batch decided entirely in the tables reports 0.  For the other queries
+ *       everything is as in the projected call;
+ *   M6. no tables: mem == NULL or num_tables == 0 gives exactly sdb_lsm_get_projected, every column, summary
+ *       word and chain column; mout->table is all 0xFFFFFFFF and mout->row all 0 (the links' likewise);
+ *   M7. no tree: num_ssts == 0, num_runs == 0 or total_blocks == 0 with tables present still searches the
+ *       tables (a store that has only replayed its WAL has no SST); nothing is read through the tree's arrays.
+ *       nkeys == 0 is SDB_OK with zeroed summaries;
+ *   M8. arguments checked on the host: NULL lsm, out or mout, exactly one of chain and mchain, NULL
+ *       mem->tables with num_tables > 0, a NULL array that nkeys > 0 (or cap_links > 0) needs, and a short
+ *       workspace return SDB_INVALID_ARGUMENT from the call, besides what sdb_lsm_get_projected checks;
+ *       nkeys * (num_runs + num_tables) over 2^40: SDB_LIMIT_EXCEEDED; after those, SDB_DEVICE_ERROR when no
+ *       device is present;
+ *   M9. arguments checked on the device: a table with n > 0 and a NULL key_arena, key_off, val_off, val_len,
+ *       seq or flags, or with n >= 2^31, fails EVERY query with SDB_INVALID_ARGUMENT, and nothing is read
+ *       through the tables.  The rows' order and the offsets' monotonicity are the caller's obligation, as
+ *       sdb_compactor_run trusts its runs: a violation can lose entries but the search never leaves rows
+ *       [0, n) of a table;
+ *   M10. conventions: no allocation, no synchronisation, launches only on `stream`, capturable into a HIP graph
+ *       as a linear sequence, the workspace reusable without a host-side reset.
+ * sdb_lsm_get_mem_workspace_bytes(0, ...) equals sdb_lsm_get_projected_workspace_bytes(...).
+ * Out of scope: the write batch (its rows all carry seq u64::MAX and are exempt from max_seq; it is one
+ * transaction's private state and stays on the host, consulted first); scans over memtables (sdb_lsm_scan*
+ * still merges them on the host); the concurrent skiplist (a table here is a finished sorted run); segments.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct sdb_mem_view {
+    const sdb_run *tables;   /* DEVICE array of num_tables sorted runs in search order: the active memtable,
+                                then the immutable memtables front first (reader.rs:142-146) */
+    uint32_t num_tables;     /* host value */
+    uint32_t pad;
+} sdb_mem_view;
+typedef struct sdb_mem_get_out {     /* device arrays, one element per query */
+    uint32_t *table;                 /* memtable that decided the get (0xFFFFFFFF: none, see out->sst) */
+    uint64_t *row;                   /* row of the deciding entry in tables[table] (else 0) */
+} sdb_mem_get_out;
+typedef struct sdb_mem_chain_out {   /* device arrays, one element per link, cap = chain->cap_links */
+    uint32_t *table;                 /* 0xFFFFFFFF: the link lies in chain->sst / chain->block */
+    uint64_t *row;
+} sdb_mem_chain_out;
+uint64_t sdb_lsm_get_mem_workspace_bytes(uint32_t num_tables, uint64_t total_blocks, uint32_t num_ssts,
+                                         uint32_t num_runs, uint64_t nkeys, int32_t merge /* 1: a chain is passed */);
+sdb_status sdb_lsm_get_mem(const sdb_mem_view *mem /* or NULL */, const sdb_lsm_view *lsm,
+                           const sdb_scan_ranges *proj /* n == num_ssts; or NULL */,
+                           const sdb_filter_policy *policies /* device, num_ssts; or NULL */,
+                           const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
+                           const int32_t *probe_len /* device, nkeys; or NULL */,
+                           const uint64_t *max_seq /* device, nkeys; NULL = no bound */, const sdb_get_out *out,
+                           const sdb_mem_get_out *mout, const sdb_chain_out *chain /* or NULL */,
+                           const sdb_mem_chain_out *mchain /* iff chain */, void *workspace, uint64_t workspace_bytes,
+                           void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * SST footer (host): everything after the data section, so data ++ footer is the whole SST object

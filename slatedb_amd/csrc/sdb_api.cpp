@@ -634,14 +634,20 @@ static sdb_status check_projections(const sdb_lsm_view *lsm, const sdb_scan_rang
 }
 
 // sdb_lsm_get (merge == false), sdb_lsm_get_merge, sdb_lsm_get_filtered (either, with policies and probe_len) and
-// sdb_lsm_get_projected (that, with proj): one set of argument checks, in one order.
+// sdb_lsm_get_projected (that, with proj): one set of argument checks, in one order.  layers: sdb_lsm_get_mem, the
+// projected call with the memtables mem (or NULL), mout and, iff chain, mchain.
 static sdb_status lsm_get_call(const sdb_lsm_view *lsm, const sdb_scan_ranges *proj, const sdb_filter_policy *policies,
                                const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys, const int32_t *probe_len,
                                const uint64_t *max_seq, const sdb_get_out *out, bool merge, const sdb_chain_out *chain,
-                               void *workspace, uint64_t workspace_bytes, void *stream) {
+                               void *workspace, uint64_t workspace_bytes, void *stream, bool layers = false,
+                               const sdb_mem_view *mem = nullptr, const sdb_mem_get_out *mout = nullptr,
+                               const sdb_mem_chain_out *mchain = nullptr) {
     if (!lsm || !out || (merge && !chain)) return SDB_INVALID_ARGUMENT;
+    const uint32_t ntab = layers && mem ? mem->num_tables : 0;
+    if (layers && (!mout || (chain != nullptr) != (mchain != nullptr) || (ntab && !mem->tables))) return SDB_INVALID_ARGUMENT;
     // (the limits all give one status, so this one may come before the tree's)
-    if (lsm->num_runs && nkeys > (1ull << 40) / lsm->num_runs) return SDB_LIMIT_EXCEEDED;  // a byte per (query, run)
+    const uint64_t per_key = (uint64_t)lsm->num_runs + ntab;  // a byte per (query, run), a record per (query, table)
+    if (per_key && nkeys > (1ull << 40) / per_key) return SDB_LIMIT_EXCEEDED;
     sdb_status st = check_tree(lsm);
     if (st) return st;
     if (check_projections(lsm, proj)) return SDB_INVALID_ARGUMENT;
@@ -650,14 +656,19 @@ static sdb_status lsm_get_call(const sdb_lsm_view *lsm, const sdb_scan_ranges *p
                   !out->val_len || !out->seq || !out->flags || !out->create_ts || !out->expire_ts || !out->ssts_read ||
                   !out->ssts_filtered))
         return SDB_INVALID_ARGUMENT;
-    if (!workspace || workspace_bytes < get_workspace_bytes(lsm->total_blocks, lsm->num_ssts, lsm->num_runs, nkeys, merge) + 256)
+    if (layers && ((nkeys && (!mout->table || !mout->row)) || (merge && chain->cap_links && (!mchain->table || !mchain->row))))
+        return SDB_INVALID_ARGUMENT;
+    if (!workspace ||
+        workspace_bytes < get_mem_workspace_bytes(ntab, lsm->total_blocks, lsm->num_ssts, lsm->num_runs, nkeys, merge) + 256)
         return SDB_INVALID_ARGUMENT;
     if (!device_ok()) return SDB_DEVICE_ERROR;
     uint8_t *w = ws_align(workspace);
-    if (launch_get(*lsm, policies, key_bytes, key_off, nkeys, probe_len, max_seq, *out, merge ? chain : nullptr, proj, w,
-                   S(stream)) != hipSuccess)
-        return SDB_DEVICE_ERROR;
-    return SDB_OK;
+    const hipError_t e =
+        layers ? launch_get_mem(mem, *lsm, policies, key_bytes, key_off, nkeys, probe_len, max_seq, *out, *mout,
+                                merge ? chain : nullptr, mchain, proj, w, S(stream))
+               : launch_get(*lsm, policies, key_bytes, key_off, nkeys, probe_len, max_seq, *out, merge ? chain : nullptr, proj, w,
+                            S(stream));
+    return e != hipSuccess ? SDB_DEVICE_ERROR : SDB_OK;
 }
 
 sdb_status sdb_lsm_get(const sdb_lsm_view *lsm, const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
@@ -702,6 +713,20 @@ sdb_status sdb_lsm_get_projected(const sdb_lsm_view *lsm, const sdb_scan_ranges 
                                  uint64_t workspace_bytes, void *stream) {
     return lsm_get_call(lsm, proj, policies, key_bytes, key_off, nkeys, probe_len, max_seq, out, chain != nullptr, chain,
                         workspace, workspace_bytes, stream);
+}
+
+uint64_t sdb_lsm_get_mem_workspace_bytes(uint32_t num_tables, uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs,
+                                         uint64_t nkeys, int32_t merge) {
+    return get_mem_workspace_bytes(num_tables, total_blocks, num_ssts, num_runs, nkeys, merge != 0) + 256;
+}
+
+sdb_status sdb_lsm_get_mem(const sdb_mem_view *mem, const sdb_lsm_view *lsm, const sdb_scan_ranges *proj,
+                           const sdb_filter_policy *policies, const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
+                           const int32_t *probe_len, const uint64_t *max_seq, const sdb_get_out *out,
+                           const sdb_mem_get_out *mout, const sdb_chain_out *chain, const sdb_mem_chain_out *mchain,
+                           void *workspace, uint64_t workspace_bytes, void *stream) {
+    return lsm_get_call(lsm, proj, policies, key_bytes, key_off, nkeys, probe_len, max_seq, out, chain != nullptr, chain,
+                        workspace, workspace_bytes, stream, true, mem, mout, mchain);
 }
 
 uint64_t sdb_lsm_scan_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nranges,

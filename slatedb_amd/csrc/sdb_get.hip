@@ -41,6 +41,19 @@
 //   scan            the link counts -> chain_start
 //   k_gm_final      both summaries, do the links fit
 //   k_gm_emit       thread per pair the chain takes: the walk again, its links written at chain_start[q] + off
+// sdb_lsm_get_mem (launch_get_mem) puts device memtables, sorted runs in the sdb_run layout, in front of run 0: a
+// (query, table) pair is one more pair, whose record comes from a binary search over the table's columns.
+//   k_mem_reset     the queries' decided bytes cleared, and the blocks' marks and statuses in place of two memsets
+//   k_mem_validate  one workgroup: every table has its columns and fewer than 2^31 rows (else the call is malformed)
+//   k_mem_probe     thread per (query, table): the lower bound of (key, max_seq) in key ascending / seq descending
+//                   order -> the pair's RunRec (hit + row) or, with a chain, the count walk's MergeRec; a query that
+//                   the tables end sets its decided byte
+//   k_get_locate    its <P, V, true> instantiation skips the pairs of decided queries before it probes or marks
+//   k_get_resolve   its <MERGE, true> instantiation takes the tables' records ahead of run 0; a deciding table row's
+//                   columns come from the table's columns
+//   k_mem_links     after k_gm_final: every link starts as a tree link (table 0xFFFFFFFF, row 0)
+//   k_mem_emit      thread per (query, table) the chain takes: its links written at chain_start[q] + off
+// The calls without tables launch none of these and the instantiations they always launched.
 // One launcher (launch_get), one workspace layout (get_bind: the plain get's arrays are a prefix of the merging
 // get's) and one resolve body serve both; what differs between them is chosen at compile time.
 // sdb_lsm_get_filtered passes the SSTs' filter policies: the filter step of k_get_locate and of the walk asks
@@ -111,6 +124,14 @@ struct GetArgs {
     unsigned long long *macc;  // kMacc* words
     // sdb_lsm_get_projected only
     sdb_scan_ranges proj;      // per SST: SsTableView.visible_range, (UNBOUNDED, UNBOUNDED) = None
+    // sdb_lsm_get_mem only
+    const sdb_run *tabs;       // the memtables in search order
+    uint32_t ntab;
+    sdb_mem_get_out mout;
+    sdb_mem_chain_out mchain;
+    RunRec *trec;              // per (table, query) pair, at table * nkeys + query: sst = the table, at = the row
+    MergeRec *tmrec;           // the same with a chain
+    uint8_t *decided;          // per query: 1 = the tables end its chain, no SST is consulted (M5)
 };
 enum { kAccFound = 0, kAccDeleted, kAccNotFound, kAccMerge, kAccFailed, kAccBlocks, kAccFirstBad, kAccWords };
 
@@ -222,7 +243,8 @@ SDB_DEV Step get_step(const GetArgs &a, const sdb_sst_view &v, uint32_t i, uint6
     return s;
 }
 
-template <bool P, bool V>
+// M: the call has memtables (sdb_lsm_get_mem): the pairs of a query that the tables decided stay kRunNone.
+template <bool P, bool V, bool M = false>
 __global__ __launch_bounds__(256) void k_get_locate(GetArgs a) {
     if (*a.bad) return;
     const uint32_t R = a.t.num_runs;
@@ -230,6 +252,10 @@ __global__ __launch_bounds__(256) void k_get_locate(GetArgs a) {
     for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x) {
         const uint64_t q = t % a.nkeys;  // pair t = run * nkeys + query: a wave holds neighbouring queries of one run
         const uint32_t r = (uint32_t)(t / a.nkeys);
+        if (M && a.decided[q]) {
+            a.rstate[t] = kRunNone;
+            continue;
+        }
         const Key k = key_of(a, q);
         uint32_t first, last;
         uint8_t rs = kRunNone;
@@ -396,7 +422,28 @@ SDB_DEV auto pair_recs(const GetArgs &a) {
 // sdb_lsm_get_merge: the runs in order until one ends the chain or fails; the columns are the first entry's with the
 // links' aggregates, and every run the chain takes learns where its links go (off, use).  A compile-time choice: the
 // plain resolve keeps the registers of a kernel that knows nothing of chains.
+// The records of the (query, table) pairs as k_mem_probe left them.
 template <bool MERGE>
+SDB_DEV auto table_recs(const GetArgs &a) {
+    if constexpr (MERGE) return a.tmrec;
+    else return a.trec;
+}
+
+// Row i of a memtable as the walks see an SST row: vl, seq, flags and the timestamps; the value starts at vbase.
+SDB_DEV Row tab_row(const sdb_run &T, uint64_t i, uint64_t &vbase) {
+    Row r{};
+    const uint8_t no = (uint8_t)((T.create_ts ? 0 : SDB_FLAG_HAS_CREATE_TS) | (T.expire_ts ? 0 : SDB_FLAG_HAS_EXPIRE_TS));
+    r.flags = (uint8_t)(T.flags[i] & ~no);
+    r.seq = T.seq[i];
+    r.vl = T.val_len[i];
+    r.cts = T.create_ts ? T.create_ts[i] : 0;
+    r.ets = T.expire_ts ? T.expire_ts[i] : 0;
+    vbase = T.val_off[i];
+    return r;
+}
+
+// M: the call has memtables (sdb_lsm_get_mem): their records come first, in table order.
+template <bool MERGE, bool M = false>
 __global__ __launch_bounds__(64) void k_get_resolve(GetArgs a) {
     const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = q < a.nkeys;
@@ -410,15 +457,11 @@ __global__ __launch_bounds__(64) void k_get_resolve(GetArgs a) {
         uint64_t vbase = 0, links = 0, newest = 0;
         int64_t cts = 0, ets = 0;
         uint8_t has = 0, end = kEndOpen;
+        bool intab = false;  // M: the first entry lies in table `sst`, at row H.at
         if (*a.bad) {
             st = SDB_INVALID_ARGUMENT;
         } else {
-            const uint32_t R = a.t.num_runs;
-            for (uint32_t j = 0; j < R && !st && (MERGE ? !end : !H.ok); j++) {
-                const uint8_t rs = a.rstate[j * a.nkeys + q];
-                if (rs == kRunFiltered) nfilt++;
-                if (rs != kRunOpen && rs != kRunOpen1) continue;
-                auto &x = pair_recs<MERGE>(a)[j * a.nkeys + q];
+            auto take = [&](auto &x, bool table) {  // the next pair of the query's chain that has a record
                 nread += x.nread;
                 nfilt += x.nfilt;
                 if (x.hit && !H.ok) {  // (a record with an error holds no hit unless it is a chain's)
@@ -426,13 +469,14 @@ __global__ __launch_bounds__(64) void k_get_resolve(GetArgs a) {
                     H.block = x.block;
                     H.at = x.at;
                     sst = x.sst;
+                    intab = table;
                 }
                 if constexpr (MERGE) {
                     if (x.nlinks) {
                         if (!links) newest = x.seq0;
                         if (x.maxseq > newest) {  // MergeTracker::update (merge_operator.rs:293-299)
                             st = SDB_INVALID_SEQUENCE_ORDER;
-                            break;
+                            return;
                         }
                         if (x.has & SDB_FLAG_HAS_CREATE_TS) cts = (has & SDB_FLAG_HAS_CREATE_TS) && cts > x.cts ? cts : x.cts;
                         if (x.has & SDB_FLAG_HAS_EXPIRE_TS) ets = (has & SDB_FLAG_HAS_EXPIRE_TS) && ets < x.ets ? ets : x.ets;
@@ -444,8 +488,19 @@ __global__ __launch_bounds__(64) void k_get_resolve(GetArgs a) {
                     end = x.end;
                 }
                 st = x.st;
+            };
+            if constexpr (M)
+                for (uint32_t j = 0; j < a.ntab && !st && (MERGE ? !end : !H.ok); j++) take(table_recs<MERGE>(a)[j * a.nkeys + q], true);
+            const uint32_t R = a.t.num_runs;
+            for (uint32_t j = 0; j < R && !st && (MERGE ? !end : !H.ok); j++) {
+                const uint8_t rs = a.rstate[j * a.nkeys + q];
+                if (rs == kRunFiltered) nfilt++;
+                if (rs != kRunOpen && rs != kRunOpen1) continue;
+                take(pair_recs<MERGE>(a)[j * a.nkeys + q], false);
             }
-            if (H.ok && !st) {  // the first entry again, for its columns
+            if (M && intab) {
+                if (H.ok && !st) r = tab_row(a.tabs[sst], H.at, vbase);  // the first entry's columns are the table's
+            } else if (H.ok && !st) {  // the first entry again, for its columns
                 const sdb_sst_view v = a.t.ssts[sst];
                 Blk b;
                 if (!(st = blk_open(v, H.block, b))) st = v.sst_version == 2 ? v2_row(b, H.at, r) : v1_row(b, H.at, r);
@@ -456,6 +511,7 @@ __global__ __launch_bounds__(64) void k_get_resolve(GetArgs a) {
             H.ok = false;
             links = 0;
         }
+        intab = intab && H.ok;
         if (H.ok) {
             const bool operand = (r.flags & SDB_FLAG_MERGE_OPERAND) != 0;
             if (r.flags & SDB_FLAG_TOMBSTONE) {
@@ -477,9 +533,13 @@ __global__ __launch_bounds__(64) void k_get_resolve(GetArgs a) {
         }
         a.out.state[q] = (uint8_t)state;
         a.out.status[q] = st;
-        a.out.sst[q] = sst;
+        a.out.sst[q] = M && intab ? 0xFFFFFFFFu : sst;
         a.out.block[q] = H.ok ? H.block : 0;
         put_row(a.out, q, vbase, r);
+        if constexpr (M) {
+            a.mout.table[q] = intab ? sst : 0xFFFFFFFFu;
+            a.mout.row[q] = intab ? H.at : 0;
+        }
         a.out.ssts_read[q] = nread;
         a.out.ssts_filtered[q] = nfilt;
         if constexpr (MERGE) {
@@ -512,6 +572,31 @@ __global__ void k_get_final(GetArgs a) {
 // Its own kernels: the count walk before the resolve (k_get_resolve<true> above), the final and the emit after it.
 // =================================================================================================
 
+// The count walk's step: the next visible version r of the key, in chain order, into the pair's record -> false: it
+// ended the chain.
+SDB_DEV bool chain_count(MergeRec &m, const Row &r) {
+    if (r.flags & SDB_FLAG_TOMBSTONE) {  // ends the chain and is no link (GetIterator returns None, db_iter.rs:108-114)
+        m.end = kEndTombstone;
+        return false;
+    }
+    if (!m.nlinks) m.seq0 = r.seq;
+    if (m.nlinks != 0xFFFFFFFFu) m.nlinks++;
+    if (r.seq > m.maxseq) m.maxseq = r.seq;
+    if (r.flags & SDB_FLAG_HAS_CREATE_TS) {  // MergeTracker::update (merge_operator.rs:289-292)
+        m.cts = (m.has & SDB_FLAG_HAS_CREATE_TS) && m.cts > r.cts ? m.cts : r.cts;
+        m.has |= SDB_FLAG_HAS_CREATE_TS;
+    }
+    if (r.flags & SDB_FLAG_HAS_EXPIRE_TS) {
+        m.ets = (m.has & SDB_FLAG_HAS_EXPIRE_TS) && m.ets < r.ets ? m.ets : r.ets;
+        m.has |= SDB_FLAG_HAS_EXPIRE_TS;
+    }
+    if (!(r.flags & SDB_FLAG_MERGE_OPERAND)) {  // the base value: the last link
+        m.end = kEndValue;
+        return false;
+    }
+    return true;
+}
+
 template <bool P, bool V>
 __global__ __launch_bounds__(64) void k_gm_walk(GetArgs a) {
     if (blockIdx.x == 0 && threadIdx.x == 0) a.macc[kMaccMaxChain] = a.macc[kMaccGo] = 0;
@@ -529,26 +614,7 @@ __global__ __launch_bounds__(64) void k_gm_walk(GetArgs a) {
                 m.block = blk;
                 m.at = at;
             }
-            if (r.flags & SDB_FLAG_TOMBSTONE) {  // ends the chain and is no link (GetIterator returns None, db_iter.rs:108-114)
-                m.end = kEndTombstone;
-                return false;
-            }
-            if (!m.nlinks) m.seq0 = r.seq;
-            if (m.nlinks != 0xFFFFFFFFu) m.nlinks++;
-            if (r.seq > m.maxseq) m.maxseq = r.seq;
-            if (r.flags & SDB_FLAG_HAS_CREATE_TS) {  // MergeTracker::update (merge_operator.rs:289-292)
-                m.cts = (m.has & SDB_FLAG_HAS_CREATE_TS) && m.cts > r.cts ? m.cts : r.cts;
-                m.has |= SDB_FLAG_HAS_CREATE_TS;
-            }
-            if (r.flags & SDB_FLAG_HAS_EXPIRE_TS) {
-                m.ets = (m.has & SDB_FLAG_HAS_EXPIRE_TS) && m.ets < r.ets ? m.ets : r.ets;
-                m.has |= SDB_FLAG_HAS_EXPIRE_TS;
-            }
-            if (!(r.flags & SDB_FLAG_MERGE_OPERAND)) {  // the base value: the last link
-                m.end = kEndValue;
-                return false;
-            }
-            return true;
+            return chain_count(m, r);
         });
         m.st = (uint8_t)st;
         m.nread = (uint16_t)(nread > 0xFFFF ? 0xFFFF : nread);
@@ -594,8 +660,157 @@ __global__ __launch_bounds__(64) void k_gm_emit(GetArgs a) {
     }
 }
 
+// =================================================================================================
+// sdb_lsm_get_mem: device memtables in front of the tree (Reader::get_key_value_with_options, reader.rs:133-182: the
+// active memtable, then the immutable ones front first, then the tree).  A table is a sorted run: key ascending, seq
+// descending (mem_table.rs:38-44), so what it yields for (key, max_seq) starts at one lower bound.
+// =================================================================================================
+
+__global__ __launch_bounds__(256) void k_mem_validate(GetArgs a) {  // after k_get_validate: it may only add to *bad
+    int bad = 0;
+    for (uint32_t j = threadIdx.x; j < a.ntab; j += blockDim.x) {
+        const sdb_run T = a.tabs[j];
+        if (T.n >= (1ull << 31)) bad = 1;
+        if (T.n && (!T.key_arena || !T.key_off || !T.val_off || !T.val_len || !T.seq || !T.flags)) bad = 1;
+    }
+    bad = __syncthreads_or(bad);
+    if (threadIdx.x == 0) {
+        if (bad) *a.bad = 1u;
+        if (a.macc) a.macc[kMaccMaxChain] = a.macc[kMaccGo] = 0;  // k_gm_walk's reset, for a call without a tree
+    }
+}
+
+// Per query: no table has decided it yet, and it names no table (k_get_resolve<., true> writes the latter again; the
+// call without tables leaves it so).  Per tree block (mark != nullptr): not marked, not read, what launch_get's two
+// memsets do.  A kernel: under HIP graph replay the memset nodes in front of a captured call's kernels were seen
+// not to take effect (stale decided bytes, blocks_checked growing from replay to replay); kernels order like kernels.
+__global__ __launch_bounds__(256) void k_mem_reset(uint8_t *decided, sdb_mem_get_out mout, uint64_t n, uint8_t *mark,
+                                                   int32_t *bstat, uint64_t tb) {
+    const uint64_t t0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t q = t0; q < n; q += step) {
+        if (decided) decided[q] = 0;
+        mout.table[q] = 0xFFFFFFFFu;
+        mout.row[q] = 0;
+    }
+    for (uint64_t k = t0; mark && k < tb; k += step) {
+        mark[k] = 0;
+        bstat[k] = -1;
+    }
+}
+static hipError_t launch_mem_reset(uint8_t *decided, const sdb_mem_get_out &mout, uint64_t n, uint8_t *mark, int32_t *bstat,
+                                   uint64_t tb, hipStream_t st) {
+    const uint32_t g = (uint32_t)std::min<uint64_t>((std::max(n, mark ? tb : 0) + 255) / 256, 1024);
+    if (g) hipLaunchKernelGGL(k_mem_reset, dim3(g), dim3(256), 0, st, decided, mout, n, mark, bstat, tb);
+    return hipGetLastError();
+}
+
+SDB_DEV int tab_cmp(const sdb_run &T, uint64_t i, const Key &k) {  // sign(key of row i cmp k)
+    const uint64_t o = T.key_off[i];
+    return cmp_bytes(T.key_arena + o, (uint32_t)(T.key_off[i + 1] - o), k.t, k.nt, 0).c;
+}
+// The first row that does not precede (k, bound) in the table's order: key > k, or key == k and seq <= bound.
+SDB_DEV uint64_t tab_seek(const sdb_run &T, const Key &k, uint64_t bound) {
+    uint64_t lo = 0, hi = T.n;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        const int c = tab_cmp(T, mid, k);
+        if (c < 0 || (c == 0 && T.seq[mid] > bound)) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+// The rows from `from` on with key == k and seq <= bound, in table order (KVTable::range(key..=key) under
+// FilterIterator::new_with_max_seq): visit(row, value base, the row) -> false: stop.
+template <typename F>
+SDB_DEV void tab_versions(const sdb_run &T, const Key &k, uint64_t bound, uint64_t from, F &&visit) {
+    for (uint64_t i = from; i < T.n; i++) {
+        if (tab_cmp(T, i, k) != 0) return;
+        if (T.seq[i] > bound) continue;
+        uint64_t vbase;
+        const Row r = tab_row(T, i, vbase);
+        if (!visit(i, vbase, r)) return;
+    }
+}
+
+template <bool MERGE>
+__global__ __launch_bounds__(256) void k_mem_probe(GetArgs a) {
+    if (*a.bad) return;
+    const uint64_t total = a.nkeys * a.ntab;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t q = t % a.nkeys;  // pair t = table * nkeys + query: a wave holds neighbouring queries of one table
+        const uint32_t j = (uint32_t)(t / a.nkeys);
+        const sdb_run T = a.tabs[j];
+        const Key k = key_of(a, q);
+        const uint64_t bound = a.max_seq ? a.max_seq[q] : ~0ull;
+        const uint64_t from = T.n ? tab_seek(T, k, bound) : 0;
+        if constexpr (MERGE) {
+            MergeRec m{};
+            tab_versions(T, k, bound, from, [&](uint64_t i, uint64_t, const Row &r) {
+                if (!m.hit) {
+                    m.hit = 1;
+                    m.sst = j;
+                    m.at = (uint32_t)i;
+                }
+                return chain_count(m, r);
+            });
+            a.tmrec[t] = m;
+            if (m.end != kEndOpen) a.decided[q] = 1;
+        } else {
+            RunRec out{j, 0, 0, 0, 0, 0, 0, {0, 0}};
+            tab_versions(T, k, bound, from, [&](uint64_t i, uint64_t, const Row &) {
+                out.at = (uint32_t)i;  // the first visible version decides
+                out.hit = 1;
+                return false;
+            });
+            a.trec[t] = out;
+            if (out.hit) a.decided[q] = 1;
+        }
+    }
+}
+
+// Every link of a chain that fits starts as a tree link; k_mem_emit then names the tables' links.
+__global__ __launch_bounds__(256) void k_mem_links(sdb_chain_out chain, sdb_mem_chain_out mchain) {
+    const sdb_chain_summary s = *chain.summary;
+    if (s.status != SDB_OK) return;
+    const uint64_t n = s.num_links < chain.cap_links ? s.num_links : chain.cap_links;
+    for (uint64_t d = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; d < n; d += (uint64_t)gridDim.x * blockDim.x) {
+        mchain.table[d] = 0xFFFFFFFFu;
+        mchain.row[d] = 0;
+    }
+}
+
+static hipError_t launch_mem_links(const sdb_chain_out &chain, const sdb_mem_chain_out &mchain, hipStream_t st) {
+    const uint32_t g = (uint32_t)std::min<uint64_t>((chain.cap_links + 255) / 256, 1024);
+    if (g) hipLaunchKernelGGL(k_mem_links, dim3(g), dim3(256), 0, st, chain, mchain);
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(64) void k_mem_emit(GetArgs a) {
+    if (*a.bad || !a.macc[kMaccGo]) return;
+    const uint64_t total = a.nkeys * a.ntab;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t q = t % a.nkeys;
+        const uint32_t j = (uint32_t)(t / a.nkeys), n = a.tmrec[t].nlinks;
+        if (!a.tmrec[t].use || !n || a.out.status[q]) continue;
+        const uint64_t at0 = a.chain.chain_start[q] + a.tmrec[t].off;
+        uint32_t x = 0;
+        tab_versions(a.tabs[j], key_of(a, q), a.max_seq ? a.max_seq[q] : ~0ull, a.tmrec[t].at, [&](uint64_t i, uint64_t vbase, const Row &r) {
+            if (r.flags & SDB_FLAG_TOMBSTONE) return false;
+            const uint64_t d = at0 + x;
+            if (x >= n || d >= a.chain.cap_links) return false;  // never out of the pair's slots
+            a.chain.sst[d] = 0xFFFFFFFFu;
+            a.chain.block[d] = 0;
+            put_row(a.chain, d, vbase, r);
+            a.mchain.table[d] = j;
+            a.mchain.row[d] = i;
+            x++;
+            return (r.flags & SDB_FLAG_MERGE_OPERAND) != 0 && x < n;
+        });
+    }
+}
+
 // The workspace arrays of a get of a.nkeys keys over the tree a.t, bound into a from w; -> their size.  merge: those
-// of the plain get, then the merging get's own.
+// of the plain get, then the merging get's own; a.ntab > 0: then those of the (query, table) pairs.
 static uint64_t get_bind(GetArgs &a, uint8_t *w, bool merge) {
     const uint64_t tb = a.t.total_blocks, n = a.nkeys, pairs = n * a.t.num_runs;
     Carver c{w, 0};
@@ -607,59 +822,95 @@ static uint64_t get_bind(GetArgs &a, uint8_t *w, bool merge) {
     c.take(a.acc, kAccWords + 1);  // the accumulators, then bad and uni
     if (w) a.bad = (uint32_t *)(a.acc + kAccWords);
     if (w) a.uni = a.bad + 1;
-    if (!merge) return c.off;
-    c.take(a.mrec, pairs + 1);
-    c.take(a.qn, n + 1);
-    c.take(a.qscan, n + 2);
-    c.take(a.tx, (n + 1023) / 1024 + 2);
-    c.take(a.ty, (n + 1023) / 1024 + 2);
-    c.take(a.macc, kMaccWords);
+    if (merge) {
+        c.take(a.mrec, pairs + 1);
+        c.take(a.qn, n + 1);
+        c.take(a.qscan, n + 2);
+        c.take(a.tx, (n + 1023) / 1024 + 2);
+        c.take(a.ty, (n + 1023) / 1024 + 2);
+        c.take(a.macc, kMaccWords);
+    }
+    if (a.ntab) {
+        c.take(a.decided, n + 1);
+        if (merge) c.take(a.tmrec, n * a.ntab + 1);
+        else c.take(a.trec, n * a.ntab + 1);
+    }
     return c.off;
 }
 
-uint64_t get_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys, bool merge) {
+uint64_t get_mem_workspace_bytes(uint32_t num_tables, uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs,
+                                 uint64_t nkeys, bool merge) {
     GetArgs a{};
     a.t.total_blocks = total_blocks;
     a.t.num_ssts = num_ssts;
     a.t.num_runs = num_runs;
     a.nkeys = nkeys;
+    a.ntab = num_tables;
     return get_bind(a, nullptr, merge);
 }
 
+uint64_t get_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys, bool merge) {
+    return get_mem_workspace_bytes(0, total_blocks, num_ssts, num_runs, nkeys, merge);
+}
+
 // The kernels of a bound get in stream order.  P: the call has filter policies, V: it has projections, each chosen
-// once for the kernels that hold the step; merge: a.chain is given.
-template <bool P, bool V>
+// once for the kernels that hold the step; merge: a.chain is given.  M: the call has memtables: their pairs are
+// probed first, and a tree without SSTs, runs or blocks (a.t.num_runs == 0 then) launches none of its kernels.
+template <bool P, bool V, bool M = false>
 static hipError_t launch_get_kernels(const GetArgs &a, bool merge, hipStream_t st) {
     const uint64_t tb = a.t.total_blocks, n = a.nkeys, pairs = n * a.t.num_runs;
+    const bool tree = !M || pairs != 0;
     // the kernels stride past these caps; the per-block parse and the per-pair walks are latency-bound threads: one
     // wave per workgroup spreads them over the CUs
     const dim3 lg((uint32_t)std::min<uint64_t>((pairs + 255) / 256, 1u << 20));
     const dim3 wg((uint32_t)std::min<uint64_t>((pairs + 63) / 64, 1u << 22)), qg((uint32_t)((n + 63) / 64));
     hipError_t e;
+    const uint64_t tpairs = n * a.ntab;
+    const dim3 tg((uint32_t)std::min<uint64_t>((tpairs + 255) / 256, 1u << 20));
     hipLaunchKernelGGL(k_get_validate<V>, dim3(1), dim3(256), 0, st, a);
-    hipLaunchKernelGGL((k_get_locate<P, V>), lg, dim3(256), 0, st, a);
-    if ((e = launch_check(CheckArgs{{}, a.t, a.bad, tb, a.mark, a.bstat}, st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_get_rows, dim3((uint32_t)((tb + 63) / 64)), dim3(64), 0, st, a);
+    if constexpr (M) {
+        hipLaunchKernelGGL(k_mem_validate, dim3(1), dim3(256), 0, st, a);
+        if (merge) hipLaunchKernelGGL(k_mem_probe<true>, tg, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(k_mem_probe<false>, tg, dim3(256), 0, st, a);
+    }
+    if (tree) {
+        hipLaunchKernelGGL((k_get_locate<P, V, M>), lg, dim3(256), 0, st, a);
+        if ((e = launch_check(CheckArgs{{}, a.t, a.bad, tb, a.mark, a.bstat}, st)) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_get_rows, dim3((uint32_t)((tb + 63) / 64)), dim3(64), 0, st, a);
+    }
     if (!merge) {
-        hipLaunchKernelGGL((k_get_walk<P, V>), wg, dim3(64), 0, st, a);
-        hipLaunchKernelGGL(k_get_resolve<false>, qg, dim3(64), 0, st, a);
+        if (tree) hipLaunchKernelGGL((k_get_walk<P, V>), wg, dim3(64), 0, st, a);
+        hipLaunchKernelGGL((k_get_resolve<false, M>), qg, dim3(64), 0, st, a);
         hipLaunchKernelGGL(k_get_final, dim3(1), dim3(64), 0, st, a);
     } else {
-        hipLaunchKernelGGL((k_gm_walk<P, V>), wg, dim3(64), 0, st, a);
-        hipLaunchKernelGGL(k_get_resolve<true>, qg, dim3(64), 0, st, a);
+        if (tree) hipLaunchKernelGGL((k_gm_walk<P, V>), wg, dim3(64), 0, st, a);
+        hipLaunchKernelGGL((k_get_resolve<true, M>), qg, dim3(64), 0, st, a);
         if ((e = launch_excl_scan2(a.qn, a.qn, n, a.tx, a.ty, a.chain.chain_start, a.qscan, st)) != hipSuccess) return e;
         hipLaunchKernelGGL(k_gm_final, dim3(1), dim3(64), 0, st, a);
-        hipLaunchKernelGGL((k_gm_emit<P, V>), wg, dim3(64), 0, st, a);
+        if (tree) hipLaunchKernelGGL((k_gm_emit<P, V>), wg, dim3(64), 0, st, a);
+        if constexpr (M) {
+            if ((e = launch_mem_links(a.chain, a.mchain, st)) != hipSuccess) return e;
+            hipLaunchKernelGGL(k_mem_emit, dim3((uint32_t)std::min<uint64_t>((tpairs + 63) / 64, 1u << 22)), dim3(64), 0, st, a);
+        }
     }
     return hipGetLastError();
 }
 
-hipError_t launch_get(const sdb_lsm_view &t, const sdb_filter_policy *pol, const uint8_t *key_bytes, const uint64_t *key_off,
-                      uint64_t nkeys, const int32_t *probe_len, const uint64_t *max_seq, const sdb_get_out &out,
-                      const sdb_chain_out *chain /* sdb_lsm_get_merge, else nullptr */,
-                      const sdb_scan_ranges *proj /* sdb_lsm_get_projected, else nullptr */, uint8_t *w, hipStream_t st) {
+template <bool M>
+static hipError_t launch_get_bound(const GetArgs &a, bool filters, bool projected, bool merge, hipStream_t st) {
+    if (projected) return filters ? launch_get_kernels<true, true, M>(a, merge, st) : launch_get_kernels<false, true, M>(a, merge, st);
+    return filters ? launch_get_kernels<true, false, M>(a, merge, st) : launch_get_kernels<false, false, M>(a, merge, st);
+}
+
+// mem (with mout, and mchain iff chain): sdb_lsm_get_mem's tables, at least one; else nullptr
+static hipError_t launch_get_layers(const sdb_mem_view *mem, const sdb_lsm_view &t, const sdb_filter_policy *pol,
+                                    const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys, const int32_t *probe_len,
+                                    const uint64_t *max_seq, const sdb_get_out &out, const sdb_mem_get_out *mout,
+                                    const sdb_chain_out *chain, const sdb_mem_chain_out *mchain, const sdb_scan_ranges *proj,
+                                    uint8_t *w, hipStream_t st) {
     const uint64_t tb = t.total_blocks, n = nkeys;
-    const bool none = n == 0 || t.num_ssts == 0 || t.num_runs == 0 || tb == 0;  // nothing to search
+    const bool no_tree = t.num_ssts == 0 || t.num_runs == 0 || tb == 0;
+    const bool none = n == 0 || (no_tree && !mem);  // nothing to search
     hipError_t e;
     if (none && chain) {  // no links
         if ((e = hipMemsetAsync(chain->summary, 0, sizeof(sdb_chain_summary), st)) != hipSuccess) return e;
@@ -688,15 +939,48 @@ hipError_t launch_get(const sdb_lsm_view &t, const sdb_filter_policy *pol, const
     a.pol = pol;
     a.probe_len = probe_len;
     if (chain) a.chain = *chain;
-    get_bind(a, w, chain != nullptr);
-    if ((e = hipMemsetAsync(a.mark, 0, tb, st)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(a.bstat, 0xFF, 4 * tb, st)) != hipSuccess) return e;
-    const bool merge = chain != nullptr;
-    if (proj) {
-        a.proj = *proj;
-        return pol || probe_len ? launch_get_kernels<true, true>(a, merge, st) : launch_get_kernels<false, true>(a, merge, st);
+    if (mem) {
+        a.tabs = mem->tables;
+        a.ntab = mem->num_tables;
+        a.mout = *mout;
+        if (chain) a.mchain = *mchain;
     }
-    return pol || probe_len ? launch_get_kernels<true, false>(a, merge, st) : launch_get_kernels<false, false>(a, merge, st);
+    const bool merge = chain != nullptr;
+    get_bind(a, w, merge);
+    if (no_tree) {  // (M7) only the tables are searched, and nothing is read through the tree's arrays
+        a.t.num_ssts = a.t.num_runs = 0;
+        a.t.total_blocks = 0;
+        a.pol = nullptr;
+        proj = nullptr;
+    } else if (!mem) {
+        if ((e = hipMemsetAsync(a.mark, 0, tb, st)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(a.bstat, 0xFF, 4 * tb, st)) != hipSuccess) return e;
+    }
+    if (proj) a.proj = *proj;
+    if (!mem) return launch_get_bound<false>(a, pol || probe_len, proj != nullptr, merge, st);
+    if ((e = launch_mem_reset(a.decided, a.mout, n, no_tree ? nullptr : a.mark, a.bstat, tb, st)) != hipSuccess) return e;
+    return launch_get_bound<true>(a, pol || probe_len, proj != nullptr, merge, st);
+}
+
+hipError_t launch_get(const sdb_lsm_view &t, const sdb_filter_policy *pol, const uint8_t *key_bytes, const uint64_t *key_off,
+                      uint64_t nkeys, const int32_t *probe_len, const uint64_t *max_seq, const sdb_get_out &out,
+                      const sdb_chain_out *chain /* sdb_lsm_get_merge, else nullptr */,
+                      const sdb_scan_ranges *proj /* sdb_lsm_get_projected, else nullptr */, uint8_t *w, hipStream_t st) {
+    return launch_get_layers(nullptr, t, pol, key_bytes, key_off, nkeys, probe_len, max_seq, out, nullptr, chain, nullptr, proj, w,
+                             st);
+}
+
+hipError_t launch_get_mem(const sdb_mem_view *mem, const sdb_lsm_view &t, const sdb_filter_policy *pol, const uint8_t *key_bytes,
+                          const uint64_t *key_off, uint64_t nkeys, const int32_t *probe_len, const uint64_t *max_seq,
+                          const sdb_get_out &out, const sdb_mem_get_out &mout, const sdb_chain_out *chain,
+                          const sdb_mem_chain_out *mchain, const sdb_scan_ranges *proj, uint8_t *w, hipStream_t st) {
+    if (mem && mem->num_tables && nkeys)
+        return launch_get_layers(mem, t, pol, key_bytes, key_off, nkeys, probe_len, max_seq, out, &mout, chain, mchain, proj, w, st);
+    // (M6) no tables: the projected call, and no query or link names a table
+    hipError_t e = launch_get(t, pol, key_bytes, key_off, nkeys, probe_len, max_seq, out, chain, proj, w, st);
+    if (e != hipSuccess) return e;
+    if ((e = launch_mem_reset(nullptr, mout, nkeys, nullptr, nullptr, 0, st)) != hipSuccess) return e;
+    return chain ? launch_mem_links(*chain, *mchain, st) : hipSuccess;
 }
 
 }  // namespace sdb

@@ -25,6 +25,15 @@ hipError_t launch_get(const sdb_lsm_view &t, const sdb_filter_policy *pol, const
                       uint64_t nkeys, const int32_t *probe_len, const uint64_t *max_seq, const sdb_get_out &out,
                       const sdb_chain_out *chain, const sdb_scan_ranges *proj, uint8_t *w, hipStream_t st);
 
+// sdb_lsm_get_mem: launch_get with the memtables `mem` (NULL or num_tables == 0: none) searched ahead of the tree;
+// mchain iff chain.  num_tables == 0 sizes exactly get_workspace_bytes.
+uint64_t get_mem_workspace_bytes(uint32_t num_tables, uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs,
+                                 uint64_t nkeys, bool merge);
+hipError_t launch_get_mem(const sdb_mem_view *mem, const sdb_lsm_view &t, const sdb_filter_policy *pol, const uint8_t *key_bytes,
+                          const uint64_t *key_off, uint64_t nkeys, const int32_t *probe_len, const uint64_t *max_seq,
+                          const sdb_get_out &out, const sdb_mem_get_out &mout, const sdb_chain_out *chain,
+                          const sdb_mem_chain_out *mchain, const sdb_scan_ranges *proj, uint8_t *w, hipStream_t st);
+
 // chain != NULL: the merging scan; fout != NULL: the filtered one, with pol and px; proj != NULL (with fout): the
 // projected one
 uint64_t lsm_scan_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint64_t nranges, uint64_t cand_entries,

@@ -56,3 +56,24 @@ def fold_chains(keys, res, sst_data, operator):
                 base = v
         out.append(fold(key, vals, base, operator))
     return out
+
+
+def fold_chains_mem(keys, res, table_vals, sst_data, operator):
+    """fold_chains for a read over memtables and the tree (lsm_get_mem_device): a link whose chain_table is not
+    0xFFFFFFFF reads its bytes from that table's value arena, table_vals[table] (uint8 array or bytes: sdb_run.val_base),
+    at chain_val_off; any other link from sst_data[chain_sst], as in fold_chains."""
+    cs = np.asarray(res["chain_start"]).astype(np.int64)
+    out = []
+    for i, key in enumerate(keys):
+        vals, base = [], None
+        for l in range(int(cs[i]), int(cs[i + 1])):
+            vo, vl = int(res["chain_val_off"][l]), int(res["chain_val_len"][l])
+            t = int(res["chain_table"][l]) & 0xFFFFFFFF
+            src = table_vals[t] if t != 0xFFFFFFFF else sst_data[int(res["chain_sst"][l])]
+            v = bytes(src[vo:vo + vl])
+            if int(res["chain_flags"][l]) & _abi.FLAG_MERGE_OPERAND:
+                vals.append(v)
+            else:
+                base = v
+        out.append(fold(key, vals, base, operator))
+    return out

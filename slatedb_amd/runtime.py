@@ -872,13 +872,15 @@ def _projections(projections, tree):
 
 
 def _lsm_get(entry, views, runs, keys, max_seq, stream, workspace, merge=False, cap_links=None, fill=0, filtered=False,
-             probe_len=None, projected=False, projections=None):
+             probe_len=None, projected=False, projections=None, mem=None):
     """The tree gets.  entry: the C entry point (sdb_lsm_get, sdb_lsm_get_merge, sdb_lsm_get_filtered or
     sdb_lsm_get_projected; its sizer is entry + "_workspace_bytes"); filtered: it takes the policies, probe_len and an
     optional chain; projected: it is a filtered call that takes the projections too; merge: the
     call has a chain.  Marshals the tree, the keys, the bounds and probe_len as device tensors, the result dict with
     the GET_FIELDS and the summary; a caller's workspace must hold the call; with merge and cap_links None the links
-    are sized at nkeys first and, when they did not fit, at the reported num_links in a second call."""
+    are sized at nkeys first and, when they did not fit, at the reported num_links in a second call.  mem: the entry
+    is sdb_lsm_get_mem: None (a NULL sdb_mem_view) or what mem_tables_device returned; the result then has table and
+    row (MEM_FIELDS) and, with a chain, chain_table and chain_row."""
     import torch
     tree = views if isinstance(views, dict) else lsm_tree_device(views, runs)
     dev = tree["device"]
@@ -894,7 +896,13 @@ def _lsm_get(entry, views, runs, keys, max_seq, stream, workspace, merge=False, 
     res = {f: torch.zeros(max(n, 1), dtype=getattr(torch, dt), device=dev) for f, dt in GET_FIELDS}
     res["summary"] = torch.zeros(len(GET_SUMMARY), dtype=torch.int64, device=dev)
     out = _abi.GetOut(*[res[f].data_ptr() for f, _ in GET_FIELDS], res["summary"].data_ptr())
-    wsb = getattr(lib(), entry + "_workspace_bytes")(tree["total_blocks"], tree["num_ssts"], tree["num_runs"], n,
+    layers = entry == "sdb_lsm_get_mem"
+    if layers:
+        for f, dt in MEM_FIELDS:  # (every call writes all n of them: no fill)
+            res[f] = torch.empty(max(n, 1), dtype=getattr(torch, dt), device=dev)
+        mout = _abi.MemGetOut(*[res[f].data_ptr() for f, _ in MEM_FIELDS])
+    wsb = getattr(lib(), entry + "_workspace_bytes")(*([mem["num_tables"] if mem else 0] if layers else []),
+                                                     tree["total_blocks"], tree["num_ssts"], tree["num_runs"], n,
                                                      *([int(bool(merge))] if filtered else []))
     ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=dev)
     assert ws.numel() >= wsb, "workspace too small"
@@ -902,10 +910,14 @@ def _lsm_get(entry, views, runs, keys, max_seq, stream, workspace, merge=False, 
 
     def run(cap):
         chain = _chain_out(res, n, cap, dev, fill) if merge else None
-        args = [C.byref(tree["lsm"])] + ([C.byref(pj) if pj is not None else None] if projected else [])
+        args = [C.byref(mem["mem"]) if mem else None] if layers else []
+        args += [C.byref(tree["lsm"])] + ([C.byref(pj) if pj is not None else None] if projected else [])
         args += ([_ptr(tree.get("_policies"))] if filtered else [])
         args += [kb.data_ptr(), ko.data_ptr(), n] + ([_ptr(probe_len)] if filtered else [])
-        args += [_ptr(max_seq), C.byref(out)] + ([C.byref(chain) if merge else None] if merge or filtered else [])
+        args += [_ptr(max_seq), C.byref(out)] + ([C.byref(mout)] if layers else [])
+        args += ([C.byref(chain) if merge else None] if merge or filtered else [])
+        if layers:
+            args += [C.byref(_mem_chain_out(res, cap, dev, fill)) if merge else None]
         st = getattr(lib(), entry)(*args, ws.data_ptr(), wsb, _sp(stream))
         if st:
             raise SdbError(st, entry)
@@ -917,7 +929,7 @@ def _lsm_get(entry, views, runs, keys, max_seq, stream, workspace, merge=False, 
             run(int(res["chain_summary"][0].item()))
     else:
         run(cap_links or 0)
-    res.update(_ws=ws, _tree=tree, _keys=(kb, ko), _max_seq=max_seq, _probe_len=probe_len, _projections=pjt)
+    res.update(_ws=ws, _tree=tree, _keys=(kb, ko), _max_seq=max_seq, _probe_len=probe_len, _projections=pjt, _mem=mem)
     return res
 
 
@@ -1126,6 +1138,45 @@ def lsm_get_projected_device(views, runs, projections, keys, probe_len=None, max
     return _lsm_get("sdb_lsm_get_projected", views, runs, keys, max_seq, stream, workspace, merge=bool(merge),
                     cap_links=cap_links, fill=fill, filtered=True, probe_len=probe_len, projected=True,
                     projections=projections)
+
+
+MEM_FIELDS = (("table", "int32"), ("row", "int64"))
+
+
+def _mem_chain_out(res, cap_links, dev, fill=0):
+    """The sdb_mem_chain_out beside _chain_out's link columns: chain_table and chain_row."""
+    import torch
+    for f, dt in MEM_FIELDS:
+        dtype = getattr(torch, dt)
+        res["chain_" + f] = torch.full((max(cap_links, 1) * dtype.itemsize,), fill, dtype=torch.uint8, device=dev).view(dtype)
+    return _abi.MemChainOut(*[res["chain_" + f].data_ptr() for f, _ in MEM_FIELDS])
+
+
+def mem_tables_device(runs, device="cuda"):
+    """The device-resident sdb_mem_view of memtables in search order (the active one, then the immutable ones front
+    first).  runs: DeviceRuns, for example ReplayedTable.as_run(), or _abi.Run structs whose pointers the caller
+    keeps alive.  Returns a dict: "mem" (the _abi.MemView), num_tables and, under "_"-prefixed keys, what it points
+    into."""
+    arr = (_abi.Run * max(len(runs), 1))()
+    for i, r in enumerate(runs):
+        arr[i] = r.to_ctypes() if hasattr(r, "to_ctypes") else r
+    if runs and hasattr(runs[0], "t"):
+        device = runs[0].t[0].device
+    tabs = _to_dev(np.frombuffer(bytes(arr), np.uint8).copy(), device)
+    return {"mem": _abi.MemView(tabs.data_ptr(), len(runs), 0), "num_tables": len(runs), "_tables": tabs, "_runs": runs}
+
+
+def lsm_get_mem_device(tables, views, runs, keys, max_seq=None, projections=None, probe_len=None, cap_links=None,
+                       merge=False, stream=None, workspace=None, fill=0):
+    """sdb_lsm_get_mem: lsm_get_projected_device with device memtables searched ahead of the tree.  tables: None
+    (a NULL sdb_mem_view), a list of DeviceRuns in search order, or what mem_tables_device returned; views, runs: as
+    lsm_tree_device (a tree without SSTs is searched too: the tables alone).  The other arguments, the retry on links
+    that do not fit and the result are lsm_get_projected_device's, plus table and row per query (table -1: the
+    tree decided, or nothing) and, with merge, chain_table and chain_row per link."""
+    mem = tables if tables is None or isinstance(tables, dict) else mem_tables_device(tables)
+    return _lsm_get("sdb_lsm_get_mem", views, runs, keys, max_seq, stream, workspace, merge=bool(merge),
+                    cap_links=cap_links, fill=fill, filtered=True, probe_len=probe_len, projected=True,
+                    projections=projections, mem=mem)
 
 
 # ------------------------------------------------------------------------------------------------
