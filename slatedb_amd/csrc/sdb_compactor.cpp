@@ -1,26 +1,33 @@
 // sdb_compactor.cpp — host orchestration of one compaction job on the device (sdb_compactor_*):
 // CompactionExecutor::run_subcompaction_merge (compactor_executor.rs:327-390 load_iterators, 818-871
-// the output side) as
-//   sdb_compactor_run:       merge + retention (sized, then emitted) -> SST cuts -> sdb_encode_ssts over
-//                            the cut ranges; three host synchronisations (merged sizes, cuts, summaries);
-//   sdb_compactor_run_ssts:  decode of every input SST's blocks (one launch sequence) -> gate -> merge +
-//                            retention + emit into buffers sized by the inputs' SstStats -> SST cuts over the
-//                            merged stream padded to the input count -> sdb_encode_ssts; two host
-//                            synchronisations (merged count + cuts together, summaries).
-//   sdb_compactor_run_merge / sdb_compactor_run_ssts_merge: the same jobs with the user's merge operator
-//                            between the merged order and retention (chain_step): the device finds the operand
-//                            chains and gathers their bytes, the host folds each chain through the operator,
-//                            and retention, cuts and encode run over the collapsed stream; two more host
-//                            synchronisations (the chain summary; the chain tables, only when there is a chain).
-//   sdb_compactor_run_ssts_ranged: run_ssts[_merge] over one job range and a visible range per input: the covering
-//                            blocks of every input (k_rx_cover), their decode, the rows inside the view ranges
-//                            (k_rx_clip, k_rx_gate; closed up by k_rx_compact when a row was dropped), then the same
-//                            merge, cuts and encode (merge_encode); two more host synchronisations (the covering
-//                            block ranges, which size the decode; the per-run row ranges, which size the merge).
-// Both job families share begin_job, order_step (the merged order; with an operator chain_step), the cut readback
-// (CutRead) and encode_outputs; a.ch, bound by chain_step, selects the unit forms of retention and emit.
-// The outputs stay in the handle's device memory; every SST of the job is encoded by one launch sequence
-// per 8 SSTs.  The handle's buffers (DevBuf, PinBuf) and every layout inside them come from sdb_host.h.
+// the output side).  A job is a Job descriptor (the handle and the arguments every entry point takes) passed through
+// stages, each of which exists once; [S] marks a host synchronisation:
+//   begin_job        the handle's last results reset, the common arguments checked                        every job
+//   check_run_shape  the inputs' SST version, the run count, run_start                                    ssts, ranged
+//   TableUpload      the per-input and per-run tables: pinned, one copy to the device, tab_ev recorded    ssts, ranged
+//                    on every return behind the copy
+//   decode_inputs    the block list of the inputs (launch_cx_blocks) and its fail-fast decode             ssts, ranged
+//   merge_front      group_runs beyond SDB_MAX_RUNS runs [S per group], the merge workspace and           every job
+//                    arguments, the gate, the merged order; with an operator chain_step instead of the
+//                    order: the chains [S], their tables when there is a chain [S], the host's fold, the
+//                    upload (up_ev); a.ch, bound by it, selects the unit forms of retention and emit
+//   cut_step         the cut walk over a stream (padded or not), the cuts' byte offsets, their readback,  every job
+//                    with the merged summary in front when asked for [S]
+//   encode_outputs   sdb_encode_ssts over the cut ranges, one launch sequence per 8 SSTs, summaries [S]   every job
+// The three job functions are those stages plus what is their own:
+//   run_job (sdb_compactor_run, _run_merge): merge_front, then retention sized with unbounded capacities [S: the
+//       sizes] and the emit into buffers of those sizes; cut_step over the stream as it is, encode_outputs.  3 [S].
+//   run_ssts_job (sdb_compactor_run_ssts, _run_ssts_merge): check_run_shape, TableUpload, decode_inputs, its gate
+//       (launch_cx_gate: the decode against the declared counts, read by the merge on the device), merge_encode.  2 [S].
+//   run_ranged_job (sdb_compactor_run_ssts_ranged): check_run_shape, TableUpload, the covering blocks of every
+//       input's view range (k_rx_cover) [S: they size the decode], decode_inputs, the rows inside the ranges and the
+//       gate (k_rx_clip, k_rx_gate) [S: the per-run row ranges size the merge], the rows closed up when a range
+//       dropped any (k_rx_compact), merge_encode.  4 [S].
+//   merge_encode (both jobs over encoded inputs): merge_front, retention + emit into buffers of the declared sizes,
+//       the stream padded to the declared count, cut_step over the padded stream with the summary, encode_outputs.
+// An operator adds chain_step's two [S] to any of them (the second only when there is a chain).
+// The outputs stay in the handle's device memory.  The handle's buffers (DevBuf, PinBuf) and every layout inside them
+// come from sdb_host.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -121,6 +128,27 @@ struct sdb_compactor {
 
 namespace {
 
+// One job: the handle and the arguments every entry point takes, as every stage takes them.
+struct Job {
+    sdb_compactor *c;
+    const sdb_retention *ret;
+    sdb_merge_batch_fn op;  // NULL: a job without a merge operator
+    void *ctx;
+    const sdb_sst_params *params;
+    uint64_t max_sst_size;
+    void *stream;  // as the public calls take it
+    uint32_t *num_ssts;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+};
+
+// An sdb_run of n entries over columns, from their entry e0 on (the arenas are not offset: *_off index them).
+sdb_run run_over(uint64_t e0, uint64_t n, const uint8_t *key_arena, const uint64_t *key_off, const uint8_t *val_base,
+                 const uint64_t *val_off, const uint32_t *val_len, const uint64_t *seq, const uint8_t *flags,
+                 const int64_t *create_ts, const int64_t *expire_ts) {
+    return sdb_run{n, key_arena, key_off + e0, val_base, val_off + e0, val_len + e0, seq + e0, flags + e0, create_ts + e0,
+                   expire_ts + e0};
+}
+
 // Sizes (base == NULL) or binds the merged-stream columns of `total` entries.
 uint64_t merged_bind(sdb_merged_out &o, uint64_t total, uint8_t *base) {
     Carver c{base, 0};
@@ -150,27 +178,18 @@ struct CutLayout {
     uint64_t num, cut, off;
 };
 CutLayout cut_layout(Carver &c, uint64_t n) { return {c.bytes(8), c.bytes(8 * (n + 2)), c.bytes(16 * (n + 2))}; }
-// The device cut list of a stream of n entries (in c->cuts) and the cut walk's workspace (c->cut_ws).
-bool cut_buffers(sdb_compactor *c, uint64_t n, const sdb_sst_params *params, uint64_t **num, uint64_t **cut,
-                 uint64_t **off) {
-    Carver k{nullptr, 0};
-    const CutLayout l = cut_layout(k, n);
-    if (!c->cut_ws.ensure(sdb_sst_cuts_workspace_bytes(n, params)) || !c->cuts.ensure(k.off)) return false;
-    *num = c->cuts.at<uint64_t>(l.num);
-    *cut = c->cuts.at<uint64_t>(l.cut);
-    *off = c->cuts.at<uint64_t>(l.off);
-    return true;
-}
 
 // A job with more runs than one merge takes (SDB_MAX_RUNS): groups of SDB_MAX_RUNS consecutive runs are
 // merged first without retention (every entry kept as it is, in the group's MergeIterator order: key asc,
 // seq desc, run), and the group streams become the job's runs.  Groups are consecutive runs, so equal keys
 // with equal seqs keep their run order and the job's merged stream is the one a single merge of every run
 // would give (merge_iterator.rs:55-69).  One host synchronisation per group (its byte sizes).  A run out
-// of order fails the job like the single merge: *fail = the group merge's summary, first_error_entry
+// of order fails the job like the single merge: c->msum = the group merge's summary, first_error_entry
 // rebased to the job's entry numbering.  gate: the decode gate of sdb_compactor_run_ssts (or NULL).
-sdb_status group_runs(sdb_compactor *c, const sdb_run *runs, uint32_t nruns, const unsigned long long *gate,
-                      std::vector<sdb_run> &grouped, sdb_merge_summary *fail, hipStream_t s) {
+sdb_status group_runs(const Job &j, const sdb_run *runs, uint32_t nruns, const unsigned long long *gate,
+                      std::vector<sdb_run> &grouped) {
+    sdb_compactor *c = j.c;
+    hipStream_t s = j.s;
     const uint32_t ng = (nruns + kMaxRuns - 1) / kMaxRuns;
     if (ng > kMaxRuns) return SDB_LIMIT_EXCEEDED;
     uint64_t job_total = 0;
@@ -198,11 +217,11 @@ sdb_status group_runs(sdb_compactor *c, const sdb_run *runs, uint32_t nruns, con
             hipStreamSynchronize(s) != hipSuccess)
             return SDB_DEVICE_ERROR;
         if (sm.status) {
-            *fail = sm;
-            fail->num_in = job_total;
+            c->msum = sm;
+            c->msum.num_in = job_total;
             // the group's entry numbering starts at `base` in the job's (a gate error can only come from
             // group 0, whose base is 0)
-            if (sm.status == SDB_INVALID_ARGUMENT && sm.first_error_entry != ~0ull) fail->first_error_entry += base;
+            if (sm.status == SDB_INVALID_ARGUMENT && sm.first_error_entry != ~0ull) c->msum.first_error_entry += base;
             return (sdb_status)sm.status;
         }
         Carver rc{nullptr, 0};  // what a run has and a merged stream lacks: value lengths, then row flags
@@ -217,18 +236,8 @@ sdb_status group_runs(sdb_compactor *c, const sdb_run *runs, uint32_t nruns, con
         uint8_t *flags = B.asrun.at<uint8_t>(o_flags);
         if (launch_merge_emit(a, s) != hipSuccess || launch_merged_as_run(a.out, total, vlen, flags, s) != hipSuccess)
             return SDB_DEVICE_ERROR;
-        sdb_run R{};
-        R.n = total;
-        R.key_arena = a.out.key_bytes;
-        R.key_off = a.out.key_off;
-        R.val_base = a.out.val_bytes;
-        R.val_off = a.out.val_off;
-        R.val_len = vlen;
-        R.seq = a.out.seq;
-        R.flags = flags;
-        R.create_ts = a.out.create_ts;
-        R.expire_ts = a.out.expire_ts;
-        grouped.push_back(R);
+        grouped.push_back(run_over(0, total, a.out.key_bytes, a.out.key_off, a.out.val_bytes, a.out.val_off, vlen, a.out.seq,
+                                   flags, a.out.create_ts, a.out.expire_ts));
         base += total;
     }
     return SDB_OK;
@@ -282,7 +291,9 @@ bool fold_chain(sdb_merge_batch_fn op, void *ctx, const uint8_t *key, uint64_t k
 // arena to pinned memory (one synchronisation), the fold of every chain through `op`, and the merged values
 // and their offsets back to the device (a.ch.moff / mval; asynchronous, from pin_up).  Leaves the job's chain
 // counts in c->mstats.  An operator failure: SDB_MERGE_OPERATOR_ERROR, with c->msum filled.
-sdb_status chain_step(sdb_compactor *c, MergeArgs &a, sdb_merge_batch_fn op, void *ctx, hipStream_t s) {
+sdb_status chain_step(const Job &j, MergeArgs &a) {
+    sdb_compactor *c = j.c;
+    hipStream_t s = j.s;
     if (!c->chain_ws.ensure(chain_bind(a.ch, a.total, nullptr), c->canaries)) return SDB_DEVICE_ERROR;
     chain_bind(a.ch, a.total, c->chain_ws.base());
     ChainSummary cs{};
@@ -329,7 +340,7 @@ sdb_status chain_step(sdb_compactor *c, MergeArgs &a, sdb_merge_batch_fn op, voi
             base_len = L.len;
         }
         moff[g] = merged.size();
-        if (!fold_chain(op, ctx, h.arena + G.key_off, G.key_len, vals, lens, base, base_len, merged, &ms.operator_calls)) {
+        if (!fold_chain(j.op, j.ctx, h.arena + G.key_off, G.key_len, vals, lens, base, base_len, merged, &ms.operator_calls)) {
             c->msum = sdb_merge_summary{};
             c->msum.num_in = a.total;
             c->msum.status = SDB_MERGE_OPERATOR_ERROR;
@@ -375,23 +386,38 @@ sdb_kv_batch batch_of(const sdb_merged_out &o, uint64_t n) {
 }
 
 // The prologue of every job: the handle's results of the last job reset, the arguments every job takes checked.
-sdb_status begin_job(sdb_compactor *c, const sdb_retention *ret, const sdb_sst_params *params, uint32_t *num_ssts) {
-    if (!c || !params || !num_ssts) return SDB_INVALID_ARGUMENT;
-    *num_ssts = 0;
+sdb_status begin_job(const Job &j) {
+    sdb_compactor *c = j.c;
+    if (!c || !j.params || !j.num_ssts) return SDB_INVALID_ARGUMENT;
+    *j.num_ssts = 0;
     c->ssts.clear();
     c->merged = sdb_kv_batch{};
     c->msum = sdb_merge_summary{};
     c->mstats = sdb_merge_op_stats{};
     c->rstats = sdb_range_job_stats{};
-    if (params->sst_type != SDB_SST_COMPACTED || !ret) return SDB_INVALID_ARGUMENT;  // compactions write compacted SSTs
+    if (j.params->sst_type != SDB_SST_COMPACTED || !j.ret) return SDB_INVALID_ARGUMENT;  // compactions write compacted SSTs
     return SDB_OK;
 }
 
-// The merged order of a job; with an operator the chains, the fold and the upload behind it (chain_step), which
-// bind a.ch, so the retention and emit launches that follow run over the units.
-sdb_status order_step(sdb_compactor *c, MergeArgs &a, sdb_merge_batch_fn op, void *ctx, hipStream_t s) {
-    if (op) return chain_step(c, a, op, ctx, s);
-    return launch_merge_order(a, s) == hipSuccess ? SDB_OK : SDB_DEVICE_ERROR;
+// The front of every merge: `runs` grouped when one merge does not take them all (group_runs), the merge workspace
+// and arguments over `out` (a copies the runs), the decode gate (or NULL), and the merged order; with an operator the
+// chains, the fold and the upload behind it (chain_step), which bind a.ch, so the retention and emit launches that
+// follow run over the units.
+sdb_status merge_front(const Job &j, const sdb_run *runs, uint32_t nruns, const unsigned long long *gate,
+                       const sdb_merged_out &out, MergeArgs &a) {
+    sdb_compactor *c = j.c;
+    sdb_status st;
+    std::vector<sdb_run> grouped;
+    if (nruns > kMaxRuns) {
+        if ((st = group_runs(j, runs, nruns, gate, grouped))) return st;
+        runs = grouped.data();
+        nruns = (uint32_t)grouped.size();
+    }
+    if (!c->merge_ws.ensure(sdb_merge_runs_workspace_bytes(runs, nruns))) return SDB_DEVICE_ERROR;
+    if ((st = build_merge_args(runs, nruns, j.ret, &out, c->merge_ws.p, c->merge_ws.cap, &a))) return st;
+    a.gate = gate;
+    if (j.op) return chain_step(j, a);
+    return launch_merge_order(a, j.s) == hipSuccess ? SDB_OK : SDB_DEVICE_ERROR;
 }
 
 // The readback of a job's cuts through c->pin, around the job's synchronisation.  Every SST but the last holds
@@ -403,24 +429,39 @@ struct CutRead {
     const sdb_merge_summary *sum;     // pinned: the merged summary (NULL: not asked for)
     const uint64_t *num, *cut, *off;  // pinned: the count, g + 1 cuts, their offsets
 };
-// Enqueues the copies: the merged summary d_sum (unless NULL), then (n > 0) the count and the first g + 1 cuts
-// and offsets of the device cut list.
-bool cut_read_begin(sdb_compactor *c, CutRead &r, uint64_t n, uint64_t bytes, uint64_t max_sst_size,
-                    const sdb_merge_summary *d_sum, const uint64_t *d_num, const uint64_t *d_cut, const uint64_t *d_off,
-                    hipStream_t s) {
-    const uint64_t g = max_sst_size ? std::min<uint64_t>(n, 2 + (bytes + 64 * n) / max_sst_size) : n;
+// The cut step of every job, over the stream m of m.n entries whose true length is *n_real on the device (NULL: m.n,
+// a stream that is not padded) and whose keys and values are at most `bytes` bytes: the cut list in c->cuts (the cut
+// walk, then the byte offsets of every cut, which size the SSTs), its readback into c->pin as r describes it, with
+// the merged summary d_sum in front (unless NULL), and the job's synchronisation.  Nothing is walked when m.n == 0.
+sdb_status cut_step(const Job &j, const sdb_kv_batch &m, const uint64_t *n_real, uint64_t bytes,
+                    const sdb_merge_summary *d_sum, CutRead &r) {
+    sdb_compactor *c = j.c;
+    const uint64_t n = m.n;
+    Carver dc{nullptr, 0};
+    const CutLayout dl = cut_layout(dc, n);
+    if (!c->cut_ws.ensure(sdb_sst_cuts_workspace_bytes(n, j.params)) || !c->cuts.ensure(dc.off)) return SDB_DEVICE_ERROR;
+    uint64_t *d_num = c->cuts.at<uint64_t>(dl.num), *d_cut = c->cuts.at<uint64_t>(dl.cut), *d_off = c->cuts.at<uint64_t>(dl.off);
+    if (n) {
+        const sdb_status st = sst_cuts_padded(&m, j.params, j.max_sst_size, d_cut, n + 1, d_num, c->cut_ws.p, c->cut_ws.cap,
+                                              j.s, n_real);
+        if (st) return st;
+        if (launch_cut_offsets(d_cut, d_num, m.key_off, m.val_off, d_off, j.s) != hipSuccess) return SDB_DEVICE_ERROR;
+    }
+    const uint64_t g = j.max_sst_size ? std::min<uint64_t>(n, 2 + (bytes + 64 * n) / j.max_sst_size) : n;
     Carver hc{nullptr, 0};
     const uint64_t h_sum = hc.bytes(sizeof(sdb_merge_summary));
     const CutLayout hl = cut_layout(hc, g);
-    if (!c->pin.ensure(hc.off)) return false;
+    if (!c->pin.ensure(hc.off)) return SDB_DEVICE_ERROR;
     sdb_merge_summary *hsum = c->pin.at<sdb_merge_summary>(h_sum);
     uint64_t *hnum = c->pin.at<uint64_t>(hl.num), *hcut = c->pin.at<uint64_t>(hl.cut), *hoff = c->pin.at<uint64_t>(hl.off);
     *hnum = 0;
     r = CutRead{g, d_cut, d_off, d_sum ? hsum : nullptr, hnum, hcut, hoff};
-    return (!d_sum || hipMemcpyAsync(hsum, d_sum, sizeof(sdb_merge_summary), hipMemcpyDeviceToHost, s) == hipSuccess) &&
-           (!n || (hipMemcpyAsync(hnum, d_num, 8, hipMemcpyDeviceToHost, s) == hipSuccess &&
-                   hipMemcpyAsync(hcut, d_cut, 8 * (g + 1), hipMemcpyDeviceToHost, s) == hipSuccess &&
-                   hipMemcpyAsync(hoff, d_off, 16 * (g + 1), hipMemcpyDeviceToHost, s) == hipSuccess));
+    const bool queued =
+        (!d_sum || hipMemcpyAsync(hsum, d_sum, sizeof(sdb_merge_summary), hipMemcpyDeviceToHost, j.s) == hipSuccess) &&
+        (!n || (hipMemcpyAsync(hnum, d_num, 8, hipMemcpyDeviceToHost, j.s) == hipSuccess &&
+                hipMemcpyAsync(hcut, d_cut, 8 * (g + 1), hipMemcpyDeviceToHost, j.s) == hipSuccess &&
+                hipMemcpyAsync(hoff, d_off, 16 * (g + 1), hipMemcpyDeviceToHost, j.s) == hipSuccess));
+    return queued && hipStreamSynchronize(j.s) == hipSuccess ? SDB_OK : SDB_DEVICE_ERROR;
 }
 // After the synchronisation: the SST count of a merged stream of n > 0 entries, its cuts and their offsets (taken
 // out of c->pin, which encode_outputs reuses).
@@ -441,12 +482,13 @@ sdb_status cut_read_end(const CutRead &r, uint64_t n, uint64_t *num, std::vector
     return SDB_OK;
 }
 
-// step 3 of both jobs, after the synchronisation of the cut readback: encode every output SST (sets of up to 8
+// The last step of every job, after the synchronisation of cut_step: encode every output SST (sets of up to 8
 // per launch sequence) over the cut ranges of c->merged (n > 0 entries), then read the summaries back (one
 // synchronisation)
-sdb_status encode_outputs(sdb_compactor *c, const CutRead &rd, uint64_t n, const sdb_sst_params *params, void *stream,
-                          uint32_t *num_ssts) {
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+sdb_status encode_outputs(const Job &j, const CutRead &rd, uint64_t n) {
+    sdb_compactor *c = j.c;
+    const sdb_sst_params *params = j.params;
+    hipStream_t s = j.s;
     const sdb_kv_batch &m = c->merged;
     uint64_t ns = 0;
     std::vector<uint64_t> cut, off;
@@ -491,7 +533,7 @@ sdb_status encode_outputs(sdb_compactor *c, const CutRead &rd, uint64_t n, const
     bind(c->sst_data.at<uint8_t>(0), c->sst_bloom.at<uint8_t>(0), c->sst_meta.at<uint8_t>(0));
     const uint64_t ews = sdb_encode_ssts_workspace_bytes((uint32_t)ns, batches.data(), params);
     if (!c->enc_ws.ensure(ews)) return SDB_DEVICE_ERROR;
-    st = sdb_encode_ssts((uint32_t)ns, batches.data(), params, outs.data(), c->enc_ws.p, c->enc_ws.cap, stream);
+    st = sdb_encode_ssts((uint32_t)ns, batches.data(), params, outs.data(), c->enc_ws.p, c->enc_ws.cap, j.stream);
     if (st) return st;
     if (!c->pin.ensure(ns * sizeof(sdb_sst_summary))) return SDB_DEVICE_ERROR;
     sdb_sst_summary *sums = static_cast<sdb_sst_summary *>(c->pin.p);
@@ -513,7 +555,7 @@ sdb_status encode_outputs(sdb_compactor *c, const CutRead &rd, uint64_t n, const
         v.summary = sums[i];
         if (!first && sums[i].status) first = (sdb_status)sums[i].status;
     }
-    *num_ssts = (uint32_t)ns;
+    *j.num_ssts = (uint32_t)ns;
     return first;
 }
 
@@ -535,35 +577,23 @@ void sdb_compactor_destroy(sdb_compactor *c) { delete c; }
 
 namespace {
 
-// sdb_compactor_run (op == NULL) / sdb_compactor_run_merge
-sdb_status run_job(sdb_compactor *c, const sdb_run *runs, uint32_t nruns, const sdb_retention *ret,
-                   sdb_merge_batch_fn op, void *ctx, const sdb_sst_params *params, uint64_t max_sst_size,
-                   void *stream, uint32_t *num_ssts) {
-    sdb_status st = begin_job(c, ret, params, num_ssts);
+// sdb_compactor_run (j.op == NULL) / sdb_compactor_run_merge
+sdb_status run_job(const Job &j, const sdb_run *runs, uint32_t nruns) {
+    sdb_status st = begin_job(j);
     if (st) return st;
     if (nruns && !runs) return SDB_INVALID_ARGUMENT;  // before group_runs reads runs[]
+    sdb_compactor *c = j.c;
     if (hipSetDevice(c->device) != hipSuccess) return SDB_DEVICE_ERROR;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t s = j.s;
     uint64_t total = 0;
-    for (uint32_t r = 0; r < nruns && runs; r++) total += runs[r].n;
-    std::vector<sdb_run> grouped;
-    if (nruns > kMaxRuns) {  // more runs than one merge takes: groups merged ahead (group_runs)
-        const sdb_status gs = group_runs(c, runs, nruns, nullptr, grouped, &c->msum, s);
-        if (gs) return gs;
-        runs = grouped.data();
-        nruns = (uint32_t)grouped.size();
-    }
+    for (uint32_t r = 0; r < nruns; r++) total += runs[r].n;
 
-    // 1. merge + retention, sized with unbounded byte capacities, then emitted
+    // merge + retention, sized with unbounded byte capacities (synchronisation 1: the sizes), then emitted
     sdb_merged_out out{};
     st = merged_columns_in(c->cols, total, &out);
     if (st) return st;
-    const uint64_t mws = sdb_merge_runs_workspace_bytes(runs, nruns);
-    if (!c->merge_ws.ensure(mws)) return SDB_DEVICE_ERROR;
     MergeArgs a;
-    st = build_merge_args(runs, nruns, ret, &out, c->merge_ws.p, c->merge_ws.cap, &a);
-    if (st) return st;
-    st = order_step(c, a, op, ctx, s);
+    st = merge_front(j, runs, nruns, nullptr, out, a);
     if (st) return st;
     if (launch_merge_retention(a, false, s) != hipSuccess ||
         hipMemcpyAsync(&c->msum, out.summary, sizeof(sdb_merge_summary), hipMemcpyDeviceToHost, s) != hipSuccess ||
@@ -581,20 +611,11 @@ sdb_status run_job(sdb_compactor *c, const sdb_run *runs, uint32_t nruns, const 
     m = batch_of(a.out, n);
     if (!n) return hipStreamSynchronize(s) == hipSuccess ? SDB_OK : SDB_DEVICE_ERROR;
 
-    // 2. cuts (and the byte offsets of every cut, to size the SSTs)
-    uint64_t *d_num, *d_cut, *d_off;
-    if (!cut_buffers(c, n, params, &d_num, &d_cut, &d_off)) return SDB_DEVICE_ERROR;
-    st = sdb_sst_cuts(&m, params, max_sst_size, d_cut, n + 1, d_num, c->cut_ws.p, c->cut_ws.cap, stream);
-    if (st) return st;
-    // the cut count, the cuts and their byte offsets in one synchronisation
+    // the cuts of the stream as it is (synchronisation 2), the output SSTs (synchronisation 3)
     CutRead rd;
-    if (launch_cut_offsets(d_cut, d_num, m.key_off, m.val_off, d_off, s) != hipSuccess ||
-        !cut_read_begin(c, rd, n, c->msum.key_bytes + c->msum.val_bytes, max_sst_size, nullptr, d_num, d_cut, d_off, s) ||
-        hipStreamSynchronize(s) != hipSuccess)
-        return SDB_DEVICE_ERROR;
-
-    // 3. encode every output SST
-    return encode_outputs(c, rd, n, params, stream, num_ssts);
+    st = cut_step(j, m, nullptr, c->msum.key_bytes + c->msum.val_bytes, nullptr, rd);
+    if (st) return st;
+    return encode_outputs(j, rd, n);
 }
 
 // The decode of a job's input blocks: its block list, the decoded columns and the gate word, in c->dec.
@@ -602,85 +623,81 @@ struct DecodeBufs {
     uint64_t *bstart, *bend;
     unsigned long long *gate;
     sdb_decoded_out out;
+    const unsigned long long *err;  // the decode's error word, in c->dec_ws (set by decode_inputs)
 };
+// Takes the columns of E decoded entries and K key bytes: what a run over them reads (runs_over).
+void take_columns(Carver &k, sdb_decoded_out &o, uint64_t K, uint64_t E) {
+    o.key_arena_cap = K;
+    o.cap_entries = E;
+    k.take(o.key_arena, K + 64);
+    k.take(o.key_off, E + 1);
+    k.take(o.val_off, E + 1);
+    k.take(o.val_len, E + 1);
+    k.take(o.seq, E + 1);
+    k.take(o.flags, E + 1);
+    k.take(o.create_ts, E + 1);
+    k.take(o.expire_ts, E + 1);
+}
 // Sizes (base == NULL) or binds them for B blocks of at most E entries and K key bytes.
 uint64_t decode_bufs_bind(DecodeBufs &b, uint64_t B, uint64_t K, uint64_t E, uint8_t *base) {
     sdb_decoded_out &dout = b.out;
     dout = sdb_decoded_out{};
-    dout.key_arena_cap = K;
-    dout.cap_entries = E;
     dout.bad_cap = 16;
     Carver k{base, 0};
     k.take(b.bstart, B + 1);
     k.take(b.bend, B + 1);
     k.take(dout.block_entry_start, B + 2);
-    k.take(dout.key_arena, K + 64);
-    k.take(dout.key_off, E + 1);
-    k.take(dout.val_off, E + 1);
-    k.take(dout.val_len, E + 1);
-    k.take(dout.seq, E + 1);
-    k.take(dout.flags, E + 1);
-    k.take(dout.create_ts, E + 1);
-    k.take(dout.expire_ts, E + 1);
+    take_columns(k, dout, K, E);
     k.take(dout.bad_block, dout.bad_cap);
     k.take(dout.summary, 1);
     k.take(b.gate, 1);
     return k.off;
 }
 
+// The decode step of the jobs over encoded inputs: the blocks `in` lists (launch_cx_blocks), decoded into one columnar
+// output of at most E entries and K key bytes in c->dec (run r = its entries [run_entry[r], run_entry[r + 1])).
+// Fail-fast (a failing block fails the job anyway, as load_iterators' reads would): checksums in the emit pass.  The
+// job's gate kernel follows.
+sdb_status decode_inputs(const Job &j, const CxInputs &in, uint64_t K, uint64_t E, uint16_t version, DecodeBufs &db) {
+    sdb_compactor *c = j.c;
+    const uint64_t B = in.nblocks;
+    if (!c->dec.ensure(decode_bufs_bind(db, B, K, E, nullptr)) || !c->dec_ws.ensure(sdb_decode_workspace_bytes(B)))
+        return SDB_DEVICE_ERROR;
+    decode_bufs_bind(db, B, K, E, c->dec.at<uint8_t>(0));
+    db.err = decode_err_word(c->dec_ws.p, B);
+    if (launch_cx_blocks(in, db.bstart, db.bend, j.s) != hipSuccess) return SDB_DEVICE_ERROR;
+    return sdb_decode_blocks_ex(reinterpret_cast<const uint8_t *>(in.base), db.bstart, db.bend, B, version,
+                                SDB_DECODE_FAIL_FAST, &db.out, c->dec_ws.p, c->dec_ws.cap, j.stream);
+}
+
 // The runs of a job over decoded columns: run r = entries [run_entry[r], run_entry[r + 1]), values in `arena`.
 std::vector<sdb_run> runs_over(const sdb_decoded_out &dout, const uint8_t *arena, const uint64_t *run_entry, uint32_t nruns) {
     std::vector<sdb_run> runs(nruns);
-    for (uint32_t r = 0; r < nruns; r++) {
-        const uint64_t e0 = run_entry[r];
-        sdb_run &R = runs[r];
-        R.n = run_entry[r + 1] - e0;
-        R.key_arena = dout.key_arena;
-        R.key_off = dout.key_off + e0;
-        R.val_base = arena;
-        R.val_off = dout.val_off + e0;
-        R.val_len = dout.val_len + e0;
-        R.seq = dout.seq + e0;
-        R.flags = dout.flags + e0;
-        R.create_ts = dout.create_ts + e0;
-        R.expire_ts = dout.expire_ts + e0;
-    }
+    for (uint32_t r = 0; r < nruns; r++)
+        runs[r] = run_over(run_entry[r], run_entry[r + 1] - run_entry[r], dout.key_arena, dout.key_off, arena, dout.val_off,
+                           dout.val_len, dout.seq, dout.flags, dout.create_ts, dout.expire_ts);
     return runs;
 }
 
-// Steps 2 and 3 of the jobs over encoded inputs, behind the decode: `runs` of E entries, K key bytes and at most V
-// value bytes; gate: the decode's gate word on the device (NULL: the host has already read it).
-sdb_status merge_encode(sdb_compactor *c, const std::vector<sdb_run> &runs, uint64_t E, uint64_t K, uint64_t V,
-                        const unsigned long long *gate, const sdb_retention *ret, sdb_merge_batch_fn op, void *ctx,
-                        const sdb_sst_params *params, uint64_t max_sst_size, void *stream, uint32_t *num_ssts) {
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const uint32_t nruns = (uint32_t)runs.size();
-    sdb_status st;
-    // 2. merge + retention + emit into buffers of the declared sizes (retention only drops entries and
-    //    values), gated on the decode; the stream padded to E entries for the cut walk
+// What follows the decode in the jobs over encoded inputs: `runs` of E entries, K key bytes and at most V value
+// bytes; gate: the decode's gate word on the device (NULL: the host has already read it).
+sdb_status merge_encode(const Job &j, const std::vector<sdb_run> &runs, uint64_t E, uint64_t K, uint64_t V,
+                        const unsigned long long *gate) {
+    sdb_compactor *c = j.c;
+    hipStream_t s = j.s;
+    const bool op = j.op != nullptr;
+    // merge + retention + emit into buffers of the declared sizes (retention only drops entries and values), gated
+    // on the decode; the stream padded to E entries for the cut walk
     sdb_merged_out out{};
-    st = merged_columns_in(c->cols, E, &out);
+    sdb_status st = merged_columns_in(c->cols, E, &out);
     if (st) return st;
     if (!c->keys.ensure(K + 16) || (!op && !c->vals.ensure(V + 16))) return SDB_DEVICE_ERROR;
     out.key_bytes = c->keys.at<uint8_t>(0);
     out.key_cap = K;
     out.val_bytes = op ? nullptr : c->vals.at<uint8_t>(0);  // (with an operator: sized after the fold)
     out.val_cap = V;
-    const sdb_run *mruns = runs.data();
-    uint32_t mn = nruns;
-    std::vector<sdb_run> grouped;
-    if (nruns > kMaxRuns) {  // more runs than one merge takes: groups merged ahead (group_runs)
-        const sdb_status gs = group_runs(c, mruns, nruns, gate, grouped, &c->msum, s);
-        if (gs) return gs;
-        mruns = grouped.data();
-        mn = (uint32_t)grouped.size();
-    }
-    if (!c->merge_ws.ensure(sdb_merge_runs_workspace_bytes(mruns, mn))) return SDB_DEVICE_ERROR;
     MergeArgs a;
-    st = build_merge_args(mruns, mn, ret, &out, c->merge_ws.p, c->merge_ws.cap, &a);
-    if (st) return st;
-    a.gate = gate;
-    st = order_step(c, a, op, ctx, s);
+    st = merge_front(j, runs.data(), (uint32_t)runs.size(), gate, out, a);
     if (st) return st;
     if (op) {
         // a merged value can be longer than all of its inputs: the links' bytes leave, the merged bytes come
@@ -691,67 +708,90 @@ sdb_status merge_encode(sdb_compactor *c, const std::vector<sdb_run> &runs, uint
     }
     if (launch_merge_retention(a, true, s) != hipSuccess || launch_merge_pad(out, E, s) != hipSuccess)
         return SDB_DEVICE_ERROR;
-    const sdb_kv_batch padded = batch_of(out, E);
-
-    // cuts over the padded stream, ending at the merged count; merged summary, cut count, cuts and their
-    // byte offsets read back in one synchronisation
-    uint64_t *d_num, *d_cut, *d_off;
-    if (!cut_buffers(c, E, params, &d_num, &d_cut, &d_off)) return SDB_DEVICE_ERROR;
-    if (E) {
-        st = sst_cuts_padded(&padded, params, max_sst_size, d_cut, E + 1, d_num, c->cut_ws.p, c->cut_ws.cap, s,
-                             &out.summary->num_out);
-        if (st) return st;
-        if (launch_cut_offsets(d_cut, d_num, out.key_off, out.val_off, d_off, s) != hipSuccess) return SDB_DEVICE_ERROR;
-    }
+    // cuts over the padded stream, ending at the merged count; the merged summary rides along (one synchronisation)
     CutRead rd;
-    if (!cut_read_begin(c, rd, E, K + V, max_sst_size, out.summary, d_num, d_cut, d_off, s) ||
-        hipStreamSynchronize(s) != hipSuccess)
-        return SDB_DEVICE_ERROR;
+    st = cut_step(j, batch_of(out, E), &out.summary->num_out, K + V, out.summary, rd);
+    if (st) return st;
     c->msum = *rd.sum;
     if (c->msum.status) return (sdb_status)c->msum.status;
     const uint64_t n = c->msum.num_out;
     c->merged = batch_of(out, n);
     if (!n) return SDB_OK;
-
-    // 3. encode every output SST
-    return encode_outputs(c, rd, n, params, stream, num_ssts);
+    return encode_outputs(j, rd, n);  // (one synchronisation)
 }
 
-// sdb_compactor_run_ssts (op == NULL) / sdb_compactor_run_ssts_merge
-sdb_status run_ssts_job(sdb_compactor *c, const sdb_compaction_input *inputs, uint32_t ninputs,
-                        const uint32_t *run_start, uint32_t nruns, uint16_t input_sst_version,
-                        const sdb_retention *ret, sdb_merge_batch_fn op, void *ctx, const sdb_sst_params *params,
-                        uint64_t max_sst_size, void *stream, uint32_t *num_ssts) {
-    sdb_status st = begin_job(c, ret, params, num_ssts);
-    if (st) return st;
-    if (ninputs && !inputs) return SDB_INVALID_ARGUMENT;
+// What the jobs over encoded inputs check of their run shape, in this order: the inputs' SST version, the run count
+// (*nruns = ninputs without run_start: every input a run of its own) against the two merge levels, run_start.
+sdb_status check_run_shape(uint16_t input_sst_version, const uint32_t *run_start, uint32_t *nruns, uint32_t ninputs) {
     if (input_sst_version != 1 && input_sst_version != 2) return SDB_INVALID_VERSION;
-    if (!run_start) nruns = ninputs;
-    if ((uint64_t)nruns > (uint64_t)kMaxRuns * kMaxRuns) return SDB_LIMIT_EXCEEDED;  // two merge levels
+    if (!run_start) *nruns = ninputs;
+    if ((uint64_t)*nruns > (uint64_t)kMaxRuns * kMaxRuns) return SDB_LIMIT_EXCEEDED;
     if (run_start) {
-        if (run_start[0] != 0 || run_start[nruns] != ninputs) return SDB_INVALID_ARGUMENT;
-        for (uint32_t r = 0; r < nruns; r++)
+        if (run_start[0] != 0 || run_start[*nruns] != ninputs) return SDB_INVALID_ARGUMENT;
+        for (uint32_t r = 0; r < *nruns; r++)
             if (run_start[r + 1] < run_start[r]) return SDB_INVALID_ARGUMENT;
     }
-    if (hipSetDevice(c->device) != hipSuccess) return SDB_DEVICE_ERROR;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    return SDB_OK;
+}
 
-    // the inputs' blocks, in input order, as offsets from the lowest data address; the per-input and per-run
-    // tables go to device memory (any number of inputs)
+// The per-input and per-run tables a job over encoded inputs hands its kernels (any number of inputs).  The job lists
+// them once, in `tables(t)`, as t.take(host, dev, count): begin() runs the list to size them and again to bind every
+// table's host pointer (in c->pin_tab, which the job then fills) and device pointer (the same offset of c->cx_tab,
+// which the kernels read); send() uploads them in one copy.
+struct TableUpload {
+    sdb_compactor *c;
+    hipStream_t s;
+    Carver h{nullptr, 0}, d{nullptr, 0};
+    bool sent = false;
+    template <typename T>
+    void take(T *&host, const T *&dev, uint64_t count) {
+        h.take(host, count);
+        d.take(dev, count);
+    }
+    template <typename F>
+    bool begin(F tables) {
+        tables(*this);
+        // the previous job's upload and kernels may still read pin_tab / cx_tab (a job that failed early returns
+        // without a synchronisation, and the caller may alternate streams)
+        if (!c->tab_ev.wait() || !c->pin_tab.ensure(h.off) || !c->cx_tab.ensure(h.off)) return false;
+        h = Carver{c->pin_tab.at<uint8_t>(0), 0};
+        d = Carver{c->cx_tab.at<uint8_t>(0), 0};
+        tables(*this);
+        return true;
+    }
+    bool send() { return sent = hipMemcpyAsync(c->cx_tab.p, c->pin_tab.p, h.off, hipMemcpyHostToDevice, s) == hipSuccess; }
+    // on every return of the job behind send(): everything the job enqueued precedes the event
+    ~TableUpload() {
+        if (sent) c->tab_ev.record(s);
+    }
+};
+
+// sdb_compactor_run_ssts (j.op == NULL) / sdb_compactor_run_ssts_merge
+sdb_status run_ssts_job(const Job &j, const sdb_compaction_input *inputs, uint32_t ninputs, const uint32_t *run_start,
+                        uint32_t nruns, uint16_t input_sst_version) {
+    sdb_status st = begin_job(j);
+    if (st) return st;
+    if (ninputs && !inputs) return SDB_INVALID_ARGUMENT;
+    if ((st = check_run_shape(input_sst_version, run_start, &nruns, ninputs))) return st;
+    sdb_compactor *c = j.c;
+    if (hipSetDevice(c->device) != hipSuccess) return SDB_DEVICE_ERROR;
+
+    // the inputs' blocks, in input order, as offsets from the lowest data address
     CxInputs in{};
     in.n = ninputs;
     in.nruns = nruns;
-    Carver tc{nullptr, 0};  // the tables' offsets in pin_tab and in cx_tab
-    const uint64_t t_data = tc.bytes(8ull * ninputs), t_boff = tc.bytes(8ull * ninputs);
-    const uint64_t t_first = tc.bytes(8ull * (ninputs + 1)), t_rblk = tc.bytes(8ull * (nruns + 1));
-    const uint64_t t_rent = tc.bytes(8ull * (nruns + 1)), t_total = tc.off;
-    // the previous job's upload and kernels may still read pin_tab / cx_tab (a job that failed early
-    // returns without a synchronisation, and the caller may alternate streams)
-    if (!c->tab_ev.wait() || !c->pin_tab.ensure(t_total) || !c->cx_tab.ensure(t_total)) return SDB_DEVICE_ERROR;
-    const uint8_t **h_data = c->pin_tab.at<const uint8_t *>(t_data);
-    const uint64_t **h_boff = c->pin_tab.at<const uint64_t *>(t_boff);
-    uint64_t *h_first = c->pin_tab.at<uint64_t>(t_first), *h_rblk = c->pin_tab.at<uint64_t>(t_rblk);
-    uint64_t *h_rent = c->pin_tab.at<uint64_t>(t_rent);
+    const uint8_t **h_data;
+    const uint64_t **h_boff;
+    uint64_t *h_first, *h_rblk, *h_rent;
+    TableUpload tab{c, j.s};
+    if (!tab.begin([&](TableUpload &t) {
+            t.take(h_data, in.data, ninputs);
+            t.take(h_boff, in.block_off, ninputs);
+            t.take(h_first, in.first_block, (uint64_t)ninputs + 1);
+            t.take(h_rblk, in.run_block, (uint64_t)nruns + 1);
+            t.take(h_rent, in.run_entry, (uint64_t)nruns + 1);
+        }))
+        return SDB_DEVICE_ERROR;
     uint64_t E = 0, K = 0, V = 0, B = 0;
     uintptr_t base = ~(uintptr_t)0;
     for (uint32_t i = 0; i < ninputs; i++) {
@@ -784,37 +824,16 @@ sdb_status run_ssts_job(sdb_compactor *c, const sdb_compaction_input *inputs, ui
     }
     in.key_bytes = K;
     if (E >= (1ull << 31)) return SDB_LIMIT_EXCEEDED;
-    if (hipMemcpyAsync(c->cx_tab.p, c->pin_tab.p, t_total, hipMemcpyHostToDevice, s) != hipSuccess) return SDB_DEVICE_ERROR;
-    struct TabRelease {  // on every return from here: everything enqueued so far precedes the event
-        sdb_compactor *c;
-        hipStream_t s;
-        ~TabRelease() { c->tab_ev.record(s); }
-    } tab_release{c, s};
-    in.data = c->cx_tab.at<const uint8_t *const>(t_data);
-    in.block_off = c->cx_tab.at<const uint64_t *const>(t_boff);
-    in.first_block = c->cx_tab.at<const uint64_t>(t_first);
-    in.run_block = c->cx_tab.at<const uint64_t>(t_rblk);
-    in.run_entry = c->cx_tab.at<const uint64_t>(t_rent);
+    if (!tab.send()) return SDB_DEVICE_ERROR;
 
-    // 1. decode every input block into one columnar output (run r = entries [run_entry[r], run_entry[r+1]))
+    // decode every input block, gate the merge on the decode and the declared counts, merge and encode (the job's two
+    // synchronisations are merge_encode's)
     DecodeBufs db;
-    if (!c->dec.ensure(decode_bufs_bind(db, B, K, E, nullptr)) || !c->dec_ws.ensure(sdb_decode_workspace_bytes(B)))
+    if ((st = decode_inputs(j, in, K, E, input_sst_version, db))) return st;
+    if (launch_cx_gate(in, db.out.summary, db.err, db.out.block_entry_start, db.gate, j.s) != hipSuccess)
         return SDB_DEVICE_ERROR;
-    decode_bufs_bind(db, B, K, E, c->dec.at<uint8_t>(0));
-    uint64_t *const bstart = db.bstart, *const bend = db.bend;
-    unsigned long long *const gate = db.gate;
-    const sdb_decoded_out &dout = db.out;
-    const uint8_t *arena = reinterpret_cast<const uint8_t *>(base);
-    if (launch_cx_blocks(in, bstart, bend, s) != hipSuccess) return SDB_DEVICE_ERROR;
-    // fail-fast (a failing block fails the job anyway, as load_iterators' reads would): checksums in the emit pass
-    st = sdb_decode_blocks_ex(arena, bstart, bend, B, input_sst_version, SDB_DECODE_FAIL_FAST, &dout,
-                              c->dec_ws.p, c->dec_ws.cap, stream);
-    if (st) return st;
-    const unsigned long long *dec_err = decode_err_word(c->dec_ws.p, B);
-    if (launch_cx_gate(in, dout.summary, dec_err, dout.block_entry_start, gate, s) != hipSuccess)
-        return SDB_DEVICE_ERROR;
-    std::vector<sdb_run> runs = runs_over(dout, arena, run_entry.data(), nruns);
-    return merge_encode(c, runs, E, K, V, gate, ret, op, ctx, params, max_sst_size, stream, num_ssts);
+    const std::vector<sdb_run> runs = runs_over(db.out, reinterpret_cast<const uint8_t *>(base), run_entry.data(), nruns);
+    return merge_encode(j, runs, E, K, V, db.gate);
 }
 
 bool ranges_null(const sdb_scan_ranges *g) {  // a NULL array inside a non-NULL struct
@@ -824,55 +843,46 @@ bool ranges_null(const sdb_scan_ranges *g) {  // a NULL array inside a non-NULL 
 // Sizes (base == NULL) or binds the columns of `rows` contributed rows and K key bytes.
 uint64_t range_cols_bind(sdb_decoded_out &o, uint64_t rows, uint64_t K, uint8_t *base) {
     o = sdb_decoded_out{};
-    o.key_arena_cap = K;
-    o.cap_entries = rows;
     Carver k{base, 0};
-    k.take(o.key_arena, K + 64);
-    k.take(o.key_off, rows + 1);
-    k.take(o.val_off, rows + 1);
-    k.take(o.val_len, rows + 1);
-    k.take(o.seq, rows + 1);
-    k.take(o.flags, rows + 1);
-    k.take(o.create_ts, rows + 1);
-    k.take(o.expire_ts, rows + 1);
+    take_columns(k, o, K, rows);
     return k.off;
 }
 
 // sdb_compactor_run_ssts_ranged.  The host arguments were checked by the entry point (R7).
-sdb_status run_ranged_job(sdb_compactor *c, const sdb_compaction_view *inputs, uint32_t ninputs, const uint32_t *run_start,
+sdb_status run_ranged_job(const Job &j, const sdb_compaction_view *inputs, uint32_t ninputs, const uint32_t *run_start,
                           uint32_t nruns, uint16_t input_sst_version, const sdb_scan_ranges *job,
-                          const sdb_scan_ranges *proj, const sdb_retention *ret, sdb_merge_batch_fn op, void *ctx,
-                          const sdb_sst_params *params, uint64_t max_sst_size, void *stream, uint32_t *num_ssts) {
-    sdb_status st = begin_job(c, ret, params, num_ssts);
+                          const sdb_scan_ranges *proj) {
+    sdb_status st = begin_job(j);
     if (st) return st;
-    if (input_sst_version != 1 && input_sst_version != 2) return SDB_INVALID_VERSION;
-    if (!run_start) nruns = ninputs;
-    if ((uint64_t)nruns > (uint64_t)kMaxRuns * kMaxRuns) return SDB_LIMIT_EXCEEDED;  // two merge levels
-    if (run_start) {
-        if (run_start[0] != 0 || run_start[nruns] != ninputs) return SDB_INVALID_ARGUMENT;
-        for (uint32_t r = 0; r < nruns; r++)
-            if (run_start[r + 1] < run_start[r]) return SDB_INVALID_ARGUMENT;
-    }
+    if ((st = check_run_shape(input_sst_version, run_start, &nruns, ninputs))) return st;
+    sdb_compactor *c = j.c;
     if (hipSetDevice(c->device) != hipSuccess) return SDB_DEVICE_ERROR;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t s = j.s;
     const uint64_t n = ninputs;
 
-    // the per-input and per-run tables the host knows, to device memory (pin_tab / cx_tab, as run_ssts_job)
+    // the per-input and per-run tables the host knows
     RxInputs a{};
     a.n = ninputs;
     a.nruns = nruns;
     if (job) a.has_job = 1, a.job = *job;
     if (proj) a.has_proj = 1, a.proj = *proj;
-    Carver tc{nullptr, 0};
-    const uint64_t t_data = tc.bytes(8 * n), t_ikeys = tc.bytes(8 * n), t_ikoff = tc.bytes(8 * n), t_boff = tc.bytes(8 * n);
-    const uint64_t t_nblk = tc.bytes(8 * n), t_gblk = tc.bytes(8 * (n + 1)), t_nent = tc.bytes(8 * n);
-    const uint64_t t_rstart = tc.bytes(4 * ((uint64_t)nruns + 1)), t_total = tc.off;
-    if (!c->tab_ev.wait() || !c->pin_tab.ensure(t_total) || !c->cx_tab.ensure(t_total)) return SDB_DEVICE_ERROR;
-    const uint8_t **h_data = c->pin_tab.at<const uint8_t *>(t_data), **h_ikeys = c->pin_tab.at<const uint8_t *>(t_ikeys);
-    const uint64_t **h_ikoff = c->pin_tab.at<const uint64_t *>(t_ikoff), **h_boff = c->pin_tab.at<const uint64_t *>(t_boff);
-    uint64_t *h_nblk = c->pin_tab.at<uint64_t>(t_nblk), *h_gblk = c->pin_tab.at<uint64_t>(t_gblk);
-    uint64_t *h_nent = c->pin_tab.at<uint64_t>(t_nent);
-    uint32_t *h_rstart = c->pin_tab.at<uint32_t>(t_rstart);
+    const uint8_t **h_data, **h_ikeys;
+    const uint8_t *const *d_data;  // (read by the decode: CxInputs below)
+    const uint64_t **h_ikoff, **h_boff;
+    uint64_t *h_nblk, *h_gblk, *h_nent;
+    uint32_t *h_rstart;
+    TableUpload tab{c, s};
+    if (!tab.begin([&](TableUpload &t) {
+            t.take(h_data, d_data, n);
+            t.take(h_ikeys, a.index_keys, n);
+            t.take(h_ikoff, a.index_key_off, n);
+            t.take(h_boff, a.block_off, n);
+            t.take(h_nblk, a.num_blocks, n);
+            t.take(h_gblk, a.gblock, n + 1);
+            t.take(h_nent, a.num_entries, n);
+            t.take(h_rstart, a.run_start, (uint64_t)nruns + 1);
+        }))
+        return SDB_DEVICE_ERROR;
     uint64_t B_all = 0, E_all = 0, K_all = 0;
     uintptr_t base = ~(uintptr_t)0;
     for (uint32_t i = 0; i < ninputs; i++) {
@@ -892,19 +902,7 @@ sdb_status run_ranged_job(sdb_compactor *c, const sdb_compaction_view *inputs, u
     h_gblk[ninputs] = B_all;
     if (base == ~(uintptr_t)0) base = 0;
     for (uint32_t r = 0; r <= nruns; r++) h_rstart[r] = run_start ? run_start[r] : r;
-    if (hipMemcpyAsync(c->cx_tab.p, c->pin_tab.p, t_total, hipMemcpyHostToDevice, s) != hipSuccess) return SDB_DEVICE_ERROR;
-    struct TabRelease {  // on every return from here: everything enqueued so far precedes the event
-        sdb_compactor *c;
-        hipStream_t s;
-        ~TabRelease() { c->tab_ev.record(s); }
-    } tab_release{c, s};
-    a.index_keys = c->cx_tab.at<const uint8_t *const>(t_ikeys);
-    a.index_key_off = c->cx_tab.at<const uint64_t *const>(t_ikoff);
-    a.block_off = c->cx_tab.at<const uint64_t *const>(t_boff);
-    a.num_blocks = c->cx_tab.at<const uint64_t>(t_nblk);
-    a.gblock = c->cx_tab.at<const uint64_t>(t_gblk);
-    a.num_entries = c->cx_tab.at<const uint64_t>(t_nent);
-    a.run_start = c->cx_tab.at<const uint32_t>(t_rstart);
+    if (!tab.send()) return SDB_DEVICE_ERROR;
     // what the kernels write
     const uint64_t nres = kRxResult + (uint64_t)nruns + 1;
     auto bind_rx = [&](uint8_t *w) {
@@ -957,19 +955,12 @@ sdb_status run_ranged_job(sdb_compactor *c, const sdb_compaction_view *inputs, u
     in.nruns = nruns;
     in.base = base;
     in.nblocks = B;
-    in.data = c->cx_tab.at<const uint8_t *const>(t_data);
+    in.data = d_data;
     in.block_off = a.cov_off;
     in.first_block = a.cov_first;
     DecodeBufs db;
-    if (!c->dec.ensure(decode_bufs_bind(db, B, K, E, nullptr)) || !c->dec_ws.ensure(sdb_decode_workspace_bytes(B)))
-        return SDB_DEVICE_ERROR;
-    decode_bufs_bind(db, B, K, E, c->dec.at<uint8_t>(0));
-    const uint8_t *arena = reinterpret_cast<const uint8_t *>(base);
-    if (launch_cx_blocks(in, db.bstart, db.bend, s) != hipSuccess) return SDB_DEVICE_ERROR;
-    st = sdb_decode_blocks_ex(arena, db.bstart, db.bend, B, input_sst_version, SDB_DECODE_FAIL_FAST, &db.out, c->dec_ws.p,
-                              c->dec_ws.cap, stream);
-    if (st) return st;
-    if (launch_rx_clip_gate(a, db.out, decode_err_word(c->dec_ws.p, B), E_all, K_all, s) != hipSuccess ||
+    if ((st = decode_inputs(j, in, K, E, input_sst_version, db))) return st;
+    if (launch_rx_clip_gate(a, db.out, db.err, E_all, K_all, s) != hipSuccess ||
         hipMemcpyAsync(h_words, a.result, 8 * nres, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
         return SDB_DEVICE_ERROR;
@@ -991,8 +982,8 @@ sdb_status run_ranged_job(sdb_compactor *c, const sdb_compaction_view *inputs, u
         if (launch_rx_compact(a, db.out, closed, rows, s) != hipSuccess) return SDB_DEVICE_ERROR;
         src = &closed;
     }
-    const std::vector<sdb_run> runs = runs_over(*src, arena, run_entry.data(), nruns);
-    return merge_encode(c, runs, rows, key_bytes, V, nullptr, ret, op, ctx, params, max_sst_size, stream, num_ssts);
+    const std::vector<sdb_run> runs = runs_over(*src, reinterpret_cast<const uint8_t *>(base), run_entry.data(), nruns);
+    return merge_encode(j, runs, rows, key_bytes, V, nullptr);
 }
 
 }  // namespace
@@ -1001,22 +992,22 @@ extern "C" {
 
 sdb_status sdb_compactor_run(sdb_compactor *c, const sdb_run *runs, uint32_t nruns, const sdb_retention *ret,
                              const sdb_sst_params *params, uint64_t max_sst_size, void *stream, uint32_t *num_ssts) {
-    return run_job(c, runs, nruns, ret, nullptr, nullptr, params, max_sst_size, stream, num_ssts);
+    return run_job(Job{c, ret, nullptr, nullptr, params, max_sst_size, stream, num_ssts}, runs, nruns);
 }
 
 sdb_status sdb_compactor_run_merge(sdb_compactor *c, const sdb_run *runs, uint32_t nruns, const sdb_retention *ret,
                                    sdb_merge_batch_fn op, void *ctx, const sdb_sst_params *params,
                                    uint64_t max_sst_size, void *stream, uint32_t *num_ssts) {
     if (!op) return SDB_INVALID_ARGUMENT;
-    return run_job(c, runs, nruns, ret, op, ctx, params, max_sst_size, stream, num_ssts);
+    return run_job(Job{c, ret, op, ctx, params, max_sst_size, stream, num_ssts}, runs, nruns);
 }
 
 sdb_status sdb_compactor_run_ssts(sdb_compactor *c, const sdb_compaction_input *inputs, uint32_t ninputs,
                                   const uint32_t *run_start, uint32_t nruns, uint16_t input_sst_version,
                                   const sdb_retention *ret, const sdb_sst_params *params, uint64_t max_sst_size,
                                   void *stream, uint32_t *num_ssts) {
-    return run_ssts_job(c, inputs, ninputs, run_start, nruns, input_sst_version, ret, nullptr, nullptr, params,
-                        max_sst_size, stream, num_ssts);
+    return run_ssts_job(Job{c, ret, nullptr, nullptr, params, max_sst_size, stream, num_ssts}, inputs, ninputs, run_start,
+                        nruns, input_sst_version);
 }
 
 sdb_status sdb_compactor_run_ssts_merge(sdb_compactor *c, const sdb_compaction_input *inputs, uint32_t ninputs,
@@ -1025,8 +1016,8 @@ sdb_status sdb_compactor_run_ssts_merge(sdb_compactor *c, const sdb_compaction_i
                                         const sdb_sst_params *params, uint64_t max_sst_size, void *stream,
                                         uint32_t *num_ssts) {
     if (!op) return SDB_INVALID_ARGUMENT;
-    return run_ssts_job(c, inputs, ninputs, run_start, nruns, input_sst_version, ret, op, ctx, params, max_sst_size,
-                        stream, num_ssts);
+    return run_ssts_job(Job{c, ret, op, ctx, params, max_sst_size, stream, num_ssts}, inputs, ninputs, run_start, nruns,
+                        input_sst_version);
 }
 
 sdb_status sdb_compactor_run_ssts_ranged(sdb_compactor *c, const sdb_compaction_view *inputs, uint32_t ninputs,
@@ -1048,8 +1039,8 @@ sdb_status sdb_compactor_run_ssts_ranged(sdb_compactor *c, const sdb_compaction_
         int n = 0;
         return hipGetDeviceCount(&n) != hipSuccess || n == 0 ? SDB_DEVICE_ERROR : SDB_INVALID_ARGUMENT;
     }
-    return run_ranged_job(c, inputs, ninputs, run_start, nruns, input_sst_version, job_range, proj, ret, op, ctx, params,
-                          max_sst_size, stream, num_ssts);
+    return run_ranged_job(Job{c, ret, op, ctx, params, max_sst_size, stream, num_ssts}, inputs, ninputs, run_start, nruns,
+                          input_sst_version, job_range, proj);
 }
 
 sdb_status sdb_compactor_range_stats(const sdb_compactor *c, sdb_range_job_stats *stats) {

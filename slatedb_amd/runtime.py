@@ -1315,8 +1315,9 @@ class Compactor:
 
     def _job(self, symbol, head, ret, operator, prm, max_sst_size, stream):
         """One job entry point: the inputs `head`, then ret, (with an operator) its callback and a NULL context,
-        params, max_sst_size, stream, num_ssts."""
-        op = ()
+        params, max_sst_size, stream, num_ssts.  The ranged symbol always takes the callback pair: NULL without an
+        operator."""
+        op = (_abi.MERGE_BATCH_FN(), None) if symbol.endswith("_ranged") else ()
         if operator is not self._PLAIN:
             cb, self.operator_state = self._operator_callback(operator)
             op = (cb, None)
@@ -1330,17 +1331,27 @@ class Compactor:
         return self._job("sdb_compactor_run" + ("_merge" if operator is not self._PLAIN else ""), (cr, len(druns)), ret,
                          operator, prm, max_sst_size, stream)
 
+    @staticmethod
+    def _inputs(inputs, views=False):
+        """The sdb_compaction_input array of a job's inputs; `views`: the sdb_compaction_view array (+ index keys)."""
+        ci = [_abi.CompactionInput(x.data.data_ptr(), x.block_off.data_ptr(), x.block_off.numel() - 1, x.num_entries,
+                                   x.key_bytes, x.val_bytes) for x in inputs]
+        if not views:
+            return (_abi.CompactionInput * max(len(ci), 1))(*ci)
+        return (_abi.CompactionView * max(len(ci), 1))(*[
+            _abi.CompactionView(c, x.index_keys.data_ptr(), x.index_key_off.data_ptr()) for c, x in zip(ci, inputs)])
+
+    @staticmethod
+    def _run_shape(run_start, ninputs):
+        """(run_start, nruns) as the jobs over encoded inputs take them: without run_start every input is a run."""
+        if run_start is None:
+            return None, ninputs
+        return (C.c_uint32 * len(run_start))(*run_start), len(run_start) - 1
+
     def _run_ssts(self, inputs, ret, operator, prm, max_sst_size, input_version, run_start, stream):
-        ci = (_abi.CompactionInput * max(len(inputs), 1))(*[
-            _abi.CompactionInput(x.data.data_ptr(), x.block_off.data_ptr(), x.block_off.numel() - 1, x.num_entries,
-                                 x.key_bytes, x.val_bytes) for x in inputs])
-        rs = None
-        nruns = len(inputs)
-        if run_start is not None:
-            rs = (C.c_uint32 * len(run_start))(*run_start)
-            nruns = len(run_start) - 1
         return self._job("sdb_compactor_run_ssts" + ("_merge" if operator is not self._PLAIN else ""),
-                         (ci, len(inputs), rs, nruns, input_version), ret, operator, prm, max_sst_size, stream)
+                         (self._inputs(inputs), len(inputs), *self._run_shape(run_start, len(inputs)), input_version),
+                         ret, operator, prm, max_sst_size, stream)
 
     def run(self, druns, ret, prm, max_sst_size, stream=None):
         return self._run(druns, ret, self._PLAIN, prm, max_sst_size, stream)
@@ -1392,16 +1403,7 @@ class Compactor:
         takes them, or None; either may also be the dict of arrays those functions return (host arrays, or device
         tensors the caller keeps)."""
         dev = inputs[0].data.device if inputs else "cuda"
-        cv = (_abi.CompactionView * max(len(inputs), 1))(*[
-            _abi.CompactionView(_abi.CompactionInput(x.data.data_ptr(), x.block_off.data_ptr(), x.block_off.numel() - 1,
-                                                     x.num_entries, x.key_bytes, x.val_bytes),
-                                x.index_keys.data_ptr(), x.index_key_off.data_ptr()) for x in inputs])
-        rs = None
-        nruns = len(inputs)
-        if run_start is not None:
-            rs = (C.c_uint32 * len(run_start))(*run_start)
-            nruns = len(run_start) - 1
-        keep = []
+        keep = []  # the range tensors: until the job's work is done
 
         def ranges(arrays):  # the arrays of an sdb_scan_ranges (host, or already on the device) -> the struct
             t = {k: a if hasattr(a, "data_ptr") else _to_dev(a, dev) for k, a in arrays.items() if k != "n"}
@@ -1412,15 +1414,11 @@ class Compactor:
         columnar = lambda x, f: x if isinstance(x, dict) else f(x)  # noqa: E731  (a dict: the host arrays themselves)
         jr = None if job_range is None else ranges(columnar(job_range, lambda r: scan_ranges_columnar([r])))
         pj = None if projections is None else ranges(columnar(projections, projections_columnar))
-        cb = _abi.MERGE_BATCH_FN()  # NULL: no operator
-        if operator is not None:
-            cb, self.operator_state = self._operator_callback(operator)
-        ns = C.c_uint32(0)
-        st = lib().sdb_compactor_run_ssts_ranged(self.h, cv, len(inputs), rs, nruns, input_version, jr, pj, C.byref(ret),
-                                                 cb, None, C.byref(prm), max_sst_size, _sp(stream), C.byref(ns))
+        res = self._job("sdb_compactor_run_ssts_ranged",
+                        (self._inputs(inputs, views=True), len(inputs), *self._run_shape(run_start, len(inputs)),
+                         input_version, jr, pj), ret, self._PLAIN if operator is None else operator, prm, max_sst_size, stream)
         _sync(stream, dev)  # the range tensors are released on return
-        self.status = st
-        return st, ns.value
+        return res
 
     def range_stats(self):
         """sdb_range_job_stats of the last run_ssts_ranged job (zeros after any other)."""
