@@ -37,6 +37,8 @@
  *   - sdb_lsm_get_mem          -> Reader::get_key_value_with_options from the active memtable down
  *                                 (reader.rs:133-182): device memtables (sorted runs, as sdb_wal_replay_emit
  *                                 leaves them) searched ahead of the tree, with or without operand chains.
+ *   - sdb_lsm_scan_mem         -> Reader::scan_with_options from the active memtable down (reader.rs:275-320,
+ *                                 db_iter.rs:145-163): the same memtables merged ahead of the tree's SSTs.
  *   - sdb_sst_builder_*        -> host-side mirror of EncodedSsTableBuilder's add()/build()/
  *                                 next_block() call order (sst_builder.rs:224-276), batching
  *                                 entries into a columnar pinned buffer and encoding on the GPU.
@@ -622,8 +624,8 @@ sdb_status sdb_lsm_get(const sdb_lsm_view *lsm, const uint8_t *key_bytes, const 
 
 /* ---------------------------------------------------------------------------------------------
  * Batched Db::scan over a tree of encoded SSTs (device): the on-disk part of Reader::scan_with_options
- * (reader.rs:275-320) -> DbIterator::new (db_iter.rs:189-257), drained.  Memtables and the write batch stay
- * on the host; the caller merges them on top.  The tree is the sdb_lsm_view of sdb_lsm_get, the ranges are
+ * (reader.rs:275-320) -> DbIterator::new (db_iter.rs:189-257), drained.  The write batch stays on the host and
+ * the caller merges it on top; memtables in device memory are merged by sdb_lsm_scan_mem.  The tree is the sdb_lsm_view of sdb_lsm_get, the ranges are
  * the sdb_scan_ranges of sdb_sst_scan.  Many ranges are scanned by one call:
  *   1. SSTs of a range: SST i takes part in range r iff it has blocks and {k : first_key[i] <= k <=
  *      last_key[i]} meets the range as a set: the range is not empty as a set, last_key[i] does not precede
@@ -1372,8 +1374,8 @@ uint32_t sdb_diag_replay_tile(void);
  *       as a linear sequence, the workspace reusable without a host-side reset.
  * sdb_lsm_get_mem_workspace_bytes(0, ...) equals sdb_lsm_get_projected_workspace_bytes(...).
  * Out of scope: the write batch (its rows all carry seq u64::MAX and are exempt from max_seq; it is one
- * transaction's private state and stays on the host, consulted first); scans over memtables (sdb_lsm_scan*
- * still merges them on the host); the concurrent skiplist (a table here is a finished sorted run); segments.
+ * transaction's private state and stays on the host, consulted first); the concurrent skiplist (a table here is a
+ * finished sorted run); segments.  Scans over memtables: sdb_lsm_scan_mem below.
  * ------------------------------------------------------------------------------------------- */
 typedef struct sdb_mem_view {
     const sdb_run *tables;   /* DEVICE array of num_tables sorted runs in search order: the active memtable,
@@ -1400,6 +1402,85 @@ sdb_status sdb_lsm_get_mem(const sdb_mem_view *mem /* or NULL */, const sdb_lsm_
                            const sdb_mem_get_out *mout, const sdb_chain_out *chain /* or NULL */,
                            const sdb_mem_chain_out *mchain /* iff chain */, void *workspace, uint64_t workspace_bytes,
                            void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Batched Db::scan over device memtables and the tree (device): Reader::scan_with_options (reader.rs:275-320)
+ * from the active memtable down.  ScanIterator merges the memtable iterators among themselves and the result
+ * with the tree's iterators (db_iter.rs:145-163); max_seq is applied per leaf, before any deduplication
+ * (db_iter.rs:205-217).  sdb_lsm_scan_mem is sdb_lsm_scan_projected (itself the superset of the plain, _merge and
+ * _filtered scans) with the memtables of sdb_lsm_get_mem merged ahead of the tree; it is the scan counterpart of
+ * that call and shares sdb_mem_view and sdb_mem_chain_out with it.  Everything not named here is as in
+ * sdb_lsm_scan_projected.
+ *   S1. sources: a range's sources are tables 0 .. num_tables - 1 in order, then the SSTs of `lsm` in their search
+ *       order.  The order of the sources only breaks ties; within one source, rows with equal key and seq keep
+ *       their physical order.  Filters, the prefixes' probes and projections concern SSTs only;
+ *   S2. one table: its rows are ordered key ascending, then seq descending (M2).  The rows whose key range r
+ *       contains are one contiguous stretch [g0, g1), found as two lower bounds over key_off / key_arena.  An
+ *       excluded start steps over every version of the bound key, an included end keeps every version of it.  A
+ *       key that is a proper prefix of its neighbour is a different key.  A range that is empty as a set, or has a
+ *       bound kind above 2, reads nothing from any table.  A table with n == 0 takes part in nothing;
+ *   S3. rows: rule 3 of sdb_lsm_scan over the union of the tables' stretches and the SST candidates.  Versions
+ *       above max_seq[r] are dropped first, then the newest version per key wins; for an equal (key, seq) the
+ *       earlier source wins, so a table wins before any SST.  A winning tombstone yields nothing, an above-bound
+ *       tombstone hides nothing.  For a row that a table won: out->sst = 0xFFFFFFFF, val_off / val_len are the
+ *       row's (tables[t].val_base[val_off .. + val_len); 0, 0 for an empty value), seq, flags and the timestamps
+ *       are the row's (NULL create_ts / expire_ts mean none), and mout->table / row name the row.  For a row that
+ *       an SST won every sdb_lsm_scan_out column is what the projected call writes, mout->table = 0xFFFFFFFF and
+ *       mout->row = 0;
+ *   S4. merge operands: without a chain a winning operand fails its range with SDB_MERGE_OPERATOR_MISSING, in a
+ *       table as in an SST.  With a chain, rule 4 of sdb_lsm_scan_merge runs over the merged order of all sources:
+ *       a chain runs through the tables and into the tree.  A link lies either in a table (chain->sst =
+ *       0xFFFFFFFF, chain->block = 0, mchain->table / row, the other link columns the row's) or in an SST
+ *       (mchain->table = 0xFFFFFFFF, mchain->row = 0), as in M4.  The MergeTracker aggregates fold over all links
+ *       of all layers (and a tombstone base's timestamps, as in sdb_lsm_scan_merge).  The cap_links protocol is
+ *       unchanged and covers the mchain columns;
+ *   S5. nothing is lazy: every SST that takes part in a range is read and checked as rule 2 says, point ranges
+ *       included.  A table that holds a range's newest versions shields the range from no block error: THIS
+ *       DIFFERS FROM M5, where a get decided in the tables consults no SST.  blocks_checked, range_ssts and
+ *       range_filtered are exactly the projected call's.  A failing range contributes no row from any source;
+ *   S6. capacity: num_candidates / candidate_key_bytes count the tables' stretches too: g1 - g0 rows and
+ *       key_off[g1] - key_off[g0] bytes per (range, table), before max_seq.  A range failed by a block, version or
+ *       argument error stages none.  Both SDB_LIMIT_EXCEEDED cases are unchanged; when no column byte is written
+ *       that includes the mout entry columns.  range_tables[r], the number of tables with a non-empty stretch for
+ *       range r, is valid whenever range_ssts is;
+ *   S7. no tables: mem == NULL or num_tables == 0 gives exactly sdb_lsm_scan_projected: every column, counter,
+ *       summary word and chain column.  For the rows written mout->table is all 0xFFFFFFFF and mout->row all 0,
+ *       and the links' likewise; range_tables is all 0.  sdb_lsm_scan_mem_workspace_bytes(0, ...) equals
+ *       sdb_lsm_scan_projected_workspace_bytes(...);
+ *   S8. no tree: num_ssts == 0, num_runs == 0 or total_blocks == 0 with tables present still scans the tables.
+ *       Nothing is read through the tree's arrays, the tree's kernels are not launched, and blocks_checked is 0.
+ *       n == 0 is SDB_OK with zeroed summaries;
+ *   S9. arguments checked on the host: NULL lsm, out or mout, exactly one of chain and mchain, NULL mem->tables
+ *       with num_tables > 0, a NULL array that a non-empty input needs, and a short workspace return
+ *       SDB_INVALID_ARGUMENT from the call, besides what sdb_lsm_scan_projected checks; n * (num_ssts +
+ *       num_tables) over 2^40: SDB_LIMIT_EXCEEDED; after all host checks, SDB_DEVICE_ERROR when no device is
+ *       present.  On the device, as M9: a table with n > 0 and a NULL key_arena, key_off, val_off, val_len, seq or
+ *       flags, or with n >= 2^31, fails EVERY range with SDB_INVALID_ARGUMENT and blocks_checked 0, and nothing is
+ *       read through the tables.  The rows' order and the offsets' monotonicity are the caller's obligation: a
+ *       violation may lose rows but the scan never leaves rows [0, n) of a table, or a pair's staging slots;
+ *   S10. conventions: no allocation, no synchronisation, launches only on `stream`, capturable into a HIP graph as
+ *       a linear sequence, the workspace reusable without a host-side reset.
+ * Out of scope: the write batch (it stays on the host, merged on top); the live skiplist (a table here is a
+ * finished sorted run); segments; and the lazy GetIterator the reference substitutes for a point range k..=k (a
+ * point range is scanned like any other: callers who need a get's laziness call sdb_lsm_get_mem).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct sdb_mem_scan_out {    /* device arrays */
+    uint32_t *table;                 /* cap_entries: memtable that holds the row (0xFFFFFFFF: see out->sst) */
+    uint64_t *row;                   /* cap_entries: its row in tables[table] (else 0) */
+    uint32_t *range_tables;          /* n: tables that hold at least one key of range r (before max_seq) */
+} sdb_mem_scan_out;
+uint64_t sdb_lsm_scan_mem_workspace_bytes(uint32_t num_tables, uint64_t total_blocks, uint32_t num_ssts,
+                                          uint32_t num_runs, uint64_t nranges, uint64_t cand_entries,
+                                          uint64_t cand_key_bytes, int32_t merge /* 1: a chain is passed */);
+sdb_status sdb_lsm_scan_mem(const sdb_mem_view *mem /* or NULL */, const sdb_lsm_view *lsm,
+                            const sdb_scan_ranges *proj /* n == num_ssts; or NULL */,
+                            const sdb_filter_policy *policies /* device, num_ssts; or NULL */,
+                            const sdb_scan_ranges *ranges, const sdb_scan_prefixes *prefixes /* or NULL */,
+                            const uint64_t *max_seq /* device, n; NULL = no bound */, int32_t descending,
+                            uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out *out,
+                            const sdb_mem_scan_out *mout, const sdb_chain_out *chain /* or NULL */,
+                            const sdb_mem_chain_out *mchain /* iff chain */, const sdb_scan_filter_out *fout,
+                            void *workspace, uint64_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * SST footer (host): everything after the data section, so data ++ footer is the whole SST object

@@ -755,11 +755,16 @@ static sdb_status lsm_scan_call(const sdb_lsm_view *lsm, const sdb_scan_ranges *
                                 int32_t descending, uint64_t cand_entries, uint64_t cand_key_bytes,
                                 const sdb_lsm_scan_out *out, bool merge, const sdb_chain_out *chain, bool filter,
                                 const sdb_filter_policy *policies, const sdb_scan_prefixes *prefixes,
-                                const sdb_scan_filter_out *fout, void *workspace, uint64_t workspace_bytes, void *stream) {
+                                const sdb_scan_filter_out *fout, void *workspace, uint64_t workspace_bytes, void *stream,
+                                bool layers = false, const sdb_mem_view *mem = nullptr,
+                                const sdb_mem_scan_out *mout = nullptr, const sdb_mem_chain_out *mchain = nullptr) {
     if (!lsm || !ranges || !out || (merge && !chain) || (filter && !fout)) return SDB_INVALID_ARGUMENT;
+    const uint32_t ntab = layers && mem ? mem->num_tables : 0;
+    if (layers && (!mout || (chain != nullptr) != (mchain != nullptr) || (ntab && !mem->tables))) return SDB_INVALID_ARGUMENT;
     const uint64_t n = ranges->n;
     // (the limits all give one status, so these may come before the tree's)
-    if (lsm->num_ssts && n > (1ull << 40) / lsm->num_ssts) return SDB_LIMIT_EXCEEDED;  // per (range, SST) state
+    const uint64_t per_range = (uint64_t)lsm->num_ssts + ntab;  // per (range, source) state
+    if (per_range && n > (1ull << 40) / per_range) return SDB_LIMIT_EXCEEDED;
     if (cand_entries > (1ull << 40) || cand_key_bytes > (1ull << 44)) return SDB_LIMIT_EXCEEDED;
     sdb_status st = check_tree(lsm);
     if (st) return st;
@@ -774,11 +779,21 @@ static sdb_status lsm_scan_call(const sdb_lsm_view *lsm, const sdb_scan_ranges *
     if (filter && n && (!fout->range_filtered || !fout->num_filtered)) return SDB_INVALID_ARGUMENT;
     if (filter && n && prefixes && (!prefixes->prefix_bytes || !prefixes->prefix_off || !prefixes->has_prefix))
         return SDB_INVALID_ARGUMENT;
-    if (!workspace || workspace_bytes < lsm_scan_workspace_bytes(lsm->total_blocks, lsm->num_ssts, n, cand_entries,
-                                                                 cand_key_bytes, merge, filter) + 256)
+    if (layers && ((n && !mout->range_tables) || (out->cap_entries && (!mout->table || !mout->row)) ||
+                   (merge && chain->cap_links && (!mchain->table || !mchain->row))))
         return SDB_INVALID_ARGUMENT;
+    const uint64_t need = layers ? lsm_scan_mem_workspace_bytes(ntab, lsm->total_blocks, lsm->num_ssts, n, cand_entries,
+                                                                cand_key_bytes, merge)
+                                 : lsm_scan_workspace_bytes(lsm->total_blocks, lsm->num_ssts, n, cand_entries, cand_key_bytes,
+                                                            merge, filter);
+    if (!workspace || workspace_bytes < need + 256) return SDB_INVALID_ARGUMENT;
     if (!device_ok()) return SDB_DEVICE_ERROR;
     uint8_t *w = ws_align(workspace);
+    if (layers)
+        return launch_lsm_scan_mem(mem, *lsm, *ranges, max_seq, descending ? 1u : 0u, cand_entries, cand_key_bytes, *out, *mout,
+                                   merge ? chain : nullptr, mchain, policies, prefixes, *fout, proj, w, S(stream)) != hipSuccess
+                   ? SDB_DEVICE_ERROR
+                   : SDB_OK;
     if (launch_lsm_scan(*lsm, *ranges, max_seq, descending ? 1u : 0u, cand_entries, cand_key_bytes, *out,
                         merge ? chain : nullptr, policies, prefixes, filter ? fout : nullptr, filter ? proj : nullptr, w,
                         S(stream)) != hipSuccess)
@@ -824,6 +839,23 @@ sdb_status sdb_lsm_scan_projected(const sdb_lsm_view *lsm, const sdb_scan_ranges
                                   void *workspace, uint64_t workspace_bytes, void *stream) {
     return lsm_scan_call(lsm, proj, ranges, max_seq, descending, cand_entries, cand_key_bytes, out, chain != nullptr, chain,
                          true, policies, prefixes, fout, workspace, workspace_bytes, stream);
+}
+
+uint64_t sdb_lsm_scan_mem_workspace_bytes(uint32_t num_tables, uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs,
+                                          uint64_t nranges, uint64_t cand_entries, uint64_t cand_key_bytes, int32_t merge) {
+    (void)num_runs;
+    return lsm_scan_mem_workspace_bytes(num_tables, total_blocks, num_ssts, nranges, cand_entries, cand_key_bytes, merge != 0) +
+           256;
+}
+
+sdb_status sdb_lsm_scan_mem(const sdb_mem_view *mem, const sdb_lsm_view *lsm, const sdb_scan_ranges *proj,
+                            const sdb_filter_policy *policies, const sdb_scan_ranges *ranges,
+                            const sdb_scan_prefixes *prefixes, const uint64_t *max_seq, int32_t descending,
+                            uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out *out,
+                            const sdb_mem_scan_out *mout, const sdb_chain_out *chain, const sdb_mem_chain_out *mchain,
+                            const sdb_scan_filter_out *fout, void *workspace, uint64_t workspace_bytes, void *stream) {
+    return lsm_scan_call(lsm, proj, ranges, max_seq, descending, cand_entries, cand_key_bytes, out, chain != nullptr, chain,
+                         true, policies, prefixes, fout, workspace, workspace_bytes, stream, true, mem, mout, mchain);
 }
 
 // ---- WAL replay / device memtable ----

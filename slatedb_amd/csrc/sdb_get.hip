@@ -67,6 +67,7 @@
 #include <algorithm>
 
 #include "sdb_decode.h"
+#include "sdb_mem.h"
 #include "sdb_range.h"
 
 namespace sdb {
@@ -154,10 +155,6 @@ __global__ __launch_bounds__(256) void k_get_validate(GetArgs a) {
     }
 }
 
-struct Key {
-    const uint8_t *t;
-    uint32_t nt;
-};
 SDB_DEV Key key_of(const GetArgs &a, uint64_t q) { return Key{a.key_bytes + a.key_off[q], (uint32_t)(a.key_off[q + 1] - a.key_off[q])}; }
 // sign(SsTableInfo.first_entry / last_entry of SST i cmp key)
 SDB_DEV int cmp_first(const GetArgs &a, uint32_t i, const Key &k) {
@@ -429,19 +426,6 @@ SDB_DEV auto table_recs(const GetArgs &a) {
     else return a.trec;
 }
 
-// Row i of a memtable as the walks see an SST row: vl, seq, flags and the timestamps; the value starts at vbase.
-SDB_DEV Row tab_row(const sdb_run &T, uint64_t i, uint64_t &vbase) {
-    Row r{};
-    const uint8_t no = (uint8_t)((T.create_ts ? 0 : SDB_FLAG_HAS_CREATE_TS) | (T.expire_ts ? 0 : SDB_FLAG_HAS_EXPIRE_TS));
-    r.flags = (uint8_t)(T.flags[i] & ~no);
-    r.seq = T.seq[i];
-    r.vl = T.val_len[i];
-    r.cts = T.create_ts ? T.create_ts[i] : 0;
-    r.ets = T.expire_ts ? T.expire_ts[i] : 0;
-    vbase = T.val_off[i];
-    return r;
-}
-
 // M: the call has memtables (sdb_lsm_get_mem): their records come first, in table order.
 template <bool MERGE, bool M = false>
 __global__ __launch_bounds__(64) void k_get_resolve(GetArgs a) {
@@ -668,11 +652,7 @@ __global__ __launch_bounds__(64) void k_gm_emit(GetArgs a) {
 
 __global__ __launch_bounds__(256) void k_mem_validate(GetArgs a) {  // after k_get_validate: it may only add to *bad
     int bad = 0;
-    for (uint32_t j = threadIdx.x; j < a.ntab; j += blockDim.x) {
-        const sdb_run T = a.tabs[j];
-        if (T.n >= (1ull << 31)) bad = 1;
-        if (T.n && (!T.key_arena || !T.key_off || !T.val_off || !T.val_len || !T.seq || !T.flags)) bad = 1;
-    }
+    for (uint32_t j = threadIdx.x; j < a.ntab; j += blockDim.x) bad |= tab_malformed(a.tabs[j]);
     bad = __syncthreads_or(bad);
     if (threadIdx.x == 0) {
         if (bad) *a.bad = 1u;
@@ -704,21 +684,6 @@ static hipError_t launch_mem_reset(uint8_t *decided, const sdb_mem_get_out &mout
     return hipGetLastError();
 }
 
-SDB_DEV int tab_cmp(const sdb_run &T, uint64_t i, const Key &k) {  // sign(key of row i cmp k)
-    const uint64_t o = T.key_off[i];
-    return cmp_bytes(T.key_arena + o, (uint32_t)(T.key_off[i + 1] - o), k.t, k.nt, 0).c;
-}
-// The first row that does not precede (k, bound) in the table's order: key > k, or key == k and seq <= bound.
-SDB_DEV uint64_t tab_seek(const sdb_run &T, const Key &k, uint64_t bound) {
-    uint64_t lo = 0, hi = T.n;
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        const int c = tab_cmp(T, mid, k);
-        if (c < 0 || (c == 0 && T.seq[mid] > bound)) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
 // The rows from `from` on with key == k and seq <= bound, in table order (KVTable::range(key..=key) under
 // FilterIterator::new_with_max_seq): visit(row, value base, the row) -> false: stop.
 template <typename F>

@@ -66,10 +66,27 @@
 //                  not asks Point(k) and hashes for itself (point_key is judged on the view range, sst_iter.rs:82-87)
 //   k_ls_edge      the candidates are the rows V contains
 // Everything behind k_ls_edge sees fewer pairs and candidates and knows nothing of projections.
+// sdb_lsm_scan_mem (MEM; ScanIterator: the memtables merged among themselves, then with the tree, db_iter.rs:145-163)
+// makes the second index of a pair a source: p = range * (T + num_ssts) + j, j < T a table, j - T an SST.  A table
+// is a sorted run (sdb_mem.h), so its candidates are the rows between two lower bounds and need no block:
+//   k_ls_mreset    the blocks' marks and statuses, in place of the two memsets (see k_mem_reset of sdb_get.hip)
+//   k_ls_tvalidate one workgroup, after k_ls_validate: tab_malformed of every table; a malformed table makes the call malformed
+//   k_ls_tprobe    thread per (range, table) pair, neighbouring ranges of one table in a wave: [g0, g1), the counts
+//                  and the key-byte rank of g0 into the slots k_ls_edge fills for an SST pair
+//   k_ls_rstat     also: range_tables; a failing range zeroes its table pairs' counts too
+//   k_ls_trows     thread per candidate of a table pair: key offset and length, seq, flags, the row, and the key
+//                  copied into the pair's span of the staging arena (neighbouring threads, neighbouring keys)
+//   k_ls_fold / k_ls_emit  a candidate of a table takes its columns from the table's (tab_row) and opens no block;
+//                  they name the table and the row in mchain / mout
+// k_ls_rank, k_ls_links, the scans and k_ls_count work on staged candidates and see sources where they saw SSTs: the
+// stride is nsrc, and j < i still means "the earlier source".  Without tables nsrc == num_ssts and the seven other
+// entry points launch the instantiations without the table step (k_ls_mfill then names no table for what they wrote).
+#include <algorithm>
 #include <climits>
 
 #include "sdb_range.h"
 #include "sdb_decode.h"
+#include "sdb_mem.h"
 
 namespace sdb {
 
@@ -123,6 +140,13 @@ struct LsArgs {
     uint64_t *qh;                   //   the length (< 0: nothing) and the filter hash
     // sdb_lsm_scan_projected only
     sdb_scan_ranges proj;           // per SST: SsTableView.visible_range, (UNBOUNDED, UNBOUNDED) = None
+    // sources: a pair is p = range * nsrc + source; without tables nsrc == t.num_ssts and spairs == pairs
+    uint32_t ntab, nsrc;            // tables; sources per range = ntab + t.num_ssts
+    uint64_t spairs;                // (range, SST) pairs
+    // sdb_lsm_scan_mem only
+    const sdb_run *tabs;            // device: the tables, sources 0 .. ntab - 1
+    sdb_mem_scan_out mout;
+    sdb_mem_chain_out mchain;
 };
 enum { kBase = 0x100 };  // a value or a tombstone ended the chain
 enum { kCtlFirstBad = 0, kCtlFailed, kCtlBad, kCtlGo1, kCtlGo2, kCtlGo3, kCtlMaxChain, kCtlFiltered, kCtlUniform, kCtlWords = 16 };
@@ -184,11 +208,13 @@ __global__ __launch_bounds__(256) void k_ls_ranges(LsArgs a) {
     a.qh[r] = pr.h;
 }
 
-// Thread t of the per-pair kernels: neighbouring ranges of one SST share a wave.
+// Thread t of the per-pair kernels: neighbouring ranges of one SST share a wave.  MEM: the call has memtables
+// (sdb_lsm_scan_mem): a range's table pairs stand before its SST pairs.
+template <bool MEM>
 SDB_DEV void ls_pair(const LsArgs &a, uint64_t t, uint64_t &r, uint32_t &i, uint64_t &p) {
     r = t % a.r.n;
     i = (uint32_t)(t / a.r.n);
-    p = r * a.t.num_ssts + i;
+    p = MEM ? r * a.nsrc + a.ntab + i : r * a.t.num_ssts + i;
 }
 
 // The view range of pair (r, SST i) (P3 of sdb_lsm_scan_projected; calculate_view_range, db_state.rs:243-251): range r
@@ -200,13 +226,13 @@ SDB_DEV void ls_view(const LsArgs &a, uint32_t i, Bound &s, Bound &e) {
 
 // FILTER: the call consults the filters (sdb_lsm_scan_filtered); the kernel exists once without the step, so the plain
 // scans keep their registers and occupancy.
-template <bool FILTER, bool PROJ>
+template <bool FILTER, bool PROJ, bool MEM = false>
 __global__ __launch_bounds__(256) void k_ls_locate(LsArgs a) {
     if (a.ctl[kCtlBad]) return;
-    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < a.pairs; t += (uint64_t)gridDim.x * blockDim.x) {
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < a.spairs; t += (uint64_t)gridDim.x * blockDim.x) {
         uint64_t r, p;
         uint32_t i;
-        ls_pair(a, t, r, i, p);
+        ls_pair<MEM>(a, t, r, i, p);
         Bound s = range_start(a.r, r), e = range_end(a.r, r);
         const sdb_sst_view v = a.t.ssts[i];
         const bool okind = !bad_kind(s, e);
@@ -282,13 +308,13 @@ SDB_DEV Clip ls_clip(const sdb_sst_view &v, uint64_t k, const Bound &s, const Bo
     return clip_block(v.sst_version, b, s, e);
 }
 
-template <bool PROJ>
+template <bool PROJ, bool MEM = false>
 __global__ __launch_bounds__(64) void k_ls_edge(LsArgs a) {
     const bool bad = a.ctl[kCtlBad] != 0;
-    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < a.pairs; t += (uint64_t)gridDim.x * blockDim.x) {
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < a.spairs; t += (uint64_t)gridDim.x * blockDim.x) {
         uint64_t r, p;
         uint32_t i;
-        ls_pair(a, t, r, i, p);
+        ls_pair<MEM>(a, t, r, i, p);
         int st = 0;
         uint32_t fb = 0;
         uint64_t g0 = 0, g1 = 0, k0 = 0, k1 = 0, items = 0;
@@ -356,28 +382,32 @@ __global__ __launch_bounds__(64) void k_ls_edge(LsArgs a) {
     }
 }
 
+template <bool MEM>
 __global__ __launch_bounds__(64) void k_ls_rstat(LsArgs a) {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= a.r.n) return;
-    const uint32_t S = a.t.num_ssts;
+    const uint32_t S = a.t.num_ssts, T = MEM ? a.ntab : 0, NS = S + T;
+    const uint64_t p0 = r * NS + T;  // the range's first SST pair
     int st = 0;
-    uint32_t ns = 0, nf = 0;
+    uint32_t ns = 0, nf = 0, nt = 0;
     if (a.ctl[kCtlBad]) {
         st = SDB_INVALID_ARGUMENT;
     } else if (bad_kind(range_start(a.r, r), range_end(a.r, r))) {
         st = SDB_INVALID_ARGUMENT;
     } else {
         for (uint32_t i = 0; i < S; i++) {
-            if (a.filter && a.filt[r * S + i]) nf++;
-            if (!a.part[r * S + i]) continue;
+            if (a.filter && a.filt[p0 + i]) nf++;
+            if (!a.part[p0 + i]) continue;
             ns++;
-            if (!st) st = a.pst[r * S + i];
+            if (!st) st = a.pst[p0 + i];
         }
+        for (uint32_t j = 0; j < T; j++) nt += a.part[r * NS + j];  // (k_ls_tprobe: the table holds a key of the range)
     }
     if (st)
-        for (uint32_t i = 0; i < S; i++) a.pn[r * S + i] = a.pkb[r * S + i] = a.pit[r * S + i] = 0;
+        for (uint32_t j = 0; j < NS; j++) a.pn[r * NS + j] = a.pkb[r * NS + j] = a.pit[r * NS + j] = 0;
     a.out.range_status[r] = st;
     a.out.range_ssts[r] = ns;
+    if (MEM) a.mout.range_tables[r] = nt;
     a.rop[r] = 0;
     if (a.filter) {
         a.fout.range_filtered[r] = nf;
@@ -400,13 +430,14 @@ __global__ __launch_bounds__(256) void k_ls_gate(LsArgs a) {
     }
 }
 
+template <bool MEM>
 __global__ __launch_bounds__(64) void k_ls_stage(LsArgs a) {
     if (!a.ctl[kCtlGo1]) return;
-    const uint32_t S = a.t.num_ssts;
+    const uint32_t S = MEM ? a.nsrc : a.t.num_ssts;
     const uint64_t total = a.pis[a.pairs];
     for (uint64_t it = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; it < total; it += (uint64_t)gridDim.x * blockDim.x) {
         const uint64_t p = last_le(a.pis, a.pairs, 1, it);
-        const uint32_t i = (uint32_t)(p % S);
+        const uint32_t i = (uint32_t)(p % S) - (MEM ? a.ntab : 0);  // (only SST pairs have items)
         const sdb_sst_view v = a.t.ssts[i];
         const uint64_t kl = a.fb[p] + (it - a.pis[p]), K = a.t.block_base[i] + kl;  // the block: in the SST, in the tree
         if (kl >= v.num_blocks) continue;
@@ -450,7 +481,7 @@ SDB_DEV bool ls_hides(const LsArgs &a, uint64_t q, uint64_t bound, const uint8_t
 
 __global__ __launch_bounds__(64) void k_ls_rank(LsArgs a) {
     if (!a.ctl[kCtlGo1]) return;
-    const uint32_t S = a.t.num_ssts;
+    const uint32_t S = a.nsrc;  // sources: the tables, then the SSTs
     const uint64_t total = a.cs[a.pairs];
     for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < total; c += (uint64_t)gridDim.x * blockDim.x) {
         const uint64_t p = last_le(a.cs, a.pairs, 1, c), r = p / S;
@@ -502,7 +533,7 @@ SDB_DEV uint64_t ls_chain_cand(const LsArgs &a, uint64_t rs, uint64_t re, uint64
 // key's first non-operand, the tombstone excluded (merge_with_older_entries, merge_operator.rs:388-411).  The
 // versions behind a winner are visible: they are older than it.
 __global__ __launch_bounds__(64) void k_ls_links(LsArgs a) {
-    const uint32_t S = a.t.num_ssts;
+    const uint32_t S = a.nsrc;
     const bool go = a.ctl[kCtlGo1] != 0;
     const uint64_t total = go ? a.cs[a.pairs] : 0;
     for (uint64_t m = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; m < a.cand_entries; m += (uint64_t)gridDim.x * blockDim.x) {
@@ -530,7 +561,7 @@ __global__ __launch_bounds__(64) void k_ls_links(LsArgs a) {
 // Where the links of the winner at merged position m of range r start: a range's rows descend with `desc`, a row's
 // links do not.
 SDB_DEV uint64_t ls_chain_start(const LsArgs &a, uint64_t r, uint64_t m) {
-    const uint32_t S = a.t.num_ssts;
+    const uint32_t S = a.nsrc;
     const uint64_t rs = a.cs[r * S], re = a.cs[(r + 1) * S];
     const uint64_t before = a.wlpos[m] - a.wlpos[rs], all = a.wlpos[re] - a.wlpos[rs];
     return a.wlpos[rs] + (a.desc ? all - before - a.wl[m] : before);
@@ -539,7 +570,7 @@ SDB_DEV uint64_t ls_chain_start(const LsArgs &a, uint64_t r, uint64_t m) {
 __global__ __launch_bounds__(64) void k_ls_count(LsArgs a) {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= a.r.n) return;
-    const uint32_t S = a.t.num_ssts;
+    const uint32_t S = a.nsrc;
     int st = a.out.range_status[r];
     uint64_t n = 0, kb = 0;
     if (a.ctl[kCtlGo1]) {
@@ -568,7 +599,7 @@ __global__ void k_ls_final(LsArgs a) {
     s.num_candidates = a.cs[a.pairs];
     s.candidate_key_bytes = a.cks[a.pairs];
     s.num_failed_ranges = a.ctl[kCtlFailed];
-    s.blocks_checked = a.pr[a.t.total_blocks];
+    s.blocks_checked = a.t.total_blocks ? a.pr[a.t.total_blocks] : 0;  // (S8: tables and no tree)
     s.status = a.ctl[kCtlFirstBad] == ~0ull ? 0 : (int32_t)(a.ctl[kCtlFirstBad] & 0xFF);
     const bool fits = a.ctl[kCtlGo1] && s.num_entries <= a.out.cap_entries && s.key_bytes <= a.out.key_arena_cap;
     if (!fits) s.status = SDB_LIMIT_EXCEEDED;
@@ -591,21 +622,29 @@ __global__ void k_ls_final(LsArgs a) {
 // sdb_lsm_scan_merge, thread per merged position that k_ls_links gave to a winner w: the row parsed, its timestamps
 // folded into w's aggregates (MergeTracker, merge_operator.rs:289-292; a tombstone base too, :421-425), and, unless it
 // is that tombstone, written as link (position - w) of w's chain where the links fit.
+template <bool MEM>
 __global__ __launch_bounds__(64) void k_ls_fold(LsArgs a) {
     if (!a.ctl[kCtlGo2]) return;
-    const uint32_t S = a.t.num_ssts;
+    const uint32_t S = a.nsrc, T = MEM ? a.ntab : 0;
     const bool put = a.ctl[kCtlGo3] != 0;
     const uint64_t total = a.cs[a.pairs];
     for (uint64_t m = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; m < total; m += (uint64_t)gridDim.x * blockDim.x) {
         const uint64_t w = a.lwin[m];
         if (w == ~0ull) continue;
         const uint64_t c = a.morder[m];
-        const uint32_t i = (uint32_t)(last_le(a.cs, a.pairs, 1, c) % S);
-        const sdb_sst_view v = a.t.ssts[i];
-        Blk b;
+        const uint32_t j = (uint32_t)(last_le(a.cs, a.pairs, 1, c) % S);
+        const bool tab = MEM && j < T;  // the link lies in a table: its columns are the table's, no block is opened
+        uint64_t base;
         Row lr;
-        if (blk_open(v, a.cblk[c], b)) continue;
-        if (v.sst_version == 2 ? v2_row(b, a.cat[c], lr) : v1_row(b, a.cat[c], lr)) continue;
+        if (tab) {
+            lr = tab_row(a.tabs[j], a.cat[c], base);
+        } else {
+            const sdb_sst_view v = a.t.ssts[j - T];
+            Blk b;
+            if (blk_open(v, a.cblk[c], b)) continue;
+            if (v.sst_version == 2 ? v2_row(b, a.cat[c], lr) : v1_row(b, a.cat[c], lr)) continue;
+            base = b.base;
+        }
         if (lr.flags & SDB_FLAG_HAS_CREATE_TS) atomicMax(&a.wcts[w], (long long)lr.cts);
         if (lr.flags & SDB_FLAG_HAS_EXPIRE_TS) atomicMin(&a.wets[w], (long long)lr.ets);
         const uint32_t has = (lr.flags & (SDB_FLAG_HAS_CREATE_TS | SDB_FLAG_HAS_EXPIRE_TS)) |
@@ -614,15 +653,20 @@ __global__ __launch_bounds__(64) void k_ls_fold(LsArgs a) {
         if ((lr.flags & SDB_FLAG_TOMBSTONE) || !put) continue;
         const uint64_t x = m - w, d = ls_chain_start(a, last_le(a.cs, a.r.n, S, w), w) + x;
         if (x >= a.wl[w] || d >= a.chain.cap_links) continue;  // never out of the winner's slots
-        a.chain.sst[d] = i;
-        a.chain.block[d] = a.cblk[c];
-        put_row(a.chain, d, b.base, lr);
+        a.chain.sst[d] = tab ? 0xFFFFFFFFu : j - T;
+        a.chain.block[d] = tab ? 0 : a.cblk[c];
+        put_row(a.chain, d, base, lr);
+        if (MEM) {
+            a.mchain.table[d] = tab ? j : 0xFFFFFFFFu;
+            a.mchain.row[d] = tab ? a.cat[c] : 0;
+        }
     }
 }
 
+template <bool MEM>
 __global__ __launch_bounds__(64) void k_ls_emit(LsArgs a) {
     if (!a.ctl[kCtlGo2]) return;
-    const uint32_t S = a.t.num_ssts;
+    const uint32_t S = a.nsrc, T = MEM ? a.ntab : 0;
     const uint64_t total = a.cs[a.pairs];
     for (uint64_t m = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; m < total; m += (uint64_t)gridDim.x * blockDim.x) {
         if (!a.wn[m]) continue;
@@ -634,15 +678,26 @@ __global__ __launch_bounds__(64) void k_ls_emit(LsArgs a) {
         const uint32_t L = a.cklen[c];
         if (x >= N || kx > KB || L > KB - kx) continue;
         const uint64_t di = a.desc ? N - 1 - x : x, dk = a.desc ? KB - kx - L : kx;
-        const uint32_t i = (uint32_t)(last_le(a.cs, a.pairs, 1, c) % S);
-        const sdb_sst_view v = a.t.ssts[i];
-        Blk b;
+        const uint32_t j = (uint32_t)(last_le(a.cs, a.pairs, 1, c) % S);
+        const bool tab = MEM && j < T;  // a table won the row (S3)
+        uint64_t base;
         Row row;
-        if (blk_open(v, a.cblk[c], b)) continue;
-        if (v.sst_version == 2 ? v2_row(b, a.cat[c], row) : v1_row(b, a.cat[c], row)) continue;
+        if (tab) {
+            row = tab_row(a.tabs[j], a.cat[c], base);
+        } else {
+            const sdb_sst_view v = a.t.ssts[j - T];
+            Blk b;
+            if (blk_open(v, a.cblk[c], b)) continue;
+            if (v.sst_version == 2 ? v2_row(b, a.cat[c], row) : v1_row(b, a.cat[c], row)) continue;
+            base = b.base;
+        }
         copy_bytes(a.out.key_arena + K0 + dk, a.ckeys + a.ckoff[c], L);
         a.out.key_off[E0 + di] = K0 + dk;
-        a.out.sst[E0 + di] = i;
+        a.out.sst[E0 + di] = tab ? 0xFFFFFFFFu : j - T;
+        if (MEM) {
+            a.mout.table[E0 + di] = tab ? j : 0xFFFFFFFFu;
+            a.mout.row[E0 + di] = tab ? a.cat[c] : 0;
+        }
         if (a.merge) {  // the entry MergeOperatorIterator returns (merge_operator.rs:437-447): k_ls_fold's aggregates
             a.chain.chain_start[E0 + di] = ls_chain_start(a, r, m);
             const uint32_t has = a.whas[m];
@@ -650,14 +705,135 @@ __global__ __launch_bounds__(64) void k_ls_emit(LsArgs a) {
             row.cts = a.wcts[m];
             row.ets = a.wets[m];
         }
-        put_row(a.out, E0 + di, b.base, row);
+        put_row(a.out, E0 + di, base, row);
     }
 }
+
+// =================================================================================================
+// sdb_lsm_scan_mem: the table sources
+// =================================================================================================
+
+// Per tree block: not marked, not read: launch_lsm_scan's two memsets as a kernel (under HIP graph replay memset nodes
+// ahead of a captured call's kernels were seen not to take effect: k_mem_reset of sdb_get.hip).
+__global__ __launch_bounds__(256) void k_ls_mreset(uint8_t *mark, int32_t *bstat, uint64_t tb) {
+    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < tb; k += (uint64_t)gridDim.x * blockDim.x) {
+        mark[k] = 0;
+        bstat[k] = -1;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_ls_tvalidate(LsArgs a) {  // after k_ls_validate: it may only add to kCtlBad
+    int bad = 0;
+    for (uint32_t j = threadIdx.x; j < a.ntab; j += blockDim.x) bad |= tab_malformed(a.tabs[j]);
+    bad = __syncthreads_or(bad);
+    if (threadIdx.x == 0 && bad) a.ctl[kCtlBad] = 1ull;
+}
+
+// The first row of T whose key is >= k, or > k with `after`: a lower bound in the table's order, where every
+// version of a key stands together.
+SDB_DEV uint64_t tab_bound(const sdb_run &T, const Key &k, bool after) {
+    uint64_t lo = 0, hi = T.n;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        const int c = tab_cmp(T, mid, k);
+        if (c < 0 || (after && c == 0)) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// S2, thread per (range, table) pair, t = table * n + range so that a wave holds neighbouring ranges of one table:
+// the stretch [g0, g1) of the rows whose key the range contains, into the slots k_ls_edge fills for an SST pair.
+// `part` here: the table holds a key of the range (range_tables).
+__global__ __launch_bounds__(256) void k_ls_tprobe(LsArgs a) {
+    const bool bad = a.ctl[kCtlBad] != 0;
+    const uint64_t total = a.r.n * a.ntab;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t r = t % a.r.n;
+        const uint32_t j = (uint32_t)(t / a.r.n);
+        const uint64_t p = r * a.nsrc + j;
+        uint64_t g0 = 0, g1 = 0, k0 = 0, kb = 0;
+        if (!bad) {  // (a malformed call reads nothing through the tables)
+            const sdb_run T = a.tabs[j];
+            const Bound s = range_start(a.r, r), e = range_end(a.r, r);
+            if (T.n && !bad_kind(s, e) && !empty_as_set(s, e)) {
+                g0 = s.kind ? tab_bound(T, Key{s.t, s.n}, s.kind == SDB_BOUND_EXCLUDED) : 0;
+                g1 = e.kind ? tab_bound(T, Key{e.t, e.n}, e.kind == SDB_BOUND_INCLUDED) : T.n;
+                if (g1 < g0) g1 = g0;  // rows that are not sorted
+                k0 = T.key_off[g0];
+                const uint64_t k1 = T.key_off[g1];
+                if (k1 < k0) g1 = g0;  // offsets that descend
+                else kb = k1 - k0;
+            }
+        }
+        a.part[p] = g1 > g0;
+        a.bs[p] = a.be[p] = a.fb[p] = 0;
+        a.pst[p] = 0;
+        a.g0[p] = g0;
+        a.g1[p] = g1;
+        a.k0[p] = k0;
+        a.pn[p] = g1 - g0;
+        a.pkb[p] = g1 > g0 ? kb : 0;
+        a.pit[p] = 0;  // no block items: k_ls_trows stages a table pair
+    }
+}
+
+// Thread per staged candidate; one of a table pair gets its words from the table's columns, read along the rows: its
+// length, seq, flags and the row (cat), and its key, copied to its place in the pair's span of the staging arena.  A
+// pair's key bytes are one span key_arena[k0, k0 + bytes) of its table and neighbouring threads copy neighbouring keys,
+// so the copy is coalesced as it stands: a separate span copy of 16 bytes a lane was measured and was not faster
+// (DESIGN.md, round 15).
+__global__ __launch_bounds__(256) void k_ls_trows(LsArgs a) {
+    if (!a.ctl[kCtlGo1]) return;
+    const uint64_t total = a.cs[a.pairs];
+    for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < total; c += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t p = last_le(a.cs, a.pairs, 1, c);
+        const uint32_t j = (uint32_t)(p % a.nsrc);
+        if (j >= a.ntab) continue;  // an SST's: k_ls_stage
+        const uint64_t i = a.g0[p] + (c - a.cs[p]), span = a.cks[p + 1] - a.cks[p];
+        if (i >= a.g1[p]) continue;
+        const sdb_run T = a.tabs[j];
+        const uint64_t o0 = T.key_off[i], o1 = T.key_off[i + 1];
+        uint64_t o = o0 - a.k0[p], L = o1 - o0;
+        if (o0 < a.k0[p] || o1 < o0 || o > span || L > span - o) o = L = 0;  // offsets that descend: never out of the pair's slots
+        copy_bytes(a.ckeys + a.cks[p] + o, T.key_arena + o0, (uint32_t)L);
+        a.ckoff[c] = a.cks[p] + o;
+        a.cklen[c] = (uint32_t)L;
+        a.cblk[c] = 0;
+        a.cat[c] = (uint32_t)i;
+        a.cseq[c] = T.seq[i];
+        a.cflags[c] = T.flags[i];
+    }
+}
+
+// Nothing a call without tables wrote lies in a table (S7): the rows' and the links' table columns, where the row
+// and the link columns were written, and range_tables.
+__global__ __launch_bounds__(256) void k_ls_mfill(sdb_lsm_scan_out out, sdb_mem_scan_out mout, uint64_t n, sdb_chain_summary *csum,
+                                                  uint64_t cap_links, sdb_mem_chain_out mchain) {
+    const uint64_t t0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t r = t0; r < n; r += step) mout.range_tables[r] = 0;
+    const sdb_lsm_scan_summary s = *out.summary;
+    const uint64_t ne = s.status == SDB_LIMIT_EXCEEDED ? 0 : (s.num_entries < out.cap_entries ? s.num_entries : out.cap_entries);
+    for (uint64_t x = t0; x < ne; x += step) {
+        mout.table[x] = 0xFFFFFFFFu;
+        mout.row[x] = 0;
+    }
+    if (!csum) return;
+    const sdb_chain_summary c = *csum;
+    const uint64_t nl = c.status != SDB_OK ? 0 : (c.num_links < cap_links ? c.num_links : cap_links);
+    for (uint64_t d = t0; d < nl; d += step) {
+        mchain.table[d] = 0xFFFFFFFFu;
+        mchain.row[d] = 0;
+    }
+}
+
 
 // The workspace arrays of a scan of a.r.n ranges over the tree a.t with room for a.cand_entries candidates of
 // a.cand_key_bytes key bytes, bound into a from w; -> their size.
 static uint64_t lsm_scan_bind(LsArgs &a, uint8_t *w) {
-    const uint64_t tb = a.t.total_blocks, n = a.r.n, P = n * a.t.num_ssts, ce = a.cand_entries;
+    a.nsrc = a.t.num_ssts + a.ntab;  // (range, source) pairs: the tables' stand before the SSTs'
+    a.spairs = a.r.n * a.t.num_ssts;
+    const uint64_t tb = a.t.total_blocks, n = a.r.n, P = n * a.nsrc, ce = a.cand_entries;
     uint64_t big = tb > n ? tb : n;
     if (P > big) big = P;
     if (ce > big) big = ce;
@@ -733,6 +909,18 @@ static uint64_t lsm_scan_filter_bind(LsArgs &a, uint8_t *w, bool merge) {
     return c.off;
 }
 
+uint64_t lsm_scan_mem_workspace_bytes(uint32_t num_tables, uint64_t total_blocks, uint32_t num_ssts, uint64_t nranges,
+                                      uint64_t cand_entries, uint64_t cand_key_bytes, bool merge) {
+    LsArgs a{};
+    a.t.total_blocks = total_blocks;
+    a.t.num_ssts = num_ssts;
+    a.ntab = num_tables;
+    a.r.n = nranges;
+    a.cand_entries = cand_entries;
+    a.cand_key_bytes = cand_key_bytes;
+    return lsm_scan_filter_bind(a, nullptr, merge);  // the pairs count the tables; no array of its own
+}
+
 uint64_t lsm_scan_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint64_t nranges, uint64_t cand_entries,
                                   uint64_t cand_key_bytes, bool merge, bool filter) {
     LsArgs a{};
@@ -745,16 +933,18 @@ uint64_t lsm_scan_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint
     return merge ? lsm_scan_merge_bind(a, nullptr) : lsm_scan_bind(a, nullptr);
 }
 
-hipError_t launch_lsm_scan(const sdb_lsm_view &t, const sdb_scan_ranges &r, const uint64_t *max_seq, uint32_t desc,
-                           uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out &out,
-                           const sdb_chain_out *chain /* sdb_lsm_scan_merge, else nullptr */,
-                           const sdb_filter_policy *pol, const sdb_scan_prefixes *px,
-                           const sdb_scan_filter_out *fout /* sdb_lsm_scan_filtered, else nullptr */,
-                           const sdb_scan_ranges *proj /* sdb_lsm_scan_projected (with fout), else nullptr */, uint8_t *w,
-                           hipStream_t st) {
-    const uint64_t tb = t.total_blocks, n = r.n;
+// mem (with mout, and mchain iff chain; fout given): sdb_lsm_scan_mem's tables, at least one, and n > 0; else nullptr
+static hipError_t launch_lsm_scan_layers(const sdb_mem_view *mem, const sdb_lsm_view &t, const sdb_scan_ranges &r,
+                                         const uint64_t *max_seq, uint32_t desc, uint64_t cand_entries,
+                                         uint64_t cand_key_bytes, const sdb_lsm_scan_out &out, const sdb_mem_scan_out *mout,
+                                         const sdb_chain_out *chain, const sdb_mem_chain_out *mchain,
+                                         const sdb_filter_policy *pol, const sdb_scan_prefixes *px,
+                                         const sdb_scan_filter_out *fout, const sdb_scan_ranges *proj, uint8_t *w,
+                                         hipStream_t st) {
+    const uint64_t n = r.n;
+    const bool no_tree = t.num_ssts == 0 || t.total_blocks == 0 || (mem && t.num_runs == 0);
     hipError_t e;
-    if (n == 0 || t.num_ssts == 0 || tb == 0) {  // every range is empty
+    if (n == 0 || (no_tree && !mem)) {  // every range is empty
         if (chain) {
             if ((e = hipMemsetAsync(chain->summary, 0, sizeof(sdb_chain_summary), st)) != hipSuccess) return e;
             if ((e = hipMemsetAsync(chain->chain_start, 0, 8, st)) != hipSuccess) return e;
@@ -779,6 +969,18 @@ hipError_t launch_lsm_scan(const sdb_lsm_view &t, const sdb_scan_ranges &r, cons
         a.merge = 1;
         a.chain = *chain;
     }
+    if (mem) {
+        a.tabs = mem->tables;
+        a.ntab = mem->num_tables;
+        a.mout = *mout;
+        if (chain) a.mchain = *mchain;
+        if (no_tree) {  // (S8) only the tables are scanned, and nothing is read through the tree's arrays
+            a.t.num_ssts = a.t.num_runs = 0;
+            a.t.total_blocks = 0;
+            pol = nullptr;
+            proj = nullptr;
+        }
+    }
     if (fout) {
         a.filter = 1;
         a.pol = pol;
@@ -791,29 +993,47 @@ hipError_t launch_lsm_scan(const sdb_lsm_view &t, const sdb_scan_ranges &r, cons
     } else {
         lsm_scan_bind(a, w);
     }
-    const uint64_t P = a.pairs, ce = cand_entries;
-    if ((e = hipMemsetAsync(a.mark, 0, tb, st)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(a.bstat, 0xFF, 4 * tb, st)) != hipSuccess) return e;
+    const uint64_t tb = a.t.total_blocks, P = a.pairs, SP = a.spairs, ce = cand_entries;
+    const bool tree = !no_tree;
+    if (mem) {
+        if (tree) hipLaunchKernelGGL(k_ls_mreset, dim3(scan_grid(tb, 256)), dim3(256), 0, st, a.mark, a.bstat, tb);
+    } else {
+        if ((e = hipMemsetAsync(a.mark, 0, tb, st)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(a.bstat, 0xFF, 4 * tb, st)) != hipSuccess) return e;
+    }
     const uint32_t rw = (uint32_t)((n + 63) / 64);
     const bool pj = a.filter && proj;
     if (pj) hipLaunchKernelGGL(k_ls_validate<true>, dim3(1), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(k_ls_validate<false>, dim3(1), dim3(256), 0, st, a);
+    if (mem) hipLaunchKernelGGL(k_ls_tvalidate, dim3(1), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_ls_ranges, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, a);
-    if (pj) hipLaunchKernelGGL((k_ls_locate<true, true>), dim3(scan_grid(P, 256)), dim3(256), 0, st, a);
-    else if (a.filter) hipLaunchKernelGGL((k_ls_locate<true, false>), dim3(scan_grid(P, 256)), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((k_ls_locate<false, false>), dim3(scan_grid(P, 256)), dim3(256), 0, st, a);
-    if ((e = launch_check(CheckArgs{{}, t, (const uint32_t *)(a.ctl + kCtlBad), tb, a.mark, a.bstat}, st)) != hipSuccess) return e;
-    // the per-block, per-pair and per-item walks are latency-bound threads: one wave per workgroup spreads them over the CUs
-    hipLaunchKernelGGL(k_ls_block, dim3((uint32_t)((tb + 63) / 64)), dim3(64), 0, st, a);
-    if ((e = launch_excl_scan2(a.cnt, a.kb, tb, a.tx, a.ty, a.pc, a.pk, st)) != hipSuccess) return e;
-    if ((e = launch_excl_scan2(a.bbad, a.rd, tb, a.tx, a.ty, a.pb, a.pr, st)) != hipSuccess) return e;
-    if (pj) hipLaunchKernelGGL(k_ls_edge<true>, dim3(scan_grid(P, 64)), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL(k_ls_edge<false>, dim3(scan_grid(P, 64)), dim3(64), 0, st, a);
-    hipLaunchKernelGGL(k_ls_rstat, dim3(rw), dim3(64), 0, st, a);
+    if (mem) hipLaunchKernelGGL(k_ls_tprobe, dim3(scan_grid(n * a.ntab, 256)), dim3(256), 0, st, a);
+    if (tree) {
+        if (mem && pj) hipLaunchKernelGGL((k_ls_locate<true, true, true>), dim3(scan_grid(SP, 256)), dim3(256), 0, st, a);
+        else if (mem) hipLaunchKernelGGL((k_ls_locate<true, false, true>), dim3(scan_grid(SP, 256)), dim3(256), 0, st, a);
+        else if (pj) hipLaunchKernelGGL((k_ls_locate<true, true>), dim3(scan_grid(SP, 256)), dim3(256), 0, st, a);
+        else if (a.filter) hipLaunchKernelGGL((k_ls_locate<true, false>), dim3(scan_grid(SP, 256)), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((k_ls_locate<false, false>), dim3(scan_grid(SP, 256)), dim3(256), 0, st, a);
+        if ((e = launch_check(CheckArgs{{}, a.t, (const uint32_t *)(a.ctl + kCtlBad), tb, a.mark, a.bstat}, st)) != hipSuccess) return e;
+        // the per-block, per-pair and per-item walks are latency-bound threads: one wave per workgroup spreads them over the CUs
+        hipLaunchKernelGGL(k_ls_block, dim3((uint32_t)((tb + 63) / 64)), dim3(64), 0, st, a);
+        if ((e = launch_excl_scan2(a.cnt, a.kb, tb, a.tx, a.ty, a.pc, a.pk, st)) != hipSuccess) return e;
+        if ((e = launch_excl_scan2(a.bbad, a.rd, tb, a.tx, a.ty, a.pb, a.pr, st)) != hipSuccess) return e;
+        if (mem && pj) hipLaunchKernelGGL((k_ls_edge<true, true>), dim3(scan_grid(SP, 64)), dim3(64), 0, st, a);
+        else if (mem) hipLaunchKernelGGL((k_ls_edge<false, true>), dim3(scan_grid(SP, 64)), dim3(64), 0, st, a);
+        else if (pj) hipLaunchKernelGGL(k_ls_edge<true>, dim3(scan_grid(SP, 64)), dim3(64), 0, st, a);
+        else hipLaunchKernelGGL(k_ls_edge<false>, dim3(scan_grid(SP, 64)), dim3(64), 0, st, a);
+    }
+    if (mem) hipLaunchKernelGGL(k_ls_rstat<true>, dim3(rw), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL(k_ls_rstat<false>, dim3(rw), dim3(64), 0, st, a);
     if ((e = launch_excl_scan2(a.pit, a.pit, P, a.tx, a.ty, a.pis, a.cs, st)) != hipSuccess) return e;
     if ((e = launch_excl_scan2(a.pn, a.pkb, P, a.tx, a.ty, a.cs, a.cks, st)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_ls_gate, dim3(scan_grid(ce, 256)), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_ls_stage, dim3(scan_grid(ce + P, 64)), dim3(64), 0, st, a);
+    if (tree && mem) hipLaunchKernelGGL(k_ls_stage<true>, dim3(scan_grid(ce + P, 64)), dim3(64), 0, st, a);
+    else if (tree) hipLaunchKernelGGL(k_ls_stage<false>, dim3(scan_grid(ce + P, 64)), dim3(64), 0, st, a);
+    if (mem) {
+        hipLaunchKernelGGL(k_ls_trows, dim3(scan_grid(ce, 256)), dim3(256), 0, st, a);
+    }
     hipLaunchKernelGGL(k_ls_rank, dim3(scan_grid(ce, 64)), dim3(64), 0, st, a);
     if (chain) {
         hipLaunchKernelGGL(k_ls_links, dim3(scan_grid(ce, 64)), dim3(64), 0, st, a);
@@ -823,8 +1043,41 @@ hipError_t launch_lsm_scan(const sdb_lsm_view &t, const sdb_scan_ranges &r, cons
     hipLaunchKernelGGL(k_ls_count, dim3(rw), dim3(64), 0, st, a);
     if ((e = launch_excl_scan2(a.rn, a.rkb, n, a.tx, a.ty, out.range_entry_start, a.rks, st)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_ls_final, dim3(1), dim3(64), 0, st, a);
-    if (chain) hipLaunchKernelGGL(k_ls_fold, dim3(scan_grid(ce, 64)), dim3(64), 0, st, a);
-    hipLaunchKernelGGL(k_ls_emit, dim3(scan_grid(ce, 64)), dim3(64), 0, st, a);
+    if (chain && mem) hipLaunchKernelGGL(k_ls_fold<true>, dim3(scan_grid(ce, 64)), dim3(64), 0, st, a);
+    else if (chain) hipLaunchKernelGGL(k_ls_fold<false>, dim3(scan_grid(ce, 64)), dim3(64), 0, st, a);
+    if (mem) hipLaunchKernelGGL(k_ls_emit<true>, dim3(scan_grid(ce, 64)), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL(k_ls_emit<false>, dim3(scan_grid(ce, 64)), dim3(64), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_lsm_scan(const sdb_lsm_view &t, const sdb_scan_ranges &r, const uint64_t *max_seq, uint32_t desc,
+                           uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out &out,
+                           const sdb_chain_out *chain /* sdb_lsm_scan_merge, else nullptr */,
+                           const sdb_filter_policy *pol, const sdb_scan_prefixes *px,
+                           const sdb_scan_filter_out *fout /* sdb_lsm_scan_filtered, else nullptr */,
+                           const sdb_scan_ranges *proj /* sdb_lsm_scan_projected (with fout), else nullptr */, uint8_t *w,
+                           hipStream_t st) {
+    return launch_lsm_scan_layers(nullptr, t, r, max_seq, desc, cand_entries, cand_key_bytes, out, nullptr, chain, nullptr, pol,
+                                  px, fout, proj, w, st);
+}
+
+hipError_t launch_lsm_scan_mem(const sdb_mem_view *mem, const sdb_lsm_view &t, const sdb_scan_ranges &r,
+                               const uint64_t *max_seq, uint32_t desc, uint64_t cand_entries, uint64_t cand_key_bytes,
+                               const sdb_lsm_scan_out &out, const sdb_mem_scan_out &mout, const sdb_chain_out *chain,
+                               const sdb_mem_chain_out *mchain, const sdb_filter_policy *pol, const sdb_scan_prefixes *px,
+                               const sdb_scan_filter_out &fout, const sdb_scan_ranges *proj, uint8_t *w, hipStream_t st) {
+    if (mem && mem->num_tables && r.n)
+        return launch_lsm_scan_layers(mem, t, r, max_seq, desc, cand_entries, cand_key_bytes, out, &mout, chain, mchain, pol, px,
+                                      &fout, proj, w, st);
+    // (S7) no tables: the projected call, and no row, link or range names a table
+    hipError_t e = launch_lsm_scan(t, r, max_seq, desc, cand_entries, cand_key_bytes, out, chain, pol, px, &fout, proj, w, st);
+    if (e != hipSuccess) return e;
+    uint64_t most = std::max(r.n, out.cap_entries);
+    if (chain) most = std::max(most, chain->cap_links);
+    if (most)
+        hipLaunchKernelGGL(k_ls_mfill, dim3(scan_grid(most, 256)), dim3(256), 0, st, out, mout, r.n,
+                           chain ? chain->summary : nullptr, chain ? chain->cap_links : 0,
+                           chain ? *mchain : sdb_mem_chain_out{nullptr, nullptr});
     return hipGetLastError();
 }
 

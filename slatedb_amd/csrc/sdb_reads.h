@@ -43,4 +43,14 @@ hipError_t launch_lsm_scan(const sdb_lsm_view &t, const sdb_scan_ranges &r, cons
                            const sdb_chain_out *chain, const sdb_filter_policy *pol, const sdb_scan_prefixes *px,
                            const sdb_scan_filter_out *fout, const sdb_scan_ranges *proj, uint8_t *w, hipStream_t st);
 
+// sdb_lsm_scan_mem: the projected launch_lsm_scan with the memtables `mem` (NULL or num_tables == 0: none) merged
+// ahead of the tree; mchain iff chain.  num_tables == 0 sizes exactly lsm_scan_workspace_bytes(..., filter = true).
+uint64_t lsm_scan_mem_workspace_bytes(uint32_t num_tables, uint64_t total_blocks, uint32_t num_ssts, uint64_t nranges,
+                                      uint64_t cand_entries, uint64_t cand_key_bytes, bool merge);
+hipError_t launch_lsm_scan_mem(const sdb_mem_view *mem, const sdb_lsm_view &t, const sdb_scan_ranges &r,
+                               const uint64_t *max_seq, uint32_t desc, uint64_t cand_entries, uint64_t cand_key_bytes,
+                               const sdb_lsm_scan_out &out, const sdb_mem_scan_out &mout, const sdb_chain_out *chain,
+                               const sdb_mem_chain_out *mchain, const sdb_filter_policy *pol, const sdb_scan_prefixes *px,
+                               const sdb_scan_filter_out &fout, const sdb_scan_ranges *proj, uint8_t *w, hipStream_t st);
+
 }  // namespace sdb

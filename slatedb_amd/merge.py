@@ -77,3 +77,15 @@ def fold_chains_mem(keys, res, table_vals, sst_data, operator):
                 base = v
         out.append(fold(key, vals, base, operator))
     return out
+
+
+def fold_scan_mem(res, table_vals, sst_data, operator):
+    """fold_chains_mem over the rows of a scan over memtables and the tree (lsm_scan_mem_device with merge=True): the
+    items are the output rows, keyed by their own keys (key_arena / key_off; summary[0] = num_entries), and a chain
+    may run through tables and into the tree.  res: a host copy of the result.  Returns [(key, merged bytes)] in
+    output order."""
+    n = int(np.asarray(res["summary"])[0])
+    ko = np.asarray(res["key_off"]).astype(np.int64)
+    ka = np.asarray(res["key_arena"])
+    keys = [ka[int(ko[i]):int(ko[i + 1])].tobytes() for i in range(n)]
+    return list(zip(keys, fold_chains_mem(keys, res, table_vals, sst_data, operator)))

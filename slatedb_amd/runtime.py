@@ -963,7 +963,7 @@ def _lsm_scan_out(res, cap_e, cap_k, dev):
 
 
 def _lsm_scan(entry, tree, ranges, max_seq, descending, stream, workspace, cand, cap, merge=False, cap_links=None, fill=0,
-              filtered=False, prefixes=None, probe_len=None, projected=False, projections=None):
+              filtered=False, prefixes=None, probe_len=None, projected=False, projections=None, mem=None):
     """The tree scans.  entry: the C entry point (sdb_lsm_scan, sdb_lsm_scan_merge, sdb_lsm_scan_filtered or
     sdb_lsm_scan_projected; its sizer is entry + "_workspace_bytes"); filtered: it takes the policies, the prefixes, an
     optional chain and the filter outputs; projected: it is a filtered call that takes the projections too; merge: the
@@ -971,9 +971,12 @@ def _lsm_scan(entry, tree, ranges, max_seq, descending, stream, workspace, cand,
     result dict; a caller's workspace that is too small is replaced by a fresh one, unless cand was given.
     With a capacity None (cap_links counts only with merge) the call runs once, and on SDB_LIMIT_EXCEEDED again
     with the staging at max(given, reported), cap like the staging and cap_links like cand_entries where those
-    were None."""
+    were None.  mem: the entry is sdb_lsm_scan_mem: None (a NULL sdb_mem_view) or what mem_tables_device returned; the
+    result then has table and row per output row (MEM_FIELDS), range_tables and, with a chain, chain_table and
+    chain_row."""
     import torch
     dev = tree["device"]
+    layers = entry == "sdb_lsm_scan_mem"
     if isinstance(ranges, dict):
         rt, n = ranges, int(ranges["n"])
     else:
@@ -998,9 +1001,12 @@ def _lsm_scan(entry, tree, ranges, max_seq, descending, stream, workspace, cand,
         res["num_filtered"] = torch.zeros(1, dtype=torch.int64, device=dev)
         fout = _abi.ScanFilterOut(res["range_filtered"].data_ptr(), res["num_filtered"].data_ptr())
     pjt, pj = _projections(projections, tree)
+    if layers:
+        res["range_tables"] = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
 
     def run(ce, ckb, cap_e, cap_k, cap_l):
-        wsb = getattr(lib(), entry + "_workspace_bytes")(tree["total_blocks"], tree["num_ssts"], tree["num_runs"], n, ce,
+        wsb = getattr(lib(), entry + "_workspace_bytes")(*([mem["num_tables"] if mem else 0] if layers else []),
+                                                         tree["total_blocks"], tree["num_ssts"], tree["num_runs"], n, ce,
                                                          ckb, *([int(bool(merge))] if filtered else []))
         ws = workspace if workspace is not None and workspace.numel() >= wsb else None
         if ws is None:
@@ -1008,11 +1014,19 @@ def _lsm_scan(entry, tree, ranges, max_seq, descending, stream, workspace, cand,
             ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
         out = _lsm_scan_out(res, cap_e, cap_k, dev)
         chain = _chain_out(res, cap_e, cap_l, dev, fill) if merge else None
-        args = [C.byref(tree["lsm"])] + ([C.byref(pj) if pj is not None else None] if projected else [])
+        args = [C.byref(mem["mem"]) if mem else None] if layers else []
+        args += [C.byref(tree["lsm"])] + ([C.byref(pj) if pj is not None else None] if projected else [])
         args += ([_ptr(tree.get("_policies"))] if filtered else []) + [C.byref(rg)]
         args += ([C.byref(px) if px is not None else None] if filtered else [])
         args += [_ptr(max_seq), int(bool(descending)), ce, ckb, C.byref(out)]
-        args += ([C.byref(chain) if merge else None] if merge or filtered else []) + ([C.byref(fout)] if filtered else [])
+        if layers:  # (rows that no call writes name no table)
+            res["table"] = torch.full((max(cap_e, 1),), -1, dtype=torch.int32, device=dev)
+            res["row"] = torch.zeros(max(cap_e, 1), dtype=torch.int64, device=dev)
+            args += [C.byref(_abi.MemScanOut(res["table"].data_ptr(), res["row"].data_ptr(), res["range_tables"].data_ptr()))]
+        args += ([C.byref(chain) if merge else None] if merge or filtered else [])
+        if layers:
+            args += [C.byref(_mem_chain_out(res, cap_l, dev, fill)) if merge else None]
+        args += [C.byref(fout)] if filtered else []
         st = getattr(lib(), entry)(*args, ws.data_ptr(), wsb, _sp(stream))
         if st:
             raise SdbError(st, entry)
@@ -1028,7 +1042,7 @@ def _lsm_scan(entry, tree, ranges, max_seq, descending, stream, workspace, cand,
             run(ce, ckb, *(cap if cap is not None else (ce, ckb)), cap_links if cap_links is not None else ce)
     else:
         run(cand[0], cand[1], cap[0], cap[1], cap_links or 0)
-    res.update(_tree=tree, _ranges=rt, _max_seq=max_seq, _prefixes=pt, _projections=pjt)
+    res.update(_tree=tree, _ranges=rt, _max_seq=max_seq, _prefixes=pt, _projections=pjt, _mem=mem)
     return res
 
 
@@ -1177,6 +1191,20 @@ def lsm_get_mem_device(tables, views, runs, keys, max_seq=None, projections=None
     return _lsm_get("sdb_lsm_get_mem", views, runs, keys, max_seq, stream, workspace, merge=bool(merge),
                     cap_links=cap_links, fill=fill, filtered=True, probe_len=probe_len, projected=True,
                     projections=projections, mem=mem)
+
+
+def lsm_scan_mem_device(tables, tree, ranges, projections=None, prefixes=None, probe_len=None, max_seq=None,
+                        descending=False, stream=None, workspace=None, cand=None, cap=None, cap_links=None, fill=0,
+                        merge=False):
+    """sdb_lsm_scan_mem: lsm_scan_projected_device with device memtables merged ahead of the tree.  tables: None (a
+    NULL sdb_mem_view), a list of DeviceRuns in search order, or what mem_tables_device returned; tree: what
+    lsm_tree_device built (a tree without SSTs is scanned too: the tables alone).  The other arguments, the retry once
+    on SDB_LIMIT_EXCEEDED and the result are lsm_scan_projected_device's, plus table and row per output row (table -1:
+    an SST holds the row), range_tables (n) and, with merge, chain_table and chain_row per link."""
+    mem = tables if tables is None or isinstance(tables, dict) else mem_tables_device(tables, tree["device"])
+    return _lsm_scan("sdb_lsm_scan_mem", tree, ranges, max_seq, descending, stream, workspace, cand, cap,
+                     merge=bool(merge), cap_links=cap_links, fill=fill, filtered=True, prefixes=prefixes,
+                     probe_len=probe_len, projected=True, projections=projections, mem=mem)
 
 
 # ------------------------------------------------------------------------------------------------
