@@ -615,10 +615,6 @@ sdb_status sdb_sst_scan(const sdb_sst_view *sst, const sdb_scan_ranges *ranges, 
     return SDB_OK;
 }
 
-uint64_t sdb_lsm_get_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys) {
-    return get_workspace_bytes(total_blocks, num_ssts, num_runs, nkeys, false) + 256;
-}
-
 // NULL: nothing missing.  The CSR offsets and the summary always, the link columns where there is room for a link.
 static bool chain_ok(const sdb_chain_out *c) {
     if (!c || !c->chain_start || !c->summary) return false;
@@ -633,91 +629,94 @@ static sdb_status check_projections(const sdb_lsm_view *lsm, const sdb_scan_rang
     return check_ranges(proj);
 }
 
-// sdb_lsm_get (merge == false), sdb_lsm_get_merge, sdb_lsm_get_filtered (either, with policies and probe_len) and
-// sdb_lsm_get_projected (that, with proj): one set of argument checks, in one order.  layers: sdb_lsm_get_mem, the
-// projected call with the memtables mem (or NULL), mout and, iff chain, mchain.
-static sdb_status lsm_get_call(const sdb_lsm_view *lsm, const sdb_scan_ranges *proj, const sdb_filter_policy *policies,
-                               const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys, const int32_t *probe_len,
-                               const uint64_t *max_seq, const sdb_get_out *out, bool merge, const sdb_chain_out *chain,
-                               void *workspace, uint64_t workspace_bytes, void *stream, bool layers = false,
-                               const sdb_mem_view *mem = nullptr, const sdb_mem_get_out *mout = nullptr,
-                               const sdb_mem_chain_out *mchain = nullptr) {
-    if (!lsm || !out || (merge && !chain)) return SDB_INVALID_ARGUMENT;
-    const uint32_t ntab = layers && mem ? mem->num_tables : 0;
-    if (layers && (!mout || (chain != nullptr) != (mchain != nullptr) || (ntab && !mem->tables))) return SDB_INVALID_ARGUMENT;
+// The five gets: one set of argument checks, in one order, over the descriptor its entry point filled (sdb_reads.h).
+static sdb_status lsm_get_call(const GetCall &c, void *workspace, uint64_t workspace_bytes, void *stream) {
+    const sdb_lsm_view *lsm = c.lsm;
+    const sdb_get_out *out = c.out;
+    const uint64_t nkeys = c.nkeys;
+    if (!lsm || !out || (c.merge && !c.chain)) return SDB_INVALID_ARGUMENT;
+    const uint32_t ntab = c.mem ? c.mem->num_tables : 0;
+    if (c.layers && (!c.mout || (c.chain != nullptr) != (c.mchain != nullptr) || (ntab && !c.mem->tables)))
+        return SDB_INVALID_ARGUMENT;
     // (the limits all give one status, so this one may come before the tree's)
     const uint64_t per_key = (uint64_t)lsm->num_runs + ntab;  // a byte per (query, run), a record per (query, table)
     if (per_key && nkeys > (1ull << 40) / per_key) return SDB_LIMIT_EXCEEDED;
     sdb_status st = check_tree(lsm);
     if (st) return st;
-    if (check_projections(lsm, proj)) return SDB_INVALID_ARGUMENT;
-    if (!out->summary || (merge && !chain_ok(chain))) return SDB_INVALID_ARGUMENT;
-    if (nkeys && (!key_bytes || !key_off || !out->state || !out->status || !out->sst || !out->block || !out->val_off ||
+    if (check_projections(lsm, c.proj)) return SDB_INVALID_ARGUMENT;
+    if (!out->summary || (c.merge && !chain_ok(c.chain))) return SDB_INVALID_ARGUMENT;
+    if (nkeys && (!c.key_bytes || !c.key_off || !out->state || !out->status || !out->sst || !out->block || !out->val_off ||
                   !out->val_len || !out->seq || !out->flags || !out->create_ts || !out->expire_ts || !out->ssts_read ||
                   !out->ssts_filtered))
         return SDB_INVALID_ARGUMENT;
-    if (layers && ((nkeys && (!mout->table || !mout->row)) || (merge && chain->cap_links && (!mchain->table || !mchain->row))))
+    if (c.layers && ((nkeys && (!c.mout->table || !c.mout->row)) ||
+                     (c.merge && c.chain->cap_links && (!c.mchain->table || !c.mchain->row))))
         return SDB_INVALID_ARGUMENT;
-    if (!workspace ||
-        workspace_bytes < get_mem_workspace_bytes(ntab, lsm->total_blocks, lsm->num_ssts, lsm->num_runs, nkeys, merge) + 256)
-        return SDB_INVALID_ARGUMENT;
+    const uint64_t need = get_workspace_bytes({.num_tables = ntab, .total_blocks = lsm->total_blocks, .num_ssts = lsm->num_ssts,
+                                               .num_runs = lsm->num_runs, .n = nkeys, .merge = c.merge});
+    if (!workspace || workspace_bytes < need + 256) return SDB_INVALID_ARGUMENT;
     if (!device_ok()) return SDB_DEVICE_ERROR;
-    uint8_t *w = ws_align(workspace);
-    const hipError_t e =
-        layers ? launch_get_mem(mem, *lsm, policies, key_bytes, key_off, nkeys, probe_len, max_seq, *out, *mout,
-                                merge ? chain : nullptr, mchain, proj, w, S(stream))
-               : launch_get(*lsm, policies, key_bytes, key_off, nkeys, probe_len, max_seq, *out, merge ? chain : nullptr, proj, w,
-                            S(stream));
-    return e != hipSuccess ? SDB_DEVICE_ERROR : SDB_OK;
+    return launch_get(c, ws_align(workspace), S(stream)) != hipSuccess ? SDB_DEVICE_ERROR : SDB_OK;
+}
+
+uint64_t sdb_lsm_get_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys) {
+    return get_workspace_bytes({.total_blocks = total_blocks, .num_ssts = num_ssts, .num_runs = num_runs, .n = nkeys}) + 256;
 }
 
 sdb_status sdb_lsm_get(const sdb_lsm_view *lsm, const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
                        const uint64_t *max_seq, const sdb_get_out *out, void *workspace, uint64_t workspace_bytes,
                        void *stream) {
-    return lsm_get_call(lsm, nullptr, nullptr, key_bytes, key_off, nkeys, nullptr, max_seq, out, false, nullptr, workspace,
-                        workspace_bytes, stream);
+    return lsm_get_call({.lsm = lsm, .key_bytes = key_bytes, .key_off = key_off, .nkeys = nkeys, .max_seq = max_seq, .out = out},
+                        workspace, workspace_bytes, stream);
 }
 
 uint64_t sdb_lsm_get_merge_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys) {
-    return get_workspace_bytes(total_blocks, num_ssts, num_runs, nkeys, true) + 256;
+    return get_workspace_bytes({.total_blocks = total_blocks, .num_ssts = num_ssts, .num_runs = num_runs, .n = nkeys,
+                                .merge = true}) + 256;
 }
 
 sdb_status sdb_lsm_get_merge(const sdb_lsm_view *lsm, const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys,
                              const uint64_t *max_seq, const sdb_get_out *out, const sdb_chain_out *chain, void *workspace,
                              uint64_t workspace_bytes, void *stream) {
-    return lsm_get_call(lsm, nullptr, nullptr, key_bytes, key_off, nkeys, nullptr, max_seq, out, true, chain, workspace,
-                        workspace_bytes, stream);
+    return lsm_get_call({.lsm = lsm, .key_bytes = key_bytes, .key_off = key_off, .nkeys = nkeys, .max_seq = max_seq, .out = out,
+                         .chain = chain, .merge = true},
+                        workspace, workspace_bytes, stream);
 }
 
 uint64_t sdb_lsm_get_filtered_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys,
                                               int32_t merge) {
-    return get_workspace_bytes(total_blocks, num_ssts, num_runs, nkeys, merge != 0) + 256;
+    return get_workspace_bytes({.total_blocks = total_blocks, .num_ssts = num_ssts, .num_runs = num_runs, .n = nkeys,
+                                .merge = merge != 0}) + 256;
 }
 
 sdb_status sdb_lsm_get_filtered(const sdb_lsm_view *lsm, const sdb_filter_policy *policies, const uint8_t *key_bytes,
                                 const uint64_t *key_off, uint64_t nkeys, const int32_t *probe_len, const uint64_t *max_seq,
                                 const sdb_get_out *out, const sdb_chain_out *chain, void *workspace, uint64_t workspace_bytes,
                                 void *stream) {
-    return lsm_get_call(lsm, nullptr, policies, key_bytes, key_off, nkeys, probe_len, max_seq, out, chain != nullptr, chain,
+    return lsm_get_call({.lsm = lsm, .pol = policies, .key_bytes = key_bytes, .key_off = key_off, .nkeys = nkeys,
+                         .probe_len = probe_len, .max_seq = max_seq, .out = out, .chain = chain, .merge = chain != nullptr},
                         workspace, workspace_bytes, stream);
 }
 
 uint64_t sdb_lsm_get_projected_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys,
                                                int32_t merge) {
-    return get_workspace_bytes(total_blocks, num_ssts, num_runs, nkeys, merge != 0) + 256;  // a projection needs no state
+    // a projection needs no state
+    return sdb_lsm_get_filtered_workspace_bytes(total_blocks, num_ssts, num_runs, nkeys, merge);
 }
 
 sdb_status sdb_lsm_get_projected(const sdb_lsm_view *lsm, const sdb_scan_ranges *proj, const sdb_filter_policy *policies,
                                  const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys, const int32_t *probe_len,
                                  const uint64_t *max_seq, const sdb_get_out *out, const sdb_chain_out *chain, void *workspace,
                                  uint64_t workspace_bytes, void *stream) {
-    return lsm_get_call(lsm, proj, policies, key_bytes, key_off, nkeys, probe_len, max_seq, out, chain != nullptr, chain,
+    return lsm_get_call({.lsm = lsm, .proj = proj, .pol = policies, .key_bytes = key_bytes, .key_off = key_off, .nkeys = nkeys,
+                         .probe_len = probe_len, .max_seq = max_seq, .out = out, .chain = chain, .merge = chain != nullptr},
                         workspace, workspace_bytes, stream);
 }
 
 uint64_t sdb_lsm_get_mem_workspace_bytes(uint32_t num_tables, uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs,
                                          uint64_t nkeys, int32_t merge) {
-    return get_mem_workspace_bytes(num_tables, total_blocks, num_ssts, num_runs, nkeys, merge != 0) + 256;
+    return get_workspace_bytes({.num_tables = num_tables, .total_blocks = total_blocks, .num_ssts = num_ssts,
+                                .num_runs = num_runs, .n = nkeys, .merge = merge != 0}) + 256;
 }
 
 sdb_status sdb_lsm_get_mem(const sdb_mem_view *mem, const sdb_lsm_view *lsm, const sdb_scan_ranges *proj,
@@ -725,95 +724,89 @@ sdb_status sdb_lsm_get_mem(const sdb_mem_view *mem, const sdb_lsm_view *lsm, con
                            const int32_t *probe_len, const uint64_t *max_seq, const sdb_get_out *out,
                            const sdb_mem_get_out *mout, const sdb_chain_out *chain, const sdb_mem_chain_out *mchain,
                            void *workspace, uint64_t workspace_bytes, void *stream) {
-    return lsm_get_call(lsm, proj, policies, key_bytes, key_off, nkeys, probe_len, max_seq, out, chain != nullptr, chain,
-                        workspace, workspace_bytes, stream, true, mem, mout, mchain);
+    return lsm_get_call({.mem = mem, .lsm = lsm, .proj = proj, .pol = policies, .key_bytes = key_bytes, .key_off = key_off,
+                         .nkeys = nkeys, .probe_len = probe_len, .max_seq = max_seq, .out = out, .mout = mout, .chain = chain,
+                         .mchain = mchain, .merge = chain != nullptr, .layers = true},
+                        workspace, workspace_bytes, stream);
 }
 
-uint64_t sdb_lsm_scan_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nranges,
-                                      uint64_t cand_entries, uint64_t cand_key_bytes) {
-    (void)num_runs;  // runs only fix the search order: the workspace is per (range, SST)
-    return lsm_scan_workspace_bytes(total_blocks, num_ssts, nranges, cand_entries, cand_key_bytes, false, false) + 256;
-}
-
-uint64_t sdb_lsm_scan_merge_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs,
-                                            uint64_t nranges, uint64_t cand_entries, uint64_t cand_key_bytes) {
-    (void)num_runs;
-    return lsm_scan_workspace_bytes(total_blocks, num_ssts, nranges, cand_entries, cand_key_bytes, true, false) + 256;
-}
-
-uint64_t sdb_lsm_scan_filtered_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs,
-                                               uint64_t nranges, uint64_t cand_entries, uint64_t cand_key_bytes,
-                                               int32_t merge) {
-    (void)num_runs;
-    return lsm_scan_workspace_bytes(total_blocks, num_ssts, nranges, cand_entries, cand_key_bytes, merge != 0, true) + 256;
-}
-
-// sdb_lsm_scan (chain == NULL, merge == false), sdb_lsm_scan_merge, sdb_lsm_scan_filtered (filter: either, with
-// policies, prefixes and fout) and sdb_lsm_scan_projected (that, with proj): one set of argument checks, in one order.
-static sdb_status lsm_scan_call(const sdb_lsm_view *lsm, const sdb_scan_ranges *proj, const sdb_scan_ranges *ranges,
-                                const uint64_t *max_seq,
-                                int32_t descending, uint64_t cand_entries, uint64_t cand_key_bytes,
-                                const sdb_lsm_scan_out *out, bool merge, const sdb_chain_out *chain, bool filter,
-                                const sdb_filter_policy *policies, const sdb_scan_prefixes *prefixes,
-                                const sdb_scan_filter_out *fout, void *workspace, uint64_t workspace_bytes, void *stream,
-                                bool layers = false, const sdb_mem_view *mem = nullptr,
-                                const sdb_mem_scan_out *mout = nullptr, const sdb_mem_chain_out *mchain = nullptr) {
-    if (!lsm || !ranges || !out || (merge && !chain) || (filter && !fout)) return SDB_INVALID_ARGUMENT;
-    const uint32_t ntab = layers && mem ? mem->num_tables : 0;
-    if (layers && (!mout || (chain != nullptr) != (mchain != nullptr) || (ntab && !mem->tables))) return SDB_INVALID_ARGUMENT;
-    const uint64_t n = ranges->n;
+// The five scans: one set of argument checks, in one order, over the descriptor its entry point filled (sdb_reads.h).
+static sdb_status lsm_scan_call(const ScanCall &c, void *workspace, uint64_t workspace_bytes, void *stream) {
+    const sdb_lsm_view *lsm = c.lsm;
+    const sdb_lsm_scan_out *out = c.out;
+    if (!lsm || !c.ranges || !out || (c.merge && !c.chain) || (c.filter && !c.fout)) return SDB_INVALID_ARGUMENT;
+    const uint32_t ntab = c.mem ? c.mem->num_tables : 0;
+    if (c.layers && (!c.mout || (c.chain != nullptr) != (c.mchain != nullptr) || (ntab && !c.mem->tables)))
+        return SDB_INVALID_ARGUMENT;
+    const uint64_t n = c.ranges->n;
     // (the limits all give one status, so these may come before the tree's)
     const uint64_t per_range = (uint64_t)lsm->num_ssts + ntab;  // per (range, source) state
     if (per_range && n > (1ull << 40) / per_range) return SDB_LIMIT_EXCEEDED;
-    if (cand_entries > (1ull << 40) || cand_key_bytes > (1ull << 44)) return SDB_LIMIT_EXCEEDED;
+    if (c.cand_entries > (1ull << 40) || c.cand_key_bytes > (1ull << 44)) return SDB_LIMIT_EXCEEDED;
     sdb_status st = check_tree(lsm);
     if (st) return st;
-    if (check_projections(lsm, proj)) return SDB_INVALID_ARGUMENT;
-    if (!out->summary || !out->range_entry_start || !out->key_off || check_ranges(ranges)) return SDB_INVALID_ARGUMENT;
+    if (check_projections(lsm, c.proj)) return SDB_INVALID_ARGUMENT;
+    if (!out->summary || !out->range_entry_start || !out->key_off || check_ranges(c.ranges)) return SDB_INVALID_ARGUMENT;
     if (n && (!out->range_status || !out->range_ssts)) return SDB_INVALID_ARGUMENT;
     if (out->key_arena_cap && !out->key_arena) return SDB_INVALID_ARGUMENT;
     if (out->cap_entries && (!out->sst || !out->val_off || !out->val_len || !out->seq || !out->flags ||
                              !out->create_ts || !out->expire_ts))
         return SDB_INVALID_ARGUMENT;
-    if (merge && !chain_ok(chain)) return SDB_INVALID_ARGUMENT;
-    if (filter && n && (!fout->range_filtered || !fout->num_filtered)) return SDB_INVALID_ARGUMENT;
-    if (filter && n && prefixes && (!prefixes->prefix_bytes || !prefixes->prefix_off || !prefixes->has_prefix))
+    if (c.merge && !chain_ok(c.chain)) return SDB_INVALID_ARGUMENT;
+    if (c.filter && n && (!c.fout->range_filtered || !c.fout->num_filtered)) return SDB_INVALID_ARGUMENT;
+    if (c.filter && n && c.prefixes && (!c.prefixes->prefix_bytes || !c.prefixes->prefix_off || !c.prefixes->has_prefix))
         return SDB_INVALID_ARGUMENT;
-    if (layers && ((n && !mout->range_tables) || (out->cap_entries && (!mout->table || !mout->row)) ||
-                   (merge && chain->cap_links && (!mchain->table || !mchain->row))))
+    if (c.layers && ((n && !c.mout->range_tables) || (out->cap_entries && (!c.mout->table || !c.mout->row)) ||
+                     (c.merge && c.chain->cap_links && (!c.mchain->table || !c.mchain->row))))
         return SDB_INVALID_ARGUMENT;
-    const uint64_t need = layers ? lsm_scan_mem_workspace_bytes(ntab, lsm->total_blocks, lsm->num_ssts, n, cand_entries,
-                                                                cand_key_bytes, merge)
-                                 : lsm_scan_workspace_bytes(lsm->total_blocks, lsm->num_ssts, n, cand_entries, cand_key_bytes,
-                                                            merge, filter);
+    const uint64_t need = lsm_scan_workspace_bytes({.num_tables = ntab, .total_blocks = lsm->total_blocks,
+                                                    .num_ssts = lsm->num_ssts, .n = n, .cand_entries = c.cand_entries,
+                                                    .cand_key_bytes = c.cand_key_bytes, .merge = c.merge, .filter = c.filter});
     if (!workspace || workspace_bytes < need + 256) return SDB_INVALID_ARGUMENT;
     if (!device_ok()) return SDB_DEVICE_ERROR;
-    uint8_t *w = ws_align(workspace);
-    if (layers)
-        return launch_lsm_scan_mem(mem, *lsm, *ranges, max_seq, descending ? 1u : 0u, cand_entries, cand_key_bytes, *out, *mout,
-                                   merge ? chain : nullptr, mchain, policies, prefixes, *fout, proj, w, S(stream)) != hipSuccess
-                   ? SDB_DEVICE_ERROR
-                   : SDB_OK;
-    if (launch_lsm_scan(*lsm, *ranges, max_seq, descending ? 1u : 0u, cand_entries, cand_key_bytes, *out,
-                        merge ? chain : nullptr, policies, prefixes, filter ? fout : nullptr, filter ? proj : nullptr, w,
-                        S(stream)) != hipSuccess)
-        return SDB_DEVICE_ERROR;
-    return SDB_OK;
+    return launch_lsm_scan(c, ws_align(workspace), S(stream)) != hipSuccess ? SDB_DEVICE_ERROR : SDB_OK;
+}
+
+// (runs only fix the search order: a scan's workspace is per (range, SST), so the sizers ignore num_runs)
+uint64_t sdb_lsm_scan_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nranges,
+                                      uint64_t cand_entries, uint64_t cand_key_bytes) {
+    (void)num_runs;
+    return lsm_scan_workspace_bytes({.total_blocks = total_blocks, .num_ssts = num_ssts, .n = nranges,
+                                     .cand_entries = cand_entries, .cand_key_bytes = cand_key_bytes}) + 256;
 }
 
 sdb_status sdb_lsm_scan(const sdb_lsm_view *lsm, const sdb_scan_ranges *ranges, const uint64_t *max_seq,
                         int32_t descending, uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out *out,
                         void *workspace, uint64_t workspace_bytes, void *stream) {
-    return lsm_scan_call(lsm, nullptr, ranges, max_seq, descending, cand_entries, cand_key_bytes, out, false, nullptr, false,
-                         nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
+    return lsm_scan_call({.lsm = lsm, .ranges = ranges, .max_seq = max_seq, .desc = descending ? 1u : 0u,
+                          .cand_entries = cand_entries, .cand_key_bytes = cand_key_bytes, .out = out},
+                         workspace, workspace_bytes, stream);
+}
+
+uint64_t sdb_lsm_scan_merge_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs,
+                                            uint64_t nranges, uint64_t cand_entries, uint64_t cand_key_bytes) {
+    (void)num_runs;
+    return lsm_scan_workspace_bytes({.total_blocks = total_blocks, .num_ssts = num_ssts, .n = nranges,
+                                     .cand_entries = cand_entries, .cand_key_bytes = cand_key_bytes, .merge = true}) + 256;
 }
 
 sdb_status sdb_lsm_scan_merge(const sdb_lsm_view *lsm, const sdb_scan_ranges *ranges, const uint64_t *max_seq,
                               int32_t descending, uint64_t cand_entries, uint64_t cand_key_bytes,
                               const sdb_lsm_scan_out *out, const sdb_chain_out *chain, void *workspace,
                               uint64_t workspace_bytes, void *stream) {
-    return lsm_scan_call(lsm, nullptr, ranges, max_seq, descending, cand_entries, cand_key_bytes, out, true, chain, false,
-                         nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
+    return lsm_scan_call({.lsm = lsm, .ranges = ranges, .max_seq = max_seq, .desc = descending ? 1u : 0u,
+                          .cand_entries = cand_entries, .cand_key_bytes = cand_key_bytes, .out = out, .chain = chain,
+                          .merge = true},
+                         workspace, workspace_bytes, stream);
+}
+
+uint64_t sdb_lsm_scan_filtered_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs,
+                                               uint64_t nranges, uint64_t cand_entries, uint64_t cand_key_bytes,
+                                               int32_t merge) {
+    (void)num_runs;
+    return lsm_scan_workspace_bytes({.total_blocks = total_blocks, .num_ssts = num_ssts, .n = nranges,
+                                     .cand_entries = cand_entries, .cand_key_bytes = cand_key_bytes, .merge = merge != 0,
+                                     .filter = true}) + 256;
 }
 
 sdb_status sdb_lsm_scan_filtered(const sdb_lsm_view *lsm, const sdb_filter_policy *policies, const sdb_scan_ranges *ranges,
@@ -821,15 +814,17 @@ sdb_status sdb_lsm_scan_filtered(const sdb_lsm_view *lsm, const sdb_filter_polic
                                  uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out *out,
                                  const sdb_chain_out *chain, const sdb_scan_filter_out *fout, void *workspace,
                                  uint64_t workspace_bytes, void *stream) {
-    return lsm_scan_call(lsm, nullptr, ranges, max_seq, descending, cand_entries, cand_key_bytes, out, chain != nullptr, chain,
-                         true, policies, prefixes, fout, workspace, workspace_bytes, stream);
+    return lsm_scan_call({.lsm = lsm, .pol = policies, .ranges = ranges, .prefixes = prefixes, .max_seq = max_seq,
+                          .desc = descending ? 1u : 0u, .cand_entries = cand_entries, .cand_key_bytes = cand_key_bytes,
+                          .out = out, .chain = chain, .fout = fout, .merge = chain != nullptr, .filter = true},
+                         workspace, workspace_bytes, stream);
 }
 
 uint64_t sdb_lsm_scan_projected_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs,
                                                 uint64_t nranges, uint64_t cand_entries, uint64_t cand_key_bytes,
                                                 int32_t merge) {
-    (void)num_runs;  // a pair's view range is recomputed where it is read: no state beyond the filtered scan's
-    return lsm_scan_workspace_bytes(total_blocks, num_ssts, nranges, cand_entries, cand_key_bytes, merge != 0, true) + 256;
+    // a pair's view range is recomputed where it is read: no state beyond the filtered scan's
+    return sdb_lsm_scan_filtered_workspace_bytes(total_blocks, num_ssts, num_runs, nranges, cand_entries, cand_key_bytes, merge);
 }
 
 sdb_status sdb_lsm_scan_projected(const sdb_lsm_view *lsm, const sdb_scan_ranges *proj, const sdb_filter_policy *policies,
@@ -837,15 +832,18 @@ sdb_status sdb_lsm_scan_projected(const sdb_lsm_view *lsm, const sdb_scan_ranges
                                   int32_t descending, uint64_t cand_entries, uint64_t cand_key_bytes,
                                   const sdb_lsm_scan_out *out, const sdb_chain_out *chain, const sdb_scan_filter_out *fout,
                                   void *workspace, uint64_t workspace_bytes, void *stream) {
-    return lsm_scan_call(lsm, proj, ranges, max_seq, descending, cand_entries, cand_key_bytes, out, chain != nullptr, chain,
-                         true, policies, prefixes, fout, workspace, workspace_bytes, stream);
+    return lsm_scan_call({.lsm = lsm, .proj = proj, .pol = policies, .ranges = ranges, .prefixes = prefixes, .max_seq = max_seq,
+                          .desc = descending ? 1u : 0u, .cand_entries = cand_entries, .cand_key_bytes = cand_key_bytes,
+                          .out = out, .chain = chain, .fout = fout, .merge = chain != nullptr, .filter = true},
+                         workspace, workspace_bytes, stream);
 }
 
 uint64_t sdb_lsm_scan_mem_workspace_bytes(uint32_t num_tables, uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs,
                                           uint64_t nranges, uint64_t cand_entries, uint64_t cand_key_bytes, int32_t merge) {
     (void)num_runs;
-    return lsm_scan_mem_workspace_bytes(num_tables, total_blocks, num_ssts, nranges, cand_entries, cand_key_bytes, merge != 0) +
-           256;
+    return lsm_scan_workspace_bytes({.num_tables = num_tables, .total_blocks = total_blocks, .num_ssts = num_ssts, .n = nranges,
+                                     .cand_entries = cand_entries, .cand_key_bytes = cand_key_bytes, .merge = merge != 0,
+                                     .filter = true}) + 256;
 }
 
 sdb_status sdb_lsm_scan_mem(const sdb_mem_view *mem, const sdb_lsm_view *lsm, const sdb_scan_ranges *proj,
@@ -854,8 +852,11 @@ sdb_status sdb_lsm_scan_mem(const sdb_mem_view *mem, const sdb_lsm_view *lsm, co
                             uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out *out,
                             const sdb_mem_scan_out *mout, const sdb_chain_out *chain, const sdb_mem_chain_out *mchain,
                             const sdb_scan_filter_out *fout, void *workspace, uint64_t workspace_bytes, void *stream) {
-    return lsm_scan_call(lsm, proj, ranges, max_seq, descending, cand_entries, cand_key_bytes, out, chain != nullptr, chain,
-                         true, policies, prefixes, fout, workspace, workspace_bytes, stream, true, mem, mout, mchain);
+    return lsm_scan_call({.mem = mem, .lsm = lsm, .proj = proj, .pol = policies, .ranges = ranges, .prefixes = prefixes,
+                          .max_seq = max_seq, .desc = descending ? 1u : 0u, .cand_entries = cand_entries,
+                          .cand_key_bytes = cand_key_bytes, .out = out, .mout = mout, .chain = chain, .mchain = mchain,
+                          .fout = fout, .merge = chain != nullptr, .filter = true, .layers = true},
+                         workspace, workspace_bytes, stream);
 }
 
 // ---- WAL replay / device memtable ----

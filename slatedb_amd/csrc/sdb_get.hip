@@ -41,7 +41,7 @@
 //   scan            the link counts -> chain_start
 //   k_gm_final      both summaries, do the links fit
 //   k_gm_emit       thread per pair the chain takes: the walk again, its links written at chain_start[q] + off
-// sdb_lsm_get_mem (launch_get_mem) puts device memtables, sorted runs in the sdb_run layout, in front of run 0: a
+// sdb_lsm_get_mem (a GetCall with layers) puts device memtables, sorted runs in the sdb_run layout, in front of run 0: a
 // (query, table) pair is one more pair, whose record comes from a binary search over the table's columns.
 //   k_mem_reset     the queries' decided bytes cleared, and the blocks' marks and statuses in place of two memsets
 //   k_mem_validate  one workgroup: every table has its columns and fewer than 2^31 rows (else the call is malformed)
@@ -64,6 +64,18 @@
 // key's chain iff its effective range, [first_key, last_key] intersected with the visible range, holds the key, and a
 // run is searched by its effective start keys (get_run<V>).  Inside an SST of the chain every version of the key is
 // visible, so only the chain changes; k_get_validate also checks the projections.
+// Host side: one descriptor (GetCall, sdb_reads.h) from the C entry point to the launches.  launch_get -> launch_get_search
+// (memsets, GetArgs, get_bind) -> launch_get_bound<M> -> launch_get_kernels<P, V, M>, where the instantiations are
+// chosen once.  The special cases, each with the rule of include/slatedb_amd.h it implements:
+//   nothing to search   no query, or neither a tree nor a table: every query NOT_FOUND (sst 0xFFFFFFFF) and no link, by
+//                       memsets alone; no kernel
+//   no_tree             the tree has no SST, no run or no block.  The get counts a tree without runs as none with or
+//                       without tables (its pairs are per run; the scan's predicate differs).  With tables (M7) only they
+//                       are searched and nothing is read through the tree's arrays: the tree counts, pol and proj are
+//                       cleared, and launch_get_kernels launches none of the tree's kernels
+//   marks and statuses  without tables two memsets; with tables k_mem_reset, which also clears the decided bytes
+//   no table (M6)       sdb_lsm_get_mem with mem NULL, no table or no query is the projected call, then k_mem_reset over
+//                       mout alone and, with a chain, k_mem_links (launch_mem_links): nothing names a table
 #include <algorithm>
 
 #include "sdb_decode.h"
@@ -677,12 +689,6 @@ __global__ __launch_bounds__(256) void k_mem_reset(uint8_t *decided, sdb_mem_get
         bstat[k] = -1;
     }
 }
-static hipError_t launch_mem_reset(uint8_t *decided, const sdb_mem_get_out &mout, uint64_t n, uint8_t *mark, int32_t *bstat,
-                                   uint64_t tb, hipStream_t st) {
-    const uint32_t g = (uint32_t)std::min<uint64_t>((std::max(n, mark ? tb : 0) + 255) / 256, 1024);
-    if (g) hipLaunchKernelGGL(k_mem_reset, dim3(g), dim3(256), 0, st, decided, mout, n, mark, bstat, tb);
-    return hipGetLastError();
-}
 
 // The rows from `from` on with key == k and seq <= bound, in table order (KVTable::range(key..=key) under
 // FilterIterator::new_with_max_seq): visit(row, value base, the row) -> false: stop.
@@ -803,19 +809,14 @@ static uint64_t get_bind(GetArgs &a, uint8_t *w, bool merge) {
     return c.off;
 }
 
-uint64_t get_mem_workspace_bytes(uint32_t num_tables, uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs,
-                                 uint64_t nkeys, bool merge) {
+uint64_t get_workspace_bytes(const ReadShape &s) {
     GetArgs a{};
-    a.t.total_blocks = total_blocks;
-    a.t.num_ssts = num_ssts;
-    a.t.num_runs = num_runs;
-    a.nkeys = nkeys;
-    a.ntab = num_tables;
-    return get_bind(a, nullptr, merge);
-}
-
-uint64_t get_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint32_t num_runs, uint64_t nkeys, bool merge) {
-    return get_mem_workspace_bytes(0, total_blocks, num_ssts, num_runs, nkeys, merge);
+    a.t.total_blocks = s.total_blocks;
+    a.t.num_ssts = s.num_ssts;
+    a.t.num_runs = s.num_runs;
+    a.nkeys = s.n;
+    a.ntab = s.num_tables;
+    return get_bind(a, nullptr, s.merge);
 }
 
 // The kernels of a bound get in stream order.  P: the call has filter policies, V: it has projections, each chosen
@@ -867,15 +868,23 @@ static hipError_t launch_get_bound(const GetArgs &a, bool filters, bool projecte
     return filters ? launch_get_kernels<true, false, M>(a, merge, st) : launch_get_kernels<false, false, M>(a, merge, st);
 }
 
-// mem (with mout, and mchain iff chain): sdb_lsm_get_mem's tables, at least one; else nullptr
-static hipError_t launch_get_layers(const sdb_mem_view *mem, const sdb_lsm_view &t, const sdb_filter_policy *pol,
-                                    const uint8_t *key_bytes, const uint64_t *key_off, uint64_t nkeys, const int32_t *probe_len,
-                                    const uint64_t *max_seq, const sdb_get_out &out, const sdb_mem_get_out *mout,
-                                    const sdb_chain_out *chain, const sdb_mem_chain_out *mchain, const sdb_scan_ranges *proj,
-                                    uint8_t *w, hipStream_t st) {
-    const uint64_t tb = t.total_blocks, n = nkeys;
+// k_mem_reset over a's queries and, with marks, a's tree blocks.
+static hipError_t launch_mem_reset(const GetArgs &a, bool marks, hipStream_t st) {
+    const uint64_t n = a.nkeys, tb = a.t.total_blocks;
+    const uint32_t g = (uint32_t)std::min<uint64_t>((std::max(n, marks ? tb : 0) + 255) / 256, 1024);
+    if (g) hipLaunchKernelGGL(k_mem_reset, dim3(g), dim3(256), 0, st, a.decided, a.mout, n, marks ? a.mark : nullptr, a.bstat, tb);
+    return hipGetLastError();
+}
+
+// The search of one get call (the special cases: the file comment).  tabs: c.mem holds a table and there is a query
+// (with c.mout, and c.mchain iff c.chain).
+static hipError_t launch_get_search(const GetCall &c, bool tabs, uint8_t *w, hipStream_t st) {
+    const sdb_lsm_view &t = *c.lsm;
+    const sdb_get_out &out = *c.out;
+    const sdb_chain_out *chain = c.chain;
+    const uint64_t tb = t.total_blocks, n = c.nkeys;
     const bool no_tree = t.num_ssts == 0 || t.num_runs == 0 || tb == 0;
-    const bool none = n == 0 || (no_tree && !mem);  // nothing to search
+    const bool none = n == 0 || (no_tree && !tabs);  // nothing to search
     hipError_t e;
     if (none && chain) {  // no links
         if ((e = hipMemsetAsync(chain->summary, 0, sizeof(sdb_chain_summary), st)) != hipSuccess) return e;
@@ -890,62 +899,55 @@ static hipError_t launch_get_layers(const sdb_mem_view *mem, const sdb_lsm_view 
         } cols[] = {{out.state, 0, 1},     {out.status, 0, 4},    {out.sst, 0xFF, 4},    {out.block, 0, 4},
                     {out.val_off, 0, 8},   {out.val_len, 0, 4},   {out.seq, 0, 8},       {out.flags, 0, 1},
                     {out.create_ts, 0, 8}, {out.expire_ts, 0, 8}, {out.ssts_read, 0, 4}, {out.ssts_filtered, 0, 4}};
-        for (const auto &c : cols)
-            if (n && (e = hipMemsetAsync(c.p, c.fill, c.width * n, st)) != hipSuccess) return e;
+        for (const auto &col : cols)
+            if (n && (e = hipMemsetAsync(col.p, col.fill, col.width * n, st)) != hipSuccess) return e;
         return hipSuccess;
     }
     GetArgs a{};
     a.t = t;
-    a.key_bytes = key_bytes;
-    a.key_off = key_off;
+    a.key_bytes = c.key_bytes;
+    a.key_off = c.key_off;
     a.nkeys = n;
-    a.max_seq = max_seq;
+    a.max_seq = c.max_seq;
     a.out = out;
-    a.pol = pol;
-    a.probe_len = probe_len;
+    a.pol = c.pol;
+    a.probe_len = c.probe_len;
     if (chain) a.chain = *chain;
-    if (mem) {
-        a.tabs = mem->tables;
-        a.ntab = mem->num_tables;
-        a.mout = *mout;
-        if (chain) a.mchain = *mchain;
+    if (tabs) {
+        a.tabs = c.mem->tables;
+        a.ntab = c.mem->num_tables;
+        a.mout = *c.mout;
+        if (chain) a.mchain = *c.mchain;
     }
     const bool merge = chain != nullptr;
     get_bind(a, w, merge);
+    const sdb_scan_ranges *proj = c.proj;
     if (no_tree) {  // (M7) only the tables are searched, and nothing is read through the tree's arrays
         a.t.num_ssts = a.t.num_runs = 0;
         a.t.total_blocks = 0;
         a.pol = nullptr;
         proj = nullptr;
-    } else if (!mem) {
+    } else if (!tabs) {
         if ((e = hipMemsetAsync(a.mark, 0, tb, st)) != hipSuccess) return e;
         if ((e = hipMemsetAsync(a.bstat, 0xFF, 4 * tb, st)) != hipSuccess) return e;
     }
     if (proj) a.proj = *proj;
-    if (!mem) return launch_get_bound<false>(a, pol || probe_len, proj != nullptr, merge, st);
-    if ((e = launch_mem_reset(a.decided, a.mout, n, no_tree ? nullptr : a.mark, a.bstat, tb, st)) != hipSuccess) return e;
-    return launch_get_bound<true>(a, pol || probe_len, proj != nullptr, merge, st);
+    const bool filters = c.pol || c.probe_len;
+    if (!tabs) return launch_get_bound<false>(a, filters, proj != nullptr, merge, st);
+    if ((e = launch_mem_reset(a, !no_tree, st)) != hipSuccess) return e;
+    return launch_get_bound<true>(a, filters, proj != nullptr, merge, st);
 }
 
-hipError_t launch_get(const sdb_lsm_view &t, const sdb_filter_policy *pol, const uint8_t *key_bytes, const uint64_t *key_off,
-                      uint64_t nkeys, const int32_t *probe_len, const uint64_t *max_seq, const sdb_get_out &out,
-                      const sdb_chain_out *chain /* sdb_lsm_get_merge, else nullptr */,
-                      const sdb_scan_ranges *proj /* sdb_lsm_get_projected, else nullptr */, uint8_t *w, hipStream_t st) {
-    return launch_get_layers(nullptr, t, pol, key_bytes, key_off, nkeys, probe_len, max_seq, out, nullptr, chain, nullptr, proj, w,
-                             st);
-}
-
-hipError_t launch_get_mem(const sdb_mem_view *mem, const sdb_lsm_view &t, const sdb_filter_policy *pol, const uint8_t *key_bytes,
-                          const uint64_t *key_off, uint64_t nkeys, const int32_t *probe_len, const uint64_t *max_seq,
-                          const sdb_get_out &out, const sdb_mem_get_out &mout, const sdb_chain_out *chain,
-                          const sdb_mem_chain_out *mchain, const sdb_scan_ranges *proj, uint8_t *w, hipStream_t st) {
-    if (mem && mem->num_tables && nkeys)
-        return launch_get_layers(mem, t, pol, key_bytes, key_off, nkeys, probe_len, max_seq, out, &mout, chain, mchain, proj, w, st);
-    // (M6) no tables: the projected call, and no query or link names a table
-    hipError_t e = launch_get(t, pol, key_bytes, key_off, nkeys, probe_len, max_seq, out, chain, proj, w, st);
-    if (e != hipSuccess) return e;
-    if ((e = launch_mem_reset(nullptr, mout, nkeys, nullptr, nullptr, 0, st)) != hipSuccess) return e;
-    return chain ? launch_mem_links(*chain, *mchain, st) : hipSuccess;
+hipError_t launch_get(const GetCall &c, uint8_t *w, hipStream_t st) {
+    const bool tabs = c.mem && c.mem->num_tables && c.nkeys;
+    hipError_t e = launch_get_search(c, tabs, w, st);
+    if (e != hipSuccess || tabs || !c.layers) return e;
+    // (M6) sdb_lsm_get_mem without a table: the projected call, and no query or link names a table
+    GetArgs r{};
+    r.nkeys = c.nkeys;
+    r.mout = *c.mout;
+    if ((e = launch_mem_reset(r, false, st)) != hipSuccess) return e;
+    return c.chain ? launch_mem_links(*c.chain, *c.mchain, st) : hipSuccess;
 }
 
 }  // namespace sdb

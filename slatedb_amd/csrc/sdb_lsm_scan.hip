@@ -81,6 +81,21 @@
 // k_ls_rank, k_ls_links, the scans and k_ls_count work on staged candidates and see sources where they saw SSTs: the
 // stride is nsrc, and j < i still means "the earlier source".  Without tables nsrc == num_ssts and the seven other
 // entry points launch the instantiations without the table step (k_ls_mfill then names no table for what they wrote).
+// Host side: one descriptor (ScanCall, sdb_reads.h) from the C entry point to the launches.  launch_lsm_scan ->
+// launch_ls_search (memsets, LsArgs, the bind) -> launch_ls_bound -> launch_ls_kernels<FILTER, PROJ, MEM>, where the
+// instantiations are chosen once: the five of (plain or merging), filtered, projected, tables, tables and projected.
+// The special cases, each with the rule of include/slatedb_amd.h it implements:
+//   nothing to search   no range, or neither a tree nor a table: every range is empty, by memsets alone; no kernel
+//   no_tree             the tree has no SST or no block; a tree without runs counts as none only with tables (a scan's
+//                       pairs are per SST, and the calls without tables never looked at num_runs; the get's predicate
+//                       differs).  With tables (S8) only they are scanned and nothing is read through the tree's
+//                       arrays: the tree counts, pol and proj are cleared, and launch_ls_kernels launches none of the
+//                       tree's kernels
+//   marks and statuses  without tables two memsets; with tables k_ls_mreset
+//   no table (S7)       sdb_lsm_scan_mem with mem NULL, no table or no range is the projected call, then k_ls_mfill: no
+//                       row, link or range names a table
+//   filter              a property of the entry point (ScanCall::filter), not of fout: it sizes the workspace, selects
+//                       k_ls_locate<true, ...> and has range_filtered / num_filtered written
 #include <algorithm>
 #include <climits>
 
@@ -909,42 +924,88 @@ static uint64_t lsm_scan_filter_bind(LsArgs &a, uint8_t *w, bool merge) {
     return c.off;
 }
 
-uint64_t lsm_scan_mem_workspace_bytes(uint32_t num_tables, uint64_t total_blocks, uint32_t num_ssts, uint64_t nranges,
-                                      uint64_t cand_entries, uint64_t cand_key_bytes, bool merge) {
-    LsArgs a{};
-    a.t.total_blocks = total_blocks;
-    a.t.num_ssts = num_ssts;
-    a.ntab = num_tables;
-    a.r.n = nranges;
-    a.cand_entries = cand_entries;
-    a.cand_key_bytes = cand_key_bytes;
-    return lsm_scan_filter_bind(a, nullptr, merge);  // the pairs count the tables; no array of its own
+// The layout of the entry point: the plain scan's arrays, then the merging scan's, then the filtered scan's.
+static uint64_t lsm_scan_bind_for(LsArgs &a, uint8_t *w, bool merge, bool filter) {
+    if (filter) return lsm_scan_filter_bind(a, w, merge);
+    return merge ? lsm_scan_merge_bind(a, w) : lsm_scan_bind(a, w);
 }
 
-uint64_t lsm_scan_workspace_bytes(uint64_t total_blocks, uint32_t num_ssts, uint64_t nranges, uint64_t cand_entries,
-                                  uint64_t cand_key_bytes, bool merge, bool filter) {
+uint64_t lsm_scan_workspace_bytes(const ReadShape &s) {
     LsArgs a{};
-    a.t.total_blocks = total_blocks;
-    a.t.num_ssts = num_ssts;
-    a.r.n = nranges;
-    a.cand_entries = cand_entries;
-    a.cand_key_bytes = cand_key_bytes;
-    if (filter) return lsm_scan_filter_bind(a, nullptr, merge);
-    return merge ? lsm_scan_merge_bind(a, nullptr) : lsm_scan_bind(a, nullptr);
+    a.t.total_blocks = s.total_blocks;
+    a.t.num_ssts = s.num_ssts;
+    a.ntab = s.num_tables;  // the pairs count the tables; no array of their own
+    a.r.n = s.n;
+    a.cand_entries = s.cand_entries;
+    a.cand_key_bytes = s.cand_key_bytes;
+    return lsm_scan_bind_for(a, nullptr, s.merge, s.filter);
 }
 
-// mem (with mout, and mchain iff chain; fout given): sdb_lsm_scan_mem's tables, at least one, and n > 0; else nullptr
-static hipError_t launch_lsm_scan_layers(const sdb_mem_view *mem, const sdb_lsm_view &t, const sdb_scan_ranges &r,
-                                         const uint64_t *max_seq, uint32_t desc, uint64_t cand_entries,
-                                         uint64_t cand_key_bytes, const sdb_lsm_scan_out &out, const sdb_mem_scan_out *mout,
-                                         const sdb_chain_out *chain, const sdb_mem_chain_out *mchain,
-                                         const sdb_filter_policy *pol, const sdb_scan_prefixes *px,
-                                         const sdb_scan_filter_out *fout, const sdb_scan_ranges *proj, uint8_t *w,
-                                         hipStream_t st) {
-    const uint64_t n = r.n;
-    const bool no_tree = t.num_ssts == 0 || t.total_blocks == 0 || (mem && t.num_runs == 0);
+// The kernels of a bound scan in stream order.  FILTER: the filters are consulted, PROJ: the call has projections, MEM:
+// it has tables (and then always FILTER), each chosen once for the kernels that hold the step; a.merge: the chain's
+// kernels.  tree: false only with tables over a tree without SSTs or blocks (S8): none of the tree's kernels is launched.
+template <bool FILTER, bool PROJ, bool MEM>
+static hipError_t launch_ls_kernels(const LsArgs &a, bool tree, hipStream_t st) {
+    const uint64_t tb = a.t.total_blocks, n = a.r.n, P = a.pairs, SP = a.spairs, ce = a.cand_entries;
+    const uint32_t rw = (uint32_t)((n + 63) / 64);
     hipError_t e;
-    if (n == 0 || (no_tree && !mem)) {  // every range is empty
+    if constexpr (MEM) {  // the marks and statuses: by a kernel with tables (k_ls_mreset), else by two memsets
+        if (tree) hipLaunchKernelGGL(k_ls_mreset, dim3(scan_grid(tb, 256)), dim3(256), 0, st, a.mark, a.bstat, tb);
+    } else {
+        if ((e = hipMemsetAsync(a.mark, 0, tb, st)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(a.bstat, 0xFF, 4 * tb, st)) != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_ls_validate<PROJ>, dim3(1), dim3(256), 0, st, a);
+    if constexpr (MEM) hipLaunchKernelGGL(k_ls_tvalidate, dim3(1), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_ls_ranges, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, a);
+    if constexpr (MEM) hipLaunchKernelGGL(k_ls_tprobe, dim3(scan_grid(n * a.ntab, 256)), dim3(256), 0, st, a);
+    if (tree) {
+        hipLaunchKernelGGL((k_ls_locate<FILTER, PROJ, MEM>), dim3(scan_grid(SP, 256)), dim3(256), 0, st, a);
+        if ((e = launch_check(CheckArgs{{}, a.t, (const uint32_t *)(a.ctl + kCtlBad), tb, a.mark, a.bstat}, st)) != hipSuccess) return e;
+        // the per-block, per-pair and per-item walks are latency-bound threads: one wave per workgroup spreads them over the CUs
+        hipLaunchKernelGGL(k_ls_block, dim3((uint32_t)((tb + 63) / 64)), dim3(64), 0, st, a);
+        if ((e = launch_excl_scan2(a.cnt, a.kb, tb, a.tx, a.ty, a.pc, a.pk, st)) != hipSuccess) return e;
+        if ((e = launch_excl_scan2(a.bbad, a.rd, tb, a.tx, a.ty, a.pb, a.pr, st)) != hipSuccess) return e;
+        hipLaunchKernelGGL((k_ls_edge<PROJ, MEM>), dim3(scan_grid(SP, 64)), dim3(64), 0, st, a);
+    }
+    hipLaunchKernelGGL(k_ls_rstat<MEM>, dim3(rw), dim3(64), 0, st, a);
+    if ((e = launch_excl_scan2(a.pit, a.pit, P, a.tx, a.ty, a.pis, a.cs, st)) != hipSuccess) return e;
+    if ((e = launch_excl_scan2(a.pn, a.pkb, P, a.tx, a.ty, a.cs, a.cks, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_ls_gate, dim3(scan_grid(ce, 256)), dim3(256), 0, st, a);
+    if (tree) hipLaunchKernelGGL(k_ls_stage<MEM>, dim3(scan_grid(ce + P, 64)), dim3(64), 0, st, a);
+    if constexpr (MEM) hipLaunchKernelGGL(k_ls_trows, dim3(scan_grid(ce, 256)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_ls_rank, dim3(scan_grid(ce, 64)), dim3(64), 0, st, a);
+    if (a.merge) {
+        hipLaunchKernelGGL(k_ls_links, dim3(scan_grid(ce, 64)), dim3(64), 0, st, a);
+        if ((e = launch_excl_scan2(a.wl, a.wl, ce, a.tx, a.ty, a.wlpos, a.wldum, st)) != hipSuccess) return e;
+    }
+    if ((e = launch_excl_scan2(a.wn, a.wkb, ce, a.tx, a.ty, a.wpos, a.wkpos, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_ls_count, dim3(rw), dim3(64), 0, st, a);
+    if ((e = launch_excl_scan2(a.rn, a.rkb, n, a.tx, a.ty, a.out.range_entry_start, a.rks, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_ls_final, dim3(1), dim3(64), 0, st, a);
+    if (a.merge) hipLaunchKernelGGL(k_ls_fold<MEM>, dim3(scan_grid(ce, 64)), dim3(64), 0, st, a);
+    hipLaunchKernelGGL(k_ls_emit<MEM>, dim3(scan_grid(ce, 64)), dim3(64), 0, st, a);
+    return hipGetLastError();
+}
+
+// The five instantiations there are: tables come with the filters, and projections too.
+static hipError_t launch_ls_bound(const LsArgs &a, bool projected, bool tabs, bool tree, hipStream_t st) {
+    if (tabs) return projected ? launch_ls_kernels<true, true, true>(a, tree, st) : launch_ls_kernels<true, false, true>(a, tree, st);
+    if (projected) return launch_ls_kernels<true, true, false>(a, tree, st);
+    return a.filter ? launch_ls_kernels<true, false, false>(a, tree, st) : launch_ls_kernels<false, false, false>(a, tree, st);
+}
+
+// The scan of one call (the special cases: the file comment).  tabs: c.mem holds a table and there is a range (with
+// c.mout, and c.mchain iff c.chain).
+static hipError_t launch_ls_search(const ScanCall &c, bool tabs, uint8_t *w, hipStream_t st) {
+    const sdb_lsm_view &t = *c.lsm;
+    const sdb_lsm_scan_out &out = *c.out;
+    const sdb_chain_out *chain = c.chain;
+    const sdb_scan_filter_out *fout = c.filter ? c.fout : nullptr;
+    const uint64_t n = c.ranges->n;
+    const bool no_tree = t.num_ssts == 0 || t.total_blocks == 0 || (tabs && t.num_runs == 0);
+    hipError_t e;
+    if (n == 0 || (no_tree && !tabs)) {  // every range is empty
         if (chain) {
             if ((e = hipMemsetAsync(chain->summary, 0, sizeof(sdb_chain_summary), st)) != hipSuccess) return e;
             if ((e = hipMemsetAsync(chain->chain_start, 0, 8, st)) != hipSuccess) return e;
@@ -959,125 +1020,51 @@ static hipError_t launch_lsm_scan_layers(const sdb_mem_view *mem, const sdb_lsm_
     }
     LsArgs a{};
     a.t = t;
-    a.r = r;
-    a.max_seq = max_seq;
+    a.r = *c.ranges;
+    a.max_seq = c.max_seq;
     a.out = out;
-    a.desc = desc;
-    a.cand_entries = cand_entries;
-    a.cand_key_bytes = cand_key_bytes;
+    a.desc = c.desc;
+    a.cand_entries = c.cand_entries;
+    a.cand_key_bytes = c.cand_key_bytes;
     if (chain) {
         a.merge = 1;
         a.chain = *chain;
     }
-    if (mem) {
-        a.tabs = mem->tables;
-        a.ntab = mem->num_tables;
-        a.mout = *mout;
-        if (chain) a.mchain = *mchain;
-        if (no_tree) {  // (S8) only the tables are scanned, and nothing is read through the tree's arrays
+    const bool tree = !(tabs && no_tree);
+    if (tabs) {
+        a.tabs = c.mem->tables;
+        a.ntab = c.mem->num_tables;
+        a.mout = *c.mout;
+        if (chain) a.mchain = *c.mchain;
+        if (!tree) {  // (S8) only the tables are scanned, and nothing is read through the tree's arrays
             a.t.num_ssts = a.t.num_runs = 0;
             a.t.total_blocks = 0;
-            pol = nullptr;
-            proj = nullptr;
         }
     }
+    const bool projected = fout && tree && c.proj;
     if (fout) {
         a.filter = 1;
-        a.pol = pol;
-        if (px) a.px = *px;
+        a.pol = tree ? c.pol : nullptr;
+        if (c.prefixes) a.px = *c.prefixes;
         a.fout = *fout;
-        if (proj) a.proj = *proj;
-        lsm_scan_filter_bind(a, w, chain != nullptr);
-    } else if (chain) {
-        lsm_scan_merge_bind(a, w);
-    } else {
-        lsm_scan_bind(a, w);
+        if (projected) a.proj = *c.proj;
     }
-    const uint64_t tb = a.t.total_blocks, P = a.pairs, SP = a.spairs, ce = cand_entries;
-    const bool tree = !no_tree;
-    if (mem) {
-        if (tree) hipLaunchKernelGGL(k_ls_mreset, dim3(scan_grid(tb, 256)), dim3(256), 0, st, a.mark, a.bstat, tb);
-    } else {
-        if ((e = hipMemsetAsync(a.mark, 0, tb, st)) != hipSuccess) return e;
-        if ((e = hipMemsetAsync(a.bstat, 0xFF, 4 * tb, st)) != hipSuccess) return e;
-    }
-    const uint32_t rw = (uint32_t)((n + 63) / 64);
-    const bool pj = a.filter && proj;
-    if (pj) hipLaunchKernelGGL(k_ls_validate<true>, dim3(1), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_ls_validate<false>, dim3(1), dim3(256), 0, st, a);
-    if (mem) hipLaunchKernelGGL(k_ls_tvalidate, dim3(1), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_ls_ranges, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, a);
-    if (mem) hipLaunchKernelGGL(k_ls_tprobe, dim3(scan_grid(n * a.ntab, 256)), dim3(256), 0, st, a);
-    if (tree) {
-        if (mem && pj) hipLaunchKernelGGL((k_ls_locate<true, true, true>), dim3(scan_grid(SP, 256)), dim3(256), 0, st, a);
-        else if (mem) hipLaunchKernelGGL((k_ls_locate<true, false, true>), dim3(scan_grid(SP, 256)), dim3(256), 0, st, a);
-        else if (pj) hipLaunchKernelGGL((k_ls_locate<true, true>), dim3(scan_grid(SP, 256)), dim3(256), 0, st, a);
-        else if (a.filter) hipLaunchKernelGGL((k_ls_locate<true, false>), dim3(scan_grid(SP, 256)), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_ls_locate<false, false>), dim3(scan_grid(SP, 256)), dim3(256), 0, st, a);
-        if ((e = launch_check(CheckArgs{{}, a.t, (const uint32_t *)(a.ctl + kCtlBad), tb, a.mark, a.bstat}, st)) != hipSuccess) return e;
-        // the per-block, per-pair and per-item walks are latency-bound threads: one wave per workgroup spreads them over the CUs
-        hipLaunchKernelGGL(k_ls_block, dim3((uint32_t)((tb + 63) / 64)), dim3(64), 0, st, a);
-        if ((e = launch_excl_scan2(a.cnt, a.kb, tb, a.tx, a.ty, a.pc, a.pk, st)) != hipSuccess) return e;
-        if ((e = launch_excl_scan2(a.bbad, a.rd, tb, a.tx, a.ty, a.pb, a.pr, st)) != hipSuccess) return e;
-        if (mem && pj) hipLaunchKernelGGL((k_ls_edge<true, true>), dim3(scan_grid(SP, 64)), dim3(64), 0, st, a);
-        else if (mem) hipLaunchKernelGGL((k_ls_edge<false, true>), dim3(scan_grid(SP, 64)), dim3(64), 0, st, a);
-        else if (pj) hipLaunchKernelGGL(k_ls_edge<true>, dim3(scan_grid(SP, 64)), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL(k_ls_edge<false>, dim3(scan_grid(SP, 64)), dim3(64), 0, st, a);
-    }
-    if (mem) hipLaunchKernelGGL(k_ls_rstat<true>, dim3(rw), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL(k_ls_rstat<false>, dim3(rw), dim3(64), 0, st, a);
-    if ((e = launch_excl_scan2(a.pit, a.pit, P, a.tx, a.ty, a.pis, a.cs, st)) != hipSuccess) return e;
-    if ((e = launch_excl_scan2(a.pn, a.pkb, P, a.tx, a.ty, a.cs, a.cks, st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_ls_gate, dim3(scan_grid(ce, 256)), dim3(256), 0, st, a);
-    if (tree && mem) hipLaunchKernelGGL(k_ls_stage<true>, dim3(scan_grid(ce + P, 64)), dim3(64), 0, st, a);
-    else if (tree) hipLaunchKernelGGL(k_ls_stage<false>, dim3(scan_grid(ce + P, 64)), dim3(64), 0, st, a);
-    if (mem) {
-        hipLaunchKernelGGL(k_ls_trows, dim3(scan_grid(ce, 256)), dim3(256), 0, st, a);
-    }
-    hipLaunchKernelGGL(k_ls_rank, dim3(scan_grid(ce, 64)), dim3(64), 0, st, a);
-    if (chain) {
-        hipLaunchKernelGGL(k_ls_links, dim3(scan_grid(ce, 64)), dim3(64), 0, st, a);
-        if ((e = launch_excl_scan2(a.wl, a.wl, ce, a.tx, a.ty, a.wlpos, a.wldum, st)) != hipSuccess) return e;
-    }
-    if ((e = launch_excl_scan2(a.wn, a.wkb, ce, a.tx, a.ty, a.wpos, a.wkpos, st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_ls_count, dim3(rw), dim3(64), 0, st, a);
-    if ((e = launch_excl_scan2(a.rn, a.rkb, n, a.tx, a.ty, out.range_entry_start, a.rks, st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_ls_final, dim3(1), dim3(64), 0, st, a);
-    if (chain && mem) hipLaunchKernelGGL(k_ls_fold<true>, dim3(scan_grid(ce, 64)), dim3(64), 0, st, a);
-    else if (chain) hipLaunchKernelGGL(k_ls_fold<false>, dim3(scan_grid(ce, 64)), dim3(64), 0, st, a);
-    if (mem) hipLaunchKernelGGL(k_ls_emit<true>, dim3(scan_grid(ce, 64)), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL(k_ls_emit<false>, dim3(scan_grid(ce, 64)), dim3(64), 0, st, a);
-    return hipGetLastError();
+    lsm_scan_bind_for(a, w, chain != nullptr, fout != nullptr);
+    return launch_ls_bound(a, projected, tabs, tree, st);
 }
 
-hipError_t launch_lsm_scan(const sdb_lsm_view &t, const sdb_scan_ranges &r, const uint64_t *max_seq, uint32_t desc,
-                           uint64_t cand_entries, uint64_t cand_key_bytes, const sdb_lsm_scan_out &out,
-                           const sdb_chain_out *chain /* sdb_lsm_scan_merge, else nullptr */,
-                           const sdb_filter_policy *pol, const sdb_scan_prefixes *px,
-                           const sdb_scan_filter_out *fout /* sdb_lsm_scan_filtered, else nullptr */,
-                           const sdb_scan_ranges *proj /* sdb_lsm_scan_projected (with fout), else nullptr */, uint8_t *w,
-                           hipStream_t st) {
-    return launch_lsm_scan_layers(nullptr, t, r, max_seq, desc, cand_entries, cand_key_bytes, out, nullptr, chain, nullptr, pol,
-                                  px, fout, proj, w, st);
-}
-
-hipError_t launch_lsm_scan_mem(const sdb_mem_view *mem, const sdb_lsm_view &t, const sdb_scan_ranges &r,
-                               const uint64_t *max_seq, uint32_t desc, uint64_t cand_entries, uint64_t cand_key_bytes,
-                               const sdb_lsm_scan_out &out, const sdb_mem_scan_out &mout, const sdb_chain_out *chain,
-                               const sdb_mem_chain_out *mchain, const sdb_filter_policy *pol, const sdb_scan_prefixes *px,
-                               const sdb_scan_filter_out &fout, const sdb_scan_ranges *proj, uint8_t *w, hipStream_t st) {
-    if (mem && mem->num_tables && r.n)
-        return launch_lsm_scan_layers(mem, t, r, max_seq, desc, cand_entries, cand_key_bytes, out, &mout, chain, mchain, pol, px,
-                                      &fout, proj, w, st);
-    // (S7) no tables: the projected call, and no row, link or range names a table
-    hipError_t e = launch_lsm_scan(t, r, max_seq, desc, cand_entries, cand_key_bytes, out, chain, pol, px, &fout, proj, w, st);
-    if (e != hipSuccess) return e;
-    uint64_t most = std::max(r.n, out.cap_entries);
+hipError_t launch_lsm_scan(const ScanCall &c, uint8_t *w, hipStream_t st) {
+    const bool tabs = c.mem && c.mem->num_tables && c.ranges->n;
+    hipError_t e = launch_ls_search(c, tabs, w, st);
+    if (e != hipSuccess || tabs || !c.layers) return e;
+    // (S7) sdb_lsm_scan_mem without a table: the projected call, and no row, link or range names a table
+    const sdb_chain_out *chain = c.chain;
+    uint64_t most = std::max(c.ranges->n, c.out->cap_entries);
     if (chain) most = std::max(most, chain->cap_links);
     if (most)
-        hipLaunchKernelGGL(k_ls_mfill, dim3(scan_grid(most, 256)), dim3(256), 0, st, out, mout, r.n,
+        hipLaunchKernelGGL(k_ls_mfill, dim3(scan_grid(most, 256)), dim3(256), 0, st, *c.out, *c.mout, c.ranges->n,
                            chain ? chain->summary : nullptr, chain ? chain->cap_links : 0,
-                           chain ? *mchain : sdb_mem_chain_out{nullptr, nullptr});
+                           chain ? *c.mchain : sdb_mem_chain_out{nullptr, nullptr});
     return hipGetLastError();
 }
 

@@ -871,17 +871,66 @@ def _projections(projections, tree):
                                _ptr(pt["end_bytes"]), _ptr(pt["end_off"]), _ptr(pt["end_kind"]))
 
 
-def _lsm_get(entry, views, runs, keys, max_seq, stream, workspace, merge=False, cap_links=None, fill=0, filtered=False,
-             probe_len=None, projected=False, projections=None, mem=None):
-    """The tree gets.  entry: the C entry point (sdb_lsm_get, sdb_lsm_get_merge, sdb_lsm_get_filtered or
-    sdb_lsm_get_projected; its sizer is entry + "_workspace_bytes"); filtered: it takes the policies, probe_len and an
-    optional chain; projected: it is a filtered call that takes the projections too; merge: the
+# The ten tree reads: symbol -> (the entry point's arguments, its sizer's), in C order, each under the name _lsm_get and
+# _lsm_scan marshal it by; every entry point ends with (workspace, workspace_bytes, stream).  What a symbol takes is
+# what its tuple names: policies and probe_len / prefixes and fout from _filtered on, proj from _projected on, mem,
+# mout and mchain for _mem; a sizer takes merge where the entry point's chain is optional.
+_TREE, _CAND, _KEYS = ("total_blocks", "num_ssts", "num_runs", "n"), ("ce", "ckb"), ("key_bytes", "key_off", "n")
+_SCAN = ("max_seq", "descending") + _CAND + ("out",)
+READ_CALLS = {
+    "sdb_lsm_get": (("lsm",) + _KEYS + ("max_seq", "out"), _TREE),
+    "sdb_lsm_get_merge": (("lsm",) + _KEYS + ("max_seq", "out", "chain"), _TREE),
+    "sdb_lsm_get_filtered": (("lsm", "policies") + _KEYS + ("probe_len", "max_seq", "out", "chain"), _TREE + ("merge",)),
+    "sdb_lsm_get_projected": (("lsm", "proj", "policies") + _KEYS + ("probe_len", "max_seq", "out", "chain"),
+                              _TREE + ("merge",)),
+    "sdb_lsm_get_mem": (("mem", "lsm", "proj", "policies") + _KEYS + ("probe_len", "max_seq", "out", "mout", "chain", "mchain"),
+                        ("num_tables",) + _TREE + ("merge",)),
+    "sdb_lsm_scan": (("lsm", "ranges") + _SCAN, _TREE + _CAND),
+    "sdb_lsm_scan_merge": (("lsm", "ranges") + _SCAN + ("chain",), _TREE + _CAND),
+    "sdb_lsm_scan_filtered": (("lsm", "policies", "ranges", "prefixes") + _SCAN + ("chain", "fout"), _TREE + _CAND + ("merge",)),
+    "sdb_lsm_scan_projected": (("lsm", "proj", "policies", "ranges", "prefixes") + _SCAN + ("chain", "fout"),
+                               _TREE + _CAND + ("merge",)),
+    "sdb_lsm_scan_mem": (("mem", "lsm", "proj", "policies", "ranges", "prefixes") + _SCAN + ("mout", "chain", "mchain", "fout"),
+                         ("num_tables",) + _TREE + _CAND + ("merge",)),
+}
+
+
+def _read_workspace_bytes(entry, v):
+    """What entry's sizer answers for the marshalled values v."""
+    return getattr(lib(), entry + "_workspace_bytes")(*[v[a] for a in READ_CALLS[entry][1]])
+
+
+def _read_call(entry, v, ws, wsb, stream):
+    """The C call of a tree read over the marshalled values v; raises SdbError on a status."""
+    st = getattr(lib(), entry)(*[v[a] for a in READ_CALLS[entry][0]], ws.data_ptr(), wsb, _sp(stream))
+    if st:
+        raise SdbError(st, entry)
+
+
+def _byref(struct):
+    return C.byref(struct) if struct is not None else None
+
+
+def _read_values(tree, mem, pj, merge):
+    """What both families marshal alike: the tables (mem_tables_device's, or None), the tree and its shape, the
+    projections (_projections' struct, or None), the policies and the sizers' merge."""
+    return {"mem": _byref(mem["mem"] if mem else None), "num_tables": mem["num_tables"] if mem else 0,
+            "lsm": C.byref(tree["lsm"]), "total_blocks": tree["total_blocks"], "num_ssts": tree["num_ssts"],
+            "num_runs": tree["num_runs"], "proj": _byref(pj), "policies": _ptr(tree.get("_policies")),
+            "merge": int(bool(merge))}
+
+
+def _lsm_get(entry, views, runs, keys, max_seq, stream, workspace, merge=False, cap_links=None, fill=0, probe_len=None,
+             projections=None, mem=None):
+    """The tree gets.  entry: the C entry point, a key of READ_CALLS, which names what it takes: the filtered ones
+    the policies, probe_len and an optional chain, the projected ones the projections too; merge: the
     call has a chain.  Marshals the tree, the keys, the bounds and probe_len as device tensors, the result dict with
     the GET_FIELDS and the summary; a caller's workspace must hold the call; with merge and cap_links None the links
-    are sized at nkeys first and, when they did not fit, at the reported num_links in a second call.  mem: the entry
-    is sdb_lsm_get_mem: None (a NULL sdb_mem_view) or what mem_tables_device returned; the result then has table and
+    are sized at nkeys first and, when they did not fit, at the reported num_links in a second call.  mem: for
+    sdb_lsm_get_mem: None (a NULL sdb_mem_view) or what mem_tables_device returned; the result then has table and
     row (MEM_FIELDS) and, with a chain, chain_table and chain_row."""
     import torch
+    takes = READ_CALLS[entry][0]
     tree = views if isinstance(views, dict) else lsm_tree_device(views, runs)
     dev = tree["device"]
     if isinstance(keys, (tuple, list)) and len(keys) == 3 and hasattr(keys[0], "data_ptr"):
@@ -895,32 +944,22 @@ def _lsm_get(entry, views, runs, keys, max_seq, stream, workspace, merge=False, 
         probe_len = _to_dev(np.asarray(list(probe_len) or [0], np.int32), dev)
     res = {f: torch.zeros(max(n, 1), dtype=getattr(torch, dt), device=dev) for f, dt in GET_FIELDS}
     res["summary"] = torch.zeros(len(GET_SUMMARY), dtype=torch.int64, device=dev)
-    out = _abi.GetOut(*[res[f].data_ptr() for f, _ in GET_FIELDS], res["summary"].data_ptr())
-    layers = entry == "sdb_lsm_get_mem"
-    if layers:
+    pjt, pj = _projections(projections, tree)
+    v = _read_values(tree, mem, pj, merge)
+    v.update(key_bytes=kb.data_ptr(), key_off=ko.data_ptr(), n=n, probe_len=_ptr(probe_len), max_seq=_ptr(max_seq),
+             out=C.byref(_abi.GetOut(*[res[f].data_ptr() for f, _ in GET_FIELDS], res["summary"].data_ptr())))
+    if "mout" in takes:
         for f, dt in MEM_FIELDS:  # (every call writes all n of them: no fill)
             res[f] = torch.empty(max(n, 1), dtype=getattr(torch, dt), device=dev)
-        mout = _abi.MemGetOut(*[res[f].data_ptr() for f, _ in MEM_FIELDS])
-    wsb = getattr(lib(), entry + "_workspace_bytes")(*([mem["num_tables"] if mem else 0] if layers else []),
-                                                     tree["total_blocks"], tree["num_ssts"], tree["num_runs"], n,
-                                                     *([int(bool(merge))] if filtered else []))
+        v["mout"] = C.byref(_abi.MemGetOut(*[res[f].data_ptr() for f, _ in MEM_FIELDS]))
+    wsb = _read_workspace_bytes(entry, v)
     ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=dev)
     assert ws.numel() >= wsb, "workspace too small"
-    pjt, pj = _projections(projections, tree)
 
     def run(cap):
-        chain = _chain_out(res, n, cap, dev, fill) if merge else None
-        args = [C.byref(mem["mem"]) if mem else None] if layers else []
-        args += [C.byref(tree["lsm"])] + ([C.byref(pj) if pj is not None else None] if projected else [])
-        args += ([_ptr(tree.get("_policies"))] if filtered else [])
-        args += [kb.data_ptr(), ko.data_ptr(), n] + ([_ptr(probe_len)] if filtered else [])
-        args += [_ptr(max_seq), C.byref(out)] + ([C.byref(mout)] if layers else [])
-        args += ([C.byref(chain) if merge else None] if merge or filtered else [])
-        if layers:
-            args += [C.byref(_mem_chain_out(res, cap, dev, fill)) if merge else None]
-        st = getattr(lib(), entry)(*args, ws.data_ptr(), wsb, _sp(stream))
-        if st:
-            raise SdbError(st, entry)
+        v["chain"] = C.byref(_chain_out(res, n, cap, dev, fill)) if merge else None
+        v["mchain"] = C.byref(_mem_chain_out(res, cap, dev, fill)) if merge and "mchain" in takes else None
+        _read_call(entry, v, ws, wsb, stream)
 
     if merge and cap_links is None:
         run(n)  # one link per query is the least a tree of values needs
@@ -963,20 +1002,19 @@ def _lsm_scan_out(res, cap_e, cap_k, dev):
 
 
 def _lsm_scan(entry, tree, ranges, max_seq, descending, stream, workspace, cand, cap, merge=False, cap_links=None, fill=0,
-              filtered=False, prefixes=None, probe_len=None, projected=False, projections=None, mem=None):
-    """The tree scans.  entry: the C entry point (sdb_lsm_scan, sdb_lsm_scan_merge, sdb_lsm_scan_filtered or
-    sdb_lsm_scan_projected; its sizer is entry + "_workspace_bytes"); filtered: it takes the policies, the prefixes, an
-    optional chain and the filter outputs; projected: it is a filtered call that takes the projections too; merge: the
-    call has a chain.  Marshals the ranges, the bounds, the prefixes and the projections as device tensors and the
+              prefixes=None, probe_len=None, projections=None, mem=None):
+    """The tree scans.  entry: the C entry point, a key of READ_CALLS, which names what it takes: the filtered ones
+    the policies, the prefixes, an optional chain and the filter outputs, the projected ones the projections too; merge:
+    the call has a chain.  Marshals the ranges, the bounds, the prefixes and the projections as device tensors and the
     result dict; a caller's workspace that is too small is replaced by a fresh one, unless cand was given.
     With a capacity None (cap_links counts only with merge) the call runs once, and on SDB_LIMIT_EXCEEDED again
     with the staging at max(given, reported), cap like the staging and cap_links like cand_entries where those
-    were None.  mem: the entry is sdb_lsm_scan_mem: None (a NULL sdb_mem_view) or what mem_tables_device returned; the
+    were None.  mem: for sdb_lsm_scan_mem: None (a NULL sdb_mem_view) or what mem_tables_device returned; the
     result then has table and row per output row (MEM_FIELDS), range_tables and, with a chain, chain_table and
     chain_row."""
     import torch
+    takes = READ_CALLS[entry][0]
     dev = tree["device"]
-    layers = entry == "sdb_lsm_scan_mem"
     if isinstance(ranges, dict):
         rt, n = ranges, int(ranges["n"])
     else:
@@ -990,46 +1028,38 @@ def _lsm_scan(entry, tree, ranges, max_seq, descending, stream, workspace, cand,
            "range_status": torch.zeros(max(n, 1), dtype=torch.int32, device=dev),
            "range_ssts": torch.zeros(max(n, 1), dtype=torch.int32, device=dev),
            "summary": torch.zeros(len(LSM_SCAN_SUMMARY), dtype=torch.int64, device=dev)}
+    pjt, pj = _projections(projections, tree)
+    v = _read_values(tree, mem, pj, merge)
+    v.update(ranges=C.byref(rg), n=n, max_seq=_ptr(max_seq), descending=int(bool(descending)))
     pt = prefixes
-    if filtered:
+    if "prefixes" in takes:
         if prefixes is not None and not isinstance(prefixes, dict):
             assert len(prefixes) == n, "one prefix (or None) per range"
             pt = {k: None if a is None else _to_dev(a, dev) for k, a in scan_prefixes_columnar(prefixes, probe_len).items()}
-        px = None if pt is None else _abi.ScanPrefixes(_ptr(pt["prefix_bytes"]), _ptr(pt["prefix_off"]),
-                                                       _ptr(pt["has_prefix"]), _ptr(pt.get("probe_len")))
+        v["prefixes"] = _byref(None if pt is None else _abi.ScanPrefixes(
+            _ptr(pt["prefix_bytes"]), _ptr(pt["prefix_off"]), _ptr(pt["has_prefix"]), _ptr(pt.get("probe_len"))))
+    if "fout" in takes:
         res["range_filtered"] = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
         res["num_filtered"] = torch.zeros(1, dtype=torch.int64, device=dev)
-        fout = _abi.ScanFilterOut(res["range_filtered"].data_ptr(), res["num_filtered"].data_ptr())
-    pjt, pj = _projections(projections, tree)
-    if layers:
+        v["fout"] = C.byref(_abi.ScanFilterOut(res["range_filtered"].data_ptr(), res["num_filtered"].data_ptr()))
+    if "mout" in takes:
         res["range_tables"] = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
 
     def run(ce, ckb, cap_e, cap_k, cap_l):
-        wsb = getattr(lib(), entry + "_workspace_bytes")(*([mem["num_tables"] if mem else 0] if layers else []),
-                                                         tree["total_blocks"], tree["num_ssts"], tree["num_runs"], n, ce,
-                                                         ckb, *([int(bool(merge))] if filtered else []))
+        v.update(ce=ce, ckb=ckb)
+        wsb = _read_workspace_bytes(entry, v)
         ws = workspace if workspace is not None and workspace.numel() >= wsb else None
         if ws is None:
             assert workspace is None or cand is None, "workspace too small"
             ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        out = _lsm_scan_out(res, cap_e, cap_k, dev)
-        chain = _chain_out(res, cap_e, cap_l, dev, fill) if merge else None
-        args = [C.byref(mem["mem"]) if mem else None] if layers else []
-        args += [C.byref(tree["lsm"])] + ([C.byref(pj) if pj is not None else None] if projected else [])
-        args += ([_ptr(tree.get("_policies"))] if filtered else []) + [C.byref(rg)]
-        args += ([C.byref(px) if px is not None else None] if filtered else [])
-        args += [_ptr(max_seq), int(bool(descending)), ce, ckb, C.byref(out)]
-        if layers:  # (rows that no call writes name no table)
+        v["out"] = C.byref(_lsm_scan_out(res, cap_e, cap_k, dev))
+        v["chain"] = C.byref(_chain_out(res, cap_e, cap_l, dev, fill)) if merge else None
+        if "mout" in takes:  # (rows that no call writes name no table)
             res["table"] = torch.full((max(cap_e, 1),), -1, dtype=torch.int32, device=dev)
             res["row"] = torch.zeros(max(cap_e, 1), dtype=torch.int64, device=dev)
-            args += [C.byref(_abi.MemScanOut(res["table"].data_ptr(), res["row"].data_ptr(), res["range_tables"].data_ptr()))]
-        args += ([C.byref(chain) if merge else None] if merge or filtered else [])
-        if layers:
-            args += [C.byref(_mem_chain_out(res, cap_l, dev, fill)) if merge else None]
-        args += [C.byref(fout)] if filtered else []
-        st = getattr(lib(), entry)(*args, ws.data_ptr(), wsb, _sp(stream))
-        if st:
-            raise SdbError(st, entry)
+            v["mout"] = C.byref(_abi.MemScanOut(res["table"].data_ptr(), res["row"].data_ptr(), res["range_tables"].data_ptr()))
+        v["mchain"] = C.byref(_mem_chain_out(res, cap_l, dev, fill)) if merge and "mchain" in takes else None
+        _read_call(entry, v, ws, wsb, stream)
         res["_ws"] = ws
 
     if cand is None or cap is None or (merge and cap_links is None):
@@ -1119,8 +1149,7 @@ def lsm_scan_filtered_device(tree, ranges, prefixes=None, probe_len=None, max_se
     lengths for SDB_PREFIX_LENGTHS SSTs.  The other arguments, the retry once on SDB_LIMIT_EXCEEDED and the result
     are the unfiltered call's, plus range_filtered (n) and num_filtered (one element)."""
     return _lsm_scan("sdb_lsm_scan_filtered", tree, ranges, max_seq, descending, stream, workspace, cand, cap,
-                     merge=bool(merge), cap_links=cap_links, fill=fill, filtered=True, prefixes=prefixes,
-                     probe_len=probe_len)
+                     merge=bool(merge), cap_links=cap_links, fill=fill, prefixes=prefixes, probe_len=probe_len)
 
 
 def lsm_get_filtered_device(views, runs, keys, probe_len=None, max_seq=None, stream=None, workspace=None, cap_links=None,
@@ -1131,7 +1160,7 @@ def lsm_get_filtered_device(views, runs, keys, probe_len=None, max_seq=None, str
     SSTs (-1: None), or a device int32 tensor.  The other arguments, the retry on links that do not fit and the
     result are the unfiltered call's."""
     return _lsm_get("sdb_lsm_get_filtered", views, runs, keys, max_seq, stream, workspace, merge=bool(merge),
-                    cap_links=cap_links, fill=fill, filtered=True, probe_len=probe_len)
+                    cap_links=cap_links, fill=fill, probe_len=probe_len)
 
 
 def lsm_scan_projected_device(tree, projections, ranges, prefixes=None, probe_len=None, max_seq=None, descending=False,
@@ -1141,8 +1170,8 @@ def lsm_scan_projected_device(tree, projections, ranges, prefixes=None, probe_le
     whole SST, else (start, start_kind, end, end_kind)), or a dict of device tensors named as projections_columnar's
     arrays plus "n".  The other arguments and the result are the filtered call's."""
     return _lsm_scan("sdb_lsm_scan_projected", tree, ranges, max_seq, descending, stream, workspace, cand, cap,
-                     merge=bool(merge), cap_links=cap_links, fill=fill, filtered=True, prefixes=prefixes,
-                     probe_len=probe_len, projected=True, projections=projections)
+                     merge=bool(merge), cap_links=cap_links, fill=fill, prefixes=prefixes,
+                     probe_len=probe_len, projections=projections)
 
 
 def lsm_get_projected_device(views, runs, projections, keys, probe_len=None, max_seq=None, stream=None, workspace=None,
@@ -1150,8 +1179,7 @@ def lsm_get_projected_device(views, runs, projections, keys, probe_len=None, max
     """sdb_lsm_get_projected: lsm_get_filtered_device over projected SST views; projections as
     lsm_scan_projected_device takes them.  The other arguments and the result are the filtered call's."""
     return _lsm_get("sdb_lsm_get_projected", views, runs, keys, max_seq, stream, workspace, merge=bool(merge),
-                    cap_links=cap_links, fill=fill, filtered=True, probe_len=probe_len, projected=True,
-                    projections=projections)
+                    cap_links=cap_links, fill=fill, probe_len=probe_len, projections=projections)
 
 
 MEM_FIELDS = (("table", "int32"), ("row", "int64"))
@@ -1189,8 +1217,7 @@ def lsm_get_mem_device(tables, views, runs, keys, max_seq=None, projections=None
     tree decided, or nothing) and, with merge, chain_table and chain_row per link."""
     mem = tables if tables is None or isinstance(tables, dict) else mem_tables_device(tables)
     return _lsm_get("sdb_lsm_get_mem", views, runs, keys, max_seq, stream, workspace, merge=bool(merge),
-                    cap_links=cap_links, fill=fill, filtered=True, probe_len=probe_len, projected=True,
-                    projections=projections, mem=mem)
+                    cap_links=cap_links, fill=fill, probe_len=probe_len, projections=projections, mem=mem)
 
 
 def lsm_scan_mem_device(tables, tree, ranges, projections=None, prefixes=None, probe_len=None, max_seq=None,
@@ -1203,8 +1230,8 @@ def lsm_scan_mem_device(tables, tree, ranges, projections=None, prefixes=None, p
     an SST holds the row), range_tables (n) and, with merge, chain_table and chain_row per link."""
     mem = tables if tables is None or isinstance(tables, dict) else mem_tables_device(tables, tree["device"])
     return _lsm_scan("sdb_lsm_scan_mem", tree, ranges, max_seq, descending, stream, workspace, cand, cap,
-                     merge=bool(merge), cap_links=cap_links, fill=fill, filtered=True, prefixes=prefixes,
-                     probe_len=probe_len, projected=True, projections=projections, mem=mem)
+                     merge=bool(merge), cap_links=cap_links, fill=fill, prefixes=prefixes,
+                     probe_len=probe_len, projections=projections, mem=mem)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""Generate tests/golden/read_workspace_bytes.json: what the six sdb_lsm_*_workspace_bytes functions of the built
+"""Generate tests/golden/read_workspace_bytes.json: what the ten sdb_lsm_*_workspace_bytes functions of the built
 library return over a small grid.  The sizes are part of the C contract (a caller may have allocated by them), so
 the fixture is recorded once and tests/test_read_workspace_bytes.py holds every later build to it.
 
@@ -19,14 +19,18 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 OUT = os.path.join(HERE, "read_workspace_bytes.json")
 
 GRID = {"total_blocks": [0, 1, 7, 1025], "num_ssts": [0, 1, 5], "num_runs": [0, 1, 3], "n": [0, 1, 1023, 1025],
-        "cand": [[0, 0], [16, 256], [1025, 40000]], "merge": [0, 1]}
+        "cand": [[0, 0], [16, 256], [1025, 40000]], "merge": [0, 1], "num_tables": [0, 1, 3]}
 TREE = ("total_blocks", "num_ssts", "num_runs", "n")
 AXES = {"sdb_lsm_get_workspace_bytes": TREE,
         "sdb_lsm_get_merge_workspace_bytes": TREE,
         "sdb_lsm_get_filtered_workspace_bytes": TREE + ("merge",),
         "sdb_lsm_scan_workspace_bytes": TREE + ("cand",),
         "sdb_lsm_scan_merge_workspace_bytes": TREE + ("cand",),
-        "sdb_lsm_scan_filtered_workspace_bytes": TREE + ("cand", "merge")}
+        "sdb_lsm_scan_filtered_workspace_bytes": TREE + ("cand", "merge"),
+        "sdb_lsm_get_projected_workspace_bytes": TREE + ("merge",),
+        "sdb_lsm_get_mem_workspace_bytes": ("num_tables",) + TREE + ("merge",),
+        "sdb_lsm_scan_projected_workspace_bytes": TREE + ("cand", "merge"),
+        "sdb_lsm_scan_mem_workspace_bytes": ("num_tables",) + TREE + ("cand", "merge")}
 
 
 def sizes(lib):

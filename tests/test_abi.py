@@ -217,3 +217,14 @@ def test_integration_declares_every_entry_point():
     want = {f for f in header_functions() if not f.startswith("sdb_diag_")}
     missing = sorted(want - declared)
     assert not missing, missing
+
+
+def test_runtime_read_calls_match_the_signatures():
+    """runtime.READ_CALLS names the arguments of the ten tree reads and of their sizers: as many as each takes, the
+    three the entry points end with (workspace, workspace_bytes, stream) apart."""
+    from slatedb_amd import runtime
+    assert sorted(runtime.READ_CALLS) == sorted("sdb_lsm_%s%s" % (f, v) for f in ("get", "scan")
+                                                for v in ("", "_merge", "_filtered", "_projected", "_mem"))
+    for symbol, (call, sizer) in runtime.READ_CALLS.items():
+        assert len(call) + 3 == len(_abi.SIGNATURES[symbol][1]), symbol
+        assert len(sizer) == len(_abi.SIGNATURES[symbol + "_workspace_bytes"][1]), symbol
