@@ -311,6 +311,10 @@ sdb_status sdb_decode_blocks_at(const uint8_t *arena, const uint64_t *block_star
  *     ascending prefix of the per-block counts, so block k's entries are [N - bes[k+1], N - bes[k]).
  *     A V2 block whose restart regions do not start at restarts with shared == 0 and end at the next
  *     one reports SDB_CORRUPT_BLOCK (the reference asserts there, block_iterator_v2.rs:76).
+ *     Within a block the status is that of the first error in descending iteration order: restart 0's key
+ *     (decoded by DescendingBlockIteratorV2::new), then the highest failing restart region and in it its first
+ *     failing row; for V1 the first key, then the highest failing entry.  A V2 block without restarts yields
+ *     nothing and no error.
  *   SDB_DECODE_FAIL_FAST   read_blocks semantics (format/sst.rs:938-1038, all or nothing): the status is
  *     the first failing block's, in block order, with its checksum verified before its rows as
  *     decode_block does, and every column is unspecified when the call fails (without the flag the

@@ -687,8 +687,8 @@ static int emit_entry(dec_ctx *c, const uint8_t *key_a, size_t na, const uint8_t
                       int64_t ets) {
     const sdb_decoded_out *o = c->out;
     if (c->n >= o->cap_entries || c->key_bytes + na + nb > o->key_arena_cap) { c->overflow = 1; return 0; }
-    memcpy(o->key_arena + c->key_bytes, key_a, na);
-    memcpy(o->key_arena + c->key_bytes + na, key_b, nb);
+    if (na) memcpy(o->key_arena + c->key_bytes, key_a, na); /* (key_a is NULL in a block without restarts) */
+    if (nb) memcpy(o->key_arena + c->key_bytes + na, key_b, nb);
     o->key_off[c->n] = c->key_bytes;
     c->key_bytes += na + nb;
     o->key_off[c->n + 1] = c->key_bytes;
@@ -758,8 +758,8 @@ static sdb_status decode_one(dec_ctx *c, uint64_t base, size_t blen, uint16_t ve
             if (!emit_entry(c, cur, sh, d + suf, un, vpos, out_vlen, seq, f, cts, ets)) { st = SDB_INVALID_ARGUMENT; break; }
             /* current_key = restored key (block_iterator_v2.rs:246) */
             uint8_t *nk = (uint8_t *)malloc(sh + un ? sh + un : 1);
-            memcpy(nk, cur, sh);
-            memcpy(nk + sh, d + suf, un);
+            if (sh) memcpy(nk, cur, sh);
+            if (un) memcpy(nk + sh, d + suf, un);
             free(cur);
             cur = nk;
             curlen = (size_t)sh + un;
@@ -767,8 +767,8 @@ static sdb_status decode_one(dec_ctx *c, uint64_t base, size_t blen, uint16_t ve
         free(cur);
         return st;
     }
-    /* V1: BlockIterator (block_iterator.rs:192-240): entries addressed by the offsets array. */
-    if (count == 0) return SDB_OK;
+    /* V1: BlockIterator (block_iterator.rs:192-240): entries addressed by the offsets array.
+     * BlockIterator::new reads the first key of every block, one without entries included (:196-203, 242-249) */
     if (data_end < 4) return SDB_CORRUPT_BLOCK;
     size_t ov = (size_t)rd_be(d, 2), fk = (size_t)rd_be(d + 2, 2);
     if (ov != 0 || 4 + fk > data_end) return SDB_CORRUPT_BLOCK; /* decode_first_key assert */
@@ -1526,6 +1526,12 @@ sdb_status orc_decode_blocks_desc(const uint8_t *blocks, const uint64_t *block_o
                     const size_t data_end = blen - 2 - 2 * count;
                     const uint8_t *offs = d + data_end;
                     if (sst_version == 2) {
+                        if (count > 0) { /* DescendingBlockIteratorV2::new decodes restart 0's key first (:332-338) */
+                            size_t q = (size_t)rd_be(offs, 2);
+                            uint32_t sh, un, vl;
+                            if (!rd_varint(d, data_end, &q, &sh) || !rd_varint(d, data_end, &q, &un) ||
+                                !rd_varint(d, data_end, &q, &vl) || sh != 0 || q + un > data_end) st = SDB_CORRUPT_BLOCK;
+                        }
                         for (size_t r = count; r-- > 0 && !st;) {
                             /* seek_to_restart(r): the restart row's key, shared == 0 asserted */
                             size_t p = (size_t)rd_be(offs + 2 * r, 2);
@@ -1558,8 +1564,8 @@ sdb_status orc_decode_blocks_desc(const uint8_t *blocks, const uint64_t *block_o
                                 uint8_t *tk = keys[a]; keys[a] = keys[b - 1]; keys[b - 1] = tk;
                             }
                         }
-                    } else if (count > 0) {
-                        /* V1: the ascending decode, then reversed */
+                    } else {
+                        /* V1: the ascending decode, then reversed (the first key is read whatever the count) */
                         if (data_end < 4) st = SDB_CORRUPT_BLOCK;
                         else {
                             size_t ov = (size_t)rd_be(d, 2), fk = (size_t)rd_be(d + 2, 2);

@@ -595,7 +595,7 @@ SDB_DEV Tally tally_v2(const BlockViewT<P> &v) {
     const int l = lane_id();
     const uint32_t R = v.count;
     bool regular = R > 0 && rd_be(v.offs, 2) == 0;
-    uint32_t my_entries = 0, my_kb = 0;
+    uint32_t my_entries = 0, my_kb = 0, my_bad = ~0u;  // my_bad: the region my_status was met in
     int my_status = 0;
     bool my_regular = true;
     for (uint32_t q = l; q < R && regular; q += 64) {
@@ -612,11 +612,13 @@ SDB_DEV Tally tally_v2(const BlockViewT<P> &v) {
             int st = parse_v2(v.d, v.data_end, pos, &r);
             if (st) {
                 my_status = st;
+                my_bad = q;
                 break;
             }
             if (firstrow && r.shared != 0) my_regular = false;
             if (!firstrow && r.shared > prevlen) {
                 my_status = SDB_CORRUPT_BLOCK;
+                my_bad = q;
                 break;
             }
             firstrow = false;
@@ -631,11 +633,16 @@ SDB_DEV Tally tally_v2(const BlockViewT<P> &v) {
     // wave-reduce: regular only if every lane stayed regular
     bool all_regular = regular && (__ballot(!my_regular) == 0);
     if (all_regular) {
-        // lowest-lane error wins (rows are in lane order within the block)
-        uint64_t bad = __ballot(my_status != 0);
-        if (bad) {
-            int first = __builtin_ctzll(bad);
-            t.status = __shfl(my_status, first, 64);
+        // the first failing row in row order wins: lane l walks regions l, l + 64, ..., so with more than 64
+        // regions that is the lowest failing region (lane region & 63), not the lowest failing lane
+        if (__ballot(my_status != 0)) {
+            uint32_t mn = my_bad;
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) {
+                const uint32_t o = __shfl_xor(mn, d, 64);
+                mn = o < mn ? o : mn;
+            }
+            t.status = __shfl(my_status, (int)(mn & 63), 64);
             return t;
         }
         t.entries = wave_sum((uint64_t)my_entries);
@@ -827,35 +834,39 @@ SDB_DEV bool tally_v2_spec(const LdsBlockView &v, Tally &t, uint16_t *rowpos, ui
     return true;
 }
 
+// descending: BlockIterator Descending (block_iterator.rs:218-227) loads the entries last to first, so the
+// highest failing entry decides.
 template <typename P>
-SDB_DEV Tally tally_v1(const BlockViewT<P> &v) {
+SDB_DEV Tally tally_v1(const BlockViewT<P> &v, bool descending) {
     Tally t{0, 0, 0, false};
     const int l = lane_id();
     const uint32_t R = v.count;
-    if (R == 0) return t;
-    // decode_first_key (block_iterator.rs:235-242)
+    // decode_first_key (block_iterator.rs:242-249), which BlockIterator::new (:196-203) runs on every block,
+    // one without entries included
     if (v.data_end < 4 || rd_be(v.d, 2) != 0 || 4 + rd_be(v.d + 2, 2) > v.data_end) {
         t.status = SDB_CORRUPT_BLOCK;
         return t;
     }
+    if (R == 0) return t;
     const uint32_t fk = (uint32_t)rd_be(v.d + 2, 2);
     uint64_t kb = 0;
     int st = 0;
-    uint64_t bad_first = ~0ull;
+    uint64_t bad_first = ~0ull;  // the failing entry met first in iteration order, as its place in that order
     for (uint32_t i = l; i < R; i += 64) {
         RowV0 r;
         int s = parse_v0(v.d, v.data_end, (uint32_t)rd_be(v.offs + 2 * i, 2), &r);
         if (!s && r.prefix > fk) s = SDB_CORRUPT_BLOCK;
         if (s) {
-            if (i < bad_first) {
-                bad_first = i;
+            const uint64_t at = descending ? R - 1 - i : i;
+            if (at < bad_first) {
+                bad_first = at;
                 st = s;
             }
             continue;
         }
         kb += r.prefix + r.suf;
     }
-    // lowest failing entry wins
+    // the first failing entry in iteration order wins
     uint64_t mn = bad_first;
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
@@ -877,14 +888,60 @@ SDB_DEV Tally tally_v1(const BlockViewT<P> &v) {
 // regular block (regions that start at restarts with shared == 0 and end exactly at the next one)
 // that is the ascending decode reversed; a block without restarts yields nothing; any other layout
 // is reported as SDB_CORRUPT_BLOCK (the reference would assert or read rows across regions).
-SDB_DEV void desc_rule(uint32_t restarts, Tally &t) {
-    if (t.status) return;
-    if (restarts == 0) {
-        t.entries = t.key_bytes = 0;
-        t.sequential = false;
-    } else if (t.sequential) {
-        t.status = SDB_CORRUPT_BLOCK;
+// Errors follow the same order: new() decodes restart 0's key (:332-338), then the highest failing region
+// decides, and inside it its first failing row.
+//
+// The status of restart region q as descending iteration meets it: seek_to_restart's key (shared == 0, inside the
+// data), the region's bounds, its rows in order, its end on the next restart.
+template <typename P>
+SDB_DEV int desc_region_status(const BlockViewT<P> &v, uint32_t q) {
+    uint32_t pos = (uint32_t)rd_be(v.offs + 2 * q, 2);
+    const uint32_t end = (q + 1 < v.count) ? (uint32_t)rd_be(v.offs + 2 * q + 2, 2) : v.data_end;
+    uint32_t p = pos, sh = 0, un = 0, vl = 0;
+    if (!rd_varint(v.d, v.data_end, &p, &sh) || !rd_varint(v.d, v.data_end, &p, &un) ||
+        !rd_varint(v.d, v.data_end, &p, &vl) || sh != 0 || (uint64_t)p + un > v.data_end)
+        return SDB_CORRUPT_BLOCK;
+    if (end <= pos || end > v.data_end || (q == 0 && pos != 0)) return SDB_CORRUPT_BLOCK;
+    uint32_t prevlen = 0;
+    while (pos < end) {
+        RowV2 r;
+        if (int st = parse_v2(v.d, v.data_end, pos, &r)) return st;
+        if (r.shared > prevlen) return SDB_CORRUPT_BLOCK;  // (0 at the restart: checked above)
+        prevlen = r.shared + r.unshared;
+        pos = r.next;
     }
+    return pos == end ? 0 : SDB_CORRUPT_BLOCK;
+}
+
+// Descending status and counts of a V2 block from its ascending tally.  Called by a whole wave; only a block
+// that failed or was walked sequentially is walked again (lane l: regions l, l + 64, ...).
+template <typename P>
+SDB_DEV void desc_rule(const BlockViewT<P> &v, Tally &t) {
+    if (v.count == 0) {  // exhausted at once (:352): nothing is decoded, whatever the bytes hold
+        t = Tally{0, 0, 0, false};
+        return;
+    }
+    if (!t.status && !t.sequential) return;
+    int st = 0;
+    {  // DescendingBlockIteratorV2::new: restart 0's key
+        uint32_t p = (uint32_t)rd_be(v.offs, 2), sh = 0, un = 0, vl = 0;
+        if (!rd_varint(v.d, v.data_end, &p, &sh) || !rd_varint(v.d, v.data_end, &p, &un) ||
+            !rd_varint(v.d, v.data_end, &p, &vl) || sh != 0 || (uint64_t)p + un > v.data_end)
+            st = SDB_CORRUPT_BLOCK;
+    }
+    if (!st) {
+        int my_status = 0;
+        uint32_t my_top = 0;  // 1 + the highest failing region of this lane
+        for (uint32_t q = (uint32_t)lane_id(); q < v.count; q += 64)
+            if (int s = desc_region_status(v, q)) {
+                my_status = s;
+                my_top = q + 1;
+            }
+        const uint32_t top = wave_max(my_top);
+        // (an irregular block has a failing region; were none found it would still be SDB_CORRUPT_BLOCK)
+        st = top ? __shfl(my_status, (int)((top - 1) & 63), 64) : SDB_CORRUPT_BLOCK;
+    }
+    t.status = st;
 }
 
 // --- blocks over one wave image (SstBlockSize 8 - 64 KiB): restart-region pieces --------------------
@@ -1075,10 +1132,10 @@ __global__ __launch_bounds__(kCntThreads) __attribute__((amdgpu_waves_per_eu(kCn
             DEC_T(t1);
             t.status = v.status;
             if (!v.status) {
-                if (a.version == 1) t = tally_v1(v);
+                if (a.version == 1) t = tally_v1(v, a.descending != 0);
                 else if (!tally_v2_spec(v, t, a.rowpos + 128 * k, &rcv) && !tally_v2_fast(v, t, a.rowpos + 128 * k, &rcv))
                     t = tally_v2(v);
-                if (a.descending && a.version == 2) desc_rule(v.count, t);
+                if (a.descending && a.version == 2) desc_rule(v, t);
             }
             if (a.fail_fast && t.status && !crc_staged_ok(img, (uint32_t)(s & 15), (uint32_t)(e - s - 4)))
                 t.status = SDB_CHECKSUM_MISMATCH;
@@ -1139,10 +1196,10 @@ __global__ __launch_bounds__(kCntThreads) __attribute__((amdgpu_waves_per_eu(kCn
         const BlockView v = load_block(a, k, stage, crc, kDecImg);
         t.status = v.status;
         if (!v.status) {
-            if (a.version == 1) t = tally_v1(v);
+            if (a.version == 1) t = tally_v1(v, a.descending != 0);
             else if (!tally_v2_pieces(a, s, v, img, t)) t = tally_v2(v);
         }
-        if (!v.status && a.descending && a.version == 2) desc_rule(v.count, t);
+        if (!v.status && a.descending && a.version == 2) desc_rule(v, t);
         count_result(a, k, t, kFlagGen);
         wave_sync_d();
     });

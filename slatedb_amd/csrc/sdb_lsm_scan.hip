@@ -302,11 +302,15 @@ __global__ __launch_bounds__(64) void k_ls_block(LsArgs a) {
         const sdb_sst_view v = a.t.ssts[i];
         Blk b;
         st = blk_open(v, k - a.t.block_base[i], b);
-        if (!st)
+        if (!st) {
             st = for_each_row(v.sst_version, b, [&](uint32_t x, uint32_t, const Row &r) {
                 cnt = x + 1;
                 kb += r.sh + r.un;
             });
+            // descending: the first error in that order (a V2 block without restarts is walked ascending here too)
+            if (st > 0 && a.desc && !(v.sst_version == 2 && b.count == 0))
+                if (const int ds = desc_status(v.sst_version, b)) st = ds;
+        }
     }
     if (st != 0) cnt = kb = 0;
     a.bstat[k] = st;

@@ -283,7 +283,7 @@ SDB_DEV int v1_row(const Blk &b, uint32_t i, Row &r) {
     r.sh = (uint32_t)be_at(b.d + p, 2);
     r.un = (uint32_t)be_at(b.d + p + 2, 2);
     p += 4;
-    if (r.sh > fk || (uint64_t)p + r.un + 9 > b.data_end) return SDB_CORRUPT_BLOCK;
+    if ((uint64_t)p + r.un + 9 > b.data_end) return SDB_CORRUPT_BLOCK;
     r.suf = p;
     p += r.un;
     if (int st = row_tail(b, p, r)) return st;
@@ -299,6 +299,9 @@ SDB_DEV int v1_row(const Blk &b, uint32_t i, Row &r) {
         r.vpos = p;
         p += r.vl;
     }
+    // restore_full_key slices first_key[..prefix] after the decode returned the row: a bad flags byte or a value
+    // past the data is reported before an over-long prefix, as sdb_decode_blocks reports them
+    if (r.sh > fk) return SDB_CORRUPT_BLOCK;
     r.next = p;
     return 0;
 }
@@ -402,13 +405,50 @@ SDB_DEV int for_each_row(uint32_t version, const Blk &b, F &&visit) {
             pos = r.next;
         }
     } else {
-        for (uint32_t i = 0; i < b.count; i++) {
+        // BlockIterator::new reads the first key of every block, one without entries included
+        if (b.data_end < 4 || be_at(b.d, 2) != 0 || 4 + (uint32_t)be_at(b.d + 2, 2) > b.data_end) st = SDB_CORRUPT_BLOCK;
+        for (uint32_t i = 0; !st && i < b.count; i++) {
             Row r;
             if ((st = v1_row(b, i, r))) break;
             visit(i, boff(b, i), r);
         }
     }
     return st;
+}
+
+// The status of a block for_each_row failed on (or found irregular) as descending iteration reports it: the first
+// error in that order.  V2 (DescendingBlockIteratorV2, block_iterator_v2.rs:318-428): new() decodes restart 0's key,
+// then the regions go last to first, each decoded ascending from its restart, so the highest failing region
+// decides and inside it its first failing row; a region that does not start at its restart with shared == 0 and
+// end on the next one fails with SDB_CORRUPT_BLOCK (the descending decode's rule).  V1 (BlockIterator Descending,
+// block_iterator.rs:218-227): the first key, then the highest failing entry.  0: the block is sound.
+SDB_DEV int desc_status(uint32_t version, const Blk &b) {
+    if (version != 2) {
+        if (b.data_end < 4 || be_at(b.d, 2) != 0 || 4 + (uint32_t)be_at(b.d + 2, 2) > b.data_end) return SDB_CORRUPT_BLOCK;
+        for (uint32_t i = b.count; i-- > 0;) {
+            Row r;
+            if (int st = v1_row(b, i, r)) return st;
+        }
+        return 0;
+    }
+    if (b.count == 0) return 0;
+    uint32_t kp, kn;
+    if (v2_restart_key(b, 0, kp, kn)) return SDB_CORRUPT_BLOCK;
+    for (uint32_t ri = b.count; ri-- > 0;) {
+        if (v2_restart_key(b, ri, kp, kn)) return SDB_CORRUPT_BLOCK;  // seek_to_restart
+        uint32_t pos = boff(b, ri), curlen = 0;
+        const uint32_t end = region_end(b, ri);
+        if (end <= pos || end > b.data_end || (ri == 0 && pos != 0)) return SDB_CORRUPT_BLOCK;
+        while (pos < end) {
+            Row r;
+            if (int st = v2_row(b, pos, r)) return st;
+            if (r.sh > curlen) return SDB_CORRUPT_BLOCK;  // (0 at the restart)
+            curlen = r.sh + r.un;
+            pos = r.next;
+        }
+        if (pos != end) return SDB_CORRUPT_BLOCK;
+    }
+    return 0;
 }
 
 // A row's value reference, seq, flags and timestamps into slot i of an out struct (sdb_lookup_out, sdb_scan_out,

@@ -206,7 +206,11 @@ __global__ __launch_bounds__(256) void k_sc_block(ScanArgs a) {
                 count(i, r, same);
                 if (have_t) c = i == 0 ? cmp_bytes(b.d + r.suf, r.un, t, nt, 0) : cmp_next(c, r.sh, b.d + r.suf, r.un, t, nt);
             });
-            if (!st && a.desc && (ri != b.count || !regular)) st = SDB_CORRUPT_BLOCK;  // the descending decode's rule
+            // the descending decode's rule and its order of errors: the first one descending iteration meets
+            if (a.desc && b.count && (st || ri != b.count || !regular)) {
+                const int ds = desc_status(2, b);
+                st = ds ? ds : SDB_CORRUPT_BLOCK;
+            }
             join = have_t && cnt > 0 && c.c == 0;
         } else {
             Row p{};
@@ -214,6 +218,7 @@ __global__ __launch_bounds__(256) void k_sc_block(ScanArgs a) {
                 count(i, r, a.desc && i > 0 && sc_same(a, b, r, p, 0));
                 p = r;
             });
+            if (st && a.desc) st = desc_status(1, b);  // descending: the highest failing entry decides
             if (!st && have_t && cnt > 0) join = v1_cmp(b, b.count - 1, t, nt, c) == 0 && c.c == 0;
         }
     }
