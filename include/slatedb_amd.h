@@ -39,6 +39,9 @@
  *                                 leaves them) searched ahead of the tree, with or without operand chains.
  *   - sdb_lsm_scan_mem         -> Reader::scan_with_options from the active memtable down (reader.rs:275-320,
  *                                 db_iter.rs:145-163): the same memtables merged ahead of the tree's SSTs.
+ *   - sdb_lsm_scan_recency     -> Reader::scan_prefix_by_recency_with_options (reader.rs:322-428) under
+ *                                 DbRecencyIterator (db_iter.rs:376-442): the same sources drained one after
+ *                                 another, newest first, up to a row limit; no merge, raw rows.
  *   - sdb_sst_builder_*        -> host-side mirror of EncodedSsTableBuilder's add()/build()/
  *                                 next_block() call order (sst_builder.rs:224-276), batching
  *                                 entries into a columnar pinned buffer and encoding on the GPU.
@@ -1485,6 +1488,80 @@ sdb_status sdb_lsm_scan_mem(const sdb_mem_view *mem /* or NULL */, const sdb_lsm
                             const sdb_mem_scan_out *mout, const sdb_chain_out *chain /* or NULL */,
                             const sdb_mem_chain_out *mchain /* iff chain */, const sdb_scan_filter_out *fout,
                             void *workspace, uint64_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Batched Db::scan_prefix_by_recency over device memtables and the tree (device): Db::scan_prefix_by_recency /
+ * scan_prefix_by_recency_with_options (db.rs:1140-1323) -> Reader::scan_prefix_by_recency_with_options
+ * (reader.rs:322-428) -> DbRecencyIterator (db_iter.rs:376-442), read up to a row limit.  This is NOT a merge: the
+ * sources are drained one after another, newest source first, nothing is deduplicated across them, tombstones and
+ * merge operands come back as raw rows, the key order restarts at every source boundary, and the caller is expected to
+ * stop early.  sdb_lsm_scan_recency takes what sdb_lsm_scan_mem takes, minus the chain and plus `limit`; the caller
+ * passes the prefix's range (BytesRange::from_prefix, reader.rs:345) in `ranges` and the prefix in `prefixes`, as for
+ * sdb_lsm_scan_filtered.  Everything not named here is as in sdb_lsm_scan_mem (S1-S10) and the calls it is the superset
+ * of.
+ *   R1. sources and walk order (reader.rs:374-424): tables 0 .. num_tables - 1, then the runs of `lsm`, newest first.
+ *       A sorted run is ONE source (SortedRunIterator, reader.rs:414-422), and an L0 SST is a run of one
+ *       (reader.rs:395-406).  Ascending, a run's SSTs are walked in `ssts` order.  Descending, a run's SSTs are walked
+ *       last to first, while the runs themselves stay newest first.  The reference's SortedRunIterator always pops
+ *       from the front, and segment_iterator.rs:44-45 states that descending over sorted runs is broken there: this
+ *       call implements the intended order.  A table without a row of the range, and a run none of whose SSTs takes
+ *       part in the range (rule 1 of sdb_lsm_scan, after the filters), hold nothing to open: they are no sources of
+ *       the range;
+ *   R2. rows of a source: the pair's candidates exactly as sdb_lsm_scan_mem defines them: participation, the filter
+ *       (F1-F3), the view range, the block clip, a table's stretch (S2).  Rows with seq > max_seq[r] are dropped per
+ *       source (apply_filters, db_iter.rs:354-374).  Nothing else is dropped: every visible version of every key is
+ *       a row.  A tombstone is a row with val_off = val_len = 0.  A merge operand is a row, never an error
+ *       (db_iter.rs:404-407): SDB_MERGE_OPERATOR_MISSING cannot come out of this call;
+ *   R3. order inside a source: ascending, the physical order (key ascending, seq descending).  Descending, the keys
+ *       descend and the versions of one key stay newest first, as sdb_sst_scan rule 3 (sst_iter.rs:567-651).  A
+ *       key's versions may straddle two SSTs of a run: each SST is ordered on its own and nothing is joined across
+ *       them;
+ *   R4. output: range r's rows are the concatenation over the walk order, at [range_entry_start[r],
+ *       range_entry_start[r + 1]).  The columns are those of S3 for "a row that a table won" / "a row that an SST
+ *       won": out->sst / mout->table, row, the flags as stored, the timestamps.  key_off and key_arena as in every
+ *       scan;
+ *   R5. limit and laziness (DbRecencyIterator::next_entry initialises a source only when the walk reaches it,
+ *       db_iter.rs:413-440).  With L = limit[r] > 0 the range returns the first L rows of R4.  The walk opens
+ *       source j iff the sources before it yielded fewer than L rows; a source that yields no visible row is passed
+ *       and counts as read; the stop source is the one in which the L-th row lies.  Only an opened source can fail
+ *       the range: a block error, an invalid version, a NULL array.  An opened source has every block of its covering
+ *       ranges checked, wherever in it the L-th row lies: every participating SST of an opened run counts.  The
+ *       status is that of the first failing source in walk order: inside it the first failing SST in walk order, then
+ *       the lowest block.  A failing range returns no row, as sdb_lsm_scan rule 5, and its range_visible is 0.  A
+ *       filtered-out SST is never opened and counts in range_filtered, not in range_sources_read.  As sdb_lsm_get
+ *       rule 4, the call may check blocks of sources the walk never reaches: those results never surface, and
+ *       blocks_checked counts what was checked.  limit == NULL or L == 0 drains every source: then any failing
+ *       participant fails the range.  range_sources_read[r] counts the sources the walk opened, the stop source or
+ *       the failing source included; range_visible[r] counts the rows at or below max_seq[r] in them;
+ *   R6. capacity: every pair without an error stages its candidates, reached or not; a pair with an error stages
+ *       none.  The two SDB_LIMIT_EXCEEDED cases and "no column byte is written" are as in S6; num_entries counts the
+ *       rows after `limit`.  When the candidates do not fit, no row was counted and the walk cannot be told: then
+ *       range_status is that of L == 0 (the first failing participant in walk order) and range_sources_read and
+ *       range_visible are all 0;
+ *   R7. arguments, malformed trees and tables, no tables, no tree, conventions: as S7-S10 (with no table the rows'
+ *       mout columns are 0xFFFFFFFF / 0 and range_tables is 0; with no tree only the tables are walked).
+ *       Additionally a NULL rout, or a NULL array in it for n > 0, is SDB_INVALID_ARGUMENT.  The call is capturable
+ *       into a HIP graph as a linear sequence and the workspace is reusable without a host-side reset.
+ * Out of scope: the write batch; segments (RecencyScanPrefixSpansMultipleSegments, reader.rs:360-368, is the host's
+ * check before the call); laziness finer than a source.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct sdb_recency_out {        /* device */
+    uint32_t *range_sources_read;       /* n: sources the walk opened for range r, the stop source included (R5) */
+    uint64_t *range_visible;            /* n: rows at or below max_seq[r] in those sources (>= rows returned) */
+} sdb_recency_out;
+uint64_t sdb_lsm_scan_recency_workspace_bytes(uint32_t num_tables, uint64_t total_blocks, uint32_t num_ssts,
+                                              uint32_t num_runs, uint64_t nranges, uint64_t cand_entries,
+                                              uint64_t cand_key_bytes);
+sdb_status sdb_lsm_scan_recency(const sdb_mem_view *mem /* or NULL */, const sdb_lsm_view *lsm,
+                                const sdb_scan_ranges *proj /* n == num_ssts; or NULL */,
+                                const sdb_filter_policy *policies /* device, num_ssts; or NULL */,
+                                const sdb_scan_ranges *ranges, const sdb_scan_prefixes *prefixes /* or NULL */,
+                                const uint64_t *max_seq /* device, n; NULL = no bound */,
+                                const uint64_t *limit /* device, n; NULL or 0 = drain every source */,
+                                int32_t descending, uint64_t cand_entries, uint64_t cand_key_bytes,
+                                const sdb_lsm_scan_out *out, const sdb_mem_scan_out *mout,
+                                const sdb_scan_filter_out *fout, const sdb_recency_out *rout,
+                                void *workspace, uint64_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * SST footer (host): everything after the data section, so data ++ footer is the whole SST object

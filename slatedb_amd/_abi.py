@@ -272,6 +272,10 @@ class MemScanOut(C.Structure):
     _fields_ = [("table", C.c_void_p), ("row", C.c_void_p), ("range_tables", C.c_void_p)]
 
 
+class RecencyOut(C.Structure):
+    _fields_ = [("range_sources_read", C.c_void_p), ("range_visible", C.c_void_p)]
+
+
 MAX_RUNS = 32
 U64_MAX = (1 << 64) - 1
 
@@ -463,6 +467,12 @@ SIGNATURES = {
                                    C.POINTER(ScanRanges), C.POINTER(ScanPrefixes), C.c_void_p, C.c_int32, C.c_uint64,
                                    C.c_uint64, C.POINTER(LsmScanOut), C.POINTER(MemScanOut), C.POINTER(ChainOut),
                                    C.POINTER(MemChainOut), C.POINTER(ScanFilterOut), C.c_void_p, C.c_uint64, C.c_void_p]),
+    "sdb_lsm_scan_recency_workspace_bytes": (C.c_uint64, [C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64,
+                                                          C.c_uint64, C.c_uint64]),
+    "sdb_lsm_scan_recency": (C.c_int, [C.POINTER(MemView), C.POINTER(LsmView), C.POINTER(ScanRanges), C.c_void_p,
+                                       C.POINTER(ScanRanges), C.POINTER(ScanPrefixes), C.c_void_p, C.c_void_p, C.c_int32,
+                                       C.c_uint64, C.c_uint64, C.POINTER(LsmScanOut), C.POINTER(MemScanOut),
+                                       C.POINTER(ScanFilterOut), C.POINTER(RecencyOut), C.c_void_p, C.c_uint64, C.c_void_p]),
     "sdb_merge_runs_workspace_bytes":(C.c_uint64, [C.POINTER(Run), C.c_uint32]),
     "sdb_merge_runs": (C.c_int, [C.POINTER(Run), C.c_uint32, C.POINTER(Retention), C.POINTER(MergedOut),
                                  C.c_void_p, C.c_uint64, C.c_void_p]),

@@ -730,7 +730,7 @@ sdb_status sdb_lsm_get_mem(const sdb_mem_view *mem, const sdb_lsm_view *lsm, con
                         workspace, workspace_bytes, stream);
 }
 
-// The five scans: one set of argument checks, in one order, over the descriptor its entry point filled (sdb_reads.h).
+// The six scans: one set of argument checks, in one order, over the descriptor its entry point filled (sdb_reads.h).
 static sdb_status lsm_scan_call(const ScanCall &c, void *workspace, uint64_t workspace_bytes, void *stream) {
     const sdb_lsm_view *lsm = c.lsm;
     const sdb_lsm_scan_out *out = c.out;
@@ -738,6 +738,7 @@ static sdb_status lsm_scan_call(const ScanCall &c, void *workspace, uint64_t wor
     const uint32_t ntab = c.mem ? c.mem->num_tables : 0;
     if (c.layers && (!c.mout || (c.chain != nullptr) != (c.mchain != nullptr) || (ntab && !c.mem->tables)))
         return SDB_INVALID_ARGUMENT;
+    if (c.recency && !c.rout) return SDB_INVALID_ARGUMENT;
     const uint64_t n = c.ranges->n;
     // (the limits all give one status, so these may come before the tree's)
     const uint64_t per_range = (uint64_t)lsm->num_ssts + ntab;  // per (range, source) state
@@ -759,9 +760,11 @@ static sdb_status lsm_scan_call(const ScanCall &c, void *workspace, uint64_t wor
     if (c.layers && ((n && !c.mout->range_tables) || (out->cap_entries && (!c.mout->table || !c.mout->row)) ||
                      (c.merge && c.chain->cap_links && (!c.mchain->table || !c.mchain->row))))
         return SDB_INVALID_ARGUMENT;
+    if (c.recency && n && (!c.rout->range_sources_read || !c.rout->range_visible)) return SDB_INVALID_ARGUMENT;
     const uint64_t need = lsm_scan_workspace_bytes({.num_tables = ntab, .total_blocks = lsm->total_blocks,
                                                     .num_ssts = lsm->num_ssts, .n = n, .cand_entries = c.cand_entries,
-                                                    .cand_key_bytes = c.cand_key_bytes, .merge = c.merge, .filter = c.filter});
+                                                    .cand_key_bytes = c.cand_key_bytes, .merge = c.merge, .filter = c.filter,
+                                                    .recency = c.recency});
     if (!workspace || workspace_bytes < need + 256) return SDB_INVALID_ARGUMENT;
     if (!device_ok()) return SDB_DEVICE_ERROR;
     return launch_lsm_scan(c, ws_align(workspace), S(stream)) != hipSuccess ? SDB_DEVICE_ERROR : SDB_OK;
@@ -856,6 +859,28 @@ sdb_status sdb_lsm_scan_mem(const sdb_mem_view *mem, const sdb_lsm_view *lsm, co
                           .max_seq = max_seq, .desc = descending ? 1u : 0u, .cand_entries = cand_entries,
                           .cand_key_bytes = cand_key_bytes, .out = out, .mout = mout, .chain = chain, .mchain = mchain,
                           .fout = fout, .merge = chain != nullptr, .filter = true, .layers = true},
+                         workspace, workspace_bytes, stream);
+}
+
+uint64_t sdb_lsm_scan_recency_workspace_bytes(uint32_t num_tables, uint64_t total_blocks, uint32_t num_ssts,
+                                              uint32_t num_runs, uint64_t nranges, uint64_t cand_entries,
+                                              uint64_t cand_key_bytes) {
+    (void)num_runs;
+    return lsm_scan_workspace_bytes({.num_tables = num_tables, .total_blocks = total_blocks, .num_ssts = num_ssts, .n = nranges,
+                                     .cand_entries = cand_entries, .cand_key_bytes = cand_key_bytes, .filter = true,
+                                     .recency = true}) + 256;
+}
+
+sdb_status sdb_lsm_scan_recency(const sdb_mem_view *mem, const sdb_lsm_view *lsm, const sdb_scan_ranges *proj,
+                                const sdb_filter_policy *policies, const sdb_scan_ranges *ranges,
+                                const sdb_scan_prefixes *prefixes, const uint64_t *max_seq, const uint64_t *limit,
+                                int32_t descending, uint64_t cand_entries, uint64_t cand_key_bytes,
+                                const sdb_lsm_scan_out *out, const sdb_mem_scan_out *mout, const sdb_scan_filter_out *fout,
+                                const sdb_recency_out *rout, void *workspace, uint64_t workspace_bytes, void *stream) {
+    return lsm_scan_call({.mem = mem, .lsm = lsm, .proj = proj, .pol = policies, .ranges = ranges, .prefixes = prefixes,
+                          .max_seq = max_seq, .desc = descending ? 1u : 0u, .cand_entries = cand_entries,
+                          .cand_key_bytes = cand_key_bytes, .out = out, .mout = mout, .fout = fout, .filter = true,
+                          .layers = true, .recency = true, .limit = limit, .rout = rout},
                          workspace, workspace_bytes, stream);
 }
 

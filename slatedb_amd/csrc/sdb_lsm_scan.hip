@@ -81,9 +81,25 @@
 // k_ls_rank, k_ls_links, the scans and k_ls_count work on staged candidates and see sources where they saw SSTs: the
 // stride is nsrc, and j < i still means "the earlier source".  Without tables nsrc == num_ssts and the seven other
 // entry points launch the instantiations without the table step (k_ls_mfill then names no table for what they wrote).
+// sdb_lsm_scan_recency (Db::scan_prefix_by_recency: DbRecencyIterator drains its sources one after another and opens one
+// only when the walk reaches it, db_iter.rs:376-442; rules R1-R7 of include/slatedb_amd.h) runs sdb_lsm_scan_mem's
+// sequence through staging, with k_ls_rstat<MEM, true> leaving the range's status open, and then no merge:
+//   k_lr_vis       thread per candidate: visible (seq <= max_seq), and first of its key group in its pair
+//   scan           both flags -> vpos (a pair's visible rows are a difference of two entries), gpos (group ids)
+//   k_lr_groups    descending only, thread per candidate: where every key group starts
+//   k_lr_plan      thread per range: the walk over the sources (tables, then runs; a run's SSTs last to first when
+//                  descending) against limit[r]: the status of the first opened failing source, the sources read, the
+//                  visible rows, and per pair its output base and take
+//   k_lr_place     thread per candidate: its rank inside its pair from vpos (descending: groups reversed, versions
+//                  newest first) -> morder / wn / wkb at the range's start + the pair's base + the rank: no key of
+//                  another source is compared
+// and then the winner scan, k_ls_count, k_ls_final and k_ls_emit<true> as they are, with rule 4 off (rop stays 0),
+// tombstones flagged as rows and the rows written in the order of their positions (desc = 0 for these launches).
 // Host side: one descriptor (ScanCall, sdb_reads.h) from the C entry point to the launches.  launch_lsm_scan ->
-// launch_ls_search (memsets, LsArgs, the bind) -> launch_ls_bound -> launch_ls_kernels<FILTER, PROJ, MEM>, where the
-// instantiations are chosen once: the five of (plain or merging), filtered, projected, tables, tables and projected.
+// launch_ls_search (memsets, LsArgs, the bind) -> launch_ls_bound -> launch_ls_front<FILTER, PROJ, MEM, REC> (through
+// staging) and one of the two tails, launch_ls_merged<MEM> or launch_lr_placed, which share launch_ls_rows.  The
+// instantiations are chosen once: the five of (plain or merging), filtered, projected, tables, tables and projected,
+// and the recency scan's two (with and without projections).
 // The special cases, each with the rule of include/slatedb_amd.h it implements:
 //   nothing to search   no range, or neither a tree nor a table: every range is empty, by memsets alone; no kernel
 //   no_tree             the tree has no SST or no block; a tree without runs counts as none only with tables (a scan's
@@ -94,6 +110,8 @@
 //   marks and statuses  without tables two memsets; with tables k_ls_mreset
 //   no table (S7)       sdb_lsm_scan_mem with mem NULL, no table or no range is the projected call, then k_ls_mfill: no
 //                       row, link or range names a table
+//   recency             always the tables' path (over no table when it has none); a tree without runs is none (R1
+//                       walks runs); with neither table nor tree the memsets, the recency outputs included
 //   filter              a property of the entry point (ScanCall::filter), not of fout: it sizes the workspace, selects
 //                       k_ls_locate<true, ...> and has range_filtered / num_filtered written
 #include <algorithm>
@@ -162,6 +180,13 @@ struct LsArgs {
     const sdb_run *tabs;            // device: the tables, sources 0 .. ntab - 1
     sdb_mem_scan_out mout;
     sdb_mem_chain_out mchain;
+    // sdb_lsm_scan_recency only
+    const uint64_t *limit;          // per range, or nullptr: every source is drained
+    sdb_recency_out rout;
+    uint64_t *vis, *head;           // per candidate: visible; first of its key group in its pair
+    uint64_t *vpos, *gpos;          // their exclusive scans (cand_entries + 1)
+    uint64_t *gstart;               // descending: per key group its first candidate; one past the last group: the total
+    uint64_t *pbase, *ptake;        // per pair: where its rows start in the range's output, and how many it gives
 };
 enum { kBase = 0x100 };  // a value or a tombstone ended the chain
 enum { kCtlFirstBad = 0, kCtlFailed, kCtlBad, kCtlGo1, kCtlGo2, kCtlGo3, kCtlMaxChain, kCtlFiltered, kCtlUniform, kCtlWords = 16 };
@@ -401,7 +426,10 @@ __global__ __launch_bounds__(64) void k_ls_edge(LsArgs a) {
     }
 }
 
-template <bool MEM>
+// REC: sdb_lsm_scan_recency: a failing pair fails its range only where the walk opens it (R5), which k_lr_plan decides
+// once the visible rows are counted; here only a malformed call or range has a status, and the failing pairs (whose
+// counts k_ls_edge left 0) are the only ones that stage nothing.
+template <bool MEM, bool REC = false>
 __global__ __launch_bounds__(64) void k_ls_rstat(LsArgs a) {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= a.r.n) return;
@@ -418,7 +446,7 @@ __global__ __launch_bounds__(64) void k_ls_rstat(LsArgs a) {
             if (a.filter && a.filt[p0 + i]) nf++;
             if (!a.part[p0 + i]) continue;
             ns++;
-            if (!st) st = a.pst[p0 + i];
+            if (!REC && !st) st = a.pst[p0 + i];
         }
         for (uint32_t j = 0; j < T; j++) nt += a.part[r * NS + j];  // (k_ls_tprobe: the table holds a key of the range)
     }
@@ -846,6 +874,122 @@ __global__ __launch_bounds__(256) void k_ls_mfill(sdb_lsm_scan_out out, sdb_mem_
     }
 }
 
+// =================================================================================================
+// sdb_lsm_scan_recency: the sources drained one after another instead of merged
+// =================================================================================================
+
+// Thread per staged candidate (R2, R3): is it visible (seq <= max_seq of its range), and does it open a key group
+// of its pair: the pair's first candidate, or its key differs from the candidate's before it.  Neighbouring threads
+// read neighbouring staged keys; the lengths are compared first.  Past the candidates, and when they did not fit,
+// both flags are 0.
+__global__ __launch_bounds__(256) void k_lr_vis(LsArgs a) {
+    const uint32_t S = a.nsrc;
+    const uint64_t total = a.ctl[kCtlGo1] ? a.cs[a.pairs] : 0;
+    for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < a.cand_entries; c += (uint64_t)gridDim.x * blockDim.x) {
+        uint64_t vis = 0, head = 0;
+        if (c < total) {
+            const uint64_t p = last_le(a.cs, a.pairs, 1, c);
+            vis = a.cseq[c] <= (a.max_seq ? a.max_seq[p / S] : ~0ull);
+            const uint32_t n = a.cklen[c];
+            head = c == a.cs[p] || a.cklen[c - 1] != n || ls_key_cmp(a, c - 1, a.ckeys + a.ckoff[c], n) != 0;
+        }
+        a.vis[c] = vis;
+        a.head[c] = head;
+    }
+}
+
+// Descending only, thread per candidate: a group's head writes where the group starts, so that group g is
+// [gstart[g], gstart[g + 1]); the group of candidate c is gpos[c + 1] - 1.
+__global__ __launch_bounds__(256) void k_lr_groups(LsArgs a) {
+    if (!a.ctl[kCtlGo1]) return;
+    const uint64_t total = a.cs[a.pairs];
+    for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c <= total && c <= a.cand_entries; c += (uint64_t)gridDim.x * blockDim.x)
+        if (c == total || a.head[c]) a.gstart[a.gpos[c]] = c;
+}
+
+// Pair (r, source j)'s visible rows (k_lr_vis counted them; 0 for a pair that staged nothing).
+SDB_DEV uint64_t lr_visible(const LsArgs &a, uint64_t p) { return a.vpos[a.cs[p + 1]] - a.vpos[a.cs[p]]; }
+
+// Thread per range: the walk of R1 / R5.  The sources are the tables, then the runs, newest first; a run's SSTs are
+// walked in `ssts` order, descending last to first.  A source is opened while the sources before it gave fewer than
+// limit[r] rows; the first opened source with a failing SST fails the range (first failing SST in walk order; its pst is
+// its lowest failing block's).  Per pair: where its rows start in the range's output and how many it gives.  When
+// the candidates did not fit nothing was counted: the status is then that of limit 0 (every participant is
+// opened), and nothing counts as read.
+__global__ __launch_bounds__(64) void k_lr_plan(LsArgs a) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= a.r.n) return;
+    const uint32_t S = a.t.num_ssts, T = a.ntab, NS = a.nsrc;
+    const bool go = a.ctl[kCtlGo1] != 0;
+    const uint64_t L = go && a.limit ? a.limit[r] : 0, p0 = r * NS;
+    int st = a.out.range_status[r];  // k_ls_rstat: a malformed call or range
+    uint64_t got = 0, seen = 0;
+    uint32_t nread = 0;
+    bool stop = st != 0;
+    for (uint32_t j = 0; j < NS; j++) a.pbase[p0 + j] = a.ptake[p0 + j] = 0;
+    for (uint32_t j = 0; j < T && !stop; j++) {  // a table cannot fail; one without a row of the range is no source
+        if (!a.part[p0 + j]) continue;
+        const uint64_t v = go ? lr_visible(a, p0 + j) : 0, take = L && v > L - got ? L - got : v;
+        a.pbase[p0 + j] = got;
+        a.ptake[p0 + j] = take;
+        got += take;
+        seen += v;
+        nread++;
+        stop = L && got >= L;
+    }
+    for (uint32_t q = 0; q < a.t.num_runs && !stop; q++) {
+        const uint32_t i0 = a.t.run_start[q], i1 = a.t.run_start[q + 1];
+        bool any = false;
+        for (uint32_t k = i0; k < i1 && k < S; k++) {
+            const uint32_t i = a.desc ? i1 - 1 - (k - i0) : k;
+            const uint64_t p = p0 + T + i;
+            if (i >= S || !a.part[p]) continue;  // (a filtered-out SST takes no part: never opened)
+            any = true;
+            if (!st) st = a.pst[p];
+            const uint64_t v = go ? lr_visible(a, p) : 0, take = L && v > L - got ? L - got : v;
+            a.pbase[p] = got;
+            a.ptake[p] = take;
+            got += take;
+            seen += v;
+        }
+        nread += any;
+        stop = st != 0 || (L && got >= L);
+    }
+    if (st) {  // a failing range returns no row
+        for (uint32_t j = 0; j < NS; j++) a.ptake[p0 + j] = 0;
+        seen = 0;
+    }
+    a.out.range_status[r] = st;
+    a.rout.range_sources_read[r] = go ? nread : 0;
+    a.rout.range_visible[r] = seen;
+}
+
+// Thread per candidate (R3, R4): its rank among its pair's visible rows.  Ascending that is the physical order;
+// descending the key groups are reversed and a group's versions stay newest first.  A visible candidate whose rank is
+// below its pair's take goes to its place in the range's output: its index into morder and the keep flag and key bytes
+// into wn / wkb (k_ls_gate zeroed them), the arrays k_ls_rank fills for the merging scans.  No key of another source
+// is looked at.
+__global__ __launch_bounds__(256) void k_lr_place(LsArgs a) {
+    if (!a.ctl[kCtlGo1]) return;
+    const uint32_t S = a.nsrc;
+    const uint64_t total = a.cs[a.pairs];
+    for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < total && c < a.cand_entries; c += (uint64_t)gridDim.x * blockDim.x) {
+        if (!a.vis[c]) continue;
+        const uint64_t p = last_le(a.cs, a.pairs, 1, c), r = p / S, ps = a.cs[p];
+        uint64_t rank = a.vpos[c] - a.vpos[ps];
+        if (a.desc) {
+            const uint64_t g = a.gpos[c + 1] - 1, gs = a.gstart[g], ge = a.gstart[g + 1];
+            if (gs > c || ge <= c || ge > a.cs[p + 1]) continue;  // (never: the groups tile the pair)
+            rank = (lr_visible(a, p) - (a.vpos[ge] - a.vpos[ps])) + (a.vpos[c] - a.vpos[gs]);
+        }
+        if (rank >= a.ptake[p]) continue;
+        const uint64_t m = a.cs[r * S] + a.pbase[p] + rank;
+        if (m >= a.cs[(r + 1) * S]) continue;  // never out of the range's slots
+        a.morder[m] = c;
+        a.wn[m] = 1;
+        a.wkb[m] = a.cklen[c];
+    }
+}
 
 // The workspace arrays of a scan of a.r.n ranges over the tree a.t with room for a.cand_entries candidates of
 // a.cand_key_bytes key bytes, bound into a from w; -> their size.
@@ -928,8 +1072,23 @@ static uint64_t lsm_scan_filter_bind(LsArgs &a, uint8_t *w, bool merge) {
     return c.off;
 }
 
-// The layout of the entry point: the plain scan's arrays, then the merging scan's, then the filtered scan's.
-static uint64_t lsm_scan_bind_for(LsArgs &a, uint8_t *w, bool merge, bool filter) {
+// The workspace arrays of the recency scan: those of the filtered scan, then its own.
+static uint64_t lsm_scan_recency_bind(LsArgs &a, uint8_t *w) {
+    Carver c{w, lsm_scan_filter_bind(a, w, false)};
+    c.take(a.vis, a.cand_entries + 1);
+    c.take(a.head, a.cand_entries + 1);
+    c.take(a.vpos, a.cand_entries + 2);
+    c.take(a.gpos, a.cand_entries + 2);
+    c.take(a.gstart, a.cand_entries + 2);
+    c.take(a.pbase, a.pairs + 1);
+    c.take(a.ptake, a.pairs + 1);
+    return c.off;
+}
+
+// The layout of the entry point: the plain scan's arrays, then the merging scan's, then the filtered scan's, then
+// the recency scan's.
+static uint64_t lsm_scan_bind_for(LsArgs &a, uint8_t *w, bool merge, bool filter, bool recency) {
+    if (recency) return lsm_scan_recency_bind(a, w);
     if (filter) return lsm_scan_filter_bind(a, w, merge);
     return merge ? lsm_scan_merge_bind(a, w) : lsm_scan_bind(a, w);
 }
@@ -942,14 +1101,15 @@ uint64_t lsm_scan_workspace_bytes(const ReadShape &s) {
     a.r.n = s.n;
     a.cand_entries = s.cand_entries;
     a.cand_key_bytes = s.cand_key_bytes;
-    return lsm_scan_bind_for(a, nullptr, s.merge, s.filter);
+    return lsm_scan_bind_for(a, nullptr, s.merge, s.filter, s.recency);
 }
 
-// The kernels of a bound scan in stream order.  FILTER: the filters are consulted, PROJ: the call has projections, MEM:
-// it has tables (and then always FILTER), each chosen once for the kernels that hold the step; a.merge: the chain's
-// kernels.  tree: false only with tables over a tree without SSTs or blocks (S8): none of the tree's kernels is launched.
-template <bool FILTER, bool PROJ, bool MEM>
-static hipError_t launch_ls_kernels(const LsArgs &a, bool tree, hipStream_t st) {
+// The kernels of a bound scan in stream order, through staging.  FILTER: the filters are consulted, PROJ: the call has
+// projections, MEM: it has tables (and then always FILTER), REC: the recency scan (and then always MEM), each chosen
+// once for the kernels that hold the step.  tree: false only with tables over a tree without SSTs or blocks (S8): none
+// of the tree's kernels is launched.
+template <bool FILTER, bool PROJ, bool MEM, bool REC = false>
+static hipError_t launch_ls_front(const LsArgs &a, bool tree, hipStream_t st) {
     const uint64_t tb = a.t.total_blocks, n = a.r.n, P = a.pairs, SP = a.spairs, ce = a.cand_entries;
     const uint32_t rw = (uint32_t)((n + 63) / 64);
     hipError_t e;
@@ -972,17 +1132,22 @@ static hipError_t launch_ls_kernels(const LsArgs &a, bool tree, hipStream_t st) 
         if ((e = launch_excl_scan2(a.bbad, a.rd, tb, a.tx, a.ty, a.pb, a.pr, st)) != hipSuccess) return e;
         hipLaunchKernelGGL((k_ls_edge<PROJ, MEM>), dim3(scan_grid(SP, 64)), dim3(64), 0, st, a);
     }
-    hipLaunchKernelGGL(k_ls_rstat<MEM>, dim3(rw), dim3(64), 0, st, a);
+    hipLaunchKernelGGL((k_ls_rstat<MEM, REC>), dim3(rw), dim3(64), 0, st, a);
     if ((e = launch_excl_scan2(a.pit, a.pit, P, a.tx, a.ty, a.pis, a.cs, st)) != hipSuccess) return e;
     if ((e = launch_excl_scan2(a.pn, a.pkb, P, a.tx, a.ty, a.cs, a.cks, st)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_ls_gate, dim3(scan_grid(ce, 256)), dim3(256), 0, st, a);
     if (tree) hipLaunchKernelGGL(k_ls_stage<MEM>, dim3(scan_grid(ce + P, 64)), dim3(64), 0, st, a);
     if constexpr (MEM) hipLaunchKernelGGL(k_ls_trows, dim3(scan_grid(ce, 256)), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_ls_rank, dim3(scan_grid(ce, 64)), dim3(64), 0, st, a);
-    if (a.merge) {
-        hipLaunchKernelGGL(k_ls_links, dim3(scan_grid(ce, 64)), dim3(64), 0, st, a);
-        if ((e = launch_excl_scan2(a.wl, a.wl, ce, a.tx, a.ty, a.wlpos, a.wldum, st)) != hipSuccess) return e;
-    }
+    return hipSuccess;
+}
+
+// What both tails end with: the winner scan over the positions morder / wn / wkb name, the ranges' totals, the
+// summary and the rows.
+template <bool MEM>
+static hipError_t launch_ls_rows(const LsArgs &a, hipStream_t st) {
+    const uint64_t n = a.r.n, ce = a.cand_entries;
+    const uint32_t rw = (uint32_t)((n + 63) / 64);
+    hipError_t e;
     if ((e = launch_excl_scan2(a.wn, a.wkb, ce, a.tx, a.ty, a.wpos, a.wkpos, st)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_ls_count, dim3(rw), dim3(64), 0, st, a);
     if ((e = launch_excl_scan2(a.rn, a.rkb, n, a.tx, a.ty, a.out.range_entry_start, a.rks, st)) != hipSuccess) return e;
@@ -992,8 +1157,50 @@ static hipError_t launch_ls_kernels(const LsArgs &a, bool tree, hipStream_t st) 
     return hipGetLastError();
 }
 
-// The five instantiations there are: tables come with the filters, and projections too.
-static hipError_t launch_ls_bound(const LsArgs &a, bool projected, bool tabs, bool tree, hipStream_t st) {
+// After staging, the merging scans: the merged rank and the winners (a.merge: and their chains), then the rows.
+template <bool MEM>
+static hipError_t launch_ls_merged(const LsArgs &a, hipStream_t st) {
+    const uint64_t ce = a.cand_entries;
+    hipError_t e;
+    hipLaunchKernelGGL(k_ls_rank, dim3(scan_grid(ce, 64)), dim3(64), 0, st, a);
+    if (a.merge) {
+        hipLaunchKernelGGL(k_ls_links, dim3(scan_grid(ce, 64)), dim3(64), 0, st, a);
+        if ((e = launch_excl_scan2(a.wl, a.wl, ce, a.tx, a.ty, a.wlpos, a.wldum, st)) != hipSuccess) return e;
+    }
+    return launch_ls_rows<MEM>(a, st);
+}
+
+// After staging, the recency scan: the flags and their scans, the walk, the placement, then the rows.  The placement
+// has put every row where it belongs, descending too, so the rows are written in the order of their positions.
+static hipError_t launch_lr_placed(const LsArgs &a, hipStream_t st) {
+    const uint64_t ce = a.cand_entries;
+    hipError_t e;
+    hipLaunchKernelGGL(k_lr_vis, dim3(scan_grid(ce, 256)), dim3(256), 0, st, a);
+    if ((e = launch_excl_scan2(a.vis, a.head, ce, a.tx, a.ty, a.vpos, a.gpos, st)) != hipSuccess) return e;
+    if (a.desc) hipLaunchKernelGGL(k_lr_groups, dim3(scan_grid(ce + 1, 256)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_lr_plan, dim3((uint32_t)((a.r.n + 63) / 64)), dim3(64), 0, st, a);
+    hipLaunchKernelGGL(k_lr_place, dim3(scan_grid(ce, 256)), dim3(256), 0, st, a);
+    LsArgs rows = a;
+    rows.desc = 0;
+    return launch_ls_rows<true>(rows, st);
+}
+
+template <bool FILTER, bool PROJ, bool MEM>
+static hipError_t launch_ls_kernels(const LsArgs &a, bool tree, hipStream_t st) {
+    const hipError_t e = launch_ls_front<FILTER, PROJ, MEM>(a, tree, st);
+    return e != hipSuccess ? e : launch_ls_merged<MEM>(a, st);
+}
+
+template <bool PROJ>
+static hipError_t launch_lr_kernels(const LsArgs &a, bool tree, hipStream_t st) {
+    const hipError_t e = launch_ls_front<true, PROJ, true, true>(a, tree, st);
+    return e != hipSuccess ? e : launch_lr_placed(a, st);
+}
+
+// The instantiations there are: tables come with the filters, and projections too; the recency scan always has the
+// tables' step (over none when it has no table).
+static hipError_t launch_ls_bound(const LsArgs &a, bool projected, bool tabs, bool tree, bool recency, hipStream_t st) {
+    if (recency) return projected ? launch_lr_kernels<true>(a, tree, st) : launch_lr_kernels<false>(a, tree, st);
     if (tabs) return projected ? launch_ls_kernels<true, true, true>(a, tree, st) : launch_ls_kernels<true, false, true>(a, tree, st);
     if (projected) return launch_ls_kernels<true, true, false>(a, tree, st);
     return a.filter ? launch_ls_kernels<true, false, false>(a, tree, st) : launch_ls_kernels<false, false, false>(a, tree, st);
@@ -1007,7 +1214,7 @@ static hipError_t launch_ls_search(const ScanCall &c, bool tabs, uint8_t *w, hip
     const sdb_chain_out *chain = c.chain;
     const sdb_scan_filter_out *fout = c.filter ? c.fout : nullptr;
     const uint64_t n = c.ranges->n;
-    const bool no_tree = t.num_ssts == 0 || t.total_blocks == 0 || (tabs && t.num_runs == 0);
+    const bool no_tree = t.num_ssts == 0 || t.total_blocks == 0 || ((tabs || c.recency) && t.num_runs == 0);
     hipError_t e;
     if (n == 0 || (no_tree && !tabs)) {  // every range is empty
         if (chain) {
@@ -1020,6 +1227,10 @@ static hipError_t launch_ls_search(const ScanCall &c, bool tabs, uint8_t *w, hip
         if (n && (e = hipMemsetAsync(out.range_ssts, 0, 4 * n, st)) != hipSuccess) return e;
         if (fout && n && (e = hipMemsetAsync(fout->range_filtered, 0, 4 * n, st)) != hipSuccess) return e;
         if (fout && fout->num_filtered && (e = hipMemsetAsync(fout->num_filtered, 0, 8, st)) != hipSuccess) return e;
+        if (c.recency && n) {
+            if ((e = hipMemsetAsync(c.rout->range_sources_read, 0, 4 * n, st)) != hipSuccess) return e;
+            if ((e = hipMemsetAsync(c.rout->range_visible, 0, 8 * n, st)) != hipSuccess) return e;
+        }
         return hipMemsetAsync(out.key_off, 0, 8, st);
     }
     LsArgs a{};
@@ -1036,8 +1247,8 @@ static hipError_t launch_ls_search(const ScanCall &c, bool tabs, uint8_t *w, hip
     }
     const bool tree = !(tabs && no_tree);
     if (tabs) {
-        a.tabs = c.mem->tables;
-        a.ntab = c.mem->num_tables;
+        a.tabs = c.mem ? c.mem->tables : nullptr;  // (the recency scan takes this path without a table too)
+        a.ntab = c.mem ? c.mem->num_tables : 0;
         a.mout = *c.mout;
         if (chain) a.mchain = *c.mchain;
         if (!tree) {  // (S8) only the tables are scanned, and nothing is read through the tree's arrays
@@ -1053,12 +1264,19 @@ static hipError_t launch_ls_search(const ScanCall &c, bool tabs, uint8_t *w, hip
         a.fout = *fout;
         if (projected) a.proj = *c.proj;
     }
-    lsm_scan_bind_for(a, w, chain != nullptr, fout != nullptr);
-    return launch_ls_bound(a, projected, tabs, tree, st);
+    if (c.recency) {
+        a.limit = c.limit;
+        a.rout = *c.rout;
+    }
+    lsm_scan_bind_for(a, w, chain != nullptr, fout != nullptr, c.recency);
+    return launch_ls_bound(a, projected, tabs, tree, c.recency, st);
 }
 
 hipError_t launch_lsm_scan(const ScanCall &c, uint8_t *w, hipStream_t st) {
-    const bool tabs = c.mem && c.mem->num_tables && c.ranges->n;
+    const sdb_lsm_view &t = *c.lsm;
+    bool tabs = c.mem && c.mem->num_tables && c.ranges->n;
+    // the recency scan walks sources: the tables' path whenever it has a table or a tree (with runs: R1) to walk
+    if (c.recency && c.ranges->n && t.num_ssts && t.total_blocks && t.num_runs) tabs = true;
     hipError_t e = launch_ls_search(c, tabs, w, st);
     if (e != hipSuccess || tabs || !c.layers) return e;
     // (S7) sdb_lsm_scan_mem without a table: the projected call, and no row, link or range names a table

@@ -32,6 +32,7 @@ struct ReadShape {
     uint64_t cand_entries, cand_key_bytes; // scans: the staging room
     bool merge;                            // the call has a chain
     bool filter;                           // scans: the entry point consults the filters (ScanCall::filter)
+    bool recency;                          // scans: sdb_lsm_scan_recency (ScanCall::recency; then filter, no merge)
 };
 
 struct GetCall {
@@ -77,6 +78,10 @@ struct ScanCall {
                                       // and fout is written
     bool layers;                      // the entry point is sdb_lsm_scan_mem: mout (and mchain) are filled even when
                                       // mem holds no table (S7)
+    bool recency;                     // the entry point is sdb_lsm_scan_recency (then filter and layers, no chain): the
+                                      // sources are drained one after another instead of merged
+    const uint64_t *limit;            // iff recency; may be NULL: every source is drained
+    const sdb_recency_out *rout;      // iff recency
 };
 uint64_t lsm_scan_workspace_bytes(const ReadShape &s);
 hipError_t launch_lsm_scan(const ScanCall &c, uint8_t *w, hipStream_t st);

@@ -893,16 +893,25 @@ READ_CALLS = {
     "sdb_lsm_scan_mem": (("mem", "lsm", "proj", "policies", "ranges", "prefixes") + _SCAN + ("mout", "chain", "mchain", "fout"),
                          ("num_tables",) + _TREE + _CAND + ("merge",)),
 }
+# The read that is no get and no merging scan, marshalled by _lsm_scan like them: limit and rout are its own.
+RECENCY_CALLS = {
+    "sdb_lsm_scan_recency": (("mem", "lsm", "proj", "policies", "ranges", "prefixes", "max_seq", "limit", "descending") + _CAND +
+                             ("out", "mout", "fout", "rout"), ("num_tables",) + _TREE + _CAND),
+}
+
+
+def _read_args(entry):
+    return READ_CALLS[entry] if entry in READ_CALLS else RECENCY_CALLS[entry]
 
 
 def _read_workspace_bytes(entry, v):
     """What entry's sizer answers for the marshalled values v."""
-    return getattr(lib(), entry + "_workspace_bytes")(*[v[a] for a in READ_CALLS[entry][1]])
+    return getattr(lib(), entry + "_workspace_bytes")(*[v[a] for a in _read_args(entry)[1]])
 
 
 def _read_call(entry, v, ws, wsb, stream):
     """The C call of a tree read over the marshalled values v; raises SdbError on a status."""
-    st = getattr(lib(), entry)(*[v[a] for a in READ_CALLS[entry][0]], ws.data_ptr(), wsb, _sp(stream))
+    st = getattr(lib(), entry)(*[v[a] for a in _read_args(entry)[0]], ws.data_ptr(), wsb, _sp(stream))
     if st:
         raise SdbError(st, entry)
 
@@ -1002,7 +1011,7 @@ def _lsm_scan_out(res, cap_e, cap_k, dev):
 
 
 def _lsm_scan(entry, tree, ranges, max_seq, descending, stream, workspace, cand, cap, merge=False, cap_links=None, fill=0,
-              prefixes=None, probe_len=None, projections=None, mem=None):
+              prefixes=None, probe_len=None, projections=None, mem=None, limit=None):
     """The tree scans.  entry: the C entry point, a key of READ_CALLS, which names what it takes: the filtered ones
     the policies, the prefixes, an optional chain and the filter outputs, the projected ones the projections too; merge:
     the call has a chain.  Marshals the ranges, the bounds, the prefixes and the projections as device tensors and the
@@ -1011,9 +1020,10 @@ def _lsm_scan(entry, tree, ranges, max_seq, descending, stream, workspace, cand,
     with the staging at max(given, reported), cap like the staging and cap_links like cand_entries where those
     were None.  mem: for sdb_lsm_scan_mem: None (a NULL sdb_mem_view) or what mem_tables_device returned; the
     result then has table and row per output row (MEM_FIELDS), range_tables and, with a chain, chain_table and
-    chain_row."""
+    chain_row.  limit: for sdb_lsm_scan_recency: None, a list / array of n row limits, or a device int64 tensor; the
+    result then has range_sources_read and range_visible."""
     import torch
-    takes = READ_CALLS[entry][0]
+    takes = _read_args(entry)[0]
     dev = tree["device"]
     if isinstance(ranges, dict):
         rt, n = ranges, int(ranges["n"])
@@ -1044,6 +1054,13 @@ def _lsm_scan(entry, tree, ranges, max_seq, descending, stream, workspace, cand,
         v["fout"] = C.byref(_abi.ScanFilterOut(res["range_filtered"].data_ptr(), res["num_filtered"].data_ptr()))
     if "mout" in takes:
         res["range_tables"] = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    if "rout" in takes:
+        if limit is not None and not hasattr(limit, "data_ptr"):
+            limit = _to_dev(np.asarray(list(limit) or [0], np.uint64), dev)
+        res["range_sources_read"] = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        res["range_visible"] = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+        v.update(limit=_ptr(limit),
+                 rout=C.byref(_abi.RecencyOut(res["range_sources_read"].data_ptr(), res["range_visible"].data_ptr())))
 
     def run(ce, ckb, cap_e, cap_k, cap_l):
         v.update(ce=ce, ckb=ckb)
@@ -1072,7 +1089,7 @@ def _lsm_scan(entry, tree, ranges, max_seq, descending, stream, workspace, cand,
             run(ce, ckb, *(cap if cap is not None else (ce, ckb)), cap_links if cap_links is not None else ce)
     else:
         run(cand[0], cand[1], cap[0], cap[1], cap_links or 0)
-    res.update(_tree=tree, _ranges=rt, _max_seq=max_seq, _prefixes=pt, _projections=pjt, _mem=mem)
+    res.update(_tree=tree, _ranges=rt, _max_seq=max_seq, _prefixes=pt, _projections=pjt, _mem=mem, _limit=limit)
     return res
 
 
@@ -1232,6 +1249,29 @@ def lsm_scan_mem_device(tables, tree, ranges, projections=None, prefixes=None, p
     return _lsm_scan("sdb_lsm_scan_mem", tree, ranges, max_seq, descending, stream, workspace, cand, cap,
                      merge=bool(merge), cap_links=cap_links, fill=fill, prefixes=prefixes,
                      probe_len=probe_len, projections=projections, mem=mem)
+
+
+def lsm_scan_recency_device(tables, tree, ranges, projections=None, prefixes=None, probe_len=None, max_seq=None, limit=None,
+                            descending=False, stream=None, workspace=None, cand=None, cap=None):
+    """sdb_lsm_scan_recency: a batch of Db::scan_prefix_by_recency over device memtables and the tree: the sources
+    drained one after another, newest first, every visible version a row, tombstones and merge operands included.
+    ranges: the prefixes' ranges (prefix_range); prefixes: the prefixes themselves, for the filters.  limit: None
+    (every source is drained), a list / array of n row limits (0: drain), or a device int64 tensor.  The other
+    arguments, the retry once on SDB_LIMIT_EXCEEDED and the result are lsm_scan_mem_device's without the chain, plus
+    range_sources_read and range_visible (n)."""
+    mem = tables if tables is None or isinstance(tables, dict) else mem_tables_device(tables, tree["device"])
+    return _lsm_scan("sdb_lsm_scan_recency", tree, ranges, max_seq, descending, stream, workspace, cand, cap,
+                     prefixes=prefixes, probe_len=probe_len, projections=projections, mem=mem, limit=limit)
+
+
+def prefix_range(prefix):
+    """BytesRange::from_prefix: (start, kind, end, kind) of the keys that start with prefix: [prefix, the prefix with
+    its last byte below 0xFF incremented and what follows it dropped), unbounded above when every byte is 0xFF."""
+    p = bytes(prefix)
+    if not p:
+        return (None, 0, None, 0)
+    end = p.rstrip(b"\xff")
+    return (p, 1, end[:-1] + bytes([end[-1] + 1]), 2) if end else (p, 1, None, 0)
 
 
 # ------------------------------------------------------------------------------------------------
