@@ -11,6 +11,7 @@ The HIP library is mandatory: a missing .so or a machine without a HIP device ra
 falls back to a CPU implementation.
 """
 import ctypes as C
+import functools
 import os
 
 import numpy as np
@@ -929,19 +930,49 @@ def _read_values(tree, mem, pj, merge):
             "merge": int(bool(merge))}
 
 
+def read_workspace_bytes(entry, tree, n, cand=(0, 0), merge=False, tables=None):
+    """What entry + "_workspace_bytes" answers for a call of the tree read `entry` (a key of READ_CALLS or
+    RECENCY_CALLS) over tree (what lsm_tree_device built) with n keys or ranges; for a scan cand = (cand_entries,
+    cand_key_bytes); merge: the call has a chain; tables: what mem_tables_device returned, or None.  A sizer takes
+    of these what its tuple names."""
+    v = _read_values(tree, tables, None, merge)
+    v.update(n=n, ce=cand[0], ckb=cand[1])
+    return _read_workspace_bytes(entry, v)
+
+
+def _read_output(dev, name, count, dtype, fill):
+    """Where every output of a tree read comes from, and the contract of the eleven lsm_*_device wrappers' alloc=:
+    alloc(name, count, dtype, fill) -> a 1-D tensor of dtype on the tree's device with at least count elements.
+    name: the output's key in the result dict ("range_status", "key_arena", "chain_seq", "table", "summary", ...;
+    "_ws": a workspace the call allocates itself).  count: its logical element count (n + 1, cap_entries,
+    key_arena_cap, cap_links, the summary's words, ...), which may be 0.  fill: the byte every element starts as: 0,
+    the caller's fill= for the link columns, 0xFF for a scan's table (rows that no call writes name no table), or
+    None where the call writes every element it later reads.  A call that retries asks again for what it sizes anew.
+    The C call gets the pointers and the capacities it was asked for, so what lies beyond count is never written:
+    an allocator may hand out slices of a pool of its own, or arrays inside guard bytes.  This one, the default,
+    returns a fresh tensor of max(count, 1) elements."""
+    import torch
+    if fill is None:
+        return torch.empty(max(count, 1), dtype=dtype, device=dev)
+    if fill == 0:
+        return torch.zeros(max(count, 1), dtype=dtype, device=dev)
+    return torch.full((max(count, 1) * dtype.itemsize,), fill, dtype=torch.uint8, device=dev).view(dtype)
+
+
 def _lsm_get(entry, views, runs, keys, max_seq, stream, workspace, merge=False, cap_links=None, fill=0, probe_len=None,
-             projections=None, mem=None):
+             projections=None, mem=None, alloc=None):
     """The tree gets.  entry: the C entry point, a key of READ_CALLS, which names what it takes: the filtered ones
     the policies, probe_len and an optional chain, the projected ones the projections too; merge: the
     call has a chain.  Marshals the tree, the keys, the bounds and probe_len as device tensors, the result dict with
     the GET_FIELDS and the summary; a caller's workspace must hold the call; with merge and cap_links None the links
     are sized at nkeys first and, when they did not fit, at the reported num_links in a second call.  mem: for
     sdb_lsm_get_mem: None (a NULL sdb_mem_view) or what mem_tables_device returned; the result then has table and
-    row (MEM_FIELDS) and, with a chain, chain_table and chain_row."""
+    row (MEM_FIELDS) and, with a chain, chain_table and chain_row.  alloc: see _read_output."""
     import torch
     takes = READ_CALLS[entry][0]
     tree = views if isinstance(views, dict) else lsm_tree_device(views, runs)
     dev = tree["device"]
+    new = alloc or functools.partial(_read_output, dev)
     if isinstance(keys, (tuple, list)) and len(keys) == 3 and hasattr(keys[0], "data_ptr"):
         kb, ko, n = keys
     else:
@@ -951,23 +982,23 @@ def _lsm_get(entry, views, runs, keys, max_seq, stream, workspace, merge=False, 
         max_seq = _to_dev(np.asarray(max_seq, np.uint64).copy(), dev)
     if probe_len is not None and not hasattr(probe_len, "data_ptr"):
         probe_len = _to_dev(np.asarray(list(probe_len) or [0], np.int32), dev)
-    res = {f: torch.zeros(max(n, 1), dtype=getattr(torch, dt), device=dev) for f, dt in GET_FIELDS}
-    res["summary"] = torch.zeros(len(GET_SUMMARY), dtype=torch.int64, device=dev)
+    res = {f: new(f, n, getattr(torch, dt), 0) for f, dt in GET_FIELDS}
+    res["summary"] = new("summary", len(GET_SUMMARY), torch.int64, 0)
     pjt, pj = _projections(projections, tree)
     v = _read_values(tree, mem, pj, merge)
     v.update(key_bytes=kb.data_ptr(), key_off=ko.data_ptr(), n=n, probe_len=_ptr(probe_len), max_seq=_ptr(max_seq),
              out=C.byref(_abi.GetOut(*[res[f].data_ptr() for f, _ in GET_FIELDS], res["summary"].data_ptr())))
     if "mout" in takes:
         for f, dt in MEM_FIELDS:  # (every call writes all n of them: no fill)
-            res[f] = torch.empty(max(n, 1), dtype=getattr(torch, dt), device=dev)
+            res[f] = new(f, n, getattr(torch, dt), None)
         v["mout"] = C.byref(_abi.MemGetOut(*[res[f].data_ptr() for f, _ in MEM_FIELDS]))
-    wsb = _read_workspace_bytes(entry, v)
-    ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=dev)
+    wsb = read_workspace_bytes(entry, tree, n, merge=merge, tables=mem)
+    ws = workspace if workspace is not None else new("_ws", wsb, torch.uint8, None)
     assert ws.numel() >= wsb, "workspace too small"
 
     def run(cap):
-        v["chain"] = C.byref(_chain_out(res, n, cap, dev, fill)) if merge else None
-        v["mchain"] = C.byref(_mem_chain_out(res, cap, dev, fill)) if merge and "mchain" in takes else None
+        v["chain"] = C.byref(_chain_out(res, n, cap, new, fill)) if merge else None
+        v["mchain"] = C.byref(_mem_chain_out(res, cap, new, fill)) if merge and "mchain" in takes else None
         _read_call(entry, v, ws, wsb, stream)
 
     if merge and cap_links is None:
@@ -981,14 +1012,15 @@ def _lsm_get(entry, views, runs, keys, max_seq, stream, workspace, merge=False, 
     return res
 
 
-def lsm_get_device(views, runs, keys, max_seq=None, stream=None, workspace=None):
+def lsm_get_device(views, runs, keys, max_seq=None, stream=None, workspace=None, alloc=None):
     """sdb_lsm_get: a batch of Db::get over a device-resident tree.  views, runs: as lsm_tree_device, or
     views = a tree lsm_tree_device built (runs is then ignored).  keys: a list of bytes, or device tensors
     (key_bytes, key_off, nkeys).  max_seq: None (no bound), a list / array of nkeys bounds, or a device
     int64 tensor.  workspace: a device uint8 tensor to use (and reuse) instead of a fresh one.  With device
     tensors and a prebuilt tree the call copies nothing from the host, so it can be captured into a graph.  Returns a dict of device tensors (GET_FIELDS, and summary: the
-    sdb_get_summary words in GET_SUMMARY order); what the call allocated stays alive under "_" keys."""
-    return _lsm_get("sdb_lsm_get", views, runs, keys, max_seq, stream, workspace)
+    sdb_get_summary words in GET_SUMMARY order); what the call allocated stays alive under "_" keys.  alloc: where
+    the outputs come from (see _read_output); None: fresh tensors."""
+    return _lsm_get("sdb_lsm_get", views, runs, keys, max_seq, stream, workspace, alloc=alloc)
 
 
 LSM_SCAN_COLUMNS = (("sst", "int32"),) + SCAN_COLUMNS
@@ -996,13 +1028,13 @@ LSM_SCAN_SUMMARY = ("num_entries", "key_bytes", "num_candidates", "candidate_key
                     "blocks_checked", "status")
 
 
-def _lsm_scan_out(res, cap_e, cap_k, dev):
+def _lsm_scan_out(res, cap_e, cap_k, new):
     """Fresh row columns for cap_e rows and cap_k key bytes in res, and the sdb_lsm_scan_out over res."""
     import torch
-    res["key_arena"] = torch.zeros(max(cap_k, 1), dtype=torch.uint8, device=dev)
-    res["key_off"] = torch.zeros(cap_e + 1, dtype=torch.int64, device=dev)
+    res["key_arena"] = new("key_arena", cap_k, torch.uint8, 0)
+    res["key_off"] = new("key_off", cap_e + 1, torch.int64, 0)
     for f, dt in LSM_SCAN_COLUMNS:
-        res[f] = torch.zeros(max(cap_e, 1), dtype=getattr(torch, dt), device=dev)
+        res[f] = new(f, cap_e, getattr(torch, dt), 0)
     out = _abi.LsmScanOut(res["range_entry_start"].data_ptr(), res["range_status"].data_ptr(),
                           res["range_ssts"].data_ptr(), res["key_arena"].data_ptr(), cap_k,
                           res["key_off"].data_ptr(), *[res[f].data_ptr() for f, _ in LSM_SCAN_COLUMNS], cap_e,
@@ -1011,7 +1043,7 @@ def _lsm_scan_out(res, cap_e, cap_k, dev):
 
 
 def _lsm_scan(entry, tree, ranges, max_seq, descending, stream, workspace, cand, cap, merge=False, cap_links=None, fill=0,
-              prefixes=None, probe_len=None, projections=None, mem=None, limit=None):
+              prefixes=None, probe_len=None, projections=None, mem=None, limit=None, alloc=None):
     """The tree scans.  entry: the C entry point, a key of READ_CALLS, which names what it takes: the filtered ones
     the policies, the prefixes, an optional chain and the filter outputs, the projected ones the projections too; merge:
     the call has a chain.  Marshals the ranges, the bounds, the prefixes and the projections as device tensors and the
@@ -1021,10 +1053,11 @@ def _lsm_scan(entry, tree, ranges, max_seq, descending, stream, workspace, cand,
     were None.  mem: for sdb_lsm_scan_mem: None (a NULL sdb_mem_view) or what mem_tables_device returned; the
     result then has table and row per output row (MEM_FIELDS), range_tables and, with a chain, chain_table and
     chain_row.  limit: for sdb_lsm_scan_recency: None, a list / array of n row limits, or a device int64 tensor; the
-    result then has range_sources_read and range_visible."""
+    result then has range_sources_read and range_visible.  alloc: see _read_output."""
     import torch
     takes = _read_args(entry)[0]
     dev = tree["device"]
+    new = alloc or functools.partial(_read_output, dev)
     if isinstance(ranges, dict):
         rt, n = ranges, int(ranges["n"])
     else:
@@ -1034,10 +1067,9 @@ def _lsm_scan(entry, tree, ranges, max_seq, descending, stream, workspace, cand,
         max_seq = _to_dev(np.asarray(list(max_seq) or [0], np.uint64), dev)
     rg = _abi.ScanRanges(n, rt["start_bytes"].data_ptr(), rt["start_off"].data_ptr(), rt["start_kind"].data_ptr(),
                          rt["end_bytes"].data_ptr(), rt["end_off"].data_ptr(), rt["end_kind"].data_ptr())
-    res = {"range_entry_start": torch.zeros(n + 1, dtype=torch.int64, device=dev),
-           "range_status": torch.zeros(max(n, 1), dtype=torch.int32, device=dev),
-           "range_ssts": torch.zeros(max(n, 1), dtype=torch.int32, device=dev),
-           "summary": torch.zeros(len(LSM_SCAN_SUMMARY), dtype=torch.int64, device=dev)}
+    res = {"range_entry_start": new("range_entry_start", n + 1, torch.int64, 0),
+           "range_status": new("range_status", n, torch.int32, 0), "range_ssts": new("range_ssts", n, torch.int32, 0),
+           "summary": new("summary", len(LSM_SCAN_SUMMARY), torch.int64, 0)}
     pjt, pj = _projections(projections, tree)
     v = _read_values(tree, mem, pj, merge)
     v.update(ranges=C.byref(rg), n=n, max_seq=_ptr(max_seq), descending=int(bool(descending)))
@@ -1049,33 +1081,33 @@ def _lsm_scan(entry, tree, ranges, max_seq, descending, stream, workspace, cand,
         v["prefixes"] = _byref(None if pt is None else _abi.ScanPrefixes(
             _ptr(pt["prefix_bytes"]), _ptr(pt["prefix_off"]), _ptr(pt["has_prefix"]), _ptr(pt.get("probe_len"))))
     if "fout" in takes:
-        res["range_filtered"] = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
-        res["num_filtered"] = torch.zeros(1, dtype=torch.int64, device=dev)
+        res["range_filtered"] = new("range_filtered", n, torch.int32, 0)
+        res["num_filtered"] = new("num_filtered", 1, torch.int64, 0)
         v["fout"] = C.byref(_abi.ScanFilterOut(res["range_filtered"].data_ptr(), res["num_filtered"].data_ptr()))
     if "mout" in takes:
-        res["range_tables"] = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        res["range_tables"] = new("range_tables", n, torch.int32, 0)
     if "rout" in takes:
         if limit is not None and not hasattr(limit, "data_ptr"):
             limit = _to_dev(np.asarray(list(limit) or [0], np.uint64), dev)
-        res["range_sources_read"] = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
-        res["range_visible"] = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+        res["range_sources_read"] = new("range_sources_read", n, torch.int32, 0)
+        res["range_visible"] = new("range_visible", n, torch.int64, 0)
         v.update(limit=_ptr(limit),
                  rout=C.byref(_abi.RecencyOut(res["range_sources_read"].data_ptr(), res["range_visible"].data_ptr())))
 
     def run(ce, ckb, cap_e, cap_k, cap_l):
         v.update(ce=ce, ckb=ckb)
-        wsb = _read_workspace_bytes(entry, v)
+        wsb = read_workspace_bytes(entry, tree, n, (ce, ckb), merge, mem)
         ws = workspace if workspace is not None and workspace.numel() >= wsb else None
         if ws is None:
             assert workspace is None or cand is None, "workspace too small"
-            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        v["out"] = C.byref(_lsm_scan_out(res, cap_e, cap_k, dev))
-        v["chain"] = C.byref(_chain_out(res, cap_e, cap_l, dev, fill)) if merge else None
+            ws = new("_ws", wsb, torch.uint8, None)
+        v["out"] = C.byref(_lsm_scan_out(res, cap_e, cap_k, new))
+        v["chain"] = C.byref(_chain_out(res, cap_e, cap_l, new, fill)) if merge else None
         if "mout" in takes:  # (rows that no call writes name no table)
-            res["table"] = torch.full((max(cap_e, 1),), -1, dtype=torch.int32, device=dev)
-            res["row"] = torch.zeros(max(cap_e, 1), dtype=torch.int64, device=dev)
+            res["table"] = new("table", cap_e, torch.int32, 0xFF)
+            res["row"] = new("row", cap_e, torch.int64, 0)
             v["mout"] = C.byref(_abi.MemScanOut(res["table"].data_ptr(), res["row"].data_ptr(), res["range_tables"].data_ptr()))
-        v["mchain"] = C.byref(_mem_chain_out(res, cap_l, dev, fill)) if merge and "mchain" in takes else None
+        v["mchain"] = C.byref(_mem_chain_out(res, cap_l, new, fill)) if merge and "mchain" in takes else None
         _read_call(entry, v, ws, wsb, stream)
         res["_ws"] = ws
 
@@ -1093,7 +1125,8 @@ def _lsm_scan(entry, tree, ranges, max_seq, descending, stream, workspace, cand,
     return res
 
 
-def lsm_scan_device(tree, ranges, max_seq=None, descending=False, stream=None, workspace=None, cand=None, cap=None):
+def lsm_scan_device(tree, ranges, max_seq=None, descending=False, stream=None, workspace=None, cand=None, cap=None,
+                    alloc=None):
     """sdb_lsm_scan: a batch of Db::scan over a device-resident tree.  tree: what lsm_tree_device built.
     ranges: a list of (start, start_kind, end, end_kind), or a dict of device tensors named as
     scan_ranges_columnar's arrays plus "n".  max_seq: None (no bound), a list / array of n bounds, or a device
@@ -1103,8 +1136,9 @@ def lsm_scan_device(tree, ranges, max_seq=None, descending=False, stream=None, w
     both given, device tensors for ranges and max_seq and a workspace it copies nothing from the host, so it can
     be captured into a graph.  Returns a dict of device tensors: range_entry_start (n + 1), range_status,
     range_ssts, key_arena, key_off, the LSM_SCAN_COLUMNS and summary (the sdb_lsm_scan_summary words in
-    LSM_SCAN_SUMMARY order); what the call allocated stays alive under "_" keys."""
-    return _lsm_scan("sdb_lsm_scan", tree, ranges, max_seq, descending, stream, workspace, cand, cap)
+    LSM_SCAN_SUMMARY order); what the call allocated stays alive under "_" keys.  alloc: where the outputs come from
+    (see _read_output); None: fresh tensors."""
+    return _lsm_scan("sdb_lsm_scan", tree, ranges, max_seq, descending, stream, workspace, cand, cap, alloc=alloc)
 
 
 CHAIN_COLUMNS = (("sst", "int32"), ("block", "int32"), ("val_off", "int64"), ("val_len", "int32"), ("seq", "int64"),
@@ -1112,39 +1146,38 @@ CHAIN_COLUMNS = (("sst", "int32"), ("block", "int32"), ("val_off", "int64"), ("v
 CHAIN_SUMMARY = ("num_links", "max_chain_len", "status")
 
 
-def _chain_out(res, items, cap_links, dev, fill=0):
+def _chain_out(res, items, cap_links, new, fill=0):
     """The sdb_chain_out of a call over `items` queries or rows with room for cap_links links; its tensors go
     into res as chain_start, chain_<column> and chain_summary."""
     import torch
-    res["chain_start"] = torch.zeros(items + 1, dtype=torch.int64, device=dev)
-    for f, dt in CHAIN_COLUMNS:
-        dtype = getattr(torch, dt)  # every byte of the link columns starts as `fill`
-        res["chain_" + f] = torch.full((max(cap_links, 1) * dtype.itemsize,), fill, dtype=torch.uint8, device=dev).view(dtype)
-    res["chain_summary"] = torch.zeros(len(CHAIN_SUMMARY), dtype=torch.int64, device=dev)
+    res["chain_start"] = new("chain_start", items + 1, torch.int64, 0)
+    for f, dt in CHAIN_COLUMNS:  # every byte of the link columns starts as `fill`
+        res["chain_" + f] = new("chain_" + f, cap_links, getattr(torch, dt), fill)
+    res["chain_summary"] = new("chain_summary", len(CHAIN_SUMMARY), torch.int64, 0)
     return _abi.ChainOut(res["chain_start"].data_ptr(), *[res["chain_" + f].data_ptr() for f, _ in CHAIN_COLUMNS],
                          cap_links, res["chain_summary"].data_ptr())
 
 
-def lsm_get_merge_device(views, runs, keys, max_seq=None, stream=None, workspace=None, cap_links=None, fill=0):
+def lsm_get_merge_device(views, runs, keys, max_seq=None, stream=None, workspace=None, cap_links=None, fill=0, alloc=None):
     """sdb_lsm_get_merge: lsm_get_device for a store with a merge operator.  Besides the GET_FIELDS and the
     summary the result holds the operand chains: chain_start (nkeys + 1), chain_<CHAIN_COLUMNS> per link and
     chain_summary (CHAIN_SUMMARY order).  cap_links: room for the links; None sizes it from a first call (a host
     synchronisation) and calls again when the links did not fit.  With cap_links given, device tensors and a
     workspace the call copies nothing from the host, so it can be captured into a graph.  fill: what the link
-    columns hold before the call, byte by byte."""
+    columns hold before the call, byte by byte.  alloc: as lsm_get_device's."""
     return _lsm_get("sdb_lsm_get_merge", views, runs, keys, max_seq, stream, workspace, merge=True, cap_links=cap_links,
-                    fill=fill)
+                    fill=fill, alloc=alloc)
 
 
 def lsm_scan_merge_device(tree, ranges, max_seq=None, descending=False, stream=None, workspace=None, cand=None,
-                          cap=None, cap_links=None, fill=0):
+                          cap=None, cap_links=None, fill=0, alloc=None):
     """sdb_lsm_scan_merge: lsm_scan_device for a store with a merge operator; arguments as there.  Besides its
     tensors the result holds the rows' operand chains: chain_start (cap_entries + 1, indexed by output row),
     chain_<CHAIN_COLUMNS> per link and chain_summary (CHAIN_SUMMARY order).  cap_links: room for the links; None
     sizes it like the staging (every link is a candidate).  With cand, cap or cap_links None the call retries
-    once on SDB_LIMIT_EXCEEDED, after a host synchronisation, as lsm_scan_device does."""
+    once on SDB_LIMIT_EXCEEDED, after a host synchronisation, as lsm_scan_device does.  alloc: as lsm_scan_device's."""
     return _lsm_scan("sdb_lsm_scan_merge", tree, ranges, max_seq, descending, stream, workspace, cand, cap, merge=True,
-                     cap_links=cap_links, fill=fill)
+                     cap_links=cap_links, fill=fill, alloc=alloc)
 
 
 def scan_prefixes_columnar(prefixes, probe_len=None):
@@ -1158,56 +1191,57 @@ def scan_prefixes_columnar(prefixes, probe_len=None):
 
 
 def lsm_scan_filtered_device(tree, ranges, prefixes=None, probe_len=None, max_seq=None, descending=False, stream=None,
-                             workspace=None, cand=None, cap=None, cap_links=None, fill=0, merge=False):
+                             workspace=None, cand=None, cap=None, cap_links=None, fill=0, merge=False, alloc=None):
     """sdb_lsm_scan_filtered: lsm_scan_device (merge=False) or lsm_scan_merge_device (merge=True) with the SSTs'
     filters consulted under the tree's policies (lsm_tree_device's per-view policy).  prefixes: None (no range has
     a prefix), a list with the scan prefix of every range (bytes: Db::scan_prefix, None: Db::scan), or a dict of
     device tensors named as scan_prefixes_columnar's arrays; probe_len: with a list of prefixes, the per-range
     lengths for SDB_PREFIX_LENGTHS SSTs.  The other arguments, the retry once on SDB_LIMIT_EXCEEDED and the result
-    are the unfiltered call's, plus range_filtered (n) and num_filtered (one element)."""
+    are the unfiltered call's, plus range_filtered (n) and num_filtered (one element).  alloc: as lsm_scan_device's."""
     return _lsm_scan("sdb_lsm_scan_filtered", tree, ranges, max_seq, descending, stream, workspace, cand, cap,
-                     merge=bool(merge), cap_links=cap_links, fill=fill, prefixes=prefixes, probe_len=probe_len)
+                     merge=bool(merge), cap_links=cap_links, fill=fill, prefixes=prefixes, probe_len=probe_len, alloc=alloc)
 
 
 def lsm_get_filtered_device(views, runs, keys, probe_len=None, max_seq=None, stream=None, workspace=None, cap_links=None,
-                            fill=0, merge=False):
+                            fill=0, merge=False, alloc=None):
     """sdb_lsm_get_filtered: lsm_get_device (merge=False) or lsm_get_merge_device (merge=True) with every SST's
     filter probed under its policy (lsm_tree_device's per-view policy), so trees written with a prefix extractor or
     without whole-key hashes are served.  probe_len: None, a list / array of nkeys lengths for SDB_PREFIX_LENGTHS
     SSTs (-1: None), or a device int32 tensor.  The other arguments, the retry on links that do not fit and the
-    result are the unfiltered call's."""
+    result are the unfiltered call's.  alloc: as lsm_get_device's."""
     return _lsm_get("sdb_lsm_get_filtered", views, runs, keys, max_seq, stream, workspace, merge=bool(merge),
-                    cap_links=cap_links, fill=fill, probe_len=probe_len)
+                    cap_links=cap_links, fill=fill, probe_len=probe_len, alloc=alloc)
 
 
 def lsm_scan_projected_device(tree, projections, ranges, prefixes=None, probe_len=None, max_seq=None, descending=False,
-                              stream=None, workspace=None, cand=None, cap=None, cap_links=None, fill=0, merge=False):
+                              stream=None, workspace=None, cand=None, cap=None, cap_links=None, fill=0, merge=False,
+                              alloc=None):
     """sdb_lsm_scan_projected: lsm_scan_filtered_device over projected SST views.  projections: None (no SST is
     projected: exactly the filtered call), a list with SsTableView.visible_range of every SST of the tree (None: the
     whole SST, else (start, start_kind, end, end_kind)), or a dict of device tensors named as projections_columnar's
-    arrays plus "n".  The other arguments and the result are the filtered call's."""
+    arrays plus "n".  The other arguments (alloc among them) and the result are the filtered call's."""
     return _lsm_scan("sdb_lsm_scan_projected", tree, ranges, max_seq, descending, stream, workspace, cand, cap,
                      merge=bool(merge), cap_links=cap_links, fill=fill, prefixes=prefixes,
-                     probe_len=probe_len, projections=projections)
+                     probe_len=probe_len, projections=projections, alloc=alloc)
 
 
 def lsm_get_projected_device(views, runs, projections, keys, probe_len=None, max_seq=None, stream=None, workspace=None,
-                             cap_links=None, fill=0, merge=False):
+                             cap_links=None, fill=0, merge=False, alloc=None):
     """sdb_lsm_get_projected: lsm_get_filtered_device over projected SST views; projections as
-    lsm_scan_projected_device takes them.  The other arguments and the result are the filtered call's."""
+    lsm_scan_projected_device takes them.  The other arguments (alloc among them) and the result are the filtered
+    call's."""
     return _lsm_get("sdb_lsm_get_projected", views, runs, keys, max_seq, stream, workspace, merge=bool(merge),
-                    cap_links=cap_links, fill=fill, probe_len=probe_len, projections=projections)
+                    cap_links=cap_links, fill=fill, probe_len=probe_len, projections=projections, alloc=alloc)
 
 
 MEM_FIELDS = (("table", "int32"), ("row", "int64"))
 
 
-def _mem_chain_out(res, cap_links, dev, fill=0):
+def _mem_chain_out(res, cap_links, new, fill=0):
     """The sdb_mem_chain_out beside _chain_out's link columns: chain_table and chain_row."""
     import torch
     for f, dt in MEM_FIELDS:
-        dtype = getattr(torch, dt)
-        res["chain_" + f] = torch.full((max(cap_links, 1) * dtype.itemsize,), fill, dtype=torch.uint8, device=dev).view(dtype)
+        res["chain_" + f] = new("chain_" + f, cap_links, getattr(torch, dt), fill)
     return _abi.MemChainOut(*[res["chain_" + f].data_ptr() for f, _ in MEM_FIELDS])
 
 
@@ -1226,42 +1260,42 @@ def mem_tables_device(runs, device="cuda"):
 
 
 def lsm_get_mem_device(tables, views, runs, keys, max_seq=None, projections=None, probe_len=None, cap_links=None,
-                       merge=False, stream=None, workspace=None, fill=0):
+                       merge=False, stream=None, workspace=None, fill=0, alloc=None):
     """sdb_lsm_get_mem: lsm_get_projected_device with device memtables searched ahead of the tree.  tables: None
     (a NULL sdb_mem_view), a list of DeviceRuns in search order, or what mem_tables_device returned; views, runs: as
-    lsm_tree_device (a tree without SSTs is searched too: the tables alone).  The other arguments, the retry on links
-    that do not fit and the result are lsm_get_projected_device's, plus table and row per query (table -1: the
-    tree decided, or nothing) and, with merge, chain_table and chain_row per link."""
+    lsm_tree_device (a tree without SSTs is searched too: the tables alone).  The other arguments (alloc among them),
+    the retry on links that do not fit and the result are lsm_get_projected_device's, plus table and row per query
+    (table -1: the tree decided, or nothing) and, with merge, chain_table and chain_row per link."""
     mem = tables if tables is None or isinstance(tables, dict) else mem_tables_device(tables)
     return _lsm_get("sdb_lsm_get_mem", views, runs, keys, max_seq, stream, workspace, merge=bool(merge),
-                    cap_links=cap_links, fill=fill, probe_len=probe_len, projections=projections, mem=mem)
+                    cap_links=cap_links, fill=fill, probe_len=probe_len, projections=projections, mem=mem, alloc=alloc)
 
 
 def lsm_scan_mem_device(tables, tree, ranges, projections=None, prefixes=None, probe_len=None, max_seq=None,
                         descending=False, stream=None, workspace=None, cand=None, cap=None, cap_links=None, fill=0,
-                        merge=False):
+                        merge=False, alloc=None):
     """sdb_lsm_scan_mem: lsm_scan_projected_device with device memtables merged ahead of the tree.  tables: None (a
     NULL sdb_mem_view), a list of DeviceRuns in search order, or what mem_tables_device returned; tree: what
-    lsm_tree_device built (a tree without SSTs is scanned too: the tables alone).  The other arguments, the retry once
-    on SDB_LIMIT_EXCEEDED and the result are lsm_scan_projected_device's, plus table and row per output row (table -1:
-    an SST holds the row), range_tables (n) and, with merge, chain_table and chain_row per link."""
+    lsm_tree_device built (a tree without SSTs is scanned too: the tables alone).  The other arguments (alloc among
+    them), the retry once on SDB_LIMIT_EXCEEDED and the result are lsm_scan_projected_device's, plus table and row per
+    output row (table -1: an SST holds the row), range_tables (n) and, with merge, chain_table and chain_row per link."""
     mem = tables if tables is None or isinstance(tables, dict) else mem_tables_device(tables, tree["device"])
     return _lsm_scan("sdb_lsm_scan_mem", tree, ranges, max_seq, descending, stream, workspace, cand, cap,
                      merge=bool(merge), cap_links=cap_links, fill=fill, prefixes=prefixes,
-                     probe_len=probe_len, projections=projections, mem=mem)
+                     probe_len=probe_len, projections=projections, mem=mem, alloc=alloc)
 
 
 def lsm_scan_recency_device(tables, tree, ranges, projections=None, prefixes=None, probe_len=None, max_seq=None, limit=None,
-                            descending=False, stream=None, workspace=None, cand=None, cap=None):
+                            descending=False, stream=None, workspace=None, cand=None, cap=None, alloc=None):
     """sdb_lsm_scan_recency: a batch of Db::scan_prefix_by_recency over device memtables and the tree: the sources
     drained one after another, newest first, every visible version a row, tombstones and merge operands included.
     ranges: the prefixes' ranges (prefix_range); prefixes: the prefixes themselves, for the filters.  limit: None
     (every source is drained), a list / array of n row limits (0: drain), or a device int64 tensor.  The other
-    arguments, the retry once on SDB_LIMIT_EXCEEDED and the result are lsm_scan_mem_device's without the chain, plus
-    range_sources_read and range_visible (n)."""
+    arguments (alloc among them), the retry once on SDB_LIMIT_EXCEEDED and the result are lsm_scan_mem_device's without
+    the chain, plus range_sources_read and range_visible (n)."""
     mem = tables if tables is None or isinstance(tables, dict) else mem_tables_device(tables, tree["device"])
     return _lsm_scan("sdb_lsm_scan_recency", tree, ranges, max_seq, descending, stream, workspace, cand, cap,
-                     prefixes=prefixes, probe_len=probe_len, projections=projections, mem=mem, limit=limit)
+                     prefixes=prefixes, probe_len=probe_len, projections=projections, mem=mem, limit=limit, alloc=alloc)
 
 
 def prefix_range(prefix):

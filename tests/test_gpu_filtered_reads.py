@@ -4,8 +4,6 @@ orders, snapshot bounds, point ranges, prefixes shorter and longer than the extr
 of one policy (the per-range hash), no false negatives against sdb_lsm_scan, NULL policies and prefixes against the
 unfiltered calls, errors behind the filter, capacities, the merge variants, the gets a tree without whole-key hashes
 needs, workspace reuse and canaries after the workspace and every output array."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -16,39 +14,12 @@ from . import get_cases as G
 from . import lsm_scan_cases as L
 from . import test_gpu_get as TG
 from . import test_gpu_lsm_scan as LS
+from .read_harness import Filled, Guard, device_tree, host, rt, to_dev, totals, view_of  # noqa: F401
 from .scan_cases import INC, partitions_covering_range
 
 pytestmark = pytest.mark.gpu
 
 U64_MAX = G.U64_MAX
-
-
-@pytest.fixture(scope="module")
-def rt():
-    from slatedb_amd import runtime
-    runtime.require_device()
-    return runtime
-
-
-def view_of(leaf, data=None, plain=False):
-    """plain: the view of the unfiltered calls' tests, no filter and no policy."""
-    v = TG.view_of(leaf, data=data)
-    v.pop("bloom", None)
-    if not plain:
-        v["policy"] = tuple(leaf.policy)
-        if leaf.bloom is not None:
-            v.update(bloom=TG._dev(leaf.bloom), bloom_len=len(leaf.bloom), num_probes=leaf.num_probes)
-    return v
-
-
-def device_tree(rt, tree, views=None, plain=False):
-    return rt.lsm_tree_device(views or [view_of(l, plain=plain) for l in tree.leaves], [len(r) for r in tree.runs])
-
-
-def host(res):
-    h = LS.host(res)
-    h["sum_num_filtered"] = int(h["num_filtered"][0])
-    return h
 
 
 _trees = {}
@@ -110,14 +81,14 @@ def test_scan_mixed_policies(rt, desc, bounded):
     check(tree, cases, bounds, desc, h, exp)
     assert h["sum_num_filtered"] >= 40 and sum(len(e.rows) for e in exp) >= 300
     # no false negatives: every range honours F4, so the rows are those of sdb_lsm_scan over the same tree
-    g = LS.host(rt.lsm_scan_device(m["plain"], [c[0] for c in cases], max_seq=bounds, descending=desc))
+    g = host(rt.lsm_scan_device(m["plain"], [c[0] for c in cases], max_seq=bounds, descending=desc))
     same_rows(h, g, len(cases))
     # (a ruled-out SST holds no key of such a range, so the candidates agree too; the blocks do not: the unfiltered
     # scan checks the covering blocks of every SST whose interval meets a tenant)
     assert h["sum_num_candidates"] == g["sum_num_candidates"]
     some = [cases[t] for t in (2, 5, 6)]  # tenants no L0 SST holds, inside every L0 SST's interval
     hb = host(call(rt, m["dev"], some, None, desc))["sum_blocks_checked"]
-    gb = LS.host(rt.lsm_scan_device(m["plain"], [c[0] for c in some], descending=desc))["sum_blocks_checked"]
+    gb = host(rt.lsm_scan_device(m["plain"], [c[0] for c in some], descending=desc))["sum_blocks_checked"]
     assert hb == len(set().union(*[e.blocks for e in model(tree, some, None, desc)])) and 0 < hb < gb
 
 
@@ -151,7 +122,7 @@ def test_scan_one_policy(rt, desc):
     assert h["sum_num_filtered"] >= 8 and exp[-3].rows == [] and exp[-3].filtered  # an absent tenant's point is pruned
     short = [e for c, e in zip(cases, exp) if c[0][0] in (b"t0", b"t03") and F.is_point(c[0])]
     assert len(short) == 4 and all(len(e.rows) == 1 and not e.filtered for e in short)
-    same_rows(h, LS.host(rt.lsm_scan_device(m["plain"], [c[0] for c in cases], descending=desc)), len(cases))
+    same_rows(h, host(rt.lsm_scan_device(m["plain"], [c[0] for c in cases], descending=desc)), len(cases))
 
 
 def test_null_policies_and_prefixes_equal_the_unfiltered_calls(rt):
@@ -159,7 +130,7 @@ def test_null_policies_and_prefixes_equal_the_unfiltered_calls(rt):
     rngs = p["ranges"][:200]
     for desc in (False, True):
         h = host(rt.lsm_scan_filtered_device(p["dev"], rngs, descending=desc))
-        g = LS.host(rt.lsm_scan_device(p["dev"], rngs, descending=desc))
+        g = host(rt.lsm_scan_device(p["dev"], rngs, descending=desc))
         for k in g:
             assert (np.asarray(h[k]) == np.asarray(g[k])).all(), k
         assert h["sum_num_filtered"] == 0 and not h["range_filtered"].any()
@@ -173,8 +144,8 @@ def test_null_policies_and_prefixes_equal_the_unfiltered_calls(rt):
     m = TG.main(rt)  # filters on most SSTs: the plain policy probes the full key, as sdb_lsm_get does
     keys, bounds = G.bounded_queries(m["tree"], m["queries"], m["straddler"])
     for b in (None, bounds):
-        h = TG.host(rt.lsm_get_filtered_device(m["dev"], None, keys, max_seq=b))
-        g = TG.host(rt.lsm_get_device(m["dev"], None, keys, max_seq=b))
+        h = host(rt.lsm_get_filtered_device(m["dev"], None, keys, max_seq=b))
+        g = host(rt.lsm_get_device(m["dev"], None, keys, max_seq=b))
         for k in g:
             assert (np.asarray(h[k]) == np.asarray(g[k])).all(), k
         assert h["ssts_filtered"].sum() > 100
@@ -223,61 +194,6 @@ def test_errors_behind_the_filter(rt, how):
     assert failing == reach and 2 <= len(failing) < len(cases)
 
 
-def raw_scan(rt, dev, cases, cand, cap, guard=None, ws=None, merge=False):
-    """One sdb_lsm_scan_filtered call with the given capacities, every output array from `guard` when given."""
-    import torch
-    n = len(cases)
-    new = guard.alloc if guard else (lambda k, dt: torch.full((max(k, 1),), 0xA5 if dt == torch.uint8 else 0, dtype=dt, device="cuda"))
-    rg = {k: TG._dev(a) for k, a in rt.scan_ranges_columnar([c[0] for c in cases]).items()}
-    px = {k: TG._dev(a) for k, a in rt.scan_prefixes_columnar([c[1] for c in cases], [c[2] for c in cases]).items()}
-    res = {"range_entry_start": new(n + 1, torch.int64), "range_status": new(n, torch.int32), "range_ssts": new(n, torch.int32),
-           "key_arena": new(cap[1], torch.uint8), "key_off": new(cap[0] + 1, torch.int64),
-           "summary": new(len(rt.LSM_SCAN_SUMMARY), torch.int64), "range_filtered": new(n, torch.int32),
-           "num_filtered": new(1, torch.int64)}
-    for f, dt in rt.LSM_SCAN_COLUMNS:
-        res[f] = new(cap[0], getattr(torch, dt))
-    out = _abi.LsmScanOut(res["range_entry_start"].data_ptr(), res["range_status"].data_ptr(), res["range_ssts"].data_ptr(),
-                          res["key_arena"].data_ptr(), cap[1], res["key_off"].data_ptr(),
-                          *[res[f].data_ptr() for f, _ in rt.LSM_SCAN_COLUMNS], cap[0], res["summary"].data_ptr())
-    ranges = _abi.ScanRanges(n, *[rg[s + k].data_ptr() for s in ("start", "end") for k in ("_bytes", "_off", "_kind")])
-    prefixes = _abi.ScanPrefixes(px["prefix_bytes"].data_ptr(), px["prefix_off"].data_ptr(), px["has_prefix"].data_ptr(),
-                                 px["probe_len"].data_ptr())
-    fout = _abi.ScanFilterOut(res["range_filtered"].data_ptr(), res["num_filtered"].data_ptr())
-    wsb = rt.lib().sdb_lsm_scan_filtered_workspace_bytes(dev["total_blocks"], dev["num_ssts"], dev["num_runs"], n, *cand, 0)
-    if ws is None:
-        ws = guard.alloc(wsb, torch.uint8, lead=257) if guard else torch.empty(wsb, dtype=torch.uint8, device="cuda")
-    st = rt.lib().sdb_lsm_scan_filtered(C.byref(dev["lsm"]), dev["_policies"].data_ptr(), C.byref(ranges), C.byref(prefixes),
-                                        None, 0, cand[0], cand[1], C.byref(out), None, C.byref(fout), ws.data_ptr(), wsb, None)
-    res["_keep"] = (rg, px, ws)
-    return st, res
-
-
-class Guard:
-    """Arrays with 0xA5 guard bytes before and after them."""
-    TAIL = 256
-
-    def __init__(self):
-        self.bufs = []
-
-    def alloc(self, n, dtype, lead=256):
-        import torch
-        nb = n * dtype.itemsize
-        big = torch.full((lead + nb + self.TAIL,), 0xA5, dtype=torch.uint8, device="cuda")
-        self.bufs.append((big, lead, nb))
-        return big[lead:lead + nb].view(dtype) if lead % 8 == 0 else big[lead:lead + nb]
-
-    def check(self):
-        import torch
-        torch.cuda.synchronize()
-        for big, lead, nb in self.bufs:
-            assert bool((big[:lead] == 0xA5).all()) and bool((big[lead + nb:] == 0xA5).all()), (lead, nb)
-
-
-def totals(exp):
-    return ((sum(e.candidates for e in exp), sum(e.cand_key_bytes for e in exp)),
-            (sum(len(e.rows) for e in exp), sum(len(r[0]) for e in exp for r in e.rows)))
-
-
 def test_scan_capacity(rt):
     m = fixture(rt, "main_tree")
     tree = m["tree"]
@@ -288,16 +204,13 @@ def test_scan_capacity(rt):
     cand, cap = totals(exp)
     free = L.scan(tree, cases[-1][0])
     assert 0 < exp[-1].candidates < free.candidates - 100 and 0 < len(exp[-1].rows) < len(free.rows)
-    st, res = raw_scan(rt, m["dev"], cases, (cand[0] - 1, cand[1]), cap)
-    h = host(res)
-    assert st == 0 and h["sum_status"] == _abi.SDB_LIMIT_EXCEEDED and h["sum_num_entries"] == 0
+    h = host(call(rt, m["dev"], cases, cand=(cand[0] - 1, cand[1]), cap=cap, alloc=Filled(0xA5)))
+    assert h["sum_status"] == _abi.SDB_LIMIT_EXCEEDED and h["sum_num_entries"] == 0
     assert (h["sum_num_candidates"], h["sum_candidate_key_bytes"]) == cand
     LS.check_ranges(exp, h)  # range_status, range_ssts and blocks_checked stay valid, and so do the filter's counts
     assert (h["range_filtered"][:len(exp)] == np.array([len(e.filtered) for e in exp])).all()
     assert h["sum_num_filtered"] == sum(len(e.filtered) for e in exp) > 0
-    st, res = raw_scan(rt, m["dev"], cases, cand, cap)
-    assert st == 0
-    check(tree, cases, None, False, host(res), exp)
+    check(tree, cases, None, False, host(call(rt, m["dev"], cases, cand=cand, cap=cap, alloc=Filled(0xA5))), exp)
 
 
 def test_scan_canaries(rt):
@@ -307,8 +220,7 @@ def test_scan_canaries(rt):
     exp = model(tree, cases, None, False)
     cand, cap = totals(exp)
     guard = Guard()
-    st, res = raw_scan(rt, m["dev"], cases, cand, cap, guard)
-    assert st == 0
+    res = call(rt, m["dev"], cases, cand=cand, cap=cap, alloc=guard)
     guard.check()
     check(tree, cases, None, False, host(res), exp)
 
@@ -322,8 +234,7 @@ def test_scan_workspace_reuse(rt):
     exp, exp2 = model(tree, cases, None, False), model(tree, other, bounds, True)
     cand = totals(exp)[0]
     dev = m["dev"]
-    ws = torch.empty(rt.lib().sdb_lsm_scan_filtered_workspace_bytes(dev["total_blocks"], dev["num_ssts"], dev["num_runs"],
-                                                                  len(cases), *cand, 0), dtype=torch.uint8, device="cuda")
+    ws = torch.empty(rt.read_workspace_bytes("sdb_lsm_scan_filtered", dev, len(cases), cand), dtype=torch.uint8, device="cuda")
     kw = dict(workspace=ws, cand=cand, cap=cand)
     r1 = call(rt, dev, cases, **kw)  # back to back on one workspace, no reset and no synchronisation between them
     r2 = call(rt, dev, other, bounds, True, **kw)
@@ -347,10 +258,10 @@ def test_scan_bad_policy_kind_and_prefix_offsets(rt):
     exp = model(tree, cases, None, False)
     assert (h["range_filtered"][:8] == np.array([len([i for i in e.filtered if i != 0]) for e in exp])).all()
     keys = [F.key(0, 1), F.key(1, 1), b"t99:"]
-    g = TG.host(rt.lsm_get_filtered_device(dev, None, keys))
+    g = host(rt.lsm_get_filtered_device(dev, None, keys))
     assert list(g["status"][:3]) == [_abi.SDB_INVALID_ARGUMENT, _abi.SDB_INVALID_ARGUMENT, 0]  # t99: is outside SST 0
     # prefix offsets that descend: the call is malformed, every range fails
-    px = {k: TG._dev(a) for k, a in rt.scan_prefixes_columnar([c[1] for c in cases], [c[2] for c in cases]).items()}
+    px = {k: to_dev(a) for k, a in rt.scan_prefixes_columnar([c[1] for c in cases], [c[2] for c in cases]).items()}
     px["prefix_off"][3] = 100
     h = host(rt.lsm_scan_filtered_device(m["dev"], [c[0] for c in cases], px))
     assert (h["range_status"][:8] == _abi.SDB_INVALID_ARGUMENT).all() and h["sum_blocks_checked"] == 0
@@ -396,7 +307,7 @@ def test_get(rt, name):
     tree = m["tree"]
     keys = F.get_keys(tree)
     pl = [F.LENGTHS_LEN] * len(keys)
-    h = TG.host(rt.lsm_get_filtered_device(m["dev"], None, keys, pl))
+    h = host(rt.lsm_get_filtered_device(m["dev"], None, keys, pl))
     got = TG.check(tree, keys, None, h)
     TG.check_blocks_checked(tree, keys, got, h)
     states = [g.state for g in got]
@@ -406,10 +317,10 @@ def test_get(rt, name):
         rows, _ = L.brute(tree, (k, INC, k, INC))
         assert (g.state == _abi.GET_FOUND) == bool(rows), k
     bounds = seq_bounds(tree, len(keys), 3)
-    h = TG.host(rt.lsm_get_filtered_device(m["dev"], None, keys, pl, max_seq=bounds))
+    h = host(rt.lsm_get_filtered_device(m["dev"], None, keys, pl, max_seq=bounds))
     TG.check(tree, keys, bounds, h)
     if name == "uniform_tree":  # the full-key probe of sdb_lsm_get loses present keys here
-        u = TG.host(rt.lsm_get_device(m["dev"], None, keys))
+        u = host(rt.lsm_get_device(m["dev"], None, keys))
         assert int((u["state"][:len(keys)] == _abi.GET_FOUND).sum()) < states.count(_abi.GET_FOUND) // 2
 
 
@@ -460,23 +371,16 @@ def test_get_filtered_with_a_chain_degenerate(rt):
     zeroed whatever they held, every query is NOT_FOUND with no SST, no link is written."""
     import torch
     m = fixture(rt, "mixed_merge_tree")
+    words = {"summary": 0x5A5A, "chain_start": 77, "chain_summary": 77}
+
+    def preset(name, count, dtype, fill):  # what every output holds before the call; the link columns byte by byte
+        if fill:
+            return torch.full((max(count, 1) * dtype.itemsize,), fill, dtype=torch.uint8, device="cuda").view(dtype)
+        return torch.full((max(count, 1),), words.get(name, 0x5A), dtype=dtype, device="cuda")
+
     for dev, keys in ((m["dev"], []), (rt.lsm_tree_device([], []), [b"a", b"", b"t03:0001"])):
         n = len(keys)
-        kb, ko = (TG._dev(a) for a in rt.keys_columnar(keys))
-        res = {f: torch.full((max(n, 1),), 0x5A, dtype=getattr(torch, dt), device="cuda") for f, dt in rt.GET_FIELDS}
-        res["summary"] = torch.full((len(rt.GET_SUMMARY),), 0x5A5A, dtype=torch.int64, device="cuda")
-        out = _abi.GetOut(*[res[f].data_ptr() for f, _ in rt.GET_FIELDS], res["summary"].data_ptr())
-        chain = rt._chain_out(res, n, 4, "cuda", 0x5A)
-        res["chain_start"].fill_(77)
-        res["chain_summary"].fill_(77)
-        wsb = rt.lib().sdb_lsm_get_filtered_workspace_bytes(dev["total_blocks"], dev["num_ssts"], dev["num_runs"], n, 1)
-        ws = torch.empty(wsb, dtype=torch.uint8, device="cuda")
-        pol = dev["_policies"]
-        st = rt.lib().sdb_lsm_get_filtered(C.byref(dev["lsm"]), pol.data_ptr() if pol is not None else None, kb.data_ptr(),
-                                           ko.data_ptr(), n, None, None, C.byref(out), C.byref(chain), ws.data_ptr(), wsb, None)
-        assert st == 0
-        torch.cuda.synchronize()
-        h = {k: v.cpu().numpy() for k, v in res.items()}
+        h = host(rt.lsm_get_filtered_device(dev, None, keys, merge=True, cap_links=4, fill=0x5A, alloc=preset))
         assert not h["chain_summary"].any() and not h["chain_start"][:n + 1].any() and not h["summary"].any()
         assert (h["chain_seq"].view(np.uint8) == 0x5A).all()
         if n:
@@ -489,28 +393,19 @@ def test_get_filtered_with_a_chain_degenerate(rt):
 
 
 def test_get_canaries_and_workspace_reuse(rt):
-    import torch
     m = fixture(rt, "main_tree")
     tree, dev = m["tree"], m["dev"]
     keys = F.get_keys(tree)
     n = len(keys)
     guard = Guard()
-    kb, ko = rt.keys_columnar(keys)
-    kb, ko = TG._dev(kb), TG._dev(ko)
-    res = {f: guard.alloc(n, getattr(torch, dt)) for f, dt in rt.GET_FIELDS}
-    res["summary"] = guard.alloc(len(rt.GET_SUMMARY), torch.int64)
-    out = _abi.GetOut(*[res[f].data_ptr() for f, _ in rt.GET_FIELDS], res["summary"].data_ptr())
-    wsb = rt.lib().sdb_lsm_get_filtered_workspace_bytes(dev["total_blocks"], dev["num_ssts"], dev["num_runs"], n, 0)
-    ws = guard.alloc(wsb, torch.uint8, lead=257)
-    for ks in (keys[::-1], keys):  # twice in one workspace, no reset: the second call's results stand
-        b, o = rt.keys_columnar(ks)
-        kb.copy_(TG._dev(b)[:kb.numel()])
-        ko.copy_(TG._dev(o))
-        st = rt.lib().sdb_lsm_get_filtered(C.byref(dev["lsm"]), dev["_policies"].data_ptr(), kb.data_ptr(), ko.data_ptr(), n,
-                                           None, None, C.byref(out), None, ws.data_ptr(), wsb, None)
-        assert st == 0
+    kb, ko = (to_dev(a) for a in rt.keys_columnar(keys[::-1]))
+    first = rt.lsm_get_filtered_device(dev, None, (kb, ko, n), alloc=guard)
+    b, o = rt.keys_columnar(keys)  # again in the same workspace and arrays, no reset: the second call's results stand
+    kb.copy_(to_dev(b)[:kb.numel()])
+    ko.copy_(to_dev(o))
+    res = rt.lsm_get_filtered_device(dev, None, (kb, ko, n), workspace=first["_ws"], alloc=lambda name, *_: first[name])
     guard.check()
-    TG.check(tree, keys, None, TG.host(res))
+    TG.check(tree, keys, None, host(res))
 
 
 def test_graph_capture(rt):
@@ -520,15 +415,13 @@ def test_graph_capture(rt):
     tree, dev, cases = m["tree"], m["dev"], F.scan_cases(m["tree"])
     exp = model(tree, cases, None, False)
     cand = totals(exp)[0]
-    rg = {k: TG._dev(a) for k, a in rt.scan_ranges_columnar([c[0] for c in cases]).items()}
+    rg = {k: to_dev(a) for k, a in rt.scan_ranges_columnar([c[0] for c in cases]).items()}
     rg["n"] = len(cases)
-    px = {k: TG._dev(a) for k, a in rt.scan_prefixes_columnar([c[1] for c in cases], [c[2] for c in cases]).items()}
+    px = {k: to_dev(a) for k, a in rt.scan_prefixes_columnar([c[1] for c in cases], [c[2] for c in cases]).items()}
     keys = F.get_keys(tree)
-    kb, ko = (TG._dev(a) for a in rt.keys_columnar(keys))
-    wss = torch.empty(rt.lib().sdb_lsm_scan_filtered_workspace_bytes(dev["total_blocks"], dev["num_ssts"], dev["num_runs"],
-                                                                   len(cases), *cand, 0), dtype=torch.uint8, device="cuda")
-    wsg = torch.empty(rt.lib().sdb_lsm_get_filtered_workspace_bytes(dev["total_blocks"], dev["num_ssts"], dev["num_runs"],
-                                                                  len(keys), 0), dtype=torch.uint8, device="cuda")
+    kb, ko = (to_dev(a) for a in rt.keys_columnar(keys))
+    wss = torch.empty(rt.read_workspace_bytes("sdb_lsm_scan_filtered", dev, len(cases), cand), dtype=torch.uint8, device="cuda")
+    wsg = torch.empty(rt.read_workspace_bytes("sdb_lsm_get_filtered", dev, len(keys)), dtype=torch.uint8, device="cuda")
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
 
@@ -550,4 +443,4 @@ def test_graph_capture(rt):
         g.replay()
         torch.cuda.synchronize()
         check(tree, cases, None, False, host(rs), exp)
-        TG.check(tree, keys, None, TG.host(rg_))
+        TG.check(tree, keys, None, host(rg_))

@@ -8,79 +8,19 @@ import pytest
 from slatedb_amd import _abi
 
 from . import get_cases as G
+from .read_harness import check_get_summary, compare, device_tree, host, rt, to_dev, view_of  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 U64_MAX = G.U64_MAX
-
-
-@pytest.fixture(scope="module")
-def rt():
-    from slatedb_amd import runtime
-    runtime.require_device()
-    return runtime
-
-
-def _dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    if a.dtype == np.uint64:
-        a = a.view(np.int64)
-    if not a.size:
-        a = np.zeros(16, a.dtype)
-    return torch.from_numpy(a).cuda()
-
-
-def view_of(leaf, data=None, block_off=None):
-    s = leaf.sst
-    v = {"data": _dev(np.concatenate([s.data if data is None else data, np.zeros(64, np.uint8)])),
-         "block_off": _dev(s.block_off if block_off is None else block_off), "num_blocks": s.nb,
-         "index_keys": _dev(s.ik_bytes), "index_key_off": _dev(s.ik_off), "sst_version": leaf.version,
-         "first_key": leaf.first_key, "last_key": leaf.last_key}
-    if leaf.bloom is not None:
-        v.update(bloom=_dev(leaf.bloom), bloom_len=len(leaf.bloom), num_probes=G.NUM_PROBES)
-    return v
-
-
-def device_tree(rt, tree, views=None):
-    return rt.lsm_tree_device(views or [view_of(l) for l in tree.leaves], [len(r) for r in tree.runs])
-
-
-def host(res):
-    import torch
-    torch.cuda.synchronize()
-    h = {k: v.cpu().numpy() for k, v in res.items() if not k.startswith("_")}
-    for i, f in enumerate(rt_summary()):
-        h["sum_" + f] = int(h["summary"][i]) & (0xFFFFFFFF if f == "status" else U64_MAX)
-    return h
-
-
-def rt_summary():
-    from slatedb_amd import runtime
-    return runtime.GET_SUMMARY
+GET_COLS = ("state", "status", "sst", "block", "val_off", "val_len", "seq", "flags", "ssts_read", "ssts_filtered")
 
 
 def check(tree, keys, bounds, h):
     """Every column of every query, and the summary, against the model.  Returns the model's results."""
-    n = len(keys)
     got = [tree.get(k, None if bounds is None else bounds[q]) for q, k in enumerate(keys)]
-    cols = [tree.columns(g) for g in got]
-    for f in ("state", "status", "sst", "block", "val_off", "val_len", "seq", "flags", "ssts_read", "ssts_filtered"):
-        want = np.array([c[f] for c in cols], np.uint64)
-        have = h[f][:n].astype(np.int64).astype(np.uint64)
-        if f in ("sst", "block", "val_len", "ssts_read", "ssts_filtered", "status"):
-            have &= np.uint64(0xFFFFFFFF)
-        bad = np.nonzero(want != have)[0]
-        assert not bad.size, (f, int(bad[0]), keys[int(bad[0])], int(want[bad[0]]), int(have[bad[0]]))
-    for f in ("create_ts", "expire_ts"):
-        for q, c in enumerate(cols):
-            assert int(h[f][q]) == (c[f] if c[f] is not None else 0), (f, q)
-    failed = [q for q, g in enumerate(got) if g.status and g.state == _abi.GET_NOT_FOUND]
-    count = lambda st: sum(1 for g in got if g.state == st)  # noqa: E731
-    assert h["sum_num_found"] == count(_abi.GET_FOUND) and h["sum_num_deleted"] == count(_abi.GET_DELETED)
-    assert h["sum_num_merge"] == count(_abi.GET_MERGE_OPERAND) and h["sum_num_failed"] == len(failed)
-    assert h["sum_num_not_found"] == count(_abi.GET_NOT_FOUND) - len(failed)
-    assert h["sum_status"] == (got[failed[0]].status if failed else 0)
+    compare(GET_COLS, [dict(tree.columns(g), key=k) for g, k in zip(got, keys)], lambda f: h[f], "get")
+    check_get_summary(got, [q for q, g in enumerate(got) if g.status and g.state == _abi.GET_NOT_FOUND], h)
     return got
 
 
@@ -331,13 +271,12 @@ def test_get_graph_capture_and_workspace_reuse(rt):
 
     def tensors(ks, bs):
         kb, ko = rt.keys_columnar(ks)
-        return _dev(kb), _dev(ko), _dev(np.array(bs, np.uint64))
+        return to_dev(kb), to_dev(ko), to_dev(np.array(bs, np.uint64))
 
     kb, ko, ms = tensors(keys, bounds)
     kb2, ko2, ms2 = tensors(keys2, bounds2)
     assert kb.numel() == kb2.numel()
-    ws = torch.empty(rt.lib().sdb_lsm_get_workspace_bytes(dev["total_blocks"], dev["num_ssts"], dev["num_runs"], n),
-                     dtype=torch.uint8, device="cuda")
+    ws = torch.empty(rt.read_workspace_bytes("sdb_lsm_get", dev, n), dtype=torch.uint8, device="cuda")
     # two calls back to back on one workspace, no reset and no synchronisation between them
     r1 = rt.lsm_get_device(dev, None, (kb, ko, n), max_seq=ms, workspace=ws)
     r2 = rt.lsm_get_device(dev, None, (kb2, ko2, n), max_seq=ms2, workspace=ws)

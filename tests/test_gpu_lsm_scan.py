@@ -3,8 +3,6 @@ tests/lsm_scan_cases.py, every column of every row and the summary: a mixed tree
 SST without blocks, a key straddling two SSTs of a run), both orders, snapshot bounds, the reference's own table,
 merge operands, block errors, a malformed tree, degenerate inputs, capacities, a workspace canary, workspace reuse
 and HIP graph capture; and, on a one-SST tree of unique keys, row for row against sdb_sst_scan."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -13,29 +11,14 @@ from slatedb_amd import _abi
 from . import get_cases as G
 from . import lsm_scan_cases as L
 from . import test_gpu_get as TG
+from .read_harness import (Filled, canaried_workspace, check_scan_core, compare, device_tree, host, intact, rt,  # noqa: F401
+                           to_dev, totals, untouched, view_of)
 from .scan_cases import EXC, INC, U
 
 pytestmark = pytest.mark.gpu
 
 U64_MAX = G.U64_MAX
 COLS = ("sst", "val_off", "val_len", "seq", "flags")
-
-
-@pytest.fixture(scope="module")
-def rt():
-    from slatedb_amd import runtime
-    runtime.require_device()
-    return runtime
-
-
-def host(res):
-    import torch
-    from slatedb_amd import runtime
-    torch.cuda.synchronize()
-    h = {k: v.cpu().numpy() for k, v in res.items() if not k.startswith("_")}
-    for i, f in enumerate(runtime.LSM_SCAN_SUMMARY):
-        h["sum_" + f] = int(h["summary"][i]) & (0xFFFFFFFF if f == "status" else U64_MAX)
-    return h
 
 
 def model(tree, rngs, bounds, desc):
@@ -53,31 +36,9 @@ def check_ranges(exp, h):
 def check(tree, rngs, bounds, desc, h, exp=None):
     """Every column of every row, and the summary, against the model.  Returns the model's results."""
     exp = exp or model(tree, rngs, bounds, desc)
-    n = len(rngs)
     check_ranges(exp, h)
-    rows = [r for e in exp for r in e.rows]
-    starts = np.concatenate([[0], np.cumsum([len(e.rows) for e in exp])]).astype(np.int64)
-    assert (h["range_entry_start"][:n + 1].astype(np.int64) == starts).all()
-    failed = [q for q, e in enumerate(exp) if e.status]
-    assert h["sum_num_entries"] == len(rows) and h["sum_key_bytes"] == sum(len(r[0]) for r in rows)
-    assert h["sum_num_candidates"] == sum(e.candidates for e in exp)
-    assert h["sum_candidate_key_bytes"] == sum(e.cand_key_bytes for e in exp)
-    assert h["sum_num_failed_ranges"] == len(failed)
-    assert h["sum_status"] == (exp[failed[0]].status if failed else 0)
-    cols = [L.columns(tree, r) for r in rows]
-    ko = h["key_off"][:len(rows) + 1].astype(np.int64)
-    assert (ko == np.concatenate([[0], np.cumsum([len(r[0]) for r in rows])])).all()
-    assert h["key_arena"][:int(ko[-1])].tobytes() == b"".join(r[0] for r in rows)
-    for f in COLS:
-        want = np.array([c[f] for c in cols], np.uint64)
-        have = h[f][:len(rows)].astype(np.int64).astype(np.uint64)
-        if f in ("sst", "val_len"):
-            have &= np.uint64(0xFFFFFFFF)
-        bad = np.nonzero(want != have)[0]
-        assert not bad.size, (f, int(bad[0]), rows[int(bad[0])], int(want[bad[0]]), int(have[bad[0]]))
-    for f in ("create_ts", "expire_ts"):
-        want = np.array([c[f] if c[f] is not None else 0 for c in cols], np.int64)
-        assert (h[f][:len(rows)] == want).all(), f
+    rows = check_scan_core(exp, h)
+    compare(COLS, [dict(L.columns(tree, r), row=r) for r in rows], lambda f: h[f], "row")
     return exp
 
 
@@ -88,14 +49,14 @@ def plain(rt):
     """The plain tree (no merge operands), its device form and its ranges, built once."""
     if not _plain:
         tree, straddler = L.plain_tree()
-        _plain.update(tree=tree, straddler=straddler, dev=TG.device_tree(rt, tree), ranges=L.ranges(tree, straddler))
+        _plain.update(tree=tree, straddler=straddler, dev=device_tree(rt, tree), ranges=L.ranges(tree, straddler))
     return _plain
 
 
 def mainm(rt):
     if not _main:
         tree, straddler = G.main_tree()
-        _main.update(tree=tree, straddler=straddler, dev=TG.device_tree(rt, tree))
+        _main.update(tree=tree, straddler=straddler, dev=device_tree(rt, tree))
     return _main
 
 
@@ -142,7 +103,7 @@ def test_scan_golden_cases(rt, version):
         tree = L.golden_tree(c, version)
         rngs = [L.golden_range(c)]
         bounds = None if c["max_seq"] is None else [c["max_seq"]]
-        h = host(rt.lsm_scan_device(TG.device_tree(rt, tree), rngs, max_seq=bounds))
+        h = host(rt.lsm_scan_device(device_tree(rt, tree), rngs, max_seq=bounds))
         check(tree, rngs, bounds, False, h)
         have = []
         ko = h["key_off"].astype(np.int64)
@@ -168,7 +129,7 @@ def test_scan_merge_operands(rt):
                     [G.leaf_of([(b"h", 1, b"old-op", 20, None, None)], 1, 4096)]])
     rngs = [(b"a", INC, b"z", INC)] * 4 + [(b"h", INC, b"h", INC)] * 2
     bounds = [U64_MAX, 90, 89, 49, U64_MAX, 25]
-    h = host(rt.lsm_scan_device(TG.device_tree(rt, small), rngs, max_seq=bounds))
+    h = host(rt.lsm_scan_device(device_tree(rt, small), rngs, max_seq=bounds))
     exp = check(small, rngs, bounds, False, h)
     M = _abi.SDB_MERGE_OPERATOR_MISSING
     assert [e.status for e in exp] == [M, M, 0, 0, 0, M]
@@ -183,19 +144,19 @@ def test_scan_block_errors(rt, how):
     i = 6  # the middle SST of the newer sorted run
     leaf = tree.leaves[i]
     bad = leaf.sst.nb // 2
-    views = [TG.view_of(l) for l in tree.leaves]
+    views = [view_of(l) for l in tree.leaves]
     if how == "crc":
         status, block_status = _abi.SDB_CHECKSUM_MISMATCH, {bad: _abi.SDB_CHECKSUM_MISMATCH}
         data = leaf.sst.data.copy()
         data[int(leaf.sst.block_off[bad]) + 5] ^= 0x40
-        views[i] = TG.view_of(leaf, data=data)
+        views[i] = view_of(leaf, data=data)
     else:  # the block's end cut to 3 bytes: Block::decode cannot hold it, and the next block starts astray
         status, block_status = _abi.SDB_CORRUPT_BLOCK, {bad: _abi.SDB_CORRUPT_BLOCK, bad + 1: _abi.SDB_CHECKSUM_MISMATCH}
         off = leaf.sst.block_off.copy()
         off[bad + 1] = off[bad] + 3
-        views[i] = TG.view_of(leaf, block_off=off)
+        views[i] = view_of(leaf, block_off=off)
     broken = TG.broken(tree, i, block_status)
-    h = host(rt.lsm_scan_device(TG.device_tree(rt, broken, views), rngs))
+    h = host(rt.lsm_scan_device(device_tree(rt, broken, views), rngs))
     exp = check(broken, rngs, None, False, h)
     clean = model(tree, rngs, None, False)
     base = int(tree.block_base[i])
@@ -216,7 +177,7 @@ def test_scan_invalid_version_view(rt):
         runs.append([G.Leaf(l.sst, False, None, 3 if j + x == 3 else l.version) for x, l in enumerate(r)])
         j += len(r)
     bad = G.Tree(runs)
-    h = host(rt.lsm_scan_device(TG.device_tree(rt, bad), rngs))
+    h = host(rt.lsm_scan_device(device_tree(rt, bad), rngs))
     exp = check(bad, rngs, None, False, h)
     hit = [e for e in exp if e.status == _abi.SDB_INVALID_VERSION]
     assert 5 < len(hit) < len(rngs) - 5 and all(3 in e.ssts for e in hit)
@@ -240,7 +201,7 @@ def test_scan_malformed_tree(rt, what):
         rs[2], rs[3] = 3, 2
         t = TG.with_arrays(rt, dev, run_start=rs)
     else:  # range offsets that descend
-        ranges = {k: TG._dev(a) for k, a in rt.scan_ranges_columnar(rngs).items()}
+        ranges = {k: to_dev(a) for k, a in rt.scan_ranges_columnar(rngs).items()}
         ranges["n"] = len(rngs)
         ranges["end_off"][40] = ranges["end_off"][41] + 1
     h = host(rt.lsm_scan_device(t, ranges))
@@ -269,78 +230,46 @@ def test_scan_degenerate(rt):
     assert not h["summary"].any() and not h["range_entry_start"].any()
     rngs = [(None, U, None, U), (b"a", INC, b"z", EXC), (b"k00002", INC, b"k00002", INC)]
     of_empty = G.Tree([[G.Leaf(G.EmptySst())], [G.Leaf(G.EmptySst()), G.Leaf(G.EmptySst())]])
-    for dev in (rt.lsm_tree_device([], []), TG.device_tree(rt, of_empty)):
+    for dev in (rt.lsm_tree_device([], []), device_tree(rt, of_empty)):
         assert dev["total_blocks"] == 0
         h = host(rt.lsm_scan_device(dev, rngs, max_seq=[5, 6, 7]))
         assert not h["summary"].any() and not h["range_entry_start"].any()
         assert not h["range_status"][:3].any() and not h["range_ssts"][:3].any()
 
 
-def raw_call(rt, dev, rngs, cand, cap, ws=None, fill=0xA5):
-    """One sdb_lsm_scan call over outputs pre-filled with `fill` -> (status, dict of device tensors)."""
-    import torch
-    n = len(rngs)
-    rg = {k: TG._dev(a) for k, a in rt.scan_ranges_columnar(rngs).items()}
-    ranges = _abi.ScanRanges(n, rg["start_bytes"].data_ptr(), rg["start_off"].data_ptr(), rg["start_kind"].data_ptr(),
-                             rg["end_bytes"].data_ptr(), rg["end_off"].data_ptr(), rg["end_kind"].data_ptr())
-    full = lambda count, dt: torch.full((max(count, 1),), fill, dtype=torch.uint8, device="cuda").repeat(  # noqa: E731
-        np.dtype(dt).itemsize).view(getattr(torch, dt))
-    res = {"range_entry_start": full(n + 1, "int64"), "range_status": full(n, "int32"), "range_ssts": full(n, "int32"),
-           "key_arena": full(cap[1] + 64, "uint8"), "key_off": full(cap[0] + 1, "int64"), "summary": full(7, "int64")}
-    for f, dt in rt.LSM_SCAN_COLUMNS:
-        res[f] = full(cap[0] + 8, dt)
-    out = _abi.LsmScanOut(res["range_entry_start"].data_ptr(), res["range_status"].data_ptr(), res["range_ssts"].data_ptr(),
-                          res["key_arena"].data_ptr(), cap[1], res["key_off"].data_ptr(),
-                          *[res[f].data_ptr() for f, _ in rt.LSM_SCAN_COLUMNS], cap[0], res["summary"].data_ptr())
-    wsb = rt.lib().sdb_lsm_scan_workspace_bytes(dev["total_blocks"], dev["num_ssts"], dev["num_runs"], n, cand[0], cand[1])
-    if ws is None:
-        ws = torch.empty(wsb, dtype=torch.uint8, device="cuda")
-    assert ws.numel() == wsb
-    st = rt.lib().sdb_lsm_scan(C.byref(dev["lsm"]), C.byref(ranges), None, 0, cand[0], cand[1], C.byref(out),
-                               ws.data_ptr(), wsb, None)
-    res["_keep"] = (rg, ws)
-    return st, res
-
-
-def untouched(h, fields):
-    return all((h[f].view(np.uint8) == 0xA5).all() for f in fields)
+def one_call(rt, dev, rngs, cand, cap, ws=None):
+    """One sdb_lsm_scan call with the given capacities over outputs pre-filled with 0xA5 -> host(result)."""
+    return host(rt.lsm_scan_device(dev, rngs, workspace=ws, cand=cand, cap=cap, alloc=Filled(0xA5)))
 
 
 def test_scan_capacity(rt):
     m = plain(rt)
     tree, rngs = m["tree"], m["ranges"][:120]
     exp = model(tree, rngs, None, False)
-    nc, ckb = sum(e.candidates for e in exp), sum(e.cand_key_bytes for e in exp)
-    ne, kb = sum(len(e.rows) for e in exp), sum(len(r[0]) for e in exp for r in e.rows)
+    (nc, ckb), (ne, kb) = totals(exp)
     assert 0 < ne < nc
     columns = ["key_arena", "key_off"] + [f for f, _ in rt.LSM_SCAN_COLUMNS]
     # no staging room: the candidate totals, nothing else
-    st, res = raw_call(rt, m["dev"], rngs, (0, 0), (ne, kb))
-    h = host(res)
-    assert st == 0 and h["sum_status"] == _abi.SDB_LIMIT_EXCEEDED
+    h = one_call(rt, m["dev"], rngs, (0, 0), (ne, kb))
+    assert h["sum_status"] == _abi.SDB_LIMIT_EXCEEDED
     assert (h["sum_num_candidates"], h["sum_candidate_key_bytes"]) == (nc, ckb)
-    assert h["sum_num_entries"] == 0 and h["sum_key_bytes"] == 0 and untouched(h, columns)
+    assert h["sum_num_entries"] == 0 and h["sum_key_bytes"] == 0 and untouched(h, columns, 0xA5)
     check_ranges(exp, h)
     # exact staging, no column room: the true totals and a valid range_entry_start, not one column byte
-    st, res = raw_call(rt, m["dev"], rngs, (nc, ckb), (0, 0))
-    h = host(res)
-    assert st == 0 and h["sum_status"] == _abi.SDB_LIMIT_EXCEEDED
-    assert (h["sum_num_entries"], h["sum_key_bytes"]) == (ne, kb) and untouched(h, columns)
+    h = one_call(rt, m["dev"], rngs, (nc, ckb), (0, 0))
+    assert h["sum_status"] == _abi.SDB_LIMIT_EXCEEDED
+    assert (h["sum_num_entries"], h["sum_key_bytes"]) == (ne, kb) and untouched(h, columns, 0xA5)
     starts = np.concatenate([[0], np.cumsum([len(e.rows) for e in exp])])
     assert (h["range_entry_start"][:len(rngs) + 1] == starts).all()
     check_ranges(exp, h)
     for short in ((ne - 1, kb), (ne, kb - 1)):  # one entry / one key byte short
-        st, res = raw_call(rt, m["dev"], rngs, (nc, ckb), short)
-        h = host(res)
-        assert h["sum_status"] == _abi.SDB_LIMIT_EXCEEDED and h["sum_num_entries"] == ne and untouched(h, columns)
+        h = one_call(rt, m["dev"], rngs, (nc, ckb), short)
+        assert h["sum_status"] == _abi.SDB_LIMIT_EXCEEDED and h["sum_num_entries"] == ne and untouched(h, columns, 0xA5)
     for short in ((nc - 1, ckb), (nc, ckb - 1)):
-        st, res = raw_call(rt, m["dev"], rngs, short, (ne, kb))
-        h = host(res)
-        assert h["sum_status"] == _abi.SDB_LIMIT_EXCEEDED and h["sum_num_entries"] == 0 and untouched(h, columns)
+        h = one_call(rt, m["dev"], rngs, short, (ne, kb))
+        assert h["sum_status"] == _abi.SDB_LIMIT_EXCEEDED and h["sum_num_entries"] == 0 and untouched(h, columns, 0xA5)
     # exact capacities: every row, and nothing past them
-    st, res = raw_call(rt, m["dev"], rngs, (nc, ckb), (ne, kb))
-    h = host(res)
-    assert st == 0
+    h = one_call(rt, m["dev"], rngs, (nc, ckb), (ne, kb))
     check(tree, rngs, None, False, h, exp)
     assert (h["key_arena"][kb:] == 0xA5).all()
     for f, _ in rt.LSM_SCAN_COLUMNS:
@@ -348,21 +277,13 @@ def test_scan_capacity(rt):
 
 
 def test_scan_workspace_canary(rt):
-    import torch
     m = plain(rt)
     tree, rngs = m["tree"], m["ranges"][:150]
     exp = model(tree, rngs, None, False)
-    cand = (sum(e.candidates for e in exp), sum(e.cand_key_bytes for e in exp))
-    cap = (sum(len(e.rows) for e in exp), sum(len(r[0]) for e in exp for r in e.rows))
-    dev = m["dev"]
-    wsb = rt.lib().sdb_lsm_scan_workspace_bytes(dev["total_blocks"], dev["num_ssts"], dev["num_runs"], len(rngs), *cand)
-    lead, tail = 257, 512
-    big = torch.full((lead + wsb + tail,), 0xA5, dtype=torch.uint8, device="cuda")
-    st, res = raw_call(rt, dev, rngs, cand, cap, ws=big[lead:lead + wsb])
-    assert st == 0
-    check(tree, rngs, None, False, host(res), exp)
-    assert bool((big[:lead] == 0xA5).all()), "bytes before the workspace changed"
-    assert bool((big[lead + wsb:] == 0xA5).all()), "bytes after the workspace changed"
+    cand, cap = totals(exp)
+    big, ws = canaried_workspace(rt, "sdb_lsm_scan", m["dev"], len(rngs), cand)
+    check(tree, rngs, None, False, one_call(rt, m["dev"], rngs, cand, cap, ws=ws), exp)
+    intact(big, ws.numel())
 
 
 def test_scan_graph_capture_and_workspace_reuse(rt):
@@ -376,15 +297,14 @@ def test_scan_graph_capture_and_workspace_reuse(rt):
     cand = (sum(e.candidates for e in exp_free), sum(e.cand_key_bytes for e in exp_free))
 
     def tensors(rs, bs):
-        d = {k: TG._dev(a) for k, a in rt.scan_ranges_columnar(rs).items()}
+        d = {k: to_dev(a) for k, a in rt.scan_ranges_columnar(rs).items()}
         d["n"] = len(rs)
-        return d, TG._dev(np.array(bs, np.uint64))
+        return d, to_dev(np.array(bs, np.uint64))
 
     rg, ms = tensors(rngs, bounds)
     rg2, ms2 = tensors(rngs2, bounds2)
     assert rg["start_bytes"].numel() == rg2["start_bytes"].numel()
-    ws = torch.empty(rt.lib().sdb_lsm_scan_workspace_bytes(dev["total_blocks"], dev["num_ssts"], dev["num_runs"], n, *cand),
-                     dtype=torch.uint8, device="cuda")
+    ws = torch.empty(rt.read_workspace_bytes("sdb_lsm_scan", dev, n, cand), dtype=torch.uint8, device="cuda")
     kw = dict(workspace=ws, cand=cand, cap=cand)
     # three calls back to back on one workspace, no reset and no synchronisation between them
     r1 = rt.lsm_scan_device(dev, rg, max_seq=ms, **kw)
@@ -457,8 +377,8 @@ def test_lsm_scan_matches_sst_scan(rt, version):
     sst, tree = leaf.sst, G.Tree([[leaf]])
     assert sst.nb >= 8 and len(set(sst.keys)) == len(sst.keys) >= 190
     rngs = _shared_ranges(sst)
-    view = TG.view_of(leaf)
-    dev = TG.device_tree(rt, tree)
+    view = view_of(leaf)
+    dev = device_tree(rt, tree)
     asc = None
     for desc in (False, True):
         # the two models agree, so a difference below lies in the kernels

@@ -15,6 +15,8 @@ from . import mem_get_cases as MG
 from . import merge_read_cases as M
 from . import replay_cases as R
 from . import test_gpu_get as TG
+from .read_harness import (canaried_workspace, check_get_summary, compare, dev_tables, dev_tree, host, intact, rt, to_dev,  # noqa: F401
+                           u64, view_of)
 
 pytestmark = pytest.mark.gpu
 
@@ -23,40 +25,6 @@ SENTINEL = 0x5A
 GET_COLS = ("state", "status", "sst", "block", "val_off", "val_len", "seq", "flags", "ssts_read", "ssts_filtered", "table",
             "row")
 LINK_COLS = ("sst", "block", "val_off", "val_len", "seq", "flags", "table", "row")
-U32_COLS = ("sst", "block", "val_len", "ssts_read", "ssts_filtered", "status", "table")
-
-
-@pytest.fixture(scope="module")
-def rt():
-    from slatedb_amd import runtime
-    runtime.require_device()
-    return runtime
-
-
-def u64(a, f):
-    a = a.astype(np.int64).astype(np.uint64)
-    return a & np.uint64(0xFFFFFFFF) if f in U32_COLS else a
-
-
-def host(res):
-    import torch
-    from slatedb_amd import runtime
-    torch.cuda.synchronize()
-    h = {k: v.cpu().numpy() for k, v in res.items() if not k.startswith("_")}
-    for i, f in enumerate(runtime.GET_SUMMARY):
-        h["sum_" + f] = int(h["summary"][i]) & (0xFFFFFFFF if f == "status" else U64_MAX)
-    if "chain_summary" in h:
-        for i, f in enumerate(runtime.CHAIN_SUMMARY):
-            h["csum_" + f] = int(h["chain_summary"][i]) & (0xFFFFFFFF if f == "status" else U64_MAX)
-    return h
-
-
-def dev_tables(rt, tables):
-    return rt.mem_tables_device([rt.DeviceRun.from_host(t.run) for t in tables])
-
-
-def dev_tree(rt, tree, views=None):
-    return TG.device_tree(rt, tree, views) if tree.leaves else rt.lsm_tree_device([], [])
 
 
 def call(rt, mem, dev, keys, bounds=None, chain=False, **kw):
@@ -64,25 +32,7 @@ def call(rt, mem, dev, keys, bounds=None, chain=False, **kw):
 
 
 def _columns(cols, keys, h, skip=()):
-    n = len(cols)
-    for f in GET_COLS:
-        if f in skip:
-            continue
-        want = np.array([c[f] for c in cols], np.uint64)
-        have = u64(h[f][:n], f)
-        bad = np.nonzero(want != have)[0]
-        assert not bad.size, (f, int(bad[0]), keys[int(bad[0])], int(want[bad[0]]), int(have[bad[0]]))
-    for f in ("create_ts", "expire_ts"):
-        want = np.array([c[f] if c[f] is not None else 0 for c in cols], np.int64)
-        assert (h[f][:n] == want).all(), f
-
-
-def _summary(got, failed, h):
-    count = lambda st: sum(1 for g in got if g.state == st)  # noqa: E731
-    assert h["sum_num_found"] == count(_abi.GET_FOUND) and h["sum_num_deleted"] == count(_abi.GET_DELETED)
-    assert h["sum_num_merge"] == count(_abi.GET_MERGE_OPERAND) and h["sum_num_failed"] == len(failed)
-    assert h["sum_num_not_found"] == count(_abi.GET_NOT_FOUND) - len(failed)
-    assert h["sum_status"] == (got[failed[0]].status if failed else 0)
+    compare([f for f in GET_COLS if f not in skip], [dict(c, key=k) for c, k in zip(cols, keys)], lambda f: h[f], "get")
 
 
 def _blocks(mt, keys, bounds, got, h, chain):
@@ -99,7 +49,7 @@ def check(mt, keys, bounds, h, skip=()):
     """A call without a chain: every column of every query, table and row, the summary.  Returns the model's results."""
     got = [mt.get(k, None if bounds is None else bounds[q]) for q, k in enumerate(keys)]
     _columns([mt.columns(g) for g in got], keys, h, skip)
-    _summary(got, [q for q, g in enumerate(got) if g.status and g.state == _abi.GET_NOT_FOUND], h)
+    check_get_summary(got, [q for q, g in enumerate(got) if g.status and g.state == _abi.GET_NOT_FOUND], h)
     _blocks(mt, keys, bounds, got, h, False)
     return got
 
@@ -109,7 +59,7 @@ def check_chain(mt, keys, bounds, h, cap=1 << 40):
     n = len(keys)
     got = [mt.get_merge(k, None if bounds is None else bounds[q]) for q, k in enumerate(keys)]
     _columns([mt.merge_columns(g) for g in got], keys, h)
-    _summary(got, [q for q, g in enumerate(got) if g.status], h)
+    check_get_summary(got, [q for q, g in enumerate(got) if g.status], h)
     _blocks(mt, keys, bounds, got, h, True)
     chains = [g.links for g in got]
     starts = np.concatenate([[0], np.cumsum([len(c) for c in chains])]).astype(np.int64)
@@ -122,15 +72,7 @@ def check_chain(mt, keys, bounds, h, cap=1 << 40):
             assert (h["chain_" + f].view(np.uint8) == SENTINEL).all(), f  # no link column written
         return got
     assert h["csum_status"] == 0
-    cols = [mt.link_columns(l) for c in chains for l in c]
-    for f in LINK_COLS:
-        want = np.array([c[f] for c in cols], np.uint64)
-        have = u64(h["chain_" + f][:total], f)
-        bad = np.nonzero(want != have)[0]
-        assert not bad.size, ("link", f, int(bad[0]), int(want[bad[0]]), int(have[bad[0]]))
-    for f in ("create_ts", "expire_ts"):
-        want = np.array([c[f] if c[f] is not None else 0 for c in cols], np.int64)
-        assert (h["chain_" + f][:total] == want).all(), f
+    compare(LINK_COLS, [mt.link_columns(l) for c in chains for l in c], lambda f: h["chain_" + f], "link")
     for f in LINK_COLS:  # nothing behind the last link
         assert (h["chain_" + f][total:].view(np.uint8) == SENTINEL).all(), f
     return got
@@ -368,10 +310,10 @@ def test_laziness(rt):
                             3 if j + x == 3 else l.version) for x, l in enumerate(r)])
         j += len(r)
     broken = G.Tree(runs)
-    views = [TG.view_of(l) for l in broken.leaves]
+    views = [view_of(l) for l in broken.leaves]
     data = leaf.sst.data.copy()
     data[int(leaf.sst.block_off[bad]) + 5] ^= 0x40
-    views[i] = TG.view_of(broken.leaves[i], data=data)
+    views[i] = view_of(broken.leaves[i], data=data)
     dev = dev_tree(rt, broken, views)
     plain = [broken.get(k) for k in keys]
     failing = [q for q, g in enumerate(plain) if g.status in (_abi.SDB_CHECKSUM_MISMATCH, _abi.SDB_INVALID_VERSION)]
@@ -516,13 +458,12 @@ def test_graph_capture_and_workspace_reuse(rt):
 
     def tensors(ks, bs):
         kb, ko = rt.keys_columnar(ks)
-        return TG._dev(kb), TG._dev(ko), TG._dev(np.array(bs, np.uint64))
+        return to_dev(kb), to_dev(ko), to_dev(np.array(bs, np.uint64))
 
     kb, ko, ms = tensors(keys, bounds)
     kb2, ko2, ms2 = tensors(keys2, bounds2)
     assert kb.numel() == kb2.numel()
-    ws = torch.empty(rt.lib().sdb_lsm_get_mem_workspace_bytes(mem["num_tables"], dev["total_blocks"], dev["num_ssts"],
-                                                              dev["num_runs"], n, 1), dtype=torch.uint8, device="cuda")
+    ws = torch.empty(rt.read_workspace_bytes("sdb_lsm_get_mem", dev, n, merge=True, tables=mem), dtype=torch.uint8, device="cuda")
     get = lambda k, b, chain=False, **kw: rt.lsm_get_mem_device(mem, dev, None, k, max_seq=b, merge=chain, fill=SENTINEL,  # noqa: E731
                                                                 workspace=ws, **kw)
     # calls back to back on one workspace, with and without a chain, no reset and no synchronisation between them
@@ -566,15 +507,10 @@ def test_graph_capture_and_workspace_reuse(rt):
 @pytest.mark.parametrize("chain", [False, True])
 def test_workspace_canary(rt, chain):
     """A workspace of exactly the advertised size inside guard bands: the call writes nothing outside it."""
-    import torch
     s = layers(rt)
     mem, dev = s["mem"], s["dev"]
     keys, bounds = s["keys"][:257], s["bounds"][:257]
-    lead, tail = 257, 512
-    wsb = rt.lib().sdb_lsm_get_mem_workspace_bytes(mem["num_tables"], dev["total_blocks"], dev["num_ssts"], dev["num_runs"],
-                                                   len(keys), int(chain))
-    big = torch.full((lead + wsb + tail,), 0xA5, dtype=torch.uint8, device="cuda")
-    h = host(rt.lsm_get_mem_device(mem, dev, None, keys, max_seq=bounds, merge=chain, fill=SENTINEL,
-                                   workspace=big[lead:lead + wsb]))
+    big, ws = canaried_workspace(rt, "sdb_lsm_get_mem", dev, len(keys), merge=chain, tables=mem)
+    h = host(rt.lsm_get_mem_device(mem, dev, None, keys, max_seq=bounds, merge=chain, fill=SENTINEL, workspace=ws))
     (check_chain if chain else check)(s["mt"], keys, bounds, h)
-    assert bool((big[:lead] == 0xA5).all()) and bool((big[lead + wsb:] == 0xA5).all())
+    intact(big, ws.numel())

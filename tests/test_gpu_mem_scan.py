@@ -3,7 +3,6 @@ against the model of tests/mem_scan_cases.py, every column of every row and link
 order of the sources and max_seq, the reference's recorded cases, chains across layers, no laziness (S5), the
 capacities (S6), no tables (S7), no tree (S8), a malformed table (S9), tables straight from the WAL replay, HIP graph
 capture with the tables changed in place, and a workspace canary."""
-import ctypes as C
 import random
 
 import numpy as np
@@ -18,6 +17,8 @@ from . import mem_scan_cases as S
 from . import merge_read_cases as M
 from . import replay_cases as R
 from . import test_gpu_get as TG
+from .read_harness import (Filled, canaried_workspace, check_scan_core, compare, dev_tables, dev_tree, device_tree, host,  # noqa: F401
+                           intact, rt, to_dev, totals, u64, untouched, view_of)
 from .scan_cases import EXC, INC, U
 
 pytestmark = pytest.mark.gpu
@@ -26,40 +27,6 @@ U64_MAX = G.U64_MAX
 SENTINEL = 0xA5
 ROW_COLS = ("sst", "table", "row", "val_off", "val_len", "seq", "flags")
 LINK_COLS = ("sst", "block", "table", "row", "val_off", "val_len", "seq", "flags")
-U32_COLS = ("sst", "block", "table", "val_len")
-
-
-@pytest.fixture(scope="module")
-def rt():
-    from slatedb_amd import runtime
-    runtime.require_device()
-    return runtime
-
-
-def host(res):
-    import torch
-    from slatedb_amd import runtime
-    torch.cuda.synchronize()
-    h = {k: v.cpu().numpy() for k, v in res.items() if not k.startswith("_")}
-    for i, f in enumerate(runtime.LSM_SCAN_SUMMARY):
-        h["sum_" + f] = int(h["summary"][i]) & (0xFFFFFFFF if f == "status" else U64_MAX)
-    if "chain_summary" in h:
-        for i, f in enumerate(runtime.CHAIN_SUMMARY):
-            h["csum_" + f] = int(h["chain_summary"][i]) & (0xFFFFFFFF if f == "status" else U64_MAX)
-    return h
-
-
-def u64(a, f):
-    a = a.astype(np.int64).astype(np.uint64)
-    return a & np.uint64(0xFFFFFFFF) if f in U32_COLS else a
-
-
-def dev_tables(rt, tables):
-    return rt.mem_tables_device([rt.DeviceRun.from_host(t.run) for t in tables])
-
-
-def dev_tree(rt, tree, views=None):
-    return TG.device_tree(rt, tree, views) if tree.leaves else rt.lsm_tree_device([], [])
 
 
 def scan(rt, mem, dev, rngs, bounds=None, desc=False, chain=False, **kw):
@@ -68,18 +35,6 @@ def scan(rt, mem, dev, rngs, bounds=None, desc=False, chain=False, **kw):
 
 def model(mt, rngs, bounds, desc, chain):
     return [S.scan(mt, r, None if bounds is None else bounds[q], desc, chain) for q, r in enumerate(rngs)]
-
-
-def _compare(names, cols, have, what):
-    n = len(cols)
-    for f in names:
-        want = np.array([c[f] for c in cols], np.uint64)
-        got = u64(have(f)[:n], f)
-        bad = np.nonzero(want != got)[0]
-        assert not bad.size, (what, f, int(bad[0]), cols[int(bad[0])], int(want[bad[0]]), int(got[bad[0]]))
-    for f in ("create_ts", "expire_ts"):
-        want = np.array([c[f] if c[f] is not None else 0 for c in cols], np.int64)
-        assert (have(f)[:n] == want).all(), (what, f)
 
 
 def check_ranges(exp, h):
@@ -96,21 +51,9 @@ def check_ranges(exp, h):
 def check(mt, rngs, bounds, desc, chain, h, exp=None, cap_links=1 << 40):
     """Every column of every row (and link), both summaries, against the model.  Returns the model's results."""
     exp = exp or model(mt, rngs, bounds, desc, chain)
-    n = len(rngs)
     check_ranges(exp, h)
-    rows = [r for e in exp for r in e.rows]
-    starts = np.concatenate([[0], np.cumsum([len(e.rows) for e in exp])]).astype(np.int64)
-    assert (h["range_entry_start"][:n + 1].astype(np.int64) == starts).all()
-    failed = [q for q, e in enumerate(exp) if e.status]
-    assert h["sum_num_entries"] == len(rows) and h["sum_key_bytes"] == sum(len(r[0]) for r in rows)
-    assert h["sum_num_candidates"] == sum(e.candidates for e in exp)
-    assert h["sum_candidate_key_bytes"] == sum(e.cand_key_bytes for e in exp)
-    assert h["sum_num_failed_ranges"] == len(failed)
-    assert h["sum_status"] == (exp[failed[0]].status if failed else 0)
-    ko = h["key_off"][:len(rows) + 1].astype(np.int64)
-    assert (ko == np.concatenate([[0], np.cumsum([len(r[0]) for r in rows])])).all()
-    assert h["key_arena"][:int(ko[-1])].tobytes() == b"".join(r[0] for r in rows)
-    _compare(ROW_COLS, [S.columns(mt, r) for r in rows], lambda f: h[f], "row")
+    rows = check_scan_core(exp, h)
+    compare(ROW_COLS, [S.columns(mt, r) for r in rows], lambda f: h[f], "row")
     if chain:
         links = [l for r in rows for l in r[1]]
         cs = np.concatenate([[0], np.cumsum([len(r[1]) for r in rows])]).astype(np.int64)
@@ -122,7 +65,7 @@ def check(mt, rngs, bounds, desc, chain, h, exp=None, cap_links=1 << 40):
                 assert (h["chain_" + f].view(np.uint8) == SENTINEL).all(), f
         else:
             assert h["csum_status"] == 0
-            _compare(LINK_COLS, [S.link_columns(mt, l) for l in links], lambda f: h["chain_" + f], "link")
+            compare(LINK_COLS, [S.link_columns(mt, l) for l in links], lambda f: h["chain_" + f], "link")
     return exp
 
 
@@ -135,7 +78,7 @@ def layers(rt):
         tree, straddler = L.plain_tree()
         tables = S.little_tables(tree)
         rngs, bounds = L.bounds_for(tree, L.ranges(tree, straddler, nrandom=60), straddler)
-        _layers.update(tree=tree, straddler=straddler, tables=tables, mt=S.MemTree(tables, tree), dev=TG.device_tree(rt, tree),
+        _layers.update(tree=tree, straddler=straddler, tables=tables, mt=S.MemTree(tables, tree), dev=device_tree(rt, tree),
                        mem=dev_tables(rt, tables), rngs=rngs[:160], bounds=bounds[:160])
     return _layers
 
@@ -308,15 +251,15 @@ def test_a_table_shields_no_block_error(rt):
     bad = leaf.sst.nb // 2
     data = leaf.sst.data.copy()
     data[int(leaf.sst.block_off[bad]) + 5] ^= 0x40
-    views = [TG.view_of(l) for l in tree.leaves]
-    views[i] = TG.view_of(leaf, data=data)
+    views = [view_of(l) for l in tree.leaves]
+    views[i] = view_of(leaf, data=data)
     broken = TG.broken(tree, i, {bad: _abi.SDB_CHECKSUM_MISMATCH})
     lo, hi = leaf.sst.keys[leaf.sst.bes[bad]], leaf.sst.keys[leaf.sst.bes[bad + 1] - 1]
     inside = [k for k in L.all_keys(tree) if lo <= k <= hi]
     cover = MG.Table([(k, 0, b"mem", 5_000_000 + n, None, None) for n, k in enumerate(inside)])  # every key of the range, newest
     mt = S.MemTree([cover] + s["tables"], broken)
     rngs = [(lo, INC, hi, INC), (inside[0], INC, inside[0], INC)] + s["rngs"][:100]
-    h = scan(rt, dev_tables(rt, mt.tables), TG.device_tree(rt, broken, views), rngs)
+    h = scan(rt, dev_tables(rt, mt.tables), device_tree(rt, broken, views), rngs)
     exp = check(mt, rngs, None, False, False, h)
     assert exp[0].status == exp[1].status == _abi.SDB_CHECKSUM_MISMATCH and exp[0].tables[0] == 0 and not exp[0].rows
     clean = model(S.MemTree([cover] + s["tables"], tree), rngs, None, False, False)
@@ -328,49 +271,11 @@ def test_a_table_shields_no_block_error(rt):
 # ------------------------------------------------------------------------------------------------
 # S6: capacity
 # ------------------------------------------------------------------------------------------------
-def raw_call(rt, mem, dev, rngs, cand, cap, cap_links=None, ws=None, fill=SENTINEL):
-    """One sdb_lsm_scan_mem call over outputs pre-filled with `fill` -> (status, dict of device tensors)."""
-    import torch
-    n = len(rngs)
-    rg = {k: TG._dev(a) for k, a in rt.scan_ranges_columnar(rngs).items()}
-    ranges = _abi.ScanRanges(n, rg["start_bytes"].data_ptr(), rg["start_off"].data_ptr(), rg["start_kind"].data_ptr(),
-                             rg["end_bytes"].data_ptr(), rg["end_off"].data_ptr(), rg["end_kind"].data_ptr())
-    full = lambda count, dt: torch.full((max(count, 1),), fill, dtype=torch.uint8, device="cuda").repeat(  # noqa: E731
-        np.dtype(dt).itemsize).view(getattr(torch, dt))
-    res = {"range_entry_start": full(n + 1, "int64"), "range_status": full(n, "int32"), "range_ssts": full(n, "int32"),
-           "range_tables": full(n, "int32"), "range_filtered": full(n, "int32"), "num_filtered": full(1, "int64"),
-           "key_arena": full(cap[1] + 64, "uint8"), "key_off": full(cap[0] + 1, "int64"), "summary": full(7, "int64"),
-           "table": full(cap[0] + 8, "int32"), "row": full(cap[0] + 8, "int64")}
-    for f, dt in rt.LSM_SCAN_COLUMNS:
-        res[f] = full(cap[0] + 8, dt)
-    out = _abi.LsmScanOut(res["range_entry_start"].data_ptr(), res["range_status"].data_ptr(), res["range_ssts"].data_ptr(),
-                          res["key_arena"].data_ptr(), cap[1], res["key_off"].data_ptr(),
-                          *[res[f].data_ptr() for f, _ in rt.LSM_SCAN_COLUMNS], cap[0], res["summary"].data_ptr())
-    mout = _abi.MemScanOut(res["table"].data_ptr(), res["row"].data_ptr(), res["range_tables"].data_ptr())
-    fout = _abi.ScanFilterOut(res["range_filtered"].data_ptr(), res["num_filtered"].data_ptr())
-    chain = mchain = None
-    if cap_links is not None:
-        res["chain_start"], res["chain_summary"] = full(cap[0] + 1, "int64"), full(3, "int64")
-        for f, dt in rt.CHAIN_COLUMNS + rt.MEM_FIELDS:
-            res["chain_" + f] = full(cap_links + 8, dt)
-        chain = _abi.ChainOut(res["chain_start"].data_ptr(), *[res["chain_" + f].data_ptr() for f, _ in rt.CHAIN_COLUMNS],
-                              cap_links, res["chain_summary"].data_ptr())
-        mchain = _abi.MemChainOut(res["chain_table"].data_ptr(), res["chain_row"].data_ptr())
-    wsb = rt.lib().sdb_lsm_scan_mem_workspace_bytes(mem["num_tables"] if mem else 0, dev["total_blocks"], dev["num_ssts"],
-                                                    dev["num_runs"], n, cand[0], cand[1], int(chain is not None))
-    if ws is None:
-        ws = torch.empty(wsb, dtype=torch.uint8, device="cuda")
-    assert ws.numel() == wsb
-    st = rt.lib().sdb_lsm_scan_mem(C.byref(mem["mem"]) if mem else None, C.byref(dev["lsm"]), None, None, C.byref(ranges), None,
-                                   None, 0, cand[0], cand[1], C.byref(out), C.byref(mout),
-                                   C.byref(chain) if chain else None, C.byref(mchain) if chain else None, C.byref(fout),
-                                   ws.data_ptr(), wsb, None)
-    res["_keep"] = (rg, ws)
-    return st, res
-
-
-def untouched(h, fields):
-    return all((h[f].view(np.uint8) == SENTINEL).all() for f in fields)
+def one_call(rt, mem, dev, rngs, cand, cap, cap_links=None, ws=None):
+    """One sdb_lsm_scan_mem call with the given capacities, without policies, projections and prefixes and with a chain
+    iff cap_links is given, over outputs pre-filled with SENTINEL -> host(result)."""
+    return host(rt.lsm_scan_mem_device(mem, dict(dev, _policies=None), rngs, workspace=ws, cand=cand, cap=cap, cap_links=cap_links,
+                                       merge=cap_links is not None, alloc=Filled(SENTINEL)))
 
 
 def test_capacity(rt):
@@ -388,24 +293,20 @@ def test_capacity(rt):
     assert 0 < ne < nc and sum(e.candidates for e in tree_only) * 4 < nc  # the need is mostly table rows
     columns = ["key_arena", "key_off", "table", "row"] + [f for f, _ in rt.LSM_SCAN_COLUMNS]
     for short in ((nc - 1, ckb), (nc, ckb - 1), (0, 0)):  # the staging one candidate / one key byte short, and none
-        st, res = raw_call(rt, mem, s["dev"], rngs, short, (ne, kb))
-        h = host(res)
-        assert st == 0 and h["sum_status"] == _abi.SDB_LIMIT_EXCEEDED
+        h = one_call(rt, mem, s["dev"], rngs, short, (ne, kb))
+        assert h["sum_status"] == _abi.SDB_LIMIT_EXCEEDED
         assert (h["sum_num_candidates"], h["sum_candidate_key_bytes"]) == (nc, ckb)
-        assert h["sum_num_entries"] == 0 and h["sum_key_bytes"] == 0 and untouched(h, columns)
+        assert h["sum_num_entries"] == 0 and h["sum_key_bytes"] == 0 and untouched(h, columns, SENTINEL)
         assert not h["range_entry_start"][:len(rngs) + 1].any()
         check_ranges(exp, h)
     for short in ((ne - 1, kb), (ne, kb - 1), (0, 0)):  # exact staging, the columns one entry / one key byte short
-        st, res = raw_call(rt, mem, s["dev"], rngs, (nc, ckb), short)
-        h = host(res)
-        assert st == 0 and h["sum_status"] == _abi.SDB_LIMIT_EXCEEDED
-        assert (h["sum_num_entries"], h["sum_key_bytes"]) == (ne, kb) and untouched(h, columns)
+        h = one_call(rt, mem, s["dev"], rngs, (nc, ckb), short)
+        assert h["sum_status"] == _abi.SDB_LIMIT_EXCEEDED
+        assert (h["sum_num_entries"], h["sum_key_bytes"]) == (ne, kb) and untouched(h, columns, SENTINEL)
         starts = np.concatenate([[0], np.cumsum([len(e.rows) for e in exp])])
         assert (h["range_entry_start"][:len(rngs) + 1] == starts).all()
         check_ranges(exp, h)
-    st, res = raw_call(rt, mem, s["dev"], rngs, (nc, ckb), (ne, kb))  # exact capacities: every row, nothing past them
-    h = host(res)
-    assert st == 0
+    h = one_call(rt, mem, s["dev"], rngs, (nc, ckb), (ne, kb))  # exact capacities: every row, nothing past them
     check(mt, rngs, None, False, False, h, exp)
     assert (h["key_arena"][kb:] == SENTINEL).all()
     for f in columns[2:]:
@@ -418,7 +319,7 @@ def test_capacity(rt):
 @pytest.mark.parametrize("chain", [False, True])
 def test_no_tables_is_the_projected_call(rt, chain):
     tree, straddler = M.chain_tree() if chain else L.plain_tree()
-    dev = TG.device_tree(rt, tree)
+    dev = device_tree(rt, tree)
     rngs = L.narrow_ranges(tree, 100) + [(None, U, None, U), (straddler, INC, None, U)]
     bounds = [U64_MAX if q % 3 else 999_000 for q in range(len(rngs))]
     n = len(rngs)
@@ -562,13 +463,10 @@ def test_graph_capture_tables_changed_in_place(rt):
     mem = rt.mem_tables_device(druns)
     exps = [model(mt, rngs, None, False, False) for mt in mts]
     cand = (max(sum(e.candidates for e in x) for x in exps), max(sum(e.cand_key_bytes for e in x) for x in exps))
-    rg = {k: TG._dev(a) for k, a in rt.scan_ranges_columnar(rngs).items()}
+    rg = {k: to_dev(a) for k, a in rt.scan_ranges_columnar(rngs).items()}
     rg["n"] = n
-    lead, tail = 257, 512
-    wsb = rt.lib().sdb_lsm_scan_mem_workspace_bytes(mem["num_tables"], dev["total_blocks"], dev["num_ssts"], dev["num_runs"], n,
-                                                    cand[0], cand[1], 0)
-    big = torch.full((lead + wsb + tail,), 0x5A, dtype=torch.uint8, device="cuda")
-    kw = dict(workspace=big[lead:lead + wsb], cand=cand, cap=cand)
+    big, ws = canaried_workspace(rt, "sdb_lsm_scan_mem", dev, n, cand, tables=mem, byte=0x5A)
+    kw = dict(workspace=ws, cand=cand, cap=cand)
     st = torch.cuda.Stream()
     st.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(st):  # the first launch (function attributes) outside the capture
@@ -595,23 +493,18 @@ def test_graph_capture_tables_changed_in_place(rt):
         check(mts[which], rngs, None, False, False, h, exps[which])
         checked.append(h["sum_blocks_checked"])
     assert checked[0] == checked[1] > 0
-    assert bool((big[:lead] == 0x5A).all()) and bool((big[lead + wsb:] == 0x5A).all())  # exactly workspace_bytes, no more
+    intact(big, ws.numel(), 0x5A)  # exactly workspace_bytes, no more
     del g
 
 
 @pytest.mark.parametrize("chain", [False, True])
 def test_workspace_canary(rt, chain):
     """A workspace of exactly the advertised size inside guard bands: the call writes nothing outside it."""
-    import torch
     mt, rngs, _ = chain_layers()
     mem, dev = dev_tables(rt, mt.tables), dev_tree(rt, mt.tree)
     exp = model(mt, rngs, None, False, chain)
-    nc, ckb = sum(e.candidates for e in exp), sum(e.cand_key_bytes for e in exp)
-    wsb = rt.lib().sdb_lsm_scan_mem_workspace_bytes(mem["num_tables"], dev["total_blocks"], dev["num_ssts"], dev["num_runs"],
-                                                    len(rngs), nc, ckb, int(chain))
-    lead, tail = 257, 512
-    big = torch.full((lead + wsb + tail,), 0x5A, dtype=torch.uint8, device="cuda")
-    st, res = raw_call(rt, mem, dev, rngs, (nc, ckb), (nc, ckb), cap_links=nc if chain else None, ws=big[lead:lead + wsb])
-    assert st == 0
-    check(mt, rngs, None, False, chain, host(res), exp)
-    assert bool((big[:lead] == 0x5A).all()) and bool((big[lead + wsb:] == 0x5A).all())
+    nc, ckb = totals(exp)[0]
+    big, ws = canaried_workspace(rt, "sdb_lsm_scan_mem", dev, len(rngs), (nc, ckb), chain, mem, byte=0x5A)
+    h = one_call(rt, mem, dev, rngs, (nc, ckb), (nc, ckb), cap_links=nc if chain else None, ws=ws)
+    check(mt, rngs, None, False, chain, h, exp)
+    intact(big, ws.numel(), 0x5A)

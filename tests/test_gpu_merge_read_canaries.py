@@ -5,46 +5,23 @@ relies on a zeroed workspace."""
 import pytest
 
 from . import merge_read_cases as M
-from . import test_gpu_get as TG
 from . import test_gpu_merge_reads as T
+from .read_harness import canaried_workspace, host, intact, rt  # noqa: F401
 from .scan_cases import EXC, INC, U
 
 pytestmark = pytest.mark.gpu
-
-LEAD, TAIL = 257, 512
-
-
-@pytest.fixture(scope="module")
-def rt():
-    from slatedb_amd import runtime
-    runtime.require_device()
-    return runtime
-
-
-def canaried(wsb):
-    import torch
-    big = torch.full((LEAD + wsb + TAIL,), 0xA5, dtype=torch.uint8, device="cuda")
-    return big, big[LEAD:LEAD + wsb]
-
-
-def intact(big, wsb):
-    import torch
-    torch.cuda.synchronize()
-    assert bool((big[:LEAD] == 0xA5).all()), "bytes before the workspace changed"
-    assert bool((big[LEAD + wsb:] == 0xA5).all()), "bytes after the workspace changed"
 
 
 @pytest.mark.parametrize("versions", ["mixed", 1])
 def test_get_merge_canaries(rt, versions):
     m = T.chain(rt, versions)
     tree, dev, keys = m["tree"], m["dev"], m["queries"]
-    wsb = rt.lib().sdb_lsm_get_merge_workspace_bytes(dev["total_blocks"], dev["num_ssts"], dev["num_runs"], len(keys))
-    big, ws = canaried(wsb)
+    big, ws = canaried_workspace(rt, "sdb_lsm_get_merge", dev, len(keys))
     bounds = M.chain_bounds(tree, keys)
     for b in (None, bounds):
-        h = T.ghost(rt.lsm_get_merge_device(dev, None, keys, max_seq=b, workspace=ws, cap_links=2048, fill=T.SENTINEL))
+        h = host(rt.lsm_get_merge_device(dev, None, keys, max_seq=b, workspace=ws, cap_links=2048, fill=T.SENTINEL))
         T.check_get(tree, keys, b, h)
-        intact(big, wsb)
+        intact(big, ws.numel())
 
 
 @pytest.mark.parametrize("desc", [False, True])
@@ -56,9 +33,8 @@ def test_scan_merge_canaries(rt, desc):
     cand = (sum(e.candidates for e in exp), sum(e.cand_key_bytes for e in exp))  # exact: the arrays end where the workspace ends
     rows = [r for e in exp for r in e.rows]
     cap = (len(rows), sum(len(r[0]) for r in rows))
-    wsb = rt.lib().sdb_lsm_scan_merge_workspace_bytes(dev["total_blocks"], dev["num_ssts"], dev["num_runs"], len(rngs), *cand)
-    big, ws = canaried(wsb)
-    h = T.shost(rt.lsm_scan_merge_device(dev, rngs, descending=desc, workspace=ws, cand=cand, cap=cap,
-                                         cap_links=sum(len(r[1]) for r in rows), fill=T.SENTINEL))
+    big, ws = canaried_workspace(rt, "sdb_lsm_scan_merge", dev, len(rngs), cand)
+    h = host(rt.lsm_scan_merge_device(dev, rngs, descending=desc, workspace=ws, cand=cand, cap=cap,
+                                      cap_links=sum(len(r[1]) for r in rows), fill=T.SENTINEL))
     T.check_scan(tree, rngs, None, desc, h)
-    intact(big, wsb)
+    intact(big, ws.numel())

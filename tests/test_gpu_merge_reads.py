@@ -13,6 +13,7 @@ from . import get_cases as G
 from . import lsm_scan_cases as L
 from . import merge_read_cases as M
 from . import test_gpu_get as TG
+from .read_harness import check_get_summary, compare, device_tree, host, rt, to_dev, view_of  # noqa: F401
 from .scan_cases import EXC, INC, U
 
 pytestmark = pytest.mark.gpu
@@ -20,40 +21,6 @@ pytestmark = pytest.mark.gpu
 U64_MAX = G.U64_MAX
 SENTINEL = 0x5A
 LINK_COLS = ("sst", "block", "val_off", "val_len", "seq", "flags")
-
-
-@pytest.fixture(scope="module")
-def rt():
-    from slatedb_amd import runtime
-    runtime.require_device()
-    return runtime
-
-
-def host(res, summary):
-    import torch
-    from slatedb_amd import runtime
-    torch.cuda.synchronize()
-    h = {k: v.cpu().numpy() for k, v in res.items() if not k.startswith("_")}
-    for i, f in enumerate(summary):
-        h["sum_" + f] = int(h["summary"][i]) & (0xFFFFFFFF if f == "status" else U64_MAX)
-    for i, f in enumerate(runtime.CHAIN_SUMMARY):
-        h["csum_" + f] = int(h["chain_summary"][i]) & (0xFFFFFFFF if f == "status" else U64_MAX)
-    return h
-
-
-def ghost(res):
-    from slatedb_amd import runtime
-    return host(res, runtime.GET_SUMMARY)
-
-
-def shost(res):
-    from slatedb_amd import runtime
-    return host(res, runtime.LSM_SCAN_SUMMARY)
-
-
-def u64(a, f):
-    a = a.astype(np.int64).astype(np.uint64)
-    return a & np.uint64(0xFFFFFFFF) if f in ("sst", "block", "val_len", "ssts_read", "ssts_filtered", "status") else a
 
 
 def check_links(tree, chains, h, cap):
@@ -69,38 +36,16 @@ def check_links(tree, chains, h, cap):
             assert (h["chain_" + f].view(np.uint8) == SENTINEL).all(), f  # no link column written
         return
     assert h["csum_status"] == 0
-    cols = [M.link_columns(tree, l) for c in chains for l in c]
-    for f in LINK_COLS:
-        want = np.array([c[f] for c in cols], np.uint64)
-        have = u64(h["chain_" + f][:total], f)
-        bad = np.nonzero(want != have)[0]
-        assert not bad.size, ("link", f, int(bad[0]), int(want[bad[0]]), int(have[bad[0]]))
-    for f in ("create_ts", "expire_ts"):
-        want = np.array([c[f] if c[f] is not None else 0 for c in cols], np.int64)
-        assert (h["chain_" + f][:total] == want).all(), f
+    compare(LINK_COLS, [M.link_columns(tree, l) for c in chains for l in c], lambda f: h["chain_" + f], "link")
     for f in LINK_COLS:  # nothing behind the last link
         assert (h["chain_" + f][total:].view(np.uint8) == SENTINEL).all(), f
 
 
 def check_get(tree, keys, bounds, h, cap=1 << 40):
     """Every column of every query, the links and both summaries against the model.  Returns the model's results."""
-    n = len(keys)
     got = [M.get_merge(tree, k, None if bounds is None else bounds[q]) for q, k in enumerate(keys)]
-    cols = [M.get_columns(tree, g) for g in got]
-    for f in ("state", "status", "sst", "block", "val_off", "val_len", "seq", "flags", "ssts_read", "ssts_filtered"):
-        want = np.array([c[f] for c in cols], np.uint64)
-        have = u64(h[f][:n], f)
-        bad = np.nonzero(want != have)[0]
-        assert not bad.size, (f, int(bad[0]), keys[int(bad[0])], int(want[bad[0]]), int(have[bad[0]]))
-    for f in ("create_ts", "expire_ts"):
-        want = np.array([c[f] if c[f] is not None else 0 for c in cols], np.int64)
-        assert (h[f][:n] == want).all(), f
-    failed = [q for q, g in enumerate(got) if g.status]
-    count = lambda st: sum(1 for g in got if g.state == st)  # noqa: E731
-    assert h["sum_num_found"] == count(_abi.GET_FOUND) and h["sum_num_deleted"] == count(_abi.GET_DELETED)
-    assert h["sum_num_merge"] == count(_abi.GET_MERGE_OPERAND) and h["sum_num_failed"] == len(failed)
-    assert h["sum_num_not_found"] == count(_abi.GET_NOT_FOUND) - len(failed)
-    assert h["sum_status"] == (got[failed[0]].status if failed else 0)
+    compare(TG.GET_COLS, [dict(M.get_columns(tree, g), key=k) for g, k in zip(got, keys)], lambda f: h[f], "get")
+    check_get_summary(got, [q for q, g in enumerate(got) if g.status], h)
     check_links(tree, [g.links for g in got], h, cap)
     return got
 
@@ -118,18 +63,10 @@ def check_scan(tree, rngs, bounds, desc, h, cap=1 << 40):
     assert h["sum_num_entries"] == len(rows) and h["sum_key_bytes"] == sum(len(r[0]) for r in rows)
     assert h["sum_num_candidates"] == sum(e.candidates for e in exp)
     assert h["sum_num_failed_ranges"] == len(failed) and h["sum_status"] == (exp[failed[0]].status if failed else 0)
-    cols = [M.scan_columns(tree, r) for r in rows]
     ko = h["key_off"][:len(rows) + 1].astype(np.int64)
     assert (ko == np.concatenate([[0], np.cumsum([len(r[0]) for r in rows])])).all()
     assert h["key_arena"][:int(ko[-1])].tobytes() == b"".join(r[0] for r in rows)
-    for f in ("sst", "val_off", "val_len", "seq", "flags"):
-        want = np.array([c[f] for c in cols], np.uint64)
-        have = u64(h[f][:len(rows)], f)
-        bad = np.nonzero(want != have)[0]
-        assert not bad.size, (f, int(bad[0]), rows[int(bad[0])][0], int(want[bad[0]]), int(have[bad[0]]))
-    for f in ("create_ts", "expire_ts"):
-        want = np.array([c[f] if c[f] is not None else 0 for c in cols], np.int64)
-        assert (h[f][:len(rows)] == want).all(), f
+    compare(("sst", "val_off", "val_len", "seq", "flags"), [dict(M.scan_columns(tree, r), key=r[0]) for r in rows], lambda f: h[f], "row")
     check_links(tree, [r[1] for r in rows], h, cap)
     return exp
 
@@ -145,7 +82,7 @@ def chain(rt, versions):
     """A chain tree, its device form and its queries, built once per format mix."""
     if versions not in _trees:
         tree, straddler = M.chain_tree(versions)
-        _trees[versions] = dict(tree=tree, straddler=straddler, dev=TG.device_tree(rt, tree),
+        _trees[versions] = dict(tree=tree, straddler=straddler, dev=device_tree(rt, tree),
                                 queries=M.chain_queries(tree, straddler))
     return _trees[versions]
 
@@ -161,7 +98,7 @@ def test_golden_gets(rt, version):
         tree = G.golden_tree(c, version, bloom=(len(c["entries"]) % 2 == 0))
         key = c["query_key"].encode()
         bounds = None if c["max_seq"] is None else [c["max_seq"]]
-        h = ghost(rt.lsm_get_merge_device(TG.device_tree(rt, tree), None, [key], max_seq=bounds, fill=SENTINEL))
+        h = host(rt.lsm_get_merge_device(device_tree(rt, tree), None, [key], max_seq=bounds, fill=SENTINEL))
         check_get(tree, [key], bounds, h)
         (got,) = folded_from_device(tree, [key], h)
         assert got == (None if c["expected"] is None else c["expected"].encode()), c["description"]
@@ -176,7 +113,7 @@ def test_golden_iterator_cases(rt, version, desc):
         for split in (1, 2):
             tree = M.iter_tree(c, version, split=split)
             rngs = [(None, U, None, U)]
-            h = shost(rt.lsm_scan_merge_device(TG.device_tree(rt, tree), rngs, descending=desc, fill=SENTINEL))
+            h = host(rt.lsm_scan_merge_device(device_tree(rt, tree), rngs, descending=desc, fill=SENTINEL))
             (exp,) = check_scan(tree, rngs, None, desc, h)
             keys = [r[0] for r in exp.rows]
             vals = folded_from_device(tree, keys, h)
@@ -195,7 +132,7 @@ def test_get_merge_chains(rt, versions):
     m = chain(rt, versions)
     tree, keys = m["tree"], m["queries"]
     assert 200 <= len(keys) <= 300 and len(keys) % 64
-    h = ghost(rt.lsm_get_merge_device(m["dev"], None, keys, fill=SENTINEL))
+    h = host(rt.lsm_get_merge_device(m["dev"], None, keys, fill=SENTINEL))
     got = check_get(tree, keys, None, h)
     ops = [g for g in got if g.state == _abi.GET_MERGE_OPERAND]
     assert len(ops) >= 40 and any(len(g.links) == 1 for g in ops) and max(len(g.links) for g in ops) >= 12
@@ -206,7 +143,7 @@ def test_get_merge_chains(rt, versions):
         assert vals[q] == (M.folded(tree, keys[q], g.links, g.base) if g.links else None)
     # bounds above, inside and below the chains
     bounds = M.chain_bounds(tree, keys)
-    hb = ghost(rt.lsm_get_merge_device(m["dev"], None, keys, max_seq=bounds, fill=SENTINEL))
+    hb = host(rt.lsm_get_merge_device(m["dev"], None, keys, max_seq=bounds, fill=SENTINEL))
     gb = check_get(tree, keys, bounds, hb)
     inside = sum(1 for a, b in zip(got, gb) if a.links and b.links and a.links != b.links and set(b.links) < set(a.links))
     assert inside >= 5 and any(b == 0 for b in bounds) and any(b == U64_MAX for b in bounds)
@@ -221,9 +158,9 @@ def test_aggregates_and_a_tombstone_base(rt):
              (b"c", 1, b"m", 17, None, None), (b"e", 1, b"solo", 16, None, 6)]
     for version in (2, 1):
         tree = G.Tree([[G.leaf_of(newer, version, 64)], [G.leaf_of(older, version, 64)]])
-        dev = TG.device_tree(rt, tree)
+        dev = device_tree(rt, tree)
         keys = [b"a", b"b", b"c", b"d", b"e", b"f"]
-        h = ghost(rt.lsm_get_merge_device(dev, None, keys, fill=SENTINEL))
+        h = host(rt.lsm_get_merge_device(dev, None, keys, fill=SENTINEL))
         check_get(tree, keys, None, h)
         assert h["state"][:6].tolist() == [3, 3, 3, 1, 3, 0] and h["chain_start"].tolist() == [0, 4, 5, 7, 8, 9, 9]
         both = _abi.FLAG_HAS_CREATE_TS | _abi.FLAG_HAS_EXPIRE_TS
@@ -232,7 +169,7 @@ def test_aggregates_and_a_tombstone_base(rt):
         assert (int(h["create_ts"][1]), int(h["expire_ts"][1]), int(h["flags"][1])) == (5, 900, both | _abi.FLAG_MERGE_OPERAND)
         assert int(h["flags"][2]) == _abi.FLAG_MERGE_OPERAND and int(h["flags"][3]) == both
         rngs = [(None, U, None, U), (b"b", INC, b"b", INC)]
-        hs = shost(rt.lsm_scan_merge_device(dev, rngs, fill=SENTINEL))
+        hs = host(rt.lsm_scan_merge_device(dev, rngs, fill=SENTINEL))
         check_scan(tree, rngs, None, False, hs)
         # b through the scan: the tombstone is the base; its create_ts is folded (V1 tombstones carry no expire_ts)
         assert [int(hs[f][5]) for f in ("create_ts", "expire_ts", "flags")] == [99, 100 if version == 2 else 900, both]
@@ -268,19 +205,19 @@ def test_get_merge_lazy_errors(rt, how):
     leaf = tree.leaves[i]
     assert leaf.bloom is not None
     bad, reach, inside, before, kept_out = pick_bad_block(tree, i, keys)
-    views = [TG.view_of(l) for l in tree.leaves]
+    views = [view_of(l) for l in tree.leaves]
     if how == "crc":
         status, block_status = _abi.SDB_CHECKSUM_MISMATCH, {bad: _abi.SDB_CHECKSUM_MISMATCH}
         data = leaf.sst.data.copy()
         data[int(leaf.sst.block_off[bad]) + 5] ^= 0x40
-        views[i] = TG.view_of(leaf, data=data)
+        views[i] = view_of(leaf, data=data)
     else:
         status, block_status = _abi.SDB_CORRUPT_BLOCK, {bad: _abi.SDB_CORRUPT_BLOCK, bad + 1: _abi.SDB_CHECKSUM_MISMATCH}
         off = leaf.sst.block_off.copy()
         off[bad + 1] = off[bad] + 3
-        views[i] = TG.view_of(leaf, block_off=off)
+        views[i] = view_of(leaf, block_off=off)
     model = TG.broken(tree, i, block_status)
-    h = ghost(rt.lsm_get_merge_device(TG.device_tree(rt, model, views), None, keys, fill=SENTINEL))
+    h = host(rt.lsm_get_merge_device(device_tree(rt, model, views), None, keys, fill=SENTINEL))
     got = check_get(model, keys, None, h)
     clean = [M.get_merge(tree, k) for k in keys]
     assert all(got[q].status == status and not got[q].links for q in reach)
@@ -299,7 +236,7 @@ def test_sequence_order_and_an_invalid_view(rt):
     tree = G.Tree([[G.leaf_of(new, 2, 4096)], [G.leaf_of(old, 1, 4096)]])
     keys = [b"k", b"m", b"z", b"k"]
     bounds = [U64_MAX, U64_MAX, U64_MAX, 55]  # under the bound the older SST's version is not seen
-    h = ghost(rt.lsm_get_merge_device(TG.device_tree(rt, tree), None, keys, max_seq=bounds, fill=SENTINEL))
+    h = host(rt.lsm_get_merge_device(device_tree(rt, tree), None, keys, max_seq=bounds, fill=SENTINEL))
     got = check_get(tree, keys, bounds, h)
     assert [g.status for g in got] == [_abi.SDB_INVALID_SEQUENCE_ORDER, 0, 0, 0]
     assert h["state"][:4].tolist() == [0, 3, 1, 3] and h["chain_start"].tolist() == [0, 0, 2, 3, 4]
@@ -312,7 +249,7 @@ def test_sequence_order_and_an_invalid_view(rt):
         j += len(r)
     model = G.Tree(runs)
     keys = m["queries"]
-    h = ghost(rt.lsm_get_merge_device(TG.device_tree(rt, model), None, keys, fill=SENTINEL))
+    h = host(rt.lsm_get_merge_device(device_tree(rt, model), None, keys, fill=SENTINEL))
     got = check_get(model, keys, None, h)
     clean = [M.get_merge(m["tree"], k) for k in keys]
     hit = [q for q, g in enumerate(got) if g.status == _abi.SDB_INVALID_VERSION]
@@ -330,10 +267,10 @@ def test_get_merge_capacity(rt):
     total = sum(len(M.get_merge(tree, k).links) for k in keys)
     assert total > len(keys)
     for cap in (0, total - 1, total):
-        h = ghost(rt.lsm_get_merge_device(m["dev"], None, keys, cap_links=cap, fill=SENTINEL))
+        h = host(rt.lsm_get_merge_device(m["dev"], None, keys, cap_links=cap, fill=SENTINEL))
         check_get(tree, keys, None, h, cap=cap)  # the per-query columns and chain_start are valid either way
         assert (h["csum_status"] == 0) == (cap == total)
-    h = ghost(rt.lsm_get_merge_device(m["dev"], None, keys, fill=SENTINEL))  # sized by a first call
+    h = host(rt.lsm_get_merge_device(m["dev"], None, keys, fill=SENTINEL))  # sized by a first call
     check_get(tree, keys, None, h)
     assert h["chain_sst"].size == total
 
@@ -348,8 +285,8 @@ def test_scan_merge_capacity_order(rt):
     rows = [r for e in exp for r in e.rows]
     nr, kb, nl = len(rows), sum(len(r[0]) for r in rows), sum(len(r[1]) for r in rows)
     assert nl > nr > 3
-    run = lambda cand, cap, cl: shost(rt.lsm_scan_merge_device(m["dev"], rngs, cand=cand, cap=cap, cap_links=cl,  # noqa: E731
-                                                                fill=SENTINEL))
+    run = lambda cand, cap, cl: host(rt.lsm_scan_merge_device(m["dev"], rngs, cand=cand, cap=cap, cap_links=cl,  # noqa: E731
+                                                               fill=SENTINEL))
     untouched = lambda h: all((h["chain_" + f].view(np.uint8) == SENTINEL).all() for f, _ in rt.CHAIN_COLUMNS)  # noqa: E731
     h = run((ce - 1, ckb), (nr, kb), nl)  # the candidates do not fit
     assert h["sum_status"] == _abi.SDB_LIMIT_EXCEEDED and h["sum_num_candidates"] == ce and h["sum_num_entries"] == 0
@@ -365,7 +302,7 @@ def test_scan_merge_capacity_order(rt):
     h = run((ce, ckb), (nr, kb), nl)  # exact
     check_scan(tree, rngs, None, False, h, cap=nl)
     assert h["csum_status"] == 0
-    h = shost(rt.lsm_scan_merge_device(m["dev"], rngs, fill=SENTINEL))  # the wrapper retries once
+    h = host(rt.lsm_scan_merge_device(m["dev"], rngs, fill=SENTINEL))  # the wrapper retries once
     check_scan(tree, rngs, None, False, h)
 
 
@@ -380,7 +317,7 @@ def test_scan_merge_chains(rt, versions, desc):
     rngs = [(None, U, None, U), (M.CUT_KEY, INC, M.CUT_KEY, INC), (M.CUT_KEY, EXC, None, U), (b"k0020", INC, b"k0060", EXC),
             (b"k0020", INC, b"k0060", EXC), (b"k0041", INC, b"k0041", INC), (b"k0090", INC, b"k0010", INC)]
     rngs += L.narrow_ranges(tree, count=200, seed=9)
-    h = shost(rt.lsm_scan_merge_device(m["dev"], rngs, descending=desc, fill=SENTINEL))
+    h = host(rt.lsm_scan_merge_device(m["dev"], rngs, descending=desc, fill=SENTINEL))
     exp = check_scan(tree, rngs, None, desc, h)
     full = exp[0].rows
     assert len(full) >= 60 and max(len(r[1]) for r in full) >= 12 and any(len(r[1]) == 1 for r in full)
@@ -399,7 +336,7 @@ def test_scan_merge_chains(rt, versions, desc):
         rng = np.random.default_rng(4)
         rb = rngs[:60]
         bounds = [U64_MAX if q % 4 == 0 else seqs[int(rng.integers(0, len(seqs)))] for q in range(len(rb))]
-        hb = shost(rt.lsm_scan_merge_device(m["dev"], rb, max_seq=bounds, fill=SENTINEL))
+        hb = host(rt.lsm_scan_merge_device(m["dev"], rb, max_seq=bounds, fill=SENTINEL))
         eb = check_scan(tree, rb, bounds, False, hb)
         assert 0 < len(eb[1].rows) + len(eb[0].rows) and len(eb[0].rows) <= len(keys0)
 
@@ -422,7 +359,7 @@ def test_scan_merge_side_by_side(rt, desc):
     for version in (2, 1):
         tree = side_by_side(version)
         rngs = [(None, U, None, U), (b"k2", INC, b"k4", INC), (b"k3", INC, b"k6", INC), (b"k70", INC, None, U)]
-        h = shost(rt.lsm_scan_merge_device(TG.device_tree(rt, tree), rngs, descending=desc, fill=SENTINEL))
+        h = host(rt.lsm_scan_merge_device(device_tree(rt, tree), rngs, descending=desc, fill=SENTINEL))
         exp = check_scan(tree, rngs, None, desc, h)
         rows = exp[0].rows[::-1] if desc else exp[0].rows
         assert [r[0] for r in rows[:5]] == [b"k1", b"k2", b"k3", b"k4", b"k6"]
@@ -435,10 +372,10 @@ def test_scan_merge_side_by_side(rt, desc):
         bad = leaf.sst.nb - 1
         data = leaf.sst.data.copy()
         data[int(leaf.sst.block_off[bad]) + 5] ^= 0x40
-        views = [TG.view_of(l) for l in tree.leaves]
-        views[2] = TG.view_of(leaf, data=data)
+        views = [view_of(l) for l in tree.leaves]
+        views[2] = view_of(leaf, data=data)
         model = TG.broken(tree, 2, {bad: _abi.SDB_CHECKSUM_MISMATCH})
-        hb = shost(rt.lsm_scan_merge_device(TG.device_tree(rt, model, views), rngs, descending=desc, fill=SENTINEL))
+        hb = host(rt.lsm_scan_merge_device(device_tree(rt, model, views), rngs, descending=desc, fill=SENTINEL))
         eb = check_scan(model, rngs, None, desc, hb)
         assert [e.status for e in eb] == [_abi.SDB_CHECKSUM_MISMATCH, 0, 0, _abi.SDB_CHECKSUM_MISMATCH]
         assert eb[1].rows == exp[1].rows and eb[2].rows == exp[2].rows
@@ -449,11 +386,11 @@ def test_scan_merge_side_by_side(rt, desc):
 # ------------------------------------------------------------------------------------------------
 def test_no_operands_equals_the_plain_reads(rt):
     tree, straddler = M.no_operand_tree()
-    dev = TG.device_tree(rt, tree)
+    dev = device_tree(rt, tree)
     keys = G.main_queries(tree, straddler)[:300]
     bounds = G.bounded_queries(tree, keys, straddler)[1][:len(keys)]
-    plain = TG.host(rt.lsm_get_device(dev, None, keys, max_seq=bounds))
-    h = ghost(rt.lsm_get_merge_device(dev, None, keys, max_seq=bounds, fill=SENTINEL))
+    plain = host(rt.lsm_get_device(dev, None, keys, max_seq=bounds))
+    h = host(rt.lsm_get_merge_device(dev, None, keys, max_seq=bounds, fill=SENTINEL))
     for f, _ in rt.GET_FIELDS:
         assert (plain[f] == h[f]).all(), f
     assert (plain["summary"] == h["summary"]).all()
@@ -463,7 +400,7 @@ def test_no_operands_equals_the_plain_reads(rt):
     rngs = L.ranges(tree, straddler)[:120]
     for desc in (False, True):
         p = rt.lsm_scan_device(dev, rngs, descending=desc)
-        hs = shost(rt.lsm_scan_merge_device(dev, rngs, descending=desc, fill=SENTINEL))
+        hs = host(rt.lsm_scan_merge_device(dev, rngs, descending=desc, fill=SENTINEL))
         ph = {k: v.cpu().numpy() for k, v in p.items() if not k.startswith("_")}
         ne = int(ph["summary"][0])
         assert ne > 150 and (ph["summary"] == hs["summary"]).all()
@@ -481,19 +418,19 @@ def test_no_operands_equals_the_plain_reads(rt):
 # ------------------------------------------------------------------------------------------------
 def test_degenerate(rt):
     m = chain(rt, "mixed")
-    h = ghost(rt.lsm_get_merge_device(m["dev"], None, [], fill=SENTINEL))
+    h = host(rt.lsm_get_merge_device(m["dev"], None, [], fill=SENTINEL))
     assert not h["summary"].any() and not h["chain_summary"].any() and h["chain_start"].tolist() == [0]
-    h = shost(rt.lsm_scan_merge_device(m["dev"], [], fill=SENTINEL))
+    h = host(rt.lsm_scan_merge_device(m["dev"], [], fill=SENTINEL))
     assert not h["summary"].any() and not h["chain_summary"].any() and int(h["chain_start"][0]) == 0
     keys = [b"a", b"", b"k0002"]
     of_empty = G.Tree([[G.Leaf(G.EmptySst())], [G.Leaf(G.EmptySst()), G.Leaf(G.EmptySst())]])
-    for dev in (rt.lsm_tree_device([], []), TG.device_tree(rt, of_empty)):
-        h = ghost(rt.lsm_get_merge_device(dev, None, keys, max_seq=[5, 6, 7], cap_links=4, fill=SENTINEL))
+    for dev in (rt.lsm_tree_device([], []), device_tree(rt, of_empty)):
+        h = host(rt.lsm_get_merge_device(dev, None, keys, max_seq=[5, 6, 7], cap_links=4, fill=SENTINEL))
         assert not h["summary"].any() and not h["chain_summary"].any() and not h["chain_start"].any()
         assert not h["state"][:3].any() and not h["status"][:3].any()
         assert ((h["sst"][:3].astype(np.int64) & 0xFFFFFFFF) == _abi.NO_SST).all()
         assert (h["chain_seq"].view(np.uint8) == SENTINEL).all()
-        h = shost(rt.lsm_scan_merge_device(dev, [(None, U, None, U), (b"a", INC, b"b", INC)], fill=SENTINEL))
+        h = host(rt.lsm_scan_merge_device(dev, [(None, U, None, U), (b"a", INC, b"b", INC)], fill=SENTINEL))
         assert not h["summary"].any() and not h["chain_summary"].any() and not h["range_entry_start"].any()
 
 
@@ -510,15 +447,15 @@ def test_malformed_tree(rt, what):
         rs[2], rs[3] = 3, 2
         t = TG.with_arrays(rt, dev, run_start=rs)
     n = len(keys)
-    h = ghost(rt.lsm_get_merge_device(t, None, keys, cap_links=64, fill=SENTINEL))
+    h = host(rt.lsm_get_merge_device(t, None, keys, cap_links=64, fill=SENTINEL))
     assert (h["status"][:n] == _abi.SDB_INVALID_ARGUMENT).all() and not h["state"][:n].any()
     assert h["sum_num_failed"] == n and h["sum_blocks_checked"] == 0 and not h["chain_start"].any()
     assert h["csum_num_links"] == 0 and h["csum_status"] == 0 and (h["chain_seq"].view(np.uint8) == SENTINEL).all()
     rngs = [(None, U, None, U), (b"k0010", INC, b"k0020", INC)]
-    hs = shost(rt.lsm_scan_merge_device(t, rngs, cand=(4096, 1 << 16), cap=(4096, 1 << 16), cap_links=4096, fill=SENTINEL))
+    hs = host(rt.lsm_scan_merge_device(t, rngs, cand=(4096, 1 << 16), cap=(4096, 1 << 16), cap_links=4096, fill=SENTINEL))
     assert (hs["range_status"][:2] == _abi.SDB_INVALID_ARGUMENT).all() and hs["sum_num_entries"] == 0
     assert hs["csum_num_links"] == 0 and (hs["chain_seq"].view(np.uint8) == SENTINEL).all()
-    check_get(m["tree"], keys, None, ghost(rt.lsm_get_merge_device(dev, None, keys, fill=SENTINEL)))  # the tree still answers
+    check_get(m["tree"], keys, None, host(rt.lsm_get_merge_device(dev, None, keys, fill=SENTINEL)))  # the tree still answers
 
 
 def test_graph_capture_and_workspace_reuse(rt):
@@ -532,20 +469,19 @@ def test_graph_capture_and_workspace_reuse(rt):
 
     def tensors(ks, bs):
         kb, ko = rt.keys_columnar(ks)
-        return TG._dev(kb), TG._dev(ko), TG._dev(np.array(bs, np.uint64))
+        return to_dev(kb), to_dev(ko), to_dev(np.array(bs, np.uint64))
 
     kb, ko, ms = tensors(keys, bounds)
     kb2, ko2, ms2 = tensors(keys2, bounds2)
     n = len(keys)
     assert kb.numel() == kb2.numel()
-    ws = torch.empty(rt.lib().sdb_lsm_get_merge_workspace_bytes(dev["total_blocks"], dev["num_ssts"], dev["num_runs"], n),
-                     dtype=torch.uint8, device="cuda")
+    ws = torch.empty(rt.read_workspace_bytes("sdb_lsm_get_merge", dev, n), dtype=torch.uint8, device="cuda")
     call = lambda k, o, b, s=None: rt.lsm_get_merge_device(dev, None, (k, o, n), max_seq=b, stream=s, workspace=ws,  # noqa: E731
                                                            cap_links=cap, fill=SENTINEL)
     r1, r2, r3 = call(kb, ko, ms), call(kb2, ko2, ms2), call(kb, ko, None)  # one workspace, no reset in between
-    check_get(tree, keys, bounds, ghost(r1))
-    check_get(tree, keys2, bounds2, ghost(r2))
-    check_get(tree, keys, None, ghost(r3))
+    check_get(tree, keys, bounds, host(r1))
+    check_get(tree, keys2, bounds2, host(r2))
+    check_get(tree, keys, None, host(r3))
     first = (kb.clone(), ko.clone(), ms.clone())
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
@@ -564,22 +500,21 @@ def test_graph_capture_and_workspace_reuse(rt):
                 t.view(torch.uint8).fill_(SENTINEL) if k.startswith("chain_") and k[6:] in dict(rt.CHAIN_COLUMNS) else t.zero_()
         torch.cuda.synchronize()
         g.replay()
-        check_get(tree, ks, bs, ghost(holder["res"]))
+        check_get(tree, ks, bs, host(holder["res"]))
     del warm
     # the scan: captured with fixed capacities, replayed twice over ranges overwritten in place
     ra = [(b"k0010", INC, b"k0050", INC), (None, U, b"k0020", EXC), (M.CUT_KEY, INC, M.CUT_KEY, INC)]
     rb = [(b"k0060", INC, b"k0090", EXC), (None, U, b"k0006", INC), (b"k0100", INC, b"k0140", INC)]
-    cols = lambda rs: {k: TG._dev(a) for k, a in rt.scan_ranges_columnar(rs).items()}  # noqa: E731
+    cols = lambda rs: {k: to_dev(a) for k, a in rt.scan_ranges_columnar(rs).items()}  # noqa: E731
     ta, tb = cols(ra), cols(rb)
     assert all(ta[k].numel() == tb[k].numel() for k in ta)
     live = {k: v.clone() for k, v in ta.items()}
     live["n"] = 3
     cand, capr = (8192, 1 << 17), (2048, 1 << 15)
-    wss = torch.empty(rt.lib().sdb_lsm_scan_merge_workspace_bytes(dev["total_blocks"], dev["num_ssts"], dev["num_runs"], 3,
-                                                                  *cand), dtype=torch.uint8, device="cuda")
+    wss = torch.empty(rt.read_workspace_bytes("sdb_lsm_scan_merge", dev, 3, cand), dtype=torch.uint8, device="cuda")
     scall = lambda st=None: rt.lsm_scan_merge_device(dev, live, stream=st, workspace=wss, cand=cand, cap=capr,  # noqa: E731
                                                      cap_links=cap, fill=SENTINEL)
-    check_scan(tree, ra, None, False, shost(scall()))
+    check_scan(tree, ra, None, False, host(scall()))
     with torch.cuda.stream(s):
         warm = scall(s)
     s.synchronize()
@@ -594,5 +529,5 @@ def test_graph_capture_and_workspace_reuse(rt):
                 t.view(torch.uint8).fill_(SENTINEL) if k.startswith("chain_") and k[6:] in dict(rt.CHAIN_COLUMNS) else t.zero_()
         torch.cuda.synchronize()
         g2.replay()
-        check_scan(tree, rs, None, False, shost(holder["scan"]))
+        check_scan(tree, rs, None, False, host(holder["scan"]))
     del warm

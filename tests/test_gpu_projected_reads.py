@@ -20,19 +20,13 @@ from . import test_gpu_filtered_reads as FR
 from . import test_gpu_get as TG
 from . import test_gpu_lsm_scan as LS
 from . import test_gpu_merge_reads as TM
+from .read_harness import Guard, device_tree, host, rt, to_dev, totals, view_of  # noqa: F401
 from .scan_cases import EXC, INC, U, partitions_covering_range
 
 pytestmark = pytest.mark.gpu
 
 ALL = (None, U, None, U)
 BAD = _abi.SDB_INVALID_ARGUMENT
-
-
-@pytest.fixture(scope="module")
-def rt():
-    from slatedb_amd import runtime
-    runtime.require_device()
-    return runtime
 
 
 _trees = {}
@@ -44,7 +38,7 @@ def fixture(rt, name, build=None):
     if name not in _trees:
         made = build() if build else getattr(F, name)()
         tree = made[0] if isinstance(made, tuple) else made
-        _trees[name] = dict(tree=tree, made=made, dev=FR.device_tree(rt, tree))
+        _trees[name] = dict(tree=tree, made=made, dev=device_tree(rt, tree))
     return _trees[name]
 
 
@@ -63,7 +57,7 @@ def call(rt, dev, vis, cases, bounds=None, desc=False, **kw):
 
 def scan_and_check(rt, m, vis, cases, bounds=None, desc=False):
     exp = model(m["tree"], vis, cases, bounds, desc)
-    h = FR.host(call(rt, m["dev"], vis, cases, bounds, desc))
+    h = host(call(rt, m["dev"], vis, cases, bounds, desc))
     FR.check(m["tree"], cases, bounds, desc, h, exp)
     return exp, h
 
@@ -71,7 +65,7 @@ def scan_and_check(rt, m, vis, cases, bounds=None, desc=False):
 def get_and_check(rt, m, vis, keys, bounds=None):
     """Every column of the gets against projected_read_cases.Tree (probe_len NULL on both sides)."""
     pt = P.projected(m["tree"], vis)
-    h = TG.host(rt.lsm_get_projected_device(m["dev"], None, vis, keys, max_seq=bounds))
+    h = host(rt.lsm_get_projected_device(m["dev"], None, vis, keys, max_seq=bounds))
     got = TG.check(pt, keys, bounds, h)
     TG.check_blocks_checked(pt, keys, got, h)
     return got, h
@@ -115,7 +109,7 @@ def test_sweep_without_policies(rt):
     """get_cases.main_tree, policies NULL (the plain whole-key filters of sdb_lsm_get): an SST without blocks, two
     runs of three, one cut inside a key's versions, merge operands."""
     tree, straddler = G.main_tree()
-    m = dict(tree=tree, dev=TG.device_tree(rt, tree))
+    m = dict(tree=tree, dev=device_tree(rt, tree))
     assert m["dev"]["_policies"] is None and sum(l.bloom is not None for l in tree.leaves) >= 6
     keys = G.main_queries(tree, straddler)[::2] + [straddler]
     cases = plain_cases(L.ranges(tree, straddler)[:80])
@@ -126,7 +120,7 @@ def test_sweep_without_policies(rt):
         pm = dict(tree=P.projected(tree, vis), dev=m["dev"])
         scan_and_check(rt, pm, vis, cases)
         res = rt.lsm_get_projected_device(m["dev"], None, vis, keys, merge=True, fill=TM.SENTINEL)
-        TM.check_get(P.merge_view(pm["tree"], vis), keys, None, TM.ghost(res))
+        TM.check_get(P.merge_view(pm["tree"], vis), keys, None, host(res))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -197,7 +191,7 @@ def test_key_gap_run(rt):
     g = P.golden()["key_gap"]
     for c in g["cases"]:
         tree, vis = P.key_gap_run(c)
-        m = dict(tree=tree, dev=FR.device_tree(rt, tree))
+        m = dict(tree=tree, dev=device_tree(rt, tree))
         keys = [b"a", b"b", b"c", b"d", b"e", b"f", b"g", b"m", b"n", b"p", b"q", b""]
         got, h = get_and_check(rt, m, vis, keys)
         exp, hs = scan_and_check(rt, m, vis, plain_cases([ALL, (b"a", INC, b"z", INC), (b"e", INC, b"g", EXC), (b"c", INC, b"m", INC)]))
@@ -226,7 +220,7 @@ def test_hidden_newer_versions(rt):
     got, h = get_and_check(rt, m, vis, keys)
     assert (got[0].state, got[0].sst, got[0].ssts_read) == (_abi.GET_FOUND, 1, 1) and P.row_value(tree, 1, got[0].row)[3] == b"old"
     assert got[1].status == _abi.SDB_MERGE_OPERATOR_MISSING and got[1].sst == 1
-    free = TG.host(rt.lsm_get_filtered_device(m["dev"], None, keys))
+    free = host(rt.lsm_get_filtered_device(m["dev"], None, keys))
     assert int(free["sst"][0]) == 0 and int(free["sst"][1]) == 0  # unprojected, the newer SST answers both
     rngs = [(None, U, P.K2, EXC), (P.K1, INC, P.K1, INC), ALL, (b"x020", INC, b"x045", INC), (P.K2, INC, None, U)]
     for desc in (False, True):
@@ -235,12 +229,12 @@ def test_hidden_newer_versions(rt):
     # the merging get: every column and link against merge_read_cases.get_merge over leaves that cover what E holds
     view = P.merge_view(tree, vis)
     res = rt.lsm_get_projected_device(m["dev"], None, vis, keys, merge=True, fill=TM.SENTINEL)
-    mg = TM.check_get(view, keys, None, TM.ghost(res))
+    mg = TM.check_get(view, keys, None, host(res))
     assert [i for i, _, _ in mg[1].links] == [1, 1, 1] and mg[1].base and mg[1].ssts_read == 1 and mg[0].ssts_read == 1
     # the merging scan: rows and links against merge_read_cases.scan_merge over the trimmed SSTs
     cut = P.trimmed(tree, vis)
     for desc in (False, True):
-        hs = TM.shost(rt.lsm_scan_projected_device(m["dev"], vis, rngs, merge=True, descending=desc))
+        hs = host(rt.lsm_scan_projected_device(m["dev"], vis, rngs, merge=True, descending=desc))
         exp = [M.scan_merge(cut, r, None, desc) for r in rngs]
         rows = [r for e in exp for r in e.rows]
         assert hs["sum_status"] == 0 and hs["csum_status"] == 0 and hs["sum_num_entries"] == len(rows)
@@ -272,10 +266,10 @@ def error_tree(rt, tree, bad_block):
     l0 = tree.leaves[0]
     data = l0.sst.data.copy()
     data[int(l0.sst.block_off[bad_block]) + 5] ^= 0x40
-    views = [FR.view_of(l) for l in tree.leaves]
-    views[0] = FR.view_of(l0, data=data)
+    views = [view_of(l) for l in tree.leaves]
+    views[0] = view_of(l0, data=data)
     views[1]["sst_version"] = 3
-    return null_arrays(rt, FR.device_tree(rt, tree, views), 2)
+    return null_arrays(rt, device_tree(rt, tree, views), 2)
 
 
 def test_errors_no_view_reaches_never_surface(rt):
@@ -308,7 +302,7 @@ def test_errors_no_view_reaches_never_surface(rt):
     got, h = get_and_check(rt, mb, vis, keys)
     assert {g.status for g in got} == {0, _abi.SDB_INVALID_VERSION, _abi.SDB_CHECKSUM_MISMATCH}
     # a NULL array that a view reaches: SDB_INVALID_ARGUMENT at that SST's place
-    h = FR.host(call(rt, dev, [(None, U, b"a", EXC), (b"zz", INC, None, U), None], plain_cases([ALL, (b"a", INC, b"b", INC)])))
+    h = host(call(rt, dev, [(None, U, b"a", EXC), (b"zz", INC, None, U), None], plain_cases([ALL, (b"a", INC, b"b", INC)])))
     assert list(h["range_status"][:2]) == [BAD, 0] and list(h["range_ssts"][:2]) == [1, 0]
 
 
@@ -321,7 +315,7 @@ def test_malformed_projection(rt, what):
     m = fixture(rt, "main_tree")
     tree, dev = m["tree"], m["dev"]
     vis = P.random_projections(tree, P.SWEEP_SEEDS[1])
-    good = {k: TG._dev(a) for k, a in rt.projections_columnar(vis).items()}
+    good = {k: to_dev(a) for k, a in rt.projections_columnar(vis).items()}
     good["n"] = len(vis)
     assert int(good["start_kind"][3]) == INC and int(good["start_off"][4]) > 0 and int(good["end_off"][4]) > 0
     bad = {k: (v.clone() if hasattr(v, "clone") else v) for k, v in good.items()}
@@ -336,26 +330,24 @@ def test_malformed_projection(rt, what):
     cases = sweep_cases(tree)[:70]
     n = len(cases)
     exp = model(tree, vis, cases)
-    cand = FR.totals(exp)[0]
-    ws = torch.empty(rt.lib().sdb_lsm_scan_projected_workspace_bytes(dev["total_blocks"], dev["num_ssts"], dev["num_runs"], n, *cand, 0),
-                     dtype=torch.uint8, device="cuda")
+    cand = totals(exp)[0]
+    ws = torch.empty(rt.read_workspace_bytes("sdb_lsm_scan_projected", dev, n, cand), dtype=torch.uint8, device="cuda")
     kw = dict(workspace=ws, cand=cand, cap=cand)
     r1 = call(rt, dev, bad, cases, **kw)  # back to back on one workspace, no reset between them
     r2 = call(rt, dev, good, cases, **kw)
-    h = FR.host(r1)
+    h = host(r1)
     assert (h["range_status"][:n] == BAD).all() and h["sum_blocks_checked"] == 0 and h["sum_num_failed_ranges"] == n
     assert h["sum_num_entries"] == 0 and h["sum_num_candidates"] == 0 and h["sum_num_filtered"] == 0 and h["sum_status"] == BAD
     assert not h["range_ssts"][:n].any() and not h["range_entry_start"][:n + 1].any()
-    FR.check(tree, cases, None, False, FR.host(r2), exp)
+    FR.check(tree, cases, None, False, host(r2), exp)
     keys = F.get_keys(tree)[::9]
-    wsg = torch.empty(rt.lib().sdb_lsm_get_projected_workspace_bytes(dev["total_blocks"], dev["num_ssts"], dev["num_runs"], len(keys), 0),
-                      dtype=torch.uint8, device="cuda")
+    wsg = torch.empty(rt.read_workspace_bytes("sdb_lsm_get_projected", dev, len(keys)), dtype=torch.uint8, device="cuda")
     g1 = rt.lsm_get_projected_device(dev, None, bad, keys, workspace=wsg)
     g2 = rt.lsm_get_projected_device(dev, None, good, keys, workspace=wsg)
-    h = TG.host(g1)
+    h = host(g1)
     assert (h["status"][:len(keys)] == BAD).all() and not h["state"][:len(keys)].any() and h["sum_blocks_checked"] == 0
     assert h["sum_num_failed"] == len(keys) and not h["ssts_read"][:len(keys)].any()
-    TG.check(P.projected(tree, vis), keys, None, TG.host(g2))
+    TG.check(P.projected(tree, vis), keys, None, host(g2))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -396,84 +388,39 @@ def test_null_and_open_projections_equal_the_filtered_calls(rt, name):
 # ------------------------------------------------------------------------------------------------
 # Capacity and canaries
 # ------------------------------------------------------------------------------------------------
-def raw_scan(rt, dev, vis, cases, cand, cap, guard):
-    """One sdb_lsm_scan_projected call with the given capacities; the workspace, of exactly the advertised size, and
-    every output array come from `guard`."""
-    import torch
-    n = len(cases)
-    new = guard.alloc
-    dv = lambda d: {k: TG._dev(a) for k, a in d.items()}  # noqa: E731
-    rg, pj = dv(rt.scan_ranges_columnar([c[0] for c in cases])), dv(rt.projections_columnar(vis))
-    px = dv(rt.scan_prefixes_columnar([c[1] for c in cases], [c[2] for c in cases]))
-    res = {"range_entry_start": new(n + 1, torch.int64), "range_status": new(n, torch.int32), "range_ssts": new(n, torch.int32),
-           "key_arena": new(cap[1], torch.uint8), "key_off": new(cap[0] + 1, torch.int64),
-           "summary": new(len(rt.LSM_SCAN_SUMMARY), torch.int64), "range_filtered": new(n, torch.int32),
-           "num_filtered": new(1, torch.int64)}
-    for f, dt in rt.LSM_SCAN_COLUMNS:
-        res[f] = new(cap[0], getattr(torch, dt))
-    out = _abi.LsmScanOut(res["range_entry_start"].data_ptr(), res["range_status"].data_ptr(), res["range_ssts"].data_ptr(),
-                          res["key_arena"].data_ptr(), cap[1], res["key_off"].data_ptr(),
-                          *[res[f].data_ptr() for f, _ in rt.LSM_SCAN_COLUMNS], cap[0], res["summary"].data_ptr())
-    as_ranges = lambda k, d: _abi.ScanRanges(k, *[d[s + f].data_ptr() for s in ("start", "end") for f in ("_bytes", "_off", "_kind")])  # noqa: E731
-    ranges, proj = as_ranges(n, rg), as_ranges(len(vis), pj)
-    prefixes = _abi.ScanPrefixes(px["prefix_bytes"].data_ptr(), px["prefix_off"].data_ptr(), px["has_prefix"].data_ptr(),
-                                 px["probe_len"].data_ptr())
-    fout = _abi.ScanFilterOut(res["range_filtered"].data_ptr(), res["num_filtered"].data_ptr())
-    wsb = rt.lib().sdb_lsm_scan_projected_workspace_bytes(dev["total_blocks"], dev["num_ssts"], dev["num_runs"], n, *cand, 0)
-    ws = guard.alloc(wsb, torch.uint8, lead=257)
-    st = rt.lib().sdb_lsm_scan_projected(C.byref(dev["lsm"]), C.byref(proj), dev["_policies"].data_ptr(), C.byref(ranges),
-                                         C.byref(prefixes), None, 0, cand[0], cand[1], C.byref(out), None, C.byref(fout),
-                                         ws.data_ptr(), wsb, None)
-    res["_keep"] = (rg, pj, px, ws)
-    return st, res
-
-
 def test_scan_capacity_and_canaries(rt):
     m = fixture(rt, "main_tree")
     tree = m["tree"]
     cases = sweep_cases(tree)
     vis = P.random_projections(tree, P.SWEEP_SEEDS[1])
     exp = model(tree, vis, cases)
-    cand, cap = FR.totals(exp)
-    free = FR.totals([F.scan(tree, r, p, pl) for r, p, pl in cases])[0]
+    cand, cap = totals(exp)
+    free = totals([F.scan(tree, r, p, pl) for r, p, pl in cases])[0]
     assert cand[0] < free[0] - 100  # the candidates fit only because of the projections
-    guard = FR.Guard()
-    st, res = raw_scan(rt, m["dev"], vis, cases, cand, cap, guard)
-    assert st == 0
+    guard = Guard()  # the workspace, of exactly the advertised size, and every output array come from it
+    res = call(rt, m["dev"], vis, cases, cand=cand, cap=cap, alloc=guard)
     guard.check()
-    FR.check(tree, cases, None, False, FR.host(res), exp)
-    guard = FR.Guard()
-    st, res = raw_scan(rt, m["dev"], vis, cases, (cand[0] - 1, cand[1]), cap, guard)
+    FR.check(tree, cases, None, False, host(res), exp)
+    guard = Guard()
+    res = call(rt, m["dev"], vis, cases, cand=(cand[0] - 1, cand[1]), cap=cap, alloc=guard)
     guard.check()
-    h = FR.host(res)
-    assert st == 0 and h["sum_status"] == _abi.SDB_LIMIT_EXCEEDED and h["sum_num_entries"] == 0
+    h = host(res)
+    assert h["sum_status"] == _abi.SDB_LIMIT_EXCEEDED and h["sum_num_entries"] == 0
     assert (h["sum_num_candidates"], h["sum_candidate_key_bytes"]) == cand  # the model's totals
     LS.check_ranges(exp, h)
     assert (h["range_filtered"][:len(exp)] == np.array([len(e.filtered) for e in exp])).all()
-    st, res = raw_scan(rt, m["dev"], [None] * len(vis), cases, cand, cap, FR.Guard())  # unprojected they do not fit
-    h = FR.host(res)
-    assert st == 0 and h["sum_status"] == _abi.SDB_LIMIT_EXCEEDED and (h["sum_num_candidates"], h["sum_candidate_key_bytes"]) == free
+    h = host(call(rt, m["dev"], [None] * len(vis), cases, cand=cand, cap=cap, alloc=Guard()))  # unprojected they do not fit
+    assert h["sum_status"] == _abi.SDB_LIMIT_EXCEEDED and (h["sum_num_candidates"], h["sum_candidate_key_bytes"]) == free
 
 
 def test_get_canaries(rt):
-    import torch
     m = fixture(rt, "main_tree")
     tree, dev = m["tree"], m["dev"]
     keys = F.get_keys(tree)[::3]
     vis = P.random_projections(tree, P.SWEEP_SEEDS[2])
-    n = len(keys)
-    guard = FR.Guard()
-    kb, ko = (TG._dev(a) for a in rt.keys_columnar(keys))
-    pj = {k: TG._dev(a) for k, a in rt.projections_columnar(vis).items()}
-    proj = _abi.ScanRanges(len(vis), *[pj[s + f].data_ptr() for s in ("start", "end") for f in ("_bytes", "_off", "_kind")])
-    res = {f: guard.alloc(n, getattr(torch, dt)) for f, dt in rt.GET_FIELDS}
-    res["summary"] = guard.alloc(len(rt.GET_SUMMARY), torch.int64)
-    out = _abi.GetOut(*[res[f].data_ptr() for f, _ in rt.GET_FIELDS], res["summary"].data_ptr())
-    wsb = rt.lib().sdb_lsm_get_projected_workspace_bytes(dev["total_blocks"], dev["num_ssts"], dev["num_runs"], n, 0)
-    ws = guard.alloc(wsb, torch.uint8, lead=257)
-    for _ in range(2):  # twice in one workspace, no reset
-        st = rt.lib().sdb_lsm_get_projected(C.byref(dev["lsm"]), C.byref(proj), dev["_policies"].data_ptr(), kb.data_ptr(),
-                                            ko.data_ptr(), n, None, None, C.byref(out), None, ws.data_ptr(), wsb, None)
-        assert st == 0
+    guard = Guard()
+    first = rt.lsm_get_projected_device(dev, None, vis, keys, alloc=guard)
+    # twice in one workspace and the same arrays, no reset
+    res = rt.lsm_get_projected_device(dev, None, vis, keys, workspace=first["_ws"], alloc=lambda name, *_: first[name])
     guard.check()
-    TG.check(P.projected(tree, vis), keys, None, TG.host(res))
+    TG.check(P.projected(tree, vis), keys, None, host(res))

@@ -2,8 +2,6 @@
 against the model of tests/recency_cases.py: every column of every row, every range_* array and every summary word.
 The trees are tiny: at most 3 tables of at most 8 rows, at most 5 SSTs of at most 4 blocks of 64 bytes, at most 16
 ranges per call."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -15,9 +13,10 @@ from . import malformed_blocks as MB
 from . import mem_get_cases as MG
 from . import mem_scan_cases as S
 from . import recency_cases as RC
-from . import test_gpu_filtered_reads as FR
 from . import test_gpu_get as TG
 from . import test_gpu_mem_scan as MS
+from .read_harness import (Filled, canaried_workspace, check_scan_core, compare, dev_tables, host, intact, rt, to_dev,  # noqa: F401
+                           totals, untouched, view_of)
 from .scan_cases import EXC, INC, U
 
 pytestmark = pytest.mark.gpu
@@ -28,13 +27,6 @@ BS = 64  # the smallest block size of the encoder fixtures
 PX = b"px:"
 ALL = RC.prefix_range(PX)
 BAD = _abi.SDB_CHECKSUM_MISMATCH
-
-
-@pytest.fixture(scope="module")
-def rt():
-    from slatedb_amd import runtime
-    runtime.require_device()
-    return runtime
 
 
 def v(key, val, seq, kind=0, ets=None):
@@ -50,8 +42,6 @@ class Layers:
         leaves = self.mt.tree.leaves
         assert len(tables) <= 3 and all(len(t.rows) <= 8 for t in tables) and len(leaves) <= 5
         assert all(l.sst.nb <= 4 for l in leaves)
-        filtered = any(hasattr(l, "policy") for l in leaves)
-        view_of = FR.view_of if filtered else TG.view_of
         views = views or [view_of(l) for l in leaves]
         for i, b in corrupt:
             data = leaves[i].sst.data.copy()
@@ -59,7 +49,7 @@ class Layers:
             views[i] = view_of(leaves[i], data=data)
             leaves[i].block_status[b] = BAD
         self.dev = rt.lsm_tree_device(views, [len(r) for r in runs])
-        self.mem = MS.dev_tables(rt, tables) if tables else None
+        self.mem = dev_tables(rt, tables) if tables else None
 
 
 def case(rng=ALL, prefix=PX, bound=None, limit=0):
@@ -72,7 +62,7 @@ def call(rt, x, cases, desc=False, visible=None, **kw):
     limits = None if all(not c["limit"] for c in cases) else [c["limit"] for c in cases]
     res = rt.lsm_scan_recency_device(x.mem, x.dev, [c["rng"] for c in cases], projections=visible,
                                      prefixes=[c["prefix"] for c in cases] or None, max_seq=bounds, limit=limits, descending=desc, **kw)
-    return MS.host(res)
+    return host(res)
 
 
 def model(x, cases, desc=False, visible=None, fits=True):
@@ -91,22 +81,14 @@ def check_ranges(exp, h):
     assert h["sum_num_failed_ranges"] == len(failed)
     assert h["sum_num_candidates"] == sum(e.candidates for e in exp)
     assert h["sum_candidate_key_bytes"] == sum(e.cand_key_bytes for e in exp)
-    return failed
 
 
 def check(x, cases, desc, h, visible=None, exp=None):
     """Every column of every row, every range array, every summary word.  Returns the model's results."""
     exp = exp or model(x, cases, desc, visible)
-    failed = check_ranges(exp, h)
-    rows = [r for e in exp for r in e.rows]
-    starts = np.concatenate([[0], np.cumsum([len(e.rows) for e in exp])]).astype(np.int64)
-    assert h["range_entry_start"][:len(exp) + 1].astype(np.int64).tolist() == starts.tolist()
-    assert h["sum_num_entries"] == len(rows) and h["sum_key_bytes"] == sum(len(r[0]) for r in rows)
-    assert h["sum_status"] == (exp[failed[0]].status if failed else 0)
-    ko = h["key_off"][:len(rows) + 1].astype(np.int64)
-    assert ko.tolist() == np.concatenate([[0], np.cumsum([len(r[0]) for r in rows])]).astype(np.int64).tolist()
-    assert h["key_arena"][:int(ko[-1])].tobytes() == b"".join(r[0] for r in rows)
-    MS._compare(MS.ROW_COLS, [RC.columns(x.mt, r) for r in rows], lambda f: h[f], "row")
+    check_ranges(exp, h)
+    rows = check_scan_core(exp, h)
+    compare(MS.ROW_COLS, [RC.columns(x.mt, r) for r in rows], lambda f: h[f], "row")
     return exp
 
 
@@ -196,7 +178,7 @@ def test_v2_block_without_restarts_descending(rt):
     payloads[-1] = L.build(offs=[], count=0)
     assert MB.walk(payloads[-1], 2)[0] == 0
     data, block_off = MB.arena(payloads)
-    x = Layers(rt, [], [[leaf]], views=[TG.view_of(leaf, data=data, block_off=block_off)])
+    x = Layers(rt, [], [[leaf]], views=[view_of(leaf, data=data, block_off=block_off)])
     for desc in (False, True):
         cases = [case(), case(limit=2)]
         exp = check(x, cases, desc, call(rt, x, cases, desc))
@@ -271,10 +253,10 @@ def test_laziness_of_errors(rt):
     # limit 0: the first failing source in walk order decides; the other ranges of the call are unaffected
     x = lazy_layers(rt, [(3, 0)])
     x.mt.tree.leaves[1].version = 3  # and an invalid version in the run before it
-    views = [TG.view_of(l) for l in x.mt.tree.leaves]
+    views = [view_of(l) for l in x.mt.tree.leaves]
     data = x.mt.tree.leaves[3].sst.data.copy()
     data[int(x.mt.tree.leaves[3].sst.block_off[0]) + 5] ^= 0x40
-    views[3] = TG.view_of(x.mt.tree.leaves[3], data=data)
+    views[3] = view_of(x.mt.tree.leaves[3], data=data)
     x.dev = rt.lsm_tree_device(views, [1, 2, 1])
     cases = [case(), case(limit=6), case(limit=7), case(RC.prefix_range(b"px:e"), b"px:e"), case(RC.prefix_range(b"px:c"), b"px:c")]
     exp = check(x, cases, False, call(rt, x, cases))
@@ -311,42 +293,12 @@ def test_projected_view_cuts_a_key_group(rt, desc):
 # ------------------------------------------------------------------------------------------------
 # R6: capacity
 # ------------------------------------------------------------------------------------------------
-def raw_call(rt, x, cases, cand, cap, desc=False, ws=None, fill=SENTINEL):
-    """One sdb_lsm_scan_recency call over outputs pre-filled with `fill` -> (status, dict of device tensors)."""
-    import torch
-    n = len(cases)
-    rg = {k: TG._dev(a) for k, a in rt.scan_ranges_columnar([c["rng"] for c in cases]).items()}
-    ranges = _abi.ScanRanges(n, rg["start_bytes"].data_ptr(), rg["start_off"].data_ptr(), rg["start_kind"].data_ptr(),
-                             rg["end_bytes"].data_ptr(), rg["end_off"].data_ptr(), rg["end_kind"].data_ptr())
-    px = {k: TG._dev(a) for k, a in rt.scan_prefixes_columnar([c["prefix"] for c in cases]).items() if a is not None}
-    prefixes = _abi.ScanPrefixes(px["prefix_bytes"].data_ptr(), px["prefix_off"].data_ptr(), px["has_prefix"].data_ptr(), None)
-    limit = TG._dev(np.array([c["limit"] for c in cases], np.uint64))
-    full = lambda count, dt: torch.full((max(count, 1),), fill, dtype=torch.uint8, device="cuda").repeat(  # noqa: E731
-        np.dtype(dt).itemsize).view(getattr(torch, dt))
-    res = {"range_entry_start": full(n + 1, "int64"), "range_status": full(n, "int32"), "range_ssts": full(n, "int32"),
-           "range_tables": full(n, "int32"), "range_filtered": full(n, "int32"), "num_filtered": full(1, "int64"),
-           "range_sources_read": full(n, "int32"), "range_visible": full(n, "int64"),
-           "key_arena": full(cap[1] + 64, "uint8"), "key_off": full(cap[0] + 1, "int64"), "summary": full(7, "int64"),
-           "table": full(cap[0] + 8, "int32"), "row": full(cap[0] + 8, "int64")}
-    for f, dt in rt.LSM_SCAN_COLUMNS:
-        res[f] = full(cap[0] + 8, dt)
-    out = _abi.LsmScanOut(res["range_entry_start"].data_ptr(), res["range_status"].data_ptr(), res["range_ssts"].data_ptr(),
-                          res["key_arena"].data_ptr(), cap[1], res["key_off"].data_ptr(),
-                          *[res[f].data_ptr() for f, _ in rt.LSM_SCAN_COLUMNS], cap[0], res["summary"].data_ptr())
-    mout = _abi.MemScanOut(res["table"].data_ptr(), res["row"].data_ptr(), res["range_tables"].data_ptr())
-    fout = _abi.ScanFilterOut(res["range_filtered"].data_ptr(), res["num_filtered"].data_ptr())
-    rout = _abi.RecencyOut(res["range_sources_read"].data_ptr(), res["range_visible"].data_ptr())
-    dev, mem = x.dev, x.mem
-    wsb = rt.lib().sdb_lsm_scan_recency_workspace_bytes(mem["num_tables"] if mem else 0, dev["total_blocks"], dev["num_ssts"],
-                                                        dev["num_runs"], n, cand[0], cand[1])
-    if ws is None:
-        ws = torch.empty(wsb, dtype=torch.uint8, device="cuda")
-    assert ws.numel() == wsb
-    st = rt.lib().sdb_lsm_scan_recency(C.byref(mem["mem"]) if mem else None, C.byref(dev["lsm"]), None, None, C.byref(ranges),
-                                       C.byref(prefixes), None, limit.data_ptr(), int(desc), cand[0], cand[1], C.byref(out),
-                                       C.byref(mout), C.byref(fout), C.byref(rout), ws.data_ptr(), wsb, None)
-    res["_keep"] = (rg, px, limit, ws)
-    return st, res
+def one_call(rt, x, cases, cand, cap, desc=False, ws=None):
+    """One sdb_lsm_scan_recency call with the given capacities, without policies and projections, over outputs
+    pre-filled with SENTINEL -> host(result)."""
+    return host(rt.lsm_scan_recency_device(x.mem, dict(x.dev, _policies=None), [c["rng"] for c in cases],
+                                           prefixes=[c["prefix"] for c in cases], limit=[c["limit"] for c in cases], descending=desc,
+                                           workspace=ws, cand=cand, cap=cap, alloc=Filled(SENTINEL)))
 
 
 def test_capacity(rt):
@@ -359,22 +311,18 @@ def test_capacity(rt):
     assert 0 < ne < nc and exp[0].status == BAD and exp[1].status == 0 and short[1].status == BAD
     columns = ["key_arena", "key_off", "table", "row"] + [f for f, _ in rt.LSM_SCAN_COLUMNS]
     for less in ((nc - 1, ckb), (nc, ckb - 1), (0, 0)):  # the staging one candidate / one key byte short, and none
-        st, res = raw_call(rt, x, cases, less, (ne, kb))
-        h = MS.host(res)
-        assert st == 0 and h["sum_status"] == _abi.SDB_LIMIT_EXCEEDED
-        assert h["sum_num_entries"] == 0 and h["sum_key_bytes"] == 0 and MS.untouched(h, columns)
+        h = one_call(rt, x, cases, less, (ne, kb))
+        assert h["sum_status"] == _abi.SDB_LIMIT_EXCEEDED
+        assert h["sum_num_entries"] == 0 and h["sum_key_bytes"] == 0 and untouched(h, columns, SENTINEL)
         assert not h["range_entry_start"][:len(cases) + 1].any()
         check_ranges(short, h)  # R6: the statuses of limit 0, nothing read
     for less in ((ne - 1, kb), (ne, kb - 1), (0, 0)):  # exact staging, the columns one entry / one key byte short
-        st, res = raw_call(rt, x, cases, (nc, ckb), less)
-        h = MS.host(res)
-        assert st == 0 and h["sum_status"] == _abi.SDB_LIMIT_EXCEEDED
-        assert (h["sum_num_entries"], h["sum_key_bytes"]) == (ne, kb) and MS.untouched(h, columns)
+        h = one_call(rt, x, cases, (nc, ckb), less)
+        assert h["sum_status"] == _abi.SDB_LIMIT_EXCEEDED
+        assert (h["sum_num_entries"], h["sum_key_bytes"]) == (ne, kb) and untouched(h, columns, SENTINEL)
         assert h["range_entry_start"][:len(cases) + 1].tolist() == np.concatenate([[0], np.cumsum([len(e.rows) for e in exp])]).tolist()
         check_ranges(exp, h)
-    st, res = raw_call(rt, x, cases, (nc, ckb), (ne, kb))  # exact capacities: every row, nothing past them
-    h = MS.host(res)
-    assert st == 0
+    h = one_call(rt, x, cases, (nc, ckb), (ne, kb))  # exact capacities: every row, nothing past them
     check(x, cases, False, h, exp=exp)
     assert (h["key_arena"][kb:] == SENTINEL).all()
     for f in columns[2:]:
@@ -421,8 +369,8 @@ def test_malformed_table_and_tree(rt):
     rs = x.dev["_run_start"].clone()
     rs[1], rs[2] = 3, 1  # not monotone
     for mem, dev in ((rt.mem_tables_device(broken), x.dev), (x.mem, TG.with_arrays(rt, x.dev, run_start=rs))):
-        h = MS.host(rt.lsm_scan_recency_device(mem, dev, [c["rng"] for c in cases], prefixes=[c["prefix"] for c in cases],
-                                               limit=[c["limit"] for c in cases]))
+        h = host(rt.lsm_scan_recency_device(mem, dev, [c["rng"] for c in cases], prefixes=[c["prefix"] for c in cases],
+                                            limit=[c["limit"] for c in cases]))
         assert (h["range_status"][:n] == _abi.SDB_INVALID_ARGUMENT).all()
         assert not h["range_ssts"][:n].any() and not h["range_tables"][:n].any() and not h["range_entry_start"].any()
         assert not h["range_sources_read"][:n].any() and not h["range_visible"][:n].any()
@@ -446,7 +394,7 @@ def test_first_occurrence_per_key_is_the_mem_scan(rt, seed):
     cases = [case(r, None) for r in rngs]
     h = call(rt, x, cases)
     check(x, cases, False, h)
-    g = MS.host(rt.lsm_scan_mem_device(x.mem, x.dev, rngs))
+    g = host(rt.lsm_scan_mem_device(x.mem, x.dev, rngs))
     assert g["sum_status"] == 0 and h["sum_num_candidates"] == g["sum_num_candidates"]
     for q in range(len(rngs)):
         first = {}
@@ -481,21 +429,19 @@ def test_graph_capture_tables_changed_in_place(rt):
     other = [rt.DeviceRun.from_host(t.run) for t in mts[1].tables]
     mem = rt.mem_tables_device(druns)
     cand = (max(sum(e.candidates for e in ex) for ex in exps), max(sum(e.cand_key_bytes for e in ex) for ex in exps))
-    rg = {k: TG._dev(a) for k, a in rt.scan_ranges_columnar([c["rng"] for c in cases]).items()}
+    rg = {k: to_dev(a) for k, a in rt.scan_ranges_columnar([c["rng"] for c in cases]).items()}
     rg["n"] = n
-    px = {k: None if a is None else TG._dev(a) for k, a in rt.scan_prefixes_columnar([c["prefix"] for c in cases]).items()}
-    lim, bnd = TG._dev(np.array([c["limit"] for c in cases], np.uint64)), TG._dev(np.array(bounds, np.uint64))
-    lead, tail = 257, 512
-    wsb = rt.lib().sdb_lsm_scan_recency_workspace_bytes(1, x.dev["total_blocks"], x.dev["num_ssts"], x.dev["num_runs"], n, *cand)
-    big = torch.full((lead + wsb + tail,), 0x5A, dtype=torch.uint8, device="cuda")
-    kw = dict(prefixes=px, max_seq=bnd, limit=lim, workspace=big[lead:lead + wsb], cand=cand, cap=cand)
+    px = {k: None if a is None else to_dev(a) for k, a in rt.scan_prefixes_columnar([c["prefix"] for c in cases]).items()}
+    lim, bnd = to_dev(np.array([c["limit"] for c in cases], np.uint64)), to_dev(np.array(bounds, np.uint64))
+    big, ws = canaried_workspace(rt, "sdb_lsm_scan_recency", x.dev, n, cand, tables=mem, byte=0x5A)
+    kw = dict(prefixes=px, max_seq=bnd, limit=lim, workspace=ws, cand=cand, cap=cand)
     st = torch.cuda.Stream()
     st.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(st):  # the first launch (function attributes) outside the capture
         warm = rt.lsm_scan_recency_device(mem, x.dev, rg, stream=st, **kw)
     st.synchronize()
     x.mt = mts[0]
-    check(x, cases, False, MS.host(warm), exp=exps[0])
+    check(x, cases, False, host(warm), exp=exps[0])
     g = torch.cuda.CUDAGraph()
     holder = {}
     with torch.cuda.graph(g, stream=st):
@@ -512,23 +458,18 @@ def test_graph_capture_tables_changed_in_place(rt):
         torch.cuda.synchronize()
         g.replay()
         x.mt = mts[which]
-        check(x, cases, False, MS.host(holder["res"]), exp=exps[which])
-    assert bool((big[:lead] == 0x5A).all()) and bool((big[lead + wsb:] == 0x5A).all())  # exactly workspace_bytes, no more
+        check(x, cases, False, host(holder["res"]), exp=exps[which])
+    intact(big, ws.numel(), 0x5A)  # exactly workspace_bytes, no more
     del g
 
 
 @pytest.mark.parametrize("desc", [False, True])
 def test_workspace_canary(rt, desc):
     """A workspace of exactly the advertised size inside guard bands: the call writes nothing outside it."""
-    import torch
     x = group_layers(rt, 2)
     cases = [case(), case(limit=4), case(RC.prefix_range(b"px:k"), b"px:k")]
     exp = model(x, cases, desc)
-    nc, ckb = sum(e.candidates for e in exp), sum(e.cand_key_bytes for e in exp)
-    wsb = rt.lib().sdb_lsm_scan_recency_workspace_bytes(1, x.dev["total_blocks"], x.dev["num_ssts"], x.dev["num_runs"], len(cases), nc, ckb)
-    lead, tail = 257, 512
-    big = torch.full((lead + wsb + tail,), 0x5A, dtype=torch.uint8, device="cuda")
-    st, res = raw_call(rt, x, cases, (nc, ckb), (nc, ckb), desc, ws=big[lead:lead + wsb])
-    assert st == 0
-    check(x, cases, desc, MS.host(res), exp=exp)
-    assert bool((big[:lead] == 0x5A).all()) and bool((big[lead + wsb:] == 0x5A).all())
+    nc, ckb = totals(exp)[0]
+    big, ws = canaried_workspace(rt, "sdb_lsm_scan_recency", x.dev, len(cases), (nc, ckb), tables=x.mem, byte=0x5A)
+    check(x, cases, desc, one_call(rt, x, cases, (nc, ckb), (nc, ckb), desc, ws=ws), exp=exp)
+    intact(big, ws.numel(), 0x5A)
