@@ -90,6 +90,7 @@ typedef enum sdb_status {
     SDB_DECOMPRESSION_ERROR = 11,   /* SlateDBError::BlockDecompressionError (format/sst.rs:884-917) */
     SDB_INVALID_SEQUENCE_ORDER = 12,/* SlateDBError::InvalidSequenceOrder (merge_operator.rs:293-299) */
     SDB_MERGE_OPERATOR_ERROR = 13,  /* SlateDBError::MergeOperatorError: the user's operator failed */
+    SDB_COMPACTION_FILTER_ERROR = 14,/* CompactionFilterError::{FilterError, CompactionEndError} */
     SDB_DEVICE_ERROR = 100          /* no HIP device / launch failure */
 } sdb_status;
 
@@ -1234,6 +1235,110 @@ sdb_status sdb_compactor_run_ssts_ranged(sdb_compactor *c, const sdb_compaction_
                                          uint32_t *num_ssts);
 /* The input side of the last sdb_compactor_run_ssts_ranged job (zeros after any other). */
 sdb_status sdb_compactor_range_stats(const sdb_compactor *c, sdb_range_job_stats *stats);
+
+/* ---------------------------------------------------------------------------------------------
+ * Compaction filters and resumed jobs: the last two stages load_iterators builds (compactor_executor.rs:327-435),
+ * CompactionFilterIterator (compaction_filter.rs, compaction_filter_iterator.rs) and ResumingIterator
+ * (compactor_executor.rs:123-199, :333-338).  Order of a job: merge -> operator (or the required check) ->
+ * retention -> filter -> resume drain -> writer (cuts, encode).
+ *
+ * Filter rules (compaction_filter_iterator.rs:19-66), over the rows retention yields, in stream order; one filter
+ * instance per job, single-threaded:
+ *   F1. Keep: the row passes unchanged.
+ *   F2. Drop: the row vanishes; no tombstone is left.
+ *   F3. Modify(Tombstone): kind becomes Tombstone, the value is empty, expire_ts is cleared (ts_mask loses
+ *       SDB_TS_EXPIRE); create_ts, seq and key are kept.  This tombstone comes after retention, so filter_tombstone
+ *       (is_dest_last_run) does not remove it.
+ *   F4. Modify(Value(b)) / Modify(Merge(b)): kind becomes Value / Merge and the value becomes b (it may be empty, and
+ *       longer than the original).  Key, seq, create_ts and expire_ts are preserved: a tombstone turned into a Value
+ *       keeps its "no expire_ts".  A Merge written by a filter in a job without an operator is legal: the
+ *       required-operator check sits before retention.
+ *   F5. Errors: a filter error aborts the job.  on_compaction_end (`end`) runs once, after the last row of a job that
+ *       did not fail; a job with no rows still runs it; an error from it aborts the job too.
+ * Resume rules (ResumingIterator::new, :150-171; seek: retention_iterator.rs:279-283, merge_operator.rs:481-484,
+ * merge_iterator.rs:18-37, 211-233), with the cursor (K, S) = the last row the interrupted job wrote:
+ *   S1. seek(K) goes down to the inputs: only rows with key >= K are read.  Merge, operator and retention act per
+ *       key, so the rows produced for keys >= K are exactly those of the unresumed job.  Rows below K contribute
+ *       nothing: no summary counts, no filter calls, no errors from blocks that hold only such rows.
+ *   S2. The leading rows with key == K && seq >= S are then drained one next() at a time from the filter's output,
+ *       so the filter IS called for them.  The drain stops at the first surviving row with another key or with
+ *       seq < S: a literal prefix, not a set.
+ *   S3. The writer starts afresh at the first surviving row: the cuts count from there.
+ * Reading the cursor out of the last output SST (last_written_key_and_seq) stays with the caller: a descending
+ * sdb_sst_scan of one row yields it.
+ *
+ * The filter callback.  One call = rows [first, first + rows->n) of the retained stream, in HOST (pinned) memory, as
+ * an sdb_kv_batch whose arrays are already offset to `first` (key_off / val_off stay absolute into key_bytes /
+ * val_bytes).  rows->val_bytes == NULL unless want_values; val_off is always valid (lengths).  decision[] arrives
+ * preset to KEEP.  For VALUE / MERGE the callback sets new_val[i] / new_len[i]; the library copies the bytes before
+ * the next call.  Non-zero return: the job fails.
+ *   F6. Identity: with filter == NULL && resume == NULL the outputs, statuses, summary words and host
+ *       synchronisations are those of sdb_compactor_run[_merge] / sdb_compactor_run_ssts_ranged.
+ *   F7. Keep-all fast path: a filter that keeps every row uploads nothing and launches no apply kernel
+ *       (h2d_bytes == 0, applied == 0); the stream and every SST byte are those of the job without a filter.
+ *   F8. Batching and `end`: calls are ascending and contiguous, batch_rows rows each (the last may be shorter; a
+ *       stream of no rows gets no call); every retained row with key >= K is shown exactly once, the S2 rows
+ *       included.  `end` is called once, after the last call, only if no call failed and the job has not failed
+ *       earlier.
+ *   F9. Failures.  A non-zero return from `filter`: SDB_COMPACTION_FILTER_ERROR, first_error_entry = `first` of that
+ *       call, no SST valid, `end` not called.  A non-zero return from `end`: the same status, first_error_entry =
+ *       rows_in.  A decision byte above SDB_CF_MERGE, or new_val == NULL with new_len > 0 (VALUE / MERGE):
+ *       SDB_INVALID_ARGUMENT (first_error_entry = the row), found on the host before anything is uploaded; `end` is not
+ *       called.  A replacement longer than 0xFFFFFFFF bytes (value lengths are u32): SDB_LIMIT_EXCEEDED, found and
+ *       reported the same way.  filter->filter == NULL, resume->key == NULL with key_len > 0, or resume->key_len >
+ *       0xFFFFFFFF: SDB_INVALID_ARGUMENT from the call.  In the decoded-runs job a cursor does not change what a run
+ *       must carry: a run with n > 0 and a NULL key_arena, key_off, val_off, val_len, seq or flags is
+ *       SDB_INVALID_ARGUMENT before anything is launched, as without a cursor.
+ *   F10. Results: sdb_compactor_merged returns the final stream, after the filter and the drain (its key_off /
+ *       val_off need not start at 0: a drained prefix stays in the arenas; its bytes end at key_off[n] / val_off[n]).
+ *       summary.num_out / key_bytes / val_bytes / expired_* stay retention's.  sdb_compacted_sst.entry_start / _end
+ *       index the final stream.  Every row dropped or drained: *num_ssts == 0 and SDB_OK, like an empty merge.
+ * Host synchronisations, on top of the job's own (run: 3; ssts: R8's):
+ *   - a filter adds one: the pinned D2H of the stream's columns (kind, seq, create_ts, expire_ts, ts_mask, key_off,
+ *     val_off) and key bytes, and of the value bytes only when want_values; d2h_bytes counts exactly what was copied.
+ *     The host then knows the final row count and bytes exactly, so the apply step and the cuts add none;
+ *   - the ssts job sizes its merged stream from declared counts and learns n with its cut list; with a filter or a
+ *     cursor it reads the merged summary first and cuts an unpadded stream: one more;
+ *   - a cursor in the decoded-runs job adds one: the lower bound of K in every run (nruns words), so sdb_run.n and
+ *     the merge's grid stay host values.  In the ssts job Included(K) is a third operand of R1's intersection: every
+ *     V[i].start is tightened by it (such an input counts as clipped for R6), and it adds none;
+ *   - S2 is computed on the host when a filter gathered the columns; without a filter a one-workgroup kernel and an
+ *     8-byte readback compute it: one more (none when the stream is empty).
+ * No allocation in steady state: the handle's buffers grow, and one handle serves filtered, resumed and plain jobs
+ * in any order.
+ * ------------------------------------------------------------------------------------------- */
+enum { SDB_CF_KEEP = 0, SDB_CF_DROP = 1, SDB_CF_TOMBSTONE = 2, SDB_CF_VALUE = 3, SDB_CF_MERGE = 4 };
+typedef int32_t (*sdb_compaction_filter_fn)(void *ctx, const sdb_kv_batch *rows, uint64_t first,
+                                            uint8_t *decision, const uint8_t **new_val, uint64_t *new_len);
+typedef int32_t (*sdb_compaction_end_fn)(void *ctx);          /* on_compaction_end; may be NULL */
+typedef struct sdb_compaction_filter {
+    sdb_compaction_filter_fn filter; sdb_compaction_end_fn end; void *ctx;
+    uint64_t batch_rows;      /* rows per call; 0 = the whole stream in one call */
+    uint32_t want_values;     /* 0: value bytes are not copied to the host */
+    uint32_t pad;
+} sdb_compaction_filter;
+typedef struct sdb_resume_cursor { const uint8_t *key; uint64_t key_len; uint64_t seq; } sdb_resume_cursor; /* host */
+typedef struct sdb_filter_stats {
+    uint64_t rows_in;                  /* rows shown to the filter */
+    uint64_t kept, dropped, tombstoned, new_values, new_merges;   /* by the filter's decisions */
+    uint64_t calls, d2h_bytes, h2d_bytes;
+    uint64_t applied;                  /* 1 iff the apply kernels ran */
+    uint64_t resume_drained;           /* rows removed by S2 */
+} sdb_filter_stats;
+sdb_status sdb_compactor_run_filtered(sdb_compactor *c, const sdb_run *runs, uint32_t nruns,
+                                      const sdb_retention *retention, sdb_merge_batch_fn op /* NULL: no operator */,
+                                      void *op_ctx, const sdb_compaction_filter *filter /* or NULL */,
+                                      const sdb_resume_cursor *resume /* or NULL */, const sdb_sst_params *params,
+                                      uint64_t max_sst_size, void *stream, uint32_t *num_ssts);
+sdb_status sdb_compactor_run_ssts_filtered(sdb_compactor *c, const sdb_compaction_view *inputs, uint32_t ninputs,
+                                           const uint32_t *run_start, uint32_t nruns, uint16_t input_sst_version,
+                                           const sdb_scan_ranges *job_range, const sdb_scan_ranges *proj,
+                                           const sdb_retention *retention, sdb_merge_batch_fn op, void *ctx,
+                                           const sdb_compaction_filter *filter /* or NULL */,
+                                           const sdb_resume_cursor *resume /* or NULL */, const sdb_sst_params *params,
+                                           uint64_t max_sst_size, void *stream, uint32_t *num_ssts);
+/* The filter and resume stages of the last job (zeros after a job without either). */
+sdb_status sdb_compactor_filter_stats(const sdb_compactor *c, sdb_filter_stats *stats);
 
 /* ---------------------------------------------------------------------------------------------
  * WAL replay / device memtable: decoded rows in WAL (arrival) order -> the replayed memtables as sorted

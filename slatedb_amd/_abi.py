@@ -19,6 +19,7 @@ SDB_MERGE_OPERATOR_MISSING = 10
 SDB_DECOMPRESSION_ERROR = 11
 SDB_INVALID_SEQUENCE_ORDER = 12
 SDB_MERGE_OPERATOR_ERROR = 13
+SDB_COMPACTION_FILTER_ERROR = 14
 SDB_DEVICE_ERROR = 100
 CODEC_NONE, CODEC_SNAPPY, CODEC_ZLIB, CODEC_LZ4, CODEC_ZSTD = 0, 1, 2, 3, 4  # CompressionFormat
 
@@ -26,7 +27,7 @@ STATUS_NAMES = {
     0: "OK", 1: "EMPTY_KEY", 2: "EMPTY_BLOCK", 3: "CHECKSUM_MISMATCH", 4: "INVALID_ROW_FLAGS",
     5: "INVALID_VERSION", 6: "LIMIT_EXCEEDED", 7: "UNSUPPORTED", 8: "INVALID_ARGUMENT",
     9: "CORRUPT_BLOCK", 10: "MERGE_OPERATOR_MISSING", 11: "DECOMPRESSION_ERROR",
-    12: "INVALID_SEQUENCE_ORDER", 13: "MERGE_OPERATOR_ERROR", 100: "DEVICE_ERROR",
+    12: "INVALID_SEQUENCE_ORDER", 13: "MERGE_OPERATOR_ERROR", 14: "COMPACTION_FILTER_ERROR", 100: "DEVICE_ERROR",
 }
 
 KIND_VALUE, KIND_MERGE, KIND_TOMBSTONE = 0, 1, 2
@@ -367,6 +368,31 @@ class WalTablesOut(C.Structure):
 MERGE_BATCH_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, u8p, C.c_uint64, u8p, C.c_uint64, C.POINTER(u8p), u64p,
                              C.c_uint32, C.POINTER(u8p), u64p)
 
+# sdb_compaction_filter_fn: (ctx, rows, first, decision, new_val, new_len); sdb_compaction_end_fn: (ctx)
+CF_KEEP, CF_DROP, CF_TOMBSTONE, CF_VALUE, CF_MERGE = 0, 1, 2, 3, 4
+COMPACTION_FILTER_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.POINTER(KvBatch), C.c_uint64, u8p, C.POINTER(C.c_void_p), u64p)
+COMPACTION_END_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p)
+
+
+class CompactionFilter(C.Structure):
+    _fields_ = [
+        ("filter", COMPACTION_FILTER_FN), ("end", COMPACTION_END_FN), ("ctx", C.c_void_p),
+        ("batch_rows", C.c_uint64), ("want_values", C.c_uint32), ("pad", C.c_uint32),
+    ]
+
+
+class ResumeCursor(C.Structure):
+    _fields_ = [("key", C.c_void_p), ("key_len", C.c_uint64), ("seq", C.c_uint64)]
+
+
+class FilterStats(C.Structure):
+    _fields_ = [
+        ("rows_in", C.c_uint64), ("kept", C.c_uint64), ("dropped", C.c_uint64), ("tombstoned", C.c_uint64),
+        ("new_values", C.c_uint64), ("new_merges", C.c_uint64), ("calls", C.c_uint64), ("d2h_bytes", C.c_uint64),
+        ("h2d_bytes", C.c_uint64), ("applied", C.c_uint64), ("resume_drained", C.c_uint64),
+    ]
+
+
 DECODE_DESCENDING = 1
 DECODE_FAIL_FAST = 2  # SDB_DECODE_FAIL_FAST
 
@@ -498,6 +524,16 @@ SIGNATURES = {
                                                 C.POINTER(Retention), MERGE_BATCH_FN, C.c_void_p,
                                                 C.POINTER(SstParams), C.c_uint64, C.c_void_p, u32p]),
     "sdb_compactor_range_stats": (C.c_int, [C.c_void_p, C.POINTER(RangeJobStats)]),
+    "sdb_compactor_run_filtered": (C.c_int, [C.c_void_p, C.POINTER(Run), C.c_uint32, C.POINTER(Retention),
+                                             MERGE_BATCH_FN, C.c_void_p, C.POINTER(CompactionFilter),
+                                             C.POINTER(ResumeCursor), C.POINTER(SstParams), C.c_uint64, C.c_void_p,
+                                             u32p]),
+    "sdb_compactor_run_ssts_filtered": (C.c_int, [C.c_void_p, C.POINTER(CompactionView), C.c_uint32, u32p, C.c_uint32,
+                                                  C.c_uint16, C.POINTER(ScanRanges), C.POINTER(ScanRanges),
+                                                  C.POINTER(Retention), MERGE_BATCH_FN, C.c_void_p,
+                                                  C.POINTER(CompactionFilter), C.POINTER(ResumeCursor),
+                                                  C.POINTER(SstParams), C.c_uint64, C.c_void_p, u32p]),
+    "sdb_compactor_filter_stats": (C.c_int, [C.c_void_p, C.POINTER(FilterStats)]),
     "sdb_wal_replay_workspace_bytes": (C.c_uint64, [C.c_uint64, C.c_uint64]),
     "sdb_wal_replay_sort": (C.c_int, [C.POINTER(Run), C.c_void_p, C.c_uint64, C.c_uint64, C.c_int32, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),

@@ -78,6 +78,7 @@ const char *sdb_status_name(int s) {
         case SDB_DECOMPRESSION_ERROR: return "DECOMPRESSION_ERROR";
         case SDB_INVALID_SEQUENCE_ORDER: return "INVALID_SEQUENCE_ORDER";
         case SDB_MERGE_OPERATOR_ERROR: return "MERGE_OPERATOR_ERROR";
+        case SDB_COMPACTION_FILTER_ERROR: return "COMPACTION_FILTER_ERROR";
         case SDB_DEVICE_ERROR: return "DEVICE_ERROR";
         default: return "UNKNOWN";
     }

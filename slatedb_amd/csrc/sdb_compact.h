@@ -187,6 +187,8 @@ struct RxInputs {  // kernel arguments: per-input tables in device memory
     uint32_t n, nruns;
     uint32_t has_job, has_proj;            // job / proj were passed (else: unbounded)
     sdb_scan_ranges job, proj;             // job.n == 1, proj.n == n
+    uint32_t has_resume, resume_len;       // a resume cursor's key K: Included(K) is a third start bound of every V[i] (S1)
+    const uint8_t *resume_key;             // uploaded with the tables
     // uploaded by the host
     const uint8_t *const *index_keys;      // n
     const uint64_t *const *index_key_off;  // n
@@ -218,6 +220,62 @@ hipError_t launch_rx_clip_gate(const RxInputs &a, const sdb_decoded_out &dec, co
 // the contributed rows of every input, closed up: columns and keys of `dec` into `out` (`rows` = out_first[n])
 hipError_t launch_rx_compact(const RxInputs &a, const sdb_decoded_out &dec, const sdb_decoded_out &out, uint64_t rows,
                              hipStream_t st);
+
+// ---- the compaction filter and the resume cursor (sdb_compact_filter.hip), between the merge emit and the cuts ----
+// The host has run the filter over the retained stream `in` (n rows) and uploaded one decision byte per row
+// (SDB_CF_*; a row the resume drain removes arrives as SDB_CF_DROP), the offsets of the m replacement values in row
+// order and their bytes.  k_cf_size / k_cf_scan / k_cf_emit write the surviving rows, rules F3 / F4 applied, into
+// `out`: tiles of kMergeTile rows, one workgroup per tile.
+struct CfArgs {
+    uint64_t n, ntiles;
+    sdb_kv_batch in;           // the retained stream (device)
+    const uint8_t *decision;   // n
+    const uint64_t *mod_off;   // m + 1: replacement j (of the j-th row whose decision is VALUE or MERGE) = arena[mod_off[j], mod_off[j + 1])
+    const uint8_t *arena;
+    uint64_t *tile_sum;        // per tile: kept rows, key bytes, modified rows, value bytes of the unmodified kept rows
+                               // (exclusive offsets after k_cf_scan); then the four totals
+    sdb_merged_out out;        // the final stream: key_off / val_off start at 0 (summary unused)
+};
+// Sizes (w == NULL) or binds everything the apply step holds on the device: the upload (n decisions, m replacements
+// of arena_bytes bytes), the tile sums, and the final stream of n_out rows, key_out key bytes and val_out value bytes
+// (each arena with the 16 bytes of slack the merge emit's arenas have).
+inline uint64_t cf_bind(CfArgs &a, uint64_t n, uint64_t m, uint64_t arena_bytes, uint64_t n_out, uint64_t key_out,
+                        uint64_t val_out, uint8_t *w) {
+    a.n = n;
+    a.ntiles = (n + kMergeTile - 1) / kMergeTile;
+    Carver c{w, 0};
+    c.take(a.decision, n);
+    c.take(a.mod_off, m + 1);
+    c.take(a.arena, arena_bytes + 16);
+    c.take(a.tile_sum, 4 * (a.ntiles + 1));
+    sdb_merged_out &o = a.out;
+    o = sdb_merged_out{};
+    o.cap_entries = n_out;
+    o.key_cap = key_out;
+    o.val_cap = val_out;
+    c.take(o.key_off, n_out + 1);
+    c.take(o.val_off, n_out + 1);
+    c.take(o.kind, n_out + 1);
+    c.take(o.seq, n_out + 1);
+    c.take(o.create_ts, n_out + 1);
+    c.take(o.expire_ts, n_out + 1);
+    c.take(o.ts_mask, n_out + 1);
+    c.take(o.key_bytes, key_out + 16);
+    c.take(o.val_bytes, val_out + 16);
+    return c.off;
+}
+hipError_t launch_cf_apply(const CfArgs &a, hipStream_t st);
+// S1 over decoded runs: lb[r] = the first row of run r whose key is >= key (device arrays; one thread per run)
+struct CfSeekRun {
+    const uint8_t *key_arena;
+    const uint64_t *key_off;
+    uint64_t n;
+};
+hipError_t launch_cf_seek(const CfSeekRun *runs, uint32_t nruns, const uint8_t *key, uint32_t key_len, uint64_t *lb,
+                          hipStream_t st);
+// S2 without a filter: *drained = the first row of the stream m at which key == K && seq >= S fails (one workgroup)
+hipError_t launch_cf_drain(const sdb_kv_batch &m, const uint8_t *key, uint32_t key_len, uint64_t seq, uint64_t *drained,
+                           hipStream_t st);
 
 // out[2i], out[2i+1] = key_off[cut[i]], val_off[cut[i]] for i <= ns
 hipError_t launch_cut_offsets(const uint64_t *cut, const uint64_t *num, const uint64_t *key_off, const uint64_t *val_off,

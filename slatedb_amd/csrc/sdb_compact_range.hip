@@ -1,7 +1,8 @@
 // sdb_compact_range.hip — the input side of sdb_compactor_run_ssts_ranged: what load_iterators does with
 // job_args.range and each input's visible_range (compactor_executor.rs:327-435; calculate_view_range,
 // db_state.rs:243-251) before the merge sees a row.
-//   k_rx_cover    one workgroup: the ranges checked (R7), V[i] = job ∩ visible[i] (R1), its covering blocks
+//   k_rx_cover    one workgroup: the ranges checked (R7), V[i] = job ∩ visible[i] (R1; with a resume cursor also
+//                 ∩ [K, ..), rule S1 of sdb_compactor_run_ssts_filtered), its covering blocks
 //                 (R2: covering_blocks of sdb_range.h over the input's index keys), and the scan over the inputs
 //                 that closes the covered blocks up into the block list k_cx_blocks fills for the decode
 //   k_rx_clip     one thread per input: the rows of its decoded blocks that V[i] contains (R3), by two bound
@@ -32,6 +33,7 @@ SDB_DEV void view_range(const RxInputs &a, uint32_t i, Bound &s, Bound &e) {
         pe = range_end(a.proj, i);
     }
     s = tighter_start(js, ps);
+    if (a.has_resume) s = tighter_start(s, Bound{a.resume_key, a.resume_len, SDB_BOUND_INCLUDED});  // S1: seek(K)
     e = tighter_end(je, pe);
 }
 

@@ -26,6 +26,14 @@
 //   merge_encode (both jobs over encoded inputs): merge_front, retention + emit into buffers of the declared sizes,
 //       the stream padded to the declared count, cut_step over the padded stream with the summary, encode_outputs.
 // An operator adds chain_step's two [S] to any of them (the second only when there is a chain).
+// A compaction filter and a resume cursor (sdb_compactor_run_filtered, _run_ssts_filtered) are Job fields of the same
+// pipeline:
+//   seek_runs        S1 of run_job: every run from the lower bound of the cursor's key on [S]; in run_ranged_job the
+//                    key is a third start bound of every view range (k_rx_cover) and costs none
+//   filtered_tail    replaces what follows the emit: filter_step (the stream gathered to pinned memory [S], the
+//                    callbacks, the upload and the apply kernels unless every row is kept; without a filter the
+//                    drain count from the device [S]), then cut_step over the final, unpadded stream and
+//                    encode_outputs.  merge_encode reads the merged summary first [S] to learn the stream's length.
 // The outputs stay in the handle's device memory.  The handle's buffers (DevBuf, PinBuf) and every layout inside them
 // come from sdb_host.h.
 #include <hip/hip_runtime.h>
@@ -33,6 +41,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <utility>
 #include <vector>
 
 #include "../../include/slatedb_amd.h"
@@ -104,6 +113,15 @@ struct sdb_compactor {
     DevBuf merge_ws, cols, keys, vals, cut_ws, cuts, sst_meta, sst_data, sst_bloom, enc_ws, dec, dec_ws, cx_tab;
     std::vector<GroupBufs> groups;
     PinBuf pin, pin_tab;
+    // the filter and resume stages: the stream gathered for the filter (pinned, with the decisions), the replacement
+    // values (pinned), the uploaded decisions and the final stream (device, cf_bind); the cursor's key and the runs'
+    // lower bounds (seek_ws and its pinned mirror)
+    PinBuf pin_cf, pin_cf_up, pin_seek;
+    DevBuf cf_ws, seek_ws;
+    sdb_filter_stats fstats{};
+    std::vector<const uint8_t *> cf_nv;  // one filter call's replacement pointers and lengths
+    std::vector<uint64_t> cf_nl;
+    std::vector<sdb_run> seeked;         // a resumed job's runs from their lower bounds on
     // the merge-operator step: per-position chain state, the chain tables + staging arena (device and pinned
     // mirror), the merged values (pinned, then device)
     GuardBuf chain_ws, chain_tab, chain_up;
@@ -118,6 +136,7 @@ struct sdb_compactor {
     // recorded on the job's stream when a run_ssts job returns (every path): the next job waits for it
     // before it rewrites pin_tab / cx_tab, which that job's upload and kernels may still be reading
     StreamEvent tab_ev;
+    StreamEvent cf_ev;  // the upload out of pin_cf / pin_cf_up: the next job waits for it before it rewrites them
     sdb_kv_batch merged{};
     sdb_merge_summary msum{};
     std::vector<sdb_compacted_sst> ssts;
@@ -139,6 +158,8 @@ struct Job {
     void *stream;  // as the public calls take it
     uint32_t *num_ssts;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const sdb_compaction_filter *filter = nullptr;  // NULL: a job without a compaction filter
+    const sdb_resume_cursor *resume = nullptr;      // NULL: a job that starts at its first row
 };
 
 // An sdb_run of n entries over columns, from their entry e0 on (the arenas are not offset: *_off index them).
@@ -385,6 +406,11 @@ sdb_kv_batch batch_of(const sdb_merged_out &o, uint64_t n) {
     return m;
 }
 
+// F9 on the host: what a filter and a cursor must carry (either may be NULL).
+bool filter_args_ok(const sdb_compaction_filter *f, const sdb_resume_cursor *r) {
+    return !(f && !f->filter) && !(r && ((!r->key && r->key_len) || r->key_len > 0xFFFFFFFFull));
+}
+
 // The prologue of every job: the handle's results of the last job reset, the arguments every job takes checked.
 sdb_status begin_job(const Job &j) {
     sdb_compactor *c = j.c;
@@ -395,6 +421,8 @@ sdb_status begin_job(const Job &j) {
     c->msum = sdb_merge_summary{};
     c->mstats = sdb_merge_op_stats{};
     c->rstats = sdb_range_job_stats{};
+    c->fstats = sdb_filter_stats{};
+    if (!filter_args_ok(j.filter, j.resume)) return SDB_INVALID_ARGUMENT;  // F9
     if (j.params->sst_type != SDB_SST_COMPACTED || !j.ret) return SDB_INVALID_ARGUMENT;  // compactions write compacted SSTs
     return SDB_OK;
 }
@@ -559,6 +587,262 @@ sdb_status encode_outputs(const Job &j, const CutRead &rd, uint64_t n) {
     return first;
 }
 
+// ---- the compaction filter and the resume cursor (rules F1-F10, S1-S3 of the header) ----
+
+// S1 of the decoded-runs job: `runs` from each run's first row with key >= K on (a device lower bound per run, read
+// back: one synchronisation), so sdb_run.n and the bases stay host values.
+sdb_status seek_runs(const Job &j, const sdb_run *runs, uint32_t nruns, std::vector<sdb_run> &out) {
+    sdb_compactor *c = j.c;
+    const sdb_resume_cursor &rc = *j.resume;
+    // what build_merge_args asks of a run, before k_cf_seek reads its keys
+    for (uint32_t r = 0; r < nruns; r++) {
+        const sdb_run &R = runs[r];
+        if (R.n && (!R.key_arena || !R.key_off || !R.val_off || !R.val_len || !R.seq || !R.flags)) return SDB_INVALID_ARGUMENT;
+    }
+    out.assign(runs, runs + nruns);
+    if (!nruns) return SDB_OK;
+    CfSeekRun *h_runs = nullptr, *d_runs = nullptr;
+    uint8_t *h_key = nullptr, *d_key = nullptr;
+    uint64_t *h_lb = nullptr, *d_lb = nullptr;
+    auto bind = [&](uint8_t *base, CfSeekRun *&r, uint8_t *&k, uint64_t *&lb) {
+        Carver k_{base, 0};
+        k_.take(r, nruns);
+        k_.take(k, rc.key_len + 1);
+        k_.take(lb, nruns);
+        return k_.off;
+    };
+    const uint64_t bytes = bind(nullptr, h_runs, h_key, h_lb);
+    if (!c->pin_seek.ensure(bytes) || !c->seek_ws.ensure(bytes)) return SDB_DEVICE_ERROR;
+    bind(c->pin_seek.at<uint8_t>(0), h_runs, h_key, h_lb);
+    bind(c->seek_ws.at<uint8_t>(0), d_runs, d_key, d_lb);
+    for (uint32_t r = 0; r < nruns; r++) h_runs[r] = CfSeekRun{runs[r].key_arena, runs[r].key_off, runs[r].n};
+    if (rc.key_len) memcpy(h_key, rc.key, rc.key_len);
+    const uint64_t up = (uint64_t)(reinterpret_cast<uint8_t *>(h_lb) - reinterpret_cast<uint8_t *>(h_runs));
+    if (hipMemcpyAsync(d_runs, h_runs, up, hipMemcpyHostToDevice, j.s) != hipSuccess ||
+        launch_cf_seek(d_runs, nruns, d_key, (uint32_t)rc.key_len, d_lb, j.s) != hipSuccess ||
+        hipMemcpyAsync(h_lb, d_lb, 8 * (uint64_t)nruns, hipMemcpyDeviceToHost, j.s) != hipSuccess ||
+        hipStreamSynchronize(j.s) != hipSuccess)
+        return SDB_DEVICE_ERROR;
+    for (uint32_t r = 0; r < nruns; r++) {
+        const uint64_t lb = std::min(h_lb[r], runs[r].n);
+        sdb_run &x = out[r];
+        x.n -= lb;
+        x.key_off += lb;
+        x.val_off += lb;
+        x.val_len += lb;
+        x.seq += lb;
+        x.flags += lb;
+        if (x.create_ts) x.create_ts += lb;
+        if (x.expire_ts) x.expire_ts += lb;
+    }
+    return SDB_OK;
+}
+
+// The stream m from its row d on (the arenas are not offset: *_off index them).
+void skip_rows(sdb_kv_batch &m, uint64_t d) {
+    m.n -= d;
+    m.key_off += d;
+    m.val_off += d;
+    m.kind += d;
+    m.seq += d;
+    m.create_ts += d;
+    m.expire_ts += d;
+    m.ts_mask += d;
+}
+
+// The retained stream as the filter reads it, in pinned memory: the columns, the key bytes, the value bytes (vb == 0:
+// not gathered), and the decisions the callbacks write.
+struct CfHost {
+    uint8_t *kind, *ts_mask, *decision, *keys, *vals;
+    uint64_t *seq, *key_off, *val_off;
+    int64_t *create_ts, *expire_ts;
+    uint64_t *mod_off;  // n + 1: the offsets of the replacements packed so far (in c->pin_cf_up)
+};
+uint64_t cf_host_bind(CfHost &h, uint64_t n, uint64_t kb, uint64_t vb, uint8_t *base) {
+    Carver k{base, 0};
+    k.take(h.key_off, n + 1);
+    k.take(h.val_off, n + 1);
+    k.take(h.seq, n);
+    k.take(h.create_ts, n);
+    k.take(h.expire_ts, n);
+    k.take(h.kind, n);
+    k.take(h.ts_mask, n);
+    k.take(h.decision, n);
+    k.take(h.mod_off, n + 1);
+    k.take(h.keys, kb);
+    k.take(h.vals, vb);
+    return k.off;
+}
+
+// b grown to `need` bytes with its first `used` bytes kept (at least doubling: amortised over a job's replacements).
+bool grow_keep(PinBuf &b, uint64_t used, uint64_t need) {
+    if (b.p && need <= b.cap) return true;
+    PinBuf nb;
+    if (!nb.ensure(std::max(need, 2 * b.cap))) return false;
+    if (used) memcpy(nb.p, b.p, used);
+    b = std::move(nb);
+    return true;
+}
+
+sdb_status filter_failed(sdb_compactor *c, sdb_status st, uint64_t at) {
+    c->msum.status = st;
+    c->msum.first_error_entry = at;
+    return st;
+}
+
+// The filter and the drain over the retained stream m (its rows start at 0; kb / vb: its key and value bytes): m
+// becomes the final stream, *bytes its key and value bytes.  With a filter: the gather [S], the callbacks, and, unless
+// every row is kept (F7), the upload and the apply kernels into c->cf_ws.  A cursor without a filter: the drain
+// count from the device [S].
+sdb_status filter_step(const Job &j, sdb_kv_batch &m, uint64_t kb, uint64_t vb, uint64_t *bytes) {
+    sdb_compactor *c = j.c;
+    hipStream_t s = j.s;
+    sdb_filter_stats &fs = c->fstats;
+    const sdb_compaction_filter *f = j.filter;
+    const sdb_resume_cursor *rc = j.resume;
+    const uint64_t n = m.n;
+    *bytes = kb + vb;
+    if (!f) {  // S2 alone: the first row at which key == K && seq >= S fails
+        if (!rc || !n) return SDB_OK;
+        Carver k{nullptr, 0};
+        const uint64_t o_key = k.bytes(rc->key_len + 1), o_d = k.bytes(8);
+        if (!c->pin_seek.ensure(k.off) || !c->seek_ws.ensure(k.off)) return SDB_DEVICE_ERROR;
+        if (rc->key_len) memcpy(c->pin_seek.at<uint8_t>(o_key), rc->key, rc->key_len);
+        uint64_t *h_d = c->pin_seek.at<uint64_t>(o_d);
+        if (hipMemcpyAsync(c->seek_ws.at<uint8_t>(o_key), c->pin_seek.at<uint8_t>(o_key), rc->key_len + 1, hipMemcpyHostToDevice, s) != hipSuccess ||
+            launch_cf_drain(m, c->seek_ws.at<uint8_t>(o_key), (uint32_t)rc->key_len, rc->seq, c->seek_ws.at<uint64_t>(o_d), s) != hipSuccess ||
+            hipMemcpyAsync(h_d, c->seek_ws.at<uint64_t>(o_d), 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess)
+            return SDB_DEVICE_ERROR;
+        fs.resume_drained = std::min(*h_d, n);
+        skip_rows(m, fs.resume_drained);
+        return SDB_OK;
+    }
+
+    // 1. the stream to the host: columns and key bytes, value bytes only when the filter wants them
+    const uint64_t hv = f->want_values ? vb : 0;
+    CfHost h{};
+    if (!c->cf_ev.wait() || !c->pin_cf.ensure(cf_host_bind(h, n, kb, hv, nullptr))) return SDB_DEVICE_ERROR;
+    cf_host_bind(h, n, kb, hv, c->pin_cf.at<uint8_t>(0));
+    if (n) {
+        auto back = [&](void *dst, const void *src, uint64_t b) {
+            fs.d2h_bytes += b;
+            return !b || hipMemcpyAsync(dst, src, b, hipMemcpyDeviceToHost, s) == hipSuccess;
+        };
+        if (!back(h.key_off, m.key_off, 8 * (n + 1)) || !back(h.val_off, m.val_off, 8 * (n + 1)) || !back(h.seq, m.seq, 8 * n) ||
+            !back(h.create_ts, m.create_ts, 8 * n) || !back(h.expire_ts, m.expire_ts, 8 * n) || !back(h.kind, m.kind, n) ||
+            !back(h.ts_mask, m.ts_mask, n) || !back(h.keys, m.key_bytes, kb) || !back(h.vals, m.val_bytes, hv) ||
+            hipStreamSynchronize(s) != hipSuccess)
+            return SDB_DEVICE_ERROR;
+        memset(h.decision, SDB_CF_KEEP, n);
+    }
+
+    // 2. the callbacks (F8), the checks of what they returned (F9), the replacements packed in row order, the drain
+    //    (S2) over the surviving rows as they come, and the final stream's exact sizes
+    //    The replacements go straight into the pinned arena c->pin_cf_up, their offsets into h.mod_off.
+    std::vector<const uint8_t *> &nv = c->cf_nv;  // (the handle's: no allocation in steady state)
+    std::vector<uint64_t> &nl = c->cf_nl;
+    uint64_t nm = 0, arena_bytes = 0;
+    h.mod_off[0] = 0;
+    bool draining = rc != nullptr, all_keep = true;
+    uint64_t n_out = 0, kb_out = 0, vb_out = 0;
+    const uint64_t step = f->batch_rows ? f->batch_rows : n;
+    for (uint64_t first = 0; first < n; first += step) {
+        const uint64_t cnt = std::min(step, n - first);
+        sdb_kv_batch rows{};
+        rows.n = cnt;
+        rows.key_bytes = h.keys;
+        rows.key_off = h.key_off + first;
+        rows.val_bytes = f->want_values ? h.vals : nullptr;
+        rows.val_off = h.val_off + first;
+        rows.kind = h.kind + first;
+        rows.seq = h.seq + first;
+        rows.create_ts = h.create_ts + first;
+        rows.expire_ts = h.expire_ts + first;
+        rows.ts_mask = h.ts_mask + first;
+        nv.assign(cnt, nullptr);
+        nl.assign(cnt, 0);
+        fs.calls++;
+        fs.rows_in += cnt;
+        if (f->filter(f->ctx, &rows, first, h.decision + first, nv.data(), nl.data()) != 0)
+            return filter_failed(c, SDB_COMPACTION_FILTER_ERROR, first);
+        for (uint64_t q = 0; q < cnt; q++) {
+            const uint64_t i = first + q;
+            const uint8_t d = h.decision[i];
+            const bool mod = d == SDB_CF_VALUE || d == SDB_CF_MERGE;
+            if (d > SDB_CF_MERGE || (mod && !nv[q] && nl[q])) return filter_failed(c, SDB_INVALID_ARGUMENT, i);
+            if (mod && nl[q] > 0xFFFFFFFFull) return filter_failed(c, SDB_LIMIT_EXCEEDED, i);  // value lengths are u32
+            (d == SDB_CF_KEEP ? fs.kept : d == SDB_CF_DROP ? fs.dropped : d == SDB_CF_TOMBSTONE ? fs.tombstoned
+             : d == SDB_CF_VALUE ? fs.new_values : fs.new_merges)++;
+            if (d != SDB_CF_KEEP) all_keep = false;
+            if (d == SDB_CF_DROP) continue;
+            const uint64_t kl = h.key_off[i + 1] - h.key_off[i];
+            if (draining) {
+                if (kl == rc->key_len && (!kl || !memcmp(h.keys + h.key_off[i], rc->key, kl)) && h.seq[i] >= rc->seq) {
+                    fs.resume_drained++;
+                    h.decision[i] = SDB_CF_DROP;  // (as the apply kernels take it; its replacement is not packed)
+                    continue;
+                }
+                draining = false;
+            }
+            n_out++;
+            kb_out += kl;
+            if (mod) {
+                if (!grow_keep(c->pin_cf_up, arena_bytes, arena_bytes + nl[q])) return SDB_DEVICE_ERROR;
+                if (nl[q]) memcpy(c->pin_cf_up.at<uint8_t>(arena_bytes), nv[q], nl[q]);
+                arena_bytes += nl[q];
+                h.mod_off[++nm] = arena_bytes;
+                vb_out += nl[q];
+            } else if (d == SDB_CF_KEEP) {
+                vb_out += h.val_off[i + 1] - h.val_off[i];
+            }
+        }
+    }
+    if (f->end && f->end(f->ctx) != 0) return filter_failed(c, SDB_COMPACTION_FILTER_ERROR, fs.rows_in);
+    if (all_keep) {  // F7: the stream as it is, from the first row the drain left
+        skip_rows(m, fs.resume_drained);
+        return SDB_OK;
+    }
+    *bytes = kb_out + vb_out;
+    if (!n_out) {
+        m = sdb_kv_batch{};
+        return SDB_OK;
+    }
+
+    // 3. the upload: the decisions, the replacements' offsets, their bytes
+    CfArgs a{};
+    if (!c->cf_ws.ensure(cf_bind(a, n, nm, arena_bytes, n_out, kb_out, vb_out, nullptr))) return SDB_DEVICE_ERROR;
+    cf_bind(a, n, nm, arena_bytes, n_out, kb_out, vb_out, c->cf_ws.at<uint8_t>(0));
+    a.in = m;
+    auto up = [&](const void *dst, const void *src, uint64_t b) {
+        fs.h2d_bytes += b;
+        return !b || hipMemcpyAsync(const_cast<void *>(dst), src, b, hipMemcpyHostToDevice, s) == hipSuccess;
+    };
+    const bool sent = up(a.decision, h.decision, n) && up(a.mod_off, h.mod_off, 8 * (nm + 1)) &&
+                      up(a.arena, c->pin_cf_up.p, arena_bytes);
+    c->cf_ev.record(s);
+    // 4. the apply kernels: the final stream in c->cf_ws
+    if (!sent || launch_cf_apply(a, s) != hipSuccess) return SDB_DEVICE_ERROR;
+    fs.applied = 1;
+    m = batch_of(a.out, n_out);
+    return SDB_OK;
+}
+
+// What follows the emit in a job with a filter or a cursor: filter_step over the retained stream m of exactly m.n
+// rows, then (S3) the cuts over the final stream as it is and the output SSTs.
+sdb_status filtered_tail(const Job &j, sdb_kv_batch m, uint64_t kb, uint64_t vb) {
+    sdb_compactor *c = j.c;
+    uint64_t bytes = 0;
+    sdb_status st = filter_step(j, m, kb, vb, &bytes);
+    if (st) return st;
+    c->merged = m;
+    if (!m.n) return hipStreamSynchronize(j.s) == hipSuccess ? SDB_OK : SDB_DEVICE_ERROR;
+    CutRead rd;
+    st = cut_step(j, m, nullptr, bytes, nullptr, rd);
+    if (st) return st;
+    return encode_outputs(j, rd, m.n);
+}
+
 }  // namespace
 
 extern "C" {
@@ -585,6 +869,11 @@ sdb_status run_job(const Job &j, const sdb_run *runs, uint32_t nruns) {
     sdb_compactor *c = j.c;
     if (hipSetDevice(c->device) != hipSuccess) return SDB_DEVICE_ERROR;
     hipStream_t s = j.s;
+    std::vector<sdb_run> &seeked = c->seeked;  // (the handle's: no allocation in steady state)
+    if (j.resume) {  // S1: every run from its first row with key >= K on (one synchronisation)
+        if ((st = seek_runs(j, runs, nruns, seeked))) return st;
+        runs = seeked.data();
+    }
     uint64_t total = 0;
     for (uint32_t r = 0; r < nruns; r++) total += runs[r].n;
 
@@ -607,6 +896,7 @@ sdb_status run_job(const Job &j, const sdb_run *runs, uint32_t nruns) {
     a.out.val_cap = c->msum.val_bytes;
     if (launch_merge_emit(a, s) != hipSuccess) return SDB_DEVICE_ERROR;
     const uint64_t n = c->msum.num_out;
+    if (j.filter || j.resume) return filtered_tail(j, batch_of(a.out, n), c->msum.key_bytes, c->msum.val_bytes);
     sdb_kv_batch &m = c->merged;
     m = batch_of(a.out, n);
     if (!n) return hipStreamSynchronize(s) == hipSuccess ? SDB_OK : SDB_DEVICE_ERROR;
@@ -706,8 +996,17 @@ sdb_status merge_encode(const Job &j, const std::vector<sdb_run> &runs, uint64_t
         a.out.val_bytes = out.val_bytes = c->vals.at<uint8_t>(0);
         a.out.val_cap = out.val_cap = V;
     }
-    if (launch_merge_retention(a, true, s) != hipSuccess || launch_merge_pad(out, E, s) != hipSuccess)
-        return SDB_DEVICE_ERROR;
+    if (launch_merge_retention(a, true, s) != hipSuccess) return SDB_DEVICE_ERROR;
+    if (j.filter || j.resume) {
+        // the filter and the drain need the stream's exact length: the merged summary first (one synchronisation
+        // more than the plain job), then the cuts over an unpadded stream
+        if (hipMemcpyAsync(&c->msum, out.summary, sizeof(sdb_merge_summary), hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess)
+            return SDB_DEVICE_ERROR;
+        if (c->msum.status) return (sdb_status)c->msum.status;
+        return filtered_tail(j, batch_of(out, c->msum.num_out), c->msum.key_bytes, c->msum.val_bytes);
+    }
+    if (launch_merge_pad(out, E, s) != hipSuccess) return SDB_DEVICE_ERROR;
     // cuts over the padded stream, ending at the merged count; the merged summary rides along (one synchronisation)
     CutRead rd;
     st = cut_step(j, batch_of(out, E), &out.summary->num_out, K + V, out.summary, rd);
@@ -866,6 +1165,8 @@ sdb_status run_ranged_job(const Job &j, const sdb_compaction_view *inputs, uint3
     a.nruns = nruns;
     if (job) a.has_job = 1, a.job = *job;
     if (proj) a.has_proj = 1, a.proj = *proj;
+    if (j.resume) a.has_resume = 1, a.resume_len = (uint32_t)j.resume->key_len;  // S1: a third start bound of every V[i]
+    uint8_t *h_rkey;
     const uint8_t **h_data, **h_ikeys;
     const uint8_t *const *d_data;  // (read by the decode: CxInputs below)
     const uint64_t **h_ikoff, **h_boff;
@@ -881,8 +1182,10 @@ sdb_status run_ranged_job(const Job &j, const sdb_compaction_view *inputs, uint3
             t.take(h_gblk, a.gblock, n + 1);
             t.take(h_nent, a.num_entries, n);
             t.take(h_rstart, a.run_start, (uint64_t)nruns + 1);
+            t.take(h_rkey, a.resume_key, (uint64_t)a.resume_len + 1);
         }))
         return SDB_DEVICE_ERROR;
+    if (a.resume_len) memcpy(h_rkey, j.resume->key, a.resume_len);
     uint64_t B_all = 0, E_all = 0, K_all = 0;
     uintptr_t base = ~(uintptr_t)0;
     for (uint32_t i = 0; i < ninputs; i++) {
@@ -1020,14 +1323,25 @@ sdb_status sdb_compactor_run_ssts_merge(sdb_compactor *c, const sdb_compaction_i
                         input_sst_version);
 }
 
-sdb_status sdb_compactor_run_ssts_ranged(sdb_compactor *c, const sdb_compaction_view *inputs, uint32_t ninputs,
-                                         const uint32_t *run_start, uint32_t nruns, uint16_t input_sst_version,
-                                         const sdb_scan_ranges *job_range, const sdb_scan_ranges *proj,
-                                         const sdb_retention *ret, sdb_merge_batch_fn op, void *ctx,
-                                         const sdb_sst_params *params, uint64_t max_sst_size, void *stream,
-                                         uint32_t *num_ssts) {
-    // R7 on the host, before anything needs a device
-    if (!ret || !params || !num_ssts || (ninputs && !inputs)) return SDB_INVALID_ARGUMENT;
+sdb_status sdb_compactor_run_filtered(sdb_compactor *c, const sdb_run *runs, uint32_t nruns, const sdb_retention *ret,
+                                      sdb_merge_batch_fn op, void *op_ctx, const sdb_compaction_filter *filter,
+                                      const sdb_resume_cursor *resume, const sdb_sst_params *params,
+                                      uint64_t max_sst_size, void *stream, uint32_t *num_ssts) {
+    Job j{c, ret, op, op_ctx, params, max_sst_size, stream, num_ssts};
+    j.filter = filter;
+    j.resume = resume;
+    return run_job(j, runs, nruns);
+}
+
+sdb_status sdb_compactor_run_ssts_filtered(sdb_compactor *c, const sdb_compaction_view *inputs, uint32_t ninputs,
+                                           const uint32_t *run_start, uint32_t nruns, uint16_t input_sst_version,
+                                           const sdb_scan_ranges *job_range, const sdb_scan_ranges *proj,
+                                           const sdb_retention *ret, sdb_merge_batch_fn op, void *ctx,
+                                           const sdb_compaction_filter *filter, const sdb_resume_cursor *resume,
+                                           const sdb_sst_params *params, uint64_t max_sst_size, void *stream,
+                                           uint32_t *num_ssts) {
+    // R7 and F9 on the host, before anything needs a device
+    if (!ret || !params || !num_ssts || (ninputs && !inputs) || !filter_args_ok(filter, resume)) return SDB_INVALID_ARGUMENT;
     if (job_range && (job_range->n != 1 || ranges_null(job_range))) return SDB_INVALID_ARGUMENT;
     if (proj && (proj->n != ninputs || ranges_null(proj))) return SDB_INVALID_ARGUMENT;
     for (uint32_t i = 0; i < ninputs; i++) {
@@ -1039,8 +1353,26 @@ sdb_status sdb_compactor_run_ssts_ranged(sdb_compactor *c, const sdb_compaction_
         int n = 0;
         return hipGetDeviceCount(&n) != hipSuccess || n == 0 ? SDB_DEVICE_ERROR : SDB_INVALID_ARGUMENT;
     }
-    return run_ranged_job(Job{c, ret, op, ctx, params, max_sst_size, stream, num_ssts}, inputs, ninputs, run_start, nruns,
-                          input_sst_version, job_range, proj);
+    Job j{c, ret, op, ctx, params, max_sst_size, stream, num_ssts};
+    j.filter = filter;
+    j.resume = resume;
+    return run_ranged_job(j, inputs, ninputs, run_start, nruns, input_sst_version, job_range, proj);
+}
+
+sdb_status sdb_compactor_run_ssts_ranged(sdb_compactor *c, const sdb_compaction_view *inputs, uint32_t ninputs,
+                                         const uint32_t *run_start, uint32_t nruns, uint16_t input_sst_version,
+                                         const sdb_scan_ranges *job_range, const sdb_scan_ranges *proj,
+                                         const sdb_retention *ret, sdb_merge_batch_fn op, void *ctx,
+                                         const sdb_sst_params *params, uint64_t max_sst_size, void *stream,
+                                         uint32_t *num_ssts) {
+    return sdb_compactor_run_ssts_filtered(c, inputs, ninputs, run_start, nruns, input_sst_version, job_range, proj, ret, op,
+                                           ctx, nullptr, nullptr, params, max_sst_size, stream, num_ssts);
+}
+
+sdb_status sdb_compactor_filter_stats(const sdb_compactor *c, sdb_filter_stats *stats) {
+    if (!c || !stats) return SDB_INVALID_ARGUMENT;
+    *stats = c->fstats;
+    return SDB_OK;
 }
 
 sdb_status sdb_compactor_range_stats(const sdb_compactor *c, sdb_range_job_stats *stats) {

@@ -1442,14 +1442,22 @@ class Compactor:
         if not self.h:
             raise SdbError(_abi.SDB_DEVICE_ERROR, "sdb_compactor_create")
 
-    def _job(self, symbol, head, ret, operator, prm, max_sst_size, stream):
+    def _job(self, symbol, head, ret, operator, prm, max_sst_size, stream, flt=None, resume=None):
         """One job entry point: the inputs `head`, then ret, (with an operator) its callback and a NULL context,
-        params, max_sst_size, stream, num_ssts.  The ranged symbol always takes the callback pair: NULL without an
-        operator."""
-        op = (_abi.MERGE_BATCH_FN(), None) if symbol.endswith("_ranged") else ()
+        (the filtered symbols) the filter and the cursor, params, max_sst_size, stream, num_ssts.  The ranged and the
+        filtered symbols always take the callback pair: NULL without an operator."""
+        filtered = symbol.endswith("_filtered")
+        op = (_abi.MERGE_BATCH_FN(), None) if symbol.endswith("_ranged") or filtered else ()
         if operator is not self._PLAIN:
             cb, self.operator_state = self._operator_callback(operator)
             op = (cb, None)
+        if filtered:
+            from . import compaction_filter as CF
+            cf, self.filter_state = (None, None) if flt is None else CF.callbacks(flt)
+            # (key, seq), or an sdb_resume_cursor the caller built itself, which passes through as it is
+            cur, keep = (None, None) if resume is None else \
+                (resume, None) if isinstance(resume, _abi.ResumeCursor) else CF.cursor(*resume)
+            op += (None if cf is None else C.byref(cf), None if cur is None else C.byref(cur))
         ns = C.c_uint32(0)
         st = getattr(lib(), symbol)(self.h, *head, C.byref(ret), *op, C.byref(prm), max_sst_size, _sp(stream), C.byref(ns))
         self.status = st
@@ -1523,14 +1531,10 @@ class Compactor:
         """sdb_compactor_run_ssts_merge: run_ssts() with the store's merge operator."""
         return self._run_ssts(inputs, ret, operator, prm, max_sst_size, input_version, run_start, stream)
 
-    def run_ssts_ranged(self, inputs, ret, prm, max_sst_size, job_range=None, projections=None, operator=None,
-                        input_version=2, run_start=None, stream=None):
-        """sdb_compactor_run_ssts_ranged: run_ssts() (with `operator`: run_ssts_merge()) over one job range and a
-        visible range per input.  inputs: as run_ssts, plus .index_keys / .index_key_off (device tensors: each
-        block's index key).  job_range: (start, start_kind, end, end_kind) as scan_ranges_columnar takes it, or
-        None = unbounded; projections: one such tuple or None (the whole SST) per input, as projections_columnar
-        takes them, or None; either may also be the dict of arrays those functions return (host arrays, or device
-        tensors the caller keeps)."""
+    def _ranged_job(self, symbol, inputs, ret, prm, max_sst_size, job_range, projections, operator, input_version,
+                    run_start, stream, *filtered):
+        """The ranged and the filtered job over encoded inputs: the views, the run shape, the job range and the
+        projections (uploaded when they are host arrays, kept until the job's work is done), then _job."""
         dev = inputs[0].data.device if inputs else "cuda"
         keep = []  # the range tensors: until the job's work is done
 
@@ -1543,11 +1547,44 @@ class Compactor:
         columnar = lambda x, f: x if isinstance(x, dict) else f(x)  # noqa: E731  (a dict: the host arrays themselves)
         jr = None if job_range is None else ranges(columnar(job_range, lambda r: scan_ranges_columnar([r])))
         pj = None if projections is None else ranges(columnar(projections, projections_columnar))
-        res = self._job("sdb_compactor_run_ssts_ranged",
-                        (self._inputs(inputs, views=True), len(inputs), *self._run_shape(run_start, len(inputs)),
-                         input_version, jr, pj), ret, self._PLAIN if operator is None else operator, prm, max_sst_size, stream)
+        res = self._job(symbol, (self._inputs(inputs, views=True), len(inputs), *self._run_shape(run_start, len(inputs)),
+                                 input_version, jr, pj), ret, self._PLAIN if operator is None else operator, prm, max_sst_size,
+                        stream, *filtered)
         _sync(stream, dev)  # the range tensors are released on return
         return res
+
+    def run_ssts_ranged(self, inputs, ret, prm, max_sst_size, job_range=None, projections=None, operator=None,
+                        input_version=2, run_start=None, stream=None):
+        """sdb_compactor_run_ssts_ranged: run_ssts() (with `operator`: run_ssts_merge()) over one job range and a
+        visible range per input.  inputs: as run_ssts, plus .index_keys / .index_key_off (device tensors: each
+        block's index key).  job_range: (start, start_kind, end, end_kind) as scan_ranges_columnar takes it, or
+        None = unbounded; projections: one such tuple or None (the whole SST) per input, as projections_columnar
+        takes them, or None; either may also be the dict of arrays those functions return (host arrays, or device
+        tensors the caller keeps)."""
+        return self._ranged_job("sdb_compactor_run_ssts_ranged", inputs, ret, prm, max_sst_size, job_range, projections,
+                                operator, input_version, run_start, stream)
+
+    def run_filtered(self, druns, ret, prm, max_sst_size, flt=None, resume=None, operator=None, stream=None):
+        """sdb_compactor_run_filtered: run() (with `operator`: run_merge()) with a compaction filter (a
+        slatedb_amd.compaction_filter BatchFilter, or an object with filter(entry)) and / or a resume cursor
+        (key, seq) = the last row the interrupted job wrote.  filter_state["error"] keeps a filter's exception."""
+        cr = (_abi.Run * max(len(druns), 1))(*[r.to_ctypes() for r in druns])
+        return self._job("sdb_compactor_run_filtered", (cr, len(druns)), ret, self._PLAIN if operator is None else operator,
+                         prm, max_sst_size, stream, flt, resume)
+
+    def run_ssts_filtered(self, inputs, ret, prm, max_sst_size, flt=None, resume=None, job_range=None, projections=None,
+                          operator=None, input_version=2, run_start=None, stream=None):
+        """sdb_compactor_run_ssts_filtered: run_ssts_ranged() with a compaction filter and / or a resume cursor."""
+        return self._ranged_job("sdb_compactor_run_ssts_filtered", inputs, ret, prm, max_sst_size, job_range, projections,
+                                operator, input_version, run_start, stream, flt, resume)
+
+    def filter_stats(self):
+        """sdb_filter_stats of the last job (zeros after a job without a filter and without a cursor)."""
+        fs = _abi.FilterStats()
+        st = lib().sdb_compactor_filter_stats(self.h, C.byref(fs))
+        if st:
+            raise SdbError(st, "sdb_compactor_filter_stats")
+        return fs
 
     def range_stats(self):
         """sdb_range_job_stats of the last run_ssts_ranged job (zeros after any other)."""
@@ -1577,8 +1614,10 @@ class Compactor:
                          np.zeros(0, np.uint8), np.zeros(0, np.uint64), np.zeros(0, np.int64), np.zeros(0, np.int64),
                          np.zeros(0, np.uint8)), sm
         g = lambda p, k, dt: _d2h(p, k * np.dtype(dt).itemsize).view(dt)
-        return Batch(g(kb.key_bytes, sm.key_bytes, np.uint8), g(kb.key_off, n + 1, np.uint64),
-                     g(kb.val_bytes, sm.val_bytes, np.uint8), g(kb.val_off, n + 1, np.uint64), g(kb.kind, n, np.uint8),
+        ko, vo = g(kb.key_off, n + 1, np.uint64), g(kb.val_off, n + 1, np.uint64)
+        # the arenas end at the last offsets (the summary's byte counts stay retention's under a filter or a cursor)
+        return Batch(g(kb.key_bytes, int(ko[n]), np.uint8), ko,
+                     g(kb.val_bytes, int(vo[n]), np.uint8), vo, g(kb.kind, n, np.uint8),
                      g(kb.seq, n, np.uint64), g(kb.create_ts, n, np.int64), g(kb.expire_ts, n, np.int64),
                      g(kb.ts_mask, n, np.uint8)), sm
 
